@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""bench.py — headline benchmark: HNSW build throughput (vectors indexed / s) + recall@10.
+"""bench.py — headline benchmark: HNSW build throughput (vectors indexed / s); recall@10 with --full.
 
 Workload (BASELINE.json configs[1], "C2"): 1M x 768 f32 Cosine, M=16 (M0=32), ef_construction=100,
 vectors resident in HBM before the timed region.  One "step" = one complete build of the index
@@ -16,10 +16,14 @@ N > 1 runs the item-sharded multi-GPU build, one rank per GPU ov
     i.e. what a Rust Writer::build would call.
 `--backend gloo` is the test mode: ranks may share one GPU, the exchange is staged through the host.
 
-Prints ONE JSON line on rank 0 (see the contract in the task statement) carrying `roofline`
-(dominant kernel = k_walk, HIP events on the build stream) and `cpu_baseline` (the CPU oracle, i.e.
-a port of the reference algorithm — the real hannoy crate cannot be built here: no Rust, no LMDB).
-`--alt-data overlap` measures a second distribution in the same run (three more builds; off by default).
+Prints ONE JSON line on rank 0 carrying `roofline` (dominant kernel = k_walk, HIP events on the build
+stream).  A plain run sets up, warms up, times the K steps and prints that line; nothing else.
+`--full` adds everything beyond the headline figure: recall@10 and search throughput, `cpu_baseline`
+(the CPU oracle, i.e. a port of the reference algorithm — the real hannoy crate cannot be built here: no
+Rust, no LMDB) and, for the headline C2 workload, a second distribution (`--alt-data`, default overlap).
+`--dump-outputs DIR` writes the graph the last timed step exported as DIR/<name>.npy (float64, a fixed
+seeded sample of its records when the whole graph would exceed 64 MB): inputs are seeded, so two builds
+of the project can be compared output for output.
 """
 import argparse
 import json
@@ -88,6 +92,11 @@ def parse():
     p.add_argument("--launch-timeout", type=float, default=3000.0,
                    help="self-launched ranks (--gpus N without torchrun) are stopped after this many seconds")
     p.add_argument("--out", default=None, help="also write the JSON line to this file")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not need: recall@10 and search throughput, the "
+                        "CPU baseline, the second distribution (--alt-data); --no-cpu / --no-recall still apply")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write the records the last timed step exported as DIR/<name>.npy (float64, at most 64 MB)")
     p.add_argument("--sort-by-cluster", action="store_true",
                    help="experiment: clustered data with ids in cluster order (neighbours in the graph then have "
                         "neighbouring ids: what a locality-ordered id space would give the visited bitsets)")
@@ -253,12 +262,53 @@ def recall_at_k(found, counts, truth):
     return hit / truth.size
 
 
+DUMP_BYTES = 64 << 20  # --dump-outputs: total size of the .npy payloads
+DUMP_SAMPLE = 1 << 16  # records in the sample when the whole graph does not fit
+DUMP_SEED = 0
+
+
+def dump_outputs(path, g, M0):
+    """The records a caller of the timed build receives (hny_graph: records (item, layer) with their neighbour
+    lists, entry points, top level) as float64 .npy files under `path`.  Whole when they fit DUMP_BYTES; else
+    DUMP_SAMPLE records drawn by a seeded generator (the same indices for the same record count), each list
+    padded with -1 to max(M0, longest list), plus every record's list length where that fits."""
+    os.makedirs(path, exist_ok=True)
+    offsets = g.offsets.astype(np.int64)
+    nrec, nlinks = len(offsets) - 1, int(offsets[-1])
+    out = {"graph_entry_points": g.entry_points, "graph_max_level": np.array([g.max_level]),
+           "graph_counts": np.array([nrec, nlinks])}
+    if 8 * (3 * nrec + 1 + nlinks + len(g.entry_points) + 3) <= DUMP_BYTES:
+        out.update(graph_rec_item=g.rec_item, graph_rec_layer=g.rec_layer, graph_offsets=offsets,
+                   graph_nbrs=g.nbrs)
+    else:
+        deg = np.diff(offsets)
+        width = max(M0, int(deg.max()), 1)
+        s = min(nrec, DUMP_SAMPLE, (DUMP_BYTES - (1 << 20)) // (8 * (width + 3)))
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(nrec, s, replace=False))
+        lists = np.full((s, width), -1.0)
+        nbrs = g.nbrs
+        for j, r in enumerate(idx):
+            lists[j, :deg[r]] = nbrs[offsets[r]:offsets[r + 1]]
+        out.update(graph_sample_records=idx, graph_sample_rec_item=g.rec_item[idx],
+                   graph_sample_rec_layer=g.rec_layer[idx], graph_sample_nbrs=lists)
+        if 8 * (nrec + s * (width + 3)) + (1 << 20) <= DUMP_BYTES:  # every list's length, where it fits
+            out["graph_degree"] = deg
+    total = 0
+    for name, arr in out.items():
+        arr = np.asarray(arr, dtype=np.float64)
+        total += arr.nbytes
+        np.save(os.path.join(path, name + ".npy"), arr)
+    assert total <= DUMP_BYTES, total
+
+
 def main():
     global SORT_BY_CLUSTER
     a = parse()
     SORT_BY_CLUSTER = a.sort_by_cluster
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if not a.full and (a.alt_data not in (None, "none") or a.cpu_full):
+        raise SystemExit("--alt-data / --cpu-full are measured by a --full run only")
     if a.gpus > 1 and not a.native and "RANK" not in os.environ:
         return self_launch(a)  # before anything touches a GPU
     rank = int(os.environ.get("RANK", "0"))
@@ -306,7 +356,7 @@ def main():
 
     # ---- synthetic data (+ held-out queries from the same distribution) ----
     x_dev = gen_data(torch, a.n, a.dim, a.data, a.seed, dev)
-    q_dev = gen_data(torch, a.queries, a.dim, a.data, a.seed, dev, queries=True) if a.queries else None
+    q_dev = gen_data(torch, a.queries, a.dim, a.data, a.seed, dev, queries=True) if a.queries and a.full else None
     x = x_dev.cpu().numpy()
     items = H.ItemSet.from_f32(metric, x)
     row_bytes = items.codes.shape[1]
@@ -493,6 +543,8 @@ def main():
 
     H.set_graph_cache(int(a.graph_cache_gb * (1 << 30)))
     builder, driver, graph, dt = timed_builds(items, a.steps, a.warmup)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, graph, M0)
     value = a.n * a.steps / dt if a.steps else 0.0
     roof = roofline_of(graph, dt, a.steps, a.data)
     roof_issue = roofline_issue_of(graph, a.data)
@@ -543,7 +595,7 @@ def main():
     if a.gpus > 1 and a.backend == "gloo" and not a.native:
         out["note_backend"] = "gloo test mode: ranks may share a GPU and exchange through the host — not a scaling measurement"
 
-    if rank == 0 and not a.no_recall and a.queries:
+    if a.full and rank == 0 and not a.no_recall and a.queries:
         truth = brute_force_topk(torch, a.metric, x_dev, q_dev, 10)
         qc, qh = H.encode_vectors(metric, q_dev.cpu().numpy())
         t1 = time.perf_counter()
@@ -562,7 +614,7 @@ def main():
         out["search"]["qps_batch_32768_incl_transfers"] = round(nqs / (time.perf_counter() - t1), 1)
 
     # ---- CPU baseline (rank 0, N=1 only): the oracle = port of the reference algorithm ----
-    if rank == 0 and a.gpus == 1 and not a.no_cpu:
+    if a.full and rank == 0 and a.gpus == 1 and not a.no_cpu:
         from oracle import orc
 
         def draw_levels(n_, M_, seed_):  # the levels hny_build itself would draw (rand 0.8.5 StdRng, hnsw.rs:113-119)
@@ -657,7 +709,7 @@ def main():
     # friendly case for the memory system; `overlap` (overlapping clusters on a 32-d manifold) is what
     # embedding collections look like.  value_alt / roofline_alt / recall_at_10_alt, same parameters.
     alt = a.alt_data or ("overlap" if default_c2 else "none")
-    if a.gpus == 1 and not a.native and alt != "none" and alt != a.data:
+    if a.full and a.gpus == 1 and not a.native and alt != "none" and alt != a.data:
         builder.close()
         del x_dev, x, items
         xa_dev = gen_data(torch, a.n, a.dim, alt, a.seed, dev)

@@ -4,7 +4,7 @@
 export TMPDIR=/tmp
 out=gpurun_out/r4_final
 rm -rf $out && mkdir -p $out
-run() { name=$1; shift; timeout -k 10 600 python bench.py "$@" --out $out/$name.json > $out/$name.log 2>&1; echo "$name rc=$?"; }
+run() { name=$1; shift; timeout -k 10 600 python bench.py --full "$@" --out $out/$name.json > $out/$name.log 2>&1; echo "$name rc=$?"; }
 run c2_bench_default_run
 run c2_bench_overlap_data --steps 3 --warmup 1 --no-cpu --data overlap --alt-data none
 run c3_1Mx768_euclidean_M32_ef200_bench --steps 3 --warmup 1 --no-cpu --metric euclidean --M 32 --ef 200

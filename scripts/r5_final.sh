@@ -5,7 +5,7 @@
 export TMPDIR=/tmp
 out=gpurun_out/r5_final
 rm -rf $out && mkdir -p $out
-run() { name=$1; shift; timeout -k 10 900 python bench.py "$@" --out $out/$name.json > $out/$name.log 2>&1; echo "$name rc=$?"; }
+run() { name=$1; shift; timeout -k 10 900 python bench.py --full "$@" --out $out/$name.json > $out/$name.log 2>&1; echo "$name rc=$?"; }
 case "${1:-all}" in
 all|c2)
 run r05_c2_bench_default_run ;;&

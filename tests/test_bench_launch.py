@@ -98,3 +98,92 @@ def test_gpus_2_self_launched_ranks_build_over_gloo_on_one_gpu():
     assert r.returncode == 0, r.stderr[-2000:]
     j = _json_line(r.stdout)
     assert j["ranks_seen"] == 2 and j["launcher"] == "self" and j["replicas_identical"] is True and j["n_collectives"] > 0
+
+
+# ---- --full / --dump-outputs ----
+def test_extras_without_full_are_refused():
+    """a plain run measures the headline figure only: asking it for a --full measurement fails instead of
+    silently leaving it out"""
+    for extra in (["--alt-data", "overlap"], ["--cpu-full"]):
+        r = subprocess.run([sys.executable, BENCH, "--rendezvous-only"] + extra, capture_output=True, text=True,
+                           env=_clean_env(), timeout=300)
+        assert r.returncode != 0 and "--full" in r.stderr
+
+
+def _fake_graph(nrec, M0, seed=1):
+    import types
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    deg = rng.integers(0, M0 + 1, nrec)
+    offsets = np.concatenate([[0], np.cumsum(deg)]).astype(np.uint64)
+    return types.SimpleNamespace(offsets=offsets, nbrs=rng.integers(0, nrec, int(offsets[-1])).astype(np.uint32),
+                                 rec_item=rng.permutation(nrec).astype(np.uint32),
+                                 rec_layer=rng.integers(0, 3, nrec).astype(np.uint8),
+                                 entry_points=np.array([5, 7], np.uint32), max_level=2)
+
+
+def _load_dir(d):
+    import numpy as np
+    return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+
+
+@pytest.mark.parametrize("nrec,M0", [(3000, 32), (1_100_000, 32), (200_000, 1024)])
+def test_dump_outputs_is_bounded_exact_and_fixed(tmp_path, nrec, M0):
+    """whole graph when it fits 64 MB, else a seeded sample of records whose lists are exact; float64 only"""
+    import numpy as np
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import bench
+    g = _fake_graph(nrec, M0)
+    bench.dump_outputs(str(tmp_path / "a"), g, M0)
+    bench.dump_outputs(str(tmp_path / "b"), g, M0)
+    a, b = _load_dir(tmp_path / "a"), _load_dir(tmp_path / "b")
+    assert a.keys() == b.keys() and all(np.array_equal(a[k], b[k]) for k in a)
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64 << 20
+    off = g.offsets.astype(np.int64)
+    assert a["graph_counts"].tolist() == [nrec, off[-1]] and a["graph_entry_points"].tolist() == [5, 7]
+    if "graph_nbrs" in a:
+        assert np.array_equal(a["graph_nbrs"], g.nbrs) and np.array_equal(a["graph_offsets"], off)
+        assert np.array_equal(a["graph_rec_item"], g.rec_item)
+    else:
+        idx = a["graph_sample_records"].astype(np.int64)
+        assert len(idx) > 1000 and np.all(np.diff(idx) > 0)
+        assert np.array_equal(a["graph_sample_rec_item"], g.rec_item[idx])
+        for j in range(0, len(idx), 997):
+            r = idx[j]
+            lst = a["graph_sample_nbrs"][j]
+            n = off[r + 1] - off[r]
+            assert np.array_equal(lst[:n], g.nbrs[off[r]:off[r + 1]]) and np.all(lst[n:] == -1)
+
+
+@pytest.mark.gpu
+def test_plain_run_times_k_steps_and_dumps_the_same_graph_twice(tmp_path):
+    """`--steps K` timed steps and `ms_per_step`; no --full measurement in a plain line; two runs with the same
+    arguments export the same graph"""
+    import numpy as np
+    args = ["--items", "30000", "--dim", "64", "--steps", "2", "--warmup", "1"]
+    lines = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, BENCH] + args + ["--dump-outputs", str(tmp_path / d)], capture_output=True,
+                           text=True, env=_clean_env(), timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(_json_line(r.stdout))
+    j = lines[0]
+    assert j["steps"] == 2 and j["ms_per_step"] > 0 and j["value"] > 0 and j["unit"] == "vectors/s"
+    assert abs(j["value"] - 30000 / (j["ms_per_step"] / 1e3)) <= 0.01 * j["value"]
+    assert not {"recall_at_10", "search", "cpu_baseline", "value_alt"} & set(j)
+    a, b = _load_dir(tmp_path / "a"), _load_dir(tmp_path / "b")
+    assert "graph_nbrs" in a and a.keys() == b.keys() and all(np.array_equal(a[k], b[k]) for k in a)
+    assert a["graph_counts"][0] >= 30000 and a["graph_counts"][1] == len(a["graph_nbrs"])
+
+
+@pytest.mark.gpu
+def test_full_run_adds_recall_and_cpu_baseline():
+    r = subprocess.run([sys.executable, BENCH, "--items", "30000", "--dim", "64", "--steps", "1", "--warmup", "0",
+                        "--queries", "200", "--cpu-sample", "5000", "--full"], capture_output=True, text=True,
+                       env=_clean_env(), timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = _json_line(r.stdout)
+    assert 0.5 < j["recall_at_10"] <= 1.0 and j["search"]["queries"] == 200
+    assert j["cpu_baseline"]["value"] > 0 and j["recall_parity_on_sample"]["n"] == 5000

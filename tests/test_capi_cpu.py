@@ -129,9 +129,14 @@ def test_argument_validation(hny):
     with pytest.raises(hny.HannoyError) as e:
         hny.build(items, M=16, M0=2048)  # beyond HNY_BIG_CAP = 1024
     assert e.value.code == -5
-    with pytest.raises(hny.HannoyError) as e:
-        hny.build(items, M=16, M0=128, x86_order=True)  # accepted since round 4 (strict mode, lists beyond 64 slots):
-    assert e.value.code == -6                            # passes validation and stops at "no HIP device" here
+    import torch
+    if torch.cuda.is_available():  # accepted since round 4 (strict mode, lists beyond 64 slots): builds
+        g = hny.build(items, M=16, M0=128, x86_order=True)
+        assert sorted(set(g.rec_item.tolist())) == [0, 1, 2, 3]
+    else:
+        with pytest.raises(hny.HannoyError) as e:
+            hny.build(items, M=16, M0=128, x86_order=True)  # passes validation and stops at "no HIP device"
+        assert e.value.code == -6
     bad = hny.ItemSet(hny.EUCLIDEAN, 16, items.ids, items.codes, items.headers)  # stride < 16*4
     with pytest.raises(hny.HannoyError) as e:
         hny.build(bad)
