@@ -2158,11 +2158,24 @@ struct SearchCancel {
   }
 };
 
+// drain_asc().take(k) (reader.rs:797-798): the first min(k, n_found) entries of a top-k row (dist bits << 32 |
+// slot) as the caller's ids and distances; returns the count
+static uint32_t copy_topk_row(const hny_builder *b, const u64 *row, uint32_t n_found, uint32_t k, uint32_t *ids,
+                              float *dists) {
+  const uint32_t c = std::min<uint32_t>(k, n_found);
+  for (uint32_t j = 0; j < c; j++) {
+    ids[j] = b->ids[(uint32_t)(row[j] & 0xFFFFFFFFull)];
+    const uint32_t db = (uint32_t)(row[j] >> 32);
+    memcpy(&dists[j], &db, 4);
+  }
+  return c;
+}
+
 static int search_knn_impl(hny_builder *b, uint64_t nq, const void *qvectors, size_t qstride,
                            const void *qheaders, uint32_t k, uint32_t ef_search, uint32_t *out_ids,
                            float *out_dists, uint32_t *out_counts, const hny_query_opts *qo);
-// the QueryBuilder searcher with its search queue as a real heap in HBM (k_nns_filtered); force_heap: also
-// for queries without a candidates filter — where search_knn_impl sends the queries whose tie pool overflowed
+// the QueryBuilder searcher with its search queue as a real heap in HBM (k_nns); force_heap: also for queries
+// without a candidates filter — where search_knn_impl sends the queries whose tie pool overflowed
 static int nns_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const void *qvectors, size_t qstride,
                     const void *qheaders, const uint32_t *query_items, uint32_t *out_ids, float *out_dists,
                     uint32_t *out_counts, bool force_heap);
@@ -2300,7 +2313,7 @@ static int search_knn_impl(hny_builder *b, uint64_t nq, const void *qvectors, si
     HIP_TRY(hipMemcpyAsync(hn.data(), dcn.p, (size_t)cnt * 4, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(sc.wait(b));
     std::vector<uint32_t> again; // queries whose tie pool overflowed (short codes, large ef_search: ties everywhere)
-    for (uint32_t i = 0; i < cnt; i++) { // drain_asc().take(k), reader.rs:797-798
+    for (uint32_t i = 0; i < cnt; i++) {
       if (sc.d && hn[i] == 0xFFFFFFFFu) { // the batch was cancelled before this query finished
         out_counts[q0 + i] = 0u;
         continue;
@@ -2309,70 +2322,12 @@ static int search_knn_impl(hny_builder *b, uint64_t nq, const void *qvectors, si
         again.push_back(i);
         continue;
       }
-      uint32_t c = std::min<uint32_t>(k, hn[i]);
-      for (uint32_t j = 0; j < c; j++) {
-        u64 e = hc[(size_t)i * k + j];
-        out_ids[(q0 + i) * k + j] = b->ids[(uint32_t)(e & 0xFFFFFFFFull)];
-        uint32_t db = (uint32_t)(e >> 32);
-        memcpy(&out_dists[(q0 + i) * k + j], &db, 4);
-      }
-      out_counts[q0 + i] = c;
+      out_counts[q0 + i] =
+          copy_topk_row(b, &hc[(size_t)i * k], hn[i], k, &out_ids[(q0 + i) * k], &out_dists[(q0 + i) * k]);
     }
-    if (!again.empty() && !sc.cancelled && ef + 1 > HNY_RES_LDS_MAX) {
-      // result sets beyond the LDS: the same queries once more with `candidates` AND `res` as heaps in HBM
-      // (k_walk_heap in reader mode: the build's own safety net), on the chunk's buffers
-      const u32 na = (u32)again.size();
-      DevBuf<u32> dlist; // [0] = count, [1] = work counter, then the members
-      DevBuf<u64> dheap_r;
-      HIP_TRY(dlist.alloc((size_t)na + 2));
-      std::vector<u32> hl((size_t)na + 2);
-      hl[0] = na;
-      hl[1] = 0u;
-      std::copy(again.begin(), again.end(), hl.begin() + 2);
-      HIP_TRY(hipMemcpyAsync(dlist.p, hl.data(), hl.size() * 4, hipMemcpyHostToDevice, b->stream));
-      const u32 hgrid = (u32)std::max<uint64_t>(
-          1, std::min<uint64_t>(std::min<u32>(na, b->heap_grid), ((uint64_t)1 << 30) / (((uint64_t)rcap + 1) * 8)));
-      HIP_TRY(dheap_r.alloc((size_t)hgrid * ((size_t)rcap + 1)));
-      WalkArgs h = w;
-      h.first = 1;
-      h.eps_in = nullptr;
-      h.perm = nullptr;
-      h.xcd_tile = 0;
-      h.descend_only = 0;
-      h.pool_flag = 0;
-      h.pool_retry = dlist.p + 2;
-      h.n_pool_retry = dlist.p;
-      h.queue = dlist.p + 1;
-      h.heap_c = b->heap_c_ptr;
-      h.heap_c_cap = b->heap_c_cap;
-      h.heap_r = dheap_r.p;
-      h.heap_r_cap = rcap + 1;
-      if (sc.d) { // "never finished" for the members a cancellation leaves out
-        for (u32 i : again) hn[i] = 0xFFFFFFFFu;
-        HIP_TRY(hipMemcpyAsync(dcn.p, hn.data(), (size_t)cnt * 4, hipMemcpyHostToDevice, b->stream));
-      }
-      b->n_walk_dispatch++;
-      HIP_TRY(hnyk_walk_heap(b->g, h, b->shape, (int)hgrid, b->stream));
-      HIP_TRY(hnyk_take_topk(dcand.p, dcn.p, rcap, k, cnt, dtop.p, b->stream));
-      HIP_TRY(hipMemcpyAsync(hc.data(), dtop.p, (size_t)cnt * k * 8, hipMemcpyDeviceToHost, b->stream));
-      HIP_TRY(hipMemcpyAsync(hn.data(), dcn.p, (size_t)cnt * 4, hipMemcpyDeviceToHost, b->stream));
-      HIP_TRY(sc.wait(b));
-      for (uint32_t i : again) {
-        if (hn[i] >= 0xFFFFFFFEu) { // cancelled before it ran (or failed: the error words say so below)
-          out_counts[q0 + i] = 0u;
-          continue;
-        }
-        const uint32_t c = std::min<uint32_t>(k, hn[i]);
-        for (uint32_t j = 0; j < c; j++) {
-          const u64 e = hc[(size_t)i * k + j];
-          out_ids[(q0 + i) * k + j] = b->ids[(uint32_t)(e & 0xFFFFFFFFull)];
-          const uint32_t db = (uint32_t)(e >> 32);
-          memcpy(&out_dists[(q0 + i) * k + j], &db, 4);
-        }
-        out_counts[q0 + i] = c;
-      }
-    } else if (!again.empty() && !sc.cancelled) {
-      // the same queries on the searcher whose queue is a real heap in HBM: nothing to overflow, same results
+    if (!again.empty() && !sc.cancelled) {
+      // the same queries on the searcher whose queue is a real heap in HBM (and `res` too, when ef + 1 >
+      // HNY_RES_LDS_MAX): nothing to overflow, same results
       const size_t na = again.size();
       std::vector<unsigned char> av(na * vb), ah(na * hb);
       std::vector<uint32_t> ai(na * k), ac(na);
@@ -2439,8 +2394,8 @@ static int nns_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const
   const uint32_t k = qo->k, ef = std::max(qo->ef_search, k); // reader.rs:746, 837
   if ((uint64_t)ef + 1 > HNY_RES_GLOBAL_MAX)
     return fail(HNY_ERR_UNSUPPORTED, "ef_search %u: result sets hold at most %u entries", ef, HNY_RES_GLOBAL_MAX - 1);
-  // k_nns_filtered keeps its result set in LDS (up to 4 096 entries); beyond that the same search runs with
-  // `res` as a heap in HBM next to the search queue's (k_nns_heap)
+  // k_nns keeps its result set in LDS (up to 4 096 entries); beyond that the same search runs with `res` as a
+  // heap in HBM next to the search queue's
   // ... and so does a search that starts from more entry points than the LDS set holds (every entry point is pushed
   // to `res` without a capacity check, reader.rs:755-761: an all-level-0 index of 4 096 - 8 192 items)
   const uint64_t eps_need = std::max<uint64_t>(b->entry_points.size(), b->entry_points.size() > 1 ? b->top_layer_nodes : 0) + 1;
@@ -2618,11 +2573,11 @@ static int nns_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const
       a.heap_cap = heap_big_c;
       a.heap_r = dheap_r.p;
       a.heap_r_cap = rcap + 1;
-      HIP_TRY(hnyk_nns_heap(b->g, a, b->shape, (int)std::min<uint32_t>(n_mem, grid_big), b->stream));
+      HIP_TRY(hnyk_nns(b->g, a, b->shape, (int)std::min<uint32_t>(n_mem, grid_big), b->stream));
     } else {
       a.heap = dheap.p;
       a.heap_cap = heap_small;
-      HIP_TRY(hnyk_nns_filtered(b->g, a, b->shape, (int)std::min<uint32_t>(n_mem, grid_small), b->stream));
+      HIP_TRY(hnyk_nns(b->g, a, b->shape, (int)std::min<uint32_t>(n_mem, grid_small), b->stream));
       HIP_TRY(hipMemcpyAsync(hst.data(), dstatus.p, (size_t)cnt * 4, hipMemcpyDeviceToHost, b->stream));
       HIP_TRY(sc.wait(b));
       uint32_t n_retry = 0;
@@ -2638,7 +2593,7 @@ static int nns_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const
         a.heap = dheap_full.p;
         a.heap_cap = heap_full;
         a.queue = queues + 1;
-        HIP_TRY(hnyk_nns_filtered(b->g, a, b->shape, (int)std::min<uint32_t>(n_retry, grid_full), b->stream));
+        HIP_TRY(hnyk_nns(b->g, a, b->shape, (int)std::min<uint32_t>(n_retry, grid_full), b->stream));
       } else if (n_retry) {
         return fail(HNY_ERR_DEVICE, "search queue overflow");
       }
@@ -2655,14 +2610,8 @@ static int nns_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const
         continue;
       }
       if (hst[i]) return fail(HNY_ERR_DEVICE, "search queue overflow");
-      uint32_t c = std::min<uint32_t>(k, hn[i]);
-      for (uint32_t j = 0; j < c; j++) {
-        u64 e = hc[(size_t)i * k + j];
-        out_ids[(q0 + i) * k + j] = b->ids[(uint32_t)(e & 0xFFFFFFFFull)];
-        uint32_t db = (uint32_t)(e >> 32);
-        memcpy(&out_dists[(q0 + i) * k + j], &db, 4);
-      }
-      out_counts[q0 + i] = c;
+      out_counts[q0 + i] =
+          copy_topk_row(b, &hc[(size_t)i * k], hn[i], k, &out_ids[(q0 + i) * k], &out_dists[(q0 + i) * k]);
     }
   }
   if (sc.cancelled && qo->did_cancel) *qo->did_cancel = 1;

@@ -2075,7 +2075,7 @@ __global__ __launch_bounds__(64, (NCH == 1 && SP >= 4 && !RM && (RC == 1 || RC =
     }
     if constexpr (RM || SP == 0) {
       // a search whose tie pool overflowed: flagged instead of counted, the host repeats the query on the
-      // heap-queue searcher (k_nns_filtered without a filter), which has no pool
+      // heap-queue searcher (k_nns without a filter), which has no pool
       // (force_pool: tests send every k-th query that way)
       if (reader_mode && ak->pool_flag && (s.pool_over || (ak->force_pool && m % ak->force_pool == 0u))) {
         total = (int)0xFFFFFFFEu;
@@ -2205,6 +2205,59 @@ __device__ __forceinline__ bool in_filter(const u32 *filter, u32 excl, u32 id) {
   return !filter || ((filter[id >> 5] >> (id & 31u)) & 1u);
 }
 
+// the next query of a work-queue loop (queue index -> members[i], or i without a list), HNY_SENT when none is
+// left; the Visitor's cancel probe (reader.rs:333) runs between queries: a cancelled batch starts no more
+__device__ __forceinline__ u32 next_member(u32 *queue, const u32 *cancel, u32 n_members, const u32 *members) {
+  u32 mi = 0;
+  if (threadIdx.x == 0) {
+    mi = atomicAdd(queue, 1u);
+    if (cancel && __hip_atomic_load(cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) mi = 0xFFFFFFFFu;
+  }
+  mi = uni(mi);
+  if (mi >= n_members) return HNY_SENT;
+  return members ? uni(members[mi]) : mi;
+}
+
+// query m's row and norm: by_item the stored vector of slot q_slots[m] (reader.rs:826-828, also returned in
+// `item`), else the caller's row m (`item` = HNY_SENT)
+__device__ __forceinline__ const unsigned char *query_row(const GraphDev &g, const NnsArgs &a, u32 m, float &qn,
+                                                          u32 &item) {
+  qn = 0.f;
+  item = HNY_SENT;
+  if (a.by_item) {
+    item = uni(a.q_slots[m]);
+    if (g.norms) qn = g.norms[item];
+    return g.rows + (size_t)item * g.row_stride;
+  }
+  if (a.q_norms) qn = a.q_norms[m];
+  return a.q_rows + (size_t)m * a.q_stride;
+}
+
+// the exhaustive fallback's scan (reader.rs:771-795 / 864-890): the first slot >= pos that is not on `path`
+// (the flushed visited bitset, 64 words at a time), or g.n when there is none
+__device__ __forceinline__ u32 next_unvisited(const GraphDev &g, u32 *bits, u32 pos) {
+  const int ln = threadIdx.x;
+  const u32 nwords = (g.n + 31) >> 5;
+  while (pos < g.n) {
+    const u32 wbase = pos >> 5;
+    const u32 widx = wbase + (u32)ln;
+    u32 unv = 0u;
+    if (widx < nwords) {
+      unv = ~__hip_atomic_load(&bits[widx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (ln == 0 && (pos & 31u)) unv &= ~((1u << (pos & 31u)) - 1u);
+      if (widx == nwords - 1 && (g.n & 31u)) unv &= (1u << (g.n & 31u)) - 1u;
+    }
+    const u64 mk = ballot(unv != 0u);
+    if (mk) {
+      const int l0 = __ffsll((long long)mk) - 1;
+      const u32 w0 = (u32)__builtin_amdgcn_readlane((int)unv, l0);
+      return ((wbase + (u32)l0) << 5) + (u32)__builtin_ctz(w0);
+    }
+    pos = (wbase + 64u) << 5;
+  }
+  return g.n;
+}
+
 // Visitor::visit at level 0 with `candidates` (reader.rs:301-369).  Returns 0, or 1 when the heap
 // is too small (the caller reports it and the host runs the query again with a larger one).
 template <int LPR, int NCH>
@@ -2284,182 +2337,33 @@ __device__ int visit_filtered(const GraphDev &g, const float4 (&q)[NCH], float q
   return 0;
 }
 
-template <int LPR, int NCH>
-__global__ __launch_bounds__(64, 4) void k_nns_filtered(GraphDev g, NnsArgs a) {
-  extern __shared__ __align__(16) unsigned char smem[];
-  u64 *res = reinterpret_cast<u64 *>(smem);
-  u64 *pool = res + a.rcap;
-  u32 *nb_ids = reinterpret_cast<u32 *>(pool + HNY_POOL_CAP);
-  float *nb_d = reinterpret_cast<float *>(nb_ids + 64);
-  u32 *eps = reinterpret_cast<u32 *>(nb_d + 64);
-  const int ln = threadIdx.x, t = ln % LPR;
 
-  Beam s; // greedy descent through the upper layers: the ordinary (unfiltered) walk
-#ifdef HNY_PHASE_CLOCKS
-  for (int i = 0; i < 12; i++) s.ph[i] = 0;
-  s.ph_t = 0;
-#endif
-  s.res = res;
-  s.pool = pool;
-  s.rcap = (int)a.rcap;
-  s.pool_over = 0;
-  s.err = 0;
-  s.res_len = 0;
-  s.pool_len = 0;
-  s.n_weird = 0;
-  s.tie_bits = 0;
-  s.dropped = false;
-  BeamR<1> rb_unused{{0ull}};
-  Visited vis;
-  visited_init(vis, a.bits + (size_t)blockIdx.x * a.bits_words, a.bits_words,
-               a.vlog + (size_t)blockIdx.x * a.log_cap, a.log_cap, eps + a.eps_cap, a.vis_slots);
-  QHeap Q;
-  Q.h = a.heap + (size_t)blockIdx.x * a.heap_cap;
-  Q.cap = a.heap_cap;
-  Q.size = 0;
-  Q.top = ~0ull;
-  u64 evals = 0;
-  u32 err_iter = 0, log_over_cnt = 0, res_err = 0;
-
-  for (;;) {
-    u32 mi = 0;
-    if (ln == 0) {
-      mi = atomicAdd(a.queue, 1u);
-      // the Visitor's cancel probe (reader.rs:333), between queries: a cancelled batch starts no more
-      if (a.cancel && __hip_atomic_load(a.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) mi = 0xFFFFFFFFu;
-    }
-    mi = uni(mi);
-    if (mi >= a.n_members) break;
-    const u32 m = a.members ? uni(a.members[mi]) : mi;
-    const unsigned char *qrow;
-    float qn = 0.f;
-    u32 excl = HNY_SENT;
-    if (a.by_item) { // :826-828 the stored vector is the query
-      excl = uni(a.q_slots[m]);
-      qrow = g.rows + (size_t)excl * g.row_stride;
-      if (g.norms) qn = g.norms[excl];
-    } else {
-      qrow = a.q_rows + (size_t)m * a.q_stride;
-      if (a.q_norms) qn = a.q_norms[m];
-    }
-    float4 q[NCH];
-    load_row<LPR, NCH>(qrow, t, g.n16, q);
-    int n_eps;
-    if (a.by_item) { // Visitor::new(vec![item], 0, ef, Some(&candidates)), :842
-      n_eps = 1;
-      if (ln == 0) eps[0] = excl;
-      WSYNC();
-    } else { // :728-743 greedy descent, no filter, `path` shared and cleared before level 0
-      n_eps = (int)a.n_entry_points;
-      for (int i = ln; i < n_eps; i += 64) eps[i] = a.entry_points[i];
-      WSYNC();
-      for (u32 layer = g.max_level; layer >= 1u; layer--) {
-        walk_one_layer<LPR, NCH, true>(g, q, qn, layer, 1, eps, n_eps, s, vis, nb_ids, nb_d, evals, err_iter, qrow, rb_unused);
-        const u32 closest = uni((u32)(s.res[0] >> 1) & 0x7FFFFFFFu);
-        WSYNC();
-        if (ln == 0) eps[0] = closest;
-        n_eps = 1;
-        if (layer == 1u) {
-          if (vis.log_over) log_over_cnt++;
-          visited_clear(vis);
-        }
-        WSYNC();
-      }
-    }
-    int res_len = 0;
-    int st = visit_filtered<LPR, NCH>(g, q, qn, (int)a.ef_main, eps, n_eps, res, res_len, (int)a.rcap, res_err,
-                                      vis, nb_ids, nb_d, Q, a.filter, excl, evals, err_iter, qrow);
-    int total = 0;
-    if (st == 0) {
-      for (int e = ln; e < res_len; e += 64) a.cand[(size_t)m * a.rcap + e] = res[e];
-      total = res_len;
-      if (total < (int)a.k) {
-        // exhaustive fallback (:771-795 / :864-890): restart from every item not on `path` yet
-        const u32 nwords = (g.n + 31) >> 5;
-        const int stop = a.by_item ? (int)a.k : (int)a.ef_opt;
-        u32 pos = 0;
-        visited_flush(vis);
-        while (pos < g.n) {
-          const u32 wbase = pos >> 5;
-          const u32 widx = wbase + (u32)ln;
-          u32 unv = 0u;
-          if (widx < nwords) {
-            unv = ~__hip_atomic_load(&vis.bits[widx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (ln == 0 && (pos & 31u)) unv &= ~((1u << (pos & 31u)) - 1u);
-            if (widx == nwords - 1 && (g.n & 31u)) unv &= (1u << (g.n & 31u)) - 1u;
-          }
-          const u64 mk = ballot(unv != 0u);
-          if (!mk) {
-            pos = (wbase + 64u) << 5;
-            continue;
-          }
-          const int l0 = __ffsll((long long)mk) - 1;
-          const u32 w0 = (u32)__builtin_amdgcn_readlane((int)unv, l0);
-          const u32 slot = ((wbase + (u32)l0) << 5) + (u32)__builtin_ctz(w0);
-          pos = slot + 1;
-          if (g.incremental && !g.has_vec[slot]) continue;
-          int ef2;
-          if (a.by_item) ef2 = (int)a.k - total;                                   // :878
-          else ef2 = (int)a.ef_opt > total ? (int)a.ef_opt - total : 0;           // :783
-          WSYNC();
-          if (ln == 0) eps[0] = slot;
-          WSYNC();
-          st = visit_filtered<LPR, NCH>(g, q, qn, ef2, eps, 1, res, res_len, (int)a.rcap, res_err, vis, nb_ids,
-                                        nb_d, Q, a.filter, excl, evals, err_iter, qrow);
-          if (st) break;
-          if (total + res_len > (int)a.rcap) {
-            res_err = 1;
-            break;
-          }
-          for (int e = ln; e < res_len; e += 64) a.cand[(size_t)m * a.rcap + total + e] = res[e];
-          total += res_len;
-          if (total >= stop) break;
-        }
-        if (st == 0 && !res_err) { // drain_asc()
-          __threadfence_block();
-          WSYNC();
-          for (int e = ln; e < total; e += 64) res[e] = a.cand[(size_t)m * a.rcap + e];
-          WSYNC();
-          for (int e = ln; e < total; e += 64) {
-            const u64 mine = res[e];
-            int rk = 0;
-            for (int k2 = 0; k2 < total; k2++) rk += res[k2] < mine ? 1 : 0;
-            a.cand[(size_t)m * a.rcap + rk] = mine;
-          }
-          WSYNC();
-        }
-      }
-    }
-    if (ln == 0) {
-      a.cand_n[m] = st ? 0u : (u32)total;
-      a.status[m] = st ? 1u : 0u;
-    }
-    if (vis.log_over) log_over_cnt++;
-    visited_clear(vis);
-  }
-  if (ln == 0) {
-    if (evals) atomicAdd(&g.stats[ST_EVALS_WALK], evals);
-    if (log_over_cnt) atomicAdd(&g.stats[ST_LOG_OVERFLOW], (u64)log_over_cnt);
-    if (s.err || res_err) atomicAdd(&g.stats[ST_ERR_RES_OVERFLOW], 1ull);
-    if (err_iter) atomicAdd(&g.stats[ST_ERR_ITER], 1ull);
+// res.into_vec(): the max-heap R (inverted keys), ascending, into row[0 .. R.size); R is left empty
+__device__ __forceinline__ void qheap_drain(QHeap &R, u64 *row) {
+  for (u32 i = R.size; i-- > 0u;) {
+    const u64 key = ~R.top;
+    if (threadIdx.x == 0) row[i] = key;
+    qheap_pop(R);
   }
 }
 
 // ---------------------------------------------------------------------------------------------
-// walk_layer with the reference's own data structures (hnsw.rs:460-518): `candidates` a real min-heap
-// (64-ary, HBM, keyed dist bits << 32 | ~slot: smallest distance first, larger id first among equals —
-// BinaryHeap<(Reverse<OrderedFloat>, ItemId)>), `res` a real max-heap (the same 64-ary heap on inverted
-// keys ~(dist bits << 32 | slot): MinMaxHeap::peek_max / push_pop_max), every accepted point pushed to
-// both, in list order, as the reference's loop does.  No beam array, no expanded bits, no tie pool: nothing
-// can overflow but the heaps' memory.  Slow (every heap step is a trip to HBM) and only used for the
-// members whose fast walk overflowed its 128-slot tie pool (k_walk_heap below) — inputs with a handful of
-// distinct distances and lists of hundreds of links.  Returns 0, or 1 when a heap is full.
+// walk_layer / Visitor::visit with the reference's own data structures (hnsw.rs:460-518, reader.rs:301-369):
+// `candidates` a real min-heap (64-ary, HBM, keyed dist bits << 32 | ~slot: smallest distance first, larger id
+// first among equals — BinaryHeap<(Reverse<OrderedFloat>, ItemId)>), `res` a real max-heap (the same 64-ary heap
+// on inverted keys ~(dist bits << 32 | slot): MinMaxHeap::peek_max / push_pop_max), every accepted point pushed
+// to both, in list order, as the reference's loop does.  No beam array, no expanded bits, no tie pool: nothing
+// can overflow but the heaps' memory.  Slow (every heap step is a trip to HBM): the build's walks whose tie pool
+// overflowed (k_walk_heap) and the searches whose result set is beyond the LDS (k_nns<.., true>).
+// filter / excl (searches: `candidates`, by_item's own slot): the queue takes every accepted point, `res` only
+// what the filter lets through (:322-324, :356-360), f_max = f32::MAX while `res` is empty (:337); builds pass
+// nullptr / HNY_SENT.  Returns 0, or 1 when a heap is full.
 // rmin: the smallest key res holds (peek_min for the greedy descent; only the max ever leaves res).
 // ---------------------------------------------------------------------------------------------
 template <int LPR, int NCH>
 __device__ int walk_layer_heap(const GraphDev &g, const float4 (&q)[NCH], float qn, u32 layer, int ef, const u32 *eps,
                                int n_eps, QHeap &C, QHeap &R, u64 &rmin, Visited &vis, u32 *nb_ids, float *nb_d,
-                               u64 &evals, const unsigned char *qrow) {
+                               const u32 *filter, u32 excl, u64 &evals, const unsigned char *qrow) {
   const int ln = threadIdx.x;
   C.size = 0;
   C.top = ~0ull;
@@ -2482,6 +2386,7 @@ __device__ int walk_layer_heap(const GraphDev &g, const float4 (&q)[NCH], float 
       const u32 db = uni(fbits(nb_d[r])), idr = uni(nb_ids[r]);
       const u64 key = ((u64)db << 32) | (u64)idr;
       if (!qheap_push(C, ((u64)db << 32) | (u64)(~idr))) return 1;
+      if (!in_filter(filter, excl, idr)) continue;
       if (!qheap_push(R, ~key)) return 1;
       rmin = key < rmin ? key : rmin;
     }
@@ -2489,8 +2394,8 @@ __device__ int walk_layer_heap(const GraphDev &g, const float4 (&q)[NCH], float 
   for (;;) {
     if (C.size == 0) break; // :483 candidates.peek()
     const u64 top = C.top;
-    const u32 dmax = (u32)((~R.top) >> 32); // res.peek_max(), captured once per pop (:484)
-    const float fmax = __uint_as_float(dmax);
+    // res.peek_max(), captured once per pop (:484)
+    const float fmax = R.size ? __uint_as_float((u32)((~R.top) >> 32)) : 3.4028235e38f;
     if (__uint_as_float((u32)(top >> 32)) > fmax) break; // raw f32 compare, :485
     qheap_pop(C);
     const u32 cslot = ~(u32)(top & 0xFFFFFFFFull);
@@ -2507,7 +2412,8 @@ __device__ int walk_layer_heap(const GraphDev &g, const float4 (&q)[NCH], float 
         if (!nmask) continue;
         visited_log(vis, id, isnew, nmask, __popcll(nmask & ((1ull << ln) - 1ull)));
         // the same id twice in one list (add_link never dedups, :521): the FIRST occurrence is the one the
-        // reference scores; which of the two lanes the atomic told "new" is arbitrary
+        // reference scores; which of the two lanes the atomic told "new" is arbitrary.  (The searches' lists
+        // are finalized, ascending and deduplicated: nothing to do there.)
         WSYNC();
         nb_ids[ln] = valid ? id : HNY_SENT;
         WSYNC();
@@ -2537,8 +2443,9 @@ __device__ int walk_layer_heap(const GraphDev &g, const float4 (&q)[NCH], float 
           if ((int)R.size < ef || __uint_as_float(db) < fmax) { // :505
             const u64 key = ((u64)db << 32) | (u64)idr;
             if (!qheap_push(C, ((u64)db << 32) | (u64)(~idr))) return 1;
-            if ((int)R.size == ef) { // push_pop_max: the new key, unless it is the greatest itself
-              if (key < ~R.top) {
+            if (!in_filter(filter, excl, idr)) continue;
+            if ((int)R.size == ef) { // push_pop_max: the new key, unless it is the greatest itself (or ef == 0)
+              if (R.size && key < ~R.top) {
                 qheap_pop(R);
                 if (!qheap_push(R, ~key)) return 1;
                 rmin = key < rmin ? key : rmin;
@@ -2556,8 +2463,7 @@ __device__ int walk_layer_heap(const GraphDev &g, const float4 (&q)[NCH], float 
 }
 
 // k_walk's member loop for the members of a.pool_retry, every walk_layer call on heaps: build walks whose
-// tie pool overflowed, and (a.reader_mode) the Reader's searches in the same situation whose result set is
-// too long for k_nns_filtered's LDS (ef_search >= 4 096: hny_builder_search_knn)
+// tie pool overflowed
 template <int LPR, int NCH>
 __global__ __launch_bounds__(64, 4) void k_walk_heap(GraphDev g, WalkArgs a) {
   extern __shared__ __align__(16) unsigned char smem[];
@@ -2578,26 +2484,12 @@ __global__ __launch_bounds__(64, 4) void k_walk_heap(GraphDev g, WalkArgs a) {
   u64 evals = 0;
   u32 err = 0, log_over_cnt = 0;
   for (;;) {
-    u32 mi = 0;
-    if (ln == 0) {
-      mi = atomicAdd(a.queue, 1u);
-      // the Visitor's cancel probe (reader.rs:333), between queries (searches only: builds pass no flag)
-      if (a.cancel && __hip_atomic_load(a.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) mi = 0xFFFFFFFFu;
-    }
-    mi = uni(mi);
-    if (mi >= n_mem) break;
-    const u32 m = uni(a.pool_retry[mi]);
+    const u32 m = next_member(a.queue, nullptr, n_mem, a.pool_retry);
+    if (m == HNY_SENT) break;
     const u64 evals_before = evals;
-    const unsigned char *qrow;
-    float qn = 0.f;
-    if (a.q_rows) { // a search: the query is not an item
-      qrow = a.q_rows + (size_t)m * a.q_stride;
-      if (a.q_norms) qn = a.q_norms[m];
-    } else {
-      const u32 qslot = a.q_slots[m];
-      qrow = g.rows + (size_t)qslot * g.row_stride;
-      if (g.norms) qn = g.norms[qslot];
-    }
+    const u32 qslot = a.q_slots[m];
+    const unsigned char *qrow = g.rows + (size_t)qslot * g.row_stride;
+    const float qn = g.norms ? g.norms[qslot] : 0.f;
     float4 q[NCH];
     load_row<LPR, NCH>(qrow, t, g.n16, q);
     int n_eps;
@@ -2623,19 +2515,15 @@ __global__ __launch_bounds__(64, 4) void k_walk_heap(GraphDev g, WalkArgs a) {
       const bool last = (layer == a.layer);
       if (last && a.descend_only) break;
       st = walk_layer_heap<LPR, NCH>(g, q, qn, layer, last ? (int)a.ef : 1, eps, n_eps, C, R, rmin, vis, nb_ids, nb_d,
-                                     evals, qrow);
+                                     nullptr, HNY_SENT, evals, qrow);
       if (st || last) break;
       const u32 closest = (u32)(rmin & 0xFFFFFFFFull); // :305-306 eps = [peek_min]
       WSYNC();
       if (ln == 0) eps[0] = closest;
       n_eps = 1;
       lkey = (lkey << 16) | (u64)((u32)g.upper_idx[closest] & 0xFFFFu);
-      // walk_layer owns a fresh visited set; Reader::hnsw_search shares `path` across the greedy layers and
-      // clears it once before layer 0 (reader.rs:731-743)
-      if (!a.reader_mode || layer == a.layer + 1) {
-        if (vis.log_over) log_over_cnt++;
-        visited_clear(vis);
-      }
+      if (vis.log_over) log_over_cnt++; // walk_layer owns a fresh visited set
+      visited_clear(vis);
       WSYNC();
     }
     if (!st && a.descend_only) {
@@ -2644,73 +2532,12 @@ __global__ __launch_bounds__(64, 4) void k_walk_heap(GraphDev g, WalkArgs a) {
         a.key_out[m - a.key_base] = lkey & 0xFFFFFFFFFFFFull;
       }
     } else if (!st) {
-      // res.into_vec(), ascending: pop the maxima into the row from its end
-      u32 total = R.size;
-      u64 *row = a.cand + (size_t)m * a.rcap;
-      auto drain = [&](u32 at) { // R, ascending, into row[at ..)
-        for (u32 i = R.size; i-- > 0u;) {
-          const u64 key = ~R.top;
-          if (ln == 0) row[at + i] = key;
-          qheap_pop(R);
-        }
-      };
+      const u32 total = R.size;
       if (total > a.rcap) {
         st = 1;
       } else {
-        drain(0u);
-        if (a.reader_mode && total < a.knn_k) {
-          // Reader::hnsw_search's exhaustive fallback (reader.rs:771-795), as in k_walk: restart from every
-          // item not seen yet, ascending, sharing the visited set, until opt.ef hits are collected
-          const u32 nwords = (g.n + 31) >> 5;
-          u32 pos = 0;
-          visited_flush(vis);
-          while (pos < g.n && !st) {
-            const u32 wbase = pos >> 5;
-            const u32 widx = wbase + (u32)ln;
-            u32 unv = 0u;
-            if (widx < nwords) {
-              unv = ~__hip_atomic_load(&vis.bits[widx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              if (ln == 0 && (pos & 31u)) unv &= ~((1u << (pos & 31u)) - 1u);
-              if (widx == nwords - 1 && (g.n & 31u)) unv &= (1u << (g.n & 31u)) - 1u;
-            }
-            const u64 mk = ballot(unv != 0u);
-            if (!mk) {
-              pos = (wbase + 64u) << 5;
-              continue;
-            }
-            const int l0 = __ffsll((long long)mk) - 1;
-            const u32 w0 = (u32)__builtin_amdgcn_readlane((int)unv, l0);
-            const u32 slot = ((wbase + (u32)l0) << 5) + (u32)__builtin_ctz(w0);
-            pos = slot + 1;
-            if (g.incremental && !g.has_vec[slot]) continue;
-            const int ef2 = a.knn_ef > total ? (int)(a.knn_ef - total) : 0; // saturating_sub :786
-            WSYNC();
-            if (ln == 0) eps[0] = slot;
-            WSYNC();
-            st = walk_layer_heap<LPR, NCH>(g, q, qn, 0u, ef2, eps, 1, C, R, rmin, vis, nb_ids, nb_d, evals, qrow);
-            if (st) break;
-            if (total + R.size > a.rcap) {
-              st = 1;
-              break;
-            }
-            const u32 got = R.size;
-            drain(total); // neighbours.extend(more_nns)
-            total += got;
-            if (total >= a.knn_ef) break; // :792-794
-          }
-          if (!st) { // drain_asc(): everything that was collected, sorted — through the heap once more
-            __threadfence_block();
-            WSYNC();
-            R.size = 0;
-            R.top = ~0ull;
-            for (u32 i = 0; i < total && !st; i++) {
-              const u64 key = uni64(row[i]);
-              if (!qheap_push(R, ~key)) st = 1;
-            }
-            if (!st) drain(0u);
-          }
-        }
-        if (!st && ln == 0) a.cand_n[m] = total;
+        qheap_drain(R, a.cand + (size_t)m * a.rcap);
+        if (ln == 0) a.cand_n[m] = total;
       }
     }
     if (st) {
@@ -2733,130 +2560,60 @@ __global__ __launch_bounds__(64, 4) void k_walk_heap(GraphDev g, WalkArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Visitor::visit at level 0 (reader.rs:301-369) with the search queue AND `res` as heaps in HBM: result sets
-// beyond the LDS (max(ef_search, k) >= 4 096 with a candidates filter / by_item — k_nns_filtered keeps `res`
-// as a sorted LDS array).  The queue takes every accepted point, `res` only what the filter lets through
-// (:322-324, :356-360); f_max = f32::MAX while `res` is empty (:337).  Returns 0, or 1 when a heap is full.
+// Reader::nns on the graph (reader.rs:301-369, 728-798, 809-896): the queries of a candidates filter and/or
+// by_item, and the plain searches whose tie pool overflowed (no filter).  The search queue is a real heap in HBM
+// (NnsArgs.heap); RES_HEAP picks where `res` lives: the sorted LDS array (visit_filtered, up to HNY_RES_LDS_MAX
+// entries) or a max-heap in HBM next to the queue's (walk_layer_heap, NnsArgs.heap_r).  Each keeps its own greedy
+// descent: the ordinary walk's LDS beam, or walk_layer_heap.  Rows of a.cand hold up to rcap hits.
 // ---------------------------------------------------------------------------------------------
-template <int LPR, int NCH>
-__device__ int visit_heap(const GraphDev &g, const float4 (&q)[NCH], float qn, int ef, const u32 *eps, int n_eps,
-                          QHeap &C, QHeap &R, Visited &vis, u32 *nb_ids, float *nb_d, const u32 *filter, u32 excl,
-                          u64 &evals, const unsigned char *qrow) {
-  const int ln = threadIdx.x;
-  C.size = 0;
-  C.top = ~0ull;
-  R.size = 0;
-  R.top = ~0ull;
-  for (int e0 = 0; e0 < n_eps; e0 += 64) { // :316-325 every entry point is queued and visited
-    const int ne = n_eps - e0 < 64 ? n_eps - e0 : 64;
-    u32 id = ln < ne ? eps[e0 + ln] : 0u;
-    bool isnew = visited_insert(vis, id, ln < ne);
-    u64 nmask = ballot(isnew);
-    visited_log(vis, id, isnew, nmask, __popcll(nmask & ((1ull << ln) - 1ull)));
-    WSYNC();
-    if (ln < ne) nb_ids[ln] = id;
-    WSYNC();
-    dist_rows<LPR, NCH>(g, q, qn, nb_ids, ne, nb_d, qrow);
-    evals += (u64)ne;
-    WSYNC();
-    for (int r = 0; r < ne; r++) {
-      const u32 db = uni(fbits(nb_d[r])), idr = uni(nb_ids[r]);
-      if (!qheap_push(C, ((u64)db << 32) | (u64)(~idr))) return 1;
-      if (in_filter(filter, excl, idr) && !qheap_push(R, ~(((u64)db << 32) | (u64)idr))) return 1;
-    }
-  }
-  for (;;) {
-    if (C.size == 0) break;
-    const u64 top = C.top;
-    const float fmax = R.size ? __uint_as_float((u32)((~R.top) >> 32)) : 3.4028235e38f; // :337, once per pop
-    if (__uint_as_float((u32)(top >> 32)) > fmax) break;                                // raw f32 compare, :338
-    qheap_pop(C);
-    const u32 cslot = ~(u32)(top & 0xFFFFFFFFull);
-    for (int pass = g.incremental ? 0 : 1; pass < 2; pass++) {
-      u32 cap;
-      const u32 *nl = pass == 0 ? disk_ids(g, 0u, cslot, cap) : nbr_ids(g, 0u, cslot, cap);
-      if (!nl) continue;
-      for (u32 c0 = 0; c0 < cap; c0 += 64u) { // lists of more than 64 slots: 64 at a time, in order
-        u32 id = c0 + (u32)ln < cap ? nl[c0 + ln] : HNY_SENT;
-        bool valid = id != HNY_SENT;
-        bool isnew = visited_insert(vis, id, valid); // path.insert(point), :347
-        u64 nmask = ballot(isnew);
-        if (!nmask) continue;
-        visited_log(vis, id, isnew, nmask, __popcll(nmask & ((1ull << ln) - 1ull)));
-        if (g.incremental) {
-          isnew = isnew && g.has_vec[id] != 0;
-          nmask = ballot(isnew);
-          if (!nmask) continue;
-        }
-        const int n_new = __popcll(nmask);
-        const int rank = __popcll(nmask & ((1ull << ln) - 1ull));
-        WSYNC();
-        if (isnew) nb_ids[rank] = id;
-        WSYNC();
-        dist_rows<LPR, NCH>(g, q, qn, nb_ids, n_new, nb_d, qrow); // :350-353
-        evals += (u64)n_new;
-        WSYNC();
-        for (int r = 0; r < n_new; r++) { // ascending ids, like links.iter()
-          const u32 db = uni(fbits(nb_d[r])), idr = uni(nb_ids[r]);
-          if ((int)R.size < ef || __uint_as_float(db) < fmax) { // :357
-            if (!qheap_push(C, ((u64)db << 32) | (u64)(~idr))) return 1;
-            if (!in_filter(filter, excl, idr)) continue;
-            const u64 key = ((u64)db << 32) | (u64)idr;
-            if ((int)R.size == ef) { // push_pop_max: the new key, unless it is the greatest itself (or ef == 0)
-              if (R.size && key < ~R.top) {
-                qheap_pop(R);
-                if (!qheap_push(R, ~key)) return 1;
-              }
-            } else if (!qheap_push(R, ~key)) {
-              return 1;
-            }
-          }
-        }
-      }
-    }
-  }
-  return 0;
-}
-
-// k_nns_filtered on heaps: same queries, same results, `res` of any length (NnsArgs.heap = the search queues,
-// heap_r = the result heaps; rows of a.cand hold up to rcap hits)
-template <int LPR, int NCH>
-__global__ __launch_bounds__(64, 4) void k_nns_heap(GraphDev g, NnsArgs a) {
+template <int LPR, int NCH, bool RES_HEAP>
+__global__ __launch_bounds__(64, 4) void k_nns(GraphDev g, NnsArgs a) {
   extern __shared__ __align__(16) unsigned char smem[];
-  u32 *nb_ids = reinterpret_cast<u32 *>(smem);
+  u64 *res = reinterpret_cast<u64 *>(smem); // (LDS variant: res, the descent's tie pool, then the rest)
+  u64 *pool = res + a.rcap;
+  u32 *nb_ids = RES_HEAP ? reinterpret_cast<u32 *>(smem) : reinterpret_cast<u32 *>(pool + HNY_POOL_CAP);
   float *nb_d = reinterpret_cast<float *>(nb_ids + 64);
   u32 *eps = reinterpret_cast<u32 *>(nb_d + 64);
   const int ln = threadIdx.x, t = ln % LPR;
+
+  Beam s; // LDS variant: greedy descent through the upper layers, the ordinary (unfiltered) walk
+#ifdef HNY_PHASE_CLOCKS
+  for (int i = 0; i < 12; i++) s.ph[i] = 0;
+  s.ph_t = 0;
+#endif
+  s.res = res;
+  s.pool = pool;
+  s.rcap = (int)a.rcap;
+  s.pool_over = 0;
+  s.err = 0;
+  s.res_len = 0;
+  s.pool_len = 0;
+  s.n_weird = 0;
+  s.tie_bits = 0;
+  s.dropped = false;
+  BeamR<1> rb_unused{{0ull}};
   Visited vis;
-  visited_init(vis, a.bits + (size_t)blockIdx.x * a.bits_words, a.bits_words, a.vlog + (size_t)blockIdx.x * a.log_cap,
-               a.log_cap, nullptr, 0u);
+  visited_init(vis, a.bits + (size_t)blockIdx.x * a.bits_words, a.bits_words,
+               a.vlog + (size_t)blockIdx.x * a.log_cap, a.log_cap, RES_HEAP ? nullptr : eps + a.eps_cap,
+               RES_HEAP ? 0u : a.vis_slots);
   QHeap C, R;
   C.h = a.heap + (size_t)blockIdx.x * a.heap_cap;
   C.cap = a.heap_cap;
-  R.h = a.heap_r + (size_t)blockIdx.x * a.heap_r_cap;
-  R.cap = a.heap_r_cap;
+  C.size = 0;
+  C.top = ~0ull;
+  if constexpr (RES_HEAP) {
+    R.h = a.heap_r + (size_t)blockIdx.x * a.heap_r_cap;
+    R.cap = a.heap_r_cap;
+  }
   u64 evals = 0;
-  u32 log_over_cnt = 0;
+  u32 err_iter = 0, log_over_cnt = 0, res_err = 0;
+
   for (;;) {
-    u32 mi = 0;
-    if (ln == 0) {
-      mi = atomicAdd(a.queue, 1u);
-      if (a.cancel && __hip_atomic_load(a.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) mi = 0xFFFFFFFFu;
-    }
-    mi = uni(mi);
-    if (mi >= a.n_members) break;
-    const u32 m = a.members ? uni(a.members[mi]) : mi;
-    const unsigned char *qrow;
-    float qn = 0.f;
-    u32 excl = HNY_SENT;
-    if (a.by_item) { // :826-828 the stored vector is the query
-      excl = uni(a.q_slots[m]);
-      qrow = g.rows + (size_t)excl * g.row_stride;
-      if (g.norms) qn = g.norms[excl];
-    } else {
-      qrow = a.q_rows + (size_t)m * a.q_stride;
-      if (a.q_norms) qn = a.q_norms[m];
-    }
+    const u32 m = next_member(a.queue, a.cancel, a.n_members, a.members);
+    if (m == HNY_SENT) break;
+    float qn;
+    u32 excl; // by_item: candidates.remove(item), reader.rs:840
+    const unsigned char *qrow = query_row(g, a, m, qn, excl);
     float4 q[NCH];
     load_row<LPR, NCH>(qrow, t, g.n16, q);
     int n_eps, st = 0;
@@ -2870,8 +2627,16 @@ __global__ __launch_bounds__(64, 4) void k_nns_heap(GraphDev g, NnsArgs a) {
       for (int i = ln; i < n_eps; i += 64) eps[i] = a.entry_points[i];
       WSYNC();
       for (u32 layer = g.max_level; layer >= 1u && !st; layer--) {
-        st = walk_layer_heap<LPR, NCH>(g, q, qn, layer, 1, eps, n_eps, C, R, rmin, vis, nb_ids, nb_d, evals, qrow);
-        const u32 closest = (u32)(rmin & 0xFFFFFFFFull);
+        u32 closest;
+        if constexpr (RES_HEAP) {
+          st = walk_layer_heap<LPR, NCH>(g, q, qn, layer, 1, eps, n_eps, C, R, rmin, vis, nb_ids, nb_d, nullptr,
+                                         HNY_SENT, evals, qrow);
+          closest = (u32)(rmin & 0xFFFFFFFFull);
+        } else {
+          walk_one_layer<LPR, NCH, true>(g, q, qn, layer, 1, eps, n_eps, s, vis, nb_ids, nb_d, evals, err_iter, qrow,
+                                         rb_unused);
+          closest = uni((u32)(s.res[0] >> 1) & 0x7FFFFFFFu);
+        }
         WSYNC();
         if (ln == 0) eps[0] = closest;
         n_eps = 1;
@@ -2882,74 +2647,75 @@ __global__ __launch_bounds__(64, 4) void k_nns_heap(GraphDev g, NnsArgs a) {
         WSYNC();
       }
     }
-    if (!st) st = visit_heap<LPR, NCH>(g, q, qn, (int)a.ef_main, eps, n_eps, C, R, vis, nb_ids, nb_d, a.filter, excl, evals, qrow);
-    u32 total = 0;
-    u64 *row = a.cand + (size_t)m * a.rcap;
-    auto drain = [&](u32 at) { // R, ascending, into row[at ..)
-      for (u32 i = R.size; i-- > 0u;) {
-        const u64 key = ~R.top;
-        if (ln == 0) row[at + i] = key;
-        qheap_pop(R);
-      }
+    // level 0 from eps[0 .. ne): `res` (len found()) is refilled
+    int res_len = 0;
+    auto visit = [&](int ef, int ne) -> int {
+      if constexpr (RES_HEAP)
+        return walk_layer_heap<LPR, NCH>(g, q, qn, 0u, ef, eps, ne, C, R, rmin, vis, nb_ids, nb_d, a.filter, excl,
+                                         evals, qrow);
+      else
+        return visit_filtered<LPR, NCH>(g, q, qn, ef, eps, ne, res, res_len, (int)a.rcap, res_err, vis, nb_ids, nb_d,
+                                        C, a.filter, excl, evals, err_iter, qrow);
     };
+    auto found = [&]() -> u32 { return RES_HEAP ? R.size : (u32)res_len; };
+    u64 *row = a.cand + (size_t)m * a.rcap;
+    auto extend = [&](u32 at) { // `res`, ascending, into row[at ..)
+      if constexpr (RES_HEAP)
+        qheap_drain(R, row + at);
+      else
+        for (int e = ln; e < res_len; e += 64) row[at + e] = res[e];
+    };
+    if (!st) st = visit((int)a.ef_main, n_eps);
+    u32 total = 0;
     if (!st) {
-      total = R.size;
+      total = found();
       if (total > a.rcap) {
         st = 1;
       } else {
-        drain(0u);
+        extend(0u);
         if (total < a.k) {
           // exhaustive fallback (:771-795 / :864-890): restart from every item not on `path` yet
-          const u32 nwords = (g.n + 31) >> 5;
           const u32 stop = a.by_item ? a.k : a.ef_opt;
-          u32 pos = 0;
           visited_flush(vis);
-          while (pos < g.n) {
-            const u32 wbase = pos >> 5;
-            const u32 widx = wbase + (u32)ln;
-            u32 unv = 0u;
-            if (widx < nwords) {
-              unv = ~__hip_atomic_load(&vis.bits[widx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              if (ln == 0 && (pos & 31u)) unv &= ~((1u << (pos & 31u)) - 1u);
-              if (widx == nwords - 1 && (g.n & 31u)) unv &= (1u << (g.n & 31u)) - 1u;
-            }
-            const u64 mk = ballot(unv != 0u);
-            if (!mk) {
-              pos = (wbase + 64u) << 5;
-              continue;
-            }
-            const int l0 = __ffsll((long long)mk) - 1;
-            const u32 w0 = (u32)__builtin_amdgcn_readlane((int)unv, l0);
-            const u32 slot = ((wbase + (u32)l0) << 5) + (u32)__builtin_ctz(w0);
+          for (u32 pos = 0, slot; (slot = next_unvisited(g, vis.bits, pos)) < g.n;) {
             pos = slot + 1;
             if (g.incremental && !g.has_vec[slot]) continue;
-            int ef2;
-            if (a.by_item) ef2 = (int)(a.k - total);                       // :878
-            else ef2 = a.ef_opt > total ? (int)(a.ef_opt - total) : 0;     // :783
+            const int ef2 = stop > total ? (int)(stop - total) : 0; // :878 / saturating_sub, :783
             WSYNC();
             if (ln == 0) eps[0] = slot;
             WSYNC();
-            st = visit_heap<LPR, NCH>(g, q, qn, ef2, eps, 1, C, R, vis, nb_ids, nb_d, a.filter, excl, evals, qrow);
+            st = visit(ef2, 1);
             if (st) break;
-            if (total + R.size > a.rcap) {
-              st = 1;
+            if (total + found() > a.rcap) {
+              if (RES_HEAP) st = 1;
+              else res_err = 1;
               break;
             }
-            const u32 got = R.size;
-            drain(total); // neighbours.extend(more_nns)
+            const u32 got = found();
+            extend(total); // neighbours.extend(more_nns)
             total += got;
             if (total >= stop) break;
           }
-          if (!st) { // drain_asc(): everything that was collected, sorted — through the heap once more
+          if (!st && !res_err) { // drain_asc(): everything that was collected, sorted
             __threadfence_block();
             WSYNC();
-            R.size = 0;
-            R.top = ~0ull;
-            for (u32 i = 0; i < total && !st; i++) {
-              const u64 key = uni64(row[i]);
-              if (!qheap_push(R, ~key)) st = 1;
+            if constexpr (RES_HEAP) { // through the heap once more
+              R.size = 0;
+              R.top = ~0ull;
+              for (u32 i = 0; i < total && !st; i++)
+                if (!qheap_push(R, ~uni64(row[i]))) st = 1;
+              if (!st) qheap_drain(R, row);
+            } else { // rank sort in LDS
+              for (u32 e = ln; e < total; e += 64) res[e] = row[e];
+              WSYNC();
+              for (u32 e = ln; e < total; e += 64) {
+                const u64 mine = res[e];
+                u32 rk = 0;
+                for (u32 k2 = 0; k2 < total; k2++) rk += res[k2] < mine ? 1 : 0;
+                row[rk] = mine;
+              }
+              WSYNC();
             }
-            if (!st) drain(0u);
           }
         }
       }
@@ -2965,6 +2731,8 @@ __global__ __launch_bounds__(64, 4) void k_nns_heap(GraphDev g, NnsArgs a) {
   if (ln == 0) {
     if (evals) atomicAdd(&g.stats[ST_EVALS_WALK], evals);
     if (log_over_cnt) atomicAdd(&g.stats[ST_LOG_OVERFLOW], (u64)log_over_cnt);
+    if (s.err || res_err) atomicAdd(&g.stats[ST_ERR_RES_OVERFLOW], 1ull);
+    if (err_iter) atomicAdd(&g.stats[ST_ERR_ITER], 1ull);
   }
 }
 
@@ -2982,24 +2750,11 @@ __global__ __launch_bounds__(64, 4) void k_nns_linear(GraphDev g, NnsArgs a) {
   u64 evals = 0;
   u32 res_err = 0;
   for (;;) {
-    u32 mi = 0;
-    if (ln == 0) {
-      mi = atomicAdd(a.queue, 1u);
-      if (a.cancel && __hip_atomic_load(a.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) mi = 0xFFFFFFFFu;
-    }
-    mi = uni(mi);
-    if (mi >= a.n_members) break;
-    const u32 m = a.members ? uni(a.members[mi]) : mi;
-    const unsigned char *qrow;
-    float qn = 0.f;
-    if (a.by_item) {
-      const u32 qs = uni(a.q_slots[m]);
-      qrow = g.rows + (size_t)qs * g.row_stride;
-      if (g.norms) qn = g.norms[qs];
-    } else {
-      qrow = a.q_rows + (size_t)m * a.q_stride;
-      if (a.q_norms) qn = a.q_norms[m];
-    }
+    const u32 m = next_member(a.queue, a.cancel, a.n_members, a.members);
+    if (m == HNY_SENT) break;
+    float qn;
+    u32 item;
+    const unsigned char *qrow = query_row(g, a, m, qn, item);
     float4 q[NCH];
     load_row<LPR, NCH>(qrow, t, g.n16, q);
     int res_len = 0;
@@ -4738,10 +4493,15 @@ struct Hot {
   };
 };
 template <int L, int C>
-struct NnsFilteredLauncher {
+struct NnsLauncher {
   static hipError_t run(const GraphDev &g, const NnsArgs &a, int grid, hipStream_t st) {
-    size_t lds = hnyk_walk_lds_bytes(a.rcap, a.eps_cap) + (size_t)a.vis_slots * 4;
-    hipLaunchKernelGGL((k_nns_filtered<L, C>), dim3(grid), dim3(64), lds, st, g, a);
+    if (a.heap_r) {
+      const size_t lds = 64 * 4 * 2 + (size_t)a.eps_cap * 4;
+      hipLaunchKernelGGL((k_nns<L, C, true>), dim3(grid), dim3(64), lds, st, g, a);
+    } else {
+      const size_t lds = hnyk_walk_lds_bytes(a.rcap, a.eps_cap) + (size_t)a.vis_slots * 4;
+      hipLaunchKernelGGL((k_nns<L, C, false>), dim3(grid), dim3(64), lds, st, g, a);
+    }
     return hipGetLastError();
   }
 };
@@ -4750,14 +4510,6 @@ struct WalkHeapLauncher {
   static hipError_t run(const GraphDev &g, const WalkArgs &a, int grid, hipStream_t st) {
     const size_t lds = 64 * 4 * 2 + (size_t)a.eps_cap * 4;
     hipLaunchKernelGGL((k_walk_heap<L, C>), dim3(grid), dim3(64), lds, st, g, a);
-    return hipGetLastError();
-  }
-};
-template <int L, int C>
-struct NnsHeapLauncher {
-  static hipError_t run(const GraphDev &g, const NnsArgs &a, int grid, hipStream_t st) {
-    const size_t lds = 64 * 4 * 2 + (size_t)a.eps_cap * 4;
-    hipLaunchKernelGGL((k_nns_heap<L, C>), dim3(grid), dim3(64), lds, st, g, a);
     return hipGetLastError();
   }
 };
@@ -4886,11 +4638,8 @@ hipError_t hnyk_walk(const GraphDev &g, const WalkArgs &a, LaunchShape s, int gr
 hipError_t hnyk_walk_heap(const GraphDev &g, const WalkArgs &a, LaunchShape s, int grid, hipStream_t st) {
   return dispatch_shape<WalkHeapLauncher>(s, g, a, grid, st);
 }
-hipError_t hnyk_nns_filtered(const GraphDev &g, const NnsArgs &a, LaunchShape s, int grid, hipStream_t st) {
-  return dispatch_shape<NnsFilteredLauncher>(s, g, a, grid, st);
-}
-hipError_t hnyk_nns_heap(const GraphDev &g, const NnsArgs &a, LaunchShape s, int grid, hipStream_t st) {
-  return dispatch_shape<NnsHeapLauncher>(s, g, a, grid, st);
+hipError_t hnyk_nns(const GraphDev &g, const NnsArgs &a, LaunchShape s, int grid, hipStream_t st) {
+  return dispatch_shape<NnsLauncher>(s, g, a, grid, st);
 }
 hipError_t hnyk_nns_linear(const GraphDev &g, const NnsArgs &a, LaunchShape s, int grid, hipStream_t st) {
   return dispatch_shape<NnsLinearLauncher>(s, g, a, grid, st);

@@ -78,8 +78,8 @@ def test_filtered_search_equals_oracle(orc, hny, metric, n, dim, M, M0):
 
 @pytest.mark.parametrize("metric,n,dim,M,M0", [(0, 6000, 64, 8, 16), (3, 7000, 64, 8, 16), (1, 5000, 24, 4, 8)])
 def test_filtered_and_by_item_search_with_result_sets_beyond_the_lds(orc, hny, metric, n, dim, M, M0):
-    """max(ef_search, k) >= 4 096 with a candidates filter / by_item: `res` no longer fits k_nns_filtered's LDS, the
-    same Visitor::visit runs with the search queue AND `res` as heaps in HBM (k_nns_heap) — ids, distances and
+    """max(ef_search, k) >= 4 096 with a candidates filter / by_item: `res` no longer fits k_nns's LDS, the
+    same Visitor::visit runs with the search queue AND `res` as heaps in HBM (k_nns<.., true>) — ids, distances and
     counts of the restated Reader; sparse filters reach the exhaustive fallback (reader.rs:771-795 / 864-890) there,
     64-bit Hamming codes are all ties; the linear scan keeps its LDS ranking (min(k, candidates) hits)."""
     ids = (np.arange(n, dtype=np.uint32) * 3 + 1)
@@ -251,9 +251,9 @@ def test_search_cancellation_through_the_c_abi(orc, hny):
 @pytest.mark.parametrize("metric,n,dim", [(1, 6000, 16), (3, 4200, 128)])
 def test_filtered_and_by_item_search_from_more_entry_points_than_the_lds_set_holds(orc, hny, metric, n, dim):
     """An all-level-0 index of more than 4 095 items: every item is an entry point (hnsw.rs:278-285) and every one
-    of them is pushed to `res` before the first pop (reader.rs:755-761), whatever ef_search says — k_nns_filtered's LDS
+    of them is pushed to `res` before the first pop (reader.rs:755-761), whatever ef_search says — k_nns's LDS
     result set (4 096 entries) cannot hold them.  Round 4 accepted such builds (up to 8 192 entry points) but sent a
-    filtered / by_item search with a small ef to the LDS kernel; it now takes the heaps in HBM (k_nns_heap).  Same
+    filtered / by_item search with a small ef to the LDS kernel; it now takes the heaps in HBM (k_nns<.., true>).  Same
     ids, distances and counts as the restated Reader."""
     rng = np.random.default_rng(n)
     vecs = rng.uniform(-1, 1, (n, dim)).astype(np.float32)

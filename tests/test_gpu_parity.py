@@ -1170,7 +1170,7 @@ def test_64_bit_hamming_codes_build_and_search_equal_oracle(orc, hny):
     """50 000 x 64-bit Hamming codes (65 distinct distances: every walk drags hundreds of ties along): the build
     — members whose tie pool overflows go through k_walk_heap — equals the oracle's edge for edge, and a search
     with ef_search = 300, whose pool overflows for most queries, is repeated on the heap-queue searcher
-    (k_nns_filtered without a filter) and returns the restated Reader's ids, distances and counts."""
+    (k_nns without a filter) and returns the restated Reader's ids, distances and counts."""
     rng = np.random.default_rng(11)
     n, dim = 50000, 64
     vecs = rng.uniform(-1, 1, (n, dim)).astype(np.float32)
@@ -1194,7 +1194,7 @@ def test_64_bit_hamming_codes_build_and_search_equal_oracle(orc, hny):
 def test_search_with_result_sets_beyond_the_lds_survives_a_tie_pool_overflow(orc, hny, monkeypatch):
     """ef_search >= 4 096 keeps the result set in HBM; on 64-bit Hamming codes the walk's tie pool overflows for
     such a search (found at C5 with ef_search = 6 400: the call failed with "tie pool overflow").  Those queries
-    are walked again by k_walk_heap in reader mode (`candidates` and `res` as heaps in HBM) and return the
+    are searched again by k_nns<.., true> (the queue and `res` as heaps in HBM, no filter) and return the
     restated Reader's ids, distances and counts.  Second half: the same path forced for EVERY query
     (HNY_POOL_FORCE_RETRY=1) on an index with zero vectors and ef_search > n, where the Reader's exhaustive
     fallback (reader.rs:771-795) runs inside the heap kernel, and with ef_search = 300 through the LDS searcher."""
