@@ -326,6 +326,7 @@ struct hny_builder {
   uint32_t walk_slots = 0, bits_words = 0, log_cap = 0, rcap = 0, max_batch = 0;
   uint64_t top_layer_nodes = 0; // see res_capacity
   int stage_rows = 0;      // selected rows staged in LDS by the workgroup prune kernels
+  int n8_stage_rows = 0;   // the same for the one-wave short-row kernels (k_prune_n8, k_apply_n8)
   u32 cur_n_ops = 0, cur_n_def = 0; // of the batch being applied
   bool apply_open = false;          // between hny_builder_apply_begin and _merge
   int vis_slots_env = -1;  // HNY_VIS_SLOTS: LDS visited table entries per walk wave, -1 = auto
@@ -964,6 +965,8 @@ static int create_impl(const hny_build_opts *opts, const hny_items *items, const
     int sl = (int)((u32)std::max(0, env_int("HNY_STAGE_BYTES", 24576)) / (n16 * 16u));
     if (sl > HNY_MAX_CAP) sl = HNY_MAX_CAP;
     b->stage_rows = sl / rpg * rpg;
+    // short rows: as many selected rows as 6 KB per wave hold (20 waves per CU)
+    b->n8_stage_rows = (int)std::min<uint32_t>(HNY_MAX_CAP, std::max<uint32_t>(1, 6144u / (n16 * 16u)));
     // the workgroup prune kernels carry their own wave-order arithmetic: strict mode and very long
     // rows use the single-wave kernels, which all go through dist_rows
     b->wave_prune_only = b->shape.nch > 8 || o.x86_order; // the one-wave prune: strict mode, rows beyond 8 KB
@@ -1305,9 +1308,8 @@ int hny_builder_search(hny_builder *b, uint32_t lo, uint32_t hi, void *sel_dev) 
   };
   auto launch_prune = [&](const PruneArgs &p, hipStream_t st) -> hipError_t {
     if (!b->wave_prune_only && hnyk_prune_n8_ok(b->g, p, b->shape)) {
-      // short rows: one wave per query; as many selected rows staged as 6 KB per wave hold (20 waves per CU)
-      const int sl = (int)std::min<uint32_t>(HNY_MAX_CAP, std::max<uint32_t>(1, 6144u / b->g.row_stride));
-      return hnyk_prune_n8(b->g, p, b->shape, sl, (int)std::min<uint32_t>(p.hi - p.lo, 5120u), st);
+      // short rows: one wave per query
+      return hnyk_prune_n8(b->g, p, b->shape, b->n8_stage_rows, (int)std::min<uint32_t>(p.hi - p.lo, 5120u), st);
     }
     if (b->wave_prune_only)
       return hnyk_prune(b->g, p, b->shape, (int)std::min<uint32_t>(p.hi - p.lo, b->walk_slots), st);
@@ -1421,7 +1423,7 @@ int hny_builder_search(hny_builder *b, uint32_t lo, uint32_t hi, void *sel_dev) 
   return HNY_OK;
 }
 
-// phase 2 up to and including k_apply: link ops emitted, sorted, segmented; every target whose list
+// phase 2 up to and including k_apply_append (k_apply): link ops emitted, sorted, segmented; every target whose list
 // cannot overflow is done, the others are listed in d_deferred (first op of their segment)
 static int apply_front(hny_builder *b, const void *sel_dev, ApplyArgs &a) {
   const uint32_t L = b->cur.level, cs = cap_of(b, L);
@@ -1468,10 +1470,8 @@ static int apply_front(hny_builder *b, const void *sel_dev, ApplyArgs &a) {
 
 // the targets whose list overflows: one wave each on short rows (k_apply_n8), a 256-thread workgroup otherwise
 static hipError_t launch_apply_deferred(hny_builder *b, const ApplyArgs &a, u32 work) {
-  if (hnyk_apply_n8_ok(b->g, b->shape)) {
-    const int sl = (int)std::min<uint32_t>(HNY_MAX_CAP, std::max<uint32_t>(1, 6144u / b->g.row_stride));
-    return hnyk_apply_n8(b->g, a, b->shape, sl, (int)std::min<u32>(work, 5120u), b->stream);
-  }
+  if (hnyk_apply_n8_ok(b->g, b->shape))
+    return hnyk_apply_n8(b->g, a, b->shape, b->n8_stage_rows, (int)std::min<u32>(work, 5120u), b->stream);
   return hnyk_apply_wg(b->g, a, b->shape, b->stage_rows, (int)std::min<u32>(work, 2048u), b->stream);
 }
 
@@ -1510,7 +1510,7 @@ int hny_builder_apply_begin(hny_builder *b, const void *sel_dev, uint32_t *n_def
   if (!b->wave_prune_only) {
     HIP_TRY(hipMemcpyAsync(&nd, b->d_nseg.p + 1, 4, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
-    if (nd > 1) { // canonical order: k_apply appended in atomic order, which differs between replicas
+    if (nd > 1) { // canonical order: k_apply_append appended in atomic order, which differs between replicas
       size_t tmp = b->sort_tmp_bytes;
       HIP_TRY(hnyk_sort_u32(b->d_sort_tmp.p, tmp, b->d_deferred.p, b->d_deferred_b.p, nd, b->stream));
       HIP_TRY(hipMemcpyAsync(b->d_deferred.p, b->d_deferred_b.p, (size_t)nd * 4, hipMemcpyDeviceToDevice, b->stream));

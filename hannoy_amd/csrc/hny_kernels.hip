@@ -618,6 +618,21 @@ __device__ __forceinline__ void dist_rows_narrow(const GraphDev &g, const float4
   }
 }
 
+// in-memory list of (layer, node): `cap` slots of ids in insertion order (HNY_SENT beyond the count) and
+// distances, and its count word (low 16 bits = count, bit 31 = frozen).  A node on layer > 0 always has
+// that layer (hnsw.rs:534 `layers.get(level)`: it was found there).
+struct NodeList {
+  u32 cap;
+  u32 *ids;
+  float *dist;
+  u32 *cnt;
+};
+__device__ __forceinline__ NodeList node_list(const GraphDev &g, u32 layer, u32 node) {
+  if (layer == 0)
+    return {g.M0, g.l0_ids + (size_t)node * g.M0, g.l0_dist + (size_t)node * g.M0, g.l0_cnt + node};
+  const size_t u = (size_t)g.upper_idx[node] * g.up_layers + (layer - 1);
+  return {g.M, g.up_ids + u * g.M, g.up_dist + u * g.M, g.up_cnt + u};
+}
 // neighbour list of (layer, node): ids in insertion order, HNY_SENT beyond the count
 // (get_neighbours, hnsw.rs:428-456, fresh DB: in-memory lists only)
 __device__ __forceinline__ const u32 *nbr_ids(const GraphDev &g, u32 layer, u32 node, u32 &cap) {
@@ -2791,6 +2806,70 @@ __global__ __launch_bounds__(64, 4) void k_nns_linear(GraphDev g, NnsArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// list steps shared by the prune, add_link and fill_gaps kernels, for blocks of NT threads (one wave:
+// 64, a workgroup: 256).  ONE: every range is known to fit one pass (lists of at most 64 slots in a
+// wave), so thread t takes entry t alone and no loop is left for the register allocator.  Keys: dist
+// bits << 32 | id.  The caller syncs after each.
+// ---------------------------------------------------------------------------------------------
+template <int NT>
+__device__ __forceinline__ void block_sync() {
+  if constexpr (NT == 64)
+    WSYNC();
+  else
+    __syncthreads();
+}
+// f(e) for every e in [0, n) (int or u32): thread t takes t, t + NT, ...
+template <int NT, bool ONE, class I, class F>
+__device__ __forceinline__ void each(I n, F f) {
+  if constexpr (ONE) {
+    if ((I)threadIdx.x < n) f((I)threadIdx.x);
+  } else {
+    for (I e = (I)threadIdx.x; e < n; e += (I)NT) f(e);
+  }
+}
+// keys[0, n) sorted into out: ascending, ties in position order
+template <int NT, bool ONE = false>
+__device__ __forceinline__ void rank_sort(const u64 *keys, int n, u64 *out) {
+  auto rank = [&](int e, u64 mine) __attribute__((always_inline)) {
+    int rk = 0;
+    for (int j = 0; j < n; j++) {
+      const u64 o = keys[j];
+      rk += (o < mine || (o == mine && j < e)) ? 1 : 0;
+    }
+    return rk;
+  };
+  if constexpr (ONE) { // every lane ranks (a lane beyond n a dummy): the loop stays uniform
+    const int e = (int)threadIdx.x;
+    const u64 mine = e < n ? keys[e] : 0ull;
+    const int rk = rank(e, mine);
+    if (e < n) out[rk] = mine;
+  } else {
+    for (int e = (int)threadIdx.x; e < n; e += NT) {
+      const u64 mine = keys[e];
+      out[rank(e, mine)] = mine;
+    }
+  }
+}
+// the list := keys[0, cnt), HNY_SENT / 0.0 beyond, with count word cw
+template <int NT, bool ONE = false>
+__device__ __forceinline__ void store_list(const NodeList &l, const u64 *keys, int cnt, u32 cw) {
+  each<NT, ONE>(l.cap, [&](u32 e) __attribute__((always_inline)) {
+    const bool on = (int)e < cnt;
+    const u64 k = on ? keys[e] : 0ull;
+    l.ids[e] = on ? (u32)(k & 0xFFFFFFFFull) : HNY_SENT;
+    l.dist[e] = on ? __uint_as_float((u32)(k >> 32)) : 0.f;
+  });
+  if (threadIdx.x == 0) *l.cnt = cw;
+}
+// a prune kernel's result for member m on the launch's layer: [0] = s_len, [1 ..] = S
+template <int NT, bool ONE = false>
+__device__ __forceinline__ void store_sel(const PruneArgs &a, u32 m, const u64 *S, int s_len) {
+  u64 *out = a.sel + (size_t)m * a.sel_stride + (size_t)(a.batch_level - a.layer) * (a.cap_sel + 1);
+  if (threadIdx.x == 0) out[0] = (u64)s_len;
+  each<NT, ONE>(s_len, [&](int e) __attribute__((always_inline)) { out[1 + e] = S[e]; });
+}
+
+// ---------------------------------------------------------------------------------------------
 // robust_prune (hnsw.rs:565-597) on a list that is already sorted ascending by (bits(d), id).
 // list/sel keys: dist bits << 32 | slot.  `exists i in S: bits(d(c,i)*alpha) < bits(dq)` does not
 // depend on evaluation order, so S is tested RPI rows at a time with an early exit per chunk.
@@ -2802,7 +2881,7 @@ __host__ __device__ inline u32 wave_capmax(const GraphDev &g) {
   return c <= (u32)HNY_MAX_CAP ? (u32)HNY_MAX_CAP : (c + 63u) / 64u * 64u;
 }
 template <int LPR, int NCH>
-__device__ int wave_prune(const GraphDev &g, const u64 *list, int n, int cap, u64 *S, u32 *s_ids,
+__device__ __forceinline__ int wave_prune(const GraphDev &g, const u64 *list, int n, int cap, u64 *S, u32 *s_ids,
                           float *tmp_d, u64 &evals) {
   constexpr int RPI = (64 / LPR) * DistGroups<LPR, NCH>::U;
   const int ln = threadIdx.x, t = ln % LPR;
@@ -2854,10 +2933,7 @@ __global__ __launch_bounds__(64) void k_prune(GraphDev g, PruneArgs a) {
     int n = (int)a.cand_n[m];
     for (int e = ln; e < n; e += 64) list[e] = a.cand[(size_t)m * a.rcap + e];
     WSYNC();
-    int s_len = wave_prune<LPR, NCH>(g, list, n, (int)a.cap, S, s_ids, tmp_d, evals);
-    u64 *out = a.sel + (size_t)m * a.sel_stride + (size_t)(a.batch_level - a.layer) * (a.cap_sel + 1);
-    if (ln == 0) out[0] = (u64)s_len;
-    for (int e = ln; e < s_len; e += 64) out[1 + e] = S[e];
+    store_sel<64>(a, m, S, wave_prune<LPR, NCH>(g, list, n, (int)a.cap, S, s_ids, tmp_d, evals));
     WSYNC();
   }
   if (ln == 0 && evals) atomicAdd(&g.stats[ST_EVALS_PRUNE], evals);
@@ -3095,6 +3171,21 @@ __device__ __forceinline__ WgPruneLds wg_prune_carve(unsigned char *base, int SL
   return L;
 }
 
+// wg_prune; the specialised kernels (SP != 0) on rows that fill every lane's chunks (768-d, 1024-d, 128-d, 1024 bits
+// ...) run it on a copy of g whose n16 is a constant, so the per-chunk bounds guards of the row loads fold away
+// (~20 % of a pass)
+template <int LPR, int NCH, int NW, int SP>
+__device__ __forceinline__ int wg_prune_sp(const GraphDev &g, const u64 *list, int n, int cap, const WgPruneLds &L,
+                                           u64 &evals) {
+  if (SP != 0 && g.n16 == (u32)(LPR * NCH) && g.row_stride == (u32)(LPR * NCH * 16)) {
+    GraphDev gf = g;
+    gf.n16 = (u32)(LPR * NCH);
+    gf.row_stride = (u32)(LPR * NCH * 16);
+    return wg_prune<LPR, NCH, NW>(gf, list, n, cap, L, evals);
+  }
+  return wg_prune<LPR, NCH, NW>(g, list, n, cap, L, evals);
+}
+
 // rows up to 3 KB: 4 workgroups of 4 waves per CU is what the LDS carve allows, keep the registers there
 constexpr int wg_waves_per_simd(int nch, int nw) { return nw == 4 && nch <= 3 ? 4 : 1; }
 
@@ -3132,24 +3223,7 @@ __global__ __launch_bounds__(NW * 64, wg_waves_per_simd(NCH, NW)) void k_prune_w
       for (int e = tid; e < n; e += blockDim.x) list[e] = a.cand[(size_t)m * a.rcap + e];
     }
     __syncthreads();
-    int s_len;
-    if constexpr (SP != 0) {
-      // rows that fill every lane's chunks (768-d, 1024-d, 128-d, 1024 bits ...): with n16 a
-      // constant the per-chunk bounds guards of the row loads fold away (~20 % of a pass)
-      if (g.n16 == (u32)(LPR * NCH) && g.row_stride == (u32)(LPR * NCH * 16)) {
-        GraphDev gf = g;
-        gf.n16 = (u32)(LPR * NCH);
-        gf.row_stride = (u32)(LPR * NCH * 16);
-        s_len = wg_prune<LPR, NCH, NW>(gf, list, n, (int)a.cap, L, evals);
-      } else {
-        s_len = wg_prune<LPR, NCH, NW>(g, list, n, (int)a.cap, L, evals);
-      }
-    } else {
-      s_len = wg_prune<LPR, NCH, NW>(g, list, n, (int)a.cap, L, evals);
-    }
-    u64 *out = a.sel + (size_t)m * a.sel_stride + (size_t)(a.batch_level - a.layer) * (a.cap_sel + 1);
-    if (tid == 0) out[0] = (u64)s_len;
-    for (int e = tid; e < s_len; e += (int)blockDim.x) out[1 + e] = L.S[e];
+    store_sel<NW * 64>(a, m, L.S, wg_prune_sp<LPR, NCH, NW, SP>(g, list, n, (int)a.cap, L, evals));
     __syncthreads();
   }
   if ((tid & 63) == 0 && evals) atomicAdd(&g.stats[ST_EVALS_PRUNE], evals);
@@ -3420,13 +3494,67 @@ __global__ __launch_bounds__(64, 5) void k_prune_n8(GraphDev g_in, PruneArgs a, 
     const int n = (int)a.cand_n[m];
     for (int e = ln; e < n; e += 64) list[e] = a.cand[(size_t)m * a.rcap + e];
     WSYNC();
-    const int s_len = prune_n8_core<LPRO>(g, list, n, (int)a.cap, S, s_ids, s_norm, stage, newrow, SL, evals);
-    u64 *out = a.sel + (size_t)m * a.sel_stride + (size_t)(a.batch_level - a.layer) * (a.cap_sel + 1);
-    if (ln == 0) out[0] = (u64)s_len;
-    if (ln < s_len) out[1 + ln] = S[ln];
+    store_sel<64, true>(a, m, S, prune_n8_core<LPRO>(g, list, n, (int)a.cap, S, s_ids, s_norm, stage, newrow, SL, evals));
     WSYNC();
   }
   if (ln == 0 && evals) atomicAdd(&g.stats[ST_EVALS_PRUNE], evals);
+}
+
+// ---------------------------------------------------------------------------------------------
+// add_link (hnsw.rs:523-560) for every op of the segment that starts at op i0, by a block of NT threads: p == q
+// is skipped (:530), a link is appended while there is room (:542-545, no dedup), and a full list prunes itself
+// instead, the new link dropped (:547-552).  ONE: lists of at most NT slots (see each).  lk / sorted: the list
+// and its sorted copy (cap entries each, LDS);
+// prune(sorted, n, cap) is the kernel's robust_prune, which leaves its selection in S and returns its length.
+// A full list that prunes to itself is frozen (count word bit 31): every later add_link would redo the same prune
+// with the same outcome, so a frozen list is never touched again.  rec (multi-GPU, else null): the exchange record
+// of the finished list, for the ranks that did not compute it — written for a list frozen on entry too.
+// ---------------------------------------------------------------------------------------------
+template <int NT, bool ONE, class Prune>
+__device__ __forceinline__ void replay_add_link(const GraphDev &g, const ApplyArgs &a, u32 i0, u64 *lk, u64 *sorted,
+                                                const u64 *S, u64 *rec, Prune prune) {
+  const int tid = threadIdx.x;
+  const u64 k0 = a.keys[i0] >> HNY_SEQ_BITS;
+  const u32 target = (u32)(k0 & 0x7FFFFFFFull);
+  const NodeList l = node_list(g, (u32)(k0 >> 31), target);
+  const u32 cw = *l.cnt;
+  bool frozen = (cw >> 31) != 0u;
+  if (frozen && !rec) return;
+  int cnt = (int)(cw & 0xFFFFu);
+  each<NT, ONE>(cnt, [&](int e) __attribute__((always_inline)) { lk[e] = ((u64)fbits(l.dist[e]) << 32) | l.ids[e]; });
+  block_sync<NT>();
+  for (u32 i = i0; i < a.n_ops && !frozen; i++) {
+    const u64 key = a.keys[i];
+    if (key == HNY_OP_INVALID || (key >> HNY_SEQ_BITS) != k0) break;
+    const u64 val = a.vals[i];
+    if ((u32)(val & 0xFFFFFFFFull) == target) continue;
+    if (cnt < (int)l.cap) {
+      if (tid == 0) lk[cnt] = val;
+      cnt++;
+      block_sync<NT>();
+    } else {
+      rank_sort<NT, ONE>(lk, cnt, sorted);
+      block_sync<NT>();
+      const int s_len = prune(sorted, cnt, (int)l.cap);
+      each<NT, ONE>(s_len, [&](int e) __attribute__((always_inline)) { lk[e] = S[e]; });
+      cnt = s_len;
+      frozen = s_len == (int)l.cap;
+      block_sync<NT>();
+    }
+  }
+  const u32 cw_out = (u32)cnt | (frozen ? 0x80000000u : 0u);
+  store_list<NT, ONE>(l, lk, cnt, cw_out);
+  if (rec) {
+    if (tid == 0) {
+      rec[0] = k0;
+      rec[1] = (u64)cw_out;
+    }
+    each<NT, ONE>(cnt, [&](int e) __attribute__((always_inline)) { rec[2 + e] = lk[e]; });
+  }
+}
+// the exchange record of deferred segment di (sw ranks share the segments round robin), or null on one GPU
+__device__ __forceinline__ u64 *exch_rec(const ApplyArgs &a, u32 di, u32 sw) {
+  return a.exch ? a.exch + (size_t)(di / sw) * a.exch_stride : nullptr;
 }
 
 // add_link for the targets whose list overflows (hnsw.rs:547-552), short rows: one WAVE per target, the
@@ -3443,75 +3571,17 @@ __global__ __launch_bounds__(64, 5) void k_apply_n8(GraphDev g_in, ApplyArgs a, 
   float *s_norm = reinterpret_cast<float *>(s_ids + HNY_MAX_CAP);
   unsigned char *stage = reinterpret_cast<unsigned char *>(s_norm + HNY_MAX_CAP);
   unsigned char *newrow = stage + (size_t)SL * g.row_stride;
-  const int ln = HNY_LANE;
   const u32 n_def = *a.n_deferred;
   u64 evals = 0;
   const u32 sw = a.shard_world ? a.shard_world : 1u;
   for (u32 di = a.shard_rank + blockIdx.x * sw; di < n_def; di += gridDim.x * sw) {
-    const u32 i0 = a.deferred[di];
-    const u64 k0 = a.keys[i0] >> HNY_SEQ_BITS;
-    const u32 target = (u32)(k0 & 0x7FFFFFFFull), layer = (u32)(k0 >> 31);
-    u32 cap, *ids, *cntp;
-    float *dist;
-    if (layer == 0) {
-      cap = g.M0;
-      ids = g.l0_ids + (size_t)target * g.M0;
-      dist = g.l0_dist + (size_t)target * g.M0;
-      cntp = g.l0_cnt + target;
-    } else {
-      size_t u = (size_t)g.upper_idx[target] * g.up_layers + (layer - 1);
-      cap = g.M;
-      ids = g.up_ids + u * g.M;
-      dist = g.up_dist + u * g.M;
-      cntp = g.up_cnt + u;
-    }
-    const u32 cw = *cntp;
-    int cnt = (int)(cw & 0xFFFFu);
-    bool frozen = (cw >> 31) != 0u;
-    if (ln < cnt) lk[ln] = ((u64)fbits(dist[ln]) << 32) | ids[ln]; // cap <= 64: one entry per lane
-    WSYNC();
-    for (u32 i = i0; i < a.n_ops && !frozen; i++) {
-      const u64 key = a.keys[i];
-      if (key == HNY_OP_INVALID || (key >> HNY_SEQ_BITS) != k0) break;
-      const u64 val = a.vals[i];
-      if ((u32)(val & 0xFFFFFFFFull) == target) continue; // hnsw.rs:530
-      if (cnt < (int)cap) {                               // :542-545
-        if (ln == 0) lk[cnt] = val;
-        cnt++;
-        WSYNC();
-      } else { // :547-552: the new link is dropped, the full list prunes itself
-        const u64 mine = ln < cnt ? lk[ln] : 0ull;
-        int rk = 0;
-        for (int j = 0; j < cnt; j++) {
-          const u64 o = lk[j];
-          rk += (o < mine || (o == mine && j < ln)) ? 1 : 0;
-        }
-        if (ln < cnt) sorted[rk] = mine;
-        WSYNC();
-        const int s_len = prune_n8_core<LPRO>(g, sorted, cnt, (int)cap, S, s_ids, s_norm, stage, newrow, SL, evals);
-        if (ln < s_len) lk[ln] = S[ln];
-        cnt = s_len;
-        frozen = (s_len == (int)cap); // a full list that prunes to itself can never change again
-        WSYNC();
-      }
-    }
-    if ((u32)ln < cap) {
-      const bool on = ln < cnt;
-      ids[ln] = on ? (u32)(lk[ln] & 0xFFFFFFFFull) : HNY_SENT;
-      dist[ln] = on ? __uint_as_float((u32)(lk[ln] >> 32)) : 0.f;
-    }
-    if (ln == 0) *cntp = (u32)cnt | (frozen ? 0x80000000u : 0u);
-    if (a.exch) { // the finished list, for the ranks that did not compute it
-      u64 *rec = a.exch + (size_t)(di / sw) * a.exch_stride;
-      if (ln == 0) {
-        rec[0] = k0;
-        rec[1] = (u64)((u32)cnt | (frozen ? 0x80000000u : 0u));
-      }
-      if (ln < cnt) rec[2 + ln] = lk[ln];
-    }
+    replay_add_link<64, true>(g, a, a.deferred[di], lk, sorted, S, exch_rec(a, di, sw),
+                        [&](u64 *list, int n, int cap) __attribute__((always_inline)) {
+                          return prune_n8_core<LPRO>(g, list, n, cap, S, s_ids, s_norm, stage, newrow, SL, evals);
+                        });
     WSYNC();
   }
-  if (ln == 0 && evals) atomicAdd(&g.stats[ST_EVALS_APPLY], evals);
+  if (threadIdx.x == 0 && evals) atomicAdd(&g.stats[ST_EVALS_APPLY], evals);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3605,54 +3675,42 @@ __global__ __launch_bounds__(256) void k_segments(const u64 *keys, u32 n_ops, u3
 
 // add_link (hnsw.rs:523-560) for the segments whose list cannot overflow — nearly all of them: one
 // THREAD per (layer, target) appends the segment's links in order (:542-545, no dedup; :530 p == q is
-// a no-op).  A segment that may overflow is left, whole, to k_apply_wg (`deferred`).  The one-wave-
-// per-segment k_apply below spent 295 us per C2 batch walking ~2 M segments of 1-2 ops each.
+// a no-op).  A segment that may overflow is left, whole, to k_apply_wg / k_apply_n8 (`deferred`).  The
+// one-wave-per-segment k_apply below spent 295 us per C2 batch walking ~2 M segments of 1-2 ops each.
 __global__ __launch_bounds__(256) void k_apply_append(GraphDev g, ApplyArgs a) {
   const u32 n_seg = *a.n_seg;
   for (u32 sg = blockIdx.x * blockDim.x + threadIdx.x; sg < n_seg; sg += gridDim.x * blockDim.x) {
     const u32 i0 = a.seg_start[sg];
     const u64 k0 = a.keys[i0] >> HNY_SEQ_BITS;
-    const u32 target = (u32)(k0 & 0x7FFFFFFFull), layer = (u32)(k0 >> 31);
-    u32 cap, *ids, *cntp;
-    float *dist;
-    if (layer == 0) {
-      cap = g.M0;
-      ids = g.l0_ids + (size_t)target * g.M0;
-      dist = g.l0_dist + (size_t)target * g.M0;
-      cntp = g.l0_cnt + target;
-    } else { // :534 `layers.get(level)` — the target always has this layer (it was found on it)
-      const size_t u = (size_t)g.upper_idx[target] * g.up_layers + (layer - 1);
-      cap = g.M;
-      ids = g.up_ids + u * g.M;
-      dist = g.up_dist + u * g.M;
-      cntp = g.up_cnt + u;
-    }
-    const u32 cw = *cntp;
-    if (cw >> 31) continue; // frozen: full and self-pruned to full, nothing can change it (see k_apply)
+    const u32 target = (u32)(k0 & 0x7FFFFFFFull);
+    const NodeList l = node_list(g, (u32)(k0 >> 31), target);
+    const u32 cw = *l.cnt;
+    if (cw >> 31) continue; // frozen: nothing can change it (see replay_add_link)
     u32 cnt = cw & 0xFFFFu;
     u32 nops = 0;
     for (u32 i = i0; i < a.n_ops; i++) {
       const u64 key = a.keys[i];
       if (key == HNY_OP_INVALID || (key >> HNY_SEQ_BITS) != k0) break;
       nops++;
-      if (cnt + nops > cap) break;
+      if (cnt + nops > l.cap) break;
     }
-    if (cnt + nops > cap) { // may overflow: k_apply_wg replays the whole segment
+    if (cnt + nops > l.cap) { // may overflow: the deferred kernel replays the whole segment
       a.deferred[atomicAdd(a.n_deferred, 1u)] = i0;
       continue;
     }
     for (u32 i = i0; i < i0 + nops; i++) {
       const u64 val = a.vals[i];
       if ((u32)(val & 0xFFFFFFFFull) == target) continue; // :530 p == q.1
-      ids[cnt] = (u32)(val & 0xFFFFFFFFull);
-      dist[cnt] = __uint_as_float((u32)(val >> 32));
+      l.ids[cnt] = (u32)(val & 0xFFFFFFFFull);
+      l.dist[cnt] = __uint_as_float((u32)(val >> 32));
       cnt++;
     }
-    *cntp = cnt;
+    *l.cnt = cnt;
   }
 }
 
-// add_link (hnsw.rs:523-560) for every op of one (layer, target), in order.
+// add_link for every op of one (layer, target), in order: strict mode and rows beyond 8 KB (`deferred` null,
+// see hny_host.cpp apply_front), the self-prune on wave_prune
 template <int LPR, int NCH, int SP>
 __global__ __launch_bounds__(64) void k_apply(GraphDev g_in, ApplyArgs a) {
   GraphDev g = g_in;
@@ -3661,94 +3719,24 @@ __global__ __launch_bounds__(64) void k_apply(GraphDev g_in, ApplyArgs a) {
   // the x86 order — are held whole and taken 64 slots at a time)
   extern __shared__ __align__(16) unsigned char smem[];
   const u32 capmax = wave_capmax(g);
-  u64 *lk = reinterpret_cast<u64 *>(smem); // the node's list: dist bits << 32 | slot
+  u64 *lk = reinterpret_cast<u64 *>(smem); // the node's list
   u64 *sorted = lk + capmax;
   u64 *S = sorted + capmax;
   u32 *s_ids = reinterpret_cast<u32 *>(S + capmax);
   float *tmp_d = reinterpret_cast<float *>(s_ids + capmax);
-  const int ln = threadIdx.x;
   const u32 n_seg = *a.n_seg;
   u64 evals = 0;
   for (u32 sg = blockIdx.x; sg < n_seg; sg += gridDim.x) {
-    const u32 i0 = a.seg_start[sg];
-    const u64 k0 = a.keys[i0] >> HNY_SEQ_BITS;
-    const u32 target = (u32)(k0 & 0x7FFFFFFFull), layer = (u32)(k0 >> 31);
-    u32 cap, *ids, *cntp;
-    float *dist;
-    if (layer == 0) {
-      cap = g.M0;
-      ids = g.l0_ids + (size_t)target * g.M0;
-      dist = g.l0_dist + (size_t)target * g.M0;
-      cntp = g.l0_cnt + target;
-    } else { // :534 `layers.get(level)` — the target always has this layer (it was found on it)
-      size_t u = (size_t)g.upper_idx[target] * g.up_layers + (layer - 1);
-      cap = g.M;
-      ids = g.up_ids + u * g.M;
-      dist = g.up_dist + u * g.M;
-      cntp = g.up_cnt + u;
-    }
-    u32 cw = *cntp;
-    int cnt = (int)(cw & 0xFFFFu);
-    bool frozen = (cw >> 31) != 0u;
-    // a frozen list never changes again (see below): nothing to do for any number of ops
-    if (frozen) continue;
-    if (a.deferred) {
-      // count the segment's ops; if the list can overflow, leave the whole segment to k_apply_wg
-      u32 nops = 0;
-      for (u32 i = i0; i < a.n_ops; i++) {
-        const u64 key = a.keys[i];
-        if (key == HNY_OP_INVALID || (key >> HNY_SEQ_BITS) != k0) break;
-        nops++;
-        if (cnt + (int)nops > (int)cap) break;
-      }
-      if (cnt + (int)nops > (int)cap) {
-        if (ln == 0) a.deferred[atomicAdd(a.n_deferred, 1u)] = i0;
-        continue;
-      }
-    }
-    for (int e = ln; e < cnt; e += 64) lk[e] = ((u64)fbits(dist[e]) << 32) | ids[e];
-    WSYNC();
-    for (u32 i = i0; i < a.n_ops; i++) {
-      const u64 key = a.keys[i];
-      if (key == HNY_OP_INVALID || (key >> HNY_SEQ_BITS) != k0) break;
-      const u64 val = a.vals[i];
-      if ((u32)(val & 0xFFFFFFFFull) == target) continue; // :530 p == q.1
-      if (cnt < (int)cap) {                               // :542-545 append, no dedup
-        if (ln == 0) lk[cnt] = val;
-        cnt++;
-        WSYNC();
-      } else if (!frozen) { // :547-552 full: self-prune, the new link is dropped
-        for (int e = ln; e < cnt; e += 64) { // stable rank sort by (distance bits, slot), ties in list order
-          const u64 mine = lk[e];
-          int rk = 0;
-          for (int j = 0; j < cnt; j++) {
-            const u64 o = lk[j];
-            rk += (o < mine || (o == mine && j < e)) ? 1 : 0;
-          }
-          sorted[rk] = mine;
-        }
-        WSYNC();
-        int s_len = wave_prune<LPR, NCH>(g, sorted, cnt, (int)cap, S, s_ids, tmp_d, evals);
-        for (int e = ln; e < s_len; e += 64) lk[e] = S[e];
-        cnt = s_len;
-        // a full list that prunes to itself can never change again: every later add_link would
-        // redo the same prune with the same outcome
-        frozen = (s_len == (int)cap);
-        WSYNC();
-      }
-    }
-    for (u32 e = (u32)ln; e < cap; e += 64) {
-      const bool on = (int)e < cnt;
-      ids[e] = on ? (u32)(lk[e] & 0xFFFFFFFFull) : HNY_SENT;
-      dist[e] = on ? __uint_as_float((u32)(lk[e] >> 32)) : 0.f;
-    }
-    if (ln == 0) *cntp = (u32)cnt | (frozen ? 0x80000000u : 0u);
+    replay_add_link<64, false>(g, a, a.seg_start[sg], lk, sorted, S, nullptr,
+                        [&](u64 *list, int n, int cap) __attribute__((always_inline)) {
+                          return wave_prune<LPR, NCH>(g, list, n, cap, S, s_ids, tmp_d, evals);
+                        });
     WSYNC();
   }
-  if (ln == 0 && evals) atomicAdd(&g.stats[ST_EVALS_APPLY], evals);
+  if (threadIdx.x == 0 && evals) atomicAdd(&g.stats[ST_EVALS_APPLY], evals);
 }
 
-// add_link for the segments k_apply deferred (their list overflows): 256 threads per segment, the
+// add_link for the segments k_apply_append deferred (their list overflows): 256 threads per segment, the
 // self-prune runs on the LDS-staged wg_prune.
 template <int LPR, int NCH, int SP>
 __global__ __launch_bounds__(256, wg_waves_per_simd(NCH, 4)) void k_apply_wg(GraphDev g_in, ApplyArgs a, int SL) {
@@ -3759,121 +3747,30 @@ __global__ __launch_bounds__(256, wg_waves_per_simd(NCH, 4)) void k_apply_wg(Gra
   u64 *lk = reinterpret_cast<u64 *>(smem);          // [capmax] the node's list
   u64 *sorted = lk + capmax;                        // [capmax]
   WgPruneLds L = wg_prune_carve(smem + (size_t)2 * capmax * 8, SL, g.row_stride, 4, capmax);
-  const int tid = threadIdx.x;
   const u32 n_def = *a.n_deferred;
   u64 evals = 0;
   const u32 sw = a.shard_world ? a.shard_world : 1u;
   for (u32 di = a.shard_rank + blockIdx.x * sw; di < n_def; di += gridDim.x * sw) {
-    const u32 i0 = a.deferred[di];
-    const u64 k0 = a.keys[i0] >> HNY_SEQ_BITS;
-    const u32 target = (u32)(k0 & 0x7FFFFFFFull), layer = (u32)(k0 >> 31);
-    u32 cap, *ids, *cntp;
-    float *dist;
-    if (layer == 0) {
-      cap = g.M0;
-      ids = g.l0_ids + (size_t)target * g.M0;
-      dist = g.l0_dist + (size_t)target * g.M0;
-      cntp = g.l0_cnt + target;
-    } else {
-      size_t u = (size_t)g.upper_idx[target] * g.up_layers + (layer - 1);
-      cap = g.M;
-      ids = g.up_ids + u * g.M;
-      dist = g.up_dist + u * g.M;
-      cntp = g.up_cnt + u;
-    }
-    const u32 cw = *cntp;
-    int cnt = (int)(cw & 0xFFFFu);
-    bool frozen = (cw >> 31) != 0u;
-    for (int e = tid; e < cnt; e += 256) lk[e] = ((u64)fbits(dist[e]) << 32) | ids[e];
-    __syncthreads();
-    for (u32 i = i0; i < a.n_ops && !frozen; i++) {
-      const u64 key = a.keys[i];
-      if (key == HNY_OP_INVALID || (key >> HNY_SEQ_BITS) != k0) break;
-      const u64 val = a.vals[i];
-      if ((u32)(val & 0xFFFFFFFFull) == target) continue; // hnsw.rs:530
-      if (cnt < (int)cap) {                               // :542-545
-        if (tid == 0) lk[cnt] = val;
-        cnt++;
-        __syncthreads();
-      } else { // :547-552
-        for (int e = tid; e < cnt; e += 256) { // (cnt <= 256: one entry per thread)
-          const u64 mine = lk[e];
-          int rk = 0;
-          for (int j = 0; j < cnt; j++) {
-            u64 o = lk[j];
-            rk += (o < mine || (o == mine && j < e)) ? 1 : 0;
-          }
-          sorted[rk] = mine;
-        }
-        __syncthreads();
-        int s_len;
-        if (SP != 0 && g.n16 == (u32)(LPR * NCH) && g.row_stride == (u32)(LPR * NCH * 16)) { // full rows: see k_prune_wg
-          GraphDev gf = g;
-          gf.n16 = (u32)(LPR * NCH);
-          gf.row_stride = (u32)(LPR * NCH * 16);
-          s_len = wg_prune<LPR, NCH, 4>(gf, sorted, cnt, (int)cap, L, evals);
-        } else {
-          s_len = wg_prune<LPR, NCH, 4>(g, sorted, cnt, (int)cap, L, evals);
-        }
-        for (int e = tid; e < s_len; e += 256) lk[e] = L.S[e];
-        cnt = s_len;
-        frozen = (s_len == (int)cap);
-        __syncthreads();
-      }
-    }
-    for (u32 e = (u32)tid; e < cap; e += 256u) {
-      const bool on = (int)e < cnt;
-      ids[e] = on ? (u32)(lk[e] & 0xFFFFFFFFull) : HNY_SENT;
-      dist[e] = on ? __uint_as_float((u32)(lk[e] >> 32)) : 0.f;
-    }
-    if (tid == 0) *cntp = (u32)cnt | (frozen ? 0x80000000u : 0u);
-    if (a.exch) { // the finished list, for the ranks that did not compute it
-      u64 *rec = a.exch + (size_t)(di / sw) * a.exch_stride;
-      if (tid == 0) {
-        rec[0] = k0;
-        rec[1] = (u64)((u32)cnt | (frozen ? 0x80000000u : 0u));
-      }
-      for (int e = tid; e < cnt; e += 256) rec[2 + e] = lk[e];
-    }
+    replay_add_link<256, false>(g, a, a.deferred[di], lk, sorted, L.S, exch_rec(a, di, sw),
+                         [&](u64 *list, int n, int cap) __attribute__((always_inline)) {
+                           return wg_prune_sp<LPR, NCH, 4, SP>(g, list, n, cap, L, evals);
+                         });
     __syncthreads();
   }
-  if ((tid & 63) == 0 && evals) atomicAdd(&g.stats[ST_EVALS_APPLY], evals);
+  if ((threadIdx.x & 63) == 0 && evals) atomicAdd(&g.stats[ST_EVALS_APPLY], evals);
 }
 
-// multi-GPU: the lists other ranks finished in their share of the deferred segments (k_apply_wg's
-// exch records, all-gathered) written into this rank's replica.  One wave per record.
+// multi-GPU: the lists other ranks finished in their share of the deferred segments (the exchange records of
+// replay_add_link, all-gathered) written into this rank's replica.  One wave per record.
 __global__ __launch_bounds__(64) void k_apply_merge(GraphDev g, const u64 *exch, u32 n_def, u32 world, u32 rank,
                                                     u32 per, u32 stride) {
-  const int ln = threadIdx.x;
   for (u32 di = blockIdx.x; di < n_def; di += gridDim.x) {
     const u32 owner = di % world;
     if (owner == rank) continue;
     const u64 *rec = exch + ((size_t)owner * per + di / world) * stride;
     const u64 k0 = rec[0];
-    const u32 target = (u32)(k0 & 0x7FFFFFFFull), layer = (u32)(k0 >> 31);
     const u32 cw = (u32)rec[1];
-    const int cnt = (int)(cw & 0xFFFFu);
-    u32 cap, *ids, *cntp;
-    float *dist;
-    if (layer == 0) {
-      cap = g.M0;
-      ids = g.l0_ids + (size_t)target * g.M0;
-      dist = g.l0_dist + (size_t)target * g.M0;
-      cntp = g.l0_cnt + target;
-    } else {
-      size_t u = (size_t)g.upper_idx[target] * g.up_layers + (layer - 1);
-      cap = g.M;
-      ids = g.up_ids + u * g.M;
-      dist = g.up_dist + u * g.M;
-      cntp = g.up_cnt + u;
-    }
-    for (u32 e0 = (u32)ln; e0 < cap; e0 += 64u) {
-      const bool on = (int)e0 < cnt;
-      const u64 e = on ? rec[2 + e0] : 0ull;
-      ids[e0] = on ? (u32)(e & 0xFFFFFFFFull) : HNY_SENT;
-      dist[e0] = on ? __uint_as_float((u32)(e >> 32)) : 0.f;
-    }
-    if (ln == 0) *cntp = cw;
+    store_list<64>(node_list(g, (u32)(k0 >> 31), (u32)(k0 & 0x7FFFFFFFull)), rec + 2, (int)(cw & 0xFFFFu), cw);
   }
 }
 
@@ -3884,6 +3781,22 @@ __global__ __launch_bounds__(64) void k_apply_merge(GraphDev g, const u64 *exch,
 // Scratch: own old links + the old links of every deleted old neighbour = at most cap * (cap + 1)
 // ids (1 056 at M0 = 32, 4 160 at M0 = 64) — a mass deletion reaches that — so the LDS arrays are
 // sized for the worst case by the launcher (`maxu`), never for a typical one.
+// The list when bm and the old list fit together (:391-400): bm ascending at distance 0.0 ("no longer
+// relevant"), then the old list: old(e) is the key of old entry e, read before the list is overwritten.
+// The caller syncs.
+template <int NT, bool ONE, class Old>
+__device__ __forceinline__ void store_gaps_fit(const NodeList &l, const u32 *bm, int nb, int cnt, Old old) {
+  each<NT, ONE>(nb, [&](int e) __attribute__((always_inline)) {
+    l.ids[e] = bm[e];
+    l.dist[e] = 0.f;
+  });
+  each<NT, ONE>(cnt, [&](int e) __attribute__((always_inline)) {
+    const u64 k = old(e);
+    l.ids[nb + e] = (u32)(k & 0xFFFFFFFFull);
+    l.dist[nb + e] = __uint_as_float((u32)(k >> 32));
+  });
+  if (threadIdx.x == 0) *l.cnt = (u32)(nb + cnt);
+}
 __host__ __device__ inline size_t fill_gaps_lds_bytes(u32 maxu) {
   return (size_t)maxu * 4 * 2 + (size_t)(maxu + HNY_MAX_CAP) * 8 * 2 + HNY_MAX_CAP * (8 + 4) + 64 * 4;
 }
@@ -3891,7 +3804,7 @@ template <int LPR, int NCH>
 __global__ __launch_bounds__(64) void k_fill_gaps(GraphDev g, const u64 *recs, u32 n_recs,
                                                   const unsigned char *deleted, u32 maxu) {
   extern __shared__ __align__(16) unsigned char smem[];
-  u64 *keys = reinterpret_cast<u64 *>(smem);            // [maxu + HNY_MAX_CAP]
+  u64 *keys = reinterpret_cast<u64 *>(smem);            // [maxu + HNY_MAX_CAP] the old list, then the scored bm
   u64 *sorted = keys + (maxu + HNY_MAX_CAP);            // [maxu + HNY_MAX_CAP]
   u64 *S = sorted + (maxu + HNY_MAX_CAP);               // [HNY_MAX_CAP]
   u32 *cand = reinterpret_cast<u32 *>(S + HNY_MAX_CAP); // [maxu]
@@ -3905,21 +3818,9 @@ __global__ __launch_bounds__(64) void k_fill_gaps(GraphDev g, const u64 *recs, u
   for (u32 ri = blockIdx.x; ri < n_recs; ri += gridDim.x) {
     const u64 rec = recs[ri];
     const u32 layer = (u32)(rec >> 31), slot = (u32)(rec & 0x7FFFFFFFull);
-    u32 cap, dcap, *ids, *cntp;
-    float *dist;
-    if (layer == 0) {
-      cap = g.M0;
-      ids = g.l0_ids + (size_t)slot * g.M0;
-      dist = g.l0_dist + (size_t)slot * g.M0;
-      cntp = g.l0_cnt + slot;
-    } else {
-      size_t u = (size_t)g.upper_idx[slot] * g.up_layers + (layer - 1);
-      cap = g.M;
-      ids = g.up_ids + u * g.M;
-      dist = g.up_dist + u * g.M;
-      cntp = g.up_cnt + u;
-    }
-    const int cnt = (int)(*cntp & 0xFFFFu);
+    const NodeList l = node_list(g, layer, slot);
+    const int cnt = (int)(*l.cnt & 0xFFFFu);
+    u32 dcap;
     const u32 *dl = disk_ids(g, layer, slot, dcap);
     // ---- gather: own old links + the old links of deleted old neighbours
     int nu = 0;
@@ -3970,19 +3871,11 @@ __global__ __launch_bounds__(64) void k_fill_gaps(GraphDev g, const u64 *recs, u
       nb += __popcll(ballot(kept));
     }
     WSYNC();
-    const u32 oi = ln < cnt ? ids[ln] : HNY_SENT;
-    const float od = ln < cnt ? dist[ln] : 0.f;
-    if (nb + cnt <= (int)cap) { // :391-400 distances are "no longer relevant": 0.0
+    // this lane's old entry (lists of at most 64 slots: one per lane), read before the list is rewritten
+    const u64 ok = ln < cnt ? ((u64)fbits(l.dist[ln]) << 32) | l.ids[ln] : (u64)HNY_SENT;
+    if (nb + cnt <= (int)l.cap) {
       WSYNC();
-      if (ln < nb) {
-        ids[ln] = bm[ln];
-        dist[ln] = 0.f;
-      }
-      if (ln < cnt) {
-        ids[nb + ln] = oi;
-        dist[nb + ln] = od;
-      }
-      if (ln == 0) *cntp = (u32)(nb + cnt);
+      store_gaps_fit<64, true>(l, bm, nb, cnt, [&](int) { return ok; });
       WSYNC();
       continue;
     }
@@ -3990,7 +3883,7 @@ __global__ __launch_bounds__(64) void k_fill_gaps(GraphDev g, const u64 *recs, u
     float4 q[NCH];
     load_row<LPR, NCH>(g.rows + (size_t)slot * g.row_stride, t, g.n16, q);
     const float qn = g.norms ? g.norms[slot] : 0.f;
-    if (ln < cnt) keys[ln] = ((u64)fbits(od) << 32) | oi;
+    if (ln < cnt) keys[ln] = ok;
     for (int base = 0; base < nb; base += 64) {
       const int c = nb - base < 64 ? nb - base : 64;
       dist_rows<LPR, NCH>(g, q, qn, bm + base, c, tmp_d, g.rows + (size_t)slot * g.row_stride);
@@ -4000,23 +3893,10 @@ __global__ __launch_bounds__(64) void k_fill_gaps(GraphDev g, const u64 *recs, u
       WSYNC();
     }
     const int n = cnt + nb;
-    for (int e = ln; e < n; e += 64) {
-      const u64 mine = keys[e];
-      int rk = 0;
-      for (int k2 = 0; k2 < n; k2++) {
-        const u64 o = keys[k2];
-        rk += (o < mine || (o == mine && k2 < e)) ? 1 : 0;
-      }
-      sorted[rk] = mine;
-    }
+    rank_sort<64>(keys, n, sorted);
     WSYNC();
-    const int s_len = wave_prune<LPR, NCH>(g, sorted, n, (int)cap, S, s_ids, tmp_d, evals);
-    if ((u32)ln < cap) {
-      const bool on = ln < s_len;
-      ids[ln] = on ? (u32)(S[ln] & 0xFFFFFFFFull) : HNY_SENT;
-      dist[ln] = on ? __uint_as_float((u32)(S[ln] >> 32)) : 0.f;
-    }
-    if (ln == 0) *cntp = (u32)s_len;
+    const int s_len = wave_prune<LPR, NCH>(g, sorted, n, (int)l.cap, S, s_ids, tmp_d, evals);
+    store_list<64, true>(l, S, s_len, (u32)s_len);
     WSYNC();
   }
   if (ln == 0) {
@@ -4043,9 +3923,8 @@ __global__ __launch_bounds__(256) void k_fill_gaps_wg(GraphDev g, const u64 *rec
                                                       int SL) {
   extern __shared__ __align__(16) unsigned char smem[];
   const u32 capmax = wg_capmax(g);
-  u32 *nl_ids = reinterpret_cast<u32 *>(smem);                 // [capmax] the record's in-memory list
-  float *nl_d = reinterpret_cast<float *>(nl_ids + capmax);    // [capmax]
-  u32 *wsc = reinterpret_cast<u32 *>(nl_d + capmax);           // [64] ids of a distance pass (+ slack)
+  u64 *nl = reinterpret_cast<u64 *>(smem);                     // [capmax] the record's in-memory list (keys)
+  u32 *wsc = reinterpret_cast<u32 *>(nl + capmax);             // [64] ids of a distance pass (+ slack)
   float *wsd = reinterpret_cast<float *>(wsc + 256);           // [64]
   int *misc = reinterpret_cast<int *>(wsd + 256);              // [0] first / [1] last touched word, [2..5] wave sums
   WgPruneLds L = wg_prune_carve(reinterpret_cast<unsigned char *>(misc + 16), SL, g.row_stride, 4, capmax);
@@ -4058,31 +3937,16 @@ __global__ __launch_bounds__(256) void k_fill_gaps_wg(GraphDev g, const u64 *rec
   for (u32 ri = blockIdx.x; ri < n_recs; ri += gridDim.x) {
     const u64 rec = recs[ri];
     const u32 layer = (u32)(rec >> 31), slot = (u32)(rec & 0x7FFFFFFFull);
-    u32 cap, dcap, *ids, *cntp;
-    float *dist;
-    if (layer == 0) {
-      cap = g.M0;
-      ids = g.l0_ids + (size_t)slot * g.M0;
-      dist = g.l0_dist + (size_t)slot * g.M0;
-      cntp = g.l0_cnt + slot;
-    } else {
-      size_t u = (size_t)g.upper_idx[slot] * g.up_layers + (layer - 1);
-      cap = g.M;
-      ids = g.up_ids + u * g.M;
-      dist = g.up_dist + u * g.M;
-      cntp = g.up_cnt + u;
-    }
-    const int cnt = (int)(*cntp & 0xFFFFu);
-    for (int e = tid; e < cnt; e += 256) {
-      nl_ids[e] = ids[e];
-      nl_d[e] = dist[e];
-    }
+    const NodeList l = node_list(g, layer, slot);
+    const int cnt = (int)(*l.cnt & 0xFFFFu);
+    for (int e = tid; e < cnt; e += 256) nl[e] = ((u64)fbits(l.dist[e]) << 32) | l.ids[e];
     if (tid == 0) {
       misc[0] = 0x7FFFFFFF;
       misc[1] = -1;
     }
     __syncthreads();
     // ---- gather (:382-388): own old links + the old links of deleted old neighbours, minus deleted
+    u32 dcap;
     const u32 *dl = disk_ids(g, layer, slot, dcap);
     auto mark = [&](u32 y) {
       if (y != HNY_SENT && deleted[y] == 0) {
@@ -4135,16 +3999,8 @@ __global__ __launch_bounds__(256) void k_fill_gaps_wg(GraphDev g, const u64 *rec
     }
     if ((u32)nb > maxb) nb = (int)maxb; // cannot happen: maxb = min(slots, cap * (cap + 1))
     __syncthreads();
-    if (nb + cnt <= (int)cap) { // :391-400 distances are "no longer relevant": 0.0
-      for (int e = tid; e < nb; e += 256) {
-        ids[e] = bm[e];
-        dist[e] = 0.f;
-      }
-      for (int e = tid; e < cnt; e += 256) {
-        ids[nb + e] = nl_ids[e];
-        dist[nb + e] = nl_d[e];
-      }
-      if (tid == 0) *cntp = (u32)(nb + cnt);
+    if (nb + cnt <= (int)l.cap) {
+      store_gaps_fit<256, false>(l, bm, nb, cnt, [&](int e) { return nl[e]; });
       __syncthreads();
       continue;
     }
@@ -4154,7 +4010,7 @@ __global__ __launch_bounds__(256) void k_fill_gaps_wg(GraphDev g, const u64 *rec
       float4 q[NCH];
       load_row<LPR, NCH>(qrow, t, g.n16, q);
       const float qn = g.norms ? g.norms[slot] : 0.f;
-      for (int e = tid; e < cnt; e += 256) keys[e] = ((u64)fbits(nl_d[e]) << 32) | nl_ids[e];
+      for (int e = tid; e < cnt; e += 256) keys[e] = nl[e];
       // (dist_rows takes its lane from threadIdx.x: a one-wave routine, so wave 0 scores the set)
       u32 *my_ids = wsc;
       float *my_d = wsd;
@@ -4172,36 +4028,23 @@ __global__ __launch_bounds__(256) void k_fill_gaps_wg(GraphDev g, const u64 *rec
     }
     __syncthreads();
     const int n = cnt + nb;
-    for (int e = tid; e < n; e += 256) {
-      const u64 mine = keys[e];
-      int rk = 0;
-      for (int k2 = 0; k2 < n; k2++) {
-        const u64 o = keys[k2];
-        rk += (o < mine || (o == mine && k2 < e)) ? 1 : 0;
-      }
-      sorted[rk] = mine;
-    }
+    rank_sort<256>(keys, n, sorted);
     __syncthreads();
     int s_len;
     if (g.x86_order) {
       // strict mode: wg_prune carries its own wave-order arithmetic, so wave 0 runs the one-wave prune (dist_rows ->
       // the reference's x86 summation order, lists taken 64 slots at a time) on the workgroup's arrays
       if (w == 0) {
-        const int sl = wave_prune<LPR, NCH>(g, sorted, n, (int)cap, L.S, L.s_ids, wsd, evals);
+        const int sl = wave_prune<LPR, NCH>(g, sorted, n, (int)l.cap, L.S, L.s_ids, wsd, evals);
         if (ln == 0) misc[6] = sl;
       }
       __syncthreads();
       s_len = misc[6];
     } else {
-      s_len = wg_prune<LPR, NCH, 4>(g, sorted, n, (int)cap, L, evals);
+      s_len = wg_prune<LPR, NCH, 4>(g, sorted, n, (int)l.cap, L, evals);
     }
     __syncthreads();
-    for (u32 e = (u32)tid; e < cap; e += 256u) {
-      const bool on = (int)e < s_len;
-      ids[e] = on ? (u32)(L.S[e] & 0xFFFFFFFFull) : HNY_SENT;
-      dist[e] = on ? __uint_as_float((u32)(L.S[e] >> 32)) : 0.f;
-    }
-    if (tid == 0) *cntp = (u32)s_len;
+    store_list<256, false>(l, L.S, s_len, (u32)s_len);
     __syncthreads();
   }
   if ((tid & 63) == 0 && evals) atomicAdd(&g.stats[ST_EVALS_APPLY], evals);
@@ -4486,9 +4329,13 @@ struct Hot {
   template <int L, int C>
   struct Apply {
     static hipError_t run(const GraphDev &g, const ApplyArgs &a, int grid, hipStream_t st) {
-      const size_t lds = (size_t)wave_capmax(g) * (8 + 8 + 8 + 4) + 64 * 4;
-      hipLaunchKernelGGL((k_apply<L, C, SP>), dim3(grid), dim3(64), lds, st, g, a);
-      return hipGetLastError();
+      if constexpr (SP != 0 && C <= 8) {
+        return hipErrorInvalidValue; // plain builds take k_apply only for rows beyond 8 KB (strict mode: SP = 0)
+      } else {
+        const size_t lds = (size_t)wave_capmax(g) * (8 + 8 + 8 + 4) + 64 * 4;
+        hipLaunchKernelGGL((k_apply<L, C, SP>), dim3(grid), dim3(64), lds, st, g, a);
+        return hipGetLastError();
+      }
     }
   };
 };
