@@ -34,6 +34,8 @@ EXPORTED = [
     "hny_multi_builder_create", "hny_multi_builder_run", "hny_multi_builder_set_profiling",
     "hny_multi_builder_world", "hny_multi_builder_collectives", "hny_multi_builder_replica",
     "hny_multi_builder_destroy", "hny_abi_sizes", "hny_set_graph_cache",
+    "hny_build_f32", "hny_build_incremental_f32", "hny_builder_create_f32", "hny_builder_load_f32",
+    "hny_builder_export_items", "hny_builder_search_knn_f32", "hny_builder_nns_f32",
 ]
 ERR_IO = -9
 NNS_NONE = 0xFFFFFFFF  # by_item: the reference returns None
@@ -234,6 +236,16 @@ def load_library():
     L.hny_multi_builder_replica.restype = vp
     L.hny_multi_builder_replica.argtypes = [vp, C.c_uint32]
     L.hny_multi_builder_destroy.argtypes = [vp]
+    for name, base in (("hny_build_f32", "hny_build"), ("hny_build_incremental_f32", "hny_build_incremental"),
+                       ("hny_builder_create_f32", "hny_builder_create"), ("hny_builder_load_f32", "hny_builder_load")):
+        getattr(L, name).restype = C.c_int
+        getattr(L, name).argtypes = getattr(L, base).argtypes
+    L.hny_builder_export_items.restype = C.c_int
+    L.hny_builder_export_items.argtypes = [vp, vp, vp]
+    L.hny_builder_search_knn_f32.restype = C.c_int
+    L.hny_builder_search_knn_f32.argtypes = [vp, C.c_uint64, vp, C.c_size_t, C.c_uint32, C.c_uint32, vp, vp, vp]
+    L.hny_builder_nns_f32.restype = C.c_int
+    L.hny_builder_nns_f32.argtypes = [vp, C.POINTER(QueryOpts), C.c_uint64, vp, C.c_size_t, vp, vp, vp]
     L.hny_abi_sizes.restype = C.c_uint32
     L.hny_abi_sizes.argtypes = [C.POINTER(C.c_uint32), C.c_uint32]
     _check_abi(L)
@@ -381,8 +393,16 @@ class ItemSet:
         self.levels = None if levels is None else np.ascontiguousarray(levels, dtype=np.uint8)
         self.n = len(self.ids)
 
+    f32 = False  # codec bytes + headers (F32ItemSet: f32 rows, encoded on the device)
+
+    def encoded(self):
+        return self
+
     @classmethod
-    def from_f32(cls, metric, vecs, ids=None, levels=None):
+    def from_f32(cls, metric, vecs, ids=None, levels=None, device=False):
+        """device=True: keep the f32 matrix and let the device encode it while it is uploaded (F32ItemSet)"""
+        if device:
+            return F32ItemSet(metric, vecs, ids, levels)
         vecs = np.ascontiguousarray(vecs, dtype=np.float32)
         codes, headers = encode_vectors(metric, vecs)
         ids = np.arange(len(vecs), dtype=np.uint32) if ids is None else ids
@@ -393,6 +413,51 @@ class ItemSet:
                      self.codes.shape[1] if self.codes.ndim == 2 else 0, _p(self.headers).value,
                      self.headers.shape[1] if self.headers.ndim == 2 else 0,
                      None if self.levels is None else _p(self.levels).value)
+
+
+def _f32_rows(a):
+    """a [n, dim] f32 matrix whose rows are contiguous (the row stride may be larger than dim * 4)"""
+    a = np.asarray(a, dtype=np.float32)
+    if a.ndim != 2:
+        raise ValueError("expected a [n, dim] matrix")
+    if a.shape[1] > 1 and a.strides[1] != 4 or a.shape[0] > 1 and a.strides[0] < a.shape[1] * 4:
+        a = np.ascontiguousarray(a)
+    return a
+
+
+class F32ItemSet:
+    """The items as the f32 vectors Writer::add_item takes (src/writer.rs:462-480): build(),
+    build_incremental() and Builder hand them to the hny_*_f32 entry points, which encode them on the device
+    while they are uploaded.  Codes and headers exist on the host only once something asks for them
+    (Graph.encode_kv(with_items=True)): encoded() runs hny_encode_vectors then."""
+    f32 = True
+
+    def __init__(self, metric, vecs, ids=None, levels=None):
+        self.vecs = _f32_rows(vecs)
+        self.metric, self.dim = int(metric), int(self.vecs.shape[1])
+        self.n = len(self.vecs)
+        self.ids = np.ascontiguousarray(np.arange(self.n) if ids is None else ids, dtype=np.uint32)
+        self.levels = None if levels is None else np.ascontiguousarray(levels, dtype=np.uint8)
+        self._encoded = None
+
+    def struct(self):
+        stride = self.vecs.strides[0] if self.n > 1 else self.dim * 4
+        return Items(self.n, _p(self.ids).value, _p(self.vecs).value, stride, None, 0,
+                     None if self.levels is None else _p(self.levels).value)
+
+    def encoded(self):
+        if self._encoded is None:
+            codes, headers = encode_vectors(self.metric, self.vecs)
+            self._encoded = ItemSet(self.metric, self.dim, self.ids, codes, headers, self.levels)
+        return self._encoded
+
+    @property
+    def codes(self):
+        return self.encoded().codes
+
+    @property
+    def headers(self):
+        return self.encoded().headers
 
 
 def make_opts(metric, dim, M=16, M0=32, ef_construction=100, alpha=1.0, seed=42, batch_frac=0.0,
@@ -481,7 +546,7 @@ class Graph:
             out.append((bytes(k[:kl]), bytes(v[:vl])))
             return 0
         cb = KV_SINK(sink)
-        it = self._items.struct()
+        it = self._items.encoded().struct()  # an F32ItemSet encodes on the host here, once
         _check(load_library().hny_encode_kv(self._gp, C.byref(self._opts), C.byref(it), index,
                                             int(with_items), cb, None))
         return out
@@ -491,7 +556,7 @@ class Graph:
         hny_lmdb_writer_put as its sink (no Python in the record loop)."""
         L = load_library()
         w = LmdbWriter(path, name, page_size, map_size)
-        it = self._items.struct()
+        it = self._items.encoded().struct()
         sink = C.cast(L.hny_lmdb_writer_put, KV_SINK)
         try:
             _check(L.hny_encode_kv(self._gp, C.byref(self._opts), C.byref(it), index, int(with_items), sink, w.handle))
@@ -589,7 +654,8 @@ def build(items, **kw):
     o = make_opts(items.metric, items.dim, **kw)
     it = items.struct()
     gp = C.POINTER(GraphStruct)()
-    _check(load_library().hny_build(C.byref(o), C.byref(it), C.byref(gp)))
+    L = load_library()
+    _check((L.hny_build_f32 if items.f32 else L.hny_build)(C.byref(o), C.byref(it), C.byref(gp)))
     return Graph(gp, o, items)
 
 
@@ -618,8 +684,9 @@ def build_incremental(items, prev, to_insert, to_delete, **kw):
     pg = PrevGraph(len(keep[0]), _p(keep[0]).value, _p(keep[1]).value, _p(keep[2]).value,
                    _p(keep[3]).value, _p(keep[4]).value, len(keep[4]), int(prev.max_level))
     gp = C.POINTER(GraphStruct)()
-    _check(load_library().hny_build_incremental(C.byref(o), C.byref(it), _p(ins), len(ins), _p(dl),
-                                                len(dl), C.byref(pg), C.byref(gp)))
+    L = load_library()
+    _check((L.hny_build_incremental_f32 if items.f32 else L.hny_build_incremental)(
+        C.byref(o), C.byref(it), _p(ins), len(ins), _p(dl), len(dl), C.byref(pg), C.byref(gp)))
     return Graph(gp, o, items)
 
 
@@ -697,12 +764,16 @@ class Builder:
         self._h = C.c_void_p()
         self.incremental = prev is not None
         it = items.struct()
+        L, f32 = load_library(), items.f32
         if prev is None:
-            _check(load_library().hny_builder_create(C.byref(self.opts), C.byref(it), C.byref(self._h)))
+            _check((L.hny_builder_create_f32 if f32 else L.hny_builder_create)(C.byref(self.opts), C.byref(it), C.byref(self._h)))
         elif load:
             pg, _keep = _prev_struct(prev)
-            _check(load_library().hny_builder_load(C.byref(self.opts), C.byref(it), C.byref(pg), C.byref(self._h)))
+            _check((L.hny_builder_load_f32 if f32 else L.hny_builder_load)(C.byref(self.opts), C.byref(it), C.byref(pg), C.byref(self._h)))
         else:
+            if f32:
+                raise HannoyError(ERR_UNSUPPORTED, "a stepwise incremental builder takes codec bytes: use build_incremental() "
+                                                   "for f32 items")
             ins = np.ascontiguousarray(to_insert, np.uint32)
             dl = np.ascontiguousarray(to_delete, np.uint32)
             pg, _keep = _prev_struct(prev)
@@ -813,8 +884,32 @@ class Builder:
                                                      _p(dists), _p(counts)))
         return ids, dists, counts
 
+    def export_items(self):
+        """hny_builder_export_items: (codes [n, vector_bytes], headers [n, header_bytes]) of the builder's items in
+        ascending id order, read back from HBM"""
+        n = self.items.n
+        codes = np.zeros((n, vector_bytes(self.items.metric, self.items.dim)), np.uint8)
+        headers = np.zeros((n, header_bytes(self.items.metric)), np.uint8)
+        _check(load_library().hny_builder_export_items(self._h, _p(codes), _p(headers)))
+        return codes, headers
+
+    def search_knn_f32(self, queries, k=10, ef_search=100):
+        """search_knn with the &[f32] queries the reference takes, encoded on the device"""
+        q = _f32_rows(queries)
+        nq = q.shape[0]
+        ids = np.zeros((nq, k), np.uint32)
+        dists = np.zeros((nq, k), np.float32)
+        counts = np.zeros(nq, np.uint32)
+        _check(load_library().hny_builder_search_knn_f32(self._h, nq, _p(q), q.strides[0] if nq > 1 else q.shape[1] * 4,
+                                                         k, ef_search, _p(ids), _p(dists), _p(counts)))
+        return ids, dists, counts
+
+    def nns_f32(self, queries, **kw):
+        """nns(by_vector) with f32 queries, encoded on the device"""
+        return self.nns(qf32=_f32_rows(queries), **kw)
+
     def nns(self, qcodes=None, qheaders=None, k=10, ef_search=100, candidates=None, query_items=None,
-            linear_below=1000, linear_below_ratio=1.0, cancel=None):
+            linear_below=1000, linear_below_ratio=1.0, cancel=None, qf32=None):
         """Reader::nns(k).ef_search(..).candidates(..).linear_below(..).by_vector / .by_item
         (/root/reference/src/reader.rs:60-262).  counts == NNS_NONE where by_item returns None.
         cancel: the closure of the *_with_cancellation variants; self.did_cancel tells whether it fired."""
@@ -834,6 +929,9 @@ class Builder:
         if query_items is not None:
             query_items = np.ascontiguousarray(query_items, np.uint32)
             nq, qc, qs, qh, qi = len(query_items), None, 0, None, _p(query_items)
+        elif qf32 is not None:
+            nq, qc, qh, qi = qf32.shape[0], _p(qf32), None, None
+            qs = qf32.strides[0] if nq > 1 else qf32.shape[1] * 4
         else:
             qcodes = np.ascontiguousarray(qcodes, np.uint8)
             qheaders = np.ascontiguousarray(qheaders, np.uint8)
@@ -841,7 +939,10 @@ class Builder:
         ids = np.zeros((nq, k), np.uint32)
         dists = np.zeros((nq, k), np.float32)
         counts = np.zeros(nq, np.uint32)
-        _check(load_library().hny_builder_nns(self._h, C.byref(qo), nq, qc, qs, qh, qi, _p(ids), _p(dists),
-                                              _p(counts)))
+        if qf32 is not None:
+            _check(load_library().hny_builder_nns_f32(self._h, C.byref(qo), nq, qc, qs, _p(ids), _p(dists), _p(counts)))
+        else:
+            _check(load_library().hny_builder_nns(self._h, C.byref(qo), nq, qc, qs, qh, qi, _p(ids), _p(dists),
+                                                  _p(counts)))
         self.did_cancel = bool(flag.value)
         return ids, dists, counts

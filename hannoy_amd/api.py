@@ -450,8 +450,7 @@ class QueryBuilder:
         q = np.ascontiguousarray(vectors, np.float32)
         if q.ndim != 2 or q.shape[1] != r.dimensions:
             raise InvalidVecDimension(f"expected {r.dimensions}, received {q.shape[-1]}")
-        qc, qh = capi.encode_vectors(r.db.distance.value, q)
-        return r._b.nns(qc, qh, cancel=cancel, **self._kw())
+        return r._b.nns_f32(q, cancel=cancel, **self._kw())  # encoded on the device
 
     def by_items(self, items, cancel=None):
         """batched by_item; counts == capi.NNS_NONE where the reference returns None"""
@@ -565,8 +564,7 @@ class Reader:
         return [(int(ids[0, j]), float(dists[0, j])) for j in range(counts[0])]
 
     def by_vecs(self, queries, n=10, ef_search=200):
-        qc, qh = capi.encode_vectors(self.db.distance.value, np.asarray(queries, np.float32))
-        return self._b.search_knn(qc, qh, k=n, ef_search=ef_search)
+        return self._b.search_knn_f32(np.asarray(queries, np.float32), k=n, ef_search=ef_search)
 
     def close(self):
         self._b.close()

@@ -233,6 +233,73 @@ struct DevBuf {
   ~DevBuf() { release(); }
 };
 
+// ---- f32 ingest: host rows -> pinned staging -> device staging -> k_ingest, double buffered.  While chunk i is
+// encoded on the consumer's stream, chunk i+1 is copied into pinned memory by the host (pageable input is the
+// normal case, so that copy is part of the pipeline) and sent on the pipe's own stream; events order the two. ----
+struct IngestPipe {
+  // bytes per staging buffer (two pinned + two on the device).  A tuning constant: large enough that a chunk's
+  // launch and event overheads vanish, small enough that the first chunk's unoverlapped host copy stays short.
+  static constexpr size_t kChunkBytes = (size_t)64 << 20;
+  unsigned char *h[2] = {nullptr, nullptr}, *d[2] = {nullptr, nullptr};
+  unsigned char *d_codes[2] = {nullptr, nullptr}, *d_hdrs[2] = {nullptr, nullptr}; // packed outputs, on demand
+  size_t cap = 0, codes_cap = 0, hdrs_cap = 0;
+  hipStream_t copy = nullptr;
+  hipEvent_t sent[2] = {nullptr, nullptr}, consumed[2] = {nullptr, nullptr};
+  bool used[2] = {false, false};
+  void release_bufs() {
+    for (int k = 0; k < 2; k++) {
+      if (h[k]) (void)hipHostFree(h[k]);
+      if (d[k]) (void)hipFree(d[k]);
+      h[k] = d[k] = nullptr;
+    }
+    cap = 0;
+  }
+  int reserve(size_t bytes) {
+    if (!copy) {
+      HIP_TRY(hipStreamCreateWithFlags(&copy, hipStreamNonBlocking));
+      for (int k = 0; k < 2; k++) {
+        HIP_TRY(hipEventCreateWithFlags(&sent[k], hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&consumed[k], hipEventDisableTiming));
+      }
+    }
+    if (bytes <= cap) return HNY_OK;
+    HIP_TRY(hipDeviceSynchronize()); // growing: nothing may still read the old buffers
+    release_bufs();
+    for (int k = 0; k < 2; k++) {
+      HIP_TRY(hipHostMalloc((void **)&h[k], bytes));
+      HIP_TRY(hipMalloc((void **)&d[k], bytes));
+      used[k] = false;
+    }
+    cap = bytes;
+    return HNY_OK;
+  }
+  int reserve_out(size_t codes, size_t hdrs) {
+    if (codes <= codes_cap && hdrs <= hdrs_cap) return HNY_OK;
+    HIP_TRY(hipDeviceSynchronize());
+    for (int k = 0; k < 2; k++) {
+      if (d_codes[k]) (void)hipFree(d_codes[k]);
+      if (d_hdrs[k]) (void)hipFree(d_hdrs[k]);
+      d_codes[k] = d_hdrs[k] = nullptr;
+      HIP_TRY(hipMalloc((void **)&d_codes[k], std::max<size_t>(codes, 16)));
+      HIP_TRY(hipMalloc((void **)&d_hdrs[k], std::max<size_t>(hdrs, 16)));
+    }
+    codes_cap = codes;
+    hdrs_cap = hdrs;
+    return HNY_OK;
+  }
+  ~IngestPipe() {
+    if (copy) (void)hipStreamSynchronize(copy);
+    release_bufs(); // (hipFree waits for the device)
+    for (int k = 0; k < 2; k++) {
+      if (d_codes[k]) (void)hipFree(d_codes[k]);
+      if (d_hdrs[k]) (void)hipFree(d_hdrs[k]);
+      if (sent[k]) (void)hipEventDestroy(sent[k]);
+      if (consumed[k]) (void)hipEventDestroy(consumed[k]);
+    }
+    if (copy) (void)hipStreamDestroy(copy);
+  }
+};
+
 } // namespace
 
 struct hny_builder {
@@ -312,6 +379,11 @@ struct hny_builder {
     ~ExportBufs() { drop(); }
   } xbuf;
   bool will_export = true;       // hny_multi.cpp: only rank 0 exports
+  // f32 entry points: the slots of the caller's items (incremental builders; a fresh builder's are 0 .. n-1),
+  // for hny_builder_export_items, and the staging buffers the f32 searches encode their queries through
+  std::vector<uint32_t> item_slot;
+  uint64_t n_items = 0;
+  std::unique_ptr<IngestPipe> qpipe;
   uint64_t nrec_bound = 0, nbr_bound = 0;
   bool locality = true;
   u32 *h_l0 = nullptr, *h_up = nullptr, *h_cnt0 = nullptr, *h_cntu = nullptr; // pinned staging
@@ -502,6 +574,114 @@ int upload_rows(const void *vectors, size_t stride, size_t vbytes, uint64_t n, u
   return HNY_OK;
 }
 
+// fn(lo, hi) over [0, n) on up to nt threads (the calling thread takes the first share).  A thread that cannot
+// be created costs parallelism, not the call: its share runs on the calling thread, and nothing is thrown.
+template <class F>
+void run_split(unsigned nt, uint64_t n, F fn) {
+  nt = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(nt, n));
+  std::vector<std::thread> th;
+  unsigned started = 1;
+  try {
+    th.reserve(nt);
+    for (; started < nt; started++) th.emplace_back(fn, n * started / nt, n * (started + 1) / nt);
+  } catch (...) {
+  }
+  fn(0, n / nt);
+  if (started < nt) fn(n * started / nt, n);
+  for (auto &t : th) t.join();
+}
+
+struct IngestJob {
+  int metric = 0;
+  uint32_t dim = 0;
+  const void *src = nullptr; // f32 rows on the host, `stride` bytes apart (>= dim * 4, multiple of 4)
+  size_t stride = 0;
+  uint64_t n = 0;
+  const u32 *d_slots = nullptr; // device: destination slot per row, NULL = identity
+  unsigned char *rows = nullptr; // device destinations (NULL = not wanted)
+  uint32_t row_stride = 0;
+  float *norms = nullptr;
+  void *out_codes = nullptr, *out_hdrs = nullptr; // host destinations of the packed outputs (NULL = not wanted)
+};
+
+// the caller synchronises `st` (the kernels and, with packed outputs, the copies back are enqueued on it)
+int run_ingest(IngestPipe &p, const IngestJob &j, hipStream_t st) {
+  if (!j.n) return HNY_OK;
+  const size_t rowb = (size_t)j.dim * 4;
+  // rows far apart are packed while they are staged (the gaps would travel otherwise); rows with a modest
+  // stride keep it, so that a chunk is one contiguous copy per thread
+  const bool pack = j.stride > 2 * rowb;
+  const size_t sstride = pack ? rowb : j.stride;
+  const size_t vb = vec_bytes(j.metric, j.dim), hb = hdr_bytes(j.metric);
+  uint64_t chunk = std::max<uint64_t>(1, IngestPipe::kChunkBytes / sstride);
+  const int env_rows = env_int("HNY_INGEST_CHUNK_ROWS", 0); // tests: several chunks from a small input
+  if (env_rows > 0) chunk = (uint64_t)env_rows;
+  chunk = std::min<uint64_t>(chunk, j.n);
+  int rc = p.reserve((size_t)chunk * sstride);
+  if (rc) return rc;
+  if (j.out_codes || j.out_hdrs) {
+    rc = p.reserve_out(j.out_codes ? (size_t)chunk * vb : 0, j.out_hdrs ? (size_t)chunk * hb : 0);
+    if (rc) return rc;
+  }
+  const unsigned nt_max = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+  uint64_t ci = 0;
+  for (uint64_t r0 = 0; r0 < j.n; r0 += chunk, ci++) {
+    const int k = (int)(ci & 1);
+    const uint64_t cnt = std::min<uint64_t>(chunk, j.n - r0);
+    if (p.used[k]) HIP_TRY(hipEventSynchronize(p.sent[k])); // the pinned buffer has left for the device
+    const unsigned char *src = (const unsigned char *)j.src + r0 * j.stride;
+    unsigned char *hk = p.h[k];
+    // the last row may end at dim * 4 bytes: never read the caller's memory past it
+    const size_t bytes = (size_t)(cnt - 1) * sstride + rowb;
+    if (pack) {
+      run_split(std::min<unsigned>(nt_max, (unsigned)(bytes / ((size_t)2 << 20)) + 1), cnt, [=](uint64_t lo, uint64_t hi) {
+        for (uint64_t r = lo; r < hi; r++) memcpy(hk + r * rowb, src + r * j.stride, rowb);
+      });
+    } else {
+      run_split(std::min<unsigned>(nt_max, (unsigned)(bytes / ((size_t)2 << 20)) + 1), bytes,
+                [=](uint64_t lo, uint64_t hi) { memcpy(hk + lo, src + lo, (size_t)(hi - lo)); });
+    }
+    if (p.used[k]) HIP_TRY(hipStreamWaitEvent(p.copy, p.consumed[k], 0)); // the kernel two chunks back has read d[k]
+    HIP_TRY(hipMemcpyAsync(p.d[k], hk, bytes, hipMemcpyHostToDevice, p.copy));
+    HIP_TRY(hipEventRecord(p.sent[k], p.copy));
+    HIP_TRY(hipStreamWaitEvent(st, p.sent[k], 0));
+    IngestArgs a{};
+    a.src = (const float *)p.d[k];
+    a.src_stride = (u32)(sstride / 4);
+    a.dim = j.dim;
+    a.cnt = (u32)cnt;
+    a.codec = j.metric == HNY_COSINE ? ING_F32_NORM : j.metric == HNY_HAMMING ? ING_BINARY : is_binary(j.metric) ? ING_BQ : ING_F32;
+    a.hdr_const = j.metric == HNY_BQ_COSINE ? sqrtf((float)(int32_t)(vb * 8)) : 0.0f; // sqrt(dot_bq(v,v)) = sqrt(padded dims)
+    a.slots = j.d_slots ? j.d_slots + r0 : nullptr;
+    a.slot_base = (u32)r0;
+    a.rows = j.rows;
+    a.row_stride = j.rows ? j.row_stride : (u32)((vb + 15) / 16 * 16); // (the kernel walks a row in these units)
+    a.norms = j.norms;
+    a.out_codes = j.out_codes ? p.d_codes[k] : nullptr;
+    a.out_hdrs = j.out_hdrs ? p.d_hdrs[k] : nullptr;
+    a.vb = (u32)vb;
+    a.hb = (u32)hb;
+    HIP_TRY(hnyk_ingest(a, st));
+    HIP_TRY(hipEventRecord(p.consumed[k], st));
+    p.used[k] = true;
+    if (j.out_codes)
+      HIP_TRY(hipMemcpyAsync((unsigned char *)j.out_codes + r0 * vb, p.d_codes[k], (size_t)cnt * vb, hipMemcpyDeviceToHost, st));
+    if (j.out_hdrs)
+      HIP_TRY(hipMemcpyAsync((unsigned char *)j.out_hdrs + r0 * hb, p.d_hdrs[k], (size_t)cnt * hb, hipMemcpyDeviceToHost, st));
+  }
+  return HNY_OK;
+}
+
+// what every f32 entry point checks before anything else
+int check_f32_rows(uint32_t dim, uint64_t n, const void *vectors, size_t stride) {
+  if (dim == 0) return fail(HNY_ERR_INVALID_DIM, "dim must be > 0");
+  if (n && !vectors) return fail(HNY_ERR_INVALID_ARG, "null f32 vectors");
+  if (n && stride < (size_t)dim * 4)
+    return fail(HNY_ERR_INVALID_DIM, "stride %zu < %zu bytes of f32 for dim %u", stride, (size_t)dim * 4, dim);
+  if (n && stride % 4) return fail(HNY_ERR_INVALID_ARG, "f32 stride %zu is not a multiple of 4", stride);
+  return HNY_OK;
+}
+
 int reset_graph(hny_builder *b) {
   hipStream_t st = b->stream;
   HIP_TRY(hnyk_fill_u32(b->d_l0_ids.p, HNY_SENT, b->d_l0_ids.n, st));
@@ -664,38 +844,34 @@ int hny_encode_vectors_gpu(int32_t metric, uint32_t dim, uint64_t n, const float
     return fail(HNY_ERR_NO_DEVICE, "no HIP device (this library has no CPU path)");
   if (device >= 0) HIP_TRY(hipSetDevice(device));
   const size_t vb = vec_bytes(metric, dim), hb = hdr_bytes(metric);
-  const uint64_t chunk = std::max<uint64_t>(1, (256ull << 20) / ((uint64_t)dim * 4));
-  DevBuf<float> dv, dn;
-  DevBuf<u64> dc;
-  HIP_TRY(dv.alloc(std::min(chunk, std::max<uint64_t>(n, 1)) * dim));
-  if (metric == HNY_COSINE) HIP_TRY(dn.alloc(std::min(chunk, std::max<uint64_t>(n, 1))));
-  if (is_binary(metric)) HIP_TRY(dc.alloc(std::min(chunk, std::max<uint64_t>(n, 1)) * (vb / 8)));
-  std::vector<float> norms;
-  for (uint64_t i0 = 0; i0 < n; i0 += chunk) {
-    const uint64_t cnt = std::min(chunk, n - i0);
-    unsigned char *codes = (unsigned char *)out_codes + i0 * vb;
-    unsigned char *hdrs = (unsigned char *)out_headers + i0 * hb;
-    memset(hdrs, 0, cnt * hb); // bias 0.0 (euclidean.rs:38-40 ...), idx 0 (hamming.rs:40-42)
-    if (metric == HNY_COSINE || is_binary(metric))
-      HIP_TRY(hipMemcpy(dv.p, vectors + i0 * dim, cnt * dim * 4, hipMemcpyHostToDevice));
-    if (!is_binary(metric)) {
-      memcpy(codes, vectors + i0 * dim, cnt * vb); // f32.rs:9-55
-      if (metric == HNY_COSINE) {
-        HIP_TRY(hnyk_norms_x86(dv.p, dim, cnt, dn.p, nullptr));
-        norms.resize(cnt);
-        HIP_TRY(hipMemcpy(norms.data(), dn.p, cnt * 4, hipMemcpyDeviceToHost));
-        memcpy(hdrs, norms.data(), cnt * 4);
-      }
-    } else {
-      HIP_TRY(hnyk_quantize(dv.p, dim, cnt, metric == HNY_HAMMING, dc.p, nullptr));
-      HIP_TRY(hipMemcpy(codes, dc.p, cnt * vb, hipMemcpyDeviceToHost));
-      if (metric == HNY_BQ_COSINE) { // sqrt(dot_bq(v,v)) = sqrt(padded dims)
-        float h = sqrtf((float)(int32_t)(vb * 8));
-        for (uint64_t i = 0; i < cnt; i++) memcpy(hdrs + i * 4, &h, 4);
-      }
+  if (!is_binary(metric)) {
+    memcpy(out_codes, vectors, (size_t)n * vb); // f32.rs:9-55
+    if (metric != HNY_COSINE) {
+      memset(out_headers, 0, (size_t)n * hb); // bias 0.0 (euclidean.rs:38-40 ...)
+      return HNY_OK;
     }
   }
-  return HNY_OK;
+  // the staging pipeline of the f32 entry points with only the packed outputs: the bit codes and the headers
+  // (Cosine: the norms; its codes are the f32 bytes copied above)
+  hipStream_t st = nullptr;
+  HIP_TRY(hipStreamCreate(&st));
+  int rc;
+  {
+    IngestPipe pipe;
+    IngestJob j;
+    j.metric = metric;
+    j.dim = dim;
+    j.src = vectors;
+    j.stride = (size_t)dim * 4;
+    j.n = n;
+    j.out_codes = is_binary(metric) ? out_codes : nullptr;
+    j.out_hdrs = out_headers;
+    rc = run_ingest(pipe, j, st);
+    hipError_t e = hipStreamSynchronize(st);
+    if (!rc && e != hipSuccess) rc = fail(HNY_ERR_NO_DEVICE, "HIP error %d (%s)", (int)e, hipGetErrorString(e));
+  }
+  (void)hipStreamDestroy(st);
+  return rc;
 }
 
 void hny_builder_destroy(hny_builder *b) {
@@ -718,11 +894,17 @@ struct IncrementalSpec {
   bool load_only = false; // Reader::open: the stored graph as it is, nothing gets (re)inserted
 };
 
+// f32: items->vectors are f32 rows (Writer::add_item's input, writer.rs:462-480) that the device encodes while they
+// arrive (run_ingest); items->headers is not read
 static int create_impl(const hny_build_opts *opts, const hny_items *items, const IncrementalSpec *inc,
-                       hny_builder **out) {
+                       hny_builder **out, bool f32 = false) {
   if (!opts || !items || !out) return fail(HNY_ERR_INVALID_ARG, "null argument");
   *out = nullptr;
   const hny_build_opts &o = *opts;
+  // decided from the options alone, before any device is counted or opened
+  if (f32 && (o.n_gpus > 1 || o.devices))
+    return fail(HNY_ERR_UNSUPPORTED, "f32 items on more than one GPU are not supported yet: encode them with "
+                                     "hny_encode_vectors_gpu and pass codec bytes, or build on one GPU");
   if (o.metric < 0 || o.metric > HNY_BQ_MANHATTAN) return fail(HNY_ERR_INVALID_ARG, "bad metric");
   if (o.dim == 0) return fail(HNY_ERR_INVALID_DIM, "dim must be > 0");
   if (o.M == 0 || o.M0 < o.M) return fail(HNY_ERR_INVALID_ARG, "need 1 <= M <= M0");
@@ -738,13 +920,18 @@ static int create_impl(const hny_build_opts *opts, const hny_items *items, const
                 HNY_MAX_EF);
   if (items->n >= (1ull << 31)) return fail(HNY_ERR_UNSUPPORTED, "n >= 2^31");
   const size_t vb = vec_bytes(o.metric, o.dim), hb = hdr_bytes(o.metric);
-  if (items->n && (!items->ids || !items->vectors || !items->headers))
+  if (items->n && (!items->ids || !items->vectors || (!f32 && !items->headers)))
     return fail(HNY_ERR_INVALID_ARG, "null item arrays");
-  if (items->n && items->stride < vb)
-    return fail(HNY_ERR_INVALID_DIM, "stride %zu < %zu codec bytes for dim %u", items->stride, vb,
-                o.dim); // Error::InvalidVecDimension
-  if (items->n && items->header_size != hb)
-    return fail(HNY_ERR_INVALID_ARG, "header_size %zu, expected %zu", items->header_size, hb);
+  if (f32) {
+    int rcf = check_f32_rows(o.dim, items->n, items->vectors, items->stride);
+    if (rcf) return rcf;
+  } else {
+    if (items->n && items->stride < vb)
+      return fail(HNY_ERR_INVALID_DIM, "stride %zu < %zu codec bytes for dim %u", items->stride, vb,
+                  o.dim); // Error::InvalidVecDimension
+    if (items->n && items->header_size != hb)
+      return fail(HNY_ERR_INVALID_ARG, "header_size %zu, expected %zu", items->header_size, hb);
+  }
   for (uint64_t i = 1; i < items->n; i++)
     if (items->ids[i] <= items->ids[i - 1]) return fail(HNY_ERR_INVALID_ARG, "ids not ascending");
 
@@ -1123,8 +1310,32 @@ static int create_impl(const hny_build_opts *opts, const hny_items *items, const
   g.stats = b->d_stats.p;
 
   // ---- upload (the "export to HBM" that replaces FrozenReader, parallel.rs:11-45) ----
+  DevBuf<u32> d_item_slot; // f32 items: alive until the stream is synchronised below
+  IngestPipe pipe;
   if (n) {
-    if (!inc) {
+    if (f32) {
+      IngestJob j;
+      if (inc) { // items are a subset of the universe: the other slots hold zero rows and zero norms
+        HIP_TRY(hipMemsetAsync(b->d_rows.p, 0, (size_t)n * g.row_stride, st));
+        if (has_norm) HIP_TRY(hipMemsetAsync(b->d_norms.p, 0, (size_t)n * 4, st));
+        if (items->n) {
+          HIP_TRY(d_item_slot.alloc(items->n));
+          HIP_TRY(hipMemcpyAsync(d_item_slot.p, item_slot.data(), (size_t)items->n * 4, hipMemcpyHostToDevice, st));
+          HIP_TRY(hipStreamSynchronize(st));
+        }
+        j.d_slots = d_item_slot.p;
+      }
+      j.metric = o.metric;
+      j.dim = o.dim;
+      j.src = items->vectors;
+      j.stride = items->stride;
+      j.n = items->n;
+      j.rows = b->d_rows.p;
+      j.row_stride = g.row_stride;
+      j.norms = has_norm ? b->d_norms.p : nullptr;
+      rc = run_ingest(pipe, j, st);
+      if (rc) return rc;
+    } else if (!inc) {
       rc = upload_rows(items->vectors, items->stride, vb, n, g.row_stride, b->d_rows.p, st);
       if (rc) return rc;
     } else {
@@ -1150,7 +1361,7 @@ static int create_impl(const hny_build_opts *opts, const hny_items *items, const
     HIP_TRY(hipMemcpyAsync(b->d_eps.p, b->entry_points.data(), b->entry_points.size() * 4,
                            hipMemcpyHostToDevice, st));
     std::vector<float> norms;
-    if (has_norm) {
+    if (has_norm && !f32) {
       norms.assign(n, 0.f);
       for (uint64_t i = 0; i < items->n; i++)
         memcpy(&norms[item_slot[i]], (const unsigned char *)items->headers + (size_t)i * hb, 4);
@@ -1192,6 +1403,8 @@ static int create_impl(const hny_build_opts *opts, const hny_items *items, const
   rc = reset_graph(b.get());
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(st));
+  b->n_items = items->n;
+  if (inc) b->item_slot = std::move(item_slot);
   b->t_upload = now_s() - t0;
   b->t_build0 = now_s();
   *out = b.release();
@@ -1200,6 +1413,37 @@ static int create_impl(const hny_build_opts *opts, const hny_items *items, const
 
 int hny_builder_create(const hny_build_opts *opts, const hny_items *items, hny_builder **out) {
   return create_impl(opts, items, nullptr, out);
+}
+
+int hny_builder_create_f32(const hny_build_opts *opts, const hny_items *f32_items, hny_builder **out) {
+  return create_impl(opts, f32_items, nullptr, out, true);
+}
+
+// the Item records' payload (node.rs:136-140: header, then codec bytes) of the builder's items in ascending id order,
+// read back from HBM: what hny_encode_vectors would have produced for the f32 rows the builder was created from
+int hny_builder_export_items(hny_builder *b, void *out_codes, void *out_headers) {
+  if (!b || (b->n_items && (!out_codes || !out_headers))) return fail(HNY_ERR_INVALID_ARG, "null argument");
+  HIP_TRY(hipSetDevice(b->device));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  const size_t vb = vec_bytes(b->o.metric, b->o.dim), hb = hdr_bytes(b->o.metric), rs = b->g.row_stride;
+  const bool ident = b->item_slot.empty();
+  auto slot_of_item = [&](uint64_t i) { return ident ? (uint32_t)i : b->item_slot[i]; };
+  const size_t chunk = std::max<size_t>(1, ((size_t)64 << 20) / rs);
+  std::vector<unsigned char> tmp(std::min<size_t>(chunk, std::max<uint32_t>(b->n, 1)) * rs);
+  uint64_t i = 0;
+  for (uint32_t s0 = 0; s0 < b->n && i < b->n_items; s0 += (uint32_t)chunk) { // item slots ascend with the ids
+    const uint32_t cnt = (uint32_t)std::min<size_t>(chunk, b->n - s0);
+    HIP_TRY(hipMemcpy(tmp.data(), b->d_rows.p + (size_t)s0 * rs, (size_t)cnt * rs, hipMemcpyDeviceToHost));
+    for (; i < b->n_items && slot_of_item(i) < s0 + cnt; i++)
+      memcpy((unsigned char *)out_codes + i * vb, &tmp[(size_t)(slot_of_item(i) - s0) * rs], vb);
+  }
+  if (b->n_items) memset(out_headers, 0, (size_t)b->n_items * hb); // bias 0.0 (euclidean.rs:38-40 ...), idx 0 (hamming.rs:40-42)
+  if (b->g.norms && b->n_items) {
+    std::vector<float> norms(b->n);
+    HIP_TRY(hipMemcpy(norms.data(), b->d_norms.p, (size_t)b->n * 4, hipMemcpyDeviceToHost));
+    for (uint64_t k = 0; k < b->n_items; k++) memcpy((unsigned char *)out_headers + k * hb, &norms[slot_of_item(k)], 4);
+  }
+  return HNY_OK;
 }
 
 int hny_builder_reset(hny_builder *b) {
@@ -1943,16 +2187,10 @@ extern "C" int hny_internal_build_multi(const hny_build_opts *opts, const hny_it
                                         const hny_prev_graph *prev, hny_graph **out); // hny_multi.cpp
 static bool wants_multi(const hny_build_opts *o) { return o && (o->n_gpus > 1 || (o->n_gpus == 1 && o->devices)); }
 
-int hny_build(const hny_build_opts *opts, const hny_items *items, hny_graph **out) {
-  if (!out) return fail(HNY_ERR_INVALID_ARG, "null out");
-  *out = nullptr;
-  if (wants_multi(opts)) {
-    if (!items) return fail(HNY_ERR_INVALID_ARG, "null argument");
-    return hny_internal_build_multi(opts, items, nullptr, 0, nullptr, 0, nullptr, out);
-  }
-  hny_builder *b = nullptr;
-  int rc = hny_builder_create(opts, items, &b);
-  if (rc) return rc;
+static int run_fill_gaps(hny_builder *b);
+// every batch of a freshly created builder, then (incremental) fill_gaps, finish and destroy
+static int run_build(hny_builder *b, const hny_build_opts *opts, hny_graph **out) {
+  int rc;
   for (;;) {
     // cancel: probed before every batch, i.e. every <= batch_max items (the reference probes every
     // CANCELLATION_PROBING = 10 000 items, lib.rs:140, hnsw.rs:174-177)
@@ -1969,9 +2207,32 @@ int hny_build(const hny_build_opts *opts, const hny_items *items, hny_graph **ou
     if (rc) break;
     if (opts->progress) opts->progress(opts->progress_ctx, b->pos, b->order.size());
   }
+  if (!rc) rc = run_fill_gaps(b); // nothing to do on a fresh index
   if (!rc) rc = hny_builder_finish(b, out);
   hny_builder_destroy(b);
   return rc;
+}
+
+int hny_build(const hny_build_opts *opts, const hny_items *items, hny_graph **out) {
+  if (!out) return fail(HNY_ERR_INVALID_ARG, "null out");
+  *out = nullptr;
+  if (wants_multi(opts)) {
+    if (!items) return fail(HNY_ERR_INVALID_ARG, "null argument");
+    return hny_internal_build_multi(opts, items, nullptr, 0, nullptr, 0, nullptr, out);
+  }
+  hny_builder *b = nullptr;
+  int rc = hny_builder_create(opts, items, &b);
+  if (rc) return rc;
+  return run_build(b, opts, out);
+}
+
+int hny_build_f32(const hny_build_opts *opts, const hny_items *f32_items, hny_graph **out) {
+  if (!out) return fail(HNY_ERR_INVALID_ARG, "null out");
+  *out = nullptr;
+  hny_builder *b = nullptr;
+  int rc = create_impl(opts, f32_items, nullptr, &b, true);
+  if (rc) return rc;
+  return run_build(b, opts, out);
 }
 
 // fill_gaps_from_deleted (hnsw.rs:187, 334-415): merge old and new links of every surviving old
@@ -2026,6 +2287,14 @@ int hny_builder_load(const hny_build_opts *opts, const hny_items *items, const h
   return create_impl(opts, items, &inc, out);
 }
 
+int hny_builder_load_f32(const hny_build_opts *opts, const hny_items *f32_items, const hny_prev_graph *prev,
+                         hny_builder **out) {
+  if (!prev) return fail(HNY_ERR_INVALID_ARG, "null graph");
+  IncrementalSpec inc{nullptr, 0, nullptr, 0, prev};
+  inc.load_only = true;
+  return create_impl(opts, f32_items, &inc, out, true);
+}
+
 // hny_multi.cpp: the distance-evaluation counters of a replica.  Work that every rank repeats (ramp-up
 // batches, small deferred sets, fill_gaps) is counted on rank 0 only: the other ranks point their kernels'
 // counter block at a scratch copy meanwhile (the error words in it are the same on every replica).
@@ -2074,24 +2343,19 @@ int hny_build_incremental(const hny_build_opts *opts, const hny_items *items, co
   hny_builder *b = nullptr;
   int rc = create_impl(opts, items, &inc, &b);
   if (rc) return rc;
-  for (;;) {
-    if (opts->cancel && opts->cancel(opts->cancel_ctx)) {
-      hny_builder_destroy(b);
-      return fail(HNY_ERR_CANCELLED, "build cancelled");
-    }
-    hny_batch bt;
-    rc = hny_builder_next_batch(b, &bt);
-    if (rc || bt.count == 0) break;
-    rc = hny_builder_search(b, 0, bt.count, nullptr);
-    if (rc) break;
-    rc = hny_builder_apply(b, nullptr);
-    if (rc) break;
-    if (opts->progress) opts->progress(opts->progress_ctx, b->pos, b->order.size());
-  }
-  if (!rc) rc = run_fill_gaps(b);
-  if (!rc) rc = hny_builder_finish(b, out);
-  hny_builder_destroy(b);
-  return rc;
+  return run_build(b, opts, out);
+}
+
+int hny_build_incremental_f32(const hny_build_opts *opts, const hny_items *f32_items, const uint32_t *to_insert,
+                              uint64_t n_insert, const uint32_t *to_delete, uint64_t n_delete,
+                              const hny_prev_graph *prev, hny_graph **out) {
+  if (!out) return fail(HNY_ERR_INVALID_ARG, "null out");
+  *out = nullptr;
+  IncrementalSpec inc{to_insert, n_insert, to_delete, n_delete, prev};
+  hny_builder *b = nullptr;
+  int rc = create_impl(opts, f32_items, &inc, &b, true);
+  if (rc) return rc;
+  return run_build(b, opts, out);
 }
 
 int hny_builder_distances(hny_builder *b, uint64_t n_pairs, const uint32_t *slot_a,
@@ -2173,12 +2437,42 @@ static uint32_t copy_topk_row(const hny_builder *b, const u64 *row, uint32_t n_f
 
 static int search_knn_impl(hny_builder *b, uint64_t nq, const void *qvectors, size_t qstride,
                            const void *qheaders, uint32_t k, uint32_t ef_search, uint32_t *out_ids,
-                           float *out_dists, uint32_t *out_counts, const hny_query_opts *qo);
+                           float *out_dists, uint32_t *out_counts, const hny_query_opts *qo, bool q_f32 = false);
 // the QueryBuilder searcher with its search queue as a real heap in HBM (k_nns); force_heap: also for queries
 // without a candidates filter — where search_knn_impl sends the queries whose tie pool overflowed
 static int nns_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const void *qvectors, size_t qstride,
                     const void *qheaders, const uint32_t *query_items, uint32_t *out_ids, float *out_dists,
-                    uint32_t *out_counts, bool force_heap);
+                    uint32_t *out_counts, bool force_heap, bool q_f32 = false);
+
+// a chunk of queries into the row buffer (and norms) the searchers read.  q_f32: Reader::nns().by_vector's &[f32]
+// (reader.rs:132-148), encoded on the device by the same kernel as the items (slot = index within the chunk);
+// otherwise codec bytes + headers
+static int stage_queries(hny_builder *b, bool q_f32, const void *qvectors, size_t qstride, const void *qheaders,
+                         uint64_t q0, uint32_t cnt, unsigned char *dq, float *dqn, std::vector<float> &qn) {
+  const size_t vb = vec_bytes(b->o.metric, b->o.dim), hb = hdr_bytes(b->o.metric);
+  const bool has_norm = b->g.norms != nullptr;
+  if (q_f32) {
+    if (!b->qpipe) b->qpipe.reset(new (std::nothrow) IngestPipe());
+    if (!b->qpipe) return fail(HNY_ERR_OOM, "out of memory");
+    IngestJob j;
+    j.metric = b->o.metric;
+    j.dim = b->o.dim;
+    j.src = (const unsigned char *)qvectors + q0 * qstride;
+    j.stride = qstride;
+    j.n = cnt;
+    j.rows = dq;
+    j.row_stride = b->g.row_stride;
+    j.norms = has_norm ? dqn : nullptr;
+    return run_ingest(*b->qpipe, j, b->stream);
+  }
+  int rc = upload_rows((const unsigned char *)qvectors + q0 * qstride, qstride, vb, cnt, b->g.row_stride, dq, b->stream);
+  if (rc) return rc;
+  if (has_norm) {
+    for (uint32_t i = 0; i < cnt; i++) memcpy(&qn[i], (const unsigned char *)qheaders + (q0 + i) * hb, 4);
+    HIP_TRY(hipMemcpyAsync(dqn, qn.data(), (size_t)cnt * 4, hipMemcpyHostToDevice, b->stream));
+  }
+  return HNY_OK;
+}
 
 int hny_builder_search_knn(hny_builder *b, uint64_t nq, const void *qvectors, size_t qstride,
                            const void *qheaders, uint32_t k, uint32_t ef_search, uint32_t *out_ids,
@@ -2186,11 +2480,20 @@ int hny_builder_search_knn(hny_builder *b, uint64_t nq, const void *qvectors, si
   return search_knn_impl(b, nq, qvectors, qstride, qheaders, k, ef_search, out_ids, out_dists, out_counts, nullptr);
 }
 
+int hny_builder_search_knn_f32(hny_builder *b, uint64_t nq, const float *queries, size_t qstride, uint32_t k,
+                               uint32_t ef_search, uint32_t *out_ids, float *out_dists, uint32_t *out_counts) {
+  return search_knn_impl(b, nq, queries, qstride, nullptr, k, ef_search, out_ids, out_dists, out_counts, nullptr, true);
+}
+
 static int search_knn_impl(hny_builder *b, uint64_t nq, const void *qvectors, size_t qstride,
                            const void *qheaders, uint32_t k, uint32_t ef_search, uint32_t *out_ids,
-                           float *out_dists, uint32_t *out_counts, const hny_query_opts *qo) {
-  if (!b || !qvectors || !qheaders || !out_ids || !out_dists || !out_counts || k == 0)
+                           float *out_dists, uint32_t *out_counts, const hny_query_opts *qo, bool q_f32) {
+  if (!b || !qvectors || (!q_f32 && !qheaders) || !out_ids || !out_dists || !out_counts || k == 0)
     return fail(HNY_ERR_INVALID_ARG, "bad argument");
+  if (q_f32) {
+    int rcf = check_f32_rows(b->o.dim, nq, qvectors, qstride);
+    if (rcf) return rcf;
+  }
   SearchCancel sc;
   if (qo && qo->did_cancel) *qo->did_cancel = 0;
   HIP_TRY(sc.init(qo));
@@ -2213,7 +2516,7 @@ static int search_knn_impl(hny_builder *b, uint64_t nq, const void *qvectors, si
   }
   const uint32_t rcap = res_capacity(ef, (uint32_t)b->entry_points.size(), b->n, b->top_layer_nodes, HNY_RES_GLOBAL_MAX);
   const size_t vb = vec_bytes(b->o.metric, b->o.dim), hb = hdr_bytes(b->o.metric);
-  if (qstride < vb) return fail(HNY_ERR_INVALID_DIM, "query stride too small");
+  if (!q_f32 && qstride < vb) return fail(HNY_ERR_INVALID_DIM, "query stride too small");
   uint32_t chunk = std::max<uint32_t>(b->max_batch, 256);
   chunk = (uint32_t)std::min<uint64_t>(chunk, std::max<uint64_t>(nq, 1)); // buffers are sized chunk x rcap / k
   // at most ~2 GB of candidate lists per chunk
@@ -2243,13 +2546,8 @@ static int search_knn_impl(hny_builder *b, uint64_t nq, const void *qvectors, si
       for (uint32_t i = 0; i < cnt; i++) out_counts[q0 + i] = 0u;
       continue;
     }
-    int rc = upload_rows((const unsigned char *)qvectors + q0 * qstride, qstride, vb, cnt,
-                         b->g.row_stride, dq.p, b->stream);
+    int rc = stage_queries(b, q_f32, qvectors, qstride, qheaders, q0, cnt, dq.p, dqn.p, qn);
     if (rc) return rc;
-    if (has_norm) {
-      for (uint32_t i = 0; i < cnt; i++) memcpy(&qn[i], (const unsigned char *)qheaders + (q0 + i) * hb, 4);
-      HIP_TRY(hipMemcpyAsync(dqn.p, qn.data(), (size_t)cnt * 4, hipMemcpyHostToDevice, b->stream));
-    }
     WalkArgs w{};
     w.q_rows = dq.p;
     w.q_norms = has_norm ? dqn.p : nullptr;
@@ -2328,13 +2626,14 @@ static int search_knn_impl(hny_builder *b, uint64_t nq, const void *qvectors, si
     if (!again.empty() && !sc.cancelled) {
       // the same queries on the searcher whose queue is a real heap in HBM (and `res` too, when ef + 1 >
       // HNY_RES_LDS_MAX): nothing to overflow, same results
-      const size_t na = again.size();
-      std::vector<unsigned char> av(na * vb), ah(na * hb);
+      // (f32 queries: their f32 rows, which the device encodes again to the same bytes)
+      const size_t na = again.size(), qb = q_f32 ? (size_t)b->o.dim * 4 : vb;
+      std::vector<unsigned char> av(na * qb), ah(na * hb);
       std::vector<uint32_t> ai(na * k), ac(na);
       std::vector<float> ad(na * k);
       for (size_t j = 0; j < na; j++) {
-        memcpy(&av[j * vb], (const unsigned char *)qvectors + (q0 + again[j]) * qstride, vb);
-        memcpy(&ah[j * hb], (const unsigned char *)qheaders + (q0 + again[j]) * hb, hb);
+        memcpy(&av[j * qb], (const unsigned char *)qvectors + (q0 + again[j]) * qstride, qb);
+        if (!q_f32) memcpy(&ah[j * hb], (const unsigned char *)qheaders + (q0 + again[j]) * hb, hb);
       }
       hny_query_opts o2{};
       o2.k = k;
@@ -2345,7 +2644,7 @@ static int search_knn_impl(hny_builder *b, uint64_t nq, const void *qvectors, si
         o2.cancel = qo->cancel;
         o2.cancel_ctx = qo->cancel_ctx;
       }
-      int rc2 = nns_impl(b, &o2, na, av.data(), vb, ah.data(), nullptr, ai.data(), ad.data(), ac.data(), true);
+      int rc2 = nns_impl(b, &o2, na, av.data(), qb, ah.data(), nullptr, ai.data(), ad.data(), ac.data(), true, q_f32);
       if (rc2) return rc2;
       for (size_t j = 0; j < na; j++) {
         const uint64_t qi = q0 + again[j];
@@ -2376,20 +2675,30 @@ int hny_builder_nns(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const
   return nns_impl(b, qo, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists, out_counts, false);
 }
 
+int hny_builder_nns_f32(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const float *queries, size_t qstride,
+                        uint32_t *out_ids, float *out_dists, uint32_t *out_counts) {
+  if (!queries) return fail(HNY_ERR_INVALID_ARG, "no queries");
+  return nns_impl(b, qo, nq, queries, qstride, nullptr, nullptr, out_ids, out_dists, out_counts, false, true);
+}
+
 static int nns_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const void *qvectors, size_t qstride,
                     const void *qheaders, const uint32_t *query_items, uint32_t *out_ids, float *out_dists,
-                    uint32_t *out_counts, bool force_heap) {
+                    uint32_t *out_counts, bool force_heap, bool q_f32) {
   if (!b || !qo || !out_ids || !out_dists || !out_counts || qo->k == 0)
     return fail(HNY_ERR_INVALID_ARG, "bad argument");
   const bool by_item = query_items != nullptr;
-  if (!by_item && (!qvectors || !qheaders)) return fail(HNY_ERR_INVALID_ARG, "no queries");
+  if (!by_item && (!qvectors || (!q_f32 && !qheaders))) return fail(HNY_ERR_INVALID_ARG, "no queries");
+  if (q_f32) {
+    int rcf = check_f32_rows(b->o.dim, nq, qvectors, qstride);
+    if (rcf) return rcf;
+  }
   if (qo->has_candidates && qo->n_candidates && !qo->candidates)
     return fail(HNY_ERR_INVALID_ARG, "candidates missing");
   if (!(qo->linear_below_ratio >= 0.f && qo->linear_below_ratio <= 1.f)) // reader.rs:253-256
     return fail(HNY_ERR_INVALID_ARG, "linear scan threshold ratio must be between 0.0 and 1.0");
   if (!qo->has_candidates && !by_item && !force_heap)
     return search_knn_impl(b, nq, qvectors, qstride, qheaders, qo->k, qo->ef_search, out_ids, out_dists,
-                           out_counts, qo);
+                           out_counts, qo, q_f32);
   if (b->pos < b->order.size()) return fail(HNY_ERR_INVALID_ARG, "build not finished");
   const uint32_t k = qo->k, ef = std::max(qo->ef_search, k); // reader.rs:746, 837
   if ((uint64_t)ef + 1 > HNY_RES_GLOBAL_MAX)
@@ -2451,8 +2760,8 @@ static int nns_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const
     rcap = 64;
     while (rcap < need) rcap *= 2;
   }
-  const size_t vb = vec_bytes(b->o.metric, b->o.dim), hb = hdr_bytes(b->o.metric);
-  if (!by_item && qstride < vb) return fail(HNY_ERR_INVALID_DIM, "query stride too small");
+  const size_t vb = vec_bytes(b->o.metric, b->o.dim);
+  if (!by_item && !q_f32 && qstride < vb) return fail(HNY_ERR_INVALID_DIM, "query stride too small");
   const uint32_t chunk = (uint32_t)std::max<uint64_t>(
       1, std::min<uint64_t>(std::min<uint64_t>(std::max<uint32_t>(b->max_batch, 256), std::max<uint64_t>(nq, 1)),
                             ((uint64_t)2 << 30) / ((uint64_t)std::max(rcap, k) * 8))); // <= ~2 GB of candidate lists
@@ -2524,14 +2833,8 @@ static int nns_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const
       }
       HIP_TRY(hipMemcpyAsync(dqslots.p, qs.data(), (size_t)cnt * 4, hipMemcpyHostToDevice, b->stream));
     } else {
-      int rc = upload_rows((const unsigned char *)qvectors + q0 * qstride, qstride, vb, cnt, b->g.row_stride,
-                           dq.p, b->stream);
+      int rc = stage_queries(b, q_f32, qvectors, qstride, qheaders, q0, cnt, dq.p, dqn.p, qn);
       if (rc) return rc;
-      if (has_norm) {
-        for (uint32_t i = 0; i < cnt; i++)
-          memcpy(&qn[i], (const unsigned char *)qheaders + (q0 + i) * hb, 4);
-        HIP_TRY(hipMemcpyAsync(dqn.p, qn.data(), (size_t)cnt * 4, hipMemcpyHostToDevice, b->stream));
-      }
       for (uint32_t i = 0; i < cnt; i++) members[n_mem++] = i;
     }
     if (n_mem == 0) continue;

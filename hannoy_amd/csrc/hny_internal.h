@@ -290,3 +290,22 @@ HNY_DECL_SP(1) HNY_DECL_SP(2) HNY_DECL_SP(3) HNY_DECL_SP(4) HNY_DECL_SP(5) HNY_D
 #undef HNY_DECL_SP
 hipError_t hnyk_norms_x86(const float *v, u32 dim, u64 n, float *out, hipStream_t st);
 hipError_t hnyk_quantize(const float *v, u32 dim, u64 n, int binary_codec, u64 *out, hipStream_t st);
+
+// k_ingest: one pass over a chunk of f32 rows on the device -> codec bytes at their final place in the
+// builder's row array, header norms, and (optionally) the packed codes + headers of the chunk
+enum { ING_F32 = 0, ING_F32_NORM = 1, ING_BINARY = 2, ING_BQ = 3 };
+struct IngestArgs {
+  const float *src;         // [cnt] rows, src_stride floats apart
+  u32 src_stride, dim, cnt;
+  int codec;                // ING_*: f32 copy, f32 copy + Cosine norm (x86 order), Binary / BinaryQuantized ballot
+  float hdr_const;          // header of the bit codecs: sqrt(padded dims) for BQ Cosine, else 0
+  const u32 *slots;         // destination slot of row i; NULL = slot_base + i
+  u32 slot_base;
+  unsigned char *rows;      // rows + slot * row_stride, zero padded to row_stride; NULL = not wanted
+  u32 row_stride;
+  float *norms;             // norms[slot]; NULL = not wanted
+  unsigned char *out_codes; // [cnt][vb] packed, NULL = not wanted
+  unsigned char *out_hdrs;  // [cnt][hb] packed, NULL = not wanted
+  u32 vb, hb;
+};
+hipError_t hnyk_ingest(const IngestArgs &a, hipStream_t st);

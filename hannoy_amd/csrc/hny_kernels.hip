@@ -4118,6 +4118,21 @@ __global__ __launch_bounds__(64) void k_finalize_lists(u32 *ids, u32 *cnt_out, u
 // (simple_avx.rs:8-13,69-110), 16 unfused partials for 16 <= dim < 32 (simple_sse.rs:10-14,64-110),
 // scalar below (simple.rs:81-83).  One half-wave (32 lanes = the 32 partials) per vector.
 // ---------------------------------------------------------------------------------------------
+// The element steps of that order, shared by k_norms_x86 and k_ingest so that the two cannot drift apart.
+__device__ __forceinline__ float sq_step_avx(float x, float acc) { return __builtin_fmaf(x, x, acc); } // _mm256_fmadd_ps
+__device__ __forceinline__ float sq_step_sse(float x, float acc) { // _mm_mul_ps, _mm_add_ps
+  float p = x * x;
+  return p + acc;
+}
+__device__ __forceinline__ float sq_step_tail(float x, float r) { // the scalar tail / the scalar loop, unfused
+  float p = x * x;
+  return r + p;
+}
+__device__ __forceinline__ float hsum_join4(float h1, float h2, float h3, float h4) { return ((h1 + h2) + h3) + h4; }
+// Binary::from_slice (binary.rs:87-89) / BinaryQuantized::from_slice (binary_quantized.rs:86)
+__device__ __forceinline__ bool quantize_bit(u32 bits, int binary_codec) {
+  return binary_codec ? (bits < 0x80000000u && bits > 0u) : (bits >> 31) == 0u;
+}
 __global__ __launch_bounds__(64) void k_norms_x86(const float *v, u32 dim, u64 n, float *out) {
   const int ln = threadIdx.x, j = ln & 31, half = ln >> 5;
   for (u64 vi = (u64)blockIdx.x * 2 + half; vi < n; vi += (u64)gridDim.x * 2) {
@@ -4126,42 +4141,30 @@ __global__ __launch_bounds__(64) void k_norms_x86(const float *v, u32 dim, u64 n
     if (dim >= 32) {
       const u32 m = dim - dim % 32;
       float acc = 0.f;
-      for (u32 i = 0; i < m; i += 32) acc = __builtin_fmaf(x[i + j], x[i + j], acc);
+      for (u32 i = 0; i < m; i += 32) acc = sq_step_avx(x[i + j], acc);
       acc = acc + __shfl_xor(acc, 4, 64); // hsum256: lane k + lane k+4
       acc = acc + __shfl_xor(acc, 2, 64); //          k + k+2
       acc = acc + __shfl_xor(acc, 1, 64); //          0 + 1
       const int b = half * 32;
       const float h1 = __shfl(acc, b, 64), h2 = __shfl(acc, b + 8, 64), h3 = __shfl(acc, b + 16, 64),
                   h4 = __shfl(acc, b + 24, 64);
-      r = ((h1 + h2) + h3) + h4;
-      for (u32 i = m; i < dim; i++) { // scalar tail, unfused
-        float p = x[i] * x[i];
-        r = r + p;
-      }
+      r = hsum_join4(h1, h2, h3, h4);
+      for (u32 i = m; i < dim; i++) r = sq_step_tail(x[i], r); // scalar tail, unfused
     } else if (dim >= 16) {
       const u32 m = dim - dim % 16;
       float acc = 0.f;
       if (j < 16)
-        for (u32 i = 0; i < m; i += 16) {
-          float p = x[i + j] * x[i + j];
-          acc = p + acc;
-        }
+        for (u32 i = 0; i < m; i += 16) acc = sq_step_sse(x[i + j], acc);
       acc = acc + __shfl_xor(acc, 2, 64); // hsum128: k + k+2
       acc = acc + __shfl_xor(acc, 1, 64); //          0 + 1
       const int b = half * 32;
       const float h1 = __shfl(acc, b, 64), h2 = __shfl(acc, b + 4, 64), h3 = __shfl(acc, b + 8, 64),
                   h4 = __shfl(acc, b + 12, 64);
-      r = ((h1 + h2) + h3) + h4;
-      for (u32 i = m; i < dim; i++) {
-        float p = x[i] * x[i];
-        r = r + p;
-      }
+      r = hsum_join4(h1, h2, h3, h4);
+      for (u32 i = m; i < dim; i++) r = sq_step_tail(x[i], r);
     } else {
       r = 0.f;
-      for (u32 i = 0; i < dim; i++) {
-        float p = x[i] * x[i];
-        r = r + p;
-      }
+      for (u32 i = 0; i < dim; i++) r = sq_step_tail(x[i], r);
     }
     if (j == 0) out[vi] = __builtin_sqrtf(r);
   }
@@ -4180,11 +4183,161 @@ __global__ __launch_bounds__(64) void k_quantize(const float *v, u32 dim, u64 n,
     const u32 d = (u32)(w % words) * 64 + (u32)ln;
     bool one = false;
     if (d < dim) {
-      const u32 bits = __float_as_uint(v[vi * dim + d]);
-      one = binary_codec ? (bits < 0x80000000u && bits > 0u) : (bits >> 31) == 0u;
+      one = quantize_bit(__float_as_uint(v[vi * dim + d]), binary_codec);
     }
     const u64 word = ballot(one);
     if (ln == 0) out[w] = word;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_ingest: the two kernels above fused with the upload's re-staging, for a chunk of f32 rows that sits in a
+// device staging buffer (hny_host.cpp, IngestPipe).  One pass over the input: every row is loaded once, and
+// the same registers feed the copy (or the ballot), the Cosine norm and the optional packed outputs.
+// V4: 16-byte loads (row stride a multiple of 16 bytes) and 16-byte stores of the packed codes (dim a multiple
+// of 4); rows of the builder's array are 16-byte aligned and padded, so they always take 16-byte stores.
+// ---------------------------------------------------------------------------------------------
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+// four consecutive floats x[e0 .. e0+3] of a row, zero where e >= dim
+template <bool V4>
+__device__ __forceinline__ f32x4 ingest_load4(const float *x, u32 e0, u32 dim) {
+  if (V4 && e0 + 4u <= dim) return __builtin_nontemporal_load((const f32x4 *)(x + e0));
+  f32x4 v;
+  v.x = e0 < dim ? __builtin_nontemporal_load(x + e0) : 0.f;
+  v.y = e0 + 1u < dim ? __builtin_nontemporal_load(x + e0 + 1u) : 0.f;
+  v.z = e0 + 2u < dim ? __builtin_nontemporal_load(x + e0 + 2u) : 0.f;
+  v.w = e0 + 3u < dim ? __builtin_nontemporal_load(x + e0 + 3u) : 0.f;
+  return v;
+}
+template <bool V4>
+__device__ __forceinline__ void ingest_store4(float *y, u32 e0, u32 lim, f32x4 v) { // elements below lim
+  if (V4 && e0 + 4u <= lim) {
+    *(f32x4 *)(y + e0) = v;
+    return;
+  }
+  if (e0 < lim) y[e0] = v.x;
+  if (e0 + 1u < lim) y[e0 + 1u] = v.y;
+  if (e0 + 2u < lim) y[e0 + 2u] = v.z;
+  if (e0 + 3u < lim) y[e0 + 3u] = v.w;
+}
+__device__ __forceinline__ float pick4(f32x4 v, u32 c) { return c == 0u ? v.x : c == 1u ? v.y : c == 2u ? v.z : v.w; }
+
+// f32 codecs: eight lanes per row.  Lane o of the eight holds elements 4o .. 4o+3 of every 32-float block, i.e.
+// partials 4o .. 4o+3 of the reference's 32 (AVX2) accumulators: each accumulator's chain runs over the blocks in
+// one lane, in the reference's order, and eight lanes read 128 contiguous bytes per load.
+template <bool V4>
+__global__ __launch_bounds__(256) void k_ingest_f32(IngestArgs a) {
+  const u32 ln = threadIdx.x & 63u, o = ln & 7u, obase = ln & ~7u;
+  const u32 dim = a.dim, m = dim & ~31u, pad_dim = a.row_stride / 4u;
+  const bool norm = a.codec == ING_F32_NORM;
+  const u64 wave0 = ((u64)blockIdx.x * 4u + (threadIdx.x >> 6)) * 8u, step = (u64)gridDim.x * 32u;
+  for (u64 r0 = wave0; r0 < a.cnt; r0 += step) { // wave-uniform: the shuffles below need every lane
+    const u64 row = r0 + (ln >> 3);
+    const bool valid = row < a.cnt;
+    const float *x = a.src + (valid ? row : 0) * a.src_stride;
+    const u32 slot = !valid ? 0u : a.slots ? a.slots[row] : a.slot_base + (u32)row;
+    float *drow = a.rows ? (float *)(a.rows + (u64)slot * a.row_stride) : nullptr;
+    float *prow = a.out_codes ? (float *)(a.out_codes + row * a.vb) : nullptr;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (u32 i = 0; i < m; i += 32u) {
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (valid) {
+        v = ingest_load4<V4>(x, i + 4u * o, dim);
+        if (drow) ingest_store4<true>(drow, i + 4u * o, pad_dim, v);
+        if (prow) ingest_store4<V4>(prow, i + 4u * o, dim, v);
+      }
+      if (norm) {
+        acc.x = sq_step_avx(v.x, acc.x);
+        acc.y = sq_step_avx(v.y, acc.y);
+        acc.z = sq_step_avx(v.z, acc.z);
+        acc.w = sq_step_avx(v.w, acc.w);
+      }
+    }
+    // the last, partial block [m, dim) with the zero padding of the destination row behind it
+    f32x4 t = {0.f, 0.f, 0.f, 0.f};
+    if (valid && m < pad_dim) {
+      t = ingest_load4<V4>(x, m + 4u * o, dim);
+      if (drow) ingest_store4<true>(drow, m + 4u * o, pad_dim, t);
+      if (prow) ingest_store4<V4>(prow, m + 4u * o, dim, t);
+    }
+    float r = 0.f;
+    if (norm) {
+      u32 e = 0; // first element of the tail block that the scalar loop takes
+      if (dim >= 32u) {
+        // hsum256 of accumulators 8q .. 8q+7 (lanes 2q, 2q+1): k + (k+4), then (0+2) + (1+3)
+        f32x4 s;
+        s.x = acc.x + __shfl_xor(acc.x, 1, 64);
+        s.y = acc.y + __shfl_xor(acc.y, 1, 64);
+        s.z = acc.z + __shfl_xor(acc.z, 1, 64);
+        s.w = acc.w + __shfl_xor(acc.w, 1, 64);
+        const float h = (s.x + s.z) + (s.y + s.w);
+        r = hsum_join4(__shfl(h, obase, 64), __shfl(h, obase + 2, 64), __shfl(h, obase + 4, 64),
+                       __shfl(h, obase + 6, 64));
+      } else if (dim >= 16u) {
+        // 16 unfused partials, one step each (a single block of 16), hsum128 per lane: (0+2) + (1+3)
+        const float h = (sq_step_sse(t.x, 0.f) + sq_step_sse(t.z, 0.f)) + (sq_step_sse(t.y, 0.f) + sq_step_sse(t.w, 0.f));
+        r = hsum_join4(__shfl(h, obase, 64), __shfl(h, obase + 1, 64), __shfl(h, obase + 2, 64),
+                       __shfl(h, obase + 3, 64));
+        e = 16u;
+      }
+      for (; e < dim - m; e++) r = sq_step_tail(__shfl(pick4(t, e & 3u), obase + (e >> 2), 64), r);
+      r = __builtin_sqrtf(r);
+    }
+    if (valid && o == 0u) {
+      if (a.norms) a.norms[slot] = r;
+      if (a.out_hdrs) *(float *)(a.out_hdrs + row * a.hb) = r; // bias 0.0 for Euclidean / Manhattan
+    }
+  }
+}
+
+// bit b of a 16-bit field -> bit 4b
+__device__ __forceinline__ u64 spread16x4(u64 x) {
+  x = (x | (x << 24)) & 0x000000FF000000FFull;
+  x = (x | (x << 12)) & 0x000F000F000F000Full;
+  x = (x | (x << 6)) & 0x0303030303030303ull;
+  x = (x | (x << 3)) & 0x1111111111111111ull;
+  return x;
+}
+
+// bit codecs: sixteen lanes per row, four floats per lane = one 64-dim word per load; the four ballots of the
+// wave hold bit 4l+c of the word at position l of the row's 16-bit field, spread16x4 puts them in place.
+template <bool V4>
+__global__ __launch_bounds__(256) void k_ingest_bits(IngestArgs a) {
+  const u32 ln = threadIdx.x & 63u, l = ln & 15u, grp = ln >> 4;
+  const u32 dim = a.dim, row_words = a.row_stride / 8u, words = a.vb / 8u;
+  const int binary_codec = a.codec == ING_BINARY;
+  const u64 wave0 = ((u64)blockIdx.x * 4u + (threadIdx.x >> 6)) * 4u, step = (u64)gridDim.x * 16u;
+  for (u64 r0 = wave0; r0 < a.cnt; r0 += step) { // wave-uniform: ballots
+    const u64 row = r0 + grp;
+    const bool valid = row < a.cnt;
+    const float *x = a.src + (valid ? row : 0) * a.src_stride;
+    const u32 slot = !valid ? 0u : a.slots ? a.slots[row] : a.slot_base + (u32)row;
+    u64 *drow = a.rows ? (u64 *)(a.rows + (u64)slot * a.row_stride) : nullptr;
+    u64 *prow = a.out_codes ? (u64 *)(a.out_codes + row * a.vb) : nullptr;
+    for (u32 w = 0; w < row_words; w++) { // the words of the zero padding included
+      const u32 e0 = w * 64u + 4u * l;
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (valid && e0 < dim) v = ingest_load4<V4>(x, e0, dim);
+      const u64 b0 = ballot(valid && e0 < dim && quantize_bit(__float_as_uint(v.x), binary_codec));
+      const u64 b1 = ballot(valid && e0 + 1u < dim && quantize_bit(__float_as_uint(v.y), binary_codec));
+      const u64 b2 = ballot(valid && e0 + 2u < dim && quantize_bit(__float_as_uint(v.z), binary_codec));
+      const u64 b3 = ballot(valid && e0 + 3u < dim && quantize_bit(__float_as_uint(v.w), binary_codec));
+      const u32 sh = 16u * grp;
+      const u64 word = spread16x4((b0 >> sh) & 0xFFFFull) | (spread16x4((b1 >> sh) & 0xFFFFull) << 1) |
+                       (spread16x4((b2 >> sh) & 0xFFFFull) << 2) | (spread16x4((b3 >> sh) & 0xFFFFull) << 3);
+      if (valid && l == 0u) {
+        if (drow) drow[w] = word;
+        if (prow && w < words) prow[w] = word;
+      }
+    }
+    if (valid && l == 0u) {
+      if (a.norms) a.norms[slot] = a.hdr_const;
+      if (a.out_hdrs) {
+        if (a.hb == 8u) *(u64 *)(a.out_hdrs + row * 8u) = 0ull; // hamming.rs:40-42 idx = 0usize
+        else *(float *)(a.out_hdrs + row * 4u) = a.hdr_const;
+      }
+    }
   }
 }
 
@@ -4576,6 +4729,23 @@ hipError_t hnyk_quantize(const float *v, u32 dim, u64 n, int binary_codec, u64 *
   u64 blocks = n * ((dim + 63) / 64);
   if (blocks > 1048576) blocks = 1048576;
   hipLaunchKernelGGL(k_quantize, dim3((unsigned)blocks), dim3(64), 0, st, v, dim, n, binary_codec, out);
+  return hipGetLastError();
+}
+hipError_t hnyk_ingest(const IngestArgs &a, hipStream_t st) {
+  if (!a.cnt) return hipSuccess;
+  const bool bits = a.codec == ING_BINARY || a.codec == ING_BQ;
+  // 16-byte accesses need 16-byte aligned rows on both sides (the builder's rows always are)
+  const bool v4 = a.src_stride % 4u == 0 && ((uintptr_t)a.src & 15u) == 0 &&
+                  (bits || !a.out_codes || (a.dim % 4u == 0 && ((uintptr_t)a.out_codes & 15u) == 0));
+  const u32 rows_per_block = bits ? 16u : 32u;
+  const unsigned grid = (unsigned)std::min<u64>(((u64)a.cnt + rows_per_block - 1) / rows_per_block, 8192);
+  if (bits) {
+    if (v4) hipLaunchKernelGGL(k_ingest_bits<true>, dim3(grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_ingest_bits<false>, dim3(grid), dim3(256), 0, st, a);
+  } else {
+    if (v4) hipLaunchKernelGGL(k_ingest_f32<true>, dim3(grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_ingest_f32<false>, dim3(grid), dim3(256), 0, st, a);
+  }
   return hipGetLastError();
 }
 hipError_t hnyk_fill_u32(u32 *p, u32 v, size_t n, hipStream_t st) {

@@ -320,9 +320,36 @@ size_t hny_header_bytes(int32_t metric);
 int hny_encode_vectors(int32_t metric, uint32_t dim, uint64_t n, const float *vectors,
                        void *out_codes, void *out_headers);
 /* the same on the GPU (bulk ingest): bit codecs by ballot, Cosine norms in the reference's x86
- * summation order (simple_avx.rs / simple_sse.rs / scalar) — byte-identical to the host path */
+ * summation order (simple_avx.rs / simple_sse.rs / scalar) — byte-identical to the host path.  Runs on the
+ * staging pipeline of the f32 entry points below; a caller that builds next wants those instead */
 int hny_encode_vectors_gpu(int32_t metric, uint32_t dim, uint64_t n, const float *vectors,
                            void *out_codes, void *out_headers, int32_t device);
+
+/* ---- f32 ingest: what Writer::add_item (src/writer.rs:462-480) and Reader::nns().by_vector
+ * (src/reader.rs:132-148) take in the reference.  `f32_items` is an hny_items whose `vectors` are f32 rows,
+ * `stride` bytes apart (>= dim * 4 and a multiple of 4, else HNY_ERR_INVALID_DIM / HNY_ERR_INVALID_ARG);
+ * `headers` is not read and may be NULL, `header_size` may be 0.  The rows travel to the device once, through
+ * pinned double buffers, and one kernel writes codec bytes and header norms at their final place while the next
+ * chunk is on its way: nothing is encoded on the host and no codes come back.  The results are byte
+ * for byte those of the calls above on hny_encode_vectors' output.  One GPU: with n_gpus > 1 or `devices` given
+ * they return HNY_ERR_UNSUPPORTED, decided from the options before any device is opened. ---- */
+int hny_build_f32(const hny_build_opts *opts, const hny_items *f32_items, hny_graph **out);
+int hny_build_incremental_f32(const hny_build_opts *opts, const hny_items *f32_items, const uint32_t *to_insert,
+                              uint64_t n_insert, const uint32_t *to_delete, uint64_t n_delete,
+                              const hny_prev_graph *prev, hny_graph **out);
+int hny_builder_create_f32(const hny_build_opts *opts, const hny_items *f32_items, hny_builder **out);
+int hny_builder_load_f32(const hny_build_opts *opts, const hny_items *f32_items, const hny_prev_graph *prev,
+                         hny_builder **out);
+/* the Item records' payload for hny_encode_kv: codes [n][hny_vector_bytes] and headers [n][hny_header_bytes]
+ * of the builder's items in ascending id order, read back from HBM (any builder, f32-created or not) */
+int hny_builder_export_items(hny_builder *b, void *out_codes, void *out_headers);
+/* hny_builder_search_knn / hny_builder_nns (by_vector; for by_item use hny_builder_nns) with the &[f32] the
+ * reference takes: every chunk of queries is encoded on the device by the kernel that encodes the items */
+int hny_builder_search_knn_f32(hny_builder *b, uint64_t n_queries, const float *queries, size_t qstride,
+                               uint32_t k, uint32_t ef_search, uint32_t *out_ids, float *out_dists,
+                               uint32_t *out_counts);
+int hny_builder_nns_f32(hny_builder *b, const hny_query_opts *opts, uint64_t n_queries, const float *queries,
+                        size_t qstride, uint32_t *out_ids, float *out_dists, uint32_t *out_counts);
 
 /* Diagnostic: runs the distance kernels' cross-lane primitives (DPP moves, v_permlane16/32_swap) next
  * to the generic __shfl_xor on one wave of `device` (-1 = current).  HNY_OK when every lane agrees;
