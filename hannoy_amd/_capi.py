@@ -36,6 +36,7 @@ EXPORTED = [
     "hny_multi_builder_destroy", "hny_abi_sizes", "hny_set_graph_cache",
     "hny_build_f32", "hny_build_incremental_f32", "hny_builder_create_f32", "hny_builder_load_f32",
     "hny_builder_export_items", "hny_builder_search_knn_f32", "hny_builder_nns_f32",
+    "hny_builder_create_update", "hny_builder_update", "hny_builder_finish_delta", "hny_graph_delta_free",
 ]
 ERR_IO = -9
 NNS_NONE = 0xFFFFFFFF  # by_item: the reference returns None
@@ -110,6 +111,27 @@ class PrevGraph(C.Structure):
     _fields_ = [("n_records", C.c_uint64), ("rec_item", C.c_void_p), ("rec_layer", C.c_void_p),
                 ("rec_offset", C.c_void_p), ("neighbours", C.c_void_p), ("entry_points", C.c_void_p),
                 ("n_entry_points", C.c_uint32), ("max_level", C.c_uint32)]
+
+
+class Update(C.Structure):
+    """hny_update; struct_size is the guard (the struct is not part of hny_abi_sizes)"""
+    _fields_ = [("struct_size", C.c_uint32), ("vectors_are_f32", C.c_int32), ("n_upsert", C.c_uint64),
+                ("upsert_ids", C.c_void_p), ("vectors", C.c_void_p), ("stride", C.c_size_t),
+                ("headers", C.c_void_p), ("header_size", C.c_size_t), ("levels", C.c_void_p),
+                ("seed", C.c_uint64), ("n_delete", C.c_uint64), ("delete_ids", C.c_void_p)]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_size = C.sizeof(Update)
+
+
+class GraphDeltaStruct(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("rec_item", C.POINTER(C.c_uint32)),
+                ("rec_layer", C.POINTER(C.c_uint8)), ("rec_offset", C.POINTER(C.c_uint64)),
+                ("neighbours", C.POINTER(C.c_uint32)), ("n_removed", C.c_uint64),
+                ("removed_item", C.POINTER(C.c_uint32)), ("removed_layer", C.POINTER(C.c_uint8)),
+                ("entry_points", C.POINTER(C.c_uint32)), ("n_entry_points", C.c_uint32),
+                ("max_level", C.c_uint32), ("n_records_total", C.c_uint64), ("t_export_s", C.c_double)]
 
 
 class Batch(C.Structure):
@@ -246,6 +268,15 @@ def load_library():
     L.hny_builder_search_knn_f32.argtypes = [vp, C.c_uint64, vp, C.c_size_t, C.c_uint32, C.c_uint32, vp, vp, vp]
     L.hny_builder_nns_f32.restype = C.c_int
     L.hny_builder_nns_f32.argtypes = [vp, C.POINTER(QueryOpts), C.c_uint64, vp, C.c_size_t, vp, vp, vp]
+    L.hny_builder_create_update.restype = C.c_int
+    L.hny_builder_create_update.argtypes = [vp, C.POINTER(Update), C.POINTER(vp)]
+    L.hny_builder_update.restype = C.c_int
+    L.hny_builder_update.argtypes = [C.POINTER(vp), C.POINTER(Update), C.POINTER(C.POINTER(GraphStruct)),
+                                     C.POINTER(C.POINTER(GraphDeltaStruct))]
+    L.hny_builder_finish_delta.restype = C.c_int
+    L.hny_builder_finish_delta.argtypes = [vp, C.POINTER(C.POINTER(GraphDeltaStruct))]
+    L.hny_graph_delta_free.restype = None
+    L.hny_graph_delta_free.argtypes = [C.POINTER(GraphDeltaStruct)]
     L.hny_abi_sizes.restype = C.c_uint32
     L.hny_abi_sizes.argtypes = [C.POINTER(C.c_uint32), C.c_uint32]
     _check_abi(L)
@@ -460,6 +491,18 @@ class F32ItemSet:
         return self.encoded().headers
 
 
+class _IdsOnly:
+    """the items of a successor Builder as far as the host knows them: ids (rows and codes live in HBM;
+    Builder.export_items reads them back)"""
+    f32 = False
+
+    def __init__(self, metric, dim, ids):
+        self.metric, self.dim, self.ids, self.n, self.levels = int(metric), int(dim), ids, len(ids), None
+
+    def encoded(self):
+        raise HannoyError(ERR_UNSUPPORTED, "the items of an updated builder live on the device: Builder.export_items()")
+
+
 def make_opts(metric, dim, M=16, M0=32, ef_construction=100, alpha=1.0, seed=42, batch_frac=0.0,
               batch_max=0, device=-1, cancel=None, progress=None, x86_order=False, n_gpus=0, devices=None,
               schedule=0):
@@ -564,6 +607,62 @@ class Graph:
             w.abort()
             raise
         w.finish()
+
+
+class GraphDelta:
+    """Host view of hny_graph_delta: what the write loop has to put (`rec_item` / `rec_layer` / `offsets` / `nbrs`:
+    records that are new or whose list changed) and to delete (`removed_item` / `removed_layer`) after an update.
+    The arrays are numpy views of library-owned memory, freed with the object."""
+
+    def __init__(self, dp, opts=None):
+        d = dp.contents
+        self._dp, self._opts = dp, opts
+        nr, nm, ne = d.n_records, d.n_removed, d.n_entry_points
+        self.max_level, self.n_records_total, self.t_export_s = d.max_level, d.n_records_total, d.t_export_s
+        self.rec_item = np.ctypeslib.as_array(d.rec_item, (max(nr, 1),))[:nr]
+        self.rec_layer = np.ctypeslib.as_array(d.rec_layer, (max(nr, 1),))[:nr]
+        self.offsets = np.ctypeslib.as_array(d.rec_offset, (nr + 1,))
+        nl = int(self.offsets[-1])
+        self.nbrs = np.ctypeslib.as_array(d.neighbours, (max(nl, 1),))[:nl]
+        self.removed_item = np.ctypeslib.as_array(d.removed_item, (max(nm, 1),))[:nm]
+        self.removed_layer = np.ctypeslib.as_array(d.removed_layer, (max(nm, 1),))[:nm]
+        self.entry_points = np.ctypeslib.as_array(d.entry_points, (max(ne, 1),))[:ne]
+
+    def __del__(self):
+        try:
+            if getattr(self, "_dp", None) is not None:
+                for f in ("rec_item", "rec_layer", "offsets", "nbrs", "removed_item", "removed_layer", "entry_points"):
+                    self.__dict__.pop(f, None)  # the views die with the memory
+                load_library().hny_graph_delta_free(self._dp)
+                self._dp = None
+        except Exception:  # interpreter shutdown
+            pass
+
+    def as_dict(self):
+        return {(int(self.rec_item[r]), int(self.rec_layer[r])):
+                self.nbrs[int(self.offsets[r]):int(self.offsets[r + 1])].tolist()
+                for r in range(len(self.rec_item))}
+
+    def removed_keys(self):
+        return [(int(i), int(l)) for i, l in zip(self.removed_item, self.removed_layer)]
+
+    def encode_kv(self, item_ids, index=0):
+        """Metadata, Version and the Links records of the delta as byte-exact (key, value) pairs (hny_encode_kv on the
+        delta's records); `item_ids`: every item of the index after the update, ascending (Metadata.items)"""
+        d = self._dp.contents
+        g = GraphStruct()
+        g.n_records, g.rec_item, g.rec_layer, g.rec_offset = d.n_records, d.rec_item, d.rec_layer, d.rec_offset
+        g.neighbours, g.entry_points, g.n_entry_points, g.max_level = d.neighbours, d.entry_points, d.n_entry_points, d.max_level
+        ids = np.ascontiguousarray(item_ids, np.uint32)
+        it = Items(len(ids), _p(ids).value, None, 0, None, 0, None)
+        out = []
+
+        def sink(_ctx, k, kl, v, vl):
+            out.append((bytes(k[:kl]), bytes(v[:vl])))
+            return 0
+        cb = KV_SINK(sink)
+        _check(load_library().hny_encode_kv(C.byref(g), C.byref(self._opts), C.byref(it), index, 0, cb, None))
+        return out
 
 
 class LmdbWriter:
@@ -863,6 +962,67 @@ class Builder:
         gp = C.POINTER(GraphStruct)()
         _check(load_library().hny_builder_finish(self._h, C.byref(gp)))
         return Graph(gp, self.opts, self.items)
+
+    # -- resident updates (hny_builder_create_update / hny_builder_update) --------------
+    def _update_struct(self, upsert_ids, vectors, codes, headers, delete_ids, levels, seed):
+        u = Update()
+        keep = [np.ascontiguousarray(upsert_ids, np.uint32), np.ascontiguousarray(delete_ids, np.uint32)]
+        u.n_upsert, u.upsert_ids = len(keep[0]), _p(keep[0]).value
+        u.n_delete, u.delete_ids = len(keep[1]), _p(keep[1]).value
+        u.seed = int(seed)
+        if vectors is not None:
+            v = _f32_rows(vectors) if len(keep[0]) else np.zeros((0, self.items.dim), np.float32)
+            u.vectors_are_f32, u.vectors = 1, _p(v).value
+            u.stride = v.strides[0] if len(v) > 1 else v.shape[1] * 4
+            keep.append(v)
+        else:
+            c = np.ascontiguousarray(codes if codes is not None else np.zeros((0, 1)), np.uint8)
+            h = np.ascontiguousarray(headers if headers is not None else np.zeros((0, 1)), np.uint8)
+            u.vectors, u.stride = _p(c).value, c.shape[1] if c.ndim == 2 else 0
+            u.headers, u.header_size = _p(h).value, h.shape[1] if h.ndim == 2 else 0
+            keep += [c, h]
+        if levels is not None:
+            lv = np.ascontiguousarray(levels, np.uint8)
+            u.levels = _p(lv).value
+            keep.append(lv)
+        return u, keep
+
+    def _successor(self, handle, keep):
+        ids = np.union1d(np.setdiff1d(self.items.ids, keep[1]), keep[0]).astype(np.uint32)
+        b = Builder.__new__(Builder)
+        b.items = _IdsOnly(self.items.metric, self.items.dim, ids)
+        b.opts, b.incremental, b._h = self.opts, True, handle
+        return b
+
+    def create_update(self, upsert_ids=(), vectors=None, codes=None, headers=None, delete_ids=(), levels=None, seed=42):
+        """hny_builder_create_update: an incremental Builder made from this (finished or loaded) builder device to
+        device; `vectors` = f32 rows of the upserts, or `codes` + `headers`.  This builder stays usable."""
+        u, keep = self._update_struct(upsert_ids, vectors, codes, headers, delete_ids, levels, seed)
+        h = C.c_void_p()
+        _check(load_library().hny_builder_create_update(self._h, C.byref(u), C.byref(h)))
+        return self._successor(h, keep)
+
+    def update(self, upsert_ids=(), vectors=None, codes=None, headers=None, delete_ids=(), levels=None, seed=42,
+               full=True, delta=False):
+        """hny_builder_update: this Builder becomes its successor (every batch + fill_gaps run); returns the complete
+        Graph, the GraphDelta, or (Graph, GraphDelta) as asked"""
+        u, keep = self._update_struct(upsert_ids, vectors, codes, headers, delete_ids, levels, seed)
+        gp, dp = C.POINTER(GraphStruct)(), C.POINTER(GraphDeltaStruct)()
+        if self._borrowed:
+            raise HannoyError(ERR_INVALID_ARG, "a borrowed replica cannot be replaced: use create_update()")
+        _check(load_library().hny_builder_update(C.byref(self._h), C.byref(u), C.byref(gp) if full else None,
+                                                 C.byref(dp) if delta else None))
+        succ = self._successor(self._h, keep)
+        self.items, self.incremental = succ.items, True
+        succ._h = C.c_void_p()  # (the handle stays with this object)
+        g = Graph(gp, self.opts, self.items) if full else None
+        d = GraphDelta(dp, self.opts) if delta else None
+        return (g, d) if full and delta else g if full else d
+
+    def finish_delta(self):
+        dp = C.POINTER(GraphDeltaStruct)()
+        _check(load_library().hny_builder_finish_delta(self._h, C.byref(dp)))
+        return GraphDelta(dp, self.opts)
 
     def distances(self, slot_a, slot_b):
         a = np.ascontiguousarray(slot_a, np.uint32)

@@ -122,6 +122,7 @@ class Database:
         capi.load_library()
         self.distance = distance
         self.kv = {}
+        self.build_generation = {}  # index -> builds any Writer has run on it (a resident Writer checks it)
         self.path, self.name, self.env_size = path, name, env_size
         if path is not None:
             os.makedirs(path, exist_ok=True)
@@ -140,8 +141,11 @@ class Database:
                 w.put(k, self.kv[k])
         os.replace(tmp, os.path.join(self.path, "data.mdb"))
 
-    def writer(self, dimensions, index=0, m=16, ef=96):
-        return Writer(self, dimensions, index, m, ef)
+    def writer(self, dimensions, index=0, m=16, ef=96, resident=False):
+        """resident=True: the Writer keeps the builder of its last build in HBM; the next build() on the same Writer
+        goes through hny_builder_update (only the changed items travel, only the changed Links records are
+        rewritten).  The records it leaves are those of the default path, byte for byte."""
+        return Writer(self, dimensions, index, m, ef, resident)
 
     def reader(self, index=0):
         return Reader(self, index)
@@ -186,10 +190,19 @@ class Writer:
     """hannoy.pyi Writer / src/writer.rs Writer + HannoyBuilder.  As in python.rs:305-314 the build
     runs when the `with` block exits (M0 = 2*m, StdRng::seed_from_u64(42), python.rs:118-120,261)."""
 
-    def __init__(self, db, dimensions, index=0, m=16, ef=96):
+    def __init__(self, db, dimensions, index=0, m=16, ef=96, resident=False):
         self.db, self.dimensions, self.index, self.m, self.ef = db, int(dimensions), index, m, ef
         self.alpha, self.seed = 1.0, 42
         self.last_graph = None
+        # resident=True: the builder of the last build, the options it was made with and the items it indexes
+        self.resident, self._rb, self._rb_kw, self._rb_ids, self._rb_gen = bool(resident), None, None, None, -1
+        self.last_delta = None  # resident: the GraphDelta of the last build that went through hny_builder_update
+
+    def close(self):
+        """releases the resident builder (a Writer without one holds nothing)"""
+        if self._rb is not None:
+            self._rb.close()
+            self._rb = None
 
     def __enter__(self):
         return self
@@ -334,28 +347,83 @@ class Writer:
             to_delete = sorted(all_updated - item_indices)
             to_insert = sorted(item_indices & all_updated)
         ids = np.array(sorted(item_indices), np.uint32)
-        items = db.item_set(index, ids, self.dimensions)
         kw = dict(M=self.m, M0=2 * self.m, ef_construction=self.ef, alpha=self.alpha, seed=self.seed)
         kw.update(opts)
         if rng is not None and levels is None:  # get_random_level per to_insert id, ascending (hnsw.rs:142-149)
             levels = dict(zip(to_insert, rng.draw_levels(kw["M"], len(to_insert)).tolist()))
-        prev = _StoredGraph(db, index)
-        if len(prev.rec_item) == 0 and meta is None:
-            if levels is not None:
-                items.levels = np.array([levels[int(i)] for i in ids], np.uint8)
-            g = capi.build(items, **kw)
+        if self.resident:
+            g = self._build_resident(meta, indexed, ids, to_insert, to_delete, levels, relink_all_items, kw)
         else:
-            if levels is not None:
-                items.levels = np.array([levels[int(i)] for i in to_insert], np.uint8)
-            g = capi.build_incremental(items, prev, to_insert, to_delete, **kw)
+            g, _ = self._build_all_records(meta, ids, to_insert, to_delete, levels, kw, keep_builder=False)
+        db.build_generation[index] = db.build_generation.get(index, 0) + 1
+        self.last_graph = g
+        return g
+
+    def _build_all_records(self, meta, ids, to_insert, to_delete, levels, kw, keep_builder):
+        """every item read from the store, the stored graph as `prev`, and every Links record written back.
+        keep_builder: build stepwise on a Builder and return it alive (the resident Writer keeps it) instead of
+        the one-call hny_build / hny_build_incremental; the graphs are the same."""
+        db, index = self.db, self.index
+        items = db.item_set(index, ids, self.dimensions)
+        prev = _StoredGraph(db, index)
+        fresh = len(prev.rec_item) == 0 and meta is None
+        if levels is not None:
+            items.levels = np.array([levels[int(i)] for i in (ids if fresh else to_insert)], np.uint8)
+        b = None
+        if not keep_builder:
+            g = capi.build(items, **kw) if fresh else capi.build_incremental(items, prev, to_insert, to_delete, **kw)
+        else:
+            b = capi.Builder(items, **kw) if fresh else capi.Builder(items, prev=prev, to_insert=to_insert,
+                                                                     to_delete=to_delete, **kw)
+            try:
+                b.run()
+                g = b.finish()
+            except BaseException:
+                b.close()
+                raise
         # write-back: every Links record of the new state (hnsw.rs:195-213) — stale ones and those
         # of deleted items go (writer.rs:580) —, then Metadata and Version (writer.rs:585-600)
-        llo, lhi = key(index, MODE_LINKS), key(index, MODE_LINKS, 0xFFFFFFFF, 0xFF)
-        for k in [k for k in db.kv if llo <= k <= lhi]:
-            del db.kv[k]
-        for k, v in g.encode_kv(index, with_items=False):
-            db.kv[k] = v
-        self.last_graph = g
+        try:
+            llo, lhi = key(index, MODE_LINKS), key(index, MODE_LINKS, 0xFFFFFFFF, 0xFF)
+            for k in [k for k in db.kv if llo <= k <= lhi]:
+                del db.kv[k]
+            for k, v in g.encode_kv(index, with_items=False):
+                db.kv[k] = v
+        except BaseException:
+            if b is not None:
+                b.close()
+            raise
+        return g, b
+
+    def _build_resident(self, meta, indexed, ids, to_insert, to_delete, levels, relink_all_items, kw):
+        """_build with the builder kept in HBM.  The held builder is updated in place (hny_builder_update) and the
+        write-back applies the delta when (1) the options and the distance are the ones it was made with, (2) it
+        indexes exactly what the Metadata record says is indexed, and (3) no other build has touched this index of
+        the Database since (Database.build_generation).  Anything else — first build, other options, force_rebuild,
+        a build by another Writer — goes through _build_all_records and keeps that builder for the next round.
+        (Records edited directly in Database.kv are not detected.)"""
+        db, index = self.db, self.index
+        opts_key = dict({k: v for k, v in kw.items() if k != "seed"}, metric=db.distance.value)
+        if (self._rb is not None and opts_key == self._rb_kw and not relink_all_items and meta is not None
+                and self._rb_gen == db.build_generation.get(index, 0) and set(self._rb_ids.tolist()) == indexed):
+            ups = db.item_set(index, np.array(to_insert, np.uint32), self.dimensions)
+            lv = None if levels is None else np.array([levels[int(i)] for i in to_insert], np.uint8)
+            g, d = self._rb.update(to_insert, codes=ups.codes, headers=ups.headers, delete_ids=to_delete, levels=lv,
+                                   seed=kw.get("seed", 42), full=True, delta=True)
+            try:  # the builder is its successor now: if the store cannot follow, the two no longer match
+                for item, layer in d.removed_keys():  # delete_links_from_db (writer.rs:692-718)
+                    del db.kv[key(index, MODE_LINKS, item, layer)]
+                for k, v in d.encode_kv(ids, index):  # the changed Links records, Metadata, Version
+                    db.kv[k] = v
+            except BaseException:
+                self.close()
+                raise
+            self.last_delta = d
+        else:
+            self.close()
+            g, self._rb = self._build_all_records(meta, ids, to_insert, to_delete, levels, kw, keep_builder=True)
+            self._rb_kw = opts_key
+        self._rb_ids, self._rb_gen = ids, db.build_generation.get(index, 0) + 1
         return g
 
 

@@ -16,6 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <iterator>
 #include <memory>
 #include <string>
 #include <thread>
@@ -314,6 +315,9 @@ struct hny_builder {
   std::vector<uint8_t> deleted;       // incremental: slot is in to_delete
   std::vector<u64> old_recs;          // incremental: surviving old records, layer << 31 | slot
   bool incremental = false;
+  bool load_only = false;             // hny_builder_load: the stored graph as it is (lists live in d_d0_ids / d_du_ids)
+  bool gaps_done = false;             // incremental: fill_gaps has run since the last reset
+  bool from_update = false;           // made by hny_builder_create_update: d_d0_ids / d_du_ids are its source's lists
   uint64_t n_done0 = 0;
   uint32_t up_layers = 1;
   std::vector<uint32_t> entry_points; // slots ascending
@@ -414,6 +418,9 @@ struct hny_builder {
   size_t ev_used = 0;
   bool profiling = false;
   uint64_t n_walk_dispatch = 0; // k_walk launches since the last reset
+  // successor builders whose source was profiling: device time (HIP events) and bytes read + written of k_move_rows
+  double t_move_rows_s = 0;
+  uint64_t move_rows_bytes = 0;
   ~hny_builder() {
     for (auto &e : sync_evs) (void)hipEventDestroy(e);
     if (h_l0) (void)hipHostFree(h_l0);
@@ -699,6 +706,7 @@ int reset_graph(hny_builder *b) {
   b->n_batches = 0;
   b->in_batch = false;
   b->finalized = false;
+  b->gaps_done = false;
   b->ev_used = 0;
   b->n_walk_dispatch = 0;
   b->sync_used = 0;
@@ -892,7 +900,165 @@ struct IncrementalSpec {
   uint64_t n_delete;
   const hny_prev_graph *prev;
   bool load_only = false; // Reader::open: the stored graph as it is, nothing gets (re)inserted
+  // hny_builder_create_update: the previous state is a finished builder on the device instead of `prev` on the host
+  // (then `items` carries the ids of the items after the update only; the upserted rows come from `upd`)
+  hny_builder *src = nullptr;
+  const hny_update *upd = nullptr;
 };
+
+// which (slot, layer) records a builder's finish() exports: bit l = layer l
+static inline uint32_t rec_mask_of(const hny_builder *b, uint32_t s) {
+  if (b->deleted[s]) return 0u;
+  uint32_t m = b->old_mask[s];
+  if (b->ins_level[s] >= 0) m |= (2u << b->ins_level[s]) - 1u;
+  return m;
+}
+// slots of a builder that hold an item's row
+static std::vector<uint8_t> live_slots(const hny_builder *b) {
+  if (!b->incremental) return std::vector<uint8_t>(b->n, 1);
+  std::vector<uint8_t> live(b->n, 0);
+  for (uint32_t s : b->item_slot) live[s] = 1;
+  return live;
+}
+
+// Resident update (hny_builder_create_update): rows, norms and the finalised lists of `src` go to their slots in
+// the successor `b` device to device, then the upserted rows land on top (same stream: an overwritten item ends
+// with its new row).  Host -> device: the two slot maps, one u16 mask per slot, the upper-index table, the upserts.
+static int move_state_from_source(hny_builder *b, hny_builder *src, const hny_update *u,
+                                  const std::vector<uint32_t> &src_of, const std::vector<uint32_t> &new_of,
+                                  const std::vector<uint8_t> &src_live, const std::vector<uint32_t> &up_slots,
+                                  IngestPipe &pipe) {
+  hipStream_t st = b->stream;
+  const hny_build_opts &o = b->o;
+  GraphDev &g = b->g;
+  const uint32_t n = b->n;
+  const bool has_norm = o.metric == HNY_COSINE || o.metric == HNY_BQ_COSINE;
+  const size_t vb = vec_bytes(o.metric, o.dim), hb = hdr_bytes(o.metric);
+  // the source's lists: a loaded graph keeps them where it put them (d_d0_ids / d_du_ids, nothing was inserted);
+  // a built one in l0_ids / up_ids, finalised (finish() and the searches do that; do it here if neither ran)
+  if (!src->load_only && !src->finalized) {
+    HIP_TRY(hnyk_finalize_lists(src->d_l0_ids.p, src->d_fin_cnt0.p, src->n, o.M0, src->stream));
+    HIP_TRY(hnyk_finalize_lists(src->d_up_ids.p, src->d_fin_cntu.p, (u32)((size_t)src->n_upper * src->up_layers), o.M,
+                                src->stream));
+    src->finalized = true;
+  }
+  HIP_TRY(hipStreamSynchronize(src->stream));
+  std::vector<unsigned short> mask(n);
+  for (uint32_t t = 0; t < n; t++)
+    mask[t] = (unsigned short)(b->old_mask[t] | (src_of[t] != HNY_SENT && src_live[src_of[t]] ? HNY_MV_LIVE : 0u));
+  std::vector<u32> up_slot(std::max<uint32_t>(b->n_upper, 1), 0);
+  for (uint32_t t = 0; t < n; t++)
+    if (b->upper_idx[t] >= 0) up_slot[b->upper_idx[t]] = t;
+  DevBuf<u32> d_src_of, d_new_of, d_up_slot, d_ups;
+  DevBuf<unsigned short> d_mask;
+  DevBuf<u64> d_bad;
+  HIP_TRY(d_src_of.alloc(n));
+  HIP_TRY(d_new_of.alloc(std::max<uint32_t>(src->n, 1)));
+  HIP_TRY(d_mask.alloc(n));
+  HIP_TRY(d_up_slot.alloc(up_slot.size()));
+  HIP_TRY(d_bad.alloc(1));
+  HIP_TRY(hipMemcpyAsync(d_src_of.p, src_of.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+  if (src->n) HIP_TRY(hipMemcpyAsync(d_new_of.p, new_of.data(), (size_t)src->n * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_mask.p, mask.data(), (size_t)n * 2, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_up_slot.p, up_slot.data(), up_slot.size() * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(d_bad.p, 0, 8, st));
+  // rows + norms
+  MoveRowsArgs mr{};
+  mr.src_rows = src->d_rows.p;
+  mr.src_norms = has_norm ? src->d_norms.p : nullptr;
+  mr.src_of = d_src_of.p;
+  mr.mask = d_mask.p;
+  mr.dst_rows = b->d_rows.p;
+  mr.dst_norms = has_norm ? b->d_norms.p : nullptr;
+  mr.n_new = n;
+  mr.n16 = g.n16;
+  // hny_builder_set_profiling(src, 1): device time and bytes of k_move_rows (scripts/update_throughput.py)
+  struct EvPair {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~EvPair() {
+      if (a) (void)hipEventDestroy(a);
+      if (b) (void)hipEventDestroy(b);
+    }
+  } ev;
+  if (src->profiling) {
+    HIP_TRY(hipEventCreate(&ev.a));
+    HIP_TRY(hipEventCreate(&ev.b));
+    HIP_TRY(hipEventRecord(ev.a, st));
+  }
+  HIP_TRY(hnyk_move_rows(mr, st));
+  if (src->profiling) HIP_TRY(hipEventRecord(ev.b, st));
+  // upserts
+  DevBuf<unsigned char> d_stage;
+  DevBuf<float> d_stage_norms;
+  std::vector<float> up_norms;
+  if (u->n_upsert) {
+    HIP_TRY(d_ups.alloc(u->n_upsert));
+    HIP_TRY(hipMemcpyAsync(d_ups.p, up_slots.data(), (size_t)u->n_upsert * 4, hipMemcpyHostToDevice, st));
+    if (u->vectors_are_f32) {
+      HIP_TRY(hipStreamSynchronize(st)); // (d_ups is read by kernels behind copies of the pipe's own stream)
+      IngestJob j;
+      j.d_slots = d_ups.p;
+      j.metric = o.metric;
+      j.dim = o.dim;
+      j.src = u->vectors;
+      j.stride = u->stride;
+      j.n = u->n_upsert;
+      j.rows = b->d_rows.p;
+      j.row_stride = g.row_stride;
+      j.norms = has_norm ? b->d_norms.p : nullptr;
+      if (int rc = run_ingest(pipe, j, st)) return rc;
+    } else {
+      HIP_TRY(d_stage.alloc((size_t)u->n_upsert * g.row_stride));
+      if (int rc = upload_rows(u->vectors, u->stride, vb, u->n_upsert, g.row_stride, d_stage.p, st)) return rc;
+      if (has_norm) {
+        up_norms.resize(u->n_upsert);
+        for (uint64_t i = 0; i < u->n_upsert; i++) memcpy(&up_norms[i], (const unsigned char *)u->headers + i * hb, 4);
+        HIP_TRY(d_stage_norms.alloc(u->n_upsert));
+        HIP_TRY(hipMemcpyAsync(d_stage_norms.p, up_norms.data(), (size_t)u->n_upsert * 4, hipMemcpyHostToDevice, st));
+      }
+      HIP_TRY(hnyk_scatter_rows(d_stage.p, d_stage_norms.p, d_ups.p, b->d_rows.p, has_norm ? b->d_norms.p : nullptr,
+                                (u32)u->n_upsert, g.n16, st));
+    }
+  }
+  // lists: records of to-be-deleted and overwritten items move like any other (the build expects them in `prev`)
+  const size_t nup = (size_t)b->n_upper * b->up_layers;
+  HIP_TRY(b->d_d0_ids.alloc((size_t)n * o.M0));
+  HIP_TRY(b->d_du_ids.alloc(std::max<size_t>(nup * o.M, 1)));
+  MoveListsArgs ml{};
+  ml.src_l0_ids = src->load_only ? src->d_d0_ids.p : src->d_l0_ids.p;
+  ml.src_up_ids = src->load_only ? src->d_du_ids.p : src->d_up_ids.p;
+  ml.src_upper_idx = src->d_upper_idx.p;
+  ml.src_up_layers = src->up_layers;
+  ml.n_src = src->n;
+  ml.src_of = d_src_of.p;
+  ml.new_of = d_new_of.p;
+  ml.mask = d_mask.p;
+  ml.up_slot = d_up_slot.p;
+  ml.dst_d0_ids = b->d_d0_ids.p;
+  ml.dst_du_ids = b->d_du_ids.p;
+  ml.n_new = n;
+  ml.n_upper = b->n_upper;
+  ml.up_layers = b->up_layers;
+  ml.M = o.M;
+  ml.M0 = o.M0;
+  ml.bad = d_bad.p;
+  if (!nup) HIP_TRY(hnyk_fill_u32(b->d_du_ids.p, HNY_SENT, b->d_du_ids.n, st));
+  HIP_TRY(hnyk_move_lists(ml, st));
+  u64 bad = 0;
+  HIP_TRY(hipMemcpyAsync(&bad, d_bad.p, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (src->profiling) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, ev.a, ev.b) == hipSuccess) b->t_move_rows_s = ms * 1e-3;
+    uint64_t moved = 0;
+    for (uint32_t t = 0; t < n; t++) moved += (mask[t] & HNY_MV_LIVE) ? 2 : 1; // read + write, or the zero row written
+    b->move_rows_bytes = moved * g.row_stride;
+  }
+  if (bad)
+    return fail(HNY_ERR_DEVICE, "update: %llu neighbours of the source's lists name a slot that owns no record — the "
+                "slot universe cannot be derived without the lists (DESIGN.md §3c)", (unsigned long long)bad);
+  return HNY_OK;
+}
 
 // f32: items->vectors are f32 rows (Writer::add_item's input, writer.rs:462-480) that the device encodes while they
 // arrive (run_ingest); items->headers is not read
@@ -920,9 +1086,12 @@ static int create_impl(const hny_build_opts *opts, const hny_items *items, const
                 HNY_MAX_EF);
   if (items->n >= (1ull << 31)) return fail(HNY_ERR_UNSUPPORTED, "n >= 2^31");
   const size_t vb = vec_bytes(o.metric, o.dim), hb = hdr_bytes(o.metric);
-  if (items->n && (!items->ids || !items->vectors || (!f32 && !items->headers)))
+  hny_builder *const src = inc ? inc->src : nullptr; // resident update: rows and lists come from this builder
+  if (items->n && (!items->ids || (!src && (!items->vectors || (!f32 && !items->headers)))))
     return fail(HNY_ERR_INVALID_ARG, "null item arrays");
-  if (f32) {
+  if (src) {
+    // (hny_builder_create_update has checked the upserted rows)
+  } else if (f32) {
     int rcf = check_f32_rows(o.dim, items->n, items->vectors, items->stride);
     if (rcf) return rcf;
   } else {
@@ -940,6 +1109,8 @@ static int create_impl(const hny_build_opts *opts, const hny_items *items, const
   b->frac = o.batch_frac > 0.0 ? o.batch_frac : 1.0;
   b->bmax = o.batch_max ? o.batch_max : hny_default_batch_max(items->n);
   b->incremental = inc != nullptr;
+  b->load_only = inc && inc->load_only;
+  b->from_update = src != nullptr;
   uint32_t n16;
   int rc = pick_shape(o.metric, o.dim, b->shape, n16);
   if (rc) return rc;
@@ -961,14 +1132,25 @@ static int create_impl(const hny_build_opts *opts, const hny_items *items, const
   // mentions (ids ascending => slot order == id order) ----
   std::vector<uint32_t> &U = b->ids;
   U.assign(items->ids, items->ids + items->n);
+  std::vector<uint8_t> src_live; // source builder: slots that hold a row
   if (inc) {
     const hny_prev_graph *pg = inc->prev;
-    if (!pg || (inc->n_insert && !inc->to_insert) || (inc->n_delete && !inc->to_delete))
+    if ((!pg && !src) || (inc->n_insert && !inc->to_insert) || (inc->n_delete && !inc->to_delete))
       return fail(HNY_ERR_INVALID_ARG, "incremental: null argument");
     U.insert(U.end(), inc->to_delete, inc->to_delete + inc->n_delete);
-    U.insert(U.end(), pg->rec_item, pg->rec_item + pg->n_records);
-    if (pg->n_records) U.insert(U.end(), pg->neighbours, pg->neighbours + pg->rec_offset[pg->n_records]);
-    U.insert(U.end(), pg->entry_points, pg->entry_points + pg->n_entry_points);
+    if (src) {
+      // The host holds no lists of the source and does not fetch them: every slot that owns a record or a row,
+      // and the entry points.  Equal to what the branch below computes from the exported graph iff no finalised
+      // list names a slot without records — k_move_lists counts the entries that would.
+      src_live = live_slots(src);
+      for (uint32_t s = 0; s < src->n; s++)
+        if (rec_mask_of(src, s) || src_live[s]) U.push_back(src->ids[s]);
+      for (uint32_t s : src->entry_points) U.push_back(src->ids[s]);
+    } else {
+      U.insert(U.end(), pg->rec_item, pg->rec_item + pg->n_records);
+      if (pg->n_records) U.insert(U.end(), pg->neighbours, pg->neighbours + pg->rec_offset[pg->n_records]);
+      U.insert(U.end(), pg->entry_points, pg->entry_points + pg->n_entry_points);
+    }
     std::sort(U.begin(), U.end());
     U.erase(std::unique(U.begin(), U.end()), U.end());
     if (U.size() >= (1ull << 31)) return fail(HNY_ERR_UNSUPPORTED, "n >= 2^31");
@@ -987,6 +1169,7 @@ static int create_impl(const hny_build_opts *opts, const hny_items *items, const
   b->old_mask.assign(n, 0);
   b->deleted.assign(n, 0);
   std::vector<std::pair<uint32_t, uint8_t>> levels; // (slot, level) in the reference's order
+  std::vector<uint32_t> src_of, new_of; // source builder: successor slot -> source slot and back, HNY_SENT = none
 
   if (!inc) {
     // ---- levels (hnsw.rs:141-149) + prepare_levels_and_entry_points, fresh DB (:222-289) ----
@@ -1006,9 +1189,31 @@ static int create_impl(const hny_build_opts *opts, const hny_items *items, const
     // deletion branch of prepare_levels_and_entry_points (:236-289) ----
     const hny_prev_graph *pg = inc->prev;
     for (uint64_t i = 0; i < inc->n_delete; i++) b->deleted[slot_of(inc->to_delete[i])] = 1;
-    for (uint64_t r = 0; r < pg->n_records; r++) {
-      if (pg->rec_layer[r] > HNY_MAX_LEVEL) return fail(HNY_ERR_INVALID_ARG, "old record on layer > %d", HNY_MAX_LEVEL);
-      b->old_mask[slot_of(pg->rec_item[r])] |= (uint16_t)(1u << pg->rec_layer[r]);
+    // the previous state: which records exist, entry points, max_level — from `prev`, or from the source builder
+    std::vector<uint32_t> prev_eps; // slots
+    uint32_t prev_max_level = 0;
+    if (src) {
+      // both universes ascend with the item ids: one merge gives both slot maps
+      src_of.assign(n, HNY_SENT);
+      new_of.assign(src->n, HNY_SENT);
+      for (uint32_t s = 0, t = 0; s < src->n && t < n; s++) {
+        while (t < n && U[t] < src->ids[s]) t++;
+        if (t < n && U[t] == src->ids[s]) {
+          src_of[t] = s;
+          new_of[s] = t;
+        }
+      }
+      for (uint32_t t = 0; t < n; t++)
+        if (src_of[t] != HNY_SENT) b->old_mask[t] = (uint16_t)rec_mask_of(src, src_of[t]);
+      for (uint32_t s : src->entry_points) prev_eps.push_back(new_of[s]);
+      prev_max_level = src->max_level;
+    } else {
+      for (uint64_t r = 0; r < pg->n_records; r++) {
+        if (pg->rec_layer[r] > HNY_MAX_LEVEL) return fail(HNY_ERR_INVALID_ARG, "old record on layer > %d", HNY_MAX_LEVEL);
+        b->old_mask[slot_of(pg->rec_item[r])] |= (uint16_t)(1u << pg->rec_layer[r]);
+      }
+      for (uint32_t i = 0; i < pg->n_entry_points; i++) prev_eps.push_back(slot_of(pg->entry_points[i]));
+      prev_max_level = pg->max_level;
     }
     std::vector<uint8_t> lv(inc->n_insert);
     if (items->levels)
@@ -1024,12 +1229,11 @@ static int create_impl(const hny_build_opts *opts, const hny_items *items, const
       levels.push_back({s, lv[i]});
       cur_max = std::max<uint32_t>(cur_max, lv[i]);
     }
-    uint32_t max_level = pg->max_level;
+    uint32_t max_level = prev_max_level;
     std::vector<uint8_t> in_new(n, 0), in_old(n, 0);
     uint32_t n_old = 0, n_new = 0;
     std::vector<uint32_t> del_eps;
-    for (uint32_t i = 0; i < pg->n_entry_points; i++) {
-      uint32_t s = slot_of(pg->entry_points[i]);
+    for (uint32_t s : prev_eps) {
       if (!in_old[s]) { in_old[s] = 1; n_old++; }
       if (b->deleted[s]) del_eps.push_back(s);
       else if (!in_new[s]) { in_new[s] = 1; n_new++; }
@@ -1313,7 +1517,12 @@ static int create_impl(const hny_build_opts *opts, const hny_items *items, const
   DevBuf<u32> d_item_slot; // f32 items: alive until the stream is synchronised below
   IngestPipe pipe;
   if (n) {
-    if (f32) {
+    if (src) {
+      std::vector<uint32_t> up_slots(inc->n_insert);
+      for (uint64_t i = 0; i < inc->n_insert; i++) up_slots[i] = slot_of(inc->to_insert[i]);
+      rc = move_state_from_source(b.get(), src, inc->upd, src_of, new_of, src_live, up_slots, pipe);
+      if (rc) return rc;
+    } else if (f32) {
       IngestJob j;
       if (inc) { // items are a subset of the universe: the other slots hold zero rows and zero norms
         HIP_TRY(hipMemsetAsync(b->d_rows.p, 0, (size_t)n * g.row_stride, st));
@@ -1361,7 +1570,7 @@ static int create_impl(const hny_build_opts *opts, const hny_items *items, const
     HIP_TRY(hipMemcpyAsync(b->d_eps.p, b->entry_points.data(), b->entry_points.size() * 4,
                            hipMemcpyHostToDevice, st));
     std::vector<float> norms;
-    if (has_norm && !f32) {
+    if (has_norm && !f32 && !src) {
       norms.assign(n, 0.f);
       for (uint64_t i = 0; i < items->n; i++)
         memcpy(&norms[item_slot[i]], (const unsigned char *)items->headers + (size_t)i * hb, 4);
@@ -1372,8 +1581,12 @@ static int create_impl(const hny_build_opts *opts, const hny_items *items, const
   if (inc && n) {
     // the previous graph, as Links records: ascending ids, HNY_SENT padded
     const hny_prev_graph *pg = inc->prev;
-    std::vector<u32> d0((size_t)n * o.M0, HNY_SENT), du(std::max<size_t>(nup * o.M, 1), HNY_SENT);
-    for (uint64_t r = 0; r < pg->n_records; r++) {
+    std::vector<u32> d0, du;
+    if (!src) {
+      d0.assign((size_t)n * o.M0, HNY_SENT);
+      du.assign(std::max<size_t>(nup * o.M, 1), HNY_SENT);
+    }
+    for (uint64_t r = 0; !src && r < pg->n_records; r++) {
       uint32_t s = slot_of(pg->rec_item[r]), ll = pg->rec_layer[r];
       uint64_t c = pg->rec_offset[r + 1] - pg->rec_offset[r];
       uint32_t cap = ll == 0 ? o.M0 : o.M;
@@ -1383,13 +1596,15 @@ static int create_impl(const hny_build_opts *opts, const hny_items *items, const
                          : &du[((size_t)b->upper_idx[s] * b->up_layers + (ll - 1)) * o.M];
       for (uint64_t k = 0; k < c; k++) dst[k] = slot_of(pg->neighbours[pg->rec_offset[r] + k]);
     }
-    HIP_TRY(b->d_d0_ids.alloc(d0.size()));
-    HIP_TRY(b->d_du_ids.alloc(du.size()));
+    if (!src) { // (a source builder's lists are in place already: move_state_from_source)
+      HIP_TRY(b->d_d0_ids.alloc(d0.size()));
+      HIP_TRY(b->d_du_ids.alloc(du.size()));
+      HIP_TRY(hipMemcpyAsync(b->d_d0_ids.p, d0.data(), d0.size() * 4, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(b->d_du_ids.p, du.data(), du.size() * 4, hipMemcpyHostToDevice, st));
+    }
     HIP_TRY(b->d_has_vec.alloc(n));
     HIP_TRY(b->d_deleted.alloc(n));
     HIP_TRY(b->d_old_recs.alloc(std::max<size_t>(b->old_recs.size(), 1)));
-    HIP_TRY(hipMemcpyAsync(b->d_d0_ids.p, d0.data(), d0.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(b->d_du_ids.p, du.data(), du.size() * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(b->d_has_vec.p, has_vec.data(), n, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(b->d_deleted.p, b->deleted.data(), n, hipMemcpyHostToDevice, st));
     if (!b->old_recs.empty())
@@ -2027,12 +2242,7 @@ int hny_builder_finish(hny_builder *b, hny_graph **out) {
   // (delete_links_from_db, writer.rs:692-718).  Which records exist never changes during a builder's
   // life: the record table (first record of every slot, item id and layer of every record) is
   // computed once and reused by every finish().
-  auto rec_mask = [&](uint32_t s) -> uint32_t {
-    if (b->deleted[s]) return 0u;
-    uint32_t m = b->old_mask[s];
-    if (b->ins_level[s] >= 0) m |= (2u << b->ins_level[s]) - 1u;
-    return m;
-  };
+  auto rec_mask = [&](uint32_t s) -> uint32_t { return rec_mask_of(b, s); };
   auto parallel = [&](auto &&fn) { // fn(thread, lo, hi) over the slots
     std::vector<std::thread> th;
     for (unsigned t = 1; t < nt; t++)
@@ -2238,7 +2448,10 @@ int hny_build_f32(const hny_build_opts *opts, const hny_items *f32_items, hny_gr
 // fill_gaps_from_deleted (hnsw.rs:187, 334-415): merge old and new links of every surviving old
 // record and bridge the holes deleted items leave
 static int run_fill_gaps(hny_builder *b) {
-  if (!b->incremental || b->old_recs.empty()) return HNY_OK;
+  if (!b->incremental || b->old_recs.empty()) {
+    b->gaps_done = true; // nothing to bridge
+    return HNY_OK;
+  }
   const u32 cap = std::max(b->g.M0, b->g.M);
   if (cap > HNY_MAX_CAP) {
     // wide lists: the workgroup kernel with its gathered set, scored list and bitmap in HBM
@@ -2262,12 +2475,14 @@ static int run_fill_gaps(hny_builder *b) {
                               maxb, b->d_gap_keys.p, b->d_gap_sorted.p, b->stage_rows,
                               (int)std::min<u32>(n_recs, (u32)b->gap_grid), b->shape, b->stream));
     prof_end(b);
+    b->gaps_done = true;
     return HNY_OK;
   }
   prof_begin(b, EV_APPLY);
   HIP_TRY(hnyk_fill_gaps(b->g, b->d_old_recs.p, (u32)b->old_recs.size(), b->d_deleted.p, b->shape,
                          b->stream));
   prof_end(b);
+  b->gaps_done = true;
   return HNY_OK;
 }
 
@@ -2356,6 +2571,248 @@ int hny_build_incremental_f32(const hny_build_opts *opts, const hny_items *f32_i
   int rc = create_impl(opts, f32_items, &inc, &b, true);
   if (rc) return rc;
   return run_build(b, opts, out);
+}
+
+// ---- resident updates (include/hannoy_amd.h) ----
+static int check_ascending(const uint32_t *ids, uint64_t n, const char *what) {
+  if (n && !ids) return fail(HNY_ERR_INVALID_ARG, "hny_update: null %s", what);
+  for (uint64_t i = 1; i < n; i++)
+    if (ids[i] <= ids[i - 1]) return fail(HNY_ERR_INVALID_ARG, "hny_update: %s not strictly ascending at index %llu", what, (unsigned long long)i);
+  return HNY_OK;
+}
+static int check_update_struct(const hny_update *u) {
+  if (!u) return fail(HNY_ERR_INVALID_ARG, "null hny_update");
+  if (u->struct_size != sizeof(hny_update))
+    return fail(HNY_ERR_INVALID_ARG, "hny_update.struct_size is %u, this library expects %zu", u->struct_size, sizeof(hny_update));
+  return HNY_OK;
+}
+
+int hny_builder_create_update(hny_builder *src, const hny_update *u, hny_builder **out) {
+  if (!out) return fail(HNY_ERR_INVALID_ARG, "null out");
+  *out = nullptr;
+  if (int rc = check_update_struct(u)) return rc;
+  if (!src) return fail(HNY_ERR_INVALID_ARG, "null source builder");
+  // everything below is decided from the arguments and the source's host state, before any device work
+  if (int rc = check_ascending(u->upsert_ids, u->n_upsert, "upsert_ids")) return rc;
+  if (int rc = check_ascending(u->delete_ids, u->n_delete, "delete_ids")) return rc;
+  const hny_build_opts &so = src->o;
+  const size_t vb = vec_bytes(so.metric, so.dim), hb = hdr_bytes(so.metric);
+  if (u->vectors_are_f32) {
+    if (int rc = check_f32_rows(so.dim, u->n_upsert, u->vectors, u->stride)) return rc;
+  } else if (u->n_upsert) {
+    if (!u->vectors || !u->headers) return fail(HNY_ERR_INVALID_ARG, "hny_update: null vectors / headers");
+    if (u->stride < vb)
+      return fail(HNY_ERR_INVALID_DIM, "hny_update: stride %zu < %zu codec bytes for dim %u", u->stride, vb, so.dim);
+    if (u->header_size != hb) return fail(HNY_ERR_INVALID_ARG, "hny_update: header_size %zu, expected %zu", u->header_size, hb);
+  }
+  if (src->pos < src->order.size() || src->in_batch || src->apply_open)
+    return fail(HNY_ERR_INVALID_ARG, "update: the source builder has batches pending");
+  if (src->incremental && !src->load_only && !src->gaps_done)
+    return fail(HNY_ERR_INVALID_ARG, "update: hny_builder_fill_gaps has not run on the incremental source builder");
+  // items after the update: the source's live items minus delete_ids, plus the upserts
+  const std::vector<uint8_t> live = live_slots(src);
+  std::vector<uint32_t> ids_after;
+  ids_after.reserve((size_t)src->n + u->n_upsert);
+  {
+    std::vector<uint32_t> kept;
+    kept.reserve(src->n);
+    uint64_t d = 0;
+    for (uint32_t s = 0; s < src->n; s++) {
+      if (!live[s]) continue;
+      const uint32_t id = src->ids[s];
+      while (d < u->n_delete && u->delete_ids[d] < id) d++;
+      if (d < u->n_delete && u->delete_ids[d] == id) continue;
+      kept.push_back(id);
+    }
+    std::set_union(kept.begin(), kept.end(), u->upsert_ids, u->upsert_ids + u->n_upsert, std::back_inserter(ids_after));
+  }
+  hny_build_opts o = so; // as the caller gave them: batch_max 0 is resolved from the successor's own item count
+  o.seed = u->seed;
+  o.device = src->device;
+  o.n_gpus = 0; // (a replica of a multi-GPU builder is an ordinary one-GPU source)
+  o.devices = nullptr;
+  hny_items items{};
+  items.n = ids_after.size();
+  items.ids = ids_after.data();
+  items.levels = u->levels;
+  IncrementalSpec inc{u->upsert_ids, u->n_upsert, u->delete_ids, u->n_delete, nullptr};
+  inc.src = src;
+  inc.upd = u;
+  return create_impl(&o, &items, &inc, out, u->vectors_are_f32 != 0);
+}
+
+void hny_graph_delta_free(hny_graph_delta *d) {
+  if (!d) return;
+  free((void *)d->rec_item);
+  free((void *)d->rec_layer);
+  free((void *)d->rec_offset);
+  free((void *)d->neighbours);
+  free((void *)d->removed_item);
+  free((void *)d->removed_layer);
+  free((void *)d->entry_points);
+  free(d);
+}
+
+// What changed against the source's records: the successor's finalised lists are compared with its own copy of the
+// previous graph (d_d0_ids / d_du_ids: read-only during the build) on the device; one flag byte and one count per
+// list come back, the flagged lists are packed by k_gather_lists and copied once.
+int hny_builder_finish_delta(hny_builder *b, hny_graph_delta **out) {
+  if (!b || !out) return fail(HNY_ERR_INVALID_ARG, "null argument");
+  *out = nullptr;
+  if (!b->from_update)
+    return fail(HNY_ERR_INVALID_ARG, "finish_delta: not a successor builder (hny_builder_create_update)");
+  if (b->pos < b->order.size() || b->in_batch) return fail(HNY_ERR_INVALID_ARG, "build not finished");
+  if (!b->gaps_done) return fail(HNY_ERR_INVALID_ARG, "finish_delta: hny_builder_fill_gaps has not run");
+  HIP_TRY(hipSetDevice(b->device));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  const double t0 = now_s();
+  hipStream_t st = b->stream;
+  const uint32_t n = b->n, M = b->o.M, M0 = b->o.M0, upl = b->up_layers;
+  const size_t nup = (size_t)b->n_upper * upl;
+  u64 stats[ST_COUNT] = {0};
+  HIP_TRY(hipMemcpy(stats, b->d_stats.p, sizeof stats, hipMemcpyDeviceToHost));
+  if (int rc = device_error_words(b, stats)) return rc;
+  if (!b->finalized) {
+    HIP_TRY(hnyk_finalize_lists(b->d_l0_ids.p, b->d_fin_cnt0.p, n, M0, st));
+    HIP_TRY(hnyk_finalize_lists(b->d_up_ids.p, b->d_fin_cntu.p, (u32)nup, M, st));
+    b->finalized = true;
+  }
+  DevBuf<unsigned char> d_flag;
+  HIP_TRY(d_flag.alloc((size_t)n + nup + 1));
+  HIP_TRY(hipMemsetAsync(d_flag.p, 0, (size_t)n + nup + 1, st));
+  if (n) HIP_TRY(hnyk_diff_records(b->d_l0_ids.p, b->d_d0_ids.p, d_flag.p, n, M0, st));
+  if (nup) HIP_TRY(hnyk_diff_records(b->d_up_ids.p, b->d_du_ids.p, d_flag.p + n, (u32)nup, M, st));
+  std::vector<unsigned char> flag((size_t)n + nup + 1);
+  HIP_TRY(hipMemcpyAsync(flag.data(), d_flag.p, flag.size(), hipMemcpyDeviceToHost, st));
+  if (n) HIP_TRY(hipMemcpyAsync(b->h_cnt0, b->d_fin_cnt0.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  if (nup) HIP_TRY(hipMemcpyAsync(b->h_cntu, b->d_fin_cntu.p, nup * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+
+  std::unique_ptr<hny_graph_delta, void (*)(hny_graph_delta *)> dh((hny_graph_delta *)calloc(1, sizeof(hny_graph_delta)),
+                                                                     hny_graph_delta_free);
+  hny_graph_delta *d = dh.get();
+  if (!d) return fail(HNY_ERR_OOM, "out of host memory");
+  std::vector<uint32_t> rec_item, rm_item;
+  std::vector<uint8_t> rec_layer, rm_layer;
+  std::vector<u64> rec_src, rec_off(1, 0);
+  uint64_t total = 0;
+  for (uint32_t s = 0; s < n; s++) {
+    const uint32_t m = rec_mask_of(b, s), om = b->old_mask[s];
+    total += (uint64_t)__builtin_popcount(m);
+    for (uint32_t l = 0; l <= HNY_MAX_LEVEL; l++) {
+      const uint32_t bit = 1u << l;
+      if ((om & bit) && !(m & bit)) {
+        rm_item.push_back(b->ids[s]);
+        rm_layer.push_back((uint8_t)l);
+      }
+      if (!(m & bit)) continue;
+      const size_t li = l == 0 ? s : (size_t)b->upper_idx[s] * upl + (l - 1);
+      const bool changed = !(om & bit) || flag[l == 0 ? li : n + li] != 0;
+      if (!changed) continue;
+      rec_item.push_back(b->ids[s]);
+      rec_layer.push_back((uint8_t)l);
+      rec_src.push_back(l == 0 ? (u64)li : ((u64)1 << 63) | (u64)li);
+      rec_off.push_back(rec_off.back() + (l == 0 ? b->h_cnt0[li] : b->h_cntu[li]));
+    }
+  }
+  const uint64_t nr = rec_item.size(), nl = rec_off.back();
+  std::vector<u32> packed(std::max<uint64_t>(nl, 1));
+  if (nr) {
+    DevBuf<u64> d_src, d_off;
+    DevBuf<u32> d_out;
+    HIP_TRY(d_src.alloc(nr));
+    HIP_TRY(d_off.alloc(nr + 1));
+    HIP_TRY(d_out.alloc(std::max<uint64_t>(nl, 1)));
+    HIP_TRY(hipMemcpyAsync(d_src.p, rec_src.data(), nr * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_off.p, rec_off.data(), (nr + 1) * 8, hipMemcpyHostToDevice, st));
+    GatherListsArgs ga{};
+    ga.l0_ids = b->d_l0_ids.p;
+    ga.up_ids = b->d_up_ids.p;
+    ga.M = M;
+    ga.M0 = M0;
+    ga.rec_src = d_src.p;
+    ga.rec_off = d_off.p;
+    ga.n_recs = nr;
+    ga.out = d_out.p;
+    HIP_TRY(hnyk_gather_lists(ga, st));
+    if (nl) HIP_TRY(hipMemcpyAsync(packed.data(), d_out.p, nl * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  auto dup = [](const void *p, size_t bytes) -> void * {
+    void *q = malloc(std::max<size_t>(bytes, 1));
+    if (q && bytes) memcpy(q, p, bytes);
+    return q;
+  };
+  for (uint64_t k = 0; k < nl; k++) packed[k] = b->ids[packed[k]]; // slot -> item id (order kept)
+  std::vector<uint32_t> eps(b->entry_points.size());
+  for (size_t i = 0; i < eps.size(); i++) eps[i] = b->ids[b->entry_points[i]];
+  d->n_records = nr;
+  d->rec_item = (const uint32_t *)dup(rec_item.data(), nr * 4);
+  d->rec_layer = (const uint8_t *)dup(rec_layer.data(), nr);
+  d->rec_offset = (const uint64_t *)dup(rec_off.data(), (nr + 1) * 8);
+  d->neighbours = (const uint32_t *)dup(packed.data(), nl * 4);
+  d->n_removed = rm_item.size();
+  d->removed_item = (const uint32_t *)dup(rm_item.data(), rm_item.size() * 4);
+  d->removed_layer = (const uint8_t *)dup(rm_layer.data(), rm_layer.size());
+  d->entry_points = (const uint32_t *)dup(eps.data(), eps.size() * 4);
+  d->n_entry_points = (uint32_t)eps.size();
+  d->max_level = b->max_level;
+  d->n_records_total = total;
+  if (!d->rec_item || !d->rec_layer || !d->rec_offset || !d->neighbours || !d->removed_item || !d->removed_layer ||
+      !d->entry_points)
+    return fail(HNY_ERR_OOM, "out of host memory for %llu delta records", (unsigned long long)nr);
+  d->t_export_s = now_s() - t0;
+  *out = dh.release();
+  return HNY_OK;
+}
+
+int hny_builder_update(hny_builder **b, const hny_update *u, hny_graph **full, hny_graph_delta **delta) {
+  if (full) *full = nullptr;
+  if (delta) *delta = nullptr;
+  if (int rc = check_update_struct(u)) return rc;
+  if (!b || !*b) return fail(HNY_ERR_INVALID_ARG, "null builder");
+  hny_builder *succ = nullptr;
+  int rc = hny_builder_create_update(*b, u, &succ);
+  if (rc) return rc;
+  const hny_build_opts &o = succ->o;
+  for (;;) {
+    if (o.cancel && o.cancel(o.cancel_ctx)) {
+      rc = fail(HNY_ERR_CANCELLED, "build cancelled");
+      break;
+    }
+    hny_batch bt;
+    rc = hny_builder_next_batch(succ, &bt);
+    if (rc || bt.count == 0) break;
+    rc = hny_builder_search(succ, 0, bt.count, nullptr);
+    if (rc) break;
+    rc = hny_builder_apply(succ, nullptr);
+    if (rc) break;
+    if (o.progress) o.progress(o.progress_ctx, succ->pos, succ->order.size());
+  }
+  if (!rc) rc = run_fill_gaps(succ);
+  if (!rc && full) rc = hny_builder_finish(succ, full);
+  if (!rc && delta) rc = hny_builder_finish_delta(succ, delta);
+  if (!rc && !full && !delta) rc = hny_builder_sync(succ); // (device errors surface in a later finish)
+  if (rc) {
+    if (full && *full) {
+      hny_graph_free(*full);
+      *full = nullptr;
+    }
+    hny_builder_destroy(succ);
+    return rc;
+  }
+  hny_builder_destroy(*b);
+  *b = succ;
+  return HNY_OK;
+}
+
+// scripts/update_throughput.py: device time and bytes (read + written) of the successor's k_move_rows; zero unless the
+// source builder was profiling (hny_builder_set_profiling) when the successor was made
+extern "C" int hny_internal_builder_move_stats(hny_builder *b, double *seconds, uint64_t *bytes) {
+  if (!b || !seconds || !bytes) return fail(HNY_ERR_INVALID_ARG, "null argument");
+  *seconds = b->t_move_rows_s;
+  *bytes = b->move_rows_bytes;
+  return HNY_OK;
 }
 
 int hny_builder_distances(hny_builder *b, uint64_t n_pairs, const uint32_t *slot_a,
@@ -2485,6 +2942,19 @@ int hny_builder_search_knn_f32(hny_builder *b, uint64_t nq, const float *queries
   return search_knn_impl(b, nq, queries, qstride, nullptr, k, ef_search, out_ids, out_dists, out_counts, nullptr, true);
 }
 
+// The graph the searches walk.  A successor builder (hny_builder_create_update) whose update has finished holds the
+// complete new lists in l0_ids / up_ids (fill_gaps rewrote every surviving record); its copy of the source's
+// lists is history, kept for finish_delta only.  The searches then read the new lists in the place of the
+// previous graph's, like a builder that loaded the new graph: same hits as Reader::open on the written records.
+static GraphDev search_graph(const hny_builder *b) {
+  GraphDev g = b->g;
+  if (b->from_update && b->gaps_done) {
+    g.d0_ids = g.l0_ids;
+    g.du_ids = g.up_ids;
+  }
+  return g;
+}
+
 static int search_knn_impl(hny_builder *b, uint64_t nq, const void *qvectors, size_t qstride,
                            const void *qheaders, uint32_t k, uint32_t ef_search, uint32_t *out_ids,
                            float *out_dists, uint32_t *out_counts, const hny_query_opts *qo, bool q_f32) {
@@ -2514,6 +2984,7 @@ static int search_knn_impl(hny_builder *b, uint64_t nq, const void *qvectors, si
                                 (u32)((size_t)b->n_upper * b->up_layers), b->o.M, b->stream));
     b->finalized = true;
   }
+  const GraphDev sg = search_graph(b);
   const uint32_t rcap = res_capacity(ef, (uint32_t)b->entry_points.size(), b->n, b->top_layer_nodes, HNY_RES_GLOBAL_MAX);
   const size_t vb = vec_bytes(b->o.metric, b->o.dim), hb = hdr_bytes(b->o.metric);
   if (!q_f32 && qstride < vb) return fail(HNY_ERR_INVALID_DIM, "query stride too small");
@@ -2587,7 +3058,7 @@ static int search_knn_impl(hny_builder *b, uint64_t nq, const void *qvectors, si
       d.eps_out = b->d_eps0.p;
       d.key_out = b->d_lkey_a.p;
       b->n_walk_dispatch++;
-    HIP_TRY(hnyk_walk(b->g, d, b->shape, grid, b->stream));
+    HIP_TRY(hnyk_walk(sg, d, b->shape, grid, b->stream));
       HIP_TRY(hnyk_iota_u64(b->d_perm_a.p, 0, cnt, b->stream));
       size_t tmp = b->sort_tmp_bytes;
       HIP_TRY(hnyk_sort_pairs48(b->d_sort_tmp.p, tmp, b->d_lkey_a.p, b->d_lkey_b.p, b->d_perm_a.p,
@@ -2605,7 +3076,7 @@ static int search_knn_impl(hny_builder *b, uint64_t nq, const void *qvectors, si
       }
     }
     b->n_walk_dispatch++;
-    HIP_TRY(hnyk_walk(b->g, w, b->shape, grid, b->stream));
+    HIP_TRY(hnyk_walk(sg, w, b->shape, grid, b->stream));
     HIP_TRY(hnyk_take_topk(dcand.p, dcn.p, rcap, k, cnt, dtop.p, b->stream));
     HIP_TRY(hipMemcpyAsync(hc.data(), dtop.p, (size_t)cnt * k * 8, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipMemcpyAsync(hn.data(), dcn.p, (size_t)cnt * 4, hipMemcpyDeviceToHost, b->stream));
@@ -2750,6 +3221,7 @@ static int nns_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const
                                 b->o.M, b->stream));
     b->finalized = true;
   }
+  const GraphDev sg = search_graph(b);
   uint32_t rcap = res_capacity(ef, (uint32_t)b->entry_points.size(), b->n, b->top_layer_nodes,
                                big ? HNY_RES_GLOBAL_MAX : HNY_RES_LDS_MAX);
   if (big && linear) { // brute_force_search ranks in LDS: it returns min(k, candidates) hits
@@ -2870,17 +3342,17 @@ static int nns_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const
     if (sc.d) HIP_TRY(hnyk_fill_u32(dstatus.p, 2u, cnt, b->stream)); // 2 = never started
     HIP_TRY(hipMemsetAsync(queues, 0, 8 * 4, b->stream));
     if (linear) {
-      HIP_TRY(hnyk_nns_linear(b->g, a, b->shape, (int)std::min<uint32_t>(n_mem, b->walk_slots), b->stream));
+      HIP_TRY(hnyk_nns_linear(sg, a, b->shape, (int)std::min<uint32_t>(n_mem, b->walk_slots), b->stream));
     } else if (big) {
       a.heap = dheap.p;
       a.heap_cap = heap_big_c;
       a.heap_r = dheap_r.p;
       a.heap_r_cap = rcap + 1;
-      HIP_TRY(hnyk_nns(b->g, a, b->shape, (int)std::min<uint32_t>(n_mem, grid_big), b->stream));
+      HIP_TRY(hnyk_nns(sg, a, b->shape, (int)std::min<uint32_t>(n_mem, grid_big), b->stream));
     } else {
       a.heap = dheap.p;
       a.heap_cap = heap_small;
-      HIP_TRY(hnyk_nns(b->g, a, b->shape, (int)std::min<uint32_t>(n_mem, grid_small), b->stream));
+      HIP_TRY(hnyk_nns(sg, a, b->shape, (int)std::min<uint32_t>(n_mem, grid_small), b->stream));
       HIP_TRY(hipMemcpyAsync(hst.data(), dstatus.p, (size_t)cnt * 4, hipMemcpyDeviceToHost, b->stream));
       HIP_TRY(sc.wait(b));
       uint32_t n_retry = 0;
@@ -2896,7 +3368,7 @@ static int nns_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const
         a.heap = dheap_full.p;
         a.heap_cap = heap_full;
         a.queue = queues + 1;
-        HIP_TRY(hnyk_nns(b->g, a, b->shape, (int)std::min<uint32_t>(n_retry, grid_full), b->stream));
+        HIP_TRY(hnyk_nns(sg, a, b->shape, (int)std::min<uint32_t>(n_retry, grid_full), b->stream));
       } else if (n_retry) {
         return fail(HNY_ERR_DEVICE, "search queue overflow");
       }

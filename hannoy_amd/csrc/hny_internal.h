@@ -309,3 +309,43 @@ struct IngestArgs {
   u32 vb, hb;
 };
 hipError_t hnyk_ingest(const IngestArgs &a, hipStream_t st);
+
+// ---- resident updates (hny_update.hip): a successor builder made from a source builder, device to device ----
+#define HNY_MV_LIVE 0x8000u // MoveRowsArgs / MoveListsArgs mask: the source slot holds a live row (bits 0..14: its records)
+struct MoveRowsArgs {
+  const unsigned char *src_rows; // source builder's rows, same n16 / row_stride
+  const float *src_norms;        // or null (metrics without a header norm)
+  const u32 *src_of;             // [n_new] successor slot -> source slot, HNY_SENT = none
+  const unsigned short *mask;    // [n_new] the source's record mask of the slot | HNY_MV_LIVE
+  unsigned char *dst_rows;
+  float *dst_norms;
+  u32 n_new, n16;
+  u32 lg_group;                  // set by hnyk_move_rows: log2 of the lanes that share a row
+};
+struct MoveListsArgs {
+  const u32 *src_l0_ids;         // source lists: finalised (ascending, HNY_SENT padded), source slot numbers
+  const u32 *src_up_ids;
+  const int *src_upper_idx;
+  u32 src_up_layers, n_src;
+  const u32 *src_of;             // [n_new]
+  const u32 *new_of;             // [n_src] source slot -> successor slot, HNY_SENT = none
+  const unsigned short *mask;    // [n_new]
+  const u32 *up_slot;            // [n_upper] successor upper index -> slot
+  u32 *dst_d0_ids, *dst_du_ids;  // GraphDev::d0_ids / du_ids of the successor
+  u32 n_new, n_upper, up_layers, M, M0;
+  u64 *bad;                      // entries whose source slot maps to no successor slot (must stay 0)
+};
+struct GatherListsArgs {
+  const u32 *l0_ids, *up_ids;
+  u32 M, M0;
+  const u64 *rec_src;            // [n_recs] list index, bit 63 = upper layers
+  const u64 *rec_off;            // [n_recs + 1] offsets into out
+  u64 n_recs;
+  u32 *out;
+};
+hipError_t hnyk_move_rows(const MoveRowsArgs &a, hipStream_t st);
+hipError_t hnyk_scatter_rows(const unsigned char *src, const float *src_norms, const u32 *slots, unsigned char *dst,
+                             float *dst_norms, u32 cnt, u32 n16, hipStream_t st);
+hipError_t hnyk_move_lists(const MoveListsArgs &a, hipStream_t st);
+hipError_t hnyk_diff_records(const u32 *fin, const u32 *old, unsigned char *flag, u32 n_lists, u32 cap, hipStream_t st);
+hipError_t hnyk_gather_lists(const GatherListsArgs &a, hipStream_t st);

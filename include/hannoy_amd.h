@@ -351,6 +351,73 @@ int hny_builder_search_knn_f32(hny_builder *b, uint64_t n_queries, const float *
 int hny_builder_nns_f32(hny_builder *b, const hny_query_opts *opts, uint64_t n_queries, const float *queries,
                         size_t qstride, uint32_t *out_ids, float *out_dists, uint32_t *out_counts);
 
+/* ---- resident updates: Writer::add_item / del_item followed by Writer::build (src/writer.rs:462-495, 521-603)
+ * on an index whose builder is still alive.  A finished builder holds the codec rows, the norms and the finalised
+ * lists of every live item in HBM; the successor takes them from there, device to device (k_move_rows /
+ * k_move_lists), instead of having the caller export the graph, re-read every item and upload both
+ * again.  Only the upserted rows cross the bus.
+ *
+ * Definition: the successor, run to the end, yields byte for byte what hny_build_incremental(opts, items_after,
+ * to_insert = upsert_ids, to_delete = delete_ids, prev = src's exported graph) yields, where items_after = src's
+ * live items minus delete_ids with the upserted rows added / replaced, items_after->levels = levels, and opts =
+ * src's options as the caller gave them with seed = u->seed (a batch_max of 0 is resolved from the successor's own
+ * item count).  Records, entry points, max_level, n_links_added and n_evals_walk included.
+ *
+ * Memory: both builders are resident while the successor exists next to its source — the rows twice (C4: 2 x 5 GB
+ * of 288 GB).  There is no in-place variant.  One GPU: a replica from hny_multi_builder_replica is an ordinary
+ * one-GPU source. ---- */
+typedef struct {
+  uint32_t struct_size;      /* sizeof(hny_update) as the caller compiled it; anything else: HNY_ERR_INVALID_ARG */
+  int32_t vectors_are_f32;   /* 0: codec bytes + headers (hny_items convention); 1: f32 rows, headers unused */
+  uint64_t n_upsert;
+  const uint32_t *upsert_ids; /* strictly ascending: items added, or overwritten with a new vector */
+  const void *vectors;       /* one row per upsert id */
+  size_t stride;
+  const void *headers;
+  size_t header_size;
+  const uint8_t *levels;     /* optional, one per upsert id; NULL: drawn from `seed` as hny_build_incremental draws them */
+  uint64_t seed;
+  uint64_t n_delete;
+  const uint32_t *delete_ids; /* strictly ascending; ids the source never held are allowed, as in hny_build_incremental */
+} hny_update;
+
+/* `src`: a builder whose hny_builder_finish returned HNY_OK, or one from hny_builder_load[_f32].  The successor is
+ * an incremental builder on src's device, ready for next_batch / search / apply / fill_gaps / finish exactly like
+ * one from hny_builder_create_incremental.  src is left intact and usable (searches) until the caller destroys
+ * it.  Decided before any device work: null arguments, a wrong struct_size, ids not ascending, a source with
+ * batches pending or an incremental source whose fill_gaps has not run (HNY_ERR_INVALID_ARG); codec stride /
+ * f32 stride too small (HNY_ERR_INVALID_DIM).  HNY_ERR_DEVICE if a list of src names a slot that owns no record
+ * (never seen; the move kernel counts them). */
+int hny_builder_create_update(hny_builder *src, const hny_update *u, hny_builder **out);
+/* every batch + fill_gaps on the successor, then *b is destroyed and replaced by it.  full != NULL: the complete
+ * graph (hny_builder_finish); delta != NULL: hny_builder_finish_delta; both may be given.  On error *b is untouched.
+ * *b must be owned by the caller: a replica borrowed from hny_multi_builder_replica belongs to its multi-builder and
+ * must go through hny_builder_create_update instead (the caller then owns, and destroys, only the successor). */
+typedef struct hny_graph_delta hny_graph_delta;
+int hny_builder_update(hny_builder **b, const hny_update *u, hny_graph **full, hny_graph_delta **delta);
+
+/* What the reference's write loop would have to put / delete after an update.  Start from the source's complete
+ * record set, delete the `removed` keys, put the records below: the result is the successor's complete record set.
+ * A record whose list did not change is not in it.  Library-owned. */
+struct hny_graph_delta {
+  uint64_t n_records;         /* records that are new or whose list changed, sorted by (item id, layer) */
+  const uint32_t *rec_item;
+  const uint8_t *rec_layer;
+  const uint64_t *rec_offset; /* n_records + 1 */
+  const uint32_t *neighbours; /* item ids, ascending */
+  uint64_t n_removed;         /* record keys that no longer exist, sorted by (item id, layer) */
+  const uint32_t *removed_item;
+  const uint8_t *removed_layer;
+  const uint32_t *entry_points;
+  uint32_t n_entry_points;
+  uint32_t max_level;
+  uint64_t n_records_total;   /* records of the complete graph */
+  double t_export_s;          /* host wall clock of this export */
+};
+/* successor builders (hny_builder_create_update) whose build has finished only, else HNY_ERR_INVALID_ARG */
+int hny_builder_finish_delta(hny_builder *b, hny_graph_delta **out);
+void hny_graph_delta_free(hny_graph_delta *d);
+
 /* Diagnostic: runs the distance kernels' cross-lane primitives (DPP moves, v_permlane16/32_swap) next
  * to the generic __shfl_xor on one wave of `device` (-1 = current).  HNY_OK when every lane agrees;
  * HNY_ERR_DEVICE otherwise, with bit (5 * log2(offset) + check) of mismatch64[lane] set (may be
