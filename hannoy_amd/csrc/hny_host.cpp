@@ -559,24 +559,27 @@ int env_int(const char *name, int dflt) {
 }
 
 // codec bytes -> zero padded device rows (UnalignedVector is byte-packed and unaligned inside
-// LMDB pages, f32.rs:9-55; the device wants 16-byte aligned rows)
+// LMDB pages, f32.rs:9-55; the device wants 16-byte aligned rows).  `slots`: row r goes to row slots[r] (ascending) of
+// the `n_slots` at dst, the rows in between are zero (items that are a subset of an incremental build's universe)
 int upload_rows(const void *vectors, size_t stride, size_t vbytes, uint64_t n, uint32_t row_stride,
-                unsigned char *dst, hipStream_t st) {
-  if (stride == row_stride && vbytes == row_stride) {
+                unsigned char *dst, hipStream_t st, const uint32_t *slots = nullptr, uint64_t n_slots = 0) {
+  if (!slots) n_slots = n;
+  if (!slots && stride == row_stride && vbytes == row_stride) {
     HIP_TRY(hipMemcpyAsync(dst, vectors, (size_t)n * row_stride, hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));
     return HNY_OK;
   }
   const size_t chunk_rows = std::max<size_t>(1, (64u << 20) / row_stride);
   std::vector<unsigned char> stage(chunk_rows * row_stride);
-  for (uint64_t r0 = 0; r0 < n; r0 += chunk_rows) {
-    size_t cnt = (size_t)std::min<uint64_t>(chunk_rows, n - r0);
+  uint64_t r = 0;
+  for (uint64_t s0 = 0; s0 < n_slots; s0 += chunk_rows) {
+    size_t cnt = (size_t)std::min<uint64_t>(chunk_rows, n_slots - s0);
     std::fill(stage.begin(), stage.begin() + cnt * row_stride, 0);
-    for (size_t r = 0; r < cnt; r++)
-      memcpy(&stage[r * row_stride], (const unsigned char *)vectors + (r0 + r) * stride, vbytes);
-    HIP_TRY(hipMemcpyAsync(dst + r0 * row_stride, stage.data(), cnt * row_stride,
+    for (; r < n && (slots ? slots[r] : r) < s0 + cnt; r++)
+      memcpy(&stage[((slots ? slots[r] : r) - s0) * row_stride], (const unsigned char *)vectors + r * stride, vbytes);
+    HIP_TRY(hipMemcpyAsync(dst + s0 * row_stride, stage.data(), cnt * row_stride,
                            hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipStreamSynchronize(st)); // (the staging buffer is filled again)
   }
   return HNY_OK;
 }
@@ -610,6 +613,20 @@ struct IngestJob {
   float *norms = nullptr;
   void *out_codes = nullptr, *out_hdrs = nullptr; // host destinations of the packed outputs (NULL = not wanted)
 };
+
+bool has_norms(int metric) { return metric == HNY_COSINE || metric == HNY_BQ_COSINE; }
+
+// the fields every caller fills the same way: the codec, and where the encoded rows land (NULL: only the packed
+// outputs are wanted) — norms only for the metrics that keep them
+IngestJob ingest_job(int metric, uint32_t dim, unsigned char *rows, uint32_t row_stride, float *norms) {
+  IngestJob j;
+  j.metric = metric;
+  j.dim = dim;
+  j.rows = rows;
+  j.row_stride = row_stride;
+  j.norms = has_norms(metric) ? norms : nullptr;
+  return j;
+}
 
 // the caller synchronises `st` (the kernels and, with packed outputs, the copies back are enqueued on it)
 int run_ingest(IngestPipe &p, const IngestJob &j, hipStream_t st) {
@@ -711,6 +728,15 @@ int reset_graph(hny_builder *b) {
   b->n_walk_dispatch = 0;
   b->sync_used = 0;
   b->t_build0 = now_s();
+  return HNY_OK;
+}
+
+// a call that needs the GPU fails without one; device >= 0: it becomes the current one
+int use_device(int device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+    return fail(HNY_ERR_NO_DEVICE, "no HIP device (this library has no CPU path)");
+  if (device >= 0) HIP_TRY(hipSetDevice(device));
   return HNY_OK;
 }
 
@@ -816,19 +842,14 @@ int hny_encode_vectors(int32_t metric, uint32_t dim, uint64_t n, const float *ve
       (void)ones;
     }
   };
-  std::vector<std::thread> th;
-  for (unsigned t = 0; t < nt; t++) th.emplace_back(work, n * t / nt, n * (t + 1) / nt);
-  for (auto &t : th) t.join();
+  run_split(nt, n, work);
   return HNY_OK;
 }
 
 // the same on the device: codes through k_quantize, Cosine norms through k_norms_x86 (bit-identical
 // to the host path above), streamed in chunks so that any n fits
 int hny_selftest_lane_ops(int32_t device, uint32_t *mismatch64) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(HNY_ERR_NO_DEVICE, "no HIP device (this library has no CPU path)");
-  if (device >= 0) HIP_TRY(hipSetDevice(device));
+  if (int rc = use_device(device)) return rc;
   DevBuf<u32> d;
   HIP_TRY(d.alloc(64));
   HIP_TRY(hnyk_lane_selftest(d.p, nullptr));
@@ -847,10 +868,7 @@ int hny_encode_vectors_gpu(int32_t metric, uint32_t dim, uint64_t n, const float
                            void *out_codes, void *out_headers, int32_t device) {
   if (!vectors || !out_codes || !out_headers || metric < 0 || metric > HNY_BQ_MANHATTAN || dim == 0)
     return fail(HNY_ERR_INVALID_ARG, "hny_encode_vectors_gpu: bad argument");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(HNY_ERR_NO_DEVICE, "no HIP device (this library has no CPU path)");
-  if (device >= 0) HIP_TRY(hipSetDevice(device));
+  if (int rc = use_device(device)) return rc;
   const size_t vb = vec_bytes(metric, dim), hb = hdr_bytes(metric);
   if (!is_binary(metric)) {
     memcpy(out_codes, vectors, (size_t)n * vb); // f32.rs:9-55
@@ -866,9 +884,7 @@ int hny_encode_vectors_gpu(int32_t metric, uint32_t dim, uint64_t n, const float
   int rc;
   {
     IngestPipe pipe;
-    IngestJob j;
-    j.metric = metric;
-    j.dim = dim;
+    IngestJob j = ingest_job(metric, dim, nullptr, 0, nullptr);
     j.src = vectors;
     j.stride = (size_t)dim * 4;
     j.n = n;
@@ -913,6 +929,15 @@ static inline uint32_t rec_mask_of(const hny_builder *b, uint32_t s) {
   if (b->ins_level[s] >= 0) m |= (2u << b->ins_level[s]) - 1u;
   return m;
 }
+// every list sorted and deduplicated, once per build (finish, the searches and a successor's move read them so);
+// enqueued on `st`
+static int ensure_finalized(hny_builder *b, hipStream_t st) {
+  if (b->finalized) return HNY_OK;
+  HIP_TRY(hnyk_finalize_lists(b->d_l0_ids.p, b->d_fin_cnt0.p, b->n, b->o.M0, st));
+  HIP_TRY(hnyk_finalize_lists(b->d_up_ids.p, b->d_fin_cntu.p, (u32)((size_t)b->n_upper * b->up_layers), b->o.M, st));
+  b->finalized = true;
+  return HNY_OK;
+}
 // slots of a builder that hold an item's row
 static std::vector<uint8_t> live_slots(const hny_builder *b) {
   if (!b->incremental) return std::vector<uint8_t>(b->n, 1);
@@ -921,34 +946,105 @@ static std::vector<uint8_t> live_slots(const hny_builder *b) {
   return live;
 }
 
+static inline uint32_t slot_of(const std::vector<uint32_t> &U, uint32_t id) {
+  return (uint32_t)(std::lower_bound(U.begin(), U.end(), id) - U.begin());
+}
+
+// What existed before an incremental build, as far as the host plans with it: taken from an hny_prev_graph, or from
+// a finished source builder whose rows and lists stay on the device (resident update).
+struct PrevState {
+  const hny_prev_graph *pg = nullptr;
+  hny_builder *src = nullptr;
+  uint32_t max_level = 0;
+  std::vector<uint32_t> eps;            // the previous entry points as slots of the new universe (bind_slots)
+  std::vector<uint8_t> src_live;        // source builder: its slots that hold a row
+  std::vector<uint32_t> src_of, new_of; // successor slot -> source slot and back, HNY_SENT = none
+
+  // the ids that join the universe U
+  int init(const IncrementalSpec *inc, std::vector<uint32_t> &U) {
+    if ((!inc->prev && !inc->src) || (inc->n_insert && !inc->to_insert) || (inc->n_delete && !inc->to_delete))
+      return fail(HNY_ERR_INVALID_ARG, "incremental: null argument");
+    if (inc->src) {
+      // The host holds no lists of the source and does not fetch them: every slot that owns a record or a row,
+      // and the entry points.  Equal to what the branch below computes from the exported graph iff no finalised
+      // list names a slot without records — k_move_lists counts the entries that would (DESIGN.md §3c).
+      src = inc->src;
+      src_live = live_slots(src);
+      for (uint32_t s = 0; s < src->n; s++)
+        if (rec_mask_of(src, s) || src_live[s]) U.push_back(src->ids[s]);
+      for (uint32_t s : src->entry_points) U.push_back(src->ids[s]);
+      max_level = src->max_level;
+    } else {
+      pg = inc->prev;
+      U.insert(U.end(), pg->rec_item, pg->rec_item + pg->n_records);
+      if (pg->n_records) U.insert(U.end(), pg->neighbours, pg->neighbours + pg->rec_offset[pg->n_records]);
+      U.insert(U.end(), pg->entry_points, pg->entry_points + pg->n_entry_points);
+      max_level = pg->max_level;
+    }
+    return HNY_OK;
+  }
+  // once b->ids is the universe: which records exist (b->old_mask) and the entry points, in slots
+  int bind_slots(hny_builder *b) {
+    if (pg) {
+      for (uint64_t r = 0; r < pg->n_records; r++) {
+        if (pg->rec_layer[r] > HNY_MAX_LEVEL) return fail(HNY_ERR_INVALID_ARG, "old record on layer > %d", HNY_MAX_LEVEL);
+        b->old_mask[slot_of(b->ids, pg->rec_item[r])] |= (uint16_t)(1u << pg->rec_layer[r]);
+      }
+      for (uint32_t i = 0; i < pg->n_entry_points; i++) eps.push_back(slot_of(b->ids, pg->entry_points[i]));
+      return HNY_OK;
+    }
+    // source builder: both universes ascend with the item ids, one merge gives both slot maps
+    const uint32_t n = b->n;
+    src_of.assign(n, HNY_SENT);
+    new_of.assign(src->n, HNY_SENT);
+    for (uint32_t s = 0, t = 0; s < src->n && t < n; s++) {
+      while (t < n && b->ids[t] < src->ids[s]) t++;
+      if (t < n && b->ids[t] == src->ids[s]) {
+        src_of[t] = s;
+        new_of[s] = t;
+      }
+    }
+    for (uint32_t t = 0; t < n; t++)
+      if (src_of[t] != HNY_SENT) b->old_mask[t] = (uint16_t)rec_mask_of(src, src_of[t]);
+    for (uint32_t s : src->entry_points) eps.push_back(new_of[s]);
+    return HNY_OK;
+  }
+};
+
+// what creation works out on the host and needs only until the rows are on the device
+struct CreatePlan {
+  const hny_items *items = nullptr;
+  const IncrementalSpec *inc = nullptr; // null: a fresh index
+  PrevState prev;
+  std::vector<uint8_t> has_vec;     // per slot: an item's row lives there
+  std::vector<uint32_t> item_slot;  // per item
+  std::vector<std::pair<uint32_t, uint8_t>> levels; // (slot, level) in the reference's order
+};
+
 // Resident update (hny_builder_create_update): rows, norms and the finalised lists of `src` go to their slots in
 // the successor `b` device to device, then the upserted rows land on top (same stream: an overwritten item ends
 // with its new row).  Host -> device: the two slot maps, one u16 mask per slot, the upper-index table, the upserts.
-static int move_state_from_source(hny_builder *b, hny_builder *src, const hny_update *u,
-                                  const std::vector<uint32_t> &src_of, const std::vector<uint32_t> &new_of,
-                                  const std::vector<uint8_t> &src_live, const std::vector<uint32_t> &up_slots,
-                                  IngestPipe &pipe) {
+static int move_state_from_source(hny_builder *b, const hny_update *u, const PrevState &prev, IngestPipe &pipe) {
+  hny_builder *const src = prev.src;
+  const std::vector<uint32_t> &src_of = prev.src_of, &new_of = prev.new_of;
   hipStream_t st = b->stream;
   const hny_build_opts &o = b->o;
   GraphDev &g = b->g;
   const uint32_t n = b->n;
-  const bool has_norm = o.metric == HNY_COSINE || o.metric == HNY_BQ_COSINE;
   const size_t vb = vec_bytes(o.metric, o.dim), hb = hdr_bytes(o.metric);
   // the source's lists: a loaded graph keeps them where it put them (d_d0_ids / d_du_ids, nothing was inserted);
   // a built one in l0_ids / up_ids, finalised (finish() and the searches do that; do it here if neither ran)
-  if (!src->load_only && !src->finalized) {
-    HIP_TRY(hnyk_finalize_lists(src->d_l0_ids.p, src->d_fin_cnt0.p, src->n, o.M0, src->stream));
-    HIP_TRY(hnyk_finalize_lists(src->d_up_ids.p, src->d_fin_cntu.p, (u32)((size_t)src->n_upper * src->up_layers), o.M,
-                                src->stream));
-    src->finalized = true;
-  }
+  if (!src->load_only)
+    if (int rc = ensure_finalized(src, src->stream)) return rc;
   HIP_TRY(hipStreamSynchronize(src->stream));
   std::vector<unsigned short> mask(n);
   for (uint32_t t = 0; t < n; t++)
-    mask[t] = (unsigned short)(b->old_mask[t] | (src_of[t] != HNY_SENT && src_live[src_of[t]] ? HNY_MV_LIVE : 0u));
+    mask[t] = (unsigned short)(b->old_mask[t] | (src_of[t] != HNY_SENT && prev.src_live[src_of[t]] ? HNY_MV_LIVE : 0u));
   std::vector<u32> up_slot(std::max<uint32_t>(b->n_upper, 1), 0);
   for (uint32_t t = 0; t < n; t++)
     if (b->upper_idx[t] >= 0) up_slot[b->upper_idx[t]] = t;
+  std::vector<uint32_t> up_slots(u->n_upsert); // where the upserted rows go
+  for (uint64_t i = 0; i < u->n_upsert; i++) up_slots[i] = slot_of(b->ids, u->upsert_ids[i]);
   DevBuf<u32> d_src_of, d_new_of, d_up_slot, d_ups;
   DevBuf<unsigned short> d_mask;
   DevBuf<u64> d_bad;
@@ -965,11 +1061,11 @@ static int move_state_from_source(hny_builder *b, hny_builder *src, const hny_up
   // rows + norms
   MoveRowsArgs mr{};
   mr.src_rows = src->d_rows.p;
-  mr.src_norms = has_norm ? src->d_norms.p : nullptr;
+  mr.src_norms = src->d_norms.p;
   mr.src_of = d_src_of.p;
   mr.mask = d_mask.p;
   mr.dst_rows = b->d_rows.p;
-  mr.dst_norms = has_norm ? b->d_norms.p : nullptr;
+  mr.dst_norms = b->d_norms.p; // (NULL for the metrics without norms)
   mr.n_new = n;
   mr.n16 = g.n16;
   // hny_builder_set_profiling(src, 1): device time and bytes of k_move_rows (scripts/update_throughput.py)
@@ -996,34 +1092,26 @@ static int move_state_from_source(hny_builder *b, hny_builder *src, const hny_up
     HIP_TRY(hipMemcpyAsync(d_ups.p, up_slots.data(), (size_t)u->n_upsert * 4, hipMemcpyHostToDevice, st));
     if (u->vectors_are_f32) {
       HIP_TRY(hipStreamSynchronize(st)); // (d_ups is read by kernels behind copies of the pipe's own stream)
-      IngestJob j;
+      IngestJob j = ingest_job(o.metric, o.dim, b->d_rows.p, g.row_stride, b->d_norms.p);
       j.d_slots = d_ups.p;
-      j.metric = o.metric;
-      j.dim = o.dim;
       j.src = u->vectors;
       j.stride = u->stride;
       j.n = u->n_upsert;
-      j.rows = b->d_rows.p;
-      j.row_stride = g.row_stride;
-      j.norms = has_norm ? b->d_norms.p : nullptr;
       if (int rc = run_ingest(pipe, j, st)) return rc;
     } else {
       HIP_TRY(d_stage.alloc((size_t)u->n_upsert * g.row_stride));
       if (int rc = upload_rows(u->vectors, u->stride, vb, u->n_upsert, g.row_stride, d_stage.p, st)) return rc;
-      if (has_norm) {
+      if (g.norms) {
         up_norms.resize(u->n_upsert);
         for (uint64_t i = 0; i < u->n_upsert; i++) memcpy(&up_norms[i], (const unsigned char *)u->headers + i * hb, 4);
         HIP_TRY(d_stage_norms.alloc(u->n_upsert));
         HIP_TRY(hipMemcpyAsync(d_stage_norms.p, up_norms.data(), (size_t)u->n_upsert * 4, hipMemcpyHostToDevice, st));
       }
-      HIP_TRY(hnyk_scatter_rows(d_stage.p, d_stage_norms.p, d_ups.p, b->d_rows.p, has_norm ? b->d_norms.p : nullptr,
-                                (u32)u->n_upsert, g.n16, st));
+      HIP_TRY(hnyk_scatter_rows(d_stage.p, d_stage_norms.p, d_ups.p, b->d_rows.p, b->d_norms.p, (u32)u->n_upsert, g.n16, st));
     }
   }
   // lists: records of to-be-deleted and overwritten items move like any other (the build expects them in `prev`)
   const size_t nup = (size_t)b->n_upper * b->up_layers;
-  HIP_TRY(b->d_d0_ids.alloc((size_t)n * o.M0));
-  HIP_TRY(b->d_du_ids.alloc(std::max<size_t>(nup * o.M, 1)));
   MoveListsArgs ml{};
   ml.src_l0_ids = src->load_only ? src->d_d0_ids.p : src->d_l0_ids.p;
   ml.src_up_ids = src->load_only ? src->d_du_ids.p : src->d_up_ids.p;
@@ -1060,14 +1148,9 @@ static int move_state_from_source(hny_builder *b, hny_builder *src, const hny_up
   return HNY_OK;
 }
 
-// f32: items->vectors are f32 rows (Writer::add_item's input, writer.rs:462-480) that the device encodes while they
-// arrive (run_ingest); items->headers is not read
-static int create_impl(const hny_build_opts *opts, const hny_items *items, const IncrementalSpec *inc,
-                       hny_builder **out, bool f32 = false) {
-  if (!opts || !items || !out) return fail(HNY_ERR_INVALID_ARG, "null argument");
-  *out = nullptr;
-  const hny_build_opts &o = *opts;
-  // decided from the options alone, before any device is counted or opened
+// ---- creation, host part: the steps down to plan_sizes fill the builder's host fields and make no HIP call ----
+// decided from the options and the item arrays alone, before any device is counted or opened
+static int check_create_args(const hny_build_opts &o, const hny_items *items, const hny_builder *src, bool f32) {
   if (f32 && (o.n_gpus > 1 || o.devices))
     return fail(HNY_ERR_UNSUPPORTED, "f32 items on more than one GPU are not supported yet: encode them with "
                                      "hny_encode_vectors_gpu and pass codec bytes, or build on one GPU");
@@ -1077,24 +1160,16 @@ static int create_impl(const hny_build_opts *opts, const hny_items *items, const
   if ((o.schedule & ~(uint32_t)(HNY_SCHED_NO_SHUFFLE | HNY_SCHED_LEVEL_ORDER_ID | HNY_SCHED_UPDATE_NO_RAMP)) || o.reserved_)
     return fail(HNY_ERR_INVALID_ARG, "unknown hny_build_opts.schedule bits 0x%x", o.schedule);
   if (o.M0 > HNY_BIG_CAP) return fail(HNY_ERR_UNSUPPORTED, "M0 %u > %d", o.M0, HNY_BIG_CAP);
-  // 64 < M0 <= HNY_BIG_CAP: lists are walked 64 slots at a time; the workgroup kernels hold them whole (incremental
-  // builds: k_fill_gaps_wg), strict mode's one-wave kernels (k_prune, k_apply) take them 64 slots at a time —
-  // for fresh builds and loaded graphs; a strict-mode UPDATE of such lists (k_fill_gaps: one lane per slot) is refused
-  const bool bigcap = o.M0 > HNY_MAX_CAP;
   if (o.ef_construction == 0 || o.ef_construction > HNY_MAX_EF)
     return fail(HNY_ERR_UNSUPPORTED, "ef_construction %u outside [1, %d]", o.ef_construction,
                 HNY_MAX_EF);
   if (items->n >= (1ull << 31)) return fail(HNY_ERR_UNSUPPORTED, "n >= 2^31");
   const size_t vb = vec_bytes(o.metric, o.dim), hb = hdr_bytes(o.metric);
-  hny_builder *const src = inc ? inc->src : nullptr; // resident update: rows and lists come from this builder
   if (items->n && (!items->ids || (!src && (!items->vectors || (!f32 && !items->headers)))))
     return fail(HNY_ERR_INVALID_ARG, "null item arrays");
-  if (src) {
-    // (hny_builder_create_update has checked the upserted rows)
-  } else if (f32) {
-    int rcf = check_f32_rows(o.dim, items->n, items->vectors, items->stride);
-    if (rcf) return rcf;
-  } else {
+  if (f32 && !src) {
+    if (int rc = check_f32_rows(o.dim, items->n, items->vectors, items->stride)) return rc;
+  } else if (!src) { // (the upserted rows of a resident update: hny_builder_create_update has checked them)
     if (items->n && items->stride < vb)
       return fail(HNY_ERR_INVALID_DIM, "stride %zu < %zu codec bytes for dim %u", items->stride, vb,
                   o.dim); // Error::InvalidVecDimension
@@ -1103,188 +1178,136 @@ static int create_impl(const hny_build_opts *opts, const hny_items *items, const
   }
   for (uint64_t i = 1; i < items->n; i++)
     if (items->ids[i] <= items->ids[i - 1]) return fail(HNY_ERR_INVALID_ARG, "ids not ascending");
-
-  auto b = std::unique_ptr<hny_builder, void (*)(hny_builder *)>(new hny_builder(), hny_builder_destroy);
-  b->o = o;
-  b->frac = o.batch_frac > 0.0 ? o.batch_frac : 1.0;
-  b->bmax = o.batch_max ? o.batch_max : hny_default_batch_max(items->n);
-  b->incremental = inc != nullptr;
-  b->load_only = inc && inc->load_only;
-  b->from_update = src != nullptr;
-  uint32_t n16;
-  int rc = pick_shape(o.metric, o.dim, b->shape, n16);
-  if (rc) return rc;
-
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(HNY_ERR_NO_DEVICE, "no HIP device (this library has no CPU path)");
-  if (o.device >= 0) {
-    b->device = o.device;
-    HIP_TRY(hipSetDevice(b->device));
-  } else {
-    HIP_TRY(hipGetDevice(&b->device));
-  }
-  HIP_TRY(hipStreamCreate(&b->stream));
-  hipStream_t st = b->stream;
-  double t0 = now_s();
-
-  // ---- slot universe: fresh = the items; incremental = items U deleted U everything the old graph
-  // mentions (ids ascending => slot order == id order) ----
+  return HNY_OK;
+}
+// slot universe: fresh = the items; incremental = items U deleted U everything the old graph mentions, which
+// PrevState::init has put into b->ids already (ids ascending => slot order == id order)
+static int plan_universe(hny_builder *b, CreatePlan &P) {
+  const hny_items *items = P.items;
+  const IncrementalSpec *inc = P.inc;
   std::vector<uint32_t> &U = b->ids;
-  U.assign(items->ids, items->ids + items->n);
-  std::vector<uint8_t> src_live; // source builder: slots that hold a row
+  U.insert(U.end(), items->ids, items->ids + items->n);
   if (inc) {
-    const hny_prev_graph *pg = inc->prev;
-    if ((!pg && !src) || (inc->n_insert && !inc->to_insert) || (inc->n_delete && !inc->to_delete))
-      return fail(HNY_ERR_INVALID_ARG, "incremental: null argument");
     U.insert(U.end(), inc->to_delete, inc->to_delete + inc->n_delete);
-    if (src) {
-      // The host holds no lists of the source and does not fetch them: every slot that owns a record or a row,
-      // and the entry points.  Equal to what the branch below computes from the exported graph iff no finalised
-      // list names a slot without records — k_move_lists counts the entries that would (DESIGN.md §3c).
-      src_live = live_slots(src);
-      for (uint32_t s = 0; s < src->n; s++)
-        if (rec_mask_of(src, s) || src_live[s]) U.push_back(src->ids[s]);
-      for (uint32_t s : src->entry_points) U.push_back(src->ids[s]);
-    } else {
-      U.insert(U.end(), pg->rec_item, pg->rec_item + pg->n_records);
-      if (pg->n_records) U.insert(U.end(), pg->neighbours, pg->neighbours + pg->rec_offset[pg->n_records]);
-      U.insert(U.end(), pg->entry_points, pg->entry_points + pg->n_entry_points);
-    }
     std::sort(U.begin(), U.end());
     U.erase(std::unique(U.begin(), U.end()), U.end());
     if (U.size() >= (1ull << 31)) return fail(HNY_ERR_UNSUPPORTED, "n >= 2^31");
   }
   b->n = (uint32_t)U.size();
   const uint32_t n = b->n;
-  auto slot_of = [&](uint32_t id) { return (uint32_t)(std::lower_bound(U.begin(), U.end(), id) - U.begin()); };
-
-  std::vector<uint8_t> has_vec(n, inc ? 0 : 1);
-  std::vector<uint32_t> item_slot(items->n);
+  P.has_vec.assign(n, inc ? 0 : 1);
+  P.item_slot.resize(items->n);
   for (uint64_t i = 0; i < items->n; i++) {
-    item_slot[i] = inc ? slot_of(items->ids[i]) : (uint32_t)i;
-    has_vec[item_slot[i]] = 1;
+    P.item_slot[i] = inc ? slot_of(U, items->ids[i]) : (uint32_t)i;
+    P.has_vec[P.item_slot[i]] = 1;
   }
   b->ins_level.assign(n, -1);
   b->old_mask.assign(n, 0);
   b->deleted.assign(n, 0);
-  std::vector<std::pair<uint32_t, uint8_t>> levels; // (slot, level) in the reference's order
-  std::vector<uint32_t> src_of, new_of; // source builder: successor slot -> source slot and back, HNY_SENT = none
-
-  if (!inc) {
-    // ---- levels (hnsw.rs:141-149) + prepare_levels_and_entry_points, fresh DB (:222-289) ----
-    std::vector<uint8_t> lv(n);
-    if (items->levels)
-      memcpy(lv.data(), items->levels, n);
-    else
-      draw_levels(o.seed, o.M, n, lv.data());
-    for (uint32_t s = 0; s < n; s++) levels.push_back({s, lv[s]});
-    hny_rust_sort::sort_levels(levels, level_order_by_id(o)); // hnsw.rs:268, ties as the reference leaves them
-    if (shuffle_groups(o, b->bmax)) hny_rust_sort::shuffle_level_groups(levels);
-    b->max_level = n ? levels[0].second : 0;
-    for (uint32_t s = 0; s < n; s++)
-      if (lv[s] == b->max_level) b->entry_points.push_back(s);
-  } else {
-    // ---- incremental: writer.rs:539-554 set algebra is the caller's; here hnsw.rs:141-149 and the
-    // deletion branch of prepare_levels_and_entry_points (:236-289) ----
-    const hny_prev_graph *pg = inc->prev;
-    for (uint64_t i = 0; i < inc->n_delete; i++) b->deleted[slot_of(inc->to_delete[i])] = 1;
-    // the previous state: which records exist, entry points, max_level — from `prev`, or from the source builder
-    std::vector<uint32_t> prev_eps; // slots
-    uint32_t prev_max_level = 0;
-    if (src) {
-      // both universes ascend with the item ids: one merge gives both slot maps
-      src_of.assign(n, HNY_SENT);
-      new_of.assign(src->n, HNY_SENT);
-      for (uint32_t s = 0, t = 0; s < src->n && t < n; s++) {
-        while (t < n && U[t] < src->ids[s]) t++;
-        if (t < n && U[t] == src->ids[s]) {
-          src_of[t] = s;
-          new_of[s] = t;
-        }
-      }
-      for (uint32_t t = 0; t < n; t++)
-        if (src_of[t] != HNY_SENT) b->old_mask[t] = (uint16_t)rec_mask_of(src, src_of[t]);
-      for (uint32_t s : src->entry_points) prev_eps.push_back(new_of[s]);
-      prev_max_level = src->max_level;
-    } else {
-      for (uint64_t r = 0; r < pg->n_records; r++) {
-        if (pg->rec_layer[r] > HNY_MAX_LEVEL) return fail(HNY_ERR_INVALID_ARG, "old record on layer > %d", HNY_MAX_LEVEL);
-        b->old_mask[slot_of(pg->rec_item[r])] |= (uint16_t)(1u << pg->rec_layer[r]);
-      }
-      for (uint32_t i = 0; i < pg->n_entry_points; i++) prev_eps.push_back(slot_of(pg->entry_points[i]));
-      prev_max_level = pg->max_level;
-    }
-    std::vector<uint8_t> lv(inc->n_insert);
-    if (items->levels)
-      memcpy(lv.data(), items->levels, inc->n_insert); // one per to_insert id, ascending
-    else
-      draw_levels(o.seed, o.M, (uint32_t)inc->n_insert, lv.data());
-    uint32_t cur_max = 0;
-    for (uint64_t i = 0; i < inc->n_insert; i++) {
-      if (i && inc->to_insert[i] <= inc->to_insert[i - 1]) return fail(HNY_ERR_INVALID_ARG, "to_insert not ascending");
-      uint32_t s = slot_of(inc->to_insert[i]);
-      if (s >= n || U[s] != inc->to_insert[i] || !has_vec[s])
-        return fail(HNY_ERR_MISSING_KEY, "to_insert id %u has no item", inc->to_insert[i]); // Error::MissingKey
-      levels.push_back({s, lv[i]});
-      cur_max = std::max<uint32_t>(cur_max, lv[i]);
-    }
-    uint32_t max_level = prev_max_level;
-    std::vector<uint8_t> in_new(n, 0), in_old(n, 0);
-    uint32_t n_old = 0, n_new = 0;
-    std::vector<uint32_t> del_eps;
-    for (uint32_t s : prev_eps) {
-      if (!in_old[s]) { in_old[s] = 1; n_old++; }
-      if (b->deleted[s]) del_eps.push_back(s);
-      else if (!in_new[s]) { in_new[s] = 1; n_new++; }
-    }
-    uint32_t l = max_level;
-    for (size_t k = 0; k < del_eps.size(); k++) { // :243-257 replace deleted entry points
-      for (;;) {
-        if (l <= HNY_MAX_LEVEL)
-          for (uint32_t s = 0; s < n; s++) // iter_layer_links(l): ascending item
-            if (((b->old_mask[s] >> l) & 1) && !b->deleted[s] && !in_new[s]) {
-              in_new[s] = 1;
-              n_new++;
-              break;
-            }
-        if (l == 0) break;
-        l -= 1;
-      }
-    }
-    if (!del_eps.empty() && n_new != n_old) max_level = 0; // :261-263
-    for (uint32_t s = 0; s < n; s++)
-      if (in_new[s] && !inc->load_only) levels.push_back({s, (uint8_t)max_level}); // :267
-    hny_rust_sort::sort_levels(levels, level_order_by_id(o)); // :268
-    if (shuffle_groups(o, b->bmax)) hny_rust_sort::shuffle_level_groups(levels);
-    if (cur_max > max_level) { // :272-276
-      std::fill(in_new.begin(), in_new.end(), 0);
-      max_level = cur_max;
-    }
-    for (auto &pr : levels) { // :278-285
-      if (pr.second != max_level) break;
-      in_new[pr.first] = 1;
-    }
-    b->max_level = max_level;
-    for (uint32_t s = 0; s < n; s++)
-      if (in_new[s]) {
-        b->entry_points.push_back(s);
-        if (!has_vec[s]) return fail(HNY_ERR_MISSING_KEY, "entry point %u has no item", U[s]);
-      }
-    // The batch schedule of an update ramps up from one member like a fresh build's (n_done0 stays 0): rounds
-    // 1-2 counted the surviving old records as "already inserted", so an update went in as one or two batches —
-    // and new items that form a region of their own (a new topic appended to an index) searched a graph that
-    // held none of them: measured recall 0.51 on such a region against 0.99 with the ramp
-    // (scripts/r3_new_region_update.py).  HNY_SCHED_UPDATE_NO_RAMP: the old rule.
-    if (o.schedule & HNY_SCHED_UPDATE_NO_RAMP)
-      for (uint32_t s = 0; s < n; s++)
-        if ((b->old_mask[s] & 1) && !b->deleted[s]) b->n_done0++;
-    for (uint32_t s = 0; s < n; s++)
-      for (uint32_t ll = 0; ll <= HNY_MAX_LEVEL; ll++)
-        if (((b->old_mask[s] >> ll) & 1) && !b->deleted[s]) b->old_recs.push_back(((u64)ll << 31) | s);
+  return HNY_OK;
+}
+// levels (hnsw.rs:141-149) + prepare_levels_and_entry_points, fresh DB (:222-289)
+static void plan_levels_fresh(hny_builder *b, CreatePlan &P) {
+  const hny_build_opts &o = b->o;
+  const uint32_t n = b->n;
+  std::vector<uint8_t> lv(n);
+  if (P.items->levels)
+    memcpy(lv.data(), P.items->levels, n);
+  else
+    draw_levels(o.seed, o.M, n, lv.data());
+  for (uint32_t s = 0; s < n; s++) P.levels.push_back({s, lv[s]});
+  hny_rust_sort::sort_levels(P.levels, level_order_by_id(o)); // hnsw.rs:268, ties as the reference leaves them
+  if (shuffle_groups(o, b->bmax)) hny_rust_sort::shuffle_level_groups(P.levels);
+  b->max_level = n ? P.levels[0].second : 0;
+  for (uint32_t s = 0; s < n; s++)
+    if (lv[s] == b->max_level) b->entry_points.push_back(s);
+}
+// incremental: writer.rs:539-554 set algebra is the caller's; here hnsw.rs:141-149 and the deletion branch of
+// prepare_levels_and_entry_points (:236-289)
+static int plan_levels_incremental(hny_builder *b, CreatePlan &P) {
+  const hny_build_opts &o = b->o;
+  const IncrementalSpec *inc = P.inc;
+  const std::vector<uint32_t> &U = b->ids;
+  auto &levels = P.levels;
+  const uint32_t n = b->n;
+  for (uint64_t i = 0; i < inc->n_delete; i++) b->deleted[slot_of(U, inc->to_delete[i])] = 1;
+  // the previous state: which records exist, entry points, max_level
+  if (int rc = P.prev.bind_slots(b)) return rc;
+  std::vector<uint8_t> lv(inc->n_insert);
+  if (P.items->levels)
+    memcpy(lv.data(), P.items->levels, inc->n_insert); // one per to_insert id, ascending
+  else
+    draw_levels(o.seed, o.M, (uint32_t)inc->n_insert, lv.data());
+  uint32_t cur_max = 0;
+  for (uint64_t i = 0; i < inc->n_insert; i++) {
+    if (i && inc->to_insert[i] <= inc->to_insert[i - 1]) return fail(HNY_ERR_INVALID_ARG, "to_insert not ascending");
+    uint32_t s = slot_of(U, inc->to_insert[i]);
+    if (s >= n || U[s] != inc->to_insert[i] || !P.has_vec[s])
+      return fail(HNY_ERR_MISSING_KEY, "to_insert id %u has no item", inc->to_insert[i]); // Error::MissingKey
+    levels.push_back({s, lv[i]});
+    cur_max = std::max<uint32_t>(cur_max, lv[i]);
   }
+  uint32_t max_level = P.prev.max_level;
+  std::vector<uint8_t> in_new(n, 0), in_old(n, 0);
+  uint32_t n_old = 0, n_new = 0;
+  std::vector<uint32_t> del_eps;
+  for (uint32_t s : P.prev.eps) {
+    if (!in_old[s]) { in_old[s] = 1; n_old++; }
+    if (b->deleted[s]) del_eps.push_back(s);
+    else if (!in_new[s]) { in_new[s] = 1; n_new++; }
+  }
+  uint32_t l = max_level;
+  for (size_t k = 0; k < del_eps.size(); k++) { // :243-257 replace deleted entry points
+    for (;;) {
+      if (l <= HNY_MAX_LEVEL)
+        for (uint32_t s = 0; s < n; s++) // iter_layer_links(l): ascending item
+          if (((b->old_mask[s] >> l) & 1) && !b->deleted[s] && !in_new[s]) {
+            in_new[s] = 1;
+            n_new++;
+            break;
+          }
+      if (l == 0) break;
+      l -= 1;
+    }
+  }
+  if (!del_eps.empty() && n_new != n_old) max_level = 0; // :261-263
+  for (uint32_t s = 0; s < n; s++)
+    if (in_new[s] && !inc->load_only) levels.push_back({s, (uint8_t)max_level}); // :267
+  hny_rust_sort::sort_levels(levels, level_order_by_id(o)); // :268
+  if (shuffle_groups(o, b->bmax)) hny_rust_sort::shuffle_level_groups(levels);
+  if (cur_max > max_level) { // :272-276
+    std::fill(in_new.begin(), in_new.end(), 0);
+    max_level = cur_max;
+  }
+  for (auto &pr : levels) { // :278-285
+    if (pr.second != max_level) break;
+    in_new[pr.first] = 1;
+  }
+  b->max_level = max_level;
+  for (uint32_t s = 0; s < n; s++)
+    if (in_new[s]) {
+      b->entry_points.push_back(s);
+      if (!P.has_vec[s]) return fail(HNY_ERR_MISSING_KEY, "entry point %u has no item", U[s]);
+    }
+  // The batch schedule of an update ramps up from one member like a fresh build's (n_done0 stays 0): rounds
+  // 1-2 counted the surviving old records as "already inserted", so an update went in as one or two batches —
+  // and new items that form a region of their own (a new topic appended to an index) searched a graph that
+  // held none of them: measured recall 0.51 on such a region against 0.99 with the ramp
+  // (scripts/r3_new_region_update.py).  HNY_SCHED_UPDATE_NO_RAMP: the old rule.
+  if (o.schedule & HNY_SCHED_UPDATE_NO_RAMP)
+    for (uint32_t s = 0; s < n; s++)
+      if ((b->old_mask[s] & 1) && !b->deleted[s]) b->n_done0++;
+  for (uint32_t s = 0; s < n; s++)
+    for (uint32_t ll = 0; ll <= HNY_MAX_LEVEL; ll++)
+      if (((b->old_mask[s] >> ll) & 1) && !b->deleted[s]) b->old_recs.push_back(((u64)ll << 31) | s);
+  return HNY_OK;
+}
+// the insertion order, where each slot's lists are stored, and how much finish() can export
+static int plan_storage(hny_builder *b, const CreatePlan &P) {
+  const hny_build_opts &o = b->o;
+  const uint32_t n = b->n;
   if (b->max_level > HNY_MAX_LEVEL) return fail(HNY_ERR_INVALID_ARG, "level > %d", HNY_MAX_LEVEL);
-  for (auto &pr : levels) {
+  for (auto &pr : P.levels) {
     b->order.push_back(pr.first);
     b->order_level.push_back(pr.second);
     b->ins_level[pr.first] = std::max<int8_t>(b->ins_level[pr.first], (int8_t)pr.second);
@@ -1308,30 +1331,32 @@ static int create_impl(const hny_build_opts *opts, const hny_items *items, const
   }
   if (b->entry_points.size() > HNY_MAX_EPS)
     return fail(HNY_ERR_UNSUPPORTED, "%zu entry points > %d", b->entry_points.size(), HNY_MAX_EPS);
-  for (uint32_t s = 0; s < n; s++) { // what finish() will export at most (its rec_mask)
-    if (b->deleted[s]) continue;
-    uint32_t m = b->old_mask[s];
-    if (b->ins_level[s] >= 0) m |= (2u << b->ins_level[s]) - 1u;
+  for (uint32_t s = 0; s < n; s++) { // what finish() will export at most
+    const uint32_t m = rec_mask_of(b, s);
     const uint32_t c = (uint32_t)__builtin_popcount(m);
     b->nrec_bound += c;
     b->nbr_bound += (m & 1u ? o.M0 : 0u) + (uint64_t)(c - (m & 1u)) * o.M;
   }
-
-  // ---- sizes ----
   b->top_layer_nodes = 0; // nodes a walk can meet on layer max_level: old records there + what gets inserted there
   for (uint32_t s = 0; s < n; s++)
     if ((((b->old_mask.empty() ? 0u : b->old_mask[s]) >> b->max_level) & 1u && !b->deleted[s]) ||
         b->ins_level[s] >= (int8_t)b->max_level)
       b->top_layer_nodes++;
+  return HNY_OK;
+}
+// the sizes of the per-batch buffers and the launch choices that follow from the plan
+static int plan_sizes(hny_builder *b, const CreatePlan &P) {
+  const hny_build_opts &o = b->o;
+  const uint32_t n = b->n, n16 = b->g.n16;
   b->rcap = res_capacity(o.ef_construction, (uint32_t)b->entry_points.size(), n, b->top_layer_nodes, HNY_RES_GLOBAL_MAX);
   b->max_batch = 1;
   b->max_ops = 2;
   b->sel_words = 2;
   for (size_t pos = 0; pos < b->order.size();) {
-    size_t e = group_end(b.get(), pos);
+    size_t e = group_end(b, pos);
     uint32_t L = b->order_level[pos];
     uint64_t bs = std::min<uint64_t>(b->bmax, e - pos);
-    uint64_t cs = cap_of(b.get(), L);
+    uint64_t cs = cap_of(b, L);
     b->max_batch = std::max<uint32_t>(b->max_batch, (uint32_t)bs);
     b->max_ops = std::max<size_t>(b->max_ops, (size_t)(bs * (L + 1) * cs * 2));
     b->sel_words = std::max<size_t>(b->sel_words, (size_t)(bs * (L + 1) * (cs + 1)));
@@ -1350,52 +1375,43 @@ static int create_impl(const hny_build_opts *opts, const hny_items *items, const
   b->bits_words = (n + 31) / 32 + 1;
   b->log_cap = (uint32_t)std::max(1024, env_int("HNY_VISITED_LOG", 16384));
   b->vis_slots_env = env_int("HNY_VIS_SLOTS", -1);
-  {
-    // LDS staging budget of the workgroup prune, whole load groups
-    int rpg = 64 / b->shape.lpr;
-    int sl = (int)((u32)std::max(0, env_int("HNY_STAGE_BYTES", 24576)) / (n16 * 16u));
-    if (sl > HNY_MAX_CAP) sl = HNY_MAX_CAP;
-    b->stage_rows = sl / rpg * rpg;
-    // short rows: as many selected rows as 6 KB per wave hold (20 waves per CU)
-    b->n8_stage_rows = (int)std::min<uint32_t>(HNY_MAX_CAP, std::max<uint32_t>(1, 6144u / (n16 * 16u)));
-    // the workgroup prune kernels carry their own wave-order arithmetic: strict mode and very long
-    // rows use the single-wave kernels, which all go through dist_rows
-    b->wave_prune_only = b->shape.nch > 8 || o.x86_order; // the one-wave prune: strict mode, rows beyond 8 KB
-    // (strict mode updates of lists beyond 64 slots: k_fill_gaps_wg with the one-wave prune inside, round 5)
-    if (bigcap && b->shape.nch > 8 && inc && !inc->load_only)
-      return fail(HNY_ERR_UNSUPPORTED, "M0 %u > %d: an incremental build needs the workgroup kernels (rows <= 8 KB)",
-                  o.M0, HNY_MAX_CAP);
-  }
+  // LDS staging budget of the workgroup prune, whole load groups
+  int rpg = 64 / b->shape.lpr;
+  int sl = (int)((u32)std::max(0, env_int("HNY_STAGE_BYTES", 24576)) / (n16 * 16u));
+  if (sl > HNY_MAX_CAP) sl = HNY_MAX_CAP;
+  b->stage_rows = sl / rpg * rpg;
+  // short rows: as many selected rows as 6 KB per wave hold (20 waves per CU)
+  b->n8_stage_rows = (int)std::min<uint32_t>(HNY_MAX_CAP, std::max<uint32_t>(1, 6144u / (n16 * 16u)));
+  // the workgroup prune kernels carry their own wave-order arithmetic: strict mode and very long
+  // rows use the single-wave kernels, which all go through dist_rows
+  b->wave_prune_only = b->shape.nch > 8 || o.x86_order; // the one-wave prune: strict mode, rows beyond 8 KB
+  // 64 < M0 <= HNY_BIG_CAP: lists are walked 64 slots at a time; the workgroup kernels hold them whole (incremental
+  // builds: k_fill_gaps_wg), strict mode's one-wave kernels (k_prune, k_apply) take them 64 slots at a time —
+  // for fresh builds and loaded graphs; a strict-mode UPDATE of such lists (k_fill_gaps: one lane per slot) is refused
+  // (strict mode updates of lists beyond 64 slots: k_fill_gaps_wg with the one-wave prune inside, round 5)
+  if (o.M0 > HNY_MAX_CAP && b->shape.nch > 8 && P.inc && !P.inc->load_only)
+    return fail(HNY_ERR_UNSUPPORTED, "M0 %u > %d: an incremental build needs the workgroup kernels (rows <= 8 KB)",
+                o.M0, HNY_MAX_CAP);
+  return HNY_OK;
+}
 
-  // ---- device memory ----
-  GraphDev &g = b->g;
-  g.n = n;
-  g.metric = o.metric;
-  g.mclass = mclass_of(o.metric);
-  g.n16 = n16;
-  g.row_stride = n16 * 16;
-  g.bin_bits = (u32)(vb * 8);
-  g.bin_inv = (g.bin_bits && (g.bin_bits & (g.bin_bits - 1)) == 0) ? 1.0f / (float)g.bin_bits : 0.0f;
-  g.M = o.M;
-  g.M0 = o.M0;
-  g.max_level = b->max_level;
-  g.up_layers = b->up_layers;
-  g.n_upper = b->n_upper;
-  g.alpha = o.alpha;
-  g.incremental = inc ? 1 : 0;
-  g.dim = o.dim;
-  g.x86_order = o.x86_order ? 1 : 0;
+// ---- creation, device part ----
+// every buffer the builder keeps, and the GraphDev the kernels are handed
+static int alloc_device(hny_builder *b, const CreatePlan &P) {
+  const hny_build_opts &o = b->o;
+  hipStream_t st = b->stream;
+  const uint32_t n = b->n;
   const size_t nn = std::max<uint32_t>(n, 1);
   const size_t no = std::max<size_t>(b->order.size(), 1);
-  HIP_TRY(b->d_rows.alloc(nn * g.row_stride));
+  const size_t nup = (size_t)b->n_upper * b->up_layers;
+  const uint32_t row_stride = b->g.n16 * 16;
+  HIP_TRY(b->d_rows.alloc(nn * row_stride));
   HIP_TRY(b->d_level.alloc(nn));
   HIP_TRY(b->d_upper_idx.alloc(nn));
-  const bool has_norm = o.metric == HNY_COSINE || o.metric == HNY_BQ_COSINE;
-  if (has_norm) HIP_TRY(b->d_norms.alloc(nn));
+  if (has_norms(o.metric)) HIP_TRY(b->d_norms.alloc(nn));
   HIP_TRY(b->d_l0_ids.alloc(nn * o.M0));
   HIP_TRY(b->d_l0_dist.alloc(nn * o.M0));
   HIP_TRY(b->d_l0_cnt.alloc(nn));
-  const size_t nup = (size_t)b->n_upper * b->up_layers;
   HIP_TRY(b->d_up_ids.alloc(nup * o.M));
   HIP_TRY(b->d_up_dist.alloc(nup * o.M));
   HIP_TRY(b->d_up_cnt.alloc(nup));
@@ -1445,7 +1461,7 @@ static int create_impl(const hny_build_opts *opts, const hny_items *items, const
     // set ~1 GB per builder aside for them (x 8 replicas on a node) and clipped a heap at 2^22 entries, which a
     // walk over > 4 M equidistant items would have overflowed.  Only a builder whose op arrays cannot hold ONE
     // full heap (tiny batch_max on a large index) gets heaps of its own, of at most 2^25 entries (256 MB).
-    const uint64_t c_full = (uint64_t)n + 1 + eps_cap_of(b.get());
+    const uint64_t c_full = (uint64_t)n + 1 + eps_cap_of(b);
     b->heap_r_cap = b->rcap + 1;
     if (b->d_ops.n >= c_full) {
       b->heap_c_cap = (uint32_t)std::min<uint64_t>(c_full, 0xFFFFFFFFull);
@@ -1500,9 +1516,33 @@ static int create_impl(const hny_build_opts *opts, const hny_items *items, const
     }
   }
   HIP_TRY(b->d_sort_tmp.alloc(b->sort_tmp_bytes + 16));
+  if (b->incremental && n) { // the previous graph as Links records, and what fill_gaps reads
+    HIP_TRY(b->d_d0_ids.alloc((size_t)n * o.M0));
+    HIP_TRY(b->d_du_ids.alloc(std::max<size_t>(nup * o.M, 1)));
+    HIP_TRY(b->d_has_vec.alloc(n));
+    HIP_TRY(b->d_deleted.alloc(n));
+    HIP_TRY(b->d_old_recs.alloc(std::max<size_t>(b->old_recs.size(), 1)));
+  }
 
+  GraphDev &g = b->g;
+  const size_t vb = vec_bytes(o.metric, o.dim);
+  g.n = n;
+  g.metric = o.metric;
+  g.mclass = mclass_of(o.metric);
+  g.row_stride = row_stride;
+  g.bin_bits = (u32)(vb * 8);
+  g.bin_inv = (g.bin_bits && (g.bin_bits & (g.bin_bits - 1)) == 0) ? 1.0f / (float)g.bin_bits : 0.0f;
+  g.M = o.M;
+  g.M0 = o.M0;
+  g.max_level = b->max_level;
+  g.up_layers = b->up_layers;
+  g.n_upper = b->n_upper;
+  g.alpha = o.alpha;
+  g.incremental = b->incremental ? 1 : 0;
+  g.dim = o.dim;
+  g.x86_order = o.x86_order ? 1 : 0;
   g.rows = b->d_rows.p;
-  g.norms = has_norm ? b->d_norms.p : nullptr;
+  g.norms = b->d_norms.p; // NULL for the metrics without norms
   g.level = b->d_level.p;
   g.upper_idx = b->d_upper_idx.p;
   g.l0_ids = b->d_l0_ids.p;
@@ -1512,114 +1552,152 @@ static int create_impl(const hny_build_opts *opts, const hny_items *items, const
   g.up_dist = b->d_up_dist.p;
   g.up_cnt = b->d_up_cnt.p;
   g.stats = b->d_stats.p;
+  g.d0_ids = b->d_d0_ids.p;
+  g.du_ids = b->d_du_ids.p;
+  g.has_vec = b->d_has_vec.p;
+  return HNY_OK;
+}
 
-  // ---- upload (the "export to HBM" that replaces FrozenReader, parallel.rs:11-45) ----
-  DevBuf<u32> d_item_slot; // f32 items: alive until the stream is synchronised below
-  IngestPipe pipe;
-  if (n) {
-    if (src) {
-      std::vector<uint32_t> up_slots(inc->n_insert);
-      for (uint64_t i = 0; i < inc->n_insert; i++) up_slots[i] = slot_of(inc->to_insert[i]);
-      rc = move_state_from_source(b.get(), src, inc->upd, src_of, new_of, src_live, up_slots, pipe);
-      if (rc) return rc;
-    } else if (f32) {
-      IngestJob j;
-      if (inc) { // items are a subset of the universe: the other slots hold zero rows and zero norms
-        HIP_TRY(hipMemsetAsync(b->d_rows.p, 0, (size_t)n * g.row_stride, st));
-        if (has_norm) HIP_TRY(hipMemsetAsync(b->d_norms.p, 0, (size_t)n * 4, st));
-        if (items->n) {
-          HIP_TRY(d_item_slot.alloc(items->n));
-          HIP_TRY(hipMemcpyAsync(d_item_slot.p, item_slot.data(), (size_t)items->n * 4, hipMemcpyHostToDevice, st));
-          HIP_TRY(hipStreamSynchronize(st));
-        }
-        j.d_slots = d_item_slot.p;
-      }
-      j.metric = o.metric;
-      j.dim = o.dim;
-      j.src = items->vectors;
-      j.stride = items->stride;
-      j.n = items->n;
-      j.rows = b->d_rows.p;
-      j.row_stride = g.row_stride;
-      j.norms = has_norm ? b->d_norms.p : nullptr;
-      rc = run_ingest(pipe, j, st);
-      if (rc) return rc;
-    } else if (!inc) {
-      rc = upload_rows(items->vectors, items->stride, vb, n, g.row_stride, b->d_rows.p, st);
-      if (rc) return rc;
-    } else {
-      HIP_TRY(hipMemsetAsync(b->d_rows.p, 0, (size_t)n * g.row_stride, st));
-      const size_t chunk = std::max<size_t>(1, (64u << 20) / g.row_stride);
-      std::vector<unsigned char> stage(chunk * g.row_stride);
-      uint64_t i = 0;
-      for (uint32_t s0 = 0; s0 < n; s0 += (uint32_t)chunk) { // items are a subset of the universe
-        uint32_t cnt = (uint32_t)std::min<size_t>(chunk, n - s0);
-        std::fill(stage.begin(), stage.begin() + (size_t)cnt * g.row_stride, 0);
-        for (; i < items->n && item_slot[i] < s0 + cnt; i++)
-          memcpy(&stage[(size_t)(item_slot[i] - s0) * g.row_stride],
-                 (const unsigned char *)items->vectors + i * items->stride, vb);
-        HIP_TRY(hipMemcpyAsync(b->d_rows.p + (size_t)s0 * g.row_stride, stage.data(),
-                               (size_t)cnt * g.row_stride, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipStreamSynchronize(st));
-      }
+// ---- the rows (the "export to HBM" that replaces FrozenReader, parallel.rs:11-45): codec bytes through upload_rows,
+// a source builder's through move_state_from_source ----
+// f32 rows (Writer::add_item's input, writer.rs:462-480; items->headers is not read): the device encodes them while
+// they arrive.  `d_item_slot` stays alive until the caller has synchronised the stream.
+static int upload_rows_f32(hny_builder *b, const CreatePlan &P, IngestPipe &pipe, DevBuf<u32> &d_item_slot) {
+  const hny_items *items = P.items;
+  hipStream_t st = b->stream;
+  const GraphDev &g = b->g;
+  IngestJob j = ingest_job(b->o.metric, b->o.dim, b->d_rows.p, g.row_stride, b->d_norms.p);
+  if (P.inc) { // items are a subset of the universe: the other slots hold zero rows and zero norms
+    HIP_TRY(hipMemsetAsync(b->d_rows.p, 0, (size_t)b->n * g.row_stride, st));
+    if (g.norms) HIP_TRY(hipMemsetAsync(b->d_norms.p, 0, (size_t)b->n * 4, st));
+    if (items->n) {
+      HIP_TRY(d_item_slot.alloc(items->n));
+      HIP_TRY(hipMemcpyAsync(d_item_slot.p, P.item_slot.data(), (size_t)items->n * 4, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipStreamSynchronize(st)); // (read by kernels behind copies of the pipe's own stream)
     }
-    HIP_TRY(hipMemcpyAsync(b->d_level.p, b->level.data(), n, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(b->d_upper_idx.p, b->upper_idx.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
-    if (!b->order.empty())
-      HIP_TRY(hipMemcpyAsync(b->d_order.p, b->order.data(), b->order.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(b->d_eps.p, b->entry_points.data(), b->entry_points.size() * 4,
-                           hipMemcpyHostToDevice, st));
-    std::vector<float> norms;
-    if (has_norm && !f32 && !src) {
-      norms.assign(n, 0.f);
-      for (uint64_t i = 0; i < items->n; i++)
-        memcpy(&norms[item_slot[i]], (const unsigned char *)items->headers + (size_t)i * hb, 4);
-      HIP_TRY(hipMemcpyAsync(b->d_norms.p, norms.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
-    }
-    HIP_TRY(hipStreamSynchronize(st));
+    j.d_slots = d_item_slot.p;
   }
-  if (inc && n) {
-    // the previous graph, as Links records: ascending ids, HNY_SENT padded
-    const hny_prev_graph *pg = inc->prev;
-    std::vector<u32> d0, du;
-    if (!src) {
-      d0.assign((size_t)n * o.M0, HNY_SENT);
-      du.assign(std::max<size_t>(nup * o.M, 1), HNY_SENT);
-    }
-    for (uint64_t r = 0; !src && r < pg->n_records; r++) {
-      uint32_t s = slot_of(pg->rec_item[r]), ll = pg->rec_layer[r];
+  j.src = items->vectors;
+  j.stride = items->stride;
+  j.n = items->n;
+  return run_ingest(pipe, j, st);
+}
+// what follows the rows whatever their source: level, upper_idx, order, the entry points — and the norms out of
+// the items' headers, where the rows came as codec bytes
+static int upload_plan(hny_builder *b, const CreatePlan &P, bool norms_from_headers) {
+  hipStream_t st = b->stream;
+  const uint32_t n = b->n;
+  HIP_TRY(hipMemcpyAsync(b->d_level.p, b->level.data(), n, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(b->d_upper_idx.p, b->upper_idx.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+  if (!b->order.empty())
+    HIP_TRY(hipMemcpyAsync(b->d_order.p, b->order.data(), b->order.size() * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(b->d_eps.p, b->entry_points.data(), b->entry_points.size() * 4,
+                         hipMemcpyHostToDevice, st));
+  std::vector<float> norms;
+  if (b->g.norms && norms_from_headers) {
+    const size_t hb = hdr_bytes(b->o.metric);
+    norms.assign(n, 0.f);
+    for (uint64_t i = 0; i < P.items->n; i++)
+      memcpy(&norms[P.item_slot[i]], (const unsigned char *)P.items->headers + (size_t)i * hb, 4);
+    HIP_TRY(hipMemcpyAsync(b->d_norms.p, norms.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  return HNY_OK;
+}
+// incremental: the previous graph's lists as Links records (ascending ids, HNY_SENT padded) — built here from an
+// hny_prev_graph; a source builder's are in place already (move_state_from_source) — then what fill_gaps reads
+static int upload_prev_state(hny_builder *b, const CreatePlan &P) {
+  const hny_build_opts &o = b->o;
+  hipStream_t st = b->stream;
+  const uint32_t n = b->n;
+  std::vector<u32> d0, du;
+  if (const hny_prev_graph *pg = P.prev.pg) {
+    d0.assign((size_t)n * o.M0, HNY_SENT);
+    du.assign(b->d_du_ids.n, HNY_SENT);
+    for (uint64_t r = 0; r < pg->n_records; r++) {
+      uint32_t s = slot_of(b->ids, pg->rec_item[r]), ll = pg->rec_layer[r];
       uint64_t c = pg->rec_offset[r + 1] - pg->rec_offset[r];
       uint32_t cap = ll == 0 ? o.M0 : o.M;
-      if (c > cap) return fail(HNY_ERR_UNSUPPORTED, "old record (%u, %u) has %llu > %u links", U[s], ll,
+      if (c > cap) return fail(HNY_ERR_UNSUPPORTED, "old record (%u, %u) has %llu > %u links", b->ids[s], ll,
                                (unsigned long long)c, cap);
       u32 *dst = ll == 0 ? &d0[(size_t)s * o.M0]
                          : &du[((size_t)b->upper_idx[s] * b->up_layers + (ll - 1)) * o.M];
-      for (uint64_t k = 0; k < c; k++) dst[k] = slot_of(pg->neighbours[pg->rec_offset[r] + k]);
+      for (uint64_t k = 0; k < c; k++) dst[k] = slot_of(b->ids, pg->neighbours[pg->rec_offset[r] + k]);
     }
-    if (!src) { // (a source builder's lists are in place already: move_state_from_source)
-      HIP_TRY(b->d_d0_ids.alloc(d0.size()));
-      HIP_TRY(b->d_du_ids.alloc(du.size()));
-      HIP_TRY(hipMemcpyAsync(b->d_d0_ids.p, d0.data(), d0.size() * 4, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(b->d_du_ids.p, du.data(), du.size() * 4, hipMemcpyHostToDevice, st));
-    }
-    HIP_TRY(b->d_has_vec.alloc(n));
-    HIP_TRY(b->d_deleted.alloc(n));
-    HIP_TRY(b->d_old_recs.alloc(std::max<size_t>(b->old_recs.size(), 1)));
-    HIP_TRY(hipMemcpyAsync(b->d_has_vec.p, has_vec.data(), n, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(b->d_deleted.p, b->deleted.data(), n, hipMemcpyHostToDevice, st));
-    if (!b->old_recs.empty())
-      HIP_TRY(hipMemcpyAsync(b->d_old_recs.p, b->old_recs.data(), b->old_recs.size() * 8,
-                             hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    g.d0_ids = b->d_d0_ids.p;
-    g.du_ids = b->d_du_ids.p;
-    g.has_vec = b->d_has_vec.p;
+    HIP_TRY(hipMemcpyAsync(b->d_d0_ids.p, d0.data(), d0.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b->d_du_ids.p, du.data(), du.size() * 4, hipMemcpyHostToDevice, st));
   }
-  rc = reset_graph(b.get());
+  HIP_TRY(hipMemcpyAsync(b->d_has_vec.p, P.has_vec.data(), n, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(b->d_deleted.p, b->deleted.data(), n, hipMemcpyHostToDevice, st));
+  if (!b->old_recs.empty())
+    HIP_TRY(hipMemcpyAsync(b->d_old_recs.p, b->old_recs.data(), b->old_recs.size() * 8,
+                           hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return HNY_OK;
+}
+
+// Every builder is made here: a fresh index, an incremental build on an hny_prev_graph or on a source builder
+// (`inc`), from codec bytes or from f32 rows (`f32`).  Host plan first, then the device.
+static int create_impl(const hny_build_opts *opts, const hny_items *items, const IncrementalSpec *inc,
+                       hny_builder **out, bool f32 = false) {
+  if (!opts || !items || !out) return fail(HNY_ERR_INVALID_ARG, "null argument");
+  *out = nullptr;
+  const hny_build_opts &o = *opts;
+  hny_builder *const src = inc ? inc->src : nullptr; // resident update: rows and lists come from this builder
+  int rc = check_create_args(o, items, src, f32);
   if (rc) return rc;
+
+  auto b = std::unique_ptr<hny_builder, void (*)(hny_builder *)>(new hny_builder(), hny_builder_destroy);
+  b->o = o;
+  b->frac = o.batch_frac > 0.0 ? o.batch_frac : 1.0;
+  b->bmax = o.batch_max ? o.batch_max : hny_default_batch_max(items->n);
+  b->incremental = inc != nullptr;
+  b->load_only = inc && inc->load_only;
+  b->from_update = src != nullptr;
+  CreatePlan P{items, inc};
+  rc = pick_shape(o.metric, o.dim, b->shape, b->g.n16);
+  if (rc) return rc;
+
+  if ((rc = use_device(o.device))) return rc;
+  HIP_TRY(hipGetDevice(&b->device));
+  HIP_TRY(hipStreamCreate(&b->stream));
+  hipStream_t st = b->stream;
+  double t0 = now_s();
+
+  // ---- the plan: host only ----
+  if (inc && (rc = P.prev.init(inc, b->ids))) return rc;
+  if ((rc = plan_universe(b.get(), P))) return rc;
+  if (!inc)
+    plan_levels_fresh(b.get(), P);
+  else if ((rc = plan_levels_incremental(b.get(), P)))
+    return rc;
+  if ((rc = plan_storage(b.get(), P))) return rc;
+  if ((rc = plan_sizes(b.get(), P))) return rc;
+
+  // ---- the device ----
+  if ((rc = alloc_device(b.get(), P))) return rc;
+  DevBuf<u32> d_item_slot; // f32 items: alive until the stream is synchronised below
+  IngestPipe pipe;
+  const size_t vb = vec_bytes(o.metric, o.dim);
+  if (b->n) {
+    if (src)
+      rc = move_state_from_source(b.get(), inc->upd, P.prev, pipe);
+    else if (f32)
+      rc = upload_rows_f32(b.get(), P, pipe, d_item_slot);
+    else if (!inc)
+      rc = upload_rows(items->vectors, items->stride, vb, b->n, b->g.row_stride, b->d_rows.p, st);
+    else { // codec bytes of items that are a subset of the universe: the other slots hold zero rows
+      HIP_TRY(hipMemsetAsync(b->d_rows.p, 0, (size_t)b->n * b->g.row_stride, st));
+      rc = upload_rows(items->vectors, items->stride, vb, items->n, b->g.row_stride, b->d_rows.p, st, P.item_slot.data(), b->n);
+    }
+    if (rc) return rc;
+    if ((rc = upload_plan(b.get(), P, !f32 && !src))) return rc;
+    if (inc && (rc = upload_prev_state(b.get(), P))) return rc;
+  }
+  if ((rc = reset_graph(b.get()))) return rc;
   HIP_TRY(hipStreamSynchronize(st));
   b->n_items = items->n;
-  if (inc) b->item_slot = std::move(item_slot);
+  if (inc) b->item_slot = std::move(P.item_slot);
   b->t_upload = now_s() - t0;
   b->t_build0 = now_s();
   *out = b.release();
@@ -2196,11 +2274,7 @@ int hny_builder_finish(hny_builder *b, hny_graph **out) {
   // finalise every list on the device (sort + dedup), then copy through pinned staging
   const uint32_t upl = b->up_layers;
   const size_t nup = (size_t)b->n_upper * upl;
-  if (!b->finalized) {
-    HIP_TRY(hnyk_finalize_lists(b->d_l0_ids.p, b->d_fin_cnt0.p, n, M0, b->stream));
-    HIP_TRY(hnyk_finalize_lists(b->d_up_ids.p, b->d_fin_cntu.p, (u32)nup, M, b->stream));
-    b->finalized = true;
-  }
+  if (int rc = ensure_finalized(b, b->stream)) return rc;
   // the counts first (small), then the lists (128 MB at C2): the record offsets are computed on the
   // host while the lists are still in flight
   if (n) HIP_TRY(hipMemcpyAsync(b->h_cnt0, b->d_fin_cnt0.p, (size_t)n * 4, hipMemcpyDeviceToHost, b->stream));
@@ -2398,25 +2472,31 @@ extern "C" int hny_internal_build_multi(const hny_build_opts *opts, const hny_it
 static bool wants_multi(const hny_build_opts *o) { return o && (o->n_gpus > 1 || (o->n_gpus == 1 && o->devices)); }
 
 static int run_fill_gaps(hny_builder *b);
-// every batch of a freshly created builder, then (incremental) fill_gaps, finish and destroy
-static int run_build(hny_builder *b, const hny_build_opts *opts, hny_graph **out) {
-  int rc;
+// every batch that is left of a builder's schedule; HNY_ERR_CANCELLED when `opts->cancel` asks for it (the builder
+// is the caller's to clean up)
+static int run_batches(hny_builder *b, const hny_build_opts *opts) {
   for (;;) {
     // cancel: probed before every batch, i.e. every <= batch_max items (the reference probes every
     // CANCELLATION_PROBING = 10 000 items, lib.rs:140, hnsw.rs:174-177)
-    if (opts->cancel && opts->cancel(opts->cancel_ctx)) {
-      hny_builder_destroy(b);
-      return fail(HNY_ERR_CANCELLED, "build cancelled");
-    }
+    if (opts->cancel && opts->cancel(opts->cancel_ctx)) return fail(HNY_ERR_CANCELLED, "build cancelled");
     hny_batch bt;
-    rc = hny_builder_next_batch(b, &bt);
-    if (rc || bt.count == 0) break;
+    int rc = hny_builder_next_batch(b, &bt);
+    if (rc || bt.count == 0) return rc;
     rc = hny_builder_search(b, 0, bt.count, nullptr);
-    if (rc) break;
+    if (rc) return rc;
     rc = hny_builder_apply(b, nullptr);
-    if (rc) break;
+    if (rc) return rc;
     if (opts->progress) opts->progress(opts->progress_ctx, b->pos, b->order.size());
   }
+}
+
+// a builder created, every batch of it, then (incremental) fill_gaps, finish and destroy
+static int run_build(const hny_build_opts *opts, const hny_items *items, const IncrementalSpec *inc, bool f32,
+                     hny_graph **out) {
+  hny_builder *b = nullptr;
+  int rc = create_impl(opts, items, inc, &b, f32);
+  if (rc) return rc;
+  rc = run_batches(b, opts);
   if (!rc) rc = run_fill_gaps(b); // nothing to do on a fresh index
   if (!rc) rc = hny_builder_finish(b, out);
   hny_builder_destroy(b);
@@ -2430,19 +2510,13 @@ int hny_build(const hny_build_opts *opts, const hny_items *items, hny_graph **ou
     if (!items) return fail(HNY_ERR_INVALID_ARG, "null argument");
     return hny_internal_build_multi(opts, items, nullptr, 0, nullptr, 0, nullptr, out);
   }
-  hny_builder *b = nullptr;
-  int rc = hny_builder_create(opts, items, &b);
-  if (rc) return rc;
-  return run_build(b, opts, out);
+  return run_build(opts, items, nullptr, false, out);
 }
 
 int hny_build_f32(const hny_build_opts *opts, const hny_items *f32_items, hny_graph **out) {
   if (!out) return fail(HNY_ERR_INVALID_ARG, "null out");
   *out = nullptr;
-  hny_builder *b = nullptr;
-  int rc = create_impl(opts, f32_items, nullptr, &b, true);
-  if (rc) return rc;
-  return run_build(b, opts, out);
+  return run_build(opts, f32_items, nullptr, true, out);
 }
 
 // fill_gaps_from_deleted (hnsw.rs:187, 334-415): merge old and new links of every surviving old
@@ -2497,16 +2571,14 @@ int hny_builder_create_incremental(const hny_build_opts *opts, const hny_items *
 int hny_builder_load(const hny_build_opts *opts, const hny_items *items, const hny_prev_graph *prev,
                      hny_builder **out) {
   if (!prev) return fail(HNY_ERR_INVALID_ARG, "null graph");
-  IncrementalSpec inc{nullptr, 0, nullptr, 0, prev};
-  inc.load_only = true;
+  IncrementalSpec inc{nullptr, 0, nullptr, 0, prev, true};
   return create_impl(opts, items, &inc, out);
 }
 
 int hny_builder_load_f32(const hny_build_opts *opts, const hny_items *f32_items, const hny_prev_graph *prev,
                          hny_builder **out) {
   if (!prev) return fail(HNY_ERR_INVALID_ARG, "null graph");
-  IncrementalSpec inc{nullptr, 0, nullptr, 0, prev};
-  inc.load_only = true;
+  IncrementalSpec inc{nullptr, 0, nullptr, 0, prev, true};
   return create_impl(opts, f32_items, &inc, out, true);
 }
 
@@ -2555,10 +2627,7 @@ int hny_build_incremental(const hny_build_opts *opts, const hny_items *items, co
     return hny_internal_build_multi(opts, items, to_insert, n_insert, to_delete, n_delete, prev, out);
   }
   IncrementalSpec inc{to_insert, n_insert, to_delete, n_delete, prev};
-  hny_builder *b = nullptr;
-  int rc = create_impl(opts, items, &inc, &b);
-  if (rc) return rc;
-  return run_build(b, opts, out);
+  return run_build(opts, items, &inc, false, out);
 }
 
 int hny_build_incremental_f32(const hny_build_opts *opts, const hny_items *f32_items, const uint32_t *to_insert,
@@ -2567,10 +2636,7 @@ int hny_build_incremental_f32(const hny_build_opts *opts, const hny_items *f32_i
   if (!out) return fail(HNY_ERR_INVALID_ARG, "null out");
   *out = nullptr;
   IncrementalSpec inc{to_insert, n_insert, to_delete, n_delete, prev};
-  hny_builder *b = nullptr;
-  int rc = create_impl(opts, f32_items, &inc, &b, true);
-  if (rc) return rc;
-  return run_build(b, opts, out);
+  return run_build(opts, f32_items, &inc, true, out);
 }
 
 // ---- resident updates (include/hannoy_amd.h) ----
@@ -2672,11 +2738,7 @@ int hny_builder_finish_delta(hny_builder *b, hny_graph_delta **out) {
   u64 stats[ST_COUNT] = {0};
   HIP_TRY(hipMemcpy(stats, b->d_stats.p, sizeof stats, hipMemcpyDeviceToHost));
   if (int rc = device_error_words(b, stats)) return rc;
-  if (!b->finalized) {
-    HIP_TRY(hnyk_finalize_lists(b->d_l0_ids.p, b->d_fin_cnt0.p, n, M0, st));
-    HIP_TRY(hnyk_finalize_lists(b->d_up_ids.p, b->d_fin_cntu.p, (u32)nup, M, st));
-    b->finalized = true;
-  }
+  if (int rc = ensure_finalized(b, st)) return rc;
   DevBuf<unsigned char> d_flag;
   HIP_TRY(d_flag.alloc((size_t)n + nup + 1));
   HIP_TRY(hipMemsetAsync(d_flag.p, 0, (size_t)n + nup + 1, st));
@@ -2774,21 +2836,7 @@ int hny_builder_update(hny_builder **b, const hny_update *u, hny_graph **full, h
   hny_builder *succ = nullptr;
   int rc = hny_builder_create_update(*b, u, &succ);
   if (rc) return rc;
-  const hny_build_opts &o = succ->o;
-  for (;;) {
-    if (o.cancel && o.cancel(o.cancel_ctx)) {
-      rc = fail(HNY_ERR_CANCELLED, "build cancelled");
-      break;
-    }
-    hny_batch bt;
-    rc = hny_builder_next_batch(succ, &bt);
-    if (rc || bt.count == 0) break;
-    rc = hny_builder_search(succ, 0, bt.count, nullptr);
-    if (rc) break;
-    rc = hny_builder_apply(succ, nullptr);
-    if (rc) break;
-    if (o.progress) o.progress(o.progress_ctx, succ->pos, succ->order.size());
-  }
+  rc = run_batches(succ, &succ->o);
   if (!rc) rc = run_fill_gaps(succ);
   if (!rc && full) rc = hny_builder_finish(succ, full);
   if (!rc && delta) rc = hny_builder_finish_delta(succ, delta);
@@ -2911,15 +2959,10 @@ static int stage_queries(hny_builder *b, bool q_f32, const void *qvectors, size_
   if (q_f32) {
     if (!b->qpipe) b->qpipe.reset(new (std::nothrow) IngestPipe());
     if (!b->qpipe) return fail(HNY_ERR_OOM, "out of memory");
-    IngestJob j;
-    j.metric = b->o.metric;
-    j.dim = b->o.dim;
+    IngestJob j = ingest_job(b->o.metric, b->o.dim, dq, b->g.row_stride, dqn);
     j.src = (const unsigned char *)qvectors + q0 * qstride;
     j.stride = qstride;
     j.n = cnt;
-    j.rows = dq;
-    j.row_stride = b->g.row_stride;
-    j.norms = has_norm ? dqn : nullptr;
     return run_ingest(*b->qpipe, j, b->stream);
   }
   int rc = upload_rows((const unsigned char *)qvectors + q0 * qstride, qstride, vb, cnt, b->g.row_stride, dq, b->stream);
@@ -2955,6 +2998,19 @@ static GraphDev search_graph(const hny_builder *b) {
   return g;
 }
 
+// how both searchers end: what the kernels of this call reported through the error words
+static int search_error_tail(hny_builder *b) {
+  u64 stats[ST_COUNT] = {0};
+  HIP_TRY(hipMemcpy(stats, b->d_stats.p, sizeof stats, hipMemcpyDeviceToHost));
+  if (stats[ST_ERR_RES_OVERFLOW] || stats[ST_ERR_ITER]) {
+    (void)clear_error_counters(b); // not sticky: the next search on this builder starts clean
+    return fail(HNY_ERR_DEVICE, "kernel overflow: res=%llu iter=%llu", stats[ST_ERR_RES_OVERFLOW],
+                stats[ST_ERR_ITER]);
+  }
+  if (stats[ST_POOL_OVERFLOW]) return pool_overflow_error(b, stats[ST_POOL_OVERFLOW]);
+  return HNY_OK;
+}
+
 static int search_knn_impl(hny_builder *b, uint64_t nq, const void *qvectors, size_t qstride,
                            const void *qheaders, uint32_t k, uint32_t ef_search, uint32_t *out_ids,
                            float *out_dists, uint32_t *out_counts, const hny_query_opts *qo, bool q_f32) {
@@ -2978,12 +3034,7 @@ static int search_knn_impl(hny_builder *b, uint64_t nq, const void *qvectors, si
     for (uint64_t i = 0; i < nq; i++) out_counts[i] = 0; // reader.rs:652-654
     return HNY_OK;
   }
-  if (!b->finalized) { // Reader::visit iterates Links bitmaps: ascending, deduplicated
-    HIP_TRY(hnyk_finalize_lists(b->d_l0_ids.p, b->d_fin_cnt0.p, b->n, b->o.M0, b->stream));
-    HIP_TRY(hnyk_finalize_lists(b->d_up_ids.p, b->d_fin_cntu.p,
-                                (u32)((size_t)b->n_upper * b->up_layers), b->o.M, b->stream));
-    b->finalized = true;
-  }
+  if (int rc = ensure_finalized(b, b->stream)) return rc; // Reader::visit iterates Links bitmaps: ascending, deduplicated
   const GraphDev sg = search_graph(b);
   const uint32_t rcap = res_capacity(ef, (uint32_t)b->entry_points.size(), b->n, b->top_layer_nodes, HNY_RES_GLOBAL_MAX);
   const size_t vb = vec_bytes(b->o.metric, b->o.dim), hb = hdr_bytes(b->o.metric);
@@ -3128,15 +3179,7 @@ static int search_knn_impl(hny_builder *b, uint64_t nq, const void *qvectors, si
     }
   }
   if (sc.cancelled && qo && qo->did_cancel) *qo->did_cancel = 1;
-  u64 stats[ST_COUNT] = {0};
-  HIP_TRY(hipMemcpy(stats, b->d_stats.p, sizeof stats, hipMemcpyDeviceToHost));
-  if (stats[ST_ERR_RES_OVERFLOW] || stats[ST_ERR_ITER]) {
-    (void)clear_error_counters(b); // not sticky: the next search on this builder starts clean
-    return fail(HNY_ERR_DEVICE, "kernel overflow: res=%llu iter=%llu", stats[ST_ERR_RES_OVERFLOW],
-                stats[ST_ERR_ITER]);
-  }
-  if (stats[ST_POOL_OVERFLOW]) return pool_overflow_error(b, stats[ST_POOL_OVERFLOW]);
-  return HNY_OK;
+  return search_error_tail(b);
 }
 
 // QueryBuilder with .candidates() and/or by_item (reader.rs:60-262, 621-711, 809-896)
@@ -3215,12 +3258,7 @@ static int nns_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const
     const uint64_t cl = cand_slots.size();
     linear = cl < (uint64_t)qo->linear_below && (float)cl / (float)n_items <= qo->linear_below_ratio;
   }
-  if (!b->finalized) { // Reader::visit iterates Links bitmaps: ascending, deduplicated
-    HIP_TRY(hnyk_finalize_lists(b->d_l0_ids.p, b->d_fin_cnt0.p, b->n, b->o.M0, b->stream));
-    HIP_TRY(hnyk_finalize_lists(b->d_up_ids.p, b->d_fin_cntu.p, (u32)((size_t)b->n_upper * b->up_layers),
-                                b->o.M, b->stream));
-    b->finalized = true;
-  }
+  if (int rc = ensure_finalized(b, b->stream)) return rc; // Reader::visit iterates Links bitmaps: ascending, deduplicated
   const GraphDev sg = search_graph(b);
   uint32_t rcap = res_capacity(ef, (uint32_t)b->entry_points.size(), b->n, b->top_layer_nodes,
                                big ? HNY_RES_GLOBAL_MAX : HNY_RES_LDS_MAX);
@@ -3390,15 +3428,7 @@ static int nns_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const
     }
   }
   if (sc.cancelled && qo->did_cancel) *qo->did_cancel = 1;
-  u64 stats[ST_COUNT] = {0};
-  HIP_TRY(hipMemcpy(stats, b->d_stats.p, sizeof stats, hipMemcpyDeviceToHost));
-  if (stats[ST_ERR_RES_OVERFLOW] || stats[ST_ERR_ITER]) {
-    (void)clear_error_counters(b); // not sticky: the next search on this builder starts clean
-    return fail(HNY_ERR_DEVICE, "kernel overflow: res=%llu iter=%llu", stats[ST_ERR_RES_OVERFLOW],
-                stats[ST_ERR_ITER]);
-  }
-  if (stats[ST_POOL_OVERFLOW]) return pool_overflow_error(b, stats[ST_POOL_OVERFLOW]);
-  return HNY_OK;
+  return search_error_tail(b);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -296,3 +296,43 @@ def test_refusals_leak_nothing(hny):
             _same(ga2, s.finish())
         # after all the refusals the good call works on the same builder
         _same(ga2, b.update(to_insert, codes=c, headers=h, delete_ids=to_delete, levels=lv))
+
+
+@pytest.mark.parametrize("metric,dim", [(0, 24), (1, 24), (3, 256)])
+def test_four_row_sources_give_one_graph(hny, metric, dim):
+    """One update (25 overwrites + 25 new items upserted, 30 deletes, an entry point among them) of a 600-item index
+    built in several batches, with the rows arriving in each of the four ways creation knows: build_incremental on
+    the exported graph from codec bytes and from f32 rows, Builder.update with byte and with f32 upserts.  The four
+    graphs are equal array for array, and export_items() of both successors equals the host encoding."""
+    n, M, M0 = 600, 8, 16
+    w = World(hny, metric, dim, M, n0=n, seed=100 + metric)
+    kw = dict(M=M, M0=M0, ef_construction=32, batch_frac=0.1, batch_max=48)
+    items = w.items(draw_levels(n, M, seed=5))
+    g0 = hny.build(items, **kw)
+    assert g0.n_batches > 3
+    rng = w.rng
+    ep = int(g0.entry_points[0])
+    others = np.setdiff1d(np.arange(n), [ep])
+    to_delete = np.sort(np.append(rng.choice(others, 29, replace=False), ep)).astype(np.uint32)
+    overwrite = rng.choice(np.setdiff1d(np.arange(n), to_delete), 25, replace=False)
+    to_insert = np.sort(np.append(overwrite, np.arange(n, n + 25))).astype(np.uint32)
+    for i in to_delete:
+        del w.vecs[int(i)]
+    for i in to_insert:
+        w.vecs[int(i)] = rng.uniform(-1, 1, dim).astype(np.float32)
+    lv = draw_levels(len(to_insert), M, seed=6)
+    want = w.items(lv)
+    graphs = [hny.build_incremental(want, g0, to_insert, to_delete, **kw),
+              hny.build_incremental(w.items(lv, f32=True), g0, to_insert, to_delete, **kw)]
+    assert graphs[0].n_batches > 3
+    c, h = hny.encode_vectors(metric, w.mat(to_insert))
+    for ups in (dict(codes=c, headers=h), dict(vectors=w.mat(to_insert))):
+        with hny.Builder(items, **kw) as b:
+            b.run()
+            _same(g0, b.finish())
+            graphs.append(b.update(to_insert, delete_ids=to_delete, levels=lv, **ups))
+            codes, hdrs = b.export_items()
+            assert np.array_equal(b.items.ids, want.ids)
+            assert np.array_equal(codes, want.codes) and np.array_equal(hdrs, want.headers)
+    for g in graphs[1:]:
+        _same(graphs[0], g)
