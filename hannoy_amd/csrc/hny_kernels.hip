@@ -293,11 +293,16 @@ __device__ __forceinline__ float finalize_f32(const GraphDev &g, float acc, floa
       float c = acc / pnqn;
       if (c < -1.0f) c = -1.0f;
       if (c > 1.0f) c = 1.0f;
-      return (1.0f - c) / 2.0f;
+      acc = (1.0f - c) / 2.0f;
+    } else {
+      return 0.0f;
     }
-    return 0.0f;
-  }
-  return acc; // squared L2 (euclidean.rs:42-44) / L1
+  } // else: squared L2 (euclidean.rs:42-44) / L1
+  // Every NaN distance leaves as 0x7FC00000: OrderedFloat orders by bit pattern (ordered_float.rs:25-29), and
+  // q - r does not preserve a NaN's sign (the subtraction negates its second source), so without this one row
+  // with a NaN component would carry two keys.  Generated NaNs (inf - inf, inf / inf) are 0x7FC00000 on gfx950
+  // already.  Once per distance, nothing per element.
+  return acc != acc ? __uint_as_float(0x7FC00000u) : acc;
 }
 
 __device__ __forceinline__ float finalize_bin(const GraphDev &g, u32 pop, float qn, float rn) {

@@ -90,7 +90,9 @@ typedef struct {
   /* 1 = strict mode: f32 distances in the reference's own x86 summation order (AVX2+FMA for
    * dim >= 32, SSE for 16..31, scalar below; src/spaces/simple*.rs), bit for bit.  Slower; with
    * batch_max = 1 the build then equals the reference run with one thread.  0 = wave order
-   * (within 1e-5 relative of it). */
+   * (within 1e-5 relative of it).  Bit for bit means every distance that is not a NaN
+   * (±inf, 0.0 and denormals included); a NaN distance carries the device's pattern, so an index
+   * that holds propagated and generated NaNs together may order them differently from an x86 host. */
   int32_t x86_order;
   /* replaces: the rayon pool of the insert loop (hnsw.rs:172-185).  n_gpus > 1, or n_gpus == 1 with
    * `devices` given: hny_build / hny_build_incremental run one replica per listed GPU of this node
