@@ -37,6 +37,7 @@ EXPORTED = [
     "hny_build_f32", "hny_build_incremental_f32", "hny_builder_create_f32", "hny_builder_load_f32",
     "hny_builder_export_items", "hny_builder_search_knn_f32", "hny_builder_nns_f32",
     "hny_builder_create_update", "hny_builder_update", "hny_builder_finish_delta", "hny_graph_delta_free",
+    "hny_builder_exact_knn", "hny_builder_exact_knn_f32",
 ]
 ERR_IO = -9
 NNS_NONE = 0xFFFFFFFF  # by_item: the reference returns None
@@ -268,6 +269,10 @@ def load_library():
     L.hny_builder_search_knn_f32.argtypes = [vp, C.c_uint64, vp, C.c_size_t, C.c_uint32, C.c_uint32, vp, vp, vp]
     L.hny_builder_nns_f32.restype = C.c_int
     L.hny_builder_nns_f32.argtypes = [vp, C.POINTER(QueryOpts), C.c_uint64, vp, C.c_size_t, vp, vp, vp]
+    L.hny_builder_exact_knn.restype = C.c_int
+    L.hny_builder_exact_knn.argtypes = [vp, C.POINTER(QueryOpts), C.c_uint64, vp, C.c_size_t, vp, vp, vp, vp, vp]
+    L.hny_builder_exact_knn_f32.restype = C.c_int
+    L.hny_builder_exact_knn_f32.argtypes = [vp, C.POINTER(QueryOpts), C.c_uint64, vp, C.c_size_t, vp, vp, vp]
     L.hny_builder_create_update.restype = C.c_int
     L.hny_builder_create_update.argtypes = [vp, C.POINTER(Update), C.POINTER(vp)]
     L.hny_builder_update.restype = C.c_int
@@ -1104,5 +1109,46 @@ class Builder:
         else:
             _check(load_library().hny_builder_nns(self._h, C.byref(qo), nq, qc, qs, qh, qi, _p(ids), _p(dists),
                                                   _p(counts)))
+        self.did_cancel = bool(flag.value)
+        return ids, dists, counts
+
+    def exact_knn_f32(self, queries, **kw):
+        """exact_knn(by_vector) with f32 queries, encoded on the device"""
+        return self.exact_knn(qf32=_f32_rows(queries), **kw)
+
+    def exact_knn(self, qcodes=None, qheaders=None, k=10, candidates=None, query_items=None, cancel=None, qf32=None):
+        """hny_builder_exact_knn: the k nearest of the live items (or of `candidates` among them) by a flat scan —
+        brute_force_search's result, the ground truth of the index's own distances.  Returns (ids, dists, counts)
+        like nns; counts == NNS_NONE where by_item names an unknown item."""
+        qo = QueryOpts()
+        qo.k = k
+        flag = C.c_int32(0)
+        if cancel is not None:
+            fn = CANCEL_FN(lambda _ctx: 1 if cancel() else 0)
+            qo.cancel = fn
+            qo.did_cancel = C.pointer(flag)
+        self._cancel_flag = flag
+        cand = None
+        if candidates is not None:
+            cand = np.ascontiguousarray(candidates, np.uint32)
+            qo.has_candidates, qo.candidates, qo.n_candidates = 1, cand.ctypes.data, len(cand)
+        L = load_library()
+        if query_items is not None:
+            query_items = np.ascontiguousarray(query_items, np.uint32)
+            nq, qc, qs, qh, qi = len(query_items), None, 0, None, _p(query_items)
+        elif qf32 is not None:
+            nq, qc, qh, qi = qf32.shape[0], _p(qf32), None, None
+            qs = qf32.strides[0] if nq > 1 else qf32.shape[1] * 4
+        else:
+            qcodes = np.ascontiguousarray(qcodes, np.uint8)
+            qheaders = np.ascontiguousarray(qheaders, np.uint8)
+            nq, qc, qs, qh, qi = qcodes.shape[0], _p(qcodes), qcodes.shape[1], _p(qheaders), None
+        ids = np.zeros((nq, k), np.uint32)
+        dists = np.zeros((nq, k), np.float32)
+        counts = np.zeros(nq, np.uint32)
+        if qf32 is not None:
+            _check(L.hny_builder_exact_knn_f32(self._h, C.byref(qo), nq, qc, qs, _p(ids), _p(dists), _p(counts)))
+        else:
+            _check(L.hny_builder_exact_knn(self._h, C.byref(qo), nq, qc, qs, qh, qi, _p(ids), _p(dists), _p(counts)))
         self.did_cancel = bool(flag.value)
         return ids, dists, counts

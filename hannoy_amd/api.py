@@ -490,6 +490,7 @@ class QueryBuilder:
         self.reader, self.count = reader, int(count)
         self._ef, self._candidates = 100, None          # reader.rs:23, 614
         self._linear_below, self._ratio = 1000, 1.0     # reader.rs:28, 31
+        self._exact = False
 
     def ef_search(self, ef):
         self._ef = int(ef)
@@ -508,6 +509,12 @@ class QueryBuilder:
         self._ratio = float(ratio)
         return self
 
+    def exact(self):
+        """the flat scan instead of the graph (hny_builder_exact_knn): brute_force_search over the live items, or
+        over `.candidates()` among them; ef_search and linear_below* are not read"""
+        self._exact = True
+        return self
+
     def _kw(self):
         return dict(k=self.count, ef_search=self._ef, candidates=self._candidates,
                     linear_below=self._linear_below, linear_below_ratio=self._ratio)
@@ -518,10 +525,15 @@ class QueryBuilder:
         q = np.ascontiguousarray(vectors, np.float32)
         if q.ndim != 2 or q.shape[1] != r.dimensions:
             raise InvalidVecDimension(f"expected {r.dimensions}, received {q.shape[-1]}")
+        if self._exact:
+            return r._b.exact_knn_f32(q, k=self.count, candidates=self._candidates, cancel=cancel)
         return r._b.nns_f32(q, cancel=cancel, **self._kw())  # encoded on the device
 
     def by_items(self, items, cancel=None):
         """batched by_item; counts == capi.NNS_NONE where the reference returns None"""
+        if self._exact:
+            return self.reader._b.exact_knn(query_items=np.ascontiguousarray(items, np.uint32), k=self.count,
+                                            candidates=self._candidates, cancel=cancel)
         return self.reader._b.nns(query_items=np.ascontiguousarray(items, np.uint32), cancel=cancel, **self._kw())
 
     def by_vector(self, vector):
@@ -633,6 +645,22 @@ class Reader:
 
     def by_vecs(self, queries, n=10, ef_search=200):
         return self._b.search_knn_f32(np.asarray(queries, np.float32), k=n, ef_search=ef_search)
+
+    def recall(self, queries, n=10, ef_search=100):
+        """mean tie-aware recall@n of by_vecs against nns(n).exact(): a hit counts if its distance bits are <= those of
+        the exact n-th hit (distances are >= 0, so their bits order like their values)"""
+        q = np.asarray(queries, np.float32)
+        _, d, c = self.by_vecs(q, n=n, ef_search=ef_search)
+        _, ed, ec = self.nns(n).exact().by_vectors(q)
+        hits = total = 0
+        for r in range(len(q)):
+            m = int(ec[r])
+            if m == 0:
+                continue
+            nth = ed[r, m - 1:m].view(np.uint32)[0]
+            hits += min(m, int((d[r, :int(c[r])].view(np.uint32) <= nth).sum()))
+            total += m
+        return hits / total if total else 1.0
 
     def close(self):
         self._b.close()

@@ -3432,6 +3432,198 @@ static int nns_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const
 }
 
 // ---------------------------------------------------------------------------------------------
+// exact k-NN: Reader::brute_force_search (reader.rs:667-711) over the live items (∩ candidates) for a batch of
+// queries.  Dense path: per block of queries and slab of HNY_EXACT_SLAB slots, k_exact_scores
+// (every row read once per tile of queries) then k_exact_topk (the slab merged into the running lists).
+// Strict mode and sparse filters go to nns_impl's linear scan over the same set: same definition.
+// ---------------------------------------------------------------------------------------------
+static int exact_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const void *qvectors, size_t qstride,
+                      const void *qheaders, const uint32_t *query_items, uint32_t *out_ids, float *out_dists,
+                      uint32_t *out_counts, bool q_f32) {
+  if (!b || !qo || !out_ids || !out_dists || !out_counts || qo->k == 0)
+    return fail(HNY_ERR_INVALID_ARG, "bad argument");
+  const bool by_item = query_items != nullptr;
+  if (!by_item && (!qvectors || (!q_f32 && !qheaders))) return fail(HNY_ERR_INVALID_ARG, "no queries");
+  if (qo->has_candidates && qo->n_candidates && !qo->candidates)
+    return fail(HNY_ERR_INVALID_ARG, "candidates missing");
+  if (q_f32) {
+    int rcf = check_f32_rows(b->o.dim, nq, qvectors, qstride);
+    if (rcf) return rcf;
+  }
+  if (b->pos < b->order.size()) return fail(HNY_ERR_INVALID_ARG, "build not finished");
+  const uint32_t n = b->n, k = qo->k, NONE = HNY_NNS_NONE;
+  auto exists = [&](uint32_t s) { return !b->incremental || !b->deleted[s]; };
+  auto slot_of = [&](uint32_t id) -> int64_t {
+    auto it = std::lower_bound(b->ids.begin(), b->ids.end(), id);
+    if (it == b->ids.end() || *it != id) return -1;
+    uint32_t s = (uint32_t)(it - b->ids.begin());
+    return exists(s) ? (int64_t)s : -1;
+  };
+  // C = live items (∩ candidates) as a mask over slots, the one nns_impl builds for its filter
+  std::vector<u32> mask(((size_t)n + 31) / 32 + 1, 0u);
+  uint64_t n_c = 0;
+  if (qo->has_candidates) {
+    for (uint64_t i = 0; i < qo->n_candidates; i++) {
+      int64_t sl = slot_of(qo->candidates[i]);
+      if (sl >= 0 && !((mask[(size_t)sl >> 5] >> (sl & 31)) & 1u)) {
+        mask[(size_t)sl >> 5] |= 1u << (sl & 31);
+        n_c++;
+      }
+    }
+  } else {
+    for (uint32_t s = 0; s < n; s++)
+      if (exists(s)) {
+        mask[s >> 5] |= 1u << (s & 31);
+        n_c++;
+      }
+  }
+  if (qo->did_cancel) *qo->did_cancel = 0;
+  if (n_c == 0) { // reader.rs:652-654 / 822-824
+    for (uint64_t i = 0; i < nq; i++) out_counts[i] = by_item ? NONE : 0u;
+    return HNY_OK;
+  }
+  const uint32_t kk = (uint32_t)std::min<uint64_t>(k, n_c); // hits per query
+  if ((uint64_t)kk + 1 > HNY_RES_LDS_MAX)
+    return fail(HNY_ERR_UNSUPPORTED, "exact scan for %u hits among %llu items: at most %u hits", k,
+                (unsigned long long)n_c, HNY_RES_LDS_MAX - 1);
+  const size_t vb = vec_bytes(b->o.metric, b->o.dim);
+  if (!by_item && !q_f32 && qstride < vb) return fail(HNY_ERR_INVALID_DIM, "query stride too small");
+  HIP_TRY(hipSetDevice(b->device));
+  const uint32_t qt = hnyk_exact_qt(b->g.row_stride);
+  const bool strict = b->g.x86_order && b->g.mclass != MC_BIN;
+  if (strict || n_c * qt < n) {
+    // a gather of C reads |C| rows per query, the dense scan n / qt: the one-wave scan over cand_slots = C
+    std::vector<uint32_t> c_ids;
+    c_ids.reserve(n_c);
+    for (uint32_t s = 0; s < n; s++)
+      if ((mask[s >> 5] >> (s & 31)) & 1u) c_ids.push_back(b->ids[s]);
+    hny_query_opts o2 = *qo;
+    o2.k = kk;
+    o2.ef_search = 0;
+    o2.has_candidates = 1;
+    o2.candidates = c_ids.data();
+    o2.n_candidates = c_ids.size();
+    o2.linear_below = 0xFFFFFFFFu;
+    o2.linear_below_ratio = 1.0f;
+    if (kk == k)
+      return nns_impl(b, &o2, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists, out_counts, false,
+                      q_f32);
+    std::vector<uint32_t> ti((size_t)nq * kk);
+    std::vector<float> td((size_t)nq * kk);
+    int rc = nns_impl(b, &o2, nq, qvectors, qstride, qheaders, query_items, ti.data(), td.data(), out_counts, false,
+                      q_f32);
+    if (rc) return rc;
+    for (uint64_t i = 0; i < nq; i++) {
+      if (out_counts[i] == NONE) continue;
+      memcpy(&out_ids[i * k], &ti[i * kk], (size_t)out_counts[i] * 4);
+      memcpy(&out_dists[i * k], &td[i * kk], (size_t)out_counts[i] * 4);
+    }
+    return HNY_OK;
+  }
+  uint32_t rcap = 64;
+  while (rcap < kk + 1) rcap *= 2;
+  // running lists within the 2 GB rule of nns_impl
+  const uint32_t qblock = (uint32_t)std::max<uint64_t>(
+      1, std::min<uint64_t>(std::min<uint64_t>(HNY_EXACT_QBLOCK, std::max<uint64_t>(nq, 1)), ((uint64_t)2 << 30) / ((uint64_t)rcap * 8)));
+  const uint32_t sstride = (std::min<uint32_t>(n, HNY_EXACT_SLAB) + 63u) & ~63u;
+  const bool has_norm = b->g.norms != nullptr;
+  DevBuf<unsigned char> dq;
+  DevBuf<float> dqn, dscores;
+  DevBuf<u64> dlists, dtop;
+  DevBuf<u32> dln, dqslots, dmask;
+  if (!by_item) {
+    HIP_TRY(dq.alloc((size_t)qblock * b->g.row_stride));
+    HIP_TRY(dqn.alloc(qblock));
+  } else {
+    HIP_TRY(dqslots.alloc(qblock));
+  }
+  HIP_TRY(dscores.alloc((size_t)qblock * sstride));
+  HIP_TRY(dlists.alloc((size_t)qblock * rcap));
+  HIP_TRY(dtop.alloc((size_t)qblock * kk));
+  HIP_TRY(dln.alloc(qblock));
+  HIP_TRY(dmask.alloc(mask.size()));
+  HIP_TRY(hipMemcpyAsync(dmask.p, mask.data(), mask.size() * 4, hipMemcpyHostToDevice, b->stream));
+  std::vector<float> qn(qblock);
+  std::vector<u32> qs(qblock), members(qblock), hn(qblock);
+  std::vector<u64> hc((size_t)qblock * kk);
+  SearchCancel sc;
+  HIP_TRY(sc.init(qo));
+  for (uint64_t q0 = 0; q0 < nq; q0 += qblock) {
+    const uint32_t cnt = (uint32_t)std::min<uint64_t>(qblock, nq - q0);
+    // the block's queries that have a row: by_item drops unknown and deleted items (Ok(None), reader.rs:826)
+    uint32_t n_mem = 0;
+    for (uint32_t i = 0; i < cnt; i++) {
+      if (by_item) {
+        int64_t sl = slot_of(query_items[q0 + i]);
+        out_counts[q0 + i] = sl >= 0 ? 0u : NONE;
+        if (sl < 0) continue;
+        qs[n_mem] = (uint32_t)sl;
+      } else {
+        out_counts[q0 + i] = 0u;
+      }
+      members[n_mem++] = i;
+    }
+    if (n_mem == 0 || sc.probe()) continue; // cancelled: nothing of this block is started, 0 hits each
+    if (by_item) {
+      HIP_TRY(hipMemcpyAsync(dqslots.p, qs.data(), (size_t)n_mem * 4, hipMemcpyHostToDevice, b->stream));
+    } else {
+      int rc = stage_queries(b, q_f32, qvectors, qstride, qheaders, q0, cnt, dq.p, dqn.p, qn);
+      if (rc) return rc;
+    }
+    ExactArgs a{};
+    a.q_slots = by_item ? dqslots.p : nullptr;
+    a.q_rows = dq.p;
+    a.q_norms = has_norm && !by_item ? dqn.p : nullptr;
+    a.q_stride = b->g.row_stride;
+    a.nq = n_mem;
+    a.qt = qt;
+    a.scores = dscores.p;
+    a.score_stride = sstride;
+    a.mask = dmask.p;
+    a.lists = dlists.p;
+    a.list_n = dln.p;
+    a.k = kk;
+    a.rcap = rcap;
+    HIP_TRY(hipMemsetAsync(dln.p, 0, (size_t)n_mem * 4, b->stream));
+    bool stopped = false;
+    for (uint32_t s0 = 0; s0 < n && !stopped; s0 += HNY_EXACT_SLAB) {
+      a.slab_base = s0;
+      a.slab_n = std::min<uint32_t>(HNY_EXACT_SLAB, n - s0);
+      if ((stopped = sc.probe())) break;
+      HIP_TRY(hnyk_exact_scores(b->g, a, b->shape, b->stream));
+      if ((stopped = sc.probe())) break;
+      HIP_TRY(hnyk_exact_topk(b->g, a, b->stream));
+    }
+    if (stopped) { // the block did not finish: 0 hits each
+      HIP_TRY(hipStreamSynchronize(b->stream));
+      continue;
+    }
+    HIP_TRY(hnyk_take_topk(dlists.p, dln.p, rcap, kk, n_mem, dtop.p, b->stream));
+    HIP_TRY(hipMemcpyAsync(hc.data(), dtop.p, (size_t)n_mem * kk * 8, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemcpyAsync(hn.data(), dln.p, (size_t)n_mem * 4, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(sc.wait(b));
+    for (uint32_t j = 0; j < n_mem; j++) {
+      const uint64_t qi = q0 + members[j];
+      out_counts[qi] = copy_topk_row(b, &hc[(size_t)j * kk], hn[j], kk, &out_ids[qi * k], &out_dists[qi * k]);
+    }
+  }
+  if (sc.cancelled && qo->did_cancel) *qo->did_cancel = 1;
+  return search_error_tail(b);
+}
+
+int hny_builder_exact_knn(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const void *qvectors,
+                          size_t qstride, const void *qheaders, const uint32_t *query_items, uint32_t *out_ids,
+                          float *out_dists, uint32_t *out_counts) {
+  return exact_impl(b, qo, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists, out_counts, false);
+}
+
+int hny_builder_exact_knn_f32(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const float *queries,
+                              size_t qstride, uint32_t *out_ids, float *out_dists, uint32_t *out_counts) {
+  if (!queries) return fail(HNY_ERR_INVALID_ARG, "no queries");
+  return exact_impl(b, qo, nq, queries, qstride, nullptr, nullptr, out_ids, out_dists, out_counts, true);
+}
+
+// ---------------------------------------------------------------------------------------------
 // on-disk records
 // ---------------------------------------------------------------------------------------------
 static void put_key(uint16_t index, uint8_t mode, uint32_t item, uint8_t layer, uint8_t k[8]) {

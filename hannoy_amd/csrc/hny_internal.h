@@ -236,6 +236,33 @@ hipError_t hnyk_prune(const GraphDev &g, const PruneArgs &a, LaunchShape s, int 
 // a.heap_r set: `res` as a heap in HBM too (result sets beyond the LDS), else the sorted LDS array
 hipError_t hnyk_nns(const GraphDev &g, const NnsArgs &a, LaunchShape s, int grid, hipStream_t st);
 hipError_t hnyk_nns_linear(const GraphDev &g, const NnsArgs &a, LaunchShape s, int grid, hipStream_t st);
+// exact k-NN (hny_builder_exact_knn): a dense scan of consecutive slots for a tile of queries
+// (k_exact_scores) and the merge of one slab of scores into every query's running top-k list (k_exact_topk)
+#define HNY_EXACT_SLAB 65536u   // slots per slab: the score buffer is query block x slab f32
+#define HNY_EXACT_CHUNK 512u    // consecutive slots per workgroup of k_exact_scores
+#define HNY_EXACT_QBLOCK 1024u  // queries per block: the score buffer is at most 256 MB
+struct ExactArgs {
+  const u32 *q_slots;          // by_item: slot of each query's stored row, else null
+  const unsigned char *q_rows; // by_vector: staged query rows / header norms
+  const float *q_norms;
+  u32 q_stride;
+  u32 nq, qt;                  // queries of the block, queries per tile (hnyk_exact_qt)
+  u32 slab_base, slab_n;       // slots [slab_base, slab_base + slab_n)
+  float *scores;               // [nq][score_stride], column = slot - slab_base
+  u32 score_stride;
+  const u32 *mask;             // live items (∩ candidates) as a bitset over slots
+  u64 *lists;                  // [nq][rcap] dist bits << 32 | slot, ascending
+  u32 *list_n;                 // [nq], zero before the first slab
+  u32 k, rcap;
+};
+// queries per tile: the largest power of two with qt * row_stride <= 64 KB, within 4 .. 32
+static inline u32 hnyk_exact_qt(u32 row_stride) {
+  u32 qt = 32;
+  while (qt > 4 && (size_t)qt * row_stride > 65536u) qt /= 2;
+  return qt;
+}
+hipError_t hnyk_exact_scores(const GraphDev &g, const ExactArgs &a, LaunchShape s, hipStream_t st);
+hipError_t hnyk_exact_topk(const GraphDev &g, const ExactArgs &a, hipStream_t st);
 hipError_t hnyk_emit(const GraphDev &g, const EmitArgs &a, hipStream_t st);
 hipError_t hnyk_segments(const u64 *keys, u32 n_ops, u32 *seg_start, u32 *n_seg, hipStream_t st);
 hipError_t hnyk_apply(const GraphDev &g, const ApplyArgs &a, LaunchShape s, int grid, hipStream_t st);

@@ -2810,6 +2810,161 @@ __global__ __launch_bounds__(64, 4) void k_nns_linear(GraphDev g, NnsArgs a) {
   }
 }
 
+// Exact k-NN, dense scan (hny_builder_exact_knn).  k_nns_linear above fetches every candidate row
+// once per query; here a workgroup of four waves stages a tile of a.qt query rows in LDS and every wave reads its
+// share of a chunk of consecutive slots from HBM once for the whole tile.  Per (query, row) pair the work is
+// dist_rows': the same lane slices (load_row / load_row_lds), the same per-lane chain (partial_*), the same
+// folded butterflies and finaliser, hence the same distance bits.  Deleted slots and slots outside the filter are
+// scored too (their rows are resident); k_exact_topk masks them.
+template <int LPR, int NCH>
+__global__ __launch_bounds__(256) void k_exact_scores(GraphDev g, ExactArgs a) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  float *qnorm = reinterpret_cast<float *>(smem + (size_t)a.qt * g.row_stride);
+  const u32 q0 = blockIdx.x * a.qt;
+  const int nqt = (int)(a.nq - q0 < a.qt ? a.nq - q0 : a.qt);
+  const u32 slab_end = a.slab_base + a.slab_n;
+  const u32 c0 = a.slab_base + blockIdx.y * HNY_EXACT_CHUNK;
+  const u32 c1 = slab_end - c0 < HNY_EXACT_CHUNK ? slab_end : c0 + HNY_EXACT_CHUNK;
+  for (u32 i = threadIdx.x; i < (u32)nqt * g.n16; i += 256u) {
+    const u32 qi = i / g.n16, f = i - qi * g.n16;
+    const unsigned char *src = a.q_slots ? g.rows + (size_t)a.q_slots[q0 + qi] * g.row_stride
+                                         : a.q_rows + (size_t)(q0 + qi) * a.q_stride;
+    *reinterpret_cast<float4 *>(smem + (size_t)qi * g.row_stride + (size_t)f * 16) =
+        *reinterpret_cast<const float4 *>(src + (size_t)f * 16);
+  }
+  if ((int)threadIdx.x < nqt) {
+    float qn = 0.f;
+    if (a.q_slots) {
+      if (g.norms) qn = g.norms[a.q_slots[q0 + threadIdx.x]];
+    } else if (a.q_norms) {
+      qn = a.q_norms[q0 + threadIdx.x];
+    }
+    qnorm[threadIdx.x] = qn;
+  }
+  __syncthreads();
+  constexpr int RPG = 64 / LPR;             // rows per wave-wide load instruction
+  constexpr int U = RowsInFlight<NCH>::U;   // load groups in flight
+  constexpr int RPI = RPG * U;              // rows per wave and pass
+  constexpr int F = (U % 4 == 0) ? 4 : (U % 2 == 0 ? 2 : 1);
+  const int ln = HNY_LANE, t = ln % LPR, sub = ln / LPR, wave = (int)(threadIdx.x >> 6);
+  const bool writer = (t & (F == 1 ? LPR - 1 : LPR / F - 1)) == 0;
+  for (u32 r0 = c0 + (u32)(wave * RPI); r0 < c1; r0 += 4u * RPI) {
+    float4 r[U][NCH];
+    float rn[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      rn[u] = 0.f;
+      if (r0 + (u32)(u * RPG) < c1) { // wave-uniform
+        u32 rid = r0 + (u32)(u * RPG + sub);
+        if (rid > c1 - 1u) rid = c1 - 1u;
+        load_row<LPR, NCH>(g.rows + (size_t)rid * g.row_stride, t, g.n16, r[u]);
+        if (g.norms) rn[u] = g.norms[rid];
+      } else {
+#pragma unroll
+        for (int c = 0; c < NCH; c++) r[u][c] = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    }
+    for (int qi = 0; qi < nqt; qi++) {
+      float4 q[NCH];
+      load_row_lds<LPR, NCH>(smem + (size_t)qi * g.row_stride, t, g.n16, q);
+      const float qn = qnorm[qi];
+      float *out = a.scores + (size_t)(q0 + (u32)qi) * a.score_stride;
+#pragma unroll
+      for (int u0 = 0; u0 < U; u0 += F) {
+        if (r0 + (u32)(u0 * RPG) < c1) { // wave-uniform
+          int j;
+          float d;
+          if (g.mclass == MC_BIN) {
+            u32 pc;
+            if constexpr (F == 4) {
+              pc = fold4<LPR, u32>(partial_bin<NCH>(q, r[u0]), partial_bin<NCH>(q, r[u0 + 1]),
+                                   partial_bin<NCH>(q, r[u0 + 2]), partial_bin<NCH>(q, r[u0 + 3]));
+              j = fold4_row<LPR>();
+            } else if constexpr (F == 1) {
+              pc = butterfly_u32<LPR>(partial_bin<NCH>(q, r[u0]));
+              j = 0;
+            } else {
+              pc = fold2<LPR, u32>(partial_bin<NCH>(q, r[u0]), partial_bin<NCH>(q, r[u0 + 1]));
+              j = fold2_row<LPR>();
+            }
+            float rnj = rn[u0];
+#pragma unroll
+            for (int jj = 1; jj < F; jj++) rnj = (j == jj) ? rn[u0 + jj] : rnj;
+            d = finalize_bin(g, pc, qn, rnj);
+          } else {
+            float pa;
+            if constexpr (F == 4) {
+              pa = fold4<LPR, float>(partial_f32<NCH>(g.mclass, q, r[u0]), partial_f32<NCH>(g.mclass, q, r[u0 + 1]),
+                                     partial_f32<NCH>(g.mclass, q, r[u0 + 2]), partial_f32<NCH>(g.mclass, q, r[u0 + 3]));
+              j = fold4_row<LPR>();
+            } else if constexpr (F == 1) {
+              pa = butterfly_f32<LPR>(partial_f32<NCH>(g.mclass, q, r[u0]));
+              j = 0;
+            } else {
+              pa = fold2<LPR, float>(partial_f32<NCH>(g.mclass, q, r[u0]), partial_f32<NCH>(g.mclass, q, r[u0 + 1]));
+              j = fold2_row<LPR>();
+            }
+            float rnj = rn[u0];
+#pragma unroll
+            for (int jj = 1; jj < F; jj++) rnj = (j == jj) ? rn[u0 + jj] : rnj;
+            d = finalize_f32(g, pa, qn, rnj);
+          }
+          const u32 rid = r0 + (u32)((u0 + j) * RPG + sub);
+          if (writer && rid < c1) out[rid - a.slab_base] = d;
+        }
+      }
+    }
+  }
+}
+
+#if HNY_PART == 0
+// One wave per query: the slab's scores of the slots in a.mask against the query's running list of the k smallest
+// (dist bits << 32 | slot) keys — k_nns_linear's loop on stored distances.  The list is read from and written back
+// to HBM around the slab; four batches of 64 scores are fetched ahead of their ballots.
+__global__ __launch_bounds__(64) void k_exact_topk(GraphDev g, ExactArgs a) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  u64 *res = reinterpret_cast<u64 *>(smem);
+  const int ln = threadIdx.x;
+  const u32 qi = blockIdx.x;
+  u64 *list = a.lists + (size_t)qi * a.rcap;
+  const float *sc = a.scores + (size_t)qi * a.score_stride;
+  int res_len = (int)uni(a.list_n[qi]);
+  u32 res_err = 0;
+  for (int e = ln; e < res_len; e += 64) res[e] = list[e];
+  WSYNC();
+  for (u32 base = 0; base < a.slab_n; base += 256u) {
+    u64 key[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const u32 s = base + (u32)(j * 64 + ln);
+      key[j] = ~0ull; // no slot is 0xFFFFFFFF: never a real key
+      if (s < a.slab_n) {
+        const u32 slot = a.slab_base + s;
+        if ((a.mask[slot >> 5] >> (slot & 31u)) & 1u) key[j] = ((u64)fbits(sc[s]) << 32) | slot;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const u64 cur_max = (res_len == (int)a.k && res_len) ? uni(res[res_len - 1]) : ~0ull;
+      u64 want = ballot(key[j] != ~0ull && (res_len < (int)a.k || key[j] < cur_max));
+      while (want) {
+        const int r = __ffsll((long long)want) - 1;
+        want &= want - 1ull;
+        const u64 kr = ((u64)(u32)__builtin_amdgcn_readlane((int)(key[j] >> 32), r) << 32) |
+                       (u64)(u32)__builtin_amdgcn_readlane((int)(key[j] & 0xFFFFFFFFull), r);
+        sorted_insert(res, res_len, kr, (int)a.k, (int)a.rcap, res_err);
+      }
+    }
+  }
+  WSYNC();
+  for (int e = ln; e < res_len; e += 64) list[e] = res[e];
+  if (ln == 0) {
+    a.list_n[qi] = (u32)res_len;
+    if (res_err) atomicAdd(&g.stats[ST_ERR_RES_OVERFLOW], 1ull);
+  }
+}
+#endif // HNY_PART == 0
+
 // ---------------------------------------------------------------------------------------------
 // list steps shared by the prune, add_link and fill_gaps kernels, for blocks of NT threads (one wave:
 // 64, a workgroup: 256).  ONE: every range is known to fit one pass (lists of at most 64 slots in a
@@ -4527,6 +4682,20 @@ struct NnsLinearLauncher {
   }
 };
 template <int L, int C>
+struct ExactScoresLauncher {
+  static hipError_t run(const GraphDev &g, const ExactArgs &a, hipStream_t st) {
+    const size_t lds = (size_t)a.qt * g.row_stride + (size_t)a.qt * 4;
+    if (lds > 65536) {
+      hipError_t rc = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_exact_scores<L, C>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (rc != hipSuccess) return rc;
+    }
+    const dim3 grid((a.nq + a.qt - 1) / a.qt, (a.slab_n + HNY_EXACT_CHUNK - 1) / HNY_EXACT_CHUNK);
+    hipLaunchKernelGGL((k_exact_scores<L, C>), grid, dim3(256), lds, st, g, a);
+    return hipGetLastError();
+  }
+};
+template <int L, int C>
 struct PruneLauncher {
   static hipError_t run(const GraphDev &g, const PruneArgs &a, int grid, hipStream_t st) {
     size_t lds = (size_t)a.rcap * 8 + (size_t)wave_capmax(g) * (8 + 4) + 64 * 4;
@@ -4648,6 +4817,15 @@ hipError_t hnyk_nns(const GraphDev &g, const NnsArgs &a, LaunchShape s, int grid
 }
 hipError_t hnyk_nns_linear(const GraphDev &g, const NnsArgs &a, LaunchShape s, int grid, hipStream_t st) {
   return dispatch_shape<NnsLinearLauncher>(s, g, a, grid, st);
+}
+hipError_t hnyk_exact_scores(const GraphDev &g, const ExactArgs &a, LaunchShape s, hipStream_t st) {
+  if (!a.nq || !a.slab_n) return hipSuccess;
+  return dispatch_shape<ExactScoresLauncher>(s, g, a, st);
+}
+hipError_t hnyk_exact_topk(const GraphDev &g, const ExactArgs &a, hipStream_t st) {
+  if (!a.nq || !a.slab_n) return hipSuccess;
+  hipLaunchKernelGGL(k_exact_topk, dim3(a.nq), dim3(64), (size_t)a.rcap * 8, st, g, a);
+  return hipGetLastError();
 }
 hipError_t hnyk_prune(const GraphDev &g, const PruneArgs &a, LaunchShape s, int grid, hipStream_t st) {
   return dispatch_shape<PruneLauncher>(s, g, a, grid, st);

@@ -353,6 +353,35 @@ int hny_builder_search_knn_f32(hny_builder *b, uint64_t n_queries, const float *
 int hny_builder_nns_f32(hny_builder *b, const hny_query_opts *opts, uint64_t n_queries, const float *queries,
                         size_t qstride, uint32_t *out_ids, float *out_dists, uint32_t *out_counts);
 
+/* ---- exact k-NN: a flat scan of the builder's items, the ground truth for recall.
+ *
+ * Definition: for every query the result is what Reader::brute_force_search (src/reader.rs:667-711) returns over
+ * C = the live items, or candidates ∩ live items when opts->has_candidates: the min(k, |C|) smallest
+ * (distance bits, item id) keys, ascending, with the distances of the index's own metric kernels.  It equals, byte
+ * for byte (ids, distance bits, counts), hny_builder_nns with has_candidates = 1, candidates = C,
+ * linear_below = UINT32_MAX and linear_below_ratio = 1.  The graph is not read: any builder whose build has
+ * finished or that was loaded will do, incremental builders with deleted slots included.
+ *
+ * opts: k, has_candidates / candidates / n_candidates and cancel / cancel_ctx / did_cancel are read; ef_search,
+ * linear_below and linear_below_ratio are not.  query_items != NULL = by_item on the stored rows: the item
+ * itself stays in (the reference's linear branch, reader.rs:831-833), an unknown or deleted item gives
+ * out_counts[i] = HNY_NNS_NONE.  No live item or C empty: 0 hits (HNY_NNS_NONE for by_item).
+ *
+ * Decided before any device work: NULL arguments (a NULL builder included) or k == 0: HNY_ERR_INVALID_ARG;
+ * min(k, |C|) > 4 095 hits: HNY_ERR_UNSUPPORTED; qstride below the codec's bytes: HNY_ERR_INVALID_DIM.
+ *
+ * Every row is read once per tile of up to 32 queries, not once per query; queries go in blocks
+ * of at most 1 024 and `cancel` is probed between the launches of a block: blocks that have not finished report
+ * 0 hits and *did_cancel = 1, finished blocks keep their results. */
+int hny_builder_exact_knn(hny_builder *b, const hny_query_opts *opts, uint64_t n_queries,
+                          const void *qvectors, size_t qstride, const void *qheaders,
+                          const uint32_t *query_items, uint32_t *out_ids, float *out_dists,
+                          uint32_t *out_counts);
+/* by_vector with f32 queries, encoded on the device like hny_builder_nns_f32's */
+int hny_builder_exact_knn_f32(hny_builder *b, const hny_query_opts *opts, uint64_t n_queries,
+                              const float *queries, size_t qstride, uint32_t *out_ids,
+                              float *out_dists, uint32_t *out_counts);
+
 /* ---- resident updates: Writer::add_item / del_item followed by Writer::build (src/writer.rs:462-495, 521-603)
  * on an index whose builder is still alive.  A finished builder holds the codec rows, the norms and the finalised
  * lists of every live item in HBM; the successor takes them from there, device to device (k_move_rows /
