@@ -1778,6 +1778,64 @@ static hipError_t next_sync_event(hny_builder *b, hipEvent_t *ev) {
   return hipSuccess;
 }
 
+// ---------------------------------------------------------------------------------------------
+// what the build's walks (hny_builder_search) and the Reader search on k_walk (search_knn_impl) share
+// ---------------------------------------------------------------------------------------------
+// the workspace half of WalkArgs: entry points, visited sets and logs, and the result sets' capacity.
+// res_global: null unless the result sets outgrow the LDS (res_capacity)
+static void walk_workspace(const hny_builder *b, WalkArgs &w, uint32_t rcap, u64 *res_global) {
+  w.entry_points = b->d_eps.p;
+  w.n_entry_points = (u32)b->entry_points.size();
+  w.rcap = rcap;
+  w.bits = b->d_bits.p;
+  w.bits_words = b->bits_words;
+  w.vlog = b->d_vlog.p;
+  w.log_cap = b->log_cap;
+  w.res_global = res_global;
+  w.vis_slots = vis_slots_for(b, res_global ? 0u : rcap);
+  w.eps_cap = eps_cap_of(b);
+  vis_buckets_for(b, w);
+}
+
+// XCD-tiled work queue of the level-0 walks (WalkArgs.xcd_tile): rows of 1 KB and more, where the walk
+// is HBM-bound and neighbouring queries on one L2 save fabric traffic (C2 walk 0.312 -> 0.289 s, C3
+// 0.601 -> 0.573 s; tiles of 256..1024 members alike); neutral within the noise on 136 / 516-byte
+// rows, so off there.  HNY_XCD_TILE overrides (0 = one counter).  0 as well for fewer than 16 tiles of members.
+static u32 xcd_tile_of(const hny_builder *b, uint32_t cnt) {
+  const u32 xcd_tile = (u32)std::max(0, env_int("HNY_XCD_TILE", b->g.row_stride >= 1024u ? 512 : 0));
+  return xcd_tile && cnt >= 16u * xcd_tile ? xcd_tile : 0u;
+}
+
+// tests: HNY_POOL_FORCE_RETRY = every k-th member takes the retry path of an overflowed tie pool;
+// HNY_NO_POOL_RETRY = there is none, an overflow is an error again (returns false)
+static bool pool_retry_env(WalkArgs &w) {
+  w.force_pool = (u32)std::max(0, env_int("HNY_POOL_FORCE_RETRY", 0));
+  return env_int("HNY_NO_POOL_RETRY", 0) == 0;
+}
+
+// Members in LOCALITY ORDER, in two steps around the caller's own launch of the descent: (1) the greedy descent
+// of every member, recording the closest node of the last greedy layers as a coarse-to-fine key; (2) the members
+// sorted by that key.  The walks below then take the members in that order (perm), so that the waves running at
+// the same time work in the same region of the graph and share candidate rows in L2 / Infinity Cache.  Results
+// are stored per member: nothing changes but the memory traffic.
+static WalkArgs region_descent(const hny_builder *b, WalkArgs w) {
+  w.descend_only = 1;
+  w.eps_out = b->d_eps0.p;
+  w.key_out = b->d_lkey_a.p;
+  return w;
+}
+// (2): enqueued behind the descent; `w`, the walk of the layer the descent stopped above, starts from its result
+static int region_order(hny_builder *b, uint32_t lo, uint32_t cnt, WalkArgs &w) {
+  HIP_TRY(hnyk_iota_u64(b->d_perm_a.p, lo, cnt, b->stream));
+  size_t tmp = b->sort_tmp_bytes;
+  HIP_TRY(hnyk_sort_pairs48(b->d_sort_tmp.p, tmp, b->d_lkey_a.p, b->d_lkey_b.p, b->d_perm_a.p, b->d_perm_b.p, cnt,
+                            b->stream));
+  w.first = 0;
+  w.eps_in = b->d_eps0.p;
+  w.perm = b->d_perm_b.p;
+  return HNY_OK;
+}
+
 int hny_builder_search(hny_builder *b, uint32_t lo, uint32_t hi, void *sel_dev) {
   if (!b || !b->in_batch) return fail(HNY_ERR_INVALID_ARG, "no current batch");
   if (lo > hi || hi > b->cur.count) return fail(HNY_ERR_INVALID_ARG, "bad member range");
@@ -1794,24 +1852,14 @@ int hny_builder_search(hny_builder *b, uint32_t lo, uint32_t hi, void *sel_dev) 
     w.ef = b->o.ef_construction;
     w.first = (l == (int32_t)L);
     w.reader_mode = 0;
-    w.entry_points = b->d_eps.p;
-    w.n_entry_points = (u32)b->entry_points.size();
     w.sel = sel;
     w.sel_stride = b->cur.sel_stride_u64;
     w.cap_sel = cs;
     w.batch_level = L;
     w.cand = b->d_cand.p;
     w.cand_n = b->d_cand_n.p;
-    w.rcap = b->rcap;
-    w.bits = b->d_bits.p;
-    w.bits_words = b->bits_words;
-    w.vlog = b->d_vlog.p;
-    w.log_cap = b->log_cap;
-    w.vis_slots = vis_slots_for(b, b->d_res_global.p ? 0u : w.rcap);
-    w.eps_cap = eps_cap_of(b);
     w.queue = queue;
-    w.res_global = b->d_res_global.p; // null unless the result sets outgrow the LDS (res_capacity)
-    vis_buckets_for(b, w);
+    walk_workspace(b, w, b->rcap, b->d_res_global.p);
     {
       // one-chunk register beam (k_walk<.., RC = 1>, rows <= 512 B): no result set of this builder's walks exceeds 64
       // entries — ef, the entry points (all pushed without a capacity check), a top layer that only grows
@@ -1852,11 +1900,6 @@ int hny_builder_search(hny_builder *b, uint32_t lo, uint32_t hi, void *sel_dev) 
       return hnyk_prune(b->g, p, b->shape, (int)std::min<uint32_t>(p.hi - p.lo, b->walk_slots), st);
     return hnyk_prune_wg(b->g, p, b->shape, b->stage_rows, 4, (int)std::min<uint32_t>(p.hi - p.lo, 2048), st);
   };
-  // XCD-tiled work queue of the level-0 walks (WalkArgs.xcd_tile): rows of 1 KB and more, where the walk
-  // is HBM-bound and neighbouring queries on one L2 save fabric traffic (C2 walk 0.312 -> 0.289 s, C3
-  // 0.601 -> 0.573 s; tiles of 256..1024 members alike); neutral within the noise on 136 / 516-byte
-  // rows, so off there.  HNY_XCD_TILE overrides (0 = one counter).
-  const u32 xcd_tile = (u32)std::max(0, env_int("HNY_XCD_TILE", b->g.row_stride >= 1024u ? 512 : 0));
   u32 *queues = b->d_nseg.p + 4; // 16 work counters: the descent + one per layer of the batch
   u32 *xqueues = queues + 16;    // the same 16, as 8 per-XCD counters each (WalkArgs.xcd_tile)
   HIP_TRY(hipMemsetAsync(queues, 0, (16 + 8 * 16) * 4, b->stream));
@@ -1878,10 +1921,9 @@ int hny_builder_search(hny_builder *b, uint32_t lo, uint32_t hi, void *sel_dev) 
     }
     u32 *pc = b->d_pool_ctr.p + b->pool_ctr_used;
     b->pool_ctr_used += 4;
-    const bool no_retry = env_int("HNY_NO_POOL_RETRY", 0) != 0; // tests: an overflow is an error again
+    const bool no_retry = !pool_retry_env(w);
     w.pool_retry = no_retry ? nullptr : b->d_pool_retry.p;
     w.n_pool_retry = pc;
-    w.force_pool = (u32)std::max(0, env_int("HNY_POOL_FORCE_RETRY", 0));
     hipError_t e = launch_walk_fast(w, st);
     if (e != hipSuccess || no_retry) return e;
     WalkArgs h = w;
@@ -1907,32 +1949,18 @@ int hny_builder_search(hny_builder *b, uint32_t lo, uint32_t hi, void *sel_dev) 
 
   const uint32_t cnt = hi - lo;
   if (b->locality && b->max_level > L && cnt >= 2048) {
-    // batch in LOCALITY ORDER: (1) greedy descent for every member, recording the closest node of
-    // the last greedy layers as a coarse-to-fine key; (2) sort the members by that key; (3) the beam
-    // searches and prunes of every layer take the members in that order, so that the waves running
-    // at the same time work in the same region of the graph and share candidate rows in L2 /
-    // Infinity Cache.  Results are stored per member: the build is unchanged, only its memory traffic.
-    WalkArgs d = walk_args(L, lo, hi, queues + 0);
-    d.descend_only = 1;
-    d.eps_out = b->d_eps0.p;
-    d.key_out = b->d_lkey_a.p;
+    // batch in locality order (region_descent): the beam searches and prunes of every layer take the members in it
+    WalkArgs top = walk_args(L, lo, hi, queues + (L + 1));
     prof_begin(b, EV_WALK);
     b->n_walk_dispatch++;
-    HIP_TRY(launch_walk(d, b->stream));
-    HIP_TRY(hnyk_iota_u64(b->d_perm_a.p, lo, cnt, b->stream));
-    size_t tmp = b->sort_tmp_bytes;
-    HIP_TRY(hnyk_sort_pairs48(b->d_sort_tmp.p, tmp, b->d_lkey_a.p, b->d_lkey_b.p, b->d_perm_a.p,
-                              b->d_perm_b.p, cnt, b->stream));
+    HIP_TRY(launch_walk(region_descent(b, walk_args(L, lo, hi, queues + 0)), b->stream));
+    if (int rc = region_order(b, lo, cnt, top)) return rc;
+    const u32 xcd_tile = xcd_tile_of(b, cnt);
     for (int32_t l = (int32_t)L; l >= 0; l--) { // hnsw.rs:312-325
-      WalkArgs w = walk_args(l, lo, hi, queues + (l + 1));
-      if (l == (int32_t)L) {
-        w.first = 0;
-        w.eps_in = b->d_eps0.p;
-      } else {
-        prof_begin(b, EV_WALK);
-      }
-      w.perm = b->d_perm_b.p;
-      if (xcd_tile && cnt >= 16u * xcd_tile) {
+      WalkArgs w = l == (int32_t)L ? top : walk_args(l, lo, hi, queues + (l + 1));
+      w.perm = top.perm;
+      if (l != (int32_t)L) prof_begin(b, EV_WALK);
+      if (xcd_tile) {
         w.xcd_tile = xcd_tile;
         w.queue = xqueues + 8 * (l + 1);
       }
@@ -2907,6 +2935,11 @@ struct SearchCancel {
     if (e != hipSuccess) return e;
     return hipEventCreateWithFlags(&ev, hipEventDisableTiming);
   }
+  // how a call starts where it clears did_cancel and arms the closure at one point
+  hipError_t begin(const hny_query_opts *qo) {
+    if (qo && qo->did_cancel) *qo->did_cancel = 0;
+    return init(qo);
+  }
   bool probe() { // before a chunk is started
     if (fn && !cancelled && fn(ctx)) {
       cancelled = true;
@@ -2927,19 +2960,6 @@ struct SearchCancel {
   }
 };
 
-// drain_asc().take(k) (reader.rs:797-798): the first min(k, n_found) entries of a top-k row (dist bits << 32 |
-// slot) as the caller's ids and distances; returns the count
-static uint32_t copy_topk_row(const hny_builder *b, const u64 *row, uint32_t n_found, uint32_t k, uint32_t *ids,
-                              float *dists) {
-  const uint32_t c = std::min<uint32_t>(k, n_found);
-  for (uint32_t j = 0; j < c; j++) {
-    ids[j] = b->ids[(uint32_t)(row[j] & 0xFFFFFFFFull)];
-    const uint32_t db = (uint32_t)(row[j] >> 32);
-    memcpy(&dists[j], &db, 4);
-  }
-  return c;
-}
-
 static int search_knn_impl(hny_builder *b, uint64_t nq, const void *qvectors, size_t qstride,
                            const void *qheaders, uint32_t k, uint32_t ef_search, uint32_t *out_ids,
                            float *out_dists, uint32_t *out_counts, const hny_query_opts *qo, bool q_f32 = false);
@@ -2948,31 +2968,6 @@ static int search_knn_impl(hny_builder *b, uint64_t nq, const void *qvectors, si
 static int nns_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const void *qvectors, size_t qstride,
                     const void *qheaders, const uint32_t *query_items, uint32_t *out_ids, float *out_dists,
                     uint32_t *out_counts, bool force_heap, bool q_f32 = false);
-
-// a chunk of queries into the row buffer (and norms) the searchers read.  q_f32: Reader::nns().by_vector's &[f32]
-// (reader.rs:132-148), encoded on the device by the same kernel as the items (slot = index within the chunk);
-// otherwise codec bytes + headers
-static int stage_queries(hny_builder *b, bool q_f32, const void *qvectors, size_t qstride, const void *qheaders,
-                         uint64_t q0, uint32_t cnt, unsigned char *dq, float *dqn, std::vector<float> &qn) {
-  const size_t vb = vec_bytes(b->o.metric, b->o.dim), hb = hdr_bytes(b->o.metric);
-  const bool has_norm = b->g.norms != nullptr;
-  if (q_f32) {
-    if (!b->qpipe) b->qpipe.reset(new (std::nothrow) IngestPipe());
-    if (!b->qpipe) return fail(HNY_ERR_OOM, "out of memory");
-    IngestJob j = ingest_job(b->o.metric, b->o.dim, dq, b->g.row_stride, dqn);
-    j.src = (const unsigned char *)qvectors + q0 * qstride;
-    j.stride = qstride;
-    j.n = cnt;
-    return run_ingest(*b->qpipe, j, b->stream);
-  }
-  int rc = upload_rows((const unsigned char *)qvectors + q0 * qstride, qstride, vb, cnt, b->g.row_stride, dq, b->stream);
-  if (rc) return rc;
-  if (has_norm) {
-    for (uint32_t i = 0; i < cnt; i++) memcpy(&qn[i], (const unsigned char *)qheaders + (q0 + i) * hb, 4);
-    HIP_TRY(hipMemcpyAsync(dqn, qn.data(), (size_t)cnt * 4, hipMemcpyHostToDevice, b->stream));
-  }
-  return HNY_OK;
-}
 
 int hny_builder_search_knn(hny_builder *b, uint64_t nq, const void *qvectors, size_t qstride,
                            const void *qheaders, uint32_t k, uint32_t ef_search, uint32_t *out_ids,
@@ -2998,8 +2993,99 @@ static GraphDev search_graph(const hny_builder *b) {
   return g;
 }
 
-// how both searchers end: what the kernels of this call reported through the error words
-static int search_error_tail(hny_builder *b) {
+// ---------------------------------------------------------------------------------------------
+// The steps the three batched searchers share: search_knn_impl (Reader on k_walk), nns_impl
+// (.candidates() / by_item on k_nns / k_nns_linear) and exact_impl (tiled full scan).  Each searcher calls the
+// argument checks in its own order (the first failure names the error), fills one QuerySet, sizes its chunk,
+// allocates a QueryStage and a TopkOut and runs its own chunk loop.
+// ---------------------------------------------------------------------------------------------
+static bool mask_has(const std::vector<u32> &mask, uint32_t s) { return (mask[s >> 5] >> (s & 31)) & 1u; }
+
+// the queries of one call and where their hits go, filled once per call
+struct QuerySet {
+  const hny_builder *b;
+  uint64_t nq;
+  const void *qvectors; // by vector: codec bytes + qheaders, or f32 rows (q_f32)
+  size_t qstride;
+  const void *qheaders;
+  const uint32_t *query_items; // by item
+  bool q_f32, by_item;
+  uint32_t k;
+  uint32_t *out_ids;
+  float *out_dists;
+  uint32_t *out_counts;
+
+  bool live(uint32_t s) const { return !b->incremental || !b->deleted[s]; }
+  // the slot of a live item, -1 for an unknown or deleted one
+  int64_t live_slot(uint32_t id) const {
+    auto it = std::lower_bound(b->ids.begin(), b->ids.end(), id);
+    if (it == b->ids.end() || *it != id) return -1;
+    uint32_t s = (uint32_t)(it - b->ids.begin());
+    return live(s) ? (int64_t)s : -1;
+  }
+  // candidates ∩ item_ids (every live item without a filter) as a mask over slots; returns how many
+  uint64_t slot_mask(const hny_query_opts *qo, std::vector<u32> &mask) const {
+    mask.assign(((size_t)b->n + 31) / 32 + 1, 0u);
+    for (uint64_t i = 0; qo->has_candidates && i < qo->n_candidates; i++) {
+      int64_t sl = live_slot(qo->candidates[i]);
+      if (sl >= 0) mask[(size_t)sl >> 5] |= 1u << (sl & 31);
+    }
+    for (uint32_t s = 0; !qo->has_candidates && s < b->n; s++)
+      if (live(s)) mask[s >> 5] |= 1u << (s & 31);
+    uint64_t count = 0;
+    for (u32 word : mask) count += (uint64_t)__builtin_popcount(word);
+    return count;
+  }
+  // nothing to search among (reader.rs:652-654 / 822-824): an empty Vec each, None by item
+  int none_found() const {
+    for (uint64_t i = 0; i < nq; i++) out_counts[i] = by_item ? HNY_NNS_NONE : 0u;
+    return HNY_OK;
+  }
+};
+
+static int check_search_outputs(const hny_builder *b, const uint32_t *out_ids, const float *out_dists,
+                                const uint32_t *out_counts, uint32_t k) {
+  return !b || !out_ids || !out_dists || !out_counts || k == 0 ? fail(HNY_ERR_INVALID_ARG, "bad argument") : HNY_OK;
+}
+static int check_query_source(const QuerySet &q, const char *what) {
+  return !q.by_item && (!q.qvectors || (!q.q_f32 && !q.qheaders)) ? fail(HNY_ERR_INVALID_ARG, "%s", what) : HNY_OK;
+}
+static int check_query_rows(const QuerySet &q) {
+  return q.q_f32 ? check_f32_rows(q.b->o.dim, q.nq, q.qvectors, q.qstride) : HNY_OK;
+}
+static int check_candidates(const hny_query_opts *qo) {
+  const bool missing = qo->has_candidates && qo->n_candidates && !qo->candidates;
+  return missing ? fail(HNY_ERR_INVALID_ARG, "candidates missing") : HNY_OK;
+}
+static int check_build_finished(const hny_builder *b) {
+  return b->pos < b->order.size() ? fail(HNY_ERR_INVALID_ARG, "build not finished") : HNY_OK;
+}
+static int check_query_stride(const QuerySet &q) {
+  if (!q.by_item && !q.q_f32 && q.qstride < vec_bytes(q.b->o.metric, q.b->o.dim))
+    return fail(HNY_ERR_INVALID_DIM, "query stride too small");
+  return HNY_OK;
+}
+// *ef = max(ef_search, k), reader.rs:746, 837.  Result sets of up to 4 096 entries live in LDS, larger ones in HBM
+// (WalkArgs.res_global / k_nns's heap_r): the reference's own tests search with ef_search = n up to 9 999
+// (src/tests/reader.rs:82-98)
+static int check_ef(uint32_t ef_search, uint32_t k, uint32_t *ef) {
+  *ef = std::max(ef_search, k);
+  if ((uint64_t)*ef + 1 > HNY_RES_GLOBAL_MAX)
+    return fail(HNY_ERR_UNSUPPORTED, "ef_search %u: result sets hold at most %u entries", *ef, HNY_RES_GLOBAL_MAX - 1);
+  return HNY_OK;
+}
+
+// queries per chunk: `most` (the build's batch, at least 256, unless the caller has a block size of its own), no
+// more than there are, and at most ~2 GB of candidate lists (buffers are sized chunk x rcap / k)
+static uint32_t search_chunk(const hny_builder *b, uint64_t nq, uint32_t rcap, uint32_t k, uint32_t most = 0) {
+  if (!most) most = std::max<uint32_t>(b->max_batch, 256);
+  const uint64_t chunk = std::min<uint64_t>(most, std::max<uint64_t>(nq, 1));
+  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(chunk, ((uint64_t)2 << 30) / ((uint64_t)std::max(rcap, k) * 8)));
+}
+
+// how every searcher ends: did_cancel, then what the kernels of this call reported through the error words
+static int search_end(hny_builder *b, const hny_query_opts *qo, const SearchCancel &sc) {
+  if (sc.cancelled && qo && qo->did_cancel) *qo->did_cancel = 1;
   u64 stats[ST_COUNT] = {0};
   HIP_TRY(hipMemcpy(stats, b->d_stats.p, sizeof stats, hipMemcpyDeviceToHost));
   if (stats[ST_ERR_RES_OVERFLOW] || stats[ST_ERR_ITER]) {
@@ -3011,56 +3097,151 @@ static int search_error_tail(hny_builder *b) {
   return HNY_OK;
 }
 
+// the staging buffers of a chunk of queries: their rows (and norms) by vector, their slots by item
+struct QueryStage {
+  hny_builder *b;
+  const QuerySet &q;
+  DevBuf<unsigned char> dq;
+  DevBuf<float> dqn;
+  DevBuf<u32> dqslots;
+  std::vector<float> qn;
+  std::vector<u32> slots, members; // members: the chunk's queries that have a row
+  uint32_t n_slots = 0;            // slots that stage() uploads
+
+  int alloc(uint32_t chunk) {
+    if (!q.by_item) {
+      HIP_TRY(dq.alloc((size_t)chunk * b->g.row_stride));
+      HIP_TRY(dqn.alloc(chunk));
+    } else {
+      HIP_TRY(dqslots.alloc(chunk));
+    }
+    qn.resize(chunk);
+    slots.resize(chunk);
+    members.resize(chunk);
+    return HNY_OK;
+  }
+  const float *norms() const { return b->g.norms && !q.by_item ? dqn.p : nullptr; }
+  // by_item drops unknown and deleted items: Ok(None) (item_vector(..)? reader.rs:826), their count is HNY_NNS_NONE.
+  // nns_impl's layout: slots[i] belongs to query i of the chunk (0 where it has none).  Returns the member count
+  uint32_t members_of(uint64_t q0, uint32_t cnt) {
+    uint32_t n_mem = 0;
+    for (uint32_t i = 0; i < cnt; i++) {
+      const int64_t sl = q.by_item ? q.live_slot(q.query_items[q0 + i]) : 0;
+      slots[i] = sl >= 0 ? (uint32_t)sl : 0u;
+      if (sl >= 0) members[n_mem++] = i;
+      else q.out_counts[q0 + i] = HNY_NNS_NONE;
+    }
+    n_slots = cnt;
+    return n_mem;
+  }
+  // exact_impl's layout: slots[j] belongs to member j, and every member starts with 0 hits
+  uint32_t members_compact(uint64_t q0, uint32_t cnt) {
+    const uint32_t n_mem = members_of(q0, cnt);
+    for (uint32_t j = 0; j < n_mem; j++) {
+      q.out_counts[q0 + members[j]] = 0u;
+      slots[j] = slots[members[j]];
+    }
+    n_slots = n_mem;
+    return n_mem;
+  }
+  // the chunk into the buffers the searchers read.  q_f32: Reader::nns().by_vector's &[f32] (reader.rs:132-148),
+  // encoded on the device by the same kernel as the items (slot = index within the chunk); otherwise codec bytes
+  // + headers
+  int stage(uint64_t q0, uint32_t cnt) {
+    if (q.by_item) {
+      HIP_TRY(hipMemcpyAsync(dqslots.p, slots.data(), (size_t)n_slots * 4, hipMemcpyHostToDevice, b->stream));
+      return HNY_OK;
+    }
+    const unsigned char *src = (const unsigned char *)q.qvectors + q0 * q.qstride;
+    if (q.q_f32) {
+      if (!b->qpipe) b->qpipe.reset(new (std::nothrow) IngestPipe());
+      if (!b->qpipe) return fail(HNY_ERR_OOM, "out of memory");
+      IngestJob j = ingest_job(b->o.metric, b->o.dim, dq.p, b->g.row_stride, dqn.p);
+      j.src = src;
+      j.stride = q.qstride;
+      j.n = cnt;
+      return run_ingest(*b->qpipe, j, b->stream);
+    }
+    const size_t vb = vec_bytes(b->o.metric, b->o.dim), hb = hdr_bytes(b->o.metric);
+    int rc = upload_rows(src, q.qstride, vb, cnt, b->g.row_stride, dq.p, b->stream);
+    if (rc) return rc;
+    if (b->g.norms) {
+      for (uint32_t i = 0; i < cnt; i++) memcpy(&qn[i], (const unsigned char *)q.qheaders + (q0 + i) * hb, 4);
+      HIP_TRY(hipMemcpyAsync(dqn.p, qn.data(), (size_t)cnt * 4, hipMemcpyHostToDevice, b->stream));
+    }
+    return HNY_OK;
+  }
+};
+
+// the k best of a chunk's candidate lists on their way to the caller's arrays; kk: hits per row, q.k unless fewer
+// items can match
+struct TopkOut {
+  hny_builder *b;
+  const QuerySet &q;
+  uint32_t kk;
+  DevBuf<u64> dtop;
+  std::vector<u64> hc;
+  std::vector<u32> hn;
+
+  int alloc(uint32_t chunk) {
+    HIP_TRY(dtop.alloc((size_t)chunk * kk));
+    hc.resize((size_t)chunk * kk);
+    hn.resize(chunk);
+    return HNY_OK;
+  }
+  // rows 0..n of `lists` (rcap entries each, `counts` filled) sorted and cut to kk, on the host when this returns
+  int fetch(const u64 *lists, const u32 *counts, uint32_t rcap, uint32_t n, SearchCancel &sc) {
+    HIP_TRY(hnyk_take_topk(lists, counts, rcap, kk, n, dtop.p, b->stream));
+    HIP_TRY(hipMemcpyAsync(hc.data(), dtop.p, (size_t)n * kk * 8, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemcpyAsync(hn.data(), counts, (size_t)n * 4, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(sc.wait(b));
+    return HNY_OK;
+  }
+  // drain_asc().take(k) (reader.rs:797-798): the first min(kk, found) entries of row j (dist bits << 32 | slot) as
+  // query qi's ids, distances and count
+  void emit(uint32_t j, uint64_t qi) const {
+    const u64 *row = &hc[(size_t)j * kk];
+    const uint32_t c = std::min<uint32_t>(kk, hn[j]);
+    for (uint32_t i = 0; i < c; i++) {
+      q.out_ids[qi * q.k + i] = b->ids[(uint32_t)(row[i] & 0xFFFFFFFFull)];
+      const uint32_t db = (uint32_t)(row[i] >> 32);
+      memcpy(&q.out_dists[qi * q.k + i], &db, 4);
+    }
+    q.out_counts[qi] = c;
+  }
+};
+
 static int search_knn_impl(hny_builder *b, uint64_t nq, const void *qvectors, size_t qstride,
                            const void *qheaders, uint32_t k, uint32_t ef_search, uint32_t *out_ids,
                            float *out_dists, uint32_t *out_counts, const hny_query_opts *qo, bool q_f32) {
-  if (!b || !qvectors || (!q_f32 && !qheaders) || !out_ids || !out_dists || !out_counts || k == 0)
-    return fail(HNY_ERR_INVALID_ARG, "bad argument");
-  if (q_f32) {
-    int rcf = check_f32_rows(b->o.dim, nq, qvectors, qstride);
-    if (rcf) return rcf;
-  }
+  if (int rc = check_search_outputs(b, out_ids, out_dists, out_counts, k)) return rc;
+  const QuerySet qs{b, nq, qvectors, qstride, qheaders, nullptr, q_f32, false, k, out_ids, out_dists, out_counts};
+  if (int rc = check_query_source(qs, "bad argument")) return rc;
+  if (int rc = check_query_rows(qs)) return rc;
   SearchCancel sc;
-  if (qo && qo->did_cancel) *qo->did_cancel = 0;
-  HIP_TRY(sc.init(qo));
-  if (b->pos < b->order.size()) return fail(HNY_ERR_INVALID_ARG, "build not finished");
-  const uint32_t ef = std::max(ef_search, k); // reader.rs:746
-  // result sets of up to 4 096 entries live in the walk's LDS, larger ones in HBM (WalkArgs.res_global, the
-  // general kernel): the reference's own tests search with ef_search = n up to 9 999 (src/tests/reader.rs:82-98)
-  if ((uint64_t)ef + 1 > HNY_RES_GLOBAL_MAX)
-    return fail(HNY_ERR_UNSUPPORTED, "ef_search %u: result sets hold at most %u entries", ef, HNY_RES_GLOBAL_MAX - 1);
+  HIP_TRY(sc.begin(qo));
+  if (int rc = check_build_finished(b)) return rc;
+  uint32_t ef;
+  if (int rc = check_ef(ef_search, k, &ef)) return rc;
   HIP_TRY(hipSetDevice(b->device));
-  if (b->n == 0) {
-    for (uint64_t i = 0; i < nq; i++) out_counts[i] = 0; // reader.rs:652-654
-    return HNY_OK;
-  }
+  if (b->n == 0) return qs.none_found();
   if (int rc = ensure_finalized(b, b->stream)) return rc; // Reader::visit iterates Links bitmaps: ascending, deduplicated
   const GraphDev sg = search_graph(b);
   const uint32_t rcap = res_capacity(ef, (uint32_t)b->entry_points.size(), b->n, b->top_layer_nodes, HNY_RES_GLOBAL_MAX);
-  const size_t vb = vec_bytes(b->o.metric, b->o.dim), hb = hdr_bytes(b->o.metric);
-  if (!q_f32 && qstride < vb) return fail(HNY_ERR_INVALID_DIM, "query stride too small");
-  uint32_t chunk = std::max<uint32_t>(b->max_batch, 256);
-  chunk = (uint32_t)std::min<uint64_t>(chunk, std::max<uint64_t>(nq, 1)); // buffers are sized chunk x rcap / k
-  // at most ~2 GB of candidate lists per chunk
-  chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(chunk, ((uint64_t)2 << 30) / ((uint64_t)std::max(rcap, k) * 8)));
-  DevBuf<unsigned char> dq;
-  DevBuf<float> dqn;
+  if (int rc = check_query_stride(qs)) return rc;
+  uint32_t chunk = search_chunk(b, nq, rcap, k);
   DevBuf<u64> dcand, dres; // dres: result sets beyond the LDS (a search from more entry points than ef, res_capacity)
   DevBuf<u32> dcn;
   if (rcap > HNY_RES_LDS_MAX) {
     chunk = std::min<uint32_t>(chunk, 4096);
     HIP_TRY(dres.alloc((size_t)std::min<uint32_t>(chunk, b->walk_slots) * rcap));
   }
-  HIP_TRY(dq.alloc((size_t)chunk * b->g.row_stride));
-  HIP_TRY(dqn.alloc(chunk));
+  QueryStage st{b, qs};
+  TopkOut top{b, qs, k};
+  if (int rc = st.alloc(chunk)) return rc;
   HIP_TRY(dcand.alloc((size_t)chunk * rcap));
   HIP_TRY(dcn.alloc(chunk));
-  const bool has_norm = b->g.norms != nullptr;
-  std::vector<float> qn(chunk);
-  DevBuf<u64> dtop;
-  HIP_TRY(dtop.alloc((size_t)chunk * k));
-  std::vector<u64> hc((size_t)chunk * k);
-  std::vector<u32> hn(chunk);
+  if (int rc = top.alloc(chunk)) return rc;
   u32 *queues = b->d_nseg.p + 4;
   for (uint64_t q0 = 0; q0 < nq; q0 += chunk) {
     uint32_t cnt = (uint32_t)std::min<uint64_t>(chunk, nq - q0);
@@ -3068,11 +3249,10 @@ static int search_knn_impl(hny_builder *b, uint64_t nq, const void *qvectors, si
       for (uint32_t i = 0; i < cnt; i++) out_counts[q0 + i] = 0u;
       continue;
     }
-    int rc = stage_queries(b, q_f32, qvectors, qstride, qheaders, q0, cnt, dq.p, dqn.p, qn);
-    if (rc) return rc;
+    if (int rc = st.stage(q0, cnt)) return rc;
     WalkArgs w{};
-    w.q_rows = dq.p;
-    w.q_norms = has_norm ? dqn.p : nullptr;
+    w.q_rows = st.dq.p;
+    w.q_norms = st.norms();
     w.q_stride = b->g.row_stride;
     w.lo = 0;
     w.hi = cnt;
@@ -3082,73 +3262,44 @@ static int search_knn_impl(hny_builder *b, uint64_t nq, const void *qvectors, si
     w.reader_mode = 1;
     w.knn_k = k;
     w.knn_ef = ef_search;
-    w.entry_points = b->d_eps.p;
-    w.n_entry_points = (u32)b->entry_points.size();
     w.cand = dcand.p;
     w.cand_n = dcn.p;
-    w.rcap = rcap;
-    w.bits = b->d_bits.p;
-    w.bits_words = b->bits_words;
-    w.vlog = b->d_vlog.p;
-    w.log_cap = b->log_cap;
-    w.res_global = dres.p;
-    w.vis_slots = vis_slots_for(b, dres.p ? 0u : w.rcap);
-    w.eps_cap = eps_cap_of(b);
     w.queue = queues;
     w.cancel = sc.d;
-    vis_buckets_for(b, w);
-    w.pool_flag = env_int("HNY_NO_POOL_RETRY", 0) == 0 ? 1u : 0u;
-    w.force_pool = (u32)std::max(0, env_int("HNY_POOL_FORCE_RETRY", 0)); // tests: every k-th query takes the retry path
+    walk_workspace(b, w, rcap, dres.p);
+    w.pool_flag = pool_retry_env(w) ? 1u : 0u;
     if (sc.d) HIP_TRY(hnyk_fill_u32(dcn.p, 0xFFFFFFFFu, cnt, b->stream)); // = never finished
     HIP_TRY(hipMemsetAsync(queues, 0, 8 * 4, b->stream));
     const int grid = (int)std::min<uint32_t>(cnt, b->walk_slots);
     if (b->locality && b->max_level >= 1 && cnt >= 2048) {
       // same locality ordering as the build: descent -> sort the queries by their region -> layer 0
-      WalkArgs d = w;
-      d.descend_only = 1;
-      d.eps_out = b->d_eps0.p;
-      d.key_out = b->d_lkey_a.p;
       b->n_walk_dispatch++;
-    HIP_TRY(hnyk_walk(sg, d, b->shape, grid, b->stream));
-      HIP_TRY(hnyk_iota_u64(b->d_perm_a.p, 0, cnt, b->stream));
-      size_t tmp = b->sort_tmp_bytes;
-      HIP_TRY(hnyk_sort_pairs48(b->d_sort_tmp.p, tmp, b->d_lkey_a.p, b->d_lkey_b.p, b->d_perm_a.p,
-                                b->d_perm_b.p, cnt, b->stream));
-      w.first = 0;
-      w.eps_in = b->d_eps0.p;
-      w.perm = b->d_perm_b.p;
+      HIP_TRY(hnyk_walk(sg, region_descent(b, w), b->shape, grid, b->stream));
+      if (int rc = region_order(b, 0, cnt, w)) return rc;
       w.queue = queues + 1;
-      // the same XCD-tiled work queue as the build's level-0 walks (rows >= 1 KB, see run_batch)
-      const u32 xcd_tile = (u32)std::max(0, env_int("HNY_XCD_TILE", b->g.row_stride >= 1024u ? 512 : 0));
-      if (xcd_tile && cnt >= 16u * xcd_tile) {
-        w.xcd_tile = xcd_tile;
+      // the same XCD-tiled work queue as the build's level-0 walks (rows >= 1 KB, see xcd_tile_of)
+      if ((w.xcd_tile = xcd_tile_of(b, cnt))) {
         w.queue = queues + 16; // 8 counters, zeroed below
         HIP_TRY(hipMemsetAsync(queues + 16, 0, 8 * 4, b->stream));
       }
     }
     b->n_walk_dispatch++;
     HIP_TRY(hnyk_walk(sg, w, b->shape, grid, b->stream));
-    HIP_TRY(hnyk_take_topk(dcand.p, dcn.p, rcap, k, cnt, dtop.p, b->stream));
-    HIP_TRY(hipMemcpyAsync(hc.data(), dtop.p, (size_t)cnt * k * 8, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipMemcpyAsync(hn.data(), dcn.p, (size_t)cnt * 4, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(sc.wait(b));
+    if (int rc = top.fetch(dcand.p, dcn.p, rcap, cnt, sc)) return rc;
     std::vector<uint32_t> again; // queries whose tie pool overflowed (short codes, large ef_search: ties everywhere)
     for (uint32_t i = 0; i < cnt; i++) {
-      if (sc.d && hn[i] == 0xFFFFFFFFu) { // the batch was cancelled before this query finished
+      if (sc.d && top.hn[i] == 0xFFFFFFFFu) // the batch was cancelled before this query finished
         out_counts[q0 + i] = 0u;
-        continue;
-      }
-      if (hn[i] == 0xFFFFFFFEu) {
+      else if (top.hn[i] == 0xFFFFFFFEu)
         again.push_back(i);
-        continue;
-      }
-      out_counts[q0 + i] =
-          copy_topk_row(b, &hc[(size_t)i * k], hn[i], k, &out_ids[(q0 + i) * k], &out_dists[(q0 + i) * k]);
+      else
+        top.emit(i, q0 + i);
     }
     if (!again.empty() && !sc.cancelled) {
       // the same queries on the searcher whose queue is a real heap in HBM (and `res` too, when ef + 1 >
       // HNY_RES_LDS_MAX): nothing to overflow, same results
       // (f32 queries: their f32 rows, which the device encodes again to the same bytes)
+      const size_t vb = vec_bytes(b->o.metric, b->o.dim), hb = hdr_bytes(b->o.metric);
       const size_t na = again.size(), qb = q_f32 ? (size_t)b->o.dim * 4 : vb;
       std::vector<unsigned char> av(na * qb), ah(na * hb);
       std::vector<uint32_t> ai(na * k), ac(na);
@@ -3178,8 +3329,7 @@ static int search_knn_impl(hny_builder *b, uint64_t nq, const void *qvectors, si
       for (uint32_t i : again) out_counts[q0 + i] = 0u;
     }
   }
-  if (sc.cancelled && qo && qo->did_cancel) *qo->did_cancel = 1;
-  return search_error_tail(b);
+  return search_end(b, qo, sc);
 }
 
 // QueryBuilder with .candidates() and/or by_item (reader.rs:60-262, 621-711, 809-896)
@@ -3198,25 +3348,21 @@ int hny_builder_nns_f32(hny_builder *b, const hny_query_opts *qo, uint64_t nq, c
 static int nns_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const void *qvectors, size_t qstride,
                     const void *qheaders, const uint32_t *query_items, uint32_t *out_ids, float *out_dists,
                     uint32_t *out_counts, bool force_heap, bool q_f32) {
-  if (!b || !qo || !out_ids || !out_dists || !out_counts || qo->k == 0)
-    return fail(HNY_ERR_INVALID_ARG, "bad argument");
+  if (int rc = check_search_outputs(b, out_ids, out_dists, out_counts, qo ? qo->k : 0)) return rc;
   const bool by_item = query_items != nullptr;
-  if (!by_item && (!qvectors || (!q_f32 && !qheaders))) return fail(HNY_ERR_INVALID_ARG, "no queries");
-  if (q_f32) {
-    int rcf = check_f32_rows(b->o.dim, nq, qvectors, qstride);
-    if (rcf) return rcf;
-  }
-  if (qo->has_candidates && qo->n_candidates && !qo->candidates)
-    return fail(HNY_ERR_INVALID_ARG, "candidates missing");
+  const uint32_t k = qo->k, NONE = HNY_NNS_NONE;
+  const QuerySet qs{b, nq, qvectors, qstride, qheaders, query_items, q_f32, by_item, k, out_ids, out_dists, out_counts};
+  if (int rc = check_query_source(qs, "no queries")) return rc;
+  if (int rc = check_query_rows(qs)) return rc; // here the f32 rows come before the candidates, in exact_impl after
+  if (int rc = check_candidates(qo)) return rc;
   if (!(qo->linear_below_ratio >= 0.f && qo->linear_below_ratio <= 1.f)) // reader.rs:253-256
     return fail(HNY_ERR_INVALID_ARG, "linear scan threshold ratio must be between 0.0 and 1.0");
   if (!qo->has_candidates && !by_item && !force_heap)
-    return search_knn_impl(b, nq, qvectors, qstride, qheaders, qo->k, qo->ef_search, out_ids, out_dists,
-                           out_counts, qo, q_f32);
-  if (b->pos < b->order.size()) return fail(HNY_ERR_INVALID_ARG, "build not finished");
-  const uint32_t k = qo->k, ef = std::max(qo->ef_search, k); // reader.rs:746, 837
-  if ((uint64_t)ef + 1 > HNY_RES_GLOBAL_MAX)
-    return fail(HNY_ERR_UNSUPPORTED, "ef_search %u: result sets hold at most %u entries", ef, HNY_RES_GLOBAL_MAX - 1);
+    return search_knn_impl(b, nq, qvectors, qstride, qheaders, k, qo->ef_search, out_ids, out_dists, out_counts, qo,
+                           q_f32);
+  if (int rc = check_build_finished(b)) return rc;
+  uint32_t ef;
+  if (int rc = check_ef(qo->ef_search, k, &ef)) return rc;
   // k_nns keeps its result set in LDS (up to 4 096 entries); beyond that the same search runs with `res` as a
   // heap in HBM next to the search queue's
   // ... and so does a search that starts from more entry points than the LDS set holds (every entry point is pushed
@@ -3225,33 +3371,15 @@ static int nns_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const
   const bool big = ef + 1 > HNY_RES_LDS_MAX || eps_need > HNY_RES_LDS_MAX;
   HIP_TRY(hipSetDevice(b->device));
   const uint32_t n = b->n;
-  auto exists = [&](uint32_t s) { return !b->incremental || !b->deleted[s]; };
-  auto slot_of = [&](uint32_t id) -> int64_t {
-    auto it = std::lower_bound(b->ids.begin(), b->ids.end(), id);
-    if (it == b->ids.end() || *it != id) return -1;
-    uint32_t s = (uint32_t)(it - b->ids.begin());
-    return exists(s) ? (int64_t)s : -1;
-  };
   uint64_t n_items = 0;
-  for (uint32_t s = 0; s < n; s++) n_items += exists(s) ? 1 : 0;
-  // candidates ∩ item_ids as a mask over slots
-  std::vector<u32> mask;
-  std::vector<u32> cand_slots;
+  for (uint32_t s = 0; s < n; s++) n_items += qs.live(s) ? 1 : 0;
+  std::vector<u32> mask, cand_slots; // the filter, and its slots in ascending order
   if (qo->has_candidates) {
-    mask.assign(((size_t)n + 31) / 32 + 1, 0u);
-    for (uint64_t i = 0; i < qo->n_candidates; i++) {
-      int64_t sl = slot_of(qo->candidates[i]);
-      if (sl >= 0) mask[(size_t)sl >> 5] |= 1u << (sl & 31);
-    }
+    cand_slots.reserve(qs.slot_mask(qo, mask));
     for (uint32_t s = 0; s < n; s++)
-      if ((mask[s >> 5] >> (s & 31)) & 1u) cand_slots.push_back(s);
+      if (mask_has(mask, s)) cand_slots.push_back(s);
   }
-  const uint32_t NONE = HNY_NNS_NONE;
-  // reader.rs:652-654 / 822-824
-  if (n_items == 0 || (qo->has_candidates && cand_slots.empty())) {
-    for (uint64_t i = 0; i < nq; i++) out_counts[i] = by_item ? NONE : 0u;
-    return HNY_OK;
-  }
+  if (n_items == 0 || (qo->has_candidates && cand_slots.empty())) return qs.none_found();
   // should_linear_scan, reader.rs:621-640
   bool linear = false;
   if (qo->has_candidates) {
@@ -3270,24 +3398,15 @@ static int nns_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const
     rcap = 64;
     while (rcap < need) rcap *= 2;
   }
-  const size_t vb = vec_bytes(b->o.metric, b->o.dim);
-  if (!by_item && !q_f32 && qstride < vb) return fail(HNY_ERR_INVALID_DIM, "query stride too small");
-  const uint32_t chunk = (uint32_t)std::max<uint64_t>(
-      1, std::min<uint64_t>(std::min<uint64_t>(std::max<uint32_t>(b->max_batch, 256), std::max<uint64_t>(nq, 1)),
-                            ((uint64_t)2 << 30) / ((uint64_t)std::max(rcap, k) * 8))); // <= ~2 GB of candidate lists
-  const bool has_norm = b->g.norms != nullptr;
-  DevBuf<unsigned char> dq;
-  DevBuf<float> dqn;
-  DevBuf<u64> dcand, dtop, dheap;
-  DevBuf<u32> dcn, dstatus, dqslots, dmembers, dfilter, dcslots;
-  if (!by_item) {
-    HIP_TRY(dq.alloc((size_t)chunk * b->g.row_stride));
-    HIP_TRY(dqn.alloc(chunk));
-  } else {
-    HIP_TRY(dqslots.alloc(chunk));
-  }
+  if (int rc = check_query_stride(qs)) return rc;
+  const uint32_t chunk = search_chunk(b, nq, rcap, k);
+  QueryStage st{b, qs};
+  TopkOut top{b, qs, k};
+  DevBuf<u64> dcand, dheap;
+  DevBuf<u32> dcn, dstatus, dmembers, dfilter, dcslots;
+  if (int rc = st.alloc(chunk)) return rc;
   HIP_TRY(dcand.alloc((size_t)chunk * rcap));
-  HIP_TRY(dtop.alloc((size_t)chunk * k));
+  if (int rc = top.alloc(chunk)) return rc;
   HIP_TRY(dcn.alloc(chunk));
   HIP_TRY(dstatus.alloc(chunk));
   HIP_TRY(dmembers.alloc(chunk));
@@ -3318,41 +3437,25 @@ static int nns_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const
     HIP_TRY(dheap.alloc((size_t)grid_small * heap_small));
   DevBuf<u64> dheap_full;
   uint32_t grid_full = 0;
-  std::vector<float> qn(chunk);
-  std::vector<u32> qs(chunk), members(chunk), hn(chunk), hst(chunk);
-  std::vector<u64> hc((size_t)chunk * k);
+  std::vector<u32> hst(chunk);
   u32 *queues = b->d_nseg.p + 4;
   SearchCancel sc; // hny_query_opts.cancel
-  if (qo->did_cancel) *qo->did_cancel = 0;
-  HIP_TRY(sc.init(qo));
+  HIP_TRY(sc.begin(qo));
   for (uint64_t q0 = 0; q0 < nq; q0 += chunk) {
     const uint32_t cnt = (uint32_t)std::min<uint64_t>(chunk, nq - q0);
     if (sc.probe()) { // nothing of this chunk is started: 0 hits each (unknown items stay None)
       for (uint32_t i = 0; i < cnt; i++)
-        out_counts[q0 + i] = by_item && slot_of(query_items[q0 + i]) < 0 ? NONE : 0u;
+        out_counts[q0 + i] = by_item && qs.live_slot(query_items[q0 + i]) < 0 ? NONE : 0u;
       continue;
     }
-    uint32_t n_mem = 0;
-    if (by_item) {
-      for (uint32_t i = 0; i < cnt; i++) {
-        int64_t sl = slot_of(query_items[q0 + i]); // item_vector(..)? else Ok(None), reader.rs:826
-        qs[i] = sl >= 0 ? (uint32_t)sl : 0u;
-        hn[i] = 0;
-        if (sl >= 0) members[n_mem++] = i;
-        else out_counts[q0 + i] = NONE;
-      }
-      HIP_TRY(hipMemcpyAsync(dqslots.p, qs.data(), (size_t)cnt * 4, hipMemcpyHostToDevice, b->stream));
-    } else {
-      int rc = stage_queries(b, q_f32, qvectors, qstride, qheaders, q0, cnt, dq.p, dqn.p, qn);
-      if (rc) return rc;
-      for (uint32_t i = 0; i < cnt; i++) members[n_mem++] = i;
-    }
+    const uint32_t n_mem = st.members_of(q0, cnt);
+    if (int rc = st.stage(q0, cnt)) return rc;
     if (n_mem == 0) continue;
-    HIP_TRY(hipMemcpyAsync(dmembers.p, members.data(), (size_t)n_mem * 4, hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(dmembers.p, st.members.data(), (size_t)n_mem * 4, hipMemcpyHostToDevice, b->stream));
     NnsArgs a{};
-    a.q_slots = dqslots.p;
-    a.q_rows = dq.p;
-    a.q_norms = has_norm && !by_item ? dqn.p : nullptr;
+    a.q_slots = st.dqslots.p;
+    a.q_rows = st.dq.p;
+    a.q_norms = st.norms();
     a.q_stride = b->g.row_stride;
     a.members = dmembers.p;
     a.n_members = n_mem;
@@ -3395,13 +3498,13 @@ static int nns_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const
       HIP_TRY(sc.wait(b));
       uint32_t n_retry = 0;
       for (uint32_t j = 0; j < n_mem; j++)
-        if (hst[members[j]] == 1u) members[n_retry++] = members[j];
+        if (hst[st.members[j]] == 1u) st.members[n_retry++] = st.members[j];
       if (n_retry && heap_small < heap_full) {
         if (!grid_full) {
           grid_full = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(b->walk_slots, (2ull << 30) / ((uint64_t)heap_full * 8)));
           HIP_TRY(dheap_full.alloc((size_t)grid_full * heap_full));
         }
-        HIP_TRY(hipMemcpyAsync(dmembers.p, members.data(), (size_t)n_retry * 4, hipMemcpyHostToDevice, b->stream));
+        HIP_TRY(hipMemcpyAsync(dmembers.p, st.members.data(), (size_t)n_retry * 4, hipMemcpyHostToDevice, b->stream));
         a.n_members = n_retry;
         a.heap = dheap_full.p;
         a.heap_cap = heap_full;
@@ -3411,24 +3514,20 @@ static int nns_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const
         return fail(HNY_ERR_DEVICE, "search queue overflow");
       }
     }
-    HIP_TRY(hnyk_take_topk(dcand.p, dcn.p, rcap, k, cnt, dtop.p, b->stream));
-    HIP_TRY(hipMemcpyAsync(hc.data(), dtop.p, (size_t)cnt * k * 8, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipMemcpyAsync(hn.data(), dcn.p, (size_t)cnt * 4, hipMemcpyDeviceToHost, b->stream));
+    // the status words travel ahead of the hits, on the same stream
     HIP_TRY(hipMemcpyAsync(hst.data(), dstatus.p, (size_t)cnt * 4, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(sc.wait(b));
+    if (int rc = top.fetch(dcand.p, dcn.p, rcap, cnt, sc)) return rc;
     for (uint32_t i = 0; i < cnt; i++) {
-      if (by_item && out_counts[q0 + i] == NONE && slot_of(query_items[q0 + i]) < 0) continue;
+      if (by_item && out_counts[q0 + i] == NONE && qs.live_slot(query_items[q0 + i]) < 0) continue;
       if (hst[i] == 2u || (sc.cancelled && hst[i] == 1u)) { // cancelled before this query (re)started
         out_counts[q0 + i] = 0u;
         continue;
       }
       if (hst[i]) return fail(HNY_ERR_DEVICE, "search queue overflow");
-      out_counts[q0 + i] =
-          copy_topk_row(b, &hc[(size_t)i * k], hn[i], k, &out_ids[(q0 + i) * k], &out_dists[(q0 + i) * k]);
+      top.emit(i, q0 + i);
     }
   }
-  if (sc.cancelled && qo->did_cancel) *qo->did_cancel = 1;
-  return search_error_tail(b);
+  return search_end(b, qo, sc);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3440,54 +3539,24 @@ static int nns_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const
 static int exact_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const void *qvectors, size_t qstride,
                       const void *qheaders, const uint32_t *query_items, uint32_t *out_ids, float *out_dists,
                       uint32_t *out_counts, bool q_f32) {
-  if (!b || !qo || !out_ids || !out_dists || !out_counts || qo->k == 0)
-    return fail(HNY_ERR_INVALID_ARG, "bad argument");
+  if (int rc = check_search_outputs(b, out_ids, out_dists, out_counts, qo ? qo->k : 0)) return rc;
   const bool by_item = query_items != nullptr;
-  if (!by_item && (!qvectors || (!q_f32 && !qheaders))) return fail(HNY_ERR_INVALID_ARG, "no queries");
-  if (qo->has_candidates && qo->n_candidates && !qo->candidates)
-    return fail(HNY_ERR_INVALID_ARG, "candidates missing");
-  if (q_f32) {
-    int rcf = check_f32_rows(b->o.dim, nq, qvectors, qstride);
-    if (rcf) return rcf;
-  }
-  if (b->pos < b->order.size()) return fail(HNY_ERR_INVALID_ARG, "build not finished");
   const uint32_t n = b->n, k = qo->k, NONE = HNY_NNS_NONE;
-  auto exists = [&](uint32_t s) { return !b->incremental || !b->deleted[s]; };
-  auto slot_of = [&](uint32_t id) -> int64_t {
-    auto it = std::lower_bound(b->ids.begin(), b->ids.end(), id);
-    if (it == b->ids.end() || *it != id) return -1;
-    uint32_t s = (uint32_t)(it - b->ids.begin());
-    return exists(s) ? (int64_t)s : -1;
-  };
+  const QuerySet qs{b, nq, qvectors, qstride, qheaders, query_items, q_f32, by_item, k, out_ids, out_dists, out_counts};
+  if (int rc = check_query_source(qs, "no queries")) return rc;
+  if (int rc = check_candidates(qo)) return rc; // here the candidates come before the f32 rows, in nns_impl after
+  if (int rc = check_query_rows(qs)) return rc;
+  if (int rc = check_build_finished(b)) return rc;
   // C = live items (∩ candidates) as a mask over slots, the one nns_impl builds for its filter
-  std::vector<u32> mask(((size_t)n + 31) / 32 + 1, 0u);
-  uint64_t n_c = 0;
-  if (qo->has_candidates) {
-    for (uint64_t i = 0; i < qo->n_candidates; i++) {
-      int64_t sl = slot_of(qo->candidates[i]);
-      if (sl >= 0 && !((mask[(size_t)sl >> 5] >> (sl & 31)) & 1u)) {
-        mask[(size_t)sl >> 5] |= 1u << (sl & 31);
-        n_c++;
-      }
-    }
-  } else {
-    for (uint32_t s = 0; s < n; s++)
-      if (exists(s)) {
-        mask[s >> 5] |= 1u << (s & 31);
-        n_c++;
-      }
-  }
+  std::vector<u32> mask;
+  const uint64_t n_c = qs.slot_mask(qo, mask);
   if (qo->did_cancel) *qo->did_cancel = 0;
-  if (n_c == 0) { // reader.rs:652-654 / 822-824
-    for (uint64_t i = 0; i < nq; i++) out_counts[i] = by_item ? NONE : 0u;
-    return HNY_OK;
-  }
+  if (n_c == 0) return qs.none_found();
   const uint32_t kk = (uint32_t)std::min<uint64_t>(k, n_c); // hits per query
   if ((uint64_t)kk + 1 > HNY_RES_LDS_MAX)
     return fail(HNY_ERR_UNSUPPORTED, "exact scan for %u hits among %llu items: at most %u hits", k,
                 (unsigned long long)n_c, HNY_RES_LDS_MAX - 1);
-  const size_t vb = vec_bytes(b->o.metric, b->o.dim);
-  if (!by_item && !q_f32 && qstride < vb) return fail(HNY_ERR_INVALID_DIM, "query stride too small");
+  if (int rc = check_query_stride(qs)) return rc;
   HIP_TRY(hipSetDevice(b->device));
   const uint32_t qt = hnyk_exact_qt(b->g.row_stride);
   const bool strict = b->g.x86_order && b->g.mclass != MC_BIN;
@@ -3496,7 +3565,7 @@ static int exact_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, con
     std::vector<uint32_t> c_ids;
     c_ids.reserve(n_c);
     for (uint32_t s = 0; s < n; s++)
-      if ((mask[s >> 5] >> (s & 31)) & 1u) c_ids.push_back(b->ids[s]);
+      if (mask_has(mask, s)) c_ids.push_back(b->ids[s]);
     hny_query_opts o2 = *qo;
     o2.k = kk;
     o2.ef_search = 0;
@@ -3522,58 +3591,31 @@ static int exact_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, con
   }
   uint32_t rcap = 64;
   while (rcap < kk + 1) rcap *= 2;
-  // running lists within the 2 GB rule of nns_impl
-  const uint32_t qblock = (uint32_t)std::max<uint64_t>(
-      1, std::min<uint64_t>(std::min<uint64_t>(HNY_EXACT_QBLOCK, std::max<uint64_t>(nq, 1)), ((uint64_t)2 << 30) / ((uint64_t)rcap * 8)));
+  const uint32_t qblock = search_chunk(b, nq, rcap, kk, HNY_EXACT_QBLOCK); // running lists within the 2 GB rule
   const uint32_t sstride = (std::min<uint32_t>(n, HNY_EXACT_SLAB) + 63u) & ~63u;
-  const bool has_norm = b->g.norms != nullptr;
-  DevBuf<unsigned char> dq;
-  DevBuf<float> dqn, dscores;
-  DevBuf<u64> dlists, dtop;
-  DevBuf<u32> dln, dqslots, dmask;
-  if (!by_item) {
-    HIP_TRY(dq.alloc((size_t)qblock * b->g.row_stride));
-    HIP_TRY(dqn.alloc(qblock));
-  } else {
-    HIP_TRY(dqslots.alloc(qblock));
-  }
+  QueryStage st{b, qs};
+  TopkOut top{b, qs, kk};
+  DevBuf<float> dscores;
+  DevBuf<u64> dlists;
+  DevBuf<u32> dln, dmask;
+  if (int rc = st.alloc(qblock)) return rc;
   HIP_TRY(dscores.alloc((size_t)qblock * sstride));
   HIP_TRY(dlists.alloc((size_t)qblock * rcap));
-  HIP_TRY(dtop.alloc((size_t)qblock * kk));
+  if (int rc = top.alloc(qblock)) return rc;
   HIP_TRY(dln.alloc(qblock));
   HIP_TRY(dmask.alloc(mask.size()));
   HIP_TRY(hipMemcpyAsync(dmask.p, mask.data(), mask.size() * 4, hipMemcpyHostToDevice, b->stream));
-  std::vector<float> qn(qblock);
-  std::vector<u32> qs(qblock), members(qblock), hn(qblock);
-  std::vector<u64> hc((size_t)qblock * kk);
   SearchCancel sc;
-  HIP_TRY(sc.init(qo));
+  HIP_TRY(sc.init(qo)); // (did_cancel was cleared above, ahead of the early returns)
   for (uint64_t q0 = 0; q0 < nq; q0 += qblock) {
     const uint32_t cnt = (uint32_t)std::min<uint64_t>(qblock, nq - q0);
-    // the block's queries that have a row: by_item drops unknown and deleted items (Ok(None), reader.rs:826)
-    uint32_t n_mem = 0;
-    for (uint32_t i = 0; i < cnt; i++) {
-      if (by_item) {
-        int64_t sl = slot_of(query_items[q0 + i]);
-        out_counts[q0 + i] = sl >= 0 ? 0u : NONE;
-        if (sl < 0) continue;
-        qs[n_mem] = (uint32_t)sl;
-      } else {
-        out_counts[q0 + i] = 0u;
-      }
-      members[n_mem++] = i;
-    }
-    if (n_mem == 0 || sc.probe()) continue; // cancelled: nothing of this block is started, 0 hits each
-    if (by_item) {
-      HIP_TRY(hipMemcpyAsync(dqslots.p, qs.data(), (size_t)n_mem * 4, hipMemcpyHostToDevice, b->stream));
-    } else {
-      int rc = stage_queries(b, q_f32, qvectors, qstride, qheaders, q0, cnt, dq.p, dqn.p, qn);
-      if (rc) return rc;
-    }
+    const uint32_t n_mem = st.members_compact(q0, cnt); // the kernels index the block's queries by member
+    if (n_mem == 0 || sc.probe()) continue;             // cancelled: nothing of this block is started, 0 hits each
+    if (int rc = st.stage(q0, cnt)) return rc;
     ExactArgs a{};
-    a.q_slots = by_item ? dqslots.p : nullptr;
-    a.q_rows = dq.p;
-    a.q_norms = has_norm && !by_item ? dqn.p : nullptr;
+    a.q_slots = st.dqslots.p;
+    a.q_rows = st.dq.p;
+    a.q_norms = st.norms();
     a.q_stride = b->g.row_stride;
     a.nq = n_mem;
     a.qt = qt;
@@ -3598,17 +3640,10 @@ static int exact_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, con
       HIP_TRY(hipStreamSynchronize(b->stream));
       continue;
     }
-    HIP_TRY(hnyk_take_topk(dlists.p, dln.p, rcap, kk, n_mem, dtop.p, b->stream));
-    HIP_TRY(hipMemcpyAsync(hc.data(), dtop.p, (size_t)n_mem * kk * 8, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipMemcpyAsync(hn.data(), dln.p, (size_t)n_mem * 4, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(sc.wait(b));
-    for (uint32_t j = 0; j < n_mem; j++) {
-      const uint64_t qi = q0 + members[j];
-      out_counts[qi] = copy_topk_row(b, &hc[(size_t)j * kk], hn[j], kk, &out_ids[qi * k], &out_dists[qi * k]);
-    }
+    if (int rc = top.fetch(dlists.p, dln.p, rcap, n_mem, sc)) return rc;
+    for (uint32_t j = 0; j < n_mem; j++) top.emit(j, q0 + st.members[j]);
   }
-  if (sc.cancelled && qo->did_cancel) *qo->did_cancel = 1;
-  return search_error_tail(b);
+  return search_end(b, qo, sc);
 }
 
 int hny_builder_exact_knn(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const void *qvectors,
