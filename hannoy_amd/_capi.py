@@ -38,9 +38,11 @@ EXPORTED = [
     "hny_builder_export_items", "hny_builder_search_knn_f32", "hny_builder_nns_f32",
     "hny_builder_create_update", "hny_builder_update", "hny_builder_finish_delta", "hny_graph_delta_free",
     "hny_builder_exact_knn", "hny_builder_exact_knn_f32",
+    "hny_builder_nns_filtered", "hny_builder_nns_filtered_f32",
 ]
 ERR_IO = -9
 NNS_NONE = 0xFFFFFFFF  # by_item: the reference returns None
+NNS_FILTER_NONE = 0xFFFFFFFF  # hny_query_filters.filter_of: no .candidates() for this query
 
 
 CANCEL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
@@ -51,6 +53,33 @@ class QueryOpts(C.Structure):
                 ("candidates", C.c_void_p), ("n_candidates", C.c_uint64), ("linear_below", C.c_uint32),
                 ("linear_below_ratio", C.c_float), ("cancel", CANCEL_FN), ("cancel_ctx", C.c_void_p),
                 ("did_cancel", C.POINTER(C.c_int32))]
+
+
+class QueryFilters(C.Structure):
+    """hny_query_filters; struct_size is the guard (the struct is not part of hny_abi_sizes)"""
+    _fields_ = [("struct_size", C.c_uint32), ("n_filters", C.c_uint32), ("offsets", C.c_void_p),
+                ("ids", C.c_void_p), ("filter_of", C.c_void_p)]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_size = C.sizeof(QueryFilters)
+
+    @classmethod
+    def pack(cls, filters, filter_of):
+        """`filters`: a list of id arrays; `filter_of`: one int per query, -1 or NNS_FILTER_NONE = none.
+        Returns (struct, arrays the struct points into)"""
+        arrs = [np.ascontiguousarray(f, np.uint32).ravel() for f in filters]
+        offsets = np.zeros(len(arrs) + 1, np.uint64)
+        if arrs:
+            offsets[1:] = np.cumsum([len(a) for a in arrs], dtype=np.uint64)
+        ids = np.concatenate(arrs) if arrs else np.zeros(0, np.uint32)
+        ids = np.ascontiguousarray(ids, np.uint32)
+        fo = np.asarray(filter_of, np.int64).ravel()
+        fo = np.ascontiguousarray(np.where(fo < 0, NNS_FILTER_NONE, fo), np.uint32)
+        s = cls()
+        s.n_filters, s.offsets, s.filter_of = len(arrs), _p(offsets).value, _p(fo).value
+        s.ids = _p(ids).value if len(ids) else None
+        return s, (offsets, ids, fo)
 
 
 class HannoyError(RuntimeError):
@@ -273,6 +302,12 @@ def load_library():
     L.hny_builder_exact_knn.argtypes = [vp, C.POINTER(QueryOpts), C.c_uint64, vp, C.c_size_t, vp, vp, vp, vp, vp]
     L.hny_builder_exact_knn_f32.restype = C.c_int
     L.hny_builder_exact_knn_f32.argtypes = [vp, C.POINTER(QueryOpts), C.c_uint64, vp, C.c_size_t, vp, vp, vp]
+    L.hny_builder_nns_filtered.restype = C.c_int
+    L.hny_builder_nns_filtered.argtypes = [vp, C.POINTER(QueryOpts), C.POINTER(QueryFilters), C.c_uint64, vp, C.c_size_t,
+                                           vp, vp, vp, vp, vp]
+    L.hny_builder_nns_filtered_f32.restype = C.c_int
+    L.hny_builder_nns_filtered_f32.argtypes = [vp, C.POINTER(QueryOpts), C.POINTER(QueryFilters), C.c_uint64, vp,
+                                               C.c_size_t, vp, vp, vp]
     L.hny_builder_create_update.restype = C.c_int
     L.hny_builder_create_update.argtypes = [vp, C.POINTER(Update), C.POINTER(vp)]
     L.hny_builder_update.restype = C.c_int
@@ -1109,6 +1144,50 @@ class Builder:
         else:
             _check(load_library().hny_builder_nns(self._h, C.byref(qo), nq, qc, qs, qh, qi, _p(ids), _p(dists),
                                                   _p(counts)))
+        self.did_cancel = bool(flag.value)
+        return ids, dists, counts
+
+    def nns_filtered_f32(self, queries, filters, filter_of, **kw):
+        """nns_filtered(by_vector) with f32 queries, encoded on the device"""
+        return self.nns_filtered(filters, filter_of, qf32=_f32_rows(queries), **kw)
+
+    def nns_filtered(self, filters, filter_of, qcodes=None, qheaders=None, k=10, ef_search=100, query_items=None,
+                     linear_below=1000, linear_below_ratio=1.0, cancel=None, qf32=None):
+        """hny_builder_nns_filtered: nns with one .candidates() filter per query.  `filters` is a list of id arrays,
+        `filter_of[i]` the filter of query i (-1 or NNS_FILTER_NONE: none).  The rows of the queries of one filter
+        equal nns(candidates=that filter) on those queries alone."""
+        qo = QueryOpts()
+        qo.k, qo.ef_search = k, ef_search
+        flag = C.c_int32(0)
+        if cancel is not None:
+            fn = CANCEL_FN(lambda _ctx: 1 if cancel() else 0)
+            qo.cancel = fn
+            qo.did_cancel = C.pointer(flag)
+        self._cancel_flag = flag
+        qo.linear_below, qo.linear_below_ratio = linear_below, linear_below_ratio
+        qf, _keep = QueryFilters.pack(filters, filter_of)
+        if query_items is not None:
+            query_items = np.ascontiguousarray(query_items, np.uint32)
+            nq, qc, qs, qh, qi = len(query_items), None, 0, None, _p(query_items)
+        elif qf32 is not None:
+            nq, qc, qh, qi = qf32.shape[0], _p(qf32), None, None
+            qs = qf32.strides[0] if nq > 1 else qf32.shape[1] * 4
+        else:
+            qcodes = np.ascontiguousarray(qcodes, np.uint8)
+            qheaders = np.ascontiguousarray(qheaders, np.uint8)
+            nq, qc, qs, qh, qi = qcodes.shape[0], _p(qcodes), qcodes.shape[1], _p(qheaders), None
+        if len(_keep[2]) != nq:
+            raise ValueError(f"filter_of has {len(_keep[2])} entries for {nq} queries")
+        ids = np.zeros((nq, k), np.uint32)
+        dists = np.zeros((nq, k), np.float32)
+        counts = np.zeros(nq, np.uint32)
+        L = load_library()
+        if qf32 is not None:
+            _check(L.hny_builder_nns_filtered_f32(self._h, C.byref(qo), C.byref(qf), nq, qc, qs, _p(ids), _p(dists),
+                                                  _p(counts)))
+        else:
+            _check(L.hny_builder_nns_filtered(self._h, C.byref(qo), C.byref(qf), nq, qc, qs, qh, qi, _p(ids), _p(dists),
+                                              _p(counts)))
         self.did_cancel = bool(flag.value)
         return ids, dists, counts
 

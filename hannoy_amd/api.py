@@ -491,6 +491,7 @@ class QueryBuilder:
         self._ef, self._candidates = 100, None          # reader.rs:23, 614
         self._linear_below, self._ratio = 1000, 1.0     # reader.rs:28, 31
         self._exact = False
+        self._per_query = None
 
     def ef_search(self, ef):
         self._ef = int(ef)
@@ -499,6 +500,32 @@ class QueryBuilder:
     def candidates(self, ids):
         self._candidates = np.ascontiguousarray(list(ids) if not isinstance(ids, np.ndarray) else ids, np.uint32)
         return self
+
+    def candidates_per_query(self, filters):
+        """one `.candidates()` per query of by_vectors / by_items (hny_builder_nns_filtered): a list with an id
+        array, or None for no filter, for every query.  The same array object given for several queries is one
+        filter.  Each query is answered as if it were searched alone with its own filter"""
+        self._per_query = list(filters)
+        return self
+
+    def _filters(self, nq):
+        """the distinct filters (by object identity) and every query's index among them, -1 = none"""
+        if len(self._per_query) != nq:
+            raise ValueError(f"candidates_per_query has {len(self._per_query)} entries for {nq} queries")
+        if self._candidates is not None or self._exact:
+            raise ValueError("candidates_per_query goes with neither candidates() nor exact()")
+        index, filters, filter_of = {}, [], np.full(nq, -1, np.int64)
+        for i, c in enumerate(self._per_query):
+            if c is None:
+                continue
+            if id(c) not in index:
+                index[id(c)] = len(filters)
+                filters.append(np.ascontiguousarray(list(c) if not isinstance(c, np.ndarray) else c, np.uint32))
+            filter_of[i] = index[id(c)]
+        return filters, filter_of
+
+    def _kw_filtered(self):
+        return dict(k=self.count, ef_search=self._ef, linear_below=self._linear_below, linear_below_ratio=self._ratio)
 
     def linear_below(self, threshold):
         self._linear_below = int(threshold)
@@ -525,12 +552,20 @@ class QueryBuilder:
         q = np.ascontiguousarray(vectors, np.float32)
         if q.ndim != 2 or q.shape[1] != r.dimensions:
             raise InvalidVecDimension(f"expected {r.dimensions}, received {q.shape[-1]}")
+        if self._per_query is not None:
+            filters, filter_of = self._filters(len(q))
+            return r._b.nns_filtered_f32(q, filters, filter_of, cancel=cancel, **self._kw_filtered())
         if self._exact:
             return r._b.exact_knn_f32(q, k=self.count, candidates=self._candidates, cancel=cancel)
         return r._b.nns_f32(q, cancel=cancel, **self._kw())  # encoded on the device
 
     def by_items(self, items, cancel=None):
         """batched by_item; counts == capi.NNS_NONE where the reference returns None"""
+        if self._per_query is not None:
+            items = np.ascontiguousarray(items, np.uint32)
+            filters, filter_of = self._filters(len(items))
+            return self.reader._b.nns_filtered(filters, filter_of, query_items=items, cancel=cancel,
+                                               **self._kw_filtered())
         if self._exact:
             return self.reader._b.exact_knn(query_items=np.ascontiguousarray(items, np.uint32), k=self.count,
                                             candidates=self._candidates, cancel=cancel)

@@ -3018,10 +3018,17 @@ struct QuerySet {
   bool live(uint32_t s) const { return !b->incremental || !b->deleted[s]; }
   // the slot of a live item, -1 for an unknown or deleted one
   int64_t live_slot(uint32_t id) const {
+    if (b->n && b->ids[b->n - 1] == b->n - 1) // ids ascending and distinct: they are 0 .. n - 1, slot == id
+      return id < b->n && live(id) ? (int64_t)id : -1;
     auto it = std::lower_bound(b->ids.begin(), b->ids.end(), id);
     if (it == b->ids.end() || *it != id) return -1;
     uint32_t s = (uint32_t)(it - b->ids.begin());
     return live(s) ? (int64_t)s : -1;
+  }
+  uint64_t n_live() const {
+    uint64_t c = 0;
+    for (uint32_t s = 0; s < b->n; s++) c += live(s) ? 1 : 0;
+    return c;
   }
   // candidates ∩ item_ids (every live item without a filter) as a mask over slots; returns how many
   uint64_t slot_mask(const hny_query_opts *qo, std::vector<u32> &mask) const {
@@ -3332,93 +3339,55 @@ static int search_knn_impl(hny_builder *b, uint64_t nq, const void *qvectors, si
   return search_end(b, qo, sc);
 }
 
-// QueryBuilder with .candidates() and/or by_item (reader.rs:60-262, 621-711, 809-896)
-int hny_builder_nns(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const void *qvectors,
-                    size_t qstride, const void *qheaders, const uint32_t *query_items, uint32_t *out_ids,
-                    float *out_dists, uint32_t *out_counts) {
-  return nns_impl(b, qo, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists, out_counts, false);
-}
-
-int hny_builder_nns_f32(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const float *queries, size_t qstride,
-                        uint32_t *out_ids, float *out_dists, uint32_t *out_counts) {
-  if (!queries) return fail(HNY_ERR_INVALID_ARG, "no queries");
-  return nns_impl(b, qo, nq, queries, qstride, nullptr, nullptr, out_ids, out_dists, out_counts, false, true);
-}
-
-static int nns_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const void *qvectors, size_t qstride,
-                    const void *qheaders, const uint32_t *query_items, uint32_t *out_ids, float *out_dists,
-                    uint32_t *out_counts, bool force_heap, bool q_f32) {
-  if (int rc = check_search_outputs(b, out_ids, out_dists, out_counts, qo ? qo->k : 0)) return rc;
-  const bool by_item = query_items != nullptr;
-  const uint32_t k = qo->k, NONE = HNY_NNS_NONE;
-  const QuerySet qs{b, nq, qvectors, qstride, qheaders, query_items, q_f32, by_item, k, out_ids, out_dists, out_counts};
-  if (int rc = check_query_source(qs, "no queries")) return rc;
-  if (int rc = check_query_rows(qs)) return rc; // here the f32 rows come before the candidates, in exact_impl after
-  if (int rc = check_candidates(qo)) return rc;
-  if (!(qo->linear_below_ratio >= 0.f && qo->linear_below_ratio <= 1.f)) // reader.rs:253-256
-    return fail(HNY_ERR_INVALID_ARG, "linear scan threshold ratio must be between 0.0 and 1.0");
-  if (!qo->has_candidates && !by_item && !force_heap)
-    return search_knn_impl(b, nq, qvectors, qstride, qheaders, k, qo->ef_search, out_ids, out_dists, out_counts, qo,
-                           q_f32);
-  if (int rc = check_build_finished(b)) return rc;
-  uint32_t ef;
-  if (int rc = check_ef(qo->ef_search, k, &ef)) return rc;
-  // k_nns keeps its result set in LDS (up to 4 096 entries); beyond that the same search runs with `res` as a
-  // heap in HBM next to the search queue's
-  // ... and so does a search that starts from more entry points than the LDS set holds (every entry point is pushed
-  // to `res` without a capacity check, reader.rs:755-761: an all-level-0 index of 4 096 - 8 192 items)
+// k_nns keeps its result set in LDS (up to 4 096 entries); beyond that the same search runs with `res` as a
+// heap in HBM next to the search queue's
+// ... and so does a search that starts from more entry points than the LDS set holds (every entry point is pushed
+// to `res` without a capacity check, reader.rs:755-761: an all-level-0 index of 4 096 - 8 192 items)
+static bool nns_res_in_hbm(const hny_builder *b, uint32_t ef) {
   const uint64_t eps_need = std::max<uint64_t>(b->entry_points.size(), b->entry_points.size() > 1 ? b->top_layer_nodes : 0) + 1;
-  const bool big = ef + 1 > HNY_RES_LDS_MAX || eps_need > HNY_RES_LDS_MAX;
-  HIP_TRY(hipSetDevice(b->device));
-  const uint32_t n = b->n;
-  uint64_t n_items = 0;
-  for (uint32_t s = 0; s < n; s++) n_items += qs.live(s) ? 1 : 0;
-  std::vector<u32> mask, cand_slots; // the filter, and its slots in ascending order
-  if (qo->has_candidates) {
-    cand_slots.reserve(qs.slot_mask(qo, mask));
-    for (uint32_t s = 0; s < n; s++)
-      if (mask_has(mask, s)) cand_slots.push_back(s);
-  }
-  if (n_items == 0 || (qo->has_candidates && cand_slots.empty())) return qs.none_found();
-  // should_linear_scan, reader.rs:621-640
-  bool linear = false;
-  if (qo->has_candidates) {
-    const uint64_t cl = cand_slots.size();
-    linear = cl < (uint64_t)qo->linear_below && (float)cl / (float)n_items <= qo->linear_below_ratio;
-  }
-  if (int rc = ensure_finalized(b, b->stream)) return rc; // Reader::visit iterates Links bitmaps: ascending, deduplicated
+  return ef + 1 > HNY_RES_LDS_MAX || eps_need > HNY_RES_LDS_MAX;
+}
+// brute_force_search ranks in LDS: the capacity of a scan that returns up to `hits` hits, 0 = beyond the LDS
+static uint32_t linear_rcap(uint64_t hits) {
+  if (hits + 1 > HNY_RES_LDS_MAX) return 0;
+  uint32_t rcap = 64;
+  while (rcap < hits + 1) rcap *= 2;
+  return rcap;
+}
+
+// where the launches of nns_run read their candidates from
+struct NnsFilters {
+  const u32 *masks = nullptr;     // the call's bitset over slots, or one per filter, mask_stride words apart
+  const u32 *cand_slots = nullptr; // linear scan: the call's slots, ascending, or those of every linear filter (cs_off)
+  u32 n_cand_slots = 0;
+  // one filter per query (nns_filtered_impl), else null
+  const u32 *filter_of = nullptr;  // host, one entry per query of the QuerySet: its filter, HNY_SENT = none
+  u32 mask_stride = 0;
+  const u64 *cs_off = nullptr;     // device, the linear filters' ranges of cand_slots
+};
+
+// The chunk loop of nns_impl and nns_filtered_impl: the queries of `qs` on k_nns_linear (linear), on k_nns with
+// `res` as a heap in HBM (big), or on k_nns with the small search-queue heaps and a retry on full ones.
+static int nns_run(hny_builder *b, const hny_query_opts *qo, const QuerySet &qs, const NnsFilters &F, bool linear,
+                   bool big, uint32_t ef, uint32_t rcap, SearchCancel &sc) {
   const GraphDev sg = search_graph(b);
-  uint32_t rcap = res_capacity(ef, (uint32_t)b->entry_points.size(), b->n, b->top_layer_nodes,
-                               big ? HNY_RES_GLOBAL_MAX : HNY_RES_LDS_MAX);
-  if (big && linear) { // brute_force_search ranks in LDS: it returns min(k, candidates) hits
-    const uint64_t need = std::min<uint64_t>(k, cand_slots.size()) + 1;
-    if (need > HNY_RES_LDS_MAX)
-      return fail(HNY_ERR_UNSUPPORTED, "linear scan for %u hits among %zu candidates: at most %u (lower linear_below)", k,
-                  cand_slots.size(), HNY_RES_LDS_MAX - 1);
-    rcap = 64;
-    while (rcap < need) rcap *= 2;
-  }
-  if (int rc = check_query_stride(qs)) return rc;
+  const uint64_t nq = qs.nq;
+  const uint32_t n = b->n, k = qs.k, NONE = HNY_NNS_NONE;
+  const bool by_item = qs.by_item;
+  const uint32_t *query_items = qs.query_items;
+  uint32_t *out_counts = qs.out_counts;
   const uint32_t chunk = search_chunk(b, nq, rcap, k);
   QueryStage st{b, qs};
   TopkOut top{b, qs, k};
   DevBuf<u64> dcand, dheap;
-  DevBuf<u32> dcn, dstatus, dmembers, dfilter, dcslots;
+  DevBuf<u32> dcn, dstatus, dmembers, dfof;
   if (int rc = st.alloc(chunk)) return rc;
   HIP_TRY(dcand.alloc((size_t)chunk * rcap));
   if (int rc = top.alloc(chunk)) return rc;
   HIP_TRY(dcn.alloc(chunk));
   HIP_TRY(dstatus.alloc(chunk));
   HIP_TRY(dmembers.alloc(chunk));
-  if (qo->has_candidates) {
-    HIP_TRY(dfilter.alloc(mask.size()));
-    HIP_TRY(hipMemcpyAsync(dfilter.p, mask.data(), mask.size() * 4, hipMemcpyHostToDevice, b->stream));
-    if (linear) {
-      HIP_TRY(dcslots.alloc(cand_slots.size()));
-      HIP_TRY(hipMemcpyAsync(dcslots.p, cand_slots.data(), cand_slots.size() * 4, hipMemcpyHostToDevice,
-                             b->stream));
-    }
-  }
+  if (F.filter_of) HIP_TRY(dfof.alloc(chunk));
   // search queue heaps: a modest one per resident wave first; queries that outgrow it run again
   // with room for every item (the queue never holds more than the visited set)
   const uint32_t heap_small = (uint32_t)std::min<uint64_t>((uint64_t)n + 1, 16384);
@@ -3439,8 +3408,6 @@ static int nns_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const
   uint32_t grid_full = 0;
   std::vector<u32> hst(chunk);
   u32 *queues = b->d_nseg.p + 4;
-  SearchCancel sc; // hny_query_opts.cancel
-  HIP_TRY(sc.begin(qo));
   for (uint64_t q0 = 0; q0 < nq; q0 += chunk) {
     const uint32_t cnt = (uint32_t)std::min<uint64_t>(chunk, nq - q0);
     if (sc.probe()) { // nothing of this chunk is started: 0 hits each (unknown items stay None)
@@ -3459,7 +3426,13 @@ static int nns_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const
     a.q_stride = b->g.row_stride;
     a.members = dmembers.p;
     a.n_members = n_mem;
-    a.filter = qo->has_candidates ? dfilter.p : nullptr;
+    a.filter = F.masks;
+    if (F.filter_of) { // one filter per query: the chunk's own indices, next to its rows
+      HIP_TRY(hipMemcpyAsync(dfof.p, F.filter_of + q0, (size_t)cnt * 4, hipMemcpyHostToDevice, b->stream));
+      a.filter_of = dfof.p;
+      a.mask_stride = F.mask_stride;
+      a.cs_off = F.cs_off;
+    }
     a.by_item = by_item ? 1 : 0;
     a.k = k;
     a.ef_main = ef;
@@ -3477,8 +3450,8 @@ static int nns_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const
     a.eps_cap = eps_cap_of(b);
     a.queue = queues;
     a.status = dstatus.p;
-    a.cand_slots = dcslots.p;
-    a.n_cand_slots = (u32)cand_slots.size();
+    a.cand_slots = F.cand_slots;
+    a.n_cand_slots = F.n_cand_slots;
     a.cancel = sc.d;
     if (sc.d) HIP_TRY(hnyk_fill_u32(dstatus.p, 2u, cnt, b->stream)); // 2 = never started
     HIP_TRY(hipMemsetAsync(queues, 0, 8 * 4, b->stream));
@@ -3527,7 +3500,368 @@ static int nns_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const
       top.emit(i, q0 + i);
     }
   }
+  return HNY_OK;
+}
+
+// QueryBuilder with .candidates() and/or by_item (reader.rs:60-262, 621-711, 809-896)
+int hny_builder_nns(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const void *qvectors,
+                    size_t qstride, const void *qheaders, const uint32_t *query_items, uint32_t *out_ids,
+                    float *out_dists, uint32_t *out_counts) {
+  return nns_impl(b, qo, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists, out_counts, false);
+}
+
+int hny_builder_nns_f32(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const float *queries, size_t qstride,
+                        uint32_t *out_ids, float *out_dists, uint32_t *out_counts) {
+  if (!queries) return fail(HNY_ERR_INVALID_ARG, "no queries");
+  return nns_impl(b, qo, nq, queries, qstride, nullptr, nullptr, out_ids, out_dists, out_counts, false, true);
+}
+
+static int nns_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const void *qvectors, size_t qstride,
+                    const void *qheaders, const uint32_t *query_items, uint32_t *out_ids, float *out_dists,
+                    uint32_t *out_counts, bool force_heap, bool q_f32) {
+  if (int rc = check_search_outputs(b, out_ids, out_dists, out_counts, qo ? qo->k : 0)) return rc;
+  const bool by_item = query_items != nullptr;
+  const uint32_t k = qo->k;
+  const QuerySet qs{b, nq, qvectors, qstride, qheaders, query_items, q_f32, by_item, k, out_ids, out_dists, out_counts};
+  if (int rc = check_query_source(qs, "no queries")) return rc;
+  if (int rc = check_query_rows(qs)) return rc; // here the f32 rows come before the candidates, in exact_impl after
+  if (int rc = check_candidates(qo)) return rc;
+  if (!(qo->linear_below_ratio >= 0.f && qo->linear_below_ratio <= 1.f)) // reader.rs:253-256
+    return fail(HNY_ERR_INVALID_ARG, "linear scan threshold ratio must be between 0.0 and 1.0");
+  if (!qo->has_candidates && !by_item && !force_heap)
+    return search_knn_impl(b, nq, qvectors, qstride, qheaders, k, qo->ef_search, out_ids, out_dists, out_counts, qo,
+                           q_f32);
+  if (int rc = check_build_finished(b)) return rc;
+  uint32_t ef;
+  if (int rc = check_ef(qo->ef_search, k, &ef)) return rc;
+  const bool big = nns_res_in_hbm(b, ef);
+  HIP_TRY(hipSetDevice(b->device));
+  const uint32_t n = b->n;
+  const uint64_t n_items = qs.n_live();
+  std::vector<u32> mask, cand_slots; // the filter, and its slots in ascending order
+  if (qo->has_candidates) {
+    cand_slots.reserve(qs.slot_mask(qo, mask));
+    for (uint32_t s = 0; s < n; s++)
+      if (mask_has(mask, s)) cand_slots.push_back(s);
+  }
+  if (n_items == 0 || (qo->has_candidates && cand_slots.empty())) return qs.none_found();
+  // should_linear_scan, reader.rs:621-640
+  bool linear = false;
+  if (qo->has_candidates) {
+    const uint64_t cl = cand_slots.size();
+    linear = cl < (uint64_t)qo->linear_below && (float)cl / (float)n_items <= qo->linear_below_ratio;
+  }
+  if (int rc = ensure_finalized(b, b->stream)) return rc; // Reader::visit iterates Links bitmaps: ascending, deduplicated
+  uint32_t rcap = res_capacity(ef, (uint32_t)b->entry_points.size(), b->n, b->top_layer_nodes,
+                               big ? HNY_RES_GLOBAL_MAX : HNY_RES_LDS_MAX);
+  if (big && linear) { // it returns min(k, candidates) hits
+    if (!(rcap = linear_rcap(std::min<uint64_t>(k, cand_slots.size()))))
+      return fail(HNY_ERR_UNSUPPORTED, "linear scan for %u hits among %zu candidates: at most %u (lower linear_below)", k,
+                  cand_slots.size(), HNY_RES_LDS_MAX - 1);
+  }
+  if (int rc = check_query_stride(qs)) return rc;
+  DevBuf<u32> dfilter, dcslots;
+  NnsFilters F;
+  if (qo->has_candidates) {
+    HIP_TRY(dfilter.alloc(mask.size()));
+    HIP_TRY(hipMemcpyAsync(dfilter.p, mask.data(), mask.size() * 4, hipMemcpyHostToDevice, b->stream));
+    F.masks = dfilter.p;
+    if (linear) {
+      HIP_TRY(dcslots.alloc(cand_slots.size()));
+      HIP_TRY(hipMemcpyAsync(dcslots.p, cand_slots.data(), cand_slots.size() * 4, hipMemcpyHostToDevice,
+                             b->stream));
+      F.cand_slots = dcslots.p;
+    }
+    F.n_cand_slots = (u32)cand_slots.size();
+  }
+  SearchCancel sc; // hny_query_opts.cancel
+  HIP_TRY(sc.begin(qo));
+  if (int rc = nns_run(b, qo, qs, F, linear, big, ef, rcap, sc)) return rc;
   return search_end(b, qo, sc);
+}
+
+// ---------------------------------------------------------------------------------------------
+// One candidates filter per query.  The rows of the queries of one filter are those of nns_impl on
+// these queries alone with that filter; here the filters become bitsets on the device (hnyk_filter_masks), each
+// decides should_linear_scan from its own count, and the queries run as three classes through the launches the
+// other searchers use: without a filter by vector (search_knn_impl), linear (k_nns_linear) and walked (k_nns).
+// ---------------------------------------------------------------------------------------------
+#define HNY_FILTER_MASK_BYTES ((uint64_t)1 << 30) // filter bitsets on the device at a time
+static uint64_t filter_mask_budget() {
+  const char *e = getenv("HNY_FILTER_MASK_BYTES"); // test hook, read per call: several rounds on a small index
+  const uint64_t v = e ? strtoull(e, nullptr, 10) : 0;
+  return v ? v : HNY_FILTER_MASK_BYTES;
+}
+
+// some of a call's queries, gathered so that the shared steps see them as a call of their own
+struct SubBatch {
+  const QuerySet &q;
+  std::vector<uint64_t> idx; // the caller's query of each row
+  std::vector<u32> filter_of;
+  std::vector<unsigned char> rows, hdrs;
+  std::vector<uint32_t> items, ids, counts;
+  std::vector<float> dists;
+
+  void add(uint64_t qi, u32 f) {
+    idx.push_back(qi);
+    filter_of.push_back(f);
+  }
+  QuerySet gather() {
+    const hny_builder *b = q.b;
+    const size_t m = idx.size(), hb = hdr_bytes(b->o.metric);
+    const size_t rb = q.q_f32 ? (size_t)b->o.dim * 4 : vec_bytes(b->o.metric, b->o.dim);
+    if (q.by_item) {
+      items.resize(m);
+      for (size_t j = 0; j < m; j++) items[j] = q.query_items[idx[j]];
+    } else {
+      rows.resize(m * rb);
+      hdrs.resize(std::max<size_t>(m * hb, 1));
+      for (size_t j = 0; j < m; j++) {
+        memcpy(&rows[j * rb], (const unsigned char *)q.qvectors + idx[j] * q.qstride, rb);
+        if (!q.q_f32 && hb) memcpy(&hdrs[j * hb], (const unsigned char *)q.qheaders + idx[j] * hb, hb);
+      }
+    }
+    ids.resize(m * q.k);
+    dists.resize(m * q.k);
+    counts.assign(m, 0u);
+    return QuerySet{b, m, rows.data(), rb, hdrs.data(), q.by_item ? items.data() : nullptr, q.q_f32, q.by_item, q.k,
+                    ids.data(), dists.data(), counts.data()};
+  }
+  // the hits to the caller's rows; like the searchers, only the first `count` entries of a row are written
+  void scatter() const {
+    for (size_t j = 0; j < idx.size(); j++) {
+      const uint32_t c = counts[j];
+      q.out_counts[idx[j]] = c;
+      if (c == HNY_NNS_NONE) continue;
+      memcpy(&q.out_ids[idx[j] * q.k], &ids[j * q.k], (size_t)c * 4);
+      memcpy(&q.out_dists[idx[j] * q.k], &dists[j * q.k], (size_t)c * 4);
+    }
+  }
+};
+
+// the bitsets of some filters on the device and how many live candidates each holds
+struct FilterMasks {
+  hny_builder *b;
+  const QuerySet &q;
+  const hny_query_filters *fl;
+  u32 stride; // words per bitset
+  DevBuf<u32> dmasks, dslots, dcount;
+  DevBuf<u64> doff;
+  std::vector<u32> count;
+
+  // filters used[r0 .. r1): ids -> live slots (unknown and deleted ids drop out, duplicates stay), CSR upload,
+  // bits set and counted on the device, the counts back in one copy
+  int build(const std::vector<u32> &used, size_t r0, size_t r1) {
+    const size_t nf = r1 - r0;
+    std::vector<u64> off(nf + 1, 0);
+    std::vector<u32> slots;
+    for (size_t j = 0; j < nf; j++) {
+      const u32 f = used[r0 + j];
+      for (uint64_t i = fl->offsets[f]; i < fl->offsets[f + 1]; i++) {
+        const int64_t sl = q.live_slot(fl->ids[i]);
+        if (sl >= 0) slots.push_back((u32)sl);
+      }
+      off[j + 1] = slots.size();
+    }
+    HIP_TRY(dmasks.alloc(nf * stride));
+    HIP_TRY(dcount.alloc(nf));
+    HIP_TRY(doff.alloc(nf + 1));
+    HIP_TRY(dslots.alloc(slots.size()));
+    HIP_TRY(hipMemsetAsync(dmasks.p, 0, nf * stride * 4, b->stream));
+    HIP_TRY(hipMemsetAsync(dcount.p, 0, nf * 4, b->stream));
+    HIP_TRY(hipMemcpyAsync(doff.p, off.data(), (nf + 1) * 8, hipMemcpyHostToDevice, b->stream));
+    if (!slots.empty())
+      HIP_TRY(hipMemcpyAsync(dslots.p, slots.data(), slots.size() * 4, hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hnyk_filter_masks(dmasks.p, stride, doff.p, dslots.p, (u32)nf, slots.size(), dcount.p, b->stream));
+    count.resize(nf);
+    HIP_TRY(hipMemcpyAsync(count.data(), dcount.p, nf * 4, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream)); // (`off` and `slots` leave scope)
+    return HNY_OK;
+  }
+};
+
+static int nns_filtered_impl(hny_builder *b, const hny_query_opts *qo, const hny_query_filters *fl, uint64_t nq,
+                             const void *qvectors, size_t qstride, const void *qheaders, const uint32_t *query_items,
+                             uint32_t *out_ids, float *out_dists, uint32_t *out_counts, bool q_f32) {
+  if (int rc = check_search_outputs(b, out_ids, out_dists, out_counts, qo ? qo->k : 0)) return rc;
+  if (!fl) return fail(HNY_ERR_INVALID_ARG, "no filters");
+  if (fl->struct_size != sizeof(hny_query_filters))
+    return fail(HNY_ERR_INVALID_ARG, "hny_query_filters.struct_size %u: this library has %zu", fl->struct_size,
+                sizeof(hny_query_filters));
+  if (qo->has_candidates)
+    return fail(HNY_ERR_INVALID_ARG, "opts->has_candidates must be 0: the candidates are in hny_query_filters");
+  if (!fl->offsets || (nq && !fl->filter_of)) return fail(HNY_ERR_INVALID_ARG, "filter offsets or filter_of missing");
+  const uint32_t n_filters = fl->n_filters, NONE = HNY_NNS_NONE;
+  if (fl->offsets[0] != 0) return fail(HNY_ERR_INVALID_ARG, "filter offsets must start at 0");
+  for (uint32_t f = 0; f < n_filters; f++)
+    if (fl->offsets[f + 1] < fl->offsets[f]) return fail(HNY_ERR_INVALID_ARG, "filter offsets decrease at filter %u", f);
+  if (fl->offsets[n_filters] && !fl->ids) return fail(HNY_ERR_INVALID_ARG, "filter ids missing");
+  for (uint64_t i = 0; i < nq; i++)
+    if (fl->filter_of[i] != HNY_FILTER_NONE && fl->filter_of[i] >= n_filters)
+      return fail(HNY_ERR_INVALID_ARG, "query %llu: filter %u of %u", (unsigned long long)i, fl->filter_of[i], n_filters);
+  const bool by_item = query_items != nullptr;
+  const uint32_t k = qo->k;
+  const QuerySet qs{b, nq, qvectors, qstride, qheaders, query_items, q_f32, by_item, k, out_ids, out_dists, out_counts};
+  if (int rc = check_query_source(qs, "no queries")) return rc;
+  if (int rc = check_query_rows(qs)) return rc;
+  if (!(qo->linear_below_ratio >= 0.f && qo->linear_below_ratio <= 1.f)) // reader.rs:253-256
+    return fail(HNY_ERR_INVALID_ARG, "linear scan threshold ratio must be between 0.0 and 1.0");
+  if (int rc = check_build_finished(b)) return rc;
+  uint32_t ef;
+  if (int rc = check_ef(qo->ef_search, k, &ef)) return rc;
+  if (int rc = check_query_stride(qs)) return rc;
+  const bool big = nns_res_in_hbm(b, ef);
+  HIP_TRY(hipSetDevice(b->device));
+  const uint64_t n_items = qs.n_live();
+
+  // the filters that queries use, ascending, and their queries in filter order
+  std::vector<u32> used;
+  {
+    std::vector<unsigned char> seen(n_filters, 0);
+    for (uint64_t i = 0; i < nq; i++)
+      if (fl->filter_of[i] != HNY_FILTER_NONE) seen[fl->filter_of[i]] = 1;
+    for (uint32_t f = 0; f < n_filters; f++)
+      if (seen[f]) used.push_back(f);
+  }
+  std::vector<uint64_t> by_filter;
+  for (uint64_t i = 0; i < nq; i++)
+    if (fl->filter_of[i] != HNY_FILTER_NONE) by_filter.push_back(i);
+  std::stable_sort(by_filter.begin(), by_filter.end(),
+                   [&](uint64_t x, uint64_t y) { return fl->filter_of[x] < fl->filter_of[y]; });
+  // rounds of as many bitsets as the budget holds (one always fits: n < 2^31 slots are 256 MB)
+  FilterMasks fm{b, qs, fl, (u32)((((size_t)b->n + 31) / 32 + 4) & ~(size_t)3)};
+  const size_t per_round = (size_t)std::max<uint64_t>(1, filter_mask_budget() / ((uint64_t)fm.stride * 4));
+  const size_t n_rounds = n_items ? (used.size() + per_round - 1) / per_round : 0;
+  auto is_linear = [&](u32 cl) { // should_linear_scan, reader.rs:621-640
+    return (uint64_t)cl < (uint64_t)qo->linear_below && (float)cl / (float)n_items <= qo->linear_below_ratio;
+  };
+  // the refusal: no query has been searched yet
+  auto check_round = [&](size_t r) -> int {
+    for (size_t j = 0; big && j < fm.count.size(); j++)
+      if (is_linear(fm.count[j]) && !linear_rcap(std::min<uint64_t>(k, fm.count[j])))
+        return fail(HNY_ERR_UNSUPPORTED,
+                    "filter %u: linear scan for %u hits among %u candidates: at most %u (lower linear_below)",
+                    used[r * per_round + j], k, fm.count[j], HNY_RES_LDS_MAX - 1);
+    return HNY_OK;
+  };
+  size_t built = (size_t)-1;
+  auto build_round = [&](size_t r) -> int {
+    if (built == r) return HNY_OK;
+    built = r;
+    return fm.build(used, r * per_round, std::min(used.size(), (r + 1) * per_round));
+  };
+  if (n_rounds == 1 || (big && (uint64_t)k + 1 > HNY_RES_LDS_MAX)) // several rounds: the counts of all, ahead
+    for (size_t r = 0; r < n_rounds; r++) {
+      if (int rc = build_round(r)) return rc;
+      if (int rc = check_round(r)) return rc;
+    }
+
+  SearchCancel sc;
+  HIP_TRY(sc.begin(qo));
+  if (n_items) {
+    if (int rc = ensure_finalized(b, b->stream)) return rc; // Reader::visit iterates Links bitmaps
+  }
+  const uint32_t rcap_walk = res_capacity(ef, (uint32_t)b->entry_points.size(), b->n, b->top_layer_nodes,
+                                          big ? HNY_RES_GLOBAL_MAX : HNY_RES_LDS_MAX);
+  // 1. without a filter: by vector the plain search on k_walk, by item k_nns with no bitset
+  {
+    SubBatch plain{qs};
+    for (uint64_t i = 0; i < nq; i++)
+      if (fl->filter_of[i] == HNY_FILTER_NONE) plain.add(i, HNY_SENT);
+    if (!plain.idx.empty() && !by_item) {
+      const QuerySet sub = plain.gather();
+      hny_query_opts o2 = *qo;
+      int32_t cancelled = 0;
+      o2.did_cancel = &cancelled;
+      if (int rc = search_knn_impl(b, sub.nq, sub.qvectors, sub.qstride, sub.qheaders, k, qo->ef_search, sub.out_ids,
+                                   sub.out_dists, sub.out_counts, &o2, q_f32))
+        return rc;
+      plain.scatter();
+      if (cancelled && sc.fn) {
+        sc.cancelled = true;
+        __atomic_store_n(sc.h, 1u, __ATOMIC_RELEASE);
+      }
+    } else if (!plain.idx.empty() && n_items == 0) {
+      for (uint64_t qi : plain.idx) out_counts[qi] = NONE;
+    } else if (!plain.idx.empty()) {
+      const QuerySet sub = plain.gather();
+      NnsFilters F;
+      F.filter_of = plain.filter_of.data();
+      if (int rc = nns_run(b, qo, sub, F, false, big, ef, rcap_walk, sc)) return rc;
+      plain.scatter();
+    }
+  }
+  // nothing to search among (reader.rs:652-654 / 822-824)
+  if (n_items == 0)
+    for (uint64_t qi : by_filter) out_counts[qi] = by_item ? NONE : 0u;
+  // 2. round by round: the linear filters' slots compacted on the device, then the linear and the walked queries
+  size_t at = 0;
+  for (size_t r = 0; r < n_rounds; r++) {
+    if (int rc = build_round(r)) return rc;
+    const size_t f0 = r * per_round, nf = fm.count.size();
+    std::vector<u32> lin;
+    std::vector<u64> cs_off(nf + 1, 0);
+    uint64_t most_hits = 0;
+    for (size_t j = 0; j < nf; j++) {
+      const bool linear = fm.count[j] && is_linear(fm.count[j]);
+      if (linear) {
+        lin.push_back((u32)j);
+        most_hits = std::max<uint64_t>(most_hits, std::min<uint64_t>(k, fm.count[j]));
+      }
+      cs_off[j + 1] = cs_off[j] + (linear ? fm.count[j] : 0u);
+    }
+    SubBatch scan{qs}, walk{qs};
+    for (; at < by_filter.size() && fl->filter_of[by_filter[at]] < (r + 1 < n_rounds ? used[f0 + nf] : n_filters); at++) {
+      const uint64_t qi = by_filter[at];
+      const u32 j = (u32)(std::lower_bound(used.begin() + f0, used.begin() + f0 + nf, fl->filter_of[qi]) - used.begin() - f0);
+      if (!fm.count[j]) out_counts[qi] = by_item ? NONE : 0u; // an empty filter: nothing can match
+      else if (cs_off[j + 1] > cs_off[j]) scan.add(qi, j);
+      else walk.add(qi, j);
+    }
+    NnsFilters F;
+    F.masks = fm.dmasks.p;
+    F.mask_stride = fm.stride;
+    DevBuf<u32> dlin, dcs;
+    DevBuf<u64> dcs_off;
+    if (!scan.idx.empty()) {
+      HIP_TRY(dlin.alloc(lin.size()));
+      HIP_TRY(dcs_off.alloc(nf + 1));
+      HIP_TRY(dcs.alloc(cs_off[nf]));
+      HIP_TRY(hipMemcpyAsync(dlin.p, lin.data(), lin.size() * 4, hipMemcpyHostToDevice, b->stream));
+      HIP_TRY(hipMemcpyAsync(dcs_off.p, cs_off.data(), (nf + 1) * 8, hipMemcpyHostToDevice, b->stream));
+      HIP_TRY(hnyk_filter_compact(fm.dmasks.p, fm.stride, dlin.p, (u32)lin.size(), dcs_off.p, dcs.p, b->stream));
+      const QuerySet sub = scan.gather();
+      NnsFilters L = F;
+      L.filter_of = scan.filter_of.data();
+      L.cand_slots = dcs.p;
+      L.cs_off = dcs_off.p;
+      const uint32_t rcap = big ? linear_rcap(most_hits) : rcap_walk; // (check_round has seen to most_hits)
+      if (!rcap) return fail(HNY_ERR_UNSUPPORTED, "linear scan for %u hits: at most %u", k, HNY_RES_LDS_MAX - 1);
+      if (int rc = nns_run(b, qo, sub, L, true, big, ef, rcap, sc)) return rc;
+      scan.scatter();
+    }
+    if (!walk.idx.empty()) {
+      const QuerySet sub = walk.gather();
+      F.filter_of = walk.filter_of.data();
+      if (int rc = nns_run(b, qo, sub, F, false, big, ef, rcap_walk, sc)) return rc;
+      walk.scatter();
+    }
+  }
+  return search_end(b, qo, sc);
+}
+
+int hny_builder_nns_filtered(hny_builder *b, const hny_query_opts *qo, const hny_query_filters *filters, uint64_t nq,
+                             const void *qvectors, size_t qstride, const void *qheaders, const uint32_t *query_items,
+                             uint32_t *out_ids, float *out_dists, uint32_t *out_counts) {
+  return nns_filtered_impl(b, qo, filters, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists, out_counts,
+                           false);
+}
+
+int hny_builder_nns_filtered_f32(hny_builder *b, const hny_query_opts *qo, const hny_query_filters *filters,
+                                 uint64_t nq, const float *queries, size_t qstride, uint32_t *out_ids,
+                                 float *out_dists, uint32_t *out_counts) {
+  if (!queries) return fail(HNY_ERR_INVALID_ARG, "no queries");
+  return nns_filtered_impl(b, qo, filters, nq, queries, qstride, nullptr, nullptr, out_ids, out_dists, out_counts, true);
 }
 
 // ---------------------------------------------------------------------------------------------

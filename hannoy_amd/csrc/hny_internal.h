@@ -180,6 +180,12 @@ struct NnsArgs {
   // cancellation (reader.rs:333): a host word (pinned, mapped) the work-queue loop polls; non-zero =
   // take no further query.  status[] == 2 marks the queries that were never started.
   const u32 *cancel;
+  // one candidates filter per query (hny_builder_nns_filtered); null = the call-wide fields above.
+  // filter_of[m]: query m's filter, HNY_SENT = none.  k_nns: `filter` then holds one bitset per filter, mask_stride
+  // words apart.  k_nns_linear: filter f's slots are cand_slots[cs_off[f] .. cs_off[f + 1])
+  const u32 *filter_of;
+  u32 mask_stride;
+  const u64 *cs_off;
 };
 
 struct PruneArgs {
@@ -236,6 +242,13 @@ hipError_t hnyk_prune(const GraphDev &g, const PruneArgs &a, LaunchShape s, int 
 // a.heap_r set: `res` as a heap in HBM too (result sets beyond the LDS), else the sorted LDS array
 hipError_t hnyk_nns(const GraphDev &g, const NnsArgs &a, LaunchShape s, int grid, hipStream_t st);
 hipError_t hnyk_nns_linear(const GraphDev &g, const NnsArgs &a, LaunchShape s, int grid, hipStream_t st);
+// per-query filters: n_filters bitsets over slots, `stride` words apart, from slot lists in CSR form
+// (off[n_filters + 1]); `masks` and `count` must be zero before hnyk_filter_masks, which sets the bits and counts them
+hipError_t hnyk_filter_masks(u32 *masks, u32 stride, const u64 *off, const u32 *slots, u32 n_filters, u64 n_slots,
+                             u32 *count, hipStream_t st);
+// the set slots of the masks lin[0 .. n_lin), ascending, into out[cs_off[f] .. cs_off[f + 1])
+hipError_t hnyk_filter_compact(const u32 *masks, u32 stride, const u32 *lin, u32 n_lin, const u64 *cs_off, u32 *out,
+                               hipStream_t st);
 // exact k-NN (hny_builder_exact_knn): a dense scan of consecutive slots for a tile of queries
 // (k_exact_scores) and the merge of one slab of scores into every query's running top-k list (k_exact_topk)
 #define HNY_EXACT_SLAB 65536u   // slots per slab: the score buffer is query block x slab f32

@@ -2253,6 +2253,14 @@ __device__ __forceinline__ const unsigned char *query_row(const GraphDev &g, con
   return a.q_rows + (size_t)m * a.q_stride;
 }
 
+// query m's candidates bitset: the call-wide one, or with a filter per query (a.filter_of) the one of its own
+// filter, null for a query without .candidates()
+__device__ __forceinline__ const u32 *query_filter(const NnsArgs &a, u32 m) {
+  if (!a.filter_of) return a.filter;
+  const u32 f = uni(a.filter_of[m]);
+  return f == HNY_SENT ? nullptr : a.filter + (size_t)f * a.mask_stride;
+}
+
 // the exhaustive fallback's scan (reader.rs:771-795 / 864-890): the first slot >= pos that is not on `path`
 // (the flushed visited bitset, 64 words at a time), or g.n when there is none
 __device__ __forceinline__ u32 next_unvisited(const GraphDev &g, u32 *bits, u32 pos) {
@@ -2634,6 +2642,7 @@ __global__ __launch_bounds__(64, 4) void k_nns(GraphDev g, NnsArgs a) {
     float qn;
     u32 excl; // by_item: candidates.remove(item), reader.rs:840
     const unsigned char *qrow = query_row(g, a, m, qn, excl);
+    const u32 *filter = query_filter(a, m);
     float4 q[NCH];
     load_row<LPR, NCH>(qrow, t, g.n16, q);
     int n_eps, st = 0;
@@ -2671,11 +2680,11 @@ __global__ __launch_bounds__(64, 4) void k_nns(GraphDev g, NnsArgs a) {
     int res_len = 0;
     auto visit = [&](int ef, int ne) -> int {
       if constexpr (RES_HEAP)
-        return walk_layer_heap<LPR, NCH>(g, q, qn, 0u, ef, eps, ne, C, R, rmin, vis, nb_ids, nb_d, a.filter, excl,
+        return walk_layer_heap<LPR, NCH>(g, q, qn, 0u, ef, eps, ne, C, R, rmin, vis, nb_ids, nb_d, filter, excl,
                                          evals, qrow);
       else
         return visit_filtered<LPR, NCH>(g, q, qn, ef, eps, ne, res, res_len, (int)a.rcap, res_err, vis, nb_ids, nb_d,
-                                        C, a.filter, excl, evals, err_iter, qrow);
+                                        C, filter, excl, evals, err_iter, qrow);
     };
     auto found = [&]() -> u32 { return RES_HEAP ? R.size : (u32)res_len; };
     u64 *row = a.cand + (size_t)m * a.rcap;
@@ -2778,10 +2787,18 @@ __global__ __launch_bounds__(64, 4) void k_nns_linear(GraphDev g, NnsArgs a) {
     float4 q[NCH];
     load_row<LPR, NCH>(qrow, t, g.n16, q);
     int res_len = 0;
-    for (u32 base = 0; base < a.n_cand_slots; base += 64u) {
-      const int nc = (int)(a.n_cand_slots - base < 64u ? a.n_cand_slots - base : 64u);
+    const u32 *cand_slots = a.cand_slots; // the call's candidates, or those of the query's own filter
+    u32 n_cand_slots = a.n_cand_slots;
+    if (a.cs_off) {
+      const u32 f = uni(a.filter_of[m]);
+      const u64 c0 = uni64(a.cs_off[f]);
+      cand_slots += c0;
+      n_cand_slots = (u32)(uni64(a.cs_off[f + 1]) - c0);
+    }
+    for (u32 base = 0; base < n_cand_slots; base += 64u) {
+      const int nc = (int)(n_cand_slots - base < 64u ? n_cand_slots - base : 64u);
       WSYNC();
-      if (ln < nc) nb_ids[ln] = a.cand_slots[base + ln];
+      if (ln < nc) nb_ids[ln] = cand_slots[base + ln];
       WSYNC();
       dist_rows<LPR, NCH>(g, q, qn, nb_ids, nc, nb_d, qrow);
       evals += (u64)nc;
@@ -2961,6 +2978,74 @@ __global__ __launch_bounds__(64) void k_exact_topk(GraphDev g, ExactArgs a) {
   if (ln == 0) {
     a.list_n[qi] = (u32)res_len;
     if (res_err) atomicAdd(&g.stats[ST_ERR_RES_OVERFLOW], 1ull);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// One candidates filter per query (hny_builder_nns_filtered): the filters' bitsets over slots are
+// made on the device from their slot lists, 4 B per candidate on the way up instead of n / 8 B per filter.
+// ---------------------------------------------------------------------------------------------
+// slots[off[f] .. off[f + 1]) are filter f's live slots, any order, duplicates allowed: one thread per entry
+__global__ __launch_bounds__(256) void k_filter_set_bits(u32 *masks, u32 stride, const u64 *off, const u32 *slots,
+                                                         u32 n_filters, u64 n_slots) {
+  for (u64 i = (u64)blockIdx.x * 256u + threadIdx.x; i < n_slots; i += (u64)gridDim.x * 256u) {
+    u32 lo = 0, hi = n_filters; // the last f with off[f] <= i (empty filters repeat their offset)
+    while (hi - lo > 1u) {
+      const u32 mid = lo + (hi - lo) / 2u;
+      if (off[mid] <= i) lo = mid;
+      else hi = mid;
+    }
+    const u32 s = slots[i];
+    if ((s >> 5) < stride) atomicOr(&masks[(size_t)lo * stride + (s >> 5)], 1u << (s & 31u));
+  }
+}
+
+#define HNY_FILTER_COUNT_WORDS 2048u // words of one mask per workgroup of k_filter_count
+// count[f] += the set bits of one block of filter f's mask; blocks_per = blocks per filter
+__global__ __launch_bounds__(256) void k_filter_count(const u32 *masks, u32 stride, u32 blocks_per, u32 *count) {
+  const u32 f = blockIdx.x / blocks_per, w0 = (blockIdx.x % blocks_per) * HNY_FILTER_COUNT_WORDS;
+  const u32 *mask = masks + (size_t)f * stride;
+  u32 pc = 0;
+  for (u32 w = w0 + threadIdx.x; w < stride && w < w0 + HNY_FILTER_COUNT_WORDS; w += 256u) pc += __popc(mask[w]);
+  for (int o = 32; o >= 1; o >>= 1) pc += (u32)__shfl_xor((int)pc, o, 64);
+  if ((threadIdx.x & 63u) == 0 && pc) atomicAdd(&count[f], pc);
+}
+
+// One workgroup per mask that takes the linear scan: its set slots in ascending order, 256 words at a time, each
+// word's place from the popcount prefix over the words before it
+__global__ __launch_bounds__(256) void k_filter_compact(const u32 *masks, u32 stride, const u32 *lin,
+                                                        const u64 *cs_off, u32 *out) {
+  __shared__ u32 wave_sum[4];
+  const u32 f = lin[blockIdx.x];
+  const u32 *mask = masks + (size_t)f * stride;
+  const u64 end = cs_off[f + 1];
+  u64 base = cs_off[f];
+  const u32 tid = threadIdx.x, ln = tid & 63u, wv = tid >> 6;
+  for (u32 w0 = 0; w0 < stride; w0 += 256u) {
+    const u32 w = w0 + tid;
+    u32 bits = w < stride ? mask[w] : 0u;
+    const u32 pc = (u32)__popc(bits);
+    u32 incl = pc; // inclusive prefix within the wave
+    for (int o = 1; o < 64; o <<= 1) {
+      const u32 up = (u32)__shfl_up((int)incl, o, 64);
+      if (ln >= (u32)o) incl += up;
+    }
+    if (ln == 63u) wave_sum[wv] = incl;
+    __syncthreads();
+    u32 before = 0, total = 0;
+    for (u32 j = 0; j < 4u; j++) {
+      before += j < wv ? wave_sum[j] : 0u;
+      total += wave_sum[j];
+    }
+    u64 at = base + before + (incl - pc);
+    while (bits) {
+      const u32 bit = (u32)__ffs((int)bits) - 1u;
+      bits &= bits - 1u;
+      if (at < end) out[at] = (w << 5) | bit;
+      at++;
+    }
+    base += total;
+    __syncthreads();
   }
 }
 #endif // HNY_PART == 0
@@ -4936,6 +5021,25 @@ hipError_t hnyk_fill_u32(u32 *p, u32 v, size_t n, hipStream_t st) {
   size_t blocks = (n + 255) / 256;
   if (blocks > 65536) blocks = 65536;
   hipLaunchKernelGGL(k_fill_u32, dim3((unsigned)blocks), dim3(256), 0, st, p, v, n);
+  return hipGetLastError();
+}
+hipError_t hnyk_filter_masks(u32 *masks, u32 stride, const u64 *off, const u32 *slots, u32 n_filters, u64 n_slots,
+                             u32 *count, hipStream_t st) {
+  if (!n_filters || !stride) return hipSuccess;
+  if (n_slots) {
+    const u64 blocks = std::min<u64>((n_slots + 255) / 256, 65536);
+    hipLaunchKernelGGL(k_filter_set_bits, dim3((unsigned)blocks), dim3(256), 0, st, masks, stride, off, slots,
+                       n_filters, n_slots);
+  }
+  const u32 blocks_per = (stride + HNY_FILTER_COUNT_WORDS - 1) / HNY_FILTER_COUNT_WORDS;
+  if ((u64)blocks_per * n_filters > 0x7FFFFFFFull) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_filter_count, dim3(blocks_per * n_filters), dim3(256), 0, st, masks, stride, blocks_per, count);
+  return hipGetLastError();
+}
+hipError_t hnyk_filter_compact(const u32 *masks, u32 stride, const u32 *lin, u32 n_lin, const u64 *cs_off, u32 *out,
+                               hipStream_t st) {
+  if (!n_lin) return hipSuccess;
+  hipLaunchKernelGGL(k_filter_compact, dim3(n_lin), dim3(256), 0, st, masks, stride, lin, cs_off, out);
   return hipGetLastError();
 }
 hipError_t hnyk_sort_pairs(void *temp, size_t &temp_bytes, u64 *keys_in, u64 *keys_out, u64 *vals_in,

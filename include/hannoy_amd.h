@@ -382,6 +382,44 @@ int hny_builder_exact_knn_f32(hny_builder *b, const hny_query_opts *opts, uint64
                               const float *queries, size_t qstride, uint32_t *out_ids,
                               float *out_dists, uint32_t *out_counts);
 
+/* ---- batched search with one `.candidates()` filter per query: the reference's filter belongs to one query
+ * (src/reader.rs:200-203), so a batch that serves several requests carries several.
+ *
+ * Definition: let G(f) be the queries with filter_of[i] == f, in call order.  Their rows of the result (ids, distance
+ * bits, counts) are, byte for byte, what hny_builder_nns returns for those queries alone with the same k, ef_search,
+ * linear_below and linear_below_ratio, has_candidates = 1 and candidates = ids[offsets[f] .. offsets[f + 1]).  The
+ * queries of G(HNY_FILTER_NONE) are searched with has_candidates = 0.  should_linear_scan (:621-640) is decided per
+ * filter from its own count of live candidates: one call may hold linear, walked and unfiltered queries.  An empty
+ * filter, or one that names only unknown or deleted ids, gives 0 hits (HNY_NNS_NONE for by_item).
+ *
+ * opts: k, ef_search, linear_below, linear_below_ratio and cancel / cancel_ctx / did_cancel hold for the whole
+ * call; has_candidates must be 0.  Cancellation as in hny_builder_nns.
+ *
+ * Decided before any query is searched, nothing is written to the outputs: NULL arguments (a NULL builder
+ * included), a wrong struct_size, opts->has_candidates != 0, offsets[0] != 0, decreasing offsets, ids == NULL with
+ * offsets[n_filters] > 0, a filter_of entry >= n_filters other than HNY_FILTER_NONE, linear_below_ratio outside
+ * [0, 1]: HNY_ERR_INVALID_ARG; qstride below the row's bytes: HNY_ERR_INVALID_DIM; a filter that some query uses,
+ * that takes the linear scan and would need more than 4 095 hits: HNY_ERR_UNSUPPORTED for the whole call.
+ *
+ * The filters' bitsets are made on the device from 4 B per candidate, at most 1 GB of them at a time; queries are
+ * taken in filter order when that takes several rounds.  hny_query_filters carries its own
+ * struct_size and is not part of hny_abi_sizes. */
+#define HNY_FILTER_NONE 0xFFFFFFFFu
+typedef struct {
+  uint32_t struct_size;      /* sizeof(hny_query_filters) as the caller compiled it; anything else: HNY_ERR_INVALID_ARG */
+  uint32_t n_filters;
+  const uint64_t *offsets;   /* n_filters + 1 entries, offsets[0] == 0, non-decreasing */
+  const uint32_t *ids;       /* offsets[n_filters] item ids: any order, duplicates and unknown / deleted ids allowed */
+  const uint32_t *filter_of; /* one entry per query: an index < n_filters, or HNY_FILTER_NONE = no .candidates() for this query */
+} hny_query_filters;
+
+int hny_builder_nns_filtered(hny_builder *b, const hny_query_opts *opts, const hny_query_filters *filters,
+                             uint64_t n_queries, const void *qvectors, size_t qstride, const void *qheaders,
+                             const uint32_t *query_items, uint32_t *out_ids, float *out_dists, uint32_t *out_counts);
+int hny_builder_nns_filtered_f32(hny_builder *b, const hny_query_opts *opts, const hny_query_filters *filters,
+                                 uint64_t n_queries, const float *queries, size_t qstride,
+                                 uint32_t *out_ids, float *out_dists, uint32_t *out_counts);
+
 /* ---- resident updates: Writer::add_item / del_item followed by Writer::build (src/writer.rs:462-495, 521-603)
  * on an index whose builder is still alive.  A finished builder holds the codec rows, the norms and the finalised
  * lists of every live item in HBM; the successor takes them from there, device to device (k_move_rows /
