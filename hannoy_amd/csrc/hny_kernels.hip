@@ -691,6 +691,23 @@ struct Beam {
 #else
 #define PH_STAMP(s, i) do { } while (0)
 #endif
+// an empty beam on res[0, rcap) and the tie pool
+__device__ __forceinline__ void beam_init(Beam &s, u64 *res, u64 *pool, int rcap) {
+#ifdef HNY_PHASE_CLOCKS
+  for (int i = 0; i < 12; i++) s.ph[i] = 0;
+  s.ph_t = 0;
+#endif
+  s.res = res;
+  s.pool = pool;
+  s.rcap = rcap;
+  s.pool_over = 0;
+  s.err = 0;
+  s.res_len = 0;
+  s.pool_len = 0;
+  s.n_weird = 0;
+  s.tie_bits = 0;
+  s.dropped = false;
+}
 
 // OrderedFloat orders by bit pattern (ordered_float.rs:25-29) while the two raw compares in
 // walk_layer (hnsw.rs:485, 505) use float order.  They disagree only for sign-bit-set or NaN
@@ -1778,6 +1795,199 @@ __device__ __forceinline__ void walk_layer_short(const GraphDev &g, const float4
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// list steps shared by the prune, add_link and fill_gaps kernels (and the searches' drain_asc), for blocks
+// of NT threads (one wave: 64, a workgroup: 256).  ONE: every range is known to fit one pass (lists of at most 64 slots in a
+// wave), so thread t takes entry t alone and no loop is left for the register allocator.  Keys: dist
+// bits << 32 | id.  The caller syncs after each.
+// ---------------------------------------------------------------------------------------------
+template <int NT>
+__device__ __forceinline__ void block_sync() {
+  if constexpr (NT == 64)
+    WSYNC();
+  else
+    __syncthreads();
+}
+// f(e) for every e in [0, n) (int or u32): thread t takes t, t + NT, ...
+template <int NT, bool ONE, class I, class F>
+__device__ __forceinline__ void each(I n, F f) {
+  if constexpr (ONE) {
+    if ((I)threadIdx.x < n) f((I)threadIdx.x);
+  } else {
+    for (I e = (I)threadIdx.x; e < n; e += (I)NT) f(e);
+  }
+}
+// keys[0, n) sorted into out: ascending, ties in position order
+template <int NT, bool ONE = false>
+__device__ __forceinline__ void rank_sort(const u64 *keys, int n, u64 *out) {
+  auto rank = [&](int e, u64 mine) __attribute__((always_inline)) {
+    int rk = 0;
+    for (int j = 0; j < n; j++) {
+      const u64 o = keys[j];
+      rk += (o < mine || (o == mine && j < e)) ? 1 : 0;
+    }
+    return rk;
+  };
+  if constexpr (ONE) { // every lane ranks (a lane beyond n a dummy): the loop stays uniform
+    const int e = (int)threadIdx.x;
+    const u64 mine = e < n ? keys[e] : 0ull;
+    const int rk = rank(e, mine);
+    if (e < n) out[rk] = mine;
+  } else {
+    for (int e = (int)threadIdx.x; e < n; e += NT) {
+      const u64 mine = keys[e];
+      out[rank(e, mine)] = mine;
+    }
+  }
+}
+// the list := keys[0, cnt), HNY_SENT / 0.0 beyond, with count word cw
+template <int NT, bool ONE = false>
+__device__ __forceinline__ void store_list(const NodeList &l, const u64 *keys, int cnt, u32 cw) {
+  each<NT, ONE>(l.cap, [&](u32 e) __attribute__((always_inline)) {
+    const bool on = (int)e < cnt;
+    const u64 k = on ? keys[e] : 0ull;
+    l.ids[e] = on ? (u32)(k & 0xFFFFFFFFull) : HNY_SENT;
+    l.dist[e] = on ? __uint_as_float((u32)(k >> 32)) : 0.f;
+  });
+  if (threadIdx.x == 0) *l.cnt = cw;
+}
+// a prune kernel's result for member m on the launch's layer: [0] = s_len, [1 ..] = S
+template <int NT, bool ONE = false>
+__device__ __forceinline__ void store_sel(const PruneArgs &a, u32 m, const u64 *S, int s_len) {
+  u64 *out = a.sel + (size_t)m * a.sel_stride + (size_t)(a.batch_level - a.layer) * (a.cap_sel + 1);
+  if (threadIdx.x == 0) out[0] = (u64)s_len;
+  each<NT, ONE>(s_len, [&](int e) __attribute__((always_inline)) { out[1 + e] = S[e]; });
+}
+
+// ---------------------------------------------------------------------------------------------
+// steps shared by the walk and search kernels (k_walk, k_walk_heap, k_nns): where a member starts, the result
+// row, the Reader's exhaustive fallback.  `A` is a handle on the launch arguments, read through -> where they
+// are used: k_walk's kernarg-segment pointer (see KA_FRESH there), or the address of a by-value copy.
+// ---------------------------------------------------------------------------------------------
+// hnsw.rs:298 / reader.rs:728: eps = all entry points; returns how many.  BIG_EPS: there may be more than 64
+// (one lane each otherwise).  The caller syncs.
+template <bool BIG_EPS, class A>
+__device__ __forceinline__ int start_at_entry_points(A a, u32 *eps) {
+  const int ln = threadIdx.x, n_eps = (int)a->n_entry_points;
+  if (BIG_EPS) {
+    for (int i = ln; i < n_eps; i += 64) eps[i] = a->entry_points[i];
+  } else if (ln < n_eps) {
+    eps[ln] = a->entry_points[ln];
+  }
+  return n_eps;
+}
+// where member m of a walk launch starts: eps[0, n_eps) and the layer of its first walk_layer call.  The caller
+// syncs.  (Returned by value: the same two results written through references moved k_walk's SGPR spills.)
+struct MemberStart {
+  int n_eps;
+  u32 layer;
+};
+template <bool BIG_EPS, class A>
+__device__ __forceinline__ MemberStart member_start(A a, const GraphDev &g, u32 m, u32 *eps) {
+  const int ln = threadIdx.x;
+  int n_eps;
+  u32 start_layer;
+  if (a->first) { // hnsw.rs:298 eps = all entry points
+    n_eps = start_at_entry_points<BIG_EPS>(a, eps);
+    start_layer = g.max_level;
+  } else if (a->eps_in) { // resume after a descend_only launch
+    n_eps = 1;
+    if (ln == 0) eps[0] = a->eps_in[m];
+    start_layer = a->layer;
+  } else { // :316-321 eps = what was selected on the layer above
+    const u64 *sl = a->sel + (size_t)m * a->sel_stride + (size_t)(a->batch_level - (a->layer + 1)) * (a->cap_sel + 1);
+    n_eps = (int)sl[0];
+    for (int i = ln; i < n_eps; i += 64) eps[i] = (u32)(sl[1 + i] & 0xFFFFFFFFull); // (more than 64: M > 64)
+    start_layer = a->layer;
+  }
+  // the lane-conditional stores above sit on the paths that define these two: without the readfirstlane the
+  // compiler's uniformity analysis calls them divergent, and with them the layer loop's exit, `ef`, and
+  // every piece of beam / pool / visited state that the expansion loop carries
+  return {uni(n_eps), uni(start_layer)};
+}
+
+// `res`, ascending, into member m's row of a->cand from entry `at` on, in the output key format (dist bits << 32 |
+// slot: the expanded bit goes): from the registers when RB, else from s.res.  a->cand and a->rcap are read inside
+// the lane-conditional stores: a row pointer computed ahead of them cost the build kernels SGPR spills.
+template <bool RB, int RCN, class A>
+__device__ __forceinline__ void beam_store(A a, u32 m, u32 at, const Beam &s, const BeamR<RCN> &rb) {
+  const int ln = threadIdx.x;
+  auto out = [](u64 k) __attribute__((always_inline)) { return (k & 0xFFFFFFFF00000000ull) | ((k >> 1) & 0x7FFFFFFFull); };
+  if constexpr (RB) {
+#pragma unroll
+    for (int c = 0; c < RCN; c++)
+      if (ln + 64 * c < s.res_len) a->cand[(size_t)m * a->rcap + at + 64 * c + ln] = out(rb.r[c]);
+  } else {
+    for (int e = ln; e < s.res_len; e += 64) a->cand[(size_t)m * a->rcap + at + e] = out(s.res[e]);
+  }
+}
+
+// the exhaustive fallback's scan (reader.rs:771-795 / 864-890): the first slot >= pos that is not on `path`
+// (the flushed visited bitset, 64 words at a time), or g.n when there is none
+__device__ __forceinline__ u32 next_unvisited(const GraphDev &g, u32 *bits, u32 pos) {
+  const int ln = threadIdx.x;
+  const u32 nwords = (g.n + 31) >> 5;
+  while (pos < g.n) {
+    const u32 wbase = pos >> 5;
+    const u32 widx = wbase + (u32)ln;
+    u32 unv = 0u;
+    if (widx < nwords) {
+      unv = ~__hip_atomic_load(&bits[widx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (ln == 0 && (pos & 31u)) unv &= ~((1u << (pos & 31u)) - 1u);
+      if (widx == nwords - 1 && (g.n & 31u)) unv &= (1u << (g.n & 31u)) - 1u;
+    }
+    const u64 mk = ballot(unv != 0u);
+    if (mk) {
+      const int l0 = __ffsll((long long)mk) - 1;
+      const u32 w0 = (u32)__builtin_amdgcn_readlane((int)unv, l0);
+      return ((wbase + (u32)l0) << 5) + (u32)__builtin_ctz(w0);
+    }
+    pos = (wbase + 64u) << 5;
+  }
+  return g.n;
+}
+
+// Reader::hnsw_search / nns_by_item exhaustive fallback (reader.rs:771-795 / 864-890): the search got trapped in
+// a sub-graph with fewer than k items, so level 0 is visited again from every existing item that is not on
+// `path` yet (ascending id, the visited set shared) until `stop` hits are collected.  `total` hits are in the
+// row on entry; it grows by what every restart finds.
+//   visit(ef, n_eps) -> status   level 0 from eps[0, n_eps), `res` refilled; non-zero: failed
+//   found() -> u32               entries in `res`
+//   extend(at)                   `res`, ascending, into row[at ..): neighbours.extend(more_nns)
+// The scan reads the bitset alone: the visited table is flushed here, a caller with a bucket table (VisB)
+// flushes that one first.  The row is left as collected; drain_asc() is the caller's, on FB_OK.
+enum { FB_OK = 0, FB_VISIT_FAILED = 1, FB_ROW_OVERFLOW = 2 };
+template <class V, class F, class E>
+__device__ __forceinline__ int exhaustive_fallback(const GraphDev &g, Visited &vis, u32 *eps, u32 &total, u32 stop,
+                                                   u32 rcap, V visit, F found, E extend) {
+  visited_flush(vis);
+  for (u32 pos = 0, slot; (slot = next_unvisited(g, vis.bits, pos)) < g.n;) {
+    pos = slot + 1;
+    if (g.incremental && !g.has_vec[slot]) continue; // prefix_iter over Item keys: existing items
+    const int ef2 = stop > total ? (int)(stop - total) : 0; // :878 / saturating_sub, :786
+    WSYNC();
+    if (threadIdx.x == 0) eps[0] = slot;
+    WSYNC();
+    if (visit(ef2, 1)) return FB_VISIT_FAILED;
+    const u32 got = found();
+    if (total + got > rcap) return FB_ROW_OVERFLOW;
+    extend(total);
+    total += got;
+    if (total >= stop) break; // :792-794
+  }
+  return FB_OK;
+}
+// drain_asc() (reader.rs:797) of a fallback's row: row[0, n) sorted ascending, through n entries of `res`.
+// Every slot is visited once, so the keys are unique and rank_sort's tie rule changes nothing.
+__device__ __forceinline__ void drain_asc(u64 *row, int n, u64 *res) {
+  __threadfence_block();
+  WSYNC();
+  each<64, false>(n, [&](int e) __attribute__((always_inline)) { res[e] = row[e]; });
+  WSYNC();
+  rank_sort<64>(res, n, row);
+  WSYNC();
+}
+
 
 #ifndef HNY_WALK_WPE
 #define HNY_WALK_WPE 4
@@ -1837,22 +2047,11 @@ __global__ __launch_bounds__(64, (NCH == 1 && SP >= 4 && !RM && (RC == 1 || RC =
   u32 *eps = reinterpret_cast<u32 *>(nb_d + 64);
   const int ln = threadIdx.x, t = ln % LPR;
 
-  Beam s;
 #ifdef HNY_PHASE_CLOCKS
-  for (int i = 0; i < 12; i++) s.ph[i] = 0;
-  s.ph_t = 0;
   const u64 ph_kernel_t0 = __builtin_readcyclecounter();
 #endif
-  s.res = res;
-  s.pool = pool;
-  s.rcap = (int)ak->rcap;
-  s.pool_over = 0;
-  s.err = 0;
-  s.res_len = 0;
-  s.pool_len = 0;
-  s.n_weird = 0;
-  s.tie_bits = 0;
-  s.dropped = false;
+  Beam s;
+  beam_init(s, res, pool, (int)ak->rcap);
   BeamR<RCN> rb;
 #pragma unroll
   for (int c = 0; c < RCN; c++) rb.r[c] = 0ull;
@@ -1941,32 +2140,9 @@ __global__ __launch_bounds__(64, (NCH == 1 && SP >= 4 && !RM && (RC == 1 || RC =
       load_row<LPR, NCH>(qrow, t, g.n16, q);
     }
 
-    int n_eps;
-    u32 start_layer;
-    if (ak->first) { // :298 eps = all entry points
-      n_eps = (int)ak->n_entry_points;
-      if (BIG_EPS) {
-        for (int i = ln; i < n_eps; i += 64) eps[i] = ak->entry_points[i];
-      } else if (ln < n_eps) {
-        eps[ln] = ak->entry_points[ln];
-      }
-      start_layer = g.max_level;
-    } else if (ak->eps_in) { // resume after a descend_only launch
-      n_eps = 1;
-      if (ln == 0) eps[0] = ak->eps_in[m];
-      start_layer = ak->layer;
-    } else { // :316-321 eps = what was selected on the layer above
-      const u64 *sl = ak->sel + (size_t)m * ak->sel_stride +
-                      (size_t)(ak->batch_level - (ak->layer + 1)) * (ak->cap_sel + 1);
-      n_eps = (int)sl[0];
-      for (int i = ln; i < n_eps; i += 64) eps[i] = (u32)(sl[1 + i] & 0xFFFFFFFFull); // (more than 64: M > 64)
-      start_layer = ak->layer;
-    }
-    // the lane-conditional stores above sit on the paths that define these two: without the readfirstlane the
-    // compiler's uniformity analysis calls them divergent, and with them the layer loop's exit, `ef`, and
-    // every piece of beam / pool / visited state that the expansion loop carries
-    n_eps = uni(n_eps);
-    start_layer = uni(start_layer);
+    const MemberStart ms = member_start<BIG_EPS>(ak, g, m, eps);
+    int n_eps = ms.n_eps;
+    const u32 start_layer = ms.layer;
     WSYNC();
     u64 lkey = 0;
     for (u32 layer = start_layer;; layer--) {
@@ -2014,95 +2190,35 @@ __global__ __launch_bounds__(64, (NCH == 1 && SP >= 4 && !RM && (RC == 1 || RC =
       continue;
     }
     // result, ascending (res.into_vec() is re-sorted by robust_prune anyway, :573)
-    if constexpr (RB) {
-#pragma unroll
-      for (int c = 0; c < RCN; c++)
-        if (ln + 64 * c < s.res_len)
-          ak->cand[(size_t)m * ak->rcap + 64 * c + ln] = (rb.r[c] & 0xFFFFFFFF00000000ull) | ((rb.r[c] >> 1) & 0x7FFFFFFFull);
-    } else {
-      for (int e = ln; e < s.res_len; e += 64) {
-        u64 k = s.res[e];
-        ak->cand[(size_t)m * ak->rcap + e] = (k & 0xFFFFFFFF00000000ull) | ((k >> 1) & 0x7FFFFFFFull);
-      }
-    }
-    int total = s.res_len;
-    if (reader_mode && total < (int)ak->knn_k) {
-      // Reader::hnsw_search exhaustive fallback (reader.rs:771-795): the walk got trapped in a
-      // sub-graph with fewer than k items; restart from every item not seen yet (ascending id),
-      // sharing the visited set, until opt.ef hits are collected.  Rare; written for clarity.
-      const u32 nwords = (g.n + 31) >> 5;
-      u32 pos = 0;
-      visited_flush(vis);
+    beam_store<RB>(ak, m, 0u, s, rb);
+    u32 total = (u32)s.res_len;
+    if (reader_mode && total < ak->knn_k) { // Reader::hnsw_search's exhaustive fallback, until opt.ef hits.  Rare.
       visb_flush(vb, vis);
-      while (pos < g.n) {
-        const u32 wbase = pos >> 5;
-        const u32 widx = wbase + (u32)ln;
-        u32 unv = 0u;
-        if (widx < nwords) {
-          unv = ~__hip_atomic_load(&vis.bits[widx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if (ln == 0 && (pos & 31u)) unv &= ~((1u << (pos & 31u)) - 1u);
-          if (widx == nwords - 1 && (g.n & 31u)) unv &= (1u << (g.n & 31u)) - 1u;
-        }
-        const u64 mk = ballot(unv != 0u);
-        if (!mk) {
-          pos = (wbase + 64u) << 5;
-          continue;
-        }
-        const int l0 = __ffsll((long long)mk) - 1;
-        const u32 w0 = (u32)__builtin_amdgcn_readlane((int)unv, l0);
-        const u32 slot = ((wbase + (u32)l0) << 5) + (u32)__builtin_ctz(w0);
-        pos = slot + 1;
-        if (g.incremental && !g.has_vec[slot]) continue; // prefix_iter over Item keys: existing items
-        const int ef2 = (int)ak->knn_ef > total ? (int)ak->knn_ef - total : 0; // saturating_sub :786
-        if (ln == 0) eps[0] = slot;
-        WSYNC();
+      auto visit = [&](int ef2, int ne) -> int { // (what goes wrong inside a walk is in s.err / err_iter)
         if constexpr (SHORT)
-          walk_layer_short<LPR, RCN>(g, q, qn, 0u, ef2, eps, 1, s, vis, vb, nb_ids, nb_d, evals, err_iter, rb);
+          walk_layer_short<LPR, RCN>(g, q, qn, 0u, ef2, eps, ne, s, vis, vb, nb_ids, nb_d, evals, err_iter, rb);
         else
-          walk_one_layer<LPR, NCH, BIG_EPS, RC, QN, LMERGE, PAGED>(g, q, qn, 0u, ef2, eps, 1, s, vis, nb_ids, nb_d, evals, err_iter, qrow, rb);
+          walk_one_layer<LPR, NCH, BIG_EPS, RC, QN, LMERGE, PAGED>(g, q, qn, 0u, ef2, eps, ne, s, vis, nb_ids, nb_d, evals, err_iter, qrow, rb);
         KA_FRESH();
-        if (total + s.res_len > (int)ak->rcap) {
-          s.err = 1;
-          break;
-        }
-        if constexpr (RB) { // neighbours.extend(more_nns)
-#pragma unroll
-          for (int c = 0; c < RCN; c++)
-            if (ln + 64 * c < s.res_len)
-              ak->cand[(size_t)m * ak->rcap + total + 64 * c + ln] =
-                  (rb.r[c] & 0xFFFFFFFF00000000ull) | ((rb.r[c] >> 1) & 0x7FFFFFFFull);
-        } else {
-          for (int e = ln; e < s.res_len; e += 64) {
-            u64 k = s.res[e];
-            ak->cand[(size_t)m * ak->rcap + total + e] = (k & 0xFFFFFFFF00000000ull) | ((k >> 1) & 0x7FFFFFFFull);
-          }
-        }
-        total += s.res_len;
-        if (total >= (int)ak->knn_ef) break; // :792-794
-      }
-      // drain_asc(): sort everything that was collected
-      __threadfence_block();
-      WSYNC();
-      for (int e = ln; e < total; e += 64) s.res[e] = ak->cand[(size_t)m * ak->rcap + e];
-      WSYNC();
-      for (int e = ln; e < total; e += 64) {
-        const u64 mine = s.res[e];
-        int rk = 0;
-        for (int k2 = 0; k2 < total; k2++) rk += s.res[k2] < mine ? 1 : 0;
-        ak->cand[(size_t)m * ak->rcap + rk] = mine;
-      }
-      WSYNC();
+        return 0;
+      };
+      auto found = [&]() -> u32 { return (u32)s.res_len; };
+      auto extend = [&](u32 at) { beam_store<RB>(ak, m, at, s, rb); };
+      if (exhaustive_fallback(g, vis, eps, total, ak->knn_ef, ak->rcap, visit, found, extend) == FB_ROW_OVERFLOW)
+        s.err = 1;
+      else
+        drain_asc(ak->cand + (size_t)m * ak->rcap, (int)total, s.res);
     }
     if constexpr (RM || SP == 0) {
       // a search whose tie pool overflowed: flagged instead of counted, the host repeats the query on the
       // heap-queue searcher (k_nns without a filter), which has no pool
       // (force_pool: tests send every k-th query that way)
       if (reader_mode && ak->pool_flag && (s.pool_over || (ak->force_pool && m % ak->force_pool == 0u))) {
-        total = (int)0xFFFFFFFEu;
+        total = 0xFFFFFFFEu;
         s.pool_over = 0;
       }
     }
-    if (ln == 0) ak->cand_n[m] = (u32)total;
+    if (ln == 0) ak->cand_n[m] = total;
     if (vis.log_over) log_over_cnt++;
     visited_clear(vis);
     visb_clear(vb);
@@ -2259,31 +2375,6 @@ __device__ __forceinline__ const u32 *query_filter(const NnsArgs &a, u32 m) {
   if (!a.filter_of) return a.filter;
   const u32 f = uni(a.filter_of[m]);
   return f == HNY_SENT ? nullptr : a.filter + (size_t)f * a.mask_stride;
-}
-
-// the exhaustive fallback's scan (reader.rs:771-795 / 864-890): the first slot >= pos that is not on `path`
-// (the flushed visited bitset, 64 words at a time), or g.n when there is none
-__device__ __forceinline__ u32 next_unvisited(const GraphDev &g, u32 *bits, u32 pos) {
-  const int ln = threadIdx.x;
-  const u32 nwords = (g.n + 31) >> 5;
-  while (pos < g.n) {
-    const u32 wbase = pos >> 5;
-    const u32 widx = wbase + (u32)ln;
-    u32 unv = 0u;
-    if (widx < nwords) {
-      unv = ~__hip_atomic_load(&bits[widx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (ln == 0 && (pos & 31u)) unv &= ~((1u << (pos & 31u)) - 1u);
-      if (widx == nwords - 1 && (g.n & 31u)) unv &= (1u << (g.n & 31u)) - 1u;
-    }
-    const u64 mk = ballot(unv != 0u);
-    if (mk) {
-      const int l0 = __ffsll((long long)mk) - 1;
-      const u32 w0 = (u32)__builtin_amdgcn_readlane((int)unv, l0);
-      return ((wbase + (u32)l0) << 5) + (u32)__builtin_ctz(w0);
-    }
-    pos = (wbase + 64u) << 5;
-  }
-  return g.n;
 }
 
 // Visitor::visit at level 0 with `candidates` (reader.rs:301-369).  Returns 0, or 1 when the heap
@@ -2520,22 +2611,9 @@ __global__ __launch_bounds__(64, 4) void k_walk_heap(GraphDev g, WalkArgs a) {
     const float qn = g.norms ? g.norms[qslot] : 0.f;
     float4 q[NCH];
     load_row<LPR, NCH>(qrow, t, g.n16, q);
-    int n_eps;
-    u32 start_layer;
-    if (a.first) { // hnsw.rs:298 eps = all entry points
-      n_eps = (int)a.n_entry_points;
-      for (int i = ln; i < n_eps; i += 64) eps[i] = a.entry_points[i];
-      start_layer = g.max_level;
-    } else if (a.eps_in) { // resume after a descend_only launch
-      n_eps = 1;
-      if (ln == 0) eps[0] = a.eps_in[m];
-      start_layer = a.layer;
-    } else { // :316-321 eps = what was selected on the layer above
-      const u64 *sl = a.sel + (size_t)m * a.sel_stride + (size_t)(a.batch_level - (a.layer + 1)) * (a.cap_sel + 1);
-      n_eps = (int)sl[0];
-      for (int i = ln; i < n_eps; i += 64) eps[i] = (u32)(sl[1 + i] & 0xFFFFFFFFull); // (more than 64: M > 64)
-      start_layer = a.layer;
-    }
+    const MemberStart ms = member_start<true>(&a, g, m, eps);
+    int n_eps = ms.n_eps;
+    const u32 start_layer = ms.layer;
     WSYNC();
     u64 lkey = 0, rmin = ~0ull;
     int st = 0;
@@ -2605,20 +2683,7 @@ __global__ __launch_bounds__(64, 4) void k_nns(GraphDev g, NnsArgs a) {
   const int ln = threadIdx.x, t = ln % LPR;
 
   Beam s; // LDS variant: greedy descent through the upper layers, the ordinary (unfiltered) walk
-#ifdef HNY_PHASE_CLOCKS
-  for (int i = 0; i < 12; i++) s.ph[i] = 0;
-  s.ph_t = 0;
-#endif
-  s.res = res;
-  s.pool = pool;
-  s.rcap = (int)a.rcap;
-  s.pool_over = 0;
-  s.err = 0;
-  s.res_len = 0;
-  s.pool_len = 0;
-  s.n_weird = 0;
-  s.tie_bits = 0;
-  s.dropped = false;
+  beam_init(s, res, pool, (int)a.rcap);
   BeamR<1> rb_unused{{0ull}};
   Visited vis;
   visited_init(vis, a.bits + (size_t)blockIdx.x * a.bits_words, a.bits_words,
@@ -2652,8 +2717,7 @@ __global__ __launch_bounds__(64, 4) void k_nns(GraphDev g, NnsArgs a) {
       if (ln == 0) eps[0] = excl;
       WSYNC();
     } else { // :728-743 greedy descent, no filter, `path` shared and cleared before level 0
-      n_eps = (int)a.n_entry_points;
-      for (int i = ln; i < n_eps; i += 64) eps[i] = a.entry_points[i];
+      n_eps = start_at_entry_points<true>(&a, eps);
       WSYNC();
       for (u32 layer = g.max_level; layer >= 1u && !st; layer--) {
         u32 closest;
@@ -2703,47 +2767,21 @@ __global__ __launch_bounds__(64, 4) void k_nns(GraphDev g, NnsArgs a) {
       } else {
         extend(0u);
         if (total < a.k) {
-          // exhaustive fallback (:771-795 / :864-890): restart from every item not on `path` yet
           const u32 stop = a.by_item ? a.k : a.ef_opt;
-          visited_flush(vis);
-          for (u32 pos = 0, slot; (slot = next_unvisited(g, vis.bits, pos)) < g.n;) {
-            pos = slot + 1;
-            if (g.incremental && !g.has_vec[slot]) continue;
-            const int ef2 = stop > total ? (int)(stop - total) : 0; // :878 / saturating_sub, :783
-            WSYNC();
-            if (ln == 0) eps[0] = slot;
-            WSYNC();
-            st = visit(ef2, 1);
-            if (st) break;
-            if (total + found() > a.rcap) {
-              if (RES_HEAP) st = 1;
-              else res_err = 1;
-              break;
-            }
-            const u32 got = found();
-            extend(total); // neighbours.extend(more_nns)
-            total += got;
-            if (total >= stop) break;
-          }
+          const int fb = exhaustive_fallback(g, vis, eps, total, stop, a.rcap, visit, found, extend);
+          if (fb == FB_VISIT_FAILED || (RES_HEAP && fb == FB_ROW_OVERFLOW)) st = 1;
+          else if (fb == FB_ROW_OVERFLOW) res_err = 1;
           if (!st && !res_err) { // drain_asc(): everything that was collected, sorted
-            __threadfence_block();
-            WSYNC();
             if constexpr (RES_HEAP) { // through the heap once more
+              __threadfence_block();
+              WSYNC();
               R.size = 0;
               R.top = ~0ull;
               for (u32 i = 0; i < total && !st; i++)
                 if (!qheap_push(R, ~uni64(row[i]))) st = 1;
               if (!st) qheap_drain(R, row);
-            } else { // rank sort in LDS
-              for (u32 e = ln; e < total; e += 64) res[e] = row[e];
-              WSYNC();
-              for (u32 e = ln; e < total; e += 64) {
-                const u64 mine = res[e];
-                u32 rk = 0;
-                for (u32 k2 = 0; k2 < total; k2++) rk += res[k2] < mine ? 1 : 0;
-                row[rk] = mine;
-              }
-              WSYNC();
+            } else {
+              drain_asc(row, (int)total, res);
             }
           }
         }
@@ -3049,70 +3087,6 @@ __global__ __launch_bounds__(256) void k_filter_compact(const u32 *masks, u32 st
   }
 }
 #endif // HNY_PART == 0
-
-// ---------------------------------------------------------------------------------------------
-// list steps shared by the prune, add_link and fill_gaps kernels, for blocks of NT threads (one wave:
-// 64, a workgroup: 256).  ONE: every range is known to fit one pass (lists of at most 64 slots in a
-// wave), so thread t takes entry t alone and no loop is left for the register allocator.  Keys: dist
-// bits << 32 | id.  The caller syncs after each.
-// ---------------------------------------------------------------------------------------------
-template <int NT>
-__device__ __forceinline__ void block_sync() {
-  if constexpr (NT == 64)
-    WSYNC();
-  else
-    __syncthreads();
-}
-// f(e) for every e in [0, n) (int or u32): thread t takes t, t + NT, ...
-template <int NT, bool ONE, class I, class F>
-__device__ __forceinline__ void each(I n, F f) {
-  if constexpr (ONE) {
-    if ((I)threadIdx.x < n) f((I)threadIdx.x);
-  } else {
-    for (I e = (I)threadIdx.x; e < n; e += (I)NT) f(e);
-  }
-}
-// keys[0, n) sorted into out: ascending, ties in position order
-template <int NT, bool ONE = false>
-__device__ __forceinline__ void rank_sort(const u64 *keys, int n, u64 *out) {
-  auto rank = [&](int e, u64 mine) __attribute__((always_inline)) {
-    int rk = 0;
-    for (int j = 0; j < n; j++) {
-      const u64 o = keys[j];
-      rk += (o < mine || (o == mine && j < e)) ? 1 : 0;
-    }
-    return rk;
-  };
-  if constexpr (ONE) { // every lane ranks (a lane beyond n a dummy): the loop stays uniform
-    const int e = (int)threadIdx.x;
-    const u64 mine = e < n ? keys[e] : 0ull;
-    const int rk = rank(e, mine);
-    if (e < n) out[rk] = mine;
-  } else {
-    for (int e = (int)threadIdx.x; e < n; e += NT) {
-      const u64 mine = keys[e];
-      out[rank(e, mine)] = mine;
-    }
-  }
-}
-// the list := keys[0, cnt), HNY_SENT / 0.0 beyond, with count word cw
-template <int NT, bool ONE = false>
-__device__ __forceinline__ void store_list(const NodeList &l, const u64 *keys, int cnt, u32 cw) {
-  each<NT, ONE>(l.cap, [&](u32 e) __attribute__((always_inline)) {
-    const bool on = (int)e < cnt;
-    const u64 k = on ? keys[e] : 0ull;
-    l.ids[e] = on ? (u32)(k & 0xFFFFFFFFull) : HNY_SENT;
-    l.dist[e] = on ? __uint_as_float((u32)(k >> 32)) : 0.f;
-  });
-  if (threadIdx.x == 0) *l.cnt = cw;
-}
-// a prune kernel's result for member m on the launch's layer: [0] = s_len, [1 ..] = S
-template <int NT, bool ONE = false>
-__device__ __forceinline__ void store_sel(const PruneArgs &a, u32 m, const u64 *S, int s_len) {
-  u64 *out = a.sel + (size_t)m * a.sel_stride + (size_t)(a.batch_level - a.layer) * (a.cap_sel + 1);
-  if (threadIdx.x == 0) out[0] = (u64)s_len;
-  each<NT, ONE>(s_len, [&](int e) __attribute__((always_inline)) { out[1 + e] = S[e]; });
-}
 
 // ---------------------------------------------------------------------------------------------
 // robust_prune (hnsw.rs:565-597) on a list that is already sorted ascending by (bits(d), id).
@@ -4616,6 +4590,18 @@ hipError_t dispatch_shape(LaunchShape s, Args &&...args) {
   return hipErrorInvalidValue;
 }
 
+// a launch whose dynamic LDS may exceed the 64 KB a kernel gets without asking: the opt-in, then the launch
+template <typename... P, typename... Args>
+hipError_t launch_with_lds(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args &...args) {
+  if (lds > 65536) {
+    hipError_t rc = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (rc != hipSuccess) return rc;
+  }
+  hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+  return hipGetLastError();
+}
+
 // launchers of the four build kernels, general (SP = 0) or specialised for metric SP - 1
 template <int SP>
 struct Hot {
@@ -4672,13 +4658,8 @@ struct Hot {
         return hipErrorInvalidValue; // 4 rows x C chunks do not fit the register file: wave prune
       } else {
         size_t lds = wg_prune_lds_bytes((SP == 0 && a.list_global) ? 0u : a.rcap, g.row_stride, SL, nw, wg_capmax(g));
-        if (lds > 65536) { // wide lists (M0 up to HNY_BIG_CAP) next to long rows
-          hipError_t rc = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_prune_wg<L, C, 4, SP>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-          if (rc != hipSuccess) return rc;
-        }
-        hipLaunchKernelGGL((k_prune_wg<L, C, 4, SP>), dim3(grid), dim3(256), lds, st, g, a, SL);
-        return hipGetLastError();
+        // (beyond 64 KB: wide lists, M0 up to HNY_BIG_CAP, next to long rows)
+        return launch_with_lds(k_prune_wg<L, C, 4, SP>, dim3(grid), dim3(256), lds, st, g, a, SL);
       }
     }
   };
@@ -4714,13 +4695,7 @@ struct Hot {
         return hipErrorInvalidValue;
       } else {
         size_t lds = wg_prune_lds_bytes(2 * wg_capmax(g), g.row_stride, SL, 4, wg_capmax(g));
-        if (lds > 65536) {
-          hipError_t rc = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_apply_wg<L, C, SP>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-          if (rc != hipSuccess) return rc;
-        }
-        hipLaunchKernelGGL((k_apply_wg<L, C, SP>), dim3(grid), dim3(256), lds, st, g, a, SL);
-        return hipGetLastError();
+        return launch_with_lds(k_apply_wg<L, C, SP>, dim3(grid), dim3(256), lds, st, g, a, SL);
       }
     }
   };
@@ -4770,14 +4745,8 @@ template <int L, int C>
 struct ExactScoresLauncher {
   static hipError_t run(const GraphDev &g, const ExactArgs &a, hipStream_t st) {
     const size_t lds = (size_t)a.qt * g.row_stride + (size_t)a.qt * 4;
-    if (lds > 65536) {
-      hipError_t rc = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_exact_scores<L, C>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (rc != hipSuccess) return rc;
-    }
     const dim3 grid((a.nq + a.qt - 1) / a.qt, (a.slab_n + HNY_EXACT_CHUNK - 1) / HNY_EXACT_CHUNK);
-    hipLaunchKernelGGL((k_exact_scores<L, C>), grid, dim3(256), lds, st, g, a);
-    return hipGetLastError();
+    return launch_with_lds(k_exact_scores<L, C>, grid, dim3(256), lds, st, g, a);
   }
 };
 template <int L, int C>
@@ -4796,13 +4765,7 @@ struct GapsLauncher {
     const u32 cap = g.M0 > g.M ? g.M0 : g.M;
     const u32 maxu = cap * (cap + 1u);
     const size_t lds = fill_gaps_lds_bytes(maxu);
-    if (lds > 65536) {
-      hipError_t rc = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fill_gaps<L, C>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (rc != hipSuccess) return rc;
-    }
-    hipLaunchKernelGGL((k_fill_gaps<L, C>), dim3(grid), dim3(64), lds, st, g, recs, n_recs, deleted, maxu);
-    return hipGetLastError();
+    return launch_with_lds(k_fill_gaps<L, C>, dim3(grid), dim3(64), lds, st, g, recs, n_recs, deleted, maxu);
   }
 };
 template <int L, int C>
@@ -4814,14 +4777,8 @@ struct GapsWgLauncher {
       return hipErrorInvalidValue; // wg_prune: rows of at most 8 KB
     } else {
       const size_t lds = fill_gaps_wg_lds_bytes(wg_capmax(g), g.row_stride, SL);
-      if (lds > 65536) {
-        hipError_t rc = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fill_gaps_wg<L, C>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (rc != hipSuccess) return rc;
-      }
-      hipLaunchKernelGGL((k_fill_gaps_wg<L, C>), dim3(grid), dim3(256), lds, st, g, recs, n_recs, deleted, bitmaps,
-                         words, bm, maxb, keys, sorted, SL);
-      return hipGetLastError();
+      return launch_with_lds(k_fill_gaps_wg<L, C>, dim3(grid), dim3(256), lds, st, g, recs, n_recs, deleted, bitmaps,
+                             words, bm, maxb, keys, sorted, SL);
     }
   }
 };
