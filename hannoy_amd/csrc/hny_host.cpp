@@ -1898,18 +1898,13 @@ int hny_builder_search(hny_builder *b, uint32_t lo, uint32_t hi, void *sel_dev) 
     }
     if (b->wave_prune_only)
       return hnyk_prune(b->g, p, b->shape, (int)std::min<uint32_t>(p.hi - p.lo, b->walk_slots), st);
-    return hnyk_prune_wg(b->g, p, b->shape, b->stage_rows, 4, (int)std::min<uint32_t>(p.hi - p.lo, 2048), st);
+    return hnyk_prune_wg(b->g, p, b->shape, b->stage_rows, (int)std::min<uint32_t>(p.hi - p.lo, 2048), st);
   };
   u32 *queues = b->d_nseg.p + 4; // 16 work counters: the descent + one per layer of the batch
   u32 *xqueues = queues + 16;    // the same 16, as 8 per-XCD counters each (WalkArgs.xcd_tile)
   HIP_TRY(hipMemsetAsync(queues, 0, (16 + 8 * 16) * 4, b->stream));
   HIP_TRY(hipMemsetAsync(b->d_pool_ctr.p, 0, b->d_pool_ctr.n * 4, b->stream));
   b->pool_ctr_used = 0;
-  // one walk launch: rows <= 512 B go to the four-queries-per-wave kernel first, and the one-wave
-  // kernel then takes the members it gave up on (none, normally) from the retry list
-  auto launch_walk_fast = [&](const WalkArgs &w, hipStream_t st) -> hipError_t {
-    return hnyk_walk(b->g, w, b->shape, (int)std::min<uint32_t>(w.hi - w.lo, b->walk_slots), st);
-  };
   // one walk launch + its safety net: the members whose tie pool overflowed (none, normally) are listed on
   // the device and walked again by k_walk_heap, which reads the count itself — no host round trip
   auto launch_walk = [&](WalkArgs w, hipStream_t st) -> hipError_t {
@@ -1924,7 +1919,7 @@ int hny_builder_search(hny_builder *b, uint32_t lo, uint32_t hi, void *sel_dev) 
     const bool no_retry = !pool_retry_env(w);
     w.pool_retry = no_retry ? nullptr : b->d_pool_retry.p;
     w.n_pool_retry = pc;
-    hipError_t e = launch_walk_fast(w, st);
+    hipError_t e = hnyk_walk(b->g, w, b->shape, (int)std::min<uint32_t>(w.hi - w.lo, b->walk_slots), st);
     if (e != hipSuccess || no_retry) return e;
     WalkArgs h = w;
     h.queue = pc + 1;

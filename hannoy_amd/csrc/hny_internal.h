@@ -281,8 +281,7 @@ hipError_t hnyk_segments(const u64 *keys, u32 n_ops, u32 *seg_start, u32 *n_seg,
 hipError_t hnyk_apply(const GraphDev &g, const ApplyArgs &a, LaunchShape s, int grid, hipStream_t st);
 // the segments that cannot overflow, one thread each (a.deferred must be set); the rest -> a.deferred
 hipError_t hnyk_apply_append(const GraphDev &g, const ApplyArgs &a, hipStream_t st);
-hipError_t hnyk_prune_wg(const GraphDev &g, const PruneArgs &a, LaunchShape s, int SL, int nw, int grid,
-                         hipStream_t st);
+hipError_t hnyk_prune_wg(const GraphDev &g, const PruneArgs &a, LaunchShape s, int SL, int grid, hipStream_t st);
 // robust_prune for rows <= 512 B: one wave per query, 8 candidates at a time (SL = selected rows staged in LDS)
 bool hnyk_prune_n8_ok(const GraphDev &g, const PruneArgs &a, LaunchShape s);
 hipError_t hnyk_prune_n8(const GraphDev &g, const PruneArgs &a, LaunchShape s, int SL, int grid, hipStream_t st);
@@ -316,8 +315,8 @@ size_t hnyk_walk_lds_bytes(u32 rcap, u32 eps_cap);
 // the build kernels specialised for metric N-1 (hny_kernels.hip compiled with -DHNY_PART=N)
 #define HNY_DECL_SP(N)                                                                                      \
   hipError_t hnyk_walk_sp##N(const GraphDev &g, const WalkArgs &a, LaunchShape s, int grid, hipStream_t st); \
-  hipError_t hnyk_prune_wg_sp##N(const GraphDev &g, const PruneArgs &a, LaunchShape s, int SL, int nw,      \
-                                 int grid, hipStream_t st);                                                 \
+  hipError_t hnyk_prune_wg_sp##N(const GraphDev &g, const PruneArgs &a, LaunchShape s, int SL, int grid,    \
+                                 hipStream_t st);                                                           \
   hipError_t hnyk_prune_n8_sp##N(const GraphDev &g, const PruneArgs &a, int lpro, int SL, int grid,         \
                                  hipStream_t st);                                                           \
   hipError_t hnyk_apply_n8_sp##N(const GraphDev &g, const ApplyArgs &a, int lpro, int SL, int grid,         \

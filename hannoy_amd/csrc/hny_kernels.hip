@@ -174,6 +174,48 @@ __device__ __forceinline__ u32 partial_bin(const float4 (&q)[NCH], const float4 
   return pc;
 }
 
+// ---------------------------------------------------------------------------------------------
+// 8-lane rows.  Rows of at most 32 units (128-d f32, 1024-bit codes) are held by EIGHT lanes whatever their
+// wave order's group is: lane t of the eight owns units t, t + 8 (, t + 16, t + 24) — NQ = 1, 2 or 4 units per
+// lane for the order of an 8-, 16- or 32-lane group.  dist16 (and dist_rows_narrow on it), dist8 and
+// prune_n8_core stand on these four and on nothing else of their own.
+// ---------------------------------------------------------------------------------------------
+template <int NQ>
+__device__ __forceinline__ void load_row8(const unsigned char *p, int t, u32 n16, float4 (&r)[NQ]) {
+  load_row<8, NQ>(p, t, n16, r);
+}
+template <int NQ>
+__device__ __forceinline__ void load_row8_lds(const unsigned char *p, int t, u32 n16, float4 (&r)[NQ]) {
+  load_row_lds<8, NQ>(p, t, n16, r);
+}
+template <int NQ>
+__device__ __forceinline__ void store_row8(unsigned char *p, int t, u32 n16, const float4 (&r)[NQ]) {
+#pragma unroll
+  for (int c = 0; c < NQ; c++) {
+    const u32 f = (u32)(c * 8 + t);
+    if (f < n16) *reinterpret_cast<float4 *>(p + (size_t)f * 16) = r[c];
+  }
+}
+// The lane's f32 partial of a row of an 8 * NQ-lane group; an 8-lane butterfly (off = 4, 2, 1) of it is that
+// group's wave order, bit for bit.  In the wave order lane l of the group runs one 4-element chain over unit l
+// and the xor butterfly then adds p[l] + p[l ^ 16], that + its partner at off = 8, and so on.  Here lane t holds
+// the chains of units t, t + 8, t + 16, t + 24 and adds them in the order of those first steps — off = 16:
+// p0 + p2 and p1 + p3, off = 8: their sum — before the butterfly goes on across the 8 lanes.  (IEEE addition
+// commutes, so which lane of a pair is "this" one does not matter.)  Bit codes need none of this: their partial
+// is an integer sum, partial_bin<NQ>.
+template <int NQ>
+__device__ __forceinline__ float partial8(int mclass, const float4 (&q)[NQ], const float4 (&r)[NQ]) {
+  float pu[NQ];
+#pragma unroll
+  for (int c = 0; c < NQ; c++) {
+    const float4 qc[1] = {q[c]}, rc[1] = {r[c]};
+    pu[c] = partial_f32<1>(mclass, qc, rc);
+  }
+  if constexpr (NQ == 4) return (pu[0] + pu[2]) + (pu[1] + pu[3]); // off = 16, then off = 8
+  else if constexpr (NQ == 2) return pu[0] + pu[1];                // off = 8
+  else return pu[0];
+}
+
 // value of lane (lane ^ OFF), OFF a power of two: the data movement of __shfl_xor(v, OFF, 64) without
 // its per-call index arithmetic (xor, width clamp, select, shift = 4 VALU instructions in front of
 // every ds_bpermute) and without the trip through the LDS pipe, which queues behind the row reads:
@@ -535,91 +577,82 @@ __device__ __forceinline__ void dist_rows(const GraphDev &g, const float4 (&q)[N
   }
 }
 
-// The wave order of a 16- or 32-lane row group, computed by EIGHT lanes per row (k_walk, rows of
-// 9..32 sixteen-byte units: 128-d f32, 129..512-B codes).  One wave-wide load then covers 8 rows
-// instead of 4 or 2, and the per-group instructions (row id, address, exec mask, shuffles,
-// finaliser) are paid once per 8 rows: ~90 instead of ~220 VALU instructions for the ~11 new rows of
-// an expansion at 128-d.  Bit-identical by construction: lane t holds units t, t + 8 (, t + 16,
-// t + 24), runs the same 4-element chain per unit and adds the per-unit partials in the order of the
-// xor butterfly's first steps — off = 16: p[t] + p[t ^ 16], off = 8: that + its partner — before
-// the butterfly continues across the 8 lanes with off = 4, 2, 1.
+// The wave order of an 8-, 16- or 32-lane row group, computed by EIGHT lanes per row (rows of at most 32
+// sixteen-byte units: 128-d f32, 512-B codes; see partial8).  One wave-wide load then covers 8 rows instead of
+// 4 or 2, and the per-group instructions (row id, address, exec mask, shuffles, finaliser) are paid once per
+// 8 rows: ~90 instead of ~220 VALU instructions for the ~11 new rows of an expansion at 128-d.
+//
+// dist16: distances of rows ids[k0 .. k0 + 16) (as far as they are < n) to the query.  The lane with
+// (t & 3) == 0 of lane group `sub` returns row ri = k0 + 8 * (t >> 2) + sub.  fold2 on both load groups: for the
+// rows of group 0 its pair sums are the butterfly's (a second group of zeros only feeds the lanes of rows that do
+// not exist), so the values are the same whether the second group holds rows or not.  ONE: take the plain
+// butterfly when it does not (fewer instructions for that step; every lane of a group then holds the row of
+// group 0).
+template <int LPRO, bool ONE = false>
+__device__ __forceinline__ void dist16(const GraphDev &g, const float4 (&q)[LPRO / 8], float qn, const u32 *ids,
+                                       int n, int k0, float &d, u32 &rid, int &ri) {
+  constexpr int NQ = LPRO / 8;
+  const int ln = HNY_LANE, t = ln & 7, sub = ln >> 3;
+  float4 r[2][NQ];
+  float rn[2];
+  u32 rids[2];
+#pragma unroll
+  for (int u = 0; u < 2; u++) {
+    int x = k0 + u * 8 + sub;
+    x = x < n - 1 ? x : n - 1;
+    rids[u] = ids[x];
+  }
+  const bool two = k0 + 8 < n; // wave-uniform: the second load group holds rows
+#pragma unroll
+  for (int u = 0; u < 2; u++) {
+    rn[u] = 0.f;
+    if (u == 0 || two) {
+      load_row8<NQ>(g.rows + (size_t)rids[u] * g.row_stride, t, g.n16, r[u]);
+      if (g.norms) rn[u] = g.norms[rids[u]];
+    } else {
+#pragma unroll
+      for (int c = 0; c < NQ; c++) r[u][c] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
+  int j = fold2_row<8>();
+  if (g.mclass == MC_BIN) {
+    const u32 p0 = partial_bin<NQ>(q, r[0]), p1 = partial_bin<NQ>(q, r[1]);
+    u32 y;
+    if (!ONE || two) {
+      y = fold2<8, u32>(p0, p1);
+    } else {
+      y = butterfly_u32<8>(p0);
+      j = 0;
+    }
+    d = finalize_bin(g, y, qn, j ? rn[1] : rn[0]);
+  } else {
+    const float p0 = partial8<NQ>(g.mclass, q, r[0]), p1 = partial8<NQ>(g.mclass, q, r[1]);
+    float y;
+    if (!ONE || two) {
+      y = fold2<8, float>(p0, p1);
+    } else {
+      y = butterfly_f32<8>(p0);
+      j = 0;
+    }
+    d = finalize_f32(g, y, qn, j ? rn[1] : rn[0]);
+  }
+  rid = j ? rids[1] : rids[0];
+  ri = k0 + j * 8 + sub;
+}
+
+// distances from the query to rows ids[0..n) (LDS) -> out[0..n) (LDS), 8 lanes per row
 template <int LPRO>
 __device__ __forceinline__ void dist_rows_narrow(const GraphDev &g, const float4 (&q)[LPRO / 8], float qn,
                                                  const u32 *ids, int n, float *out) {
   static_assert(LPRO == 16 || LPRO == 32, "8 lanes stand in for 16 or 32");
-  constexpr int NQ = LPRO / 8, U = 2;
-  const int ln = HNY_LANE, t = ln & 7, sub = ln >> 3;
-  const int j2 = fold2_row<8>();
-  for (int k0 = 0; k0 < n; k0 += 8 * U) {
-    float4 r[U][NQ];
-    float rn[U];
-    u32 rids[U];
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      int ri = k0 + u * 8 + sub;
-      if (ri > n - 1) ri = n - 1;
-      rids[u] = ids[ri];
-    }
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      rn[u] = 0.f;
-      if (k0 + u * 8 < n) { // wave-uniform
-        const unsigned char *p = g.rows + (size_t)rids[u] * g.row_stride;
-#pragma unroll
-        for (int c = 0; c < NQ; c++) {
-          const u32 f = (u32)(c * 8 + t);
-          r[u][c] = f < g.n16 ? *reinterpret_cast<const float4 *>(p + (size_t)f * 16)
-                              : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        if (g.norms) rn[u] = g.norms[rids[u]];
-      } else {
-#pragma unroll
-        for (int c = 0; c < NQ; c++) r[u][c] = make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-    }
-    const bool two = k0 + 8 < n; // wave-uniform: the second group holds rows
+  const int t = HNY_LANE & 7;
+  for (int k0 = 0; k0 < n; k0 += 16) {
     float d;
-    int j;
-    if (g.mclass == MC_BIN) {
-      u32 pc[U];
-#pragma unroll
-      for (int u = 0; u < U; u++) pc[u] = partial_bin<NQ>(q, r[u]);
-      u32 y;
-      if (two) {
-        y = fold2<8, u32>(pc[0], pc[1]);
-        j = j2;
-      } else {
-        y = butterfly_u32<8>(pc[0]);
-        j = 0;
-      }
-      d = finalize_bin(g, y, qn, j ? rn[1] : rn[0]);
-    } else {
-      float pa[U];
-#pragma unroll
-      for (int u = 0; u < U; u++) {
-        float pu[NQ];
-#pragma unroll
-        for (int c = 0; c < NQ; c++) {
-          const float4 qc[1] = {q[c]}, rc[1] = {r[u][c]};
-          pu[c] = partial_f32<1>(g.mclass, qc, rc);
-        }
-        if constexpr (NQ == 4)
-          pa[u] = (pu[0] + pu[2]) + (pu[1] + pu[3]); // off = 16, then off = 8
-        else
-          pa[u] = pu[0] + pu[1];                     // off = 8
-      }
-      float y;
-      if (two) {
-        y = fold2<8, float>(pa[0], pa[1]);
-        j = j2;
-      } else {
-        y = butterfly_f32<8>(pa[0]);
-        j = 0;
-      }
-      d = finalize_f32(g, y, qn, j ? rn[1] : rn[0]);
-    }
-    const int ri = k0 + j * 8 + sub;
-    if ((two ? (t & 3) == 0 : t == 0) && ri < n) out[ri] = d;
+    u32 rid;
+    int ri;
+    dist16<LPRO, true>(g, q, qn, ids, n, k0, d, rid, ri);
+    // (a lone load group went through the plain butterfly: every lane of a row's eight holds it, lane 0 stores)
+    if ((k0 + 8 < n ? (t & 3) == 0 : t == 0) && ri < n) out[ri] = d;
   }
 }
 
@@ -1521,66 +1554,6 @@ __device__ __forceinline__ bool visb_insert(const VisB &v, Visited &vis, u32 id,
     isnew = isnew || onew;
   }
   return isnew;
-}
-
-// distances of rows ids[k0 .. k0 + 16) (as far as they are < n) to the query: the lane with (t & 3) == 0 of
-// lane group `sub` returns row ri = k0 + 8 * (t >> 2) + sub (wave order of an LPRO-lane row group, computed
-// by 8 lanes exactly as dist_rows_narrow does; LPRO == 8 is the plain 8-lane butterfly)
-template <int LPRO>
-__device__ __forceinline__ void dist16(const GraphDev &g, const float4 (&q)[LPRO / 8], float qn, const u32 *ids,
-                                       int n, int k0, float &d, u32 &rid, int &ri) {
-  constexpr int NQ = LPRO / 8;
-  const int ln = HNY_LANE, t = ln & 7, sub = ln >> 3;
-  const int j = (t >> 2) & 1; // fold2_row<8>()
-  float4 r[2][NQ];
-  float rn[2];
-  u32 rids[2];
-#pragma unroll
-  for (int u = 0; u < 2; u++) {
-    int x = k0 + u * 8 + sub;
-    x = x < n - 1 ? x : n - 1;
-    rids[u] = ids[x];
-  }
-  const bool two = k0 + 8 < n; // wave-uniform: the second load group holds rows
-#pragma unroll
-  for (int u = 0; u < 2; u++) {
-    rn[u] = 0.f;
-    if (u == 0 || two) {
-      const unsigned char *p = g.rows + (size_t)rids[u] * g.row_stride;
-#pragma unroll
-      for (int c = 0; c < NQ; c++) {
-        const u32 f = (u32)(c * 8 + t);
-        r[u][c] = f < g.n16 ? *reinterpret_cast<const float4 *>(p + (size_t)f * 16) : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-      if (g.norms) rn[u] = g.norms[rids[u]];
-    } else {
-#pragma unroll
-      for (int c = 0; c < NQ; c++) r[u][c] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  }
-  // fold2 on both groups always: for the rows of group 0 its pair sums are the butterfly's (a second group
-  // of zeros only feeds the lanes of rows that do not exist)
-  if (g.mclass == MC_BIN) {
-    const u32 y = fold2<8, u32>(partial_bin<NQ>(q, r[0]), partial_bin<NQ>(q, r[1]));
-    d = finalize_bin(g, y, qn, j ? rn[1] : rn[0]);
-  } else {
-    float pa[2];
-#pragma unroll
-    for (int u = 0; u < 2; u++) {
-      float pu[NQ];
-#pragma unroll
-      for (int c = 0; c < NQ; c++) {
-        const float4 qc[1] = {q[c]}, rc[1] = {r[u][c]};
-        pu[c] = partial_f32<1>(g.mclass, qc, rc);
-      }
-      if constexpr (NQ == 4) pa[u] = (pu[0] + pu[2]) + (pu[1] + pu[3]); // off = 16, then off = 8
-      else if constexpr (NQ == 2) pa[u] = pu[0] + pu[1];                // off = 8
-      else pa[u] = pu[0];
-    }
-    d = finalize_f32(g, fold2<8, float>(pa[0], pa[1]), qn, j ? rn[1] : rn[0]);
-  }
-  rid = j ? rids[1] : rids[0];
-  ri = k0 + j * 8 + sub;
 }
 
 // value of lane - K within its row of 16 lanes (v_mov_b32_dpp row_shr:K); lanes without a source get 0
@@ -3164,6 +3137,7 @@ __global__ __launch_bounds__(64) void k_prune(GraphDev g, PruneArgs a) {
 // every candidate row is read from HBM once (prefetched one candidate ahead) and compared against
 // the selected rows held in LDS; the 4 waves split the selected rows.  Same distances, same result.
 // ---------------------------------------------------------------------------------------------
+constexpr int WG_WAVES = 4; // waves of the workgroup = candidates per chunk
 struct WgPruneLds {
   u64 *S;          // [HNY_MAX_CAP] selected keys
   u32 *s_ids;      // [HNY_MAX_CAP]
@@ -3171,22 +3145,21 @@ struct WgPruneLds {
   int *surv;       // [2][8] chunk member survived the test against S (by chunk parity)
   u32 *vmask;      // [8] bit j: chunk member violates against chunk member j
   float *cnorm;    // [8]
-  unsigned char *cbuf;  // [NW][row_stride] the chunk's candidate rows
+  unsigned char *cbuf;  // [WG_WAVES][row_stride] the chunk's candidate rows
   unsigned char *stage; // [SL][row_stride] selected rows
   int SL;          // staged rows (multiple of 64/LPR)
 };
 
-// robust_prune for an NW-wave workgroup (NW = 4 or 8).  `exists i in S: bits(d(c,i)*alpha) <
-// bits(dq)` does not depend on the order in which S is scanned, so NW consecutive candidates are
+// robust_prune for a workgroup of WG_WAVES waves.  `exists i in S: bits(d(c,i)*alpha) <
+// bits(dq)` does not depend on the order in which S is scanned, so WG_WAVES consecutive candidates are
 // tested concurrently, one per wave, against the selected set as it stood before the chunk (rows
 // from LDS, early exit); the survivors are then tested against each other (rows exchanged through
 // LDS) and the chunk is resolved in candidate order — exactly the sequential outcome, with 1 to 3
-// barriers per NW candidates (see there).  Each wave streams its next candidate row from HBM one chunk ahead.
-template <int LPR, int NCH, int NW>
+// barriers per chunk (see there).  Each wave streams its next candidate row from HBM one chunk ahead.
+template <int LPR, int NCH>
 __device__ __forceinline__ int wg_prune(const GraphDev &g, const u64 *list, int n, int cap, const WgPruneLds &L,
                                         u64 &evals) {
   constexpr int RPG = 64 / LPR;
-  static_assert(NW == 4 || NW == 8, "chunk of 4 or 8 candidates");
   // (w through readfirstlane: the compiler then knows every per-wave condition below is uniform)
   const int tid = threadIdx.x, w = __builtin_amdgcn_readfirstlane(tid >> 6), ln = tid & 63, t = ln % LPR, sub = ln / LPR;
   const int j4 = fold4_row<LPR>();
@@ -3199,7 +3172,7 @@ __device__ __forceinline__ int wg_prune(const GraphDev &g, const u64 *list, int 
     if (g.norms) nxt_n = g.norms[c0];
   }
   __syncthreads();
-  for (int base = 0; base < n && s_len < cap; base += NW) {
+  for (int base = 0; base < n && s_len < cap; base += WG_WAVES) {
     const int ci = base + w;
     const bool have = ci < n;
     float4 c[NCH];
@@ -3217,8 +3190,8 @@ __device__ __forceinline__ int wg_prune(const GraphDev &g, const u64 *list, int 
         if (f < g.n16) *reinterpret_cast<float4 *>(cb + (size_t)f * 16) = c[k];
       }
     }
-    if (ci + NW < n) {
-      const u32 nx = (u32)(list[ci + NW] & 0xFFFFFFFFull);
+    if (ci + WG_WAVES < n) {
+      const u32 nx = (u32)(list[ci + WG_WAVES] & 0xFFFFFFFFull);
       load_row<LPR, NCH>(g.rows + (size_t)nx * g.row_stride, t, g.n16, nxt);
       if (g.norms) nxt_n = g.norms[nx];
     }
@@ -3286,7 +3259,7 @@ __device__ __forceinline__ int wg_prune(const GraphDev &g, const u64 *list, int 
     // only around the intra-chunk tests (two or more survivors), a third only when S changed.  The
     // survivor flags alternate between two sets, so a wave that runs ahead into the next chunk never
     // overwrites flags a slower wave is still reading (they meet again at that chunk's first barrier).
-    int *sv = L.surv + ((base / NW) & 1) * 8;
+    int *sv = L.surv + ((base / WG_WAVES) & 1) * 8;
     if (ln == 0) {
       sv[w] = surv ? 1 : 0;
       L.cnorm[w] = cn;
@@ -3294,7 +3267,7 @@ __device__ __forceinline__ int wg_prune(const GraphDev &g, const u64 *list, int 
     __syncthreads();
     u32 svmask = 0;
 #pragma unroll
-    for (int j = 0; j < NW; j++) svmask |= (sv[j] != 0 ? 1u : 0u) << j;
+    for (int j = 0; j < WG_WAVES; j++) svmask |= (sv[j] != 0 ? 1u : 0u) << j;
     svmask = (u32)__builtin_amdgcn_readfirstlane((int)svmask);
     const bool need_c = (svmask & (svmask - 1u)) != 0u; // two or more survivors
     // C: survivors against the earlier survivors of the chunk (folded passes over cbuf, 4 rows each)
@@ -3302,7 +3275,7 @@ __device__ __forceinline__ int wg_prune(const GraphDev &g, const u64 *list, int 
     if (need_c) {
       if (surv && (svmask & ((1u << w) - 1u)) != 0u) {
 #pragma unroll
-        for (int q4 = 0; q4 < NW / 4; q4++) {
+        for (int q4 = 0; q4 < WG_WAVES / 4; q4++) {
           if (q4 * 4 < w) { // wave-uniform
             float4 r[4][NCH];
 #pragma unroll
@@ -3337,7 +3310,7 @@ __device__ __forceinline__ int wg_prune(const GraphDev &g, const u64 *list, int 
     u32 selmask = 0;
     int cnt = s_len;
 #pragma unroll
-    for (int j = 0; j < NW; j++) {
+    for (int j = 0; j < WG_WAVES; j++) {
       const u32 vmj = need_c ? L.vmask[j] : 0u;
       if (cnt < cap && ((svmask >> j) & 1u) != 0u && (vmj & selmask) == 0u) { // :577-579, :583-592
         selmask |= 1u << j;
@@ -3372,11 +3345,11 @@ __host__ __device__ inline u32 wg_capmax(const GraphDev &g) {
   const u32 c = g.M0 > g.M ? g.M0 : g.M;
   return (c + 63u) / 64u * 64u;
 }
-__host__ __device__ inline size_t wg_prune_lds_bytes(u32 rcap, u32 row_stride, int SL, int NW, u32 capmax) {
-  return (size_t)rcap * 8 + (size_t)capmax * (8 + 4 + 4) + 128 + (size_t)(SL + NW) * row_stride;
+__host__ __device__ inline size_t wg_prune_lds_bytes(u32 rcap, u32 row_stride, int SL, u32 capmax) {
+  return (size_t)rcap * 8 + (size_t)capmax * (8 + 4 + 4) + 128 + (size_t)(SL + WG_WAVES) * row_stride;
 }
 
-__device__ __forceinline__ WgPruneLds wg_prune_carve(unsigned char *base, int SL, u32 row_stride, int NW, u32 capmax) {
+__device__ __forceinline__ WgPruneLds wg_prune_carve(unsigned char *base, int SL, u32 row_stride, u32 capmax) {
   WgPruneLds L;
   L.S = reinterpret_cast<u64 *>(base);
   L.s_ids = reinterpret_cast<u32 *>(L.S + capmax);
@@ -3385,7 +3358,7 @@ __device__ __forceinline__ WgPruneLds wg_prune_carve(unsigned char *base, int SL
   L.vmask = reinterpret_cast<u32 *>(L.surv + 16);
   L.cnorm = reinterpret_cast<float *>(L.vmask + 8);
   L.cbuf = reinterpret_cast<unsigned char *>(L.cnorm + 8);
-  L.stage = L.cbuf + (size_t)NW * row_stride;
+  L.stage = L.cbuf + (size_t)WG_WAVES * row_stride;
   L.SL = SL;
   return L;
 }
@@ -3393,29 +3366,29 @@ __device__ __forceinline__ WgPruneLds wg_prune_carve(unsigned char *base, int SL
 // wg_prune; the specialised kernels (SP != 0) on rows that fill every lane's chunks (768-d, 1024-d, 128-d, 1024 bits
 // ...) run it on a copy of g whose n16 is a constant, so the per-chunk bounds guards of the row loads fold away
 // (~20 % of a pass)
-template <int LPR, int NCH, int NW, int SP>
+template <int LPR, int NCH, int SP>
 __device__ __forceinline__ int wg_prune_sp(const GraphDev &g, const u64 *list, int n, int cap, const WgPruneLds &L,
                                            u64 &evals) {
   if (SP != 0 && g.n16 == (u32)(LPR * NCH) && g.row_stride == (u32)(LPR * NCH * 16)) {
     GraphDev gf = g;
     gf.n16 = (u32)(LPR * NCH);
     gf.row_stride = (u32)(LPR * NCH * 16);
-    return wg_prune<LPR, NCH, NW>(gf, list, n, cap, L, evals);
+    return wg_prune<LPR, NCH>(gf, list, n, cap, L, evals);
   }
-  return wg_prune<LPR, NCH, NW>(g, list, n, cap, L, evals);
+  return wg_prune<LPR, NCH>(g, list, n, cap, L, evals);
 }
 
 // rows up to 3 KB: 4 workgroups of 4 waves per CU is what the LDS carve allows, keep the registers there
-constexpr int wg_waves_per_simd(int nch, int nw) { return nw == 4 && nch <= 3 ? 4 : 1; }
+constexpr int wg_waves_per_simd(int nch) { return nch <= 3 ? 4 : 1; }
 
-template <int LPR, int NCH, int NW, int SP>
-__global__ __launch_bounds__(NW * 64, wg_waves_per_simd(NCH, NW)) void k_prune_wg(GraphDev g_in, PruneArgs a, int SL) {
+template <int LPR, int NCH, int SP>
+__global__ __launch_bounds__(WG_WAVES * 64, wg_waves_per_simd(NCH)) void k_prune_wg(GraphDev g_in, PruneArgs a, int SL) {
   GraphDev g = g_in;
   specialize<SP>(g);
   extern __shared__ __align__(16) unsigned char smem[];
   u64 *list = reinterpret_cast<u64 *>(smem);
   const bool list_global = SP == 0 && a.list_global != 0; // lists too long for LDS: pruned straight from HBM
-  WgPruneLds L = wg_prune_carve(smem + (list_global ? (size_t)0 : (size_t)a.rcap * 8), SL, g.row_stride, NW, wg_capmax(g));
+  WgPruneLds L = wg_prune_carve(smem + (list_global ? (size_t)0 : (size_t)a.rcap * 8), SL, g.row_stride, wg_capmax(g));
   const int tid = threadIdx.x;
   u64 evals = 0;
   // Workgroups go to the XCDs round robin, so with member = blockIdx + k * gridDim neighbouring members (locality
@@ -3442,7 +3415,7 @@ __global__ __launch_bounds__(NW * 64, wg_waves_per_simd(NCH, NW)) void k_prune_w
       for (int e = tid; e < n; e += blockDim.x) list[e] = a.cand[(size_t)m * a.rcap + e];
     }
     __syncthreads();
-    store_sel<NW * 64>(a, m, L.S, wg_prune_sp<LPR, NCH, NW, SP>(g, list, n, (int)a.cap, L, evals));
+    store_sel<WG_WAVES * 64>(a, m, L.S, wg_prune_sp<LPR, NCH, SP>(g, list, n, (int)a.cap, L, evals));
     __syncthreads();
   }
   if ((tid & 63) == 0 && evals) atomicAdd(&g.stats[ST_EVALS_PRUNE], evals);
@@ -3460,25 +3433,14 @@ __global__ __launch_bounds__(NW * 64, wg_waves_per_simd(NCH, NW)) void k_prune_w
 //   (3) the survivors are taken in candidate order: the first joins S, the others are scored against
 //       that one new row, and so on — `exists i in S: bits(d(c, i) * alpha) < bits(d(c, q))` does not
 //       depend on the order in which S is scanned, so this is the sequential outcome (hnsw.rs:577-592).
-// No workgroup barrier anywhere; the wave order of a 16- / 32-lane row is computed by 8 lanes exactly
-// as dist_rows_narrow does (unit partials added in the butterfly's own order).
+// No workgroup barrier anywhere; the wave order of a 16- / 32-lane row is computed by 8 lanes (partial8).
 // ---------------------------------------------------------------------------------------------
 template <int LPRO>
 __device__ __forceinline__ float dist8(const GraphDev &g, const float4 (&c)[LPRO / 8], const float4 (&r)[LPRO / 8],
                                        float cn, float rn) {
   constexpr int NQ = LPRO / 8;
   if (g.mclass == MC_BIN) return finalize_bin(g, butterfly_u32<8>(partial_bin<NQ>(c, r)), cn, rn);
-  float pu[NQ];
-#pragma unroll
-  for (int k = 0; k < NQ; k++) {
-    const float4 ck[1] = {c[k]}, rk[1] = {r[k]};
-    pu[k] = partial_f32<1>(g.mclass, ck, rk);
-  }
-  float pa;
-  if constexpr (NQ == 4) pa = (pu[0] + pu[2]) + (pu[1] + pu[3]); // off = 16, then off = 8
-  else if constexpr (NQ == 2) pa = pu[0] + pu[1];                // off = 8
-  else pa = pu[0];
-  return finalize_f32(g, butterfly_f32<8>(pa), cn, rn);
+  return finalize_f32(g, butterfly_f32<8>(partial8<NQ>(g.mclass, c, r)), cn, rn);
 }
 __host__ __device__ inline size_t prune_n8_lds_bytes(u32 rcap, u32 row_stride, int SL) {
   return (size_t)rcap * 8 + (size_t)HNY_MAX_CAP * (8 + 4 + 4) + (size_t)(SL + 1) * row_stride;
@@ -3497,16 +3459,16 @@ __host__ __device__ inline size_t apply_n8_lds_bytes(u32 row_stride, int SL) {
 // per counted evaluation where a full step needs ~5.  Once S holds K0 >= 2 rows, the remaining candidates are
 // therefore first run past those K0 rows alone — one or two steps per chunk of eight, every group busy, rows
 // streamed a chunk ahead — and only the survivors (compacted in place, order kept) go through the chunks, starting
-// at row K0.  A candidate's tests are the same tests in the same order (rows 0 .. K0-1 now, the rest later): same
-// selection, same evaluation count; a survivor's row is fetched a second time.
+// at row K0.  A candidate's tests are the same tests in the same order (rows 0 .. K0-1 now, the rest later): the
+// same selection; a survivor's row is fetched a second time.  The evaluation count is NOT the unfiltered one on
+// lists that fill: the chunks stop where S reaches `cap`, the filter has by then tested the candidates behind
+// that point against its K0 rows, and those tests are counted.  n_evals_prune / n_evals_apply are what the
+// kernels computed (include/hannoy_amd.h), not the reference's count.
 #ifndef HNY_PRUNE_FILTER
 #define HNY_PRUNE_FILTER 1
 #endif
 #ifndef HNY_PRUNE_FILTER_MIN
 #define HNY_PRUNE_FILTER_MIN 40 // candidates left for the filter to be worth its second fetch
-#endif
-#ifndef HNY_PRUNE_TOUCH
-#define HNY_PRUNE_TOUCH 0
 #endif
 #ifndef HNY_PRUNE_FILTER_ROWS
 #define HNY_PRUNE_FILTER_ROWS 4 // rows of S the filter tests (the closest selected neighbours reject the most; 2: C4 prune 0.197 s, 4: 0.189, all: 0.190)
@@ -3517,76 +3479,38 @@ __device__ __forceinline__ int prune_n8_core(const GraphDev &g, u64 *list, int n
                                              u64 &evals) {
   constexpr int NQ = LPRO / 8;
   const int ln = HNY_LANE, t = ln & 7, gidx = ln >> 3;
-  auto load8 = [&](const unsigned char *row, float4 (&r)[NQ]) __attribute__((always_inline)) {
-#pragma unroll
-    for (int k = 0; k < NQ; k++) {
-      const u32 f = (u32)(k * 8 + t);
-      r[k] = f < g.n16 ? *reinterpret_cast<const float4 *>(row + (size_t)f * 16) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  };
-  auto load8_lds = [&](const unsigned char *row, float4 (&r)[NQ]) __attribute__((always_inline)) {
-    const unsigned lp = (unsigned)(size_t)row;
-#pragma unroll
-    for (int k = 0; k < NQ; k++) {
-      const u32 f = (u32)(k * 8 + t);
-      if (f < g.n16) {
-        const f32x4_t v = *reinterpret_cast<lds_cf4 *>((size_t)(lp + f * 16u));
-        r[k] = make_float4(v.x, v.y, v.z, v.w);
-      } else {
-        r[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-    }
-  };
   int s_len = 0;
   float4 nxt[NQ];
   float nxt_n = 0.f;
   // the row of candidate ci (this group's member of the chunk after next) on its way into `nxt`
-  u32 touched = 0u; // (sink of the touch loads below: never true, keeps them alive)
   auto prefetch = [&](int ci) __attribute__((always_inline)) {
     if (ci < n) {
       const u32 nx = (u32)(list[ci] & 0xFFFFFFFFull);
-      load8(g.rows + (size_t)nx * g.row_stride, nxt);
+      load_row8<NQ>(g.rows + (size_t)nx * g.row_stride, t, g.n16, nxt);
       if (g.norms) nxt_n = g.norms[nx];
     }
-#if HNY_PRUNE_TOUCH
-    // and the row of the candidate one chunk further on its way into the L2: one dword per 128-B line (lane t of
-    // the group touches line t), so that the load above finds it there a chunk later instead of in HBM
-    if (ci + 8 < n) {
-      const u32 n2 = (u32)(list[ci + 8] & 0xFFFFFFFFull);
-      const u32 off = (u32)t * 128u;
-      if (off < g.row_stride) touched |= *reinterpret_cast<const u32 *>(g.rows + (size_t)n2 * g.row_stride + off) & 0x7FC00000u;
-    }
-#endif
   };
 #pragma unroll
   for (int k = 0; k < NQ; k++) nxt[k] = make_float4(0.f, 0.f, 0.f, 0.f);
   prefetch(gidx);
-  // one chunk: candidates [base, base + 8) against S rows [row0, s_len), then its survivors in candidate order
-  auto chunk = [&](const int base, const int row0) __attribute__((always_inline)) {
-    const int ci = base + gidx;
-    const bool have = ci < n;
-    float4 c[NQ];
-#pragma unroll
-    for (int k = 0; k < NQ; k++) c[k] = nxt[k];
-    const float cn = nxt_n;
-    const u64 ck = have ? list[ci] : 0ull;
-    const u32 cid = (u32)(ck & 0xFFFFFFFFull), cdb = (u32)(ck >> 32);
-    prefetch(ci + 8); // the next chunk's rows travel while this one is scored
-    // (2) against S as it stands
-    // two selected rows per step: `exists i in S` does not care about the order, and the two dependent chains
-    // of a step (LDS read -> fma chain -> 8-lane butterfly -> finaliser -> compare) then overlap inside the wave —
-    // this loop is bound by their latency, not by issue (k_prune_n8: vector port 0.32 busy)
+  // the candidate of every 8-lane group (have: the group holds one) against the selected rows [j0, j1), staged
+  // (below SL) or from L2 (beyond the stage, rare): does one of them violate?  Two selected rows per step:
+  // `exists i in S` does not care about the order, and the two dependent chains of a step (LDS read -> fma chain ->
+  // 8-lane butterfly -> finaliser -> compare) then overlap inside the wave — this loop is bound by their latency,
+  // not by issue (k_prune_n8: vector port 0.32 busy)
+  auto scan_S = [&](const float4 (&c)[NQ], const float cn, const u32 cdb, const bool have, const int j0,
+                    const int j1) __attribute__((always_inline)) {
     bool viol = false;
-    for (int j = row0; j < s_len; j += 2) {
+    for (int j = j0; j < j1; j += 2) {
       const u64 open = ballot(have && !viol);
       if (!open) break;
-      const bool two = j + 1 < s_len; // wave-uniform
+      const bool two = j + 1 < j1; // wave-uniform
       float4 r0[NQ], r1[NQ];
-      if (j < SL) load8_lds(stage + (size_t)j * g.row_stride, r0);
-      else load8(g.rows + (size_t)s_ids[j] * g.row_stride, r0); // beyond the stage (rare): from L2
+      if (j < SL) load_row8_lds<NQ>(stage + (size_t)j * g.row_stride, t, g.n16, r0);
+      else load_row8<NQ>(g.rows + (size_t)s_ids[j] * g.row_stride, t, g.n16, r0);
       if (two) {
-        if (j + 1 < SL) load8_lds(stage + (size_t)(j + 1) * g.row_stride, r1);
-        else load8(g.rows + (size_t)s_ids[j + 1] * g.row_stride, r1);
+        if (j + 1 < SL) load_row8_lds<NQ>(stage + (size_t)(j + 1) * g.row_stride, t, g.n16, r1);
+        else load_row8<NQ>(g.rows + (size_t)s_ids[j + 1] * g.row_stride, t, g.n16, r1);
       }
       const float d0 = dist8<LPRO>(g, c, r0, cn, s_norm[j]);
       bool v = fbits(d0 * g.alpha) < cdb; // hnsw.rs:585
@@ -3601,6 +3525,21 @@ __device__ __forceinline__ int prune_n8_core(const GraphDev &g, u64 *list, int n
       viol = viol || v;
       evals += (u64)(__popcll(open) >> 3) + (two ? (u64)(__popcll(counted) >> 3) : 0ull);
     }
+    return viol;
+  };
+  // one chunk: candidates [base, base + 8) against S rows [row0, s_len), then its survivors in candidate order
+  auto chunk = [&](const int base, const int row0) __attribute__((always_inline)) {
+    const int ci = base + gidx;
+    const bool have = ci < n;
+    float4 c[NQ];
+#pragma unroll
+    for (int k = 0; k < NQ; k++) c[k] = nxt[k];
+    const float cn = nxt_n;
+    const u64 ck = have ? list[ci] : 0ull;
+    const u32 cid = (u32)(ck & 0xFFFFFFFFull), cdb = (u32)(ck >> 32);
+    prefetch(ci + 8); // the next chunk's rows travel while this one is scored
+    // (2) against S as it stands
+    const bool viol = scan_S(c, cn, cdb, have, row0, s_len);
     // (3) the survivors, in candidate order
     u64 sv = ballot(have && !viol && t == 0);
     while (sv && s_len < cap) {
@@ -3612,19 +3551,13 @@ __device__ __forceinline__ int prune_n8_core(const GraphDev &g, u64 *list, int n
         s_norm[s_len] = cn;
       }
       if (gidx == g1) {
-#pragma unroll
-        for (int k = 0; k < NQ; k++) {
-          const u32 f = (u32)(k * 8 + t);
-          if (f < g.n16) {
-            *reinterpret_cast<float4 *>(newrow + (size_t)f * 16) = c[k];
-            if (s_len < SL) *reinterpret_cast<float4 *>(stage + (size_t)s_len * g.row_stride + (size_t)f * 16) = c[k];
-          }
-        }
+        store_row8<NQ>(newrow, t, g.n16, c);
+        if (s_len < SL) store_row8<NQ>(stage + (size_t)s_len * g.row_stride, t, g.n16, c);
       }
       WSYNC();
       if (sv) { // the later survivors against the row that has just joined
         float4 r[NQ];
-        load8_lds(newrow, r);
+        load_row8_lds<NQ>(newrow, t, g.n16, r);
         const float d = dist8<LPRO>(g, c, r, cn, s_norm[s_len]);
         const bool out = fbits(d * g.alpha) < cdb;
         evals += (u64)__popcll(sv);
@@ -3653,29 +3586,7 @@ __device__ __forceinline__ int prune_n8_core(const GraphDev &g, u64 *list, int n
       const u64 ck = have ? list[ci] : 0ull;
       const u32 cdb = (u32)(ck >> 32);
       prefetch(ci + 8);
-      bool viol = false;
-      for (int j = 0; j < K0; j += 2) {
-        const u64 open = ballot(have && !viol);
-        if (!open) break;
-        const bool two = j + 1 < K0; // wave-uniform
-        float4 r0[NQ], r1[NQ];
-        if (j < SL) load8_lds(stage + (size_t)j * g.row_stride, r0);
-        else load8(g.rows + (size_t)s_ids[j] * g.row_stride, r0);
-        if (two) {
-          if (j + 1 < SL) load8_lds(stage + (size_t)(j + 1) * g.row_stride, r1);
-          else load8(g.rows + (size_t)s_ids[j + 1] * g.row_stride, r1);
-        }
-        const float d0 = dist8<LPRO>(g, c, r0, cn, s_norm[j]);
-        bool v = fbits(d0 * g.alpha) < cdb; // hnsw.rs:585
-        u64 counted = open;
-        if (two) {
-          counted = ballot(have && !viol && !v);
-          const float d1 = dist8<LPRO>(g, c, r1, cn, s_norm[j + 1]);
-          v = v || fbits(d1 * g.alpha) < cdb;
-        }
-        viol = viol || v;
-        evals += (u64)(__popcll(open) >> 3) + (two ? (u64)(__popcll(counted) >> 3) : 0ull);
-      }
+      const bool viol = scan_S(c, cn, cdb, have, 0, K0);
       const bool keep = have && !viol && t == 0;
       const u64 sv = ballot(keep);
       // (every lane read its list entries above; the writes land at or below the chunk's own first index)
@@ -3688,9 +3599,6 @@ __device__ __forceinline__ int prune_n8_core(const GraphDev &g, u64 *list, int n
     // ---- the survivors through the chunks: rows [0, K0) are behind them
     for (; base < n && s_len < cap; base += 8) chunk(base, K0);
   }
-#if HNY_PRUNE_TOUCH
-  if (touched == 0x7FC00001u) evals++; // (never: bit 0 is masked off)
-#endif
   return s_len;
 }
 
@@ -3958,21 +3866,21 @@ __global__ __launch_bounds__(64) void k_apply(GraphDev g_in, ApplyArgs a) {
 // add_link for the segments k_apply_append deferred (their list overflows): 256 threads per segment, the
 // self-prune runs on the LDS-staged wg_prune.
 template <int LPR, int NCH, int SP>
-__global__ __launch_bounds__(256, wg_waves_per_simd(NCH, 4)) void k_apply_wg(GraphDev g_in, ApplyArgs a, int SL) {
+__global__ __launch_bounds__(WG_WAVES * 64, wg_waves_per_simd(NCH)) void k_apply_wg(GraphDev g_in, ApplyArgs a, int SL) {
   GraphDev g = g_in;
   specialize<SP>(g);
   extern __shared__ __align__(16) unsigned char smem[];
   const u32 capmax = wg_capmax(g);
   u64 *lk = reinterpret_cast<u64 *>(smem);          // [capmax] the node's list
   u64 *sorted = lk + capmax;                        // [capmax]
-  WgPruneLds L = wg_prune_carve(smem + (size_t)2 * capmax * 8, SL, g.row_stride, 4, capmax);
+  WgPruneLds L = wg_prune_carve(smem + (size_t)2 * capmax * 8, SL, g.row_stride, capmax);
   const u32 n_def = *a.n_deferred;
   u64 evals = 0;
   const u32 sw = a.shard_world ? a.shard_world : 1u;
   for (u32 di = a.shard_rank + blockIdx.x * sw; di < n_def; di += gridDim.x * sw) {
     replay_add_link<256, false>(g, a, a.deferred[di], lk, sorted, L.S, exch_rec(a, di, sw),
                          [&](u64 *list, int n, int cap) __attribute__((always_inline)) {
-                           return wg_prune_sp<LPR, NCH, 4, SP>(g, list, n, cap, L, evals);
+                           return wg_prune_sp<LPR, NCH, SP>(g, list, n, cap, L, evals);
                          });
     __syncthreads();
   }
@@ -4146,7 +4054,7 @@ __global__ __launch_bounds__(256) void k_fill_gaps_wg(GraphDev g, const u64 *rec
   u32 *wsc = reinterpret_cast<u32 *>(nl + capmax);             // [64] ids of a distance pass (+ slack)
   float *wsd = reinterpret_cast<float *>(wsc + 256);           // [64]
   int *misc = reinterpret_cast<int *>(wsd + 256);              // [0] first / [1] last touched word, [2..5] wave sums
-  WgPruneLds L = wg_prune_carve(reinterpret_cast<unsigned char *>(misc + 16), SL, g.row_stride, 4, capmax);
+  WgPruneLds L = wg_prune_carve(reinterpret_cast<unsigned char *>(misc + 16), SL, g.row_stride, capmax);
   const int tid = threadIdx.x, w = __builtin_amdgcn_readfirstlane(tid >> 6), ln = tid & 63, t = ln % LPR;
   u32 *bitmap = bitmaps + (size_t)blockIdx.x * words;
   u32 *bm = bm_all + (size_t)blockIdx.x * maxb;
@@ -4260,7 +4168,7 @@ __global__ __launch_bounds__(256) void k_fill_gaps_wg(GraphDev g, const u64 *rec
       __syncthreads();
       s_len = misc[6];
     } else {
-      s_len = wg_prune<LPR, NCH, 4>(g, sorted, n, (int)l.cap, L, evals);
+      s_len = wg_prune<LPR, NCH>(g, sorted, n, (int)l.cap, L, evals);
     }
     __syncthreads();
     store_list<256, false>(l, L.S, s_len, (u32)s_len);
@@ -4653,13 +4561,13 @@ struct Hot {
   };
   template <int L, int C>
   struct PruneWg {
-    static hipError_t run(const GraphDev &g, const PruneArgs &a, int SL, int nw, int grid, hipStream_t st) {
+    static hipError_t run(const GraphDev &g, const PruneArgs &a, int SL, int grid, hipStream_t st) {
       if constexpr (C > 8) {
         return hipErrorInvalidValue; // 4 rows x C chunks do not fit the register file: wave prune
       } else {
-        size_t lds = wg_prune_lds_bytes((SP == 0 && a.list_global) ? 0u : a.rcap, g.row_stride, SL, nw, wg_capmax(g));
+        size_t lds = wg_prune_lds_bytes((SP == 0 && a.list_global) ? 0u : a.rcap, g.row_stride, SL, wg_capmax(g));
         // (beyond 64 KB: wide lists, M0 up to HNY_BIG_CAP, next to long rows)
-        return launch_with_lds(k_prune_wg<L, C, 4, SP>, dim3(grid), dim3(256), lds, st, g, a, SL);
+        return launch_with_lds(k_prune_wg<L, C, SP>, dim3(grid), dim3(WG_WAVES * 64), lds, st, g, a, SL);
       }
     }
   };
@@ -4694,7 +4602,7 @@ struct Hot {
       if constexpr (C > 8) {
         return hipErrorInvalidValue;
       } else {
-        size_t lds = wg_prune_lds_bytes(2 * wg_capmax(g), g.row_stride, SL, 4, wg_capmax(g));
+        size_t lds = wg_prune_lds_bytes(2 * wg_capmax(g), g.row_stride, SL, wg_capmax(g));
         return launch_with_lds(k_apply_wg<L, C, SP>, dim3(grid), dim3(256), lds, st, g, a, SL);
       }
     }
@@ -4804,8 +4712,8 @@ hipError_t HNY_CAT(hnyk_walk_sp, HNY_PART)(const GraphDev &g, const WalkArgs &a,
   return dispatch_shape<Hot<HNY_PART>::Walk>(s, g, a, grid, st);
 }
 hipError_t HNY_CAT(hnyk_prune_wg_sp, HNY_PART)(const GraphDev &g, const PruneArgs &a, LaunchShape s, int SL,
-                                               int nw, int grid, hipStream_t st) {
-  return dispatch_shape<Hot<HNY_PART>::PruneWg>(s, g, a, SL, nw, grid, st);
+                                               int grid, hipStream_t st) {
+  return dispatch_shape<Hot<HNY_PART>::PruneWg>(s, g, a, SL, grid, st);
 }
 hipError_t HNY_CAT(hnyk_prune_n8_sp, HNY_PART)(const GraphDev &g, const PruneArgs &a, int lpro, int SL, int grid,
                                                hipStream_t st) {
@@ -4893,10 +4801,10 @@ bool hnyk_apply_n8_ok(const GraphDev &g, LaunchShape s) {
 hipError_t hnyk_apply_n8(const GraphDev &g, const ApplyArgs &a, LaunchShape s, int SL, int grid, hipStream_t st) {
   HNY_SP_SWITCH(hnyk_apply_n8_sp, g, a, s.lpr, SL, grid, st)
 }
-hipError_t hnyk_prune_wg(const GraphDev &g, const PruneArgs &a, LaunchShape s, int SL, int nw, int grid,
+hipError_t hnyk_prune_wg(const GraphDev &g, const PruneArgs &a, LaunchShape s, int SL, int grid,
                          hipStream_t st) {
-  if (fast_path(g) && nw == 4 && !a.list_global) { HNY_SP_SWITCH(hnyk_prune_wg_sp, g, a, s, SL, nw, grid, st) }
-  return dispatch_shape<Hot<0>::PruneWg>(s, g, a, SL, nw, grid, st);
+  if (fast_path(g) && !a.list_global) { HNY_SP_SWITCH(hnyk_prune_wg_sp, g, a, s, SL, grid, st) }
+  return dispatch_shape<Hot<0>::PruneWg>(s, g, a, SL, grid, st);
 }
 hipError_t hnyk_apply_wg(const GraphDev &g, const ApplyArgs &a, LaunchShape s, int SL, int grid,
                          hipStream_t st) {
