@@ -400,6 +400,9 @@ struct hny_builder {
   DevBuf<unsigned char> d_sort_tmp;
   size_t sort_tmp_bytes = 0;
   uint32_t walk_slots = 0, bits_words = 0, log_cap = 0, rcap = 0, max_batch = 0;
+  // the work-queue switches, read once at creation: HNY_XCD_TILE (xcd_tile_of), HNY_PRUNE_XCD_TILE (k_prune_wg's
+  // tiles) and HNY_WALK_RESIDENT (walk_resident_of: waves of a tiled layer-0 build walk, 0 = walk_slots)
+  uint32_t xcd_tile = 0, prune_xcd_tile = 0, walk_resident = 0;
   uint64_t top_layer_nodes = 0; // see res_capacity
   int stage_rows = 0;      // selected rows staged in LDS by the workgroup prune kernels
   int n8_stage_rows = 0;   // the same for the one-wave short-row kernels (k_prune_n8, k_apply_n8)
@@ -1372,6 +1375,17 @@ static int plan_sizes(hny_builder *b, const CreatePlan &P) {
   const bool six_waves = b->shape.nch == 1 && b->shape.lpr <= 32 && o.metric >= HNY_HAMMING && b->rcap <= 128 &&
                          env_int("HNY_NO_RB", 0) == 0;
   b->walk_slots = (uint32_t)std::min<int64_t>(std::max(1, env_int("HNY_WALK_SLOTS", six_waves ? 6144 : 4096)), 65536);
+  b->xcd_tile = (u32)std::max(0, env_int("HNY_XCD_TILE", n16 * 16u >= 1024u ? 512 : 0));
+  b->prune_xcd_tile = (u32)std::max(0, env_int("HNY_PRUNE_XCD_TILE", 512));
+  // HNY_WALK_RESIDENT = waves per CU (of 256 CUs) that a tiled layer-0 build walk keeps resident; 0 = walk_slots.
+  // Default 12 where the walk runs on the register beam over long rows: rows of 1 - 3 KB (the beam's
+  // HNY_RB_MAX_NCH chunks) and result sets of at most 128 entries.  The LDS-beam walk (ef beyond 128) loses at every
+  // residency below 16 (walk_resident_of) and keeps walk_slots.
+  const bool long_row_rb = n16 * 16u >= 1024u && b->shape.nch <= 3 && b->rcap <= 128;
+  const int resident = env_int("HNY_WALK_RESIDENT", long_row_rb ? 12 : 0);
+  if (resident < 0 || resident > 256)
+    return fail(HNY_ERR_INVALID_ARG, "HNY_WALK_RESIDENT=%d: 0 (= HNY_WALK_SLOTS) .. 256 waves per CU", resident);
+  b->walk_resident = 256u * (u32)resident;
   b->bits_words = (n + 31) / 32 + 1;
   b->log_cap = (uint32_t)std::max(1024, env_int("HNY_VISITED_LOG", 16384));
   b->vis_slots_env = env_int("HNY_VIS_SLOTS", -1);
@@ -1802,8 +1816,24 @@ static void walk_workspace(const hny_builder *b, WalkArgs &w, uint32_t rcap, u64
 // 0.601 -> 0.573 s; tiles of 256..1024 members alike); neutral within the noise on 136 / 516-byte
 // rows, so off there.  HNY_XCD_TILE overrides (0 = one counter).  0 as well for fewer than 16 tiles of members.
 static u32 xcd_tile_of(const hny_builder *b, uint32_t cnt) {
-  const u32 xcd_tile = (u32)std::max(0, env_int("HNY_XCD_TILE", b->g.row_stride >= 1024u ? 512 : 0));
-  return xcd_tile && cnt >= 16u * xcd_tile ? xcd_tile : 0u;
+  return b->xcd_tile && cnt >= 16u * b->xcd_tile ? b->xcd_tile : 0u;
+}
+
+// Waves of one tiled layer-0 walk of the build: walk_slots, or b->walk_resident where that is less (a multiple of
+// 256, so block k still sits on XCD k % 8).  Each XCD claims its tiles member by member in locality order and takes
+// its next tile only when the current one has no unclaimed member left (k_walk's claim), so the members in flight
+// on one L2 are the last grid / 8 of its sequence: fewer waves = fewer regions live per L2, and fewer rows in
+// flight.  Measured at 1M x 768 (profiles/walk_resident_sweep.json, DESIGN.md §5 "Resident walks per XCD"):
+// 16 -> 12 waves per CU lifts k_walk's L2 hit rate 0.285 -> 0.305 (clustered; overlap 0.158 -> 0.169) and takes
+// 5 ms off the register-beam walk (284 -> 279 ms, 332 -> 327 ms), flat from 10 to 13; 8 waves hit more (0.334)
+// and starve the fabric (296 ms), 6 and 4 cost 24 % and 67 %.  Sizing the resident regions to one L2 (4 MiB, a
+// 3 MB cluster) would ask for 2 - 3 waves per CU, far below that floor, so the floor is the answer for every
+// tiled launch; keeping 16 waves for the launches on a graph below 64 K .. 512 K items costs 1.0 .. 2.0 ms
+// (same file), so the early tiled batches take 12 as well.  Batches of fewer than 16 tiles are not tiled and
+// keep walk_slots.  The LDS-beam walk of C3 (ef 200) loses at every residency below 16 (573 -> 588 ms at 12).
+static int walk_resident_of(const hny_builder *b, uint32_t cnt) {
+  const u32 slots = b->walk_resident ? std::min(b->walk_resident, b->walk_slots) : b->walk_slots;
+  return (int)std::min<uint32_t>(cnt, slots);
 }
 
 // tests: HNY_POOL_FORCE_RETRY = every k-th member takes the retry path of an overflowed tie pool;
@@ -1888,7 +1918,7 @@ int hny_builder_search(hny_builder *b, uint32_t lo, uint32_t hi, void *sel_dev) 
     // neighbouring members of the long-row prune on one XCD, like the walk's tiles: k_prune_wg's L2 hit rate 0.12 ->
     // 0.19, its fabric reads 368 -> 338 GB at C2 — and not a microsecond of its 66 ms (profiles/r05_prune_xcd_tile_fetch.txt:
     // the workgroup prune is bound by its barriers and dependent chains, not by bytes)
-    p.xcd_tile = (u32)std::max(0, env_int("HNY_PRUNE_XCD_TILE", 512));
+    p.xcd_tile = b->prune_xcd_tile;
     return p;
   };
   auto launch_prune = [&](const PruneArgs &p, hipStream_t st) -> hipError_t {
@@ -1919,7 +1949,9 @@ int hny_builder_search(hny_builder *b, uint32_t lo, uint32_t hi, void *sel_dev) 
     const bool no_retry = !pool_retry_env(w);
     w.pool_retry = no_retry ? nullptr : b->d_pool_retry.p;
     w.n_pool_retry = pc;
-    hipError_t e = hnyk_walk(b->g, w, b->shape, (int)std::min<uint32_t>(w.hi - w.lo, b->walk_slots), st);
+    const int grid = w.xcd_tile && w.layer == 0u ? walk_resident_of(b, w.hi - w.lo)
+                                                 : (int)std::min<uint32_t>(w.hi - w.lo, b->walk_slots);
+    hipError_t e = hnyk_walk(b->g, w, b->shape, grid, st);
     if (e != hipSuccess || no_retry) return e;
     WalkArgs h = w;
     h.queue = pc + 1;
