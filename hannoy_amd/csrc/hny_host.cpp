@@ -400,16 +400,17 @@ struct hny_builder {
   DevBuf<unsigned char> d_sort_tmp;
   size_t sort_tmp_bytes = 0;
   uint32_t walk_slots = 0, bits_words = 0, log_cap = 0, rcap = 0, max_batch = 0;
-  // the work-queue switches, read once at creation: HNY_XCD_TILE (xcd_tile_of), HNY_PRUNE_XCD_TILE (k_prune_wg's
-  // tiles) and HNY_WALK_RESIDENT (walk_resident_of: waves of a tiled layer-0 build walk, 0 = walk_slots)
+  // every HNY_* switch, read once at creation (plan_sizes); the sizes below are what they and the plan give
+  Knobs knobs{};
+  // the work-queue sizes: HNY_XCD_TILE (xcd_tile_of), HNY_PRUNE_XCD_TILE (k_prune_wg's tiles) and HNY_WALK_RESIDENT
+  // (walk_resident_of: waves of a tiled layer-0 build walk, 0 = walk_slots)
   uint32_t xcd_tile = 0, prune_xcd_tile = 0, walk_resident = 0;
   uint64_t top_layer_nodes = 0; // see res_capacity
-  int stage_rows = 0;      // selected rows staged in LDS by the workgroup prune kernels
-  int n8_stage_rows = 0;   // the same for the one-wave short-row kernels (k_prune_n8, k_apply_n8)
+  StageRows stage{0, 0};   // selected rows staged in LDS by the workgroup kernels / the one-wave short-row kernels
+  bool rb_one = false;     // no result set of this builder's build walks exceeds 64 entries (WalkArgs.rb_one)
+  ApplyForm apply_form{};  // the link phase of every batch of this builder (hnyk_apply_form)
   u32 cur_n_ops = 0, cur_n_def = 0; // of the batch being applied
   bool apply_open = false;          // between hny_builder_apply_begin and _merge
-  int vis_slots_env = -1;  // HNY_VIS_SLOTS: LDS visited table entries per walk wave, -1 = auto
-  bool wave_prune_only = false;
   size_t max_ops = 0, sel_words = 0;
   double t_upload = 0, t_build0 = 0, t_build = 0;
   // optional per-kernel-family timing (HIP events on `stream`)
@@ -473,7 +474,7 @@ static uint32_t vis_slots_for(const hny_builder *b, uint32_t rcap) {
   // 0.73-0.91 s against 0.66 s; round 4, same table in walk_layer_short: 0.58-0.72 s against 0.59 s): rows > 1 KB
   // only — rows <= 512 B have their own table of 16-bit remainders (vis_buckets_for)
   if ((size_t)b->g.n16 * 16 <= 1024) return 0;
-  if (b->vis_slots_env >= 0) return (uint32_t)std::min(8192, b->vis_slots_env);
+  if (knob_or(b->knobs.vis_slots, -1) >= 0) return (uint32_t)std::min(8192, b->knobs.vis_slots);
   const size_t fixed = hnyk_walk_lds_bytes(rcap, eps_cap_of(b));
   if (fixed + 512 * 4 > 10240) return 512;
   return (uint32_t)((10240 - fixed) / 4 / 64 * 64);
@@ -484,19 +485,38 @@ static uint32_t vis_slots_for(const hny_builder *b, uint32_t rcap) {
 // buckets were best, 640 / 768 3 % / 1.5 % slower) — and only while a remainder fits 16 bits (2^k / buckets
 // < 65 535, n < 2^28).
 // HNY_VIS_BUCKETS overrides (0 = bitset only).
+static size_t walk_lds_budget(int waves_per_simd) { return waves_per_simd == HNY_WALK_WPE_SMALL ? 6400 : 10240; }
+// The form a walk of `rcap` result entries takes in a PLAIN build on this builder's rows: wave order, fresh index,
+// lists of at most 64 slots, at most 64 entry points, HNY_NO_FAST unset.  The sizes that follow from the walk's
+// occupancy (walk_slots, the bucket budget, the resident waves) ask this form whatever the builder itself launches;
+// where that is wider than the launcher's rule the numbers are the ones measured and kept.
+static WalkForm plain_walk_form(const hny_builder *b, uint32_t rcap, bool no_rb) {
+  GraphDev g{};
+  g.metric = b->o.metric;
+  Knobs k = b->knobs;
+  k.no_fast = 0;
+  k.no_rb = no_rb;
+  WalkArgs w{};
+  w.rcap = rcap;
+  w.eps_cap = 64;
+  w.rb_one = b->rb_one;
+  return hnyk_walk_form(g, w, b->shape, k);
+}
 static void vis_buckets_for(const hny_builder *b, WalkArgs &w) {
   w.vis_buckets = w.vis_magic = w.vis_shift = w.vis_smask = 0;
   if ((size_t)b->g.n16 * 16 > 512 || w.vis_slots || w.res_global || w.rcap > 128 || w.eps_cap > 64) return;
   const size_t fixed = hnyk_walk_lds_bytes(w.rcap, w.eps_cap);
-  const size_t budget = (b->shape.nch == 1 && b->o.metric >= HNY_HAMMING) ? 6400 : 10240;
+  // (the budget of the six-wave build kernel also where this walk runs another one: the Reader's searches, strict
+  // mode, incremental builds, HNY_NO_RB, HNY_NO_FAST)
+  const size_t budget = walk_lds_budget(plain_walk_form(b, w.rcap, false).waves_per_simd);
   int nb = fixed + 1024 <= budget ? (int)((budget - fixed) / 8 / 64 * 64) : 0;
-  const char *e = getenv("HNY_VIS_BUCKETS");
-  if (e && *e) nb = std::max(0, std::min(4096, atoi(e) / 2 * 2));
+  const bool forced = b->knobs.vis_buckets != HNY_KNOB_UNSET;
+  if (forced) nb = std::max(0, std::min(4096, b->knobs.vis_buckets / 2 * 2));
   if (nb < 64) return;
   uint32_t k = 1;
   while (k < 28 && (1ull << k) < (uint64_t)std::max<uint32_t>(b->g.n, 2)) k++;
   if ((1ull << k) < (uint64_t)b->g.n) return;
-  if (!(e && *e)) // a larger index: more buckets (fewer resident waves) before giving the table up
+  if (!forced) // a larger index: more buckets (fewer resident waves) before giving the table up
     while (((1ull << k) - 1) / (uint64_t)nb + 1 >= 65535 && fixed + (size_t)(nb + 64) * 8 <= 12288) nb += 64;
   if (((1ull << k) - 1) / (uint64_t)nb + 1 >= 65535) return;
   w.vis_buckets = (u32)nb;
@@ -559,6 +579,25 @@ uint32_t cap_of(const hny_builder *b, uint32_t layer_or_level) {
 int env_int(const char *name, int dflt) {
   const char *v = getenv(name);
   return v && *v ? atoi(v) : dflt;
+}
+
+Knobs knobs_from_env() {
+  Knobs k{};
+  k.no_fast = env_int("HNY_NO_FAST", 0) != 0;
+  k.no_rb = env_int("HNY_NO_RB", 0) != 0;
+  k.rb_one = env_int("HNY_RB_ONE", 1) != 0;
+  k.prune_n8 = env_int("HNY_PRUNE_N8", 1) != 0;
+  k.walk_slots = env_int("HNY_WALK_SLOTS", HNY_KNOB_UNSET);
+  k.xcd_tile = env_int("HNY_XCD_TILE", HNY_KNOB_UNSET);
+  k.prune_xcd_tile = env_int("HNY_PRUNE_XCD_TILE", HNY_KNOB_UNSET);
+  k.walk_resident = env_int("HNY_WALK_RESIDENT", HNY_KNOB_UNSET);
+  k.visited_log = env_int("HNY_VISITED_LOG", HNY_KNOB_UNSET);
+  k.vis_slots = env_int("HNY_VIS_SLOTS", HNY_KNOB_UNSET);
+  k.stage_bytes = env_int("HNY_STAGE_BYTES", HNY_KNOB_UNSET);
+  k.no_locality = env_int("HNY_NO_LOCALITY", 0) != 0;
+  k.heap_small_cap = env_int("HNY_HEAP_SMALL_CAP", HNY_KNOB_UNSET);
+  k.vis_buckets = env_int("HNY_VIS_BUCKETS", HNY_KNOB_UNSET);
+  return k;
 }
 
 // codec bytes -> zero padded device rows (UnalignedVector is byte-packed and unaligned inside
@@ -849,8 +888,6 @@ int hny_encode_vectors(int32_t metric, uint32_t dim, uint64_t n, const float *ve
   return HNY_OK;
 }
 
-// the same on the device: codes through k_quantize, Cosine norms through k_norms_x86 (bit-identical
-// to the host path above), streamed in chunks so that any n fits
 int hny_selftest_lane_ops(int32_t device, uint32_t *mismatch64) {
   if (int rc = use_device(device)) return rc;
   DevBuf<u32> d;
@@ -1347,11 +1384,59 @@ static int plan_storage(hny_builder *b, const CreatePlan &P) {
       b->top_layer_nodes++;
   return HNY_OK;
 }
+// one-chunk register beam (k_walk<.., RC = 1>, rows <= 512 B): no result set of a builder's build walks exceeds 64
+// entries — ef, the entry points (all pushed without a capacity check), a top layer that only grows
+static bool rb_one_of(uint32_t ef, uint64_t neps, uint64_t top_layer_nodes, uint32_t M) {
+  const uint64_t most = std::max<uint64_t>(std::max<uint64_t>(ef, neps), neps > 1 ? std::max<uint64_t>(top_layer_nodes, neps) : 0);
+  return most <= 64 && M <= 64;
+}
+static uint32_t walk_slots_default(const WalkForm &plain) { return 256u * 4u * (uint32_t)plain.waves_per_simd; }
+// what the knobs and the plan's figures (row shape, entry points, ef, M, M0, mode) decide: the launch forms and the
+// sizes that follow from them.  Host arithmetic only (hny_internal_launch_forms runs it without a device).
+static int plan_launch(hny_builder *b, const Knobs &knobs) {
+  const hny_build_opts &o = b->o;
+  const uint32_t n = b->n, n16 = b->g.n16;
+  const Knobs &k = b->knobs = knobs;
+  // what the launch forms read of the GraphDev (alloc_device fills in the rest)
+  b->g.metric = o.metric;
+  b->g.M = o.M;
+  b->g.M0 = o.M0;
+  b->g.incremental = b->incremental ? 1 : 0;
+  b->g.x86_order = o.x86_order ? 1 : 0;
+  b->rcap = res_capacity(o.ef_construction, (uint32_t)b->entry_points.size(), n, b->top_layer_nodes, HNY_RES_GLOBAL_MAX);
+  b->rb_one = rb_one_of(o.ef_construction, b->entry_points.size(), b->top_layer_nodes, o.M);
+  // resident walk waves: 256 CUs x 4 SIMDs x the waves per SIMD of the plain build walk (6 for binary codes <= 512 B
+  // on the register beam, 4 otherwise) — also for a strict-mode or incremental builder, lists beyond 64 slots and
+  // HNY_NO_FAST, whose general kernels hold 4
+  b->walk_slots = walk_slots_default(plain_walk_form(b, b->rcap, k.no_rb != 0));
+  b->walk_slots = (uint32_t)std::min<int64_t>(std::max(1, knob_or(k.walk_slots, (int)b->walk_slots)), 65536);
+  b->xcd_tile = (u32)std::max(0, knob_or(k.xcd_tile, n16 * 16u >= 1024u ? 512 : 0));
+  b->prune_xcd_tile = (u32)std::max(0, knob_or(k.prune_xcd_tile, 512));
+  // HNY_WALK_RESIDENT = waves per CU (of 256 CUs) that a tiled layer-0 build walk keeps resident; 0 = walk_slots.
+  // Default 12 where the plain build walk runs on the register beam over long rows (1 - 3 KB, result sets of at most
+  // 128 entries) — HNY_NO_RB does not change it.  The LDS-beam walk (ef beyond 128) loses at every residency below
+  // 16 (walk_resident_of) and keeps walk_slots.
+  const bool long_row_rb = n16 * 16u >= 1024u && plain_walk_form(b, b->rcap, false).rc != 0;
+  const int resident = knob_or(k.walk_resident, long_row_rb ? 12 : 0);
+  if (resident < 0 || resident > 256)
+    return fail(HNY_ERR_INVALID_ARG, "HNY_WALK_RESIDENT=%d: 0 (= HNY_WALK_SLOTS) .. 256 waves per CU", resident);
+  b->walk_resident = 256u * (u32)resident;
+  b->bits_words = (n + 31) / 32 + 1;
+  b->log_cap = (uint32_t)std::max(1024, knob_or(k.visited_log, 16384));
+  b->locality = !k.no_locality;
+  // LDS staging budget of the workgroup prune, whole load groups
+  int rpg = 64 / b->shape.lpr;
+  int sl = (int)((u32)std::max(0, knob_or(k.stage_bytes, 24576)) / (n16 * 16u));
+  if (sl > HNY_MAX_CAP) sl = HNY_MAX_CAP;
+  b->stage.wg = sl / rpg * rpg;
+  // short rows: as many selected rows as 6 KB per wave hold (20 waves per CU)
+  b->stage.n8 = (int)std::min<uint32_t>(HNY_MAX_CAP, std::max<uint32_t>(1, 6144u / (n16 * 16u)));
+  b->apply_form = hnyk_apply_form(b->g, b->shape, k);
+  return HNY_OK;
+}
 // the sizes of the per-batch buffers and the launch choices that follow from the plan
 static int plan_sizes(hny_builder *b, const CreatePlan &P) {
   const hny_build_opts &o = b->o;
-  const uint32_t n = b->n, n16 = b->g.n16;
-  b->rcap = res_capacity(o.ef_construction, (uint32_t)b->entry_points.size(), n, b->top_layer_nodes, HNY_RES_GLOBAL_MAX);
   b->max_batch = 1;
   b->max_ops = 2;
   b->sel_words = 2;
@@ -1370,35 +1455,7 @@ static int plan_sizes(hny_builder *b, const CreatePlan &P) {
                 "batch_max %u too large for M0 %u: %zu link ops per batch >= 2^%d (pass batch_max <= %u; the schedule "
                 "is part of the result, so it is never shrunk silently)",
                 b->bmax, o.M0, b->max_ops, HNY_SEQ_BITS, (uint32_t)((1ull << (HNY_SEQ_BITS - 1)) / std::max(o.M0, 2 * o.M) / 2));
-  // resident walk waves: 256 CUs x 4 SIMDs x waves per SIMD (6 for binary codes <= 512 B on the register beam —
-  // the instances k_walk's launch bound gives six waves, see there; 4 otherwise)
-  const bool six_waves = b->shape.nch == 1 && b->shape.lpr <= 32 && o.metric >= HNY_HAMMING && b->rcap <= 128 &&
-                         env_int("HNY_NO_RB", 0) == 0;
-  b->walk_slots = (uint32_t)std::min<int64_t>(std::max(1, env_int("HNY_WALK_SLOTS", six_waves ? 6144 : 4096)), 65536);
-  b->xcd_tile = (u32)std::max(0, env_int("HNY_XCD_TILE", n16 * 16u >= 1024u ? 512 : 0));
-  b->prune_xcd_tile = (u32)std::max(0, env_int("HNY_PRUNE_XCD_TILE", 512));
-  // HNY_WALK_RESIDENT = waves per CU (of 256 CUs) that a tiled layer-0 build walk keeps resident; 0 = walk_slots.
-  // Default 12 where the walk runs on the register beam over long rows: rows of 1 - 3 KB (the beam's
-  // HNY_RB_MAX_NCH chunks) and result sets of at most 128 entries.  The LDS-beam walk (ef beyond 128) loses at every
-  // residency below 16 (walk_resident_of) and keeps walk_slots.
-  const bool long_row_rb = n16 * 16u >= 1024u && b->shape.nch <= 3 && b->rcap <= 128;
-  const int resident = env_int("HNY_WALK_RESIDENT", long_row_rb ? 12 : 0);
-  if (resident < 0 || resident > 256)
-    return fail(HNY_ERR_INVALID_ARG, "HNY_WALK_RESIDENT=%d: 0 (= HNY_WALK_SLOTS) .. 256 waves per CU", resident);
-  b->walk_resident = 256u * (u32)resident;
-  b->bits_words = (n + 31) / 32 + 1;
-  b->log_cap = (uint32_t)std::max(1024, env_int("HNY_VISITED_LOG", 16384));
-  b->vis_slots_env = env_int("HNY_VIS_SLOTS", -1);
-  // LDS staging budget of the workgroup prune, whole load groups
-  int rpg = 64 / b->shape.lpr;
-  int sl = (int)((u32)std::max(0, env_int("HNY_STAGE_BYTES", 24576)) / (n16 * 16u));
-  if (sl > HNY_MAX_CAP) sl = HNY_MAX_CAP;
-  b->stage_rows = sl / rpg * rpg;
-  // short rows: as many selected rows as 6 KB per wave hold (20 waves per CU)
-  b->n8_stage_rows = (int)std::min<uint32_t>(HNY_MAX_CAP, std::max<uint32_t>(1, 6144u / (n16 * 16u)));
-  // the workgroup prune kernels carry their own wave-order arithmetic: strict mode and very long
-  // rows use the single-wave kernels, which all go through dist_rows
-  b->wave_prune_only = b->shape.nch > 8 || o.x86_order; // the one-wave prune: strict mode, rows beyond 8 KB
+  if (int rc = plan_launch(b, knobs_from_env())) return rc;
   // 64 < M0 <= HNY_BIG_CAP: lists are walked 64 slots at a time; the workgroup kernels hold them whole (incremental
   // builds: k_fill_gaps_wg), strict mode's one-wave kernels (k_prune, k_apply) take them 64 slots at a time —
   // for fresh builds and loaded graphs; a strict-mode UPDATE of such lists (k_fill_gaps: one lane per slot) is refused
@@ -1445,7 +1502,7 @@ static int alloc_device(hny_builder *b, const CreatePlan &P) {
   HIP_TRY(b->d_sel.alloc(b->sel_words));
   const size_t cand_rows = std::max<uint32_t>(b->max_batch, 256);
   if (b->rcap > HNY_RES_LDS_MAX) { // walks that never evict (res_capacity): result sets and candidate lists in HBM
-    if (b->wave_prune_only)
+    if (b->apply_form.kind == APPLY_WAVE)
       return fail(HNY_ERR_UNSUPPORTED, "a result set of %u entries needs the workgroup prune kernels (no x86_order, rows <= 8 KB)", b->rcap);
     if ((cand_rows + slots) * (size_t)b->rcap * 8 > ((size_t)24 << 30))
       return fail(HNY_ERR_UNSUPPORTED, "result sets of %u entries for %zu batch members exceed the 24 GB set aside for them; "
@@ -1462,7 +1519,6 @@ static int alloc_device(hny_builder *b, const CreatePlan &P) {
   b->d_keys_a.n = b->d_keys_b.n = b->d_vals_a.n = b->d_vals_b.n = b->max_ops;
   HIP_TRY(b->d_seg_start.alloc(b->max_ops));
   HIP_TRY(b->d_nseg.alloc(4 + 16 + 8 * 16)); // + 8 per-XCD counters for each of the 16 work queues
-  b->locality = env_int("HNY_NO_LOCALITY", 0) == 0;
   HIP_TRY(b->d_lkey_a.alloc(cand_rows));
   HIP_TRY(b->d_lkey_b.alloc(cand_rows));
   HIP_TRY(b->d_perm_a.alloc(cand_rows));
@@ -1492,7 +1548,7 @@ static int alloc_device(hny_builder *b, const CreatePlan &P) {
     // holds (up to 512), and only a member that outgrows such a heap is walked once more by the few blocks whose
     // heaps hold every item (C4: 13).  One tier when the full heaps are no larger than that.
     const uint64_t area = b->heap_c_ptr == b->d_ops.p ? b->d_ops.n : b->d_heap_c.n;
-    const uint64_t small_cap = (uint64_t)std::max(16, env_int("HNY_HEAP_SMALL_CAP", 1 << 18));
+    const uint64_t small_cap = (uint64_t)std::max(16, knob_or(b->knobs.heap_small_cap, 1 << 18));
     if ((uint64_t)b->heap_c_cap > small_cap) {
       b->heap_c_cap1 = (uint32_t)small_cap;
       b->heap_grid1 = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(slots, 512), area / small_cap));
@@ -1890,14 +1946,7 @@ int hny_builder_search(hny_builder *b, uint32_t lo, uint32_t hi, void *sel_dev) 
     w.cand_n = b->d_cand_n.p;
     w.queue = queue;
     walk_workspace(b, w, b->rcap, b->d_res_global.p);
-    {
-      // one-chunk register beam (k_walk<.., RC = 1>, rows <= 512 B): no result set of this builder's walks exceeds 64
-      // entries — ef, the entry points (all pushed without a capacity check), a top layer that only grows
-      const uint64_t neps = b->entry_points.size();
-      const uint64_t most = std::max<uint64_t>(std::max<uint64_t>(b->o.ef_construction, neps),
-                                               neps > 1 ? std::max<uint64_t>(b->top_layer_nodes, neps) : 0);
-      w.rb_one = most <= 64 && b->o.M <= 64 && env_int("HNY_RB_ONE", 1) != 0;
-    }
+    w.rb_one = b->rb_one;
     return w;
   };
   auto prune_args = [&](int32_t l, uint32_t clo, uint32_t chi) {
@@ -1922,13 +1971,7 @@ int hny_builder_search(hny_builder *b, uint32_t lo, uint32_t hi, void *sel_dev) 
     return p;
   };
   auto launch_prune = [&](const PruneArgs &p, hipStream_t st) -> hipError_t {
-    if (!b->wave_prune_only && hnyk_prune_n8_ok(b->g, p, b->shape)) {
-      // short rows: one wave per query
-      return hnyk_prune_n8(b->g, p, b->shape, b->n8_stage_rows, (int)std::min<uint32_t>(p.hi - p.lo, 5120u), st);
-    }
-    if (b->wave_prune_only)
-      return hnyk_prune(b->g, p, b->shape, (int)std::min<uint32_t>(p.hi - p.lo, b->walk_slots), st);
-    return hnyk_prune_wg(b->g, p, b->shape, b->stage_rows, (int)std::min<uint32_t>(p.hi - p.lo, 2048), st);
+    return hnyk_prune(b->g, p, b->shape, hnyk_prune_form(b->g, p, b->shape, b->knobs, b->walk_slots), b->stage, st);
   };
   u32 *queues = b->d_nseg.p + 4; // 16 work counters: the descent + one per layer of the batch
   u32 *xqueues = queues + 16;    // the same 16, as 8 per-XCD counters each (WalkArgs.xcd_tile)
@@ -1951,7 +1994,7 @@ int hny_builder_search(hny_builder *b, uint32_t lo, uint32_t hi, void *sel_dev) 
     w.n_pool_retry = pc;
     const int grid = w.xcd_tile && w.layer == 0u ? walk_resident_of(b, w.hi - w.lo)
                                                  : (int)std::min<uint32_t>(w.hi - w.lo, b->walk_slots);
-    hipError_t e = hnyk_walk(b->g, w, b->shape, grid, st);
+    hipError_t e = hnyk_walk(b->g, w, b->shape, hnyk_walk_form(b->g, w, b->shape, b->knobs), grid, st);
     if (e != hipSuccess || no_retry) return e;
     WalkArgs h = w;
     h.queue = pc + 1;
@@ -2047,24 +2090,18 @@ static int apply_front(hny_builder *b, const void *sel_dev, ApplyArgs &a) {
   a.n_ops = n_ops;
   a.seg_start = b->d_seg_start.p;
   a.n_seg = b->d_nseg.p;
-  a.deferred = b->wave_prune_only ? nullptr : b->d_deferred.p;
+  a.deferred = b->apply_form.kind == APPLY_WAVE ? nullptr : b->d_deferred.p;
   a.n_deferred = b->d_nseg.p + 1;
-  const int grid = (int)std::min<u32>(std::max<u32>(n_ops / 2, 1), 8192);
   prof_begin(b, EV_APPLY);
-  if (a.deferred)
+  if (a.deferred) {
     HIP_TRY(hnyk_apply_append(b->g, a, b->stream)); // appends: one thread per target; overflowing lists deferred
-  else // strict mode / rows beyond 8 KB: one wave per target (one lane per list slot), prunes included
-    HIP_TRY(hnyk_apply(b->g, a, b->shape, grid, b->stream));
+  } else { // strict mode / rows beyond 8 KB: one wave per target (one lane per list slot), prunes included
+    const int grid = (int)std::min<u32>(std::max<u32>(n_ops / 2, 1), b->apply_form.grid_cap);
+    HIP_TRY(hnyk_apply(b->g, a, b->shape, b->apply_form, grid, b->stream));
+  }
   prof_end(b);
   b->cur_n_ops = n_ops;
   return HNY_OK;
-}
-
-// the targets whose list overflows: one wave each on short rows (k_apply_n8), a 256-thread workgroup otherwise
-static hipError_t launch_apply_deferred(hny_builder *b, const ApplyArgs &a, u32 work) {
-  if (hnyk_apply_n8_ok(b->g, b->shape))
-    return hnyk_apply_n8(b->g, a, b->shape, b->n8_stage_rows, (int)std::min<u32>(work, 5120u), b->stream);
-  return hnyk_apply_wg(b->g, a, b->shape, b->stage_rows, (int)std::min<u32>(work, 2048u), b->stream);
 }
 
 static void apply_back(hny_builder *b) {
@@ -2080,9 +2117,9 @@ int hny_builder_apply(hny_builder *b, const void *sel_dev) {
   HIP_TRY(hipSetDevice(b->device));
   ApplyArgs a;
   if (int rc = apply_front(b, sel_dev, a)) return rc;
-  if (!b->wave_prune_only) {
+  if (b->apply_form.kind != APPLY_WAVE) { // the targets whose list overflows
     prof_begin(b, EV_APPLY);
-    HIP_TRY(launch_apply_deferred(b, a, std::max<u32>(b->cur_n_ops / 8, 1)));
+    HIP_TRY(hnyk_apply_deferred(b->g, a, b->shape, b->apply_form, b->stage, std::max<u32>(b->cur_n_ops / 8, 1), b->stream));
     prof_end(b);
   }
   apply_back(b);
@@ -2099,7 +2136,7 @@ int hny_builder_apply_begin(hny_builder *b, const void *sel_dev, uint32_t *n_def
   ApplyArgs a;
   if (int rc = apply_front(b, sel_dev, a)) return rc;
   u32 nd = 0;
-  if (!b->wave_prune_only) {
+  if (b->apply_form.kind != APPLY_WAVE) {
     HIP_TRY(hipMemcpyAsync(&nd, b->d_nseg.p + 1, 4, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     if (nd > 1) { // canonical order: k_apply_append appended in atomic order, which differs between replicas
@@ -2118,7 +2155,7 @@ int hny_builder_apply_deferred(hny_builder *b, uint32_t rank, uint32_t world, vo
   if (!b || !b->apply_open || world == 0 || rank >= world || (world > 1 && !exch_dev))
     return fail(HNY_ERR_INVALID_ARG, "hny_builder_apply_deferred: bad argument or no open apply");
   HIP_TRY(hipSetDevice(b->device));
-  if (b->wave_prune_only || b->cur_n_def == 0) return HNY_OK;
+  if (b->apply_form.kind == APPLY_WAVE || b->cur_n_def == 0) return HNY_OK;
   ApplyArgs a{};
   a.keys = b->d_keys_b.p;
   a.vals = b->d_vals_b.p;
@@ -2133,7 +2170,7 @@ int hny_builder_apply_deferred(hny_builder *b, uint32_t rank, uint32_t world, vo
   const u32 per = (b->cur_n_def + world - 1) / world;
   a.exch = world > 1 ? (u64 *)exch_dev + (size_t)rank * per * a.exch_stride : nullptr;
   prof_begin(b, EV_APPLY);
-  HIP_TRY(launch_apply_deferred(b, a, std::max<u32>(per, 1)));
+  HIP_TRY(hnyk_apply_deferred(b->g, a, b->shape, b->apply_form, b->stage, std::max<u32>(per, 1), b->stream));
   prof_end(b);
   return HNY_OK;
 }
@@ -2142,7 +2179,7 @@ int hny_builder_apply_merge(hny_builder *b, const void *exch_all_dev, uint32_t r
   if (!b || !b->apply_open || world == 0 || rank >= world)
     return fail(HNY_ERR_INVALID_ARG, "hny_builder_apply_merge: bad argument or no open apply");
   HIP_TRY(hipSetDevice(b->device));
-  if (world > 1 && b->cur_n_def && !b->wave_prune_only) {
+  if (world > 1 && b->cur_n_def && b->apply_form.kind != APPLY_WAVE) {
     if (!exch_all_dev) return fail(HNY_ERR_INVALID_ARG, "hny_builder_apply_merge: null exchange buffer");
     const u32 per = (b->cur_n_def + world - 1) / world;
     prof_begin(b, EV_APPLY);
@@ -2601,7 +2638,7 @@ static int run_fill_gaps(hny_builder *b) {
     }
     prof_begin(b, EV_APPLY);
     HIP_TRY(hnyk_fill_gaps_wg(b->g, b->d_old_recs.p, n_recs, b->d_deleted.p, b->d_gap_bitmap.p, words, b->d_gap_bm.p,
-                              maxb, b->d_gap_keys.p, b->d_gap_sorted.p, b->stage_rows,
+                              maxb, b->d_gap_keys.p, b->d_gap_sorted.p, b->stage.wg,
                               (int)std::min<u32>(n_recs, (u32)b->gap_grid), b->shape, b->stream));
     prof_end(b);
     b->gaps_done = true;
@@ -2641,6 +2678,47 @@ int hny_builder_load_f32(const hny_build_opts *opts, const hny_items *f32_items,
 // batches, small deferred sets, fill_gaps) is counted on rank 0 only: the other ranks point their kernels'
 // counter block at a scratch copy meanwhile (the error words in it are the same on every replica).
 extern "C" void hny_internal_builder_set_export(hny_builder *b, int on) { b->will_export = on != 0; }
+// The launch forms and the default walk_slots of a builder with these figures, from the arguments alone (no device):
+// in  = metric, dim, M, M0, ef, entry points, x86_order, incremental, reader_mode, HNY_NO_FAST, HNY_NO_RB,
+//       HNY_RB_ONE, HNY_PRUNE_N8 (the size knobs unset; a fresh index of 2^20 items whose top layer holds the entry points)
+// out = the walk of layer 0 (the Reader's search with reader_mode, ef = ef_search): sp, big_eps, reader, rc, waves per
+//       SIMD; the prune of a level-0 batch: kind, sp, grid cap; the apply: kind, sp, grid cap; walk_slots
+extern "C" int hny_internal_launch_forms(const int32_t in[13], int32_t out[12]) {
+  if (!in || !out) return fail(HNY_ERR_INVALID_ARG, "null argument");
+  hny_builder b;
+  b.o.metric = in[0];
+  b.o.dim = (uint32_t)in[1];
+  b.o.M = (uint32_t)in[2];
+  b.o.M0 = (uint32_t)in[3];
+  b.o.ef_construction = (uint32_t)in[4];
+  b.o.x86_order = in[6] != 0;
+  b.incremental = in[7] != 0;
+  b.n = 1u << 20;
+  b.entry_points.assign((size_t)std::max(in[5], 0), 0u);
+  b.top_layer_nodes = b.entry_points.size();
+  if (int rc = pick_shape(b.o.metric, b.o.dim, b.shape, b.g.n16)) return rc;
+  Knobs k{};
+  k.no_fast = in[9], k.no_rb = in[10], k.rb_one = in[11], k.prune_n8 = in[12];
+  k.walk_slots = k.xcd_tile = k.prune_xcd_tile = k.walk_resident = k.visited_log = k.vis_slots = k.stage_bytes =
+      k.heap_small_cap = k.vis_buckets = HNY_KNOB_UNSET;
+  if (int rc = plan_launch(&b, k)) return rc;
+  static u64 res_global_stub; // only its presence is read
+  WalkArgs w{};
+  w.reader_mode = in[8] != 0;
+  w.rb_one = w.reader_mode ? 0u : (u32)b.rb_one;
+  walk_workspace(&b, w, b.rcap, b.rcap > HNY_RES_LDS_MAX ? &res_global_stub : nullptr);
+  const WalkForm wf = hnyk_walk_form(b.g, w, b.shape, b.knobs);
+  PruneArgs p{};
+  p.cap = b.o.M0;
+  p.rcap = b.rcap;
+  p.list_global = b.rcap > HNY_RES_LDS_MAX ? 1u : 0u;
+  const PruneForm pf = hnyk_prune_form(b.g, p, b.shape, b.knobs, b.walk_slots);
+  const ApplyForm af = b.apply_form;
+  const int32_t r[12] = {wf.sp, wf.big_eps, wf.reader, wf.rc, wf.waves_per_simd, pf.kind, pf.sp, (int32_t)pf.grid_cap,
+                         af.kind, af.sp, (int32_t)af.grid_cap, (int32_t)b.walk_slots};
+  memcpy(out, r, sizeof r);
+  return HNY_OK;
+}
 extern "C" int hny_internal_builder_count_evals(hny_builder *b, int on) {
   if (!b) return fail(HNY_ERR_INVALID_ARG, "null builder");
   HIP_TRY(hipSetDevice(b->device));
@@ -3308,7 +3386,7 @@ static int search_knn_impl(hny_builder *b, uint64_t nq, const void *qvectors, si
     if (b->locality && b->max_level >= 1 && cnt >= 2048) {
       // same locality ordering as the build: descent -> sort the queries by their region -> layer 0
       b->n_walk_dispatch++;
-      HIP_TRY(hnyk_walk(sg, region_descent(b, w), b->shape, grid, b->stream));
+      HIP_TRY(hnyk_walk(sg, region_descent(b, w), b->shape, hnyk_walk_form(sg, w, b->shape, b->knobs), grid, b->stream));
       if (int rc = region_order(b, 0, cnt, w)) return rc;
       w.queue = queues + 1;
       // the same XCD-tiled work queue as the build's level-0 walks (rows >= 1 KB, see xcd_tile_of)
@@ -3318,7 +3396,7 @@ static int search_knn_impl(hny_builder *b, uint64_t nq, const void *qvectors, si
       }
     }
     b->n_walk_dispatch++;
-    HIP_TRY(hnyk_walk(sg, w, b->shape, grid, b->stream));
+    HIP_TRY(hnyk_walk(sg, w, b->shape, hnyk_walk_form(sg, w, b->shape, b->knobs), grid, b->stream));
     if (int rc = top.fetch(dcand.p, dcn.p, rcap, cnt, sc)) return rc;
     std::vector<uint32_t> again; // queries whose tie pool overflowed (short codes, large ef_search: ties everywhere)
     for (uint32_t i = 0; i < cnt; i++) {

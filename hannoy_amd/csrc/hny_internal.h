@@ -234,11 +234,124 @@ struct LaunchShape {
   int nch; // 16-byte chunks per lane: 1,2,3,4,6,8
 };
 
-// kernels' host launchers (hny_kernels.hip)
-hipError_t hnyk_walk(const GraphDev &g, const WalkArgs &a, LaunchShape s, int grid, hipStream_t st);
+// ---- which kernel a launch gets (DESIGN.md §3h has the table): one knob record, one form function per family ----
+// Every HNY_* switch of the single-GPU library.  knobs_from_env (hny_host.cpp) fills it, a builder reads it
+// once (plan_sizes) and keeps it; HNY_KNOB_UNSET = not in the environment, the planned default holds.  The per-call
+// test hooks (HNY_POOL_FORCE_RETRY, HNY_NO_POOL_RETRY, HNY_FILTER_MASK_BYTES, HNY_INGEST_CHUNK_ROWS,
+// HNY_DEBUG_COUNTS) are not here: tests flip them during a builder's life.
+#define HNY_KNOB_UNSET (-2147483647 - 1)
+struct Knobs {
+  // form switches
+  int no_fast;  // HNY_NO_FAST=1: the general kernels everywhere
+  int no_rb;    // HNY_NO_RB=1: the walk's beam in LDS, never in registers
+  int rb_one;   // HNY_RB_ONE=0: two register chunks also where one would do
+  int prune_n8; // HNY_PRUNE_N8=0: short rows on the workgroup prune / apply kernels
+  // size switches
+  int walk_slots, xcd_tile, prune_xcd_tile, walk_resident, visited_log, vis_slots, stage_bytes, no_locality,
+      heap_small_cap, vis_buckets;
+};
+static inline int knob_or(int v, int dflt) { return v == HNY_KNOB_UNSET ? dflt : v; }
+
+// register beam of the specialised walks: rows of at most this many 16-byte chunks per lane
+#ifndef HNY_RB_MAX_NCH
+#define HNY_RB_MAX_NCH 3
+#endif
+#ifndef HNY_WALK_WPE
+#define HNY_WALK_WPE 4
+#endif
+// binary codes of at most 1 KB (NCH == 1): the specialised BUILD kernels run 6 waves per SIMD in 79 VGPRs (two
+// spilled) — the walk on 128-B codes is bound by instruction issue and latency, and with the visited set in LDS
+// the sixth wave pays (C5 walk 0.401 -> 0.377 s with 6 144 resident waves and 448 buckets; 7 waves: 0.382, 9
+// spilled VGPRs and too little LDS left for the table).  Only walk_layer_short was shown to fit (codes of at
+// most 512 B, register beam): codes of 513 - 1 024 B and the LDS-beam variant (ef >= 128) run walk_one_layer,
+// measured at ~96 VGPRs, and keep 4 waves.  The Reader's variant carries the exhaustive fallback
+// and spills at 96: 4 waves; the f32 kernels of that row size need 128 VGPRs; the general kernels spill at 4.
+#ifndef HNY_WALK_WPE_SMALL
+#define HNY_WALK_WPE_SMALL 6
+#endif
+// waves per SIMD of k_walk<LPR, NCH, ., SP, RM, RC>: its __launch_bounds__ and every host size that follows from it
+constexpr int hnyk_walk_waves_per_simd(int lpr, int nch, int sp, bool rm, int rc) {
+  return nch == 1 && sp >= 4 && !rm && (rc == 1 || rc == 2) && lpr <= 32 ? HNY_WALK_WPE_SMALL : HNY_WALK_WPE;
+}
+
+// the specialised kernels (hny_kernels.hip parts 1..7) serve the plain build: wave order, fresh index, lists of at
+// most 64 slots
+static inline bool hnyk_fast_path(const GraphDev &g, const Knobs &k) {
+  return !k.no_fast && !g.x86_order && !g.incremental && g.metric >= 0 && g.metric < 7 && g.M0 <= 64u;
+}
+// k_walk<lpr, nch, big_eps, sp, reader, rc>
+struct WalkForm {
+  int sp;          // 0: general kernel (metric, strict mode, incremental build, Reader at run time), else metric + 1
+  bool big_eps;    // general kernel only: more than 64 entry points
+  bool reader;     // specialised kernels: the Reader's semantics compiled in (RM)
+  int rc;          // specialised kernels: 64-entry chunks of the beam in registers, 0 = beam in LDS
+  int waves_per_simd;
+};
+static inline WalkForm hnyk_walk_form(const GraphDev &g, const WalkArgs &a, LaunchShape s, const Knobs &k) {
+  WalkForm f{0, a.eps_cap > 64, false, 0, 0};
+  if (hnyk_fast_path(g, k) && a.eps_cap <= 64 && !a.res_global) {
+    f.sp = g.metric + 1;
+    f.reader = a.reader_mode != 0;
+    // beam in registers: result sets of at most 128 entries; ONE chunk for the build walks on rows <= 512 B of a
+    // builder none of whose result sets exceeds 64 entries (WalkArgs.rb_one)
+    if (s.nch <= HNY_RB_MAX_NCH && a.rcap <= 128 && !k.no_rb)
+      f.rc = s.nch == 1 && s.lpr <= 32 && !f.reader && a.rb_one && k.rb_one ? 1 : 2;
+  }
+  f.waves_per_simd = hnyk_walk_waves_per_simd(s.lpr, s.nch, f.sp, f.reader, f.rc);
+  return f;
+}
+
+// robust_prune of a batch's candidate lists
+enum { PRUNE_N8 = 0, PRUNE_WG = 1, PRUNE_WAVE = 2 };
+#define HNY_N8_GRID_CAP 5120u // k_prune_n8, k_apply_n8: one wave per query / target, 20 waves per CU
+#define HNY_WG_GRID_CAP 2048u // k_prune_wg, k_apply_wg: one 256-thread workgroup per query / target
+struct PruneForm {
+  int kind;     // PRUNE_N8: k_prune_n8<lpr, sp>; PRUNE_WG: k_prune_wg<lpr, nch, sp>; PRUNE_WAVE: k_prune<lpr, nch>
+  int sp;       // 0: general kernel, else metric + 1 (never 0 with PRUNE_N8, always 0 with PRUNE_WAVE)
+  u32 grid_cap;
+};
+// the workgroup kernels carry their own wave-order arithmetic and hold four rows of at most 8 chunks per lane:
+// strict mode and rows beyond 8 KB take the one-wave kernels, which all go through dist_rows
+static inline bool hnyk_wave_only(const GraphDev &g, LaunchShape s) { return s.nch > 8 || g.x86_order; }
+static inline bool hnyk_short_rows(const GraphDev &g, LaunchShape s, const Knobs &k) {
+  return k.prune_n8 && hnyk_fast_path(g, k) && s.nch == 1 && s.lpr <= 32;
+}
+static inline PruneForm hnyk_prune_form(const GraphDev &g, const PruneArgs &a, LaunchShape s, const Knobs &k,
+                                        u32 walk_slots) {
+  if (hnyk_wave_only(g, s)) return {PRUNE_WAVE, 0, walk_slots};
+  // short rows: one wave per query, lists that fit the LDS
+  if (hnyk_short_rows(g, s, k) && !a.list_global && a.rcap <= 512 && a.cap <= (u32)HNY_MAX_CAP)
+    return {PRUNE_N8, g.metric + 1, HNY_N8_GRID_CAP};
+  return {PRUNE_WG, hnyk_fast_path(g, k) && !a.list_global ? g.metric + 1 : 0, HNY_WG_GRID_CAP};
+}
+
+// add_link of a batch's sorted link ops
+enum { APPLY_APPEND_N8 = 0, APPLY_APPEND_WG = 1, APPLY_WAVE = 2 };
+struct ApplyForm {
+  // APPLY_APPEND_*: k_apply_append takes the targets whose list cannot overflow and defers the others to
+  // k_apply_n8<lpr, sp> / k_apply_wg<lpr, nch, sp>; APPLY_WAVE: k_apply<lpr, nch, sp> does everything
+  int kind;
+  int sp;       // 0: general kernel, else metric + 1 (never 0 with APPLY_APPEND_N8)
+  u32 grid_cap; // of the deferred launch; k_apply: HNY_APPLY_WAVE_GRID_CAP
+};
+#define HNY_APPLY_WAVE_GRID_CAP 8192u
+static inline ApplyForm hnyk_apply_form(const GraphDev &g, LaunchShape s, const Knobs &k) {
+  const int sp = hnyk_fast_path(g, k) ? g.metric + 1 : 0;
+  if (hnyk_wave_only(g, s)) return {APPLY_WAVE, sp, HNY_APPLY_WAVE_GRID_CAP}; // (sp != 0: rows beyond 8 KB)
+  if (hnyk_short_rows(g, s, k) && g.M <= (u32)HNY_MAX_CAP) return {APPLY_APPEND_N8, sp, HNY_N8_GRID_CAP};
+  return {APPLY_APPEND_WG, sp, HNY_WG_GRID_CAP};
+}
+// selected rows staged in LDS by the workgroup kernels / by the one-wave short-row kernels
+struct StageRows {
+  int wg, n8;
+};
+
+// kernels' host launchers (hny_kernels.hip): the build kernels instantiate the form they are handed
+hipError_t hnyk_walk(const GraphDev &g, const WalkArgs &a, LaunchShape s, const WalkForm &f, int grid, hipStream_t st);
 // the members of a.pool_retry[0 .. *a.n_pool_retry) again, on heaps in HBM (a.queue: its own work counter)
 hipError_t hnyk_walk_heap(const GraphDev &g, const WalkArgs &a, LaunchShape s, int grid, hipStream_t st);
-hipError_t hnyk_prune(const GraphDev &g, const PruneArgs &a, LaunchShape s, int grid, hipStream_t st);
+// min(members, f.grid_cap) blocks
+hipError_t hnyk_prune(const GraphDev &g, const PruneArgs &a, LaunchShape s, const PruneForm &f, StageRows sl, hipStream_t st);
 // a.heap_r set: `res` as a heap in HBM too (result sets beyond the LDS), else the sorted LDS array
 hipError_t hnyk_nns(const GraphDev &g, const NnsArgs &a, LaunchShape s, int grid, hipStream_t st);
 hipError_t hnyk_nns_linear(const GraphDev &g, const NnsArgs &a, LaunchShape s, int grid, hipStream_t st);
@@ -278,21 +391,16 @@ hipError_t hnyk_exact_scores(const GraphDev &g, const ExactArgs &a, LaunchShape 
 hipError_t hnyk_exact_topk(const GraphDev &g, const ExactArgs &a, hipStream_t st);
 hipError_t hnyk_emit(const GraphDev &g, const EmitArgs &a, hipStream_t st);
 hipError_t hnyk_segments(const u64 *keys, u32 n_ops, u32 *seg_start, u32 *n_seg, hipStream_t st);
-hipError_t hnyk_apply(const GraphDev &g, const ApplyArgs &a, LaunchShape s, int grid, hipStream_t st);
-// the segments that cannot overflow, one thread each (a.deferred must be set); the rest -> a.deferred
+// APPLY_WAVE: every segment, one wave per target (one lane per list slot), prunes included
+hipError_t hnyk_apply(const GraphDev &g, const ApplyArgs &a, LaunchShape s, const ApplyForm &f, int grid, hipStream_t st);
+// APPLY_APPEND_*: the segments that cannot overflow, one thread each (a.deferred must be set); the rest -> a.deferred ...
 hipError_t hnyk_apply_append(const GraphDev &g, const ApplyArgs &a, hipStream_t st);
-hipError_t hnyk_prune_wg(const GraphDev &g, const PruneArgs &a, LaunchShape s, int SL, int grid, hipStream_t st);
-// robust_prune for rows <= 512 B: one wave per query, 8 candidates at a time (SL = selected rows staged in LDS)
-bool hnyk_prune_n8_ok(const GraphDev &g, const PruneArgs &a, LaunchShape s);
-hipError_t hnyk_prune_n8(const GraphDev &g, const PruneArgs &a, LaunchShape s, int SL, int grid, hipStream_t st);
-// the deferred add_link targets (k_apply_wg's job) for rows <= 512 B: one wave per target
-bool hnyk_apply_n8_ok(const GraphDev &g, LaunchShape s);
-hipError_t hnyk_apply_n8(const GraphDev &g, const ApplyArgs &a, LaunchShape s, int SL, int grid, hipStream_t st);
+// ... and those: min(work, f.grid_cap) blocks, one wave per target on short rows, a 256-thread workgroup otherwise
+hipError_t hnyk_apply_deferred(const GraphDev &g, const ApplyArgs &a, LaunchShape s, const ApplyForm &f, StageRows sl,
+                               u32 work, hipStream_t st);
 hipError_t hnyk_apply_merge(const GraphDev &g, const u64 *exch, u32 n_def, u32 world, u32 rank, u32 per,
                             u32 stride, hipStream_t st);
 hipError_t hnyk_sort_u32(void *temp, size_t &temp_bytes, u32 *in, u32 *out, u32 n, hipStream_t st);
-hipError_t hnyk_apply_wg(const GraphDev &g, const ApplyArgs &a, LaunchShape s, int SL, int grid,
-                         hipStream_t st);
 hipError_t hnyk_sort_pairs(void *temp, size_t &temp_bytes, u64 *keys_in, u64 *keys_out, u64 *vals_in,
                            u64 *vals_out, u32 n, u32 begin_bit, u32 end_bit, hipStream_t st);
 hipError_t hnyk_sort_pairs48(void *temp, size_t &temp_bytes, u64 *keys_in, u64 *keys_out, u64 *vals_in,
@@ -313,22 +421,15 @@ hipError_t hnyk_fill_gaps(const GraphDev &g, const u64 *recs, u32 n_recs, const 
 hipError_t hnyk_finalize_lists(u32 *ids, u32 *cnt_out, u32 n_lists, u32 cap, hipStream_t st);
 size_t hnyk_walk_lds_bytes(u32 rcap, u32 eps_cap);
 // the build kernels specialised for metric N-1 (hny_kernels.hip compiled with -DHNY_PART=N)
-#define HNY_DECL_SP(N)                                                                                      \
-  hipError_t hnyk_walk_sp##N(const GraphDev &g, const WalkArgs &a, LaunchShape s, int grid, hipStream_t st); \
-  hipError_t hnyk_prune_wg_sp##N(const GraphDev &g, const PruneArgs &a, LaunchShape s, int SL, int grid,    \
-                                 hipStream_t st);                                                           \
-  hipError_t hnyk_prune_n8_sp##N(const GraphDev &g, const PruneArgs &a, int lpro, int SL, int grid,         \
-                                 hipStream_t st);                                                           \
-  hipError_t hnyk_apply_n8_sp##N(const GraphDev &g, const ApplyArgs &a, int lpro, int SL, int grid,         \
-                                 hipStream_t st);                                                           \
-  hipError_t hnyk_apply_sp##N(const GraphDev &g, const ApplyArgs &a, LaunchShape s, int grid,               \
-                              hipStream_t st);                                                              \
-  hipError_t hnyk_apply_wg_sp##N(const GraphDev &g, const ApplyArgs &a, LaunchShape s, int SL, int grid,    \
-                                 hipStream_t st);
+#define HNY_DECL_SP(N)                                                                                         \
+  hipError_t hnyk_walk_sp##N(const GraphDev &g, const WalkArgs &a, LaunchShape s, const WalkForm &f, int grid, \
+                             hipStream_t st);                                                                  \
+  hipError_t hnyk_prune_sp##N(const GraphDev &g, const PruneArgs &a, LaunchShape s, const PruneForm &f, int SL, \
+                              int grid, hipStream_t st);                                                       \
+  hipError_t hnyk_apply_sp##N(const GraphDev &g, const ApplyArgs &a, LaunchShape s, const ApplyForm &f, int SL, \
+                              int grid, hipStream_t st);
 HNY_DECL_SP(1) HNY_DECL_SP(2) HNY_DECL_SP(3) HNY_DECL_SP(4) HNY_DECL_SP(5) HNY_DECL_SP(6) HNY_DECL_SP(7)
 #undef HNY_DECL_SP
-hipError_t hnyk_norms_x86(const float *v, u32 dim, u64 n, float *out, hipStream_t st);
-hipError_t hnyk_quantize(const float *v, u32 dim, u64 n, int binary_codec, u64 *out, hipStream_t st);
 
 // k_ingest: one pass over a chunk of f32 rows on the device -> codec bytes at their final place in the
 // builder's row array, header norms, and (optionally) the packed codes + headers of the chunk

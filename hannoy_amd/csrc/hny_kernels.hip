@@ -51,9 +51,6 @@
 #ifndef HNY_RB_MERGE
 #define HNY_RB_MERGE 1
 #endif
-#ifndef HNY_RB_MAX_NCH
-#define HNY_RB_MAX_NCH 3
-#endif
 #ifndef HNY_RB_MERGE_MIN
 #define HNY_RB_MERGE_MIN 2
 #endif
@@ -1962,21 +1959,9 @@ __device__ __forceinline__ void drain_asc(u64 *row, int n, u64 *res) {
 }
 
 
-#ifndef HNY_WALK_WPE
-#define HNY_WALK_WPE 4
-#endif
-// binary codes of at most 1 KB (NCH == 1): the specialised BUILD kernels run 6 waves per SIMD in 79 VGPRs (two
-// spilled) — the walk on 128-B codes is bound by instruction issue and latency, and with the visited set in LDS
-// the sixth wave pays (C5 walk 0.401 -> 0.377 s with 6 144 resident waves and 448 buckets; 7 waves: 0.382, 9
-// spilled VGPRs and too little LDS left for the table).  Only walk_layer_short was shown to fit (codes of at
-// most 512 B, register beam): codes of 513 - 1 024 B and the LDS-beam variant (ef >= 128) run walk_one_layer,
-// measured at ~96 VGPRs, and keep 4 waves.  The Reader's variant carries the exhaustive fallback
-// and spills at 96: 4 waves; the f32 kernels of that row size need 128 VGPRs; the general kernels spill at 4.
-#ifndef HNY_WALK_WPE_SMALL
-#define HNY_WALK_WPE_SMALL 6
-#endif
+// (waves per SIMD: hnyk_walk_waves_per_simd, hny_internal.h)
 template <int LPR, int NCH, bool BIG_EPS, int SP, bool RM = false, int RC = 0>
-__global__ __launch_bounds__(64, (NCH == 1 && SP >= 4 && !RM && (RC == 1 || RC == 2) && LPR <= 32 ? HNY_WALK_WPE_SMALL : HNY_WALK_WPE)) void k_walk(GraphDev g_in, WalkArgs a_in) {
+__global__ __launch_bounds__(64, hnyk_walk_waves_per_simd(LPR, NCH, SP, RM, RC)) void k_walk(GraphDev g_in, WalkArgs a_in) {
   constexpr bool RB = RC != 0;
   constexpr int RCN = RC ? RC : 1;
   static_assert(!(RB && (BIG_EPS || SP == 0)), "register beam: specialised kernels only");
@@ -4243,9 +4228,9 @@ __global__ __launch_bounds__(64) void k_finalize_lists(u32 *ids, u32 *cnt_out, u
 // Cosine norm = sqrt(dot(v, v)) in the REFERENCE's x86 summation order, so that the stored headers
 // are bit-identical to what hannoy itself writes: 32 fma partials + hsum tree for dim >= 32
 // (simple_avx.rs:8-13,69-110), 16 unfused partials for 16 <= dim < 32 (simple_sse.rs:10-14,64-110),
-// scalar below (simple.rs:81-83).  One half-wave (32 lanes = the 32 partials) per vector.
+// scalar below (simple.rs:81-83).
 // ---------------------------------------------------------------------------------------------
-// The element steps of that order, shared by k_norms_x86 and k_ingest so that the two cannot drift apart.
+// The element steps of that order (k_ingest_f32).
 __device__ __forceinline__ float sq_step_avx(float x, float acc) { return __builtin_fmaf(x, x, acc); } // _mm256_fmadd_ps
 __device__ __forceinline__ float sq_step_sse(float x, float acc) { // _mm_mul_ps, _mm_add_ps
   float p = x * x;
@@ -4256,69 +4241,14 @@ __device__ __forceinline__ float sq_step_tail(float x, float r) { // the scalar 
   return r + p;
 }
 __device__ __forceinline__ float hsum_join4(float h1, float h2, float h3, float h4) { return ((h1 + h2) + h3) + h4; }
-// Binary::from_slice (binary.rs:87-89) / BinaryQuantized::from_slice (binary_quantized.rs:86)
+// Binary::from_slice (binary.rs:80-94: bit = 0 < bits < 0x8000_0000) / BinaryQuantized::from_slice
+// (binary_quantized.rs:80-91: bit = is_sign_positive); dim i -> bit i%64 of u64 word i/64, zero padded
 __device__ __forceinline__ bool quantize_bit(u32 bits, int binary_codec) {
   return binary_codec ? (bits < 0x80000000u && bits > 0u) : (bits >> 31) == 0u;
 }
-__global__ __launch_bounds__(64) void k_norms_x86(const float *v, u32 dim, u64 n, float *out) {
-  const int ln = threadIdx.x, j = ln & 31, half = ln >> 5;
-  for (u64 vi = (u64)blockIdx.x * 2 + half; vi < n; vi += (u64)gridDim.x * 2) {
-    const float *x = v + vi * dim;
-    float r;
-    if (dim >= 32) {
-      const u32 m = dim - dim % 32;
-      float acc = 0.f;
-      for (u32 i = 0; i < m; i += 32) acc = sq_step_avx(x[i + j], acc);
-      acc = acc + __shfl_xor(acc, 4, 64); // hsum256: lane k + lane k+4
-      acc = acc + __shfl_xor(acc, 2, 64); //          k + k+2
-      acc = acc + __shfl_xor(acc, 1, 64); //          0 + 1
-      const int b = half * 32;
-      const float h1 = __shfl(acc, b, 64), h2 = __shfl(acc, b + 8, 64), h3 = __shfl(acc, b + 16, 64),
-                  h4 = __shfl(acc, b + 24, 64);
-      r = hsum_join4(h1, h2, h3, h4);
-      for (u32 i = m; i < dim; i++) r = sq_step_tail(x[i], r); // scalar tail, unfused
-    } else if (dim >= 16) {
-      const u32 m = dim - dim % 16;
-      float acc = 0.f;
-      if (j < 16)
-        for (u32 i = 0; i < m; i += 16) acc = sq_step_sse(x[i + j], acc);
-      acc = acc + __shfl_xor(acc, 2, 64); // hsum128: k + k+2
-      acc = acc + __shfl_xor(acc, 1, 64); //          0 + 1
-      const int b = half * 32;
-      const float h1 = __shfl(acc, b, 64), h2 = __shfl(acc, b + 4, 64), h3 = __shfl(acc, b + 8, 64),
-                  h4 = __shfl(acc, b + 12, 64);
-      r = hsum_join4(h1, h2, h3, h4);
-      for (u32 i = m; i < dim; i++) r = sq_step_tail(x[i], r);
-    } else {
-      r = 0.f;
-      for (u32 i = 0; i < dim; i++) r = sq_step_tail(x[i], r);
-    }
-    if (j == 0) out[vi] = __builtin_sqrtf(r);
-  }
-}
-
-// Binary::from_slice (binary.rs:80-94: bit = 0 < bits < 0x8000_0000) / BinaryQuantized::from_slice
-// (binary_quantized.rs:80-91: bit = is_sign_positive); dim i -> bit i%64 of u64 word i/64, zero
-// padded.  One wave per 64-dim word: the ballot IS the word.
-__global__ __launch_bounds__(64) void k_quantize(const float *v, u32 dim, u64 n, int binary_codec,
-                                                 u64 *out) {
-  const u32 words = (dim + 63) / 64;
-  const u64 total = n * words;
-  const int ln = threadIdx.x;
-  for (u64 w = blockIdx.x; w < total; w += gridDim.x) {
-    const u64 vi = w / words;
-    const u32 d = (u32)(w % words) * 64 + (u32)ln;
-    bool one = false;
-    if (d < dim) {
-      one = quantize_bit(__float_as_uint(v[vi * dim + d]), binary_codec);
-    }
-    const u64 word = ballot(one);
-    if (ln == 0) out[w] = word;
-  }
-}
 
 // ---------------------------------------------------------------------------------------------
-// k_ingest: the two kernels above fused with the upload's re-staging, for a chunk of f32 rows that sits in a
+// k_ingest: norm and bit codecs fused with the upload's re-staging, for a chunk of f32 rows that sits in a
 // device staging buffer (hny_host.cpp, IngestPipe).  One pass over the input: every row is loaded once, and
 // the same registers feed the copy (or the ballot), the Cosine norm and the optional packed outputs.
 // V4: 16-byte loads (row stride a multiple of 16 bytes) and 16-byte stores of the packed codes (dim a multiple
@@ -4510,113 +4440,83 @@ hipError_t launch_with_lds(void (*kernel)(P...), dim3 grid, dim3 block, size_t l
   return hipGetLastError();
 }
 
-// launchers of the four build kernels, general (SP = 0) or specialised for metric SP - 1
+// launchers of the build kernels, general (SP = 0) or specialised for metric SP - 1.  They instantiate the form
+// they are handed (hnyk_walk_form, hnyk_prune_form, hnyk_apply_form in hny_internal.h decide) and
+// decide nothing themselves.  Some forms have no instance in some Hot<SP>::X<L, C>, and the `if constexpr` guards
+// keep those from being compiled: the register beams beyond HNY_RB_MAX_NCH chunks, the one-wave short-row kernels
+// outside the specialised parts and rows of at most 32 units, the workgroup kernels beyond 8 chunks per lane (4 rows
+// x C chunks do not fit the register file), the specialised k_apply within them (plain builds take k_apply only
+// for rows beyond 8 KB).  The forms are plain records, so the types do not rule such a form out: the closing error of
+// a launcher stays, and it is the form functions, which never name those (tests/test_capi_forms_cpu.py), that keep
+// it from being reached.
 template <int SP>
 struct Hot {
   template <int L, int C>
   struct Walk {
-    static hipError_t run(const GraphDev &g, const WalkArgs &a, int grid, hipStream_t st) {
-      size_t lds = hnyk_walk_lds_bytes(a.res_global ? 0u : a.rcap, a.eps_cap) + (size_t)a.vis_slots * 4 +
-                   (size_t)a.vis_buckets * 8;
+    template <bool BIG_EPS, bool RM, int RC>
+    static hipError_t go(const GraphDev &g, const WalkArgs &a, int grid, hipStream_t st) {
+      const size_t lds = hnyk_walk_lds_bytes(a.res_global ? 0u : a.rcap, a.eps_cap) + (size_t)a.vis_slots * 4 +
+                         (size_t)a.vis_buckets * 8;
+      hipLaunchKernelGGL((k_walk<L, C, BIG_EPS, SP, RM, RC>), dim3(grid), dim3(64), lds, st, g, a);
+      return hipGetLastError();
+    }
+    static hipError_t run(const GraphDev &g, const WalkArgs &a, const WalkForm &f, int grid, hipStream_t st) {
       if constexpr (SP == 0) {
-        if (a.eps_cap > 64) {
-          hipLaunchKernelGGL((k_walk<L, C, true, 0>), dim3(grid), dim3(64), lds, st, g, a);
-          return hipGetLastError();
-        }
-      }
-      if constexpr (SP != 0) {
-        if constexpr (C <= HNY_RB_MAX_NCH) { // beam in registers (res <= 128 entries)
-          const char *e = getenv("HNY_NO_RB"); // read per launch: tests flip it inside one process
-          if (a.rcap <= 128 && !(e && atoi(e) != 0)) {
-            // (a ONE-chunk register beam for ef <= 64 — every beam scan a single ballot — was measured on
-            // C5: walk 0.692 s against 0.668 s with two chunks, i.e. no gain; the beam scans are not what
-            // bounds the short-row walk)
-            if constexpr (C == 1 && L <= 32) {
-              // build walks on short rows whose result sets never exceed 64 entries (ef <= 64, few entry points —
-              // the host decides, WalkArgs.rb_one): ONE 64-entry chunk in registers.  Round 3 measured this form
-              // as no gain (0.692 against 0.668 s) while the walk was bound by its global atomics; on the
-              // issue-bound walk of round 5 every beam scan, merge rank and eviction round it halves counts.
-              if (!a.reader_mode && a.rb_one) {
-                hipLaunchKernelGGL((k_walk<L, C, false, SP, false, 1>), dim3(grid), dim3(64), lds, st, g, a);
-                return hipGetLastError();
-              }
-            }
-            if (a.reader_mode)
-              hipLaunchKernelGGL((k_walk<L, C, false, SP, true, 2>), dim3(grid), dim3(64), lds, st, g, a);
-            else
-              hipLaunchKernelGGL((k_walk<L, C, false, SP, false, 2>), dim3(grid), dim3(64), lds, st, g, a);
-            return hipGetLastError();
-          }
-          // (a 4-chunk register beam for ef 128..255 was measured and is slower than the LDS beam:
-          // 128-d efC=200 walk 0.85 -> 1.00 s, 768-d (C3) 0.62 -> 0.68 s — registers spill)
-        }
-        if (a.reader_mode) {
-          hipLaunchKernelGGL((k_walk<L, C, false, SP, true>), dim3(grid), dim3(64), lds, st, g, a);
-          return hipGetLastError();
-        }
-      }
-      hipLaunchKernelGGL((k_walk<L, C, false, SP>), dim3(grid), dim3(64), lds, st, g, a);
-      return hipGetLastError();
-    }
-  };
-  template <int L, int C>
-  struct PruneWg {
-    static hipError_t run(const GraphDev &g, const PruneArgs &a, int SL, int grid, hipStream_t st) {
-      if constexpr (C > 8) {
-        return hipErrorInvalidValue; // 4 rows x C chunks do not fit the register file: wave prune
+        return f.big_eps ? go<true, false, 0>(g, a, grid, st) : go<false, false, 0>(g, a, grid, st);
       } else {
-        size_t lds = wg_prune_lds_bytes((SP == 0 && a.list_global) ? 0u : a.rcap, g.row_stride, SL, wg_capmax(g));
-        // (beyond 64 KB: wide lists, M0 up to HNY_BIG_CAP, next to long rows)
-        return launch_with_lds(k_prune_wg<L, C, SP>, dim3(grid), dim3(WG_WAVES * 64), lds, st, g, a, SL);
-      }
-    }
-  };
-  // short rows (<= 512 B): one wave per query, eight candidates at a time (k_prune_n8)
-  static hipError_t prune_n8(const GraphDev &g, const PruneArgs &a, int lpro, int SL, int grid, hipStream_t st) {
-    if constexpr (SP == 0) {
-      return hipErrorInvalidValue;
-    } else {
-      const size_t lds = prune_n8_lds_bytes(a.rcap, g.row_stride, SL);
-      if (lpro == 8) hipLaunchKernelGGL((k_prune_n8<8, SP>), dim3(grid), dim3(64), lds, st, g, a, SL);
-      else if (lpro == 16) hipLaunchKernelGGL((k_prune_n8<16, SP>), dim3(grid), dim3(64), lds, st, g, a, SL);
-      else if (lpro == 32) hipLaunchKernelGGL((k_prune_n8<32, SP>), dim3(grid), dim3(64), lds, st, g, a, SL);
-      else return hipErrorInvalidValue;
-      return hipGetLastError();
-    }
-  }
-  static hipError_t apply_n8(const GraphDev &g, const ApplyArgs &a, int lpro, int SL, int grid, hipStream_t st) {
-    if constexpr (SP == 0) {
-      return hipErrorInvalidValue;
-    } else {
-      const size_t lds = apply_n8_lds_bytes(g.row_stride, SL);
-      if (lpro == 8) hipLaunchKernelGGL((k_apply_n8<8, SP>), dim3(grid), dim3(64), lds, st, g, a, SL);
-      else if (lpro == 16) hipLaunchKernelGGL((k_apply_n8<16, SP>), dim3(grid), dim3(64), lds, st, g, a, SL);
-      else if (lpro == 32) hipLaunchKernelGGL((k_apply_n8<32, SP>), dim3(grid), dim3(64), lds, st, g, a, SL);
-      else return hipErrorInvalidValue;
-      return hipGetLastError();
-    }
-  }
-  template <int L, int C>
-  struct ApplyWg {
-    static hipError_t run(const GraphDev &g, const ApplyArgs &a, int SL, int grid, hipStream_t st) {
-      if constexpr (C > 8) {
+        if constexpr (C == 1 && L <= 32)
+          if (f.rc == 1) return go<false, false, 1>(g, a, grid, st);
+        if constexpr (C <= HNY_RB_MAX_NCH)
+          if (f.rc == 2) return f.reader ? go<false, true, 2>(g, a, grid, st) : go<false, false, 2>(g, a, grid, st);
+        if (f.rc == 0) return f.reader ? go<false, true, 0>(g, a, grid, st) : go<false, false, 0>(g, a, grid, st);
         return hipErrorInvalidValue;
-      } else {
-        size_t lds = wg_prune_lds_bytes(2 * wg_capmax(g), g.row_stride, SL, wg_capmax(g));
-        return launch_with_lds(k_apply_wg<L, C, SP>, dim3(grid), dim3(256), lds, st, g, a, SL);
       }
+    }
+  };
+  template <int L, int C>
+  struct Prune {
+    static hipError_t run(const GraphDev &g, const PruneArgs &a, const PruneForm &f, int SL, int grid, hipStream_t st) {
+      if constexpr (SP != 0 && C == 1 && L <= 32)
+        if (f.kind == PRUNE_N8) { // short rows (<= 512 B): one wave per query, eight candidates at a time
+          hipLaunchKernelGGL((k_prune_n8<L, SP>), dim3(grid), dim3(64), prune_n8_lds_bytes(a.rcap, g.row_stride, SL), st,
+                             g, a, SL);
+          return hipGetLastError();
+        }
+      if constexpr (C <= 8)
+        if (f.kind == PRUNE_WG) {
+          const size_t lds = wg_prune_lds_bytes((SP == 0 && a.list_global) ? 0u : a.rcap, g.row_stride, SL, wg_capmax(g));
+          // (beyond 64 KB: wide lists, M0 up to HNY_BIG_CAP, next to long rows)
+          return launch_with_lds(k_prune_wg<L, C, SP>, dim3(grid), dim3(WG_WAVES * 64), lds, st, g, a, SL);
+        }
+      if constexpr (SP == 0)
+        if (f.kind == PRUNE_WAVE) {
+          const size_t lds = (size_t)a.rcap * 8 + (size_t)wave_capmax(g) * (8 + 4) + 64 * 4;
+          hipLaunchKernelGGL((k_prune<L, C>), dim3(grid), dim3(64), lds, st, g, a);
+          return hipGetLastError();
+        }
+      return hipErrorInvalidValue;
     }
   };
   template <int L, int C>
   struct Apply {
-    static hipError_t run(const GraphDev &g, const ApplyArgs &a, int grid, hipStream_t st) {
-      if constexpr (SP != 0 && C <= 8) {
-        return hipErrorInvalidValue; // plain builds take k_apply only for rows beyond 8 KB (strict mode: SP = 0)
-      } else {
-        const size_t lds = (size_t)wave_capmax(g) * (8 + 8 + 8 + 4) + 64 * 4;
-        hipLaunchKernelGGL((k_apply<L, C, SP>), dim3(grid), dim3(64), lds, st, g, a);
-        return hipGetLastError();
-      }
+    static hipError_t run(const GraphDev &g, const ApplyArgs &a, const ApplyForm &f, int SL, int grid, hipStream_t st) {
+      if constexpr (SP != 0 && C == 1 && L <= 32)
+        if (f.kind == APPLY_APPEND_N8) {
+          hipLaunchKernelGGL((k_apply_n8<L, SP>), dim3(grid), dim3(64), apply_n8_lds_bytes(g.row_stride, SL), st, g, a, SL);
+          return hipGetLastError();
+        }
+      if constexpr (C <= 8)
+        if (f.kind == APPLY_APPEND_WG) {
+          const size_t lds = wg_prune_lds_bytes(2 * wg_capmax(g), g.row_stride, SL, wg_capmax(g));
+          return launch_with_lds(k_apply_wg<L, C, SP>, dim3(grid), dim3(256), lds, st, g, a, SL);
+        }
+      if constexpr (SP == 0 || C > 8)
+        if (f.kind == APPLY_WAVE) {
+          const size_t lds = (size_t)wave_capmax(g) * (8 + 8 + 8 + 4) + 64 * 4;
+          hipLaunchKernelGGL((k_apply<L, C, SP>), dim3(grid), dim3(64), lds, st, g, a);
+          return hipGetLastError();
+        }
+      return hipErrorInvalidValue;
     }
   };
 };
@@ -4655,14 +4555,6 @@ struct ExactScoresLauncher {
     const size_t lds = (size_t)a.qt * g.row_stride + (size_t)a.qt * 4;
     const dim3 grid((a.nq + a.qt - 1) / a.qt, (a.slab_n + HNY_EXACT_CHUNK - 1) / HNY_EXACT_CHUNK);
     return launch_with_lds(k_exact_scores<L, C>, grid, dim3(256), lds, st, g, a);
-  }
-};
-template <int L, int C>
-struct PruneLauncher {
-  static hipError_t run(const GraphDev &g, const PruneArgs &a, int grid, hipStream_t st) {
-    size_t lds = (size_t)a.rcap * 8 + (size_t)wave_capmax(g) * (8 + 4) + 64 * 4;
-    hipLaunchKernelGGL((k_prune<L, C>), dim3(grid), dim3(64), lds, st, g, a);
-    return hipGetLastError();
   }
 };
 template <int L, int C>
@@ -4707,47 +4599,30 @@ struct PairLauncher {
 #define HNY_CAT(a, b) HNY_CAT2(a, b)
 #if HNY_PART != 0
 // ---- part 1..7: the build kernels specialised for one metric ----
-hipError_t HNY_CAT(hnyk_walk_sp, HNY_PART)(const GraphDev &g, const WalkArgs &a, LaunchShape s, int grid,
-                                           hipStream_t st) {
-  return dispatch_shape<Hot<HNY_PART>::Walk>(s, g, a, grid, st);
+hipError_t HNY_CAT(hnyk_walk_sp, HNY_PART)(const GraphDev &g, const WalkArgs &a, LaunchShape s, const WalkForm &f,
+                                           int grid, hipStream_t st) {
+  return dispatch_shape<Hot<HNY_PART>::Walk>(s, g, a, f, grid, st);
 }
-hipError_t HNY_CAT(hnyk_prune_wg_sp, HNY_PART)(const GraphDev &g, const PruneArgs &a, LaunchShape s, int SL,
-                                               int grid, hipStream_t st) {
-  return dispatch_shape<Hot<HNY_PART>::PruneWg>(s, g, a, SL, grid, st);
+hipError_t HNY_CAT(hnyk_prune_sp, HNY_PART)(const GraphDev &g, const PruneArgs &a, LaunchShape s, const PruneForm &f,
+                                            int SL, int grid, hipStream_t st) {
+  return dispatch_shape<Hot<HNY_PART>::Prune>(s, g, a, f, SL, grid, st);
 }
-hipError_t HNY_CAT(hnyk_prune_n8_sp, HNY_PART)(const GraphDev &g, const PruneArgs &a, int lpro, int SL, int grid,
-                                               hipStream_t st) {
-  return Hot<HNY_PART>::prune_n8(g, a, lpro, SL, grid, st);
-}
-hipError_t HNY_CAT(hnyk_apply_n8_sp, HNY_PART)(const GraphDev &g, const ApplyArgs &a, int lpro, int SL, int grid,
-                                               hipStream_t st) {
-  return Hot<HNY_PART>::apply_n8(g, a, lpro, SL, grid, st);
-}
-hipError_t HNY_CAT(hnyk_apply_sp, HNY_PART)(const GraphDev &g, const ApplyArgs &a, LaunchShape s, int grid,
-                                            hipStream_t st) {
-  return dispatch_shape<Hot<HNY_PART>::Apply>(s, g, a, grid, st);
-}
-hipError_t HNY_CAT(hnyk_apply_wg_sp, HNY_PART)(const GraphDev &g, const ApplyArgs &a, LaunchShape s, int SL,
-                                               int grid, hipStream_t st) {
-  return dispatch_shape<Hot<HNY_PART>::ApplyWg>(s, g, a, SL, grid, st);
+hipError_t HNY_CAT(hnyk_apply_sp, HNY_PART)(const GraphDev &g, const ApplyArgs &a, LaunchShape s, const ApplyForm &f,
+                                            int SL, int grid, hipStream_t st) {
+  return dispatch_shape<Hot<HNY_PART>::Apply>(s, g, a, f, SL, grid, st);
 }
 #else
 // ---- part 0: the launch entry points ----
-// the specialised kernels serve the plain build: wave order, fresh index (HNY_NO_FAST=1 keeps every
-// launch on the general kernels)
-static bool fast_path(const GraphDev &g) {
-  const char *e = getenv("HNY_NO_FAST"); // read per launch: tests flip it inside one process
-  const bool off = e && atoi(e) != 0;
-  return !off && !g.x86_order && !g.incremental && g.metric >= 0 && g.metric < 7 && g.M0 <= 64u;
-}
-#define HNY_SP_SWITCH(fn, ...)                 \
-  switch (g.metric) {                          \
-    case 0: return fn##1(__VA_ARGS__);         \
-    case 1: return fn##2(__VA_ARGS__);         \
-    case 2: return fn##3(__VA_ARGS__);         \
-    case 3: return fn##4(__VA_ARGS__);         \
-    case 4: return fn##5(__VA_ARGS__);         \
-    case 5: return fn##6(__VA_ARGS__);         \
+// a form with sp != 0 names the part that holds its kernel
+#define HNY_SP_SWITCH(sp, fn, ...)             \
+  switch (sp) {                                \
+    case 0: break;                             \
+    case 1: return fn##1(__VA_ARGS__);         \
+    case 2: return fn##2(__VA_ARGS__);         \
+    case 3: return fn##3(__VA_ARGS__);         \
+    case 4: return fn##4(__VA_ARGS__);         \
+    case 5: return fn##5(__VA_ARGS__);         \
+    case 6: return fn##6(__VA_ARGS__);         \
     default: return fn##7(__VA_ARGS__);        \
   }
 
@@ -4755,9 +4630,9 @@ size_t hnyk_walk_lds_bytes(u32 rcap, u32 eps_cap) {
   return (size_t)rcap * 8 + HNY_POOL_CAP * 8 + 64 * 4 * 2 + (size_t)eps_cap * 4;
 }
 
-hipError_t hnyk_walk(const GraphDev &g, const WalkArgs &a, LaunchShape s, int grid, hipStream_t st) {
-  if (fast_path(g) && a.eps_cap <= 64 && !a.res_global) { HNY_SP_SWITCH(hnyk_walk_sp, g, a, s, grid, st) }
-  return dispatch_shape<Hot<0>::Walk>(s, g, a, grid, st);
+hipError_t hnyk_walk(const GraphDev &g, const WalkArgs &a, LaunchShape s, const WalkForm &f, int grid, hipStream_t st) {
+  HNY_SP_SWITCH(f.sp, hnyk_walk_sp, g, a, s, f, grid, st)
+  return dispatch_shape<Hot<0>::Walk>(s, g, a, f, grid, st);
 }
 hipError_t hnyk_walk_heap(const GraphDev &g, const WalkArgs &a, LaunchShape s, int grid, hipStream_t st) {
   return dispatch_shape<WalkHeapLauncher>(s, g, a, grid, st);
@@ -4777,39 +4652,21 @@ hipError_t hnyk_exact_topk(const GraphDev &g, const ExactArgs &a, hipStream_t st
   hipLaunchKernelGGL(k_exact_topk, dim3(a.nq), dim3(64), (size_t)a.rcap * 8, st, g, a);
   return hipGetLastError();
 }
-hipError_t hnyk_prune(const GraphDev &g, const PruneArgs &a, LaunchShape s, int grid, hipStream_t st) {
-  return dispatch_shape<PruneLauncher>(s, g, a, grid, st);
+hipError_t hnyk_prune(const GraphDev &g, const PruneArgs &a, LaunchShape s, const PruneForm &f, StageRows sl,
+                      hipStream_t st) {
+  const int SL = f.kind == PRUNE_N8 ? sl.n8 : sl.wg, grid = (int)std::min<u32>(a.hi - a.lo, f.grid_cap);
+  HNY_SP_SWITCH(f.sp, hnyk_prune_sp, g, a, s, f, SL, grid, st)
+  return dispatch_shape<Hot<0>::Prune>(s, g, a, f, SL, grid, st);
 }
-hipError_t hnyk_apply(const GraphDev &g, const ApplyArgs &a, LaunchShape s, int grid, hipStream_t st) {
-  if (fast_path(g)) { HNY_SP_SWITCH(hnyk_apply_sp, g, a, s, grid, st) }
-  return dispatch_shape<Hot<0>::Apply>(s, g, a, grid, st);
+hipError_t hnyk_apply(const GraphDev &g, const ApplyArgs &a, LaunchShape s, const ApplyForm &f, int grid, hipStream_t st) {
+  HNY_SP_SWITCH(f.sp, hnyk_apply_sp, g, a, s, f, 0, grid, st)
+  return dispatch_shape<Hot<0>::Apply>(s, g, a, f, 0, grid, st);
 }
-// the one-wave prune for short rows: plain build, rows of at most 32 units, lists that fit the LDS
-bool hnyk_prune_n8_ok(const GraphDev &g, const PruneArgs &a, LaunchShape s) {
-  const char *e = getenv("HNY_PRUNE_N8"); // read per launch: tests and A/B runs flip it inside one process
-  if (e && atoi(e) == 0) return false;
-  return fast_path(g) && s.nch == 1 && s.lpr <= 32 && !a.list_global && a.rcap <= 512 && a.cap <= (u32)HNY_MAX_CAP;
-}
-hipError_t hnyk_prune_n8(const GraphDev &g, const PruneArgs &a, LaunchShape s, int SL, int grid, hipStream_t st) {
-  HNY_SP_SWITCH(hnyk_prune_n8_sp, g, a, s.lpr, SL, grid, st)
-}
-bool hnyk_apply_n8_ok(const GraphDev &g, LaunchShape s) {
-  const char *e = getenv("HNY_PRUNE_N8");
-  if (e && atoi(e) == 0) return false;
-  return fast_path(g) && s.nch == 1 && s.lpr <= 32 && g.M0 <= (u32)HNY_MAX_CAP && g.M <= (u32)HNY_MAX_CAP;
-}
-hipError_t hnyk_apply_n8(const GraphDev &g, const ApplyArgs &a, LaunchShape s, int SL, int grid, hipStream_t st) {
-  HNY_SP_SWITCH(hnyk_apply_n8_sp, g, a, s.lpr, SL, grid, st)
-}
-hipError_t hnyk_prune_wg(const GraphDev &g, const PruneArgs &a, LaunchShape s, int SL, int grid,
-                         hipStream_t st) {
-  if (fast_path(g) && !a.list_global) { HNY_SP_SWITCH(hnyk_prune_wg_sp, g, a, s, SL, grid, st) }
-  return dispatch_shape<Hot<0>::PruneWg>(s, g, a, SL, grid, st);
-}
-hipError_t hnyk_apply_wg(const GraphDev &g, const ApplyArgs &a, LaunchShape s, int SL, int grid,
-                         hipStream_t st) {
-  if (fast_path(g)) { HNY_SP_SWITCH(hnyk_apply_wg_sp, g, a, s, SL, grid, st) }
-  return dispatch_shape<Hot<0>::ApplyWg>(s, g, a, SL, grid, st);
+hipError_t hnyk_apply_deferred(const GraphDev &g, const ApplyArgs &a, LaunchShape s, const ApplyForm &f, StageRows sl,
+                               u32 work, hipStream_t st) {
+  const int SL = f.kind == APPLY_APPEND_N8 ? sl.n8 : sl.wg, grid = (int)std::min<u32>(work, f.grid_cap);
+  HNY_SP_SWITCH(f.sp, hnyk_apply_sp, g, a, s, f, SL, grid, st)
+  return dispatch_shape<Hot<0>::Apply>(s, g, a, f, SL, grid, st);
 }
 hipError_t hnyk_pair_distances(const GraphDev &g, const u32 *a, const u32 *b, u32 n, float *out,
                                LaunchShape s, hipStream_t st) {
@@ -4848,20 +4705,6 @@ hipError_t hnyk_finalize_lists(u32 *ids, u32 *cnt_out, u32 n_lists, u32 cap, hip
   if (!n_lists) return hipSuccess;
   unsigned grid = n_lists < 65536u * 4u ? n_lists : 65536u * 4u;
   hipLaunchKernelGGL(k_finalize_lists, dim3(grid), dim3(64), 0, st, ids, cnt_out, n_lists, cap);
-  return hipGetLastError();
-}
-hipError_t hnyk_norms_x86(const float *v, u32 dim, u64 n, float *out, hipStream_t st) {
-  if (!n) return hipSuccess;
-  u64 blocks = (n + 1) / 2;
-  if (blocks > 262144) blocks = 262144;
-  hipLaunchKernelGGL(k_norms_x86, dim3((unsigned)blocks), dim3(64), 0, st, v, dim, n, out);
-  return hipGetLastError();
-}
-hipError_t hnyk_quantize(const float *v, u32 dim, u64 n, int binary_codec, u64 *out, hipStream_t st) {
-  if (!n) return hipSuccess;
-  u64 blocks = n * ((dim + 63) / 64);
-  if (blocks > 1048576) blocks = 1048576;
-  hipLaunchKernelGGL(k_quantize, dim3((unsigned)blocks), dim3(64), 0, st, v, dim, n, binary_codec, out);
   return hipGetLastError();
 }
 hipError_t hnyk_ingest(const IngestArgs &a, hipStream_t st) {
