@@ -39,6 +39,7 @@ EXPORTED = [
     "hny_builder_create_update", "hny_builder_update", "hny_builder_finish_delta", "hny_graph_delta_free",
     "hny_builder_exact_knn", "hny_builder_exact_knn_f32",
     "hny_builder_nns_filtered", "hny_builder_nns_filtered_f32",
+    "hny_builder_exact_knn_filtered", "hny_builder_exact_knn_filtered_f32", "hny_builder_exact_rows_read",
 ]
 ERR_IO = -9
 NNS_NONE = 0xFFFFFFFF  # by_item: the reference returns None
@@ -308,6 +309,12 @@ def load_library():
     L.hny_builder_nns_filtered_f32.restype = C.c_int
     L.hny_builder_nns_filtered_f32.argtypes = [vp, C.POINTER(QueryOpts), C.POINTER(QueryFilters), C.c_uint64, vp,
                                                C.c_size_t, vp, vp, vp]
+    L.hny_builder_exact_knn_filtered.restype = C.c_int
+    L.hny_builder_exact_knn_filtered.argtypes = L.hny_builder_nns_filtered.argtypes
+    L.hny_builder_exact_knn_filtered_f32.restype = C.c_int
+    L.hny_builder_exact_knn_filtered_f32.argtypes = L.hny_builder_nns_filtered_f32.argtypes
+    L.hny_builder_exact_rows_read.restype = C.c_uint64
+    L.hny_builder_exact_rows_read.argtypes = [vp]
     L.hny_builder_create_update.restype = C.c_int
     L.hny_builder_create_update.argtypes = [vp, C.POINTER(Update), C.POINTER(vp)]
     L.hny_builder_update.restype = C.c_int
@@ -1231,3 +1238,50 @@ class Builder:
             _check(L.hny_builder_exact_knn(self._h, C.byref(qo), nq, qc, qs, qh, qi, _p(ids), _p(dists), _p(counts)))
         self.did_cancel = bool(flag.value)
         return ids, dists, counts
+
+    def exact_knn_filtered_f32(self, queries, filters, filter_of, **kw):
+        """exact_knn_filtered(by_vector) with f32 queries, encoded on the device"""
+        return self.exact_knn_filtered(filters, filter_of, qf32=_f32_rows(queries), **kw)
+
+    def exact_knn_filtered(self, filters, filter_of, qcodes=None, qheaders=None, k=10, query_items=None, cancel=None,
+                           qf32=None):
+        """hny_builder_exact_knn_filtered: exact_knn with one .candidates() filter per query, `filters` and
+        `filter_of` as in nns_filtered.  The rows of the queries of one filter equal exact_knn(candidates=that
+        filter) on those queries alone: counts[i] = min(k, live candidates of query i's filter)."""
+        qo = QueryOpts()
+        qo.k = k
+        flag = C.c_int32(0)
+        if cancel is not None:
+            fn = CANCEL_FN(lambda _ctx: 1 if cancel() else 0)
+            qo.cancel = fn
+            qo.did_cancel = C.pointer(flag)
+        self._cancel_flag = flag
+        qf, _keep = QueryFilters.pack(filters, filter_of)
+        if query_items is not None:
+            query_items = np.ascontiguousarray(query_items, np.uint32)
+            nq, qc, qs, qh, qi = len(query_items), None, 0, None, _p(query_items)
+        elif qf32 is not None:
+            nq, qc, qh, qi = qf32.shape[0], _p(qf32), None, None
+            qs = qf32.strides[0] if nq > 1 else qf32.shape[1] * 4
+        else:
+            qcodes = np.ascontiguousarray(qcodes, np.uint8)
+            qheaders = np.ascontiguousarray(qheaders, np.uint8)
+            nq, qc, qs, qh, qi = qcodes.shape[0], _p(qcodes), qcodes.shape[1], _p(qheaders), None
+        if len(_keep[2]) != nq:
+            raise ValueError(f"filter_of has {len(_keep[2])} entries for {nq} queries")
+        ids = np.zeros((nq, k), np.uint32)
+        dists = np.zeros((nq, k), np.float32)
+        counts = np.zeros(nq, np.uint32)
+        L = load_library()
+        if qf32 is not None:
+            _check(L.hny_builder_exact_knn_filtered_f32(self._h, C.byref(qo), C.byref(qf), nq, qc, qs, _p(ids),
+                                                        _p(dists), _p(counts)))
+        else:
+            _check(L.hny_builder_exact_knn_filtered(self._h, C.byref(qo), C.byref(qf), nq, qc, qs, qh, qi, _p(ids),
+                                                    _p(dists), _p(counts)))
+        self.did_cancel = bool(flag.value)
+        return ids, dists, counts
+
+    def exact_rows_read(self):
+        """(tile, row) loads of the dense scan in the last exact_knn_filtered call on this builder; 0 if none ran"""
+        return int(load_library().hny_builder_exact_rows_read(self._h))

@@ -502,9 +502,10 @@ class QueryBuilder:
         return self
 
     def candidates_per_query(self, filters):
-        """one `.candidates()` per query of by_vectors / by_items (hny_builder_nns_filtered): a list with an id
-        array, or None for no filter, for every query.  The same array object given for several queries is one
-        filter.  Each query is answered as if it were searched alone with its own filter"""
+        """one `.candidates()` per query of by_vectors / by_items (hny_builder_nns_filtered, with .exact()
+        hny_builder_exact_knn_filtered): a list with an id array, or None for no filter, for every query.  The
+        same array object given for several queries is one filter.  Each query is answered as if it were searched
+        alone with its own filter"""
         self._per_query = list(filters)
         return self
 
@@ -512,8 +513,8 @@ class QueryBuilder:
         """the distinct filters (by object identity) and every query's index among them, -1 = none"""
         if len(self._per_query) != nq:
             raise ValueError(f"candidates_per_query has {len(self._per_query)} entries for {nq} queries")
-        if self._candidates is not None or self._exact:
-            raise ValueError("candidates_per_query goes with neither candidates() nor exact()")
+        if self._candidates is not None:
+            raise ValueError("candidates_per_query does not go with candidates()")
         index, filters, filter_of = {}, [], np.full(nq, -1, np.int64)
         for i, c in enumerate(self._per_query):
             if c is None:
@@ -554,6 +555,8 @@ class QueryBuilder:
             raise InvalidVecDimension(f"expected {r.dimensions}, received {q.shape[-1]}")
         if self._per_query is not None:
             filters, filter_of = self._filters(len(q))
+            if self._exact:
+                return r._b.exact_knn_filtered_f32(q, filters, filter_of, k=self.count, cancel=cancel)
             return r._b.nns_filtered_f32(q, filters, filter_of, cancel=cancel, **self._kw_filtered())
         if self._exact:
             return r._b.exact_knn_f32(q, k=self.count, candidates=self._candidates, cancel=cancel)
@@ -564,6 +567,9 @@ class QueryBuilder:
         if self._per_query is not None:
             items = np.ascontiguousarray(items, np.uint32)
             filters, filter_of = self._filters(len(items))
+            if self._exact:
+                return self.reader._b.exact_knn_filtered(filters, filter_of, query_items=items, k=self.count,
+                                                         cancel=cancel)
             return self.reader._b.nns_filtered(filters, filter_of, query_items=items, cancel=cancel,
                                                **self._kw_filtered())
         if self._exact:
@@ -681,12 +687,18 @@ class Reader:
     def by_vecs(self, queries, n=10, ef_search=200):
         return self._b.search_knn_f32(np.asarray(queries, np.float32), k=n, ef_search=ef_search)
 
-    def recall(self, queries, n=10, ef_search=100):
+    def recall(self, queries, n=10, ef_search=100, filters=None):
         """mean tie-aware recall@n of by_vecs against nns(n).exact(): a hit counts if its distance bits are <= those of
-        the exact n-th hit (distances are >= 0, so their bits order like their values)"""
+        the exact n-th hit (distances are >= 0, so their bits order like their values).  filters: one candidates set
+        (or None) per query as for candidates_per_query; the recall of the filtered search against the filtered
+        exact scan"""
         q = np.asarray(queries, np.float32)
-        _, d, c = self.by_vecs(q, n=n, ef_search=ef_search)
-        _, ed, ec = self.nns(n).exact().by_vectors(q)
+        if filters is not None:
+            _, d, c = self.nns(n).ef_search(ef_search).candidates_per_query(filters).by_vectors(q)
+            _, ed, ec = self.nns(n).candidates_per_query(filters).exact().by_vectors(q)
+        else:
+            _, d, c = self.by_vecs(q, n=n, ef_search=ef_search)
+            _, ed, ec = self.nns(n).exact().by_vectors(q)
         hits = total = 0
         for r in range(len(q)):
             m = int(ec[r])

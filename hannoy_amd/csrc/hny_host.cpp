@@ -422,6 +422,7 @@ struct hny_builder {
   size_t ev_used = 0;
   bool profiling = false;
   uint64_t n_walk_dispatch = 0; // k_walk launches since the last reset
+  uint64_t exact_rows_read = 0; // hny_builder_exact_rows_read: the last hny_builder_exact_knn_filtered call's
   // successor builders whose source was profiling: device time (HIP events) and bytes read + written of k_move_rows
   double t_move_rows_s = 0;
   uint64_t move_rows_bytes = 0;
@@ -3169,6 +3170,25 @@ static int check_candidates(const hny_query_opts *qo) {
   const bool missing = qo->has_candidates && qo->n_candidates && !qo->candidates;
   return missing ? fail(HNY_ERR_INVALID_ARG, "candidates missing") : HNY_OK;
 }
+// hny_query_filters of the calls with a filter per query; the candidates are there and not in the opts
+static int check_filters(const hny_query_opts *qo, const hny_query_filters *fl, uint64_t nq) {
+  if (!fl) return fail(HNY_ERR_INVALID_ARG, "no filters");
+  if (fl->struct_size != sizeof(hny_query_filters))
+    return fail(HNY_ERR_INVALID_ARG, "hny_query_filters.struct_size %u: this library has %zu", fl->struct_size,
+                sizeof(hny_query_filters));
+  if (qo->has_candidates)
+    return fail(HNY_ERR_INVALID_ARG, "opts->has_candidates must be 0: the candidates are in hny_query_filters");
+  if (!fl->offsets || (nq && !fl->filter_of)) return fail(HNY_ERR_INVALID_ARG, "filter offsets or filter_of missing");
+  const uint32_t n_filters = fl->n_filters;
+  if (fl->offsets[0] != 0) return fail(HNY_ERR_INVALID_ARG, "filter offsets must start at 0");
+  for (uint32_t f = 0; f < n_filters; f++)
+    if (fl->offsets[f + 1] < fl->offsets[f]) return fail(HNY_ERR_INVALID_ARG, "filter offsets decrease at filter %u", f);
+  if (fl->offsets[n_filters] && !fl->ids) return fail(HNY_ERR_INVALID_ARG, "filter ids missing");
+  for (uint64_t i = 0; i < nq; i++)
+    if (fl->filter_of[i] != HNY_FILTER_NONE && fl->filter_of[i] >= n_filters)
+      return fail(HNY_ERR_INVALID_ARG, "query %llu: filter %u of %u", (unsigned long long)i, fl->filter_of[i], n_filters);
+  return HNY_OK;
+}
 static int check_build_finished(const hny_builder *b) {
   return b->pos < b->order.size() ? fail(HNY_ERR_INVALID_ARG, "build not finished") : HNY_OK;
 }
@@ -3698,9 +3718,25 @@ static uint64_t filter_mask_budget() {
   return v ? v : HNY_FILTER_MASK_BYTES;
 }
 
+// the filters that queries use, ascending, and the queries that have one in filter order
+static void filters_in_use(const hny_query_filters *fl, uint64_t nq, std::vector<u32> &used,
+                           std::vector<uint64_t> &by_filter) {
+  std::vector<unsigned char> seen(fl->n_filters, 0);
+  for (uint64_t i = 0; i < nq; i++)
+    if (fl->filter_of[i] != HNY_FILTER_NONE) {
+      seen[fl->filter_of[i]] = 1;
+      by_filter.push_back(i);
+    }
+  for (uint32_t f = 0; f < fl->n_filters; f++)
+    if (seen[f]) used.push_back(f);
+  std::stable_sort(by_filter.begin(), by_filter.end(),
+                   [&](uint64_t x, uint64_t y) { return fl->filter_of[x] < fl->filter_of[y]; });
+}
+
 // some of a call's queries, gathered so that the shared steps see them as a call of their own
 struct SubBatch {
   const QuerySet &q;
+  uint32_t k = 0; // hits per row of its own arrays where that is less than the call's (0 = q.k)
   std::vector<uint64_t> idx; // the caller's query of each row
   std::vector<u32> filter_of;
   std::vector<unsigned char> rows, hdrs;
@@ -3726,10 +3762,11 @@ struct SubBatch {
         if (!q.q_f32 && hb) memcpy(&hdrs[j * hb], (const unsigned char *)q.qheaders + idx[j] * hb, hb);
       }
     }
-    ids.resize(m * q.k);
-    dists.resize(m * q.k);
+    const uint32_t kk = k ? k : q.k;
+    ids.resize(m * kk);
+    dists.resize(m * kk);
     counts.assign(m, 0u);
-    return QuerySet{b, m, rows.data(), rb, hdrs.data(), q.by_item ? items.data() : nullptr, q.q_f32, q.by_item, q.k,
+    return QuerySet{b, m, rows.data(), rb, hdrs.data(), q.by_item ? items.data() : nullptr, q.q_f32, q.by_item, kk,
                     ids.data(), dists.data(), counts.data()};
   }
   // the hits to the caller's rows; like the searchers, only the first `count` entries of a row are written
@@ -3738,8 +3775,9 @@ struct SubBatch {
       const uint32_t c = counts[j];
       q.out_counts[idx[j]] = c;
       if (c == HNY_NNS_NONE) continue;
-      memcpy(&q.out_ids[idx[j] * q.k], &ids[j * q.k], (size_t)c * 4);
-      memcpy(&q.out_dists[idx[j] * q.k], &dists[j * q.k], (size_t)c * 4);
+      const uint32_t kk = k ? k : q.k;
+      memcpy(&q.out_ids[idx[j] * q.k], &ids[j * kk], (size_t)c * 4);
+      memcpy(&q.out_dists[idx[j] * q.k], &dists[j * kk], (size_t)c * 4);
     }
   }
 };
@@ -3755,14 +3793,17 @@ struct FilterMasks {
   std::vector<u32> count;
 
   // filters used[r0 .. r1): ids -> live slots (unknown and deleted ids drop out, duplicates stay), CSR upload,
-  // bits set and counted on the device, the counts back in one copy
+  // bits set and counted on the device, the counts back in one copy.  HNY_SENT in `used` (last, if at all) is
+  // the live set as one more filter: exact_filtered_impl's queries without a filter in strict mode
   int build(const std::vector<u32> &used, size_t r0, size_t r1) {
     const size_t nf = r1 - r0;
     std::vector<u64> off(nf + 1, 0);
     std::vector<u32> slots;
     for (size_t j = 0; j < nf; j++) {
       const u32 f = used[r0 + j];
-      for (uint64_t i = fl->offsets[f]; i < fl->offsets[f + 1]; i++) {
+      for (uint32_t sl = 0; f == HNY_SENT && sl < b->n; sl++)
+        if (q.live(sl)) slots.push_back(sl);
+      for (uint64_t i = f == HNY_SENT ? 0 : fl->offsets[f]; f != HNY_SENT && i < fl->offsets[f + 1]; i++) {
         const int64_t sl = q.live_slot(fl->ids[i]);
         if (sl >= 0) slots.push_back((u32)sl);
       }
@@ -3789,21 +3830,8 @@ static int nns_filtered_impl(hny_builder *b, const hny_query_opts *qo, const hny
                              const void *qvectors, size_t qstride, const void *qheaders, const uint32_t *query_items,
                              uint32_t *out_ids, float *out_dists, uint32_t *out_counts, bool q_f32) {
   if (int rc = check_search_outputs(b, out_ids, out_dists, out_counts, qo ? qo->k : 0)) return rc;
-  if (!fl) return fail(HNY_ERR_INVALID_ARG, "no filters");
-  if (fl->struct_size != sizeof(hny_query_filters))
-    return fail(HNY_ERR_INVALID_ARG, "hny_query_filters.struct_size %u: this library has %zu", fl->struct_size,
-                sizeof(hny_query_filters));
-  if (qo->has_candidates)
-    return fail(HNY_ERR_INVALID_ARG, "opts->has_candidates must be 0: the candidates are in hny_query_filters");
-  if (!fl->offsets || (nq && !fl->filter_of)) return fail(HNY_ERR_INVALID_ARG, "filter offsets or filter_of missing");
+  if (int rc = check_filters(qo, fl, nq)) return rc;
   const uint32_t n_filters = fl->n_filters, NONE = HNY_NNS_NONE;
-  if (fl->offsets[0] != 0) return fail(HNY_ERR_INVALID_ARG, "filter offsets must start at 0");
-  for (uint32_t f = 0; f < n_filters; f++)
-    if (fl->offsets[f + 1] < fl->offsets[f]) return fail(HNY_ERR_INVALID_ARG, "filter offsets decrease at filter %u", f);
-  if (fl->offsets[n_filters] && !fl->ids) return fail(HNY_ERR_INVALID_ARG, "filter ids missing");
-  for (uint64_t i = 0; i < nq; i++)
-    if (fl->filter_of[i] != HNY_FILTER_NONE && fl->filter_of[i] >= n_filters)
-      return fail(HNY_ERR_INVALID_ARG, "query %llu: filter %u of %u", (unsigned long long)i, fl->filter_of[i], n_filters);
   const bool by_item = query_items != nullptr;
   const uint32_t k = qo->k;
   const QuerySet qs{b, nq, qvectors, qstride, qheaders, query_items, q_f32, by_item, k, out_ids, out_dists, out_counts};
@@ -3819,20 +3847,9 @@ static int nns_filtered_impl(hny_builder *b, const hny_query_opts *qo, const hny
   HIP_TRY(hipSetDevice(b->device));
   const uint64_t n_items = qs.n_live();
 
-  // the filters that queries use, ascending, and their queries in filter order
   std::vector<u32> used;
-  {
-    std::vector<unsigned char> seen(n_filters, 0);
-    for (uint64_t i = 0; i < nq; i++)
-      if (fl->filter_of[i] != HNY_FILTER_NONE) seen[fl->filter_of[i]] = 1;
-    for (uint32_t f = 0; f < n_filters; f++)
-      if (seen[f]) used.push_back(f);
-  }
   std::vector<uint64_t> by_filter;
-  for (uint64_t i = 0; i < nq; i++)
-    if (fl->filter_of[i] != HNY_FILTER_NONE) by_filter.push_back(i);
-  std::stable_sort(by_filter.begin(), by_filter.end(),
-                   [&](uint64_t x, uint64_t y) { return fl->filter_of[x] < fl->filter_of[y]; });
+  filters_in_use(fl, nq, used, by_filter);
   // rounds of as many bitsets as the budget holds (one always fits: n < 2^31 slots are 256 MB)
   FilterMasks fm{b, qs, fl, (u32)((((size_t)b->n + 31) / 32 + 4) & ~(size_t)3)};
   const size_t per_round = (size_t)std::max<uint64_t>(1, filter_mask_budget() / ((uint64_t)fm.stride * 4));
@@ -3975,6 +3992,116 @@ int hny_builder_nns_filtered_f32(hny_builder *b, const hny_query_opts *qo, const
 // (every row read once per tile of queries) then k_exact_topk (the slab merged into the running lists).
 // Strict mode and sparse filters go to nns_impl's linear scan over the same set: same definition.
 // ---------------------------------------------------------------------------------------------
+// a filter and a k per query for the dense scan (exact_filtered_impl); exact_impl has none
+struct ExactFilters {
+  const u32 *filter_of; // host, one entry per query of the QuerySet: its mask among `masks`, HNY_SENT = the live mask
+  const u32 *k_of;      // host, one entry per query: its own k
+  const u32 *count_of;  // host, one entry per query: the live candidates of its filter (the live items without one)
+  const u32 *masks;     // device, mask_stride words apart
+  u32 mask_stride;
+  bool skip;            // false (HNY_EXACT_SKIP=0): an all-ones tile mask, every row is read
+};
+
+// The dense scan of exact_impl and exact_filtered_impl: the queries of `qs` in blocks of at most HNY_EXACT_QBLOCK, per
+// block and slab k_exact_scores then k_exact_topk, `cancel` probed before every launch; a block that does not
+// finish reports 0 hits.  dmask: the call-wide mask (the live items for the members without a filter); kk: the most
+// hits of a row.  With F the scan reads only what a tile wants; tiles are as homogeneous as the order of `qs`
+// makes them, so the caller hands the queries over in filter order, unfiltered ones last.
+static int exact_dense_run(hny_builder *b, const QuerySet &qs, const u32 *dmask, uint32_t kk, const ExactFilters *F,
+                           SearchCancel &sc) {
+  const uint32_t n = b->n, qt = hnyk_exact_qt(b->g.row_stride);
+  const uint64_t nq = qs.nq;
+  uint32_t rcap = 64;
+  while (rcap < kk + 1) rcap *= 2;
+  const uint32_t qblock = search_chunk(b, nq, rcap, kk, HNY_EXACT_QBLOCK); // running lists within the 2 GB rule
+  const uint32_t sstride = (std::min<uint32_t>(n, HNY_EXACT_SLAB) + 63u) & ~63u;
+  QueryStage st{b, qs};
+  TopkOut top{b, qs, kk};
+  DevBuf<float> dscores;
+  DevBuf<u64> dlists;
+  DevBuf<u32> dln, dfof, dkof, dtile;
+  std::vector<u32> hfof, hkof;
+  if (int rc = st.alloc(qblock)) return rc;
+  HIP_TRY(dscores.alloc((size_t)qblock * sstride));
+  HIP_TRY(dlists.alloc((size_t)qblock * rcap));
+  if (int rc = top.alloc(qblock)) return rc;
+  HIP_TRY(dln.alloc(qblock));
+  const size_t tile_words = (size_t)((qblock + qt - 1) / qt) * (HNY_EXACT_SLAB / 32u);
+  if (F) {
+    HIP_TRY(dfof.alloc(qblock));
+    HIP_TRY(dkof.alloc(qblock));
+    HIP_TRY(dtile.alloc(tile_words));
+    hfof.resize(qblock);
+    hkof.resize(qblock);
+  }
+  for (uint64_t q0 = 0; q0 < nq; q0 += qblock) {
+    const uint32_t cnt = (uint32_t)std::min<uint64_t>(qblock, nq - q0);
+    const uint32_t n_mem = st.members_compact(q0, cnt); // the kernels index the block's queries by member
+    if (n_mem == 0 || sc.probe()) continue;             // cancelled: nothing of this block is started, 0 hits each
+    if (int rc = st.stage(q0, cnt)) return rc;
+    bool skip = false; // this block's tile masks are made from its members' masks
+    ExactArgs a{};
+    a.q_slots = st.dqslots.p;
+    a.q_rows = st.dq.p;
+    a.q_norms = st.norms();
+    a.q_stride = b->g.row_stride;
+    a.nq = n_mem;
+    a.qt = qt;
+    a.scores = dscores.p;
+    a.score_stride = sstride;
+    a.mask = dmask;
+    a.lists = dlists.p;
+    a.list_n = dln.p;
+    a.k = kk;
+    a.rcap = rcap;
+    if (F) {
+      for (uint32_t j = 0; j < n_mem; j++) {
+        hfof[j] = F->filter_of[q0 + st.members[j]];
+        hkof[j] = F->k_of[q0 + st.members[j]];
+      }
+      HIP_TRY(hipMemcpyAsync(dfof.p, hfof.data(), (size_t)n_mem * 4, hipMemcpyHostToDevice, b->stream));
+      HIP_TRY(hipMemcpyAsync(dkof.p, hkof.data(), (size_t)n_mem * 4, hipMemcpyHostToDevice, b->stream));
+      a.filter_of = dfof.p;
+      a.masks = F->masks;
+      a.mask_stride = F->mask_stride;
+      a.k_of = dkof.p;
+      a.tile_mask = dtile.p;
+      // Skipping pays where tiles want few rows.  An upper bound on what the block's tiles want: per tile the counts
+      // of its distinct filters (members come in filter order), at most n.  Where that bound is above half of
+      // tiles x n, the masks are not made and every row is read: heterogeneous tiles of wide filters measured 2 - 5 %
+      // slower with the skip than without
+      uint64_t wanted = 0;
+      const uint32_t n_tiles = (n_mem + qt - 1) / qt;
+      for (uint32_t t0 = 0; t0 < n_mem; t0 += qt) {
+        uint64_t w = 0;
+        for (uint32_t j = t0; j < std::min(n_mem, t0 + qt); j++)
+          if (j == t0 || hfof[j] != hfof[j - 1]) w += F->count_of[q0 + st.members[j]];
+        wanted += std::min<uint64_t>(w, n);
+      }
+      skip = F->skip && wanted * 2 <= (uint64_t)n_tiles * n;
+      if (!skip) HIP_TRY(hnyk_fill_u32(dtile.p, 0xFFFFFFFFu, tile_words, b->stream));
+    }
+    HIP_TRY(hipMemsetAsync(dln.p, 0, (size_t)n_mem * 4, b->stream));
+    bool stopped = false;
+    for (uint32_t s0 = 0; s0 < n && !stopped; s0 += HNY_EXACT_SLAB) {
+      a.slab_base = s0;
+      a.slab_n = std::min<uint32_t>(HNY_EXACT_SLAB, n - s0);
+      if ((stopped = sc.probe())) break;
+      if (skip) HIP_TRY(hnyk_exact_tile_masks(a, b->stream));
+      HIP_TRY(hnyk_exact_scores(b->g, a, b->shape, b->stream));
+      if ((stopped = sc.probe())) break;
+      HIP_TRY(hnyk_exact_topk(b->g, a, b->stream));
+    }
+    if (stopped) { // the block did not finish: 0 hits each
+      HIP_TRY(hipStreamSynchronize(b->stream));
+      continue;
+    }
+    if (int rc = top.fetch(dlists.p, dln.p, rcap, n_mem, sc)) return rc;
+    for (uint32_t j = 0; j < n_mem; j++) top.emit(j, q0 + st.members[j]);
+  }
+  return HNY_OK;
+}
+
 static int exact_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const void *qvectors, size_t qstride,
                       const void *qheaders, const uint32_t *query_items, uint32_t *out_ids, float *out_dists,
                       uint32_t *out_counts, bool q_f32) {
@@ -4028,60 +4155,12 @@ static int exact_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, con
     }
     return HNY_OK;
   }
-  uint32_t rcap = 64;
-  while (rcap < kk + 1) rcap *= 2;
-  const uint32_t qblock = search_chunk(b, nq, rcap, kk, HNY_EXACT_QBLOCK); // running lists within the 2 GB rule
-  const uint32_t sstride = (std::min<uint32_t>(n, HNY_EXACT_SLAB) + 63u) & ~63u;
-  QueryStage st{b, qs};
-  TopkOut top{b, qs, kk};
-  DevBuf<float> dscores;
-  DevBuf<u64> dlists;
-  DevBuf<u32> dln, dmask;
-  if (int rc = st.alloc(qblock)) return rc;
-  HIP_TRY(dscores.alloc((size_t)qblock * sstride));
-  HIP_TRY(dlists.alloc((size_t)qblock * rcap));
-  if (int rc = top.alloc(qblock)) return rc;
-  HIP_TRY(dln.alloc(qblock));
+  DevBuf<u32> dmask;
   HIP_TRY(dmask.alloc(mask.size()));
   HIP_TRY(hipMemcpyAsync(dmask.p, mask.data(), mask.size() * 4, hipMemcpyHostToDevice, b->stream));
   SearchCancel sc;
   HIP_TRY(sc.init(qo)); // (did_cancel was cleared above, ahead of the early returns)
-  for (uint64_t q0 = 0; q0 < nq; q0 += qblock) {
-    const uint32_t cnt = (uint32_t)std::min<uint64_t>(qblock, nq - q0);
-    const uint32_t n_mem = st.members_compact(q0, cnt); // the kernels index the block's queries by member
-    if (n_mem == 0 || sc.probe()) continue;             // cancelled: nothing of this block is started, 0 hits each
-    if (int rc = st.stage(q0, cnt)) return rc;
-    ExactArgs a{};
-    a.q_slots = st.dqslots.p;
-    a.q_rows = st.dq.p;
-    a.q_norms = st.norms();
-    a.q_stride = b->g.row_stride;
-    a.nq = n_mem;
-    a.qt = qt;
-    a.scores = dscores.p;
-    a.score_stride = sstride;
-    a.mask = dmask.p;
-    a.lists = dlists.p;
-    a.list_n = dln.p;
-    a.k = kk;
-    a.rcap = rcap;
-    HIP_TRY(hipMemsetAsync(dln.p, 0, (size_t)n_mem * 4, b->stream));
-    bool stopped = false;
-    for (uint32_t s0 = 0; s0 < n && !stopped; s0 += HNY_EXACT_SLAB) {
-      a.slab_base = s0;
-      a.slab_n = std::min<uint32_t>(HNY_EXACT_SLAB, n - s0);
-      if ((stopped = sc.probe())) break;
-      HIP_TRY(hnyk_exact_scores(b->g, a, b->shape, b->stream));
-      if ((stopped = sc.probe())) break;
-      HIP_TRY(hnyk_exact_topk(b->g, a, b->stream));
-    }
-    if (stopped) { // the block did not finish: 0 hits each
-      HIP_TRY(hipStreamSynchronize(b->stream));
-      continue;
-    }
-    if (int rc = top.fetch(dlists.p, dln.p, rcap, n_mem, sc)) return rc;
-    for (uint32_t j = 0; j < n_mem; j++) top.emit(j, q0 + st.members[j]);
-  }
+  if (int rc = exact_dense_run(b, qs, dmask.p, kk, nullptr, sc)) return rc;
   return search_end(b, qo, sc);
 }
 
@@ -4096,6 +4175,171 @@ int hny_builder_exact_knn_f32(hny_builder *b, const hny_query_opts *qo, uint64_t
   if (!queries) return fail(HNY_ERR_INVALID_ARG, "no queries");
   return exact_impl(b, qo, nq, queries, qstride, nullptr, nullptr, out_ids, out_dists, out_counts, true);
 }
+
+// ---------------------------------------------------------------------------------------------
+// exact k-NN with one candidates filter per query.  The rows of the queries of one filter are
+// those of exact_impl on these queries alone with that filter.  The filters become bitsets on the device
+// (FilterMasks); each is routed by §3d's traffic model from its own count: count x qt < n rows -> the gather
+// (k_filter_compact, k_nns_linear on the CSR), else the dense scan, which all dense filters and the queries without
+// one share (exact_dense_run with ExactFilters).  Strict mode gathers everything, the live set being one more filter.
+// ---------------------------------------------------------------------------------------------
+static bool exact_skip_env() {
+  const char *e = getenv("HNY_EXACT_SKIP"); // A/B switch, read per call: 0 = the dense scan reads every row
+  return !(e && e[0] == '0' && !e[1]);
+}
+
+static int exact_filtered_impl(hny_builder *b, const hny_query_opts *qo, const hny_query_filters *fl, uint64_t nq,
+                               const void *qvectors, size_t qstride, const void *qheaders, const uint32_t *query_items,
+                               uint32_t *out_ids, float *out_dists, uint32_t *out_counts, bool q_f32) {
+  if (int rc = check_search_outputs(b, out_ids, out_dists, out_counts, qo ? qo->k : 0)) return rc;
+  if (int rc = check_filters(qo, fl, nq)) return rc; // the candidates' side before the f32 rows, as in exact_impl
+  const bool by_item = query_items != nullptr;
+  const uint32_t n = b->n, k = qo->k, NONE = HNY_NNS_NONE;
+  const QuerySet qs{b, nq, qvectors, qstride, qheaders, query_items, q_f32, by_item, k, out_ids, out_dists, out_counts};
+  if (int rc = check_query_source(qs, "no queries")) return rc;
+  if (int rc = check_query_rows(qs)) return rc;
+  if (int rc = check_build_finished(b)) return rc;
+  if (int rc = check_query_stride(qs)) return rc;
+  HIP_TRY(hipSetDevice(b->device));
+  b->exact_rows_read = 0;
+  const uint32_t qt = hnyk_exact_qt(b->g.row_stride);
+  const bool strict = b->g.x86_order && b->g.mclass != MC_BIN;
+  std::vector<u32> live;
+  const uint64_t n_items = qs.slot_mask(qo, live); // (has_candidates == 0: the live items)
+  auto hits_of = [&](uint64_t c) { return (uint32_t)std::min<uint64_t>(k, c); };
+  auto gathered = [&](uint64_t c) { return strict || c * qt < n; }; // §3d: |C| rows per query against n / qt
+
+  std::vector<u32> used;
+  std::vector<uint64_t> by_filter, plain;
+  filters_in_use(fl, nq, used, by_filter);
+  for (uint64_t i = 0; i < nq; i++)
+    if (fl->filter_of[i] == HNY_FILTER_NONE) plain.push_back(i);
+  if (strict && !plain.empty()) { // the live set is one more filter, the last: its queries are gathered like the others
+    used.push_back(HNY_SENT);
+    by_filter.insert(by_filter.end(), plain.begin(), plain.end());
+  }
+  FilterMasks fm{b, qs, fl, (u32)((((size_t)n + 31) / 32 + 4) & ~(size_t)3)};
+  const size_t per_round = (size_t)std::max<uint64_t>(1, filter_mask_budget() / ((uint64_t)fm.stride * 4));
+  const size_t n_rounds = n_items ? (used.size() + per_round - 1) / per_round : 0;
+  size_t built = (size_t)-1;
+  auto build_round = [&](size_t r) -> int {
+    if (built == r) return HNY_OK;
+    built = r;
+    return fm.build(used, r * per_round, std::min(used.size(), (r + 1) * per_round));
+  };
+  // the refusal, from the counts of every round: no query has been searched yet
+  if (!plain.empty() && (uint64_t)hits_of(n_items) + 1 > HNY_RES_LDS_MAX)
+    return fail(HNY_ERR_UNSUPPORTED, "exact scan for %u hits among %llu items: at most %u hits", k,
+                (unsigned long long)n_items, HNY_RES_LDS_MAX - 1);
+  for (size_t r = 0; r < n_rounds; r++) {
+    if (int rc = build_round(r)) return rc;
+    for (size_t j = 0; j < fm.count.size(); j++)
+      if ((uint64_t)hits_of(fm.count[j]) + 1 > HNY_RES_LDS_MAX)
+        return fail(HNY_ERR_UNSUPPORTED, "filter %u: exact scan for %u hits among %u candidates: at most %u hits",
+                    used[r * per_round + j], k, fm.count[j], HNY_RES_LDS_MAX - 1);
+  }
+  SearchCancel sc;
+  HIP_TRY(sc.begin(qo));
+  if (n_items == 0) return qs.none_found();
+  HIP_TRY(hipMemsetAsync(b->g.stats + ST_EXACT_ROWS, 0, sizeof(u64), b->stream));
+  const bool skip = exact_skip_env();
+  DevBuf<u32> dlive;
+  if (!plain.empty() && !strict) {
+    HIP_TRY(dlive.alloc(live.size()));
+    HIP_TRY(hipMemcpyAsync(dlive.p, live.data(), live.size() * 4, hipMemcpyHostToDevice, b->stream));
+  }
+  // the dense queries of a round, in filter order, and with the last round the queries without a filter
+  auto run_dense = [&](SubBatch &dense) -> int {
+    std::vector<u32> k_of(dense.idx.size()), count_of(dense.idx.size());
+    uint32_t most = 0;
+    for (size_t j = 0; j < k_of.size(); j++) {
+      count_of[j] = dense.filter_of[j] == HNY_SENT ? (u32)n_items : fm.count[dense.filter_of[j]];
+      k_of[j] = hits_of(count_of[j]);
+      most = std::max(most, k_of[j]);
+    }
+    dense.k = most;
+    const QuerySet sub = dense.gather();
+    const ExactFilters F{dense.filter_of.data(), k_of.data(), count_of.data(), fm.dmasks.p, fm.stride, skip};
+    if (int rc = exact_dense_run(b, sub, dlive.p, most, &F, sc)) return rc;
+    dense.scatter();
+    return HNY_OK;
+  };
+  size_t at = 0;
+  for (size_t r = 0; r < n_rounds; r++) {
+    if (int rc = build_round(r)) return rc;
+    const size_t f0 = r * per_round, nf = fm.count.size();
+    std::vector<u32> lin;
+    std::vector<u64> cs_off(nf + 1, 0);
+    uint32_t most_hits = 0;
+    for (size_t j = 0; j < nf; j++) {
+      const bool g = fm.count[j] && gathered(fm.count[j]);
+      if (g) {
+        lin.push_back((u32)j);
+        most_hits = std::max(most_hits, hits_of(fm.count[j]));
+      }
+      cs_off[j + 1] = cs_off[j] + (g ? fm.count[j] : 0u);
+    }
+    SubBatch scan{qs}, dense{qs};
+    const uint64_t f_end = r + 1 < n_rounds ? used[f0 + nf] : (uint64_t)1 << 32; // (HNY_SENT sorts last)
+    for (; at < by_filter.size() && fl->filter_of[by_filter[at]] < f_end; at++) {
+      const uint64_t qi = by_filter[at];
+      const u32 j = (u32)(std::lower_bound(used.begin() + f0, used.begin() + f0 + nf, fl->filter_of[qi]) - used.begin() - f0);
+      if (!fm.count[j]) out_counts[qi] = by_item ? NONE : 0u; // an empty filter: nothing can match
+      else if (cs_off[j + 1] > cs_off[j]) scan.add(qi, j);
+      else dense.add(qi, j);
+    }
+    if (r + 1 == n_rounds && !strict)
+      for (uint64_t qi : plain) dense.add(qi, HNY_SENT);
+    if (!scan.idx.empty()) {
+      DevBuf<u32> dlin, dcs;
+      DevBuf<u64> dcs_off;
+      HIP_TRY(dlin.alloc(lin.size()));
+      HIP_TRY(dcs_off.alloc(nf + 1));
+      HIP_TRY(dcs.alloc(cs_off[nf]));
+      HIP_TRY(hipMemcpyAsync(dlin.p, lin.data(), lin.size() * 4, hipMemcpyHostToDevice, b->stream));
+      HIP_TRY(hipMemcpyAsync(dcs_off.p, cs_off.data(), (nf + 1) * 8, hipMemcpyHostToDevice, b->stream));
+      HIP_TRY(hnyk_filter_compact(fm.dmasks.p, fm.stride, dlin.p, (u32)lin.size(), dcs_off.p, dcs.p, b->stream));
+      scan.k = most_hits; // min(k, count) of the sub-batch's largest filter; a smaller one fills its row short
+      const QuerySet sub = scan.gather();
+      NnsFilters L;
+      L.masks = fm.dmasks.p;
+      L.mask_stride = fm.stride;
+      L.filter_of = scan.filter_of.data();
+      L.cand_slots = dcs.p;
+      L.cs_off = dcs_off.p;
+      if (int rc = nns_run(b, qo, sub, L, true, false, most_hits, linear_rcap(most_hits), sc)) return rc;
+      scan.scatter();
+    }
+    if (!dense.idx.empty())
+      if (int rc = run_dense(dense)) return rc;
+  }
+  if (!plain.empty() && !strict && n_rounds == 0) { // no filter in use at all
+    SubBatch rest{qs};
+    for (uint64_t qi : plain) rest.add(qi, HNY_SENT);
+    if (int rc = run_dense(rest)) return rc;
+  }
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  HIP_TRY(hipMemcpy(&b->exact_rows_read, b->g.stats + ST_EXACT_ROWS, sizeof(u64), hipMemcpyDeviceToHost));
+  return search_end(b, qo, sc);
+}
+
+int hny_builder_exact_knn_filtered(hny_builder *b, const hny_query_opts *qo, const hny_query_filters *filters,
+                                   uint64_t nq, const void *qvectors, size_t qstride, const void *qheaders,
+                                   const uint32_t *query_items, uint32_t *out_ids, float *out_dists,
+                                   uint32_t *out_counts) {
+  return exact_filtered_impl(b, qo, filters, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists,
+                             out_counts, false);
+}
+
+int hny_builder_exact_knn_filtered_f32(hny_builder *b, const hny_query_opts *qo, const hny_query_filters *filters,
+                                       uint64_t nq, const float *queries, size_t qstride, uint32_t *out_ids,
+                                       float *out_dists, uint32_t *out_counts) {
+  if (!queries) return fail(HNY_ERR_INVALID_ARG, "no queries");
+  return exact_filtered_impl(b, qo, filters, nq, queries, qstride, nullptr, nullptr, out_ids, out_dists, out_counts,
+                             true);
+}
+
+uint64_t hny_builder_exact_rows_read(const hny_builder *b) { return b ? b->exact_rows_read : 0; }
 
 // ---------------------------------------------------------------------------------------------
 // on-disk records

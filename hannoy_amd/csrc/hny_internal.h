@@ -34,6 +34,9 @@ enum {
   ST_ERR_RES_OVERFLOW = 6,
   ST_ERR_ITER = 7,
   ST_ERR_GAPS_OVERFLOW = 8,
+  // not a build counter: owned by exact_filtered_impl (hny_host.cpp), which clears it at the start of a call and reads
+  // it at the end; between calls it keeps the last call's value and shows up in whole-array read-backs
+  ST_EXACT_ROWS = 9, // (tile, row) loads of k_exact_scores<.., TILE = true> (hny_builder_exact_rows_read)
 #ifdef HNY_PHASE_CLOCKS // diagnostic build (HNY_CFLAGS=-DHNY_PHASE_CLOCKS): wave cycles per walk phase
   ST_PH_POP = 16, ST_PH_LIST = 17, ST_PH_DIST = 18, ST_PH_INSERT = 19, ST_PH_EXPANSIONS = 20, ST_PH_REST = 21,
   // walk_layer_short only: the visited round trip apart from the list fetch; lanes that asked the visited set,
@@ -380,6 +383,14 @@ struct ExactArgs {
   u64 *lists;                  // [nq][rcap] dist bits << 32 | slot, ascending
   u32 *list_n;                 // [nq], zero before the first slab
   u32 k, rcap;
+  // one candidates filter per query (hny_builder_exact_knn_filtered); all null in exact_impl's call
+  const u32 *filter_of;        // [nq] the member's mask among `masks`, HNY_SENT = `mask` (the live items)
+  const u32 *masks;            // the filters' bitsets over slots (live slots only), mask_stride words apart
+  u32 mask_stride;
+  const u32 *k_of;             // [nq] the member's own k (<= k; rcap is sized for the largest)
+  // != null: k_exact_scores<.., TILE = true> reads no row outside tile_mask[tile][HNY_EXACT_SLAB / 32], the OR of
+  // the masks of the tile's members over the slab (k_exact_tile_masks, or all ones: nothing is skipped)
+  u32 *tile_mask;
 };
 // queries per tile: the largest power of two with qt * row_stride <= 64 KB, within 4 .. 32
 static inline u32 hnyk_exact_qt(u32 row_stride) {
@@ -389,6 +400,8 @@ static inline u32 hnyk_exact_qt(u32 row_stride) {
 }
 hipError_t hnyk_exact_scores(const GraphDev &g, const ExactArgs &a, LaunchShape s, hipStream_t st);
 hipError_t hnyk_exact_topk(const GraphDev &g, const ExactArgs &a, hipStream_t st);
+// a.tile_mask for the slab a.slab_base / a.slab_n from the members' masks (a.filter_of must be set)
+hipError_t hnyk_exact_tile_masks(const ExactArgs &a, hipStream_t st);
 hipError_t hnyk_emit(const GraphDev &g, const EmitArgs &a, hipStream_t st);
 hipError_t hnyk_segments(const u64 *keys, u32 n_ops, u32 *seg_start, u32 *n_seg, hipStream_t st);
 // APPLY_WAVE: every segment, one wave per target (one lane per list slot), prunes included

@@ -2829,7 +2829,16 @@ __global__ __launch_bounds__(64, 4) void k_nns_linear(GraphDev g, NnsArgs a) {
 // dist_rows': the same lane slices (load_row / load_row_lds), the same per-lane chain (partial_*), the same
 // folded butterflies and finaliser, hence the same distance bits.  Deleted slots and slots outside the filter are
 // scored too (their rows are resident); k_exact_topk masks them.
-template <int LPR, int NCH>
+// TILE (hny_builder_exact_knn_filtered, a filter per query): a.tile_mask holds, per tile of queries, the OR of its
+// members' masks over the slab (k_exact_tile_masks).  A load group (the RPG rows of one u) none of whose rows is in
+// it is not loaded, its registers are zeroed like the out-of-range case; a fold group (F load groups) without a
+// wanted row is neither evaluated nor stored; a chunk without one ends the workgroup before it stages its queries.
+// All three tests are wave-uniform: the wave's RPI <= 64 rows of a pass are one 64-bit window of two scalar words.
+// The scores of skipped rows stay UNWRITTEN (whatever an earlier slab or call left there): k_exact_topk reads a
+// score only under the member's mask bit, and a member's mask is a subset of its tile's.  A row that is read is
+// scored with the same lane slices, chain, fold and finaliser as without TILE; which rows share its fold does not
+// enter its additions, so zeroed neighbours leave its bits alone.
+template <int LPR, int NCH, bool TILE>
 __global__ __launch_bounds__(256) void k_exact_scores(GraphDev g, ExactArgs a) {
   extern __shared__ __align__(16) unsigned char smem[];
   float *qnorm = reinterpret_cast<float *>(smem + (size_t)a.qt * g.row_stride);
@@ -2838,6 +2847,15 @@ __global__ __launch_bounds__(256) void k_exact_scores(GraphDev g, ExactArgs a) {
   const u32 slab_end = a.slab_base + a.slab_n;
   const u32 c0 = a.slab_base + blockIdx.y * HNY_EXACT_CHUNK;
   const u32 c1 = slab_end - c0 < HNY_EXACT_CHUNK ? slab_end : c0 + HNY_EXACT_CHUNK;
+  // the chunk's HNY_EXACT_CHUNK / 32 words of the tile's mask (bits at and beyond slab_n: zero, or never looked at)
+  const u32 *tmask = nullptr;
+  if constexpr (TILE) {
+    tmask = a.tile_mask + (size_t)blockIdx.x * (HNY_EXACT_SLAB / 32u) + blockIdx.y * (HNY_EXACT_CHUNK / 32u);
+    u32 any = 0;
+#pragma unroll
+    for (u32 w = 0; w < HNY_EXACT_CHUNK / 32u; w++) any |= tmask[w];
+    if (!any) return; // nobody in the tile wants a row of this chunk
+  }
   for (u32 i = threadIdx.x; i < (u32)nqt * g.n16; i += 256u) {
     const u32 qi = i / g.n16, f = i - qi * g.n16;
     const unsigned char *src = a.q_slots ? g.rows + (size_t)a.q_slots[q0 + qi] * g.row_stride
@@ -2859,15 +2877,28 @@ __global__ __launch_bounds__(256) void k_exact_scores(GraphDev g, ExactArgs a) {
   constexpr int U = RowsInFlight<NCH>::U;   // load groups in flight
   constexpr int RPI = RPG * U;              // rows per wave and pass
   constexpr int F = (U % 4 == 0) ? 4 : (U % 2 == 0 ? 2 : 1);
-  const int ln = HNY_LANE, t = ln % LPR, sub = ln / LPR, wave = (int)(threadIdx.x >> 6);
+  const int ln = HNY_LANE, t = ln % LPR, sub = ln / LPR;
+  const int wave = TILE ? uni((int)(threadIdx.x >> 6)) : (int)(threadIdx.x >> 6);
   const bool writer = (t & (F == 1 ? LPR - 1 : LPR / F - 1)) == 0;
+  u32 rows_read = 0; // TILE: rows of the load groups this wave loaded
   for (u32 r0 = c0 + (u32)(wave * RPI); r0 < c1; r0 += 4u * RPI) {
     float4 r[U][NCH];
     float rn[U];
+    u64 win = ~0ull; // bit i: row r0 + i is in the tile's mask
+    if constexpr (TILE) {
+      // r0 - c0 is a multiple of RPG <= 8: no load group crosses a word, and RPI <= 64 rows span at most two
+      const u32 off = r0 - c0, w = off >> 5, w1 = w + 1u < HNY_EXACT_CHUNK / 32u ? w + 1u : w; // (rows of w1 == w: >= c1)
+      win = (((u64)tmask[w1] << 32) | (u64)tmask[w]) >> (off & 31u);
+    }
 #pragma unroll
     for (int u = 0; u < U; u++) {
       rn[u] = 0.f;
-      if (r0 + (u32)(u * RPG) < c1) { // wave-uniform
+      bool wanted = r0 + (u32)(u * RPG) < c1; // wave-uniform
+      if constexpr (TILE) {
+        wanted = wanted && ((win >> (u * RPG)) & ((1ull << RPG) - 1ull)) != 0ull;
+        if (wanted) rows_read += c1 - (r0 + (u32)(u * RPG)) < (u32)RPG ? c1 - (r0 + (u32)(u * RPG)) : (u32)RPG;
+      }
+      if (wanted) {
         u32 rid = r0 + (u32)(u * RPG + sub);
         if (rid > c1 - 1u) rid = c1 - 1u;
         load_row<LPR, NCH>(g.rows + (size_t)rid * g.row_stride, t, g.n16, r[u]);
@@ -2884,7 +2915,9 @@ __global__ __launch_bounds__(256) void k_exact_scores(GraphDev g, ExactArgs a) {
       float *out = a.scores + (size_t)(q0 + (u32)qi) * a.score_stride;
 #pragma unroll
       for (int u0 = 0; u0 < U; u0 += F) {
-        if (r0 + (u32)(u0 * RPG) < c1) { // wave-uniform
+        bool wanted = r0 + (u32)(u0 * RPG) < c1; // wave-uniform
+        if constexpr (TILE) wanted = wanted && ((win >> (u0 * RPG)) & ((1ull << (F * RPG)) - 1ull)) != 0ull;
+        if (wanted) {
           int j;
           float d;
           if (g.mclass == MC_BIN) {
@@ -2928,12 +2961,16 @@ __global__ __launch_bounds__(256) void k_exact_scores(GraphDev g, ExactArgs a) {
       }
     }
   }
+  if constexpr (TILE)
+    if (ln == 0 && rows_read) atomicAdd(&g.stats[ST_EXACT_ROWS], (u64)rows_read);
 }
 
 #if HNY_PART == 0
 // One wave per query: the slab's scores of the slots in a.mask against the query's running list of the k smallest
 // (dist bits << 32 | slot) keys — k_nns_linear's loop on stored distances.  The list is read from and written back
 // to HBM around the slab; four batches of 64 scores are fetched ahead of their ballots.
+// A filter per query (a.filter_of, hny_builder_exact_knn_filtered): the member's own mask, which holds live slots
+// only, the live mask for a member without a filter, and the member's own k (a.k_of); a.rcap is the block's largest.
 __global__ __launch_bounds__(64) void k_exact_topk(GraphDev g, ExactArgs a) {
   extern __shared__ __align__(16) unsigned char smem[];
   u64 *res = reinterpret_cast<u64 *>(smem);
@@ -2941,6 +2978,12 @@ __global__ __launch_bounds__(64) void k_exact_topk(GraphDev g, ExactArgs a) {
   const u32 qi = blockIdx.x;
   u64 *list = a.lists + (size_t)qi * a.rcap;
   const float *sc = a.scores + (size_t)qi * a.score_stride;
+  const u32 *mask = a.mask;
+  if (a.filter_of) {
+    const u32 f = uni(a.filter_of[qi]);
+    if (f != HNY_SENT) mask = a.masks + (size_t)f * a.mask_stride;
+  }
+  const int k = (int)(a.k_of ? uni(a.k_of[qi]) : a.k);
   int res_len = (int)uni(a.list_n[qi]);
   u32 res_err = 0;
   for (int e = ln; e < res_len; e += 64) res[e] = list[e];
@@ -2953,19 +2996,19 @@ __global__ __launch_bounds__(64) void k_exact_topk(GraphDev g, ExactArgs a) {
       key[j] = ~0ull; // no slot is 0xFFFFFFFF: never a real key
       if (s < a.slab_n) {
         const u32 slot = a.slab_base + s;
-        if ((a.mask[slot >> 5] >> (slot & 31u)) & 1u) key[j] = ((u64)fbits(sc[s]) << 32) | slot;
+        if ((mask[slot >> 5] >> (slot & 31u)) & 1u) key[j] = ((u64)fbits(sc[s]) << 32) | slot;
       }
     }
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-      const u64 cur_max = (res_len == (int)a.k && res_len) ? uni(res[res_len - 1]) : ~0ull;
-      u64 want = ballot(key[j] != ~0ull && (res_len < (int)a.k || key[j] < cur_max));
+      const u64 cur_max = (res_len == k && res_len) ? uni(res[res_len - 1]) : ~0ull;
+      u64 want = ballot(key[j] != ~0ull && (res_len < k || key[j] < cur_max));
       while (want) {
         const int r = __ffsll((long long)want) - 1;
         want &= want - 1ull;
         const u64 kr = ((u64)(u32)__builtin_amdgcn_readlane((int)(key[j] >> 32), r) << 32) |
                        (u64)(u32)__builtin_amdgcn_readlane((int)(key[j] & 0xFFFFFFFFull), r);
-        sorted_insert(res, res_len, kr, (int)a.k, (int)a.rcap, res_err);
+        sorted_insert(res, res_len, kr, k, (int)a.rcap, res_err);
       }
     }
   }
@@ -2974,6 +3017,27 @@ __global__ __launch_bounds__(64) void k_exact_topk(GraphDev g, ExactArgs a) {
   if (ln == 0) {
     a.list_n[qi] = (u32)res_len;
     if (res_err) atomicAdd(&g.stats[ST_ERR_RES_OVERFLOW], 1ull);
+  }
+}
+
+// tile_mask[tile][w] = the OR over the tile's members of their mask word for word w of the slab, for the
+// `words` words of the slab (a whole number of chunks; bits at and beyond slab_n are zero).  Consecutive threads
+// take consecutive words of one tile: every mask is read coalesced, and the waves in flight read the same masks.
+// The host orders members by filter, so a run of members with one filter costs one read.
+__global__ __launch_bounds__(256) void k_exact_tile_masks(ExactArgs a, u32 n_tiles, u32 words) {
+  const u32 w_base = a.slab_base >> 5, w_real = (a.slab_n + 31u) >> 5;
+  for (u64 i = (u64)blockIdx.x * 256u + threadIdx.x; i < (u64)n_tiles * words; i += (u64)gridDim.x * 256u) {
+    const u32 tile = (u32)(i / words), w = (u32)(i - (u64)tile * words);
+    const u32 m0 = tile * a.qt, m1 = a.nq - m0 < a.qt ? a.nq : m0 + a.qt;
+    u32 acc = 0, prev = 0;
+    for (u32 m = m0; m < m1 && w < w_real; m++) {
+      const u32 f = a.filter_of[m];
+      if (m > m0 && f == prev) continue;
+      prev = f;
+      const u32 *mask = f == HNY_SENT ? a.mask : a.masks + (size_t)f * a.mask_stride;
+      acc |= mask[w_base + w];
+    }
+    a.tile_mask[(size_t)tile * (HNY_EXACT_SLAB / 32u) + w] = acc;
   }
 }
 
@@ -4554,7 +4618,8 @@ struct ExactScoresLauncher {
   static hipError_t run(const GraphDev &g, const ExactArgs &a, hipStream_t st) {
     const size_t lds = (size_t)a.qt * g.row_stride + (size_t)a.qt * 4;
     const dim3 grid((a.nq + a.qt - 1) / a.qt, (a.slab_n + HNY_EXACT_CHUNK - 1) / HNY_EXACT_CHUNK);
-    return launch_with_lds(k_exact_scores<L, C>, grid, dim3(256), lds, st, g, a);
+    if (a.tile_mask) return launch_with_lds(k_exact_scores<L, C, true>, grid, dim3(256), lds, st, g, a);
+    return launch_with_lds(k_exact_scores<L, C, false>, grid, dim3(256), lds, st, g, a);
   }
 };
 template <int L, int C>
@@ -4650,6 +4715,14 @@ hipError_t hnyk_exact_scores(const GraphDev &g, const ExactArgs &a, LaunchShape 
 hipError_t hnyk_exact_topk(const GraphDev &g, const ExactArgs &a, hipStream_t st) {
   if (!a.nq || !a.slab_n) return hipSuccess;
   hipLaunchKernelGGL(k_exact_topk, dim3(a.nq), dim3(64), (size_t)a.rcap * 8, st, g, a);
+  return hipGetLastError();
+}
+hipError_t hnyk_exact_tile_masks(const ExactArgs &a, hipStream_t st) {
+  if (!a.nq || !a.slab_n) return hipSuccess;
+  const u32 n_tiles = (a.nq + a.qt - 1) / a.qt;
+  const u32 words = (a.slab_n + HNY_EXACT_CHUNK - 1) / HNY_EXACT_CHUNK * (HNY_EXACT_CHUNK / 32u);
+  const u64 blocks = std::min<u64>(((u64)n_tiles * words + 255) / 256, 4096);
+  hipLaunchKernelGGL(k_exact_tile_masks, dim3((unsigned)blocks), dim3(256), 0, st, a, n_tiles, words);
   return hipGetLastError();
 }
 hipError_t hnyk_prune(const GraphDev &g, const PruneArgs &a, LaunchShape s, const PruneForm &f, StageRows sl,

@@ -420,6 +420,36 @@ int hny_builder_nns_filtered_f32(hny_builder *b, const hny_query_opts *opts, con
                                  uint64_t n_queries, const float *queries, size_t qstride,
                                  uint32_t *out_ids, float *out_dists, uint32_t *out_counts);
 
+/* ---- exact k-NN with one `.candidates()` filter per query: the ground truth of hny_builder_nns_filtered in one call.
+ *
+ * Definition: let G(f) be the queries with filter_of[i] == f, in call order.  Their rows of the result (ids, distance
+ * bits, counts) are, byte for byte, what hny_builder_exact_knn returns for those queries alone with the same k,
+ * has_candidates = 1 and candidates = ids[offsets[f] .. offsets[f + 1]); G(HNY_FILTER_NONE) is answered as with
+ * has_candidates = 0.  A filter of |C_f| live candidates gives min(k, |C_f|) hits: one call may return rows of
+ * different lengths, and only the first out_counts[i] entries of a row are written.  An empty filter, or one that
+ * names only unknown or deleted ids, gives 0 hits (HNY_NNS_NONE for by_item), cancelled or not.  by_item: an unknown
+ * or deleted item gives HNY_NNS_NONE; the item itself stays in when its filter holds it.
+ *
+ * opts: k and cancel / cancel_ctx / did_cancel are read; ef_search, linear_below and linear_below_ratio are not;
+ * has_candidates must be 0.  Cancellation as in hny_builder_exact_knn.
+ *
+ * Decided before any query is searched, nothing is written to the outputs: NULL arguments (a NULL builder
+ * included), k == 0, a wrong struct_size, opts->has_candidates != 0, offsets[0] != 0, decreasing offsets,
+ * ids == NULL with offsets[n_filters] > 0, a filter_of entry >= n_filters other than HNY_FILTER_NONE:
+ * HNY_ERR_INVALID_ARG; qstride below the row's bytes: HNY_ERR_INVALID_DIM; a filter that some query uses (or the
+ * live items, for a query without one) with min(k, |C|) > 4 095: HNY_ERR_UNSUPPORTED for the whole call.
+ *
+ * Filters of few candidates are gathered, the others share one dense scan that reads, per tile of queries, only
+ * the rows some query of the tile wants. */
+int hny_builder_exact_knn_filtered(hny_builder *b, const hny_query_opts *opts, const hny_query_filters *filters,
+                                   uint64_t n_queries, const void *qvectors, size_t qstride, const void *qheaders,
+                                   const uint32_t *query_items, uint32_t *out_ids, float *out_dists, uint32_t *out_counts);
+int hny_builder_exact_knn_filtered_f32(hny_builder *b, const hny_query_opts *opts, const hny_query_filters *filters,
+                                       uint64_t n_queries, const float *queries, size_t qstride,
+                                       uint32_t *out_ids, float *out_dists, uint32_t *out_counts);
+/* (tile, row) loads of the dense scan in the last hny_builder_exact_knn_filtered[_f32] call on b; 0 if none ran */
+uint64_t hny_builder_exact_rows_read(const hny_builder *b);
+
 /* ---- resident updates: Writer::add_item / del_item followed by Writer::build (src/writer.rs:462-495, 521-603)
  * on an index whose builder is still alive.  A finished builder holds the codec rows, the norms and the finalised
  * lists of every live item in HBM; the successor takes them from there, device to device (k_move_rows /
