@@ -503,6 +503,44 @@ def _f32_rows(a):
     return a
 
 
+def _query_opts(k, ef_search=0, linear_below=0, linear_below_ratio=0.0, candidates=None, cancel=None):
+    """hny_query_opts of one search call.  cancel: a closure without arguments, true = stop.
+    Returns (struct, what it points into, the int32 did_cancel points at: stays 0 without a closure)"""
+    qo = QueryOpts()
+    qo.k, qo.ef_search = k, ef_search
+    qo.linear_below, qo.linear_below_ratio = linear_below, linear_below_ratio
+    flag = C.c_int32(0)
+    keep = [flag]
+    if cancel is not None:
+        fn = CANCEL_FN(lambda _ctx: 1 if cancel() else 0)
+        qo.cancel, qo.did_cancel = fn, C.pointer(flag)
+        keep.append(fn)
+    if candidates is not None:
+        cand = np.ascontiguousarray(candidates, np.uint32)
+        qo.has_candidates, qo.candidates, qo.n_candidates = 1, cand.ctypes.data, len(cand)
+        keep.append(cand)
+    return qo, keep, flag
+
+
+def _query_source(query_items=None, qf32=None, qcodes=None, qheaders=None):
+    """The queries of one search call, by item, as f32 rows (see _f32_rows) or as codes + headers.
+    Returns ((nq, qvectors, qstride, qheaders, query_items) as the entry points take them, the arrays behind them)"""
+    if query_items is not None:
+        items = np.ascontiguousarray(query_items, np.uint32)
+        return (len(items), None, 0, None, _p(items)), (items,)
+    if qf32 is not None:
+        nq = qf32.shape[0]  # (numpy gives a one-row view whatever stride it likes)
+        return (nq, _p(qf32), qf32.strides[0] if nq > 1 else qf32.shape[1] * 4, None, None), (qf32,)
+    qcodes = np.ascontiguousarray(qcodes, np.uint8)
+    qheaders = np.ascontiguousarray(qheaders, np.uint8)
+    return (qcodes.shape[0], _p(qcodes), qcodes.shape[1], _p(qheaders), None), (qcodes, qheaders)
+
+
+def _result_arrays(nq, k):
+    """(ids, dists, counts) for nq queries of k hits"""
+    return np.zeros((nq, k), np.uint32), np.zeros((nq, k), np.float32), np.zeros(nq, np.uint32)
+
+
 class F32ItemSet:
     """The items as the f32 vectors Writer::add_item takes (src/writer.rs:462-480): build(),
     build_incremental() and Builder hand them to the hny_*_f32 entry points, which encode them on the device
@@ -1080,16 +1118,10 @@ class Builder:
 
     def search_knn(self, qcodes, qheaders, k=10, ef_search=100):
         """Reader::nns(k).by_vector (/root/reference/src/reader.rs:132-148) on the built graph."""
-        qcodes = np.ascontiguousarray(qcodes, np.uint8)
-        qheaders = np.ascontiguousarray(qheaders, np.uint8)
-        nq = qcodes.shape[0]
-        ids = np.zeros((nq, k), np.uint32)
-        dists = np.zeros((nq, k), np.float32)
-        counts = np.zeros(nq, np.uint32)
-        _check(load_library().hny_builder_search_knn(self._h, nq, _p(qcodes), qcodes.shape[1],
-                                                     _p(qheaders), k, ef_search, _p(ids),
-                                                     _p(dists), _p(counts)))
-        return ids, dists, counts
+        (nq, qc, qs, qh, _), _keep = _query_source(qcodes=qcodes, qheaders=qheaders)
+        out = _result_arrays(nq, k)
+        _check(load_library().hny_builder_search_knn(self._h, nq, qc, qs, qh, k, ef_search, *map(_p, out)))
+        return out
 
     def export_items(self):
         """hny_builder_export_items: (codes [n, vector_bytes], headers [n, header_bytes]) of the builder's items in
@@ -1102,14 +1134,28 @@ class Builder:
 
     def search_knn_f32(self, queries, k=10, ef_search=100):
         """search_knn with the &[f32] queries the reference takes, encoded on the device"""
-        q = _f32_rows(queries)
-        nq = q.shape[0]
-        ids = np.zeros((nq, k), np.uint32)
-        dists = np.zeros((nq, k), np.float32)
-        counts = np.zeros(nq, np.uint32)
-        _check(load_library().hny_builder_search_knn_f32(self._h, nq, _p(q), q.strides[0] if nq > 1 else q.shape[1] * 4,
-                                                         k, ef_search, _p(ids), _p(dists), _p(counts)))
-        return ids, dists, counts
+        (nq, qc, qs, _, _), _keep = _query_source(qf32=_f32_rows(queries))
+        out = _result_arrays(nq, k)
+        _check(load_library().hny_builder_search_knn_f32(self._h, nq, qc, qs, k, ef_search, *map(_p, out)))
+        return out
+
+    def _search(self, name, opts, source, f32, filters=None):
+        """One call of the entry point `name` that takes hny_query_opts, of its _f32 form for f32 queries: `opts`
+        from _query_opts, `source` from _query_source, `filters` from QueryFilters.pack.  Returns (ids, dists,
+        counts) and sets did_cancel."""
+        qo, _keep, flag = opts
+        (nq, qc, qs, qh, qi), _arrays = source
+        if filters is not None and len(filters[1][2]) != nq:
+            raise ValueError(f"filter_of has {len(filters[1][2])} entries for {nq} queries")
+        self._cancel_flag = flag
+        out = _result_arrays(nq, qo.k)
+        head = (self._h, C.byref(qo)) + (() if filters is None else (C.byref(filters[0]),))
+        if f32:
+            _check(getattr(load_library(), name + "_f32")(*head, nq, qc, qs, *map(_p, out)))
+        else:
+            _check(getattr(load_library(), name)(*head, nq, qc, qs, qh, qi, *map(_p, out)))
+        self.did_cancel = bool(flag.value)
+        return out
 
     def nns_f32(self, queries, **kw):
         """nns(by_vector) with f32 queries, encoded on the device"""
@@ -1120,39 +1166,9 @@ class Builder:
         """Reader::nns(k).ef_search(..).candidates(..).linear_below(..).by_vector / .by_item
         (/root/reference/src/reader.rs:60-262).  counts == NNS_NONE where by_item returns None.
         cancel: the closure of the *_with_cancellation variants; self.did_cancel tells whether it fired."""
-        qo = QueryOpts()
-        qo.k, qo.ef_search = k, ef_search
-        flag = C.c_int32(0)
-        if cancel is not None:
-            fn = CANCEL_FN(lambda _ctx: 1 if cancel() else 0)
-            qo.cancel = fn
-            qo.did_cancel = C.pointer(flag)
-        self._cancel_flag = flag
-        cand = None
-        if candidates is not None:
-            cand = np.ascontiguousarray(candidates, np.uint32)
-            qo.has_candidates, qo.candidates, qo.n_candidates = 1, cand.ctypes.data, len(cand)
-        qo.linear_below, qo.linear_below_ratio = linear_below, linear_below_ratio
-        if query_items is not None:
-            query_items = np.ascontiguousarray(query_items, np.uint32)
-            nq, qc, qs, qh, qi = len(query_items), None, 0, None, _p(query_items)
-        elif qf32 is not None:
-            nq, qc, qh, qi = qf32.shape[0], _p(qf32), None, None
-            qs = qf32.strides[0] if nq > 1 else qf32.shape[1] * 4
-        else:
-            qcodes = np.ascontiguousarray(qcodes, np.uint8)
-            qheaders = np.ascontiguousarray(qheaders, np.uint8)
-            nq, qc, qs, qh, qi = qcodes.shape[0], _p(qcodes), qcodes.shape[1], _p(qheaders), None
-        ids = np.zeros((nq, k), np.uint32)
-        dists = np.zeros((nq, k), np.float32)
-        counts = np.zeros(nq, np.uint32)
-        if qf32 is not None:
-            _check(load_library().hny_builder_nns_f32(self._h, C.byref(qo), nq, qc, qs, _p(ids), _p(dists), _p(counts)))
-        else:
-            _check(load_library().hny_builder_nns(self._h, C.byref(qo), nq, qc, qs, qh, qi, _p(ids), _p(dists),
-                                                  _p(counts)))
-        self.did_cancel = bool(flag.value)
-        return ids, dists, counts
+        opts = _query_opts(k, ef_search, linear_below, linear_below_ratio, candidates, cancel)
+        return self._search("hny_builder_nns", opts, _query_source(query_items, qf32, qcodes, qheaders),
+                            qf32 is not None)
 
     def nns_filtered_f32(self, queries, filters, filter_of, **kw):
         """nns_filtered(by_vector) with f32 queries, encoded on the device"""
@@ -1163,40 +1179,10 @@ class Builder:
         """hny_builder_nns_filtered: nns with one .candidates() filter per query.  `filters` is a list of id arrays,
         `filter_of[i]` the filter of query i (-1 or NNS_FILTER_NONE: none).  The rows of the queries of one filter
         equal nns(candidates=that filter) on those queries alone."""
-        qo = QueryOpts()
-        qo.k, qo.ef_search = k, ef_search
-        flag = C.c_int32(0)
-        if cancel is not None:
-            fn = CANCEL_FN(lambda _ctx: 1 if cancel() else 0)
-            qo.cancel = fn
-            qo.did_cancel = C.pointer(flag)
-        self._cancel_flag = flag
-        qo.linear_below, qo.linear_below_ratio = linear_below, linear_below_ratio
-        qf, _keep = QueryFilters.pack(filters, filter_of)
-        if query_items is not None:
-            query_items = np.ascontiguousarray(query_items, np.uint32)
-            nq, qc, qs, qh, qi = len(query_items), None, 0, None, _p(query_items)
-        elif qf32 is not None:
-            nq, qc, qh, qi = qf32.shape[0], _p(qf32), None, None
-            qs = qf32.strides[0] if nq > 1 else qf32.shape[1] * 4
-        else:
-            qcodes = np.ascontiguousarray(qcodes, np.uint8)
-            qheaders = np.ascontiguousarray(qheaders, np.uint8)
-            nq, qc, qs, qh, qi = qcodes.shape[0], _p(qcodes), qcodes.shape[1], _p(qheaders), None
-        if len(_keep[2]) != nq:
-            raise ValueError(f"filter_of has {len(_keep[2])} entries for {nq} queries")
-        ids = np.zeros((nq, k), np.uint32)
-        dists = np.zeros((nq, k), np.float32)
-        counts = np.zeros(nq, np.uint32)
-        L = load_library()
-        if qf32 is not None:
-            _check(L.hny_builder_nns_filtered_f32(self._h, C.byref(qo), C.byref(qf), nq, qc, qs, _p(ids), _p(dists),
-                                                  _p(counts)))
-        else:
-            _check(L.hny_builder_nns_filtered(self._h, C.byref(qo), C.byref(qf), nq, qc, qs, qh, qi, _p(ids), _p(dists),
-                                              _p(counts)))
-        self.did_cancel = bool(flag.value)
-        return ids, dists, counts
+        opts = _query_opts(k, ef_search, linear_below, linear_below_ratio, cancel=cancel)
+        qf = QueryFilters.pack(filters, filter_of)
+        return self._search("hny_builder_nns_filtered", opts, _query_source(query_items, qf32, qcodes, qheaders),
+                            qf32 is not None, qf)
 
     def exact_knn_f32(self, queries, **kw):
         """exact_knn(by_vector) with f32 queries, encoded on the device"""
@@ -1206,38 +1192,9 @@ class Builder:
         """hny_builder_exact_knn: the k nearest of the live items (or of `candidates` among them) by a flat scan —
         brute_force_search's result, the ground truth of the index's own distances.  Returns (ids, dists, counts)
         like nns; counts == NNS_NONE where by_item names an unknown item."""
-        qo = QueryOpts()
-        qo.k = k
-        flag = C.c_int32(0)
-        if cancel is not None:
-            fn = CANCEL_FN(lambda _ctx: 1 if cancel() else 0)
-            qo.cancel = fn
-            qo.did_cancel = C.pointer(flag)
-        self._cancel_flag = flag
-        cand = None
-        if candidates is not None:
-            cand = np.ascontiguousarray(candidates, np.uint32)
-            qo.has_candidates, qo.candidates, qo.n_candidates = 1, cand.ctypes.data, len(cand)
-        L = load_library()
-        if query_items is not None:
-            query_items = np.ascontiguousarray(query_items, np.uint32)
-            nq, qc, qs, qh, qi = len(query_items), None, 0, None, _p(query_items)
-        elif qf32 is not None:
-            nq, qc, qh, qi = qf32.shape[0], _p(qf32), None, None
-            qs = qf32.strides[0] if nq > 1 else qf32.shape[1] * 4
-        else:
-            qcodes = np.ascontiguousarray(qcodes, np.uint8)
-            qheaders = np.ascontiguousarray(qheaders, np.uint8)
-            nq, qc, qs, qh, qi = qcodes.shape[0], _p(qcodes), qcodes.shape[1], _p(qheaders), None
-        ids = np.zeros((nq, k), np.uint32)
-        dists = np.zeros((nq, k), np.float32)
-        counts = np.zeros(nq, np.uint32)
-        if qf32 is not None:
-            _check(L.hny_builder_exact_knn_f32(self._h, C.byref(qo), nq, qc, qs, _p(ids), _p(dists), _p(counts)))
-        else:
-            _check(L.hny_builder_exact_knn(self._h, C.byref(qo), nq, qc, qs, qh, qi, _p(ids), _p(dists), _p(counts)))
-        self.did_cancel = bool(flag.value)
-        return ids, dists, counts
+        opts = _query_opts(k, candidates=candidates, cancel=cancel)
+        return self._search("hny_builder_exact_knn", opts, _query_source(query_items, qf32, qcodes, qheaders),
+                            qf32 is not None)
 
     def exact_knn_filtered_f32(self, queries, filters, filter_of, **kw):
         """exact_knn_filtered(by_vector) with f32 queries, encoded on the device"""
@@ -1248,39 +1205,10 @@ class Builder:
         """hny_builder_exact_knn_filtered: exact_knn with one .candidates() filter per query, `filters` and
         `filter_of` as in nns_filtered.  The rows of the queries of one filter equal exact_knn(candidates=that
         filter) on those queries alone: counts[i] = min(k, live candidates of query i's filter)."""
-        qo = QueryOpts()
-        qo.k = k
-        flag = C.c_int32(0)
-        if cancel is not None:
-            fn = CANCEL_FN(lambda _ctx: 1 if cancel() else 0)
-            qo.cancel = fn
-            qo.did_cancel = C.pointer(flag)
-        self._cancel_flag = flag
-        qf, _keep = QueryFilters.pack(filters, filter_of)
-        if query_items is not None:
-            query_items = np.ascontiguousarray(query_items, np.uint32)
-            nq, qc, qs, qh, qi = len(query_items), None, 0, None, _p(query_items)
-        elif qf32 is not None:
-            nq, qc, qh, qi = qf32.shape[0], _p(qf32), None, None
-            qs = qf32.strides[0] if nq > 1 else qf32.shape[1] * 4
-        else:
-            qcodes = np.ascontiguousarray(qcodes, np.uint8)
-            qheaders = np.ascontiguousarray(qheaders, np.uint8)
-            nq, qc, qs, qh, qi = qcodes.shape[0], _p(qcodes), qcodes.shape[1], _p(qheaders), None
-        if len(_keep[2]) != nq:
-            raise ValueError(f"filter_of has {len(_keep[2])} entries for {nq} queries")
-        ids = np.zeros((nq, k), np.uint32)
-        dists = np.zeros((nq, k), np.float32)
-        counts = np.zeros(nq, np.uint32)
-        L = load_library()
-        if qf32 is not None:
-            _check(L.hny_builder_exact_knn_filtered_f32(self._h, C.byref(qo), C.byref(qf), nq, qc, qs, _p(ids),
-                                                        _p(dists), _p(counts)))
-        else:
-            _check(L.hny_builder_exact_knn_filtered(self._h, C.byref(qo), C.byref(qf), nq, qc, qs, qh, qi, _p(ids),
-                                                    _p(dists), _p(counts)))
-        self.did_cancel = bool(flag.value)
-        return ids, dists, counts
+        opts = _query_opts(k, cancel=cancel)
+        qf = QueryFilters.pack(filters, filter_of)
+        return self._search("hny_builder_exact_knn_filtered", opts,
+                            _query_source(query_items, qf32, qcodes, qheaders), qf32 is not None, qf)
 
     def exact_rows_read(self):
         """(tile, row) loads of the dense scan in the last exact_knn_filtered call on this builder; 0 if none ran"""

@@ -16,6 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <iterator>
 #include <memory>
 #include <string>
@@ -3718,19 +3719,13 @@ static uint64_t filter_mask_budget() {
   return v ? v : HNY_FILTER_MASK_BYTES;
 }
 
-// the filters that queries use, ascending, and the queries that have one in filter order
-static void filters_in_use(const hny_query_filters *fl, uint64_t nq, std::vector<u32> &used,
-                           std::vector<uint64_t> &by_filter) {
-  std::vector<unsigned char> seen(fl->n_filters, 0);
-  for (uint64_t i = 0; i < nq; i++)
-    if (fl->filter_of[i] != HNY_FILTER_NONE) {
-      seen[fl->filter_of[i]] = 1;
-      by_filter.push_back(i);
-    }
-  for (uint32_t f = 0; f < fl->n_filters; f++)
-    if (seen[f]) used.push_back(f);
-  std::stable_sort(by_filter.begin(), by_filter.end(),
-                   [&](uint64_t x, uint64_t y) { return fl->filter_of[x] < fl->filter_of[y]; });
+// A row of hits, `c` of them, to query qi of the caller's arrays, whose rows may be wider.  Like the searchers, only
+// the first `c` entries of a row are written, and none of a row without an answer (HNY_NNS_NONE)
+static void copy_hits(const QuerySet &q, uint64_t qi, uint32_t c, const uint32_t *ids, const float *dists) {
+  q.out_counts[qi] = c;
+  if (c == HNY_NNS_NONE) return;
+  memcpy(&q.out_ids[qi * q.k], ids, (size_t)c * 4);
+  memcpy(&q.out_dists[qi * q.k], dists, (size_t)c * 4);
 }
 
 // some of a call's queries, gathered so that the shared steps see them as a call of their own
@@ -3769,34 +3764,69 @@ struct SubBatch {
     return QuerySet{b, m, rows.data(), rb, hdrs.data(), q.by_item ? items.data() : nullptr, q.q_f32, q.by_item, kk,
                     ids.data(), dists.data(), counts.data()};
   }
-  // the hits to the caller's rows; like the searchers, only the first `count` entries of a row are written
+  // the hits to the caller's rows
   void scatter() const {
-    for (size_t j = 0; j < idx.size(); j++) {
-      const uint32_t c = counts[j];
-      q.out_counts[idx[j]] = c;
-      if (c == HNY_NNS_NONE) continue;
-      const uint32_t kk = k ? k : q.k;
-      memcpy(&q.out_ids[idx[j] * q.k], &ids[j * kk], (size_t)c * 4);
-      memcpy(&q.out_dists[idx[j] * q.k], &dists[j * kk], (size_t)c * 4);
-    }
+    const uint32_t kk = k ? k : q.k;
+    for (size_t j = 0; j < idx.size(); j++) copy_hits(q, idx[j], counts[j], &ids[j * kk], &dists[j * kk]);
   }
 };
 
-// the bitsets of some filters on the device and how many live candidates each holds
-struct FilterMasks {
+// The filters of a call with one filter per query, in rounds of as many bitsets as the budget holds (one always
+// fits: n < 2^31 slots are 256 MB).  nns_filtered_impl and exact_filtered_impl each run their own loop over the
+// rounds: build(r), classify(r, ..) and, where the scan class has queries, compact(); the refusals, the launches
+// and the class without a filter stay theirs.
+static_assert(HNY_FILTER_NONE == HNY_SENT, "a query without a filter sorts with the live set, after every filter");
+struct FilterRounds {
   hny_builder *b;
   const QuerySet &q;
   const hny_query_filters *fl;
-  u32 stride; // words per bitset
+  std::vector<u32> used;           // the filters that queries use, ascending
+  std::vector<uint64_t> by_filter; // the queries that have one, in filter order
+  u32 stride;                      // words per bitset
+  size_t per_round, built = (size_t)-1, at = 0; // at: the first query of by_filter that no round has taken yet
+  // round `built`: the bitsets on the device and how many live candidates each holds
   DevBuf<u32> dmasks, dslots, dcount;
   DevBuf<u64> doff;
   std::vector<u32> count;
+  // its gathered filters, once classified: their places in the round, the CSR offsets of their live slots (a filter
+  // that is not gathered holds none), the most hits one of them gives (min(k, count)); compact()'s buffers
+  std::vector<u32> lin;
+  std::vector<u64> cs_off;
+  uint32_t most_hits = 0;
+  DevBuf<u32> dlin, dcs;
+  DevBuf<u64> dcs_off;
 
-  // filters used[r0 .. r1): ids -> live slots (unknown and deleted ids drop out, duplicates stay), CSR upload,
-  // bits set and counted on the device, the counts back in one copy.  HNY_SENT in `used` (last, if at all) is
-  // the live set as one more filter: exact_filtered_impl's queries without a filter in strict mode
-  int build(const std::vector<u32> &used, size_t r0, size_t r1) {
-    const size_t nf = r1 - r0;
+  static u32 mask_stride(uint32_t n) { return (u32)((((size_t)n + 31) / 32 + 4) & ~(size_t)3); }
+  FilterRounds(hny_builder *b, const QuerySet &q, const hny_query_filters *fl)
+      : b(b), q(q), fl(fl), stride(mask_stride(b->n)),
+        per_round((size_t)std::max<uint64_t>(1, filter_mask_budget() / ((uint64_t)stride * 4))) {
+    std::vector<unsigned char> seen(fl->n_filters, 0);
+    for (uint64_t i = 0; i < q.nq; i++)
+      if (fl->filter_of[i] != HNY_FILTER_NONE) {
+        seen[fl->filter_of[i]] = 1;
+        by_filter.push_back(i);
+      }
+    for (uint32_t f = 0; f < fl->n_filters; f++)
+      if (seen[f]) used.push_back(f);
+    std::stable_sort(by_filter.begin(), by_filter.end(),
+                     [&](uint64_t x, uint64_t y) { return fl->filter_of[x] < fl->filter_of[y]; });
+  }
+  // strict exact mode: the live set is one more filter, the last, and `plain` (the queries without one) are its own
+  void add_live(const std::vector<uint64_t> &plain) {
+    used.push_back(HNY_SENT);
+    by_filter.insert(by_filter.end(), plain.begin(), plain.end());
+  }
+  size_t n_rounds(uint64_t n_items) const { return n_items ? (used.size() + per_round - 1) / per_round : 0; }
+
+  // Round r unless it is the one held.  Ids -> live slots (unknown and deleted ids drop out, duplicates stay), CSR
+  // upload, bits set and counted on the device, the counts back in one copy
+  int build(size_t r) {
+    if (built == r) return HNY_OK;
+    built = r;
+    dlin.release(); // the gathered slots of the round before go with its bitsets
+    dcs.release();
+    dcs_off.release();
+    const size_t r0 = r * per_round, nf = std::min(used.size() - r0, per_round);
     std::vector<u64> off(nf + 1, 0);
     std::vector<u32> slots;
     for (size_t j = 0; j < nf; j++) {
@@ -3824,6 +3854,48 @@ struct FilterMasks {
     HIP_TRY(hipStreamSynchronize(b->stream)); // (`off` and `slots` leave scope)
     return HNY_OK;
   }
+  // The round held: a filter with live candidates whose count `gathered` accepts is scanned over its compacted
+  // slots.  The round's queries follow in by_filter from where the round before stopped (the last round takes the
+  // rest, HNY_SENT's included): those of an empty filter are answered here, nothing can match; the others go to
+  // `scan` (filter gathered) or `rest`, each with its filter's place in the round
+  void classify(const std::function<bool(u32)> &gathered, SubBatch &scan, SubBatch &rest) {
+    const size_t nf = count.size(), f1 = built * per_round + nf;
+    lin.clear();
+    cs_off.assign(nf + 1, 0);
+    most_hits = 0;
+    for (size_t j = 0; j < nf; j++) {
+      const bool g = count[j] && gathered(count[j]);
+      if (g) {
+        lin.push_back((u32)j);
+        most_hits = std::max(most_hits, std::min(q.k, count[j]));
+      }
+      cs_off[j + 1] = cs_off[j] + (g ? count[j] : 0u);
+    }
+    for (; at < by_filter.size() && (f1 == used.size() || fl->filter_of[by_filter[at]] < used[f1]); at++) {
+      const uint64_t qi = by_filter[at];
+      const u32 j = (u32)(std::lower_bound(used.begin() + (f1 - nf), used.begin() + f1, fl->filter_of[qi]) -
+                          used.begin() - (f1 - nf));
+      if (!count[j]) q.out_counts[qi] = q.by_item ? HNY_NNS_NONE : 0u;
+      else if (cs_off[j + 1] > cs_off[j]) scan.add(qi, j);
+      else rest.add(qi, j);
+    }
+  }
+  // the live slots of the round's gathered filters as a CSR on the device (k_filter_compact), and the view of bitsets
+  // and CSR for the scan class; the caller adds its sub-batch's filter_of
+  int compact(NnsFilters &L) {
+    const size_t nf = count.size();
+    HIP_TRY(dlin.alloc(lin.size()));
+    HIP_TRY(dcs_off.alloc(nf + 1));
+    HIP_TRY(dcs.alloc(cs_off[nf]));
+    HIP_TRY(hipMemcpyAsync(dlin.p, lin.data(), lin.size() * 4, hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(dcs_off.p, cs_off.data(), (nf + 1) * 8, hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hnyk_filter_compact(dmasks.p, stride, dlin.p, (u32)lin.size(), dcs_off.p, dcs.p, b->stream));
+    L.masks = dmasks.p;
+    L.mask_stride = stride;
+    L.cand_slots = dcs.p;
+    L.cs_off = dcs_off.p;
+    return HNY_OK;
+  }
 };
 
 static int nns_filtered_impl(hny_builder *b, const hny_query_opts *qo, const hny_query_filters *fl, uint64_t nq,
@@ -3831,9 +3903,8 @@ static int nns_filtered_impl(hny_builder *b, const hny_query_opts *qo, const hny
                              uint32_t *out_ids, float *out_dists, uint32_t *out_counts, bool q_f32) {
   if (int rc = check_search_outputs(b, out_ids, out_dists, out_counts, qo ? qo->k : 0)) return rc;
   if (int rc = check_filters(qo, fl, nq)) return rc;
-  const uint32_t n_filters = fl->n_filters, NONE = HNY_NNS_NONE;
   const bool by_item = query_items != nullptr;
-  const uint32_t k = qo->k;
+  const uint32_t k = qo->k, NONE = HNY_NNS_NONE;
   const QuerySet qs{b, nq, qvectors, qstride, qheaders, query_items, q_f32, by_item, k, out_ids, out_dists, out_counts};
   if (int rc = check_query_source(qs, "no queries")) return rc;
   if (int rc = check_query_rows(qs)) return rc;
@@ -3847,34 +3918,23 @@ static int nns_filtered_impl(hny_builder *b, const hny_query_opts *qo, const hny
   HIP_TRY(hipSetDevice(b->device));
   const uint64_t n_items = qs.n_live();
 
-  std::vector<u32> used;
-  std::vector<uint64_t> by_filter;
-  filters_in_use(fl, nq, used, by_filter);
-  // rounds of as many bitsets as the budget holds (one always fits: n < 2^31 slots are 256 MB)
-  FilterMasks fm{b, qs, fl, (u32)((((size_t)b->n + 31) / 32 + 4) & ~(size_t)3)};
-  const size_t per_round = (size_t)std::max<uint64_t>(1, filter_mask_budget() / ((uint64_t)fm.stride * 4));
-  const size_t n_rounds = n_items ? (used.size() + per_round - 1) / per_round : 0;
+  FilterRounds fr(b, qs, fl);
+  const size_t n_rounds = fr.n_rounds(n_items);
   auto is_linear = [&](u32 cl) { // should_linear_scan, reader.rs:621-640
     return (uint64_t)cl < (uint64_t)qo->linear_below && (float)cl / (float)n_items <= qo->linear_below_ratio;
   };
   // the refusal: no query has been searched yet
   auto check_round = [&](size_t r) -> int {
-    for (size_t j = 0; big && j < fm.count.size(); j++)
-      if (is_linear(fm.count[j]) && !linear_rcap(std::min<uint64_t>(k, fm.count[j])))
+    for (size_t j = 0; big && j < fr.count.size(); j++)
+      if (is_linear(fr.count[j]) && !linear_rcap(std::min<uint64_t>(k, fr.count[j])))
         return fail(HNY_ERR_UNSUPPORTED,
                     "filter %u: linear scan for %u hits among %u candidates: at most %u (lower linear_below)",
-                    used[r * per_round + j], k, fm.count[j], HNY_RES_LDS_MAX - 1);
+                    fr.used[r * fr.per_round + j], k, fr.count[j], HNY_RES_LDS_MAX - 1);
     return HNY_OK;
-  };
-  size_t built = (size_t)-1;
-  auto build_round = [&](size_t r) -> int {
-    if (built == r) return HNY_OK;
-    built = r;
-    return fm.build(used, r * per_round, std::min(used.size(), (r + 1) * per_round));
   };
   if (n_rounds == 1 || (big && (uint64_t)k + 1 > HNY_RES_LDS_MAX)) // several rounds: the counts of all, ahead
     for (size_t r = 0; r < n_rounds; r++) {
-      if (int rc = build_round(r)) return rc;
+      if (int rc = fr.build(r)) return rc;
       if (int rc = check_round(r)) return rc;
     }
 
@@ -3915,55 +3975,27 @@ static int nns_filtered_impl(hny_builder *b, const hny_query_opts *qo, const hny
   }
   // nothing to search among (reader.rs:652-654 / 822-824)
   if (n_items == 0)
-    for (uint64_t qi : by_filter) out_counts[qi] = by_item ? NONE : 0u;
+    for (uint64_t qi : fr.by_filter) out_counts[qi] = by_item ? NONE : 0u;
   // 2. round by round: the linear filters' slots compacted on the device, then the linear and the walked queries
-  size_t at = 0;
   for (size_t r = 0; r < n_rounds; r++) {
-    if (int rc = build_round(r)) return rc;
-    const size_t f0 = r * per_round, nf = fm.count.size();
-    std::vector<u32> lin;
-    std::vector<u64> cs_off(nf + 1, 0);
-    uint64_t most_hits = 0;
-    for (size_t j = 0; j < nf; j++) {
-      const bool linear = fm.count[j] && is_linear(fm.count[j]);
-      if (linear) {
-        lin.push_back((u32)j);
-        most_hits = std::max<uint64_t>(most_hits, std::min<uint64_t>(k, fm.count[j]));
-      }
-      cs_off[j + 1] = cs_off[j] + (linear ? fm.count[j] : 0u);
-    }
+    if (int rc = fr.build(r)) return rc;
     SubBatch scan{qs}, walk{qs};
-    for (; at < by_filter.size() && fl->filter_of[by_filter[at]] < (r + 1 < n_rounds ? used[f0 + nf] : n_filters); at++) {
-      const uint64_t qi = by_filter[at];
-      const u32 j = (u32)(std::lower_bound(used.begin() + f0, used.begin() + f0 + nf, fl->filter_of[qi]) - used.begin() - f0);
-      if (!fm.count[j]) out_counts[qi] = by_item ? NONE : 0u; // an empty filter: nothing can match
-      else if (cs_off[j + 1] > cs_off[j]) scan.add(qi, j);
-      else walk.add(qi, j);
-    }
-    NnsFilters F;
-    F.masks = fm.dmasks.p;
-    F.mask_stride = fm.stride;
-    DevBuf<u32> dlin, dcs;
-    DevBuf<u64> dcs_off;
+    fr.classify(is_linear, scan, walk);
     if (!scan.idx.empty()) {
-      HIP_TRY(dlin.alloc(lin.size()));
-      HIP_TRY(dcs_off.alloc(nf + 1));
-      HIP_TRY(dcs.alloc(cs_off[nf]));
-      HIP_TRY(hipMemcpyAsync(dlin.p, lin.data(), lin.size() * 4, hipMemcpyHostToDevice, b->stream));
-      HIP_TRY(hipMemcpyAsync(dcs_off.p, cs_off.data(), (nf + 1) * 8, hipMemcpyHostToDevice, b->stream));
-      HIP_TRY(hnyk_filter_compact(fm.dmasks.p, fm.stride, dlin.p, (u32)lin.size(), dcs_off.p, dcs.p, b->stream));
+      NnsFilters L;
+      if (int rc = fr.compact(L)) return rc;
       const QuerySet sub = scan.gather();
-      NnsFilters L = F;
       L.filter_of = scan.filter_of.data();
-      L.cand_slots = dcs.p;
-      L.cs_off = dcs_off.p;
-      const uint32_t rcap = big ? linear_rcap(most_hits) : rcap_walk; // (check_round has seen to most_hits)
+      const uint32_t rcap = big ? linear_rcap(fr.most_hits) : rcap_walk; // (check_round has seen to most_hits)
       if (!rcap) return fail(HNY_ERR_UNSUPPORTED, "linear scan for %u hits: at most %u", k, HNY_RES_LDS_MAX - 1);
       if (int rc = nns_run(b, qo, sub, L, true, big, ef, rcap, sc)) return rc;
       scan.scatter();
     }
     if (!walk.idx.empty()) {
       const QuerySet sub = walk.gather();
+      NnsFilters F;
+      F.masks = fr.dmasks.p;
+      F.mask_stride = fr.stride;
       F.filter_of = walk.filter_of.data();
       if (int rc = nns_run(b, qo, sub, F, false, big, ef, rcap_walk, sc)) return rc;
       walk.scatter();
@@ -4107,7 +4139,7 @@ static int exact_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, con
                       uint32_t *out_counts, bool q_f32) {
   if (int rc = check_search_outputs(b, out_ids, out_dists, out_counts, qo ? qo->k : 0)) return rc;
   const bool by_item = query_items != nullptr;
-  const uint32_t n = b->n, k = qo->k, NONE = HNY_NNS_NONE;
+  const uint32_t n = b->n, k = qo->k;
   const QuerySet qs{b, nq, qvectors, qstride, qheaders, query_items, q_f32, by_item, k, out_ids, out_dists, out_counts};
   if (int rc = check_query_source(qs, "no queries")) return rc;
   if (int rc = check_candidates(qo)) return rc; // here the candidates come before the f32 rows, in nns_impl after
@@ -4148,11 +4180,7 @@ static int exact_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, con
     int rc = nns_impl(b, &o2, nq, qvectors, qstride, qheaders, query_items, ti.data(), td.data(), out_counts, false,
                       q_f32);
     if (rc) return rc;
-    for (uint64_t i = 0; i < nq; i++) {
-      if (out_counts[i] == NONE) continue;
-      memcpy(&out_ids[i * k], &ti[i * kk], (size_t)out_counts[i] * 4);
-      memcpy(&out_dists[i * k], &td[i * kk], (size_t)out_counts[i] * 4);
-    }
+    for (uint64_t i = 0; i < nq; i++) copy_hits(qs, i, out_counts[i], &ti[i * kk], &td[i * kk]);
     return HNY_OK;
   }
   DevBuf<u32> dmask;
@@ -4179,7 +4207,7 @@ int hny_builder_exact_knn_f32(hny_builder *b, const hny_query_opts *qo, uint64_t
 // ---------------------------------------------------------------------------------------------
 // exact k-NN with one candidates filter per query.  The rows of the queries of one filter are
 // those of exact_impl on these queries alone with that filter.  The filters become bitsets on the device
-// (FilterMasks); each is routed by §3d's traffic model from its own count: count x qt < n rows -> the gather
+// (FilterRounds); each is routed by §3d's traffic model from its own count: count x qt < n rows -> the gather
 // (k_filter_compact, k_nns_linear on the CSR), else the dense scan, which all dense filters and the queries without
 // one share (exact_dense_run with ExactFilters).  Strict mode gathers everything, the live set being one more filter.
 // ---------------------------------------------------------------------------------------------
@@ -4194,7 +4222,7 @@ static int exact_filtered_impl(hny_builder *b, const hny_query_opts *qo, const h
   if (int rc = check_search_outputs(b, out_ids, out_dists, out_counts, qo ? qo->k : 0)) return rc;
   if (int rc = check_filters(qo, fl, nq)) return rc; // the candidates' side before the f32 rows, as in exact_impl
   const bool by_item = query_items != nullptr;
-  const uint32_t n = b->n, k = qo->k, NONE = HNY_NNS_NONE;
+  const uint32_t n = b->n, k = qo->k;
   const QuerySet qs{b, nq, qvectors, qstride, qheaders, query_items, q_f32, by_item, k, out_ids, out_dists, out_counts};
   if (int rc = check_query_source(qs, "no queries")) return rc;
   if (int rc = check_query_rows(qs)) return rc;
@@ -4209,34 +4237,22 @@ static int exact_filtered_impl(hny_builder *b, const hny_query_opts *qo, const h
   auto hits_of = [&](uint64_t c) { return (uint32_t)std::min<uint64_t>(k, c); };
   auto gathered = [&](uint64_t c) { return strict || c * qt < n; }; // §3d: |C| rows per query against n / qt
 
-  std::vector<u32> used;
-  std::vector<uint64_t> by_filter, plain;
-  filters_in_use(fl, nq, used, by_filter);
+  FilterRounds fr(b, qs, fl);
+  std::vector<uint64_t> plain;
   for (uint64_t i = 0; i < nq; i++)
     if (fl->filter_of[i] == HNY_FILTER_NONE) plain.push_back(i);
-  if (strict && !plain.empty()) { // the live set is one more filter, the last: its queries are gathered like the others
-    used.push_back(HNY_SENT);
-    by_filter.insert(by_filter.end(), plain.begin(), plain.end());
-  }
-  FilterMasks fm{b, qs, fl, (u32)((((size_t)n + 31) / 32 + 4) & ~(size_t)3)};
-  const size_t per_round = (size_t)std::max<uint64_t>(1, filter_mask_budget() / ((uint64_t)fm.stride * 4));
-  const size_t n_rounds = n_items ? (used.size() + per_round - 1) / per_round : 0;
-  size_t built = (size_t)-1;
-  auto build_round = [&](size_t r) -> int {
-    if (built == r) return HNY_OK;
-    built = r;
-    return fm.build(used, r * per_round, std::min(used.size(), (r + 1) * per_round));
-  };
+  if (strict && !plain.empty()) fr.add_live(plain); // their queries are gathered like the others
+  const size_t n_rounds = fr.n_rounds(n_items);
   // the refusal, from the counts of every round: no query has been searched yet
   if (!plain.empty() && (uint64_t)hits_of(n_items) + 1 > HNY_RES_LDS_MAX)
     return fail(HNY_ERR_UNSUPPORTED, "exact scan for %u hits among %llu items: at most %u hits", k,
                 (unsigned long long)n_items, HNY_RES_LDS_MAX - 1);
   for (size_t r = 0; r < n_rounds; r++) {
-    if (int rc = build_round(r)) return rc;
-    for (size_t j = 0; j < fm.count.size(); j++)
-      if ((uint64_t)hits_of(fm.count[j]) + 1 > HNY_RES_LDS_MAX)
+    if (int rc = fr.build(r)) return rc;
+    for (size_t j = 0; j < fr.count.size(); j++)
+      if ((uint64_t)hits_of(fr.count[j]) + 1 > HNY_RES_LDS_MAX)
         return fail(HNY_ERR_UNSUPPORTED, "filter %u: exact scan for %u hits among %u candidates: at most %u hits",
-                    used[r * per_round + j], k, fm.count[j], HNY_RES_LDS_MAX - 1);
+                    fr.used[r * fr.per_round + j], k, fr.count[j], HNY_RES_LDS_MAX - 1);
   }
   SearchCancel sc;
   HIP_TRY(sc.begin(qo));
@@ -4253,60 +4269,30 @@ static int exact_filtered_impl(hny_builder *b, const hny_query_opts *qo, const h
     std::vector<u32> k_of(dense.idx.size()), count_of(dense.idx.size());
     uint32_t most = 0;
     for (size_t j = 0; j < k_of.size(); j++) {
-      count_of[j] = dense.filter_of[j] == HNY_SENT ? (u32)n_items : fm.count[dense.filter_of[j]];
+      count_of[j] = dense.filter_of[j] == HNY_SENT ? (u32)n_items : fr.count[dense.filter_of[j]];
       k_of[j] = hits_of(count_of[j]);
       most = std::max(most, k_of[j]);
     }
     dense.k = most;
     const QuerySet sub = dense.gather();
-    const ExactFilters F{dense.filter_of.data(), k_of.data(), count_of.data(), fm.dmasks.p, fm.stride, skip};
+    const ExactFilters F{dense.filter_of.data(), k_of.data(), count_of.data(), fr.dmasks.p, fr.stride, skip};
     if (int rc = exact_dense_run(b, sub, dlive.p, most, &F, sc)) return rc;
     dense.scatter();
     return HNY_OK;
   };
-  size_t at = 0;
   for (size_t r = 0; r < n_rounds; r++) {
-    if (int rc = build_round(r)) return rc;
-    const size_t f0 = r * per_round, nf = fm.count.size();
-    std::vector<u32> lin;
-    std::vector<u64> cs_off(nf + 1, 0);
-    uint32_t most_hits = 0;
-    for (size_t j = 0; j < nf; j++) {
-      const bool g = fm.count[j] && gathered(fm.count[j]);
-      if (g) {
-        lin.push_back((u32)j);
-        most_hits = std::max(most_hits, hits_of(fm.count[j]));
-      }
-      cs_off[j + 1] = cs_off[j] + (g ? fm.count[j] : 0u);
-    }
+    if (int rc = fr.build(r)) return rc;
     SubBatch scan{qs}, dense{qs};
-    const uint64_t f_end = r + 1 < n_rounds ? used[f0 + nf] : (uint64_t)1 << 32; // (HNY_SENT sorts last)
-    for (; at < by_filter.size() && fl->filter_of[by_filter[at]] < f_end; at++) {
-      const uint64_t qi = by_filter[at];
-      const u32 j = (u32)(std::lower_bound(used.begin() + f0, used.begin() + f0 + nf, fl->filter_of[qi]) - used.begin() - f0);
-      if (!fm.count[j]) out_counts[qi] = by_item ? NONE : 0u; // an empty filter: nothing can match
-      else if (cs_off[j + 1] > cs_off[j]) scan.add(qi, j);
-      else dense.add(qi, j);
-    }
+    fr.classify(gathered, scan, dense);
     if (r + 1 == n_rounds && !strict)
       for (uint64_t qi : plain) dense.add(qi, HNY_SENT);
     if (!scan.idx.empty()) {
-      DevBuf<u32> dlin, dcs;
-      DevBuf<u64> dcs_off;
-      HIP_TRY(dlin.alloc(lin.size()));
-      HIP_TRY(dcs_off.alloc(nf + 1));
-      HIP_TRY(dcs.alloc(cs_off[nf]));
-      HIP_TRY(hipMemcpyAsync(dlin.p, lin.data(), lin.size() * 4, hipMemcpyHostToDevice, b->stream));
-      HIP_TRY(hipMemcpyAsync(dcs_off.p, cs_off.data(), (nf + 1) * 8, hipMemcpyHostToDevice, b->stream));
-      HIP_TRY(hnyk_filter_compact(fm.dmasks.p, fm.stride, dlin.p, (u32)lin.size(), dcs_off.p, dcs.p, b->stream));
+      NnsFilters L;
+      if (int rc = fr.compact(L)) return rc;
+      const uint32_t most_hits = fr.most_hits;
       scan.k = most_hits; // min(k, count) of the sub-batch's largest filter; a smaller one fills its row short
       const QuerySet sub = scan.gather();
-      NnsFilters L;
-      L.masks = fm.dmasks.p;
-      L.mask_stride = fm.stride;
       L.filter_of = scan.filter_of.data();
-      L.cand_slots = dcs.p;
-      L.cs_off = dcs_off.p;
       if (int rc = nns_run(b, qo, sub, L, true, false, most_hits, linear_rcap(most_hits), sc)) return rc;
       scan.scatter();
     }

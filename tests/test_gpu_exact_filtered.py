@@ -563,3 +563,43 @@ def test_api_layer(hny):
         assert 0.9 < rec <= 1.0 and r.recall(qs, n=10, ef_search=n) == 1.0
     finally:
         r.close()
+
+
+# 15 ------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def strict600(orc, hny):
+    rng = np.random.default_rng(15)
+    ds, b, g = _built(orc, hny, EUCLIDEAN, rng.uniform(-1, 1, (600, 8)).astype(np.float32), M=8, M0=16, ef=40,
+                      x86_order=True)
+    yield ds, b
+    b.close()
+
+
+@pytest.mark.parametrize("empty", [False, True], ids=["", "empty-middle"])
+@pytest.mark.parametrize("n_filters", [4, 5])
+def test_strict_live_set_across_mask_rounds(orc, hny, strict600, monkeypatch, n_filters, empty):
+    """strict mode, queries without a filter and two masks per round: the live set is one more filter after the last.
+    4 filters: rounds {0, 1}, {2, 3}, {live set}; 5 filters: {0, 1}, {2, 3}, {4, live set}; with `empty`, filter 2 of
+    the middle round holds unknown ids only.  Two or three queries per filter, dealt out of filter order; by vector
+    and by item (one unknown item) against one exact_knn call per filter"""
+    ds, b = strict600
+    n, k = len(ds.ids), 5
+    rng = np.random.default_rng(150 + 2 * n_filters + empty)
+    filters = [rng.choice(ds.ids, 60, replace=False).astype(np.uint32) for _ in range(n_filters)]
+    if empty:
+        filters[2] = np.arange(n, n + 60, dtype=np.uint32)  # ids == slots: none of these is known
+    fo = rng.permutation(np.concatenate([np.full(2 + f % 2, f) for f in range(-1, n_filters)]))
+    nq = len(fo)
+    _, qc, qh = _queries(orc, EUCLIDEAN, rng, nq, 8)
+    qi = ds.ids[rng.integers(0, n, nq)].astype(np.uint32)
+    qi[int(np.flatnonzero(fo == 1)[0])] = 10 ** 6
+    stride_bytes = ((n + 31) // 32 + 4) // 4 * 4 * 4
+    monkeypatch.setenv("HNY_FILTER_MASK_BYTES", str(2 * stride_bytes + 8))
+    got = b.exact_knn_filtered(filters, fo, qc, qh, k=k)
+    _same(got, _loop(b, filters, fo, k, qc, qh), "by_vector")
+    assert (got[2][fo != 2] == k).all() and (got[2][fo == 2] == (0 if empty else k)).all()
+    got = b.exact_knn_filtered(filters, fo, query_items=qi, k=k)
+    _same(got, _loop(b, filters, fo, k, qi=qi), "by_item")
+    known = qi != 10 ** 6
+    assert (got[2][~known] == NONE).all() and (got[2][known & (fo != 2)] == k).all()
+    assert (got[2][known & (fo == 2)] == (NONE if empty else k)).all() and b.exact_rows_read() == 0

@@ -390,3 +390,30 @@ def test_query_builder_candidates_per_query(hny):
         cnt = 0 if counts[0] == NONE else int(counts[0])
         assert np.array_equal(ids[0, :cnt], got[0][i, :cnt])
     r.close()
+
+
+def test_unfiltered_queries_across_mask_rounds(orc, hny, monkeypatch):
+    """four filters of 60 ids and queries without one, two bitsets per round: the last round takes what is left.  Two
+    or three queries per filter, dealt out of filter order; scanned (linear_below = 1000) and walked (0), by vector
+    and by item (one unknown item) against one nns call per filter"""
+    n, dim, k, ef = 600, 8, 5, 40
+    rng, vecs, ds, b, g = _index(orc, hny, 1, n, dim, 8, 16, 40, 16)
+    filters = [rng.choice(ds.ids, 60, replace=False).astype(np.uint32) for _ in range(4)]
+    fo = rng.permutation(np.concatenate([np.full(2 + f % 2, f) for f in range(-1, 4)]))
+    qs = rng.uniform(-1, 1, (len(fo), dim)).astype(np.float32)
+    qc = orc.encode_vectors(1, qs)
+    qh = orc.make_headers(1, dim, qc)
+    qi = ds.ids[rng.integers(0, n, len(fo))].astype(np.uint32)
+    qi[int(np.flatnonzero(fo == 1)[0])] = 10 ** 6
+    stride_bytes = ((n + 31) // 32 + 4) // 4 * 4 * 4
+    monkeypatch.setenv("HNY_FILTER_MASK_BYTES", str(2 * stride_bytes + 8))
+    with b:
+        for lb in (1000, 0):
+            got = b.nns_filtered(filters, fo, qc, qh, k=k, ef_search=ef, linear_below=lb)
+            _same(got, _per_group(b, filters, fo, k, lambda rows, c: b.nns(qc[rows], qh[rows], k=k, ef_search=ef,
+                                                                           candidates=c, linear_below=lb)))
+            assert lb == 0 or (got[2] == k).all()  # a scan ranks every candidate
+            got = b.nns_filtered(filters, fo, query_items=qi, k=k, ef_search=ef, linear_below=lb)
+            _same(got, _per_group(b, filters, fo, k, lambda rows, c: b.nns(query_items=qi[rows], k=k, ef_search=ef,
+                                                                           candidates=c, linear_below=lb)))
+            assert (got[2][qi == 10 ** 6] == NONE).all() and (lb == 0 or (got[2][qi != 10 ** 6] == k).all())
