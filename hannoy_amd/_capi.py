@@ -40,6 +40,7 @@ EXPORTED = [
     "hny_builder_exact_knn", "hny_builder_exact_knn_f32",
     "hny_builder_nns_filtered", "hny_builder_nns_filtered_f32",
     "hny_builder_exact_knn_filtered", "hny_builder_exact_knn_filtered_f32", "hny_builder_exact_rows_read",
+    "hny_distance_keeps_links", "hny_builder_create_changed_distance", "hny_builder_recode_items",
 ]
 ERR_IO = -9
 NNS_NONE = 0xFFFFFFFF  # by_item: the reference returns None
@@ -154,6 +155,16 @@ class Update(C.Structure):
     def __init__(self, *a, **kw):
         super().__init__(*a, **kw)
         self.struct_size = C.sizeof(Update)
+
+
+class ChangeDistance(C.Structure):
+    """hny_change_distance; struct_size is the guard (the struct is not part of hny_abi_sizes)"""
+    _fields_ = [("struct_size", C.c_uint32), ("new_metric", C.c_int32), ("levels", C.c_void_p),
+                ("seed", C.c_uint64), ("update", C.POINTER(Update))]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_size = C.sizeof(ChangeDistance)
 
 
 class GraphDeltaStruct(C.Structure):
@@ -324,6 +335,12 @@ def load_library():
     L.hny_builder_finish_delta.argtypes = [vp, C.POINTER(C.POINTER(GraphDeltaStruct))]
     L.hny_graph_delta_free.restype = None
     L.hny_graph_delta_free.argtypes = [C.POINTER(GraphDeltaStruct)]
+    L.hny_distance_keeps_links.restype = C.c_int
+    L.hny_distance_keeps_links.argtypes = [C.c_int32, C.c_int32]
+    L.hny_builder_create_changed_distance.restype = C.c_int
+    L.hny_builder_create_changed_distance.argtypes = [vp, C.POINTER(ChangeDistance), C.POINTER(vp)]
+    L.hny_builder_recode_items.restype = C.c_int
+    L.hny_builder_recode_items.argtypes = [vp, C.c_int32, vp, vp]
     L.hny_abi_sizes.restype = C.c_uint32
     L.hny_abi_sizes.argtypes = [C.POINTER(C.c_uint32), C.c_uint32]
     _check_abi(L)
@@ -435,6 +452,11 @@ class StdRng:
         _check(load_library().hny_draw_levels_from_seed(seed, self.drawn, M, n, _p(out)))
         self.drawn += n
         return out
+
+
+def distance_keeps_links(old_metric, new_metric):
+    """hny_distance_keeps_links: Writer::prepare_changing_distance keeps links and Metadata for this pair"""
+    return bool(load_library().hny_distance_keeps_links(int(old_metric), int(new_metric)))
 
 
 def vector_bytes(metric, dim):
@@ -674,7 +696,11 @@ class Graph:
             out.append((bytes(k[:kl]), bytes(v[:vl])))
             return 0
         cb = KV_SINK(sink)
-        it = self._items.encoded().struct()  # an F32ItemSet encodes on the host here, once
+        if isinstance(self._items, _IdsOnly) and not with_items:  # a successor's items live on the device
+            ids = np.ascontiguousarray(self._items.ids, np.uint32)
+            it = Items(len(ids), _p(ids).value, None, 0, None, 0, None)
+        else:
+            it = self._items.encoded().struct()  # an F32ItemSet encodes on the host here, once
         _check(load_library().hny_encode_kv(self._gp, C.byref(self._opts), C.byref(it), index,
                                             int(with_items), cb, None))
         return out
@@ -1103,6 +1129,42 @@ class Builder:
         g = Graph(gp, self.opts, self.items) if full else None
         d = GraphDelta(dp, self.opts) if delta else None
         return (g, d) if full and delta else g if full else d
+
+    # -- resident change of distance (hny_builder_create_changed_distance) ----------
+    def create_changed_distance(self, new_metric, levels=None, seed=42, upsert_ids=(), vectors=None, codes=None,
+                                headers=None, delete_ids=()):
+        """hny_builder_create_changed_distance: a Builder of `new_metric` whose rows are encoded on the device from
+        the f32 rows of this (finished or loaded) builder.  `levels`: one per item that exists after the change.
+        Upserts are f32 `vectors`, or `codes` + `headers` of the NEW codec.  Kept-links pairs (distance_keeps_links)
+        give an incremental Builder on this builder's graph, the others a fresh one.  This builder stays usable."""
+        new_metric = int(new_metric)
+        u, keep = self._update_struct(upsert_ids, vectors, codes, headers, delete_ids, None, seed)
+        c = ChangeDistance()
+        c.new_metric, c.seed = new_metric, int(seed)
+        if len(keep[0]) or len(keep[1]):
+            c.update = C.pointer(u)
+        if levels is not None:
+            lv = np.ascontiguousarray(levels, np.uint8)
+            c.levels = _p(lv).value
+            keep.append(lv)
+        h = C.c_void_p()
+        _check(load_library().hny_builder_create_changed_distance(self._h, C.byref(c), C.byref(h)))
+        b = self._successor(h, keep)
+        b.items = _IdsOnly(new_metric, self.items.dim, b.items.ids)
+        b.opts = BuildOpts.from_buffer_copy(self.opts)
+        b.opts.metric, b.opts.seed = new_metric, int(seed)
+        b._opts_keep = self.opts  # (the callbacks the copied pointers refer to)
+        b.incremental = distance_keeps_links(self.items.metric, new_metric)
+        return b
+
+    def recode_items(self, new_metric):
+        """hny_builder_recode_items: (codes, headers) of this builder's items as `new_metric` stores them, encoded on
+        the device from the resident f32 rows; ascending id order"""
+        n = self.items.n
+        codes = np.zeros((n, vector_bytes(new_metric, self.items.dim)), np.uint8)
+        headers = np.zeros((n, header_bytes(new_metric)), np.uint8)
+        _check(load_library().hny_builder_recode_items(self._h, int(new_metric), _p(codes), _p(headers)))
+        return codes, headers
 
     def finish_delta(self):
         dp = C.POINTER(GraphDeltaStruct)()

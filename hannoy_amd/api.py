@@ -197,6 +197,9 @@ class Writer:
         # resident=True: the builder of the last build, the options it was made with and the items it indexes
         self.resident, self._rb, self._rb_kw, self._rb_ids, self._rb_gen = bool(resident), None, None, None, -1
         self.last_delta = None  # resident: the GraphDelta of the last build that went through hny_builder_update
+        # resident, between prepare_changing_distance and the next build: (old metric, the recoded codes, headers) of
+        # the held builder's items — that build goes through hny_builder_create_changed_distance
+        self._rb_change = None
 
     def close(self):
         """releases the resident builder (a Writer without one holds nothing)"""
@@ -270,13 +273,10 @@ class Writer:
         """writer.rs:358-410: re-encode every item for the new distance, mark all of them updated;
         links and metadata go unless the new distance is the binary-quantized form of the old one."""
         old = self.db.distance
+        if distance != old and self._resident_change_ok(old):
+            return self._prepare_changing_distance_resident(distance)
         if distance != old:
-            new_name, old_name = str(distance), str(old)
-            if not (new_name.startswith("binary quantized ") and new_name[len("binary quantized "):] == old_name):
-                llo, lhi = key(self.index, MODE_LINKS), key(self.index, MODE_LINKS, 0xFFFFFFFF, 0xFF)
-                for k in [k for k in self.db.kv if llo <= k <= lhi]:
-                    del self.db.kv[k]
-                self.db.kv.pop(key(self.index, MODE_METADATA), None)
+            self._drop_links_unless_kept(old, distance)
             ids = self.db.item_ids(self.index)
             hb = capi.header_bytes(old.value)
             vecs = []
@@ -293,6 +293,50 @@ class Writer:
                     self.db.kv[key(self.index, MODE_UPDATED, int(i))] = UPDATED
         w = Writer(self.db, self.dimensions, self.index, self.m, self.ef)
         w.alpha, w.seed = self.alpha, self.seed
+        return w
+
+    def _drop_links_unless_kept(self, old, distance):
+        """writer.rs:359-368: links and Metadata go unless the new distance is the binary-quantized form of the old"""
+        new_name, old_name = str(distance), str(old)
+        if not (new_name.startswith("binary quantized ") and new_name[len("binary quantized "):] == old_name):
+            llo, lhi = key(self.index, MODE_LINKS), key(self.index, MODE_LINKS, 0xFFFFFFFF, 0xFF)
+            for k in [k for k in self.db.kv if llo <= k <= lhi]:
+                del self.db.kv[k]
+            self.db.kv.pop(key(self.index, MODE_METADATA), None)
+
+    def _resident_change_ok(self, old):
+        """the held builder can serve prepare_changing_distance: it has an f32 codec and is valid in the sense of
+        _build_resident — (2) it indexes exactly what the Metadata record says is indexed, (3) no other build has
+        touched this index since — and the store holds exactly its items, none added or removed since its build"""
+        db, index = self.db, self.index
+        if not self.resident or self._rb is None or self._rb_change is not None:
+            return False
+        if old.value not in (capi.COSINE, capi.EUCLIDEAN, capi.MANHATTAN) or self._rb_kw["metric"] != old.value:
+            return False
+        meta = db.metadata(index)
+        if meta is None or self._rb_gen != db.build_generation.get(index, 0):
+            return False
+        if set(self._rb_ids.tolist()) != set(meta["items"].tolist()) or len(self._rb_ids) == 0:
+            return False
+        lo, hi = key(index, MODE_UPDATED), key(index, MODE_UPDATED, 0xFFFFFFFF, 0xFF)
+        return not any(lo <= k <= hi for k in db.kv) and np.array_equal(db.item_ids(index), self._rb_ids)
+
+    def _prepare_changing_distance_resident(self, distance):
+        """prepare_changing_distance on the held builder: the Item records come from hny_builder_recode_items (the
+        device encodes its f32 rows for the new distance), and the builder goes to the returned Writer, whose next
+        build() runs hny_builder_create_changed_distance on it"""
+        db, index, old = self.db, self.index, self.db.distance
+        codes, hdrs = self._rb.recode_items(distance.value)
+        self._drop_links_unless_kept(old, distance)
+        db.distance = distance
+        for r, i in enumerate(self._rb_ids):
+            db.kv[key(index, MODE_ITEM, int(i))] = b"\x00" + hdrs[r].tobytes() + codes[r].tobytes()
+            db.kv[key(index, MODE_UPDATED, int(i))] = UPDATED
+        w = Writer(db, self.dimensions, index, self.m, self.ef, resident=True)
+        w.alpha, w.seed = self.alpha, self.seed
+        w._rb, w._rb_kw, w._rb_ids, w._rb_gen = self._rb, self._rb_kw, self._rb_ids, self._rb_gen
+        w._rb_change = (old.value, codes, hdrs)
+        self._rb = None
         return w
 
     def builder(self, rng=42):
@@ -404,6 +448,11 @@ class Writer:
         (Records edited directly in Database.kv are not detected.)"""
         db, index = self.db, self.index
         opts_key = dict({k: v for k, v in kw.items() if k != "seed"}, metric=db.distance.value)
+        if self._rb_change is not None:
+            g = self._build_changed_distance(meta, indexed, ids, to_insert, to_delete, levels, relink_all_items, kw, opts_key)
+            if g is not None:
+                self._rb_ids, self._rb_gen = ids, db.build_generation.get(index, 0) + 1
+                return g
         if (self._rb is not None and opts_key == self._rb_kw and not relink_all_items and meta is not None
                 and self._rb_gen == db.build_generation.get(index, 0) and set(self._rb_ids.tolist()) == indexed):
             ups = db.item_set(index, np.array(to_insert, np.uint32), self.dimensions)
@@ -424,6 +473,59 @@ class Writer:
             g, self._rb = self._build_all_records(meta, ids, to_insert, to_delete, levels, kw, keep_builder=True)
             self._rb_kw = opts_key
         self._rb_ids, self._rb_gen = ids, db.build_generation.get(index, 0) + 1
+        return g
+
+
+    def _build_changed_distance(self, meta, indexed, ids, to_insert, to_delete, levels, relink_all_items, kw, opts_key):
+        """the first build after a resident prepare_changing_distance: hny_builder_create_changed_distance on the
+        held builder, the items added, overwritten or deleted since travelling as its update.  The store gets the
+        delta (kept-links pairs) or every record (the others).  Returns None, with the held builder released, when
+        it no longer fits (other options, another build in between, force_rebuild): the caller takes the host path."""
+        db, index = self.db, self.index
+        old_metric, codes, hdrs = self._rb_change
+        new_metric = db.distance.value
+        keeps = capi.distance_keeps_links(old_metric, new_metric)
+        fits = (self._rb is not None and not relink_all_items and len(ids) > 0
+                and opts_key == dict(self._rb_kw, metric=new_metric)
+                and self._rb_gen == db.build_generation.get(index, 0)
+                and list(to_insert) == ids.tolist()
+                and ((meta is not None and set(self._rb_ids.tolist()) == indexed) if keeps else meta is None))
+        if not fits:
+            self._rb_change = None
+            self.close()
+            return None
+        # upserts: items the builder does not hold, or whose record is no longer the recoded one
+        row_of = {int(i): r for r, i in enumerate(self._rb_ids)}
+        ups = []
+        for i in ids.tolist():
+            r = row_of.get(i)
+            if r is None or db.kv[key(index, MODE_ITEM, i)] != b"\x00" + hdrs[r].tobytes() + codes[r].tobytes():
+                ups.append(i)
+        up = db.item_set(index, np.array(ups, np.uint32), self.dimensions)
+        lv = None if levels is None else np.array([levels[int(i)] for i in ids], np.uint8)
+        succ = self._rb.create_changed_distance(new_metric, levels=lv, seed=kw.get("seed", 42), upsert_ids=up.ids,
+                                                codes=up.codes, headers=up.headers, delete_ids=to_delete)
+        try:
+            succ.run()
+            g = succ.finish()
+            if keeps:
+                d = succ.finish_delta()
+                for item, layer in d.removed_keys():  # delete_links_from_db (writer.rs:692-718)
+                    del db.kv[key(index, MODE_LINKS, item, layer)]
+                for k, v in d.encode_kv(ids, index):  # the changed Links records, Metadata, Version
+                    db.kv[k] = v
+                self.last_delta = d
+            else:
+                llo, lhi = key(index, MODE_LINKS), key(index, MODE_LINKS, 0xFFFFFFFF, 0xFF)
+                for k in [k for k in db.kv if llo <= k <= lhi]:
+                    del db.kv[k]
+                for k, v in g.encode_kv(index, with_items=False):
+                    db.kv[k] = v
+        except BaseException:
+            succ.close()
+            raise
+        self._rb.close()
+        self._rb, self._rb_kw, self._rb_change = succ, opts_key, None
         return g
 
 

@@ -672,6 +672,16 @@ IngestJob ingest_job(int metric, uint32_t dim, unsigned char *rows, uint32_t row
   return j;
 }
 
+// what the codec of `metric` asks of k_ingest
+void ingest_codec(IngestArgs &a, int metric, uint32_t dim) {
+  const size_t vb = vec_bytes(metric, dim);
+  a.dim = dim;
+  a.codec = metric == HNY_COSINE ? ING_F32_NORM : metric == HNY_HAMMING ? ING_BINARY : is_binary(metric) ? ING_BQ : ING_F32;
+  a.hdr_const = metric == HNY_BQ_COSINE ? sqrtf((float)(int32_t)(vb * 8)) : 0.0f; // sqrt(dot_bq(v,v)) = sqrt(padded dims)
+  a.vb = (u32)vb;
+  a.hb = (u32)hdr_bytes(metric);
+}
+
 // the caller synchronises `st` (the kernels and, with packed outputs, the copies back are enqueued on it)
 int run_ingest(IngestPipe &p, const IngestJob &j, hipStream_t st) {
   if (!j.n) return HNY_OK;
@@ -716,10 +726,8 @@ int run_ingest(IngestPipe &p, const IngestJob &j, hipStream_t st) {
     IngestArgs a{};
     a.src = (const float *)p.d[k];
     a.src_stride = (u32)(sstride / 4);
-    a.dim = j.dim;
     a.cnt = (u32)cnt;
-    a.codec = j.metric == HNY_COSINE ? ING_F32_NORM : j.metric == HNY_HAMMING ? ING_BINARY : is_binary(j.metric) ? ING_BQ : ING_F32;
-    a.hdr_const = j.metric == HNY_BQ_COSINE ? sqrtf((float)(int32_t)(vb * 8)) : 0.0f; // sqrt(dot_bq(v,v)) = sqrt(padded dims)
+    ingest_codec(a, j.metric, j.dim);
     a.slots = j.d_slots ? j.d_slots + r0 : nullptr;
     a.slot_base = (u32)r0;
     a.rows = j.rows;
@@ -727,8 +735,6 @@ int run_ingest(IngestPipe &p, const IngestJob &j, hipStream_t st) {
     a.norms = j.norms;
     a.out_codes = j.out_codes ? p.d_codes[k] : nullptr;
     a.out_hdrs = j.out_hdrs ? p.d_hdrs[k] : nullptr;
-    a.vb = (u32)vb;
-    a.hb = (u32)hb;
     HIP_TRY(hnyk_ingest(a, st));
     HIP_TRY(hipEventRecord(p.consumed[k], st));
     p.used[k] = true;
@@ -962,6 +968,9 @@ struct IncrementalSpec {
   // (then `items` carries the ids of the items after the update only; the upserted rows come from `upd`)
   hny_builder *src = nullptr;
   const hny_update *upd = nullptr;
+  // hny_builder_create_changed_distance outside the kept-links pairs: `src` gives its rows only, re-encoded; the
+  // successor is planned and built as a fresh index over `items` (no universe, no lists, no deletes to plan)
+  bool rows_only = false;
 };
 
 // which (slot, layer) records a builder's finish() exports: bit l = layer l
@@ -1063,9 +1072,87 @@ struct CreatePlan {
   std::vector<std::pair<uint32_t, uint8_t>> levels; // (slot, level) in the reference's order
 };
 
+// ---- a successor's rows from its source builder, device to device ----
+// HIP events around the row kernel when the source is profiling (hny_builder_set_profiling(src, 1)): device time and
+// bytes read + written, for scripts/update_throughput.py and scripts/change_distance_throughput.py
+struct RowsTimer {
+  hipEvent_t a = nullptr, b = nullptr;
+  int begin(hipStream_t st) {
+    HIP_TRY(hipEventCreate(&a));
+    HIP_TRY(hipEventCreate(&b));
+    HIP_TRY(hipEventRecord(a, st));
+    return HNY_OK;
+  }
+  ~RowsTimer() {
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+  }
+};
+// Change of distance: slot t of `b` gets the f32 row live_of[t] of `src` encoded for b's codec, or
+// a zero row and a zero norm (HNY_SENT).  One k_ingest launch with a gathered source; enqueued on `st`.
+static int recode_rows_from_source(hny_builder *b, const hny_builder *src, const u32 *d_live_of, hipStream_t st) {
+  IngestArgs a{};
+  a.src = (const float *)src->d_rows.p;
+  a.src_stride = src->g.row_stride / 4u;
+  a.src_of = d_live_of;
+  a.cnt = b->n;
+  ingest_codec(a, b->o.metric, b->o.dim);
+  a.rows = b->d_rows.p;
+  a.row_stride = b->g.row_stride;
+  a.norms = b->d_norms.p; // (NULL for the metrics without norms)
+  HIP_TRY(hnyk_ingest(a, st));
+  return HNY_OK;
+}
+// the upserted rows on top of the moved ones (same stream: an overwritten item ends with its new row): f32 rows are
+// encoded on the device, codec bytes are staged and scattered.  `ub` stays alive until the stream is synchronised.
+struct UpsertBufs {
+  std::vector<uint32_t> slots;
+  std::vector<float> norms;
+  DevBuf<u32> d_slots;
+  DevBuf<unsigned char> d_stage;
+  DevBuf<float> d_stage_norms;
+};
+static int place_upserts(hny_builder *b, const hny_update *u, IngestPipe &pipe, UpsertBufs &ub) {
+  if (!u || !u->n_upsert) return HNY_OK;
+  hipStream_t st = b->stream;
+  const hny_build_opts &o = b->o;
+  const GraphDev &g = b->g;
+  const size_t vb = vec_bytes(o.metric, o.dim), hb = hdr_bytes(o.metric);
+  ub.slots.resize(u->n_upsert); // where the upserted rows go
+  for (uint64_t i = 0; i < u->n_upsert; i++) ub.slots[i] = slot_of(b->ids, u->upsert_ids[i]);
+  HIP_TRY(ub.d_slots.alloc(u->n_upsert));
+  HIP_TRY(hipMemcpyAsync(ub.d_slots.p, ub.slots.data(), (size_t)u->n_upsert * 4, hipMemcpyHostToDevice, st));
+  if (u->vectors_are_f32) {
+    HIP_TRY(hipStreamSynchronize(st)); // (d_slots is read by kernels behind copies of the pipe's own stream)
+    IngestJob j = ingest_job(o.metric, o.dim, b->d_rows.p, g.row_stride, b->d_norms.p);
+    j.d_slots = ub.d_slots.p;
+    j.src = u->vectors;
+    j.stride = u->stride;
+    j.n = u->n_upsert;
+    return run_ingest(pipe, j, st);
+  }
+  HIP_TRY(ub.d_stage.alloc((size_t)u->n_upsert * g.row_stride));
+  if (int rc = upload_rows(u->vectors, u->stride, vb, u->n_upsert, g.row_stride, ub.d_stage.p, st)) return rc;
+  if (g.norms) {
+    ub.norms.resize(u->n_upsert);
+    for (uint64_t i = 0; i < u->n_upsert; i++) memcpy(&ub.norms[i], (const unsigned char *)u->headers + i * hb, 4);
+    HIP_TRY(ub.d_stage_norms.alloc(u->n_upsert));
+    HIP_TRY(hipMemcpyAsync(ub.d_stage_norms.p, ub.norms.data(), (size_t)u->n_upsert * 4, hipMemcpyHostToDevice, st));
+  }
+  HIP_TRY(hnyk_scatter_rows(ub.d_stage.p, ub.d_stage_norms.p, ub.d_slots.p, b->d_rows.p, b->d_norms.p, (u32)u->n_upsert, g.n16, st));
+  return HNY_OK;
+}
+static void rows_timer_read(hny_builder *b, const hny_builder *src, const RowsTimer &ev, uint64_t n_live) {
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, ev.a, ev.b) == hipSuccess) b->t_move_rows_s = ms * 1e-3;
+  // every live source row read, every successor row written (a zero row where there is no source)
+  b->move_rows_bytes = n_live * src->g.row_stride + (uint64_t)b->n * b->g.row_stride;
+}
+
 // Resident update (hny_builder_create_update): rows, norms and the finalised lists of `src` go to their slots in
-// the successor `b` device to device, then the upserted rows land on top (same stream: an overwritten item ends
-// with its new row).  Host -> device: the two slot maps, one u16 mask per slot, the upper-index table, the upserts.
+// the successor `b` device to device, then the upserted rows land on top.  A successor of another distance
+// (hny_builder_create_changed_distance, kept-links pairs) gets its rows encoded from the source's instead of moved.
+// Host -> device: the two slot maps, one u16 mask per slot, the upper-index table, the upserts.
 static int move_state_from_source(hny_builder *b, const hny_update *u, const PrevState &prev, IngestPipe &pipe) {
   hny_builder *const src = prev.src;
   const std::vector<uint32_t> &src_of = prev.src_of, &new_of = prev.new_of;
@@ -1073,21 +1160,23 @@ static int move_state_from_source(hny_builder *b, const hny_update *u, const Pre
   const hny_build_opts &o = b->o;
   GraphDev &g = b->g;
   const uint32_t n = b->n;
-  const size_t vb = vec_bytes(o.metric, o.dim), hb = hdr_bytes(o.metric);
+  const bool recode = src->o.metric != o.metric;
   // the source's lists: a loaded graph keeps them where it put them (d_d0_ids / d_du_ids, nothing was inserted);
   // a built one in l0_ids / up_ids, finalised (finish() and the searches do that; do it here if neither ran)
   if (!src->load_only)
     if (int rc = ensure_finalized(src, src->stream)) return rc;
   HIP_TRY(hipStreamSynchronize(src->stream));
   std::vector<unsigned short> mask(n);
-  for (uint32_t t = 0; t < n; t++)
-    mask[t] = (unsigned short)(b->old_mask[t] | (src_of[t] != HNY_SENT && prev.src_live[src_of[t]] ? HNY_MV_LIVE : 0u));
+  uint64_t n_live = 0;
+  for (uint32_t t = 0; t < n; t++) {
+    const bool live = src_of[t] != HNY_SENT && prev.src_live[src_of[t]];
+    mask[t] = (unsigned short)(b->old_mask[t] | (live ? HNY_MV_LIVE : 0u));
+    n_live += live;
+  }
   std::vector<u32> up_slot(std::max<uint32_t>(b->n_upper, 1), 0);
   for (uint32_t t = 0; t < n; t++)
     if (b->upper_idx[t] >= 0) up_slot[b->upper_idx[t]] = t;
-  std::vector<uint32_t> up_slots(u->n_upsert); // where the upserted rows go
-  for (uint64_t i = 0; i < u->n_upsert; i++) up_slots[i] = slot_of(b->ids, u->upsert_ids[i]);
-  DevBuf<u32> d_src_of, d_new_of, d_up_slot, d_ups;
+  DevBuf<u32> d_src_of, d_new_of, d_up_slot, d_live_of;
   DevBuf<unsigned short> d_mask;
   DevBuf<u64> d_bad;
   HIP_TRY(d_src_of.alloc(n));
@@ -1100,58 +1189,34 @@ static int move_state_from_source(hny_builder *b, const hny_update *u, const Pre
   HIP_TRY(hipMemcpyAsync(d_mask.p, mask.data(), (size_t)n * 2, hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(d_up_slot.p, up_slot.data(), up_slot.size() * 4, hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemsetAsync(d_bad.p, 0, 8, st));
+  std::vector<u32> live_of; // recode: the source row of each slot, HNY_SENT where the mask has no HNY_MV_LIVE
+  if (recode) {
+    live_of.resize(n);
+    for (uint32_t t = 0; t < n; t++) live_of[t] = (mask[t] & HNY_MV_LIVE) ? src_of[t] : HNY_SENT;
+    HIP_TRY(d_live_of.alloc(n));
+    HIP_TRY(hipMemcpyAsync(d_live_of.p, live_of.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+  }
   // rows + norms
-  MoveRowsArgs mr{};
-  mr.src_rows = src->d_rows.p;
-  mr.src_norms = src->d_norms.p;
-  mr.src_of = d_src_of.p;
-  mr.mask = d_mask.p;
-  mr.dst_rows = b->d_rows.p;
-  mr.dst_norms = b->d_norms.p; // (NULL for the metrics without norms)
-  mr.n_new = n;
-  mr.n16 = g.n16;
-  // hny_builder_set_profiling(src, 1): device time and bytes of k_move_rows (scripts/update_throughput.py)
-  struct EvPair {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~EvPair() {
-      if (a) (void)hipEventDestroy(a);
-      if (b) (void)hipEventDestroy(b);
-    }
-  } ev;
-  if (src->profiling) {
-    HIP_TRY(hipEventCreate(&ev.a));
-    HIP_TRY(hipEventCreate(&ev.b));
-    HIP_TRY(hipEventRecord(ev.a, st));
+  RowsTimer ev;
+  if (src->profiling)
+    if (int rc = ev.begin(st)) return rc;
+  if (recode) {
+    if (int rc = recode_rows_from_source(b, src, d_live_of.p, st)) return rc;
+  } else {
+    MoveRowsArgs mr{};
+    mr.src_rows = src->d_rows.p;
+    mr.src_norms = src->d_norms.p;
+    mr.src_of = d_src_of.p;
+    mr.mask = d_mask.p;
+    mr.dst_rows = b->d_rows.p;
+    mr.dst_norms = b->d_norms.p; // (NULL for the metrics without norms)
+    mr.n_new = n;
+    mr.n16 = g.n16;
+    HIP_TRY(hnyk_move_rows(mr, st));
   }
-  HIP_TRY(hnyk_move_rows(mr, st));
   if (src->profiling) HIP_TRY(hipEventRecord(ev.b, st));
-  // upserts
-  DevBuf<unsigned char> d_stage;
-  DevBuf<float> d_stage_norms;
-  std::vector<float> up_norms;
-  if (u->n_upsert) {
-    HIP_TRY(d_ups.alloc(u->n_upsert));
-    HIP_TRY(hipMemcpyAsync(d_ups.p, up_slots.data(), (size_t)u->n_upsert * 4, hipMemcpyHostToDevice, st));
-    if (u->vectors_are_f32) {
-      HIP_TRY(hipStreamSynchronize(st)); // (d_ups is read by kernels behind copies of the pipe's own stream)
-      IngestJob j = ingest_job(o.metric, o.dim, b->d_rows.p, g.row_stride, b->d_norms.p);
-      j.d_slots = d_ups.p;
-      j.src = u->vectors;
-      j.stride = u->stride;
-      j.n = u->n_upsert;
-      if (int rc = run_ingest(pipe, j, st)) return rc;
-    } else {
-      HIP_TRY(d_stage.alloc((size_t)u->n_upsert * g.row_stride));
-      if (int rc = upload_rows(u->vectors, u->stride, vb, u->n_upsert, g.row_stride, d_stage.p, st)) return rc;
-      if (g.norms) {
-        up_norms.resize(u->n_upsert);
-        for (uint64_t i = 0; i < u->n_upsert; i++) memcpy(&up_norms[i], (const unsigned char *)u->headers + i * hb, 4);
-        HIP_TRY(d_stage_norms.alloc(u->n_upsert));
-        HIP_TRY(hipMemcpyAsync(d_stage_norms.p, up_norms.data(), (size_t)u->n_upsert * 4, hipMemcpyHostToDevice, st));
-      }
-      HIP_TRY(hnyk_scatter_rows(d_stage.p, d_stage_norms.p, d_ups.p, b->d_rows.p, b->d_norms.p, (u32)u->n_upsert, g.n16, st));
-    }
-  }
+  UpsertBufs ub;
+  if (int rc = place_upserts(b, u, pipe, ub)) return rc;
   // lists: records of to-be-deleted and overwritten items move like any other (the build expects them in `prev`)
   const size_t nup = (size_t)b->n_upper * b->up_layers;
   MoveListsArgs ml{};
@@ -1177,16 +1242,40 @@ static int move_state_from_source(hny_builder *b, const hny_update *u, const Pre
   u64 bad = 0;
   HIP_TRY(hipMemcpyAsync(&bad, d_bad.p, 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
-  if (src->profiling) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, ev.a, ev.b) == hipSuccess) b->t_move_rows_s = ms * 1e-3;
-    uint64_t moved = 0;
-    for (uint32_t t = 0; t < n; t++) moved += (mask[t] & HNY_MV_LIVE) ? 2 : 1; // read + write, or the zero row written
-    b->move_rows_bytes = moved * g.row_stride;
-  }
+  if (src->profiling) rows_timer_read(b, src, ev, n_live);
   if (bad)
     return fail(HNY_ERR_DEVICE, "update: %llu neighbours of the source's lists name a slot that owns no record — the "
                 "slot universe cannot be derived without the lists (DESIGN.md §3c)", (unsigned long long)bad);
+  return HNY_OK;
+}
+// Change of distance outside the kept-links pairs: the successor `b` is a fresh index over the items after the change
+// (b->ids, ascending like src->ids: one merge gives the map); it takes nothing from `src` but the re-encoded rows.
+static int recode_state_from_source(hny_builder *b, hny_builder *src, const hny_update *u, IngestPipe &pipe) {
+  hipStream_t st = b->stream;
+  const uint32_t n = b->n;
+  const std::vector<uint8_t> live = live_slots(src);
+  std::vector<u32> live_of(n, HNY_SENT);
+  uint64_t n_live = 0;
+  for (uint32_t s = 0, t = 0; s < src->n && t < n; s++) {
+    while (t < n && b->ids[t] < src->ids[s]) t++;
+    if (t < n && b->ids[t] == src->ids[s] && live[s]) {
+      live_of[t] = s;
+      n_live++;
+    }
+  }
+  HIP_TRY(hipStreamSynchronize(src->stream));
+  DevBuf<u32> d_live_of;
+  HIP_TRY(d_live_of.alloc(n));
+  HIP_TRY(hipMemcpyAsync(d_live_of.p, live_of.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+  RowsTimer ev;
+  if (src->profiling)
+    if (int rc = ev.begin(st)) return rc;
+  if (int rc = recode_rows_from_source(b, src, d_live_of.p, st)) return rc;
+  if (src->profiling) HIP_TRY(hipEventRecord(ev.b, st));
+  UpsertBufs ub;
+  if (int rc = place_upserts(b, u, pipe, ub)) return rc;
+  HIP_TRY(hipStreamSynchronize(st));
+  if (src->profiling) rows_timer_read(b, src, ev, n_live);
   return HNY_OK;
 }
 
@@ -1716,6 +1805,8 @@ static int create_impl(const hny_build_opts *opts, const hny_items *items, const
   *out = nullptr;
   const hny_build_opts &o = *opts;
   hny_builder *const src = inc ? inc->src : nullptr; // resident update: rows and lists come from this builder
+  const hny_update *const upd = inc ? inc->upd : nullptr;
+  if (inc && inc->rows_only) inc = nullptr; // ... or only its rows, for a fresh index
   int rc = check_create_args(o, items, src, f32);
   if (rc) return rc;
 
@@ -1725,7 +1816,7 @@ static int create_impl(const hny_build_opts *opts, const hny_items *items, const
   b->bmax = o.batch_max ? o.batch_max : hny_default_batch_max(items->n);
   b->incremental = inc != nullptr;
   b->load_only = inc && inc->load_only;
-  b->from_update = src != nullptr;
+  b->from_update = src != nullptr && inc != nullptr;
   CreatePlan P{items, inc};
   rc = pick_shape(o.metric, o.dim, b->shape, b->g.n16);
   if (rc) return rc;
@@ -1752,8 +1843,10 @@ static int create_impl(const hny_build_opts *opts, const hny_items *items, const
   IngestPipe pipe;
   const size_t vb = vec_bytes(o.metric, o.dim);
   if (b->n) {
-    if (src)
-      rc = move_state_from_source(b.get(), inc->upd, P.prev, pipe);
+    if (src && inc)
+      rc = move_state_from_source(b.get(), upd, P.prev, pipe);
+    else if (src)
+      rc = recode_state_from_source(b.get(), src, upd, pipe);
     else if (f32)
       rc = upload_rows_f32(b.get(), P, pipe, d_item_slot);
     else if (!inc)
@@ -2788,50 +2881,67 @@ static int check_update_struct(const hny_update *u) {
   return HNY_OK;
 }
 
+// the ids and the upserted rows of `u`, for a successor whose codec is that of `metric`
+static int check_update_rows(const hny_update *u, int metric, uint32_t dim) {
+  if (int rc = check_ascending(u->upsert_ids, u->n_upsert, "upsert_ids")) return rc;
+  if (int rc = check_ascending(u->delete_ids, u->n_delete, "delete_ids")) return rc;
+  const size_t vb = vec_bytes(metric, dim), hb = hdr_bytes(metric);
+  if (u->vectors_are_f32) {
+    if (int rc = check_f32_rows(dim, u->n_upsert, u->vectors, u->stride)) return rc;
+  } else if (u->n_upsert) {
+    if (!u->vectors || !u->headers) return fail(HNY_ERR_INVALID_ARG, "hny_update: null vectors / headers");
+    if (u->stride < vb)
+      return fail(HNY_ERR_INVALID_DIM, "hny_update: stride %zu < %zu codec bytes for dim %u", u->stride, vb, dim);
+    if (u->header_size != hb) return fail(HNY_ERR_INVALID_ARG, "hny_update: header_size %zu, expected %zu", u->header_size, hb);
+  }
+  return HNY_OK;
+}
+// a source must be at rest: finished (or loaded), gaps filled
+static int check_source_at_rest(const hny_builder *src, const char *what) {
+  if (src->pos < src->order.size() || src->in_batch || src->apply_open)
+    return fail(HNY_ERR_INVALID_ARG, "%s: the source builder has batches pending", what);
+  if (src->incremental && !src->load_only && !src->gaps_done)
+    return fail(HNY_ERR_INVALID_ARG, "%s: hny_builder_fill_gaps has not run on the incremental source builder", what);
+  return HNY_OK;
+}
+// items after the update: the source's live items minus delete_ids, plus the upserts
+static std::vector<uint32_t> ids_after_update(const hny_builder *src, const hny_update *u) {
+  const std::vector<uint8_t> live = live_slots(src);
+  std::vector<uint32_t> ids_after, kept;
+  ids_after.reserve((size_t)src->n + u->n_upsert);
+  kept.reserve(src->n);
+  uint64_t d = 0;
+  for (uint32_t s = 0; s < src->n; s++) {
+    if (!live[s]) continue;
+    const uint32_t id = src->ids[s];
+    while (d < u->n_delete && u->delete_ids[d] < id) d++;
+    if (d < u->n_delete && u->delete_ids[d] == id) continue;
+    kept.push_back(id);
+  }
+  std::set_union(kept.begin(), kept.end(), u->upsert_ids, u->upsert_ids + u->n_upsert, std::back_inserter(ids_after));
+  return ids_after;
+}
+// the source's options as the caller gave them (batch_max 0 is resolved from the successor's own item count), on the
+// source's device; a replica of a multi-GPU builder is an ordinary one-GPU source
+static hny_build_opts successor_opts(const hny_builder *src, uint64_t seed) {
+  hny_build_opts o = src->o;
+  o.seed = seed;
+  o.device = src->device;
+  o.n_gpus = 0;
+  o.devices = nullptr;
+  return o;
+}
+
 int hny_builder_create_update(hny_builder *src, const hny_update *u, hny_builder **out) {
   if (!out) return fail(HNY_ERR_INVALID_ARG, "null out");
   *out = nullptr;
   if (int rc = check_update_struct(u)) return rc;
   if (!src) return fail(HNY_ERR_INVALID_ARG, "null source builder");
   // everything below is decided from the arguments and the source's host state, before any device work
-  if (int rc = check_ascending(u->upsert_ids, u->n_upsert, "upsert_ids")) return rc;
-  if (int rc = check_ascending(u->delete_ids, u->n_delete, "delete_ids")) return rc;
-  const hny_build_opts &so = src->o;
-  const size_t vb = vec_bytes(so.metric, so.dim), hb = hdr_bytes(so.metric);
-  if (u->vectors_are_f32) {
-    if (int rc = check_f32_rows(so.dim, u->n_upsert, u->vectors, u->stride)) return rc;
-  } else if (u->n_upsert) {
-    if (!u->vectors || !u->headers) return fail(HNY_ERR_INVALID_ARG, "hny_update: null vectors / headers");
-    if (u->stride < vb)
-      return fail(HNY_ERR_INVALID_DIM, "hny_update: stride %zu < %zu codec bytes for dim %u", u->stride, vb, so.dim);
-    if (u->header_size != hb) return fail(HNY_ERR_INVALID_ARG, "hny_update: header_size %zu, expected %zu", u->header_size, hb);
-  }
-  if (src->pos < src->order.size() || src->in_batch || src->apply_open)
-    return fail(HNY_ERR_INVALID_ARG, "update: the source builder has batches pending");
-  if (src->incremental && !src->load_only && !src->gaps_done)
-    return fail(HNY_ERR_INVALID_ARG, "update: hny_builder_fill_gaps has not run on the incremental source builder");
-  // items after the update: the source's live items minus delete_ids, plus the upserts
-  const std::vector<uint8_t> live = live_slots(src);
-  std::vector<uint32_t> ids_after;
-  ids_after.reserve((size_t)src->n + u->n_upsert);
-  {
-    std::vector<uint32_t> kept;
-    kept.reserve(src->n);
-    uint64_t d = 0;
-    for (uint32_t s = 0; s < src->n; s++) {
-      if (!live[s]) continue;
-      const uint32_t id = src->ids[s];
-      while (d < u->n_delete && u->delete_ids[d] < id) d++;
-      if (d < u->n_delete && u->delete_ids[d] == id) continue;
-      kept.push_back(id);
-    }
-    std::set_union(kept.begin(), kept.end(), u->upsert_ids, u->upsert_ids + u->n_upsert, std::back_inserter(ids_after));
-  }
-  hny_build_opts o = so; // as the caller gave them: batch_max 0 is resolved from the successor's own item count
-  o.seed = u->seed;
-  o.device = src->device;
-  o.n_gpus = 0; // (a replica of a multi-GPU builder is an ordinary one-GPU source)
-  o.devices = nullptr;
+  if (int rc = check_update_rows(u, src->o.metric, src->o.dim)) return rc;
+  if (int rc = check_source_at_rest(src, "update")) return rc;
+  const std::vector<uint32_t> ids_after = ids_after_update(src, u);
+  const hny_build_opts o = successor_opts(src, u->seed);
   hny_items items{};
   items.n = ids_after.size();
   items.ids = ids_after.data();
@@ -2840,6 +2950,94 @@ int hny_builder_create_update(hny_builder *src, const hny_update *u, hny_builder
   inc.src = src;
   inc.upd = u;
   return create_impl(&o, &items, &inc, out, u->vectors_are_f32 != 0);
+}
+
+// ---- resident change of distance (include/hannoy_amd.h) ----
+int hny_distance_keeps_links(int32_t old_metric, int32_t new_metric) {
+  // "binary quantized " + the old name (writer.rs:359-368): the BQ form of an f32 distance
+  return old_metric >= HNY_COSINE && old_metric <= HNY_MANHATTAN && new_metric == old_metric + HNY_BQ_COSINE;
+}
+// what both entry points decide about (src, new_metric) before any device work
+static int check_change_of_distance(const hny_builder *src, int32_t new_metric, const char *what) {
+  if (!src) return fail(HNY_ERR_INVALID_ARG, "%s: null source builder", what);
+  if (new_metric < 0 || new_metric > HNY_BQ_MANHATTAN)
+    return fail(HNY_ERR_INVALID_ARG, "%s: new_metric %d is no hny_metric", what, new_metric);
+  if (is_binary(src->o.metric))
+    return fail(HNY_ERR_UNSUPPORTED, "%s: the source builder holds bit codes (metric %d): their to_vec is lossy and "
+                "padded to 64 dims, re-encode them on the host", what, src->o.metric);
+  if (new_metric == src->o.metric)
+    return fail(HNY_ERR_INVALID_ARG, "%s: new_metric %d is the source's own (nothing to change: "
+                "hny_builder_create_update)", what, new_metric);
+  return check_source_at_rest(src, what);
+}
+
+int hny_builder_create_changed_distance(hny_builder *src, const hny_change_distance *c, hny_builder **out) {
+  // refusals leave *out untouched
+  if (!c) return fail(HNY_ERR_INVALID_ARG, "null hny_change_distance");
+  if (c->struct_size != sizeof(hny_change_distance))
+    return fail(HNY_ERR_INVALID_ARG, "hny_change_distance.struct_size is %u, this library expects %zu", c->struct_size,
+                sizeof(hny_change_distance));
+  if (!out) return fail(HNY_ERR_INVALID_ARG, "null out");
+  hny_update none{};
+  none.struct_size = (uint32_t)sizeof(hny_update);
+  const hny_update *u = c->update ? c->update : &none;
+  if (int rc = check_update_struct(u)) return rc;
+  if (int rc = check_change_of_distance(src, c->new_metric, "change of distance")) return rc;
+  if (int rc = check_update_rows(u, c->new_metric, src->o.dim)) return rc;
+  const std::vector<uint32_t> ids_after = ids_after_update(src, u);
+  hny_build_opts o = successor_opts(src, c->seed);
+  o.metric = c->new_metric;
+  hny_items items{};
+  items.n = ids_after.size();
+  items.ids = ids_after.data();
+  items.levels = c->levels;
+  // kept-links pairs: every item is marked updated (writer.rs:396-399) and the old graph is `prev`
+  IncrementalSpec inc{ids_after.data(), ids_after.size(), u->delete_ids, u->n_delete, nullptr};
+  inc.src = src;
+  inc.upd = u;
+  inc.rows_only = !hny_distance_keeps_links(src->o.metric, c->new_metric);
+  hny_builder *succ = nullptr;
+  int rc = create_impl(&o, &items, &inc, &succ, u->vectors_are_f32 != 0);
+  if (!rc) *out = succ;
+  return rc;
+}
+
+int hny_builder_recode_items(hny_builder *src, int32_t new_metric, void *out_codes, void *out_headers) {
+  if (int rc = check_change_of_distance(src, new_metric, "recode_items")) return rc;
+  std::vector<u32> rows; // the live items' slots: ascending like their ids
+  {
+    const std::vector<uint8_t> live = live_slots(src);
+    for (uint32_t s = 0; s < src->n; s++)
+      if (live[s]) rows.push_back(s);
+  }
+  if (!rows.empty() && (!out_codes || !out_headers)) return fail(HNY_ERR_INVALID_ARG, "recode_items: null output");
+  if (rows.empty()) return HNY_OK;
+  HIP_TRY(hipSetDevice(src->device));
+  hipStream_t st = src->stream;
+  IngestArgs a{};
+  ingest_codec(a, new_metric, src->o.dim);
+  a.src = (const float *)src->d_rows.p;
+  a.src_stride = src->g.row_stride / 4u;
+  a.row_stride = (a.vb + 15u) / 16u * 16u; // (the kernel walks a row in these units)
+  const size_t chunk = std::min<size_t>(rows.size(), std::max<size_t>(1, ((size_t)64 << 20) / a.vb));
+  DevBuf<u32> d_rows_of;
+  DevBuf<unsigned char> d_codes, d_hdrs;
+  HIP_TRY(d_rows_of.alloc(rows.size()));
+  HIP_TRY(d_codes.alloc(chunk * a.vb));
+  HIP_TRY(d_hdrs.alloc(chunk * a.hb));
+  HIP_TRY(hipMemcpyAsync(d_rows_of.p, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, st));
+  a.out_codes = d_codes.p;
+  a.out_hdrs = d_hdrs.p;
+  for (size_t r0 = 0; r0 < rows.size(); r0 += chunk) {
+    const size_t cnt = std::min(chunk, rows.size() - r0);
+    a.src_of = d_rows_of.p + r0;
+    a.cnt = (u32)cnt;
+    HIP_TRY(hnyk_ingest(a, st));
+    HIP_TRY(hipMemcpyAsync((unsigned char *)out_codes + r0 * a.vb, d_codes.p, cnt * a.vb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync((unsigned char *)out_headers + r0 * a.hb, d_hdrs.p, cnt * a.hb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st)); // (the two buffers are filled again)
+  }
+  return HNY_OK;
 }
 
 void hny_graph_delta_free(hny_graph_delta *d) {

@@ -450,6 +450,10 @@ enum { ING_F32 = 0, ING_F32_NORM = 1, ING_BINARY = 2, ING_BQ = 3 };
 struct IngestArgs {
   const float *src;         // [cnt] rows, src_stride floats apart
   u32 src_stride, dim, cnt;
+  // gathered source (k_ingest<.., GATHER>): row i is read at src + src_of[i] * src_stride, `src`
+  // being a builder's f32 rows (16-byte aligned, zero padded to 16 bytes); HNY_SENT = no source row: a zero row and
+  // a zero norm.  NULL = row i of a staged chunk
+  const u32 *src_of;
   int codec;                // ING_*: f32 copy, f32 copy + Cosine norm (x86 order), Binary / BinaryQuantized ballot
   float hdr_const;          // header of the bit codecs: sqrt(padded dims) for BQ Cosine, else 0
   const u32 *slots;         // destination slot of row i; NULL = slot_base + i

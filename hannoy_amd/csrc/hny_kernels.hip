@@ -4317,11 +4317,18 @@ __device__ __forceinline__ bool quantize_bit(u32 bits, int binary_codec) {
 // the same registers feed the copy (or the ballot), the Cosine norm and the optional packed outputs.
 // V4: 16-byte loads (row stride a multiple of 16 bytes) and 16-byte stores of the packed codes (dim a multiple
 // of 4); rows of the builder's array are 16-byte aligned and padded, so they always take 16-byte stores.
+// GATHER: the source is a builder's f32 row array instead of a staged chunk — row i is read at
+// src_of[i] * src_stride, in whole 16-byte units (those rows are padded to 16 bytes with zeros), and a row without
+// a source (HNY_SENT) becomes a zero row with a zero norm, as in k_move_rows.
 // ---------------------------------------------------------------------------------------------
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 // four consecutive floats x[e0 .. e0+3] of a row, zero where e >= dim
-template <bool V4>
+template <bool V4, bool GATHER = false>
 __device__ __forceinline__ f32x4 ingest_load4(const float *x, u32 e0, u32 dim) {
+  if (GATHER) { // a builder's row: the unit that holds element e0 < dim is there whole, zero beyond dim
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    return e0 < dim ? __builtin_nontemporal_load((const f32x4 *)(x + e0)) : z;
+  }
   if (V4 && e0 + 4u <= dim) return __builtin_nontemporal_load((const f32x4 *)(x + e0));
   f32x4 v;
   v.x = e0 < dim ? __builtin_nontemporal_load(x + e0) : 0.f;
@@ -4346,7 +4353,7 @@ __device__ __forceinline__ float pick4(f32x4 v, u32 c) { return c == 0u ? v.x : 
 // f32 codecs: eight lanes per row.  Lane o of the eight holds elements 4o .. 4o+3 of every 32-float block, i.e.
 // partials 4o .. 4o+3 of the reference's 32 (AVX2) accumulators: each accumulator's chain runs over the blocks in
 // one lane, in the reference's order, and eight lanes read 128 contiguous bytes per load.
-template <bool V4>
+template <bool V4, bool GATHER = false>
 __global__ __launch_bounds__(256) void k_ingest_f32(IngestArgs a) {
   const u32 ln = threadIdx.x & 63u, o = ln & 7u, obase = ln & ~7u;
   const u32 dim = a.dim, m = dim & ~31u, pad_dim = a.row_stride / 4u;
@@ -4355,7 +4362,9 @@ __global__ __launch_bounds__(256) void k_ingest_f32(IngestArgs a) {
   for (u64 r0 = wave0; r0 < a.cnt; r0 += step) { // wave-uniform: the shuffles below need every lane
     const u64 row = r0 + (ln >> 3);
     const bool valid = row < a.cnt;
-    const float *x = a.src + (valid ? row : 0) * a.src_stride;
+    const u32 srow = GATHER && valid ? a.src_of[row] : 0u;
+    const bool live = GATHER ? valid && srow != HNY_SENT : valid; // the row has a source
+    const float *x = a.src + (GATHER ? (u64)(live ? srow : 0u) : (valid ? row : 0)) * a.src_stride;
     const u32 slot = !valid ? 0u : a.slots ? a.slots[row] : a.slot_base + (u32)row;
     float *drow = a.rows ? (float *)(a.rows + (u64)slot * a.row_stride) : nullptr;
     float *prow = a.out_codes ? (float *)(a.out_codes + row * a.vb) : nullptr;
@@ -4364,7 +4373,7 @@ __global__ __launch_bounds__(256) void k_ingest_f32(IngestArgs a) {
     for (u32 i = 0; i < m; i += 32u) {
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
       if (valid) {
-        v = ingest_load4<V4>(x, i + 4u * o, dim);
+        if (live) v = ingest_load4<V4, GATHER>(x, i + 4u * o, dim);
         if (drow) ingest_store4<true>(drow, i + 4u * o, pad_dim, v);
         if (prow) ingest_store4<V4>(prow, i + 4u * o, dim, v);
       }
@@ -4378,7 +4387,7 @@ __global__ __launch_bounds__(256) void k_ingest_f32(IngestArgs a) {
     // the last, partial block [m, dim) with the zero padding of the destination row behind it
     f32x4 t = {0.f, 0.f, 0.f, 0.f};
     if (valid && m < pad_dim) {
-      t = ingest_load4<V4>(x, m + 4u * o, dim);
+      if (live) t = ingest_load4<V4, GATHER>(x, m + 4u * o, dim);
       if (drow) ingest_store4<true>(drow, m + 4u * o, pad_dim, t);
       if (prow) ingest_store4<V4>(prow, m + 4u * o, dim, t);
     }
@@ -4423,7 +4432,7 @@ __device__ __forceinline__ u64 spread16x4(u64 x) {
 
 // bit codecs: sixteen lanes per row, four floats per lane = one 64-dim word per load; the four ballots of the
 // wave hold bit 4l+c of the word at position l of the row's 16-bit field, spread16x4 puts them in place.
-template <bool V4>
+template <bool V4, bool GATHER = false>
 __global__ __launch_bounds__(256) void k_ingest_bits(IngestArgs a) {
   const u32 ln = threadIdx.x & 63u, l = ln & 15u, grp = ln >> 4;
   const u32 dim = a.dim, row_words = a.row_stride / 8u, words = a.vb / 8u;
@@ -4432,18 +4441,20 @@ __global__ __launch_bounds__(256) void k_ingest_bits(IngestArgs a) {
   for (u64 r0 = wave0; r0 < a.cnt; r0 += step) { // wave-uniform: ballots
     const u64 row = r0 + grp;
     const bool valid = row < a.cnt;
-    const float *x = a.src + (valid ? row : 0) * a.src_stride;
+    const u32 srow = GATHER && valid ? a.src_of[row] : 0u;
+    const bool live = GATHER ? valid && srow != HNY_SENT : valid; // the row has a source
+    const float *x = a.src + (GATHER ? (u64)(live ? srow : 0u) : (valid ? row : 0)) * a.src_stride;
     const u32 slot = !valid ? 0u : a.slots ? a.slots[row] : a.slot_base + (u32)row;
     u64 *drow = a.rows ? (u64 *)(a.rows + (u64)slot * a.row_stride) : nullptr;
     u64 *prow = a.out_codes ? (u64 *)(a.out_codes + row * a.vb) : nullptr;
     for (u32 w = 0; w < row_words; w++) { // the words of the zero padding included
       const u32 e0 = w * 64u + 4u * l;
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (valid && e0 < dim) v = ingest_load4<V4>(x, e0, dim);
-      const u64 b0 = ballot(valid && e0 < dim && quantize_bit(__float_as_uint(v.x), binary_codec));
-      const u64 b1 = ballot(valid && e0 + 1u < dim && quantize_bit(__float_as_uint(v.y), binary_codec));
-      const u64 b2 = ballot(valid && e0 + 2u < dim && quantize_bit(__float_as_uint(v.z), binary_codec));
-      const u64 b3 = ballot(valid && e0 + 3u < dim && quantize_bit(__float_as_uint(v.w), binary_codec));
+      if (live && e0 < dim) v = ingest_load4<V4, GATHER>(x, e0, dim);
+      const u64 b0 = ballot(live && e0 < dim && quantize_bit(__float_as_uint(v.x), binary_codec));
+      const u64 b1 = ballot(live && e0 + 1u < dim && quantize_bit(__float_as_uint(v.y), binary_codec));
+      const u64 b2 = ballot(live && e0 + 2u < dim && quantize_bit(__float_as_uint(v.z), binary_codec));
+      const u64 b3 = ballot(live && e0 + 3u < dim && quantize_bit(__float_as_uint(v.w), binary_codec));
       const u32 sh = 16u * grp;
       const u64 word = spread16x4((b0 >> sh) & 0xFFFFull) | (spread16x4((b1 >> sh) & 0xFFFFull) << 1) |
                        (spread16x4((b2 >> sh) & 0xFFFFull) << 2) | (spread16x4((b3 >> sh) & 0xFFFFull) << 3);
@@ -4453,10 +4464,11 @@ __global__ __launch_bounds__(256) void k_ingest_bits(IngestArgs a) {
       }
     }
     if (valid && l == 0u) {
-      if (a.norms) a.norms[slot] = a.hdr_const;
+      const float hdr = live ? a.hdr_const : 0.0f;
+      if (a.norms) a.norms[slot] = hdr;
       if (a.out_hdrs) {
         if (a.hb == 8u) *(u64 *)(a.out_hdrs + row * 8u) = 0ull; // hamming.rs:40-42 idx = 0usize
-        else *(float *)(a.out_hdrs + row * 4u) = a.hdr_const;
+        else *(float *)(a.out_hdrs + row * 4u) = hdr;
       }
     }
   }
@@ -4784,10 +4796,17 @@ hipError_t hnyk_ingest(const IngestArgs &a, hipStream_t st) {
   if (!a.cnt) return hipSuccess;
   const bool bits = a.codec == ING_BINARY || a.codec == ING_BQ;
   // 16-byte accesses need 16-byte aligned rows on both sides (the builder's rows always are)
-  const bool v4 = a.src_stride % 4u == 0 && ((uintptr_t)a.src & 15u) == 0 &&
-                  (bits || !a.out_codes || (a.dim % 4u == 0 && ((uintptr_t)a.out_codes & 15u) == 0));
+  const bool src16 = a.src_stride % 4u == 0 && ((uintptr_t)a.src & 15u) == 0;
+  const bool v4 = src16 && (bits || !a.out_codes || (a.dim % 4u == 0 && ((uintptr_t)a.out_codes & 15u) == 0));
   const u32 rows_per_block = bits ? 16u : 32u;
   const unsigned grid = (unsigned)std::min<u64>(((u64)a.cnt + rows_per_block - 1) / rows_per_block, 8192);
+  if (a.src_of) { // gathered source: a builder's rows, whole 16-byte units
+    if (!src16 || a.src_stride * 4u < (a.dim + 3u) / 4u * 16u) return hipErrorInvalidValue;
+    if (bits) hipLaunchKernelGGL((k_ingest_bits<true, true>), dim3(grid), dim3(256), 0, st, a);
+    else if (v4) hipLaunchKernelGGL((k_ingest_f32<true, true>), dim3(grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_ingest_f32<false, true>), dim3(grid), dim3(256), 0, st, a);
+    return hipGetLastError();
+  }
   if (bits) {
     if (v4) hipLaunchKernelGGL(k_ingest_bits<true>, dim3(grid), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(k_ingest_bits<false>, dim3(grid), dim3(256), 0, st, a);

@@ -517,6 +517,51 @@ struct hny_graph_delta {
 int hny_builder_finish_delta(hny_builder *b, hny_graph_delta **out);
 void hny_graph_delta_free(hny_graph_delta *d);
 
+/* ---- resident change of distance: Writer::prepare_changing_distance followed by Writer::build
+ * (src/writer.rs:358-410, 521-603) on an index whose f32-codec builder is still alive.  The builder holds the
+ * original f32 rows in HBM: the successor's rows are encoded from them for the new distance on the device
+ * (k_ingest with a gathered source), nothing is decoded, re-encoded or uploaded by the host. ---- */
+
+/* 1 when Writer::prepare_changing_distance keeps links and Metadata (writer.rs:359-368: the new distance's name is
+ * "binary quantized " + the old one's): COSINE->BQ_COSINE, EUCLIDEAN->BQ_EUCLIDEAN, MANHATTAN->BQ_MANHATTAN; else 0 */
+int hny_distance_keeps_links(int32_t old_metric, int32_t new_metric);
+
+typedef struct {
+  uint32_t struct_size;     /* sizeof as compiled, else HNY_ERR_INVALID_ARG; not part of hny_abi_sizes */
+  int32_t new_metric;
+  const uint8_t *levels;    /* optional: one per item that exists AFTER the change, ascending id */
+  uint64_t seed;
+  const hny_update *update; /* optional: upserts / deletes applied in the same build; upserted rows are f32 or
+                             * bytes of the NEW codec; its levels / seed fields are not read */
+} hny_change_distance;
+
+/* Definition.  items_new = src's live items minus the deletes with the upserts added / replaced, every surviving
+ * source row encoded as hny_encode_vectors(new_metric, dim, ..) encodes its stored f32 values; opts_new = src's
+ * options as the caller gave them with metric = new_metric and seed = c->seed (batch_max 0 is resolved from the
+ * successor's item count).
+ *   Kept-links pairs (hny_distance_keeps_links == 1): run to the end like a builder from
+ *     hny_builder_create_incremental (batches, fill_gaps, finish), the successor yields byte for byte what
+ *     hny_build_incremental(opts_new, items_new, to_insert = every id of items_new, to_delete = delete_ids, prev =
+ *     src's exported graph) yields: records, entry points, max_level, n_links_added, n_evals_walk.  The lists move
+ *     through k_move_lists; hny_builder_finish_delta works as on any successor.
+ *   Every other pair: run like a builder from hny_builder_create, the successor yields byte for byte what
+ *     hny_build(opts_new, items_new) yields.  No list is moved; hny_builder_finish_delta returns
+ *     HNY_ERR_INVALID_ARG (the store dropped every Links record: the full graph is the delta).
+ * hny_builder_export_items(successor) equals hny_encode_vectors' bytes.  src stays intact until the caller destroys
+ * it; both builders are resident.  The successor is a one-GPU builder on src's device.
+ *
+ * src: an f32 codec (Cosine, Euclidean, Manhattan), finished or loaded as for hny_builder_create_update.
+ * Refused before any device work, nothing created, *out untouched: null arguments, a wrong struct_size of either
+ * struct, new_metric outside the enum or equal to src's (the reference does nothing then: hny_builder_create_update),
+ * batches pending or an incremental source before fill_gaps, update ids not strictly ascending
+ * (HNY_ERR_INVALID_ARG); a bit-codec source, whose to_vec is lossy (HNY_ERR_UNSUPPORTED); an upsert stride too
+ * small for the new codec or for f32 (HNY_ERR_INVALID_DIM). */
+int hny_builder_create_changed_distance(hny_builder *src, const hny_change_distance *c, hny_builder **out);
+/* The Item-record payloads after the change: [n_live][hny_vector_bytes(new_metric, dim)] codes and
+ * [n_live][hny_header_bytes(new_metric)] headers of src's live items in ascending id order, equal to
+ * hny_encode_vectors on their f32 values.  Only the new codes cross the bus.  Sources and refusals as above. */
+int hny_builder_recode_items(hny_builder *src, int32_t new_metric, void *out_codes, void *out_headers);
+
 /* Diagnostic: runs the distance kernels' cross-lane primitives (DPP moves, v_permlane16/32_swap) next
  * to the generic __shfl_xor on one wave of `device` (-1 = current).  HNY_OK when every lane agrees;
  * HNY_ERR_DEVICE otherwise, with bit (5 * log2(offset) + check) of mismatch64[lane] set (may be
