@@ -41,6 +41,8 @@ EXPORTED = [
     "hny_builder_nns_filtered", "hny_builder_nns_filtered_f32",
     "hny_builder_exact_knn_filtered", "hny_builder_exact_knn_filtered_f32", "hny_builder_exact_rows_read",
     "hny_distance_keeps_links", "hny_builder_create_changed_distance", "hny_builder_recode_items",
+    "hny_builder_nns_bitsets", "hny_builder_nns_bitsets_f32",
+    "hny_builder_exact_knn_bitsets", "hny_builder_exact_knn_bitsets_f32",
 ]
 ERR_IO = -9
 NNS_NONE = 0xFFFFFFFF  # by_item: the reference returns None
@@ -82,6 +84,52 @@ class QueryFilters(C.Structure):
         s.n_filters, s.offsets, s.filter_of = len(arrs), _p(offsets).value, _p(fo).value
         s.ids = _p(ids).value if len(ids) else None
         return s, (offsets, ids, fo)
+
+
+def pack_id_bits(masks, n_bits=None):
+    """filters as bitsets over item ids: a bool array [n_filters, n_bits] packed little-endian (item id i is bit
+    i & 31 of word i >> 5), or an already packed uint32 array [n_filters, words] with `n_bits`.  Returns (uint32
+    [n_filters, words], n_bits)"""
+    m = np.asarray(masks)
+    if m.ndim != 2:
+        raise ValueError("filter bitsets are a 2-d array, one row per filter")
+    if m.dtype == np.bool_:
+        if n_bits is not None and int(n_bits) != m.shape[1]:
+            raise ValueError(f"n_bits {n_bits} for bool masks of {m.shape[1]} columns")
+        nb = m.shape[1]
+        if nb % 32:
+            m = np.pad(m, ((0, 0), (0, -nb % 32)))
+        bits = np.packbits(m, axis=1, bitorder="little").view("<u4") if nb else np.zeros((len(m), 0), np.uint32)
+        return np.ascontiguousarray(bits, np.uint32), nb
+    if m.dtype != np.uint32:
+        raise ValueError(f"filter bitsets are bool or packed uint32, not {m.dtype}")
+    if n_bits is None:
+        raise ValueError("packed filter bitsets need n_bits")
+    return np.ascontiguousarray(m), int(n_bits)
+
+
+class QueryBitsets(C.Structure):
+    """hny_query_bitsets; struct_size is the guard (the struct is not part of hny_abi_sizes)"""
+    _fields_ = [("struct_size", C.c_uint32), ("n_filters", C.c_uint32), ("n_bits", C.c_uint64),
+                ("stride_words", C.c_uint64), ("bits", C.c_void_p), ("filter_of", C.c_void_p)]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_size = C.sizeof(QueryBitsets)
+
+    @classmethod
+    def pack(cls, bits, n_bits, filter_of):
+        """`bits`: uint32 [n_filters, words] (rows may be longer than ceil(n_bits / 32): the row length is the
+        stride); `filter_of`: one int per query, -1 or NNS_FILTER_NONE = none.  Returns (struct, arrays the struct
+        points into), filter_of last as in QueryFilters.pack"""
+        bits, n_bits = pack_id_bits(bits, n_bits)
+        fo = np.asarray(filter_of, np.int64).ravel()
+        fo = np.ascontiguousarray(np.where(fo < 0, NNS_FILTER_NONE, fo), np.uint32)
+        s = cls()
+        s.n_filters, s.n_bits, s.stride_words = bits.shape[0], n_bits, bits.shape[1]
+        s.bits = _p(bits).value if bits.size else None
+        s.filter_of = _p(fo).value
+        return s, (bits, n_bits, fo)
 
 
 class HannoyError(RuntimeError):
@@ -324,6 +372,11 @@ def load_library():
     L.hny_builder_exact_knn_filtered.argtypes = L.hny_builder_nns_filtered.argtypes
     L.hny_builder_exact_knn_filtered_f32.restype = C.c_int
     L.hny_builder_exact_knn_filtered_f32.argtypes = L.hny_builder_nns_filtered_f32.argtypes
+    for name in ("hny_builder_nns_bitsets", "hny_builder_exact_knn_bitsets"):
+        fn, f32 = getattr(L, name), getattr(L, name + "_f32")
+        fn.restype = f32.restype = C.c_int
+        fn.argtypes = [vp, C.POINTER(QueryOpts), C.POINTER(QueryBitsets)] + L.hny_builder_nns_filtered.argtypes[3:]
+        f32.argtypes = [vp, C.POINTER(QueryOpts), C.POINTER(QueryBitsets)] + L.hny_builder_nns_filtered_f32.argtypes[3:]
     L.hny_builder_exact_rows_read.restype = C.c_uint64
     L.hny_builder_exact_rows_read.argtypes = [vp]
     L.hny_builder_create_update.restype = C.c_int
@@ -1271,6 +1324,33 @@ class Builder:
         qf = QueryFilters.pack(filters, filter_of)
         return self._search("hny_builder_exact_knn_filtered", opts,
                             _query_source(query_items, qf32, qcodes, qheaders), qf32 is not None, qf)
+
+    def nns_bitsets_f32(self, queries, bits, n_bits, filter_of, **kw):
+        """nns_bitsets(by_vector) with f32 queries, encoded on the device"""
+        return self.nns_bitsets(bits, n_bits, filter_of, qf32=_f32_rows(queries), **kw)
+
+    def nns_bitsets(self, bits, n_bits, filter_of, qcodes=None, qheaders=None, k=10, ef_search=100, query_items=None,
+                    linear_below=1000, linear_below_ratio=1.0, cancel=None, qf32=None):
+        """hny_builder_nns_bitsets: nns_filtered with the filters as bitsets over item ids, `bits` a uint32
+        [n_filters, words] array (np.packbits(mask, bitorder="little").view("<u4")) that covers ids 0 .. n_bits-1.
+        Equal to nns_filtered on the set bits of each filter."""
+        opts = _query_opts(k, ef_search, linear_below, linear_below_ratio, cancel=cancel)
+        qb = QueryBitsets.pack(bits, n_bits, filter_of)
+        return self._search("hny_builder_nns_bitsets", opts, _query_source(query_items, qf32, qcodes, qheaders),
+                            qf32 is not None, qb)
+
+    def exact_knn_bitsets_f32(self, queries, bits, n_bits, filter_of, **kw):
+        """exact_knn_bitsets(by_vector) with f32 queries, encoded on the device"""
+        return self.exact_knn_bitsets(bits, n_bits, filter_of, qf32=_f32_rows(queries), **kw)
+
+    def exact_knn_bitsets(self, bits, n_bits, filter_of, qcodes=None, qheaders=None, k=10, query_items=None,
+                          cancel=None, qf32=None):
+        """hny_builder_exact_knn_bitsets: exact_knn_filtered with the filters as bitsets over item ids, `bits`,
+        `n_bits` and `filter_of` as in nns_bitsets.  Equal to exact_knn_filtered on the set bits of each filter."""
+        opts = _query_opts(k, cancel=cancel)
+        qb = QueryBitsets.pack(bits, n_bits, filter_of)
+        return self._search("hny_builder_exact_knn_bitsets", opts,
+                            _query_source(query_items, qf32, qcodes, qheaders), qf32 is not None, qb)
 
     def exact_rows_read(self):
         """(tile, row) loads of the dense scan in the last exact_knn_filtered call on this builder; 0 if none ran"""

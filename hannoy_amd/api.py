@@ -594,6 +594,7 @@ class QueryBuilder:
         self._linear_below, self._ratio = 1000, 1.0     # reader.rs:28, 31
         self._exact = False
         self._per_query = None
+        self._bitsets = None
 
     def ef_search(self, ef):
         self._ef = int(ef)
@@ -611,12 +612,35 @@ class QueryBuilder:
         self._per_query = list(filters)
         return self
 
+    def candidates_bitsets(self, masks, filter_of=None, n_bits=None):
+        """one `.candidates()` per query of by_vectors / by_items with the filters as bitsets over item ids
+        (hny_builder_nns_bitsets, with .exact() hny_builder_exact_knn_bitsets): `masks` is a bool array
+        [n_filters, n_bits], bit i = item id i is a candidate, or the same packed little-endian into uint32 words
+        with `n_bits=`.  `filter_of[i]` is the filter of query i, -1 for none; None means one filter per query, in
+        order.  Equal to candidates_per_query on the set bits of each filter"""
+        self._bitsets = (masks, filter_of, n_bits)
+        return self
+
+    def _id_bits(self, nq):
+        """(bits, n_bits, filter_of) of candidates_bitsets for nq queries"""
+        if self._candidates is not None or self._per_query is not None:
+            raise ValueError("candidates_bitsets does not go with candidates() or candidates_per_query()")
+        masks, filter_of, n_bits = self._bitsets
+        bits, n_bits = capi.pack_id_bits(masks, n_bits)
+        if filter_of is None:
+            if len(bits) != nq:
+                raise ValueError(f"candidates_bitsets has {len(bits)} filters for {nq} queries")
+            filter_of = np.arange(nq)
+        if len(filter_of) != nq:
+            raise ValueError(f"filter_of has {len(filter_of)} entries for {nq} queries")
+        return bits, n_bits, filter_of
+
     def _filters(self, nq):
         """the distinct filters (by object identity) and every query's index among them, -1 = none"""
         if len(self._per_query) != nq:
             raise ValueError(f"candidates_per_query has {len(self._per_query)} entries for {nq} queries")
-        if self._candidates is not None:
-            raise ValueError("candidates_per_query does not go with candidates()")
+        if self._candidates is not None or self._bitsets is not None:
+            raise ValueError("candidates_per_query does not go with candidates() or candidates_bitsets()")
         index, filters, filter_of = {}, [], np.full(nq, -1, np.int64)
         for i, c in enumerate(self._per_query):
             if c is None:
@@ -655,6 +679,11 @@ class QueryBuilder:
         q = np.ascontiguousarray(vectors, np.float32)
         if q.ndim != 2 or q.shape[1] != r.dimensions:
             raise InvalidVecDimension(f"expected {r.dimensions}, received {q.shape[-1]}")
+        if self._bitsets is not None:
+            bits, n_bits, filter_of = self._id_bits(len(q))
+            if self._exact:
+                return r._b.exact_knn_bitsets_f32(q, bits, n_bits, filter_of, k=self.count, cancel=cancel)
+            return r._b.nns_bitsets_f32(q, bits, n_bits, filter_of, cancel=cancel, **self._kw_filtered())
         if self._per_query is not None:
             filters, filter_of = self._filters(len(q))
             if self._exact:
@@ -666,6 +695,14 @@ class QueryBuilder:
 
     def by_items(self, items, cancel=None):
         """batched by_item; counts == capi.NNS_NONE where the reference returns None"""
+        if self._bitsets is not None:
+            items = np.ascontiguousarray(items, np.uint32)
+            bits, n_bits, filter_of = self._id_bits(len(items))
+            if self._exact:
+                return self.reader._b.exact_knn_bitsets(bits, n_bits, filter_of, query_items=items, k=self.count,
+                                                        cancel=cancel)
+            return self.reader._b.nns_bitsets(bits, n_bits, filter_of, query_items=items, cancel=cancel,
+                                              **self._kw_filtered())
         if self._per_query is not None:
             items = np.ascontiguousarray(items, np.uint32)
             filters, filter_of = self._filters(len(items))

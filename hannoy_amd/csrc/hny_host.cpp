@@ -424,6 +424,11 @@ struct hny_builder {
   bool profiling = false;
   uint64_t n_walk_dispatch = 0; // k_walk launches since the last reset
   uint64_t exact_rows_read = 0; // hny_builder_exact_rows_read: the last hny_builder_exact_knn_filtered call's
+  // filters as bitsets over item ids (FilterRounds::build_from_id_bits), made by the first such call:
+  // the item id of every slot (none where ids are 0 .. n-1) and the live slots as a bitset.  ids and deleted are fixed
+  // at creation (hny_builder_reset empties the graph and keeps both; an update makes a successor, a builder of its
+  // own), so the two live until hny_builder_destroy and nothing ever has to refresh them
+  DevBuf<u32> d_item_ids, d_live_bits;
   // successor builders whose source was profiling: device time (HIP events) and bytes read + written of k_move_rows
   double t_move_rows_s = 0;
   uint64_t move_rows_bytes = 0;
@@ -3369,8 +3374,44 @@ static int check_candidates(const hny_query_opts *qo) {
   const bool missing = qo->has_candidates && qo->n_candidates && !qo->candidates;
   return missing ? fail(HNY_ERR_INVALID_ARG, "candidates missing") : HNY_OK;
 }
-// hny_query_filters of the calls with a filter per query; the candidates are there and not in the opts
-static int check_filters(const hny_query_opts *qo, const hny_query_filters *fl, uint64_t nq) {
+// Where the filters of a call with a filter per query come from: id lists (hny_query_filters) or bitsets over item ids
+// (hny_query_bitsets).  The drivers read n_filters and filter_of; FilterRounds::build the rest
+struct FilterSource {
+  const hny_query_filters *lists = nullptr;
+  const hny_query_bitsets *id_bits = nullptr;
+  uint32_t n_filters = 0;
+  const uint32_t *filter_of = nullptr;
+  FilterSource(const hny_query_filters *fl) : lists(fl) {
+    if (fl) n_filters = fl->n_filters, filter_of = fl->filter_of;
+  }
+  FilterSource(const hny_query_bitsets *fl) : id_bits(fl) {
+    if (fl) n_filters = fl->n_filters, filter_of = fl->filter_of;
+  }
+};
+// hny_query_bitsets: check_filters' order, the bitsets' own conditions in the place of the offsets'
+static int check_id_bits(const hny_query_opts *qo, const hny_query_bitsets *fl, uint64_t nq) {
+  if (fl->struct_size != sizeof(hny_query_bitsets))
+    return fail(HNY_ERR_INVALID_ARG, "hny_query_bitsets.struct_size %u: this library has %zu", fl->struct_size,
+                sizeof(hny_query_bitsets));
+  if (qo->has_candidates)
+    return fail(HNY_ERR_INVALID_ARG, "opts->has_candidates must be 0: the candidates are in hny_query_bitsets");
+  if (nq && !fl->filter_of) return fail(HNY_ERR_INVALID_ARG, "filter_of missing");
+  if (fl->n_bits > (uint64_t)1 << 32)
+    return fail(HNY_ERR_INVALID_ARG, "n_bits %llu: item ids have 32 bits", (unsigned long long)fl->n_bits);
+  if (fl->stride_words < (fl->n_bits + 31) / 32)
+    return fail(HNY_ERR_INVALID_ARG, "stride_words %llu: %llu bits take %llu words", (unsigned long long)fl->stride_words,
+                (unsigned long long)fl->n_bits, (unsigned long long)((fl->n_bits + 31) / 32));
+  if (fl->n_filters && fl->n_bits && !fl->bits) return fail(HNY_ERR_INVALID_ARG, "filter bits missing");
+  for (uint64_t i = 0; i < nq; i++)
+    if (fl->filter_of[i] != HNY_FILTER_NONE && fl->filter_of[i] >= fl->n_filters)
+      return fail(HNY_ERR_INVALID_ARG, "query %llu: filter %u of %u", (unsigned long long)i, fl->filter_of[i],
+                  fl->n_filters);
+  return HNY_OK;
+}
+// the filters of the calls with a filter per query; the candidates are there and not in the opts
+static int check_filters(const hny_query_opts *qo, const FilterSource *src, uint64_t nq) {
+  if (src->id_bits) return check_id_bits(qo, src->id_bits, nq);
+  const hny_query_filters *fl = src->lists;
   if (!fl) return fail(HNY_ERR_INVALID_ARG, "no filters");
   if (fl->struct_size != sizeof(hny_query_filters))
     return fail(HNY_ERR_INVALID_ARG, "hny_query_filters.struct_size %u: this library has %zu", fl->struct_size,
@@ -3977,13 +4018,13 @@ static_assert(HNY_FILTER_NONE == HNY_SENT, "a query without a filter sorts with 
 struct FilterRounds {
   hny_builder *b;
   const QuerySet &q;
-  const hny_query_filters *fl;
+  const FilterSource *fl;
   std::vector<u32> used;           // the filters that queries use, ascending
   std::vector<uint64_t> by_filter; // the queries that have one, in filter order
   u32 stride;                      // words per bitset
   size_t per_round, built = (size_t)-1, at = 0; // at: the first query of by_filter that no round has taken yet
   // round `built`: the bitsets on the device and how many live candidates each holds
-  DevBuf<u32> dmasks, dslots, dcount;
+  DevBuf<u32> dmasks, dslots, dcount, dstage; // dstage: id bitsets on their way to becoming masks (§3f-2)
   DevBuf<u64> doff;
   std::vector<u32> count;
   // its gathered filters, once classified: their places in the round, the CSR offsets of their live slots (a filter
@@ -3995,7 +4036,7 @@ struct FilterRounds {
   DevBuf<u64> dcs_off;
 
   static u32 mask_stride(uint32_t n) { return (u32)((((size_t)n + 31) / 32 + 4) & ~(size_t)3); }
-  FilterRounds(hny_builder *b, const QuerySet &q, const hny_query_filters *fl)
+  FilterRounds(hny_builder *b, const QuerySet &q, const FilterSource *fl)
       : b(b), q(q), fl(fl), stride(mask_stride(b->n)),
         per_round((size_t)std::max<uint64_t>(1, filter_mask_budget() / ((uint64_t)stride * 4))) {
     std::vector<unsigned char> seen(fl->n_filters, 0);
@@ -4016,8 +4057,7 @@ struct FilterRounds {
   }
   size_t n_rounds(uint64_t n_items) const { return n_items ? (used.size() + per_round - 1) / per_round : 0; }
 
-  // Round r unless it is the one held.  Ids -> live slots (unknown and deleted ids drop out, duplicates stay), CSR
-  // upload, bits set and counted on the device, the counts back in one copy
+  // Round r unless it is the one held, from either source: bits set and counted on the device
   int build(size_t r) {
     if (built == r) return HNY_OK;
     built = r;
@@ -4025,6 +4065,58 @@ struct FilterRounds {
     dcs.release();
     dcs_off.release();
     const size_t r0 = r * per_round, nf = std::min(used.size() - r0, per_round);
+    return fl->id_bits ? build_from_id_bits(r0, nf) : build_from_lists(r0, nf);
+  }
+  // the counts back in one copy; the round is on the device when this returns
+  int fetch_counts(size_t nf) {
+    count.resize(nf);
+    HIP_TRY(hipMemcpyAsync(count.data(), dcount.p, nf * 4, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return HNY_OK;
+  }
+  // Bitsets over item ids: the rows of the round's filters go up as they are, as many at a time as
+  // the masks' budget holds (one always fits: 2^32 bits are 512 MB), and k_filter_from_id_bits makes each group's
+  // masks from the builder's ids and live bits, which the first call puts on the device.  No id is touched here
+  int build_from_id_bits(size_t r0, size_t nf) {
+    const hny_query_bitsets *ib = fl->id_bits;
+    const bool identity = b->ids[b->n - 1] == b->n - 1; // QuerySet::live_slot's test: slot == id
+    if (!b->d_live_bits.p) {
+      std::vector<u32> live(stride, 0u);
+      for (uint32_t s = 0; s < b->n; s++)
+        if (q.live(s)) live[s >> 5] |= 1u << (s & 31);
+      if (!identity) {
+        HIP_TRY(b->d_item_ids.alloc(b->n));
+        HIP_TRY(hipMemcpy(b->d_item_ids.p, b->ids.data(), (size_t)b->n * 4, hipMemcpyHostToDevice));
+      }
+      HIP_TRY(b->d_live_bits.alloc(stride));
+      HIP_TRY(hipMemcpy(b->d_live_bits.p, live.data(), (size_t)stride * 4, hipMemcpyHostToDevice));
+    }
+    const size_t row_words = (size_t)((ib->n_bits + 31) / 32);
+    const size_t group = (size_t)std::max<uint64_t>(1, filter_mask_budget() / std::max<uint64_t>(row_words * 4, 1));
+    HIP_TRY(dmasks.alloc(nf * stride));
+    HIP_TRY(dcount.alloc(nf));
+    HIP_TRY(dstage.alloc(std::min(group, nf) * row_words));
+    HIP_TRY(hipMemsetAsync(dcount.p, 0, nf * 4, b->stream));
+    for (size_t j0 = 0; j0 < nf; j0 += group) {
+      const size_t j1 = std::min(nf, j0 + group);
+      FilterIdBits a{dmasks.p + j0 * stride, stride, b->n, identity ? nullptr : b->d_item_ids.p, b->d_live_bits.p,
+                     dstage.p, (u32)row_words, ib->n_bits, (u32)(j1 - j0), HNY_SENT};
+      for (size_t j = j0; j < j1; j++) {
+        const u32 f = used[r0 + j];
+        if (f == HNY_SENT) a.live_f = (u32)(j - j0); // add_live's: the last of all, it has no row
+        else if (row_words)
+          HIP_TRY(hipMemcpyAsync(dstage.p + (j - j0) * row_words, ib->bits + (size_t)f * ib->stride_words, row_words * 4,
+                                 hipMemcpyHostToDevice, b->stream));
+      }
+      HIP_TRY(hnyk_filter_from_id_bits(a, b->stream)); // (in stream order: the next group's rows wait for it)
+    }
+    HIP_TRY(hnyk_filter_masks(dmasks.p, stride, nullptr, nullptr, (u32)nf, 0, dcount.p, b->stream)); // counts alone
+    return fetch_counts(nf);
+  }
+  // Id lists: ids -> live slots (unknown and deleted ids drop out, duplicates stay), CSR upload, bits set and counted
+  // on the device, the counts back in one copy
+  int build_from_lists(size_t r0, size_t nf) {
+    const hny_query_filters *fl = this->fl->lists;
     std::vector<u64> off(nf + 1, 0);
     std::vector<u32> slots;
     for (size_t j = 0; j < nf; j++) {
@@ -4047,10 +4139,7 @@ struct FilterRounds {
     if (!slots.empty())
       HIP_TRY(hipMemcpyAsync(dslots.p, slots.data(), slots.size() * 4, hipMemcpyHostToDevice, b->stream));
     HIP_TRY(hnyk_filter_masks(dmasks.p, stride, doff.p, dslots.p, (u32)nf, slots.size(), dcount.p, b->stream));
-    count.resize(nf);
-    HIP_TRY(hipMemcpyAsync(count.data(), dcount.p, nf * 4, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream)); // (`off` and `slots` leave scope)
-    return HNY_OK;
+    return fetch_counts(nf); // (`off` and `slots` leave scope)
   }
   // The round held: a filter with live candidates whose count `gathered` accepts is scanned over its compacted
   // slots.  The round's queries follow in by_filter from where the round before stopped (the last round takes the
@@ -4096,7 +4185,7 @@ struct FilterRounds {
   }
 };
 
-static int nns_filtered_impl(hny_builder *b, const hny_query_opts *qo, const hny_query_filters *fl, uint64_t nq,
+static int nns_filtered_impl(hny_builder *b, const hny_query_opts *qo, const FilterSource *fl, uint64_t nq,
                              const void *qvectors, size_t qstride, const void *qheaders, const uint32_t *query_items,
                              uint32_t *out_ids, float *out_dists, uint32_t *out_counts, bool q_f32) {
   if (int rc = check_search_outputs(b, out_ids, out_dists, out_counts, qo ? qo->k : 0)) return rc;
@@ -4205,7 +4294,8 @@ static int nns_filtered_impl(hny_builder *b, const hny_query_opts *qo, const hny
 int hny_builder_nns_filtered(hny_builder *b, const hny_query_opts *qo, const hny_query_filters *filters, uint64_t nq,
                              const void *qvectors, size_t qstride, const void *qheaders, const uint32_t *query_items,
                              uint32_t *out_ids, float *out_dists, uint32_t *out_counts) {
-  return nns_filtered_impl(b, qo, filters, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists, out_counts,
+  const FilterSource src(filters);
+  return nns_filtered_impl(b, qo, &src, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists, out_counts,
                            false);
 }
 
@@ -4213,7 +4303,25 @@ int hny_builder_nns_filtered_f32(hny_builder *b, const hny_query_opts *qo, const
                                  uint64_t nq, const float *queries, size_t qstride, uint32_t *out_ids,
                                  float *out_dists, uint32_t *out_counts) {
   if (!queries) return fail(HNY_ERR_INVALID_ARG, "no queries");
-  return nns_filtered_impl(b, qo, filters, nq, queries, qstride, nullptr, nullptr, out_ids, out_dists, out_counts, true);
+  const FilterSource src(filters);
+  return nns_filtered_impl(b, qo, &src, nq, queries, qstride, nullptr, nullptr, out_ids, out_dists, out_counts, true);
+}
+
+// the same with the filters as bitsets over item ids: FilterRounds' second source, nothing else
+int hny_builder_nns_bitsets(hny_builder *b, const hny_query_opts *qo, const hny_query_bitsets *filters, uint64_t nq,
+                            const void *qvectors, size_t qstride, const void *qheaders, const uint32_t *query_items,
+                            uint32_t *out_ids, float *out_dists, uint32_t *out_counts) {
+  const FilterSource src(filters);
+  return nns_filtered_impl(b, qo, &src, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists, out_counts,
+                           false);
+}
+
+int hny_builder_nns_bitsets_f32(hny_builder *b, const hny_query_opts *qo, const hny_query_bitsets *filters,
+                                uint64_t nq, const float *queries, size_t qstride, uint32_t *out_ids, float *out_dists,
+                                uint32_t *out_counts) {
+  if (!queries) return fail(HNY_ERR_INVALID_ARG, "no queries");
+  const FilterSource src(filters);
+  return nns_filtered_impl(b, qo, &src, nq, queries, qstride, nullptr, nullptr, out_ids, out_dists, out_counts, true);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -4414,7 +4522,7 @@ static bool exact_skip_env() {
   return !(e && e[0] == '0' && !e[1]);
 }
 
-static int exact_filtered_impl(hny_builder *b, const hny_query_opts *qo, const hny_query_filters *fl, uint64_t nq,
+static int exact_filtered_impl(hny_builder *b, const hny_query_opts *qo, const FilterSource *fl, uint64_t nq,
                                const void *qvectors, size_t qstride, const void *qheaders, const uint32_t *query_items,
                                uint32_t *out_ids, float *out_dists, uint32_t *out_counts, bool q_f32) {
   if (int rc = check_search_outputs(b, out_ids, out_dists, out_counts, qo ? qo->k : 0)) return rc;
@@ -4511,7 +4619,8 @@ int hny_builder_exact_knn_filtered(hny_builder *b, const hny_query_opts *qo, con
                                    uint64_t nq, const void *qvectors, size_t qstride, const void *qheaders,
                                    const uint32_t *query_items, uint32_t *out_ids, float *out_dists,
                                    uint32_t *out_counts) {
-  return exact_filtered_impl(b, qo, filters, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists,
+  const FilterSource src(filters);
+  return exact_filtered_impl(b, qo, &src, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists,
                              out_counts, false);
 }
 
@@ -4519,7 +4628,27 @@ int hny_builder_exact_knn_filtered_f32(hny_builder *b, const hny_query_opts *qo,
                                        uint64_t nq, const float *queries, size_t qstride, uint32_t *out_ids,
                                        float *out_dists, uint32_t *out_counts) {
   if (!queries) return fail(HNY_ERR_INVALID_ARG, "no queries");
-  return exact_filtered_impl(b, qo, filters, nq, queries, qstride, nullptr, nullptr, out_ids, out_dists, out_counts,
+  const FilterSource src(filters);
+  return exact_filtered_impl(b, qo, &src, nq, queries, qstride, nullptr, nullptr, out_ids, out_dists, out_counts,
+                             true);
+}
+
+// the same with the filters as bitsets over item ids
+int hny_builder_exact_knn_bitsets(hny_builder *b, const hny_query_opts *qo, const hny_query_bitsets *filters,
+                                  uint64_t nq, const void *qvectors, size_t qstride, const void *qheaders,
+                                  const uint32_t *query_items, uint32_t *out_ids, float *out_dists,
+                                  uint32_t *out_counts) {
+  const FilterSource src(filters);
+  return exact_filtered_impl(b, qo, &src, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists,
+                             out_counts, false);
+}
+
+int hny_builder_exact_knn_bitsets_f32(hny_builder *b, const hny_query_opts *qo, const hny_query_bitsets *filters,
+                                      uint64_t nq, const float *queries, size_t qstride, uint32_t *out_ids,
+                                      float *out_dists, uint32_t *out_counts) {
+  if (!queries) return fail(HNY_ERR_INVALID_ARG, "no queries");
+  const FilterSource src(filters);
+  return exact_filtered_impl(b, qo, &src, nq, queries, qstride, nullptr, nullptr, out_ids, out_dists, out_counts,
                              true);
 }
 

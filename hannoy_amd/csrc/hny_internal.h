@@ -365,6 +365,22 @@ hipError_t hnyk_filter_masks(u32 *masks, u32 stride, const u64 *off, const u32 *
 // the set slots of the masks lin[0 .. n_lin), ascending, into out[cs_off[f] .. cs_off[f + 1])
 hipError_t hnyk_filter_compact(const u32 *masks, u32 stride, const u32 *lin, u32 n_lin, const u64 *cs_off, u32 *out,
                                hipStream_t st);
+// the same masks from filters given as bitsets over item ids: every word of masks[n_filters][stride]
+// is written, nothing has to be zero before; hnyk_filter_masks with n_slots = 0 counts them afterwards
+struct FilterIdBits {
+  u32 *masks;      // [n_filters][stride] bitsets over slots, the output
+  u32 stride, n;   // words per mask (a multiple of 4, beyond ceil(n / 32)); slots
+  const u32 *ids;  // the item id of each slot, ascending; null = ids are 0 .. n-1
+  const u32 *live; // `stride` words: bit s = slot s holds a live item, zero from n on
+  const u32 *bits; // [n_filters][row_words] bitsets over item ids (the live set's mask has no row)
+  u32 row_words;   // ceil(n_bits / 32)
+  u64 n_bits;      // an id >= n_bits is no candidate
+  u32 n_filters;
+  u32 live_f;      // the mask that is the live set itself (always the last), HNY_SENT = none
+};
+#define HNY_IDBITS_GRID 1024u       // workgroups of k_filter_from_id_bits at most: four runs of 64 slots per trip each
+#define HNY_IDBITS_IDENTITY_GRID 4096u // workgroups of k_filter_from_id_bits_identity at most: 256 mask words per trip each
+hipError_t hnyk_filter_from_id_bits(const FilterIdBits &a, hipStream_t st);
 // exact k-NN (hny_builder_exact_knn): a dense scan of consecutive slots for a tile of queries
 // (k_exact_scores) and the merge of one slab of scores into every query's running top-k list (k_exact_topk)
 #define HNY_EXACT_SLAB 65536u   // slots per slab: the score buffer is query block x slab f32

@@ -3108,6 +3108,63 @@ __global__ __launch_bounds__(256) void k_filter_compact(const u32 *masks, u32 st
     __syncthreads();
   }
 }
+
+// ---------------------------------------------------------------------------------------------
+// The same bitsets over slots from filters given as bitsets over item ids (hny_builder_nns_bitsets, DESIGN.md
+// §3f-2): a.bits holds a.n_filters rows of a.row_words words, item id i is bit (i & 31) of word i >> 5 and an id at or
+// beyond a.n_bits is no candidate.  Mask a.live_f (HNY_SENT: none) has no row: it is the live set.  Every word of
+// every mask is written, zeros past n included, so the masks need no memset; no atomics.
+// ---------------------------------------------------------------------------------------------
+// One wave per run of 64 consecutive slots, the grid strides over the runs (stride is a multiple of 4 words: whole
+// runs).  A lane loads its slot's id and live bit once and tests the id in every filter; the ballot of a filter is
+// two words of its mask, stored by lanes 0 and 1.  Slots ascend with ids: a wave's bit reads fall into few words.
+__global__ __launch_bounds__(256) void k_filter_from_id_bits(FilterIdBits a) {
+  const u32 ln = threadIdx.x & 63u, runs = a.stride / 2u;
+  const u32 waves = gridDim.x * 4u;
+  const u32 rows = a.live_f == HNY_SENT ? a.n_filters : a.n_filters - 1u; // the live set's mask is the last
+  for (u32 r = blockIdx.x * 4u + (threadIdx.x >> 6); r < runs; r += waves) {
+    const u32 s = r * 64u + ln;
+    u32 id = 0;
+    bool live = false;
+    if (s < a.n) {
+      id = a.ids[s];
+      live = (a.live[s >> 5] >> (s & 31u)) & 1u;
+    }
+    const bool covered = live && (u64)id < a.n_bits;
+    const u32 *word = a.bits + (id >> 5);
+    const u32 sh = id & 31u;
+    auto store = [&](u32 f, u64 hit) {
+      if (ln < 2u) a.masks[(size_t)f * a.stride + 2u * r + ln] = ln ? (u32)(hit >> 32) : (u32)hit;
+    };
+    u32 f = 0;
+    for (; f + 4u <= rows; f += 4u) { // four filters' words in flight
+      u32 w[4];
+#pragma unroll
+      for (u32 j = 0; j < 4u; j++) w[j] = covered ? word[(size_t)(f + j) * a.row_words] : 0u;
+#pragma unroll
+      for (u32 j = 0; j < 4u; j++) store(f + j, __ballot((w[j] >> sh) & 1u));
+    }
+    for (; f < rows; f++) store(f, __ballot(covered && ((word[(size_t)f * a.row_words] >> sh) & 1u)));
+    if (rows < a.n_filters) store(rows, __ballot(live));
+  }
+}
+
+// ids 0 .. n-1 (slot == id): one thread per mask word, the filter's word under the live word, the tail cut at
+// min(n, n_bits).  a.live holds a.stride words, zero past n
+__global__ __launch_bounds__(256) void k_filter_from_id_bits_identity(FilterIdBits a) {
+  const u64 last = a.n_bits < (u64)a.n ? a.n_bits : (u64)a.n; // ids below `last` can be candidates
+  const u64 total = (u64)a.n_filters * a.stride;
+  for (u64 i = (u64)blockIdx.x * 256u + threadIdx.x; i < total; i += (u64)gridDim.x * 256u) {
+    const u32 f = (u32)(i / a.stride), w = (u32)(i - (u64)f * a.stride);
+    u32 v = 0;
+    if (f == a.live_f) v = a.live[w];
+    else if ((u64)w * 32u < last) {
+      v = a.bits[(size_t)f * a.row_words + w] & a.live[w];
+      if (last - (u64)w * 32u < 32u) v &= (1u << (u32)(last - (u64)w * 32u)) - 1u;
+    }
+    a.masks[i] = v;
+  }
+}
 #endif // HNY_PART == 0
 
 // ---------------------------------------------------------------------------------------------
@@ -4834,6 +4891,18 @@ hipError_t hnyk_filter_masks(u32 *masks, u32 stride, const u64 *off, const u32 *
   const u32 blocks_per = (stride + HNY_FILTER_COUNT_WORDS - 1) / HNY_FILTER_COUNT_WORDS;
   if ((u64)blocks_per * n_filters > 0x7FFFFFFFull) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_filter_count, dim3(blocks_per * n_filters), dim3(256), 0, st, masks, stride, blocks_per, count);
+  return hipGetLastError();
+}
+hipError_t hnyk_filter_from_id_bits(const FilterIdBits &a, hipStream_t st) {
+  if (!a.n_filters || !a.stride) return hipSuccess;
+  if (a.stride % 4u || (u64)a.stride * 32u <= a.n) return hipErrorInvalidValue; // whole runs, every slot inside
+  if (!a.ids) {
+    const u64 blocks = std::min<u64>(((u64)a.n_filters * a.stride + 255) / 256, HNY_IDBITS_IDENTITY_GRID);
+    hipLaunchKernelGGL(k_filter_from_id_bits_identity, dim3((unsigned)blocks), dim3(256), 0, st, a);
+  } else {
+    const u32 blocks = std::min<u32>((a.stride / 2u + 3u) / 4u, HNY_IDBITS_GRID);
+    hipLaunchKernelGGL(k_filter_from_id_bits, dim3(blocks), dim3(256), 0, st, a);
+  }
   return hipGetLastError();
 }
 hipError_t hnyk_filter_compact(const u32 *masks, u32 stride, const u32 *lin, u32 n_lin, const u64 *cs_off, u32 *out,

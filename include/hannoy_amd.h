@@ -450,6 +450,50 @@ int hny_builder_exact_knn_filtered_f32(hny_builder *b, const hny_query_opts *opt
 /* (tile, row) loads of the dense scan in the last hny_builder_exact_knn_filtered[_f32] call on b; 0 if none ran */
 uint64_t hny_builder_exact_rows_read(const hny_builder *b);
 
+/* ---- the filters of the two calls above as bitsets over item ids: the reference's `.candidates()` takes a
+ * RoaringBitmap over item ids (src/reader.rs:200-203), and a caller that serves filtered requests (a tenant mask, a
+ * facet, an ACL) holds each filter as a bitmap already.  The bitmaps go to the device as they are (n_bits / 8 B per
+ * filter instead of 4 B per candidate) and become the bitsets over slots there (k_filter_from_id_bits, DESIGN.md
+ * 3f-2); the host walks no id.
+ *
+ * Definition: let ids_f be the set bits of filter f below n_bits, ascending.  Each call returns, byte for byte (ids,
+ * distance bits, counts, did_cancel, hny_builder_exact_rows_read), what the _filtered call of the same name returns
+ * for the same queries, opts and filter_of with filter f given as ids_f.  Everything said there carries over: bits of
+ * unknown or deleted ids drop out, an all-zero filter gives 0 hits (HNY_NNS_NONE by item), should_linear_scan per
+ * filter from its own live count, the gather / dense routing of the exact call, strict mode, by_item, cancellation,
+ * the 4 095-hit refusals.  n_bits == 0 is legal: every filter is empty.
+ *
+ * Decided before any device work, nothing is written to the outputs, in the order and with the codes of the _filtered
+ * calls; in the place of their offsets / ids checks: n_bits > 2^32, stride_words < ceil(n_bits / 32), bits == NULL
+ * with n_filters > 0 and n_bits > 0: HNY_ERR_INVALID_ARG.
+ *
+ * Only the filters that some query uses are uploaded, rows of ceil(n_bits / 32) words, at most 1 GB of them on the
+ * device at a time (one always fits).  The first such call on a builder puts its slot -> item id table (none when
+ * the ids are 0 .. n-1) and a bitset of its live slots on the device; they stay until hny_builder_destroy.
+ * hny_query_bitsets carries its own struct_size and is not part of hny_abi_sizes. */
+typedef struct {
+  uint32_t struct_size;      /* sizeof(hny_query_bitsets) as the caller compiled it; anything else: HNY_ERR_INVALID_ARG */
+  uint32_t n_filters;
+  uint64_t n_bits;           /* ids 0 .. n_bits-1 are covered; an id >= n_bits is not a candidate; <= 2^32 */
+  uint64_t stride_words;     /* u32 words from one filter to the next, >= ceil(n_bits / 32) */
+  const uint32_t *bits;      /* [n_filters][stride_words]; item id i is bit (i & 31) of word i >> 5.  Bits at and beyond
+                                n_bits and the words beyond ceil(n_bits / 32) of a row may hold anything */
+  const uint32_t *filter_of; /* as in hny_query_filters: an index < n_filters or HNY_FILTER_NONE */
+} hny_query_bitsets;
+
+int hny_builder_nns_bitsets(hny_builder *b, const hny_query_opts *opts, const hny_query_bitsets *filters,
+                            uint64_t n_queries, const void *qvectors, size_t qstride, const void *qheaders,
+                            const uint32_t *query_items, uint32_t *out_ids, float *out_dists, uint32_t *out_counts);
+int hny_builder_nns_bitsets_f32(hny_builder *b, const hny_query_opts *opts, const hny_query_bitsets *filters,
+                                uint64_t n_queries, const float *queries, size_t qstride,
+                                uint32_t *out_ids, float *out_dists, uint32_t *out_counts);
+int hny_builder_exact_knn_bitsets(hny_builder *b, const hny_query_opts *opts, const hny_query_bitsets *filters,
+                                  uint64_t n_queries, const void *qvectors, size_t qstride, const void *qheaders,
+                                  const uint32_t *query_items, uint32_t *out_ids, float *out_dists, uint32_t *out_counts);
+int hny_builder_exact_knn_bitsets_f32(hny_builder *b, const hny_query_opts *opts, const hny_query_bitsets *filters,
+                                      uint64_t n_queries, const float *queries, size_t qstride,
+                                      uint32_t *out_ids, float *out_dists, uint32_t *out_counts);
+
 /* ---- resident updates: Writer::add_item / del_item followed by Writer::build (src/writer.rs:462-495, 521-603)
  * on an index whose builder is still alive.  A finished builder holds the codec rows, the norms and the finalised
  * lists of every live item in HBM; the successor takes them from there, device to device (k_move_rows /
