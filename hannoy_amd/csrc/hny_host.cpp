@@ -3270,26 +3270,6 @@ struct SearchCancel {
   }
 };
 
-static int search_knn_impl(hny_builder *b, uint64_t nq, const void *qvectors, size_t qstride,
-                           const void *qheaders, uint32_t k, uint32_t ef_search, uint32_t *out_ids,
-                           float *out_dists, uint32_t *out_counts, const hny_query_opts *qo, bool q_f32 = false);
-// the QueryBuilder searcher with its search queue as a real heap in HBM (k_nns); force_heap: also for queries
-// without a candidates filter — where search_knn_impl sends the queries whose tie pool overflowed
-static int nns_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const void *qvectors, size_t qstride,
-                    const void *qheaders, const uint32_t *query_items, uint32_t *out_ids, float *out_dists,
-                    uint32_t *out_counts, bool force_heap, bool q_f32 = false);
-
-int hny_builder_search_knn(hny_builder *b, uint64_t nq, const void *qvectors, size_t qstride,
-                           const void *qheaders, uint32_t k, uint32_t ef_search, uint32_t *out_ids,
-                           float *out_dists, uint32_t *out_counts) {
-  return search_knn_impl(b, nq, qvectors, qstride, qheaders, k, ef_search, out_ids, out_dists, out_counts, nullptr);
-}
-
-int hny_builder_search_knn_f32(hny_builder *b, uint64_t nq, const float *queries, size_t qstride, uint32_t k,
-                               uint32_t ef_search, uint32_t *out_ids, float *out_dists, uint32_t *out_counts) {
-  return search_knn_impl(b, nq, queries, qstride, nullptr, k, ef_search, out_ids, out_dists, out_counts, nullptr, true);
-}
-
 // The graph the searches walk.  A successor builder (hny_builder_create_update) whose update has finished holds the
 // complete new lists in l0_ids / up_ids (fill_gaps rewrote every surviving record); its copy of the source's
 // lists is history, kept for finish_delta only.  The searches then read the new lists in the place of the
@@ -3304,14 +3284,16 @@ static GraphDev search_graph(const hny_builder *b) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// The steps the three batched searchers share: search_knn_impl (Reader on k_walk), nns_impl
-// (.candidates() / by_item on k_nns / k_nns_linear) and exact_impl (tiled full scan).  Each searcher calls the
-// argument checks in its own order (the first failure names the error), fills one QuerySet, sizes its chunk,
-// allocates a QueryStage and a TopkOut and runs its own chunk loop.
+// The steps the batched searchers share: search_knn_impl (Reader on k_walk), nns_impl
+// (.candidates() / by_item on k_nns / k_nns_linear), exact_impl (tiled full scan) and the two with a filter per
+// query.  An entry point fills one QuerySet and hands it to its driver, f(b, qo, qs, ...); the driver calls the
+// argument checks in its own order (the first failure names the error), sizes its chunk, allocates a QueryStage and
+// a TopkOut and runs its own chunk loop.  A driver that sends queries to another hands it the QuerySet, or a
+// SubBatch of it.
 // ---------------------------------------------------------------------------------------------
 static bool mask_has(const std::vector<u32> &mask, uint32_t s) { return (mask[s >> 5] >> (s & 31)) & 1u; }
 
-// the queries of one call and where their hits go, filled once per call
+// the queries of one call and where their hits go, filled once per call by the entry point
 struct QuerySet {
   const hny_builder *b;
   uint64_t nq;
@@ -3324,6 +3306,19 @@ struct QuerySet {
   uint32_t *out_ids;
   float *out_dists;
   uint32_t *out_counts;
+
+  // The two source forms of the entry points.  `b` and `qo` are the caller's and may be null: neither is read here,
+  // check_search_outputs refuses a null builder and k = 0
+  static QuerySet of(const hny_builder *b, const hny_query_opts *qo, uint64_t nq, const void *qvectors, size_t qstride,
+                     const void *qheaders, const uint32_t *query_items, uint32_t *out_ids, float *out_dists,
+                     uint32_t *out_counts) {
+    return {b, nq, qvectors, qstride, qheaders, query_items, false, query_items != nullptr, qo ? qo->k : 0,
+            out_ids, out_dists, out_counts};
+  }
+  static QuerySet of_f32(const hny_builder *b, const hny_query_opts *qo, uint64_t nq, const float *queries,
+                         size_t qstride, uint32_t *out_ids, float *out_dists, uint32_t *out_counts) {
+    return {b, nq, queries, qstride, nullptr, nullptr, true, false, qo ? qo->k : 0, out_ids, out_dists, out_counts};
+  }
 
   bool live(uint32_t s) const { return !b->incremental || !b->deleted[s]; }
   // the slot of a live item, -1 for an unknown or deleted one
@@ -3360,9 +3355,10 @@ struct QuerySet {
   }
 };
 
-static int check_search_outputs(const hny_builder *b, const uint32_t *out_ids, const float *out_dists,
-                                const uint32_t *out_counts, uint32_t k) {
-  return !b || !out_ids || !out_dists || !out_counts || k == 0 ? fail(HNY_ERR_INVALID_ARG, "bad argument") : HNY_OK;
+// the first check of every driver; past it the builder and (k came from them) the opts are there
+static int check_search_outputs(const QuerySet &q) {
+  return !q.b || !q.out_ids || !q.out_dists || !q.out_counts || q.k == 0 ? fail(HNY_ERR_INVALID_ARG, "bad argument")
+                                                                         : HNY_OK;
 }
 static int check_query_source(const QuerySet &q, const char *what) {
   return !q.by_item && (!q.qvectors || (!q.q_f32 && !q.qheaders)) ? fail(HNY_ERR_INVALID_ARG, "%s", what) : HNY_OK;
@@ -3583,18 +3579,85 @@ struct TopkOut {
   }
 };
 
-static int search_knn_impl(hny_builder *b, uint64_t nq, const void *qvectors, size_t qstride,
-                           const void *qheaders, uint32_t k, uint32_t ef_search, uint32_t *out_ids,
-                           float *out_dists, uint32_t *out_counts, const hny_query_opts *qo, bool q_f32) {
-  if (int rc = check_search_outputs(b, out_ids, out_dists, out_counts, k)) return rc;
-  const QuerySet qs{b, nq, qvectors, qstride, qheaders, nullptr, q_f32, false, k, out_ids, out_dists, out_counts};
+// A row of hits, `c` of them, to query qi of the caller's arrays, whose rows may be wider.  Like the searchers, only
+// the first `c` entries of a row are written, and none of a row without an answer (HNY_NNS_NONE)
+static void copy_hits(const QuerySet &q, uint64_t qi, uint32_t c, const uint32_t *ids, const float *dists) {
+  q.out_counts[qi] = c;
+  if (c == HNY_NNS_NONE) return;
+  memcpy(&q.out_ids[qi * q.k], ids, (size_t)c * 4);
+  memcpy(&q.out_dists[qi * q.k], dists, (size_t)c * 4);
+}
+
+// some of a call's queries, gathered so that the shared steps and the other drivers see them as a call of their own
+struct SubBatch {
+  const QuerySet &q;
+  uint32_t k = 0; // hits per row of its own arrays where that is less than the call's (0 = q.k)
+  std::vector<uint64_t> idx; // the caller's query of each row
+  std::vector<u32> filter_of;
+  std::vector<unsigned char> rows, hdrs;
+  std::vector<uint32_t> items, ids, counts;
+  std::vector<float> dists;
+
+  void add(uint64_t qi, u32 f = HNY_SENT) {
+    idx.push_back(qi);
+    filter_of.push_back(f);
+  }
+  QuerySet gather() {
+    const hny_builder *b = q.b;
+    const size_t m = idx.size(), hb = hdr_bytes(b->o.metric);
+    const size_t rb = q.q_f32 ? (size_t)b->o.dim * 4 : vec_bytes(b->o.metric, b->o.dim);
+    if (q.by_item) {
+      items.resize(m);
+      for (size_t j = 0; j < m; j++) items[j] = q.query_items[idx[j]];
+    } else {
+      rows.resize(m * rb);
+      hdrs.resize(std::max<size_t>(m * hb, 1));
+      for (size_t j = 0; j < m; j++) {
+        memcpy(&rows[j * rb], (const unsigned char *)q.qvectors + idx[j] * q.qstride, rb);
+        if (!q.q_f32 && hb) memcpy(&hdrs[j * hb], (const unsigned char *)q.qheaders + idx[j] * hb, hb);
+      }
+    }
+    const uint32_t kk = k ? k : q.k;
+    ids.resize(m * kk);
+    dists.resize(m * kk);
+    counts.assign(m, 0u);
+    return QuerySet{b, m, rows.data(), rb, hdrs.data(), q.by_item ? items.data() : nullptr, q.q_f32, q.by_item, kk,
+                    ids.data(), dists.data(), counts.data()};
+  }
+  // the hits to the caller's rows
+  void scatter() const {
+    const uint32_t kk = k ? k : q.k;
+    for (size_t j = 0; j < idx.size(); j++) copy_hits(q, idx[j], counts[j], &ids[j * kk], &dists[j * kk]);
+  }
+};
+
+// What one driver hands another in the place of the caller's opts: k, ef_search, the cancel closure, and where the
+// callee reports a cancellation.  Candidates and the linear thresholds do not cross: the calling driver has decided
+static hny_query_opts handed_opts(uint32_t k, uint32_t ef_search, const hny_query_opts *from, int32_t *did_cancel) {
+  hny_query_opts o{};
+  o.k = k;
+  o.ef_search = ef_search;
+  if (from) o.cancel = from->cancel, o.cancel_ctx = from->cancel_ctx;
+  o.did_cancel = did_cancel;
+  return o;
+}
+
+// a call's candidates once they are slots (nns_slots_impl, below nns_run)
+struct SlotCandidates;
+static int nns_slots_impl(hny_builder *b, const hny_query_opts *qo, const QuerySet &qs, const SlotCandidates *C);
+
+static int search_knn_impl(hny_builder *b, const hny_query_opts *qo, const QuerySet &qs) {
+  if (int rc = check_search_outputs(qs)) return rc;
   if (int rc = check_query_source(qs, "bad argument")) return rc;
   if (int rc = check_query_rows(qs)) return rc;
+  const uint64_t nq = qs.nq;
+  const uint32_t k = qs.k;
+  uint32_t *out_counts = qs.out_counts;
   SearchCancel sc;
   HIP_TRY(sc.begin(qo));
   if (int rc = check_build_finished(b)) return rc;
   uint32_t ef;
-  if (int rc = check_ef(ef_search, k, &ef)) return rc;
+  if (int rc = check_ef(qo->ef_search, k, &ef)) return rc;
   HIP_TRY(hipSetDevice(b->device));
   if (b->n == 0) return qs.none_found();
   if (int rc = ensure_finalized(b, b->stream)) return rc; // Reader::visit iterates Links bitmaps: ascending, deduplicated
@@ -3633,7 +3696,7 @@ static int search_knn_impl(hny_builder *b, uint64_t nq, const void *qvectors, si
     w.first = 1;
     w.reader_mode = 1;
     w.knn_k = k;
-    w.knn_ef = ef_search;
+    w.knn_ef = qo->ef_search;
     w.cand = dcand.p;
     w.cand_n = dcn.p;
     w.queue = queues;
@@ -3658,50 +3721,40 @@ static int search_knn_impl(hny_builder *b, uint64_t nq, const void *qvectors, si
     b->n_walk_dispatch++;
     HIP_TRY(hnyk_walk(sg, w, b->shape, hnyk_walk_form(sg, w, b->shape, b->knobs), grid, b->stream));
     if (int rc = top.fetch(dcand.p, dcn.p, rcap, cnt, sc)) return rc;
-    std::vector<uint32_t> again; // queries whose tie pool overflowed (short codes, large ef_search: ties everywhere)
+    SubBatch again{qs}; // queries whose tie pool overflowed (short codes, large ef_search: ties everywhere)
     for (uint32_t i = 0; i < cnt; i++) {
       if (sc.d && top.hn[i] == 0xFFFFFFFFu) // the batch was cancelled before this query finished
         out_counts[q0 + i] = 0u;
       else if (top.hn[i] == 0xFFFFFFFEu)
-        again.push_back(i);
+        again.add(q0 + i);
       else
         top.emit(i, q0 + i);
     }
-    if (!again.empty() && !sc.cancelled) {
-      // the same queries on the searcher whose queue is a real heap in HBM (and `res` too, when ef + 1 >
-      // HNY_RES_LDS_MAX): nothing to overflow, same results
+    if (!again.idx.empty() && !sc.cancelled) {
+      // the same queries, without candidates, on the searcher whose queue is a real heap in HBM (and `res` too, when
+      // ef + 1 > HNY_RES_LDS_MAX): nothing to overflow, same results
       // (f32 queries: their f32 rows, which the device encodes again to the same bytes)
-      const size_t vb = vec_bytes(b->o.metric, b->o.dim), hb = hdr_bytes(b->o.metric);
-      const size_t na = again.size(), qb = q_f32 ? (size_t)b->o.dim * 4 : vb;
-      std::vector<unsigned char> av(na * qb), ah(na * hb);
-      std::vector<uint32_t> ai(na * k), ac(na);
-      std::vector<float> ad(na * k);
-      for (size_t j = 0; j < na; j++) {
-        memcpy(&av[j * qb], (const unsigned char *)qvectors + (q0 + again[j]) * qstride, qb);
-        if (!q_f32) memcpy(&ah[j * hb], (const unsigned char *)qheaders + (q0 + again[j]) * hb, hb);
-      }
-      hny_query_opts o2{};
-      o2.k = k;
-      o2.ef_search = ef_search;
-      o2.linear_below = 1000;
-      o2.linear_below_ratio = 1.0f;
-      if (qo) {
-        o2.cancel = qo->cancel;
-        o2.cancel_ctx = qo->cancel_ctx;
-      }
-      int rc2 = nns_impl(b, &o2, na, av.data(), qb, ah.data(), nullptr, ai.data(), ad.data(), ac.data(), true, q_f32);
-      if (rc2) return rc2;
-      for (size_t j = 0; j < na; j++) {
-        const uint64_t qi = q0 + again[j];
-        out_counts[qi] = ac[j];
-        memcpy(&out_ids[qi * k], &ai[j * k], (size_t)k * 4);
-        memcpy(&out_dists[qi * k], &ad[j * k], (size_t)k * 4);
-      }
+      const hny_query_opts o2 = handed_opts(k, qo->ef_search, qo, nullptr);
+      if (int rc = nns_slots_impl(b, &o2, again.gather(), nullptr)) return rc;
+      again.scatter();
     } else {
-      for (uint32_t i : again) out_counts[q0 + i] = 0u;
+      for (uint64_t qi : again.idx) out_counts[qi] = 0u;
     }
   }
   return search_end(b, qo, sc);
+}
+
+int hny_builder_search_knn(hny_builder *b, uint64_t nq, const void *qvectors, size_t qstride,
+                           const void *qheaders, uint32_t k, uint32_t ef_search, uint32_t *out_ids,
+                           float *out_dists, uint32_t *out_counts) {
+  const hny_query_opts qo = handed_opts(k, ef_search, nullptr, nullptr);
+  return search_knn_impl(b, &qo, QuerySet::of(b, &qo, nq, qvectors, qstride, qheaders, nullptr, out_ids, out_dists, out_counts));
+}
+
+int hny_builder_search_knn_f32(hny_builder *b, uint64_t nq, const float *queries, size_t qstride, uint32_t k,
+                               uint32_t ef_search, uint32_t *out_ids, float *out_dists, uint32_t *out_counts) {
+  const hny_query_opts qo = handed_opts(k, ef_search, nullptr, nullptr);
+  return search_knn_impl(b, &qo, QuerySet::of_f32(b, &qo, nq, queries, qstride, out_ids, out_dists, out_counts));
 }
 
 // k_nns keeps its result set in LDS (up to 4 096 entries); beyond that the same search runs with `res` as a
@@ -3868,81 +3921,87 @@ static int nns_run(hny_builder *b, const hny_query_opts *qo, const QuerySet &qs,
   return HNY_OK;
 }
 
-// QueryBuilder with .candidates() and/or by_item (reader.rs:60-262, 621-711, 809-896)
-int hny_builder_nns(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const void *qvectors,
-                    size_t qstride, const void *qheaders, const uint32_t *query_items, uint32_t *out_ids,
-                    float *out_dists, uint32_t *out_counts) {
-  return nns_impl(b, qo, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists, out_counts, false);
-}
+// A call's candidates once they are slots, as one driver hands them to nns_slots_impl: the bitset over slots (live
+// ones only: QuerySet::slot_mask), the same slots ascending, and the caller's decision between the scan over them
+// (k_nns_linear) and the walk under the bitset (k_nns)
+struct SlotCandidates {
+  std::vector<u32> mask, slots;
+  bool linear = false;
+  void list_slots(uint32_t n, uint64_t count) {
+    slots.reserve(count);
+    for (uint32_t s = 0; s < n; s++)
+      if (mask_has(mask, s)) slots.push_back(s);
+  }
+};
 
-int hny_builder_nns_f32(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const float *queries, size_t qstride,
-                        uint32_t *out_ids, float *out_dists, uint32_t *out_counts) {
-  if (!queries) return fail(HNY_ERR_INVALID_ARG, "no queries");
-  return nns_impl(b, qo, nq, queries, qstride, nullptr, nullptr, out_ids, out_dists, out_counts, false, true);
-}
-
-static int nns_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const void *qvectors, size_t qstride,
-                    const void *qheaders, const uint32_t *query_items, uint32_t *out_ids, float *out_dists,
-                    uint32_t *out_counts, bool force_heap, bool q_f32) {
-  if (int rc = check_search_outputs(b, out_ids, out_dists, out_counts, qo ? qo->k : 0)) return rc;
-  const bool by_item = query_items != nullptr;
-  const uint32_t k = qo->k;
-  const QuerySet qs{b, nq, qvectors, qstride, qheaders, query_items, q_f32, by_item, k, out_ids, out_dists, out_counts};
-  if (int rc = check_query_source(qs, "no queries")) return rc;
-  if (int rc = check_query_rows(qs)) return rc; // here the f32 rows come before the candidates, in exact_impl after
-  if (int rc = check_candidates(qo)) return rc;
-  if (!(qo->linear_below_ratio >= 0.f && qo->linear_below_ratio <= 1.f)) // reader.rs:253-256
-    return fail(HNY_ERR_INVALID_ARG, "linear scan threshold ratio must be between 0.0 and 1.0");
-  if (!qo->has_candidates && !by_item && !force_heap)
-    return search_knn_impl(b, nq, qvectors, qstride, qheaders, k, qo->ef_search, out_ids, out_dists, out_counts, qo,
-                           q_f32);
+// The second half of the nns driver: the QueryBuilder searcher with its search queue as a real heap in HBM (k_nns),
+// or the scan of C.  Its callers have checked the QuerySet: nns_impl; exact_impl with the C it holds, always scanned;
+// search_knn_impl without candidates (C == null), for the queries whose tie pool overflowed.  Of `qo` it reads
+// ef_search, the cancel closure and did_cancel
+static int nns_slots_impl(hny_builder *b, const hny_query_opts *qo, const QuerySet &qs, const SlotCandidates *C) {
   if (int rc = check_build_finished(b)) return rc;
+  const uint32_t k = qs.k;
   uint32_t ef;
   if (int rc = check_ef(qo->ef_search, k, &ef)) return rc;
-  const bool big = nns_res_in_hbm(b, ef);
+  const bool big = nns_res_in_hbm(b, ef), linear = C && C->linear;
   HIP_TRY(hipSetDevice(b->device));
-  const uint32_t n = b->n;
-  const uint64_t n_items = qs.n_live();
-  std::vector<u32> mask, cand_slots; // the filter, and its slots in ascending order
-  if (qo->has_candidates) {
-    cand_slots.reserve(qs.slot_mask(qo, mask));
-    for (uint32_t s = 0; s < n; s++)
-      if (mask_has(mask, s)) cand_slots.push_back(s);
-  }
-  if (n_items == 0 || (qo->has_candidates && cand_slots.empty())) return qs.none_found();
-  // should_linear_scan, reader.rs:621-640
-  bool linear = false;
-  if (qo->has_candidates) {
-    const uint64_t cl = cand_slots.size();
-    linear = cl < (uint64_t)qo->linear_below && (float)cl / (float)n_items <= qo->linear_below_ratio;
-  }
+  if (C ? C->slots.empty() : qs.n_live() == 0) return qs.none_found(); // (no live item: no candidate slot either)
   if (int rc = ensure_finalized(b, b->stream)) return rc; // Reader::visit iterates Links bitmaps: ascending, deduplicated
   uint32_t rcap = res_capacity(ef, (uint32_t)b->entry_points.size(), b->n, b->top_layer_nodes,
                                big ? HNY_RES_GLOBAL_MAX : HNY_RES_LDS_MAX);
   if (big && linear) { // it returns min(k, candidates) hits
-    if (!(rcap = linear_rcap(std::min<uint64_t>(k, cand_slots.size()))))
+    if (!(rcap = linear_rcap(std::min<uint64_t>(k, C->slots.size()))))
       return fail(HNY_ERR_UNSUPPORTED, "linear scan for %u hits among %zu candidates: at most %u (lower linear_below)", k,
-                  cand_slots.size(), HNY_RES_LDS_MAX - 1);
+                  C->slots.size(), HNY_RES_LDS_MAX - 1);
   }
   if (int rc = check_query_stride(qs)) return rc;
   DevBuf<u32> dfilter, dcslots;
   NnsFilters F;
-  if (qo->has_candidates) {
-    HIP_TRY(dfilter.alloc(mask.size()));
-    HIP_TRY(hipMemcpyAsync(dfilter.p, mask.data(), mask.size() * 4, hipMemcpyHostToDevice, b->stream));
+  if (C) {
+    HIP_TRY(dfilter.alloc(C->mask.size()));
+    HIP_TRY(hipMemcpyAsync(dfilter.p, C->mask.data(), C->mask.size() * 4, hipMemcpyHostToDevice, b->stream));
     F.masks = dfilter.p;
     if (linear) {
-      HIP_TRY(dcslots.alloc(cand_slots.size()));
-      HIP_TRY(hipMemcpyAsync(dcslots.p, cand_slots.data(), cand_slots.size() * 4, hipMemcpyHostToDevice,
-                             b->stream));
+      HIP_TRY(dcslots.alloc(C->slots.size()));
+      HIP_TRY(hipMemcpyAsync(dcslots.p, C->slots.data(), C->slots.size() * 4, hipMemcpyHostToDevice, b->stream));
       F.cand_slots = dcslots.p;
     }
-    F.n_cand_slots = (u32)cand_slots.size();
+    F.n_cand_slots = (u32)C->slots.size();
   }
   SearchCancel sc; // hny_query_opts.cancel
   HIP_TRY(sc.begin(qo));
   if (int rc = nns_run(b, qo, qs, F, linear, big, ef, rcap, sc)) return rc;
   return search_end(b, qo, sc);
+}
+
+// The first half: the checks, then the opts' candidates as slots.  Without candidates, queries by vector are the plain
+// search (search_knn_impl), queries by item walk k_nns without a bitset
+static int nns_impl(hny_builder *b, const hny_query_opts *qo, const QuerySet &qs) {
+  if (int rc = check_search_outputs(qs)) return rc;
+  if (int rc = check_query_source(qs, "no queries")) return rc;
+  if (int rc = check_query_rows(qs)) return rc; // here the f32 rows come before the candidates, in exact_impl after
+  if (int rc = check_candidates(qo)) return rc;
+  if (!(qo->linear_below_ratio >= 0.f && qo->linear_below_ratio <= 1.f)) // reader.rs:253-256
+    return fail(HNY_ERR_INVALID_ARG, "linear scan threshold ratio must be between 0.0 and 1.0");
+  if (!qo->has_candidates) return qs.by_item ? nns_slots_impl(b, qo, qs, nullptr) : search_knn_impl(b, qo, qs);
+  SlotCandidates C;
+  C.list_slots(b->n, qs.slot_mask(qo, C.mask));
+  const uint64_t cl = C.slots.size(); // should_linear_scan, reader.rs:621-640
+  C.linear = cl < (uint64_t)qo->linear_below && (float)cl / (float)qs.n_live() <= qo->linear_below_ratio;
+  return nns_slots_impl(b, qo, qs, &C);
+}
+
+// QueryBuilder with .candidates() and/or by_item (reader.rs:60-262, 621-711, 809-896)
+int hny_builder_nns(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const void *qvectors,
+                    size_t qstride, const void *qheaders, const uint32_t *query_items, uint32_t *out_ids,
+                    float *out_dists, uint32_t *out_counts) {
+  return nns_impl(b, qo, QuerySet::of(b, qo, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists, out_counts));
+}
+
+int hny_builder_nns_f32(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const float *queries, size_t qstride,
+                        uint32_t *out_ids, float *out_dists, uint32_t *out_counts) {
+  if (!queries) return fail(HNY_ERR_INVALID_ARG, "no queries");
+  return nns_impl(b, qo, QuerySet::of_f32(b, qo, nq, queries, qstride, out_ids, out_dists, out_counts));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3957,58 +4016,6 @@ static uint64_t filter_mask_budget() {
   const uint64_t v = e ? strtoull(e, nullptr, 10) : 0;
   return v ? v : HNY_FILTER_MASK_BYTES;
 }
-
-// A row of hits, `c` of them, to query qi of the caller's arrays, whose rows may be wider.  Like the searchers, only
-// the first `c` entries of a row are written, and none of a row without an answer (HNY_NNS_NONE)
-static void copy_hits(const QuerySet &q, uint64_t qi, uint32_t c, const uint32_t *ids, const float *dists) {
-  q.out_counts[qi] = c;
-  if (c == HNY_NNS_NONE) return;
-  memcpy(&q.out_ids[qi * q.k], ids, (size_t)c * 4);
-  memcpy(&q.out_dists[qi * q.k], dists, (size_t)c * 4);
-}
-
-// some of a call's queries, gathered so that the shared steps see them as a call of their own
-struct SubBatch {
-  const QuerySet &q;
-  uint32_t k = 0; // hits per row of its own arrays where that is less than the call's (0 = q.k)
-  std::vector<uint64_t> idx; // the caller's query of each row
-  std::vector<u32> filter_of;
-  std::vector<unsigned char> rows, hdrs;
-  std::vector<uint32_t> items, ids, counts;
-  std::vector<float> dists;
-
-  void add(uint64_t qi, u32 f) {
-    idx.push_back(qi);
-    filter_of.push_back(f);
-  }
-  QuerySet gather() {
-    const hny_builder *b = q.b;
-    const size_t m = idx.size(), hb = hdr_bytes(b->o.metric);
-    const size_t rb = q.q_f32 ? (size_t)b->o.dim * 4 : vec_bytes(b->o.metric, b->o.dim);
-    if (q.by_item) {
-      items.resize(m);
-      for (size_t j = 0; j < m; j++) items[j] = q.query_items[idx[j]];
-    } else {
-      rows.resize(m * rb);
-      hdrs.resize(std::max<size_t>(m * hb, 1));
-      for (size_t j = 0; j < m; j++) {
-        memcpy(&rows[j * rb], (const unsigned char *)q.qvectors + idx[j] * q.qstride, rb);
-        if (!q.q_f32 && hb) memcpy(&hdrs[j * hb], (const unsigned char *)q.qheaders + idx[j] * hb, hb);
-      }
-    }
-    const uint32_t kk = k ? k : q.k;
-    ids.resize(m * kk);
-    dists.resize(m * kk);
-    counts.assign(m, 0u);
-    return QuerySet{b, m, rows.data(), rb, hdrs.data(), q.by_item ? items.data() : nullptr, q.q_f32, q.by_item, kk,
-                    ids.data(), dists.data(), counts.data()};
-  }
-  // the hits to the caller's rows
-  void scatter() const {
-    const uint32_t kk = k ? k : q.k;
-    for (size_t j = 0; j < idx.size(); j++) copy_hits(q, idx[j], counts[j], &ids[j * kk], &dists[j * kk]);
-  }
-};
 
 // The filters of a call with one filter per query, in rounds of as many bitsets as the budget holds (one always
 // fits: n < 2^31 slots are 256 MB).  nns_filtered_impl and exact_filtered_impl each run their own loop over the
@@ -4185,14 +4192,14 @@ struct FilterRounds {
   }
 };
 
-static int nns_filtered_impl(hny_builder *b, const hny_query_opts *qo, const FilterSource *fl, uint64_t nq,
-                             const void *qvectors, size_t qstride, const void *qheaders, const uint32_t *query_items,
-                             uint32_t *out_ids, float *out_dists, uint32_t *out_counts, bool q_f32) {
-  if (int rc = check_search_outputs(b, out_ids, out_dists, out_counts, qo ? qo->k : 0)) return rc;
+static int nns_filtered_impl(hny_builder *b, const hny_query_opts *qo, const QuerySet &qs, const FilterSource &src) {
+  const FilterSource *fl = &src;
+  const uint64_t nq = qs.nq;
+  if (int rc = check_search_outputs(qs)) return rc;
   if (int rc = check_filters(qo, fl, nq)) return rc;
-  const bool by_item = query_items != nullptr;
-  const uint32_t k = qo->k, NONE = HNY_NNS_NONE;
-  const QuerySet qs{b, nq, qvectors, qstride, qheaders, query_items, q_f32, by_item, k, out_ids, out_dists, out_counts};
+  const bool by_item = qs.by_item;
+  const uint32_t k = qs.k, NONE = HNY_NNS_NONE;
+  uint32_t *out_counts = qs.out_counts;
   if (int rc = check_query_source(qs, "no queries")) return rc;
   if (int rc = check_query_rows(qs)) return rc;
   if (!(qo->linear_below_ratio >= 0.f && qo->linear_below_ratio <= 1.f)) // reader.rs:253-256
@@ -4238,13 +4245,9 @@ static int nns_filtered_impl(hny_builder *b, const hny_query_opts *qo, const Fil
     for (uint64_t i = 0; i < nq; i++)
       if (fl->filter_of[i] == HNY_FILTER_NONE) plain.add(i, HNY_SENT);
     if (!plain.idx.empty() && !by_item) {
-      const QuerySet sub = plain.gather();
-      hny_query_opts o2 = *qo;
       int32_t cancelled = 0;
-      o2.did_cancel = &cancelled;
-      if (int rc = search_knn_impl(b, sub.nq, sub.qvectors, sub.qstride, sub.qheaders, k, qo->ef_search, sub.out_ids,
-                                   sub.out_dists, sub.out_counts, &o2, q_f32))
-        return rc;
+      const hny_query_opts o2 = handed_opts(k, qo->ef_search, qo, &cancelled);
+      if (int rc = search_knn_impl(b, &o2, plain.gather())) return rc;
       plain.scatter();
       if (cancelled && sc.fn) {
         sc.cancelled = true;
@@ -4294,34 +4297,30 @@ static int nns_filtered_impl(hny_builder *b, const hny_query_opts *qo, const Fil
 int hny_builder_nns_filtered(hny_builder *b, const hny_query_opts *qo, const hny_query_filters *filters, uint64_t nq,
                              const void *qvectors, size_t qstride, const void *qheaders, const uint32_t *query_items,
                              uint32_t *out_ids, float *out_dists, uint32_t *out_counts) {
-  const FilterSource src(filters);
-  return nns_filtered_impl(b, qo, &src, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists, out_counts,
-                           false);
+  return nns_filtered_impl(
+      b, qo, QuerySet::of(b, qo, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists, out_counts), filters);
 }
 
 int hny_builder_nns_filtered_f32(hny_builder *b, const hny_query_opts *qo, const hny_query_filters *filters,
                                  uint64_t nq, const float *queries, size_t qstride, uint32_t *out_ids,
                                  float *out_dists, uint32_t *out_counts) {
   if (!queries) return fail(HNY_ERR_INVALID_ARG, "no queries");
-  const FilterSource src(filters);
-  return nns_filtered_impl(b, qo, &src, nq, queries, qstride, nullptr, nullptr, out_ids, out_dists, out_counts, true);
+  return nns_filtered_impl(b, qo, QuerySet::of_f32(b, qo, nq, queries, qstride, out_ids, out_dists, out_counts), filters);
 }
 
 // the same with the filters as bitsets over item ids: FilterRounds' second source, nothing else
 int hny_builder_nns_bitsets(hny_builder *b, const hny_query_opts *qo, const hny_query_bitsets *filters, uint64_t nq,
                             const void *qvectors, size_t qstride, const void *qheaders, const uint32_t *query_items,
                             uint32_t *out_ids, float *out_dists, uint32_t *out_counts) {
-  const FilterSource src(filters);
-  return nns_filtered_impl(b, qo, &src, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists, out_counts,
-                           false);
+  return nns_filtered_impl(
+      b, qo, QuerySet::of(b, qo, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists, out_counts), filters);
 }
 
 int hny_builder_nns_bitsets_f32(hny_builder *b, const hny_query_opts *qo, const hny_query_bitsets *filters,
                                 uint64_t nq, const float *queries, size_t qstride, uint32_t *out_ids, float *out_dists,
                                 uint32_t *out_counts) {
   if (!queries) return fail(HNY_ERR_INVALID_ARG, "no queries");
-  const FilterSource src(filters);
-  return nns_filtered_impl(b, qo, &src, nq, queries, qstride, nullptr, nullptr, out_ids, out_dists, out_counts, true);
+  return nns_filtered_impl(b, qo, QuerySet::of_f32(b, qo, nq, queries, qstride, out_ids, out_dists, out_counts), filters);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -4440,20 +4439,16 @@ static int exact_dense_run(hny_builder *b, const QuerySet &qs, const u32 *dmask,
   return HNY_OK;
 }
 
-static int exact_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const void *qvectors, size_t qstride,
-                      const void *qheaders, const uint32_t *query_items, uint32_t *out_ids, float *out_dists,
-                      uint32_t *out_counts, bool q_f32) {
-  if (int rc = check_search_outputs(b, out_ids, out_dists, out_counts, qo ? qo->k : 0)) return rc;
-  const bool by_item = query_items != nullptr;
-  const uint32_t n = b->n, k = qo->k;
-  const QuerySet qs{b, nq, qvectors, qstride, qheaders, query_items, q_f32, by_item, k, out_ids, out_dists, out_counts};
+static int exact_impl(hny_builder *b, const hny_query_opts *qo, const QuerySet &qs) {
+  if (int rc = check_search_outputs(qs)) return rc;
+  const uint32_t n = b->n, k = qs.k;
   if (int rc = check_query_source(qs, "no queries")) return rc;
   if (int rc = check_candidates(qo)) return rc; // here the candidates come before the f32 rows, in nns_impl after
   if (int rc = check_query_rows(qs)) return rc;
   if (int rc = check_build_finished(b)) return rc;
   // C = live items (∩ candidates) as a mask over slots, the one nns_impl builds for its filter
-  std::vector<u32> mask;
-  const uint64_t n_c = qs.slot_mask(qo, mask);
+  SlotCandidates C;
+  const uint64_t n_c = qs.slot_mask(qo, C.mask);
   if (qo->did_cancel) *qo->did_cancel = 0;
   if (n_c == 0) return qs.none_found();
   const uint32_t kk = (uint32_t)std::min<uint64_t>(k, n_c); // hits per query
@@ -4465,33 +4460,21 @@ static int exact_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, con
   const uint32_t qt = hnyk_exact_qt(b->g.row_stride);
   const bool strict = b->g.x86_order && b->g.mclass != MC_BIN;
   if (strict || n_c * qt < n) {
-    // a gather of C reads |C| rows per query, the dense scan n / qt: the one-wave scan over cand_slots = C
-    std::vector<uint32_t> c_ids;
-    c_ids.reserve(n_c);
-    for (uint32_t s = 0; s < n; s++)
-      if (mask_has(mask, s)) c_ids.push_back(b->ids[s]);
-    hny_query_opts o2 = *qo;
-    o2.k = kk;
-    o2.ef_search = 0;
-    o2.has_candidates = 1;
-    o2.candidates = c_ids.data();
-    o2.n_candidates = c_ids.size();
-    o2.linear_below = 0xFFFFFFFFu;
-    o2.linear_below_ratio = 1.0f;
-    if (kk == k)
-      return nns_impl(b, &o2, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists, out_counts, false,
-                      q_f32);
-    std::vector<uint32_t> ti((size_t)nq * kk);
-    std::vector<float> td((size_t)nq * kk);
-    int rc = nns_impl(b, &o2, nq, qvectors, qstride, qheaders, query_items, ti.data(), td.data(), out_counts, false,
-                      q_f32);
-    if (rc) return rc;
-    for (uint64_t i = 0; i < nq; i++) copy_hits(qs, i, out_counts[i], &ti[i * kk], &td[i * kk]);
+    // a gather of C reads |C| rows per query, the dense scan n / qt: the one-wave scan over cand_slots = C, the
+    // slots of the mask as they are
+    C.list_slots(n, n_c);
+    C.linear = true;
+    const hny_query_opts o2 = handed_opts(kk, 0, qo, qo->did_cancel);
+    if (kk == k) return nns_slots_impl(b, &o2, qs, &C);
+    SubBatch all{qs, kk}; // rows of kk entries: fewer candidates than k
+    for (uint64_t i = 0; i < qs.nq; i++) all.add(i);
+    if (int rc = nns_slots_impl(b, &o2, all.gather(), &C)) return rc;
+    all.scatter();
     return HNY_OK;
   }
   DevBuf<u32> dmask;
-  HIP_TRY(dmask.alloc(mask.size()));
-  HIP_TRY(hipMemcpyAsync(dmask.p, mask.data(), mask.size() * 4, hipMemcpyHostToDevice, b->stream));
+  HIP_TRY(dmask.alloc(C.mask.size()));
+  HIP_TRY(hipMemcpyAsync(dmask.p, C.mask.data(), C.mask.size() * 4, hipMemcpyHostToDevice, b->stream));
   SearchCancel sc;
   HIP_TRY(sc.init(qo)); // (did_cancel was cleared above, ahead of the early returns)
   if (int rc = exact_dense_run(b, qs, dmask.p, kk, nullptr, sc)) return rc;
@@ -4501,13 +4484,13 @@ static int exact_impl(hny_builder *b, const hny_query_opts *qo, uint64_t nq, con
 int hny_builder_exact_knn(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const void *qvectors,
                           size_t qstride, const void *qheaders, const uint32_t *query_items, uint32_t *out_ids,
                           float *out_dists, uint32_t *out_counts) {
-  return exact_impl(b, qo, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists, out_counts, false);
+  return exact_impl(b, qo, QuerySet::of(b, qo, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists, out_counts));
 }
 
 int hny_builder_exact_knn_f32(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const float *queries,
                               size_t qstride, uint32_t *out_ids, float *out_dists, uint32_t *out_counts) {
   if (!queries) return fail(HNY_ERR_INVALID_ARG, "no queries");
-  return exact_impl(b, qo, nq, queries, qstride, nullptr, nullptr, out_ids, out_dists, out_counts, true);
+  return exact_impl(b, qo, QuerySet::of_f32(b, qo, nq, queries, qstride, out_ids, out_dists, out_counts));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -4522,14 +4505,12 @@ static bool exact_skip_env() {
   return !(e && e[0] == '0' && !e[1]);
 }
 
-static int exact_filtered_impl(hny_builder *b, const hny_query_opts *qo, const FilterSource *fl, uint64_t nq,
-                               const void *qvectors, size_t qstride, const void *qheaders, const uint32_t *query_items,
-                               uint32_t *out_ids, float *out_dists, uint32_t *out_counts, bool q_f32) {
-  if (int rc = check_search_outputs(b, out_ids, out_dists, out_counts, qo ? qo->k : 0)) return rc;
+static int exact_filtered_impl(hny_builder *b, const hny_query_opts *qo, const QuerySet &qs, const FilterSource &src) {
+  const FilterSource *fl = &src;
+  const uint64_t nq = qs.nq;
+  if (int rc = check_search_outputs(qs)) return rc;
   if (int rc = check_filters(qo, fl, nq)) return rc; // the candidates' side before the f32 rows, as in exact_impl
-  const bool by_item = query_items != nullptr;
-  const uint32_t n = b->n, k = qo->k;
-  const QuerySet qs{b, nq, qvectors, qstride, qheaders, query_items, q_f32, by_item, k, out_ids, out_dists, out_counts};
+  const uint32_t n = b->n, k = qs.k;
   if (int rc = check_query_source(qs, "no queries")) return rc;
   if (int rc = check_query_rows(qs)) return rc;
   if (int rc = check_build_finished(b)) return rc;
@@ -4619,18 +4600,15 @@ int hny_builder_exact_knn_filtered(hny_builder *b, const hny_query_opts *qo, con
                                    uint64_t nq, const void *qvectors, size_t qstride, const void *qheaders,
                                    const uint32_t *query_items, uint32_t *out_ids, float *out_dists,
                                    uint32_t *out_counts) {
-  const FilterSource src(filters);
-  return exact_filtered_impl(b, qo, &src, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists,
-                             out_counts, false);
+  return exact_filtered_impl(
+      b, qo, QuerySet::of(b, qo, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists, out_counts), filters);
 }
 
 int hny_builder_exact_knn_filtered_f32(hny_builder *b, const hny_query_opts *qo, const hny_query_filters *filters,
                                        uint64_t nq, const float *queries, size_t qstride, uint32_t *out_ids,
                                        float *out_dists, uint32_t *out_counts) {
   if (!queries) return fail(HNY_ERR_INVALID_ARG, "no queries");
-  const FilterSource src(filters);
-  return exact_filtered_impl(b, qo, &src, nq, queries, qstride, nullptr, nullptr, out_ids, out_dists, out_counts,
-                             true);
+  return exact_filtered_impl(b, qo, QuerySet::of_f32(b, qo, nq, queries, qstride, out_ids, out_dists, out_counts), filters);
 }
 
 // the same with the filters as bitsets over item ids
@@ -4638,18 +4616,15 @@ int hny_builder_exact_knn_bitsets(hny_builder *b, const hny_query_opts *qo, cons
                                   uint64_t nq, const void *qvectors, size_t qstride, const void *qheaders,
                                   const uint32_t *query_items, uint32_t *out_ids, float *out_dists,
                                   uint32_t *out_counts) {
-  const FilterSource src(filters);
-  return exact_filtered_impl(b, qo, &src, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists,
-                             out_counts, false);
+  return exact_filtered_impl(
+      b, qo, QuerySet::of(b, qo, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists, out_counts), filters);
 }
 
 int hny_builder_exact_knn_bitsets_f32(hny_builder *b, const hny_query_opts *qo, const hny_query_bitsets *filters,
                                       uint64_t nq, const float *queries, size_t qstride, uint32_t *out_ids,
                                       float *out_dists, uint32_t *out_counts) {
   if (!queries) return fail(HNY_ERR_INVALID_ARG, "no queries");
-  const FilterSource src(filters);
-  return exact_filtered_impl(b, qo, &src, nq, queries, qstride, nullptr, nullptr, out_ids, out_dists, out_counts,
-                             true);
+  return exact_filtered_impl(b, qo, QuerySet::of_f32(b, qo, nq, queries, qstride, out_ids, out_dists, out_counts), filters);
 }
 
 uint64_t hny_builder_exact_rows_read(const hny_builder *b) { return b ? b->exact_rows_read : 0; }

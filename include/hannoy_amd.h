@@ -280,7 +280,8 @@ int hny_builder_distances(hny_builder *b, uint64_t n_pairs, const uint32_t *slot
 /* ef_search (and k) up to 65 535: result sets of up to 4 096 entries live in the walk's LDS, larger ones in
  * HBM — the reference's own tests search with ef_search = n up to 9 999 (src/tests/reader.rs:82-98).  A query
  * whose walk overflows its tie pool (short codes: a handful of distinct distances) is searched again on heaps
- * in HBM and returns the same hits: no input fails for it. */
+ * in HBM and returns the same hits: no input fails for it.  Only the first out_counts[i] entries of row i of
+ * out_ids and out_dists are written; the entries past them stay as the caller had them. */
 int hny_builder_search_knn(hny_builder *b, uint64_t n_queries, const void *qvectors, size_t qstride,
                            const void *qheaders, uint32_t k, uint32_t ef_search, uint32_t *out_ids,
                            float *out_dists, uint32_t *out_counts);

@@ -11,6 +11,8 @@ checks that (a), (b) and (c) are identical (ids, distance bits, counts) and writ
 calls, the spread of the repetitions and Builder.exact_rows_read() of (b) and (c) to
 profiles/exact_filtered_throughput.json (OUT=path overrides; a run adds its shape to the file it finds).  One
 warm-up of each, then --repeat timed repetitions, alternating; medians.  Wall clock only: no counter is read.
+Last, on a second builder of the same items in strict mode (x86_order), one unfiltered exact_knn_f32 call of the same
+queries, timed alike ("strict_exact_knn_f32"): the path that hands every live item to the one-wave scan.
 
   python scripts/exact_filtered_throughput.py --n 200000 --dim 768
   python scripts/exact_filtered_throughput.py --n 1000000 --dim 128
@@ -128,6 +130,11 @@ def main():
                 entry["exact_knn_f32_single_call"] = entry["loop"]  # the loop IS the one call
             res["filters"][str(nf)] = entry
             print(nf, json.dumps(entry), flush=True)
+    # strict mode (x86_order): exact_knn_f32 over every live item goes to the one-wave scan
+    with H.Builder(items, prev=Ring(np, a.n), load=True, M=2, M0=2, ef_construction=1, x86_order=True) as b:
+        ts = [timed(lambda: b.exact_knn_f32(q, k=a.k))[0] for _ in range(1 + a.repeat)][1:]  # the first warms up
+        res["strict_exact_knn_f32"] = stats(ts)
+        print("strict", json.dumps(res["strict_exact_knn_f32"]), flush=True)
     out = os.environ.get("OUT") or os.path.join(ROOT, "profiles", NAME)
     os.makedirs(os.path.dirname(out), exist_ok=True)
     runs = {}

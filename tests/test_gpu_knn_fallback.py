@@ -76,6 +76,45 @@ def test_knn_on_a_disconnected_graph_equals_oracle(orc, hny, monkeypatch, dim, f
         _check(orc, b, ds, b.finish(), queries, ef_search)
 
 
+@pytest.mark.parametrize("force_retry", [None, "2"], ids=["plain", "every-second-query-on-the-heap-searcher"])
+def test_knn_writes_nothing_past_the_count(orc, hny, monkeypatch, force_retry):
+    """k = 64 on the 60 items: every row has 60 hits, and entries 60 .. 63 of the caller's arrays stay as they were,
+    in the rows that the walk answers and, with HNY_POOL_FORCE_RETRY=2, in those (queries 0, 2 and 4) that come back
+    from the heap searcher through SubBatch::scatter.  Codes and f32 queries, through the C entry points themselves
+    so that the output arrays are the test's own."""
+    if force_retry:
+        monkeypatch.setenv("HNY_POOL_FORCE_RETRY", force_retry)
+    dim, k, ef_search, n = 64, 64, 200, NA + NB  # (ef_search = 50 gives 50 hits, ef_search >= k all 60)
+    _, vecs, levels, queries = _world(dim)
+    nq = len(queries)
+    assert k > n and min((np.arange(nq) % 2 == 0).sum(), (np.arange(nq) % 2 != 0).sum()) >= 2
+    ds = orc.Dataset.from_f32(METRIC, vecs, levels)
+    items = hny.ItemSet(METRIC, dim, ds.ids, ds.codes, ds.headers, ds.levels)
+    qc = orc.encode_vectors(METRIC, queries)
+    qh = orc.make_headers(METRIC, dim, qc)
+    capi, L = hny._capi, hny.load_library()
+    with hny.Builder(items, M=M, M0=M0, ef_construction=EF_C, **BUILD) as b:
+        b.run()
+        g = b.finish()
+        oids, odists, ocounts = orc.search(ds, g, qc, qh, k=k, ef_search=ef_search, order=orc.ORDER_WAVE)
+        assert ocounts.tolist() == [n] * nq
+        for tag in ("codes", "f32"):
+            ids, dists, counts = out = (np.full((nq, k), 77, np.uint32), np.full((nq, k), 7.5, np.float32),
+                                        np.full(nq, 77, np.uint32))
+            if tag == "codes":
+                (_, pq, qstride, ph, _), _keep = capi._query_source(qcodes=qc, qheaders=qh)
+                rc = L.hny_builder_search_knn(b._h, nq, pq, qstride, ph, k, ef_search, *map(capi._p, out))
+            else:
+                (_, pq, qstride, _, _), _keep = capi._query_source(qf32=capi._f32_rows(queries))
+                rc = L.hny_builder_search_knn_f32(b._h, nq, pq, qstride, k, ef_search, *map(capi._p, out))
+            assert rc == 0, tag
+            assert np.array_equal(counts, ocounts), tag
+            assert np.array_equal(ids[:, :n], oids[:, :n]), tag
+            assert np.array_equal(dists[:, :n].view(np.uint32), odists[:, :n].view(np.uint32)), tag
+            for r in range(nq):
+                assert (ids[r, n:] == 77).all() and (dists[r, n:] == 7.5).all(), (tag, r)
+
+
 def test_knn_on_a_disconnected_graph_after_deletes_equals_oracle(orc, hny):
     """The same on the successor of a resident update: the slots of the deleted items stay in the index without a
     vector, and the fallback's scan has to pass over them."""

@@ -95,7 +95,7 @@ def _check(call, nq, oracle, tag):
 @pytest.mark.parametrize("force_retry", [None, "3"], ids=["plain", "every-third-query-falls-back"])
 def test_knn_chunks(orc, hny, world, monkeypatch, force_retry):
     """search_knn / search_knn_f32 over three chunks; with HNY_POOL_FORCE_RETRY=3 every third query of every chunk is
-    sent to the heap searcher (nns_impl, force_heap) from inside the chunk loop: same hits"""
+    sent to the heap searcher (nns_slots_impl without candidates) from inside the chunk loop: same hits"""
     w = world
     if force_retry:
         monkeypatch.setenv("HNY_POOL_FORCE_RETRY", force_retry)
