@@ -688,8 +688,9 @@ void robust_prune(Builder &B, std::vector<Link> cands, uint32_t cap, uint64_t &e
   }
 }
 
-/* hnsw.rs:523-560 add_link */
-void add_link(Builder &B, uint32_t p, Link q, uint32_t layer, uint64_t &evals) {
+/* hnsw.rs:523-560 add_link.  full (orc_stepper, else null): collects (layer << 32 | p) of every call that met a
+ * full list */
+void add_link(Builder &B, uint32_t p, Link q, uint32_t layer, uint64_t &evals, std::vector<uint64_t> *full = nullptr) {
   if (p == q.id) return;              /* :530 */
   NodeList *nl = B.list(layer, p);    /* :534 layer missing → no-op */
   if (!nl) return;
@@ -699,6 +700,7 @@ void add_link(Builder &B, uint32_t p, Link q, uint32_t layer, uint64_t &evals) {
   if (nl->links.size() < cap) {
     nl->links.push_back(q); /* :542-545, no dedup */
   } else {
+    if (full) full->push_back(((uint64_t)layer << 32) | p);
     std::vector<Link> pruned; /* :547-552 — q itself is dropped */
     robust_prune(B, nl->links, cap, evals, pruned);
     nl->links.swap(pruned);
@@ -736,11 +738,11 @@ void insert_search(Builder &B, Scratch &S, uint32_t q, uint32_t level, Selection
 }
 /* ... and its mutating half (:316-324) */
 void insert_apply(Builder &B, uint32_t q, uint32_t level, const Selection &sel, uint64_t &evals,
-                  uint64_t &links) {
+                  uint64_t &links, std::vector<uint64_t> *full = nullptr) {
   for (int32_t l = (int32_t)level; l >= 0; l--)
     for (const Link &s : sel.per_layer[l]) {
-      add_link(B, q, s, (uint32_t)l, evals);
-      add_link(B, s.id, Link{s.d, q}, (uint32_t)l, evals);
+      add_link(B, q, s, (uint32_t)l, evals, full);
+      add_link(B, s.id, Link{s.d, q}, (uint32_t)l, evals, full);
       links += 2; /* build_stats.incr_link_count(2) :323 */
     }
 }
@@ -875,6 +877,85 @@ uint32_t orc_level_probas(uint32_t M, float *out, uint32_t cap) {
   return level;
 }
 
+/* One batch of the batch-synchronous schedule in its two halves, shared by run_schedule and orc_stepper.
+ * batch_search: members ord[pos, pos + cnt) against the frozen graph, one Selection per member. */
+typedef std::vector<std::pair<uint32_t, uint32_t>> InsertOrder; /* (slot, level) in insertion order */
+static void batch_search(Builder &B, const InsertOrder &ord, size_t pos, size_t cnt, std::vector<Scratch> &scratch,
+                         std::vector<Selection> &sels) {
+  const int nthreads = (int)scratch.size();
+  sels.assign(cnt, Selection{});
+  if (nthreads == 1) {
+    for (size_t i = 0; i < cnt; i++)
+      insert_search(B, scratch[0], ord[pos + i].first, ord[pos + i].second, sels[i]);
+  } else {
+    std::atomic<size_t> next{0};
+    std::vector<std::thread> th;
+    for (int t = 0; t < nthreads; t++)
+      th.emplace_back([&, t]() {
+        for (;;) {
+          size_t i = next.fetch_add(1);
+          if (i >= cnt) break;
+          insert_search(B, scratch[t], ord[pos + i].first, ord[pos + i].second, sels[i]);
+        }
+      });
+    for (auto &t : th) t.join();
+  }
+}
+/* members of the batch that starts at ord[pos] with n_done items inserted: never past the level group (hnsw.rs:160) */
+static size_t batch_count(const orc_opts *o, const InsertOrder &ord, size_t pos, uint64_t n_done) {
+  size_t gend = pos;
+  while (gend < ord.size() && ord[gend].second == ord[pos].second) gend++;
+  return std::min(gend - pos, (size_t)orc_batch_size(o->batch_frac, o->batch_max, n_done));
+}
+/* batch_apply: the members registered, then their links in batch order.  full (or null): the (layer << 32 | target)
+ * of every add_link that met a full list, in no particular order, repeats included. */
+static void batch_apply(Builder &B, const InsertOrder &ord, size_t pos, size_t cnt, const std::vector<Selection> &sels,
+                        int nthreads, uint64_t &evals, uint64_t &links, std::vector<uint64_t> *full) {
+  bool was_threaded = B.threaded;
+  B.threaded = false; /* apply is sequential by definition */
+  for (size_t i = 0; i < cnt; i++) register_item(B, ord[pos + i].first, ord[pos + i].second);
+  if (nthreads == 1 || cnt < 256) {
+    for (size_t i = 0; i < cnt; i++)
+      insert_apply(B, ord[pos + i].first, ord[pos + i].second, sels[i], evals, links, full);
+  } else {
+    /* The same sequence of add_link calls, executed by several threads without changing its outcome: an
+     * add_link touches only the lists of its TARGET, so calls on different targets commute; every thread
+     * walks the whole sequence in batch order and performs the calls whose target it owns (blocks of 16
+     * slots, round robin) — per target the order is the sequential one, no list is shared, no lock taken.
+     * (Round 5: at 10M items this phase, on one thread, was most of the oracle's build time.) */
+    const uint32_t T = (uint32_t)nthreads;
+    std::vector<uint64_t> tev(T, 0), tln(T, 0);
+    std::vector<std::vector<uint64_t>> tfull(T);
+    std::vector<std::thread> th;
+    for (uint32_t t = 0; t < T; t++)
+      th.emplace_back([&, t]() {
+        uint64_t ev = 0, ln = 0;
+        std::vector<uint64_t> *fl = full ? &tfull[t] : nullptr;
+        for (size_t i = 0; i < cnt; i++) {
+          const uint32_t q = ord[pos + i].first, lvl = ord[pos + i].second;
+          const bool mine_q = (q >> 4) % T == t;
+          for (int32_t l = (int32_t)lvl; l >= 0; l--)
+            for (const Link &sl : sels[i].per_layer[l]) {
+              if (mine_q) {
+                add_link(B, q, sl, (uint32_t)l, ev, fl);
+                ln += 2; /* build_stats.incr_link_count(2) :323, counted by the owner of q */
+              }
+              if ((sl.id >> 4) % T == t) add_link(B, sl.id, Link{sl.d, q}, (uint32_t)l, ev, fl);
+            }
+        }
+        tev[t] = ev;
+        tln[t] = ln;
+      });
+    for (auto &x : th) x.join();
+    for (uint32_t t = 0; t < T; t++) {
+      evals += tev[t];
+      links += tln[t];
+      if (full) full->insert(full->end(), tfull[t].begin(), tfull[t].end());
+    }
+  }
+  B.threaded = was_threaded;
+}
+
 /* hnsw.rs:160-185: level groups in order; inside a group either the reference's plain insertion
  * (1 thread or rayon-like) or the batch-synchronous schedule of the GPU build */
 static void run_schedule(Builder &B, const orc_opts *opts,
@@ -943,29 +1024,13 @@ static void run_schedule(Builder &B, const orc_opts *opts,
     } else {
       /* batch-synchronous schedule: every member of a batch searches the same frozen graph,
        * then links are applied in batch order (DESIGN.md "Batch semantics") */
-      size_t bsz = orc_batch_size(opts->batch_frac, opts->batch_max, n_done);
-      size_t bend = std::min(gend, pos + bsz);
-      size_t cnt = bend - pos;
-      std::vector<Selection> sels(cnt);
+      size_t cnt = batch_count(opts, ord, pos, n_done);
+      size_t bend = pos + cnt;
+      std::vector<Selection> sels;
       const char *trace_path = std::getenv("ORC_TRACE_EVALS"); /* diagnostics: the LAST batch's level-0 walks */
       const bool trace_now = trace_path && bend == ord.size();
       for (auto &sc : scratch) sc.tracing = trace_now;
-      if (nthreads == 1) {
-        for (size_t i = 0; i < cnt; i++)
-          insert_search(B, scratch[0], ord[pos + i].first, ord[pos + i].second, sels[i]);
-      } else {
-        std::atomic<size_t> next{0};
-        std::vector<std::thread> th;
-        for (int t = 0; t < nthreads; t++)
-          th.emplace_back([&, t]() {
-            for (;;) {
-              size_t i = next.fetch_add(1);
-              if (i >= cnt) break;
-              insert_search(B, scratch[t], ord[pos + i].first, ord[pos + i].second, sels[i]);
-            }
-          });
-        for (auto &t : th) t.join();
-      }
+      batch_search(B, ord, pos, cnt, scratch, sels);
       if (trace_now) {
         if (FILE *f = std::fopen(trace_path, "wb")) {
           for (auto &sc : scratch) {
@@ -976,46 +1041,7 @@ static void run_schedule(Builder &B, const orc_opts *opts,
           std::fclose(f);
         }
       }
-      bool was_threaded = B.threaded;
-      B.threaded = false; /* apply is sequential by definition */
-      for (size_t i = 0; i < cnt; i++) register_item(B, ord[pos + i].first, ord[pos + i].second);
-      if (nthreads == 1 || cnt < 256) {
-        for (size_t i = 0; i < cnt; i++)
-          insert_apply(B, ord[pos + i].first, ord[pos + i].second, sels[i], evals, links);
-      } else {
-        /* The same sequence of add_link calls, executed by several threads without changing its outcome: an
-         * add_link touches only the lists of its TARGET, so calls on different targets commute; every thread
-         * walks the whole sequence in batch order and performs the calls whose target it owns (blocks of 16
-         * slots, round robin) — per target the order is the sequential one, no list is shared, no lock taken.
-         * (Round 5: at 10M items this phase, on one thread, was most of the oracle's build time.) */
-        const uint32_t T = (uint32_t)nthreads;
-        std::vector<uint64_t> tev(T, 0), tln(T, 0);
-        std::vector<std::thread> th;
-        for (uint32_t t = 0; t < T; t++)
-          th.emplace_back([&, t]() {
-            uint64_t ev = 0, ln = 0;
-            for (size_t i = 0; i < cnt; i++) {
-              const uint32_t q = ord[pos + i].first, lvl = ord[pos + i].second;
-              const bool mine_q = (q >> 4) % T == t;
-              for (int32_t l = (int32_t)lvl; l >= 0; l--)
-                for (const Link &sl : sels[i].per_layer[l]) {
-                  if (mine_q) {
-                    add_link(B, q, sl, (uint32_t)l, ev);
-                    ln += 2; /* build_stats.incr_link_count(2) :323, counted by the owner of q */
-                  }
-                  if ((sl.id >> 4) % T == t) add_link(B, sl.id, Link{sl.d, q}, (uint32_t)l, ev);
-                }
-            }
-            tev[t] = ev;
-            tln[t] = ln;
-          });
-        for (auto &x : th) x.join();
-        for (uint32_t t = 0; t < T; t++) {
-          evals += tev[t];
-          links += tln[t];
-        }
-      }
-      B.threaded = was_threaded;
+      batch_apply(B, ord, pos, cnt, sels, nthreads, evals, links, nullptr);
       n_done += cnt;
       pos = bend;
     }
@@ -1294,17 +1320,14 @@ void orc_rust_sort_levels(uint32_t *ids, uint32_t *levels, uint64_t n) {
   }
 }
 
-int orc_build(const orc_opts *opts, const orc_items *items, orc_graph **out) {
-  if (!opts || !items || !out) return -1;
-  if (opts->M == 0 || opts->M0 < opts->M) return -2;
-  Builder B;
+/* a fresh build up to its first insertion: levels, insertion order, empty layers, entry points (orc_build, orc_stepper) */
+static void build_prepare(Builder &B, const orc_opts *opts, const orc_items *items, InsertOrder &ord) {
   B.o = *opts;
   B.it = *items;
   B.dist = Dist{opts->metric, opts->order, opts->dim, vec_bytes(opts->metric, opts->dim)};
   B.n = (uint32_t)items->n;
   B.threaded = opts->threads > 1;
   uint32_t n = B.n;
-  auto g = std::make_unique<orc_graph>();
 
   /* hnsw.rs:141-149 levels (injected) */
   B.level.assign(items->levels, items->levels + n);
@@ -1344,15 +1367,15 @@ int orc_build(const orc_opts *opts, const orc_items *items, orc_graph **out) {
         register_item(B, s, B.max_level);
       }
   }
+  ord.resize(n);
+  for (uint32_t i = 0; i < n; i++) ord[i] = {order[i], B.level[order[i]]};
+}
 
-  uint64_t evals = 0, links = 0;
-  int nthreads = std::max(1, opts->threads);
-  std::vector<Scratch> scratch(nthreads);
-  {
-    std::vector<std::pair<uint32_t, uint32_t>> ord(n);
-    for (uint32_t i = 0; i < n; i++) ord[i] = {order[i], B.level[order[i]]};
-    run_schedule(B, opts, ord, 0, scratch, evals, links);
-  }
+/* the finished build as orc_graph; evals / links: what the apply halves counted (the walks' are in scratch) */
+static orc_graph *build_export(Builder &B, const std::vector<Scratch> &scratch, uint64_t evals, uint64_t links) {
+  auto g = std::make_unique<orc_graph>();
+  const orc_items *items = &B.it;
+  const uint32_t n = B.n;
   uint64_t evals_walk = 0;
   for (auto &s : scratch) {
     evals += s.evals;
@@ -1386,7 +1409,139 @@ int orc_build(const orc_opts *opts, const orc_items *items, orc_graph **out) {
   g->n_evals = evals;
   g->n_evals_walk = evals_walk;
   g->n_links = links;
-  *out = g.release();
+  return g.release();
+}
+
+int orc_build(const orc_opts *opts, const orc_items *items, orc_graph **out) {
+  if (!opts || !items || !out) return -1;
+  if (opts->M == 0 || opts->M0 < opts->M) return -2;
+  Builder B;
+  InsertOrder ord;
+  build_prepare(B, opts, items, ord);
+  uint64_t evals = 0, links = 0;
+  std::vector<Scratch> scratch(std::max(1, opts->threads));
+  run_schedule(B, opts, ord, 0, scratch, evals, links);
+  *out = build_export(B, scratch, evals, links);
+  return 0;
+}
+
+/* ---- orc_build one batch half at a time (hannoy_oracle.h): batch_count / batch_search / batch_apply as
+ * run_schedule calls them, with the selections passing through the caller in the device layout ---- */
+struct orc_stepper {
+  Builder B;
+  InsertOrder ord;
+  std::vector<Scratch> scratch;
+  uint64_t evals = 0, links = 0, n_done = 0;
+  size_t pos = 0, cnt = 0; /* cnt > 0: a batch is open */
+  std::vector<uint64_t> full; /* of the last apply: ascending, unique */
+  uint32_t level() const { return ord[pos].second; }
+  uint32_t cap_sel() const { return B.cap(level()); }
+  size_t stride() const { return (size_t)(level() + 1) * (cap_sel() + 1); }
+};
+
+int orc_stepper_create(const orc_opts *opts, const orc_items *items, orc_stepper **out) {
+  if (!opts || !items || !out) return -1;
+  if (opts->M == 0 || opts->M0 < opts->M || opts->batch_max == 0) return -2;
+  auto s = std::make_unique<orc_stepper>();
+  build_prepare(s->B, opts, items, s->ord);
+  s->scratch.resize(std::max(1, opts->threads));
+  *out = s.release();
+  return 0;
+}
+void orc_stepper_free(orc_stepper *s) { delete s; }
+
+int orc_stepper_next_batch(orc_stepper *s, orc_batch *out) {
+  if (!s || !out) return -1;
+  if (s->cnt) return -3; /* previous batch not applied */
+  memset(out, 0, sizeof *out);
+  if (s->pos >= s->ord.size()) return 0;
+  s->cnt = batch_count(&s->B.o, s->ord, s->pos, s->n_done);
+  out->first = s->pos;
+  out->count = (uint32_t)s->cnt;
+  out->level = s->level();
+  out->sel_stride_u64 = (uint32_t)s->stride();
+  return 0;
+}
+int orc_stepper_members(const orc_stepper *s, uint32_t *out_slots) {
+  if (!s || !s->cnt || !out_slots) return -1;
+  for (size_t i = 0; i < s->cnt; i++) out_slots[i] = s->ord[s->pos + i].first;
+  return 0;
+}
+
+int orc_stepper_search(orc_stepper *s, uint64_t *out_sel) {
+  if (!s || !s->cnt || !out_sel) return -1;
+  std::vector<Selection> sels;
+  batch_search(s->B, s->ord, s->pos, s->cnt, s->scratch, sels);
+  const uint32_t L = s->level(), cs = s->cap_sel();
+  for (size_t m = 0; m < s->cnt; m++)
+    for (uint32_t li = 0; li <= L; li++) {
+      const std::vector<Link> &v = sels[m].per_layer[L - li];
+      uint64_t *row = out_sel + m * s->stride() + (size_t)li * (cs + 1);
+      row[0] = v.size(); /* <= cs: robust_prune stops at cap(level) */
+      for (size_t k = 0; k < v.size(); k++) row[1 + k] = link_key(v[k]);
+    }
+  return 0;
+}
+
+int orc_stepper_apply(orc_stepper *s, const uint64_t *sel) {
+  if (!s || !s->cnt || !sel) return -1;
+  const uint32_t L = s->level(), cs = s->cap_sel();
+  std::vector<Selection> sels(s->cnt);
+  for (size_t m = 0; m < s->cnt; m++) {
+    sels[m].per_layer.assign(L + 1, {});
+    for (uint32_t li = 0; li <= L; li++) {
+      const uint64_t *row = sel + m * s->stride() + (size_t)li * (cs + 1);
+      if (row[0] > cs) return -4;
+      for (uint64_t k = 0; k < row[0]; k++) {
+        const uint32_t bits = (uint32_t)(row[1 + k] >> 32), id = (uint32_t)row[1 + k];
+        if (id >= s->B.n) return -4;
+        Link l;
+        memcpy(&l.d, &bits, 4);
+        l.id = id;
+        sels[m].per_layer[L - li].push_back(l);
+      }
+    }
+  }
+  s->full.clear();
+  batch_apply(s->B, s->ord, s->pos, s->cnt, sels, (int)s->scratch.size(), s->evals, s->links, &s->full);
+  std::sort(s->full.begin(), s->full.end());
+  s->full.erase(std::unique(s->full.begin(), s->full.end()), s->full.end());
+  s->n_done += s->cnt;
+  s->pos += s->cnt;
+  s->cnt = 0;
+  return 0;
+}
+uint64_t orc_stepper_n_full(const orc_stepper *s) { return s->full.size(); }
+void orc_stepper_full(const orc_stepper *s, uint64_t *out) { std::copy(s->full.begin(), s->full.end(), out); }
+
+int64_t orc_stepper_list(orc_stepper *s, uint32_t layer, uint32_t slot, uint32_t *out_slots, uint32_t *out_dist_bits,
+                         uint32_t cap) {
+  if (!s || slot >= s->B.n) return -1;
+  NodeList *nl = s->B.list(layer, slot);
+  if (!nl) return -1;
+  for (size_t k = 0; k < nl->links.size() && k < cap; k++) {
+    out_slots[k] = nl->links[k].id;
+    out_dist_bits[k] = f32_bits(nl->links[k].d);
+  }
+  return (int64_t)nl->links.size();
+}
+
+int orc_stepper_prunes_to_itself(orc_stepper *s, uint32_t layer, uint32_t slot) {
+  if (!s || slot >= s->B.n) return -1;
+  NodeList *nl = s->B.list(layer, slot);
+  if (!nl) return -1;
+  const uint32_t cap = s->B.cap(layer);
+  if (nl->links.size() < cap) return 0;
+  std::vector<Link> kept;
+  uint64_t evals = 0; /* a question, not a step of the build: not counted */
+  robust_prune(s->B, nl->links, cap, evals, kept);
+  return kept.size() == nl->links.size();
+}
+
+int orc_stepper_finish(orc_stepper *s, orc_graph **out) {
+  if (!s || !out) return -1;
+  if (s->cnt || s->pos < s->ord.size()) return -3;
+  *out = build_export(s->B, s->scratch, s->evals, s->links);
   return 0;
 }
 

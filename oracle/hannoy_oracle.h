@@ -133,6 +133,44 @@ void orc_rust_sort_levels(uint32_t *ids, uint32_t *levels, uint64_t n);
 int orc_build(const orc_opts *opts, const orc_items *items, orc_graph **out);
 void orc_graph_free(orc_graph *g);
 
+/* ---- orc_build of a fresh index in steps: one batch of the batch-synchronous schedule at a time, its search half
+ * and its link half apart, with the selections passing through the caller.  The halves are the functions orc_build
+ * runs (run_schedule's batch branch), so stepping every batch with the stepper's own search + apply IS orc_build
+ * (tests/test_oracle_stepper.py).  batch_max > 0; every other option as for orc_build.  `items` must outlive the
+ * stepper.  Slots are dense item indices (position in items->ids), as in the product's selection buffers.
+ *
+ * Selection buffer (the product's device layout, hny_builder_search): count * sel_stride_u64 u64 words, row m =
+ * member m in batch order; inside a row, layer index li = level - layer takes cap(level) + 1 words: word 0 the
+ * count, then count words (f32 bits of the distance << 32) | slot in selection order. ---- */
+typedef struct orc_stepper orc_stepper;
+typedef struct {
+  uint64_t first;          /* index of the batch's first member in insertion order */
+  uint32_t count;          /* 0 = every item inserted */
+  uint32_t level;          /* shared by every member */
+  uint32_t sel_stride_u64; /* (level + 1) * (cap(level) + 1) */
+} orc_batch;
+int orc_stepper_create(const orc_opts *opts, const orc_items *items, orc_stepper **out);
+void orc_stepper_free(orc_stepper *s);
+int orc_stepper_next_batch(orc_stepper *s, orc_batch *out);
+/* the open batch's member slots in batch order (count of them) */
+int orc_stepper_members(const orc_stepper *s, uint32_t *out_slots);
+/* insert_search of every member against the frozen graph; words past a count are left as given */
+int orc_stepper_search(orc_stepper *s, uint64_t *out_sel);
+/* registers the members and runs insert_apply in batch order from ANY selection buffer in the layout above (-4: a
+ * count beyond cap(level) or a slot beyond n), and closes the batch */
+int orc_stepper_apply(orc_stepper *s, const uint64_t *sel);
+/* the targets (layer << 32 | slot, ascending, unique) for which some add_link of the last apply met a full list */
+uint64_t orc_stepper_n_full(const orc_stepper *s);
+void orc_stepper_full(const orc_stepper *s, uint64_t *out);
+/* the raw list of (layer, slot) in stored order: returns its length (at most cap entries are written), -1 if the
+ * slot has no list on that layer */
+int64_t orc_stepper_list(orc_stepper *s, uint32_t layer, uint32_t slot, uint32_t *out_slots, uint32_t *out_dist_bits,
+                         uint32_t cap);
+/* 1 if the list is full and robust_prune of it keeps every entry, else 0 (-1: no such list) */
+int orc_stepper_prunes_to_itself(orc_stepper *s, uint32_t layer, uint32_t slot);
+/* after the last batch: the graph orc_build returns (-3 while items remain) */
+int orc_stepper_finish(orc_stepper *s, orc_graph **out);
+
 /* ---- incremental build (hnsw.rs:122-216 on a non-empty DB: prepare_levels_and_entry_points
  * :236-289 deletion branch, get_neighbours :438-441 on-disk links, fill_gaps_from_deleted :334-415,
  * Writer::build set algebra writer.rs:539-554 + delete_links_from_db :692-718).  `items` = every

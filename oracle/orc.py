@@ -361,6 +361,116 @@ def build(ds, **kw):
     return g
 
 
+class StepBatch(C.Structure):
+    _fields_ = [("first", C.c_uint64), ("count", C.c_uint32), ("level", C.c_uint32), ("sel_stride_u64", C.c_uint32)]
+
+
+class Stepper:
+    """orc_stepper: orc_build of a fresh index one batch half at a time (hannoy_oracle.h).  Selections are uint64 arrays
+    of count * sel_stride_u64 words in the product's device layout; slots are indices into ds.ids."""
+
+    def __init__(self, ds, **kw):
+        L = lib()
+        L.orc_stepper_create.restype = C.c_int
+        L.orc_stepper_create.argtypes = [C.POINTER(Opts), C.POINTER(Items), C.POINTER(C.c_void_p)]
+        L.orc_stepper_free.argtypes = [C.c_void_p]
+        L.orc_stepper_next_batch.argtypes = [C.c_void_p, C.POINTER(StepBatch)]
+        for name in ("orc_stepper_members", "orc_stepper_search", "orc_stepper_apply", "orc_stepper_full"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
+        L.orc_stepper_n_full.restype = C.c_uint64
+        L.orc_stepper_n_full.argtypes = [C.c_void_p]
+        L.orc_stepper_list.restype = C.c_int64
+        L.orc_stepper_list.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
+        L.orc_stepper_prunes_to_itself.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+        L.orc_stepper_finish.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        self.ds = ds  # the stepper reads the dataset's arrays until it is freed
+        self.opts = make_opts(ds.metric, ds.dim, **kw)
+        self._it = ds.items_struct()
+        self._h = C.c_void_p()
+        rc = L.orc_stepper_create(C.byref(self.opts), C.byref(self._it), C.byref(self._h))
+        if rc != 0:
+            raise RuntimeError(f"orc_stepper_create failed: {rc}")
+        self.batch = None
+
+    def _ok(self, rc, what):
+        if rc != 0:
+            raise RuntimeError(f"orc_stepper_{what} failed: {rc}")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().orc_stepper_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def cap(self, layer_or_level):
+        return self.opts.M0 if layer_or_level == 0 else self.opts.M
+
+    def next_batch(self):
+        """the next batch (count == 0: none left), with .slots = its member slots in batch order"""
+        b = StepBatch()
+        self._ok(lib().orc_stepper_next_batch(self._h, C.byref(b)), "next_batch")
+        b.slots = np.zeros(b.count, np.uint32)
+        if b.count:
+            self._ok(lib().orc_stepper_members(self._h, _p(b.slots)), "members")
+        self.batch = b
+        return b
+
+    def search(self, out_sel=None):
+        """selections of the open batch, written into out_sel (words past a count are left as given)"""
+        b = self.batch
+        if out_sel is None:
+            out_sel = np.zeros(b.count * b.sel_stride_u64, np.uint64)
+        assert out_sel.dtype == np.uint64 and out_sel.flags.c_contiguous and out_sel.size == b.count * b.sel_stride_u64
+        self._ok(lib().orc_stepper_search(self._h, _p(out_sel)), "search")
+        return out_sel
+
+    def apply(self, sel):
+        """add_link for every selected pair of `sel`, in batch order; returns the (layer, slot) targets for which
+        some add_link met a full list, as an int64 array [k, 2] ascending"""
+        b = self.batch
+        sel = np.ascontiguousarray(sel, np.uint64)
+        assert sel.size == b.count * b.sel_stride_u64
+        self._ok(lib().orc_stepper_apply(self._h, _p(sel)), "apply")
+        full = np.zeros(lib().orc_stepper_n_full(self._h), np.uint64)
+        if len(full):
+            lib().orc_stepper_full(self._h, _p(full))
+        return np.stack([full >> np.uint64(32), full & np.uint64(0xFFFFFFFF)], axis=1).astype(np.int64)
+
+    def list(self, layer, slot):
+        """raw list of (layer, slot) in stored order: (slots uint32, distance bits uint32)"""
+        cap = self.cap(layer)
+        ids, bits = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)
+        n = lib().orc_stepper_list(self._h, layer, slot, _p(ids), _p(bits), cap)
+        if n < 0:
+            raise KeyError((layer, slot))
+        assert n <= cap
+        return ids[:n], bits[:n]
+
+    def prunes_to_itself(self, layer, slot):
+        r = lib().orc_stepper_prunes_to_itself(self._h, layer, slot)
+        if r < 0:
+            raise KeyError((layer, slot))
+        return bool(r)
+
+    def finish(self):
+        h = C.c_void_p()
+        self._ok(lib().orc_stepper_finish(self._h, C.byref(h)), "finish")
+        g = Graph(h)
+        g.opts = self.opts
+        return g
+
+
 def build_incremental(ds, prev, to_insert, insert_levels, to_delete, **kw):
     """ds: items that exist after the update; prev: graph of the previous build."""
     o = make_opts(ds.metric, ds.dim, **kw)
