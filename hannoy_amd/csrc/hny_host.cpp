@@ -8,6 +8,7 @@
 
 #include <malloc.h>
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <mutex>
 #include <chrono>
@@ -19,8 +20,11 @@
 #include <functional>
 #include <iterator>
 #include <memory>
+#include <numeric>
 #include <string>
 #include <thread>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 namespace {
@@ -302,6 +306,29 @@ struct IngestPipe {
   }
 };
 
+// the four large arrays of an hny_graph, as the prefault, the cache and finish() name them
+enum ExportArray { XA_REC_ITEM, XA_REC_LAYER, XA_REC_OFFSET, XA_NEIGHBOURS, XA_COUNT };
+// their sizes in bytes for `nrec` records that hold `nlinks` links (bounds when prepared, actual counts in finish())
+std::array<size_t, XA_COUNT> export_bytes(uint64_t nrec, uint64_t nlinks) {
+  return {(size_t)std::max<uint64_t>(nrec, 1) * 4, (size_t)std::max<uint64_t>(nrec, 1), (size_t)(nrec + 1) * 8,
+          (size_t)std::max<uint64_t>(nlinks, 1) * 4};
+}
+// one malloc'ed array and its capacity per ExportArray: what a builder has prepared, what the cache holds
+struct ExportSlots {
+  void *p[XA_COUNT] = {};
+  size_t cap[XA_COUNT] = {};
+  bool holds(int i, size_t bytes) const { return p[i] && cap[i] >= bytes; }
+  void *take(int i) { cap[i] = 0; return std::exchange(p[i], nullptr); }
+  void put(int i, void *q, size_t c) { // (frees what the slot held)
+    free(p[i]);
+    p[i] = q;
+    cap[i] = q ? c : 0;
+  }
+  void drop_all() {
+    for (int i = 0; i < XA_COUNT; i++) put(i, nullptr, 0);
+  }
+};
+
 } // namespace
 
 struct hny_builder {
@@ -364,22 +391,17 @@ struct hny_builder {
   // the four large arrays of the hny_graph this build will export, allocated and touched page by page on a helper
   // thread WHILE the device builds (the host is idle then): finish() would otherwise pay the first touch of up to
   // 1.3 GB of fresh pages (C4: 45 ms, C5: 25 ms of the step).  Owned by the builder until finish() hands them to
-  // the graph; hny_graph_free frees them plainly (rounds 3-4 kept them in a process-wide cache instead, which
-  // only helped the second build of a loop and held ~1.3 GB for the life of the process).
-  struct ExportBufs {
-    void *p[4] = {nullptr, nullptr, nullptr, nullptr};
-    size_t cap[4] = {0, 0, 0, 0};
+  // the graph (indexed by ExportArray).  hny_graph_free frees them, unless the caller has asked for the opt-in
+  // cache of released arrays (hny_set_graph_cache, off by default): then it keeps them for the next export, and
+  // start_export_prefault / take_export_buf look there before they allocate.
+  struct ExportBufs : ExportSlots {
     std::thread th;
     void join() {
       if (th.joinable()) th.join();
     }
     void drop() {
       join();
-      for (int i = 0; i < 4; i++) {
-        free(p[i]);
-        p[i] = nullptr;
-        cap[i] = 0;
-      }
+      drop_all();
     }
     ~ExportBufs() { drop(); }
   } xbuf;
@@ -633,20 +655,35 @@ int upload_rows(const void *vectors, size_t stride, size_t vbytes, uint64_t n, u
   return HNY_OK;
 }
 
-// fn(lo, hi) over [0, n) on up to nt threads (the calling thread takes the first share).  A thread that cannot
-// be created costs parallelism, not the call: its share runs on the calling thread, and nothing is thrown.
+// share t of nt of [0, n): the one split of work over host threads (run_split, and the pieces finish() downloads
+// the layer-0 lists in, which must cover whole shares)
+struct Share {
+  uint64_t lo, hi;
+};
+inline Share share_of(uint64_t n, unsigned t, unsigned nt) { return {n * t / nt, n * (t + 1) / nt}; }
+
+// fn(lo, hi) or fn(share, lo, hi) over [0, n) on up to nt threads (the calling thread takes the first share).  A
+// thread that cannot be created costs parallelism, not the call: its share runs on the calling thread, under its
+// own index, and nothing is thrown.
 template <class F>
 void run_split(unsigned nt, uint64_t n, F fn) {
   nt = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(nt, n));
+  auto run = [&fn, n, nt](unsigned t) {
+    const Share r = share_of(n, t, nt);
+    if constexpr (std::is_invocable_v<F &, unsigned, uint64_t, uint64_t>)
+      fn(t, r.lo, r.hi);
+    else
+      fn(r.lo, r.hi);
+  };
   std::vector<std::thread> th;
   unsigned started = 1;
   try {
     th.reserve(nt);
-    for (; started < nt; started++) th.emplace_back(fn, n * started / nt, n * (started + 1) / nt);
+    for (; started < nt; started++) th.emplace_back(run, started);
   } catch (...) {
   }
-  fn(0, n / nt);
-  if (started < nt) fn(n * started / nt, n);
+  run(0);
+  for (unsigned t = started; t < nt; t++) run(t);
   for (auto &t : th) t.join();
 }
 
@@ -799,6 +836,21 @@ size_t group_end(const hny_builder *b, size_t pos) {
   size_t e = pos;
   while (e < b->order.size() && b->order_level[e] == b->order_level[pos]) e++;
   return e;
+}
+
+// which (slot, layer) records a builder's finish() exports: bit l = layer l
+inline uint32_t rec_mask_of(const hny_builder *b, uint32_t s) {
+  if (b->deleted[s]) return 0u;
+  uint32_t m = b->old_mask[s];
+  if (b->ins_level[s] >= 0) m |= (2u << b->ins_level[s]) - 1u;
+  return m;
+}
+// the records slot `s` owns, lowest layer first: fn(layer, list) with `list` the index of the record's list — the
+// slot on layer 0, an index into the upper-layer arrays (counts: h_cntu, ids: h_up) above it
+template <class F>
+inline void for_each_record(const hny_builder *b, uint32_t s, F &&fn) {
+  for (uint32_t m = rec_mask_of(b, s), l = 0; m; m >>= 1, l++)
+    if (m & 1) fn(l, l == 0 ? (size_t)s : (size_t)b->upper_idx[s] * b->up_layers + (l - 1));
 }
 
 } // namespace
@@ -978,13 +1030,6 @@ struct IncrementalSpec {
   bool rows_only = false;
 };
 
-// which (slot, layer) records a builder's finish() exports: bit l = layer l
-static inline uint32_t rec_mask_of(const hny_builder *b, uint32_t s) {
-  if (b->deleted[s]) return 0u;
-  uint32_t m = b->old_mask[s];
-  if (b->ins_level[s] >= 0) m |= (2u << b->ins_level[s]) - 1u;
-  return m;
-}
 // every list sorted and deduplicated, once per build (finish, the searches and a successor's move read them so);
 // enqueued on `st`
 static int ensure_finalized(hny_builder *b, hipStream_t st) {
@@ -2343,32 +2388,18 @@ static int device_error_words(hny_builder *b, const u64 *stats) {
 // (hny_set_graph_cache): a service that rebuilds in a loop saves the munmap of the old arrays and the first touch of
 // the new ones (C4: 1.4 GB each way, ~100 ms per build); anybody else gets plain malloc / free and holds nothing.
 namespace {
-struct GraphBufCache {
+struct GraphBufCache : ExportSlots {
   std::mutex mu;
   size_t limit = 0; // bytes the cache may hold; 0 = off
-  void *p[4] = {nullptr, nullptr, nullptr, nullptr};
-  size_t cap[4] = {0, 0, 0, 0};
-  size_t held() const { return cap[0] + cap[1] + cap[2] + cap[3]; }
-  void drop_all() {
-    for (int i = 0; i < 4; i++) {
-      free(p[i]);
-      p[i] = nullptr;
-      cap[i] = 0;
-    }
-  }
+  size_t held() const { return std::accumulate(cap, cap + XA_COUNT, (size_t)0); }
   ~GraphBufCache() { drop_all(); }
 } g_gcache;
 // a cached array of at least `bytes` (and not more than twice that), or null
 void *gcache_take(int slot, size_t bytes, size_t *cap_out) {
   std::lock_guard<std::mutex> lk(g_gcache.mu);
-  if (g_gcache.p[slot] && g_gcache.cap[slot] >= bytes && g_gcache.cap[slot] / 2 <= bytes + ((size_t)1 << 20)) {
-    void *q = g_gcache.p[slot];
-    *cap_out = g_gcache.cap[slot];
-    g_gcache.p[slot] = nullptr;
-    g_gcache.cap[slot] = 0;
-    return q;
-  }
-  return nullptr;
+  if (!g_gcache.holds(slot, bytes) || g_gcache.cap[slot] / 2 > bytes + ((size_t)1 << 20)) return nullptr;
+  *cap_out = g_gcache.cap[slot];
+  return g_gcache.take(slot);
 }
 void gcache_release(int slot, void *q) {
   if (!q) return;
@@ -2398,43 +2429,33 @@ void hny_set_graph_cache(size_t max_bytes) {
 static void start_export_prefault(hny_builder *b) {
   if (!b->will_export) return;
   b->xbuf.join();
-  const size_t want[4] = {(size_t)std::max<uint64_t>(b->nrec_bound, 1) * 4, (size_t)std::max<uint64_t>(b->nrec_bound, 1),
-                          (size_t)(b->nrec_bound + 1) * 8, (size_t)std::max<uint64_t>(b->nbr_bound, 1) * 4};
-  if (want[0] + want[1] + want[2] + want[3] < ((size_t)8 << 20)) return; // small: finish() allocates
+  const auto want = export_bytes(b->nrec_bound, b->nbr_bound);
+  if (std::accumulate(want.begin(), want.end(), (size_t)0) < ((size_t)8 << 20)) return; // small: finish() allocates
+  auto *x = &b->xbuf;
   bool have = true;
-  for (int i = 0; i < 4; i++) {
-    if (!(b->xbuf.p[i] && b->xbuf.cap[i] >= want[i])) { // (else: a build reset before its finish() left it here)
-      size_t cap = 0;
-      if (void *q = gcache_take(i, want[i], &cap)) { // released by an earlier graph: allocated and touched already
-        free(b->xbuf.p[i]);
-        b->xbuf.p[i] = q;
-        b->xbuf.cap[i] = cap;
-      }
-    }
-    have = have && b->xbuf.p[i] && b->xbuf.cap[i] >= want[i];
+  for (int i = 0; i < XA_COUNT; i++) {
+    size_t cap = 0;
+    if (!x->holds(i, want[i])) // (else: a build reset before its finish() left it here)
+      if (void *q = gcache_take(i, want[i], &cap)) x->put(i, q, cap); // released by an earlier graph: touched already
+    have = have && x->holds(i, want[i]);
   }
   if (have) return;
-  auto *x = &b->xbuf;
-  x->th = std::thread([x, want]() {
-    for (int i = 0; i < 4; i++) {
-      if (x->p[i] && x->cap[i] >= want[i]) continue;
-      free(x->p[i]);
-      x->p[i] = malloc(want[i]);
-      x->cap[i] = x->p[i] ? want[i] : 0;
-      volatile unsigned char *q = (volatile unsigned char *)x->p[i];
-      for (size_t o = 0; q && o < want[i]; o += 4096) q[o] = 0;
-    }
-  });
+  try {
+    x->th = std::thread([x, want]() {
+      for (int i = 0; i < XA_COUNT; i++) {
+        if (x->holds(i, want[i])) continue;
+        x->put(i, malloc(want[i]), want[i]);
+        volatile unsigned char *q = (volatile unsigned char *)x->p[i];
+        for (size_t o = 0; q && o < want[i]; o += 4096) q[o] = 0;
+      }
+    });
+  } catch (...) { // no helper thread (nothing is thrown across the C ABI): finish() allocates
+  }
 }
 // one export array: the prepared one when it is large enough, else a fresh allocation
 static void *take_export_buf(hny_builder *b, int slot, size_t bytes) {
   b->xbuf.join();
-  if (b->xbuf.p[slot] && b->xbuf.cap[slot] >= bytes) {
-    void *q = b->xbuf.p[slot];
-    b->xbuf.p[slot] = nullptr;
-    b->xbuf.cap[slot] = 0;
-    return q;
-  }
+  if (b->xbuf.holds(slot, bytes)) return b->xbuf.take(slot);
   size_t cap = 0;
   if (void *q = gcache_take(slot, bytes, &cap)) return q;
   return malloc(bytes);
@@ -2442,128 +2463,134 @@ static void *take_export_buf(hny_builder *b, int slot, size_t bytes) {
 
 void hny_graph_free(hny_graph *g) {
   if (!g) return;
-  gcache_release(0, (void *)g->rec_item);
-  gcache_release(1, (void *)g->rec_layer);
-  gcache_release(2, (void *)g->rec_offset);
-  gcache_release(3, (void *)g->neighbours);
+  gcache_release(XA_REC_ITEM, (void *)g->rec_item);
+  gcache_release(XA_REC_LAYER, (void *)g->rec_layer);
+  gcache_release(XA_REC_OFFSET, (void *)g->rec_offset);
+  gcache_release(XA_NEIGHBOURS, (void *)g->neighbours);
   free((void *)g->entry_points);
   free(g);
 }
 
-// the write loop's input (hnsw.rs:191-213): one record per (item, layer), ids deduplicated
-int hny_builder_finish(hny_builder *b, hny_graph **out) {
-  if (!b || !out) return fail(HNY_ERR_INVALID_ARG, "null argument");
-  *out = nullptr;
-  if (b->pos < b->order.size() || b->in_batch) return fail(HNY_ERR_INVALID_ARG, "build not finished");
+// What finish() and finish_delta() begin with, after their own argument checks: the build has ended on the device
+// (*t0: the export's clock starts here), its error words are clean and every list is finalised (enqueued).
+static int export_begin(hny_builder *b, u64 (&stats)[ST_COUNT], double *t0) {
   HIP_TRY(hipSetDevice(b->device));
   HIP_TRY(hipStreamSynchronize(b->stream));
-  b->t_build = now_s() - b->t_build0;
-  double t0 = now_s();
-  const uint32_t n = b->n, M = b->o.M, M0 = b->o.M0, ml = b->max_level;
-  u64 stats[ST_COUNT] = {0};
+  *t0 = now_s();
   HIP_TRY(hipMemcpy(stats, b->d_stats.p, sizeof stats, hipMemcpyDeviceToHost));
   if (int rc = device_error_words(b, stats)) return rc;
-  // finalise every list on the device (sort + dedup), then copy through pinned staging
-  const uint32_t upl = b->up_layers;
-  const size_t nup = (size_t)b->n_upper * upl;
-  if (int rc = ensure_finalized(b, b->stream)) return rc;
-  // the counts first (small), then the lists (128 MB at C2): the record offsets are computed on the
-  // host while the lists are still in flight
+  return ensure_finalized(b, b->stream); // finalise every list on the device (sort + dedup)
+}
+// ... and how both go on: the finalised count of every list, enqueued behind export_begin (finish_delta's diff goes
+// between the two).  Not waited for here: finish() records an event and goes on, finish_delta synchronises.
+static int enqueue_count_downloads(hny_builder *b) {
+  const size_t n = b->n, nup = (size_t)b->n_upper * b->up_layers;
   if (n) HIP_TRY(hipMemcpyAsync(b->h_cnt0, b->d_fin_cnt0.p, (size_t)n * 4, hipMemcpyDeviceToHost, b->stream));
   if (nup) HIP_TRY(hipMemcpyAsync(b->h_cntu, b->d_fin_cntu.p, nup * 4, hipMemcpyDeviceToHost, b->stream));
-  hipEvent_t ev_counts;
-  HIP_TRY(next_sync_event(b, &ev_counts));
-  HIP_TRY(hipEventRecord(ev_counts, b->stream));
-  // The layer-0 lists travel in as many pieces as the host has compaction threads (the same slot ranges), an
-  // event behind each: thread t compacts its range as soon as ITS piece has landed, while the later pieces are
-  // still on the bus — the export costs the transfer plus one piece's compaction instead of their sum (C4: 1.28 GB
-  // down at ~30 GB/s, 0.84 GB compacted: 54 -> 44 ms; C5 29 -> 23 ms).  The small upper-layer lists go first.
-  unsigned nt = std::max(1u, std::min(64u, std::thread::hardware_concurrency() / 2));
-  if (n < 10000) nt = 1;
+  return HNY_OK;
+}
+// the downloaded count of a record's list (`list` as for_each_record gives it)
+static inline uint32_t list_count(const hny_builder *b, uint32_t l, size_t list) {
+  return l == 0 ? b->h_cnt0[list] : b->h_cntu[list];
+}
+// the entry points as item ids (the builder keeps slots): a malloc'ed array, never of size 0
+static uint32_t *entry_point_ids(const hny_builder *b) {
+  uint32_t *eps = (uint32_t *)malloc(std::max<size_t>(b->entry_points.size(), 1) * 4);
+  for (size_t i = 0; eps && i < b->entry_points.size(); i++) eps[i] = b->ids[b->entry_points[i]];
+  return eps;
+}
+
+// host threads (shares of the slots, share_of) of a finish(): half the hardware threads, at most 64
+static unsigned export_shares(uint32_t n) {
+  return n < 10000 ? 1u : std::max(1u, std::min(64u, std::thread::hardware_concurrency() / 2));
+}
+static int record_sync_event(hny_builder *b, hipEvent_t *ev) {
+  HIP_TRY(next_sync_event(b, ev));
+  HIP_TRY(hipEventRecord(*ev, b->stream));
+  return HNY_OK;
+}
+struct ExportEvents {
+  hipEvent_t counts = nullptr, up = nullptr; // the counts / the upper-layer lists have landed
+  std::vector<hipEvent_t> l0;                // [share]: the piece of the layer-0 lists that covers it has landed
+};
+// finish(), step 1: every download, enqueued.  The counts first (small), then the lists (128 MB at C2): the record
+// offsets are computed on the host while the lists are still in flight.
+// The layer-0 lists travel in pieces that cover whole shares of the `nt` compaction threads, an event behind each:
+// share t compacts its range as soon as ITS piece has landed, while the later pieces are still on the bus — the
+// export costs the transfer plus one piece's compaction instead of their sum (C4: 1.28 GB down at ~30 GB/s,
+// 0.84 GB compacted: 54 -> 44 ms; C5 29 -> 23 ms).  The small upper-layer lists go first.
+static int enqueue_export_downloads(hny_builder *b, unsigned nt, ExportEvents *ev) {
+  const uint32_t n = b->n, M = b->o.M, M0 = b->o.M0;
+  const size_t nup = (size_t)b->n_upper * b->up_layers;
+  if (int rc = enqueue_count_downloads(b)) return rc;
+  if (int rc = record_sync_event(b, &ev->counts)) return rc;
   if (nup) HIP_TRY(hipMemcpyAsync(b->h_up, b->d_up_ids.p, nup * M * 4, hipMemcpyDeviceToHost, b->stream));
-  hipEvent_t up_landed;
-  HIP_TRY(next_sync_event(b, &up_landed));
-  HIP_TRY(hipEventRecord(up_landed, b->stream));
+  if (int rc = record_sync_event(b, &ev->up)) return rc;
   // (pieces of at least 16 MB: C2's 128 MB go in 8, not in 64 — a piece costs a copy command and an event.  The
   // download itself runs at ~30 GB/s on these boxes whether one stream or two alternate on the pieces — measured.)
-  std::vector<hipEvent_t> l0_landed(nt, nullptr);
-  {
-    const unsigned pieces = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(nt, (uint64_t)n * M0 * 4 / ((uint64_t)16 << 20)));
-    for (unsigned c = 0; c < pieces && n; c++) {
-      const unsigned t0 = (unsigned)((uint64_t)c * nt / pieces), t1 = (unsigned)((uint64_t)(c + 1) * nt / pieces); // threads of the piece
-      const size_t lo = (size_t)((uint64_t)n * t0 / nt), hi = (size_t)((uint64_t)n * t1 / nt);
-      if (hi > lo)
-        HIP_TRY(hipMemcpyAsync(b->h_l0 + lo * M0, b->d_l0_ids.p + lo * M0, (hi - lo) * M0 * 4, hipMemcpyDeviceToHost, b->stream));
-      hipEvent_t ev;
-      HIP_TRY(next_sync_event(b, &ev));
-      HIP_TRY(hipEventRecord(ev, b->stream));
-      for (unsigned t = t0; t < t1; t++) l0_landed[t] = ev;
-    }
+  ev->l0.assign(nt, nullptr);
+  const unsigned pieces = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(nt, (uint64_t)n * M0 * 4 / ((uint64_t)16 << 20)));
+  for (unsigned c = 0; c < pieces && n; c++) {
+    const Share ts = share_of(nt, c, pieces); // the shares of the piece (pieces <= nt: at least one)
+    const size_t lo = (size_t)share_of(n, (unsigned)ts.lo, nt).lo, hi = (size_t)share_of(n, (unsigned)ts.hi - 1, nt).hi;
+    if (hi > lo)
+      HIP_TRY(hipMemcpyAsync(b->h_l0 + lo * M0, b->d_l0_ids.p + lo * M0, (hi - lo) * M0 * 4, hipMemcpyDeviceToHost, b->stream));
+    hipEvent_t landed;
+    if (int rc = record_sync_event(b, &landed)) return rc;
+    std::fill(ev->l0.begin() + ts.lo, ev->l0.begin() + ts.hi, landed);
   }
-  const u32 *l0 = b->h_l0, *up = b->h_up;
+  return HNY_OK;
+}
 
-  // every inserted item owns a (possibly empty) record on layers 0..=level (add_in_layers_below,
-  // hnsw.rs:419-424); after an incremental build every surviving old record is rewritten too
-  // (fill_gaps_from_deleted puts it in memory, :398/:410) and deleted items own nothing
-  // (delete_links_from_db, writer.rs:692-718).  Which records exist never changes during a builder's
-  // life: the record table (first record of every slot, item id and layer of every record) is
-  // computed once and reused by every finish().
-  auto rec_mask = [&](uint32_t s) -> uint32_t { return rec_mask_of(b, s); };
-  auto parallel = [&](auto &&fn) { // fn(thread, lo, hi) over the slots
-    std::vector<std::thread> th;
-    for (unsigned t = 1; t < nt; t++)
-      th.emplace_back(fn, t, (uint32_t)((uint64_t)n * t / nt), (uint32_t)((uint64_t)n * (t + 1) / nt));
-    fn(0u, 0u, (uint32_t)((uint64_t)n / nt));
-    for (auto &t : th) t.join();
-  };
-  if (b->rec_first.size() != (size_t)n + 1) {
-    b->rec_first.assign((size_t)n + 1, 0);
-    for (uint32_t s = 0; s < n; s++) b->rec_first[s + 1] = b->rec_first[s] + (uint32_t)__builtin_popcount(rec_mask(s));
-    const uint64_t nr = b->rec_first[n];
-    b->rec_item_t.resize(nr);
-    b->rec_layer_t.resize(nr);
-    parallel([&](unsigned, uint32_t lo, uint32_t hi) {
-      for (uint32_t s = lo; s < hi; s++) {
-        uint64_t r = b->rec_first[s];
-        for (uint32_t m = rec_mask(s), l = 0; m; m >>= 1, l++)
-          if (m & 1) {
-            b->rec_item_t[r] = b->ids[s];
-            b->rec_layer_t[r] = (uint8_t)l;
-            r++;
-          }
-      }
-    });
-  }
+// finish(), step 2: the record table (first record of every slot, item id and layer of every record).
+// Every inserted item owns a (possibly empty) record on layers 0..=level (add_in_layers_below,
+// hnsw.rs:419-424); after an incremental build every surviving old record is rewritten too
+// (fill_gaps_from_deleted puts it in memory, :398/:410) and deleted items own nothing
+// (delete_links_from_db, writer.rs:692-718).  Which records exist never changes during a builder's
+// life: the table is computed once and reused by every finish().
+static void ensure_record_table(hny_builder *b, unsigned nt) {
+  const uint32_t n = b->n;
+  if (b->rec_first.size() == (size_t)n + 1) return;
+  b->rec_first.assign((size_t)n + 1, 0);
+  for (uint32_t s = 0; s < n; s++) b->rec_first[s + 1] = b->rec_first[s] + (uint32_t)__builtin_popcount(rec_mask_of(b, s));
+  b->rec_item_t.resize(b->rec_first[n]);
+  b->rec_layer_t.resize(b->rec_first[n]);
+  run_split(nt, n, [b](uint64_t lo, uint64_t hi) {
+    for (uint32_t s = (uint32_t)lo; s < hi; s++) {
+      uint64_t r = b->rec_first[s];
+      for_each_record(b, s, [&](uint32_t l, size_t) {
+        b->rec_item_t[r] = b->ids[s];
+        b->rec_layer_t[r] = (uint8_t)l;
+        r++;
+      });
+    }
+  });
+}
+
+// finish(), step 3: the three per-record arrays of `g`.  Offsets = prefix sum over the device-computed counts, in
+// record order: per-share sums of a slot range, a scan of those, then every share fills its range (the record
+// table is copied alongside).
+static int export_records(hny_builder *b, unsigned nt, hipEvent_t counts_landed, hny_graph *g) {
   const std::vector<uint64_t> &rec_first = b->rec_first;
+  const uint32_t n = b->n;
   const uint64_t nrec = rec_first[n];
-  // the graph owns its arrays from the start, so that every error return below frees them
-  std::unique_ptr<hny_graph, void (*)(hny_graph *)> gh((hny_graph *)calloc(1, sizeof(hny_graph)), hny_graph_free);
-  hny_graph *g = gh.get();
-  uint32_t *rec_item = (uint32_t *)take_export_buf(b, 0, std::max<uint64_t>(nrec, 1) * 4);
-  uint8_t *rec_layer = (uint8_t *)take_export_buf(b, 1, std::max<uint64_t>(nrec, 1));
-  uint64_t *rec_off = (uint64_t *)take_export_buf(b, 2, (nrec + 1) * 8);
-  if (!g || !rec_item || !rec_layer || !rec_off) {
-    free(rec_item);
-    free(rec_layer);
-    free(rec_off);
-    return fail(HNY_ERR_OOM, "out of host memory for %llu records", (unsigned long long)nrec);
-  }
-  g->rec_item = rec_item;
+  const auto bytes = export_bytes(nrec, 0);
+  uint32_t *rec_item = (uint32_t *)take_export_buf(b, XA_REC_ITEM, bytes[XA_REC_ITEM]);
+  uint8_t *rec_layer = (uint8_t *)take_export_buf(b, XA_REC_LAYER, bytes[XA_REC_LAYER]);
+  uint64_t *rec_off = (uint64_t *)take_export_buf(b, XA_REC_OFFSET, bytes[XA_REC_OFFSET]);
+  g->n_records = nrec;
+  g->rec_item = rec_item; // (the graph owns its arrays from the start: every error return frees them)
   g->rec_layer = rec_layer;
   g->rec_offset = rec_off;
+  if (!rec_item || !rec_layer || !rec_off)
+    return fail(HNY_ERR_OOM, "out of host memory for %llu records", (unsigned long long)nrec);
   rec_off[0] = 0;
-  HIP_TRY(hipEventSynchronize(ev_counts));
-  // offsets = prefix sum over the device-computed counts, in record order: per-thread sums of a slot
-  // range, a scan of those, then every thread fills its range (the record table is copied alongside)
-  auto count_of = [&](uint32_t s, uint32_t l) -> uint32_t {
-    return l == 0 ? b->h_cnt0[s] : b->h_cntu[(size_t)b->upper_idx[s] * upl + (l - 1)];
-  };
+  HIP_TRY(hipEventSynchronize(counts_landed));
   std::vector<uint64_t> part(nt + 1, 0);
-  parallel([&](unsigned t, uint32_t lo, uint32_t hi) {
+  run_split(nt, n, [&](unsigned t, uint64_t lo, uint64_t hi) {
     uint64_t sum = 0;
-    for (uint32_t s = lo; s < hi; s++)
-      for (uint32_t m = rec_mask(s), l = 0; m; m >>= 1, l++)
-        if (m & 1) sum += count_of(s, l);
+    for (uint32_t s = (uint32_t)lo; s < hi; s++)
+      for_each_record(b, s, [&](uint32_t l, size_t list) { sum += list_count(b, l, list); });
     part[t + 1] = sum;
     if (hi > lo) {
       memcpy(rec_item + rec_first[lo], b->rec_item_t.data() + rec_first[lo], (rec_first[hi] - rec_first[lo]) * 4);
@@ -2571,33 +2598,37 @@ int hny_builder_finish(hny_builder *b, hny_graph **out) {
     }
   });
   for (unsigned t = 0; t < nt; t++) part[t + 1] += part[t];
-  parallel([&](unsigned t, uint32_t lo, uint32_t hi) {
+  run_split(nt, n, [&](unsigned t, uint64_t lo, uint64_t hi) {
     uint64_t off = part[t];
-    for (uint32_t s = lo; s < hi; s++) {
+    for (uint32_t s = (uint32_t)lo; s < hi; s++) {
       uint64_t r = rec_first[s];
-      for (uint32_t m = rec_mask(s), l = 0; m; m >>= 1, l++)
-        if (m & 1) {
-          off += count_of(s, l);
-          rec_off[++r] = off;
-        }
+      for_each_record(b, s, [&](uint32_t l, size_t list) {
+        off += list_count(b, l, list);
+        rec_off[++r] = off;
+      });
     }
   });
-  uint32_t *nbrs = (uint32_t *)take_export_buf(b, 3, std::max<uint64_t>(rec_off[nrec], 1) * 4);
-  if (!nbrs) return fail(HNY_ERR_OOM, "out of host memory for %llu links", (unsigned long long)rec_off[nrec]);
+  return HNY_OK;
+}
+
+// finish(), step 4: the neighbour array of `g` — every share waits for the upper-layer lists and for its own piece
+// of the layer-0 lists, then compacts its records and translates slots to item ids
+static int export_neighbours(hny_builder *b, unsigned nt, const ExportEvents &ev, hny_graph *g) {
+  const uint32_t n = b->n, M = b->o.M, M0 = b->o.M0;
+  const uint64_t *rec_off = g->rec_offset, nlinks = rec_off[g->n_records];
+  uint32_t *nbrs = (uint32_t *)take_export_buf(b, XA_NEIGHBOURS, export_bytes(g->n_records, nlinks)[XA_NEIGHBOURS]);
+  if (!nbrs) return fail(HNY_ERR_OOM, "out of host memory for %llu links", (unsigned long long)nlinks);
   g->neighbours = nbrs;
   const bool identity = !b->incremental && n && b->ids[n - 1] == n - 1; // ids 0..n-1: slot == item id
   std::atomic<int> landed_err{0};
-  parallel([&](unsigned t, uint32_t lo, uint32_t hi) {
-    // the upper-layer lists and this thread's piece of the layer-0 lists have arrived
-    if (l0_landed[t] && (hipSetDevice(b->device) != hipSuccess || hipEventSynchronize(up_landed) != hipSuccess ||
-                         hipEventSynchronize(l0_landed[t]) != hipSuccess))
+  run_split(nt, n, [&](unsigned t, uint64_t lo, uint64_t hi) {
+    if (ev.l0[t] && (hipSetDevice(b->device) != hipSuccess || hipEventSynchronize(ev.up) != hipSuccess ||
+                     hipEventSynchronize(ev.l0[t]) != hipSuccess))
       landed_err.store(1);
-    for (uint32_t s = lo; s < hi; s++) {
-      uint64_t r = rec_first[s];
-      for (uint32_t m = rec_mask(s), l = 0; m; m >>= 1, l++) {
-        if (!(m & 1)) continue;
-        const u32 *src = l == 0 ? &l0[(size_t)s * M0]
-                                : &up[((size_t)b->upper_idx[s] * upl + (l - 1)) * M];
+    for (uint32_t s = (uint32_t)lo; s < hi; s++) {
+      uint64_t r = b->rec_first[s];
+      for_each_record(b, s, [&](uint32_t l, size_t list) {
+        const u32 *src = l == 0 ? b->h_l0 + list * M0 : b->h_up + list * M;
         const uint32_t c = (uint32_t)(rec_off[r + 1] - rec_off[r]);
         uint32_t *dst = nbrs + rec_off[r];
         if (identity)
@@ -2605,17 +2636,16 @@ int hny_builder_finish(hny_builder *b, hny_graph **out) {
         else
           for (uint32_t k = 0; k < c; k++) dst[k] = b->ids[src[k]]; // slot -> item id (order kept)
         r++;
-      }
+      });
     }
   });
   HIP_TRY(hipStreamSynchronize(b->stream));
   if (landed_err.load()) return fail(HNY_ERR_NO_DEVICE, "export: waiting for the lists failed");
-  uint32_t *eps = (uint32_t *)malloc(std::max<size_t>(b->entry_points.size(), 1) * 4);
-  for (size_t i = 0; i < b->entry_points.size(); i++) eps[i] = b->ids[b->entry_points[i]];
-  g->n_records = nrec;
-  g->entry_points = eps;
-  g->n_entry_points = (uint32_t)b->entry_points.size();
-  g->max_level = ml;
+  return HNY_OK;
+}
+
+// finish(), step 5: counters, times and (when profiling) kernel times of the build; the export's clock stops here
+static void export_statistics(hny_builder *b, const u64 *stats, double t0, hny_graph *g) {
 #ifdef HNY_PHASE_CLOCKS
   fprintf(stderr, "[hny] walk wave cycles: pop %llu list+visited %llu distances %llu insert %llu | expansions %llu | whole kernel %llu\n",
           stats[ST_PH_POP], stats[ST_PH_LIST], stats[ST_PH_DIST], stats[ST_PH_INSERT], stats[ST_PH_EXPANSIONS],
@@ -2637,23 +2667,42 @@ int hny_builder_finish(hny_builder *b, hny_graph **out) {
   g->t_upload_s = b->t_upload;
   g->t_build_s = b->t_build;
   g->t_export_s = now_s() - t0;
-  if (b->profiling) {
-    double acc[EV_KINDS] = {0};
-    uint64_t cnt[EV_KINDS] = {0};
-    for (size_t i = 0; i < b->ev_used; i++) {
-      float ms = 0.f;
-      if (hipEventElapsedTime(&ms, b->evs[i].a, b->evs[i].b) == hipSuccess) {
-        acc[b->evs[i].kind] += ms * 1e-3;
-        cnt[b->evs[i].kind]++;
-      }
-    }
-    g->t_walk_kernels_s = acc[EV_WALK];
-    g->t_prune_kernels_s = acc[EV_PRUNE];
-    g->t_sort_kernels_s = acc[EV_SORT];
-    g->t_apply_kernels_s = acc[EV_APPLY];
-    (void)cnt;
-    g->n_walk_launches = b->n_walk_dispatch; // k_walk dispatches (rocprofv3 counts the same)
+  if (!b->profiling) return;
+  double acc[EV_KINDS] = {0};
+  for (size_t i = 0; i < b->ev_used; i++) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, b->evs[i].a, b->evs[i].b) == hipSuccess) acc[b->evs[i].kind] += ms * 1e-3;
   }
+  g->t_walk_kernels_s = acc[EV_WALK];
+  g->t_prune_kernels_s = acc[EV_PRUNE];
+  g->t_sort_kernels_s = acc[EV_SORT];
+  g->t_apply_kernels_s = acc[EV_APPLY];
+  g->n_walk_launches = b->n_walk_dispatch; // k_walk dispatches (rocprofv3 counts the same)
+}
+
+// the write loop's input (hnsw.rs:191-213): one record per (item, layer), ids deduplicated
+int hny_builder_finish(hny_builder *b, hny_graph **out) {
+  if (!b || !out) return fail(HNY_ERR_INVALID_ARG, "null argument");
+  *out = nullptr;
+  if (b->pos < b->order.size() || b->in_batch) return fail(HNY_ERR_INVALID_ARG, "build not finished");
+  u64 stats[ST_COUNT] = {0};
+  double t0 = 0;
+  if (int rc = export_begin(b, stats, &t0)) return rc;
+  b->t_build = t0 - b->t_build0;
+  const unsigned nt = export_shares(b->n);
+  ExportEvents ev;
+  if (int rc = enqueue_export_downloads(b, nt, &ev)) return rc;
+  ensure_record_table(b, nt);
+  std::unique_ptr<hny_graph, void (*)(hny_graph *)> gh((hny_graph *)calloc(1, sizeof(hny_graph)), hny_graph_free);
+  hny_graph *g = gh.get();
+  if (!g) return fail(HNY_ERR_OOM, "out of host memory for %llu records", (unsigned long long)b->rec_first[b->n]);
+  if (int rc = export_records(b, nt, ev.counts, g)) return rc;
+  if (int rc = export_neighbours(b, nt, ev, g)) return rc;
+  g->entry_points = entry_point_ids(b);
+  if (!g->entry_points) return fail(HNY_ERR_OOM, "out of host memory for %llu records", (unsigned long long)g->n_records);
+  g->n_entry_points = (uint32_t)b->entry_points.size();
+  g->max_level = b->max_level;
+  export_statistics(b, stats, t0, g);
   *out = gh.release();
   return HNY_OK;
 }
@@ -3067,16 +3116,12 @@ int hny_builder_finish_delta(hny_builder *b, hny_graph_delta **out) {
     return fail(HNY_ERR_INVALID_ARG, "finish_delta: not a successor builder (hny_builder_create_update)");
   if (b->pos < b->order.size() || b->in_batch) return fail(HNY_ERR_INVALID_ARG, "build not finished");
   if (!b->gaps_done) return fail(HNY_ERR_INVALID_ARG, "finish_delta: hny_builder_fill_gaps has not run");
-  HIP_TRY(hipSetDevice(b->device));
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  const double t0 = now_s();
-  hipStream_t st = b->stream;
-  const uint32_t n = b->n, M = b->o.M, M0 = b->o.M0, upl = b->up_layers;
-  const size_t nup = (size_t)b->n_upper * upl;
   u64 stats[ST_COUNT] = {0};
-  HIP_TRY(hipMemcpy(stats, b->d_stats.p, sizeof stats, hipMemcpyDeviceToHost));
-  if (int rc = device_error_words(b, stats)) return rc;
-  if (int rc = ensure_finalized(b, st)) return rc;
+  double t0 = 0;
+  if (int rc = export_begin(b, stats, &t0)) return rc;
+  hipStream_t st = b->stream;
+  const uint32_t n = b->n, M = b->o.M, M0 = b->o.M0;
+  const size_t nup = (size_t)b->n_upper * b->up_layers;
   DevBuf<unsigned char> d_flag;
   HIP_TRY(d_flag.alloc((size_t)n + nup + 1));
   HIP_TRY(hipMemsetAsync(d_flag.p, 0, (size_t)n + nup + 1, st));
@@ -3084,8 +3129,7 @@ int hny_builder_finish_delta(hny_builder *b, hny_graph_delta **out) {
   if (nup) HIP_TRY(hnyk_diff_records(b->d_up_ids.p, b->d_du_ids.p, d_flag.p + n, (u32)nup, M, st));
   std::vector<unsigned char> flag((size_t)n + nup + 1);
   HIP_TRY(hipMemcpyAsync(flag.data(), d_flag.p, flag.size(), hipMemcpyDeviceToHost, st));
-  if (n) HIP_TRY(hipMemcpyAsync(b->h_cnt0, b->d_fin_cnt0.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-  if (nup) HIP_TRY(hipMemcpyAsync(b->h_cntu, b->d_fin_cntu.p, nup * 4, hipMemcpyDeviceToHost, st));
+  if (int rc = enqueue_count_downloads(b)) return rc;
   HIP_TRY(hipStreamSynchronize(st));
 
   std::unique_ptr<hny_graph_delta, void (*)(hny_graph_delta *)> dh((hny_graph_delta *)calloc(1, sizeof(hny_graph_delta)),
@@ -3097,23 +3141,21 @@ int hny_builder_finish_delta(hny_builder *b, hny_graph_delta **out) {
   std::vector<u64> rec_src, rec_off(1, 0);
   uint64_t total = 0;
   for (uint32_t s = 0; s < n; s++) {
-    const uint32_t m = rec_mask_of(b, s), om = b->old_mask[s];
-    total += (uint64_t)__builtin_popcount(m);
-    for (uint32_t l = 0; l <= HNY_MAX_LEVEL; l++) {
-      const uint32_t bit = 1u << l;
-      if ((om & bit) && !(m & bit)) {
+    const uint32_t om = b->old_mask[s];
+    for (uint32_t gone = om & ~rec_mask_of(b, s), l = 0; gone; gone >>= 1, l++) // layers the slot no longer owns
+      if (gone & 1) {
         rm_item.push_back(b->ids[s]);
         rm_layer.push_back((uint8_t)l);
       }
-      if (!(m & bit)) continue;
-      const size_t li = l == 0 ? s : (size_t)b->upper_idx[s] * upl + (l - 1);
-      const bool changed = !(om & bit) || flag[l == 0 ? li : n + li] != 0;
-      if (!changed) continue;
+    for_each_record(b, s, [&](uint32_t l, size_t li) {
+      total++;
+      const bool changed = !(om >> l & 1) || flag[l == 0 ? li : n + li] != 0;
+      if (!changed) return;
       rec_item.push_back(b->ids[s]);
       rec_layer.push_back((uint8_t)l);
       rec_src.push_back(l == 0 ? (u64)li : ((u64)1 << 63) | (u64)li);
-      rec_off.push_back(rec_off.back() + (l == 0 ? b->h_cnt0[li] : b->h_cntu[li]));
-    }
+      rec_off.push_back(rec_off.back() + list_count(b, l, li));
+    });
   }
   const uint64_t nr = rec_item.size(), nl = rec_off.back();
   std::vector<u32> packed(std::max<uint64_t>(nl, 1));
@@ -3144,8 +3186,6 @@ int hny_builder_finish_delta(hny_builder *b, hny_graph_delta **out) {
     return q;
   };
   for (uint64_t k = 0; k < nl; k++) packed[k] = b->ids[packed[k]]; // slot -> item id (order kept)
-  std::vector<uint32_t> eps(b->entry_points.size());
-  for (size_t i = 0; i < eps.size(); i++) eps[i] = b->ids[b->entry_points[i]];
   d->n_records = nr;
   d->rec_item = (const uint32_t *)dup(rec_item.data(), nr * 4);
   d->rec_layer = (const uint8_t *)dup(rec_layer.data(), nr);
@@ -3154,8 +3194,8 @@ int hny_builder_finish_delta(hny_builder *b, hny_graph_delta **out) {
   d->n_removed = rm_item.size();
   d->removed_item = (const uint32_t *)dup(rm_item.data(), rm_item.size() * 4);
   d->removed_layer = (const uint8_t *)dup(rm_layer.data(), rm_layer.size());
-  d->entry_points = (const uint32_t *)dup(eps.data(), eps.size() * 4);
-  d->n_entry_points = (uint32_t)eps.size();
+  d->entry_points = entry_point_ids(b);
+  d->n_entry_points = (uint32_t)b->entry_points.size();
   d->max_level = b->max_level;
   d->n_records_total = total;
   if (!d->rec_item || !d->rec_layer || !d->rec_offset || !d->neighbours || !d->removed_item || !d->removed_layer ||

@@ -95,6 +95,71 @@ def test_upper_layer_lists_beyond_one_grid(orc, hny):
     assert changed[0] < base[4000] and sum(i > base[UPPER_N - UPPER_TOP] for i in changed) >= 20
 
 
+# ---- finish(): the layer-0 lists downloaded in more than one piece, compacted by several host threads -------------------
+# hny_host.cpp enqueue_export_downloads: `pieces = max(1, min(nt, (uint64_t)n * M0 * 4 / ((uint64_t)16 << 20)))`
+PIECE_BYTES = 16 << 20
+# hny_host.cpp export_shares: `n < 10000 ? 1u : std::max(1u, std::min(64u, std::thread::hardware_concurrency() / 2))`
+SHARES_FROM, SHARES_MOST = 10000, 64
+# hny_host.cpp start_export_prefault: `< ((size_t)8 << 20)) return; // small: finish() allocates`, over export_bytes()
+# of the bounds: 4 + 1 + 8 bytes per record (and 8 more), 4 per list slot
+PREFAULT_FLOOR = 8 << 20
+PIECES_N, PIECES_M, PIECES_UPPER_EVERY = 140000, 64, 467
+assert PIECES_N * PIECES_M * 4 == 35840000 and PIECES_N * PIECES_M * 4 // PIECE_BYTES == 2  # two pieces, given two threads
+assert PIECES_N >= SHARES_FROM and PIECES_N % SHARES_MOST == 32     # several shares, whatever their number: uneven tails
+assert 200 < -(-PIECES_N // PIECES_UPPER_EVERY) < 400               # items on layer 1: the upper lists travel too
+assert PIECES_N * (13 + PIECES_M * 4) + 8 > PREFAULT_FLOOR          # the arrays are prepared while the device works
+
+
+def test_export_in_several_pieces_and_shares(hny):
+    """A loaded ring of 140 000 items with ids 2 i (slot != item id), 300 of them on layer 1, M = M0 = 64: the
+    layer-0 lists are 35.84 MB on the device, which finish() downloads in two pieces on a host with at least four
+    hardware threads, and compacts in as many shares as it has threads (half the hardware threads, at most 64).  The
+    share that compacts a slot range must wait for the piece that covers it, and both must place the range where
+    the record table has it.  An empty resident update (test_sources_and_degenerate_updates: accepted) makes the
+    successor whose fill_gaps rewrites every record; its finish() returns the ring's entry point, max_level and
+    records, the expected ones being the ring's own (numpy), no oracle — but for the one thing an empty update does
+    to a graph: the old entry point is indexed again (hnsw.rs:267), so item 0 walks from itself and gains a few
+    links on both layers, and the items it links gain it.  Measured on this ring: 9 of 140 300 records.  Those
+    records are held against the ring too: the entry point's lists keep what they had, every other changed list is
+    the ring's plus the entry point, and the two sets of new links mirror each other; at most 2 (1 + ef) records
+    may change at all.  The delta holds exactly those records and removes nothing.  A second finish() with the
+    graph cache on, after the first graph went back to it, gives the same arrays again."""
+    dim, M, ef = 8, PIECES_M, 16
+    base = np.arange(PIECES_N, dtype=np.uint32) * 2
+    levels = np.zeros(PIECES_N, np.uint8)
+    levels[::PIECES_UPPER_EVERY] = 1
+    ring = Ring(base, levels)
+    want = ring.as_dict()
+    assert len(want) == PIECES_N + int(levels.sum()) and (ring.rec_layer == 1).sum() == 300
+    ep = int(ring.entry_points[0])
+    items = hny.ItemSet.from_f32(EUCLIDEAN, _vecs(np.random.default_rng(64), PIECES_N, dim), ids=base, levels=levels)
+    c, h = hny.encode_vectors(EUCLIDEAN, np.zeros((0, dim), np.float32))
+    none = np.zeros(0, np.uint32)
+    with hny.Builder(items, prev=ring, load=True, M=M, M0=M, ef_construction=ef, batch_frac=0.1, batch_max=256) as b:
+        g, d = b.update(none, codes=c, headers=h, delete_ids=none, levels=np.zeros(0, np.uint8), delta=True)
+        assert g.entry_points.tolist() == ring.entry_points.tolist() and g.max_level == ring.max_level == 1
+        assert np.array_equal(g.rec_item, ring.rec_item) and np.array_equal(g.rec_layer, ring.rec_layer)
+        got = _check_delta(want, g, d, none)  # ring + delta == g, nothing unchanged in the delta, no key removed
+        changed = {k for k in want if got[k] != want[k]}
+        print(f"records that differ from the ring's: {len(changed)} of {len(want)}")
+        assert changed == set(d.as_dict()) and len(d.removed_keys()) == 0 and len(changed) <= 2 * (1 + ef)
+        for layer in (0, 1):
+            gained = set(got[(ep, layer)]) - set(want[(ep, layer)])
+            assert set(want[(ep, layer)]) <= set(got[(ep, layer)]) and got[(ep, layer)] == sorted(set(got[(ep, layer)]))
+            assert gained == {i for (i, l) in changed if l == layer and i != ep}
+            for i in gained:
+                assert got[(i, layer)] == sorted(want[(i, layer)] + [ep])
+        first = [np.array(a) for a in (g.rec_item, g.rec_layer, g.offsets, g.nbrs)]
+        hny.set_graph_cache(1 << 30)
+        try:
+            del g  # its arrays go to the cache, the next export takes them from there
+            g2 = b.finish()
+            assert all(np.array_equal(a, e) for a, e in zip((g2.rec_item, g2.rec_layer, g2.offsets, g2.nbrs), first))
+            assert g2.entry_points.tolist() == ring.entry_points.tolist() and g2.max_level == ring.max_level
+        finally:
+            hny.set_graph_cache(0)
+
+
 # ---- deferred targets shared among ranks: k_apply_n8, k_apply_wg, k_apply_merge ----------------------------------------
 # hny_host.cpp launch_apply_deferred: `(int)std::min<u32>(work, 5120u)` blocks of k_apply_n8, `std::min<u32>(work,
 # 2048u)` of k_apply_wg; both kernels: `for (u32 di = a.shard_rank + blockIdx.x * sw; di < n_def; di += gridDim.x * sw)`
