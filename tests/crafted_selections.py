@@ -19,6 +19,7 @@ before), never on the graph, so the CPU test reproduces exactly the buffers the 
 import numpy as np
 
 from conftest import draw_levels
+from support import vecs
 
 EUCLIDEAN, HAMMING = 1, 3
 U64_MAX = np.uint64(0xFFFFFFFFFFFFFFFF)
@@ -100,10 +101,6 @@ def n_segments(batch, cap_sel, sel):
     return total
 
 
-def _vecs(rng, n, dim):
-    return rng.uniform(-1, 1, (n, dim)).astype(np.float32)
-
-
 class Scenario:
     """ds, build options, and select(batch, progress) -> crafted buffer or None; `crafted` counts the chosen batches"""
     x86 = False
@@ -148,7 +145,7 @@ class FlatPrivateTargets(Scenario):
             self.ds = orc.Dataset(metric, dim, ids, rng.integers(0, 256, (n, dim // 8), dtype=np.uint8),
                                   np.zeros((n, 8), np.uint8), levels)
         else:
-            self.ds = orc.Dataset.from_f32(metric, _vecs(rng, n, dim), levels, ids)
+            self.ds = orc.Dataset.from_f32(metric, vecs(rng, n, dim), levels, ids)
         self.kw = dict(M=M, M0=M0, batch_frac=1.0, batch_max=members)
         self.members, self.private = members, private
 
@@ -170,7 +167,7 @@ class Hub(Scenario):
     def __init__(self, orc, dim, n=3000):
         super().__init__(orc)
         self.kw = dict(M=3, M0=6, batch_frac=1.0, batch_max=self.HUB_BATCH)
-        self.ds = orc.Dataset.from_f32(EUCLIDEAN, _vecs(np.random.default_rng(dim), n, dim), draw_levels(n, 3, seed=dim))
+        self.ds = orc.Dataset.from_f32(EUCLIDEAN, vecs(np.random.default_rng(dim), n, dim), draw_levels(n, 3, seed=dim))
         self.hub = None
 
     def select(self, batch, progress):
@@ -199,7 +196,7 @@ class EmptyLayers(Scenario):
     def __init__(self, orc, dim=8, n=3000):
         super().__init__(orc)
         self.kw = dict(M=4, M0=8, batch_frac=1.0, batch_max=256)
-        self.ds = orc.Dataset.from_f32(EUCLIDEAN, _vecs(np.random.default_rng(77), n, dim), draw_levels(n, 4, seed=77))
+        self.ds = orc.Dataset.from_f32(EUCLIDEAN, vecs(np.random.default_rng(77), n, dim), draw_levels(n, 4, seed=77))
 
     def select(self, batch, progress):
         M = self.kw["M"]

@@ -11,6 +11,8 @@ import re
 import numpy as np
 import pytest
 
+from support import hny, param_types, prefilled, untouched  # noqa: F401
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BY_VECTOR = ["hny_builder *", "const hny_query_opts *", "const hny_query_bitsets *", "uint64_t", "const void *",
              "size_t", "const void *", "const uint32_t *", "uint32_t *", "float *", "uint32_t *"]
@@ -21,23 +23,6 @@ DECLARED = {"hny_builder_nns_bitsets": BY_VECTOR, "hny_builder_nns_bitsets_f32":
             "hny_builder_exact_knn_bitsets": BY_VECTOR, "hny_builder_exact_knn_bitsets_f32": F32}
 
 
-@pytest.fixture(scope="module")
-def hny():
-    import hannoy_amd
-    hannoy_amd.load_library()
-    return hannoy_amd
-
-
-def _param_types(header, name):
-    m = re.search(r"\bint %s\(([^;]*?)\);" % name, header, re.S)
-    assert m, f"{name} is not declared"
-    out = []
-    for p in m.group(1).split(","):
-        p = " ".join(p.split())
-        out.append(re.sub(r"\s*\b\w+$", "", p).strip())  # drop the parameter's name
-    return out
-
-
 def test_bitsets_symbols_are_exported_and_declared(hny):
     from hannoy_amd import _capi
     L = hny.load_library()
@@ -46,7 +31,7 @@ def test_bitsets_symbols_are_exported_and_declared(hny):
     for name, types in DECLARED.items():
         fn = getattr(L, name)
         assert name in _capi.EXPORTED
-        assert _param_types(header, name) == types, name
+        assert param_types(header, name) == types, name
         assert fn.restype is C.c_int
         want = [C.c_uint64 if t == "uint64_t" else C.c_size_t if t == "size_t" else
                 C.POINTER(_capi.QueryOpts) if t == "const hny_query_opts *" else
@@ -55,8 +40,8 @@ def test_bitsets_symbols_are_exported_and_declared(hny):
     # the _filtered calls, argument for argument, but for the filters' struct
     for a, b in (("nns_bitsets", "nns_filtered"), ("exact_knn_bitsets", "exact_knn_filtered")):
         for suffix in ("", "_f32"):
-            x = _param_types(header, f"hny_builder_{a}{suffix}")
-            y = _param_types(header, f"hny_builder_{b}{suffix}")
+            x = param_types(header, f"hny_builder_{a}{suffix}")
+            y = param_types(header, f"hny_builder_{b}{suffix}")
             assert [t.replace("hny_query_bitsets", "hny_query_filters") for t in x] == y
 
 
@@ -137,7 +122,7 @@ def test_refusals_leave_the_outputs_untouched(hny, case, exact):
     v = np.zeros((n, dim), np.float32)
     hdr = np.zeros((n, 4), np.uint8)
     items = np.arange(n, dtype=np.uint32)
-    out = (np.full((n, 1), 77, np.uint32), np.full((n, 1), 7.5, np.float32), np.full(n, 77, np.uint32))
+    out = prefilled(n, 1)
     qo = _capi.QueryOpts()
     qo.k, qo.ef_search, qo.linear_below, qo.linear_below_ratio = 1, 10, 1000, 1.0
     qb, _keep = _bitsets(_capi, **REFUSALS[case])
@@ -149,7 +134,7 @@ def test_refusals_leave_the_outputs_untouched(hny, case, exact):
     assert L.hny_last_error()
     assert bv(None, C.byref(qo), C.byref(qb), n, None, 0, None, p(items), *map(p, out)) == E
     assert f32(None, C.byref(qo), C.byref(qb), n, p(v), dim * 4, *map(p, out)) == E
-    assert (out[0] == 77).all() and (out[1] == 7.5).all() and (out[2] == 77).all()
+    assert untouched(out)
 
 
 @pytest.mark.parametrize("exact", [False, True], ids=["nns", "exact"])
@@ -161,7 +146,7 @@ def test_inherited_refusals_leave_the_outputs_untouched(hny, exact):
     n, dim = 4, 8
     v = np.zeros((n, dim), np.float32)
     hdr = np.zeros((n, 4), np.uint8)
-    out = (np.full((n, 1), 77, np.uint32), np.full((n, 1), 7.5, np.float32), np.full(n, 77, np.uint32))
+    out = prefilled(n, 1)
     p = _capi._p
     E = _capi.ERR_INVALID_ARG
     bv = L.hny_builder_exact_knn_bitsets if exact else L.hny_builder_nns_bitsets
@@ -188,7 +173,7 @@ def test_inherited_refusals_leave_the_outputs_untouched(hny, exact):
     assert f32(None, C.byref(qo), C.byref(good), n, None, dim * 4, *map(p, out)) == E  # NULL queries
     assert bv(None, C.byref(qo), C.byref(good), n, None, dim * 4, None, None, *map(p, out)) == E
     assert bv(None, C.byref(qo), C.byref(good), n, p(v), dim * 4, p(hdr), None, None, p(out[1]), p(out[2])) == E
-    assert (out[0] == 77).all() and (out[1] == 7.5).all() and (out[2] == 77).all()
+    assert untouched(out)
 
 
 def test_bitsets_python_surface(hny):

@@ -8,14 +8,9 @@ import re
 import numpy as np
 import pytest
 
+from support import hny  # noqa: F401
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def hny():
-    import hannoy_amd
-    hannoy_amd.load_library()
-    return hannoy_amd
 
 
 def test_exports_every_declared_symbol(hny):

@@ -2,10 +2,11 @@
 signatures, the ctypes prototypes match them, and a NULL builder is refused from the arguments alone."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
+
+from support import hny, param_types  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the declarations of include/hannoy_amd.h, one parameter type per entry
@@ -17,23 +18,6 @@ DECLARED = {
 }
 
 
-@pytest.fixture(scope="module")
-def hny():
-    import hannoy_amd
-    hannoy_amd.load_library()
-    return hannoy_amd
-
-
-def _param_types(header, name):
-    m = re.search(r"\bint %s\(([^;]*?)\);" % name, header, re.S)
-    assert m, f"{name} is not declared"
-    out = []
-    for p in m.group(1).split(","):
-        p = " ".join(p.split())
-        out.append(re.sub(r"\s*\b\w+$", "", p).strip())  # drop the parameter's name
-    return out
-
-
 def test_exact_symbols_are_exported_and_declared(hny):
     from hannoy_amd import _capi
     L = hny.load_library()
@@ -42,7 +26,7 @@ def test_exact_symbols_are_exported_and_declared(hny):
     for name, types in DECLARED.items():
         fn = getattr(L, name)
         assert name in _capi.EXPORTED
-        assert _param_types(header, name) == types, name
+        assert param_types(header, name) == types, name
         # the ctypes prototype: one entry per declared parameter, integers where the header has integers
         assert fn.restype is C.c_int
         want = [C.c_uint64 if t == "uint64_t" else C.c_size_t if t == "size_t" else

@@ -3,10 +3,11 @@ declared signatures, the ctypes prototypes match them, hny_query_filters stays o
 builder is refused from the arguments alone."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
+
+from support import hny, param_types, prefilled, untouched  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the declarations of include/hannoy_amd.h, one parameter type per entry
@@ -19,23 +20,6 @@ DECLARED = {
 }
 
 
-@pytest.fixture(scope="module")
-def hny():
-    import hannoy_amd
-    hannoy_amd.load_library()
-    return hannoy_amd
-
-
-def _param_types(header, name):
-    m = re.search(r"\bint %s\(([^;]*?)\);" % name, header, re.S)
-    assert m, f"{name} is not declared"
-    out = []
-    for p in m.group(1).split(","):
-        p = " ".join(p.split())
-        out.append(re.sub(r"\s*\b\w+$", "", p).strip())  # drop the parameter's name
-    return out
-
-
 def test_filtered_symbols_are_exported_and_declared(hny):
     from hannoy_amd import _capi
     L = hny.load_library()
@@ -44,7 +28,7 @@ def test_filtered_symbols_are_exported_and_declared(hny):
     for name, types in DECLARED.items():
         fn = getattr(L, name)
         assert name in _capi.EXPORTED
-        assert _param_types(header, name) == types, name
+        assert param_types(header, name) == types, name
         assert fn.restype is C.c_int
         want = [C.c_uint64 if t == "uint64_t" else C.c_size_t if t == "size_t" else
                 C.POINTER(_capi.QueryOpts) if t == "const hny_query_opts *" else
@@ -77,7 +61,7 @@ def test_filtered_null_builder_is_an_argument_error(hny):
     v = np.zeros((n, dim), np.float32)
     hdr = np.zeros((n, 4), np.uint8)
     items = np.arange(n, dtype=np.uint32)
-    out = (np.full((n, 1), 77, np.uint32), np.full((n, 1), 7.5, np.float32), np.full(n, 77, np.uint32))
+    out = prefilled(n, 1)
     qo = _capi.QueryOpts()
     qo.k = 1
     qf, _keep = _capi.QueryFilters.pack([[1, 2]], [0, -1, 0, 0])
@@ -89,7 +73,7 @@ def test_filtered_null_builder_is_an_argument_error(hny):
     assert L.hny_builder_nns_filtered_f32(None, C.byref(qo), C.byref(qf), n, None, dim * 4, *map(p, out)) == E
     assert L.hny_builder_nns_filtered_f32(None, C.byref(qo), None, n, p(v), dim * 4, *map(p, out)) == E
     assert L.hny_last_error()
-    assert (out[0] == 77).all() and (out[1] == 7.5).all() and (out[2] == 77).all()
+    assert untouched(out)
 
 
 def test_filtered_python_surface(hny):

@@ -6,15 +6,10 @@ import re
 import numpy as np
 import pytest
 
+from support import hny  # noqa: F401
+
 F32_SYMBOLS = ["hny_build_f32", "hny_build_incremental_f32", "hny_builder_create_f32", "hny_builder_load_f32",
                "hny_builder_export_items", "hny_builder_search_knn_f32", "hny_builder_nns_f32"]
-
-
-@pytest.fixture(scope="module")
-def hny():
-    import hannoy_amd
-    hannoy_amd.load_library()
-    return hannoy_amd
 
 
 def test_f32_symbols_are_exported_and_declared(hny):

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from synthetic_graphs import Ring as _Ring
+from support import hny, queries  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -43,25 +44,12 @@ assert N_FILTERS_IDENTITY * mask_stride(N_BIG) > IDENTITY_TRIP_WORDS and TRIP_FI
 assert N_FILTERS_IDENTITY * mask_stride(N_BIG) * 4 < 1 << 30  # one round (HNY_FILTER_MASK_BYTES)
 
 
-@pytest.fixture(scope="module")
-def hny():
-    import hannoy_amd
-    hannoy_amd.load_library()
-    return hannoy_amd
-
-
 def _loaded(orc, hny, n, ids, seed):
     rng = np.random.default_rng(seed)
     vecs = rng.uniform(-1, 1, (n, 64)).astype(np.float32)
     ds = orc.Dataset.from_f32(HAMMING, vecs, np.zeros(n, np.uint8), ids)
     items = hny.ItemSet(HAMMING, 64, ds.ids, ds.codes, ds.headers, ds.levels)
     return rng, hny.Builder(items, prev=_Ring(ds.ids), load=True, M=2, M0=2, ef_construction=1)
-
-
-def _queries(orc, rng, nq):
-    qs = rng.uniform(-1, 1, (nq, 64)).astype(np.float32)
-    qc = orc.encode_vectors(HAMMING, qs)
-    return qc, orc.make_headers(HAMMING, 64, qc)
 
 
 def _pack(sets, n_bits):
@@ -101,7 +89,7 @@ def test_grid_stride_over_the_slot_runs(orc, hny):
     sets = [np.sort(ids[s]).astype(np.uint32) for s in slots]
     n_bits = int(ids.max()) + 1
     fo = np.array([0, 1, 2, 3, 4, 5, 1, 0])
-    qc, qh = _queries(orc, rng, len(fo))
+    _, qc, qh = queries(orc, HAMMING, rng, len(fo), 64)
     with b:
         _whole_filters(b, sets, n_bits, fo, qc, qh, k=1000)
         # n_bits that ends inside the second trip: the slots above drop out
@@ -123,7 +111,7 @@ def test_every_remainder_of_the_four_filter_step(orc, hny, small, n_filters):
     rng = np.random.default_rng(n_filters)
     sets = [np.sort(rng.choice(ids, 20 + f, replace=False)).astype(np.uint32) for f in range(n_filters)]
     fo = rng.permutation(n_filters)
-    qc, qh = _queries(orc, rng, n_filters)
+    _, qc, qh = queries(orc, HAMMING, rng, n_filters, 64)
     assert n_filters // FILTER_STEP * FILTER_STEP + n_filters % FILTER_STEP == n_filters
     _whole_filters(b, sets, int(ids.max()) + 1, fo, qc, qh, k=40)
 
@@ -151,7 +139,7 @@ def test_groups_of_id_bitsets_within_a_round(orc, hny, small, monkeypatch):
     used = np.setdiff1d(np.arange(20), [0, 6, 13, 19])
     assert len(used) == 16
     fo = rng.permutation(np.concatenate([used, used[:5]]))
-    qc, qh = _queries(orc, rng, len(fo))
+    _, qc, qh = queries(orc, HAMMING, rng, len(fo), 64)
     one_round = _whole_filters(b, sets, n_bits, fo, qc, qh, k=40)
     monkeypatch.setenv("HNY_FILTER_MASK_BYTES", str(budget))
     got = _whole_filters(b, sets, n_bits, fo, qc, qh, k=40)
@@ -175,7 +163,7 @@ def test_identity_word_loop(orc, hny):
     sets[TRIP_FILTER + 1] = np.array([0, edge - 1, n - 1], np.uint32)
     sets[nf - 1] = np.array([n - 1], np.uint32)
     fo = np.arange(nf)
-    qc, qh = _queries(orc, rng, nf)
+    _, qc, qh = queries(orc, HAMMING, rng, nf, 64)
     with b:
         _whole_filters(b, sets, n, fo, qc, qh, k=100)
         # n_bits below n: the tail is cut at n_bits, in the middle of a word

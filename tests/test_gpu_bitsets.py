@@ -12,6 +12,7 @@ import pytest
 
 from conftest import draw_levels
 from synthetic_graphs import Ring as _Ring
+from support import hny, identical_hits, prefilled, untouched  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -21,13 +22,6 @@ N = 3001
 NQ = 120
 LB = 1000
 assert N % 64 and N % 32
-
-
-@pytest.fixture(scope="module")
-def hny():
-    import hannoy_amd
-    hannoy_amd.load_library()
-    return hannoy_amd
 
 
 def _ids(layout, n=N):
@@ -112,11 +106,6 @@ def _sets(mask):
     return [np.flatnonzero(row).astype(np.uint32) for row in mask]
 
 
-def _identical(got, want, tag=None):
-    for x, y in zip(got, want):
-        assert np.array_equal(x.view(np.uint32), y.view(np.uint32)), tag
-
-
 def _both(b, mask, fo, exact=False, bits=None, f32=None, **kw):
     """the bitset call and the id-list call on the same sets; returns the former's result"""
     bits = _pack(mask) if bits is None else bits
@@ -130,7 +119,7 @@ def _both(b, mask, fo, exact=False, bits=None, f32=None, **kw):
         got = (b.exact_knn_bitsets if exact else b.nns_bitsets)(bits, n_bits, fo, **kw)
         read = b.exact_rows_read()
         want = (b.exact_knn_filtered if exact else b.nns_filtered)(sets, fo, **kw)
-    _identical(got, want, (exact, n_bits))
+    identical_hits(got, want, (exact, n_bits))
     if exact:
         assert read == b.exact_rows_read()
     return got
@@ -207,7 +196,7 @@ def test_garbage_beyond_n_bits_and_in_the_stride_padding(worlds, layout):
     assert bits.shape[1] == (n_bits + 31) // 32 + 3 and not np.array_equal(bits[:, :-3], _pack(mask))
     clean = w.b.nns_bitsets(_pack(mask), n_bits, w.fo, w.qc, w.qh, k=10, ef_search=50, linear_below=LB)
     got = _both(w.b, mask, w.fo, bits=bits, qcodes=w.qc, qheaders=w.qh, k=10, ef_search=50, linear_below=LB)
-    _identical(got, clean)
+    identical_hits(got, clean)
     assert got[0][w.fo >= 0].max() < n_bits
     _both(w.b, mask, w.fo, exact=True, bits=bits, qcodes=w.qc, qheaders=w.qh, k=10)
 
@@ -295,7 +284,7 @@ def test_exact_routing_skip_and_rows_read(worlds, monkeypatch):
     monkeypatch.setenv("HNY_EXACT_SKIP", "0")
     every = _both(w.b, mask, fo, exact=True, qcodes=w.qc, qheaders=w.qh, k=10)
     assert w.b.exact_rows_read() >= read  # (_both: and equal to the id-list call's, which reads every row)
-    _identical(got, every)
+    identical_hits(got, every)
 
 
 def test_exact_strict_mode(orc, hny):
@@ -342,14 +331,6 @@ def _raw(hny, b, bits, n_bits, filter_of, qc, qh, out, exact=False, k=10, ef_sea
                             qc.shape[1] if qstride is None else qstride, p(qh), None, *map(p, out))
 
 
-def _prefilled(nq, k):
-    return np.full((nq, k), 77, np.uint32), np.full((nq, k), 7.5, np.float32), np.full(nq, 77, np.uint32)
-
-
-def _untouched(out):
-    return (out[0] == 77).all() and (out[1] == 7.5).all() and (out[2] == 77).all()
-
-
 def test_k_4095_is_accepted_and_4096_hits_are_refused(orc, hny):
     rng = np.random.default_rng(23)
     n, dim, nq = 5000, 8, 6
@@ -368,13 +349,13 @@ def test_k_4095_is_accepted_and_4096_hits_are_refused(orc, hny):
     with hny.Builder(items, prev=_Ring(ds.ids), load=True, M=2, M0=2, ef_construction=1) as b:
         got = _both(b, mask, fo, exact=True, qcodes=qc, qheaders=qh, k=4095)
         assert (got[2][fo == 0] == 4095).all() and (got[2][fo == 1] == len(ids[::9])).all()
-        out = _prefilled(nq, 4096)
+        out = prefilled(nq, 4096)
         rc = _raw(hny, b, _pack(mask), n_bits, [0, 1, 2, 0, 1, 0], qc, qh, out, exact=True, k=4096)
         assert rc == hny._capi.ERR_UNSUPPORTED and "filter 2" in hny.load_library().hny_last_error().decode()
-        assert _untouched(out)
-        out = _prefilled(nq, 5000)  # and the linear scan of the nns call on the big path
+        assert untouched(out)
+        out = prefilled(nq, 5000)  # and the linear scan of the nns call on the big path
         rc = _raw(hny, b, _pack(mask), n_bits, [0, 1, 2, 0, 1, 0], qc, qh, out, k=5000, ef_search=5000, linear_below=ALL)
-        assert rc == hny._capi.ERR_UNSUPPORTED and _untouched(out)
+        assert rc == hny._capi.ERR_UNSUPPORTED and untouched(out)
 
 
 @pytest.mark.parametrize("layout", ["identity", "strided"])
@@ -395,8 +376,8 @@ def test_several_rounds_of_masks_and_groups_of_id_bitsets(worlds, monkeypatch, l
     for lb in (LB, 0, ALL):
         got = _both(w.b, mask, w.fo, qcodes=w.qc, qheaders=w.qh, k=10, ef_search=50, linear_below=lb)
         if lb == LB:
-            _identical(got, one)
-    _identical(_both(w.b, mask, w.fo, exact=True, qcodes=w.qc, qheaders=w.qh, k=10), one_exact)
+            identical_hits(got, one)
+    identical_hits(_both(w.b, mask, w.fo, exact=True, qcodes=w.qc, qheaders=w.qh, k=10), one_exact)
 
 
 @pytest.mark.parametrize("name", ["hamming", "cosine768"])
@@ -424,16 +405,16 @@ def test_cancellation_before_the_first_launch(worlds):
         kw = dict(k=10) if exact else dict(k=10, ef_search=50)
         got = call(bits, n_bits, w.fo, w.qc, w.qh, cancel=lambda: False, **kw)
         assert not w.b.did_cancel
-        _identical(got, ref(sets, w.fo, w.qc, w.qh, **kw))
+        identical_hits(got, ref(sets, w.fo, w.qc, w.qh, **kw))
         got = call(bits, n_bits, w.fo, w.qc, w.qh, cancel=lambda: True, **kw)
         mine = w.b.did_cancel
         want = ref(sets, w.fo, w.qc, w.qh, cancel=lambda: True, **kw)
         assert mine and w.b.did_cancel and (exact or not got[2].any())
-        _identical(got, want)
+        identical_hits(got, want)
         got = call(bits, n_bits, [0, 1, -1, 2, 5, 3], query_items=qi, cancel=lambda: True, **kw)
         want = ref(sets, [0, 1, -1, 2, 5, 3], query_items=qi, cancel=lambda: True, **kw)
         assert w.b.did_cancel and got[2][1] == NONE and got[2][5] == NONE
-        _identical(got, want)
+        identical_hits(got, want)
 
 
 def test_refusals_on_a_builder_leave_the_outputs_alone(hny, worlds):
@@ -478,12 +459,12 @@ def test_refusals_on_a_builder_leave_the_outputs_alone(hny, worlds):
         extra = [] if exact else [(INV, "ratio", dict(ratio=1.5)), (INV, "ratio", dict(ratio=-0.1)),
                                   (INV, "ratio", dict(ratio=float("nan")))]
         for code, word, kw in cases + extra:
-            out = _prefilled(NQ, 10)
+            out = prefilled(NQ, 10)
             assert _raw(hny, w.b, bits, n_bits, w.fo, w.qc, w.qh, out, exact=exact, **kw) == code, (exact, word)
             assert word in L.hny_last_error().decode(), (exact, word)
-            assert _untouched(out), (exact, word)
+            assert untouched(out), (exact, word)
         # n_bits == 2^32 itself is legal (stride_words says the rows are that long: nothing is read, no query uses one)
-        out = _prefilled(4, 10)
+        out = prefilled(4, 10)
 
         def whole_range(qo, qb, keep):
             qb.n_bits, qb.stride_words = 2 ** 32, 2 ** 27
@@ -491,7 +472,7 @@ def test_refusals_on_a_builder_leave_the_outputs_alone(hny, worlds):
                     edit=whole_range) == capi.OK
         assert (out[2] == 10).all()
         # stride_words == ceil(n_bits / 32) and the arguments unbent are accepted
-        out = _prefilled(NQ, 10)
+        out = prefilled(NQ, 10)
         assert _raw(hny, w.b, bits, n_bits, w.fo, w.qc, w.qh, out, exact=exact) == capi.OK
         assert not (out[2] == 77).any()
     # NULL arguments
@@ -499,7 +480,7 @@ def test_refusals_on_a_builder_leave_the_outputs_alone(hny, worlds):
     qo.k = 10
     qb, keep = capi.QueryBitsets.pack(bits, n_bits, w.fo)
     p = capi._p
-    out = _prefilled(NQ, 10)
+    out = prefilled(NQ, 10)
     args = [w.b._h, C.byref(qo), C.byref(qb), NQ, p(w.qc), w.qc.shape[1], p(w.qh), None, p(out[0]), p(out[1]), p(out[2])]
     for fn in (L.hny_builder_nns_bitsets, L.hny_builder_exact_knn_bitsets):
         for hole in (0, 1, 2, 4, 6, 8, 9, 10):
@@ -507,7 +488,7 @@ def test_refusals_on_a_builder_leave_the_outputs_alone(hny, worlds):
             a[hole] = None
             assert fn(*a) == INV, hole
             assert L.hny_last_error(), hole
-    assert _untouched(out)
+    assert untouched(out)
 
 
 def test_query_builder_candidates_bitsets(hny):
@@ -534,14 +515,14 @@ def test_query_builder_candidates_bitsets(hny):
             qb = r.nns(10).ef_search(40)
             return qb.exact() if exact else qb
         want = q().candidates_per_query(per).by_vectors(qs)
-        _identical(q().candidates_bitsets(mask, fo).by_vectors(qs), want)
-        _identical(q().candidates_bitsets(packed, fo, n_bits=n + 100).by_vectors(qs), want)
+        identical_hits(q().candidates_bitsets(mask, fo).by_vectors(qs), want)
+        identical_hits(q().candidates_bitsets(packed, fo, n_bits=n + 100).by_vectors(qs), want)
         want = q().candidates_per_query(per).by_items(items)
-        _identical(q().candidates_bitsets(mask, fo).by_items(items), want)
-        _identical(q().candidates_bitsets(packed, fo, n_bits=n + 100).by_items(items), want)
+        identical_hits(q().candidates_bitsets(mask, fo).by_items(items), want)
+        identical_hits(q().candidates_bitsets(packed, fo, n_bits=n + 100).by_items(items), want)
     # filter_of=None: one filter per query, in order
     want = r.nns(5).candidates_per_query(sets).by_vectors(qs[:3])
-    _identical(r.nns(5).candidates_bitsets(mask).by_vectors(qs[:3]), want)
+    identical_hits(r.nns(5).candidates_bitsets(mask).by_vectors(qs[:3]), want)
     with pytest.raises(ValueError):
         r.nns(5).candidates_bitsets(mask).by_vectors(qs[:4])
     with pytest.raises(ValueError):

@@ -10,25 +10,15 @@ stored ring graph, which hny_build_incremental, hny_builder_load and the oracle 
 import numpy as np
 import pytest
 
+import support
 from conftest import draw_levels
 from synthetic_graphs import Ring
-from test_gpu_update import _check_delta, _same
-from test_gpu_update_passes import GRID_CAP, chunked_trip, _same_as_oracle
+from support import NO_COUNTERS, check_delta, hny, same_graph, same_hits  # noqa: F401
+from test_gpu_update_passes import GRID_CAP, chunked_trip
 
 pytestmark = pytest.mark.gpu
 
 EUCLIDEAN, HAMMING = 1, 3
-
-
-@pytest.fixture(scope="module")
-def hny():
-    import hannoy_amd
-    hannoy_amd.load_library()
-    return hannoy_amd
-
-
-def _vecs(rng, n, dim):
-    return rng.uniform(-1, 1, (n, dim)).astype(np.float32)
 
 
 # ---- k_move_lists<true>, k_diff_records on the upper layers (and k_fill_gaps_wg far past its grid) ---------------------
@@ -67,12 +57,12 @@ def test_upper_layer_lists_beyond_one_grid(orc, hny):
     to_delete = base[del_at]
     to_insert = np.sort(np.concatenate([base[over_at], base[new_at] + 1])).astype(np.uint32)
     assert len(to_delete) == UPPER_DEL and len(to_insert) == UPPER_NEW + 20
-    vecs0 = _vecs(rng, UPPER_N, dim)
+    vecs0 = support.vecs(rng, UPPER_N, dim)
     items0 = hny.ItemSet.from_f32(EUCLIDEAN, vecs0, ids=base, levels=np.ones(UPPER_N, np.uint8))
     ids1 = np.union1d(base[kept], to_insert).astype(np.uint32)
     vecs1 = np.empty((len(ids1), dim), np.float32)
     vecs1[np.searchsorted(ids1, base[kept])] = vecs0[kept]
-    up = _vecs(rng, len(to_insert), dim)
+    up = support.vecs(rng, len(to_insert), dim)
     vecs1[np.searchsorted(ids1, to_insert)] = up
     lv = np.ones(len(to_insert), np.uint8)  # every upsert on layer 1: the upper lists of the successor exceed a trip
     ds1 = orc.Dataset.from_f32(EUCLIDEAN, vecs1, np.zeros(len(ids1), np.uint8), ids1)
@@ -80,16 +70,16 @@ def test_upper_layer_lists_beyond_one_grid(orc, hny):
     kw = dict(M=M, M0=M, batch_frac=0.1, batch_max=256)
     o = orc.build_incremental(ds1, ring, to_insert, lv, to_delete, ef=ef, order=orc.ORDER_WAVE, **kw)
     ga = hny.build_incremental(items1, ring, to_insert, to_delete, ef_construction=ef, **kw)
-    _same_as_oracle(ga, o)
+    same_graph(ga, o, counters=NO_COUNTERS)
     c, h = hny.encode_vectors(EUCLIDEAN, up)
     with hny.Builder(items0, prev=ring, load=True, ef_construction=ef, **kw) as b:
         gb, d = b.update(to_insert, codes=c, headers=h, delete_ids=to_delete, levels=lv, delta=True)
         codes, hdrs = b.export_items()
         assert np.array_equal(b.items.ids, ids1)
         assert np.array_equal(codes, items1.codes) and np.array_equal(hdrs, items1.headers)
-    _same(ga, gb)
+    same_graph(ga, gb)
     assert (gb.rec_layer == 1).sum() == len(ids1) > UPPER_TRIP
-    _check_delta(ring.as_dict(), gb, d, to_delete)
+    check_delta(ring.as_dict(), gb, d, to_delete)
     # changed upper records on both sides of list 8 192 (the lists follow the items in id order)
     changed = sorted(i for (i, l) in d.as_dict() if l == 1)
     assert changed[0] < base[4000] and sum(i > base[UPPER_N - UPPER_TOP] for i in changed) >= 20
@@ -132,14 +122,14 @@ def test_export_in_several_pieces_and_shares(hny):
     want = ring.as_dict()
     assert len(want) == PIECES_N + int(levels.sum()) and (ring.rec_layer == 1).sum() == 300
     ep = int(ring.entry_points[0])
-    items = hny.ItemSet.from_f32(EUCLIDEAN, _vecs(np.random.default_rng(64), PIECES_N, dim), ids=base, levels=levels)
+    items = hny.ItemSet.from_f32(EUCLIDEAN, support.vecs(np.random.default_rng(64), PIECES_N, dim), ids=base, levels=levels)
     c, h = hny.encode_vectors(EUCLIDEAN, np.zeros((0, dim), np.float32))
     none = np.zeros(0, np.uint32)
     with hny.Builder(items, prev=ring, load=True, M=M, M0=M, ef_construction=ef, batch_frac=0.1, batch_max=256) as b:
         g, d = b.update(none, codes=c, headers=h, delete_ids=none, levels=np.zeros(0, np.uint8), delta=True)
         assert g.entry_points.tolist() == ring.entry_points.tolist() and g.max_level == ring.max_level == 1
         assert np.array_equal(g.rec_item, ring.rec_item) and np.array_equal(g.rec_layer, ring.rec_layer)
-        got = _check_delta(want, g, d, none)  # ring + delta == g, nothing unchanged in the delta, no key removed
+        got = check_delta(want, g, d, none)  # ring + delta == g, nothing unchanged in the delta, no key removed
         changed = {k for k in want if got[k] != want[k]}
         print(f"records that differ from the ring's: {len(changed)} of {len(want)}")
         assert changed == set(d.as_dict()) and len(d.removed_keys()) == 0 and len(changed) <= 2 * (1 + ef)
@@ -188,14 +178,14 @@ def test_deferred_targets_of_two_ranks_beyond_one_grid(orc, hny, dim, n, bmax, c
     import torch
     M, M0, ef = 3, 6, 12
     rng = np.random.default_rng(dim + n)
-    vecs = _vecs(rng, n, dim)
+    vecs = support.vecs(rng, n, dim)
     vecs[:, 8:] = 0.0
     items = hny.ItemSet.from_f32(EUCLIDEAN, vecs, levels=draw_levels(n, M, seed=dim))
     ds = orc.Dataset(EUCLIDEAN, dim, items.ids, items.codes, items.headers, items.levels)
     kw = dict(M=M, M0=M0, batch_frac=1.0, batch_max=bmax)
     o = orc.build(ds, ef=ef, order=orc.ORDER_WAVE, threads=orc.host_threads(), **kw)
     one_call = hny.build(items, ef_construction=ef, **kw)
-    _same_as_oracle(one_call, o)
+    same_graph(one_call, o, counters=NO_COUNTERS)
     dev = torch.device("cuda", 0)
     most = 0
     with hny.Builder(items, ef_construction=ef, **kw) as b0, hny.Builder(items, ef_construction=ef, **kw) as b1:
@@ -224,8 +214,8 @@ def test_deferred_targets_of_two_ranks_beyond_one_grid(orc, hny, dim, n, bmax, c
         g0, g1 = b0.finish(), b1.finish()
     assert most > cap * WORLD
     assert not merge or most > APPLY_MERGE_GRID
-    _same(g0, one_call)
-    _same(g1, one_call)
+    same_graph(g0, one_call)
+    same_graph(g1, one_call)
 
 
 # ---- strict mode: k_prune and the general k_walk (one wave per member) ------------------------------------------------
@@ -243,12 +233,12 @@ def test_strict_mode_batches_beyond_one_grid(orc, hny, monkeypatch):
     monkeypatch.setenv("HNY_WALK_SLOTS", str(STRICT_SLOTS))
     n, dim, M, M0, ef = 4600, 24, 6, 12, 24
     rng = np.random.default_rng(24)
-    ds = orc.Dataset.from_f32(EUCLIDEAN, _vecs(rng, n, dim), draw_levels(n, M, seed=24))
+    ds = orc.Dataset.from_f32(EUCLIDEAN, support.vecs(rng, n, dim), draw_levels(n, M, seed=24))
     items = hny.ItemSet(EUCLIDEAN, dim, ds.ids, ds.codes, ds.headers, ds.levels)
     kw = dict(M=M, M0=M0, batch_frac=1.0, batch_max=STRICT_BATCH)
     o = orc.build(ds, ef=ef, order=orc.ORDER_X86, threads=orc.host_threads(), **kw)
     g = hny.build(items, ef_construction=ef, x86_order=True, **kw)
-    _same_as_oracle(g, o)
+    same_graph(g, o, counters=NO_COUNTERS)
     assert g.n_links_added == o.n_links_added and g.n_evals_walk == o.n_evals_walk
     upper, level0 = int((ds.levels > 0).sum()), int((ds.levels == 0).sum())
     assert 3 * upper >= STRICT_BATCH and level0 - 3 * upper >= STRICT_BATCH  # 740, 1 480, then a batch of 1 501
@@ -271,7 +261,7 @@ def test_ingest_chunk_beyond_one_grid(hny, case):
     take per trip: 262 221 Cosine rows of 8 dimensions (32 rows per block), 131 149 Hamming rows of 64 (16 per block).
     export_items() is byte for byte numpy's own encoding of the rows, and the host encoder's codes and headers."""
     metric, dim, n = INGEST[case]
-    v = _vecs(np.random.default_rng(n), n, dim)
+    v = support.vecs(np.random.default_rng(n), n, dim)
     levels = np.zeros(n, np.uint8)
     levels[n // 2] = 1  # one item on the top layer: one entry point
     with hny.Builder(hny.F32ItemSet(metric, v, levels=levels), M=2, M0=2, ef_construction=1) as b:
@@ -304,28 +294,22 @@ def test_searches_with_fewer_slots_than_queries(orc, hny, monkeypatch):
     monkeypatch.setenv("HNY_WALK_SLOTS", str(SEARCH_SLOTS))
     n, dim, M, M0, ef = 1500, 24, 6, 12, 32
     rng = np.random.default_rng(48)
-    ds = orc.Dataset.from_f32(EUCLIDEAN, _vecs(rng, n, dim), draw_levels(n, M, seed=48), np.arange(n, dtype=np.uint32) * 3 + 1)
-    qs = _vecs(rng, SEARCH_NQ, dim)
+    ds = orc.Dataset.from_f32(EUCLIDEAN, support.vecs(rng, n, dim), draw_levels(n, M, seed=48), np.arange(n, dtype=np.uint32) * 3 + 1)
+    qs = support.vecs(rng, SEARCH_NQ, dim)
     qc = orc.encode_vectors(EUCLIDEAN, qs)
     qh = orc.make_headers(EUCLIDEAN, dim, qc)
     cand = np.concatenate([ds.ids[rng.random(n) < 0.4], [0, 2, 10 ** 7]]).astype(np.uint32)
 
-    def same(got, want, tag):
-        assert np.array_equal(got[2], want[2]), tag
-        for r in range(SEARCH_NQ):
-            c = int(got[2][r])
-            assert np.array_equal(got[0][r, :c], want[0][r, :c]), (tag, r)
-            assert np.array_equal(got[1][r, :c].view(np.uint32), want[1][r, :c].view(np.uint32)), (tag, r)
     with hny.Builder(hny.ItemSet(EUCLIDEAN, dim, ds.ids, ds.codes, ds.headers, ds.levels), M=M, M0=M0, ef_construction=ef,
                      batch_frac=0.1, batch_max=128) as b:
         b.run()
         g = b.finish()
         want = orc.search(ds, g, qc, qh, k=10, ef_search=32, order=orc.ORDER_WAVE, threads=8)
         assert (want[2] == 10).all()
-        same(b.search_knn(qc, qh, k=10, ef_search=32), want, "knn")
+        same_hits(b.search_knn(qc, qh, k=10, ef_search=32), want, "knn")
         monkeypatch.setenv("HNY_POOL_FORCE_RETRY", "3")
-        same(b.search_knn(qc, qh, k=10, ef_search=32), want, "knn, every third query on the heap searcher")
+        same_hits(b.search_knn(qc, qh, k=10, ef_search=32), want, "knn, every third query on the heap searcher")
         monkeypatch.delenv("HNY_POOL_FORCE_RETRY")
         for linear_below, tag in ((0, "filtered on the graph"), (2 ** 32 - 1, "filtered, linear scan")):
             kw = dict(k=10, ef_search=32, candidates=cand, linear_below=linear_below)
-            same(b.nns(qc, qh, **kw), orc.search(ds, g, qc, qh, order=orc.ORDER_WAVE, threads=8, **kw), tag)
+            same_hits(b.nns(qc, qh, **kw), orc.search(ds, g, qc, qh, order=orc.ORDER_WAVE, threads=8, **kw), tag)

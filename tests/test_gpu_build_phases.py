@@ -22,6 +22,7 @@ import pytest
 
 import crafted_selections as cs
 from conftest import draw_levels
+from support import LINKS, hny, same_graph, vecs  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -47,17 +48,6 @@ assert _source_has("hny_kernels.hip", "for (u32 sg = blockIdx.x; sg < n_seg; sg 
 FROZEN = 1 << 31
 
 
-@pytest.fixture(scope="module")
-def hny():
-    import hannoy_amd
-    hannoy_amd.load_library()
-    return hannoy_amd
-
-
-def _vecs(rng, n, dim):
-    return rng.uniform(-1, 1, (n, dim)).astype(np.float32)
-
-
 # name -> (metric, dim, n, M, M0, ef, strict)
 CASES = {
     "short-rows-32B": (EUCLIDEAN, 8, 3000, 3, 6, 12, False),      # k_walk_n8 / k_prune_n8 / k_apply_n8
@@ -75,17 +65,10 @@ def _case(orc, hny, name, n=None, M0=None):
     rng = np.random.default_rng(dim + n)
     levels = draw_levels(n, M, seed=dim)
     assert levels.max() >= 2  # three or more layers
-    ds = orc.Dataset.from_f32(metric, _vecs(rng, n, dim), levels)
+    ds = orc.Dataset.from_f32(metric, vecs(rng, n, dim), levels)
     items = hny.ItemSet(metric, dim, ds.ids, ds.codes, ds.headers, ds.levels)
     kw = dict(M=M, M0=M0 or M0_, batch_frac=1.0, batch_max=BATCH_MAX)
     return ds, items, kw, ef, strict
-
-
-def _same_graph(g, o):
-    assert g.entry_points.tolist() == o.entry_points.tolist() and g.max_level == o.max_level
-    assert np.array_equal(g.rec_item, o.rec_item) and np.array_equal(g.rec_layer, o.rec_layer)
-    assert np.array_equal(g.offsets, o.offsets) and np.array_equal(g.nbrs, o.nbrs)
-    assert g.n_links_added == o.n_links_added
 
 
 def _same_batch(bt, ob):
@@ -148,7 +131,7 @@ def test_selection_of_every_batch_equals_oracle(orc, hny, name):
             b.sync()  # the buffer is released in the next turn
         g, o = b.finish(), st.finish()
     assert len(layers) >= 3
-    _same_graph(g, o)
+    same_graph(g, o, counters=LINKS)
     assert g.n_evals_walk == o.n_evals_walk
 
 
@@ -191,7 +174,7 @@ def test_search_in_uneven_slices(orc, hny):
             whole.sync()
         g, w = b.finish(), whole.finish()
     assert cut >= 8
-    _same_graph(g, w)
+    same_graph(g, w, counters=LINKS)
 
 
 # ---- the link phase through the two-replica apply: exchange records ------------------------------------------------------
@@ -291,8 +274,8 @@ def test_raw_lists_of_repruned_targets(orc, hny, name):
     print(f"{name}: {n_batches} batches, {deferring} deferring, {n_recs} records, {n_frozen} frozen, {n_short} short")
     # what the case is for: most batches defer, and both outcomes of a re-prune occur
     assert 2 * deferring >= n_batches and n_recs > 0 and n_frozen > 0 and n_short > 0
-    _same_graph(g0, o)
-    _same_graph(g1, o)
+    same_graph(g0, o, counters=LINKS)
+    same_graph(g1, o, counters=LINKS)
 
 
 # ---- the link phase on hand-made selections -----------------------------------------------------------------------------
@@ -345,7 +328,7 @@ def _run_scenario(orc, hny, scen, two_replicas=False):
 def _same_flat_graph(g, o):
     """whole arrays: the graphs, the counters, and the raw counts (crafted targets are distinct and nothing is pruned
     unless the oracle prunes it too, so a record's length is its raw count wherever the oracle's is)"""
-    _same_graph(g, o)
+    same_graph(g, o, counters=LINKS)
     assert np.array_equal(np.diff(g.offsets.astype(np.int64)), np.diff(o.raw_offsets.astype(np.int64)))
 
 
@@ -380,7 +363,7 @@ def test_one_target_of_256_members(orc, hny, name):
     assert scen.chosen[0][1] == 1 + 3 * cs.Hub.HUB_BATCH
     assert recs is not None and (0, scen.hub) in recs.keys  # _check_records compared it
     for g in graphs:
-        _same_graph(g, o)
+        same_graph(g, o, counters=LINKS)
 
 
 def test_rows_with_an_empty_layer(orc, hny):
@@ -389,4 +372,4 @@ def test_rows_with_an_empty_layer(orc, hny):
     middle of each row, which the sort moves behind the last segment for k_segments.  The graph is the stepper's."""
     scen = cs.SCENARIOS["empty-layers"](orc)
     (g,), o, _ = _run_scenario(orc, hny, scen)
-    _same_graph(g, o)
+    same_graph(g, o, counters=LINKS)

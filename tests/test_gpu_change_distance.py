@@ -7,8 +7,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import support
 from conftest import draw_levels
-from test_gpu_update import World, _check_delta, _same
+from support import check_delta, hny, same_graph  # noqa: F401
+from test_gpu_update import World
 
 pytestmark = pytest.mark.gpu
 
@@ -17,17 +19,6 @@ F32 = (COSINE, EUCLIDEAN, MANHATTAN)
 PAIRS = [(old, new) for old in F32 for new in range(7) if new != old]
 KEPT = {(COSINE, BQ_COSINE), (EUCLIDEAN, BQ_EUCLIDEAN), (MANHATTAN, BQ_MANHATTAN)}
 assert len(PAIRS) == 18 and KEPT <= set(PAIRS)
-
-
-@pytest.fixture(scope="module")
-def hny():
-    import hannoy_amd
-    hannoy_amd.load_library()
-    return hannoy_amd
-
-
-def _vecs(seed, n, dim):
-    return np.random.default_rng(seed).uniform(-1, 1, (n, dim)).astype(np.float32)
 
 
 def _source(hny, metric, vecs, ids, levels, kw):
@@ -48,7 +39,7 @@ def _host_route(hny, old, new, vecs, ids, levels, g_src, to_delete, kw, seed=42)
 def _run_and_compare(succ, items, want):
     succ.run()
     g = succ.finish()
-    _same(want, g)
+    same_graph(want, g)
     codes, hdrs = succ.export_items()
     assert np.array_equal(succ.items.ids, items.ids)
     assert np.array_equal(codes, items.codes) and np.array_equal(hdrs, items.headers)
@@ -70,7 +61,7 @@ KW18 = dict(M=8, M0=16, ef_construction=32, batch_frac=0.1, batch_max=64)
 @pytest.fixture(scope="module")
 def sources18(hny):
     """one finished source builder per f32 distance, shared by the 18 pairs (a source stays intact)"""
-    vecs = _vecs(18, N18, DIM18)
+    vecs = support.vecs(18, N18, DIM18)
     ids = (np.arange(N18, dtype=np.uint32) * 3 + 1)
     out = {m: _source(hny, m, vecs, ids, draw_levels(N18, 8, seed=1), KW18) for m in F32}
     yield vecs, ids, out
@@ -108,7 +99,7 @@ EDGE_PAIRS = [(COSINE, BQ_COSINE), (EUCLIDEAN, COSINE), (COSINE, HAMMING)]
 def test_row_shape_edges(hny, dim):
     n, M = 300, 4
     kw = dict(M=M, M0=8, ef_construction=16, batch_frac=0.2, batch_max=64)
-    vecs = _vecs(dim, n, dim)
+    vecs = support.vecs(dim, n, dim)
     ids = np.arange(n, dtype=np.uint32)
     srcs = {}
     try:
@@ -205,7 +196,7 @@ def test_update_in_the_same_build(hny, old, new, M, M0, as_f32):
     n, dim = 600, 40
     kw = dict(M=M, M0=M0, ef_construction=32, batch_frac=0.1, batch_max=64)
     rng = np.random.default_rng(M0 + new)
-    vecs = _vecs(1, n, dim)
+    vecs = support.vecs(1, n, dim)
     ids = np.arange(n, dtype=np.uint32) * 2
     b, g_src = _source(hny, old, vecs, ids, draw_levels(n, M, seed=1), kw)
     try:
@@ -213,7 +204,7 @@ def test_update_in_the_same_build(hny, old, new, M, M0, as_f32):
         kept = np.setdiff1d(ids, to_delete)
         up_ids = np.sort(np.concatenate([kept[[17]], np.arange(40, dtype=np.uint32) * 2 + 301])).astype(np.uint32)
         assert len(np.intersect1d(up_ids, ids)) == 1  # one overwritten item, 40 new ones between the old ids
-        up_vecs = _vecs(2, len(up_ids), dim)
+        up_vecs = support.vecs(2, len(up_ids), dim)
         table = {int(i): vecs[r] for r, i in enumerate(ids) if i in set(kept.tolist())}
         table.update({int(i): up_vecs[r] for r, i in enumerate(up_ids)})
         ids_new = np.array(sorted(table), np.uint32)
@@ -228,7 +219,7 @@ def test_update_in_the_same_build(hny, old, new, M, M0, as_f32):
         with b.create_changed_distance(new, levels=lv, seed=5, upsert_ids=up_ids, delete_ids=to_delete, **up) as s:
             g = _run_and_compare(s, items, want)
             if (old, new) in KEPT:
-                _check_delta(g_src.as_dict(), g, s.finish_delta(), to_delete)
+                check_delta(g_src.as_dict(), g, s.finish_delta(), to_delete)
             else:
                 with pytest.raises(hny.HannoyError) as e:
                     s.finish_delta()
@@ -243,7 +234,7 @@ def test_update_in_the_same_build(hny, old, new, M, M0, as_f32):
 def test_strict_mode_is_inherited(hny, old, new):
     n, dim, M = 400, 33, 6
     kw = dict(M=M, M0=12, ef_construction=24, batch_frac=0.1, batch_max=32, x86_order=True)
-    vecs = _vecs(6, n, dim)
+    vecs = support.vecs(6, n, dim)
     ids = np.arange(n, dtype=np.uint32)
     b, g_src = _source(hny, old, vecs, ids, draw_levels(n, M, seed=1), kw)
     try:
@@ -270,7 +261,7 @@ def test_more_rows_than_one_trip(hny):
     Hamming successor is built and compared with hny_build."""
     n, dim, M = SECOND_TRIP_N, 4, 2
     kw = dict(M=M, M0=2, ef_construction=1, batch_frac=1.0, batch_max=65536)
-    v = _vecs(n, n, dim)
+    v = support.vecs(n, n, dim)
     ids = np.arange(n, dtype=np.uint32)
     lv = np.zeros(n, np.uint8)
     lv[n // 2] = 1  # one item on the top layer: one entry point
@@ -288,7 +279,7 @@ def test_more_rows_than_one_trip(hny):
                 assert np.array_equal(ec, want) and np.array_equal(eh, hh)
                 if new == HAMMING:
                     s.run()
-                    _same(hny.build(hny.ItemSet(new, dim, ids, hc, hh, lv), **kw), s.finish())
+                    same_graph(hny.build(hny.ItemSet(new, dim, ids, hc, hh, lv), **kw), s.finish())
     finally:
         b.close()
 
@@ -299,7 +290,7 @@ def test_refusals(hny):
     L = capi.load_library()
     n, dim, M = 300, 24, 4
     kw = dict(M=M, M0=8, ef_construction=16, batch_frac=0.2, batch_max=64)
-    vecs = _vecs(8, n, dim)
+    vecs = support.vecs(8, n, dim)
     ids = np.arange(n, dtype=np.uint32)
     lv = draw_levels(n, M, seed=1)
     b, g_src = _source(hny, COSINE, vecs, ids, lv, kw)

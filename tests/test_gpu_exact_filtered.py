@@ -10,6 +10,7 @@ import pytest
 
 from conftest import draw_levels
 from synthetic_graphs import Ring as _Ring
+from support import hny, prefilled, queries, same_hits, untouched  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -19,13 +20,6 @@ COSINE, EUCLIDEAN, MANHATTAN, HAMMING = range(4)
 SLAB = 65536  # HNY_EXACT_SLAB
 EDGES = [32, 64, 128, 256, 512, 768, 1024, 1536, 2048, 3072, 4096]  # the upper edge of the eleven row shapes
 N, NQ = 1501, 69  # as in test_gpu_exact_knn.py: no multiple of any rows-per-pass; two tiles of 32 and a ragged one
-
-
-@pytest.fixture(scope="module")
-def hny():
-    import hannoy_amd
-    hannoy_amd.load_library()
-    return hannoy_amd
 
 
 def _built(orc, hny, metric, vecs, ids=None, M=4, M0=8, ef=8, **kw):
@@ -46,22 +40,6 @@ def _loaded(orc, hny, metric, vecs, ids=None):
     items = hny.ItemSet(metric, dim, ds.ids, ds.codes, ds.headers, ds.levels)
     g = _Ring(ds.ids)
     return ds, hny.Builder(items, prev=g, load=True, M=2, M0=2, ef_construction=1), g
-
-
-def _queries(orc, metric, rng, nq, dim):
-    qs = rng.uniform(-1, 1, (nq, dim)).astype(np.float32)
-    qc = orc.encode_vectors(metric, qs)
-    return qs, qc, orc.make_headers(metric, dim, qc)
-
-
-def _same(got, want, tag=None):
-    ids, dists, counts = got
-    oids, odists, ocounts = want
-    assert np.array_equal(counts, ocounts), tag
-    for r in range(len(counts)):
-        c = 0 if counts[r] == NONE else int(counts[r])
-        assert np.array_equal(ids[r, :c], oids[r, :c]), (tag, r)
-        assert np.array_equal(dists[r, :c].view(np.uint32), odists[r, :c].view(np.uint32)), (tag, r)
 
 
 def _per_group(filters, filter_of, k, run):
@@ -100,8 +78,8 @@ def _check(orc, b, ds, g, filters, fo, k, qc=None, qh=None, qi=None, order=None,
         got = b.exact_knn_filtered(filters, fo, query_items=qi, k=k)
     else:
         got = b.exact_knn_filtered(filters, fo, qc, qh, k=k)
-    _same(got, _loop(b, filters, fo, k, qc, qh, qi), (tag, "loop"))
-    _same(got, _oracle(orc, ds, g, filters, fo, k, qc, qh, qi, order), (tag, "oracle"))
+    same_hits(got, _loop(b, filters, fo, k, qc, qh, qi), (tag, "loop"))
+    same_hits(got, _oracle(orc, ds, g, filters, fo, k, qc, qh, qi, order), (tag, "oracle"))
     return got
 
 
@@ -126,14 +104,6 @@ def _raw(hny, b, filters, filter_of, qc, qh, out, k=10, qstride=None, edit=None,
                                             qc.shape[1] if qstride is None else qstride, p(qh), None, *map(p, out))
 
 
-def _prefilled(nq, k):
-    return np.full((nq, k), 77, np.uint32), np.full((nq, k), 7.5, np.float32), np.full(nq, 77, np.uint32)
-
-
-def _untouched(out):
-    return (out[0] == 77).all() and (out[1] == 7.5).all() and (out[2] == 77).all()
-
-
 def _mixed_filters(rng, ids):
     n = len(ids)
     junk = np.array([0, 2, 10 ** 7], np.uint32)  # unknown ids (ids are 3 i + 1)
@@ -155,7 +125,7 @@ def test_mixed_batch(orc, hny, metric, dim):
     rng = np.random.default_rng(50 + metric)
     ids = np.arange(N, dtype=np.uint32) * 3 + 1
     ds, b, g = _built(orc, hny, metric, rng.uniform(-1, 1, (N, dim)).astype(np.float32), ids=ids)
-    _, qc, qh = _queries(orc, metric, rng, NQ, dim)
+    _, qc, qh = queries(orc, metric, rng, NQ, dim)
     filters = _mixed_filters(rng, ids)
     live = [len(set(f.tolist()) & set(ids.tolist())) for f in filters]
     assert live[0] * 32 >= N and live[1] * 32 >= N and live[5] * 32 >= N and 0 < live[2] * 32 < N
@@ -170,10 +140,10 @@ def test_mixed_batch(orc, hny, metric, dim):
                 assert all(int(v) in allowed for r in np.flatnonzero(fo == f) for v in got[0][r])
             # k beyond the small filters: rows of different lengths in one call, nothing written past a row's count
             k = 40
-            out = _prefilled(NQ, k)
+            out = prefilled(NQ, k)
             assert _raw(hny, b, filters, fo, qc, qh, out, k=k) == hny._capi.OK
             want = _loop(b, filters, fo, k, qc, qh)
-            _same(out, want, tag)
+            same_hits(out, want, tag)
             assert (out[2][fo == 2] == 30).all() and (out[2][fo == 0] == k).all()
             for r in range(NQ):
                 assert (out[0][r, out[2][r]:] == 77).all() and (out[1][r, out[2][r]:] == 7.5).all(), (tag, r)
@@ -187,7 +157,7 @@ def test_every_row_shape(orc, hny, dim):
     every (rows per load group, load groups, fold)"""
     rng = np.random.default_rng(dim)
     ds, b, g = _built(orc, hny, EUCLIDEAN, rng.uniform(-1, 1, (N, dim)).astype(np.float32))  # ids == slots
-    _, qc, qh = _queries(orc, EUCLIDEAN, rng, NQ, dim)
+    _, qc, qh = queries(orc, EUCLIDEAN, rng, NQ, dim)
     ids = ds.ids
     filters = [ids[517:1033], ids[::7], ids[rng.random(N) < 0.3]]
     with b:
@@ -201,7 +171,7 @@ def test_skipping_happens_and_is_bounded(orc, hny, monkeypatch):
     rng = np.random.default_rng(3)
     dim, nq, L = 768, 64, 516
     ds, b, g = _built(orc, hny, COSINE, rng.uniform(-1, 1, (N, dim)).astype(np.float32))
-    _, qc, qh = _queries(orc, COSINE, rng, nq, dim)
+    _, qc, qh = queries(orc, COSINE, rng, nq, dim)
     tiles = nq // 16  # rows of 3 072 B: 16 queries per tile (hnyk_exact_qt)
     filters, fo = [ds.ids[517:517 + L]], np.zeros(nq, int)
     with b:
@@ -222,7 +192,7 @@ def test_a_k_per_query(orc, hny):
     rng = np.random.default_rng(4)
     dim = 24
     ds, b, g = _built(orc, hny, EUCLIDEAN, rng.uniform(-1, 1, (N, dim)).astype(np.float32))
-    _, qc, qh = _queries(orc, EUCLIDEAN, rng, NQ, dim)
+    _, qc, qh = queries(orc, EUCLIDEAN, rng, NQ, dim)
     with b:
         # 3 and 1 500 candidates, neighbours in the batch.  (3 x 32 < 1 501: the short filter is gathered here and
         # only the batch is shared; the 90-item index below is where both sit in one tile of the dense scan)
@@ -325,7 +295,7 @@ def test_deleted_slots(orc, hny):
     keep = ~np.isin(ids, gone)
     ds2 = orc.Dataset.from_f32(EUCLIDEAN, vecs[keep], np.zeros(0, np.uint8), ids[keep])
     items2 = hny.ItemSet(EUCLIDEAN, dim, ds2.ids, ds2.codes, ds2.headers, ds2.levels)
-    _, qc, qh = _queries(orc, EUCLIDEAN, rng, NQ, dim)
+    _, qc, qh = queries(orc, EUCLIDEAN, rng, NQ, dim)
     filters = [np.concatenate([gone, ids[keep][:700]]), gone, np.concatenate([gone[:50], ids[keep][-20:]]),
                ids[rng.random(N) < 0.4]]
     fo = np.arange(NQ) % 5 - 1
@@ -362,7 +332,7 @@ def test_strict_mode(orc, hny, dim):
     n = 400
     ds, b, g = _built(orc, hny, EUCLIDEAN, rng.uniform(-1, 1, (n, dim)).astype(np.float32), x86_order=True,
                       batch_frac=0.0, batch_max=1)
-    _, qc, qh = _queries(orc, EUCLIDEAN, rng, NQ, dim)
+    _, qc, qh = queries(orc, EUCLIDEAN, rng, NQ, dim)
     filters = [ds.ids[rng.random(n) < 0.5], rng.choice(ds.ids, 7, replace=False), np.zeros(0, np.uint32)]
     fo = np.arange(NQ) % 4 - 1
     qi = ds.ids[rng.integers(0, n, NQ)]
@@ -380,7 +350,7 @@ def test_several_mask_rounds_and_query_blocks(orc, hny, monkeypatch):
     dim, nq = 8, 1100
     ids = np.arange(N, dtype=np.uint32) * 3 + 1
     ds, b, g = _built(orc, hny, EUCLIDEAN, rng.uniform(-1, 1, (N, dim)).astype(np.float32), ids=ids)
-    _, qc, qh = _queries(orc, EUCLIDEAN, rng, nq, dim)
+    _, qc, qh = queries(orc, EUCLIDEAN, rng, nq, dim)
     filters = [ids[rng.random(N) < p] for p in (0.5, 0.2, 0.01, 0.3, 0.08)]
     fo = rng.integers(-1, 5, nq)
     with b:
@@ -404,13 +374,13 @@ def test_special_values(orc, hny):
     v[200, 5] = np.inf
     v[300] = 0.0
     ds, b, g = _built(orc, hny, COSINE, v)
-    _, qc, qh = _queries(orc, COSINE, rng, NQ, dim)
+    _, qc, qh = queries(orc, COSINE, rng, NQ, dim)
     filters = [ds.ids[90:310], ds.ids[rng.random(n) < 0.5]]
     fo = np.arange(NQ) % 3 - 1
     with b:
         for k in (10, 220):
             got = b.exact_knn_filtered(filters, fo, qc, qh, k=k)
-            _same(got, _loop(b, filters, fo, k, qc, qh), k)
+            same_hits(got, _loop(b, filters, fo, k, qc, qh), k)
             oids, odists, ocounts = _oracle(orc, ds, g, filters, fo, k, qc, qh)
             assert np.array_equal(got[2], ocounts)
             for r in range(NQ):
@@ -428,7 +398,7 @@ def test_refusals_leave_the_outputs_alone(orc, hny):
     rng = np.random.default_rng(12)
     dim, k = 24, 10
     ds, b, g = _loaded(orc, hny, EUCLIDEAN, rng.uniform(-1, 1, (5000, dim)).astype(np.float32))
-    qs, qc, qh = _queries(orc, EUCLIDEAN, rng, NQ, dim)
+    qs, qc, qh = queries(orc, EUCLIDEAN, rng, NQ, dim)
     filters = [ds.ids[:2000], ds.ids[100:130], ds.ids[::3]]
     fo = np.arange(NQ) % 4 - 1
     capi = hny._capi
@@ -469,16 +439,16 @@ def test_refusals_leave_the_outputs_alone(orc, hny):
              (DIM, dict(qstride=qc.shape[1] - 1)), (DIM, dict(f32=qs, qstride=dim * 4 - 4)), (INV, dict(k=0))]
     with b:
         for code, kw in cases:
-            out = _prefilled(NQ, k)
+            out = prefilled(NQ, k)
             assert _raw(hny, b, filters, fo, qc, qh, out, **kw) == code, kw
             assert L.hny_last_error(), kw
-            assert _untouched(out), kw
+            assert untouched(out), kw
         # NULL arguments
         qo = capi.QueryOpts()
         qo.k = k
         qf, keep = capi.QueryFilters.pack(filters, fo)
         p = capi._p
-        out = _prefilled(NQ, k)
+        out = prefilled(NQ, k)
         args = [b._h, C.byref(qo), C.byref(qf), NQ, p(qc), qc.shape[1], p(qh), None, p(out[0]), p(out[1]), p(out[2])]
         for hole in (0, 1, 2, 4, 6, 8, 9, 10):
             a = list(args)
@@ -487,22 +457,22 @@ def test_refusals_leave_the_outputs_alone(orc, hny):
             assert L.hny_last_error(), hole
         assert L.hny_builder_exact_knn_filtered_f32(b._h, C.byref(qo), C.byref(qf), NQ, None, dim * 4, p(out[0]),
                                                     p(out[1]), p(out[2])) == INV
-        assert _untouched(out)
+        assert untouched(out)
         # more than 4 095 hits: a filter of 4 096 live candidates at k = 4 096, and the live items for a query
         # without a filter, for the whole call
         big = [ds.ids[:2000], ds.ids[200:200 + 4096]]
         for fo2 in (np.arange(NQ) % 2, np.r_[np.zeros(NQ - 1, int), -1]):
-            out = _prefilled(NQ, 4096)
+            out = prefilled(NQ, 4096)
             assert _raw(hny, b, big, fo2, qc, qh, out, k=4096) == capi.ERR_UNSUPPORTED
             assert "4095" in L.hny_last_error().decode()
-            assert _untouched(out)
+            assert untouched(out)
         # a filter that no query uses does not count, and the same arguments unbent are accepted
-        out = _prefilled(NQ, 4096)
+        out = prefilled(NQ, 4096)
         assert _raw(hny, b, big, np.zeros(NQ, int), qc, qh, out, k=4096) == capi.OK
         assert (out[2] == 2000).all()
-        out = _prefilled(NQ, k)
+        out = prefilled(NQ, k)
         assert _raw(hny, b, filters, fo, qc, qh, out) == capi.OK
-        _same(out, _loop(b, filters, fo, k, qc, qh))
+        same_hits(out, _loop(b, filters, fo, k, qc, qh))
 
 
 # 13 ------------------------------------------------------------------------------------------------------------
@@ -511,7 +481,7 @@ def test_cancellation(orc, hny):
     dim = 16
     ids = np.arange(N, dtype=np.uint32) * 3 + 1
     ds, b, g = _built(orc, hny, EUCLIDEAN, rng.uniform(-1, 1, (N, dim)).astype(np.float32), ids=ids)
-    _, qc, qh = _queries(orc, EUCLIDEAN, rng, NQ, dim)
+    _, qc, qh = queries(orc, EUCLIDEAN, rng, NQ, dim)
     filters = _mixed_filters(rng, ids)
     fo = np.arange(NQ) % 7 - 1
     with b:
@@ -590,16 +560,16 @@ def test_strict_live_set_across_mask_rounds(orc, hny, strict600, monkeypatch, n_
         filters[2] = np.arange(n, n + 60, dtype=np.uint32)  # ids == slots: none of these is known
     fo = rng.permutation(np.concatenate([np.full(2 + f % 2, f) for f in range(-1, n_filters)]))
     nq = len(fo)
-    _, qc, qh = _queries(orc, EUCLIDEAN, rng, nq, 8)
+    _, qc, qh = queries(orc, EUCLIDEAN, rng, nq, 8)
     qi = ds.ids[rng.integers(0, n, nq)].astype(np.uint32)
     qi[int(np.flatnonzero(fo == 1)[0])] = 10 ** 6
     stride_bytes = ((n + 31) // 32 + 4) // 4 * 4 * 4
     monkeypatch.setenv("HNY_FILTER_MASK_BYTES", str(2 * stride_bytes + 8))
     got = b.exact_knn_filtered(filters, fo, qc, qh, k=k)
-    _same(got, _loop(b, filters, fo, k, qc, qh), "by_vector")
+    same_hits(got, _loop(b, filters, fo, k, qc, qh), "by_vector")
     assert (got[2][fo != 2] == k).all() and (got[2][fo == 2] == (0 if empty else k)).all()
     got = b.exact_knn_filtered(filters, fo, query_items=qi, k=k)
-    _same(got, _loop(b, filters, fo, k, qi=qi), "by_item")
+    same_hits(got, _loop(b, filters, fo, k, qi=qi), "by_item")
     known = qi != 10 ** 6
     assert (got[2][~known] == NONE).all() and (got[2][known & (fo != 2)] == k).all()
     assert (got[2][known & (fo == 2)] == (NONE if empty else k)).all() and b.exact_rows_read() == 0

@@ -7,6 +7,7 @@ import pytest
 
 from conftest import draw_levels
 from synthetic_graphs import Ring as _Ring
+from support import hny, queries, same_hits  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -17,13 +18,6 @@ SLAB = 65536  # HNY_EXACT_SLAB
 EDGES = [(1, 32), (33, 64), (65, 128), (129, 256), (257, 512), (513, 768), (769, 1024), (1025, 1536), (1537, 2048),
          (2049, 3072), (3073, 4096)]
 N, NQ = 1501, 69  # 1 501: no multiple of any rows-per-pass; 69: two tiles of 32 and a ragged one, no multiple of 4 or 16
-
-
-@pytest.fixture(scope="module")
-def hny():
-    import hannoy_amd
-    hannoy_amd.load_library()
-    return hannoy_amd
 
 
 def _built(orc, hny, metric, vecs, ids=None, M=4, M0=8, ef=8, **kw):
@@ -46,22 +40,6 @@ def _loaded(orc, hny, metric, vecs, ids=None):
     return ds, hny.Builder(items, prev=g, load=True, M=2, M0=2, ef_construction=1), g
 
 
-def _queries(orc, metric, rng, nq, dim):
-    qs = rng.uniform(-1, 1, (nq, dim)).astype(np.float32)
-    qc = orc.encode_vectors(metric, qs)
-    return qs, qc, orc.make_headers(metric, dim, qc)
-
-
-def _same(got, want, tag=None):
-    ids, dists, counts = got
-    oids, odists, ocounts = want
-    assert np.array_equal(counts, ocounts), tag
-    for r in range(len(counts)):
-        c = 0 if counts[r] == 0xFFFFFFFF else int(counts[r])
-        assert np.array_equal(ids[r, :c], oids[r, :c]), (tag, r)
-        assert np.array_equal(dists[r, :c].view(np.uint32), odists[r, :c].view(np.uint32)), (tag, r)
-
-
 def _want(orc, ds, g, qc, qh, k, cand=None, order=None, query_items=None):
     """the oracle's brute_force_search over `cand` (default: every item)"""
     return orc.search(ds, g, qc, qh, k=k, order=orc.ORDER_WAVE if order is None else order, threads=8,
@@ -73,11 +51,11 @@ def _want(orc, ds, g, qc, qh, k, cand=None, order=None, query_items=None):
 def test_every_row_shape(orc, hny, metric, dim):
     rng = np.random.default_rng(1000 * metric + dim)
     ds, b, g = _built(orc, hny, metric, rng.uniform(-1, 1, (N, dim)).astype(np.float32))
-    _, qc, qh = _queries(orc, metric, rng, NQ, dim)
+    _, qc, qh = queries(orc, metric, rng, NQ, dim)
     with b:
         got = b.exact_knn(qc, qh, k=10)
     assert (got[2] == 10).all()
-    _same(got, _want(orc, ds, g, qc, qh, 10))
+    same_hits(got, _want(orc, ds, g, qc, qh, 10))
 
 
 @pytest.mark.parametrize("metric", [HAMMING, BQ_COSINE, BQ_EUCLIDEAN, BQ_MANHATTAN],
@@ -86,10 +64,10 @@ def test_every_row_shape(orc, hny, metric, dim):
 def test_binary_metrics(orc, hny, metric, dim):
     rng = np.random.default_rng(77 * metric + dim)
     ds, b, g = _built(orc, hny, metric, rng.uniform(-1, 1, (N, dim)).astype(np.float32))
-    _, qc, qh = _queries(orc, metric, rng, NQ, dim)
+    _, qc, qh = queries(orc, metric, rng, NQ, dim)
     with b:
         got = b.exact_knn(qc, qh, k=10)
-    _same(got, _want(orc, ds, g, qc, qh, 10))
+    same_hits(got, _want(orc, ds, g, qc, qh, 10))
 
 
 def test_hamming_64_bit_codes_are_all_ties(orc, hny):
@@ -97,12 +75,12 @@ def test_hamming_64_bit_codes_are_all_ties(orc, hny):
     rng = np.random.default_rng(64)
     ds, b, g = _built(orc, hny, HAMMING, rng.uniform(-1, 1, (N, 64)).astype(np.float32),
                       ids=np.arange(N, dtype=np.uint32) * 3 + 1)
-    _, qc, qh = _queries(orc, HAMMING, rng, NQ, 64)
+    _, qc, qh = queries(orc, HAMMING, rng, NQ, 64)
     with b:
         got = b.exact_knn(qc, qh, k=50)
     assert (got[2] == 50).all()
     assert min(len(np.unique(got[1][r])) for r in range(NQ)) < 50  # ties inside the result
-    _same(got, _want(orc, ds, g, qc, qh, 50))
+    same_hits(got, _want(orc, ds, g, qc, qh, 50))
 
 
 @pytest.mark.parametrize("metric,dim", [(EUCLIDEAN, 8), (HAMMING, 64)], ids=["euclidean-8", "hamming-64"])
@@ -129,34 +107,34 @@ def test_slab_boundary(orc, hny, metric, dim):
         assert set(slots) <= set(hits), qi
         if metric == EUCLIDEAN:  # (64-bit codes: other rows may share the query's code; ids decide)
             assert hits[:4] == slots and not got[1][qi, :4].any(), qi
-    _same(got, _want(orc, ds, g, qc, qh, 10))
+    same_hits(got, _want(orc, ds, g, qc, qh, 10))
 
 
 def test_k_edges(orc, hny):
     rng = np.random.default_rng(5)
     dim = 24
     ds, b, g = _built(orc, hny, EUCLIDEAN, rng.uniform(-1, 1, (300, dim)).astype(np.float32))
-    _, qc, qh = _queries(orc, EUCLIDEAN, rng, NQ, dim)
+    _, qc, qh = queries(orc, EUCLIDEAN, rng, NQ, dim)
     with b:
-        _same(b.exact_knn(qc, qh, k=1), _want(orc, ds, g, qc, qh, 1), "k=1")
+        same_hits(b.exact_knn(qc, qh, k=1), _want(orc, ds, g, qc, qh, 1), "k=1")
         got = b.exact_knn(qc, qh, k=300)  # k = n: every item, in order
         assert (got[2] == 300).all() and all(sorted(got[0][r].tolist()) == ds.ids.tolist() for r in range(NQ))
-        _same(got, _want(orc, ds, g, qc, qh, 300), "k=n")
+        same_hits(got, _want(orc, ds, g, qc, qh, 300), "k=n")
         got = b.exact_knn(qc, qh, k=1000)  # k > n: min(k, |C|) hits
         assert (got[2] == 300).all()
-        _same(got, _want(orc, ds, g, qc, qh, 1000), "k>n")
+        same_hits(got, _want(orc, ds, g, qc, qh, 1000), "k>n")
     ds, b, g = _built(orc, hny, EUCLIDEAN, rng.uniform(-1, 1, (5000, dim)).astype(np.float32))
     with b:
         got = b.exact_knn(qc, qh, k=4095)
         assert (got[2] == 4095).all()
-        _same(got, _want(orc, ds, g, qc, qh, 4095), "k=4095")
+        same_hits(got, _want(orc, ds, g, qc, qh, 4095), "k=4095")
         with pytest.raises(hny.HannoyError) as e:
             b.exact_knn(qc, qh, k=4096)
         assert e.value.code == -5 and "4095" in str(e.value)  # HNY_ERR_UNSUPPORTED, naming the cap
         with pytest.raises(hny.HannoyError) as e:
             b.exact_knn(qc[:, :-4], qh, k=3)
         assert e.value.code == -4  # HNY_ERR_INVALID_DIM: stride below the codec's bytes
-        _same(b.exact_knn(qc, qh, k=3), _want(orc, ds, g, qc, qh, 3), "after the refusals")
+        same_hits(b.exact_knn(qc, qh, k=3), _want(orc, ds, g, qc, qh, 3), "after the refusals")
 
 
 @pytest.mark.parametrize("metric,dim", [(COSINE, 96), (HAMMING, 256)], ids=["cosine-96", "hamming-256"])
@@ -164,7 +142,7 @@ def test_filters(orc, hny, metric, dim):
     rng = np.random.default_rng(9 + metric)
     ids = np.arange(N, dtype=np.uint32) * 3 + 1
     ds, b, g = _built(orc, hny, metric, rng.uniform(-1, 1, (N, dim)).astype(np.float32), ids=ids)
-    _, qc, qh = _queries(orc, metric, rng, NQ, dim)
+    _, qc, qh = queries(orc, metric, rng, NQ, dim)
     junk = np.array([0, 2, 10 ** 7], np.uint32)  # unknown ids
     dense = np.concatenate([ids[rng.random(N) < 0.5], junk])
     dense = np.concatenate([dense, dense[:40]])  # duplicates
@@ -177,10 +155,10 @@ def test_filters(orc, hny, metric, dim):
             got = b.exact_knn(qc, qh, k=10, candidates=cand)
             cs = set(cand.tolist())
             assert all(int(v) in cs for r in range(NQ) for v in got[0][r, :got[2][r]]), tag
-            _same(got, _want(orc, ds, g, qc, qh, 10, cand), tag)
+            same_hits(got, _want(orc, ds, g, qc, qh, 10, cand), tag)
         got = b.exact_knn(qc, qh, k=30, candidates=sparse)  # fewer candidates than k
         assert (got[2] == 21).all()
-        _same(got, _want(orc, ds, g, qc, qh, 30, sparse), "sparse, k > |C|")
+        same_hits(got, _want(orc, ds, g, qc, qh, 30, sparse), "sparse, k > |C|")
         for cand in (junk, np.zeros(0, np.uint32)):  # empty intersection
             assert not b.exact_knn(qc, qh, k=5, candidates=cand)[2].any()
             assert (b.exact_knn(k=5, query_items=ids[:4], candidates=cand)[2] == hny.NNS_NONE).all()
@@ -198,9 +176,9 @@ def test_by_item(orc, hny):
         got = b.exact_knn(k=10, query_items=qi)
         assert (got[2][-3:] == hny.NNS_NONE).all() and (got[2][:-3] == 10).all()
         assert np.array_equal(got[0][:-3, 0], qi[:-3]) and not got[1][:-3, 0].any()  # the item itself, at rank 0
-        _same(got, _want(orc, ds, g, None, None, 10, query_items=qi), "by_item")
+        same_hits(got, _want(orc, ds, g, None, None, 10, query_items=qi), "by_item")
         got = b.exact_knn(k=10, query_items=qi, candidates=dense)
-        _same(got, _want(orc, ds, g, None, None, 10, dense, query_items=qi), "by_item, filtered")
+        same_hits(got, _want(orc, ds, g, None, None, 10, dense, query_items=qi), "by_item, filtered")
         # an incremental builder: deleted slots stay in the row array, never in a result
         gone = np.sort(rng.choice(ids, 200, replace=False)).astype(np.uint32)
         keep = ~np.isin(ids, gone)
@@ -213,13 +191,13 @@ def test_by_item(orc, hny):
             got = b2.exact_knn(k=10, query_items=qi2)
             assert (got[2][:9] == hny.NNS_NONE).all() and (got[2][-3:] == hny.NNS_NONE).all()
             assert not np.isin(got[0][9:-3], gone).any()
-            _same(got, _want(orc, ds2, g2, None, None, 10, query_items=qi2), "by_item after deletions")
-            _, qc, qh = _queries(orc, EUCLIDEAN, rng, NQ, dim)
+            same_hits(got, _want(orc, ds2, g2, None, None, 10, query_items=qi2), "by_item after deletions")
+            _, qc, qh = queries(orc, EUCLIDEAN, rng, NQ, dim)
             got = b2.exact_knn(qc, qh, k=10)
             assert not np.isin(got[0], gone).any()
-            _same(got, _want(orc, ds2, g2, qc, qh, 10), "by_vector after deletions")
+            same_hits(got, _want(orc, ds2, g2, qc, qh, 10), "by_vector after deletions")
             got = b2.exact_knn(qc, qh, k=10, candidates=np.concatenate([gone, ids[keep][:700]]))
-            _same(got, _want(orc, ds2, g2, qc, qh, 10, ids[keep][:700]), "filter naming deleted items")
+            same_hits(got, _want(orc, ds2, g2, qc, qh, 10, ids[keep][:700]), "filter naming deleted items")
 
 
 @pytest.mark.parametrize("metric,dim", [(COSINE, 100), (BQ_EUCLIDEAN, 300)], ids=["cosine-100", "bq-euclidean-300"])
@@ -234,7 +212,7 @@ def test_f32_queries(orc, hny, metric, dim):
     assert (got[2] == 10).all()
     for x, y in zip(got, want):
         assert np.array_equal(x.view(np.uint32), y.view(np.uint32))
-    _same(got, _want(orc, ds, g, qc, qh, 10))
+    same_hits(got, _want(orc, ds, g, qc, qh, 10))
 
 
 def _special_rows(rng, n, dim):
@@ -292,13 +270,13 @@ def test_strict_mode(orc, hny, metric, dim):
     rng = np.random.default_rng(dim + metric)
     ds, b, g = _built(orc, hny, metric, rng.uniform(-1, 1, (400, dim)).astype(np.float32), x86_order=True,
                       batch_frac=0.0, batch_max=1)
-    _, qc, qh = _queries(orc, metric, rng, NQ, dim)
+    _, qc, qh = queries(orc, metric, rng, NQ, dim)
     qi = ds.ids[rng.integers(0, 400, 20)]
     with b:
-        _same(b.exact_knn(qc, qh, k=10), _want(orc, ds, g, qc, qh, 10, order=orc.ORDER_X86), "by_vector")
-        _same(b.exact_knn(k=10, query_items=qi), _want(orc, ds, g, None, None, 10, order=orc.ORDER_X86, query_items=qi),
-              "by_item")
-        _same(b.exact_knn(qc, qh, k=500), _want(orc, ds, g, qc, qh, 500, order=orc.ORDER_X86), "k > n")
+        same_hits(b.exact_knn(qc, qh, k=10), _want(orc, ds, g, qc, qh, 10, order=orc.ORDER_X86), "by_vector")
+        same_hits(b.exact_knn(k=10, query_items=qi),
+                  _want(orc, ds, g, None, None, 10, order=orc.ORDER_X86, query_items=qi), "by_item")
+        same_hits(b.exact_knn(qc, qh, k=500), _want(orc, ds, g, qc, qh, 500, order=orc.ORDER_X86), "k > n")
 
 
 def test_equals_the_existing_scan(orc, hny):
@@ -306,7 +284,7 @@ def test_equals_the_existing_scan(orc, hny):
     rng = np.random.default_rng(8)
     dim = 768
     ds, b, g = _built(orc, hny, COSINE, rng.uniform(-1, 1, (N, dim)).astype(np.float32))
-    _, qc, qh = _queries(orc, COSINE, rng, NQ, dim)
+    _, qc, qh = queries(orc, COSINE, rng, NQ, dim)
     with b:
         got = b.exact_knn(qc, qh, k=10)
         want = b.nns(qc, qh, k=10, candidates=ds.ids, linear_below=ALL)
@@ -322,13 +300,13 @@ def test_equals_the_existing_scan(orc, hny):
 def test_cancel_before_the_first_launch(orc, hny):
     rng = np.random.default_rng(2)
     ds, b, g = _built(orc, hny, EUCLIDEAN, rng.uniform(-1, 1, (N, 16)).astype(np.float32))
-    _, qc, qh = _queries(orc, EUCLIDEAN, rng, NQ, 16)
+    _, qc, qh = queries(orc, EUCLIDEAN, rng, NQ, 16)
     with b:
         got = b.exact_knn(qc, qh, k=5, cancel=lambda: True)
         assert b.did_cancel and not got[2].any()
         got = b.exact_knn(qc, qh, k=5, cancel=lambda: False)
         assert not b.did_cancel
-        _same(got, _want(orc, ds, g, qc, qh, 5))
+        same_hits(got, _want(orc, ds, g, qc, qh, 5))
 
 
 def test_reader_recall(hny):

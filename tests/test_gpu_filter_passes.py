@@ -17,7 +17,8 @@ import numpy as np
 import pytest
 
 from conftest import draw_levels
-from test_gpu_nns_filtered import NONE, _index, _per_group, _same
+from support import hny, same_hits  # noqa: F401
+from test_gpu_nns_filtered import NONE, _index, _per_group
 
 pytestmark = pytest.mark.gpu
 
@@ -55,13 +56,6 @@ assert COUNT_BOUNDARY == 65536 < N_COUNT
 
 LB = 5000  # linear_below of the compaction worlds: filters 0 .. 5 are scanned, 6 and 7 walked
 NQ = 150
-
-
-@pytest.fixture(scope="module")
-def hny():
-    import hannoy_amd
-    hannoy_amd.load_library()
-    return hannoy_amd
 
 
 def _compact_world(orc, hny, scheme):
@@ -130,7 +124,7 @@ def _oracle_rows(orc, w, filters, live, filter_of, qc, qh, k, ef, lb, per_filter
 
 
 def _same_rows(got, rows, want):
-    _same(tuple(x[rows] for x in got), want)
+    same_hits(tuple(x[rows] for x in got), want)
 
 
 @pytest.mark.parametrize("bitsets_per_round", [0, 2], ids=["one-round", "two-per-round"])
@@ -146,7 +140,7 @@ def test_two_pass_compaction_in_a_mixed_batch(orc, worlds, monkeypatch, scheme, 
     got = w.b.nns_filtered(w.filters, w.filter_of, w.qc, w.qh, k=k, ef_search=ef, linear_below=LB)
     want = _per_group(w.b, w.filters, w.filter_of, k,
                       lambda rows, c: w.b.nns(w.qc[rows], w.qh[rows], k=k, ef_search=ef, candidates=c, linear_below=LB))
-    _same(got, want)
+    same_hits(got, want)
     for rows, o in zip(*_oracle_rows(orc, w, w.filters, w.live, w.filter_of, w.qc, w.qh, k, ef, LB)):
         _same_rows(got, rows, o)
     ids, _, counts = got
@@ -208,7 +202,7 @@ def test_identity_ids_on_a_successor_with_deleted_slots(orc, worlds):
             def one(rows, c):
                 qq = dict(query_items=qi[rows]) if by_item else dict(qcodes=w.qc[rows], qheaders=w.qh[rows])
                 return b2.nns(k=k, ef_search=ef, candidates=c, linear_below=LB, **qq)
-            _same(got, _per_group(b2, filters, fo, k, one))
+            same_hits(got, _per_group(b2, filters, fo, k, one))
             ids, _, counts = got
             if by_item:
                 assert np.array_equal(counts == NONE, none_by_item)
@@ -283,7 +277,7 @@ def test_count_split_over_two_workgroups(orc, worlds):
     got = w.b.nns_filtered(filters, fo, w.qc, w.qh, k=k, ef_search=ef, linear_below=LB2)
     want = _per_group(w.b, filters, fo, k,
                       lambda rows, c: w.b.nns(w.qc[rows], w.qh[rows], k=k, ef_search=ef, candidates=c, linear_below=LB2))
-    _same(got, want)
+    same_hits(got, want)
     for rows, o in zip(*_oracle_rows(orc, w, filters, live, fo, w.qc, w.qh, k, ef, LB2)):
         _same_rows(got, rows, o)
     ids, _, counts = got
@@ -329,7 +323,7 @@ def test_set_bits_beyond_one_trip_of_the_grid(worlds):
     print(f"nns_filtered, {sum(map(len, filters))} filter entries: {time.perf_counter() - t0:.2f} s")
     assert (got[2][full] == k).all() and not got[2][list(empty_at)].any()
     want = w.b.nns(qc, qh, k=k, ef_search=ef, candidates=w.ids)
-    _same(tuple(x[full] for x in got), tuple(x[full] for x in want))
+    same_hits(tuple(x[full] for x in got), tuple(x[full] for x in want))
     for f in (1, 121, 125, 134):  # and the single-filter call, on both sides of the second trip
         one = w.b.nns_filtered([filters[f]], [0], qc[f:f + 1], qh[f:f + 1], k=k, ef_search=ef)
-        _same(tuple(x[f:f + 1] for x in got), one)
+        same_hits(tuple(x[f:f + 1] for x in got), one)

@@ -7,39 +7,12 @@ import numpy as np
 import pytest
 
 from conftest import draw_levels
+from support import NO_COUNTERS, hny, identical_hits, same_graph, vecs  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 DIMS = (1, 15, 16, 17, 31, 32, 33, 63, 64, 65, 100, 768, 1063)  # every branch of the norm and quantize code
 KW = dict(M=8, M0=16, ef_construction=32, batch_frac=0.1, batch_max=128)
-
-
-@pytest.fixture(scope="module")
-def hny():
-    import hannoy_amd
-    hannoy_amd.load_library()
-    return hannoy_amd
-
-
-def _same_graph(g, o, counters=True):
-    assert g.entry_points.tolist() == o.entry_points.tolist()
-    assert g.max_level == o.max_level
-    assert np.array_equal(g.rec_item, o.rec_item)
-    assert np.array_equal(g.rec_layer, o.rec_layer)
-    assert np.array_equal(g.offsets, o.offsets)
-    assert np.array_equal(g.nbrs, o.nbrs)
-    if counters:
-        assert g.n_links_added == o.n_links_added
-        assert g.n_evals_walk == o.n_evals_walk
-
-
-def _same_hits(got, want):
-    for a, b in zip(got, want):
-        assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
-def _vecs(seed, n, dim):
-    return np.random.default_rng(seed).uniform(-1, 1, (n, dim)).astype(np.float32)
 
 
 def _n_for(dim):
@@ -51,23 +24,23 @@ def _n_for(dim):
 def test_build_f32_equals_build_on_host_codes(hny, metric, dim):
     """1. graph identity: same records, entry points, max_level, n_links_added, n_evals_walk"""
     n = _n_for(dim)
-    v = _vecs(1000 * metric + dim, n, dim)
+    v = vecs(1000 * metric + dim, n, dim)
     lv = draw_levels(n, KW["M"], seed=dim)
     g_host = hny.build(hny.ItemSet.from_f32(metric, v, levels=lv), **KW)
     g_f32 = hny.build(hny.ItemSet.from_f32(metric, v, levels=lv, device=True), **KW)
-    _same_graph(g_f32, g_host)
+    same_graph(g_f32, g_host)
 
 
 def test_build_f32_equals_oracle(orc, hny):
     """... and one case edge for edge against the oracle, as smoke() does"""
     n, dim, M, M0, ef = 3000, 768, 16, 32, 100
-    v = _vecs(0, n, dim)
+    v = vecs(0, n, dim)
     lv = hny.draw_levels(1, M, n)
     ds = orc.Dataset.from_f32(orc.COSINE, v, lv)
     g = hny.build(hny.F32ItemSet(hny.COSINE, v, ds.ids, ds.levels), M=M, M0=M0, ef_construction=ef, batch_frac=0.05,
                   batch_max=256)
     o = orc.build(ds, M=M, M0=M0, ef=ef, order=orc.ORDER_WAVE, batch_frac=0.05, batch_max=256)
-    _same_graph(g, o, counters=False)
+    same_graph(g, o, counters=NO_COUNTERS)
     assert g.n_evals_walk == o.n_evals_walk
 
 
@@ -107,7 +80,7 @@ def test_strides_and_sparse_ids(hny, metric, dim, pad):
     """2. stride > dim * 4 (16-byte aligned or not, and far apart) and ids that are not 0..n-1"""
     n = 1200
     wide = np.full((n, dim + pad), np.float32(7.5))  # the padding must never be read as data
-    wide[:, :dim] = _vecs(31 * metric + dim, n, dim)
+    wide[:, :dim] = vecs(31 * metric + dim, n, dim)
     v = wide[:, :dim]
     assert v.strides[0] == (dim + pad) * 4
     ids = np.arange(n, dtype=np.uint32) * 5 + 3
@@ -115,7 +88,7 @@ def test_strides_and_sparse_ids(hny, metric, dim, pad):
     f32_items = hny.F32ItemSet(metric, v, ids, lv)
     assert f32_items.struct().stride == (dim + pad) * 4
     host_items = hny.ItemSet.from_f32(metric, np.ascontiguousarray(v), ids, lv)
-    _same_graph(hny.build(f32_items, **KW), hny.build(host_items, **KW))
+    same_graph(hny.build(f32_items, **KW), hny.build(host_items, **KW))
     with hny.Builder(f32_items, **KW) as b:
         codes, headers = b.export_items()
     assert np.array_equal(codes, host_items.codes) and np.array_equal(headers, host_items.headers)
@@ -125,7 +98,7 @@ def test_strides_and_sparse_ids(hny, metric, dim, pad):
 def test_encode_kv_of_f32_build(hny, metric, dim):
     """3. encode_kv(with_items=True) of an f32-built graph == that of a host-encoded build, record for record"""
     n = 900
-    v = _vecs(7 + metric, n, dim)
+    v = vecs(7 + metric, n, dim)
     ids = np.arange(n, dtype=np.uint32) * 2
     lv = draw_levels(n, KW["M"], seed=3)
     g_f32 = hny.build(hny.F32ItemSet(metric, v, ids, lv), **KW)
@@ -149,7 +122,7 @@ def test_incremental_f32_equals_incremental(hny, metric, dim):
     host0, f0 = mats(lv0)
     g_host = hny.build(host0, **KW)
     g_f32 = hny.build(f0, **KW)
-    _same_graph(g_f32, g_host)
+    same_graph(g_f32, g_host)
     alive = sorted(vecs)
     to_delete = sorted(rng.choice(alive, 120, replace=False).tolist())
     for i in to_delete:
@@ -163,7 +136,7 @@ def test_incremental_f32_equals_incremental(hny, metric, dim):
     host1, f1 = mats(ins_levels)
     g_host1 = hny.build_incremental(host1, g_host, to_insert, to_delete, **KW)
     g_f321 = hny.build_incremental(f1, g_f32, to_insert, to_delete, **KW)
-    _same_graph(g_f321, g_host1)
+    same_graph(g_f321, g_host1)
     # a loaded graph (Reader::open) over f32 items holds the same rows
     with hny.Builder(f1, prev=g_f321, load=True, **KW) as b:
         codes, headers = b.export_items()
@@ -173,21 +146,21 @@ def test_incremental_f32_equals_incremental(hny, metric, dim):
 def test_strict_mode_f32_equals_code_bytes(hny):
     """5. x86_order = 1, batch_max = 1"""
     n, dim = 600, 100
-    v = _vecs(5, n, dim)
+    v = vecs(5, n, dim)
     lv = draw_levels(n, 8, seed=5)
     kw = dict(M=8, M0=16, ef_construction=32, batch_max=1, x86_order=True)
-    _same_graph(hny.build(hny.F32ItemSet(hny.COSINE, v, levels=lv), **kw),
-                hny.build(hny.ItemSet.from_f32(hny.COSINE, v, levels=lv), **kw))
+    same_graph(hny.build(hny.F32ItemSet(hny.COSINE, v, levels=lv), **kw),
+               hny.build(hny.ItemSet.from_f32(hny.COSINE, v, levels=lv), **kw))
 
 
 def _search_case(hny, metric, dim, n=3000, nq=300):
-    v = _vecs(90 + metric, n, dim)
+    v = vecs(90 + metric, n, dim)
     ids = np.arange(n, dtype=np.uint32) * 3 + 1
     items = hny.F32ItemSet(metric, v, ids, draw_levels(n, 8, seed=metric))
     b = hny.Builder(items, M=8, M0=16, ef_construction=48, batch_frac=0.1, batch_max=256)
     b.run()
     wide = np.full((nq, dim + 4), np.float32(-3.0))
-    wide[:, :dim] = _vecs(190 + metric, nq, dim)
+    wide[:, :dim] = vecs(190 + metric, nq, dim)
     q = wide[:, :dim]  # strided queries
     qc, qh = hny.encode_vectors(metric, np.ascontiguousarray(q))
     return b, ids, q, qc, qh
@@ -200,12 +173,12 @@ def test_search_f32_equals_search_on_host_codes(hny, metric, dim):
     rng = np.random.default_rng(metric)
     with b:
         for k, ef in ((10, 50), (3, 2), (1, 100)):
-            _same_hits(b.search_knn_f32(q, k=k, ef_search=ef), b.search_knn(qc, qh, k=k, ef_search=ef))
-            _same_hits(b.nns_f32(q, k=k, ef_search=ef), b.nns(qc, qh, k=k, ef_search=ef))
+            identical_hits(b.search_knn_f32(q, k=k, ef_search=ef), b.search_knn(qc, qh, k=k, ef_search=ef))
+            identical_hits(b.nns_f32(q, k=k, ef_search=ef), b.nns(qc, qh, k=k, ef_search=ef))
             for frac, lb in ((0.5, 0), (0.05, 0), (0.1, 1000)):
                 cand = ids[rng.random(len(ids)) < frac]
-                _same_hits(b.nns_f32(q, k=k, ef_search=ef, candidates=cand, linear_below=lb),
-                           b.nns(qc, qh, k=k, ef_search=ef, candidates=cand, linear_below=lb))
+                identical_hits(b.nns_f32(q, k=k, ef_search=ef, candidates=cand, linear_below=lb),
+                               b.nns(qc, qh, k=k, ef_search=ef, candidates=cand, linear_below=lb))
 
 
 @pytest.mark.parametrize("metric,dim", [(0, 96), (3, 256)])
@@ -216,29 +189,29 @@ def test_search_f32_through_tie_pool_retry(hny, metric, dim, monkeypatch):
     with b:
         plain = b.search_knn(qc, qh, k=10, ef_search=50)
         monkeypatch.setenv("HNY_POOL_FORCE_RETRY", "2")
-        _same_hits(b.search_knn_f32(q, k=10, ef_search=50), plain)
-        _same_hits(b.nns_f32(q, k=10, ef_search=50), plain)
-        _same_hits(b.search_knn(qc, qh, k=10, ef_search=50), plain)
+        identical_hits(b.search_knn_f32(q, k=10, ef_search=50), plain)
+        identical_hits(b.nns_f32(q, k=10, ef_search=50), plain)
+        identical_hits(b.search_knn(qc, qh, k=10, ef_search=50), plain)
 
 
 @pytest.mark.parametrize("metric,dim,chunk_rows", [(0, 100, 256), (3, 300, 112), (4, 64, 333), (1, 32, 1)])
 def test_chunk_boundaries(hny, metric, dim, chunk_rows, monkeypatch):
     """7. more rows than one staging chunk: both buffers several times over and a last partial chunk"""
     n = 1500 if chunk_rows > 1 else 40
-    v = _vecs(11 * metric + dim, n, dim)
+    v = vecs(11 * metric + dim, n, dim)
     lv = draw_levels(n, KW["M"], seed=9)
     g_host = hny.build(hny.ItemSet.from_f32(metric, v, levels=lv), **KW)
     hc, hh = hny.encode_vectors(metric, v)
     monkeypatch.setenv("HNY_INGEST_CHUNK_ROWS", str(chunk_rows))
     assert n % chunk_rows or chunk_rows == 1
-    _same_graph(hny.build(hny.F32ItemSet(metric, v, levels=lv), **KW), g_host)
+    same_graph(hny.build(hny.F32ItemSet(metric, v, levels=lv), **KW), g_host)
     gc, gh = hny.encode_vectors(metric, v, gpu=True)  # the same pipeline with the packed outputs
     assert np.array_equal(gc, hc) and np.array_equal(gh, hh)
     with hny.Builder(hny.F32ItemSet(metric, v, levels=lv), **KW) as b:
         b.run()
-        q = _vecs(5, 700, dim)
+        q = vecs(5, 700, dim)
         qc, qh = hny.encode_vectors(metric, q)
-        _same_hits(b.search_knn_f32(q, k=5, ef_search=20), b.search_knn(qc, qh, k=5, ef_search=20))
+        identical_hits(b.search_knn_f32(q, k=5, ef_search=20), b.search_knn(qc, qh, k=5, ef_search=20))
 
 
 def test_refusals(hny):
@@ -248,7 +221,7 @@ def test_refusals(hny):
     from hannoy_amd import _capi
     L = hny.load_library()
     dim, n = 24, 64
-    v = _vecs(1, n, dim)
+    v = vecs(1, n, dim)
     items = hny.F32ItemSet(hny.COSINE, v)
     for kw in (dict(n_gpus=2), dict(devices=[0, 1]), dict(n_gpus=1, devices=[0])):
         with pytest.raises(hny.HannoyError) as e:
@@ -281,14 +254,14 @@ def test_reader_queries_take_the_device_path(hny, tmp_path):
     """QueryBuilder.by_vectors / Reader.by_vecs hand their f32 queries to the device: same hits as the code path"""
     from hannoy_amd import Database, Metric
     n, dim = 800, 40
-    v = _vecs(77, n, dim)
+    v = vecs(77, n, dim)
     db = Database(distance=Metric.COSINE)
     w = db.writer(dim)
     w.add_items(np.arange(n, dtype=np.uint32), v)
     w.build()
     r = db.reader()
-    q = _vecs(78, 50, dim)
+    q = vecs(78, 50, dim)
     qc, qh = hny.encode_vectors(hny.COSINE, q)
-    _same_hits(r.by_vecs(q, n=7, ef_search=40), r._b.search_knn(qc, qh, k=7, ef_search=40))
-    _same_hits(r.nns(7).ef_search(40).by_vectors(q), r._b.nns(qc, qh, k=7, ef_search=40))
+    identical_hits(r.by_vecs(q, n=7, ef_search=40), r._b.search_knn(qc, qh, k=7, ef_search=40))
+    identical_hits(r.nns(7).ef_search(40).by_vectors(q), r._b.nns(qc, qh, k=7, ef_search=40))
     r.close()

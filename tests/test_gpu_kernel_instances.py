@@ -13,18 +13,11 @@ import pytest
 
 import kernel_instances as ki
 from conftest import draw_levels
-from test_gpu_row_shapes import _same, _same_hits
+from support import hny, same_graph, same_hits  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 NQ, K, PAIRS = 64, 10, 256
-
-
-@pytest.fixture(scope="module")
-def hny():
-    import hannoy_amd
-    hannoy_amd.load_library()
-    return hannoy_amd
 
 
 def n_items(metric, dim, efc):
@@ -100,7 +93,7 @@ def test_instance_equals_oracle(orc, index_of, config):
     want = orc.distance_pairs(ds, orc.ORDER_WAVE, a, c)
     assert np.array_equal(ix.b.distances(a, c).view(np.uint32), want.view(np.uint32))
     # the fresh build; without a tie-pool overflow the instance under test did all the walking, not k_walk_heap
-    _same(ix.g, ix.og)
+    same_graph(ix.g, ix.og)
     assert ix.g.n_tie_pool_overflow == 0
     # the Reader's walks: half of the queries are items of the index, half fresh vectors
     at = rng.choice(n, NQ // 2, replace=False)
@@ -109,4 +102,4 @@ def test_instance_equals_oracle(orc, index_of, config):
     qh = np.concatenate([ds.headers[at], orc.make_headers(metric, dim, fresh)])
     want = orc.search(ds, ix.og, qc, qh, k=K, ef_search=efs, order=orc.ORDER_WAVE, threads=8)
     assert (want[2] == K).all()
-    _same_hits(ix.b.search_knn(qc, qh, k=K, ef_search=efs), want)
+    same_hits(ix.b.search_knn(qc, qh, k=K, ef_search=efs), want)

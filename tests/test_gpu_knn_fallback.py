@@ -5,6 +5,8 @@ has to restart from items it has not seen, in every form of the walk kernel.  Ev
 import numpy as np
 import pytest
 
+from support import hny, prefilled  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 METRIC, NA, NB, M, M0, EF_C, K = 1, 30, 30, 4, 8, 32, 40  # euclidean; k is larger than either group
@@ -14,13 +16,6 @@ FORMS = {"default": ({}, 50),
          "lds_beam": ({"HNY_NO_RB": "1"}, 50),      # the beam in LDS instead of registers
          "general": ({"HNY_NO_FAST": "1"}, 50),     # the general kernel, reader_mode at run time
          "lds_beam_by_size": ({}, 200)}             # ef_search beyond what the register beam holds
-
-
-@pytest.fixture(scope="module")
-def hny():
-    import hannoy_amd
-    hannoy_amd.load_library()
-    return hannoy_amd
 
 
 def _world(dim):
@@ -99,8 +94,7 @@ def test_knn_writes_nothing_past_the_count(orc, hny, monkeypatch, force_retry):
         oids, odists, ocounts = orc.search(ds, g, qc, qh, k=k, ef_search=ef_search, order=orc.ORDER_WAVE)
         assert ocounts.tolist() == [n] * nq
         for tag in ("codes", "f32"):
-            ids, dists, counts = out = (np.full((nq, k), 77, np.uint32), np.full((nq, k), 7.5, np.float32),
-                                        np.full(nq, 77, np.uint32))
+            ids, dists, counts = out = prefilled(nq, k)
             if tag == "codes":
                 (_, pq, qstride, ph, _), _keep = capi._query_source(qcodes=qc, qheaders=qh)
                 rc = L.hny_builder_search_knn(b._h, nq, pq, qstride, ph, k, ef_search, *map(capi._p, out))

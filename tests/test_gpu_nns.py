@@ -6,15 +6,9 @@ import numpy as np
 import pytest
 
 from conftest import draw_levels
+from support import hny, queries, same_hits  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def hny():
-    import hannoy_amd
-    hannoy_amd.load_library()
-    return hannoy_amd
 
 
 def _index(orc, hny, metric, n, dim, M, M0, ef, seed, ids=None):
@@ -28,28 +22,12 @@ def _index(orc, hny, metric, n, dim, M, M0, ef, seed, ids=None):
     return rng, vecs, ds, b, g
 
 
-def _queries(orc, metric, rng, nq, dim):
-    qs = rng.uniform(-1, 1, (nq, dim)).astype(np.float32)
-    qc = orc.encode_vectors(metric, qs)
-    return qs, qc, orc.make_headers(metric, dim, qc)
-
-
-def _same(got, want):
-    ids, dists, counts = got
-    oids, odists, ocounts = want
-    assert np.array_equal(counts, ocounts)
-    for r in range(len(counts)):
-        c = 0 if counts[r] == 0xFFFFFFFF else int(counts[r])
-        assert np.array_equal(ids[r, :c], oids[r, :c]), r
-        assert np.array_equal(dists[r, :c].view(np.uint32), odists[r, :c].view(np.uint32)), r
-
-
 @pytest.mark.parametrize("metric,n,dim,M,M0", [(0, 3000, 96, 8, 16), (1, 2500, 40, 6, 12), (3, 3000, 256, 8, 16),
                                                (4, 2000, 192, 8, 16)])
 def test_filtered_search_equals_oracle(orc, hny, metric, n, dim, M, M0):
     ids = (np.arange(n, dtype=np.uint32) * 3 + 1)
     rng, vecs, ds, b, g = _index(orc, hny, metric, n, dim, M, M0, 48, 11 + metric, ids)
-    qs, qc, qh = _queries(orc, metric, rng, 300, dim)
+    qs, qc, qh = queries(orc, metric, rng, 300, dim)
     with b:
         for frac_kept, lb in ((0.5, 0), (0.05, 0), (0.004, 0), (0.1, 1000), (0.5, 5000)):
             cand = ids[rng.random(n) < frac_kept]
@@ -59,7 +37,7 @@ def test_filtered_search_equals_oracle(orc, hny, metric, n, dim, M, M0):
                 got = b.nns(qc, qh, k=k, ef_search=ef, candidates=cand, linear_below=lb)
                 want = orc.search(ds, g, qc, qh, k=k, ef_search=ef, order=orc.ORDER_WAVE, threads=8,
                                   candidates=cand, linear_below=lb)
-                _same(got, want)
+                same_hits(got, want)
                 cs = set(cand.tolist())
                 assert all(int(v) in cs for r in range(len(qc)) for v in got[0][r, :got[2][r]])
         # nothing can match: empty Vec (reader.rs:652-654)
@@ -73,7 +51,7 @@ def test_filtered_search_equals_oracle(orc, hny, metric, n, dim, M, M0):
             got = b.nns(qc, qh, k=10, ef_search=30, candidates=cand, linear_below_ratio=ratio)
             want = orc.search(ds, g, qc, qh, k=10, ef_search=30, order=orc.ORDER_WAVE, threads=8,
                               candidates=cand, linear_below_ratio=ratio)
-            _same(got, want)
+            same_hits(got, want)
 
 
 @pytest.mark.parametrize("metric,n,dim,M,M0", [(0, 6000, 64, 8, 16), (3, 7000, 64, 8, 16), (1, 5000, 24, 4, 8)])
@@ -84,7 +62,7 @@ def test_filtered_and_by_item_search_with_result_sets_beyond_the_lds(orc, hny, m
     64-bit Hamming codes are all ties; the linear scan keeps its LDS ranking (min(k, candidates) hits)."""
     ids = (np.arange(n, dtype=np.uint32) * 3 + 1)
     rng, vecs, ds, b, g = _index(orc, hny, metric, n, dim, M, M0, 48, 31 + metric, ids)
-    qs, qc, qh = _queries(orc, metric, rng, 40, dim)
+    qs, qc, qh = queries(orc, metric, rng, 40, dim)
     qi = np.concatenate([ids[rng.integers(0, n, 40)], [0, 2, 10 ** 7]]).astype(np.uint32)
     with b:
         for frac_kept in (0.9, 0.3, 0.01):
@@ -94,20 +72,20 @@ def test_filtered_and_by_item_search_with_result_sets_beyond_the_lds(orc, hny, m
                 got = b.nns(qc, qh, k=k, ef_search=ef, candidates=cand, linear_below=0)
                 want = orc.search(ds, g, qc, qh, k=k, ef_search=ef, order=orc.ORDER_WAVE, threads=8,
                                   candidates=cand, linear_below=0)
-                _same(got, want)
+                same_hits(got, want)
                 got = b.nns(k=k, ef_search=ef, query_items=qi, candidates=cand, linear_below=0)
                 want = orc.search(ds, g, None, None, k=k, ef_search=ef, order=orc.ORDER_WAVE, threads=8,
                                   query_items=qi, candidates=cand, linear_below=0)
-                _same(got, want)
+                same_hits(got, want)
         for k, ef in ((10, 4500), (4100, 10)):  # by_item without a filter
             got = b.nns(k=k, ef_search=ef, query_items=qi)
             want = orc.search(ds, g, None, None, k=k, ef_search=ef, order=orc.ORDER_WAVE, threads=8, query_items=qi)
-            _same(got, want)
+            same_hits(got, want)
         cand = ids[rng.random(n) < 0.1]  # linear scan: below the default threshold of 1 000 candidates
         got = b.nns(qc, qh, k=5000, ef_search=10, candidates=cand, linear_below=1000)
         want = orc.search(ds, g, qc, qh, k=5000, ef_search=10, order=orc.ORDER_WAVE, threads=8, candidates=cand,
                           linear_below=1000)
-        _same(got, want)
+        same_hits(got, want)
 
 
 @pytest.mark.parametrize("metric,n,dim,M,M0", [(0, 2000, 768, 16, 32), (1, 3000, 24, 4, 8), (3, 2500, 128, 8, 16)])
@@ -120,7 +98,7 @@ def test_by_item_equals_oracle(orc, hny, metric, n, dim, M, M0):
             got = b.nns(k=k, ef_search=ef, query_items=qi)
             want = orc.search(ds, g, None, None, k=k, ef_search=ef, order=orc.ORDER_WAVE, threads=8,
                               query_items=qi)
-            _same(got, want)
+            same_hits(got, want)
             # search_by_item_returns_none_if_not_exists (src/tests/reader.rs:130-143)
             assert (got[2][-4:] == hny.NNS_NONE).all()
             # search_by_item_does_not_contain_item (src/tests/reader.rs:114-127)
@@ -131,7 +109,7 @@ def test_by_item_equals_oracle(orc, hny, metric, n, dim, M, M0):
             got = b.nns(k=10, ef_search=40, query_items=qi, candidates=cand, linear_below=lb)
             want = orc.search(ds, g, None, None, k=10, ef_search=40, order=orc.ORDER_WAVE, threads=8,
                               query_items=qi, candidates=cand, linear_below=lb)
-            _same(got, want)
+            same_hits(got, want)
         got = b.nns(k=3, query_items=qi, candidates=np.array([1], np.uint32))  # disjoint: None (:822-824)
         assert (got[2] == hny.NNS_NONE).all()
 
@@ -139,7 +117,7 @@ def test_by_item_equals_oracle(orc, hny, metric, n, dim, M, M0):
 def test_search_on_candidates_has_right_num(orc, hny):
     """src/tests/reader.rs:42-78: 1000 x 768 cosine; 10 (then 1) random candidates -> exactly those."""
     rng, vecs, ds, b, g = _index(orc, hny, 0, 1000, 768, 16, 32, 100, 3)
-    qs, qc, qh = _queries(orc, 0, rng, 20, 768)
+    qs, qc, qh = queries(orc, 0, rng, 20, 768)
     with b:
         for r in range(20):
             cand = np.unique(rng.integers(0, 1000, 10).astype(np.uint32))
@@ -158,13 +136,13 @@ def test_queue_overflow_retries_with_full_heap(orc, hny):
     query is run again with room for every item — same answer as the oracle."""
     n, dim = 40000, 16
     rng, vecs, ds, b, g = _index(orc, hny, 1, n, dim, 8, 16, 32, 5)
-    qs, qc, qh = _queries(orc, 1, rng, 64, dim)
+    qs, qc, qh = queries(orc, 1, rng, 64, dim)
     cand = rng.choice(n, 12, replace=False).astype(np.uint32)
     with b:
         got = b.nns(qc, qh, k=10, ef_search=100, candidates=cand, linear_below=0)
     want = orc.search(ds, g, qc, qh, k=10, ef_search=100, order=orc.ORDER_WAVE, threads=8, candidates=cand,
                       linear_below=0)
-    _same(got, want)
+    same_hits(got, want)
     assert (got[2] == 10).all()
 
 
@@ -187,23 +165,23 @@ def test_loaded_graph_search_equals_oracle(orc, hny):
     ids = db.metadata(0)["items"]
     items = db.item_set(0, ids, dim)
     ds = orc.Dataset(1, dim, ids, items.codes, items.headers, np.zeros(len(ids), np.uint8))
-    qs, qc, qh = _queries(orc, 1, rng, 2500, dim)
+    qs, qc, qh = queries(orc, 1, rng, 2500, dim)
     r = db.reader(0)
     r.assert_validity()
     got = r.nns(10).ef_search(40).by_vectors(qs)
     want = orc.search(ds, stored, qc, qh, k=10, ef_search=40, order=orc.ORDER_WAVE, threads=8)
-    _same(got, want)
+    same_hits(got, want)
     got = r.by_vecs(qs, n=10, ef_search=40)
-    _same(got, want)
+    same_hits(got, want)
     cand = ids[rng.random(len(ids)) < 0.3]
     got = r.nns(10).ef_search(40).candidates(cand).linear_below(0).by_vectors(qs)
     want = orc.search(ds, stored, qc, qh, k=10, ef_search=40, order=orc.ORDER_WAVE, threads=8, candidates=cand,
                       linear_below=0)
-    _same(got, want)
+    same_hits(got, want)
     qi = ids[rng.integers(0, len(ids), 500)]
     got = r.nns(10).ef_search(40).by_items(qi)
     want = orc.search(ds, stored, None, None, k=10, ef_search=40, order=orc.ORDER_WAVE, threads=8, query_items=qi)
-    _same(got, want)
+    same_hits(got, want)
     r.close()
 
 
@@ -259,7 +237,7 @@ def test_filtered_and_by_item_search_from_more_entry_points_than_the_lds_set_hol
     vecs = rng.uniform(-1, 1, (n, dim)).astype(np.float32)
     ds = orc.Dataset.from_f32(metric, vecs, np.zeros(n, np.uint8))
     items = hny.ItemSet(metric, dim, ds.ids, ds.codes, ds.headers, ds.levels)
-    qs, qc, qh = _queries(orc, metric, rng, 24, dim)
+    qs, qc, qh = queries(orc, metric, rng, 24, dim)
     qi = np.concatenate([ds.ids[rng.integers(0, n, 24)], [10 ** 7]]).astype(np.uint32)
     with hny.Builder(items, M=8, M0=16, ef_construction=24, batch_frac=0.5, batch_max=512) as b:
         b.run()
@@ -271,11 +249,11 @@ def test_filtered_and_by_item_search_from_more_entry_points_than_the_lds_set_hol
                 got = b.nns(qc, qh, k=k, ef_search=ef, candidates=cand, linear_below=0)
                 want = orc.search(ds, g, qc, qh, k=k, ef_search=ef, order=orc.ORDER_WAVE, threads=8,
                                   candidates=cand, linear_below=0)
-                _same(got, want)
+                same_hits(got, want)
                 got = b.nns(k=k, ef_search=ef, query_items=qi, candidates=cand, linear_below=0)
                 want = orc.search(ds, g, None, None, k=k, ef_search=ef, order=orc.ORDER_WAVE, threads=8,
                                   query_items=qi, candidates=cand, linear_below=0)
-                _same(got, want)
+                same_hits(got, want)
         got = b.nns(k=5, ef_search=20, query_items=qi)
         want = orc.search(ds, g, None, None, k=5, ef_search=20, order=orc.ORDER_WAVE, threads=8, query_items=qi)
-        _same(got, want)
+        same_hits(got, want)

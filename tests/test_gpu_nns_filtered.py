@@ -10,19 +10,13 @@ import numpy as np
 import pytest
 
 from conftest import draw_levels
+from support import hny, identical_hits, prefilled, same_hits, untouched  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 NONE = 0xFFFFFFFF
 NQ = 300  # batch_max = 256: two chunks
 SHAPES = {"cosine": (0, 3000, 96, 8, 16), "euclidean": (1, 2500, 40, 6, 12), "hamming": (3, 3000, 256, 8, 16)}
-
-
-@pytest.fixture(scope="module")
-def hny():
-    import hannoy_amd
-    hannoy_amd.load_library()
-    return hannoy_amd
 
 
 def _index(orc, hny, metric, n, dim, M, M0, ef, seed, ids=None):
@@ -94,21 +88,11 @@ def _per_group(b, filters, filter_of, k, run):
     return ids, dists, counts
 
 
-def _same(got, want):
-    ids, dists, counts = got
-    oids, odists, ocounts = want
-    assert np.array_equal(counts, ocounts)
-    for r in range(len(counts)):
-        c = 0 if counts[r] == NONE else int(counts[r])
-        assert np.array_equal(ids[r, :c], oids[r, :c]), r
-        assert np.array_equal(dists[r, :c].view(np.uint32), odists[r, :c].view(np.uint32)), r
-
-
 def _check_equal_to_group_calls(w, lb, k, ef):
     got = w.b.nns_filtered(w.filters, w.filter_of, w.qc, w.qh, k=k, ef_search=ef, linear_below=lb)
     want = _per_group(w.b, w.filters, w.filter_of, k,
                       lambda rows, c: w.b.nns(w.qc[rows], w.qh[rows], k=k, ef_search=ef, candidates=c, linear_below=lb))
-    _same(got, want)
+    same_hits(got, want)
     return got
 
 
@@ -139,7 +123,7 @@ def test_equals_the_oracle_per_filter(orc, cosine):
     want = _per_group(w.b, w.filters, w.filter_of, k,
                       lambda rows, c: orc.search(w.ds, w.g, w.qc[rows], w.qh[rows], k=k, ef_search=ef,
                                                  order=orc.ORDER_WAVE, threads=8, candidates=c, linear_below=1000))
-    _same(got, want)
+    same_hits(got, want)
 
 
 def test_by_item(orc, cosine):
@@ -160,13 +144,13 @@ def test_by_item(orc, cosine):
         want = _per_group(w.b, w.filters, fo, 10,
                           lambda rows, c: w.b.nns(query_items=qi[rows], k=10, ef_search=40, candidates=c,
                                                   linear_below=lb))
-        _same(got, want)
+        same_hits(got, want)
         if lb == 1000:
             oracle = _per_group(w.b, w.filters, fo, 10,
                                 lambda rows, c: orc.search(w.ds, w.g, None, None, k=10, ef_search=40,
                                                            order=orc.ORDER_WAVE, threads=8, query_items=qi[rows],
                                                            candidates=c, linear_below=lb))
-            _same(got, oracle)
+            same_hits(got, oracle)
             for r in range(7, 10):  # the linear branch keeps the item itself
                 assert got[0][r, 0] == qi[r]
         assert (got[2][:7] == NONE).all()
@@ -199,16 +183,16 @@ def test_result_sets_beyond_the_lds(orc, hny):
             want = _per_group(b, filters, fo, 10,
                               lambda rows, c: b.nns(qc[rows], qh[rows], k=10, ef_search=5000, candidates=c,
                                                     linear_below=lb))
-            _same(got, want)
+            same_hits(got, want)
         # the refusal of a linear scan for more than 4 095 hits, for the whole call, naming the filter
         k = 5000
-        out = (np.full((40, k), 77, np.uint32), np.full((40, k), 7.5, np.float32), np.full(40, 77, np.uint32))
+        out = prefilled(40, k)
         rc = _raw(hny, b, [ids[:5], ids], np.r_[np.zeros(20, int), np.ones(20, int)], qc, qh, out, k=k,
                   linear_below=0xFFFFFFFF)
         assert rc == hny._capi.ERR_UNSUPPORTED
         msg = hny.load_library().hny_last_error().decode()
         assert msg and "filter 1" in msg
-        assert (out[0] == 77).all() and (out[1] == 7.5).all() and (out[2] == 77).all()
+        assert untouched(out)
 
 
 def test_deleted_slots(orc, hny):
@@ -230,7 +214,7 @@ def test_deleted_slots(orc, hny):
             want = _per_group(b2, filters, fo, 10,
                               lambda rows, c: b2.nns(qc[rows], qh[rows], k=10, ef_search=50, candidates=c,
                                                      linear_below=lb))
-            _same(got, want)
+            same_hits(got, want)
             dead = set(gone.tolist())
             assert not any(int(v) in dead for r in range(NQ) for v in got[0][r, :got[2][r]])
             assert not got[2][fo == 6].any()
@@ -246,8 +230,7 @@ def test_several_rounds_of_masks(cosine, monkeypatch):
     for lb in (1000, 0, 0xFFFFFFFF):
         got = _check_equal_to_group_calls(w, lb, 10, 50)
         if lb == 1000:
-            for x, y in zip(got, one):
-                assert np.array_equal(x.view(np.uint32), y.view(np.uint32))
+            identical_hits(got, one)
 
 
 def _raw(hny, b, filters, filter_of, qc, qh, out, k=10, ef_search=50, linear_below=1000, ratio=1.0, qstride=None,
@@ -313,16 +296,16 @@ def test_refusals_leave_the_outputs_alone(hny, cosine):
              (DIM, dict(qstride=w.qc.shape[1] - 1)), (DIM, dict(f32=w.qs, qstride=w.dim * 4 - 4)),
              (INV, dict(k=0))]
     for code, kw in cases:
-        out = (np.full((NQ, k), 77, np.uint32), np.full((NQ, k), 7.5, np.float32), np.full(NQ, 77, np.uint32))
+        out = prefilled(NQ, k)
         assert _raw(hny, w.b, w.filters, w.filter_of, w.qc, w.qh, out, **kw) == code, kw
         assert L.hny_last_error(), kw
-        assert (out[0] == 77).all() and (out[1] == 7.5).all() and (out[2] == 77).all(), kw
+        assert untouched(out), kw
     # NULL arguments
     qo = capi.QueryOpts()
     qo.k = k
     qf, keep = capi.QueryFilters.pack(w.filters, w.filter_of)
     p = capi._p
-    out = (np.full((NQ, k), 77, np.uint32), np.full((NQ, k), 7.5, np.float32), np.full(NQ, 77, np.uint32))
+    out = prefilled(NQ, k)
     args = [w.b._h, C.byref(qo), C.byref(qf), NQ, p(w.qc), w.qc.shape[1], p(w.qh), None, p(out[0]), p(out[1]), p(out[2])]
     for hole in (0, 1, 2, 4, 6, 8, 9, 10):
         a = list(args)
@@ -331,7 +314,7 @@ def test_refusals_leave_the_outputs_alone(hny, cosine):
         assert L.hny_last_error(), hole
     assert L.hny_builder_nns_filtered_f32(w.b._h, C.byref(qo), C.byref(qf), NQ, None, w.dim * 4, p(out[0]), p(out[1]),
                                           p(out[2])) == INV
-    assert (out[0] == 77).all() and (out[1] == 7.5).all() and (out[2] == 77).all()
+    assert untouched(out)
     # and the same arguments unbent are accepted
     assert _raw(hny, w.b, w.filters, w.filter_of, w.qc, w.qh, out) == capi.OK
     assert not (out[2] == 77).any()
@@ -410,10 +393,10 @@ def test_unfiltered_queries_across_mask_rounds(orc, hny, monkeypatch):
     with b:
         for lb in (1000, 0):
             got = b.nns_filtered(filters, fo, qc, qh, k=k, ef_search=ef, linear_below=lb)
-            _same(got, _per_group(b, filters, fo, k, lambda rows, c: b.nns(qc[rows], qh[rows], k=k, ef_search=ef,
-                                                                           candidates=c, linear_below=lb)))
+            same_hits(got, _per_group(b, filters, fo, k, lambda rows, c: b.nns(qc[rows], qh[rows], k=k, ef_search=ef,
+                                                                               candidates=c, linear_below=lb)))
             assert lb == 0 or (got[2] == k).all()  # a scan ranks every candidate
             got = b.nns_filtered(filters, fo, query_items=qi, k=k, ef_search=ef, linear_below=lb)
-            _same(got, _per_group(b, filters, fo, k, lambda rows, c: b.nns(query_items=qi[rows], k=k, ef_search=ef,
-                                                                           candidates=c, linear_below=lb)))
+            same_hits(got, _per_group(b, filters, fo, k, lambda rows, c: b.nns(query_items=qi[rows], k=k, ef_search=ef,
+                                                                               candidates=c, linear_below=lb)))
             assert (got[2][qi == 10 ** 6] == NONE).all() and (lb == 0 or (got[2][qi != 10 ** 6] == k).all())

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import draw_levels
+from support import check_delta, hny, same_graph, same_hits  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -54,52 +55,6 @@ assert [shape_of(*p.values[:2]) for p in LIFECYCLE[33:]] == [(64, 1), (64, 3), (
 assert {p.values[1] for p in LIFECYCLE[:33]} == {d for e in EDGES for d in e}
 assert [shape_of(*p.values[:2]) for p in HEAP_RETRY] == SHAPES
 assert {shape_of(1, d) for d in STRICT_DIMS} == set(SHAPES)
-
-
-@pytest.fixture(scope="module")
-def hny():
-    import hannoy_amd
-    hannoy_amd.load_library()
-    return hannoy_amd
-
-
-def _same(a, b):
-    assert a.entry_points.tolist() == b.entry_points.tolist()
-    assert a.max_level == b.max_level
-    assert np.array_equal(a.rec_item, b.rec_item)
-    assert np.array_equal(a.rec_layer, b.rec_layer)
-    assert np.array_equal(a.offsets, b.offsets)
-    assert np.array_equal(a.nbrs, b.nbrs)
-    assert a.n_links_added == b.n_links_added
-    assert a.n_evals_walk == b.n_evals_walk
-
-
-def _same_hits(got, want):
-    ids, dists, counts = got
-    oids, odists, ocounts = want
-    assert np.array_equal(counts, ocounts)
-    for r in range(len(counts)):
-        c = 0 if counts[r] == 0xFFFFFFFF else int(counts[r])
-        assert np.array_equal(ids[r, :c], oids[r, :c]), r
-        assert np.array_equal(dists[r, :c].view(np.uint32), odists[r, :c].view(np.uint32)), r
-
-
-def _check_delta(prev, full, d, to_delete):
-    """the delta definition: prev - removed + records == full; nothing unchanged in it; removed = keys of deleted items"""
-    fd = full.as_dict()
-    out = dict(prev)
-    for k in d.removed_keys():
-        assert k in out, f"removed key {k} never existed"
-        del out[k]
-    out.update(d.as_dict())
-    assert out == fd
-    for k, nb in d.as_dict().items():
-        assert prev.get(k) != nb, f"record {k} is in the delta with an unchanged list"
-    gone = set(int(i) for i in to_delete)
-    assert sorted(d.removed_keys()) == sorted(k for k in prev if k[0] in gone)
-    assert d.n_records_total == len(fd) == len(full.rec_item)
-    assert d.entry_points.tolist() == full.entry_points.tolist() and d.max_level == full.max_level
-    return fd
 
 
 def _prune_branch_records(g, to_delete, M, M0):
@@ -158,12 +113,12 @@ class Life:
         self.items = items = hny.ItemSet(self.metric, self.dim, ds.ids, ds.codes, ds.headers, ds.levels)
         self.og = self.orc.build(ds, **self.kw_o)
         self.ga = hny.build(items, **self.kw_g)
-        _same(self.ga, self.og)
+        same_graph(self.ga, self.og)
         assert self.ga.n_tie_pool_overflow == 0
         self.b = hny.Builder(items, **self.kw_g)
         self.b.run()
         gb = self.b.finish()
-        _same(gb, self.og)
+        same_graph(gb, self.og)
         assert gb.n_tie_pool_overflow == 0
         self.prev = gb.as_dict()
 
@@ -189,16 +144,16 @@ class Life:
         self.items = items = hny.ItemSet(self.metric, self.dim, ds.ids, ds.codes, ds.headers, lv)
         self.og = self.orc.build_incremental(ds, self.og, to_insert, lv, to_delete, **self.kw_o)
         self.ga = hny.build_incremental(items, self.ga, to_insert, to_delete, **self.kw_g)
-        _same(self.ga, self.og)
+        same_graph(self.ga, self.og)
         if f32:
             ups = dict(vectors=self.mat(to_insert))
         else:
             at = np.searchsorted(ds.ids, to_insert)
             ups = dict(codes=ds.codes[at], headers=ds.headers[at])
         gb, d = self.b.update(to_insert, delete_ids=to_delete, levels=lv, delta=True, **ups)
-        _same(gb, self.og)
+        same_graph(gb, self.og)
         assert self.ga.n_tie_pool_overflow == 0 and gb.n_tie_pool_overflow == 0
-        self.prev = _check_delta(self.prev, gb, d, to_delete)
+        self.prev = check_delta(self.prev, gb, d, to_delete)
         codes, hdrs = self.b.export_items()
         assert np.array_equal(self.b.items.ids, ds.ids)
         assert np.array_equal(codes, ds.codes) and np.array_equal(hdrs, ds.headers)
@@ -242,7 +197,7 @@ class Life:
                    "linear": lambda: b.nns(qc, qh, candidates=few, **gkw),
                    "by_item": lambda: b.nns(query_items=qi, **gkw)}
             for kind in kinds:
-                _same_hits(got[kind](), want[kind])
+                same_hits(got[kind](), want[kind])
 
 
 @pytest.mark.parametrize("metric,dim,n0", LIFECYCLE)
@@ -325,7 +280,7 @@ def test_long_row_refusals_are_loud(orc, hny):
     og0 = orc.build(ds0, **small.kw_o)
 
     def still_builds():
-        _same(hny.build(items0, **small.kw_g), og0)
+        same_graph(hny.build(items0, **small.kw_g), og0)
 
     dim = 2049
     w = Life(orc, hny, 1, dim, 300, M=16, M0=100, ef=32)
@@ -343,7 +298,7 @@ def test_long_row_refusals_are_loud(orc, hny):
             w.b.update(to_insert, vectors=w.mat(to_insert), delete_ids=to_delete, levels=lv)
         assert e.value.code == -5 and "incremental" in str(e.value)
         still_builds()
-        _same(w.b.finish(), w.og)  # the refused source is intact
+        same_graph(w.b.finish(), w.og)  # the refused source is intact
     finally:
         w.close()
     # every item an entry point (all levels 0, hnsw.rs:278-285), more of them than the LDS result set holds: such

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import draw_levels
+from support import hny, same_hits  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -16,13 +17,6 @@ EUCLIDEAN, HAMMING = 1, 3
 N, M, M0, EF = 1500, 6, 12, 32
 NQ, NQ_EXACT = 700, 1100  # chunks of 256 / 256 / 188; blocks of 1 024 / 76
 ALL = 2 ** 32 - 1
-
-
-@pytest.fixture(scope="module")
-def hny():
-    import hannoy_amd
-    hannoy_amd.load_library()
-    return hannoy_amd
 
 
 class _World:
@@ -68,16 +62,6 @@ def world(request, orc, hny):
     w.b.close()
 
 
-def _same(got, want, tag=None):
-    ids, dists, counts = got
-    oids, odists, ocounts = want
-    assert np.array_equal(counts, ocounts), tag
-    for r in range(len(counts)):
-        c = 0 if counts[r] == 0xFFFFFFFF else int(counts[r])
-        assert np.array_equal(ids[r, :c], oids[r, :c]), (tag, r)
-        assert np.array_equal(dists[r, :c].view(np.uint32), odists[r, :c].view(np.uint32)), (tag, r)
-
-
 def _in_slices(call, nq, step=200):
     """call(slice) on slices of one chunk each, concatenated"""
     parts = [call(slice(i, min(i + step, nq))) for i in range(0, nq, step)]
@@ -87,8 +71,8 @@ def _in_slices(call, nq, step=200):
 def _check(call, nq, oracle, tag):
     """the chunked call against its slices (every query) and against the oracle (the first 50)"""
     got = call(slice(0, nq))
-    _same(got, _in_slices(call, nq), tag)
-    _same(tuple(x[:50] for x in got), oracle(slice(0, 50)), tag + " / oracle")
+    same_hits(got, _in_slices(call, nq), tag)
+    same_hits(tuple(x[:50] for x in got), oracle(slice(0, 50)), tag + " / oracle")
     return got
 
 
@@ -105,7 +89,7 @@ def test_knn_chunks(orc, hny, world, monkeypatch, force_retry):
     got = _check(lambda s: w.b.search_knn(w.qc[s], w.qh[s], k=10, ef_search=32), NQ, oracle, "codes")
     assert (got[2] == 10).all()
     got32 = _check(lambda s: w.b.search_knn_f32(w.qs[s], k=10, ef_search=32), NQ, oracle, "f32")
-    _same(got32, got, "f32 == codes")
+    same_hits(got32, got, "f32 == codes")
 
 
 @pytest.mark.parametrize("linear_below", [0, ALL], ids=["heap-search", "linear-scan"])

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from conftest import draw_levels
+from support import NO_COUNTERS, WALK, hny, same_graph  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -56,25 +57,9 @@ def input_sha1(vecs):
 
 
 @pytest.fixture(scope="module")
-def hny():
-    import hannoy_amd
-    hannoy_amd.load_library()
-    return hannoy_amd
-
-
-@pytest.fixture(scope="module")
 def recorded():
     with open(FIXTURE) as f:
         return json.load(f)
-
-
-def _same_graph(g, o):
-    assert g.entry_points.tolist() == o.entry_points.tolist()
-    assert g.max_level == o.max_level
-    assert np.array_equal(g.rec_item, o.rec_item)
-    assert np.array_equal(g.rec_layer, o.rec_layer)
-    assert np.array_equal(g.offsets, o.offsets)
-    assert np.array_equal(g.nbrs, o.nbrs)
 
 
 @pytest.mark.parametrize("case", CASES, ids=case_key)
@@ -88,8 +73,7 @@ def test_short_row_prune_and_apply_counts_equal_the_recording(orc, hny, recorded
         o = orc.build(ds, M=M, M0=M0, ef=ef, order=orc.ORDER_WAVE, threads=8, **kw)
         g = hny.build(items, M=M, M0=M0, ef_construction=ef, **kw)
         print(case_key(case), schedule_key(kw), "n_evals_prune", g.n_evals_prune, "n_evals_apply", g.n_evals_apply)
-        _same_graph(g, o)
-        assert g.n_links_added == o.n_links_added and g.n_evals_walk == o.n_evals_walk
+        same_graph(g, o, counters=WALK)
         built.append((kw, g))
     rec = recorded["cases"][case_key(case)]
     assert input_sha1(vecs) == rec["input_sha1"], (
@@ -102,4 +86,4 @@ def test_short_row_prune_and_apply_counts_equal_the_recording(orc, hny, recorded
         # the workgroup kernels serve these rows with HNY_PRUNE_N8=0: their counts are their own and not
         # pinned, their graph is the same
         monkeypatch.setenv("HNY_PRUNE_N8", "0")
-        _same_graph(hny.build(items, M=M, M0=M0, ef_construction=ef, **kw), o)
+        same_graph(hny.build(items, M=M, M0=M0, ef_construction=ef, **kw), o, counters=NO_COUNTERS)

@@ -9,23 +9,19 @@ Every graph comparison is on a dataset of ONE kind: all its NaN distances then s
 side, no f32 metric yields a negative distance, so the (bits, id) order is the same on both sides whatever the
 pattern is, and the graphs must be identical.  `mixed` (propagated and generated NaNs in one index) builds under
 Manhattan (fabs clears the sign) and Cosine (a propagated NaN gives 0.0) only: DESIGN.md §4."""
+import functools
+
 import numpy as np
 import pytest
 
 from conftest import draw_levels
+from support import hny, same_graph, same_hits  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 EPS = float(np.finfo(np.float32).eps)       # f32::EPSILON, cosine.rs:45
 DENORM_ULP = float(np.float32(2.0 ** -149))  # spacing of the f32 denormals
 KINDS = ("nan", "inf", "huge", "zero", "tiny", "denormal", "mixed")
-
-
-@pytest.fixture(scope="module")
-def hny():
-    import hannoy_amd
-    hannoy_amd.load_library()
-    return hannoy_amd
 
 
 def special_vectors(kind, n, dim, seed):
@@ -72,17 +68,6 @@ def _mk(orc, hny, metric, vecs, levels, ids=None):
     ds = orc.Dataset.from_f32(metric, vecs, levels, ids)
     items = hny.ItemSet(metric, vecs.shape[1], ds.ids, ds.codes, ds.headers, ds.levels)
     return ds, items
-
-
-def _same_graph(g, o):
-    assert g.entry_points.tolist() == o.entry_points.tolist()
-    assert g.max_level == o.max_level
-    assert np.array_equal(g.rec_item, o.rec_item)
-    assert np.array_equal(g.rec_layer, o.rec_layer)
-    assert np.array_equal(g.offsets, o.offsets)
-    assert np.array_equal(g.nbrs, o.nbrs)
-    assert g.n_links_added == o.n_links_added
-    assert g.n_evals_walk == o.n_evals_walk
 
 
 def _same_dists(got, want, tag=None):
@@ -298,7 +283,7 @@ def test_build_with_special_rows_equals_oracle(cache, orc, hny, monkeypatch, met
         o = _oracle(cache, orc, metric, kind, ds, M, M0, ef, frac, bmax)
         g = hny.build(items, M=M, M0=M0, ef_construction=ef, batch_frac=frac, batch_max=bmax)
         assert g.n_tie_pool_overflow == 0
-        _same_graph(g, o)
+        same_graph(g, o)
 
 
 def test_inf_ties_overflow_the_tie_pool_naturally(cache, orc, hny):
@@ -309,7 +294,7 @@ def test_inf_ties_overflow_the_tie_pool_naturally(cache, orc, hny):
     o = _oracle(cache, orc, metric, kind, ds, M, M0, ef, 0.05, 64)
     g = hny.build(items, M=M, M0=M0, ef_construction=ef, batch_frac=0.05, batch_max=64)
     assert g.n_tie_pool_overflow == 0
-    _same_graph(g, o)
+    same_graph(g, o)
 
 
 @pytest.mark.parametrize("n8", ["1", "0"])
@@ -320,7 +305,7 @@ def test_prune_of_zero_distance_ties(cache, orc, hny, monkeypatch, n8):
     metric, kind, n, dim, M, M0, ef = 0, "zero", 1500, 24, 8, 16, 40
     _, _, ds, items = _data(cache, orc, hny, metric, kind, n, dim, M)
     o = _oracle(cache, orc, metric, kind, ds, M, M0, ef, 0.05, 64)
-    _same_graph(hny.build(items, M=M, M0=M0, ef_construction=ef, batch_frac=0.05, batch_max=64), o)
+    same_graph(hny.build(items, M=M, M0=M0, ef_construction=ef, batch_frac=0.05, batch_max=64), o)
 
 
 @pytest.mark.parametrize("metric,kind,n,dim,M,M0,ef", [
@@ -334,7 +319,7 @@ def test_long_rows_wide_beams_and_paged_lists_with_nan_distances(cache, orc, hny
     o = _oracle(cache, orc, metric, kind, ds, M, M0, ef, 0.05, 64)
     g = hny.build(items, M=M, M0=M0, ef_construction=ef, batch_frac=0.05, batch_max=64)
     assert g.n_tie_pool_overflow == 0
-    _same_graph(g, o)
+    same_graph(g, o)
 
 
 STRICT_KINDS = {0: ("zero", "inf", "tiny"), 1: ("nan", "inf", "huge"), 2: ("nan", "inf", "denormal")}
@@ -350,7 +335,7 @@ def test_strict_mode_with_special_rows_equals_x86_oracle(cache, orc, hny, metric
         _, _, ds, items = _data(cache, orc, hny, metric, kind, n, dim, M)
         o = _oracle(cache, orc, metric, kind, ds, M, M0, ef, 0.0, 0, x86=True)
         g = hny.build(items, M=M, M0=M0, ef_construction=ef, batch_max=1, x86_order=True)
-        _same_graph(g, o)
+        same_graph(g, o)
 
 
 def test_f32_ingest_of_inf_rows_builds_the_same_graph(cache, orc, hny):
@@ -361,7 +346,7 @@ def test_f32_ingest_of_inf_rows_builds_the_same_graph(cache, orc, hny):
     o = _oracle(cache, orc, metric, kind, ds, M, M0, ef, 0.05, 64)
     f32 = hny.ItemSet.from_f32(metric, vecs, levels=ds.levels, device=True)
     g = hny.build(f32, M=M, M0=M0, ef_construction=ef, batch_frac=0.05, batch_max=64)
-    _same_graph(g, o)
+    same_graph(g, o)
     with hny.Builder(f32, M=M, M0=M0, ef_construction=ef) as b:
         codes, hdrs = b.export_items()
     assert np.array_equal(codes, ds.codes)
@@ -388,7 +373,7 @@ def test_update_with_special_rows(orc, hny, metric, kind):
     og = orc.build(ds, **kw_o)
     _guard(orc, metric, kind, ds, og, ef)
     gg = hny.build(items, **kw_g)
-    _same_graph(gg, og)
+    same_graph(gg, og)
 
     sp = np.flatnonzero(special[:n0])
     sp = sp[rng.permutation(len(sp))]
@@ -408,15 +393,15 @@ def test_update_with_special_rows(orc, hny, metric, kind):
     og2 = orc.build_incremental(ds2, og, to_insert, lv, to_delete, **kw_o)
     _guard(orc, metric, kind, ds2, og2, ef)
     gg2 = hny.build_incremental(items2, gg, to_insert, to_delete, **kw_g)
-    _same_graph(gg2, og2)
+    same_graph(gg2, og2)
     d = gg2.as_dict()
     assert all(set(nb) <= set(alive.tolist()) for nb in d.values())
     with hny.Builder(items, **kw_g) as b:
         b.run()
-        _same_graph(b.finish(), gg)
+        same_graph(b.finish(), gg)
         c, h = hny.encode_vectors(metric, vecs[to_insert])
         gb = b.update(to_insert, codes=c, headers=h, delete_ids=to_delete, levels=lv)
-        _same_graph(gb, gg2)
+        same_graph(gb, gg2)
         codes, hdrs = b.export_items()
         assert np.array_equal(codes, ds2.codes) and np.array_equal(hdrs, ds2.headers)
 
@@ -424,14 +409,7 @@ def test_update_with_special_rows(orc, hny, metric, kind):
 # ---------------------------------------------------------------------------------------------------------
 # 4. search
 # ---------------------------------------------------------------------------------------------------------
-def _same_hits(got, want, tag):
-    ids, dists, counts = got
-    oids, odists, ocounts = want
-    assert np.array_equal(counts, ocounts), tag
-    for r in range(len(counts)):
-        c = 0 if counts[r] == 0xFFFFFFFF else int(counts[r])
-        assert np.array_equal(ids[r, :c], oids[r, :c]), (tag, r)
-        _same_dists(dists[r, :c], odists[r, :c], (tag, r))
+equal_hits = functools.partial(same_hits, dists=_same_dists)  # a NaN is a NaN, whatever its bits
 
 
 @pytest.mark.parametrize("metric,kind", [(1, "nan"), (1, "inf"), (0, "zero"), (1, "huge"), (0, "inf"), (2, "nan")])
@@ -456,13 +434,13 @@ def test_search_on_graphs_with_special_rows(cache, orc, hny, metric, kind):
     kw = dict(order=orc.ORDER_WAVE, threads=8)
     with hny.Builder(items, M=M, M0=M0, ef_construction=ef, batch_frac=0.05, batch_max=64) as b:
         b.run()
-        _same_graph(b.finish(), o)
+        same_graph(b.finish(), o)
         for ef_s in (50, n):
-            _same_hits(b.search_knn(qc, qh, k=10, ef_search=ef_s),
+            equal_hits(b.search_knn(qc, qh, k=10, ef_search=ef_s),
                        orc.search(ds, o, qc, qh, k=10, ef_search=ef_s, **kw), ("knn", ef_s))
-        _same_hits(b.nns(qc, qh, k=10, ef_search=50, candidates=wide, linear_below=100),
+        equal_hits(b.nns(qc, qh, k=10, ef_search=50, candidates=wide, linear_below=100),
                    orc.search(ds, o, qc, qh, k=10, ef_search=50, candidates=wide, linear_below=100, **kw), "filtered")
-        _same_hits(b.nns(qc, qh, k=10, ef_search=50, candidates=few, linear_below=1000),
+        equal_hits(b.nns(qc, qh, k=10, ef_search=50, candidates=few, linear_below=1000),
                    orc.search(ds, o, qc, qh, k=10, ef_search=50, candidates=few, linear_below=1000, **kw), "linear")
-        _same_hits(b.nns(k=10, ef_search=50, query_items=qi),
+        equal_hits(b.nns(k=10, ef_search=50, query_items=qi),
                    orc.search(ds, o, None, None, k=10, ef_search=50, query_items=qi, **kw), "by_item")

@@ -5,26 +5,9 @@ import numpy as np
 import pytest
 
 from conftest import draw_levels
+from support import apply_delta, check_delta, hny, same_graph  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def hny():
-    import hannoy_amd
-    hannoy_amd.load_library()
-    return hannoy_amd
-
-
-def _same(a, b):
-    assert a.entry_points.tolist() == b.entry_points.tolist()
-    assert a.max_level == b.max_level
-    assert np.array_equal(a.rec_item, b.rec_item)
-    assert np.array_equal(a.rec_layer, b.rec_layer)
-    assert np.array_equal(a.offsets, b.offsets)
-    assert np.array_equal(a.nbrs, b.nbrs)
-    assert a.n_links_added == b.n_links_added
-    assert a.n_evals_walk == b.n_evals_walk
 
 
 class World:
@@ -60,28 +43,6 @@ class World:
         return np.array(sorted(overwrite + added), np.uint32), np.array(to_delete, np.uint32)
 
 
-def _apply_delta(prev, d):
-    out = dict(prev)
-    for k in d.removed_keys():
-        assert k in out, f"removed key {k} never existed"
-        del out[k]
-    out.update(d.as_dict())
-    return out
-
-
-def _check_delta(prev, full, d, to_delete):
-    """the delta definition: prev - removed + records == full; nothing unchanged in it; removed = keys of deleted items"""
-    fd = full.as_dict()
-    assert _apply_delta(prev, d) == fd
-    for k, nb in d.as_dict().items():
-        assert prev.get(k) != nb, f"record {k} is in the delta with an unchanged list"
-    gone = set(int(i) for i in to_delete)
-    assert sorted(d.removed_keys()) == sorted(k for k in prev if k[0] in gone)
-    assert d.n_records_total == len(fd) == len(full.rec_item)
-    assert d.entry_points.tolist() == full.entry_points.tolist() and d.max_level == full.max_level
-    return fd
-
-
 CHAIN = [(1, 24, 6, 12, 32, 0.0, 1, 0), (0, 48, 8, 16, 40, 0.1, 64, 0), (3, 128, 8, 16, 24, 0.1, 32, 0),
          (1, 40, 16, 100, 40, 0.1, 64, 0),   # wide lists
          (4, 64, 8, 16, 32, 0.1, 64, 0),     # a BQ metric
@@ -103,7 +64,7 @@ def test_chain_parity_state_and_delta(hny, metric, dim, M, M0, ef, frac, bmax, x
     try:
         b.run()
         gb = b.finish()
-        _same(ga, gb)
+        same_graph(ga, gb)
         prev = gb.as_dict()
         for rnd in range(3):
             to_insert, to_delete = w.round()
@@ -115,8 +76,8 @@ def test_chain_parity_state_and_delta(hny, metric, dim, M, M0, ef, frac, bmax, x
             was_successor = b.incremental
             gb, d = b.update(to_insert, codes=c, headers=h, delete_ids=to_delete, levels=lv, seed=77 + rnd, delta=True)
             assert b.incremental and was_successor == (rnd > 0)  # from the second round on the source is itself a successor
-            _same(ga, gb)
-            prev = _check_delta(prev, gb, d, to_delete)
+            same_graph(ga, gb)
+            prev = check_delta(prev, gb, d, to_delete)
             codes, hdrs = b.export_items()
             assert np.array_equal(b.items.ids, items.ids)
             assert np.array_equal(codes, items.codes) and np.array_equal(hdrs, items.headers)
@@ -141,14 +102,14 @@ def test_f32_upserts_equal_build_incremental_f32(hny, metric, dim):
     ga = hny.build(items, **kw)
     with hny.Builder(items, **kw) as b:
         b.run()
-        _same(ga, b.finish())
+        same_graph(ga, b.finish())
         for rnd in range(2):
             to_insert, to_delete = w.round(100, 30, 150)
             lv = draw_levels(len(to_insert), M, seed=20 + rnd)
             items = w.items(lv, f32=True)
             ga = hny.build_incremental(items, ga, to_insert, to_delete, **kw)
             gb = b.update(to_insert, vectors=w.mat(to_insert), delete_ids=to_delete, levels=lv)
-            _same(ga, gb)
+            same_graph(ga, gb)
             codes, hdrs = b.export_items()
             assert np.array_equal(codes, items.codes) and np.array_equal(hdrs, items.headers)
 
@@ -162,8 +123,8 @@ def _one_round(hny, w, kw, ga, src, to_insert, to_delete, lv):
         s.run()
         gb2 = s.finish()
         d = s.finish_delta()
-        _same(ga2, gb2)
-        _check_delta(ga.as_dict(), gb2, d, to_delete)
+        same_graph(ga2, gb2)
+        check_delta(ga.as_dict(), gb2, d, to_delete)
     return ga2
 
 
@@ -178,7 +139,7 @@ def test_sources_and_degenerate_updates(hny):
     state = (dict(w.vecs), w.next_id)
     with hny.Builder(items, **kw) as b, hny.Builder(items, prev=ga, load=True, **kw) as ld:
         b.run()
-        _same(ga, b.finish())
+        same_graph(ga, b.finish())
         for src in (b, ld):
             for n_del, n_over, n_add, ghosts in [(120, 40, 200, 0), (150, 0, 0, 0), (0, 30, 100, 0), (0, 0, 0, 0),
                                                  (60, 10, 50, 7)]:
@@ -219,8 +180,8 @@ def test_update_deleting_every_entry_point(hny, new_level1):
         prev = b.finish().as_dict()
         c, h = hny.encode_vectors(6, vecs[to_insert])
         gb2, d = b.update(to_insert, codes=c, headers=h, delete_ids=to_delete, levels=lv, delta=True)
-        _same(ga2, gb2)
-        _check_delta(prev, gb2, d, to_delete)
+        same_graph(ga2, gb2)
+        check_delta(prev, gb2, d, to_delete)
 
 
 def test_delta_of_a_small_addition_is_small(hny):
@@ -240,7 +201,7 @@ def test_delta_of_a_small_addition_is_small(hny):
         assert len(d.removed_item) == 0
         assert d.n_records_total == len(g1.rec_item) > n
         assert 5 <= len(d.rec_item) < d.n_records_total / 10
-        assert _apply_delta(g0.as_dict(), d) == g1.as_dict()
+        assert apply_delta(g0.as_dict(), d) == g1.as_dict()
 
 
 def test_refusals_leak_nothing(hny):
@@ -269,7 +230,7 @@ def test_refusals_leak_nothing(hny):
         with pytest.raises(hny.HannoyError) as e:
             b.finish_delta()
         assert e.value.code == hny.ERR_INVALID_ARG and "successor" in str(e.value)
-        _same(ga, b.finish())
+        same_graph(ga, b.finish())
         for ups, dels in ((to_insert[::-1], to_delete), (to_insert, to_delete[::-1]),
                           (np.repeat(to_insert, 2)[:len(to_insert)], to_delete)):
             with pytest.raises(hny.HannoyError) as e:
@@ -293,9 +254,9 @@ def test_refusals_leak_nothing(hny):
             assert e.value.code == hny.ERR_INVALID_ARG
             s.fill_gaps()
             ga2 = hny.build_incremental(w.items(lv), ga, to_insert, to_delete, **kw)
-            _same(ga2, s.finish())
+            same_graph(ga2, s.finish())
         # after all the refusals the good call works on the same builder
-        _same(ga2, b.update(to_insert, codes=c, headers=h, delete_ids=to_delete, levels=lv))
+        same_graph(ga2, b.update(to_insert, codes=c, headers=h, delete_ids=to_delete, levels=lv))
 
 
 @pytest.mark.parametrize("metric,dim", [(0, 24), (1, 24), (3, 256)])
@@ -329,10 +290,10 @@ def test_four_row_sources_give_one_graph(hny, metric, dim):
     for ups in (dict(codes=c, headers=h), dict(vectors=w.mat(to_insert))):
         with hny.Builder(items, **kw) as b:
             b.run()
-            _same(g0, b.finish())
+            same_graph(g0, b.finish())
             graphs.append(b.update(to_insert, delete_ids=to_delete, levels=lv, **ups))
             codes, hdrs = b.export_items()
             assert np.array_equal(b.items.ids, want.ids)
             assert np.array_equal(codes, want.codes) and np.array_equal(hdrs, want.headers)
     for g in graphs[1:]:
-        _same(graphs[0], g)
+        same_graph(graphs[0], g)

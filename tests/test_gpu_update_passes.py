@@ -14,7 +14,8 @@ import numpy as np
 import pytest
 
 from conftest import draw_levels
-from test_gpu_update import World, _check_delta, _same
+from support import NO_COUNTERS, check_delta, hny, identical_hits, same_graph  # noqa: F401
+from test_gpu_update import World
 
 pytestmark = pytest.mark.gpu
 
@@ -58,13 +59,6 @@ assert chunked_trip(768) == (5, 10240) and chunked_trip(1024) == (4, 8192)
 assert n16_of(3, 131072) == 1024 and GATHER_TRIP == 8192
 
 
-@pytest.fixture(scope="module")
-def hny():
-    import hannoy_amd
-    hannoy_amd.load_library()
-    return hannoy_amd
-
-
 class SpreadWorld(World):
     """World whose ids are drawn from one range for the base items and for every round's new items: the sorted slot
     order interleaves old and new rows instead of appending the new ones"""
@@ -92,18 +86,11 @@ class SpreadWorld(World):
         return np.array(sorted(overwrite + added), np.uint32), np.array(to_delete, np.uint32)
 
 
-def _same_as_oracle(g, o):
-    assert g.entry_points.tolist() == o.entry_points.tolist() and g.max_level == o.max_level
-    assert np.array_equal(g.rec_item, o.rec_item) and np.array_equal(g.rec_layer, o.rec_layer)
-    assert np.array_equal(g.offsets, o.offsets) and np.array_equal(g.nbrs, o.nbrs)
-
-
 def _search_equals_loaded_copy(hny, b, items, ga, kw, qc, qh):
     with hny.Builder(items, prev=ga, load=True, **kw) as ld:
         want = ld.search_knn(qc, qh, k=10, ef_search=50)
     got = b.search_knn(qc, qh, k=10, ef_search=50)
-    assert np.array_equal(got[2], want[2]) and np.array_equal(got[0], want[0])
-    assert np.array_equal(got[1].view(np.uint32), want[1].view(np.uint32))
+    identical_hits(got, want)
 
 
 # (metric, dim, M, M0, ef, n0, rounds of (deletes, overwrites, additions), oracle)
@@ -135,13 +122,13 @@ def test_update_beyond_one_grid(orc, hny, metric, dim, M, M0, ef, n0, rounds, or
     ga = hny.build(items, **kw)
     if oracle:
         og = orc.build(orc.Dataset(metric, dim, items.ids, items.codes, items.headers, items.levels), **kw_o)
-        _same_as_oracle(ga, og)
+        same_graph(ga, og, counters=NO_COUNTERS)
     q = w.rng.uniform(-1, 1, (64, dim)).astype(np.float32)
     qc, qh = hny.encode_vectors(metric, q)
     with hny.Builder(items, **kw) as b:
         b.run()
         gb = b.finish()
-        _same(ga, gb)
+        same_graph(ga, gb)
         prev = gb.as_dict()
         for rnd, (n_del, n_over, n_add) in enumerate(rounds):
             to_insert, to_delete = w.round(n_del, n_over, n_add)
@@ -155,14 +142,14 @@ def test_update_beyond_one_grid(orc, hny, metric, dim, M, M0, ef, n0, rounds, or
             assert np.array_equal(b.items.ids, items.ids)
             assert np.array_equal(codes, items.codes) and np.array_equal(hdrs, items.headers)
             # graph and delta
-            _same(ga, gb)
-            prev = _check_delta(prev, gb, d, to_delete)
+            same_graph(ga, gb)
+            prev = check_delta(prev, gb, d, to_delete)
             if rnd == 0 and n_add > GATHER_TRIP:
                 assert len(d.rec_item) > GATHER_TRIP
             if oracle:
                 ds = orc.Dataset(metric, dim, items.ids, items.codes, items.headers, np.zeros(items.n, np.uint8))
                 og = orc.build_incremental(ds, og, to_insert, lv, to_delete, **kw_o)
-                _same_as_oracle(gb, og)
+                same_graph(gb, og, counters=NO_COUNTERS)
             _search_equals_loaded_copy(hny, b, items, ga, kw, qc, qh)
 
 
@@ -207,11 +194,11 @@ def test_scatter_of_16_kb_rows_beyond_one_grid(hny):
     with hny.Builder(items0, **kw) as b:
         b.run()
         gb0 = b.finish()
-        _same(ga0, gb0)
+        same_graph(ga0, gb0)
         gb, d = b.update(to_insert, codes=up_codes, headers=np.zeros((SCATTER_UPSERTS, hb), np.uint8),
                          delete_ids=to_delete, levels=lv, delta=True)
         codes, hdrs = b.export_items()
         assert np.array_equal(b.items.ids, ids1) and np.array_equal(codes, codes1) and not hdrs.any()
-        _same(ga, gb)
-        _check_delta(gb0.as_dict(), gb, d, to_delete)
+        same_graph(ga, gb)
+        check_delta(gb0.as_dict(), gb, d, to_delete)
         _search_equals_loaded_copy(hny, b, items1, ga, kw, up_codes[:16], np.zeros((16, hb), np.uint8))

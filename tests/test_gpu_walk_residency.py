@@ -9,11 +9,13 @@ residency.  The switch is read when a builder is created: every value runs in a 
 import os
 import subprocess
 import sys
+import types
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
+from support import same_graph
 
 pytestmark = pytest.mark.gpu
 
@@ -63,18 +65,7 @@ def _child_build(case, tag, expect_error=None, **env):
         assert r.returncode != 0 and expect_error in r.stderr, r.stderr[-2000:]
         return None
     assert r.returncode == 0, r.stderr[-2000:]
-    return np.load(out)
-
-
-def _same(g, o):
-    assert g["entry_points"].tolist() == o.entry_points.tolist()
-    assert int(g["max_level"]) == o.max_level
-    assert np.array_equal(g["rec_item"], o.rec_item)
-    assert np.array_equal(g["rec_layer"], o.rec_layer)
-    assert np.array_equal(g["offsets"], o.offsets)
-    assert np.array_equal(g["nbrs"], o.nbrs)
-    assert int(g["n_links_added"]) == o.n_links_added
-    assert int(g["n_evals_walk"]) == o.n_evals_walk
+    return types.SimpleNamespace(**np.load(out))
 
 
 @pytest.fixture(scope="module")
@@ -104,7 +95,7 @@ def test_tiled_walk_equals_oracle_at_every_residency(tiled_case, waves_per_cu):
     """4 096 (= walk_slots), 1 024 and 256 resident waves on the tiled queue of the 3 000-member batch: with 256 waves
     (32 per counter) every wave claims members from several tiles of its XCD"""
     g = _child_build(tiled_case, f"r{waves_per_cu}", HNY_XCD_TILE=64, HNY_WALK_RESIDENT=waves_per_cu)
-    _same(g, tiled_case["oracle"])
+    same_graph(g, tiled_case["oracle"])
 
 
 @pytest.mark.parametrize("tile,waves_per_cu", [(64, 1), (64, 4), (256, 1)])
@@ -113,14 +104,14 @@ def test_partial_last_tile_and_untiled_fallback(short_case, tile, waves_per_cu):
     tile and its waves steal from the next XCD); tiles of 256 would be fewer than 16, so the launch falls back to
     the single counter on walk_slots waves whatever the residency asked for"""
     g = _child_build(short_case, f"t{tile}r{waves_per_cu}", HNY_XCD_TILE=tile, HNY_WALK_RESIDENT=waves_per_cu)
-    _same(g, short_case["oracle"])
+    same_graph(g, short_case["oracle"])
 
 
 def test_heap_retry_behind_reduced_residency(tiled_case):
     """HNY_POOL_FORCE_RETRY=3: every third member of every walk launch is handed to k_walk_heap, behind a tiled
     launch of 1 024 waves; the heap kernel's evaluations are the ones counted"""
     g = _child_build(tiled_case, "retry", HNY_XCD_TILE=64, HNY_WALK_RESIDENT=4, HNY_POOL_FORCE_RETRY=3)
-    _same(g, tiled_case["oracle"])
+    same_graph(g, tiled_case["oracle"])
 
 
 @pytest.mark.parametrize("value", [-1, 257])

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import draw_levels
+from support import WALK, same_graph
 
 N, M, M0, EF, BATCH_MAX, BATCH_FRAC = 2000, 4, 8, 16, 64, 0.5
 SENTINEL = np.uint64(0xDEADBEEFDEADBEEF)
@@ -20,14 +21,11 @@ def _dataset(orc, metric):
     return orc.Dataset.from_f32(metric, rng.uniform(-1, 1, (N, dim)).astype(np.float32), levels)
 
 
-def same_graph(a, b):
-    """two orc.Graph: everything either exports"""
-    assert np.array_equal(a.rec_item, b.rec_item) and np.array_equal(a.rec_layer, b.rec_layer)
-    assert np.array_equal(a.offsets, b.offsets) and np.array_equal(a.nbrs, b.nbrs)
+def same_export(a, b):
+    """two orc.Graph: everything either exports, the raw lists and their distance bits included"""
+    same_graph(a, b, counters=WALK)
     assert np.array_equal(a.raw_offsets, b.raw_offsets) and np.array_equal(a.raw_nbrs, b.raw_nbrs)
     assert np.array_equal(a.raw_dists.view(np.uint32), b.raw_dists.view(np.uint32))
-    assert np.array_equal(a.entry_points, b.entry_points) and a.max_level == b.max_level
-    assert a.n_evals_walk == b.n_evals_walk and a.n_links_added == b.n_links_added
     assert a.n_distance_evals == b.n_distance_evals
 
 
@@ -77,7 +75,7 @@ def test_stepping_every_batch_is_orc_build(orc, metric, order, many_threads):
             if len(ids) < st.cap(layer):
                 assert not st.prunes_to_itself(layer, item)
     assert n_done == N and len(levels_seen) >= 3
-    same_graph(got, want)
+    same_export(got, want)
 
 
 def test_apply_takes_a_foreign_selection(orc):
@@ -130,4 +128,4 @@ def test_threaded_apply_is_the_sequential_one(orc):
             for layer, slot in fa[::7]:
                 assert a.prunes_to_itself(int(layer), int(slot)) == b.prunes_to_itself(int(layer), int(slot))
         assert b.next_batch().count == 0 and most == 512
-        same_graph(a.finish(), b.finish())
+        same_export(a.finish(), b.finish())
