@@ -43,10 +43,13 @@ EXPORTED = [
     "hny_distance_keeps_links", "hny_builder_create_changed_distance", "hny_builder_recode_items",
     "hny_builder_nns_bitsets", "hny_builder_nns_bitsets_f32",
     "hny_builder_exact_knn_bitsets", "hny_builder_exact_knn_bitsets_f32",
+    "hny_builder_exact_range", "hny_builder_exact_range_f32", "hny_builder_exact_range_count",
+    "hny_builder_exact_range_count_f32", "hny_range_result_free",
 ]
 ERR_IO = -9
 NNS_NONE = 0xFFFFFFFF  # by_item: the reference returns None
 NNS_FILTER_NONE = 0xFFFFFFFF  # hny_query_filters.filter_of: no .candidates() for this query
+RANGE_NONE = 0xFFFFFFFFFFFFFFFF  # exact_range_count by_item: the reference returns None
 
 
 CANCEL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
@@ -130,6 +133,23 @@ class QueryBitsets(C.Structure):
         s.bits = _p(bits).value if bits.size else None
         s.filter_of = _p(fo).value
         return s, (bits, n_bits, fo)
+
+
+class RangeOpts(C.Structure):
+    """hny_range_opts; struct_size is the guard (the struct is not part of hny_abi_sizes)"""
+    _fields_ = [("struct_size", C.c_uint32), ("has_candidates", C.c_int32), ("candidates", C.c_void_p),
+                ("n_candidates", C.c_uint64), ("radius", C.c_void_p), ("max_total", C.c_uint64),
+                ("cancel", CANCEL_FN), ("cancel_ctx", C.c_void_p), ("did_cancel", C.POINTER(C.c_int32))]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_size = C.sizeof(RangeOpts)
+
+
+class RangeResult(C.Structure):
+    """hny_range_result: owned by the library (hny_range_result_free)"""
+    _fields_ = [("n_queries", C.c_uint64), ("offsets", C.POINTER(C.c_uint64)), ("ids", C.POINTER(C.c_uint32)),
+                ("dists", C.POINTER(C.c_float)), ("is_none", C.POINTER(C.c_uint8))]
 
 
 class HannoyError(RuntimeError):
@@ -377,6 +397,18 @@ def load_library():
         fn.restype = f32.restype = C.c_int
         fn.argtypes = [vp, C.POINTER(QueryOpts), C.POINTER(QueryBitsets)] + L.hny_builder_nns_filtered.argtypes[3:]
         f32.argtypes = [vp, C.POINTER(QueryOpts), C.POINTER(QueryBitsets)] + L.hny_builder_nns_filtered_f32.argtypes[3:]
+    L.hny_builder_exact_range.restype = C.c_int
+    L.hny_builder_exact_range.argtypes = [vp, C.POINTER(RangeOpts), C.c_uint64, vp, C.c_size_t, vp, vp,
+                                          C.POINTER(C.POINTER(RangeResult))]
+    L.hny_builder_exact_range_f32.restype = C.c_int
+    L.hny_builder_exact_range_f32.argtypes = [vp, C.POINTER(RangeOpts), C.c_uint64, vp, C.c_size_t,
+                                              C.POINTER(C.POINTER(RangeResult))]
+    L.hny_builder_exact_range_count.restype = C.c_int
+    L.hny_builder_exact_range_count.argtypes = [vp, C.POINTER(RangeOpts), C.c_uint64, vp, C.c_size_t, vp, vp, vp]
+    L.hny_builder_exact_range_count_f32.restype = C.c_int
+    L.hny_builder_exact_range_count_f32.argtypes = [vp, C.POINTER(RangeOpts), C.c_uint64, vp, C.c_size_t, vp]
+    L.hny_range_result_free.restype = None
+    L.hny_range_result_free.argtypes = [C.POINTER(RangeResult)]
     L.hny_builder_exact_rows_read.restype = C.c_uint64
     L.hny_builder_exact_rows_read.argtypes = [vp]
     L.hny_builder_create_update.restype = C.c_int
@@ -609,6 +641,28 @@ def _query_source(query_items=None, qf32=None, qcodes=None, qheaders=None):
     qcodes = np.ascontiguousarray(qcodes, np.uint8)
     qheaders = np.ascontiguousarray(qheaders, np.uint8)
     return (qcodes.shape[0], _p(qcodes), qcodes.shape[1], _p(qheaders), None), (qcodes, qheaders)
+
+
+def _range_opts(radius, nq, candidates=None, cancel=None, max_total=0):
+    """hny_range_opts of one range call.  radius: a scalar or one value per query.
+    Returns (struct, what it points into, the int32 did_cancel points at)"""
+    ro = RangeOpts()
+    r = np.asarray(radius, np.float32)
+    r = np.full(nq, r, np.float32) if r.ndim == 0 else np.ascontiguousarray(r.ravel())
+    if len(r) != nq:
+        raise ValueError(f"radius has {len(r)} entries for {nq} queries")
+    flag = C.c_int32(0)
+    keep = [flag, r]
+    ro.radius, ro.max_total = r.ctypes.data, int(max_total)
+    if cancel is not None:
+        fn = CANCEL_FN(lambda _ctx: 1 if cancel() else 0)
+        ro.cancel, ro.did_cancel = fn, C.pointer(flag)
+        keep.append(fn)
+    if candidates is not None:
+        cand = np.ascontiguousarray(candidates, np.uint32)
+        ro.has_candidates, ro.candidates, ro.n_candidates = 1, cand.ctypes.data, len(cand)
+        keep.append(cand)
+    return ro, keep, flag
 
 
 def _result_arrays(nq, k):
@@ -1310,6 +1364,54 @@ class Builder:
         opts = _query_opts(k, candidates=candidates, cancel=cancel)
         return self._search("hny_builder_exact_knn", opts, _query_source(query_items, qf32, qcodes, qheaders),
                             qf32 is not None)
+
+    def _range(self, radius, count_only, qcodes, qheaders, candidates, query_items, cancel, qf32, max_total):
+        (nq, qc, qs, qh, qi), _arrays = _query_source(query_items, qf32, qcodes, qheaders)
+        ro, _keep, flag = _range_opts(radius, nq, candidates, cancel, max_total)
+        self._cancel_flag = flag
+        L = load_library()
+        name = "hny_builder_exact_range" + ("_count" if count_only else "") + ("_f32" if qf32 is not None else "")
+        src = (nq, qc, qs) if qf32 is not None else (nq, qc, qs, qh, qi)
+        if count_only:
+            counts = np.zeros(nq, np.uint64)
+            _check(getattr(L, name)(self._h, C.byref(ro), *src, _p(counts)))
+            self.did_cancel = bool(flag.value)
+            return counts
+        res = C.POINTER(RangeResult)()
+        _check(getattr(L, name)(self._h, C.byref(ro), *src, C.byref(res)))
+        try:
+            r = res.contents
+            offsets = np.ctypeslib.as_array(r.offsets, (nq + 1,)).copy()
+            total = int(offsets[-1])
+            ids = np.ctypeslib.as_array(r.ids, (total,)).copy() if total else np.zeros(0, np.uint32)
+            dists = np.ctypeslib.as_array(r.dists, (total,)).copy() if total else np.zeros(0, np.float32)
+            is_none = np.ctypeslib.as_array(r.is_none, (nq,)).copy() if nq else np.zeros(0, np.uint8)
+        finally:
+            L.hny_range_result_free(res)
+        self.did_cancel = bool(flag.value)
+        return offsets, ids, dists, is_none
+
+    def exact_range(self, radius, qcodes=None, qheaders=None, candidates=None, query_items=None, cancel=None,
+                    qf32=None, max_total=0):
+        """hny_builder_exact_range: every live item (or every one of `candidates` among them) whose distance to query
+        i is <= radius[i] (a scalar holds for every query), ordered by (distance bits, item id).  Returns (offsets
+        [nq + 1], ids, dists, is_none): the hits of query i are ids / dists[offsets[i]:offsets[i + 1]]; is_none is 1
+        where by_item names an unknown item.  max_total != 0: more hits than that in all are refused."""
+        return self._range(radius, False, qcodes, qheaders, candidates, query_items, cancel, qf32, max_total)
+
+    def exact_range_f32(self, queries, radius, **kw):
+        """exact_range(by_vector) with f32 queries, encoded on the device"""
+        return self.exact_range(radius, qf32=_f32_rows(queries), **kw)
+
+    def exact_range_count(self, radius, qcodes=None, qheaders=None, candidates=None, query_items=None, cancel=None,
+                          qf32=None):
+        """hny_builder_exact_range_count: the sizes of exact_range's rows alone (uint64), RANGE_NONE where by_item
+        names an unknown item; one scan, nothing is emitted or sorted"""
+        return self._range(radius, True, qcodes, qheaders, candidates, query_items, cancel, qf32, 0)
+
+    def exact_range_count_f32(self, queries, radius, **kw):
+        """exact_range_count(by_vector) with f32 queries, encoded on the device"""
+        return self.exact_range_count(radius, qf32=_f32_rows(queries), **kw)
 
     def exact_knn_filtered_f32(self, queries, filters, filter_of, **kw):
         """exact_knn_filtered(by_vector) with f32 queries, encoded on the device"""

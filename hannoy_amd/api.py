@@ -595,6 +595,7 @@ class QueryBuilder:
         self._exact = False
         self._per_query = None
         self._bitsets = None
+        self._radius = None
 
     def ef_search(self, ef):
         self._ef = int(ef)
@@ -669,6 +670,34 @@ class QueryBuilder:
         self._exact = True
         return self
 
+    def within(self, radius):
+        """only the hits with distance <= radius, a scalar or one value per query of by_vectors / by_items, which
+        then return (offsets [nq + 1], ids, dists): the hits of query i are ids / dists[offsets[i]:offsets[i + 1]].
+        With .exact() every such item (hny_builder_exact_range; count is not read, .candidates() is honoured);
+        otherwise the graph search with its count, each row cut to the hits within the radius.  A by_item query
+        without an answer has no hits"""
+        self._radius = radius
+        return self
+
+    def _cut(self, hits):
+        """(ids, dists, counts) of a top-k search as the CSR of within(): per row the hits with distance <= radius"""
+        ids, dists, counts = hits
+        nq = len(counts)
+        r = np.asarray(self._radius, np.float32)
+        r = np.full(nq, r, np.float32) if r.ndim == 0 else r.ravel()
+        if len(r) != nq:
+            raise ValueError(f"radius has {len(r)} entries for {nq} queries")
+        c = np.where(counts == capi.NNS_NONE, 0, counts).astype(np.int64)
+        keep = (np.arange(ids.shape[1])[None, :] < c[:, None]) & (dists <= r[:, None])
+        offsets = np.zeros(nq + 1, np.uint64)
+        offsets[1:] = np.cumsum(keep.sum(axis=1), dtype=np.uint64)
+        return offsets, ids[keep], dists[keep]
+
+    def _within_exact(self, **source):
+        if self._per_query is not None or self._bitsets is not None:
+            raise ValueError("within().exact() takes one .candidates() for the whole call, not a filter per query")
+        return self.reader._b.exact_range(self._radius, candidates=self._candidates, **source)[:3]
+
     def _kw(self):
         return dict(k=self.count, ef_search=self._ef, candidates=self._candidates,
                     linear_below=self._linear_below, linear_below_ratio=self._ratio)
@@ -679,6 +708,15 @@ class QueryBuilder:
         q = np.ascontiguousarray(vectors, np.float32)
         if q.ndim != 2 or q.shape[1] != r.dimensions:
             raise InvalidVecDimension(f"expected {r.dimensions}, received {q.shape[-1]}")
+        if self._radius is not None:
+            if self._exact:
+                return self._within_exact(qf32=capi._f32_rows(q), cancel=cancel)
+            radius, self._radius = self._radius, None
+            try:
+                hits = self.by_vectors(q, cancel=cancel)
+            finally:
+                self._radius = radius
+            return self._cut(hits)
         if self._bitsets is not None:
             bits, n_bits, filter_of = self._id_bits(len(q))
             if self._exact:
@@ -695,6 +733,15 @@ class QueryBuilder:
 
     def by_items(self, items, cancel=None):
         """batched by_item; counts == capi.NNS_NONE where the reference returns None"""
+        if self._radius is not None:
+            if self._exact:
+                return self._within_exact(query_items=np.ascontiguousarray(items, np.uint32), cancel=cancel)
+            radius, self._radius = self._radius, None
+            try:
+                hits = self.by_items(items, cancel=cancel)
+            finally:
+                self._radius = radius
+            return self._cut(hits)
         if self._bitsets is not None:
             items = np.ascontiguousarray(items, np.uint32)
             bits, n_bits, filter_of = self._id_bits(len(items))

@@ -4670,6 +4670,324 @@ int hny_builder_exact_knn_bitsets_f32(hny_builder *b, const hny_query_opts *qo, 
 uint64_t hny_builder_exact_rows_read(const hny_builder *b) { return b ? b->exact_rows_read : 0; }
 
 // ---------------------------------------------------------------------------------------------
+// exact range search: every item of C within radius[i] of query i, and how many.  exact_impl's
+// dense scan with another consumer of the scores: blocks of at most HNY_EXACT_QBLOCK queries, slabs of
+// HNY_EXACT_SLAB slots, k_exact_scores as it is, then k_range_count (pass 1) and, once the host has made the offsets
+// from the counts, k_range_emit, the segmented sort and k_range_finish (pass 2, scores computed again: nothing is
+// kept between the passes).  Always the dense scan: a sparse C is not gathered, strict f32 builders are refused.
+// ---------------------------------------------------------------------------------------------
+#define HNY_RANGE_KEY_BYTES ((uint64_t)2 << 30) // keys of the queries in flight, 16 B per hit with the sort's second buffer
+static uint64_t range_key_budget() {
+  const char *e = getenv("HNY_RANGE_KEY_BYTES"); // test hook, read per call: several sub-blocks on a small index
+  const uint64_t v = e ? strtoull(e, nullptr, 10) : 0;
+  return v ? v : HNY_RANGE_KEY_BYTES;
+}
+
+// what hny_range_result points into
+struct RangeResult {
+  hny_range_result pub{};
+  uint64_t *offsets = nullptr;
+  uint32_t *ids = nullptr;
+  float *dists = nullptr;
+  uint8_t *is_none = nullptr;
+  ~RangeResult() {
+    free(offsets);
+    free(ids);
+    free(dists);
+    free(is_none);
+  }
+  bool alloc(uint64_t nq, uint64_t total) {
+    offsets = (uint64_t *)malloc((size_t)(nq + 1) * 8);
+    is_none = (uint8_t *)malloc((size_t)std::max<uint64_t>(nq, 1));
+    ids = (uint32_t *)malloc((size_t)std::max<uint64_t>(total, 1) * 4);
+    dists = (float *)malloc((size_t)std::max<uint64_t>(total, 1) * 4);
+    pub = {nq, offsets, ids, dists, is_none};
+    return offsets && is_none && ids && dists;
+  }
+};
+
+// one block of queries staged and ready for the slab loop
+struct RangeBlock {
+  uint64_t q0;
+  uint32_t cnt, n_mem;
+};
+
+static int range_impl(hny_builder *b, const hny_range_opts *ro, uint64_t nq, const void *qvectors, size_t qstride,
+                      const void *qheaders, const uint32_t *query_items, bool q_f32, uint64_t *out_counts,
+                      hny_range_result **out) {
+  // the opts' own conditions first, then the builder: each refusal names its cause, with or without a device
+  if (!ro || (!out_counts && !out)) return fail(HNY_ERR_INVALID_ARG, "bad argument");
+  if (ro->struct_size != sizeof(hny_range_opts))
+    return fail(HNY_ERR_INVALID_ARG, "hny_range_opts.struct_size %u: this library has %zu", ro->struct_size,
+                sizeof(hny_range_opts));
+  if (nq && !ro->radius) return fail(HNY_ERR_INVALID_ARG, "radius missing");
+  if (ro->n_candidates && !ro->candidates) return fail(HNY_ERR_INVALID_ARG, "candidates missing");
+  if (!b) return fail(HNY_ERR_INVALID_ARG, "no builder");
+  hny_query_opts qo{}; // the shared steps read the candidates and the cancel closure from here
+  qo.k = 1;
+  qo.has_candidates = ro->has_candidates;
+  qo.candidates = ro->candidates;
+  qo.n_candidates = ro->n_candidates;
+  qo.cancel = ro->cancel;
+  qo.cancel_ctx = ro->cancel_ctx;
+  qo.did_cancel = ro->did_cancel;
+  std::vector<uint32_t> none32; // QueryStage marks the by_item queries without a row here (HNY_NNS_NONE)
+  QuerySet qs = q_f32 ? QuerySet::of_f32(b, &qo, nq, (const float *)qvectors, qstride, nullptr, nullptr, nullptr)
+                      : QuerySet::of(b, &qo, nq, qvectors, qstride, qheaders, query_items, nullptr, nullptr, nullptr);
+  if (int rc = check_query_source(qs, "no queries")) return rc;
+  if (int rc = check_query_rows(qs)) return rc;
+  if (int rc = check_build_finished(b)) return rc;
+  if (int rc = check_query_stride(qs)) return rc;
+  if (b->g.x86_order && b->g.mclass != MC_BIN)
+    return fail(HNY_ERR_UNSUPPORTED, "exact range search on a strict-mode (x86_order) f32 builder: the dense scan does "
+                                     "not restate the reference's summation order");
+  try {
+    none32.assign((size_t)nq, 0u);
+  } catch (const std::bad_alloc &) {
+    return fail(HNY_ERR_OOM, "out of memory");
+  }
+  qs.out_counts = none32.data();
+  const uint32_t n = b->n;
+  SlotCandidates C;
+  const uint64_t n_c = qs.slot_mask(&qo, C.mask);
+  if (ro->did_cancel) *ro->did_cancel = 0;
+  std::vector<uint64_t> counts((size_t)nq, 0);
+  SearchCancel sc;
+  uint64_t total = 0;
+  std::unique_ptr<RangeResult> res;
+
+  // what both passes share
+  const uint32_t qt = hnyk_exact_qt(b->g.row_stride);
+  const uint32_t qblock = (uint32_t)std::min<uint64_t>(HNY_EXACT_QBLOCK, std::max<uint64_t>(nq, 1));
+  const uint32_t sstride = (std::min<uint32_t>(n, HNY_EXACT_SLAB) + 63u) & ~63u;
+  QueryStage st{b, qs};
+  DevBuf<u32> dmask, dseg, dcursor;
+  DevBuf<float> dscores, dradius;
+  DevBuf<u64> dcount;
+  std::vector<float> hradius(qblock);
+  std::vector<u64> hcount(qblock);
+  ExactArgs a{};
+  RangeArgs r{};
+  // the members [m0, m1) of the staged block as the scan's queries
+  auto aim = [&](uint32_t m0, uint32_t m1) {
+    a.q_slots = st.dqslots.p ? st.dqslots.p + m0 : nullptr;
+    a.q_rows = st.dq.p ? st.dq.p + (size_t)m0 * b->g.row_stride : nullptr;
+    a.q_norms = st.norms() ? st.norms() + m0 : nullptr;
+    a.nq = r.nq = m1 - m0;
+    r.radius = dradius.p + m0;
+  };
+  auto slab = [&](uint32_t s0) {
+    a.slab_base = r.slab_base = s0;
+    a.slab_n = r.slab_n = std::min<uint32_t>(HNY_EXACT_SLAB, n - s0);
+  };
+  // by_item: which queries have a row, decided on the host for the whole call
+  auto begin_block = [&](uint64_t q0, RangeBlock &blk) {
+    blk.q0 = q0;
+    blk.cnt = (uint32_t)std::min<uint64_t>(qblock, nq - q0);
+    blk.n_mem = st.members_compact(q0, blk.cnt);
+  };
+  auto stage_block = [&](const RangeBlock &blk) -> int {
+    if (int rc = st.stage(blk.q0, blk.cnt)) return rc;
+    for (uint32_t j = 0; j < blk.n_mem; j++) hradius[j] = ro->radius[blk.q0 + st.members[j]];
+    HIP_TRY(hipMemcpyAsync(dradius.p, hradius.data(), (size_t)blk.n_mem * 4, hipMemcpyHostToDevice, b->stream));
+    return HNY_OK;
+  };
+
+  if (n_c != 0 && nq != 0) {
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(sc.init(&qo));
+    HIP_TRY(dmask.alloc(C.mask.size()));
+    HIP_TRY(hipMemcpyAsync(dmask.p, C.mask.data(), C.mask.size() * 4, hipMemcpyHostToDevice, b->stream));
+    if (int rc = st.alloc(qblock)) return rc;
+    HIP_TRY(dscores.alloc((size_t)qblock * sstride));
+    HIP_TRY(dradius.alloc(qblock));
+    HIP_TRY(dcount.alloc(qblock));
+    a.q_stride = b->g.row_stride;
+    a.qt = qt;
+    a.scores = dscores.p;
+    a.score_stride = sstride;
+    a.mask = dmask.p;
+    r.scores = dscores.p;
+    r.score_stride = sstride;
+    r.mask = dmask.p;
+    r.count = dcount.p;
+    // pass 1: the counts
+    for (uint64_t q0 = 0; q0 < nq; q0 += qblock) {
+      RangeBlock blk;
+      begin_block(q0, blk);
+      if (blk.n_mem == 0 || sc.probe()) continue; // cancelled: nothing of this block is started, 0 hits each
+      if (int rc = stage_block(blk)) return rc;
+      aim(0, blk.n_mem);
+      HIP_TRY(hipMemsetAsync(dcount.p, 0, (size_t)blk.n_mem * 8, b->stream));
+      bool stopped = false;
+      for (uint32_t s0 = 0; s0 < n && !stopped; s0 += HNY_EXACT_SLAB) {
+        slab(s0);
+        if ((stopped = sc.probe())) break;
+        HIP_TRY(hnyk_exact_scores(b->g, a, b->shape, b->stream));
+        if ((stopped = sc.probe())) break;
+        HIP_TRY(hnyk_range_count(r, b->stream));
+      }
+      if (stopped) { // the block did not finish: 0 hits each
+        HIP_TRY(hipStreamSynchronize(b->stream));
+        continue;
+      }
+      HIP_TRY(hipMemcpyAsync(hcount.data(), dcount.p, (size_t)blk.n_mem * 8, hipMemcpyDeviceToHost, b->stream));
+      HIP_TRY(sc.wait(b));
+      for (uint32_t j = 0; j < blk.n_mem; j++) counts[q0 + st.members[j]] = hcount[j];
+    }
+  } else {
+    // nothing to search among: no hits, by_item None for every query (reader.rs:822-824) once it is known
+    for (uint64_t i = 0; i < nq; i++) none32[i] = qs.by_item ? HNY_NNS_NONE : 0u;
+  }
+  for (uint64_t i = 0; i < nq; i++) total += counts[i];
+
+  if (!out) { // _count stops here
+    for (uint64_t i = 0; i < nq; i++) out_counts[i] = none32[i] == HNY_NNS_NONE ? HNY_RANGE_NONE : counts[i];
+    return n_c != 0 && nq != 0 ? search_end(b, &qo, sc) : HNY_OK;
+  }
+  if (ro->max_total && total > ro->max_total)
+    return fail(HNY_ERR_UNSUPPORTED, "exact range search found %llu hits in all: max_total is %llu",
+                (unsigned long long)total, (unsigned long long)ro->max_total);
+  res.reset(new (std::nothrow) RangeResult());
+  if (!res || !res->alloc(nq, total))
+    return fail(HNY_ERR_OOM, "out of memory for %llu hits of %llu queries", (unsigned long long)total,
+                (unsigned long long)nq);
+  res->offsets[0] = 0;
+  for (uint64_t i = 0; i < nq; i++) {
+    res->offsets[i + 1] = res->offsets[i] + counts[i];
+    res->is_none[i] = none32[i] == HNY_NNS_NONE;
+  }
+
+  if (total != 0) {
+    // pass 2: the hits.  The members of a block go in runs ("sub-blocks") whose keys fit the budget, one member at
+    // least; a run is scanned on its own (k_exact_scores' bits of a (query, row) pair do not depend on the tile's other
+    // queries), emitted, sorted and fetched to its place: the hits of consecutive queries are consecutive in the result
+    const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(range_key_budget() / 16, 1), 0xFFFFFFFFull - n);
+    const bool identity = b->ids[n - 1] == n - 1; // QuerySet::live_slot's test: slot == id
+    if (!identity && !b->d_item_ids.p) {
+      HIP_TRY(b->d_item_ids.alloc(n));
+      HIP_TRY(hipMemcpy(b->d_item_ids.p, b->ids.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    }
+    DevBuf<u64> dkeys; // the keys and the sort's second buffer, which then takes the ids and the distances
+    DevBuf<unsigned char> dtemp;
+    size_t keys_cap = 0;
+    std::vector<u32> hseg(qblock + 1), hcursor(qblock);
+    HIP_TRY(dseg.alloc(qblock + 1));
+    HIP_TRY(dcursor.alloc(qblock));
+    r.seg = dseg.p;
+    r.cursor = dcursor.p;
+    uint64_t done_q = nq; // the first query whose hits were not fetched: it and all after it report 0 hits
+    bool stopped = false;
+    for (uint64_t q0 = 0; q0 < nq && !stopped; q0 += qblock) {
+      RangeBlock blk;
+      begin_block(q0, blk);
+      uint64_t block_hits = 0;
+      for (uint32_t j = 0; j < blk.n_mem; j++) block_hits += counts[q0 + st.members[j]];
+      if (block_hits == 0) continue;
+      if ((stopped = sc.probe())) {
+        done_q = q0;
+        break;
+      }
+      if (int rc = stage_block(blk)) return rc;
+      for (uint32_t m0 = 0; m0 < blk.n_mem && !stopped;) {
+        uint32_t m1 = m0;
+        uint64_t hits = 0;
+        while (m1 < blk.n_mem && (m1 == m0 || hits + counts[q0 + st.members[m1]] <= cap))
+          hits += counts[q0 + st.members[m1++]];
+        const uint64_t first_q = q0 + st.members[m0];
+        if (hits == 0) {
+          m0 = m1;
+          continue;
+        }
+        if (hits > keys_cap) {
+          HIP_TRY(hipStreamSynchronize(b->stream));
+          HIP_TRY(dkeys.alloc((size_t)hits * 2));
+          keys_cap = (size_t)hits;
+        }
+        const uint32_t nsub = m1 - m0, nh = (uint32_t)hits;
+        hseg[0] = 0;
+        for (uint32_t j = 0; j < nsub; j++) hseg[j + 1] = hseg[j] + (u32)counts[q0 + st.members[m0 + j]];
+        size_t temp_bytes = 0;
+        HIP_TRY(hnyk_range_sort(nullptr, temp_bytes, dkeys.p, dkeys.p + keys_cap, nh, nsub, dseg.p, nullptr, b->stream));
+        if (temp_bytes > dtemp.n) {
+          HIP_TRY(hipStreamSynchronize(b->stream));
+          HIP_TRY(dtemp.alloc(temp_bytes));
+        }
+        HIP_TRY(hipMemcpyAsync(dseg.p, hseg.data(), (size_t)(nsub + 1) * 4, hipMemcpyHostToDevice, b->stream));
+        HIP_TRY(hipMemsetAsync(dcursor.p, 0, (size_t)nsub * 4, b->stream));
+        aim(m0, m1);
+        r.keys = dkeys.p;
+        for (uint32_t s0 = 0; s0 < n && !stopped; s0 += HNY_EXACT_SLAB) {
+          slab(s0);
+          if ((stopped = sc.probe())) break;
+          HIP_TRY(hnyk_exact_scores(b->g, a, b->shape, b->stream));
+          if ((stopped = sc.probe())) break;
+          HIP_TRY(hnyk_range_emit(r, b->stream));
+        }
+        if (!stopped && !(stopped = sc.probe())) {
+          u64 *sorted = nullptr;
+          HIP_TRY(hnyk_range_sort(dtemp.p, temp_bytes, dkeys.p, dkeys.p + keys_cap, nh, nsub, dseg.p, &sorted, b->stream));
+          u64 *other = sorted == dkeys.p ? dkeys.p + keys_cap : dkeys.p;
+          u32 *dids = reinterpret_cast<u32 *>(other), *dbits = dids + nh;
+          HIP_TRY(hnyk_range_finish(sorted, nh, identity ? nullptr : b->d_item_ids.p, dids, dbits, b->stream));
+          const uint64_t off = res->offsets[first_q];
+          HIP_TRY(hipMemcpyAsync(res->ids + off, dids, (size_t)nh * 4, hipMemcpyDeviceToHost, b->stream));
+          HIP_TRY(hipMemcpyAsync(res->dists + off, dbits, (size_t)nh * 4, hipMemcpyDeviceToHost, b->stream));
+          HIP_TRY(hipMemcpyAsync(hcursor.data(), dcursor.p, (size_t)nsub * 4, hipMemcpyDeviceToHost, b->stream));
+          HIP_TRY(sc.wait(b));
+          for (uint32_t j = 0; j < nsub; j++) // the two passes voted alike
+            if (hcursor[j] != hseg[j + 1] - hseg[j])
+              return fail(HNY_ERR_DEVICE, "exact range search: query %llu emitted %u hits, counted %u",
+                          (unsigned long long)(q0 + st.members[m0 + j]), hcursor[j], hseg[j + 1] - hseg[j]);
+        }
+        if (stopped) { // this run and everything after it: 0 hits
+          HIP_TRY(hipStreamSynchronize(b->stream));
+          done_q = first_q;
+          break;
+        }
+        m0 = m1;
+      }
+    }
+    for (uint64_t i = done_q; i < nq; i++) res->offsets[i + 1] = res->offsets[done_q];
+  }
+  if (n_c != 0 && nq != 0)
+    if (int rc = search_end(b, &qo, sc)) return rc;
+  if (out_counts)
+    for (uint64_t i = 0; i < nq; i++) out_counts[i] = res->is_none[i] ? HNY_RANGE_NONE : res->offsets[i + 1] - res->offsets[i];
+  *out = &res.release()->pub;
+  return HNY_OK;
+}
+
+int hny_builder_exact_range_count(hny_builder *b, const hny_range_opts *ro, uint64_t nq, const void *qvectors,
+                                  size_t qstride, const void *qheaders, const uint32_t *query_items,
+                                  uint64_t *out_counts) {
+  if (!out_counts) return fail(HNY_ERR_INVALID_ARG, "bad argument");
+  return range_impl(b, ro, nq, qvectors, qstride, qheaders, query_items, false, out_counts, nullptr);
+}
+
+int hny_builder_exact_range(hny_builder *b, const hny_range_opts *ro, uint64_t nq, const void *qvectors, size_t qstride,
+                            const void *qheaders, const uint32_t *query_items, hny_range_result **out) {
+  if (!out) return fail(HNY_ERR_INVALID_ARG, "bad argument");
+  return range_impl(b, ro, nq, qvectors, qstride, qheaders, query_items, false, nullptr, out);
+}
+
+int hny_builder_exact_range_count_f32(hny_builder *b, const hny_range_opts *ro, uint64_t nq, const float *queries,
+                                      size_t qstride, uint64_t *out_counts) {
+  if (!out_counts || !queries) return fail(HNY_ERR_INVALID_ARG, !queries ? "no queries" : "bad argument");
+  return range_impl(b, ro, nq, queries, qstride, nullptr, nullptr, true, out_counts, nullptr);
+}
+
+int hny_builder_exact_range_f32(hny_builder *b, const hny_range_opts *ro, uint64_t nq, const float *queries,
+                                size_t qstride, hny_range_result **out) {
+  if (!out || !queries) return fail(HNY_ERR_INVALID_ARG, !queries ? "no queries" : "bad argument");
+  return range_impl(b, ro, nq, queries, qstride, nullptr, nullptr, true, nullptr, out);
+}
+
+void hny_range_result_free(hny_range_result *r) {
+  if (r) delete reinterpret_cast<RangeResult *>(r); // pub is RangeResult's first member
+}
+
+// ---------------------------------------------------------------------------------------------
 // on-disk records
 // ---------------------------------------------------------------------------------------------
 static void put_key(uint16_t index, uint8_t mode, uint32_t item, uint8_t layer, uint8_t k[8]) {

@@ -418,6 +418,28 @@ hipError_t hnyk_exact_scores(const GraphDev &g, const ExactArgs &a, LaunchShape 
 hipError_t hnyk_exact_topk(const GraphDev &g, const ExactArgs &a, hipStream_t st);
 // a.tile_mask for the slab a.slab_base / a.slab_n from the members' masks (a.filter_of must be set)
 hipError_t hnyk_exact_tile_masks(const ExactArgs &a, hipStream_t st);
+// exact range search (hny_builder_exact_range; hny_range.hip): the consumers of a slab of
+// k_exact_scores' scores that are not a top-k list.  One wave per query of the block
+struct RangeArgs {
+  const float *scores;         // ExactArgs::scores of the same block and slab
+  u32 score_stride;
+  u32 nq;                      // queries of the (sub-)block
+  u32 slab_base, slab_n;
+  const u32 *mask;             // live items (∩ candidates) as a bitset over slots
+  const float *radius;         // [nq]
+  u64 *count;                  // k_range_count: [nq] hits so far, zero before the first slab
+  u64 *keys;                   // k_range_emit: dist bits << 32 | slot of query q at keys[seg[q] + cursor[q] ..)
+  const u32 *seg;              // [nq + 1] where each query's keys start, from the counts
+  u32 *cursor;                 // [nq] keys written so far, zero before the first slab
+};
+hipError_t hnyk_range_count(const RangeArgs &a, hipStream_t st);
+hipError_t hnyk_range_emit(const RangeArgs &a, hipStream_t st);
+// the n keys of n_seg segments seg[i] .. seg[i + 1], each segment ascending; `keys` and `other` are both scratch,
+// *sorted is the one that holds the result.  temp == nullptr: temp_bytes is set and nothing runs
+hipError_t hnyk_range_sort(void *temp, size_t &temp_bytes, u64 *keys, u64 *other, u32 n, u32 n_seg, const u32 *seg,
+                           u64 **sorted, hipStream_t st);
+// keys -> ids[i] = item_ids[slot] (null: the slot itself), dist_bits[i] = the key's high word
+hipError_t hnyk_range_finish(const u64 *keys, u32 n, const u32 *item_ids, u32 *ids, u32 *dist_bits, hipStream_t st);
 hipError_t hnyk_emit(const GraphDev &g, const EmitArgs &a, hipStream_t st);
 hipError_t hnyk_segments(const u64 *keys, u32 n_ops, u32 *seg_start, u32 *n_seg, hipStream_t st);
 // APPLY_WAVE: every segment, one wave per target (one lane per list slot), prunes included

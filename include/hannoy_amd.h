@@ -495,6 +495,72 @@ int hny_builder_exact_knn_bitsets_f32(hny_builder *b, const hny_query_opts *opts
                                       uint64_t n_queries, const float *queries, size_t qstride,
                                       uint32_t *out_ids, float *out_dists, uint32_t *out_counts);
 
+/* ---- exact range search: every item within a radius of each query, and how many there are.  The question a score
+ * threshold, a near-duplicate check before an upsert or "how many items lie within r" asks; it has no k, and no k of
+ * the calls above answers it.
+ *
+ * Definition: let C be the live items, or candidates ∩ live items when has_candidates, and d(i, c) the distance
+ * hny_builder_exact_knn reports for query i and item c (the same bits: the same k_exact_scores).  The hits of query i
+ * are { c in C : d(i, c) <= radius[i] }, compared as f32: a NaN distance is never a hit, a NaN radius gives no hits,
+ * +inf gives every distance that is not a NaN.  They are ordered by the exact scan's key, (distance bits, item id)
+ * ascending.  Wherever a query has at most 4 095 hits its row is, byte for byte, the hits with distance <= radius of
+ * hny_builder_exact_knn(k = 4 095) over the same C, in that call's order.
+ *
+ * hny_builder_exact_range returns a CSR the library owns (hny_range_result_free): the hits of query i are
+ * ids / dists[offsets[i] .. offsets[i + 1]).  hny_builder_exact_range_count returns only the sizes: out_counts[i] ==
+ * offsets[i + 1] - offsets[i] of the full call, and nothing is emitted or sorted (one scan instead of two).
+ * query_items != NULL = by_item on the stored rows: the item itself stays in, as in hny_builder_exact_knn; where the
+ * reference returns None (an unknown or deleted item, or no live item / an empty C) is_none[i] = 1, the query has no
+ * hits and out_counts[i] = HNY_RANGE_NONE.  is_none is all zero by vector.  An empty C gives 0 hits.
+ *
+ * Decided before any device work, *out and out_counts untouched: NULL arguments (a NULL builder included), a wrong
+ * struct_size, radius == NULL with n_queries > 0, candidates == NULL with n_candidates > 0: HNY_ERR_INVALID_ARG;
+ * qstride below the codec's bytes: HNY_ERR_INVALID_DIM; strict mode (x86_order) with an f32 metric:
+ * HNY_ERR_UNSUPPORTED, since the dense scan does not restate the half-wave order (bit metrics in strict mode are served).
+ * Decided after the counting pass and before anything is emitted, *out untouched: more than max_total hits in all
+ * (max_total != 0): HNY_ERR_UNSUPPORTED, hny_last_error names the total found; an allocation that fails: HNY_ERR_OOM.
+ *
+ * Cancellation as in hny_builder_exact_knn: `cancel` is probed between the launches; the query blocks that have not
+ * finished report 0 hits, *did_cancel = 1 and the call returns HNY_OK.
+ *
+ * Two passes over the slabs of the dense scan: k_range_count, then, with the offsets known,
+ * k_range_emit, a segmented sort per query and k_range_finish.  The device holds 16 B per hit of at most 2 GB worth of
+ * queries at a time (one query always goes: at most n hits).  hny_range_opts carries its own struct_size and is not
+ * part of hny_abi_sizes. */
+#define HNY_RANGE_NONE UINT64_MAX
+typedef struct {
+  uint32_t struct_size;       /* sizeof(hny_range_opts) as the caller compiled it; anything else: HNY_ERR_INVALID_ARG */
+  int32_t has_candidates;     /* as in hny_query_opts: one .candidates() set for the whole call, it may be empty */
+  const uint32_t *candidates; /* item ids, any order, duplicates and unknown / deleted ids allowed */
+  uint64_t n_candidates;
+  const float *radius;        /* one per query */
+  uint64_t max_total;         /* hny_builder_exact_range[_f32] only: refuse more hits than this in all; 0 = no cap */
+  int (*cancel)(void *);      /* as in hny_query_opts */
+  void *cancel_ctx;
+  int32_t *did_cancel;
+} hny_range_opts;
+
+typedef struct {
+  uint64_t n_queries;
+  const uint64_t *offsets;    /* n_queries + 1 entries, offsets[0] == 0 */
+  const uint32_t *ids;        /* offsets[n_queries] item ids */
+  const float *dists;         /* and their distances */
+  const uint8_t *is_none;     /* n_queries entries: 1 where by_item has no answer (the reference's None) */
+} hny_range_result;
+
+int hny_builder_exact_range_count(hny_builder *b, const hny_range_opts *opts, uint64_t n_queries,
+                                  const void *qvectors, size_t qstride, const void *qheaders,
+                                  const uint32_t *query_items, uint64_t *out_counts);
+int hny_builder_exact_range(hny_builder *b, const hny_range_opts *opts, uint64_t n_queries,
+                            const void *qvectors, size_t qstride, const void *qheaders,
+                            const uint32_t *query_items, hny_range_result **out);
+/* by_vector with f32 queries, encoded on the device like hny_builder_exact_knn_f32's */
+int hny_builder_exact_range_count_f32(hny_builder *b, const hny_range_opts *opts, uint64_t n_queries,
+                                      const float *queries, size_t qstride, uint64_t *out_counts);
+int hny_builder_exact_range_f32(hny_builder *b, const hny_range_opts *opts, uint64_t n_queries,
+                                const float *queries, size_t qstride, hny_range_result **out);
+void hny_range_result_free(hny_range_result *r); /* NULL is fine */
+
 /* ---- resident updates: Writer::add_item / del_item followed by Writer::build (src/writer.rs:462-495, 521-603)
  * on an index whose builder is still alive.  A finished builder holds the codec rows, the norms and the finalised
  * lists of every live item in HBM; the successor takes them from there, device to device (k_move_rows /
