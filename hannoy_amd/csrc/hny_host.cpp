@@ -3542,16 +3542,6 @@ struct QueryStage {
     n_slots = cnt;
     return n_mem;
   }
-  // exact_impl's layout: slots[j] belongs to member j, and every member starts with 0 hits
-  uint32_t members_compact(uint64_t q0, uint32_t cnt) {
-    const uint32_t n_mem = members_of(q0, cnt);
-    for (uint32_t j = 0; j < n_mem; j++) {
-      q.out_counts[q0 + members[j]] = 0u;
-      slots[j] = slots[members[j]];
-    }
-    n_slots = n_mem;
-    return n_mem;
-  }
   // the chunk into the buffers the searchers read.  q_f32: Reader::nns().by_vector's &[f32] (reader.rs:132-148),
   // encoded on the device by the same kernel as the items (slot = index within the chunk); otherwise codec bytes
   // + headers
@@ -3616,6 +3606,72 @@ struct TopkOut {
       memcpy(&q.out_dists[qi * q.k + i], &db, 4);
     }
     q.out_counts[qi] = c;
+  }
+};
+
+// The dense exact scan: what exact_dense_run and the two passes of range_impl share.  The
+// caller walks its queries in blocks of a size it chose; per block it calls block() (which of them have a row),
+// stage() and aim() (which members the scan takes) and runs slabs(): per slab of HNY_EXACT_SLAB slots k_exact_scores
+// (every row read once per tile of qt queries), then the consumer of the slab's scores: k_exact_topk, k_range_count
+// or k_range_emit.  `cancel` is probed before every launch; what slabs() left unfinished reports 0 hits.
+struct DenseScan {
+  hny_builder *b;
+  const QuerySet &q;
+  RangeArgs *r; // a range consumer's, null for top-k.  Set here: scores, score_stride, mask, nq, slab_*, radius
+  QueryStage st;
+  DevBuf<float> dscores;
+  ExactArgs a{};
+  uint64_t q0 = 0; // the block: queries [q0, q0 + cnt) of the call, n_mem of them with a row
+  uint32_t cnt = 0, n_mem = 0;
+
+  DenseScan(hny_builder *b, const QuerySet &q, RangeArgs *r = nullptr) : b(b), q(q), r(r), st{b, q} {}
+  int alloc(uint32_t qblock, const u32 *mask) { // blocks of at most qblock queries; mask: C over slots, on the device
+    const uint32_t sstride = (std::min<uint32_t>(b->n, HNY_EXACT_SLAB) + 63u) & ~63u;
+    if (int rc = st.alloc(qblock)) return rc;
+    HIP_TRY(dscores.alloc((size_t)qblock * sstride));
+    a.q_stride = b->g.row_stride;
+    a.qt = hnyk_exact_qt(b->g.row_stride);
+    a.scores = dscores.p;
+    a.score_stride = sstride;
+    a.mask = mask;
+    if (r) r->scores = dscores.p, r->score_stride = sstride, r->mask = mask;
+    return HNY_OK;
+  }
+  // the block at q0: its members (the kernels index a block's queries by member), each at 0 hits
+  uint32_t block(uint64_t at, uint32_t qblock) {
+    q0 = at;
+    cnt = (uint32_t)std::min<uint64_t>(qblock, q.nq - q0);
+    st.n_slots = n_mem = st.members_of(q0, cnt);
+    for (uint32_t j = 0; j < n_mem; j++) q.out_counts[query_of(j)] = 0u, st.slots[j] = st.slots[st.members[j]];
+    return n_mem;
+  }
+  int stage() { return st.stage(q0, cnt); }
+  uint64_t query_of(uint32_t j) const { return q0 + st.members[j]; } // member j's place in the call
+  // the members [m0, m1) of the staged block as the scan's queries; radius: a range caller's, one per member
+  void aim(uint32_t m0, uint32_t m1, const float *radius = nullptr) {
+    a.q_slots = st.dqslots.p ? st.dqslots.p + m0 : nullptr;
+    a.q_rows = st.dq.p ? st.dq.p + (size_t)m0 * b->g.row_stride : nullptr;
+    a.q_norms = st.norms() ? st.norms() + m0 : nullptr;
+    a.nq = m1 - m0;
+    if (r) r->nq = a.nq, r->radius = radius + m0;
+  }
+  // Every slab for the queries aimed at: probe, before() if there is one (the filtered top-k's tile masks), the
+  // scores, probe, consume().  *stopped: the closure fired, the stream is idle, the consumer's buffers hold a part
+  using Launch = std::function<hipError_t()>;
+  int slabs(SearchCancel &sc, bool *stopped, const Launch &consume, const Launch &before = nullptr) {
+    *stopped = false;
+    for (uint32_t s0 = 0; s0 < b->n; s0 += HNY_EXACT_SLAB) {
+      a.slab_base = s0;
+      a.slab_n = std::min<uint32_t>(HNY_EXACT_SLAB, b->n - s0);
+      if (r) r->slab_base = a.slab_base, r->slab_n = a.slab_n;
+      if ((*stopped = sc.probe())) break;
+      if (before) HIP_TRY(before());
+      HIP_TRY(hnyk_exact_scores(b->g, a, b->shape, b->stream));
+      if ((*stopped = sc.probe())) break;
+      HIP_TRY(consume());
+    }
+    if (*stopped) HIP_TRY(hipStreamSynchronize(b->stream));
+    return HNY_OK;
   }
 };
 
@@ -4365,9 +4421,8 @@ int hny_builder_nns_bitsets_f32(hny_builder *b, const hny_query_opts *qo, const 
 
 // ---------------------------------------------------------------------------------------------
 // exact k-NN: Reader::brute_force_search (reader.rs:667-711) over the live items (∩ candidates) for a batch of
-// queries.  Dense path: per block of queries and slab of HNY_EXACT_SLAB slots, k_exact_scores
-// (every row read once per tile of queries) then k_exact_topk (the slab merged into the running lists).
-// Strict mode and sparse filters go to nns_impl's linear scan over the same set: same definition.
+// queries.  Dense path: DenseScan's loop with k_exact_topk as the consumer (the slab merged into the
+// running lists).  Strict mode and sparse filters go to nns_impl's linear scan over the same set: same definition.
 // ---------------------------------------------------------------------------------------------
 // a filter and a k per query for the dense scan (exact_filtered_impl); exact_impl has none
 struct ExactFilters {
@@ -4379,70 +4434,55 @@ struct ExactFilters {
   bool skip;            // false (HNY_EXACT_SKIP=0): an all-ones tile mask, every row is read
 };
 
-// The dense scan of exact_impl and exact_filtered_impl: the queries of `qs` in blocks of at most HNY_EXACT_QBLOCK, per
-// block and slab k_exact_scores then k_exact_topk, `cancel` probed before every launch; a block that does not
-// finish reports 0 hits.  dmask: the call-wide mask (the live items for the members without a filter); kk: the most
-// hits of a row.  With F the scan reads only what a tile wants; tiles are as homogeneous as the order of `qs`
-// makes them, so the caller hands the queries over in filter order, unfiltered ones last.
+// The dense scan of exact_impl and exact_filtered_impl: the queries of `qs` in blocks of at most HNY_EXACT_QBLOCK on
+// DenseScan's slab loop; a block that does not finish reports 0 hits.  dmask: the call-wide mask (the live items for
+// the members without a filter); kk: the most hits of a row.  With F the scan reads only what a tile wants; tiles are
+// as homogeneous as the order of `qs` makes them: the caller hands the queries over in filter order, unfiltered last.
 static int exact_dense_run(hny_builder *b, const QuerySet &qs, const u32 *dmask, uint32_t kk, const ExactFilters *F,
                            SearchCancel &sc) {
-  const uint32_t n = b->n, qt = hnyk_exact_qt(b->g.row_stride);
-  const uint64_t nq = qs.nq;
+  const uint32_t n = b->n;
   uint32_t rcap = 64;
   while (rcap < kk + 1) rcap *= 2;
-  const uint32_t qblock = search_chunk(b, nq, rcap, kk, HNY_EXACT_QBLOCK); // running lists within the 2 GB rule
-  const uint32_t sstride = (std::min<uint32_t>(n, HNY_EXACT_SLAB) + 63u) & ~63u;
-  QueryStage st{b, qs};
+  const uint32_t qblock = search_chunk(b, qs.nq, rcap, kk, HNY_EXACT_QBLOCK); // running lists within the 2 GB rule
+  DenseScan scan{b, qs};
   TopkOut top{b, qs, kk};
-  DevBuf<float> dscores;
   DevBuf<u64> dlists;
   DevBuf<u32> dln, dfof, dkof, dtile;
-  std::vector<u32> hfof, hkof;
-  if (int rc = st.alloc(qblock)) return rc;
-  HIP_TRY(dscores.alloc((size_t)qblock * sstride));
+  std::vector<u32> hfof(F ? qblock : 0), hkof(F ? qblock : 0);
+  if (int rc = scan.alloc(qblock, dmask)) return rc;
   HIP_TRY(dlists.alloc((size_t)qblock * rcap));
   if (int rc = top.alloc(qblock)) return rc;
   HIP_TRY(dln.alloc(qblock));
+  ExactArgs &a = scan.a;
+  const uint32_t qt = a.qt;
   const size_t tile_words = (size_t)((qblock + qt - 1) / qt) * (HNY_EXACT_SLAB / 32u);
   if (F) {
     HIP_TRY(dfof.alloc(qblock));
     HIP_TRY(dkof.alloc(qblock));
     HIP_TRY(dtile.alloc(tile_words));
-    hfof.resize(qblock);
-    hkof.resize(qblock);
+    a.filter_of = dfof.p;
+    a.masks = F->masks;
+    a.mask_stride = F->mask_stride;
+    a.k_of = dkof.p;
+    a.tile_mask = dtile.p;
   }
-  for (uint64_t q0 = 0; q0 < nq; q0 += qblock) {
-    const uint32_t cnt = (uint32_t)std::min<uint64_t>(qblock, nq - q0);
-    const uint32_t n_mem = st.members_compact(q0, cnt); // the kernels index the block's queries by member
-    if (n_mem == 0 || sc.probe()) continue;             // cancelled: nothing of this block is started, 0 hits each
-    if (int rc = st.stage(q0, cnt)) return rc;
+  a.lists = dlists.p;
+  a.list_n = dln.p;
+  a.k = kk;
+  a.rcap = rcap;
+  for (uint64_t q0 = 0; q0 < qs.nq; q0 += qblock) {
+    const uint32_t n_mem = scan.block(q0, qblock);
+    if (n_mem == 0 || sc.probe()) continue; // cancelled: nothing of this block is started, 0 hits each
+    if (int rc = scan.stage()) return rc;
+    scan.aim(0, n_mem);
     bool skip = false; // this block's tile masks are made from its members' masks
-    ExactArgs a{};
-    a.q_slots = st.dqslots.p;
-    a.q_rows = st.dq.p;
-    a.q_norms = st.norms();
-    a.q_stride = b->g.row_stride;
-    a.nq = n_mem;
-    a.qt = qt;
-    a.scores = dscores.p;
-    a.score_stride = sstride;
-    a.mask = dmask;
-    a.lists = dlists.p;
-    a.list_n = dln.p;
-    a.k = kk;
-    a.rcap = rcap;
     if (F) {
       for (uint32_t j = 0; j < n_mem; j++) {
-        hfof[j] = F->filter_of[q0 + st.members[j]];
-        hkof[j] = F->k_of[q0 + st.members[j]];
+        hfof[j] = F->filter_of[scan.query_of(j)];
+        hkof[j] = F->k_of[scan.query_of(j)];
       }
       HIP_TRY(hipMemcpyAsync(dfof.p, hfof.data(), (size_t)n_mem * 4, hipMemcpyHostToDevice, b->stream));
       HIP_TRY(hipMemcpyAsync(dkof.p, hkof.data(), (size_t)n_mem * 4, hipMemcpyHostToDevice, b->stream));
-      a.filter_of = dfof.p;
-      a.masks = F->masks;
-      a.mask_stride = F->mask_stride;
-      a.k_of = dkof.p;
-      a.tile_mask = dtile.p;
       // Skipping pays where tiles want few rows.  An upper bound on what the block's tiles want: per tile the counts
       // of its distinct filters (members come in filter order), at most n.  Where that bound is above half of
       // tiles x n, the masks are not made and every row is read: heterogeneous tiles of wide filters measured 2 - 5 %
@@ -4452,29 +4492,20 @@ static int exact_dense_run(hny_builder *b, const QuerySet &qs, const u32 *dmask,
       for (uint32_t t0 = 0; t0 < n_mem; t0 += qt) {
         uint64_t w = 0;
         for (uint32_t j = t0; j < std::min(n_mem, t0 + qt); j++)
-          if (j == t0 || hfof[j] != hfof[j - 1]) w += F->count_of[q0 + st.members[j]];
+          if (j == t0 || hfof[j] != hfof[j - 1]) w += F->count_of[scan.query_of(j)];
         wanted += std::min<uint64_t>(w, n);
       }
       skip = F->skip && wanted * 2 <= (uint64_t)n_tiles * n;
       if (!skip) HIP_TRY(hnyk_fill_u32(dtile.p, 0xFFFFFFFFu, tile_words, b->stream));
     }
     HIP_TRY(hipMemsetAsync(dln.p, 0, (size_t)n_mem * 4, b->stream));
-    bool stopped = false;
-    for (uint32_t s0 = 0; s0 < n && !stopped; s0 += HNY_EXACT_SLAB) {
-      a.slab_base = s0;
-      a.slab_n = std::min<uint32_t>(HNY_EXACT_SLAB, n - s0);
-      if ((stopped = sc.probe())) break;
-      if (skip) HIP_TRY(hnyk_exact_tile_masks(a, b->stream));
-      HIP_TRY(hnyk_exact_scores(b->g, a, b->shape, b->stream));
-      if ((stopped = sc.probe())) break;
-      HIP_TRY(hnyk_exact_topk(b->g, a, b->stream));
-    }
-    if (stopped) { // the block did not finish: 0 hits each
-      HIP_TRY(hipStreamSynchronize(b->stream));
-      continue;
-    }
+    const DenseScan::Launch topk = [&] { return hnyk_exact_topk(b->g, a, b->stream); };
+    const DenseScan::Launch tile_masks = [&] { return hnyk_exact_tile_masks(a, b->stream); };
+    bool stopped;
+    if (int rc = scan.slabs(sc, &stopped, topk, skip ? tile_masks : nullptr)) return rc;
+    if (stopped) continue; // the block did not finish: 0 hits each
     if (int rc = top.fetch(dlists.p, dln.p, rcap, n_mem, sc)) return rc;
-    for (uint32_t j = 0; j < n_mem; j++) top.emit(j, q0 + st.members[j]);
+    for (uint32_t j = 0; j < n_mem; j++) top.emit(j, scan.query_of(j));
   }
   return HNY_OK;
 }
@@ -4670,11 +4701,10 @@ int hny_builder_exact_knn_bitsets_f32(hny_builder *b, const hny_query_opts *qo, 
 uint64_t hny_builder_exact_rows_read(const hny_builder *b) { return b ? b->exact_rows_read : 0; }
 
 // ---------------------------------------------------------------------------------------------
-// exact range search: every item of C within radius[i] of query i, and how many.  exact_impl's
-// dense scan with another consumer of the scores: blocks of at most HNY_EXACT_QBLOCK queries, slabs of
-// HNY_EXACT_SLAB slots, k_exact_scores as it is, then k_range_count (pass 1) and, once the host has made the offsets
-// from the counts, k_range_emit, the segmented sort and k_range_finish (pass 2, scores computed again: nothing is
-// kept between the passes).  Always the dense scan: a sparse C is not gathered, strict f32 builders are refused.
+// exact range search: every item of C within radius[i] of query i, and how many.  DenseScan's loop
+// with two other consumers of the scores: k_range_count (pass 1) and, once the host has made the offsets from the
+// counts, k_range_emit, then the segmented sort and k_range_finish (pass 2, scores computed again: nothing is kept
+// between the passes).  Always the dense scan: a sparse C is not gathered, strict f32 builders are refused.
 // ---------------------------------------------------------------------------------------------
 #define HNY_RANGE_KEY_BYTES ((uint64_t)2 << 30) // keys of the queries in flight, 16 B per hit with the sort's second buffer
 static uint64_t range_key_budget() {
@@ -4706,34 +4736,40 @@ struct RangeResult {
   }
 };
 
-// one block of queries staged and ready for the slab loop
-struct RangeBlock {
-  uint64_t q0;
-  uint32_t cnt, n_mem;
+// What the passes of range_impl share and what pass 2 adds.  Of `r`, count, keys, seg and cursor are set here
+struct RangeScan {
+  const float *radius; // the caller's, one per query
+  RangeArgs r{};
+  DenseScan scan;
+  SearchCancel sc;
+  uint32_t qblock;
+  std::unique_ptr<uint32_t[]> none32; // for out_counts: QueryStage marks the by_item queries without a row here
+  std::vector<uint64_t> counts;       // the hits of every query: pass 1's, 0 from where pass 2 was cancelled
+  std::vector<float> hradius;
+  std::vector<u64> hcount;
+  std::vector<u32> hseg, hcursor;
+  DevBuf<u32> dmask, dseg, dcursor;
+  DevBuf<float> dradius;
+  DevBuf<u64> dcount, dkeys; // dkeys: a run's keys and the sort's second buffer, which then takes the ids and distances
+  DevBuf<unsigned char> dtemp;
+  uint64_t keys_cap = 0, cap = 0; // pass 2: the keys that half of dkeys holds, and the most of a run
+  RangeScan(hny_builder *b, const QuerySet &q, const float *radius)
+      : radius(radius), scan(b, q, &r),
+        qblock((uint32_t)std::min<uint64_t>(HNY_EXACT_QBLOCK, std::max<uint64_t>(q.nq, 1))),
+        none32(new (std::nothrow) uint32_t[(size_t)q.nq]()), counts((size_t)q.nq, 0), hradius(qblock), hcount(qblock),
+        hseg(qblock + 1), hcursor(qblock) {}
+  uint64_t hits_of(uint32_t j) const { return counts[scan.query_of(j)]; } // of member j of the block at hand
 };
 
-static int range_impl(hny_builder *b, const hny_range_opts *ro, uint64_t nq, const void *qvectors, size_t qstride,
-                      const void *qheaders, const uint32_t *query_items, bool q_f32, uint64_t *out_counts,
-                      hny_range_result **out) {
-  // the opts' own conditions first, then the builder: each refusal names its cause, with or without a device
-  if (!ro || (!out_counts && !out)) return fail(HNY_ERR_INVALID_ARG, "bad argument");
+// the opts' own conditions, then the builder, then the queries: each refusal names its cause, with or without a device
+static int range_check_args(const hny_builder *b, const hny_range_opts *ro, const QuerySet &qs, bool has_out) {
+  if (!ro || !has_out) return fail(HNY_ERR_INVALID_ARG, "bad argument");
   if (ro->struct_size != sizeof(hny_range_opts))
     return fail(HNY_ERR_INVALID_ARG, "hny_range_opts.struct_size %u: this library has %zu", ro->struct_size,
                 sizeof(hny_range_opts));
-  if (nq && !ro->radius) return fail(HNY_ERR_INVALID_ARG, "radius missing");
+  if (qs.nq && !ro->radius) return fail(HNY_ERR_INVALID_ARG, "radius missing");
   if (ro->n_candidates && !ro->candidates) return fail(HNY_ERR_INVALID_ARG, "candidates missing");
   if (!b) return fail(HNY_ERR_INVALID_ARG, "no builder");
-  hny_query_opts qo{}; // the shared steps read the candidates and the cancel closure from here
-  qo.k = 1;
-  qo.has_candidates = ro->has_candidates;
-  qo.candidates = ro->candidates;
-  qo.n_candidates = ro->n_candidates;
-  qo.cancel = ro->cancel;
-  qo.cancel_ctx = ro->cancel_ctx;
-  qo.did_cancel = ro->did_cancel;
-  std::vector<uint32_t> none32; // QueryStage marks the by_item queries without a row here (HNY_NNS_NONE)
-  QuerySet qs = q_f32 ? QuerySet::of_f32(b, &qo, nq, (const float *)qvectors, qstride, nullptr, nullptr, nullptr)
-                      : QuerySet::of(b, &qo, nq, qvectors, qstride, qheaders, query_items, nullptr, nullptr, nullptr);
   if (int rc = check_query_source(qs, "no queries")) return rc;
   if (int rc = check_query_rows(qs)) return rc;
   if (int rc = check_build_finished(b)) return rc;
@@ -4741,219 +4777,182 @@ static int range_impl(hny_builder *b, const hny_range_opts *ro, uint64_t nq, con
   if (b->g.x86_order && b->g.mclass != MC_BIN)
     return fail(HNY_ERR_UNSUPPORTED, "exact range search on a strict-mode (x86_order) f32 builder: the dense scan does "
                                      "not restate the reference's summation order");
-  try {
-    none32.assign((size_t)nq, 0u);
-  } catch (const std::bad_alloc &) {
-    return fail(HNY_ERR_OOM, "out of memory");
+  return HNY_OK;
+}
+static hny_query_opts range_query_opts(const hny_range_opts *ro) {
+  hny_query_opts qo = handed_opts(1, 0, nullptr, ro->did_cancel);
+  qo.has_candidates = ro->has_candidates;
+  qo.candidates = ro->candidates;
+  qo.n_candidates = ro->n_candidates;
+  qo.cancel = ro->cancel;
+  qo.cancel_ctx = ro->cancel_ctx;
+  return qo;
+}
+static int range_stage_block(RangeScan &R) {
+  if (int rc = R.scan.stage()) return rc;
+  for (uint32_t j = 0; j < R.scan.n_mem; j++) R.hradius[j] = R.radius[R.scan.query_of(j)];
+  hipStream_t st = R.scan.b->stream;
+  HIP_TRY(hipMemcpyAsync(R.dradius.p, R.hradius.data(), (size_t)R.scan.n_mem * 4, hipMemcpyHostToDevice, st));
+  return HNY_OK;
+}
+// pass 1: the device's side of what both passes share, then R.counts on DenseScan's slab loop with k_range_count
+static int range_count_pass(RangeScan &R, const std::vector<u32> &mask, const hny_query_opts *qo) {
+  hny_builder *b = R.scan.b;
+  HIP_TRY(hipSetDevice(b->device));
+  HIP_TRY(R.sc.init(qo));
+  HIP_TRY(R.dmask.alloc(mask.size()));
+  HIP_TRY(hipMemcpyAsync(R.dmask.p, mask.data(), mask.size() * 4, hipMemcpyHostToDevice, b->stream));
+  if (int rc = R.scan.alloc(R.qblock, R.dmask.p)) return rc;
+  HIP_TRY(R.dradius.alloc(R.qblock));
+  HIP_TRY(R.dcount.alloc(R.qblock));
+  R.r.count = R.dcount.p;
+  for (uint64_t q0 = 0; q0 < R.scan.q.nq; q0 += R.qblock) {
+    const uint32_t n_mem = R.scan.block(q0, R.qblock);
+    if (n_mem == 0 || R.sc.probe()) continue; // cancelled: nothing of this block is started, 0 hits each
+    if (int rc = range_stage_block(R)) return rc;
+    R.scan.aim(0, n_mem, R.dradius.p);
+    HIP_TRY(hipMemsetAsync(R.dcount.p, 0, (size_t)n_mem * 8, b->stream));
+    bool stopped;
+    if (int rc = R.scan.slabs(R.sc, &stopped, [&R, b] { return hnyk_range_count(R.r, b->stream); })) return rc;
+    if (stopped) continue; // the block did not finish: 0 hits each
+    HIP_TRY(hipMemcpyAsync(R.hcount.data(), R.dcount.p, (size_t)n_mem * 8, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(R.sc.wait(b));
+    for (uint32_t j = 0; j < n_mem; j++) R.counts[R.scan.query_of(j)] = R.hcount[j];
   }
-  qs.out_counts = none32.data();
-  const uint32_t n = b->n;
-  SlotCandidates C;
-  const uint64_t n_c = qs.slot_mask(&qo, C.mask);
-  if (ro->did_cancel) *ro->did_cancel = 0;
-  std::vector<uint64_t> counts((size_t)nq, 0);
-  SearchCancel sc;
+  return HNY_OK;
+}
+static void range_sizes_out(const RangeScan &R, uint64_t *out_counts) {
+  for (uint64_t i = 0; i < R.scan.q.nq; i++) out_counts[i] = R.none32[i] == HNY_NNS_NONE ? HNY_RANGE_NONE : R.counts[i];
+}
+// the result's layout from the counts: the max_total refusal, the arrays, the offsets and who is None
+static int range_layout(const RangeScan &R, uint64_t max_total, std::unique_ptr<RangeResult> &res) {
+  const uint64_t nq = R.scan.q.nq;
   uint64_t total = 0;
-  std::unique_ptr<RangeResult> res;
-
-  // what both passes share
-  const uint32_t qt = hnyk_exact_qt(b->g.row_stride);
-  const uint32_t qblock = (uint32_t)std::min<uint64_t>(HNY_EXACT_QBLOCK, std::max<uint64_t>(nq, 1));
-  const uint32_t sstride = (std::min<uint32_t>(n, HNY_EXACT_SLAB) + 63u) & ~63u;
-  QueryStage st{b, qs};
-  DevBuf<u32> dmask, dseg, dcursor;
-  DevBuf<float> dscores, dradius;
-  DevBuf<u64> dcount;
-  std::vector<float> hradius(qblock);
-  std::vector<u64> hcount(qblock);
-  ExactArgs a{};
-  RangeArgs r{};
-  // the members [m0, m1) of the staged block as the scan's queries
-  auto aim = [&](uint32_t m0, uint32_t m1) {
-    a.q_slots = st.dqslots.p ? st.dqslots.p + m0 : nullptr;
-    a.q_rows = st.dq.p ? st.dq.p + (size_t)m0 * b->g.row_stride : nullptr;
-    a.q_norms = st.norms() ? st.norms() + m0 : nullptr;
-    a.nq = r.nq = m1 - m0;
-    r.radius = dradius.p + m0;
-  };
-  auto slab = [&](uint32_t s0) {
-    a.slab_base = r.slab_base = s0;
-    a.slab_n = r.slab_n = std::min<uint32_t>(HNY_EXACT_SLAB, n - s0);
-  };
-  // by_item: which queries have a row, decided on the host for the whole call
-  auto begin_block = [&](uint64_t q0, RangeBlock &blk) {
-    blk.q0 = q0;
-    blk.cnt = (uint32_t)std::min<uint64_t>(qblock, nq - q0);
-    blk.n_mem = st.members_compact(q0, blk.cnt);
-  };
-  auto stage_block = [&](const RangeBlock &blk) -> int {
-    if (int rc = st.stage(blk.q0, blk.cnt)) return rc;
-    for (uint32_t j = 0; j < blk.n_mem; j++) hradius[j] = ro->radius[blk.q0 + st.members[j]];
-    HIP_TRY(hipMemcpyAsync(dradius.p, hradius.data(), (size_t)blk.n_mem * 4, hipMemcpyHostToDevice, b->stream));
-    return HNY_OK;
-  };
-
-  if (n_c != 0 && nq != 0) {
-    HIP_TRY(hipSetDevice(b->device));
-    HIP_TRY(sc.init(&qo));
-    HIP_TRY(dmask.alloc(C.mask.size()));
-    HIP_TRY(hipMemcpyAsync(dmask.p, C.mask.data(), C.mask.size() * 4, hipMemcpyHostToDevice, b->stream));
-    if (int rc = st.alloc(qblock)) return rc;
-    HIP_TRY(dscores.alloc((size_t)qblock * sstride));
-    HIP_TRY(dradius.alloc(qblock));
-    HIP_TRY(dcount.alloc(qblock));
-    a.q_stride = b->g.row_stride;
-    a.qt = qt;
-    a.scores = dscores.p;
-    a.score_stride = sstride;
-    a.mask = dmask.p;
-    r.scores = dscores.p;
-    r.score_stride = sstride;
-    r.mask = dmask.p;
-    r.count = dcount.p;
-    // pass 1: the counts
-    for (uint64_t q0 = 0; q0 < nq; q0 += qblock) {
-      RangeBlock blk;
-      begin_block(q0, blk);
-      if (blk.n_mem == 0 || sc.probe()) continue; // cancelled: nothing of this block is started, 0 hits each
-      if (int rc = stage_block(blk)) return rc;
-      aim(0, blk.n_mem);
-      HIP_TRY(hipMemsetAsync(dcount.p, 0, (size_t)blk.n_mem * 8, b->stream));
-      bool stopped = false;
-      for (uint32_t s0 = 0; s0 < n && !stopped; s0 += HNY_EXACT_SLAB) {
-        slab(s0);
-        if ((stopped = sc.probe())) break;
-        HIP_TRY(hnyk_exact_scores(b->g, a, b->shape, b->stream));
-        if ((stopped = sc.probe())) break;
-        HIP_TRY(hnyk_range_count(r, b->stream));
-      }
-      if (stopped) { // the block did not finish: 0 hits each
-        HIP_TRY(hipStreamSynchronize(b->stream));
-        continue;
-      }
-      HIP_TRY(hipMemcpyAsync(hcount.data(), dcount.p, (size_t)blk.n_mem * 8, hipMemcpyDeviceToHost, b->stream));
-      HIP_TRY(sc.wait(b));
-      for (uint32_t j = 0; j < blk.n_mem; j++) counts[q0 + st.members[j]] = hcount[j];
-    }
-  } else {
-    // nothing to search among: no hits, by_item None for every query (reader.rs:822-824) once it is known
-    for (uint64_t i = 0; i < nq; i++) none32[i] = qs.by_item ? HNY_NNS_NONE : 0u;
-  }
-  for (uint64_t i = 0; i < nq; i++) total += counts[i];
-
-  if (!out) { // _count stops here
-    for (uint64_t i = 0; i < nq; i++) out_counts[i] = none32[i] == HNY_NNS_NONE ? HNY_RANGE_NONE : counts[i];
-    return n_c != 0 && nq != 0 ? search_end(b, &qo, sc) : HNY_OK;
-  }
-  if (ro->max_total && total > ro->max_total)
+  for (uint64_t i = 0; i < nq; i++) total += R.counts[i];
+  if (max_total && total > max_total)
     return fail(HNY_ERR_UNSUPPORTED, "exact range search found %llu hits in all: max_total is %llu",
-                (unsigned long long)total, (unsigned long long)ro->max_total);
+                (unsigned long long)total, (unsigned long long)max_total);
   res.reset(new (std::nothrow) RangeResult());
   if (!res || !res->alloc(nq, total))
     return fail(HNY_ERR_OOM, "out of memory for %llu hits of %llu queries", (unsigned long long)total,
                 (unsigned long long)nq);
   res->offsets[0] = 0;
   for (uint64_t i = 0; i < nq; i++) {
-    res->offsets[i + 1] = res->offsets[i] + counts[i];
-    res->is_none[i] = none32[i] == HNY_NNS_NONE;
+    res->offsets[i + 1] = res->offsets[i] + R.counts[i];
+    res->is_none[i] = R.none32[i] == HNY_NNS_NONE;
   }
+  return HNY_OK;
+}
+// One run of pass 2, the members [m0, m1) of the staged block with `hits` keys: scanned on its own (k_exact_scores'
+// bits of a pair do not depend on the tile's other queries), emitted, sorted, fetched.  *stopped: nothing was fetched
+static int range_emit_run(RangeScan &R, RangeResult &res, uint32_t m0, uint32_t m1, uint64_t hits, bool *stopped) {
+  hny_builder *b = R.scan.b;
+  if (hits > R.keys_cap) {
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    HIP_TRY(R.dkeys.alloc((size_t)hits * 2));
+    R.keys_cap = hits;
+  }
+  const uint32_t nsub = m1 - m0, nh = (uint32_t)hits;
+  u64 *const keys = R.dkeys.p, *const keys2 = R.dkeys.p + R.keys_cap;
+  R.hseg[0] = 0;
+  for (uint32_t j = 0; j < nsub; j++) R.hseg[j + 1] = R.hseg[j] + (u32)R.hits_of(m0 + j);
+  size_t temp_bytes = 0;
+  HIP_TRY(hnyk_range_sort(nullptr, temp_bytes, keys, keys2, nh, nsub, R.dseg.p, nullptr, b->stream));
+  if (temp_bytes > R.dtemp.n) {
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    HIP_TRY(R.dtemp.alloc(temp_bytes));
+  }
+  HIP_TRY(hipMemcpyAsync(R.dseg.p, R.hseg.data(), (size_t)(nsub + 1) * 4, hipMemcpyHostToDevice, b->stream));
+  HIP_TRY(hipMemsetAsync(R.dcursor.p, 0, (size_t)nsub * 4, b->stream));
+  R.scan.aim(m0, m1, R.dradius.p);
+  R.r.keys = keys;
+  const int rc = R.scan.slabs(R.sc, stopped, [&R, b] { return hnyk_range_emit(R.r, b->stream); });
+  if (rc || *stopped) return rc;
+  if ((*stopped = R.sc.probe())) {
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return HNY_OK;
+  }
+  u64 *sorted = nullptr;
+  HIP_TRY(hnyk_range_sort(R.dtemp.p, temp_bytes, keys, keys2, nh, nsub, R.dseg.p, &sorted, b->stream));
+  u32 *dids = reinterpret_cast<u32 *>(sorted == keys ? keys2 : keys), *dbits = dids + nh;
+  HIP_TRY(hnyk_range_finish(sorted, nh, b->d_item_ids.p, dids, dbits, b->stream));
+  const uint64_t off = res.offsets[R.scan.query_of(m0)];
+  HIP_TRY(hipMemcpyAsync(res.ids + off, dids, (size_t)nh * 4, hipMemcpyDeviceToHost, b->stream));
+  HIP_TRY(hipMemcpyAsync(res.dists + off, dbits, (size_t)nh * 4, hipMemcpyDeviceToHost, b->stream));
+  HIP_TRY(hipMemcpyAsync(R.hcursor.data(), R.dcursor.p, (size_t)nsub * 4, hipMemcpyDeviceToHost, b->stream));
+  HIP_TRY(R.sc.wait(b));
+  for (uint32_t j = 0; j < nsub; j++) // the two passes voted alike
+    if (R.hcursor[j] != R.hseg[j + 1] - R.hseg[j])
+      return fail(HNY_ERR_DEVICE, "exact range search: query %llu emitted %u hits, counted %u",
+                  (unsigned long long)R.scan.query_of(m0 + j), R.hcursor[j], R.hseg[j + 1] - R.hseg[j]);
+  return HNY_OK;
+}
+// pass 2: the hits.  The members of a block go in runs ("sub-blocks") whose keys fit the budget, one member at least.
+// A block without hits is passed over before the probe; cancelled, the run at hand and all after it report 0 hits
+static int range_emit_pass(RangeScan &R, RangeResult &res) {
+  hny_builder *b = R.scan.b;
+  const uint32_t n = b->n;
+  const uint64_t nq = R.scan.q.nq;
+  R.cap = std::min<uint64_t>(std::max<uint64_t>(range_key_budget() / 16, 1), 0xFFFFFFFFull - n);
+  if (b->ids[n - 1] != n - 1 && !b->d_item_ids.p) { // slot != id (QuerySet::live_slot's test): k_range_finish's table
+    HIP_TRY(b->d_item_ids.alloc(n));
+    HIP_TRY(hipMemcpy(b->d_item_ids.p, b->ids.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+  }
+  HIP_TRY(R.dseg.alloc(R.qblock + 1));
+  HIP_TRY(R.dcursor.alloc(R.qblock));
+  R.r.seg = R.dseg.p, R.r.cursor = R.dcursor.p;
+  uint64_t done_q = nq; // the first query whose hits were not fetched
+  bool stopped = false;
+  for (uint64_t q0 = 0; q0 < nq && !stopped; q0 += R.qblock) {
+    const uint32_t n_mem = R.scan.block(q0, R.qblock);
+    uint64_t block_hits = 0;
+    for (uint32_t j = 0; j < n_mem; j++) block_hits += R.hits_of(j);
+    if (block_hits == 0) continue;
+    if ((stopped = R.sc.probe())) {
+      done_q = q0;
+      break;
+    }
+    if (int rc = range_stage_block(R)) return rc;
+    for (uint32_t m0 = 0, m1; m0 < n_mem && !stopped; m0 = m1) {
+      uint64_t run_hits = R.hits_of(m0);
+      for (m1 = m0 + 1; m1 < n_mem && run_hits + R.hits_of(m1) <= R.cap; m1++) run_hits += R.hits_of(m1);
+      if (run_hits == 0) continue;
+      if (int rc = range_emit_run(R, res, m0, m1, run_hits, &stopped)) return rc;
+      if (stopped) done_q = R.scan.query_of(m0);
+    }
+  }
+  for (uint64_t i = done_q; i < nq; i++) res.offsets[i + 1] = res.offsets[done_q], R.counts[i] = 0;
+  return HNY_OK;
+}
 
-  if (total != 0) {
-    // pass 2: the hits.  The members of a block go in runs ("sub-blocks") whose keys fit the budget, one member at
-    // least; a run is scanned on its own (k_exact_scores' bits of a (query, row) pair do not depend on the tile's other
-    // queries), emitted, sorted and fetched to its place: the hits of consecutive queries are consecutive in the result
-    const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(range_key_budget() / 16, 1), 0xFFFFFFFFull - n);
-    const bool identity = b->ids[n - 1] == n - 1; // QuerySet::live_slot's test: slot == id
-    if (!identity && !b->d_item_ids.p) {
-      HIP_TRY(b->d_item_ids.alloc(n));
-      HIP_TRY(hipMemcpy(b->d_item_ids.p, b->ids.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    }
-    DevBuf<u64> dkeys; // the keys and the sort's second buffer, which then takes the ids and the distances
-    DevBuf<unsigned char> dtemp;
-    size_t keys_cap = 0;
-    std::vector<u32> hseg(qblock + 1), hcursor(qblock);
-    HIP_TRY(dseg.alloc(qblock + 1));
-    HIP_TRY(dcursor.alloc(qblock));
-    r.seg = dseg.p;
-    r.cursor = dcursor.p;
-    uint64_t done_q = nq; // the first query whose hits were not fetched: it and all after it report 0 hits
-    bool stopped = false;
-    for (uint64_t q0 = 0; q0 < nq && !stopped; q0 += qblock) {
-      RangeBlock blk;
-      begin_block(q0, blk);
-      uint64_t block_hits = 0;
-      for (uint32_t j = 0; j < blk.n_mem; j++) block_hits += counts[q0 + st.members[j]];
-      if (block_hits == 0) continue;
-      if ((stopped = sc.probe())) {
-        done_q = q0;
-        break;
-      }
-      if (int rc = stage_block(blk)) return rc;
-      for (uint32_t m0 = 0; m0 < blk.n_mem && !stopped;) {
-        uint32_t m1 = m0;
-        uint64_t hits = 0;
-        while (m1 < blk.n_mem && (m1 == m0 || hits + counts[q0 + st.members[m1]] <= cap))
-          hits += counts[q0 + st.members[m1++]];
-        const uint64_t first_q = q0 + st.members[m0];
-        if (hits == 0) {
-          m0 = m1;
-          continue;
-        }
-        if (hits > keys_cap) {
-          HIP_TRY(hipStreamSynchronize(b->stream));
-          HIP_TRY(dkeys.alloc((size_t)hits * 2));
-          keys_cap = (size_t)hits;
-        }
-        const uint32_t nsub = m1 - m0, nh = (uint32_t)hits;
-        hseg[0] = 0;
-        for (uint32_t j = 0; j < nsub; j++) hseg[j + 1] = hseg[j] + (u32)counts[q0 + st.members[m0 + j]];
-        size_t temp_bytes = 0;
-        HIP_TRY(hnyk_range_sort(nullptr, temp_bytes, dkeys.p, dkeys.p + keys_cap, nh, nsub, dseg.p, nullptr, b->stream));
-        if (temp_bytes > dtemp.n) {
-          HIP_TRY(hipStreamSynchronize(b->stream));
-          HIP_TRY(dtemp.alloc(temp_bytes));
-        }
-        HIP_TRY(hipMemcpyAsync(dseg.p, hseg.data(), (size_t)(nsub + 1) * 4, hipMemcpyHostToDevice, b->stream));
-        HIP_TRY(hipMemsetAsync(dcursor.p, 0, (size_t)nsub * 4, b->stream));
-        aim(m0, m1);
-        r.keys = dkeys.p;
-        for (uint32_t s0 = 0; s0 < n && !stopped; s0 += HNY_EXACT_SLAB) {
-          slab(s0);
-          if ((stopped = sc.probe())) break;
-          HIP_TRY(hnyk_exact_scores(b->g, a, b->shape, b->stream));
-          if ((stopped = sc.probe())) break;
-          HIP_TRY(hnyk_range_emit(r, b->stream));
-        }
-        if (!stopped && !(stopped = sc.probe())) {
-          u64 *sorted = nullptr;
-          HIP_TRY(hnyk_range_sort(dtemp.p, temp_bytes, dkeys.p, dkeys.p + keys_cap, nh, nsub, dseg.p, &sorted, b->stream));
-          u64 *other = sorted == dkeys.p ? dkeys.p + keys_cap : dkeys.p;
-          u32 *dids = reinterpret_cast<u32 *>(other), *dbits = dids + nh;
-          HIP_TRY(hnyk_range_finish(sorted, nh, identity ? nullptr : b->d_item_ids.p, dids, dbits, b->stream));
-          const uint64_t off = res->offsets[first_q];
-          HIP_TRY(hipMemcpyAsync(res->ids + off, dids, (size_t)nh * 4, hipMemcpyDeviceToHost, b->stream));
-          HIP_TRY(hipMemcpyAsync(res->dists + off, dbits, (size_t)nh * 4, hipMemcpyDeviceToHost, b->stream));
-          HIP_TRY(hipMemcpyAsync(hcursor.data(), dcursor.p, (size_t)nsub * 4, hipMemcpyDeviceToHost, b->stream));
-          HIP_TRY(sc.wait(b));
-          for (uint32_t j = 0; j < nsub; j++) // the two passes voted alike
-            if (hcursor[j] != hseg[j + 1] - hseg[j])
-              return fail(HNY_ERR_DEVICE, "exact range search: query %llu emitted %u hits, counted %u",
-                          (unsigned long long)(q0 + st.members[m0 + j]), hcursor[j], hseg[j + 1] - hseg[j]);
-        }
-        if (stopped) { // this run and everything after it: 0 hits
-          HIP_TRY(hipStreamSynchronize(b->stream));
-          done_q = first_q;
-          break;
-        }
-        m0 = m1;
-      }
-    }
-    for (uint64_t i = done_q; i < nq; i++) res->offsets[i + 1] = res->offsets[done_q];
+static int range_impl(hny_builder *b, const hny_range_opts *ro, uint64_t nq, const void *qvectors, size_t qstride,
+                      const void *qheaders, const uint32_t *query_items, bool q_f32, uint64_t *out_counts,
+                      hny_range_result **out) {
+  uint32_t *const no = nullptr; // (the hits go to a RangeResult)
+  QuerySet qs = q_f32 ? QuerySet::of_f32(b, nullptr, nq, (const float *)qvectors, qstride, no, nullptr, no)
+                      : QuerySet::of(b, nullptr, nq, qvectors, qstride, qheaders, query_items, no, nullptr, no);
+  if (int rc = range_check_args(b, ro, qs, out_counts || out)) return rc;
+  const hny_query_opts qo = range_query_opts(ro);
+  RangeScan R{b, qs, ro->radius};
+  if (!R.none32) return fail(HNY_ERR_OOM, "out of memory");
+  qs.out_counts = R.none32.get();
+  SlotCandidates C;
+  const uint64_t n_c = qs.slot_mask(&qo, C.mask);
+  if (ro->did_cancel) *ro->did_cancel = 0;
+  const bool scanned = n_c != 0 && nq != 0; // otherwise nothing touches the device
+  // nothing to search among: no hits, by_item None for every query (reader.rs:822-824) once it is known
+  for (uint64_t i = 0; !scanned && i < nq; i++) R.none32[i] = qs.by_item ? HNY_NNS_NONE : 0u;
+  if (scanned)
+    if (int rc = range_count_pass(R, C.mask, &qo)) return rc;
+  if (!out) { // _count stops here
+    range_sizes_out(R, out_counts);
+    return scanned ? search_end(b, &qo, R.sc) : HNY_OK;
   }
-  if (n_c != 0 && nq != 0)
-    if (int rc = search_end(b, &qo, sc)) return rc;
-  if (out_counts)
-    for (uint64_t i = 0; i < nq; i++) out_counts[i] = res->is_none[i] ? HNY_RANGE_NONE : res->offsets[i + 1] - res->offsets[i];
+  std::unique_ptr<RangeResult> res;
+  if (int rc = range_layout(R, ro->max_total, res)) return rc;
+  if (int rc = res->offsets[nq] ? range_emit_pass(R, *res) : HNY_OK) return rc;
+  if (int rc = scanned ? search_end(b, &qo, R.sc) : HNY_OK) return rc;
+  if (out_counts) range_sizes_out(R, out_counts);
   *out = &res.release()->pub;
   return HNY_OK;
 }
