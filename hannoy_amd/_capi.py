@@ -75,7 +75,7 @@ class QueryFilters(C.Structure):
     def pack(cls, filters, filter_of):
         """`filters`: a list of id arrays; `filter_of`: one int per query, -1 or NNS_FILTER_NONE = none.
         Returns (struct, arrays the struct points into)"""
-        arrs = [np.ascontiguousarray(f, np.uint32).ravel() for f in filters]
+        arrs = [u32_ids(f).ravel() for f in filters]
         offsets = np.zeros(len(arrs) + 1, np.uint64)
         if arrs:
             offsets[1:] = np.cumsum([len(a) for a in arrs], dtype=np.uint64)
@@ -472,6 +472,26 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def u32_ids(a):
+    """item ids (hny_items.ids, candidates, query_items, to_insert, to_delete ...) as a contiguous uint32 array.  An
+    ItemId is a full u32: 0 .. 2^32 - 1 are all legal, 2^32 - 1 included.  Anything else is refused here — a negative
+    value, one >= 2^32, a fraction, NaN — because a numpy cast to uint32 would wrap it into some other item's id"""
+    if isinstance(a, np.ndarray) and a.dtype == np.uint32:
+        return np.ascontiguousarray(a)
+    arr = np.asarray(a if isinstance(a, np.ndarray) else list(a))
+    if arr.size == 0:
+        return np.zeros(arr.shape, np.uint32)
+    if arr.dtype.kind == "f":
+        if not np.isfinite(arr).all() or (arr != np.floor(arr)).any():
+            raise ValueError("item ids must be integers")
+    elif arr.dtype.kind not in "iu":
+        raise TypeError(f"item ids must be integers, not {arr.dtype}")
+    if arr.min() < 0 or arr.max() > 0xFFFFFFFF:
+        bad = arr[(arr < 0) | (arr > 0xFFFFFFFF)].ravel()[0]
+        raise OverflowError(f"item id {bad} is outside 0 .. 2^32 - 1")
+    return np.ascontiguousarray(arr, np.uint32)
+
+
 def set_graph_cache(max_bytes):
     """hny_set_graph_cache: opt-in recycling of released export arrays (0 = off, the default)"""
     L = load_library()
@@ -572,7 +592,7 @@ class ItemSet:
 
     def __init__(self, metric, dim, ids, codes, headers, levels=None):
         self.metric, self.dim = int(metric), int(dim)
-        self.ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        self.ids = u32_ids(ids)
         self.codes = np.ascontiguousarray(codes, dtype=np.uint8)
         self.headers = np.ascontiguousarray(headers, dtype=np.uint8)
         self.levels = None if levels is None else np.ascontiguousarray(levels, dtype=np.uint8)
@@ -623,7 +643,7 @@ def _query_opts(k, ef_search=0, linear_below=0, linear_below_ratio=0.0, candidat
         qo.cancel, qo.did_cancel = fn, C.pointer(flag)
         keep.append(fn)
     if candidates is not None:
-        cand = np.ascontiguousarray(candidates, np.uint32)
+        cand = u32_ids(candidates)
         qo.has_candidates, qo.candidates, qo.n_candidates = 1, cand.ctypes.data, len(cand)
         keep.append(cand)
     return qo, keep, flag
@@ -633,7 +653,7 @@ def _query_source(query_items=None, qf32=None, qcodes=None, qheaders=None):
     """The queries of one search call, by item, as f32 rows (see _f32_rows) or as codes + headers.
     Returns ((nq, qvectors, qstride, qheaders, query_items) as the entry points take them, the arrays behind them)"""
     if query_items is not None:
-        items = np.ascontiguousarray(query_items, np.uint32)
+        items = u32_ids(query_items)
         return (len(items), None, 0, None, _p(items)), (items,)
     if qf32 is not None:
         nq = qf32.shape[0]  # (numpy gives a one-row view whatever stride it likes)
@@ -659,7 +679,7 @@ def _range_opts(radius, nq, candidates=None, cancel=None, max_total=0):
         ro.cancel, ro.did_cancel = fn, C.pointer(flag)
         keep.append(fn)
     if candidates is not None:
-        cand = np.ascontiguousarray(candidates, np.uint32)
+        cand = u32_ids(candidates)
         ro.has_candidates, ro.candidates, ro.n_candidates = 1, cand.ctypes.data, len(cand)
         keep.append(cand)
     return ro, keep, flag
@@ -681,7 +701,7 @@ class F32ItemSet:
         self.vecs = _f32_rows(vecs)
         self.metric, self.dim = int(metric), int(self.vecs.shape[1])
         self.n = len(self.vecs)
-        self.ids = np.ascontiguousarray(np.arange(self.n) if ids is None else ids, dtype=np.uint32)
+        self.ids = u32_ids(np.arange(self.n) if ids is None else ids)
         self.levels = None if levels is None else np.ascontiguousarray(levels, dtype=np.uint8)
         self._encoded = None
 
@@ -871,7 +891,7 @@ class GraphDelta:
         g = GraphStruct()
         g.n_records, g.rec_item, g.rec_layer, g.rec_offset = d.n_records, d.rec_item, d.rec_layer, d.rec_offset
         g.neighbours, g.entry_points, g.n_entry_points, g.max_level = d.neighbours, d.entry_points, d.n_entry_points, d.max_level
-        ids = np.ascontiguousarray(item_ids, np.uint32)
+        ids = u32_ids(item_ids)
         it = Items(len(ids), _p(ids).value, None, 0, None, 0, None)
         out = []
 
@@ -992,8 +1012,8 @@ def build_incremental(items, prev, to_insert, to_delete, **kw):
     nbrs/entry_points/max_level)."""
     o = make_opts(items.metric, items.dim, **kw)
     it = items.struct()
-    ins = np.ascontiguousarray(to_insert, np.uint32)
-    dl = np.ascontiguousarray(to_delete, np.uint32)
+    ins = u32_ids(to_insert)
+    dl = u32_ids(to_delete)
     keep = [np.ascontiguousarray(prev.rec_item, np.uint32), np.ascontiguousarray(prev.rec_layer, np.uint8),
             np.ascontiguousarray(prev.offsets, np.uint64),
             np.ascontiguousarray(prev.nbrs if len(prev.nbrs) else np.zeros(1), np.uint32),
@@ -1091,8 +1111,8 @@ class Builder:
             if f32:
                 raise HannoyError(ERR_UNSUPPORTED, "a stepwise incremental builder takes codec bytes: use build_incremental() "
                                                    "for f32 items")
-            ins = np.ascontiguousarray(to_insert, np.uint32)
-            dl = np.ascontiguousarray(to_delete, np.uint32)
+            ins = u32_ids(to_insert)
+            dl = u32_ids(to_delete)
             pg, _keep = _prev_struct(prev)
             _check(load_library().hny_builder_create_incremental(
                 C.byref(self.opts), C.byref(it), _p(ins), len(ins), _p(dl), len(dl), C.byref(pg),
@@ -1184,7 +1204,7 @@ class Builder:
     # -- resident updates (hny_builder_create_update / hny_builder_update) --------------
     def _update_struct(self, upsert_ids, vectors, codes, headers, delete_ids, levels, seed):
         u = Update()
-        keep = [np.ascontiguousarray(upsert_ids, np.uint32), np.ascontiguousarray(delete_ids, np.uint32)]
+        keep = [u32_ids(upsert_ids), u32_ids(delete_ids)]
         u.n_upsert, u.upsert_ids = len(keep[0]), _p(keep[0]).value
         u.n_delete, u.delete_ids = len(keep[1]), _p(keep[1]).value
         u.seed = int(seed)

@@ -183,7 +183,7 @@ class Database:
             v = self.kv[key(index, MODE_ITEM, int(i))]
             hdrs[r] = np.frombuffer(v, np.uint8, hb, 1)
             codes[r] = np.frombuffer(v, np.uint8, vb, 1 + hb)
-        return capi.ItemSet(metric, dim, np.asarray(ids, np.uint32), codes, hdrs)
+        return capi.ItemSet(metric, dim, ids, codes, hdrs)
 
 
 class Writer:
@@ -602,7 +602,7 @@ class QueryBuilder:
         return self
 
     def candidates(self, ids):
-        self._candidates = np.ascontiguousarray(list(ids) if not isinstance(ids, np.ndarray) else ids, np.uint32)
+        self._candidates = capi.u32_ids(ids)
         return self
 
     def candidates_per_query(self, filters):
@@ -648,7 +648,7 @@ class QueryBuilder:
                 continue
             if id(c) not in index:
                 index[id(c)] = len(filters)
-                filters.append(np.ascontiguousarray(list(c) if not isinstance(c, np.ndarray) else c, np.uint32))
+                filters.append(capi.u32_ids(c))
             filter_of[i] = index[id(c)]
         return filters, filter_of
 
@@ -735,7 +735,7 @@ class QueryBuilder:
         """batched by_item; counts == capi.NNS_NONE where the reference returns None"""
         if self._radius is not None:
             if self._exact:
-                return self._within_exact(query_items=np.ascontiguousarray(items, np.uint32), cancel=cancel)
+                return self._within_exact(query_items=capi.u32_ids(items), cancel=cancel)
             radius, self._radius = self._radius, None
             try:
                 hits = self.by_items(items, cancel=cancel)
@@ -743,7 +743,7 @@ class QueryBuilder:
                 self._radius = radius
             return self._cut(hits)
         if self._bitsets is not None:
-            items = np.ascontiguousarray(items, np.uint32)
+            items = capi.u32_ids(items)
             bits, n_bits, filter_of = self._id_bits(len(items))
             if self._exact:
                 return self.reader._b.exact_knn_bitsets(bits, n_bits, filter_of, query_items=items, k=self.count,
@@ -751,7 +751,7 @@ class QueryBuilder:
             return self.reader._b.nns_bitsets(bits, n_bits, filter_of, query_items=items, cancel=cancel,
                                               **self._kw_filtered())
         if self._per_query is not None:
-            items = np.ascontiguousarray(items, np.uint32)
+            items = capi.u32_ids(items)
             filters, filter_of = self._filters(len(items))
             if self._exact:
                 return self.reader._b.exact_knn_filtered(filters, filter_of, query_items=items, k=self.count,
@@ -759,9 +759,9 @@ class QueryBuilder:
             return self.reader._b.nns_filtered(filters, filter_of, query_items=items, cancel=cancel,
                                                **self._kw_filtered())
         if self._exact:
-            return self.reader._b.exact_knn(query_items=np.ascontiguousarray(items, np.uint32), k=self.count,
+            return self.reader._b.exact_knn(query_items=capi.u32_ids(items), k=self.count,
                                             candidates=self._candidates, cancel=cancel)
-        return self.reader._b.nns(query_items=np.ascontiguousarray(items, np.uint32), cancel=cancel, **self._kw())
+        return self.reader._b.nns(query_items=capi.u32_ids(items), cancel=cancel, **self._kw())
 
     def by_vector(self, vector):
         """reader.rs:132-148"""

@@ -119,7 +119,10 @@ enum {
 /* replaces: what FrozenReader hands to the builder (src/parallel.rs:33-45) */
 typedef struct {
   uint64_t n;
-  const uint32_t *ids;       /* strictly ascending (RoaringBitmap order, hnsw.rs:142-144) */
+  const uint32_t *ids;       /* strictly ascending (RoaringBitmap order, hnsw.rs:142-144).  Every u32 is a legal id,
+                              * 0xFFFFFFFF included: it shares its value with HNY_NNS_NONE and HNY_FILTER_NONE,
+                              * which live in out_counts and filter_of, never in an id column.  A query without an
+                              * answer is told by its count; ids are read only up to the count */
   const void *vectors;       /* codec bytes exactly as stored after the header (node.rs:136-140) */
   size_t stride;             /* bytes between vectors; >= codec size */
   const void *headers;       /* D::Header bytes: f32 norm | f32 bias | u64 idx (hamming.rs:21-25) */
