@@ -467,6 +467,21 @@ struct hny_builder {
   }
 };
 enum { EV_WALK = 0, EV_PRUNE = 1, EV_SORT = 2, EV_APPLY = 3, EV_KINDS = 4 };
+// The builder's work counters (hny_builder::d_nseg), one buffer: the apply's two counts, 16 work queues (the descent +
+// one per layer of a batch; searches take the first few) and the same 16 as 8 per-XCD counters each (WalkArgs.xcd_tile)
+struct WorkCounters {
+  u32 *p;
+  enum { HEAD = 4, QUEUES = 16, XCDS = 8, WORDS = HEAD + QUEUES + XCDS * QUEUES };
+  static constexpr size_t COUNTS_BYTES = 2 * 4;                          // n_seg and n_deferred
+  static constexpr size_t ALL_QUEUES_BYTES = (QUEUES + XCDS * QUEUES) * 4; // every queue, plain and per XCD
+  static constexpr size_t SEARCH_QUEUES_BYTES = QUEUES / 2 * 4;           // the first half: what a search call clears
+  static constexpr size_t XCD_QUEUE_BYTES = XCDS * 4;
+  u32 *n_seg() const { return p; }          // segments of the sorted link ops (hnyk_segments)
+  u32 *n_deferred() const { return p + 1; } // segments whose list may overflow (k_apply_append)
+  u32 *queue(uint32_t i) const { return p + HEAD + i; }
+  u32 *xcd_queue(uint32_t i) const { return p + HEAD + QUEUES + XCDS * i; }
+};
+
 // LDS visited table of a walk wave: what is left of a 10 KB share (16 waves per CU in 160 KB) after
 // the beam, in whole 64-entry rows
 static uint32_t eps_cap_of(const hny_builder *b) {
@@ -1659,7 +1674,7 @@ static int alloc_device(hny_builder *b, const CreatePlan &P) {
   b->d_vals_b.p = b->d_ops.p + 3 * b->max_ops;
   b->d_keys_a.n = b->d_keys_b.n = b->d_vals_a.n = b->d_vals_b.n = b->max_ops;
   HIP_TRY(b->d_seg_start.alloc(b->max_ops));
-  HIP_TRY(b->d_nseg.alloc(4 + 16 + 8 * 16)); // + 8 per-XCD counters for each of the 16 work queues
+  HIP_TRY(b->d_nseg.alloc(WorkCounters::WORDS));
   HIP_TRY(b->d_lkey_a.alloc(cand_rows));
   HIP_TRY(b->d_lkey_b.alloc(cand_rows));
   HIP_TRY(b->d_perm_a.alloc(cand_rows));
@@ -2118,9 +2133,8 @@ int hny_builder_search(hny_builder *b, uint32_t lo, uint32_t hi, void *sel_dev) 
   auto launch_prune = [&](const PruneArgs &p, hipStream_t st) -> hipError_t {
     return hnyk_prune(b->g, p, b->shape, hnyk_prune_form(b->g, p, b->shape, b->knobs, b->walk_slots), b->stage, st);
   };
-  u32 *queues = b->d_nseg.p + 4; // 16 work counters: the descent + one per layer of the batch
-  u32 *xqueues = queues + 16;    // the same 16, as 8 per-XCD counters each (WalkArgs.xcd_tile)
-  HIP_TRY(hipMemsetAsync(queues, 0, (16 + 8 * 16) * 4, b->stream));
+  const WorkCounters wc{b->d_nseg.p}; // queue 0: the descent, then one per layer of the batch
+  HIP_TRY(hipMemsetAsync(wc.queue(0), 0, WorkCounters::ALL_QUEUES_BYTES, b->stream));
   HIP_TRY(hipMemsetAsync(b->d_pool_ctr.p, 0, b->d_pool_ctr.n * 4, b->stream));
   b->pool_ctr_used = 0;
   // one walk launch + its safety net: the members whose tie pool overflowed (none, normally) are listed on
@@ -2165,19 +2179,19 @@ int hny_builder_search(hny_builder *b, uint32_t lo, uint32_t hi, void *sel_dev) 
   const uint32_t cnt = hi - lo;
   if (b->locality && b->max_level > L && cnt >= 2048) {
     // batch in locality order (region_descent): the beam searches and prunes of every layer take the members in it
-    WalkArgs top = walk_args(L, lo, hi, queues + (L + 1));
+    WalkArgs top = walk_args(L, lo, hi, wc.queue(L + 1));
     prof_begin(b, EV_WALK);
     b->n_walk_dispatch++;
-    HIP_TRY(launch_walk(region_descent(b, walk_args(L, lo, hi, queues + 0)), b->stream));
+    HIP_TRY(launch_walk(region_descent(b, walk_args(L, lo, hi, wc.queue(0))), b->stream));
     if (int rc = region_order(b, lo, cnt, top)) return rc;
     const u32 xcd_tile = xcd_tile_of(b, cnt);
     for (int32_t l = (int32_t)L; l >= 0; l--) { // hnsw.rs:312-325
-      WalkArgs w = l == (int32_t)L ? top : walk_args(l, lo, hi, queues + (l + 1));
+      WalkArgs w = l == (int32_t)L ? top : walk_args(l, lo, hi, wc.queue((uint32_t)l + 1));
       w.perm = top.perm;
       if (l != (int32_t)L) prof_begin(b, EV_WALK);
       if (xcd_tile) {
         w.xcd_tile = xcd_tile;
-        w.queue = xqueues + 8 * (l + 1);
+        w.queue = wc.xcd_queue((uint32_t)l + 1);
       }
       b->n_walk_dispatch++;
       HIP_TRY(launch_walk(w, b->stream));
@@ -2191,7 +2205,7 @@ int hny_builder_search(hny_builder *b, uint32_t lo, uint32_t hi, void *sel_dev) 
     return HNY_OK;
   }
   for (int32_t l = (int32_t)L; l >= 0; l--) { // hnsw.rs:312-325
-    WalkArgs w = walk_args(l, lo, hi, queues + l);
+    WalkArgs w = walk_args(l, lo, hi, wc.queue((uint32_t)l));
     prof_begin(b, EV_WALK);
     b->n_walk_dispatch++;
     HIP_TRY(launch_walk(w, b->stream));
@@ -2226,17 +2240,18 @@ static int apply_front(hny_builder *b, const void *sel_dev, ApplyArgs &a) {
   // rocPRIM switches algorithms with size and bit range; the full 64-bit key is sorted)
   HIP_TRY(hnyk_sort_pairs(b->d_sort_tmp.p, tmp, b->d_keys_a.p, b->d_keys_b.p, b->d_vals_a.p,
                           b->d_vals_b.p, n_ops, 0, 64, b->stream));
-  HIP_TRY(hipMemsetAsync(b->d_nseg.p, 0, 8, b->stream));
-  HIP_TRY(hnyk_segments(b->d_keys_b.p, n_ops, b->d_seg_start.p, b->d_nseg.p, b->stream));
+  const WorkCounters wc{b->d_nseg.p};
+  HIP_TRY(hipMemsetAsync(wc.n_seg(), 0, WorkCounters::COUNTS_BYTES, b->stream));
+  HIP_TRY(hnyk_segments(b->d_keys_b.p, n_ops, b->d_seg_start.p, wc.n_seg(), b->stream));
   prof_end(b);
   a = ApplyArgs{};
   a.keys = b->d_keys_b.p;
   a.vals = b->d_vals_b.p;
   a.n_ops = n_ops;
   a.seg_start = b->d_seg_start.p;
-  a.n_seg = b->d_nseg.p;
+  a.n_seg = wc.n_seg();
   a.deferred = b->apply_form.kind == APPLY_WAVE ? nullptr : b->d_deferred.p;
-  a.n_deferred = b->d_nseg.p + 1;
+  a.n_deferred = wc.n_deferred();
   prof_begin(b, EV_APPLY);
   if (a.deferred) {
     HIP_TRY(hnyk_apply_append(b->g, a, b->stream)); // appends: one thread per target; overflowing lists deferred
@@ -2282,7 +2297,7 @@ int hny_builder_apply_begin(hny_builder *b, const void *sel_dev, uint32_t *n_def
   if (int rc = apply_front(b, sel_dev, a)) return rc;
   u32 nd = 0;
   if (b->apply_form.kind != APPLY_WAVE) {
-    HIP_TRY(hipMemcpyAsync(&nd, b->d_nseg.p + 1, 4, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemcpyAsync(&nd, WorkCounters{b->d_nseg.p}.n_deferred(), 4, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     if (nd > 1) { // canonical order: k_apply_append appended in atomic order, which differs between replicas
       size_t tmp = b->sort_tmp_bytes;
@@ -2306,9 +2321,9 @@ int hny_builder_apply_deferred(hny_builder *b, uint32_t rank, uint32_t world, vo
   a.vals = b->d_vals_b.p;
   a.n_ops = b->cur_n_ops;
   a.seg_start = b->d_seg_start.p;
-  a.n_seg = b->d_nseg.p;
+  a.n_seg = WorkCounters{b->d_nseg.p}.n_seg();
   a.deferred = b->d_deferred.p;
-  a.n_deferred = b->d_nseg.p + 1;
+  a.n_deferred = WorkCounters{b->d_nseg.p}.n_deferred();
   a.shard_rank = rank;
   a.shard_world = world;
   a.exch_stride = hny_builder_exch_stride_u64(b);
@@ -2866,6 +2881,35 @@ extern "C" int hny_internal_launch_forms(const int32_t in[13], int32_t out[12]) 
   const int32_t r[12] = {wf.sp, wf.big_eps, wf.reader, wf.rc, wf.waves_per_simd, pf.kind, pf.sp, (int32_t)pf.grid_cap,
                          af.kind, af.sp, (int32_t)af.grid_cap, (int32_t)b.walk_slots};
   memcpy(out, r, sizeof r);
+  return HNY_OK;
+}
+// The dynamic LDS of one kernel family (LdsFamily, hny_internal.h), from its layout function on a null cursor (no
+// device); p = the function's sizes in the order of its parameters.  spans = (offset, bytes) of every array in the order
+// it is taken, *n = room for that many pairs on entry, their number on return (no layout has more than 16 arrays);
+// out2 = the launch's bytes, and whether a take<T> missed alignof(T) (rows: 16)
+extern "C" int hny_internal_lds_layout(int family, const uint32_t p[4], uint64_t *spans, int32_t *n, uint64_t out2[2]) {
+  if (!p || !spans || !n || !out2) return fail(HNY_ERR_INVALID_ARG, "null argument");
+  LdsSpan rec[16];
+  LdsCarve c;
+  c.spans = rec;
+  switch (family) {
+    case LDS_HEAP_WALK: (void)heap_walk_lds(c, p[0]); break;
+    case LDS_NNS: (void)nns_lds(c, p[0], p[1], p[2]); break;
+    case LDS_NNS_LINEAR: (void)nns_linear_lds(c, p[0]); break;
+    case LDS_EXACT_TOPK: (void)exact_topk_lds(c, p[0]); break;
+    case LDS_EXACT_SCORES: (void)exact_scores_lds(c, p[0], p[1]); break;
+    case LDS_PRUNE: (void)prune_lds(c, p[0], p[1]); break;
+    case LDS_APPLY: (void)apply_lds(c, p[0]); break;
+    case LDS_FILL_GAPS: (void)fill_gaps_lds(c, p[0]); break;
+    case LDS_PRUNE_N8: (void)prune_n8_lds(c, p[0], p[1], (int)p[2]); break;
+    case LDS_APPLY_N8: (void)apply_n8_lds(c, p[0], (int)p[1]); break;
+    default: return fail(HNY_ERR_INVALID_ARG, "hny_internal_lds_layout: no such kernel family");
+  }
+  if (c.n_spans > *n) return fail(HNY_ERR_INVALID_ARG, "hny_internal_lds_layout: too few spans");
+  for (int i = 0; i < c.n_spans; i++) spans[2 * i] = rec[i].off, spans[2 * i + 1] = rec[i].bytes;
+  *n = c.n_spans;
+  out2[0] = c.bytes();
+  out2[1] = c.misaligned ? 1u : 0u;
   return HNY_OK;
 }
 extern "C" int hny_internal_builder_count_evals(hny_builder *b, int on) {
@@ -3773,7 +3817,7 @@ static int search_knn_impl(hny_builder *b, const hny_query_opts *qo, const Query
   HIP_TRY(dcand.alloc((size_t)chunk * rcap));
   HIP_TRY(dcn.alloc(chunk));
   if (int rc = top.alloc(chunk)) return rc;
-  u32 *queues = b->d_nseg.p + 4;
+  const WorkCounters wc{b->d_nseg.p};
   for (uint64_t q0 = 0; q0 < nq; q0 += chunk) {
     uint32_t cnt = (uint32_t)std::min<uint64_t>(chunk, nq - q0);
     if (sc.probe()) { // cancelled: nothing of this chunk is started
@@ -3795,23 +3839,23 @@ static int search_knn_impl(hny_builder *b, const hny_query_opts *qo, const Query
     w.knn_ef = qo->ef_search;
     w.cand = dcand.p;
     w.cand_n = dcn.p;
-    w.queue = queues;
+    w.queue = wc.queue(0);
     w.cancel = sc.d;
     walk_workspace(b, w, rcap, dres.p);
     w.pool_flag = pool_retry_env(w) ? 1u : 0u;
     if (sc.d) HIP_TRY(hnyk_fill_u32(dcn.p, 0xFFFFFFFFu, cnt, b->stream)); // = never finished
-    HIP_TRY(hipMemsetAsync(queues, 0, 8 * 4, b->stream));
+    HIP_TRY(hipMemsetAsync(wc.queue(0), 0, WorkCounters::SEARCH_QUEUES_BYTES, b->stream));
     const int grid = (int)std::min<uint32_t>(cnt, b->walk_slots);
     if (b->locality && b->max_level >= 1 && cnt >= 2048) {
       // same locality ordering as the build: descent -> sort the queries by their region -> layer 0
       b->n_walk_dispatch++;
       HIP_TRY(hnyk_walk(sg, region_descent(b, w), b->shape, hnyk_walk_form(sg, w, b->shape, b->knobs), grid, b->stream));
       if (int rc = region_order(b, 0, cnt, w)) return rc;
-      w.queue = queues + 1;
+      w.queue = wc.queue(1);
       // the same XCD-tiled work queue as the build's level-0 walks (rows >= 1 KB, see xcd_tile_of)
       if ((w.xcd_tile = xcd_tile_of(b, cnt))) {
-        w.queue = queues + 16; // 8 counters, zeroed below
-        HIP_TRY(hipMemsetAsync(queues + 16, 0, 8 * 4, b->stream));
+        w.queue = wc.xcd_queue(0); // 8 counters, zeroed below
+        HIP_TRY(hipMemsetAsync(wc.xcd_queue(0), 0, WorkCounters::XCD_QUEUE_BYTES, b->stream));
       }
     }
     b->n_walk_dispatch++;
@@ -3921,7 +3965,7 @@ static int nns_run(hny_builder *b, const hny_query_opts *qo, const QuerySet &qs,
   DevBuf<u64> dheap_full;
   uint32_t grid_full = 0;
   std::vector<u32> hst(chunk);
-  u32 *queues = b->d_nseg.p + 4;
+  const WorkCounters wc{b->d_nseg.p};
   for (uint64_t q0 = 0; q0 < nq; q0 += chunk) {
     const uint32_t cnt = (uint32_t)std::min<uint64_t>(chunk, nq - q0);
     if (sc.probe()) { // nothing of this chunk is started: 0 hits each (unknown items stay None)
@@ -3962,13 +4006,13 @@ static int nns_run(hny_builder *b, const hny_query_opts *qo, const QuerySet &qs,
     a.log_cap = b->log_cap;
     a.vis_slots = vis_slots_for(b, a.rcap);
     a.eps_cap = eps_cap_of(b);
-    a.queue = queues;
+    a.queue = wc.queue(0);
     a.status = dstatus.p;
     a.cand_slots = F.cand_slots;
     a.n_cand_slots = F.n_cand_slots;
     a.cancel = sc.d;
     if (sc.d) HIP_TRY(hnyk_fill_u32(dstatus.p, 2u, cnt, b->stream)); // 2 = never started
-    HIP_TRY(hipMemsetAsync(queues, 0, 8 * 4, b->stream));
+    HIP_TRY(hipMemsetAsync(wc.queue(0), 0, WorkCounters::SEARCH_QUEUES_BYTES, b->stream));
     if (linear) {
       HIP_TRY(hnyk_nns_linear(sg, a, b->shape, (int)std::min<uint32_t>(n_mem, b->walk_slots), b->stream));
     } else if (big) {
@@ -3995,7 +4039,7 @@ static int nns_run(hny_builder *b, const hny_query_opts *qo, const QuerySet &qs,
         a.n_members = n_retry;
         a.heap = dheap_full.p;
         a.heap_cap = heap_full;
-        a.queue = queues + 1;
+        a.queue = wc.queue(1);
         HIP_TRY(hnyk_nns(sg, a, b->shape, (int)std::min<uint32_t>(n_retry, grid_full), b->stream));
       } else if (n_retry) {
         return fail(HNY_ERR_DEVICE, "search queue overflow");

@@ -349,6 +349,213 @@ struct StageRows {
   int wg, n8;
 };
 
+// ---- dynamic LDS: one description per kernel family ----
+// A cursor over a kernel's dynamic LDS.  The kernel runs its family's layout function on `smem` and keeps the
+// pointers; the launcher (and the host, where a size follows from a layout) runs the same function on a null base
+// and reads bytes().  The cursor is the next array's address and its offset from the base, which is 16-aligned; every
+// array is addressed from the end of the one before it, the way the kernels' cast chains did, and in a kernel the
+// offset and the flag fold away.  `misaligned`: some take<T> landed on an offset that is no multiple of alignof(T).
+// (always inlined: a kernel's prologue must come out as the cast chain it replaces, whatever the inliner would decide)
+#define HNY_LDS_FN __host__ __device__ __forceinline__
+struct LdsSpan {
+  size_t off, bytes;
+};
+struct LdsCarve {
+  unsigned char *next;
+  size_t off = 0;
+  bool misaligned = false;
+  LdsSpan *spans = nullptr; // measuring (hny_internal_lds_layout): every array taken is noted here; null in a kernel
+  int n_spans = 0;
+  HNY_LDS_FN explicit LdsCarve(unsigned char *base = nullptr) : next(base) {}
+  template <class T>
+  HNY_LDS_FN T *take(size_t count, size_t align = alignof(T)) {
+    misaligned |= off % align != 0;
+    if (spans) spans[n_spans++] = LdsSpan{off, count * sizeof(T)};
+    T *p = reinterpret_cast<T *>(next);
+    if (carving()) next = reinterpret_cast<unsigned char *>(p + count); // (typed, as in the cast chains)
+    off += count * sizeof(T);
+    return p;
+  }
+  // whole rows (row_stride is a multiple of 16), read and written as 16-byte units
+  HNY_LDS_FN unsigned char *take_rows(size_t bytes) { return take<unsigned char>(bytes, 16); }
+  // reserved and used by no array: named where it is taken
+  HNY_LDS_FN void skip(size_t bytes) {
+    if (carving()) next += bytes;
+    off += bytes;
+  }
+  HNY_LDS_FN bool carving() const {
+#ifdef __HIP_DEVICE_COMPILE__
+    return true; // a kernel always carves smem
+#else
+    return next != nullptr; // measuring: no arithmetic on a null pointer
+#endif
+  }
+  HNY_LDS_FN size_t bytes() const { return off; }
+};
+// The layouts: sizes by value, the arrays in the order the kernels have always had them.  k_walk, k_prune_wg,
+// k_apply_wg and k_fill_gaps_wg are not here: they keep their cast chains and formulas (hny_kernels.hip), because
+// every form of these functions tried moved the register allocation of instances that sit on a measured budget.
+enum LdsFamily { // hny_internal_lds_layout: the family, and its sizes in the order of the function's parameters
+  LDS_HEAP_WALK, LDS_NNS, LDS_NNS_LINEAR, LDS_EXACT_TOPK, LDS_EXACT_SCORES, LDS_PRUNE, LDS_APPLY, LDS_FILL_GAPS,
+  LDS_PRUNE_N8, LDS_APPLY_N8
+};
+
+// k_walk_heap, k_nns<.., true>: the scratch of a distance pass and the entry points
+struct HeapWalkLds {
+  u32 *nb_ids; // [64]
+  float *nb_d; // [64]
+  u32 *eps;    // [eps_cap]
+};
+HNY_LDS_FN HeapWalkLds heap_walk_lds(LdsCarve &c, u32 eps_cap) {
+  HeapWalkLds L;
+  L.nb_ids = c.take<u32>(64);
+  L.nb_d = c.take<float>(64);
+  L.eps = c.take<u32>(eps_cap);
+  return L;
+}
+// k_nns<.., false>: the beam, the tie pool, the heap walk's arrays and the visited table behind all eps_cap entry
+// points.  Without the table this is the fixed part of k_walk's LDS too (hnyk_walk_lds_bytes)
+struct NnsLds {
+  u64 *res;  // [rcap] the beam
+  u64 *pool; // [HNY_POOL_CAP] the tie pool
+  HeapWalkLds h;
+  u32 *vis;  // [vis_slots] visited table (Visited)
+};
+HNY_LDS_FN NnsLds nns_lds(LdsCarve &c, u32 rcap, u32 eps_cap, u32 vis_slots) {
+  NnsLds L;
+  L.res = c.take<u64>(rcap);
+  L.pool = c.take<u64>(HNY_POOL_CAP);
+  L.h = heap_walk_lds(c, eps_cap);
+  L.vis = c.take<u32>(vis_slots);
+  return L;
+}
+// k_nns_linear
+struct NnsLinearLds {
+  u64 *res;    // [rcap]
+  u32 *nb_ids; // [64]
+  float *nb_d; // [64]
+};
+HNY_LDS_FN NnsLinearLds nns_linear_lds(LdsCarve &c, u32 rcap) {
+  NnsLinearLds L;
+  L.res = c.take<u64>(rcap);
+  L.nb_ids = c.take<u32>(64);
+  L.nb_d = c.take<float>(64);
+  return L;
+}
+// k_exact_topk
+struct ExactTopkLds {
+  u64 *res; // [rcap]
+};
+HNY_LDS_FN ExactTopkLds exact_topk_lds(LdsCarve &c, u32 rcap) { return ExactTopkLds{c.take<u64>(rcap)}; }
+// k_exact_scores
+struct ExactScoresLds {
+  unsigned char *qrows; // [qt][row_stride] the tile's query rows
+  float *qnorm;         // [qt]
+};
+HNY_LDS_FN ExactScoresLds exact_scores_lds(LdsCarve &c, u32 qt, u32 row_stride) {
+  ExactScoresLds L;
+  L.qrows = c.take_rows((size_t)qt * row_stride);
+  L.qnorm = c.take<float>(qt);
+  return L;
+}
+// wave_prune's scratch (capmax = wave_capmax), behind the front of k_prune and k_apply
+struct WavePruneLds {
+  u64 *S;       // [capmax] selected keys
+  u32 *s_ids;   // [capmax]
+  float *tmp_d; // [64]
+};
+HNY_LDS_FN WavePruneLds wave_prune_lds(LdsCarve &c, u32 capmax) {
+  WavePruneLds L;
+  L.S = c.take<u64>(capmax);
+  L.s_ids = c.take<u32>(capmax);
+  L.tmp_d = c.take<float>(64);
+  return L;
+}
+// k_prune
+struct PruneLds {
+  u64 *list; // [rcap] the member's candidates
+  WavePruneLds w;
+};
+HNY_LDS_FN PruneLds prune_lds(LdsCarve &c, u32 rcap, u32 capmax) {
+  PruneLds L;
+  L.list = c.take<u64>(rcap);
+  L.w = wave_prune_lds(c, capmax);
+  return L;
+}
+// k_apply
+struct ApplyLds {
+  u64 *lk, *sorted; // [capmax] each: the node's list and its sorted copy
+  WavePruneLds w;
+};
+HNY_LDS_FN ApplyLds apply_lds(LdsCarve &c, u32 capmax) {
+  ApplyLds L;
+  L.lk = c.take<u64>(capmax);
+  L.sorted = c.take<u64>(capmax);
+  L.w = wave_prune_lds(c, capmax);
+  return L;
+}
+// k_fill_gaps (lists of at most HNY_MAX_CAP slots): the gathered ids sit between S and s_ids
+struct FillGapsLds {
+  u64 *keys, *sorted; // [maxu + HNY_MAX_CAP] each: the old list, then the scored bm / its sorted copy
+  u64 *S;             // [HNY_MAX_CAP]
+  u32 *cand, *bm;     // [maxu] each
+  u32 *s_ids;         // [HNY_MAX_CAP]
+  float *tmp_d;       // [64]
+};
+HNY_LDS_FN FillGapsLds fill_gaps_lds(LdsCarve &c, u32 maxu) {
+  FillGapsLds L;
+  L.keys = c.take<u64>((size_t)maxu + HNY_MAX_CAP);
+  L.sorted = c.take<u64>((size_t)maxu + HNY_MAX_CAP);
+  L.S = c.take<u64>(HNY_MAX_CAP);
+  L.cand = c.take<u32>(maxu);
+  L.bm = c.take<u32>(maxu);
+  L.s_ids = c.take<u32>(HNY_MAX_CAP);
+  L.tmp_d = c.take<float>(64);
+  return L;
+}
+// prune_n8_core's arrays, behind the front of each short-row kernel
+struct N8Lds {
+  u64 *S;                // [HNY_MAX_CAP] selected keys
+  u32 *s_ids;            // [HNY_MAX_CAP]
+  float *s_norm;         // [HNY_MAX_CAP]
+  unsigned char *stage;  // [SL][row_stride] selected rows
+  unsigned char *newrow; // [row_stride] the row that has just joined S
+};
+HNY_LDS_FN N8Lds n8_lds(LdsCarve &c, u32 row_stride, int SL) {
+  N8Lds L;
+  L.S = c.take<u64>(HNY_MAX_CAP);
+  L.s_ids = c.take<u32>(HNY_MAX_CAP);
+  L.s_norm = c.take<float>(HNY_MAX_CAP);
+  L.stage = c.take_rows((size_t)SL * row_stride);
+  L.newrow = c.take_rows(row_stride);
+  return L;
+}
+// k_prune_n8
+struct PruneN8Lds {
+  u64 *list; // [rcap]
+  N8Lds n;
+};
+HNY_LDS_FN PruneN8Lds prune_n8_lds(LdsCarve &c, u32 rcap, u32 row_stride, int SL) {
+  PruneN8Lds L;
+  L.list = c.take<u64>(rcap);
+  L.n = n8_lds(c, row_stride, SL);
+  return L;
+}
+// k_apply_n8
+struct ApplyN8Lds {
+  u64 *lk, *sorted; // [HNY_MAX_CAP] each
+  N8Lds n;
+};
+HNY_LDS_FN ApplyN8Lds apply_n8_lds(LdsCarve &c, u32 row_stride, int SL) {
+  ApplyN8Lds L;
+  L.lk = c.take<u64>(HNY_MAX_CAP);
+  L.sorted = c.take<u64>(HNY_MAX_CAP);
+  L.n = n8_lds(c, row_stride, SL);
+  return L;
+}
+// bytes of a layout: HNY_LDS_BYTES(prune_lds, rcap, capmax) runs the function on a null cursor
+#define HNY_LDS_BYTES(layout, ...) ([&] { LdsCarve c_; (void)layout(c_, __VA_ARGS__); return c_.bytes(); }())
+
 // kernels' host launchers (hny_kernels.hip): the build kernels instantiate the form they are handed
 hipError_t hnyk_walk(const GraphDev &g, const WalkArgs &a, LaunchShape s, const WalkForm &f, int grid, hipStream_t st);
 // the members of a.pool_retry[0 .. *a.n_pool_retry) again, on heaps in HBM (a.queue: its own work counter)

@@ -1989,6 +1989,8 @@ __global__ __launch_bounds__(64, hnyk_walk_waves_per_simd(LPR, NCH, SP, RM, RC))
   (void)a_in;
 #define KA_FRESH() asm volatile("" : "+s"(ak))
   const int reader_mode = SP != 0 ? (RM ? 1 : 0) : ak->reader_mode; // RM: the Reader's search (hny_builder_search_knn)
+  // (k_walk, k_prune_wg, k_apply_wg and k_fill_gaps_wg keep their cast chains and byte formulas: each instance sits
+  // on a measured register budget, and the layout functions of hny_internal.h moved their allocation)
   extern __shared__ __align__(16) unsigned char smem[];
   u64 *res = reinterpret_cast<u64 *>(smem);
   u64 *pool = res + ak->rcap;
@@ -2544,9 +2546,11 @@ __device__ int walk_layer_heap(const GraphDev &g, const float4 (&q)[NCH], float 
 template <int LPR, int NCH>
 __global__ __launch_bounds__(64, 4) void k_walk_heap(GraphDev g, WalkArgs a) {
   extern __shared__ __align__(16) unsigned char smem[];
-  u32 *nb_ids = reinterpret_cast<u32 *>(smem);
-  float *nb_d = reinterpret_cast<float *>(nb_ids + 64);
-  u32 *eps = reinterpret_cast<u32 *>(nb_d + 64);
+  LdsCarve lds(smem);
+  const HeapWalkLds lay = heap_walk_lds(lds, a.eps_cap);
+  u32 *nb_ids = lay.nb_ids;
+  float *nb_d = lay.nb_d;
+  u32 *eps = lay.eps;
   const int ln = threadIdx.x, t = ln % LPR;
   const u32 n_mem = *a.n_pool_retry;
   if (n_mem == 0u) return;
@@ -2633,11 +2637,17 @@ __global__ __launch_bounds__(64, 4) void k_walk_heap(GraphDev g, WalkArgs a) {
 template <int LPR, int NCH, bool RES_HEAP>
 __global__ __launch_bounds__(64, 4) void k_nns(GraphDev g, NnsArgs a) {
   extern __shared__ __align__(16) unsigned char smem[];
-  u64 *res = reinterpret_cast<u64 *>(smem); // (LDS variant: res, the descent's tie pool, then the rest)
-  u64 *pool = res + a.rcap;
-  u32 *nb_ids = RES_HEAP ? reinterpret_cast<u32 *>(smem) : reinterpret_cast<u32 *>(pool + HNY_POOL_CAP);
-  float *nb_d = reinterpret_cast<float *>(nb_ids + 64);
-  u32 *eps = reinterpret_cast<u32 *>(nb_d + 64);
+  LdsCarve lds(smem); // (RES_HEAP: the heap walk's arrays only)
+  NnsLds lay{};
+  if constexpr (RES_HEAP)
+    lay.h = heap_walk_lds(lds, a.eps_cap);
+  else
+    lay = nns_lds(lds, a.rcap, a.eps_cap, a.vis_slots);
+  u64 *res = lay.res;
+  u64 *pool = lay.pool;
+  u32 *nb_ids = lay.h.nb_ids;
+  float *nb_d = lay.h.nb_d;
+  u32 *eps = lay.h.eps;
   const int ln = threadIdx.x, t = ln % LPR;
 
   Beam s; // LDS variant: greedy descent through the upper layers, the ordinary (unfiltered) walk
@@ -2645,8 +2655,7 @@ __global__ __launch_bounds__(64, 4) void k_nns(GraphDev g, NnsArgs a) {
   BeamR<1> rb_unused{{0ull}};
   Visited vis;
   visited_init(vis, a.bits + (size_t)blockIdx.x * a.bits_words, a.bits_words,
-               a.vlog + (size_t)blockIdx.x * a.log_cap, a.log_cap, RES_HEAP ? nullptr : eps + a.eps_cap,
-               RES_HEAP ? 0u : a.vis_slots);
+               a.vlog + (size_t)blockIdx.x * a.log_cap, a.log_cap, lay.vis, RES_HEAP ? 0u : a.vis_slots);
   QHeap C, R;
   C.h = a.heap + (size_t)blockIdx.x * a.heap_cap;
   C.cap = a.heap_cap;
@@ -2768,9 +2777,11 @@ __global__ __launch_bounds__(64, 4) void k_nns(GraphDev g, NnsArgs a) {
 template <int LPR, int NCH>
 __global__ __launch_bounds__(64, 4) void k_nns_linear(GraphDev g, NnsArgs a) {
   extern __shared__ __align__(16) unsigned char smem[];
-  u64 *res = reinterpret_cast<u64 *>(smem);
-  u32 *nb_ids = reinterpret_cast<u32 *>(res + a.rcap);
-  float *nb_d = reinterpret_cast<float *>(nb_ids + 64);
+  LdsCarve lds(smem);
+  const NnsLinearLds lay = nns_linear_lds(lds, a.rcap);
+  u64 *res = lay.res;
+  u32 *nb_ids = lay.nb_ids;
+  float *nb_d = lay.nb_d;
   const int ln = threadIdx.x, t = ln % LPR;
   u64 evals = 0;
   u32 res_err = 0;
@@ -2841,7 +2852,10 @@ __global__ __launch_bounds__(64, 4) void k_nns_linear(GraphDev g, NnsArgs a) {
 template <int LPR, int NCH, bool TILE>
 __global__ __launch_bounds__(256) void k_exact_scores(GraphDev g, ExactArgs a) {
   extern __shared__ __align__(16) unsigned char smem[];
-  float *qnorm = reinterpret_cast<float *>(smem + (size_t)a.qt * g.row_stride);
+  LdsCarve lds(smem);
+  const ExactScoresLds lay = exact_scores_lds(lds, a.qt, g.row_stride);
+  unsigned char *qrows = lay.qrows;
+  float *qnorm = lay.qnorm;
   const u32 q0 = blockIdx.x * a.qt;
   const int nqt = (int)(a.nq - q0 < a.qt ? a.nq - q0 : a.qt);
   const u32 slab_end = a.slab_base + a.slab_n;
@@ -2860,7 +2874,7 @@ __global__ __launch_bounds__(256) void k_exact_scores(GraphDev g, ExactArgs a) {
     const u32 qi = i / g.n16, f = i - qi * g.n16;
     const unsigned char *src = a.q_slots ? g.rows + (size_t)a.q_slots[q0 + qi] * g.row_stride
                                          : a.q_rows + (size_t)(q0 + qi) * a.q_stride;
-    *reinterpret_cast<float4 *>(smem + (size_t)qi * g.row_stride + (size_t)f * 16) =
+    *reinterpret_cast<float4 *>(qrows + (size_t)qi * g.row_stride + (size_t)f * 16) =
         *reinterpret_cast<const float4 *>(src + (size_t)f * 16);
   }
   if ((int)threadIdx.x < nqt) {
@@ -2910,7 +2924,7 @@ __global__ __launch_bounds__(256) void k_exact_scores(GraphDev g, ExactArgs a) {
     }
     for (int qi = 0; qi < nqt; qi++) {
       float4 q[NCH];
-      load_row_lds<LPR, NCH>(smem + (size_t)qi * g.row_stride, t, g.n16, q);
+      load_row_lds<LPR, NCH>(qrows + (size_t)qi * g.row_stride, t, g.n16, q);
       const float qn = qnorm[qi];
       float *out = a.scores + (size_t)(q0 + (u32)qi) * a.score_stride;
 #pragma unroll
@@ -2973,7 +2987,8 @@ __global__ __launch_bounds__(256) void k_exact_scores(GraphDev g, ExactArgs a) {
 // only, the live mask for a member without a filter, and the member's own k (a.k_of); a.rcap is the block's largest.
 __global__ __launch_bounds__(64) void k_exact_topk(GraphDev g, ExactArgs a) {
   extern __shared__ __align__(16) unsigned char smem[];
-  u64 *res = reinterpret_cast<u64 *>(smem);
+  LdsCarve lds(smem);
+  u64 *res = exact_topk_lds(lds, a.rcap).res;
   const int ln = threadIdx.x;
   const u32 qi = blockIdx.x;
   u64 *list = a.lists + (size_t)qi * a.rcap;
@@ -3220,11 +3235,12 @@ __device__ __forceinline__ int wave_prune(const GraphDev &g, const u64 *list, in
 template <int LPR, int NCH>
 __global__ __launch_bounds__(64) void k_prune(GraphDev g, PruneArgs a) {
   extern __shared__ __align__(16) unsigned char smem[];
-  u64 *list = reinterpret_cast<u64 *>(smem);
-  u64 *S = list + a.rcap;
-  const u32 capmax = wave_capmax(g);
-  u32 *s_ids = reinterpret_cast<u32 *>(S + capmax);
-  float *tmp_d = reinterpret_cast<float *>(s_ids + capmax);
+  LdsCarve lds(smem);
+  const PruneLds lay = prune_lds(lds, a.rcap, wave_capmax(g));
+  u64 *list = lay.list;
+  u64 *S = lay.w.S;
+  u32 *s_ids = lay.w.s_ids;
+  float *tmp_d = lay.w.tmp_d;
   const int ln = threadIdx.x;
   u64 evals = 0;
   for (u32 m = a.lo + blockIdx.x; m < a.hi; m += gridDim.x) {
@@ -3548,12 +3564,6 @@ __device__ __forceinline__ float dist8(const GraphDev &g, const float4 (&c)[LPRO
   if (g.mclass == MC_BIN) return finalize_bin(g, butterfly_u32<8>(partial_bin<NQ>(c, r)), cn, rn);
   return finalize_f32(g, butterfly_f32<8>(partial8<NQ>(g.mclass, c, r)), cn, rn);
 }
-__host__ __device__ inline size_t prune_n8_lds_bytes(u32 rcap, u32 row_stride, int SL) {
-  return (size_t)rcap * 8 + (size_t)HNY_MAX_CAP * (8 + 4 + 4) + (size_t)(SL + 1) * row_stride;
-}
-__host__ __device__ inline size_t apply_n8_lds_bytes(u32 row_stride, int SL) {
-  return (size_t)HNY_MAX_CAP * (8 + 8 + 8 + 4 + 4) + (size_t)(SL + 1) * row_stride;
-}
 
 // the prune of one sorted list by one wave (see above); S / s_ids / s_norm: HNY_MAX_CAP entries, stage: SL rows,
 // newrow: one row.  Returns the number of selected entries, left in S.  `list` (LDS, owned by the caller) is
@@ -3714,12 +3724,14 @@ __global__ __launch_bounds__(64, 5) void k_prune_n8(GraphDev g_in, PruneArgs a, 
   GraphDev g = g_in;
   specialize<SP>(g);
   extern __shared__ __align__(16) unsigned char smem[];
-  u64 *list = reinterpret_cast<u64 *>(smem);
-  u64 *S = list + a.rcap;
-  u32 *s_ids = reinterpret_cast<u32 *>(S + HNY_MAX_CAP);
-  float *s_norm = reinterpret_cast<float *>(s_ids + HNY_MAX_CAP);
-  unsigned char *stage = reinterpret_cast<unsigned char *>(s_norm + HNY_MAX_CAP); // [SL] selected rows
-  unsigned char *newrow = stage + (size_t)SL * g.row_stride;                      // the row that has just joined S
+  LdsCarve lds(smem);
+  const PruneN8Lds lay = prune_n8_lds(lds, a.rcap, g.row_stride, SL);
+  u64 *list = lay.list;
+  u64 *S = lay.n.S;
+  u32 *s_ids = lay.n.s_ids;
+  float *s_norm = lay.n.s_norm;
+  unsigned char *stage = lay.n.stage;
+  unsigned char *newrow = lay.n.newrow;
   const int ln = HNY_LANE;
   u64 evals = 0;
   for (u32 mi = a.lo + blockIdx.x; mi < a.hi; mi += gridDim.x) {
@@ -3797,13 +3809,15 @@ __global__ __launch_bounds__(64, 5) void k_apply_n8(GraphDev g_in, ApplyArgs a, 
   GraphDev g = g_in;
   specialize<SP>(g);
   extern __shared__ __align__(16) unsigned char smem[];
-  u64 *lk = reinterpret_cast<u64 *>(smem); // [HNY_MAX_CAP] the node's list
-  u64 *sorted = lk + HNY_MAX_CAP;          // [HNY_MAX_CAP]
-  u64 *S = sorted + HNY_MAX_CAP;
-  u32 *s_ids = reinterpret_cast<u32 *>(S + HNY_MAX_CAP);
-  float *s_norm = reinterpret_cast<float *>(s_ids + HNY_MAX_CAP);
-  unsigned char *stage = reinterpret_cast<unsigned char *>(s_norm + HNY_MAX_CAP);
-  unsigned char *newrow = stage + (size_t)SL * g.row_stride;
+  LdsCarve lds(smem);
+  const ApplyN8Lds lay = apply_n8_lds(lds, g.row_stride, SL);
+  u64 *lk = lay.lk; // the node's list
+  u64 *sorted = lay.sorted;
+  u64 *S = lay.n.S;
+  u32 *s_ids = lay.n.s_ids;
+  float *s_norm = lay.n.s_norm;
+  unsigned char *stage = lay.n.stage;
+  unsigned char *newrow = lay.n.newrow;
   const u32 n_def = *a.n_deferred;
   u64 evals = 0;
   const u32 sw = a.shard_world ? a.shard_world : 1u;
@@ -3951,12 +3965,13 @@ __global__ __launch_bounds__(64) void k_apply(GraphDev g_in, ApplyArgs a) {
   // (lists of more than 64 slots — strict mode with M0 up to HNY_BIG_CAP, the reference's fuzz pair (16, 768) in
   // the x86 order — are held whole and taken 64 slots at a time)
   extern __shared__ __align__(16) unsigned char smem[];
-  const u32 capmax = wave_capmax(g);
-  u64 *lk = reinterpret_cast<u64 *>(smem); // the node's list
-  u64 *sorted = lk + capmax;
-  u64 *S = sorted + capmax;
-  u32 *s_ids = reinterpret_cast<u32 *>(S + capmax);
-  float *tmp_d = reinterpret_cast<float *>(s_ids + capmax);
+  LdsCarve lds(smem);
+  const ApplyLds lay = apply_lds(lds, wave_capmax(g));
+  u64 *lk = lay.lk; // the node's list
+  u64 *sorted = lay.sorted;
+  u64 *S = lay.w.S;
+  u32 *s_ids = lay.w.s_ids;
+  float *tmp_d = lay.w.tmp_d;
   const u32 n_seg = *a.n_seg;
   u64 evals = 0;
   for (u32 sg = blockIdx.x; sg < n_seg; sg += gridDim.x) {
@@ -4030,20 +4045,19 @@ __device__ __forceinline__ void store_gaps_fit(const NodeList &l, const u32 *bm,
   });
   if (threadIdx.x == 0) *l.cnt = (u32)(nb + cnt);
 }
-__host__ __device__ inline size_t fill_gaps_lds_bytes(u32 maxu) {
-  return (size_t)maxu * 4 * 2 + (size_t)(maxu + HNY_MAX_CAP) * 8 * 2 + HNY_MAX_CAP * (8 + 4) + 64 * 4;
-}
 template <int LPR, int NCH>
 __global__ __launch_bounds__(64) void k_fill_gaps(GraphDev g, const u64 *recs, u32 n_recs,
                                                   const unsigned char *deleted, u32 maxu) {
   extern __shared__ __align__(16) unsigned char smem[];
-  u64 *keys = reinterpret_cast<u64 *>(smem);            // [maxu + HNY_MAX_CAP] the old list, then the scored bm
-  u64 *sorted = keys + (maxu + HNY_MAX_CAP);            // [maxu + HNY_MAX_CAP]
-  u64 *S = sorted + (maxu + HNY_MAX_CAP);               // [HNY_MAX_CAP]
-  u32 *cand = reinterpret_cast<u32 *>(S + HNY_MAX_CAP); // [maxu]
-  u32 *bm = cand + maxu;                                // [maxu]
-  u32 *s_ids = bm + maxu;                               // [HNY_MAX_CAP]
-  float *tmp_d = reinterpret_cast<float *>(s_ids + HNY_MAX_CAP); // [64]
+  LdsCarve lds(smem);
+  const FillGapsLds lay = fill_gaps_lds(lds, maxu);
+  u64 *keys = lay.keys; // the old list, then the scored bm
+  u64 *sorted = lay.sorted;
+  u64 *S = lay.S;
+  u32 *cand = lay.cand;
+  u32 *bm = lay.bm;
+  u32 *s_ids = lay.s_ids;
+  float *tmp_d = lay.tmp_d;
   const int MAXU = (int)maxu;
   const int ln = threadIdx.x, t = ln % LPR;
   u64 evals = 0;
@@ -4611,8 +4625,8 @@ struct Hot {
     static hipError_t run(const GraphDev &g, const PruneArgs &a, const PruneForm &f, int SL, int grid, hipStream_t st) {
       if constexpr (SP != 0 && C == 1 && L <= 32)
         if (f.kind == PRUNE_N8) { // short rows (<= 512 B): one wave per query, eight candidates at a time
-          hipLaunchKernelGGL((k_prune_n8<L, SP>), dim3(grid), dim3(64), prune_n8_lds_bytes(a.rcap, g.row_stride, SL), st,
-                             g, a, SL);
+          hipLaunchKernelGGL((k_prune_n8<L, SP>), dim3(grid), dim3(64),
+                             HNY_LDS_BYTES(prune_n8_lds, a.rcap, g.row_stride, SL), st, g, a, SL);
           return hipGetLastError();
         }
       if constexpr (C <= 8)
@@ -4623,7 +4637,7 @@ struct Hot {
         }
       if constexpr (SP == 0)
         if (f.kind == PRUNE_WAVE) {
-          const size_t lds = (size_t)a.rcap * 8 + (size_t)wave_capmax(g) * (8 + 4) + 64 * 4;
+          const size_t lds = HNY_LDS_BYTES(prune_lds, a.rcap, wave_capmax(g));
           hipLaunchKernelGGL((k_prune<L, C>), dim3(grid), dim3(64), lds, st, g, a);
           return hipGetLastError();
         }
@@ -4635,7 +4649,8 @@ struct Hot {
     static hipError_t run(const GraphDev &g, const ApplyArgs &a, const ApplyForm &f, int SL, int grid, hipStream_t st) {
       if constexpr (SP != 0 && C == 1 && L <= 32)
         if (f.kind == APPLY_APPEND_N8) {
-          hipLaunchKernelGGL((k_apply_n8<L, SP>), dim3(grid), dim3(64), apply_n8_lds_bytes(g.row_stride, SL), st, g, a, SL);
+          hipLaunchKernelGGL((k_apply_n8<L, SP>), dim3(grid), dim3(64), HNY_LDS_BYTES(apply_n8_lds, g.row_stride, SL), st,
+                             g, a, SL);
           return hipGetLastError();
         }
       if constexpr (C <= 8)
@@ -4645,7 +4660,7 @@ struct Hot {
         }
       if constexpr (SP == 0 || C > 8)
         if (f.kind == APPLY_WAVE) {
-          const size_t lds = (size_t)wave_capmax(g) * (8 + 8 + 8 + 4) + 64 * 4;
+          const size_t lds = HNY_LDS_BYTES(apply_lds, wave_capmax(g));
           hipLaunchKernelGGL((k_apply<L, C, SP>), dim3(grid), dim3(64), lds, st, g, a);
           return hipGetLastError();
         }
@@ -4657,10 +4672,10 @@ template <int L, int C>
 struct NnsLauncher {
   static hipError_t run(const GraphDev &g, const NnsArgs &a, int grid, hipStream_t st) {
     if (a.heap_r) {
-      const size_t lds = 64 * 4 * 2 + (size_t)a.eps_cap * 4;
+      const size_t lds = HNY_LDS_BYTES(heap_walk_lds, a.eps_cap);
       hipLaunchKernelGGL((k_nns<L, C, true>), dim3(grid), dim3(64), lds, st, g, a);
     } else {
-      const size_t lds = hnyk_walk_lds_bytes(a.rcap, a.eps_cap) + (size_t)a.vis_slots * 4;
+      const size_t lds = HNY_LDS_BYTES(nns_lds, a.rcap, a.eps_cap, a.vis_slots);
       hipLaunchKernelGGL((k_nns<L, C, false>), dim3(grid), dim3(64), lds, st, g, a);
     }
     return hipGetLastError();
@@ -4669,7 +4684,7 @@ struct NnsLauncher {
 template <int L, int C>
 struct WalkHeapLauncher {
   static hipError_t run(const GraphDev &g, const WalkArgs &a, int grid, hipStream_t st) {
-    const size_t lds = 64 * 4 * 2 + (size_t)a.eps_cap * 4;
+    const size_t lds = HNY_LDS_BYTES(heap_walk_lds, a.eps_cap);
     hipLaunchKernelGGL((k_walk_heap<L, C>), dim3(grid), dim3(64), lds, st, g, a);
     return hipGetLastError();
   }
@@ -4677,7 +4692,7 @@ struct WalkHeapLauncher {
 template <int L, int C>
 struct NnsLinearLauncher {
   static hipError_t run(const GraphDev &g, const NnsArgs &a, int grid, hipStream_t st) {
-    size_t lds = (size_t)a.rcap * 8 + 64 * 4 * 2;
+    const size_t lds = HNY_LDS_BYTES(nns_linear_lds, a.rcap);
     hipLaunchKernelGGL((k_nns_linear<L, C>), dim3(grid), dim3(64), lds, st, g, a);
     return hipGetLastError();
   }
@@ -4685,7 +4700,7 @@ struct NnsLinearLauncher {
 template <int L, int C>
 struct ExactScoresLauncher {
   static hipError_t run(const GraphDev &g, const ExactArgs &a, hipStream_t st) {
-    const size_t lds = (size_t)a.qt * g.row_stride + (size_t)a.qt * 4;
+    const size_t lds = HNY_LDS_BYTES(exact_scores_lds, a.qt, g.row_stride);
     const dim3 grid((a.nq + a.qt - 1) / a.qt, (a.slab_n + HNY_EXACT_CHUNK - 1) / HNY_EXACT_CHUNK);
     if (a.tile_mask) return launch_with_lds(k_exact_scores<L, C, true>, grid, dim3(256), lds, st, g, a);
     return launch_with_lds(k_exact_scores<L, C, false>, grid, dim3(256), lds, st, g, a);
@@ -4698,7 +4713,7 @@ struct GapsLauncher {
     int grid = n_recs < 16384u ? (int)n_recs : 16384;
     const u32 cap = g.M0 > g.M ? g.M0 : g.M;
     const u32 maxu = cap * (cap + 1u);
-    const size_t lds = fill_gaps_lds_bytes(maxu);
+    const size_t lds = HNY_LDS_BYTES(fill_gaps_lds, maxu);
     return launch_with_lds(k_fill_gaps<L, C>, dim3(grid), dim3(64), lds, st, g, recs, n_recs, deleted, maxu);
   }
 };
@@ -4761,7 +4776,7 @@ hipError_t HNY_CAT(hnyk_apply_sp, HNY_PART)(const GraphDev &g, const ApplyArgs &
   }
 
 size_t hnyk_walk_lds_bytes(u32 rcap, u32 eps_cap) {
-  return (size_t)rcap * 8 + HNY_POOL_CAP * 8 + 64 * 4 * 2 + (size_t)eps_cap * 4;
+  return HNY_LDS_BYTES(nns_lds, rcap, eps_cap, 0u); // k_nns's layout without its table: what k_walk's cast chain fixes too
 }
 
 hipError_t hnyk_walk(const GraphDev &g, const WalkArgs &a, LaunchShape s, const WalkForm &f, int grid, hipStream_t st) {
@@ -4783,7 +4798,7 @@ hipError_t hnyk_exact_scores(const GraphDev &g, const ExactArgs &a, LaunchShape 
 }
 hipError_t hnyk_exact_topk(const GraphDev &g, const ExactArgs &a, hipStream_t st) {
   if (!a.nq || !a.slab_n) return hipSuccess;
-  hipLaunchKernelGGL(k_exact_topk, dim3(a.nq), dim3(64), (size_t)a.rcap * 8, st, g, a);
+  hipLaunchKernelGGL(k_exact_topk, dim3(a.nq), dim3(64), HNY_LDS_BYTES(exact_topk_lds, a.rcap), st, g, a);
   return hipGetLastError();
 }
 hipError_t hnyk_exact_tile_masks(const ExactArgs &a, hipStream_t st) {
