@@ -45,6 +45,7 @@ EXPORTED = [
     "hny_builder_exact_knn_bitsets", "hny_builder_exact_knn_bitsets_f32",
     "hny_builder_exact_range", "hny_builder_exact_range_f32", "hny_builder_exact_range_count",
     "hny_builder_exact_range_count_f32", "hny_range_result_free",
+    "hny_builder_finish_encoded", "hny_encoded_links_free", "hny_encode_kv_encoded",
 ]
 ERR_IO = -9
 NNS_NONE = 0xFFFFFFFF  # by_item: the reference returns None
@@ -244,6 +245,17 @@ class GraphDeltaStruct(C.Structure):
                 ("max_level", C.c_uint32), ("n_records_total", C.c_uint64), ("t_export_s", C.c_double)]
 
 
+class EncodedLinksStruct(C.Structure):
+    """hny_encoded_links: library-owned and read-only here, not part of hny_abi_sizes"""
+    _fields_ = [("n_records", C.c_uint64), ("rec_item", C.POINTER(C.c_uint32)),
+                ("rec_layer", C.POINTER(C.c_uint8)), ("val_offset", C.POINTER(C.c_uint64)),
+                ("values", C.POINTER(C.c_uint8)), ("entry_points", C.POINTER(C.c_uint32)),
+                ("n_entry_points", C.c_uint32), ("max_level", C.c_uint32),
+                ("n_links_added", C.c_uint64), ("n_evals_walk", C.c_uint64), ("n_batches", C.c_uint64),
+                ("t_export_s", C.c_double), ("t_device_s", C.c_double), ("t_download_s", C.c_double),
+                ("bytes_downloaded", C.c_uint64)]
+
+
 class Batch(C.Structure):
     _fields_ = [("first", C.c_uint64), ("count", C.c_uint32), ("level", C.c_uint32),
                 ("n_layers", C.c_uint32), ("sel_stride_u64", C.c_uint32)]
@@ -426,6 +438,13 @@ def load_library():
     L.hny_builder_create_changed_distance.argtypes = [vp, C.POINTER(ChangeDistance), C.POINTER(vp)]
     L.hny_builder_recode_items.restype = C.c_int
     L.hny_builder_recode_items.argtypes = [vp, C.c_int32, vp, vp]
+    L.hny_builder_finish_encoded.restype = C.c_int
+    L.hny_builder_finish_encoded.argtypes = [vp, C.POINTER(C.POINTER(EncodedLinksStruct))]
+    L.hny_encoded_links_free.restype = None
+    L.hny_encoded_links_free.argtypes = [C.POINTER(EncodedLinksStruct)]
+    L.hny_encode_kv_encoded.restype = C.c_int
+    L.hny_encode_kv_encoded.argtypes = [C.POINTER(EncodedLinksStruct), C.POINTER(BuildOpts), C.POINTER(Items),
+                                        C.c_uint16, C.c_int, KV_SINK, vp]
     L.hny_abi_sizes.restype = C.c_uint32
     L.hny_abi_sizes.argtypes = [C.POINTER(C.c_uint32), C.c_uint32]
     _check_abi(L)
@@ -823,11 +842,7 @@ class Graph:
             out.append((bytes(k[:kl]), bytes(v[:vl])))
             return 0
         cb = KV_SINK(sink)
-        if isinstance(self._items, _IdsOnly) and not with_items:  # a successor's items live on the device
-            ids = np.ascontiguousarray(self._items.ids, np.uint32)
-            it = Items(len(ids), _p(ids).value, None, 0, None, 0, None)
-        else:
-            it = self._items.encoded().struct()  # an F32ItemSet encodes on the host here, once
+        it, _keep = _kv_items(self._items, with_items)
         _check(load_library().hny_encode_kv(self._gp, C.byref(self._opts), C.byref(it), index,
                                             int(with_items), cb, None))
         return out
@@ -841,6 +856,86 @@ class Graph:
         sink = C.cast(L.hny_lmdb_writer_put, KV_SINK)
         try:
             _check(L.hny_encode_kv(self._gp, C.byref(self._opts), C.byref(it), index, int(with_items), sink, w.handle))
+        except Exception:
+            w.abort()
+            raise
+        w.finish()
+
+
+def _kv_items(items, with_items):
+    """(hny_items for hny_encode_kv[_encoded], what keeps its arrays alive)"""
+    if isinstance(items, _IdsOnly) and not with_items:  # a successor's items live on the device
+        ids = np.ascontiguousarray(items.ids, np.uint32)
+        return Items(len(ids), _p(ids).value, None, 0, None, 0, None), ids
+    enc = items.encoded()  # an F32ItemSet encodes on the host here, once
+    return enc.struct(), enc
+
+
+class EncodedLinks:
+    """hny_encoded_links (Builder.finish_encoded): the Links records of a finished builder, their values serialised
+    on the device.  `rec_item`, `rec_layer`, `val_offset`, `values` are numpy views of the library's arrays (valid
+    while this object lives, which frees them); the value of record r is values[val_offset[r]:val_offset[r + 1]]."""
+
+    _VIEWS = ("rec_item", "rec_layer", "val_offset", "values")
+
+    def __init__(self, ep, opts=None, items=None):
+        e = ep.contents
+        for f in ("max_level", "n_links_added", "n_evals_walk", "n_batches", "t_export_s", "t_device_s",
+                  "t_download_s", "bytes_downloaded"):
+            setattr(self, f, getattr(e, f))
+        ne = e.n_entry_points
+        self.entry_points = np.ctypeslib.as_array(e.entry_points, (max(ne, 1),))[:ne].copy()
+        self._ep, self._opts, self._items = ep, opts, items
+
+    def __getattr__(self, name):
+        if name not in EncodedLinks._VIEWS or self.__dict__.get("_ep") is None:
+            raise AttributeError(name)
+        e = self._ep.contents
+        nrec = e.n_records
+        if name == "val_offset":
+            v = np.ctypeslib.as_array(e.val_offset, (nrec + 1,))
+        elif name == "values":
+            nb = int(self.val_offset[-1])
+            v = np.ctypeslib.as_array(e.values, (max(nb, 1),))[:nb]
+        else:
+            v = np.ctypeslib.as_array(getattr(e, name), (max(nrec, 1),))[:nrec]
+        self.__dict__[name] = v
+        return v
+
+    def __del__(self):
+        try:
+            if getattr(self, "_ep", None) is not None:
+                for name in EncodedLinks._VIEWS:  # (the views die with the arrays)
+                    self.__dict__.pop(name, None)
+                load_library().hny_encoded_links_free(self._ep)
+                self._ep = None
+        except Exception:  # interpreter shutdown
+            pass
+
+    def encode_kv(self, index=0, with_items=False):
+        """Byte-exact (key, value) records in LMDB key order (hny_encode_kv_encoded): what Graph.encode_kv gives for
+        the Graph of the same builder."""
+        out = []
+
+        def sink(_ctx, k, kl, v, vl):
+            out.append((bytes(k[:kl]), bytes(v[:vl])))
+            return 0
+        cb = KV_SINK(sink)
+        it, _keep = _kv_items(self._items, with_items)
+        _check(load_library().hny_encode_kv_encoded(self._ep, C.byref(self._opts), C.byref(it), index,
+                                                    int(with_items), cb, None))
+        return out
+
+    def write_lmdb(self, path, index=0, with_items=True, name=None, page_size=0, map_size=0):
+        """The records straight into an LMDB `data.mdb`: hny_encode_kv_encoded with hny_lmdb_writer_put as its sink
+        (the Links values go from the downloaded buffer into the pages, no Python in the record loop)."""
+        L = load_library()
+        w = LmdbWriter(path, name, page_size, map_size)
+        it, _keep = _kv_items(self._items, with_items)
+        sink = C.cast(L.hny_lmdb_writer_put, KV_SINK)
+        try:
+            _check(L.hny_encode_kv_encoded(self._ep, C.byref(self._opts), C.byref(it), index, int(with_items), sink,
+                                           w.handle))
         except Exception:
             w.abort()
             raise
@@ -1200,6 +1295,12 @@ class Builder:
         gp = C.POINTER(GraphStruct)()
         _check(load_library().hny_builder_finish(self._h, C.byref(gp)))
         return Graph(gp, self.opts, self.items)
+
+    def finish_encoded(self):
+        """hny_builder_finish_encoded: the Links records with their values serialised on the device"""
+        ep = C.POINTER(EncodedLinksStruct)()
+        _check(load_library().hny_builder_finish_encoded(self._h, C.byref(ep)))
+        return EncodedLinks(ep, self.opts, self.items)
 
     # -- resident updates (hny_builder_create_update / hny_builder_update, DESIGN.md §3c) --------------
     def _update_struct(self, upsert_ids, vectors, codes, headers, delete_ids, levels, seed):

@@ -363,17 +363,20 @@ class Writer:
             self.db.kv = snapshot
             raise
 
-    def build(self, levels=None, relink_all_items=False, rng=None, **opts):
+    def build(self, levels=None, relink_all_items=False, rng=None, encoded_links=False, **opts):
         """Writer::build (writer.rs:521-603).  `levels`: optional {item id: level} for the items that
-        get (re)inserted, instead of drawing them from StdRng::seed_from_u64(self.seed)."""
+        get (re)inserted, instead of drawing them from StdRng::seed_from_u64(self.seed).
+        encoded_links: the write paths that store every Links record take them from Builder.finish_encoded (their
+        values serialised on the device) and the build returns that EncodedLinks instead of a Graph; the paths that
+        store a delta are not affected.  The records written are the same either way."""
         snapshot = dict(self.db.kv)  # writer.rs:521-603 runs in the caller's RwTxn: an error (cancel,
         try:                         # unsupported, device, OOM) aborts it and nothing is changed
-            return self._build(levels, relink_all_items, rng, opts)
+            return self._build(levels, relink_all_items, rng, opts, bool(encoded_links))
         except BaseException:
             self.db.kv = snapshot
             raise
 
-    def _build(self, levels, relink_all_items, rng, opts):
+    def _build(self, levels, relink_all_items, rng, opts, encoded=False):
         db, index = self.db, self.index
         meta = db.metadata(index)
         indexed = set(meta["items"].tolist()) if meta else set()
@@ -396,17 +399,19 @@ class Writer:
         if rng is not None and levels is None:  # get_random_level per to_insert id, ascending (hnsw.rs:142-149)
             levels = dict(zip(to_insert, rng.draw_levels(kw["M"], len(to_insert)).tolist()))
         if self.resident:
-            g = self._build_resident(meta, indexed, ids, to_insert, to_delete, levels, relink_all_items, kw)
+            g = self._build_resident(meta, indexed, ids, to_insert, to_delete, levels, relink_all_items, kw, encoded)
         else:
-            g, _ = self._build_all_records(meta, ids, to_insert, to_delete, levels, kw, keep_builder=False)
+            g, _ = self._build_all_records(meta, ids, to_insert, to_delete, levels, kw, keep_builder=False,
+                                           encoded=encoded)
         db.build_generation[index] = db.build_generation.get(index, 0) + 1
         self.last_graph = g
         return g
 
-    def _build_all_records(self, meta, ids, to_insert, to_delete, levels, kw, keep_builder):
+    def _build_all_records(self, meta, ids, to_insert, to_delete, levels, kw, keep_builder, encoded=False):
         """every item read from the store, the stored graph as `prev`, and every Links record written back.
         keep_builder: build stepwise on a Builder and return it alive (the resident Writer keeps it) instead of
-        the one-call hny_build / hny_build_incremental; the graphs are the same."""
+        the one-call hny_build / hny_build_incremental; the graphs are the same.  encoded: stepwise as well, and
+        the records come from finish_encoded()."""
         db, index = self.db, self.index
         items = db.item_set(index, ids, self.dimensions)
         prev = _StoredGraph(db, index)
@@ -414,14 +419,14 @@ class Writer:
         if levels is not None:
             items.levels = np.array([levels[int(i)] for i in (ids if fresh else to_insert)], np.uint8)
         b = None
-        if not keep_builder:
+        if not keep_builder and not encoded:
             g = capi.build(items, **kw) if fresh else capi.build_incremental(items, prev, to_insert, to_delete, **kw)
         else:
             b = capi.Builder(items, **kw) if fresh else capi.Builder(items, prev=prev, to_insert=to_insert,
                                                                      to_delete=to_delete, **kw)
             try:
                 b.run()
-                g = b.finish()
+                g = b.finish_encoded() if encoded else b.finish()
             except BaseException:
                 b.close()
                 raise
@@ -437,9 +442,12 @@ class Writer:
             if b is not None:
                 b.close()
             raise
+        if b is not None and not keep_builder:
+            b.close()
+            b = None
         return g, b
 
-    def _build_resident(self, meta, indexed, ids, to_insert, to_delete, levels, relink_all_items, kw):
+    def _build_resident(self, meta, indexed, ids, to_insert, to_delete, levels, relink_all_items, kw, encoded=False):
         """_build with the builder kept in HBM.  The held builder is updated in place (hny_builder_update) and the
         write-back applies the delta when (1) the options and the distance are the ones it was made with, (2) it
         indexes exactly what the Metadata record says is indexed, and (3) no other build has touched this index of
@@ -449,7 +457,8 @@ class Writer:
         db, index = self.db, self.index
         opts_key = dict({k: v for k, v in kw.items() if k != "seed"}, metric=db.distance.value)
         if self._rb_change is not None:
-            g = self._build_changed_distance(meta, indexed, ids, to_insert, to_delete, levels, relink_all_items, kw, opts_key)
+            g = self._build_changed_distance(meta, indexed, ids, to_insert, to_delete, levels, relink_all_items, kw, opts_key,
+                                             encoded)
             if g is not None:
                 self._rb_ids, self._rb_gen = ids, db.build_generation.get(index, 0) + 1
                 return g
@@ -470,13 +479,15 @@ class Writer:
             self.last_delta = d
         else:
             self.close()
-            g, self._rb = self._build_all_records(meta, ids, to_insert, to_delete, levels, kw, keep_builder=True)
+            g, self._rb = self._build_all_records(meta, ids, to_insert, to_delete, levels, kw, keep_builder=True,
+                                                  encoded=encoded)
             self._rb_kw = opts_key
         self._rb_ids, self._rb_gen = ids, db.build_generation.get(index, 0) + 1
         return g
 
 
-    def _build_changed_distance(self, meta, indexed, ids, to_insert, to_delete, levels, relink_all_items, kw, opts_key):
+    def _build_changed_distance(self, meta, indexed, ids, to_insert, to_delete, levels, relink_all_items, kw, opts_key,
+                                encoded=False):
         """the first build after a resident prepare_changing_distance: hny_builder_create_changed_distance on the
         held builder, the items added, overwritten or deleted since travelling as its update.  The store gets the
         delta (kept-links pairs) or every record (the others).  Returns None, with the held builder released, when
@@ -507,7 +518,7 @@ class Writer:
                                                 codes=up.codes, headers=up.headers, delete_ids=to_delete)
         try:
             succ.run()
-            g = succ.finish()
+            g = succ.finish_encoded() if encoded and not keeps else succ.finish()
             if keeps:
                 d = succ.finish_delta()
                 for item, layer in d.removed_keys():  # delete_links_from_db (writer.rs:692-718)

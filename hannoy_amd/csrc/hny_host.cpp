@@ -353,6 +353,10 @@ struct hny_builder {
   std::vector<uint64_t> rec_first;
   std::vector<uint32_t> rec_item_t;
   std::vector<uint8_t> rec_layer_t;
+  // ... and on the device for hny_builder_finish_encoded: the list of every record (for_each_record's `list`) and
+  // its layer, uploaded by the first such call
+  DevBuf<u32> d_rec_list;
+  DevBuf<unsigned char> d_rec_layer;
   std::vector<int32_t> upper_idx;
   uint32_t max_level = 0, n_upper = 0;
   LaunchShape shape{64, 1};
@@ -2722,6 +2726,110 @@ int hny_builder_finish(hny_builder *b, hny_graph **out) {
   return HNY_OK;
 }
 
+// ---- encoded export: the Links values serialised on the device (hny_export.hip) ----
+void hny_encoded_links_free(hny_encoded_links *e) {
+  if (!e) return;
+  free((void *)e->rec_item);
+  free((void *)e->rec_layer);
+  free((void *)e->entry_points);
+  if (e->val_offset) (void)hipHostFree((void *)e->val_offset);
+  if (e->values) (void)hipHostFree((void *)e->values);
+  free(e);
+}
+// the record table on the device, next to the host's (ensure_record_table): made once, kept with the builder
+static int ensure_device_record_table(hny_builder *b, unsigned nt) {
+  const uint64_t nrec = b->rec_first[b->n];
+  if (b->d_rec_list.p || !nrec) return HNY_OK;
+  std::vector<u32> list(nrec);
+  run_split(nt, b->n, [&](uint64_t lo, uint64_t hi) {
+    for (uint32_t s = (uint32_t)lo; s < hi; s++) {
+      uint64_t r = b->rec_first[s];
+      for_each_record(b, s, [&](uint32_t, size_t li) { list[r++] = (u32)li; });
+    }
+  });
+  HIP_TRY(b->d_rec_list.alloc(nrec));
+  HIP_TRY(b->d_rec_layer.alloc(nrec));
+  HIP_TRY(hipMemcpy(b->d_rec_list.p, list.data(), nrec * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b->d_rec_layer.p, b->rec_layer_t.data(), nrec, hipMemcpyHostToDevice));
+  return HNY_OK;
+}
+
+int hny_builder_finish_encoded(hny_builder *b, hny_encoded_links **out) {
+  if (!b || !out) return fail(HNY_ERR_INVALID_ARG, "null argument");
+  *out = nullptr;
+  if (b->pos < b->order.size() || b->in_batch) return fail(HNY_ERR_INVALID_ARG, "build not finished");
+  if (std::max(b->o.M, b->o.M0) > HNY_EXPORT_MAX_CAP)
+    return fail(HNY_ERR_UNSUPPORTED, "lists of more than %u entries may need bitmap containers", HNY_EXPORT_MAX_CAP);
+  u64 stats[ST_COUNT] = {0};
+  double t0 = 0;
+  if (int rc = export_begin(b, stats, &t0)) return rc;
+  const uint32_t n = b->n;
+  const unsigned nt = export_shares(n);
+  ensure_record_table(b, nt);
+  if (int rc = ensure_device_record_table(b, nt)) return rc;
+  const uint64_t nrec = b->rec_first[n];
+  if (n && b->ids[n - 1] != n - 1 && !b->d_item_ids.p) { // slot != id: the table the filters and the range search share
+    HIP_TRY(b->d_item_ids.alloc(n));
+    HIP_TRY(hipMemcpy(b->d_item_ids.p, b->ids.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+  }
+  std::unique_ptr<hny_encoded_links, void (*)(hny_encoded_links *)> eh(
+      (hny_encoded_links *)calloc(1, sizeof(hny_encoded_links)), hny_encoded_links_free);
+  hny_encoded_links *e = eh.get();
+  if (!e) return fail(HNY_ERR_OOM, "out of host memory for %llu records", (unsigned long long)nrec);
+  // sizes -> offsets (one more element than records: the last offset is the total) -> values
+  DevBuf<u64> d_sizes, d_off;
+  DevBuf<unsigned char> d_tmp, d_values;
+  HIP_TRY(d_sizes.alloc(nrec + 1));
+  HIP_TRY(d_off.alloc(nrec + 1));
+  EncodeLinksArgs a{};
+  a.l0_ids = b->d_l0_ids.p, a.up_ids = b->d_up_ids.p, a.cnt0 = b->d_fin_cnt0.p, a.cntu = b->d_fin_cntu.p;
+  a.item_ids = n && b->ids[n - 1] != n - 1 ? b->d_item_ids.p : nullptr;
+  a.n = n, a.M = b->o.M, a.M0 = b->o.M0;
+  a.rec_list = b->d_rec_list.p, a.rec_layer = b->d_rec_layer.p, a.n_recs = nrec;
+  a.sizes = d_sizes.p, a.off = d_off.p;
+  HIP_TRY(hipMemsetAsync(d_sizes.p + nrec, 0, 8, b->stream));
+  HIP_TRY(hnyk_encode_links_sizes(a, b->stream));
+  size_t tmp_bytes = 0;
+  HIP_TRY(hnyk_exclusive_scan_u64(nullptr, &tmp_bytes, d_sizes.p, d_off.p, nrec + 1, b->stream));
+  HIP_TRY(d_tmp.alloc(std::max<size_t>(tmp_bytes, 16)));
+  HIP_TRY(hnyk_exclusive_scan_u64(d_tmp.p, &tmp_bytes, d_sizes.p, d_off.p, nrec + 1, b->stream));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  u64 total = 0;
+  HIP_TRY(hipMemcpy(&total, d_off.p + nrec, 8, hipMemcpyDeviceToHost));
+  HIP_TRY(d_values.alloc(std::max<size_t>(total, 16)));
+  a.values = d_values.p;
+  HIP_TRY(hnyk_encode_links_emit(a, b->stream));
+  // the host's share while the emit runs: the pinned arrays of the result, the record table, the entry points
+  HIP_TRY(hipHostMalloc((void **)&e->val_offset, (nrec + 1) * 8, hipHostMallocDefault));
+  HIP_TRY(hipHostMalloc((void **)&e->values, std::max<size_t>(total, 16), hipHostMallocDefault));
+  uint32_t *rec_item = (uint32_t *)malloc(std::max<uint64_t>(nrec, 1) * 4);
+  uint8_t *rec_layer = (uint8_t *)malloc(std::max<uint64_t>(nrec, 1));
+  e->rec_item = rec_item, e->rec_layer = rec_layer;
+  e->entry_points = entry_point_ids(b);
+  if (!rec_item || !rec_layer || !e->entry_points)
+    return fail(HNY_ERR_OOM, "out of host memory for %llu records", (unsigned long long)nrec);
+  memcpy(rec_item, b->rec_item_t.data(), nrec * 4);
+  memcpy(rec_layer, b->rec_layer_t.data(), nrec);
+  e->n_records = nrec;
+  e->n_entry_points = (uint32_t)b->entry_points.size();
+  e->max_level = b->max_level;
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  const double t1 = now_s();
+  HIP_TRY(hipMemcpyAsync((void *)e->val_offset, d_off.p, (nrec + 1) * 8, hipMemcpyDeviceToHost, b->stream));
+  if (total) HIP_TRY(hipMemcpyAsync((void *)e->values, d_values.p, total, hipMemcpyDeviceToHost, b->stream));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  const double t2 = now_s();
+  e->n_links_added = stats[ST_LINKS];
+  e->n_evals_walk = stats[ST_EVALS_WALK];
+  e->n_batches = b->n_batches;
+  e->t_device_s = t1 - t0;
+  e->t_download_s = t2 - t1;
+  e->t_export_s = t2 - t0;
+  e->bytes_downloaded = (nrec + 1) * 8 + total;
+  *out = eh.release();
+  return HNY_OK;
+}
+
 extern "C" int hny_internal_build_multi(const hny_build_opts *opts, const hny_items *items, const uint32_t *to_insert,
                                         uint64_t n_insert, const uint32_t *to_delete, uint64_t n_delete,
                                         const hny_prev_graph *prev, hny_graph **out); // hny_multi.cpp
@@ -2903,6 +3011,7 @@ extern "C" int hny_internal_lds_layout(int family, const uint32_t p[4], uint64_t
     case LDS_FILL_GAPS: (void)fill_gaps_lds(c, p[0]); break;
     case LDS_PRUNE_N8: (void)prune_n8_lds(c, p[0], p[1], (int)p[2]); break;
     case LDS_APPLY_N8: (void)apply_n8_lds(c, p[0], (int)p[1]); break;
+    case LDS_ENCODE_LINKS: (void)encode_links_lds(c, p[0], p[1]); break;
     default: return fail(HNY_ERR_INVALID_ARG, "hny_internal_lds_layout: no such kernel family");
   }
   if (c.n_spans > *n) return fail(HNY_ERR_INVALID_ARG, "hny_internal_lds_layout: too few spans");
@@ -5096,9 +5205,12 @@ static const char *metric_name(int m) {
   return names[m];
 }
 
-int hny_encode_kv(const hny_graph *g, const hny_build_opts *opts, const hny_items *items,
-                  uint16_t index, int with_items, hny_kv_sink sink, void *ctx) {
-  if (!g || !opts || !items || !sink) return fail(HNY_ERR_INVALID_ARG, "null argument");
+// the stream of hny_encode_kv / hny_encode_kv_encoded: Metadata, Version, the Links records (`links(key)` emits
+// them in record order, through `key`), then the Item records
+extern "C++" template <class LinksFn>
+static int encode_kv_stream(const uint32_t *entry_points, uint32_t n_entry_points, uint32_t max_level,
+                            const hny_build_opts *opts, const hny_items *items, uint16_t index, int with_items,
+                            hny_kv_sink sink, void *ctx, LinksFn &&links) {
   if (opts->metric < 0 || opts->metric > HNY_BQ_MANHATTAN) return fail(HNY_ERR_INVALID_ARG, "bad metric");
   uint8_t key[8];
   std::vector<uint8_t> val;
@@ -5112,12 +5224,12 @@ int hny_encode_kv(const hny_graph *g, const hny_build_opts *opts, const hny_item
   roaring_append(rb, items->ids, items->n);
   for (int k = 3; k >= 0; k--) val.push_back((uint8_t)((uint32_t)rb.size() >> (8 * k)));
   val.insert(val.end(), rb.begin(), rb.end());
-  for (uint32_t i = 0; i < g->n_entry_points; i++) { // ItemIds::raw_bytes: native-endian u32
+  for (uint32_t i = 0; i < n_entry_points; i++) { // ItemIds::raw_bytes: native-endian u32
     uint8_t e[4];
-    memcpy(e, &g->entry_points[i], 4);
+    memcpy(e, &entry_points[i], 4);
     val.insert(val.end(), e, e + 4);
   }
-  val.push_back((uint8_t)g->max_level);
+  val.push_back((uint8_t)max_level);
   put_key(index, 0, 0, 0, key);
   if (int rc = emit()) return rc;
   // Version (version.rs:36-48): crate version 0.1.3
@@ -5127,12 +5239,7 @@ int hny_encode_kv(const hny_graph *g, const hny_build_opts *opts, const hny_item
   put_key(index, 0, 1, 0, key);
   if (int rc = emit()) return rc;
   // Links (node.rs:141-144)
-  for (uint64_t r = 0; r < g->n_records; r++) {
-    val.assign(1, 1);
-    roaring_append(val, g->neighbours + g->rec_offset[r], g->rec_offset[r + 1] - g->rec_offset[r]);
-    put_key(index, 2, g->rec_item[r], g->rec_layer[r], key);
-    if (int rc = emit()) return rc;
-  }
+  if (int rc = links(key)) return rc;
   // Items (node.rs:136-140)
   if (with_items) {
     const size_t vb = vec_bytes(opts->metric, opts->dim), hb = items->header_size;
@@ -5145,6 +5252,39 @@ int hny_encode_kv(const hny_graph *g, const hny_build_opts *opts, const hny_item
     }
   }
   return HNY_OK;
+}
+
+int hny_encode_kv(const hny_graph *g, const hny_build_opts *opts, const hny_items *items,
+                  uint16_t index, int with_items, hny_kv_sink sink, void *ctx) {
+  if (!g || !opts || !items || !sink) return fail(HNY_ERR_INVALID_ARG, "null argument");
+  return encode_kv_stream(g->entry_points, g->n_entry_points, g->max_level, opts, items, index, with_items, sink, ctx,
+                          [&](uint8_t *key) {
+                            std::vector<uint8_t> val;
+                            for (uint64_t r = 0; r < g->n_records; r++) {
+                              val.assign(1, 1);
+                              roaring_append(val, g->neighbours + g->rec_offset[r], g->rec_offset[r + 1] - g->rec_offset[r]);
+                              put_key(index, 2, g->rec_item[r], g->rec_layer[r], key);
+                              if (int rc = sink(ctx, key, 8, val.data(), val.size())) return rc;
+                            }
+                            return (int)HNY_OK;
+                          });
+}
+
+// the Links values come serialised (hny_builder_finish_encoded, or a caller's own struct): handed to the sink from
+// where they lie, nothing copied, nothing encoded again; no device call
+int hny_encode_kv_encoded(const hny_encoded_links *e, const hny_build_opts *opts, const hny_items *items,
+                          uint16_t index, int with_items, hny_kv_sink sink, void *ctx) {
+  if (!e || !opts || !items || !sink) return fail(HNY_ERR_INVALID_ARG, "null argument");
+  return encode_kv_stream(e->entry_points, e->n_entry_points, e->max_level, opts, items, index, with_items, sink, ctx,
+                          [&](uint8_t *key) {
+                            for (uint64_t r = 0; r < e->n_records; r++) {
+                              put_key(index, 2, e->rec_item[r], e->rec_layer[r], key);
+                              if (int rc = sink(ctx, key, 8, e->values + e->val_offset[r],
+                                                (size_t)(e->val_offset[r + 1] - e->val_offset[r])))
+                                return rc;
+                            }
+                            return (int)HNY_OK;
+                          });
 }
 
 } // extern "C"

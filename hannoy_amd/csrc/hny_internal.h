@@ -397,7 +397,7 @@ struct LdsCarve {
 // every form of these functions tried moved the register allocation of instances that sit on a measured budget.
 enum LdsFamily { // hny_internal_lds_layout: the family, and its sizes in the order of the function's parameters
   LDS_HEAP_WALK, LDS_NNS, LDS_NNS_LINEAR, LDS_EXACT_TOPK, LDS_EXACT_SCORES, LDS_PRUNE, LDS_APPLY, LDS_FILL_GAPS,
-  LDS_PRUNE_N8, LDS_APPLY_N8
+  LDS_PRUNE_N8, LDS_APPLY_N8, LDS_ENCODE_LINKS
 };
 
 // k_walk_heap, k_nns<.., true>: the scratch of a distance pass and the entry points
@@ -551,6 +551,17 @@ HNY_LDS_FN ApplyN8Lds apply_n8_lds(LdsCarve &c, u32 row_stride, int SL) {
   L.lk = c.take<u64>(HNY_MAX_CAP);
   L.sorted = c.take<u64>(HNY_MAX_CAP);
   L.n = n8_lds(c, row_stride, SL);
+  return L;
+}
+// k_links_emit (hny_export.hip): one window of the workgroup's output range, and the byte offsets of its records
+struct EncodeLinksLds {
+  unsigned char *stage; // [stage_bytes] stored to global memory as 16-byte words
+  u64 *off;             // [recs + 1]
+};
+HNY_LDS_FN EncodeLinksLds encode_links_lds(LdsCarve &c, u32 stage_bytes, u32 recs) {
+  EncodeLinksLds L;
+  L.stage = c.take_rows(stage_bytes);
+  L.off = c.take<u64>((size_t)recs + 1);
   return L;
 }
 // bytes of a layout: HNY_LDS_BYTES(prune_lds, rcap, capmax) runs the function on a null cursor
@@ -751,3 +762,25 @@ hipError_t hnyk_scatter_rows(const unsigned char *src, const float *src_norms, c
 hipError_t hnyk_move_lists(const MoveListsArgs &a, hipStream_t st);
 hipError_t hnyk_diff_records(const u32 *fin, const u32 *old, unsigned char *flag, u32 n_lists, u32 cap, hipStream_t st);
 hipError_t hnyk_gather_lists(const GatherListsArgs &a, hipStream_t st);
+
+// ---- encoded export (hny_export.hip): the Links values of a table of records, serialised on the device ----
+#define HNY_EXPORT_RECS_PER_WG 64u    // consecutive records a workgroup of k_links_emit takes: one output range
+#define HNY_EXPORT_STAGE_BYTES 8192u  // of that range, assembled in LDS and stored at a time (a multiple of 16)
+#define HNY_EXPORT_GRID_CAP 2048u     // blocks of either kernel; the rest is a grid stride
+#define HNY_EXPORT_MAX_CAP 4096u      // a longer list could need a bitmap container, which these kernels do not write
+struct EncodeLinksArgs {
+  const u32 *l0_ids, *up_ids;     // finalised lists: ascending slots, [.][M0] / [.][M]
+  const u32 *cnt0, *cntu;         // their counts
+  const u32 *item_ids;            // [n] slot -> item id, null = the identity
+  u32 n, M, M0;
+  const u32 *rec_list;            // [n_recs] the record's list: a slot (layer 0) or an index into the upper lists
+  const unsigned char *rec_layer; // [n_recs]
+  u64 n_recs;
+  u64 *sizes;                     // k_links_sizes: [n_recs] bytes of every value
+  const u64 *off;                 // k_links_emit: [n_recs + 1] the exclusive scan of sizes
+  unsigned char *values;          // k_links_emit: [off[n_recs]], 16-byte aligned
+  u32 lg_group, n_strides;        // set by the launchers: log2 of the lanes per record, their steps over a list
+};
+hipError_t hnyk_encode_links_sizes(const EncodeLinksArgs &a, hipStream_t st);
+hipError_t hnyk_encode_links_emit(const EncodeLinksArgs &a, hipStream_t st);
+hipError_t hnyk_exclusive_scan_u64(void *temp, size_t *temp_bytes, const u64 *in, u64 *out, size_t n, hipStream_t st);

@@ -691,6 +691,34 @@ typedef int (*hny_kv_sink)(void *ctx, const uint8_t *key, size_t key_len, const 
 int hny_encode_kv(const hny_graph *g, const hny_build_opts *opts, const hny_items *items,
                   uint16_t index, int with_items, hny_kv_sink sink, void *ctx);
 
+/* ---- encoded export: the Links records of a finished builder with their values serialised on
+ * the device — what hny_builder_finish + hny_encode_kv produce, without the lists padded to M0 crossing the bus and
+ * without the host's per-link loop.  Library-owned, read-only for the caller; not part of hny_abi_sizes. */
+typedef struct {
+  uint64_t n_records;          /* as hny_graph: one per (item, layer), sorted by (item id, layer) */
+  const uint32_t *rec_item;
+  const uint8_t *rec_layer;
+  const uint64_t *val_offset;  /* n_records + 1 byte offsets into values */
+  const uint8_t *values;       /* per record: tag 0x01 | RoaringBitmap::serialize_into of the neighbour ids
+                                * (node.rs:141-144), 1 + 8 + 8 nc + 2 c bytes for c ids in nc high-16 groups */
+  const uint32_t *entry_points;
+  uint32_t n_entry_points, max_level;
+  uint64_t n_links_added, n_evals_walk, n_batches; /* as in the hny_graph of the same builder */
+  double t_export_s;           /* host wall clock of the call, of which ... */
+  double t_device_s;           /* ... the sizes, scan and emit kernels (finalising the lists included) */
+  double t_download_s;         /* ... and the copy of val_offset and values to (pinned) host memory */
+  uint64_t bytes_downloaded;
+} hny_encoded_links;
+/* Accepts exactly the builders hny_builder_finish accepts and refuses the others with its codes (*out = NULL); the
+ * builder stays usable, and neither call changes what the other returns, in either order. */
+int hny_builder_finish_encoded(hny_builder *b, hny_encoded_links **out);
+void hny_encoded_links_free(hny_encoded_links *e); /* NULL is fine */
+/* The stream hny_encode_kv(g, ...) emits for the hny_graph g of the same builder, byte for byte: Metadata, Version,
+ * every Links record (key from rec_item / rec_layer, value handed to the sink straight from `values`), then
+ * (with_items) the Item records.  No device call: `e` may be a struct the caller filled in. */
+int hny_encode_kv_encoded(const hny_encoded_links *e, const hny_build_opts *opts, const hny_items *items,
+                          uint16_t index, int with_items, hny_kv_sink sink, void *ctx);
+
 /* ---- LMDB writeback: the KV stream above as an LMDB environment file
  * (`<dir>/data.mdb`) that heed/LMDB can open — what `db.put` produces in the reference's write
  * loop (hnsw.rs:195-213, writer.rs:462-480, 585-600) through heed 0.22 / LMDB 0.9 (third party,
