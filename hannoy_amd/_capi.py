@@ -46,6 +46,7 @@ EXPORTED = [
     "hny_builder_exact_range", "hny_builder_exact_range_f32", "hny_builder_exact_range_count",
     "hny_builder_exact_range_count_f32", "hny_range_result_free",
     "hny_builder_finish_encoded", "hny_encoded_links_free", "hny_encode_kv_encoded",
+    "hny_builder_finish_delta_encoded", "hny_encoded_delta_free",
 ]
 ERR_IO = -9
 NNS_NONE = 0xFFFFFFFF  # by_item: the reference returns None
@@ -256,6 +257,13 @@ class EncodedLinksStruct(C.Structure):
                 ("bytes_downloaded", C.c_uint64)]
 
 
+class EncodedDeltaStruct(C.Structure):
+    """hny_encoded_delta: library-owned and read-only here, not part of hny_abi_sizes"""
+    _fields_ = [("links", EncodedLinksStruct), ("n_removed", C.c_uint64),
+                ("removed_item", C.POINTER(C.c_uint32)), ("removed_layer", C.POINTER(C.c_uint8)),
+                ("n_records_total", C.c_uint64)]
+
+
 class Batch(C.Structure):
     _fields_ = [("first", C.c_uint64), ("count", C.c_uint32), ("level", C.c_uint32),
                 ("n_layers", C.c_uint32), ("sel_stride_u64", C.c_uint32)]
@@ -445,6 +453,10 @@ def load_library():
     L.hny_encode_kv_encoded.restype = C.c_int
     L.hny_encode_kv_encoded.argtypes = [C.POINTER(EncodedLinksStruct), C.POINTER(BuildOpts), C.POINTER(Items),
                                         C.c_uint16, C.c_int, KV_SINK, vp]
+    L.hny_builder_finish_delta_encoded.restype = C.c_int
+    L.hny_builder_finish_delta_encoded.argtypes = [vp, C.POINTER(C.POINTER(EncodedDeltaStruct))]
+    L.hny_encoded_delta_free.restype = None
+    L.hny_encoded_delta_free.argtypes = [C.POINTER(EncodedDeltaStruct)]
     L.hny_abi_sizes.restype = C.c_uint32
     L.hny_abi_sizes.argtypes = [C.POINTER(C.c_uint32), C.c_uint32]
     _check_abi(L)
@@ -878,8 +890,10 @@ class EncodedLinks:
 
     _VIEWS = ("rec_item", "rec_layer", "val_offset", "values")
 
-    def __init__(self, ep, opts=None, items=None):
+    def __init__(self, ep, opts=None, items=None, owner=None):
+        """owner: `ep` points into a struct that another object frees (EncodedDelta): this view frees nothing"""
         e = ep.contents
+        self._owner = owner
         for f in ("max_level", "n_links_added", "n_evals_walk", "n_batches", "t_export_s", "t_device_s",
                   "t_download_s", "bytes_downloaded"):
             setattr(self, f, getattr(e, f))
@@ -907,8 +921,9 @@ class EncodedLinks:
             if getattr(self, "_ep", None) is not None:
                 for name in EncodedLinks._VIEWS:  # (the views die with the arrays)
                     self.__dict__.pop(name, None)
-                load_library().hny_encoded_links_free(self._ep)
-                self._ep = None
+                if getattr(self, "_owner", None) is None:
+                    load_library().hny_encoded_links_free(self._ep)
+                self._ep = self._owner = None
         except Exception:  # interpreter shutdown
             pass
 
@@ -995,6 +1010,63 @@ class GraphDelta:
             return 0
         cb = KV_SINK(sink)
         _check(load_library().hny_encode_kv(C.byref(g), C.byref(self._opts), C.byref(it), index, 0, cb, None))
+        return out
+
+
+class EncodedDelta:
+    """hny_encoded_delta (Builder.finish_delta_encoded): GraphDelta's records with their values serialised on the
+    device.  `links` is an EncodedLinks view of the new / changed records (it frees nothing); its `rec_item`,
+    `rec_layer`, `val_offset`, `values`, `entry_points`, `max_level`, counters and timings are attributes of this
+    object too.  `removed_item` / `removed_layer` are the keys to delete.  All valid while this object lives."""
+
+    _LINKS = EncodedLinks._VIEWS + ("entry_points", "max_level", "n_links_added", "n_evals_walk", "n_batches",
+                                    "t_export_s", "t_device_s", "t_download_s", "bytes_downloaded")
+
+    def __init__(self, dp, opts=None):
+        self._dp = dp  # first: whatever fails below, __del__ frees the struct
+        d = dp.contents
+        nm = d.n_removed
+        self.n_records_total = d.n_records_total
+        self.removed_item = np.ctypeslib.as_array(d.removed_item, (max(nm, 1),))[:nm]
+        self.removed_layer = np.ctypeslib.as_array(d.removed_layer, (max(nm, 1),))[:nm]
+        self.links = EncodedLinks(C.pointer(d.links), opts, None, owner=True)
+
+    def __getattr__(self, name):
+        if name not in EncodedDelta._LINKS or self.__dict__.get("links") is None:
+            raise AttributeError(name)
+        return getattr(self.links, name)
+
+    def __del__(self):
+        try:
+            if getattr(self, "_dp", None) is not None:
+                for name in ("removed_item", "removed_layer"):  # (the views die with the arrays)
+                    self.__dict__.pop(name, None)
+                links = self.__dict__.pop("links", None)
+                if links is not None:
+                    links.__del__()  # drops its views and its pointer into the struct
+                load_library().hny_encoded_delta_free(self._dp)
+                self._dp = None
+        except Exception:  # interpreter shutdown
+            pass
+
+    def removed_keys(self):
+        return [(int(i), int(l)) for i, l in zip(self.removed_item, self.removed_layer)]
+
+    def encode_kv(self, item_ids, index=0):
+        """What GraphDelta.encode_kv gives for the delta of the same builder (hny_encode_kv_encoded on `links`);
+        `item_ids`: every item of the index after the update, ascending (Metadata.items)"""
+        if np.ndim(item_ids) != 1:
+            raise HannoyError(ERR_INVALID_ARG, "EncodedDelta.encode_kv(item_ids, index): item_ids is a sequence of ids")
+        ids = u32_ids(item_ids)
+        it = Items(len(ids), _p(ids).value, None, 0, None, 0, None)
+        out = []
+
+        def sink(_ctx, k, kl, v, vl):
+            out.append((bytes(k[:kl]), bytes(v[:vl])))
+            return 0
+        cb = KV_SINK(sink)
+        _check(load_library().hny_encode_kv_encoded(self.links._ep, C.byref(self.links._opts), C.byref(it), index, 0,
+                                                    cb, None))
         return out
 
 
@@ -1344,18 +1416,23 @@ class Builder:
     def update(self, upsert_ids=(), vectors=None, codes=None, headers=None, delete_ids=(), levels=None, seed=42,
                full=True, delta=False):
         """hny_builder_update: this Builder becomes its successor (every batch + fill_gaps run); returns the complete
-        Graph, the GraphDelta, or (Graph, GraphDelta) as asked"""
+        Graph, the GraphDelta, or (Graph, GraphDelta) as asked.  delta="encoded": the delta is an EncodedDelta
+        (finish_delta_encoded on the successor, after hny_builder_update has returned: if that second call fails,
+        this Builder is the successor already and finish() / finish_delta() on it give what the update made)"""
         u, keep = self._update_struct(upsert_ids, vectors, codes, headers, delete_ids, levels, seed)
         gp, dp = C.POINTER(GraphStruct)(), C.POINTER(GraphDeltaStruct)()
         if self._borrowed:
             raise HannoyError(ERR_INVALID_ARG, "a borrowed replica cannot be replaced: use create_update()")
+        encoded = isinstance(delta, str)
+        if encoded and delta != "encoded":
+            raise HannoyError(ERR_INVALID_ARG, f"delta={delta!r}: True, False or \"encoded\"")
         _check(load_library().hny_builder_update(C.byref(self._h), C.byref(u), C.byref(gp) if full else None,
-                                                 C.byref(dp) if delta else None))
+                                                 C.byref(dp) if delta and not encoded else None))
         succ = self._successor(self._h, keep)
         self.items, self.incremental = succ.items, True
         succ._h = C.c_void_p()  # (the handle stays with this object)
         g = Graph(gp, self.opts, self.items) if full else None
-        d = GraphDelta(dp, self.opts) if delta else None
+        d = self.finish_delta_encoded() if encoded else GraphDelta(dp, self.opts) if delta else None
         return (g, d) if full and delta else g if full else d
 
     # -- resident change of distance (hny_builder_create_changed_distance, DESIGN.md §3c-2) ----------
@@ -1398,6 +1475,12 @@ class Builder:
         dp = C.POINTER(GraphDeltaStruct)()
         _check(load_library().hny_builder_finish_delta(self._h, C.byref(dp)))
         return GraphDelta(dp, self.opts)
+
+    def finish_delta_encoded(self):
+        """hny_builder_finish_delta_encoded: finish_delta's records with their values serialised on the device"""
+        dp = C.POINTER(EncodedDeltaStruct)()
+        _check(load_library().hny_builder_finish_delta_encoded(self._h, C.byref(dp)))
+        return EncodedDelta(dp, self.opts)
 
     def distances(self, slot_a, slot_b):
         a = np.ascontiguousarray(slot_a, np.uint32)

@@ -196,7 +196,7 @@ class Writer:
         self.last_graph = None
         # resident=True: the builder of the last build, the options it was made with and the items it indexes
         self.resident, self._rb, self._rb_kw, self._rb_ids, self._rb_gen = bool(resident), None, None, None, -1
-        self.last_delta = None  # resident: the GraphDelta of the last build that went through hny_builder_update
+        self.last_delta = None  # resident: the GraphDelta (encoded_links: EncodedDelta) of the last build that stored a delta
         # resident, between prepare_changing_distance and the next build: (old metric, the recoded codes, headers) of
         # the held builder's items — that build goes through hny_builder_create_changed_distance
         self._rb_change = None
@@ -367,8 +367,9 @@ class Writer:
         """Writer::build (writer.rs:521-603).  `levels`: optional {item id: level} for the items that
         get (re)inserted, instead of drawing them from StdRng::seed_from_u64(self.seed).
         encoded_links: the write paths that store every Links record take them from Builder.finish_encoded (their
-        values serialised on the device) and the build returns that EncodedLinks instead of a Graph; the paths that
-        store a delta are not affected.  The records written are the same either way."""
+        values serialised on the device) and the build returns that EncodedLinks instead of a Graph; the resident
+        paths that store a delta take the changed records from Builder.finish_delta_encoded, leave that EncodedDelta
+        in `last_delta` and return the Graph as before.  The records written are the same either way."""
         snapshot = dict(self.db.kv)  # writer.rs:521-603 runs in the caller's RwTxn: an error (cancel,
         try:                         # unsupported, device, OOM) aborts it and nothing is changed
             return self._build(levels, relink_all_items, rng, opts, bool(encoded_links))
@@ -467,7 +468,7 @@ class Writer:
             ups = db.item_set(index, np.array(to_insert, np.uint32), self.dimensions)
             lv = None if levels is None else np.array([levels[int(i)] for i in to_insert], np.uint8)
             g, d = self._rb.update(to_insert, codes=ups.codes, headers=ups.headers, delete_ids=to_delete, levels=lv,
-                                   seed=kw.get("seed", 42), full=True, delta=True)
+                                   seed=kw.get("seed", 42), full=True, delta="encoded" if encoded else True)
             try:  # the builder is its successor now: if the store cannot follow, the two no longer match
                 for item, layer in d.removed_keys():  # delete_links_from_db (writer.rs:692-718)
                     del db.kv[key(index, MODE_LINKS, item, layer)]
@@ -520,7 +521,7 @@ class Writer:
             succ.run()
             g = succ.finish_encoded() if encoded and not keeps else succ.finish()
             if keeps:
-                d = succ.finish_delta()
+                d = succ.finish_delta_encoded() if encoded else succ.finish_delta()
                 for item, layer in d.removed_keys():  # delete_links_from_db (writer.rs:692-718)
                     del db.kv[key(index, MODE_LINKS, item, layer)]
                 for k, v in d.encode_kv(ids, index):  # the changed Links records, Metadata, Version

@@ -4,7 +4,8 @@
 // every container is an array container and a value's length is 1 + 8 + 8 nc + 2 c for c neighbours in nc distinct
 // high-16 groups: a sizes pass, an exclusive scan (rocprim) and an emit pass.  No atomics, nothing depends on
 // scheduling: two runs give the same bytes.
-// Both passes take a table of records (list index + layer), not "every slot".
+// Both passes take a table of records (list index + layer), not "every slot": the full export hands them every
+// record, the delta export (§3c-4) the table that k_delta_count / k_delta_write below make of the changed ones.
 #include "hny_internal.h"
 #include <algorithm>
 #include <rocprim/device/device_scan.hpp>
@@ -153,7 +154,97 @@ __global__ __launch_bounds__(kBlock) void k_links_emit(EncodeLinksArgs a) {
   }
 }
 
+// ---- the delta's record table (hny_builder_finish_delta_encoded) ----
+// One slot per thread.  A slot owns at most 16 records, whose places follow from the scans alone: no atomics, two runs
+// give the same tables.  Both passes stream 2 + 2 (+ 4 + flags) bytes per slot, coalesced; the stores of a slot's few
+// records are scattered by nature (a record every ~1 / changed-fraction slots).
+
+// the flag of the record (s, l), l >= 1 (`up` = upper_idx[s]; the clamp keeps a bad index inside the array)
+__device__ __forceinline__ bool upper_flag(const DeltaTableArgs &a, int up, u32 l) {
+  const u64 at = (u64)a.n + (u64)(u32)up * a.up_layers + (l - 1u);
+  return a.flag[min(at, a.n_flags - 1u)] != 0;
+}
+
+// chg[s], cnt_chg[s], cnt_rm[s]
+__global__ __launch_bounds__(HNY_DELTA_BLOCK) void k_delta_count(DeltaTableArgs a) {
+  const u64 stride = (u64)gridDim.x * HNY_DELTA_BLOCK;
+  for (u64 s = (u64)blockIdx.x * HNY_DELTA_BLOCK + threadIdx.x; s < a.n; s += stride) {
+    const u32 om = a.old_mask[s], nm = a.new_mask[s];
+    u32 chg = nm & ~om; // a record the previous graph does not hold
+    const u32 both = nm & om;
+    if ((both & 1u) && a.flag[s]) chg |= 1u;
+    if (both >> 1) {
+      const int up = a.upper_idx[s];
+      for (u32 m = both >> 1, l = 1; m; m >>= 1, l++)
+        if ((m & 1u) && upper_flag(a, up, l)) chg |= 1u << l;
+    }
+    a.chg[s] = (unsigned short)chg;
+    a.cnt_chg[s] = (u64)__popc(chg);
+    a.cnt_rm[s] = (u64)__popc(om & ~nm);
+  }
+}
+
+// the tables, and how many entries this block stored (wrote[2 b], wrote[2 b + 1]): the host sums them against the
+// scans' totals
+__global__ __launch_bounds__(HNY_DELTA_BLOCK) void k_delta_write(DeltaTableArgs a) {
+  __shared__ u64 part[2][HNY_DELTA_BLOCK / 64];
+  const u64 stride = (u64)gridDim.x * HNY_DELTA_BLOCK;
+  u64 n_chg = 0, n_rm = 0;
+  for (u64 s = (u64)blockIdx.x * HNY_DELTA_BLOCK + threadIdx.x; s < a.n; s += stride) {
+    const u32 chg = a.chg[s], gone = (u32)a.old_mask[s] & ~(u32)a.new_mask[s];
+    if (!(chg | gone)) continue;
+    const u32 item = a.item_ids ? a.item_ids[s] : (u32)s;
+    if (chg) {
+      u64 r = a.off_chg[s];
+      const u64 r_end = a.off_chg[s + 1];
+      const u32 up = chg >> 1 ? (u32)a.upper_idx[s] : 0u;
+      for (u32 m = chg, l = 0; m && r < r_end; m >>= 1, l++)
+        if (m & 1u) {
+          a.rec_list[r] = l == 0 ? (u32)s : up * a.up_layers + (l - 1u);
+          a.rec_layer[r] = (unsigned char)l;
+          a.rec_item[r] = item;
+          r++, n_chg++;
+        }
+    }
+    if (gone) {
+      u64 q = a.off_rm[s];
+      const u64 q_end = a.off_rm[s + 1];
+      for (u32 m = gone, l = 0; m && q < q_end; m >>= 1, l++)
+        if (m & 1u) {
+          a.rm_item[q] = item;
+          a.rm_layer[q] = (unsigned char)l;
+          q++, n_rm++;
+        }
+    }
+  }
+  for (int d = 32; d; d >>= 1) {
+    n_chg += __shfl_down((unsigned long long)n_chg, d);
+    n_rm += __shfl_down((unsigned long long)n_rm, d);
+  }
+  if ((threadIdx.x & 63u) == 0u) part[0][threadIdx.x >> 6] = n_chg, part[1][threadIdx.x >> 6] = n_rm;
+  __syncthreads();
+  if (threadIdx.x < 2u) {
+    u64 t = 0;
+    for (u32 w = 0; w < HNY_DELTA_BLOCK / 64; w++) t += part[threadIdx.x][w];
+    a.wrote[2u * blockIdx.x + threadIdx.x] = t;
+  }
+}
+
 } // namespace
+
+static u32 delta_grid(u32 n) {
+  return (u32)std::min<u64>(((u64)n + HNY_DELTA_BLOCK - 1u) / HNY_DELTA_BLOCK, HNY_DELTA_GRID_CAP);
+}
+hipError_t hnyk_delta_table_count(const DeltaTableArgs &a, hipStream_t st) {
+  if (!a.n) return hipSuccess;
+  hipLaunchKernelGGL(k_delta_count, dim3(delta_grid(a.n)), dim3(HNY_DELTA_BLOCK), 0, st, a);
+  return hipGetLastError();
+}
+hipError_t hnyk_delta_table_write(const DeltaTableArgs &a, hipStream_t st) {
+  if (!a.n) return hipSuccess;
+  hipLaunchKernelGGL(k_delta_write, dim3(delta_grid(a.n)), dim3(HNY_DELTA_BLOCK), 0, st, a);
+  return hipGetLastError();
+}
 
 // lanes per record: the smallest power of two that covers the longest list, 8 .. 64
 static void set_shape(EncodeLinksArgs &a) {

@@ -357,6 +357,12 @@ struct hny_builder {
   // its layer, uploaded by the first such call
   DevBuf<u32> d_rec_list;
   DevBuf<unsigned char> d_rec_layer;
+  // ... and for hny_builder_finish_delta_encoded: per slot old_mask, then rec_mask_of ([2 n], as fixed as the
+  // table above), and the sum of the latter's bits.  Made only for a finished successor after fill_gaps, and nothing
+  // changes which records exist after that; a path that ever lets such a builder take more inserts has to release
+  // d_delta_masks together with rec_first and d_rec_list
+  DevBuf<unsigned short> d_delta_masks;
+  uint64_t delta_recs_total = 0;
   std::vector<int32_t> upper_idx;
   uint32_t max_level = 0, n_upper = 0;
   LaunchShape shape{64, 1};
@@ -2727,14 +2733,24 @@ int hny_builder_finish(hny_builder *b, hny_graph **out) {
 }
 
 // ---- encoded export: the Links values serialised on the device (hny_export.hip) ----
-void hny_encoded_links_free(hny_encoded_links *e) {
-  if (!e) return;
+static void encoded_links_release(hny_encoded_links *e) { // the arrays, not the struct
   free((void *)e->rec_item);
   free((void *)e->rec_layer);
   free((void *)e->entry_points);
   if (e->val_offset) (void)hipHostFree((void *)e->val_offset);
   if (e->values) (void)hipHostFree((void *)e->values);
+}
+void hny_encoded_links_free(hny_encoded_links *e) {
+  if (!e) return;
+  encoded_links_release(e);
   free(e);
+}
+void hny_encoded_delta_free(hny_encoded_delta *d) {
+  if (!d) return;
+  encoded_links_release(&d->links);
+  free((void *)d->removed_item);
+  free((void *)d->removed_layer);
+  free(d);
 }
 // the record table on the device, next to the host's (ensure_record_table): made once, kept with the builder
 static int ensure_device_record_table(hny_builder *b, unsigned nt) {
@@ -2754,6 +2770,80 @@ static int ensure_device_record_table(hny_builder *b, unsigned nt) {
   return HNY_OK;
 }
 
+// What hny_builder_finish_encoded and hny_builder_finish_delta_encoded share; the caller adds the table of records
+// (rec_list, rec_layer, n_recs) to encode_args' lists.  encode_enqueue: sizes -> offsets (one more element than
+// records: the last offset is the total) -> values, the emit enqueued and not waited for, e's pinned arrays allocated ...
+static EncodeLinksArgs encode_args(const hny_builder *b, const u32 *item_ids) {
+  EncodeLinksArgs a{};
+  a.l0_ids = b->d_l0_ids.p, a.up_ids = b->d_up_ids.p, a.cnt0 = b->d_fin_cnt0.p, a.cntu = b->d_fin_cntu.p;
+  a.item_ids = item_ids;
+  a.n = b->n, a.M = b->o.M, a.M0 = b->o.M0;
+  return a;
+}
+struct EncodeRun {
+  DevBuf<u64> d_sizes, d_off;
+  DevBuf<unsigned char> d_tmp, d_values;
+  u64 total = 0; // bytes of all values
+};
+static int encode_enqueue(hny_builder *b, EncodeLinksArgs &a, hny_encoded_links *e, EncodeRun &R) {
+  const uint64_t nrec = a.n_recs;
+  HIP_TRY(R.d_sizes.alloc(nrec + 1));
+  HIP_TRY(R.d_off.alloc(nrec + 1));
+  a.sizes = R.d_sizes.p, a.off = R.d_off.p;
+  HIP_TRY(hipMemsetAsync(R.d_sizes.p + nrec, 0, 8, b->stream));
+  HIP_TRY(hnyk_encode_links_sizes(a, b->stream));
+  size_t tmp_bytes = 0;
+  HIP_TRY(hnyk_exclusive_scan_u64(nullptr, &tmp_bytes, R.d_sizes.p, R.d_off.p, nrec + 1, b->stream));
+  HIP_TRY(R.d_tmp.alloc(std::max<size_t>(tmp_bytes, 16)));
+  HIP_TRY(hnyk_exclusive_scan_u64(R.d_tmp.p, &tmp_bytes, R.d_sizes.p, R.d_off.p, nrec + 1, b->stream));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  HIP_TRY(hipMemcpy(&R.total, R.d_off.p + nrec, 8, hipMemcpyDeviceToHost));
+  HIP_TRY(R.d_values.alloc(std::max<size_t>(R.total, 16)));
+  a.values = R.d_values.p;
+  HIP_TRY(hnyk_encode_links_emit(a, b->stream));
+  HIP_TRY(hipHostMalloc((void **)&e->val_offset, (nrec + 1) * 8, hipHostMallocDefault));
+  HIP_TRY(hipHostMalloc((void **)&e->values, std::max<size_t>(R.total, 16), hipHostMallocDefault));
+  return HNY_OK;
+}
+// ... encode_header: the fields that do not come from the device ...
+static int encode_header(const hny_builder *b, const u64 (&stats)[ST_COUNT], uint64_t nrec, hny_encoded_links *e) {
+  e->entry_points = entry_point_ids(b);
+  if (!e->entry_points) return fail(HNY_ERR_OOM, "out of host memory for %llu records", (unsigned long long)nrec);
+  e->n_records = nrec;
+  e->n_entry_points = (uint32_t)b->entry_points.size();
+  e->max_level = b->max_level;
+  e->n_links_added = stats[ST_LINKS];
+  e->n_evals_walk = stats[ST_EVALS_WALK];
+  e->n_batches = b->n_batches;
+  return HNY_OK;
+}
+// ... encode_download: the copies of val_offset and values, enqueued ...
+static int encode_download(hny_builder *b, const EncodeRun &R, hny_encoded_links *e) {
+  const uint64_t nrec = R.d_sizes.n - 1;
+  HIP_TRY(hipMemcpyAsync((void *)e->val_offset, R.d_off.p, (nrec + 1) * 8, hipMemcpyDeviceToHost, b->stream));
+  if (R.total) HIP_TRY(hipMemcpyAsync((void *)e->values, R.d_values.p, R.total, hipMemcpyDeviceToHost, b->stream));
+  e->bytes_downloaded = (nrec + 1) * 8 + R.total;
+  return HNY_OK;
+}
+// ... and the clocks: t0 the call began, t1 the device was done, t2 the copies had landed
+static void encode_timings(hny_encoded_links *e, double t0, double t1, double t2) {
+  e->t_device_s = t1 - t0;
+  e->t_download_s = t2 - t1;
+  e->t_export_s = t2 - t0;
+}
+// the slot -> item id table where slots are not ids (the filters and the range search share it); null = the identity
+static int ensure_item_ids(hny_builder *b, const u32 **item_ids) {
+  const uint32_t n = b->n;
+  *item_ids = nullptr;
+  if (!n || b->ids[n - 1] == n - 1) return HNY_OK;
+  if (!b->d_item_ids.p) {
+    HIP_TRY(b->d_item_ids.alloc(n));
+    HIP_TRY(hipMemcpy(b->d_item_ids.p, b->ids.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+  }
+  *item_ids = b->d_item_ids.p;
+  return HNY_OK;
+}
+
 int hny_builder_finish_encoded(hny_builder *b, hny_encoded_links **out) {
   if (!b || !out) return fail(HNY_ERR_INVALID_ARG, "null argument");
   *out = nullptr;
@@ -2768,64 +2858,29 @@ int hny_builder_finish_encoded(hny_builder *b, hny_encoded_links **out) {
   ensure_record_table(b, nt);
   if (int rc = ensure_device_record_table(b, nt)) return rc;
   const uint64_t nrec = b->rec_first[n];
-  if (n && b->ids[n - 1] != n - 1 && !b->d_item_ids.p) { // slot != id: the table the filters and the range search share
-    HIP_TRY(b->d_item_ids.alloc(n));
-    HIP_TRY(hipMemcpy(b->d_item_ids.p, b->ids.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-  }
+  const u32 *item_ids = nullptr;
+  if (int rc = ensure_item_ids(b, &item_ids)) return rc;
   std::unique_ptr<hny_encoded_links, void (*)(hny_encoded_links *)> eh(
       (hny_encoded_links *)calloc(1, sizeof(hny_encoded_links)), hny_encoded_links_free);
   hny_encoded_links *e = eh.get();
   if (!e) return fail(HNY_ERR_OOM, "out of host memory for %llu records", (unsigned long long)nrec);
-  // sizes -> offsets (one more element than records: the last offset is the total) -> values
-  DevBuf<u64> d_sizes, d_off;
-  DevBuf<unsigned char> d_tmp, d_values;
-  HIP_TRY(d_sizes.alloc(nrec + 1));
-  HIP_TRY(d_off.alloc(nrec + 1));
-  EncodeLinksArgs a{};
-  a.l0_ids = b->d_l0_ids.p, a.up_ids = b->d_up_ids.p, a.cnt0 = b->d_fin_cnt0.p, a.cntu = b->d_fin_cntu.p;
-  a.item_ids = n && b->ids[n - 1] != n - 1 ? b->d_item_ids.p : nullptr;
-  a.n = n, a.M = b->o.M, a.M0 = b->o.M0;
+  EncodeLinksArgs a = encode_args(b, item_ids);
   a.rec_list = b->d_rec_list.p, a.rec_layer = b->d_rec_layer.p, a.n_recs = nrec;
-  a.sizes = d_sizes.p, a.off = d_off.p;
-  HIP_TRY(hipMemsetAsync(d_sizes.p + nrec, 0, 8, b->stream));
-  HIP_TRY(hnyk_encode_links_sizes(a, b->stream));
-  size_t tmp_bytes = 0;
-  HIP_TRY(hnyk_exclusive_scan_u64(nullptr, &tmp_bytes, d_sizes.p, d_off.p, nrec + 1, b->stream));
-  HIP_TRY(d_tmp.alloc(std::max<size_t>(tmp_bytes, 16)));
-  HIP_TRY(hnyk_exclusive_scan_u64(d_tmp.p, &tmp_bytes, d_sizes.p, d_off.p, nrec + 1, b->stream));
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  u64 total = 0;
-  HIP_TRY(hipMemcpy(&total, d_off.p + nrec, 8, hipMemcpyDeviceToHost));
-  HIP_TRY(d_values.alloc(std::max<size_t>(total, 16)));
-  a.values = d_values.p;
-  HIP_TRY(hnyk_encode_links_emit(a, b->stream));
-  // the host's share while the emit runs: the pinned arrays of the result, the record table, the entry points
-  HIP_TRY(hipHostMalloc((void **)&e->val_offset, (nrec + 1) * 8, hipHostMallocDefault));
-  HIP_TRY(hipHostMalloc((void **)&e->values, std::max<size_t>(total, 16), hipHostMallocDefault));
+  EncodeRun run;
+  if (int rc = encode_enqueue(b, a, e, run)) return rc;
+  // the host's share while the emit runs: the record table, the entry points
   uint32_t *rec_item = (uint32_t *)malloc(std::max<uint64_t>(nrec, 1) * 4);
   uint8_t *rec_layer = (uint8_t *)malloc(std::max<uint64_t>(nrec, 1));
   e->rec_item = rec_item, e->rec_layer = rec_layer;
-  e->entry_points = entry_point_ids(b);
-  if (!rec_item || !rec_layer || !e->entry_points)
-    return fail(HNY_ERR_OOM, "out of host memory for %llu records", (unsigned long long)nrec);
+  if (!rec_item || !rec_layer) return fail(HNY_ERR_OOM, "out of host memory for %llu records", (unsigned long long)nrec);
   memcpy(rec_item, b->rec_item_t.data(), nrec * 4);
   memcpy(rec_layer, b->rec_layer_t.data(), nrec);
-  e->n_records = nrec;
-  e->n_entry_points = (uint32_t)b->entry_points.size();
-  e->max_level = b->max_level;
+  if (int rc = encode_header(b, stats, nrec, e)) return rc;
   HIP_TRY(hipStreamSynchronize(b->stream));
   const double t1 = now_s();
-  HIP_TRY(hipMemcpyAsync((void *)e->val_offset, d_off.p, (nrec + 1) * 8, hipMemcpyDeviceToHost, b->stream));
-  if (total) HIP_TRY(hipMemcpyAsync((void *)e->values, d_values.p, total, hipMemcpyDeviceToHost, b->stream));
+  if (int rc = encode_download(b, run, e)) return rc;
   HIP_TRY(hipStreamSynchronize(b->stream));
-  const double t2 = now_s();
-  e->n_links_added = stats[ST_LINKS];
-  e->n_evals_walk = stats[ST_EVALS_WALK];
-  e->n_batches = b->n_batches;
-  e->t_device_s = t1 - t0;
-  e->t_download_s = t2 - t1;
-  e->t_export_s = t2 - t0;
-  e->bytes_downloaded = (nrec + 1) * 8 + total;
+  encode_timings(e, t0, t1, now_s());
   *out = eh.release();
   return HNY_OK;
 }
@@ -3355,6 +3410,130 @@ int hny_builder_finish_delta(hny_builder *b, hny_graph_delta **out) {
       !d->entry_points)
     return fail(HNY_ERR_OOM, "out of host memory for %llu delta records", (unsigned long long)nr);
   d->t_export_s = now_s() - t0;
+  *out = dh.release();
+  return HNY_OK;
+}
+
+// ---- encoded delta export: finish_delta's records without its host loops.  The flags of the same
+// comparison stay on the device; k_delta_count / scans / k_delta_write (hny_export.hip) make the table of changed
+// records and the removed keys from them, and the table goes through the sizes / scan / emit passes of the encoded
+// export.  The host's share is one pass over the slots (the two masks, once per builder). ----
+static int ensure_delta_masks(hny_builder *b) {
+  const uint32_t n = b->n;
+  if (b->d_delta_masks.p || !n) return HNY_OK;
+  std::vector<unsigned short> m((size_t)n * 2);
+  uint64_t total = 0;
+  for (uint32_t s = 0; s < n; s++) {
+    const uint32_t own = rec_mask_of(b, s);
+    m[s] = b->old_mask[s];
+    m[(size_t)n + s] = (unsigned short)own;
+    total += (uint32_t)__builtin_popcount(own);
+  }
+  HIP_TRY(b->d_delta_masks.alloc((size_t)n * 2));
+  HIP_TRY(hipMemcpy(b->d_delta_masks.p, m.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+  b->delta_recs_total = total;
+  return HNY_OK;
+}
+
+int hny_builder_finish_delta_encoded(hny_builder *b, hny_encoded_delta **out) {
+  if (!b || !out) return fail(HNY_ERR_INVALID_ARG, "null argument");
+  *out = nullptr;
+  if (!b->from_update)
+    return fail(HNY_ERR_INVALID_ARG, "finish_delta: not a successor builder (hny_builder_create_update)");
+  if (b->pos < b->order.size() || b->in_batch) return fail(HNY_ERR_INVALID_ARG, "build not finished");
+  if (!b->gaps_done) return fail(HNY_ERR_INVALID_ARG, "finish_delta: hny_builder_fill_gaps has not run");
+  if (std::max(b->o.M, b->o.M0) > HNY_EXPORT_MAX_CAP)
+    return fail(HNY_ERR_UNSUPPORTED, "lists of more than %u entries may need bitmap containers", HNY_EXPORT_MAX_CAP);
+  u64 stats[ST_COUNT] = {0};
+  double t0 = 0;
+  if (int rc = export_begin(b, stats, &t0)) return rc;
+  hipStream_t st = b->stream;
+  const uint32_t n = b->n, M = b->o.M, M0 = b->o.M0;
+  const size_t nup = (size_t)b->n_upper * b->up_layers, nn = (size_t)n + 1;
+  std::unique_ptr<hny_encoded_delta, void (*)(hny_encoded_delta *)> dh(
+      (hny_encoded_delta *)calloc(1, sizeof(hny_encoded_delta)), hny_encoded_delta_free);
+  hny_encoded_delta *d = dh.get();
+  if (!d) return fail(HNY_ERR_OOM, "out of host memory");
+  hny_encoded_links *e = &d->links;
+  if (int rc = ensure_delta_masks(b)) return rc;
+  const u32 *item_ids = nullptr;
+  if (int rc = ensure_item_ids(b, &item_ids)) return rc;
+  // the flags (as finish_delta), the count pass, its two scans (one more element than slots: the last is the total)
+  DevBuf<unsigned char> d_flag, d_tmp, d_layers;
+  DevBuf<unsigned short> d_chg;
+  DevBuf<u64> d_cnt, d_off, d_wrote;
+  DevBuf<u32> d_tab;
+  HIP_TRY(d_flag.alloc((size_t)n + nup + 1));
+  HIP_TRY(d_chg.alloc(nn));
+  HIP_TRY(d_cnt.alloc(2 * nn));
+  HIP_TRY(d_off.alloc(2 * nn));
+  HIP_TRY(d_wrote.alloc(2 * (size_t)HNY_DELTA_GRID_CAP));
+  HIP_TRY(hipMemsetAsync(d_flag.p, 0, (size_t)n + nup + 1, st));
+  HIP_TRY(hipMemsetAsync(d_cnt.p, 0, 2 * nn * 8, st)); // (the two terminators, and everything when n == 0)
+  HIP_TRY(hipMemsetAsync(d_wrote.p, 0, 2 * (size_t)HNY_DELTA_GRID_CAP * 8, st));
+  if (n) HIP_TRY(hnyk_diff_records(b->d_l0_ids.p, b->d_d0_ids.p, d_flag.p, n, M0, st));
+  if (nup) HIP_TRY(hnyk_diff_records(b->d_up_ids.p, b->d_du_ids.p, d_flag.p + n, (u32)nup, M, st));
+  DeltaTableArgs ta{};
+  ta.flag = d_flag.p, ta.n_flags = (u64)n + nup + 1;
+  ta.old_mask = b->d_delta_masks.p, ta.new_mask = b->d_delta_masks.p + n;
+  ta.upper_idx = b->d_upper_idx.p, ta.up_layers = b->up_layers;
+  ta.item_ids = item_ids, ta.n = n;
+  ta.chg = d_chg.p, ta.cnt_chg = d_cnt.p, ta.cnt_rm = d_cnt.p + nn;
+  ta.off_chg = d_off.p, ta.off_rm = d_off.p + nn;
+  HIP_TRY(hnyk_delta_table_count(ta, st));
+  size_t tmp_bytes = 0;
+  HIP_TRY(hnyk_exclusive_scan_u64(nullptr, &tmp_bytes, d_cnt.p, d_off.p, nn, st));
+  HIP_TRY(d_tmp.alloc(std::max<size_t>(tmp_bytes, 16)));
+  HIP_TRY(hnyk_exclusive_scan_u64(d_tmp.p, &tmp_bytes, d_cnt.p, d_off.p, nn, st));
+  HIP_TRY(hnyk_exclusive_scan_u64(d_tmp.p, &tmp_bytes, d_cnt.p + nn, d_off.p + nn, nn, st));
+  u64 nr = 0, nrm = 0;
+  HIP_TRY(hipMemcpyAsync(&nr, d_off.p + n, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&nrm, d_off.p + nn + n, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (nr > b->delta_recs_total || nrm > (u64)n * 16)
+    return fail(HNY_ERR_DEVICE, "encoded delta: %llu changed records and %llu removed keys counted, %llu records exist",
+                (unsigned long long)nr, (unsigned long long)nrm, (unsigned long long)b->delta_recs_total);
+  // the write pass: rec_list | rec_item | rm_item in one u32 buffer, rec_layer | rm_layer in one of bytes
+  HIP_TRY(d_tab.alloc(std::max<u64>(2 * nr + nrm, 1)));
+  HIP_TRY(d_layers.alloc(std::max<u64>(nr + nrm, 1)));
+  ta.rec_list = d_tab.p, ta.rec_item = d_tab.p + nr, ta.rm_item = d_tab.p + 2 * nr;
+  ta.rec_layer = d_layers.p, ta.rm_layer = d_layers.p + nr;
+  ta.wrote = d_wrote.p;
+  HIP_TRY(hnyk_delta_table_write(ta, st));
+  // the values of that table
+  EncodeLinksArgs a = encode_args(b, item_ids);
+  a.rec_list = ta.rec_list, a.rec_layer = ta.rec_layer, a.n_recs = nr;
+  EncodeRun run;
+  if (int rc = encode_enqueue(b, a, e, run)) return rc;
+  uint32_t *rec_item = (uint32_t *)malloc(std::max<u64>(nr, 1) * 4), *rm_item = (uint32_t *)malloc(std::max<u64>(nrm, 1) * 4);
+  uint8_t *rec_layer = (uint8_t *)malloc(std::max<u64>(nr, 1)), *rm_layer = (uint8_t *)malloc(std::max<u64>(nrm, 1));
+  e->rec_item = rec_item, e->rec_layer = rec_layer, d->removed_item = rm_item, d->removed_layer = rm_layer;
+  if (!rec_item || !rec_layer || !rm_item || !rm_layer)
+    return fail(HNY_ERR_OOM, "out of host memory for %llu delta records", (unsigned long long)nr);
+  if (int rc = encode_header(b, stats, nr, e)) return rc;
+  d->n_removed = nrm;
+  d->n_records_total = b->delta_recs_total;
+  HIP_TRY(hipStreamSynchronize(st));
+  const double t1 = now_s();
+  if (int rc = encode_download(b, run, e)) return rc;
+  std::vector<u64> wrote(2 * (size_t)HNY_DELTA_GRID_CAP);
+  if (nr) HIP_TRY(hipMemcpyAsync(rec_item, ta.rec_item, nr * 4, hipMemcpyDeviceToHost, st));
+  if (nr) HIP_TRY(hipMemcpyAsync(rec_layer, ta.rec_layer, nr, hipMemcpyDeviceToHost, st));
+  if (nrm) HIP_TRY(hipMemcpyAsync(rm_item, ta.rm_item, nrm * 4, hipMemcpyDeviceToHost, st));
+  if (nrm) HIP_TRY(hipMemcpyAsync(rm_layer, ta.rm_layer, nrm, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(wrote.data(), d_wrote.p, wrote.size() * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  e->bytes_downloaded += (nr + nrm) * 5;
+  encode_timings(e, t0, t1, now_s());
+  // the passes voted alike: what the write pass stored, and where the emit's offsets end
+  u64 w_chg = 0, w_rm = 0;
+  for (size_t k = 0; k < HNY_DELTA_GRID_CAP; k++) w_chg += wrote[2 * k], w_rm += wrote[2 * k + 1];
+  if (w_chg != nr || w_rm != nrm)
+    return fail(HNY_ERR_DEVICE, "encoded delta: %llu records and %llu removed keys written, %llu and %llu counted",
+                (unsigned long long)w_chg, (unsigned long long)w_rm, (unsigned long long)nr, (unsigned long long)nrm);
+  if (e->val_offset[0] != 0 || e->val_offset[nr] != run.total || run.total < 9 * nr)
+    return fail(HNY_ERR_DEVICE, "encoded delta: the values of %llu records end at byte %llu, %llu counted",
+                (unsigned long long)nr, (unsigned long long)e->val_offset[nr], (unsigned long long)run.total);
   *out = dh.release();
   return HNY_OK;
 }

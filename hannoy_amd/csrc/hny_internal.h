@@ -784,3 +784,28 @@ struct EncodeLinksArgs {
 hipError_t hnyk_encode_links_sizes(const EncodeLinksArgs &a, hipStream_t st);
 hipError_t hnyk_encode_links_emit(const EncodeLinksArgs &a, hipStream_t st);
 hipError_t hnyk_exclusive_scan_u64(void *temp, size_t *temp_bytes, const u64 *in, u64 *out, size_t n, hipStream_t st);
+
+// ---- encoded delta export (hny_export.hip): the table of the records an update changed, and the
+// keys it removed, made on the device from k_diff_records' flags: a count pass, two exclusive scans, a write pass ----
+#define HNY_DELTA_GRID_CAP 512u       // blocks of either pass (one slot per thread); the rest is a grid stride
+#define HNY_DELTA_BLOCK 256u          // threads of a block of either pass
+struct DeltaTableArgs {
+  const unsigned char *flag;          // [n_flags] k_diff_records: layer-0 lists [0, n), then the upper lists
+  const unsigned short *old_mask;     // [n] bit l = the previous graph holds a record (slot, l)
+  const unsigned short *new_mask;     // [n] bit l = the successor owns the record (slot, l)
+  const int *upper_idx;               // [n] the slot's row of upper lists (read only where it owns a record above 0)
+  const u32 *item_ids;                // [n] slot -> item id, null = the identity
+  u32 n, up_layers;
+  u64 n_flags;
+  unsigned short *chg;                // [n] count pass: bit l = the record (slot, l) is new or its list changed
+  u64 *cnt_chg, *cnt_rm;              // [n] count pass: changed records / removed keys of the slot
+  const u64 *off_chg, *off_rm;        // [n + 1] write pass: their exclusive scans
+  u32 *rec_list;                      // [off_chg[n]] as EncodeLinksArgs::rec_list
+  unsigned char *rec_layer;           // [off_chg[n]]
+  u32 *rec_item;                      // [off_chg[n]] item ids
+  u32 *rm_item;                       // [off_rm[n]]
+  unsigned char *rm_layer;            // [off_rm[n]]
+  u64 *wrote;                         // [2 * HNY_DELTA_GRID_CAP] write pass: records, keys every block stored
+};
+hipError_t hnyk_delta_table_count(const DeltaTableArgs &a, hipStream_t st);
+hipError_t hnyk_delta_table_write(const DeltaTableArgs &a, hipStream_t st);

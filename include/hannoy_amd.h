@@ -719,6 +719,30 @@ void hny_encoded_links_free(hny_encoded_links *e); /* NULL is fine */
 int hny_encode_kv_encoded(const hny_encoded_links *e, const hny_build_opts *opts, const hny_items *items,
                           uint16_t index, int with_items, hny_kv_sink sink, void *ctx);
 
+/* ---- encoded delta export: what hny_builder_finish_delta returns for a successor builder, with
+ * the values of the changed records serialised on the device.  The table of changed records and the removed keys are
+ * made on the device as well (from the flags of the list comparison), so the host runs no loop over records or
+ * links.  Library-owned, read-only for the caller; not part of hny_abi_sizes. */
+typedef struct {
+  hny_encoded_links links;      /* the new / changed records in (item id, layer) order: rec_item, rec_layer,
+                                 * val_offset, values (both pinned), entry points, max_level, counters and timings as
+                                 * hny_builder_finish_encoded fills them; t_device_s covers the list comparison and
+                                 * the table passes too.  Zero records: val_offset = {0} */
+  uint64_t n_removed;           /* as hny_graph_delta: keys the previous graph held and this one does not */
+  const uint32_t *removed_item;
+  const uint8_t *removed_layer;
+  uint64_t n_records_total;     /* records of the full graph, as hny_graph_delta */
+} hny_encoded_delta;
+/* For D = hny_builder_finish_delta(b): the same records, removed keys, entry points, max_level and n_records_total,
+ * and the value of record r = tag 0x01 | the roaring bytes of D's record r, so that
+ * hny_encode_kv_encoded(&d->links, opts, ids-only items, index, 0, ...) emits the stream hny_encode_kv emits for D
+ * viewed as an hny_graph.  Accepts exactly the builders hny_builder_finish_delta accepts and refuses the others with
+ * its codes, lists longer than hny_builder_finish_encoded serialises with HNY_ERR_UNSUPPORTED (*out = NULL, no
+ * device work).  The builder stays usable; none of finish, finish_encoded, finish_delta and this call changes what
+ * another returns, in any order.  HNY_ERR_DEVICE if the passes disagree about how many records there are. */
+int hny_builder_finish_delta_encoded(hny_builder *b, hny_encoded_delta **out);
+void hny_encoded_delta_free(hny_encoded_delta *d); /* NULL is fine */
+
 /* ---- LMDB writeback: the KV stream above as an LMDB environment file
  * (`<dir>/data.mdb`) that heed/LMDB can open — what `db.put` produces in the reference's write
  * loop (hnsw.rs:195-213, writer.rs:462-480, 585-600) through heed 0.22 / LMDB 0.9 (third party,
