@@ -47,6 +47,8 @@ EXPORTED = [
     "hny_builder_exact_range_count_f32", "hny_range_result_free",
     "hny_builder_finish_encoded", "hny_encoded_links_free", "hny_encode_kv_encoded",
     "hny_builder_finish_delta_encoded", "hny_encoded_delta_free",
+    "hny_builder_load_encoded", "hny_builder_load_encoded_f32", "hny_builder_create_incremental_encoded",
+    "hny_build_incremental_encoded", "hny_encoded_links_measure", "hny_lmdb_read_links",
 ]
 ERR_IO = -9
 NNS_NONE = 0xFFFFFFFF  # by_item: the reference returns None
@@ -392,6 +394,21 @@ def load_library():
                        ("hny_builder_create_f32", "hny_builder_create"), ("hny_builder_load_f32", "hny_builder_load")):
         getattr(L, name).restype = C.c_int
         getattr(L, name).argtypes = getattr(L, base).argtypes
+    el = C.POINTER(EncodedLinksStruct)
+    for name in ("hny_builder_load_encoded", "hny_builder_load_encoded_f32"):
+        getattr(L, name).restype = C.c_int
+        getattr(L, name).argtypes = [C.POINTER(BuildOpts), C.POINTER(Items), el, C.POINTER(vp)]
+    L.hny_builder_create_incremental_encoded.restype = C.c_int
+    L.hny_builder_create_incremental_encoded.argtypes = [C.POINTER(BuildOpts), C.POINTER(Items), vp, C.c_uint64, vp,
+                                                         C.c_uint64, el, C.POINTER(vp)]
+    L.hny_build_incremental_encoded.restype = C.c_int
+    L.hny_build_incremental_encoded.argtypes = [C.POINTER(BuildOpts), C.POINTER(Items), vp, C.c_uint64, vp, C.c_uint64,
+                                                el, C.POINTER(C.POINTER(GraphStruct))]
+    L.hny_encoded_links_measure.restype = C.c_int
+    L.hny_encoded_links_measure.argtypes = [el, C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                            C.POINTER(C.c_uint64)]
+    L.hny_lmdb_read_links.restype = C.c_int
+    L.hny_lmdb_read_links.argtypes = [vp, C.c_uint16, C.POINTER(el)]
     L.hny_builder_export_items.restype = C.c_int
     L.hny_builder_export_items.argtypes = [vp, vp, vp]
     L.hny_builder_search_knn_f32.restype = C.c_int
@@ -901,6 +918,34 @@ class EncodedLinks:
         self.entry_points = np.ctypeslib.as_array(e.entry_points, (max(ne, 1),))[:ne].copy()
         self._ep, self._opts, self._items = ep, opts, items
 
+    @classmethod
+    def from_records(cls, rec_item, rec_layer, values_list, entry_points, max_level):
+        """A struct filled in here, for Builder(stored=...), build_incremental(stored=...), encoded_links_measure and
+        encode_kv: the Links records (item, layer) in key order with their values as they lie on disk (bytes-like
+        each: tag 0x01 | roaring bytes).  Nothing is decoded or checked here."""
+        lens = np.fromiter((len(v) for v in values_list), np.uint64, len(values_list))
+        keep = [np.ascontiguousarray(rec_item, np.uint32), np.ascontiguousarray(rec_layer, np.uint8),
+                np.concatenate([np.zeros(1, np.uint64), np.cumsum(lens, dtype=np.uint64)]),
+                np.frombuffer(b"".join(values_list) or b"\0", np.uint8),
+                np.ascontiguousarray(entry_points if len(entry_points) else np.zeros(1), np.uint32)]
+        if not len(keep[0]) == len(keep[1]) == len(lens):
+            raise ValueError("rec_item, rec_layer and values_list differ in length")
+        st = EncodedLinksStruct()
+        st.n_records = len(lens)
+        for f, a, t in zip(("rec_item", "rec_layer", "val_offset", "values", "entry_points"), keep,
+                           (C.c_uint32, C.c_uint8, C.c_uint64, C.c_uint8, C.c_uint32)):
+            if not len(a):  # (no NULL arrays: the views of an empty struct are empty arrays)
+                a = np.zeros(1, a.dtype)
+                keep.append(a)
+            setattr(st, f, C.cast(a.ctypes.data, C.POINTER(t)))
+        st.n_entry_points, st.max_level = len(entry_points), int(max_level)
+        return cls(C.pointer(st), owner=keep)
+
+    @property
+    def ptr(self):
+        """POINTER(hny_encoded_links) for the calls that take the struct as input"""
+        return self._ep
+
     def __getattr__(self, name):
         if name not in EncodedLinks._VIEWS or self.__dict__.get("_ep") is None:
             raise AttributeError(name)
@@ -1140,6 +1185,13 @@ class LmdbEnv:
     def verify(self):
         _check(load_library().hny_lmdb_scan(self._e, None, 0, None, 0, KV_SINK(), None))
 
+    def read_links(self, index=0):
+        """hny_lmdb_read_links: every Links record of `index` with its value as it lies in the file, plus the entry
+        points and max_level of the Metadata record, as an EncodedLinks (no Python in the record loop)"""
+        ep = C.POINTER(EncodedLinksStruct)()
+        _check(load_library().hny_lmdb_read_links(self._e, index, C.byref(ep)))
+        return EncodedLinks(ep)
+
     def close(self):
         if self._e is not None:
             load_library().hny_lmdb_close(self._e)
@@ -1173,14 +1225,32 @@ def _prev_struct(prev):
     return pg, keep
 
 
-def build_incremental(items, prev, to_insert, to_delete, **kw):
+def encoded_links_measure(stored, device=-1):
+    """hny_encoded_links_measure: (longest layer-0 list, longest upper list, links) of an EncodedLinks, from the
+    container headers alone, on the device"""
+    m0, mu, nl = C.c_uint32(), C.c_uint32(), C.c_uint64()
+    _check(load_library().hny_encoded_links_measure(stored.ptr, device, C.byref(m0), C.byref(mu), C.byref(nl)))
+    return m0.value, mu.value, nl.value
+
+
+def build_incremental(items, prev=None, to_insert=(), to_delete=(), stored=None, **kw):
     """hny_build_incremental: `items` = every item present after the update (levels, if any: one per
     to_insert id); `prev` = graph of the previous build (anything with rec_item/rec_layer/offsets/
-    nbrs/entry_points/max_level)."""
+    nbrs/entry_points/max_level), or `stored` = its Links records undecoded (an EncodedLinks:
+    hny_build_incremental_encoded)."""
     o = make_opts(items.metric, items.dim, **kw)
     it = items.struct()
     ins = u32_ids(to_insert)
     dl = u32_ids(to_delete)
+    if (prev is None) == (stored is None):
+        raise ValueError("build_incremental takes either prev or stored")
+    if stored is not None:
+        if items.f32:
+            raise HannoyError(ERR_UNSUPPORTED, "build_incremental(stored=...) takes codec bytes")
+        gp = C.POINTER(GraphStruct)()
+        _check(load_library().hny_build_incremental_encoded(C.byref(o), C.byref(it), _p(ins), len(ins), _p(dl), len(dl),
+                                                            stored.ptr, C.byref(gp)))
+        return Graph(gp, o, items)
     keep = [np.ascontiguousarray(prev.rec_item, np.uint32), np.ascontiguousarray(prev.rec_layer, np.uint8),
             np.ascontiguousarray(prev.offsets, np.uint64),
             np.ascontiguousarray(prev.nbrs if len(prev.nbrs) else np.zeros(1), np.uint32),
@@ -1260,16 +1330,31 @@ class Builder:
     """Stepwise builder (hny_builder_*): vectors stay resident in HBM across reset()/rebuilds."""
     _borrowed = False
 
-    def __init__(self, items, prev=None, to_insert=(), to_delete=(), load=False, **kw):
+    def __init__(self, items, prev=None, to_insert=(), to_delete=(), load=False, stored=None, **kw):
         """prev given -> incremental builder on top of a stored graph (hny_builder_create_incremental);
-        with load=True the stored graph is only loaded for searching (hny_builder_load)"""
+        with load=True the stored graph is only loaded for searching (hny_builder_load).  stored (an EncodedLinks)
+        in place of prev: the same from the Links records as they lie on disk, decoded on the device
+        (hny_builder_create_incremental_encoded / hny_builder_load_encoded)"""
+        if prev is not None and stored is not None:
+            raise ValueError("Builder takes either prev or stored")
         self.items = items
         self.opts = make_opts(items.metric, items.dim, **kw)
         self._h = C.c_void_p()
-        self.incremental = prev is not None
+        self.incremental = prev is not None or stored is not None
         it = items.struct()
         L, f32 = load_library(), items.f32
-        if prev is None:
+        if stored is not None:
+            if load:
+                _check((L.hny_builder_load_encoded_f32 if f32 else L.hny_builder_load_encoded)(
+                    C.byref(self.opts), C.byref(it), stored.ptr, C.byref(self._h)))
+            else:
+                if f32:
+                    raise HannoyError(ERR_UNSUPPORTED, "a stepwise incremental builder takes codec bytes")
+                ins = u32_ids(to_insert)
+                dl = u32_ids(to_delete)
+                _check(L.hny_builder_create_incremental_encoded(
+                    C.byref(self.opts), C.byref(it), _p(ins), len(ins), _p(dl), len(dl), stored.ptr, C.byref(self._h)))
+        elif prev is None:
             _check((L.hny_builder_create_f32 if f32 else L.hny_builder_create)(C.byref(self.opts), C.byref(it), C.byref(self._h)))
         elif load:
             pg, _keep = _prev_struct(prev)

@@ -113,6 +113,18 @@ class _StoredGraph:
         self.max_level = meta["max_level"] if meta else 0
 
 
+def _stored_encoded(db, index):
+    """the Links records + Metadata of one index as they lie in the store, not decoded: a capi.EncodedLinks for
+    hny_builder_load_encoded / hny_build_incremental_encoded"""
+    lo, hi = key(index, MODE_LINKS), key(index, MODE_LINKS, 0xFFFFFFFF, 0xFF)
+    keys = sorted(k for k in db.kv if lo <= k <= hi)
+    cols = np.array([struct.unpack(">HBIB", k)[2:] for k in keys], np.uint32).reshape(len(keys), 2)
+    meta = db.metadata(index)
+    return capi.EncodedLinks.from_records(cols[:, 0], cols[:, 1].astype(np.uint8), [db.kv[k] for k in keys],
+                                          meta["entry_points"] if meta else np.zeros(0, np.uint32),
+                                          meta["max_level"] if meta else 0)
+
+
 class Database:
     """hannoy.pyi Database (python.rs:60-100): `path` = the LMDB environment directory (None = in
     memory only), `name` = a named database inside it, `env_size` = the map size recorded in the
@@ -147,8 +159,11 @@ class Database:
         rewritten).  The records it leaves are those of the default path, byte for byte."""
         return Writer(self, dimensions, index, m, ef, resident)
 
-    def reader(self, index=0):
-        return Reader(self, index)
+    def reader(self, index=0, encoded_links=False):
+        """encoded_links=True: the stored Links values go to the device as they lie and are decoded there
+        (hny_builder_load_encoded); a store the device does not decode (run or bitmap containers, links to ids that
+        own nothing) is opened the default way.  The Reader answers the same either way."""
+        return Reader(self, index, encoded_links)
 
     # -- record level helpers -------------------------------------------------------------------
     def dump(self, index=None):
@@ -363,21 +378,24 @@ class Writer:
             self.db.kv = snapshot
             raise
 
-    def build(self, levels=None, relink_all_items=False, rng=None, encoded_links=False, **opts):
+    def build(self, levels=None, relink_all_items=False, rng=None, encoded_links=False, read_encoded=False, **opts):
         """Writer::build (writer.rs:521-603).  `levels`: optional {item id: level} for the items that
         get (re)inserted, instead of drawing them from StdRng::seed_from_u64(self.seed).
         encoded_links: the write paths that store every Links record take them from Builder.finish_encoded (their
         values serialised on the device) and the build returns that EncodedLinks instead of a Graph; the resident
         paths that store a delta take the changed records from Builder.finish_delta_encoded, leave that EncodedDelta
-        in `last_delta` and return the Graph as before.  The records written are the same either way."""
+        in `last_delta` and return the Graph as before.  The records written are the same either way.
+        read_encoded: a non-resident incremental build hands the previous graph's Links values to the device as they
+        lie (hny_build_incremental_encoded) instead of decoding them here; a store the device does not decode is read
+        the default way.  The records written are the same either way."""
         snapshot = dict(self.db.kv)  # writer.rs:521-603 runs in the caller's RwTxn: an error (cancel,
         try:                         # unsupported, device, OOM) aborts it and nothing is changed
-            return self._build(levels, relink_all_items, rng, opts, bool(encoded_links))
+            return self._build(levels, relink_all_items, rng, opts, bool(encoded_links), bool(read_encoded))
         except BaseException:
             self.db.kv = snapshot
             raise
 
-    def _build(self, levels, relink_all_items, rng, opts, encoded=False):
+    def _build(self, levels, relink_all_items, rng, opts, encoded=False, read_encoded=False):
         db, index = self.db, self.index
         meta = db.metadata(index)
         indexed = set(meta["items"].tolist()) if meta else set()
@@ -403,34 +421,43 @@ class Writer:
             g = self._build_resident(meta, indexed, ids, to_insert, to_delete, levels, relink_all_items, kw, encoded)
         else:
             g, _ = self._build_all_records(meta, ids, to_insert, to_delete, levels, kw, keep_builder=False,
-                                           encoded=encoded)
+                                           encoded=encoded, read_encoded=read_encoded)
         db.build_generation[index] = db.build_generation.get(index, 0) + 1
         self.last_graph = g
         return g
 
-    def _build_all_records(self, meta, ids, to_insert, to_delete, levels, kw, keep_builder, encoded=False):
+    def _build_all_records(self, meta, ids, to_insert, to_delete, levels, kw, keep_builder, encoded=False,
+                           read_encoded=False):
         """every item read from the store, the stored graph as `prev`, and every Links record written back.
         keep_builder: build stepwise on a Builder and return it alive (the resident Writer keeps it) instead of
         the one-call hny_build / hny_build_incremental; the graphs are the same.  encoded: stepwise as well, and
         the records come from finish_encoded()."""
         db, index = self.db, self.index
         items = db.item_set(index, ids, self.dimensions)
-        prev = _StoredGraph(db, index)
+        prev = _stored_encoded(db, index) if read_encoded else _StoredGraph(db, index)
         fresh = len(prev.rec_item) == 0 and meta is None
         if levels is not None:
             items.levels = np.array([levels[int(i)] for i in (ids if fresh else to_insert)], np.uint8)
-        b = None
-        if not keep_builder and not encoded:
-            g = capi.build(items, **kw) if fresh else capi.build_incremental(items, prev, to_insert, to_delete, **kw)
-        else:
-            b = capi.Builder(items, **kw) if fresh else capi.Builder(items, prev=prev, to_insert=to_insert,
-                                                                     to_delete=to_delete, **kw)
+
+        def run(prev):
+            how = {"stored" if isinstance(prev, capi.EncodedLinks) else "prev": prev}
+            if not keep_builder and not encoded:
+                return (capi.build(items, **kw) if fresh else
+                        capi.build_incremental(items, to_insert=to_insert, to_delete=to_delete, **how, **kw)), None
+            b = capi.Builder(items, **kw) if fresh else capi.Builder(items, to_insert=to_insert, to_delete=to_delete,
+                                                                     **how, **kw)
             try:
                 b.run()
-                g = b.finish_encoded() if encoded else b.finish()
+                return (b.finish_encoded() if encoded else b.finish()), b
             except BaseException:
                 b.close()
                 raise
+        try:
+            g, b = run(prev)
+        except capi.HannoyError as e:  # the device does not decode this store: the decoded lists, as by default
+            if not read_encoded or e.code != capi.ERR_UNSUPPORTED:
+                raise
+            g, b = run(_StoredGraph(db, index))
         # write-back: every Links record of the new state (hnsw.rs:195-213) — stale ones and those
         # of deleted items go (writer.rs:580) —, then Metadata and Version (writer.rs:585-600)
         try:
@@ -806,8 +833,10 @@ class Reader:
     (:546-608), `nns(count)` -> QueryBuilder (:611-619), `by_vec` = Reader::nns(n).by_vector on the
     GPU."""
 
-    def __init__(self, db, index=0):
+    def __init__(self, db, index=0, encoded_links=False):
         self.db, self.index = db, index
+        self._stored = None  # the decoded _StoredGraph, made when something asks for it (_graph)
+        self.loaded_encoded = False
         meta = db.metadata(index)
         if meta is None:
             raise MissingMetadata("MissingMetadata")  # Error::MissingMetadata
@@ -819,11 +848,27 @@ class Reader:
         self.meta = meta
         self._dimensions = meta["dimensions"]
         items = db.item_set(index, meta["items"], self._dimensions)
-        prev = _StoredGraph(db, index)
+        if encoded_links:
+            enc = _stored_encoded(db, index)
+            try:
+                m0, mu, _ = capi.encoded_links_measure(enc)
+                m0, mu = max(m0, 1), max(mu, 1)
+                self._b = capi.Builder(items, stored=enc, load=True, M=mu, M0=max(m0, mu), ef_construction=1)
+                self.loaded_encoded = True
+                return
+            except capi.HannoyError as e:
+                if e.code != capi.ERR_UNSUPPORTED:
+                    raise
+        prev = self._graph
         m0 = max([int(c) for c in np.diff(prev.offsets.astype(np.int64))[prev.rec_layer == 0]] + [1])
         mu = max([int(c) for c in np.diff(prev.offsets.astype(np.int64))[prev.rec_layer > 0]] + [1])
-        self._graph = prev
         self._b = capi.Builder(items, prev=prev, load=True, M=mu, M0=max(m0, mu), ef_construction=1)
+
+    @property
+    def _graph(self):
+        if self._stored is None:
+            self._stored = _StoredGraph(self.db, self.index)
+        return self._stored
 
     @property
     def dimensions(self):

@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libhannoy_amd.so")
 SOURCES = ["hny_host.cpp", "hny_multi.cpp", "hny_kernels.hip", "hny_update.hip", "hny_range.hip", "hny_export.hip",
-           "hny_lmdb.cpp"]
+           "hny_import.hip", "hny_lmdb.cpp"]
 HOST_ONLY = {"hny_lmdb.cpp"}  # no device code: compiled as plain C++
 HEADERS = [os.path.join(CSRC, "hny_internal.h"),
            os.path.join(CSRC, "hny_rust_sort.h"),

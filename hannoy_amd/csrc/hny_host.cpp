@@ -1046,6 +1046,9 @@ struct IncrementalSpec {
   uint64_t n_delete;
   const hny_prev_graph *prev;
   bool load_only = false; // Reader::open: the stored graph as it is, nothing gets (re)inserted
+  // the _encoded entry points: the previous graph as stored Links values instead of `prev`; the host
+  // reads its record keys and entry points, the lists are decoded on the device (upload_prev_state)
+  const hny_encoded_links *enc = nullptr;
   // hny_builder_create_update: the previous state is a finished builder on the device instead of `prev` on the host
   // (then `items` carries the ids of the items after the update only; the upserted rows come from `upd`)
   hny_builder *src = nullptr;
@@ -1081,6 +1084,8 @@ static inline uint32_t slot_of(const std::vector<uint32_t> &U, uint32_t id) {
 struct PrevState {
   const hny_prev_graph *pg = nullptr;
   hny_builder *src = nullptr;
+  const hny_encoded_links *enc = nullptr; // with it, pg = &enc_keys: the records' keys and the entry points, no lists
+  hny_prev_graph enc_keys{};
   uint32_t max_level = 0;
   std::vector<uint32_t> eps;            // the previous entry points as slots of the new universe (bind_slots)
   std::vector<uint8_t> src_live;        // source builder: its slots that hold a row
@@ -1088,7 +1093,7 @@ struct PrevState {
 
   // the ids that join the universe U
   int init(const IncrementalSpec *inc, std::vector<uint32_t> &U) {
-    if ((!inc->prev && !inc->src) || (inc->n_insert && !inc->to_insert) || (inc->n_delete && !inc->to_delete))
+    if ((!inc->prev && !inc->src && !inc->enc) || (inc->n_insert && !inc->to_insert) || (inc->n_delete && !inc->to_delete))
       return fail(HNY_ERR_INVALID_ARG, "incremental: null argument");
     if (inc->src) {
       // The host holds no lists of the source and does not fetch them: every slot that owns a record or a row,
@@ -1101,9 +1106,15 @@ struct PrevState {
       for (uint32_t s : src->entry_points) U.push_back(src->ids[s]);
       max_level = src->max_level;
     } else {
-      pg = inc->prev;
+      if ((enc = inc->enc)) { // the host sees no neighbour id: as for a source builder, the lists join no id
+        enc_keys.n_records = enc->n_records;
+        enc_keys.rec_item = enc->rec_item, enc_keys.rec_layer = enc->rec_layer;
+        enc_keys.entry_points = enc->entry_points, enc_keys.n_entry_points = enc->n_entry_points;
+        enc_keys.max_level = enc->max_level;
+      }
+      pg = enc ? &enc_keys : inc->prev;
       U.insert(U.end(), pg->rec_item, pg->rec_item + pg->n_records);
-      if (pg->n_records) U.insert(U.end(), pg->neighbours, pg->neighbours + pg->rec_offset[pg->n_records]);
+      if (pg->n_records && !enc) U.insert(U.end(), pg->neighbours, pg->neighbours + pg->rec_offset[pg->n_records]);
       U.insert(U.end(), pg->entry_points, pg->entry_points + pg->n_entry_points);
       max_level = pg->max_level;
     }
@@ -1840,6 +1851,130 @@ static int upload_plan(hny_builder *b, const CreatePlan &P, bool norms_from_head
   HIP_TRY(hipStreamSynchronize(st));
   return HNY_OK;
 }
+// ---- encoded import (hny_import.hip) ----
+// what can be said of an hny_encoded_links given as input without a device
+static int check_encoded_input(const hny_encoded_links *e) {
+  if (!e) return fail(HNY_ERR_INVALID_ARG, "null stored links");
+  const uint64_t nr = e->n_records;
+  if (!e->val_offset || (nr && (!e->rec_item || !e->rec_layer)) || (e->n_entry_points && !e->entry_points))
+    return fail(HNY_ERR_INVALID_ARG, "stored links: null array");
+  if (e->val_offset[0] != 0) return fail(HNY_ERR_INVALID_ARG, "stored links: val_offset[0] = %llu, not 0",
+                                         (unsigned long long)e->val_offset[0]);
+  for (uint64_t r = 0; r < nr; r++) {
+    if (e->val_offset[r + 1] < e->val_offset[r] || e->val_offset[r + 1] - e->val_offset[r] < 9)
+      return fail(HNY_ERR_INVALID_ARG, "stored links: the value of record %llu (%u, %u) is shorter than 9 bytes",
+                  (unsigned long long)r, e->rec_item[r], e->rec_layer[r]);
+    if (e->rec_layer[r] > HNY_MAX_LEVEL)
+      return fail(HNY_ERR_INVALID_ARG, "stored links: record %llu on layer %u > %d", (unsigned long long)r,
+                  e->rec_layer[r], HNY_MAX_LEVEL);
+    if (r && (e->rec_item[r] < e->rec_item[r - 1] ||
+              (e->rec_item[r] == e->rec_item[r - 1] && e->rec_layer[r] <= e->rec_layer[r - 1])))
+      return fail(HNY_ERR_INVALID_ARG, "stored links: record %llu (%u, %u) not after (%u, %u)", (unsigned long long)r,
+                  e->rec_item[r], e->rec_layer[r], e->rec_item[r - 1], e->rec_layer[r - 1]);
+  }
+  if (e->val_offset[nr] && !e->values) return fail(HNY_ERR_INVALID_ARG, "stored links: null values");
+  return HNY_OK;
+}
+// val_offset, values and the layers on the device, and the measure pass over them: out = the host's end of the
+// reduction.  The first record that is not in order, if any, is refused here by name.
+struct ImportRun {
+  DevBuf<u64> d_off;
+  DevBuf<unsigned char> d_values, d_layer;
+  DevBuf<ImportBlockOut> d_out;
+  u32 max0 = 0, maxu = 0;
+  u64 n_links = 0;
+};
+static int import_measure(const hny_encoded_links *e, u32 cap0, u32 capu, hipStream_t st, ImportLinksArgs &a,
+                          ImportRun &R) {
+  const uint64_t nr = e->n_records, total = e->val_offset[nr];
+  a = ImportLinksArgs{};
+  a.n_recs = nr, a.cap0 = cap0, a.capu = capu;
+  if (!nr) return HNY_OK;
+  const u32 grid = hnyk_import_measure_grid(nr);
+  HIP_TRY(R.d_off.alloc(nr + 1));
+  HIP_TRY(R.d_values.alloc((total + 15) / 16 * 16)); // (total >= 9 nr; whole 16-byte words: the decode's loads)
+  HIP_TRY(R.d_layer.alloc(nr));
+  HIP_TRY(R.d_out.alloc(grid));
+  // (pinned arrays, as hny_builder_finish_encoded and hny_lmdb_read_links return them, go by DMA; pageable ones
+  // through the runtime's own staging)
+  HIP_TRY(hipMemcpyAsync(R.d_off.p, e->val_offset, (nr + 1) * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(R.d_values.p, e->values, total, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(R.d_layer.p, e->rec_layer, nr, hipMemcpyHostToDevice, st));
+  a.off = R.d_off.p, a.values = R.d_values.p, a.rec_layer = R.d_layer.p, a.block_out = R.d_out.p;
+  HIP_TRY(hnyk_import_links_measure(a, st));
+  std::vector<ImportBlockOut> out(grid);
+  HIP_TRY(hipMemcpyAsync(out.data(), R.d_out.p, grid * sizeof(ImportBlockOut), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const ImportBlockOut *bad = nullptr;
+  for (const ImportBlockOut &o : out) {
+    R.max0 = std::max(R.max0, o.max0), R.maxu = std::max(R.maxu, o.maxu), R.n_links += o.n_links;
+    if (o.first_bad != ~0ull && (!bad || o.first_bad < bad->first_bad)) bad = &o;
+  }
+  if (!bad) return HNY_OK;
+  const uint64_t r = std::min<uint64_t>(bad->first_bad, nr - 1);
+  const unsigned long long ur = r;
+  const u32 it = e->rec_item[r], ly = e->rec_layer[r], x = bad->info;
+  switch (bad->code) {
+    case IMP_TAG: return fail(HNY_ERR_INVALID_ARG, "stored record %llu (%u, %u): tag 0x%02x, not 0x01 (Links)", ur, it, ly, x);
+    case IMP_COOKIE:
+      return fail(HNY_ERR_UNSUPPORTED, "stored record %llu (%u, %u): roaring cookie %u, not 12346 (run containers are "
+                  "not decoded on the device; hny_builder_load takes the decoded lists)", ur, it, ly, x);
+    case IMP_NC: return fail(HNY_ERR_INVALID_ARG, "stored record %llu (%u, %u): %u containers do not fit its value", ur, it, ly, x);
+    case IMP_KEYS: return fail(HNY_ERR_INVALID_ARG, "stored record %llu (%u, %u): key of container %u not above the one before", ur, it, ly, x);
+    case IMP_BITMAP:
+      return fail(HNY_ERR_UNSUPPORTED, "stored record %llu (%u, %u): container %u holds more than %u ids (bitmap "
+                  "containers are not decoded on the device; hny_builder_load takes the decoded lists)", ur, it, ly, x, HNY_EXPORT_MAX_CAP);
+    case IMP_LENGTH:
+      return fail(HNY_ERR_INVALID_ARG, "stored record %llu (%u, %u): the cardinalities of its %u containers disagree with "
+                  "the length of its value", ur, it, ly, x);
+    case IMP_OFFSET: return fail(HNY_ERR_INVALID_ARG, "stored record %llu (%u, %u): wrong offset of container %u", ur, it, ly, x);
+    case IMP_TOO_LONG:
+      return fail(HNY_ERR_UNSUPPORTED, "old record (%u, %u) has %u > %u links", it, ly, x, ly ? capu : cap0);
+  }
+  return fail(HNY_ERR_DEVICE, "stored record %llu: unknown code %u of the measure pass", ur, bad->code);
+}
+static int ensure_item_ids(hny_builder *b, const u32 **item_ids);
+// upload_prev_state's third source: measure -> check -> memset -> decode -> check, on the builder's stream
+static int decode_prev_lists(hny_builder *b, const hny_encoded_links *e) {
+  const hny_build_opts &o = b->o;
+  hipStream_t st = b->stream;
+  ImportLinksArgs a;
+  ImportRun R;
+  if (int rc = import_measure(e, o.M0, o.M, st, a, R)) return rc;
+  HIP_TRY(hipMemsetAsync(b->d_d0_ids.p, 0xFF, b->d_d0_ids.n * 4, st)); // HNY_SENT
+  HIP_TRY(hipMemsetAsync(b->d_du_ids.p, 0xFF, b->d_du_ids.n * 4, st));
+  const uint64_t nr = e->n_records;
+  if (!nr) return HNY_OK;
+  // every record's list, from its key alone (bind_slots has put every rec_item into the universe)
+  std::vector<u32> list(nr);
+  for (uint64_t r = 0; r < nr; r++) {
+    const uint32_t s = slot_of(b->ids, e->rec_item[r]), ll = e->rec_layer[r];
+    list[r] = ll == 0 ? s : (u32)b->upper_idx[s] * b->up_layers + (ll - 1);
+  }
+  const u32 grid = hnyk_import_decode_grid(nr);
+  DevBuf<u32> d_list, d_bad;
+  HIP_TRY(d_list.alloc(nr));
+  HIP_TRY(d_bad.alloc(2 * (size_t)grid));
+  HIP_TRY(hipMemcpyAsync(d_list.p, list.data(), nr * 4, hipMemcpyHostToDevice, st));
+  const u32 *item_ids = nullptr;
+  if (int rc = ensure_item_ids(b, &item_ids)) return rc;
+  a.rec_list = d_list.p, a.item_ids = item_ids, a.n = b->n, a.M = o.M, a.M0 = o.M0;
+  a.d0_ids = b->d_d0_ids.p, a.du_ids = b->d_du_ids.p, a.bad = d_bad.p;
+  HIP_TRY(hnyk_import_links_decode(a, st));
+  std::vector<u32> bad(2 * (size_t)grid);
+  HIP_TRY(hipMemcpyAsync(bad.data(), d_bad.p, bad.size() * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  uint64_t n_out = 0, n_ord = 0;
+  for (u32 i = 0; i < grid; i++) n_out += bad[2 * i], n_ord += bad[2 * i + 1];
+  if (n_ord)
+    return fail(HNY_ERR_INVALID_ARG, "stored links: %llu values inside a container are not above the one before",
+                (unsigned long long)n_ord);
+  if (n_out)
+    return fail(HNY_ERR_UNSUPPORTED, "stored links: %llu links name an id that is no item, owns no record and is not "
+                "deleted here; hny_builder_load takes such a graph from its decoded lists", (unsigned long long)n_out);
+  return HNY_OK;
+}
+
 // incremental: the previous graph's lists as Links records (ascending ids, HNY_SENT padded) — built here from an
 // hny_prev_graph; a source builder's are in place already (move_state_from_source) — then what fill_gaps reads
 static int upload_prev_state(hny_builder *b, const CreatePlan &P) {
@@ -1847,7 +1982,9 @@ static int upload_prev_state(hny_builder *b, const CreatePlan &P) {
   hipStream_t st = b->stream;
   const uint32_t n = b->n;
   std::vector<u32> d0, du;
-  if (const hny_prev_graph *pg = P.prev.pg) {
+  if (P.prev.enc) {
+    if (int rc = decode_prev_lists(b, P.prev.enc)) return rc;
+  } else if (const hny_prev_graph *pg = P.prev.pg) {
     d0.assign((size_t)n * o.M0, HNY_SENT);
     du.assign(b->d_du_ids.n, HNY_SENT);
     for (uint64_t r = 0; r < pg->n_records; r++) {
@@ -2733,17 +2870,54 @@ int hny_builder_finish(hny_builder *b, hny_graph **out) {
 }
 
 // ---- encoded export: the Links values serialised on the device (hny_export.hip) ----
-static void encoded_links_release(hny_encoded_links *e) { // the arrays, not the struct
+// an hny_encoded_links the library hands out on its own: val_offset and values are pinned, or (hny_lmdb_read_links on
+// a host without a device) plain host memory
+struct OwnedEncodedLinks {
+  hny_encoded_links e;
+  bool pageable;
+};
+static void encoded_links_release(hny_encoded_links *e, bool pageable = false) { // the arrays, not the struct
   free((void *)e->rec_item);
   free((void *)e->rec_layer);
   free((void *)e->entry_points);
+  if (pageable) {
+    free((void *)e->val_offset);
+    free((void *)e->values);
+    return;
+  }
   if (e->val_offset) (void)hipHostFree((void *)e->val_offset);
   if (e->values) (void)hipHostFree((void *)e->values);
 }
 void hny_encoded_links_free(hny_encoded_links *e) {
   if (!e) return;
-  encoded_links_release(e);
+  encoded_links_release(e, reinterpret_cast<OwnedEncodedLinks *>(e)->pageable);
   free(e);
+}
+// hny_lmdb.cpp: a struct for n_records records, value_bytes bytes and n_eps entry points whose arrays the caller
+// fills in (they are const only to the library's users); null = out of memory
+extern "C" hny_encoded_links *hny_internal_encoded_links_alloc(uint64_t n_records, uint64_t value_bytes, uint32_t n_eps) {
+  OwnedEncodedLinks *o = (OwnedEncodedLinks *)calloc(1, sizeof(OwnedEncodedLinks));
+  if (!o) return nullptr;
+  hny_encoded_links *e = &o->e;
+  e->n_records = n_records, e->n_entry_points = n_eps;
+  e->rec_item = (uint32_t *)malloc(std::max<uint64_t>(n_records, 1) * 4);
+  e->rec_layer = (uint8_t *)malloc(std::max<uint64_t>(n_records, 1));
+  e->entry_points = (uint32_t *)malloc(std::max<uint64_t>(n_eps, 1) * 4);
+  const size_t ob = (n_records + 1) * 8, vb = std::max<uint64_t>(value_bytes, 16);
+  if (hipHostMalloc((void **)&e->val_offset, ob, hipHostMallocDefault) != hipSuccess) e->val_offset = nullptr;
+  if (e->val_offset && hipHostMalloc((void **)&e->values, vb, hipHostMallocDefault) != hipSuccess) e->values = nullptr;
+  if (!e->val_offset || !e->values) { // no device to pin memory for
+    if (e->val_offset) (void)hipHostFree((void *)e->val_offset);
+    (void)hipGetLastError();
+    o->pageable = true;
+    e->val_offset = (uint64_t *)malloc(ob);
+    e->values = (uint8_t *)malloc(vb);
+  }
+  if (!e->rec_item || !e->rec_layer || !e->entry_points || !e->val_offset || !e->values) {
+    hny_encoded_links_free(e);
+    return nullptr;
+  }
+  return e;
 }
 void hny_encoded_delta_free(hny_encoded_delta *d) {
   if (!d) return;
@@ -2861,7 +3035,7 @@ int hny_builder_finish_encoded(hny_builder *b, hny_encoded_links **out) {
   const u32 *item_ids = nullptr;
   if (int rc = ensure_item_ids(b, &item_ids)) return rc;
   std::unique_ptr<hny_encoded_links, void (*)(hny_encoded_links *)> eh(
-      (hny_encoded_links *)calloc(1, sizeof(hny_encoded_links)), hny_encoded_links_free);
+      (hny_encoded_links *)calloc(1, sizeof(OwnedEncodedLinks)), hny_encoded_links_free);
   hny_encoded_links *e = eh.get();
   if (!e) return fail(HNY_ERR_OOM, "out of host memory for %llu records", (unsigned long long)nrec);
   EncodeLinksArgs a = encode_args(b, item_ids);
@@ -3001,6 +3175,54 @@ int hny_builder_load_f32(const hny_build_opts *opts, const hny_items *f32_items,
   return create_impl(opts, f32_items, &inc, out, true);
 }
 
+// the _encoded forms: `stored` checked before create_impl opens a device
+static int create_encoded(const hny_build_opts *opts, const hny_items *items, IncrementalSpec inc,
+                          const hny_encoded_links *stored, hny_builder **out, bool f32) {
+  if (!out) return fail(HNY_ERR_INVALID_ARG, "null out");
+  *out = nullptr;
+  if (!opts || !items) return fail(HNY_ERR_INVALID_ARG, "null argument");
+  if (int rc = check_encoded_input(stored)) return rc;
+  inc.enc = stored;
+  return create_impl(opts, items, &inc, out, f32);
+}
+int hny_builder_load_encoded(const hny_build_opts *opts, const hny_items *items, const hny_encoded_links *stored,
+                             hny_builder **out) {
+  return create_encoded(opts, items, IncrementalSpec{nullptr, 0, nullptr, 0, nullptr, true}, stored, out, false);
+}
+int hny_builder_load_encoded_f32(const hny_build_opts *opts, const hny_items *f32_items,
+                                 const hny_encoded_links *stored, hny_builder **out) {
+  return create_encoded(opts, f32_items, IncrementalSpec{nullptr, 0, nullptr, 0, nullptr, true}, stored, out, true);
+}
+int hny_builder_create_incremental_encoded(const hny_build_opts *opts, const hny_items *items,
+                                           const uint32_t *to_insert, uint64_t n_insert, const uint32_t *to_delete,
+                                           uint64_t n_delete, const hny_encoded_links *stored, hny_builder **out) {
+  return create_encoded(opts, items, IncrementalSpec{to_insert, n_insert, to_delete, n_delete, nullptr}, stored, out,
+                        false);
+}
+int hny_build_incremental_encoded(const hny_build_opts *opts, const hny_items *items, const uint32_t *to_insert,
+                                  uint64_t n_insert, const uint32_t *to_delete, uint64_t n_delete,
+                                  const hny_encoded_links *stored, hny_graph **out) {
+  if (!out) return fail(HNY_ERR_INVALID_ARG, "null out");
+  *out = nullptr;
+  if (!opts || !items) return fail(HNY_ERR_INVALID_ARG, "null argument");
+  if (int rc = check_encoded_input(stored)) return rc;
+  IncrementalSpec inc{to_insert, n_insert, to_delete, n_delete, nullptr};
+  inc.enc = stored;
+  return run_build(opts, items, &inc, false, out);
+}
+int hny_encoded_links_measure(const hny_encoded_links *stored, int32_t device, uint32_t *max_links0,
+                              uint32_t *max_links_upper, uint64_t *n_links) {
+  if (!max_links0 || !max_links_upper || !n_links) return fail(HNY_ERR_INVALID_ARG, "null argument");
+  *max_links0 = *max_links_upper = 0, *n_links = 0;
+  if (int rc = check_encoded_input(stored)) return rc;
+  if (int rc = use_device(device)) return rc;
+  ImportLinksArgs a;
+  ImportRun R;
+  if (int rc = import_measure(stored, 0xFFFFFFFFu, 0xFFFFFFFFu, nullptr, a, R)) return rc;
+  *max_links0 = R.max0, *max_links_upper = R.maxu, *n_links = R.n_links;
+  return HNY_OK;
+}
+
 // hny_multi.cpp: the distance-evaluation counters of a replica.  Work that every rank repeats (ramp-up
 // batches, small deferred sets, fill_gaps) is counted on rank 0 only: the other ranks point their kernels'
 // counter block at a scratch copy meanwhile (the error words in it are the same on every replica).
@@ -3067,6 +3289,7 @@ extern "C" int hny_internal_lds_layout(int family, const uint32_t p[4], uint64_t
     case LDS_PRUNE_N8: (void)prune_n8_lds(c, p[0], p[1], (int)p[2]); break;
     case LDS_APPLY_N8: (void)apply_n8_lds(c, p[0], (int)p[1]); break;
     case LDS_ENCODE_LINKS: (void)encode_links_lds(c, p[0], p[1]); break;
+    case LDS_DECODE_LINKS: (void)decode_links_lds(c, p[0], p[1]); break;
     default: return fail(HNY_ERR_INVALID_ARG, "hny_internal_lds_layout: no such kernel family");
   }
   if (c.n_spans > *n) return fail(HNY_ERR_INVALID_ARG, "hny_internal_lds_layout: too few spans");

@@ -397,7 +397,7 @@ struct LdsCarve {
 // every form of these functions tried moved the register allocation of instances that sit on a measured budget.
 enum LdsFamily { // hny_internal_lds_layout: the family, and its sizes in the order of the function's parameters
   LDS_HEAP_WALK, LDS_NNS, LDS_NNS_LINEAR, LDS_EXACT_TOPK, LDS_EXACT_SCORES, LDS_PRUNE, LDS_APPLY, LDS_FILL_GAPS,
-  LDS_PRUNE_N8, LDS_APPLY_N8, LDS_ENCODE_LINKS
+  LDS_PRUNE_N8, LDS_APPLY_N8, LDS_ENCODE_LINKS, LDS_DECODE_LINKS
 };
 
 // k_walk_heap, k_nns<.., true>: the scratch of a distance pass and the entry points
@@ -562,6 +562,19 @@ HNY_LDS_FN EncodeLinksLds encode_links_lds(LdsCarve &c, u32 stage_bytes, u32 rec
   EncodeLinksLds L;
   L.stage = c.take_rows(stage_bytes);
   L.off = c.take<u64>((size_t)recs + 1);
+  return L;
+}
+// k_links_decode (hny_import.hip): one window of the workgroup's input range, and the byte offsets of its records
+struct DecodeLinksLds {
+  unsigned char *stage; // [stage_bytes] loaded from global memory as 16-byte words
+  u64 *off;             // [recs + 1]
+  u32 *bad;             // [2] ids outside the universe, order violations: this block's counts
+};
+HNY_LDS_FN DecodeLinksLds decode_links_lds(LdsCarve &c, u32 stage_bytes, u32 recs) {
+  DecodeLinksLds L;
+  L.stage = c.take_rows(stage_bytes);
+  L.off = c.take<u64>((size_t)recs + 1);
+  L.bad = c.take<u32>(2);
   return L;
 }
 // bytes of a layout: HNY_LDS_BYTES(prune_lds, rcap, capmax) runs the function on a null cursor
@@ -784,6 +797,34 @@ struct EncodeLinksArgs {
 hipError_t hnyk_encode_links_sizes(const EncodeLinksArgs &a, hipStream_t st);
 hipError_t hnyk_encode_links_emit(const EncodeLinksArgs &a, hipStream_t st);
 hipError_t hnyk_exclusive_scan_u64(void *temp, size_t *temp_bytes, const u64 *in, u64 *out, size_t n, hipStream_t st);
+
+// ---- encoded import (hny_import.hip): stored Links values checked and decoded on the device ----
+enum { // what k_links_measure finds wrong with a value, in the order it looks
+  IMP_OK = 0, IMP_TAG, IMP_COOKIE, IMP_NC, IMP_KEYS, IMP_BITMAP, IMP_LENGTH, IMP_OFFSET, IMP_TOO_LONG
+};
+struct ImportBlockOut { // one per block of k_links_measure; the host finishes the reduction
+  u64 n_links, first_bad; // first_bad: the lowest record of this block with a code, ~0 = none
+  u32 max0, maxu, code, info; // info: the list's length (IMP_TOO_LONG) or the container (the others)
+};
+struct ImportLinksArgs {
+  const u64 *off;                 // [n_recs + 1] val_offset: ascending, every value >= 9 bytes (checked on the host)
+  const unsigned char *values;    // [off[n_recs]]
+  const unsigned char *rec_layer; // [n_recs]
+  u64 n_recs;
+  u32 cap0, capu;                 // k_links_measure: the longest list allowed on layer 0 / above
+  ImportBlockOut *block_out;      // k_links_measure: [gridDim.x]
+  // k_links_decode
+  const u32 *rec_list;            // [n_recs] as EncodeLinksArgs::rec_list
+  const u32 *item_ids;            // [n] slot -> item id, ascending; null = the identity
+  u32 n, M, M0;
+  u32 *d0_ids, *du_ids;           // the lists, HNY_SENT everywhere on entry
+  u32 *bad;                       // [2 * gridDim.x] per block: ids outside the universe, order violations
+  u32 lg_group;                   // set by the launcher: log2 of the lanes per record, as for EncodeLinksArgs
+};
+u32 hnyk_import_measure_grid(u64 n_recs);
+u32 hnyk_import_decode_grid(u64 n_recs);
+hipError_t hnyk_import_links_measure(const ImportLinksArgs &a, hipStream_t st);
+hipError_t hnyk_import_links_decode(const ImportLinksArgs &a, hipStream_t st);
 
 // ---- encoded delta export (hny_export.hip): the table of the records an update changed, and the
 // keys it removed, made on the device from k_diff_records' flags: a count pass, two exclusive scans, a write pass ----

@@ -616,4 +616,70 @@ int hny_lmdb_scan(const hny_lmdb_env *e, const uint8_t *lo, size_t lo_len, const
   return HNY_OK;
 }
 
+// every Links record of `index` as the struct hny_builder_load_encoded takes: one cursor walk that
+// notes where the values lie in the mapping, then one memcpy per value into the (pinned) buffer
+namespace {
+struct LinksWalk {
+  std::vector<uint32_t> item;
+  std::vector<uint8_t> layer;
+  std::vector<std::pair<const uint8_t *, size_t>> val;
+  uint64_t bytes = 0;
+};
+int links_walk_sink(void *ctx, const uint8_t *key, size_t klen, const uint8_t *val, size_t vlen) {
+  LinksWalk &w = *(LinksWalk *)ctx;
+  if (klen != 8) return failf(HNY_ERR_IO, "Links key of %zu bytes", klen);
+  w.item.push_back((uint32_t)key[3] << 24 | (uint32_t)key[4] << 16 | (uint32_t)key[5] << 8 | key[6]);
+  w.layer.push_back(key[7]);
+  w.val.push_back({val, vlen});
+  w.bytes += vlen;
+  return HNY_OK;
+}
+} // namespace
+hny_encoded_links *hny_internal_encoded_links_alloc(uint64_t n_records, uint64_t value_bytes, uint32_t n_eps);
+
+int hny_lmdb_read_links(const hny_lmdb_env *e, uint16_t index, hny_encoded_links **out) {
+  if (!e || !out) return failf(HNY_ERR_INVALID_ARG, "hny_lmdb_read_links: null argument");
+  *out = nullptr;
+  // Metadata (metadata.rs:28-48), as far as its lengths: name NUL | dim u32 BE | size u32 BE | item bitmap | entry
+  // points (native u32 each) | level
+  const uint8_t mkey[8] = {(uint8_t)(index >> 8), (uint8_t)index, 0, 0, 0, 0, 0, 0};
+  const uint8_t *mv = nullptr;
+  size_t ml = 0;
+  int rc = hny_lmdb_get(e, mkey, 8, &mv, &ml);
+  if (rc < 0) return rc;
+  if (!rc) return failf(HNY_ERR_MISSING_KEY, "index %u has no Metadata record", index);
+  const uint8_t *nul = (const uint8_t *)memchr(mv, 0, ml);
+  size_t at = nul ? (size_t)(nul - mv) + 1 : ml;
+  if (ml - at < 8) return failf(HNY_ERR_IO, "Metadata record of index %u: %zu bytes end inside its header", index, ml);
+  const size_t blob = (size_t)mv[at + 4] << 24 | (size_t)mv[at + 5] << 16 | (size_t)mv[at + 6] << 8 | mv[at + 7];
+  at += 8;
+  if (ml - at < blob + 1 || (ml - at - blob - 1) % 4)
+    return failf(HNY_ERR_IO, "Metadata record of index %u: %zu bytes do not hold a %zu-byte item bitmap, entry points and "
+                 "a level", index, ml, blob);
+  at += blob;
+  const uint32_t n_eps = (uint32_t)((ml - at - 1) / 4);
+
+  LinksWalk w;
+  const uint8_t lo[8] = {mkey[0], mkey[1], 2, 0, 0, 0, 0, 0}, hi[8] = {mkey[0], mkey[1], 2, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF};
+  if ((rc = hny_lmdb_scan(e, lo, 8, hi, 8, links_walk_sink, &w))) return rc;
+  const uint64_t nr = w.item.size();
+  hny_encoded_links *L = hny_internal_encoded_links_alloc(nr, w.bytes, n_eps);
+  if (!L) return failf(HNY_ERR_OOM, "out of host memory for %llu Links records", (unsigned long long)nr);
+  uint64_t *off = (uint64_t *)L->val_offset;
+  uint8_t *values = (uint8_t *)L->values;
+  off[0] = 0;
+  for (uint64_t r = 0; r < nr; r++) {
+    memcpy(values + off[r], w.val[r].first, w.val[r].second);
+    off[r + 1] = off[r] + w.val[r].second;
+  }
+  if (nr) {
+    memcpy((void *)L->rec_item, w.item.data(), nr * 4);
+    memcpy((void *)L->rec_layer, w.layer.data(), nr);
+  }
+  if (n_eps) memcpy((void *)L->entry_points, mv + at, (size_t)n_eps * 4);
+  L->max_level = mv[ml - 1];
+  *out = L;
+  return HNY_OK;
+}
+
 } // extern "C"

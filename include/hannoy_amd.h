@@ -712,12 +712,49 @@ typedef struct {
 /* Accepts exactly the builders hny_builder_finish accepts and refuses the others with its codes (*out = NULL); the
  * builder stays usable, and neither call changes what the other returns, in either order. */
 int hny_builder_finish_encoded(hny_builder *b, hny_encoded_links **out);
-void hny_encoded_links_free(hny_encoded_links *e); /* NULL is fine */
+/* NULL is fine.  Only for structs this library returned (hny_builder_finish_encoded, hny_lmdb_read_links): it reads
+ * how they were allocated from the library's own bookkeeping behind the struct.  A struct the caller filled in is the
+ * caller's to release. */
+void hny_encoded_links_free(hny_encoded_links *e);
 /* The stream hny_encode_kv(g, ...) emits for the hny_graph g of the same builder, byte for byte: Metadata, Version,
  * every Links record (key from rec_item / rec_layer, value handed to the sink straight from `values`), then
  * (with_items) the Item records.  No device call: `e` may be a struct the caller filled in. */
 int hny_encode_kv_encoded(const hny_encoded_links *e, const hny_build_opts *opts, const hny_items *items,
                           uint16_t index, int with_items, hny_kv_sink sink, void *ctx);
+
+/* ---- encoded import: the way back.  Each call yields, byte for byte, what its namesake without
+ * `_encoded` yields on the hny_prev_graph `prev` whose record r holds the ids RoaringBitmap::deserialize_from reads
+ * from values[val_offset[r] + 1 .. val_offset[r + 1]) — searches, finish, finish_encoded, export_items, an
+ * incremental build's records and counters, successors.  (A loaded builder, however it was loaded, keeps the stored
+ * lists for its searches and its successors; its finish and finish_encoded do not export them, so finish_encoded of a
+ * builder loaded from `stored` is not a round trip.  The successor of an empty hny_builder_update exports them.)  The values are checked and decoded on the device; the host reads n_records, rec_item, rec_layer,
+ * val_offset, entry_points, n_entry_points and max_level of `stored` (a struct the caller may fill in; the counters
+ * and timings are ignored) and never sees a neighbour id.  The universe is therefore item ids U rec_item U to_delete U
+ * entry points, and a list that names an id outside it makes the call return HNY_ERR_UNSUPPORTED with their number
+ * in hny_last_error: hny_builder_load takes such a graph (the reference never writes one).
+ * HNY_ERR_INVALID_ARG before any device work (*out = NULL): null arguments, val_offset[0] != 0, decreasing offsets, a
+ * value shorter than 9 bytes, records not strictly ascending by (item, layer), a layer above 14, values == NULL with
+ * bytes to read; then create's own checks.  After the measure pass and before anything is decoded, with the first
+ * offending record named in hny_last_error: HNY_ERR_INVALID_ARG for a tag other than 0x01, a container count or
+ * cardinalities that disagree with the value's length, container keys not strictly ascending, a wrong offset-header
+ * entry; HNY_ERR_UNSUPPORTED for a cookie other than 12346 (run containers), a container of more than 4 096 ids
+ * (bitmap container), a list longer than M0 on layer 0 or M above.  Low-16 values not strictly ascending inside a
+ * container: HNY_ERR_INVALID_ARG from the decode pass.  No byte outside a record's value is read while it is parsed;
+ * nothing is created on any error. */
+int hny_builder_load_encoded(const hny_build_opts *opts, const hny_items *items, const hny_encoded_links *stored,
+                             hny_builder **out);
+int hny_builder_load_encoded_f32(const hny_build_opts *opts, const hny_items *f32_items,
+                                 const hny_encoded_links *stored, hny_builder **out);
+int hny_builder_create_incremental_encoded(const hny_build_opts *opts, const hny_items *items,
+                                           const uint32_t *to_insert, uint64_t n_insert, const uint32_t *to_delete,
+                                           uint64_t n_delete, const hny_encoded_links *stored, hny_builder **out);
+int hny_build_incremental_encoded(const hny_build_opts *opts, const hny_items *items, const uint32_t *to_insert,
+                                  uint64_t n_insert, const uint32_t *to_delete, uint64_t n_delete,
+                                  const hny_encoded_links *stored, hny_graph **out); /* one device */
+/* longest layer-0 list, longest upper list and the number of links of `stored`, from the container headers alone (the
+ * measure pass without caps; the format errors above are refused the same way) */
+int hny_encoded_links_measure(const hny_encoded_links *stored, int32_t device, uint32_t *max_links0,
+                              uint32_t *max_links_upper, uint64_t *n_links);
 
 /* ---- encoded delta export: what hny_builder_finish_delta returns for a successor builder, with
  * the values of the changed records serialised on the device.  The table of changed records and the removed keys are
@@ -781,6 +818,11 @@ int hny_lmdb_get(const hny_lmdb_env *e, const uint8_t *key, size_t key_len, cons
  * also checks the page invariants it passes (flags, bounds, key order, counts) */
 int hny_lmdb_scan(const hny_lmdb_env *e, const uint8_t *lo, size_t lo_len, const uint8_t *hi,
                   size_t hi_len, hny_kv_sink sink, void *ctx);
+/* every Links record of `index` in key order as an hny_encoded_links the library owns (hny_encoded_links_free; its
+ * val_offset and values are pinned where a device is there to pin them for), with the entry points and max_level
+ * from the tail of the Metadata record, whose item bitmap is skipped, not decoded: what hny_builder_load_encoded
+ * takes.  One cursor walk, one memcpy per value.  HNY_ERR_MISSING_KEY if the index has no Metadata record. */
+int hny_lmdb_read_links(const hny_lmdb_env *e, uint16_t index, hny_encoded_links **out);
 void hny_lmdb_close(hny_lmdb_env *e);
 
 const char *hny_last_error(void);
