@@ -45,6 +45,10 @@ EXPORTED = [
     "hny_builder_exact_knn_bitsets", "hny_builder_exact_knn_bitsets_f32",
     "hny_builder_exact_range", "hny_builder_exact_range_f32", "hny_builder_exact_range_count",
     "hny_builder_exact_range_count_f32", "hny_range_result_free",
+    "hny_builder_exact_range_filtered", "hny_builder_exact_range_filtered_f32",
+    "hny_builder_exact_range_count_filtered", "hny_builder_exact_range_count_filtered_f32",
+    "hny_builder_exact_range_bitsets", "hny_builder_exact_range_bitsets_f32",
+    "hny_builder_exact_range_count_bitsets", "hny_builder_exact_range_count_bitsets_f32",
     "hny_builder_finish_encoded", "hny_encoded_links_free", "hny_encode_kv_encoded",
     "hny_builder_finish_delta_encoded", "hny_encoded_delta_free",
     "hny_builder_load_encoded", "hny_builder_load_encoded_f32", "hny_builder_create_incremental_encoded",
@@ -444,6 +448,14 @@ def load_library():
     L.hny_builder_exact_range_count.argtypes = [vp, C.POINTER(RangeOpts), C.c_uint64, vp, C.c_size_t, vp, vp, vp]
     L.hny_builder_exact_range_count_f32.restype = C.c_int
     L.hny_builder_exact_range_count_f32.argtypes = [vp, C.POINTER(RangeOpts), C.c_uint64, vp, C.c_size_t, vp]
+    for kind, struct in (("filtered", QueryFilters), ("bitsets", QueryBitsets)):
+        for count in ("", "_count"):
+            plain = "hny_builder_exact_range" + count
+            fn, f32 = getattr(L, f"{plain}_{kind}"), getattr(L, f"{plain}_{kind}_f32")
+            fn.restype = f32.restype = C.c_int
+            fn.argtypes = getattr(L, plain).argtypes[:2] + [C.POINTER(struct)] + getattr(L, plain).argtypes[2:]
+            f32.argtypes = (getattr(L, plain + "_f32").argtypes[:2] + [C.POINTER(struct)] +
+                            getattr(L, plain + "_f32").argtypes[2:])
     L.hny_range_result_free.restype = None
     L.hny_range_result_free.argtypes = [C.POINTER(RangeResult)]
     L.hny_builder_exact_rows_read.restype = C.c_uint64
@@ -1654,20 +1666,27 @@ class Builder:
         return self._search("hny_builder_exact_knn", opts, _query_source(query_items, qf32, qcodes, qheaders),
                             qf32 is not None)
 
-    def _range(self, radius, count_only, qcodes, qheaders, candidates, query_items, cancel, qf32, max_total):
+    def _range(self, radius, count_only, qcodes, qheaders, candidates, query_items, cancel, qf32, max_total,
+               filters=None):
+        """One call of hny_builder_exact_range in the form the arguments name; `filters`: ("filtered" | "bitsets",
+        QueryFilters.pack's / QueryBitsets.pack's result) for the calls with a filter per query"""
         (nq, qc, qs, qh, qi), _arrays = _query_source(query_items, qf32, qcodes, qheaders)
         ro, _keep, flag = _range_opts(radius, nq, candidates, cancel, max_total)
+        if filters is not None and len(filters[1][1][2]) != nq:
+            raise ValueError(f"filter_of has {len(filters[1][1][2])} entries for {nq} queries")
         self._cancel_flag = flag
         L = load_library()
-        name = "hny_builder_exact_range" + ("_count" if count_only else "") + ("_f32" if qf32 is not None else "")
+        name = ("hny_builder_exact_range" + ("_count" if count_only else "") +
+                ("" if filters is None else "_" + filters[0]) + ("_f32" if qf32 is not None else ""))
+        head = (self._h, C.byref(ro)) + (() if filters is None else (C.byref(filters[1][0]),))
         src = (nq, qc, qs) if qf32 is not None else (nq, qc, qs, qh, qi)
         if count_only:
             counts = np.zeros(nq, np.uint64)
-            _check(getattr(L, name)(self._h, C.byref(ro), *src, _p(counts)))
+            _check(getattr(L, name)(*head, *src, _p(counts)))
             self.did_cancel = bool(flag.value)
             return counts
         res = C.POINTER(RangeResult)()
-        _check(getattr(L, name)(self._h, C.byref(ro), *src, C.byref(res)))
+        _check(getattr(L, name)(*head, *src, C.byref(res)))
         try:
             r = res.contents
             offsets = np.ctypeslib.as_array(r.offsets, (nq + 1,)).copy()
@@ -1701,6 +1720,49 @@ class Builder:
     def exact_range_count_f32(self, queries, radius, **kw):
         """exact_range_count(by_vector) with f32 queries, encoded on the device"""
         return self.exact_range_count(radius, qf32=_f32_rows(queries), **kw)
+
+    def exact_range_filtered(self, radius, filters, filter_of, qcodes=None, qheaders=None, query_items=None,
+                             cancel=None, qf32=None, max_total=0):
+        """hny_builder_exact_range_filtered: exact_range with one .candidates() filter per query, `filters` and
+        `filter_of` as in nns_filtered.  The rows of the queries of one filter equal exact_range(candidates=that
+        filter) on those queries alone; the result is in call order."""
+        qf = ("filtered", QueryFilters.pack(filters, filter_of))
+        return self._range(radius, False, qcodes, qheaders, None, query_items, cancel, qf32, max_total, qf)
+
+    def exact_range_filtered_f32(self, queries, radius, filters, filter_of, **kw):
+        """exact_range_filtered(by_vector) with f32 queries, encoded on the device"""
+        return self.exact_range_filtered(radius, filters, filter_of, qf32=_f32_rows(queries), **kw)
+
+    def exact_range_count_filtered(self, radius, filters, filter_of, qcodes=None, qheaders=None, query_items=None,
+                                   cancel=None, qf32=None):
+        """hny_builder_exact_range_count_filtered: the sizes of exact_range_filtered's rows alone, one scan"""
+        qf = ("filtered", QueryFilters.pack(filters, filter_of))
+        return self._range(radius, True, qcodes, qheaders, None, query_items, cancel, qf32, 0, qf)
+
+    def exact_range_count_filtered_f32(self, queries, radius, filters, filter_of, **kw):
+        """exact_range_count_filtered(by_vector) with f32 queries, encoded on the device"""
+        return self.exact_range_count_filtered(radius, filters, filter_of, qf32=_f32_rows(queries), **kw)
+
+    def exact_range_bitsets(self, radius, bits, n_bits, filter_of, qcodes=None, qheaders=None, query_items=None,
+                            cancel=None, qf32=None, max_total=0):
+        """hny_builder_exact_range_bitsets: exact_range_filtered with the filters as bitsets over item ids, `bits`,
+        `n_bits` and `filter_of` as in nns_bitsets.  Equal to exact_range_filtered on the set bits of each filter."""
+        qb = ("bitsets", QueryBitsets.pack(bits, n_bits, filter_of))
+        return self._range(radius, False, qcodes, qheaders, None, query_items, cancel, qf32, max_total, qb)
+
+    def exact_range_bitsets_f32(self, queries, radius, bits, n_bits, filter_of, **kw):
+        """exact_range_bitsets(by_vector) with f32 queries, encoded on the device"""
+        return self.exact_range_bitsets(radius, bits, n_bits, filter_of, qf32=_f32_rows(queries), **kw)
+
+    def exact_range_count_bitsets(self, radius, bits, n_bits, filter_of, qcodes=None, qheaders=None, query_items=None,
+                                  cancel=None, qf32=None):
+        """hny_builder_exact_range_count_bitsets: the sizes of exact_range_bitsets' rows alone, one scan"""
+        qb = ("bitsets", QueryBitsets.pack(bits, n_bits, filter_of))
+        return self._range(radius, True, qcodes, qheaders, None, query_items, cancel, qf32, 0, qb)
+
+    def exact_range_count_bitsets_f32(self, queries, radius, bits, n_bits, filter_of, **kw):
+        """exact_range_count_bitsets(by_vector) with f32 queries, encoded on the device"""
+        return self.exact_range_count_bitsets(radius, bits, n_bits, filter_of, qf32=_f32_rows(queries), **kw)
 
     def exact_knn_filtered_f32(self, queries, filters, filter_of, **kw):
         """exact_knn_filtered(by_vector) with f32 queries, encoded on the device"""
@@ -1744,5 +1806,6 @@ class Builder:
                             _query_source(query_items, qf32, qcodes, qheaders), qf32 is not None, qb)
 
     def exact_rows_read(self):
-        """(tile, row) loads of the dense scan in the last exact_knn_filtered call on this builder; 0 if none ran"""
+        """(tile, row) loads of the dense scan in the last exact_knn_filtered / exact_range_filtered call (or their
+        bitsets forms) on this builder, both passes of a range call; 0 if none ran"""
         return int(load_library().hny_builder_exact_rows_read(self._h))

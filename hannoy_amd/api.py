@@ -635,6 +635,7 @@ class QueryBuilder:
         self._per_query = None
         self._bitsets = None
         self._radius = None
+        self._within_filtered = False
 
     def ef_search(self, ef):
         self._ef = int(ef)
@@ -709,13 +710,16 @@ class QueryBuilder:
         self._exact = True
         return self
 
-    def within(self, radius):
+    def within(self, radius, filtered=False):
         """only the hits with distance <= radius, a scalar or one value per query of by_vectors / by_items, which
         then return (offsets [nq + 1], ids, dists): the hits of query i are ids / dists[offsets[i]:offsets[i + 1]].
         With .exact() every such item (hny_builder_exact_range; count is not read, .candidates() is honoured);
         otherwise the graph search with its count, each row cut to the hits within the radius.  A by_item query
-        without an answer has no hits"""
+        without an answer has no hits.
+        filtered=True, which needs .exact(): candidates_per_query() / candidates_bitsets() are honoured, one filter
+        per query (hny_builder_exact_range_filtered / _bitsets); without it a filter per query is refused"""
         self._radius = radius
+        self._within_filtered = bool(filtered)
         return self
 
     def _cut(self, hits):
@@ -732,10 +736,20 @@ class QueryBuilder:
         offsets[1:] = np.cumsum(keep.sum(axis=1), dtype=np.uint64)
         return offsets, ids[keep], dists[keep]
 
-    def _within_exact(self, **source):
+    def _within_exact(self, nq, **source):
+        b = self.reader._b
+        if self._within_filtered and self._bitsets is not None:
+            return b.exact_range_bitsets(self._radius, *self._id_bits(nq), **source)[:3]
+        if self._within_filtered and self._per_query is not None:
+            return b.exact_range_filtered(self._radius, *self._filters(nq), **source)[:3]
         if self._per_query is not None or self._bitsets is not None:
-            raise ValueError("within().exact() takes one .candidates() for the whole call, not a filter per query")
-        return self.reader._b.exact_range(self._radius, candidates=self._candidates, **source)[:3]
+            raise ValueError("within().exact() takes one .candidates() for the whole call, not a filter per query "
+                             "(within(radius, filtered=True) does)")
+        return b.exact_range(self._radius, candidates=self._candidates, **source)[:3]
+
+    def _check_within(self):
+        if self._radius is not None and self._within_filtered and not self._exact:
+            raise ValueError("within(radius, filtered=True) needs .exact(): the graph search has no range form")
 
     def _kw(self):
         return dict(k=self.count, ef_search=self._ef, candidates=self._candidates,
@@ -743,13 +757,14 @@ class QueryBuilder:
 
     def by_vectors(self, vectors, cancel=None):
         """batched by_vector: (ids [nq, count], distances, counts)"""
+        self._check_within()
         r = self.reader
         q = np.ascontiguousarray(vectors, np.float32)
         if q.ndim != 2 or q.shape[1] != r.dimensions:
             raise InvalidVecDimension(f"expected {r.dimensions}, received {q.shape[-1]}")
         if self._radius is not None:
             if self._exact:
-                return self._within_exact(qf32=capi._f32_rows(q), cancel=cancel)
+                return self._within_exact(len(q), qf32=capi._f32_rows(q), cancel=cancel)
             radius, self._radius = self._radius, None
             try:
                 hits = self.by_vectors(q, cancel=cancel)
@@ -772,9 +787,11 @@ class QueryBuilder:
 
     def by_items(self, items, cancel=None):
         """batched by_item; counts == capi.NNS_NONE where the reference returns None"""
+        self._check_within()
         if self._radius is not None:
             if self._exact:
-                return self._within_exact(query_items=capi.u32_ids(items), cancel=cancel)
+                items = capi.u32_ids(items)
+                return self._within_exact(len(items), query_items=items, cancel=cancel)
             radius, self._radius = self._radius, None
             try:
                 hits = self.by_items(items, cancel=cancel)

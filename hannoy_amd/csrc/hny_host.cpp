@@ -4178,8 +4178,13 @@ struct DenseScan {
   ExactArgs a{};
   uint64_t q0 = 0; // the block: queries [q0, q0 + cnt) of the call, n_mem of them with a row
   uint32_t cnt = 0, n_mem = 0;
+  uint64_t q_end; // where the blocks stop: q.nq, or the end of the part of `q` a caller walks (a filter round's)
+  // A filter per query for a range consumer (alloc_filters): the staged block's filter_of, which
+  // aim() hands to `a` and `r` with the members, and the tile masks of the members aimed at
+  DevBuf<u32> dfof, dtile;
+  size_t tile_words = 0;
 
-  DenseScan(hny_builder *b, const QuerySet &q, RangeArgs *r = nullptr) : b(b), q(q), r(r), st{b, q} {}
+  DenseScan(hny_builder *b, const QuerySet &q, RangeArgs *r = nullptr) : b(b), q(q), r(r), st{b, q}, q_end(q.nq) {}
   int alloc(uint32_t qblock, const u32 *mask) { // blocks of at most qblock queries; mask: C over slots, on the device
     const uint32_t sstride = (std::min<uint32_t>(b->n, HNY_EXACT_SLAB) + 63u) & ~63u;
     if (int rc = st.alloc(qblock)) return rc;
@@ -4192,10 +4197,22 @@ struct DenseScan {
     if (r) r->scores = dscores.p, r->score_stride = sstride, r->mask = mask;
     return HNY_OK;
   }
+  int alloc_filters(uint32_t qblock) { // after alloc()
+    tile_words = (size_t)((qblock + a.qt - 1) / a.qt) * (HNY_EXACT_SLAB / 32u);
+    HIP_TRY(dfof.alloc(qblock));
+    HIP_TRY(dtile.alloc(tile_words));
+    a.tile_mask = dtile.p;
+    return HNY_OK;
+  }
+  // the bitsets that the staged filter_of entries index: a filter round's
+  void filters(const u32 *masks, u32 mask_stride) {
+    a.masks = masks, a.mask_stride = mask_stride;
+    if (r) r->masks = masks, r->mask_stride = mask_stride;
+  }
   // the block at q0: its members (the kernels index a block's queries by member), each at 0 hits
   uint32_t block(uint64_t at, uint32_t qblock) {
     q0 = at;
-    cnt = (uint32_t)std::min<uint64_t>(qblock, q.nq - q0);
+    cnt = (uint32_t)std::min<uint64_t>(qblock, q_end - q0);
     st.n_slots = n_mem = st.members_of(q0, cnt);
     for (uint32_t j = 0; j < n_mem; j++) q.out_counts[query_of(j)] = 0u, st.slots[j] = st.slots[st.members[j]];
     return n_mem;
@@ -4208,7 +4225,8 @@ struct DenseScan {
     a.q_rows = st.dq.p ? st.dq.p + (size_t)m0 * b->g.row_stride : nullptr;
     a.q_norms = st.norms() ? st.norms() + m0 : nullptr;
     a.nq = m1 - m0;
-    if (r) r->nq = a.nq, r->radius = radius + m0;
+    if (dfof.p) a.filter_of = dfof.p + m0;
+    if (r) r->nq = a.nq, r->radius = radius + m0, r->filter_of = dfof.p ? dfof.p + m0 : nullptr;
   }
   // Every slab for the queries aimed at: probe, before() if there is one (the filtered top-k's tile masks), the
   // scores, probe, consume().  *stopped: the closure fired, the stream is idle, the consumer's buffers hold a part
@@ -4993,6 +5011,23 @@ struct ExactFilters {
 // DenseScan's slab loop; a block that does not finish reports 0 hits.  dmask: the call-wide mask (the live items for
 // the members without a filter); kk: the most hits of a row.  With F the scan reads only what a tile wants; tiles are
 // as homogeneous as the order of `qs` makes them: the caller hands the queries over in filter order, unfiltered last.
+// Skipping pays where tiles want few rows.  An upper bound on what the tiles of `n_mem` members want: per tile the
+// counts of its distinct filters (members come in filter order; fof / count_of: the members' filter and its live
+// candidates), at most n.  Where that bound is above half of tiles x n, the masks are not made and every row is
+// read: heterogeneous tiles of wide filters measured 2 - 5 % slower with the skip than without
+static bool exact_tiles_sparse(const u32 *fof, uint32_t n_mem, uint32_t qt, uint32_t n,
+                               const std::function<u32(uint32_t)> &count_of) {
+  uint64_t wanted = 0;
+  const uint32_t n_tiles = (n_mem + qt - 1) / qt;
+  for (uint32_t t0 = 0; t0 < n_mem; t0 += qt) {
+    uint64_t w = 0;
+    for (uint32_t j = t0; j < std::min(n_mem, t0 + qt); j++)
+      if (j == t0 || fof[j] != fof[j - 1]) w += count_of(j);
+    wanted += std::min<uint64_t>(w, n);
+  }
+  return wanted * 2 <= (uint64_t)n_tiles * n;
+}
+
 static int exact_dense_run(hny_builder *b, const QuerySet &qs, const u32 *dmask, uint32_t kk, const ExactFilters *F,
                            SearchCancel &sc) {
   const uint32_t n = b->n;
@@ -5038,19 +5073,8 @@ static int exact_dense_run(hny_builder *b, const QuerySet &qs, const u32 *dmask,
       }
       HIP_TRY(hipMemcpyAsync(dfof.p, hfof.data(), (size_t)n_mem * 4, hipMemcpyHostToDevice, b->stream));
       HIP_TRY(hipMemcpyAsync(dkof.p, hkof.data(), (size_t)n_mem * 4, hipMemcpyHostToDevice, b->stream));
-      // Skipping pays where tiles want few rows.  An upper bound on what the block's tiles want: per tile the counts
-      // of its distinct filters (members come in filter order), at most n.  Where that bound is above half of
-      // tiles x n, the masks are not made and every row is read: heterogeneous tiles of wide filters measured 2 - 5 %
-      // slower with the skip than without
-      uint64_t wanted = 0;
-      const uint32_t n_tiles = (n_mem + qt - 1) / qt;
-      for (uint32_t t0 = 0; t0 < n_mem; t0 += qt) {
-        uint64_t w = 0;
-        for (uint32_t j = t0; j < std::min(n_mem, t0 + qt); j++)
-          if (j == t0 || hfof[j] != hfof[j - 1]) w += F->count_of[scan.query_of(j)];
-        wanted += std::min<uint64_t>(w, n);
-      }
-      skip = F->skip && wanted * 2 <= (uint64_t)n_tiles * n;
+      skip = F->skip && exact_tiles_sparse(hfof.data(), n_mem, qt, n,
+                                           [&](uint32_t j) { return F->count_of[scan.query_of(j)]; });
       if (!skip) HIP_TRY(hnyk_fill_u32(dtile.p, 0xFFFFFFFFu, tile_words, b->stream));
     }
     HIP_TRY(hipMemsetAsync(dln.p, 0, (size_t)n_mem * 4, b->stream));
@@ -5308,6 +5332,12 @@ struct RangeScan {
   DevBuf<u64> dcount, dkeys; // dkeys: a run's keys and the sort's second buffer, which then takes the ids and distances
   DevBuf<unsigned char> dtemp;
   uint64_t keys_cap = 0, cap = 0; // pass 2: the keys that half of dkeys holds, and the most of a run
+  // A filter per query (range_filtered_impl), empty without: per query of the set its mask among those of its round
+  // (HNY_SENT: the live items) and how many live candidates that mask holds; hfof: the staged block's entries
+  std::vector<u32> fof, fcount, hfof;
+  bool skip = false;  // HNY_EXACT_SKIP
+  bool tiles = false; // the members aimed at have their tile masks made per slab (range_aim)
+  bool dropped = false; // a cancellation left a block of pass 1 or a run of pass 2 unanswered
   RangeScan(hny_builder *b, const QuerySet &q, const float *radius)
       : radius(radius), scan(b, q, &r),
         qblock((uint32_t)std::min<uint64_t>(HNY_EXACT_QBLOCK, std::max<uint64_t>(q.nq, 1))),
@@ -5348,10 +5378,31 @@ static int range_stage_block(RangeScan &R) {
   for (uint32_t j = 0; j < R.scan.n_mem; j++) R.hradius[j] = R.radius[R.scan.query_of(j)];
   hipStream_t st = R.scan.b->stream;
   HIP_TRY(hipMemcpyAsync(R.dradius.p, R.hradius.data(), (size_t)R.scan.n_mem * 4, hipMemcpyHostToDevice, st));
+  if (R.fof.empty()) return HNY_OK;
+  for (uint32_t j = 0; j < R.scan.n_mem; j++) R.hfof[j] = R.fof[R.scan.query_of(j)];
+  HIP_TRY(hipMemcpyAsync(R.scan.dfof.p, R.hfof.data(), (size_t)R.scan.n_mem * 4, hipMemcpyHostToDevice, st));
   return HNY_OK;
 }
-// pass 1: the device's side of what both passes share, then R.counts on DenseScan's slab loop with k_range_count
-static int range_count_pass(RangeScan &R, const std::vector<u32> &mask, const hny_query_opts *qo) {
+// The members [m0, m1) of the staged block as the scan's queries.  With a filter per query the scan reads what their
+// tiles want: the tile masks are made per slab where exact_tiles_sparse expects them to pay (tiles start at m0, so
+// this is decided per run), and are all ones otherwise
+static int range_aim(RangeScan &R, uint32_t m0, uint32_t m1) {
+  DenseScan &scan = R.scan;
+  scan.aim(m0, m1, R.dradius.p);
+  if (R.fof.empty()) return HNY_OK;
+  R.tiles = R.skip && exact_tiles_sparse(R.hfof.data() + m0, m1 - m0, scan.a.qt, scan.b->n, [&](uint32_t j) {
+              return R.fcount[scan.query_of(m0 + j)];
+            });
+  if (!R.tiles) HIP_TRY(hnyk_fill_u32(scan.dtile.p, 0xFFFFFFFFu, scan.tile_words, scan.b->stream));
+  return HNY_OK;
+}
+// DenseScan's slab loop for the members aimed at, with `consume` after each slab's scores
+static int range_slabs(RangeScan &R, bool *stopped, const DenseScan::Launch &consume) {
+  const DenseScan::Launch tile_masks = [&R] { return hnyk_exact_tile_masks(R.scan.a, R.scan.b->stream); };
+  return R.scan.slabs(R.sc, stopped, consume, R.tiles ? tile_masks : nullptr);
+}
+// the device's side of what both passes share
+static int range_scan_begin(RangeScan &R, const std::vector<u32> &mask, const hny_query_opts *qo) {
   hny_builder *b = R.scan.b;
   HIP_TRY(hipSetDevice(b->device));
   HIP_TRY(R.sc.init(qo));
@@ -5361,20 +5412,33 @@ static int range_count_pass(RangeScan &R, const std::vector<u32> &mask, const hn
   HIP_TRY(R.dradius.alloc(R.qblock));
   HIP_TRY(R.dcount.alloc(R.qblock));
   R.r.count = R.dcount.p;
-  for (uint64_t q0 = 0; q0 < R.scan.q.nq; q0 += R.qblock) {
+  if (R.fof.empty()) return HNY_OK;
+  R.hfof.resize(R.qblock);
+  return R.scan.alloc_filters(R.qblock);
+}
+// pass 1 for the queries [lo, hi) of the set: R.counts on DenseScan's slab loop with k_range_count
+static int range_count_blocks(RangeScan &R, uint64_t lo, uint64_t hi) {
+  hny_builder *b = R.scan.b;
+  R.scan.q_end = hi;
+  for (uint64_t q0 = lo; q0 < hi; q0 += R.qblock) {
     const uint32_t n_mem = R.scan.block(q0, R.qblock);
-    if (n_mem == 0 || R.sc.probe()) continue; // cancelled: nothing of this block is started, 0 hits each
+    if (n_mem == 0) continue;
+    if ((R.dropped |= R.sc.probe())) continue; // cancelled: nothing of this block is started, 0 hits each
     if (int rc = range_stage_block(R)) return rc;
-    R.scan.aim(0, n_mem, R.dradius.p);
+    if (int rc = range_aim(R, 0, n_mem)) return rc;
     HIP_TRY(hipMemsetAsync(R.dcount.p, 0, (size_t)n_mem * 8, b->stream));
     bool stopped;
-    if (int rc = R.scan.slabs(R.sc, &stopped, [&R, b] { return hnyk_range_count(R.r, b->stream); })) return rc;
-    if (stopped) continue; // the block did not finish: 0 hits each
+    if (int rc = range_slabs(R, &stopped, [&R, b] { return hnyk_range_count(R.r, b->stream); })) return rc;
+    if ((R.dropped |= stopped)) continue; // the block did not finish: 0 hits each
     HIP_TRY(hipMemcpyAsync(R.hcount.data(), R.dcount.p, (size_t)n_mem * 8, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(R.sc.wait(b));
     for (uint32_t j = 0; j < n_mem; j++) R.counts[R.scan.query_of(j)] = R.hcount[j];
   }
   return HNY_OK;
+}
+static int range_count_pass(RangeScan &R, const std::vector<u32> &mask, const hny_query_opts *qo) {
+  if (int rc = range_scan_begin(R, mask, qo)) return rc;
+  return range_count_blocks(R, 0, R.scan.q.nq);
 }
 static void range_sizes_out(const RangeScan &R, uint64_t *out_counts) {
   for (uint64_t i = 0; i < R.scan.q.nq; i++) out_counts[i] = R.none32[i] == HNY_NNS_NONE ? HNY_RANGE_NONE : R.counts[i];
@@ -5419,9 +5483,9 @@ static int range_emit_run(RangeScan &R, RangeResult &res, uint32_t m0, uint32_t 
   }
   HIP_TRY(hipMemcpyAsync(R.dseg.p, R.hseg.data(), (size_t)(nsub + 1) * 4, hipMemcpyHostToDevice, b->stream));
   HIP_TRY(hipMemsetAsync(R.dcursor.p, 0, (size_t)nsub * 4, b->stream));
-  R.scan.aim(m0, m1, R.dradius.p);
+  if (int rc = range_aim(R, m0, m1)) return rc;
   R.r.keys = keys;
-  const int rc = R.scan.slabs(R.sc, stopped, [&R, b] { return hnyk_range_emit(R.r, b->stream); });
+  const int rc = range_slabs(R, stopped, [&R, b] { return hnyk_range_emit(R.r, b->stream); });
   if (rc || *stopped) return rc;
   if ((*stopped = R.sc.probe())) {
     HIP_TRY(hipStreamSynchronize(b->stream));
@@ -5443,11 +5507,12 @@ static int range_emit_run(RangeScan &R, RangeResult &res, uint32_t m0, uint32_t 
   return HNY_OK;
 }
 // pass 2: the hits.  The members of a block go in runs ("sub-blocks") whose keys fit the budget, one member at least.
-// A block without hits is passed over before the probe; cancelled, the run at hand and all after it report 0 hits
-static int range_emit_pass(RangeScan &R, RangeResult &res) {
+// A block without hits is passed over before the probe; cancelled, the run at hand and all after it report 0 hits.
+// range_emit_begin, then range_emit_blocks for the queries [lo, hi) of the set, parts in ascending order, then
+// range_emit_end with the first query whose hits were not fetched
+static int range_emit_begin(RangeScan &R) {
   hny_builder *b = R.scan.b;
   const uint32_t n = b->n;
-  const uint64_t nq = R.scan.q.nq;
   R.cap = std::min<uint64_t>(std::max<uint64_t>(range_key_budget() / 16, 1), 0xFFFFFFFFull - n);
   if (b->ids[n - 1] != n - 1 && !b->d_item_ids.p) { // slot != id (QuerySet::live_slot's test): k_range_finish's table
     HIP_TRY(b->d_item_ids.alloc(n));
@@ -5456,15 +5521,18 @@ static int range_emit_pass(RangeScan &R, RangeResult &res) {
   HIP_TRY(R.dseg.alloc(R.qblock + 1));
   HIP_TRY(R.dcursor.alloc(R.qblock));
   R.r.seg = R.dseg.p, R.r.cursor = R.dcursor.p;
-  uint64_t done_q = nq; // the first query whose hits were not fetched
+  return HNY_OK;
+}
+static int range_emit_blocks(RangeScan &R, RangeResult &res, uint64_t lo, uint64_t hi, uint64_t *done_q, bool *stop) {
   bool stopped = false;
-  for (uint64_t q0 = 0; q0 < nq && !stopped; q0 += R.qblock) {
+  R.scan.q_end = hi;
+  for (uint64_t q0 = lo; q0 < hi && !stopped; q0 += R.qblock) {
     const uint32_t n_mem = R.scan.block(q0, R.qblock);
     uint64_t block_hits = 0;
     for (uint32_t j = 0; j < n_mem; j++) block_hits += R.hits_of(j);
     if (block_hits == 0) continue;
     if ((stopped = R.sc.probe())) {
-      done_q = q0;
+      *done_q = q0;
       break;
     }
     if (int rc = range_stage_block(R)) return rc;
@@ -5473,10 +5541,23 @@ static int range_emit_pass(RangeScan &R, RangeResult &res) {
       for (m1 = m0 + 1; m1 < n_mem && run_hits + R.hits_of(m1) <= R.cap; m1++) run_hits += R.hits_of(m1);
       if (run_hits == 0) continue;
       if (int rc = range_emit_run(R, res, m0, m1, run_hits, &stopped)) return rc;
-      if (stopped) done_q = R.scan.query_of(m0);
+      if (stopped) *done_q = R.scan.query_of(m0);
     }
   }
-  for (uint64_t i = done_q; i < nq; i++) res.offsets[i + 1] = res.offsets[done_q], R.counts[i] = 0;
+  *stop = stopped;
+  R.dropped |= stopped;
+  return HNY_OK;
+}
+static void range_emit_end(RangeScan &R, RangeResult &res, uint64_t done_q) {
+  for (uint64_t i = done_q; i < R.scan.q.nq; i++) res.offsets[i + 1] = res.offsets[done_q], R.counts[i] = 0;
+}
+static int range_emit_pass(RangeScan &R, RangeResult &res) {
+  const uint64_t nq = R.scan.q.nq;
+  uint64_t done_q = nq;
+  bool stopped;
+  if (int rc = range_emit_begin(R)) return rc;
+  if (int rc = range_emit_blocks(R, res, 0, nq, &done_q, &stopped)) return rc;
+  range_emit_end(R, res, done_q);
   return HNY_OK;
 }
 
@@ -5535,6 +5616,193 @@ int hny_builder_exact_range_f32(hny_builder *b, const hny_range_opts *ro, uint64
                                 size_t qstride, hny_range_result **out) {
   if (!out || !queries) return fail(HNY_ERR_INVALID_ARG, !queries ? "no queries" : "bad argument");
   return range_impl(b, ro, nq, queries, qstride, nullptr, nullptr, true, nullptr, out);
+}
+
+// ---------------------------------------------------------------------------------------------
+// exact range search with one candidates filter per query.  The hits of the queries of one filter
+// are those of range_impl on these queries alone with that filter.  The call's queries are taken in filter order,
+// those without a filter last (a SubBatch of the whole call), and the two passes of range_impl run on that set, one
+// part of it per FilterRounds round: every filter takes the dense scan, which reads, per tile of queries, only the
+// rows some query of the tile wants, and k_range_count / k_range_emit vote under each query's own mask.  All rounds
+// are counted before the layout and the max_total refusal; the emit pass builds each round again.  The result is
+// laid out in scan order and its rows are moved to call order at the end.
+// ---------------------------------------------------------------------------------------------
+static int range_filtered_impl(hny_builder *b, const hny_range_opts *ro, const FilterSource &src, uint64_t nq,
+                               const void *qvectors, size_t qstride, const void *qheaders, const uint32_t *query_items,
+                               bool q_f32, uint64_t *out_counts, hny_range_result **out) {
+  const FilterSource *fl = &src;
+  uint32_t *const no = nullptr; // (the hits go to a RangeResult)
+  const QuerySet qs = q_f32 ? QuerySet::of_f32(b, nullptr, nq, (const float *)qvectors, qstride, no, nullptr, no)
+                            : QuerySet::of(b, nullptr, nq, qvectors, qstride, qheaders, query_items, no, nullptr, no);
+  if (int rc = range_check_args(b, ro, qs, out_counts || out)) return rc;
+  const hny_query_opts qo = range_query_opts(ro);
+  if (int rc = check_filters(&qo, fl, nq)) return rc;
+  b->exact_rows_read = 0;
+  if (ro->did_cancel) *ro->did_cancel = 0;
+  std::vector<u32> live;
+  const uint64_t n_items = qs.slot_mask(&qo, live); // (has_candidates == 0: the live items)
+  const bool scanned = n_items != 0 && nq != 0;     // otherwise nothing touches the device
+
+  // the scan order, and the part of it that each round takes: the queries of its filters, with the last round (or
+  // alone, where no filter is in use) the queries without one
+  FilterRounds fr(b, qs, fl);
+  SubBatch order{qs};
+  for (uint64_t qi : fr.by_filter) order.add(qi, fl->filter_of[qi]);
+  for (uint64_t i = 0; i < nq; i++)
+    if (fl->filter_of[i] == HNY_FILTER_NONE) order.add(i, HNY_SENT);
+  QuerySet sub = order.gather();
+  std::vector<float> radius((size_t)nq);
+  for (uint64_t j = 0; j < nq; j++) radius[j] = ro->radius[order.idx[j]];
+  RangeScan R{b, sub, radius.data()};
+  if (!R.none32) return fail(HNY_ERR_OOM, "out of memory");
+  sub.out_counts = R.none32.get();
+  const uint32_t NONE = qs.by_item ? HNY_NNS_NONE : 0u;
+  // nothing to search among: no hits, by_item None for every query (reader.rs:822-824) once it is known
+  for (uint64_t j = 0; !scanned && j < nq; j++) R.none32[j] = NONE;
+  const size_t n_rounds = fr.n_rounds(n_items), n_parts = scanned ? std::max<size_t>(n_rounds, 1) : 0;
+  std::vector<uint64_t> part(n_parts + 1, 0); // part p: the queries [part[p], part[p + 1]) of the scan order
+  R.fof.assign((size_t)std::max<uint64_t>(nq, 1), HNY_SENT);
+  R.fcount.assign(R.fof.size(), (u32)n_items);
+  R.skip = exact_skip_env();
+  for (size_t p = 0, at = 0; p < n_parts; p++) {
+    const size_t f0 = std::min(p * fr.per_round, fr.used.size()), f1 = std::min(f0 + fr.per_round, fr.used.size());
+    for (; at < fr.by_filter.size() && (f1 == fr.used.size() || order.filter_of[at] < fr.used[f1]); at++)
+      R.fof[at] = (u32)(std::lower_bound(fr.used.begin() + f0, fr.used.begin() + f1, order.filter_of[at]) -
+                        fr.used.begin() - f0);
+    part[p + 1] = p + 1 == n_parts ? nq : at;
+  }
+  auto round_of = [&](size_t p) -> int { // part p's bitsets on the device, the round's unless it is held
+    if (p >= n_rounds) return HNY_OK;
+    if (int rc = fr.build(p)) return rc;
+    R.scan.filters(fr.dmasks.p, fr.stride);
+    return HNY_OK;
+  };
+
+  if (scanned) {
+    if (int rc = range_scan_begin(R, live, &qo)) return rc;
+    HIP_TRY(hipMemsetAsync(b->g.stats + ST_EXACT_ROWS, 0, sizeof(u64), b->stream));
+  }
+  for (size_t p = 0; p < n_parts && !R.dropped; p++) { // cancelled: the later rounds are not built, 0 hits each
+    if (int rc = round_of(p)) return rc;
+    for (uint64_t j = part[p]; j < part[p + 1]; j++)
+      if (R.fof[j] != HNY_SENT) R.fcount[j] = fr.count[R.fof[j]];
+    if (int rc = range_count_blocks(R, part[p], part[p + 1])) return rc;
+    // an empty filter, or one of unknown and deleted ids alone: nothing to search among for its queries
+    for (uint64_t j = part[p]; j < part[p + 1]; j++)
+      if (R.fcount[j] == 0) R.none32[j] = NONE;
+  }
+  auto rows_read = [&]() -> int { // hny_builder_exact_rows_read's figure, of what has run so far
+    if (!scanned) return HNY_OK;
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    HIP_TRY(hipMemcpy(&b->exact_rows_read, b->g.stats + ST_EXACT_ROWS, sizeof(u64), hipMemcpyDeviceToHost));
+    return HNY_OK;
+  };
+  auto scan_end = [&]() -> int { // that figure, then what the kernels reported
+    if (!scanned) return HNY_OK;
+    if (int rc = rows_read()) return rc;
+    // did_cancel tells that a query went unanswered: a closure that fired while the last answers were on their way
+    // (SearchCancel::wait probes too) dropped nothing
+    R.sc.cancelled = R.dropped;
+    return search_end(b, &qo, R.sc);
+  };
+  if (!out) { // _count stops here
+    if (int rc = scan_end()) return rc;
+    for (uint64_t j = 0; j < nq; j++)
+      out_counts[order.idx[j]] = R.none32[j] == HNY_NNS_NONE ? HNY_RANGE_NONE : R.counts[j];
+    return HNY_OK;
+  }
+  std::unique_ptr<RangeResult> res; // in scan order
+  if (int rc = range_layout(R, ro->max_total, res)) { // refused after the counting pass: its rows were read
+    (void)rows_read(); // (on success it leaves the refusal's text as it is)
+    return rc;
+  }
+  if (res->offsets[nq]) {
+    uint64_t done_q = nq;
+    bool stopped = false;
+    if (int rc = range_emit_begin(R)) return rc;
+    for (size_t p = 0; p < n_parts && !stopped; p++) {
+      if (res->offsets[part[p + 1]] == res->offsets[part[p]]) continue; // no hits: the round is not built again
+      if (int rc = round_of(p)) return rc;
+      if (int rc = range_emit_blocks(R, *res, part[p], part[p + 1], &done_q, &stopped)) return rc;
+    }
+    range_emit_end(R, *res, done_q);
+  }
+  if (int rc = scan_end()) return rc;
+  // the rows to call order (a cancelled query's row is empty: the offsets are made from what was fetched)
+  bool in_order = true;
+  for (uint64_t j = 0; j < nq && in_order; j++) in_order = order.idx[j] == j;
+  if (!in_order) {
+    std::unique_ptr<RangeResult> fin(new (std::nothrow) RangeResult());
+    if (!fin || !fin->alloc(nq, res->offsets[nq])) return fail(HNY_ERR_OOM, "out of memory");
+    for (uint64_t j = 0; j < nq; j++) {
+      fin->offsets[order.idx[j] + 1] = res->offsets[j + 1] - res->offsets[j];
+      fin->is_none[order.idx[j]] = res->is_none[j];
+    }
+    fin->offsets[0] = 0;
+    for (uint64_t i = 0; i < nq; i++) fin->offsets[i + 1] += fin->offsets[i];
+    for (uint64_t j = 0; j < nq; j++) {
+      const uint64_t from = res->offsets[j], to = fin->offsets[order.idx[j]], c = res->offsets[j + 1] - from;
+      if (c) memcpy(fin->ids + to, res->ids + from, (size_t)c * 4), memcpy(fin->dists + to, res->dists + from, (size_t)c * 4);
+    }
+    res = std::move(fin);
+  }
+  *out = &res.release()->pub;
+  return HNY_OK;
+}
+
+int hny_builder_exact_range_count_filtered(hny_builder *b, const hny_range_opts *ro, const hny_query_filters *filters,
+                                           uint64_t nq, const void *qvectors, size_t qstride, const void *qheaders,
+                                           const uint32_t *query_items, uint64_t *out_counts) {
+  if (!out_counts) return fail(HNY_ERR_INVALID_ARG, "bad argument");
+  return range_filtered_impl(b, ro, filters, nq, qvectors, qstride, qheaders, query_items, false, out_counts, nullptr);
+}
+
+int hny_builder_exact_range_filtered(hny_builder *b, const hny_range_opts *ro, const hny_query_filters *filters,
+                                     uint64_t nq, const void *qvectors, size_t qstride, const void *qheaders,
+                                     const uint32_t *query_items, hny_range_result **out) {
+  if (!out) return fail(HNY_ERR_INVALID_ARG, "bad argument");
+  return range_filtered_impl(b, ro, filters, nq, qvectors, qstride, qheaders, query_items, false, nullptr, out);
+}
+
+int hny_builder_exact_range_count_filtered_f32(hny_builder *b, const hny_range_opts *ro,
+                                               const hny_query_filters *filters, uint64_t nq, const float *queries,
+                                               size_t qstride, uint64_t *out_counts) {
+  if (!out_counts || !queries) return fail(HNY_ERR_INVALID_ARG, !queries ? "no queries" : "bad argument");
+  return range_filtered_impl(b, ro, filters, nq, queries, qstride, nullptr, nullptr, true, out_counts, nullptr);
+}
+
+int hny_builder_exact_range_filtered_f32(hny_builder *b, const hny_range_opts *ro, const hny_query_filters *filters,
+                                         uint64_t nq, const float *queries, size_t qstride, hny_range_result **out) {
+  if (!out || !queries) return fail(HNY_ERR_INVALID_ARG, !queries ? "no queries" : "bad argument");
+  return range_filtered_impl(b, ro, filters, nq, queries, qstride, nullptr, nullptr, true, nullptr, out);
+}
+
+// the same with the filters as bitsets over item ids
+int hny_builder_exact_range_count_bitsets(hny_builder *b, const hny_range_opts *ro, const hny_query_bitsets *filters,
+                                          uint64_t nq, const void *qvectors, size_t qstride, const void *qheaders,
+                                          const uint32_t *query_items, uint64_t *out_counts) {
+  if (!out_counts) return fail(HNY_ERR_INVALID_ARG, "bad argument");
+  return range_filtered_impl(b, ro, filters, nq, qvectors, qstride, qheaders, query_items, false, out_counts, nullptr);
+}
+
+int hny_builder_exact_range_bitsets(hny_builder *b, const hny_range_opts *ro, const hny_query_bitsets *filters,
+                                    uint64_t nq, const void *qvectors, size_t qstride, const void *qheaders,
+                                    const uint32_t *query_items, hny_range_result **out) {
+  if (!out) return fail(HNY_ERR_INVALID_ARG, "bad argument");
+  return range_filtered_impl(b, ro, filters, nq, qvectors, qstride, qheaders, query_items, false, nullptr, out);
+}
+
+int hny_builder_exact_range_count_bitsets_f32(hny_builder *b, const hny_range_opts *ro,
+                                              const hny_query_bitsets *filters, uint64_t nq, const float *queries,
+                                              size_t qstride, uint64_t *out_counts) {
+  if (!out_counts || !queries) return fail(HNY_ERR_INVALID_ARG, !queries ? "no queries" : "bad argument");
+  return range_filtered_impl(b, ro, filters, nq, queries, qstride, nullptr, nullptr, true, out_counts, nullptr);
+}
+
+int hny_builder_exact_range_bitsets_f32(hny_builder *b, const hny_range_opts *ro, const hny_query_bitsets *filters,
+                                        uint64_t nq, const float *queries, size_t qstride, hny_range_result **out) {
+  if (!out || !queries) return fail(HNY_ERR_INVALID_ARG, !queries ? "no queries" : "bad argument");
+  return range_filtered_impl(b, ro, filters, nq, queries, qstride, nullptr, nullptr, true, nullptr, out);
 }
 
 void hny_range_result_free(hny_range_result *r) {

@@ -662,6 +662,11 @@ struct RangeArgs {
   u64 *keys;                   // k_range_emit: dist bits << 32 | slot of query q at keys[seg[q] + cursor[q] ..)
   const u32 *seg;              // [nq + 1] where each query's keys start, from the counts
   u32 *cursor;                 // [nq] keys written so far, zero before the first slab
+  // one candidates filter per query (hny_builder_exact_range_filtered), as in ExactArgs; all null in
+  // range_impl's call without filters.  != null: the PER_QUERY instances of the two kernels
+  const u32 *filter_of;        // [nq] the query's mask among `masks`, HNY_SENT = `mask` (the live items)
+  const u32 *masks;            // the filters' bitsets over slots (live slots only), mask_stride words apart
+  u32 mask_stride;
 };
 hipError_t hnyk_range_count(const RangeArgs &a, hipStream_t st);
 hipError_t hnyk_range_emit(const RangeArgs &a, hipStream_t st);

@@ -451,7 +451,9 @@ int hny_builder_exact_knn_filtered(hny_builder *b, const hny_query_opts *opts, c
 int hny_builder_exact_knn_filtered_f32(hny_builder *b, const hny_query_opts *opts, const hny_query_filters *filters,
                                        uint64_t n_queries, const float *queries, size_t qstride,
                                        uint32_t *out_ids, float *out_dists, uint32_t *out_counts);
-/* (tile, row) loads of the dense scan in the last hny_builder_exact_knn_filtered[_f32] call on b; 0 if none ran */
+/* (tile, row) loads of the dense scan in the last call on b of hny_builder_exact_knn_filtered / _bitsets or of
+ * hny_builder_exact_range[_count]_filtered / _bitsets (any form): there the sum over both passes, the counting pass
+ * alone for the _count calls and for a call refused over max_total; 0 if none ran */
 uint64_t hny_builder_exact_rows_read(const hny_builder *b);
 
 /* ---- the filters of the two calls above as bitsets over item ids: the reference's `.candidates()` takes a
@@ -563,6 +565,66 @@ int hny_builder_exact_range_count_f32(hny_builder *b, const hny_range_opts *opts
 int hny_builder_exact_range_f32(hny_builder *b, const hny_range_opts *opts, uint64_t n_queries,
                                 const float *queries, size_t qstride, hny_range_result **out);
 void hny_range_result_free(hny_range_result *r); /* NULL is fine */
+
+/* ---- exact range search with one `.candidates()` filter per query: what a serving process asks that checks for
+ * near duplicates inside each tenant's own items, or applies a score threshold under a per-request ACL or facet.  One
+ * call in the place of one hny_builder_exact_range call per distinct filter, each of which reads every row twice.
+ *
+ * Definition: let G(f) be the queries with filter_of[i] == f, in call order.  Their hits and counts (ids, distance
+ * bits, order, is_none, out_counts) are, byte for byte, what hny_builder_exact_range / _count returns for those queries
+ * alone with the same radius entries, has_candidates = 1 and candidates = filter f (ids[offsets[f] .. offsets[f + 1]),
+ * or the set bits of row f below n_bits); G(HNY_FILTER_NONE) is answered as with has_candidates = 0.  The result's CSR
+ * is in call order.  An empty filter, or one that names only unknown or deleted ids, gives 0 hits; by item
+ * is_none = 1 / HNY_RANGE_NONE, as hny_builder_exact_range does with an empty C.  The _bitsets form equals the
+ * _filtered form on the set bits below n_bits, as for the top-k calls.
+ *
+ * opts: radius, max_total and cancel / cancel_ctx / did_cancel are read; has_candidates must be 0.  max_total is
+ * decided from the counts of all filters before anything is emitted, *out untouched.
+ *
+ * Decided before any device work, *out and out_counts untouched: first what hny_builder_exact_range refuses, with its
+ * codes and in its order (NULL arguments, struct_size, radius, candidates == NULL with n_candidates > 0, qstride, a
+ * strict-mode f32 builder: HNY_ERR_UNSUPPORTED, bit metrics in strict mode are served); then what the _filtered /
+ * _bitsets top-k calls refuse about their filters: filters == NULL, a wrong struct_size, opts->has_candidates != 0,
+ * offsets[0] != 0, decreasing offsets, ids == NULL with offsets[n_filters] > 0, a filter_of entry >= n_filters other
+ * than HNY_FILTER_NONE, n_bits > 2^32, stride_words < ceil(n_bits / 32), bits == NULL with n_filters > 0 and
+ * n_bits > 0: HNY_ERR_INVALID_ARG.
+ *
+ * Cancellation: `cancel` is probed between the launches; a query whose hits were not fetched reports 0 hits, the
+ * offsets stay consistent, *did_cancel = 1 (it stays 0 where no query was dropped) and the call returns HNY_OK; every
+ * other query has its complete row.  The
+ * queries are taken in filter order (those without a filter last), so the cancelled ones need not be a suffix of
+ * the call.  Once a query was dropped the filters that come later are not built: a dropped by_item query has
+ * is_none = 1 only where its item is unknown or deleted.
+ *
+ * Every filter takes the dense scan (there is no gather path): per round of filters that fit the device
+ * (HNY_FILTER_MASK_BYTES) the two passes of hny_builder_exact_range run on the round's queries in filter order; the
+ * scan reads, per tile of queries, only the rows some query of the tile wants, and the counting and emitting kernels
+ * pass over every batch of 256 slots that holds no candidate of their query.
+ * hny_builder_exact_rows_read reports the rows read. */
+int hny_builder_exact_range_count_filtered(hny_builder *b, const hny_range_opts *opts, const hny_query_filters *filters,
+                                           uint64_t n_queries, const void *qvectors, size_t qstride,
+                                           const void *qheaders, const uint32_t *query_items, uint64_t *out_counts);
+int hny_builder_exact_range_filtered(hny_builder *b, const hny_range_opts *opts, const hny_query_filters *filters,
+                                     uint64_t n_queries, const void *qvectors, size_t qstride, const void *qheaders,
+                                     const uint32_t *query_items, hny_range_result **out);
+int hny_builder_exact_range_count_filtered_f32(hny_builder *b, const hny_range_opts *opts,
+                                               const hny_query_filters *filters, uint64_t n_queries,
+                                               const float *queries, size_t qstride, uint64_t *out_counts);
+int hny_builder_exact_range_filtered_f32(hny_builder *b, const hny_range_opts *opts, const hny_query_filters *filters,
+                                         uint64_t n_queries, const float *queries, size_t qstride,
+                                         hny_range_result **out);
+int hny_builder_exact_range_count_bitsets(hny_builder *b, const hny_range_opts *opts, const hny_query_bitsets *filters,
+                                          uint64_t n_queries, const void *qvectors, size_t qstride,
+                                          const void *qheaders, const uint32_t *query_items, uint64_t *out_counts);
+int hny_builder_exact_range_bitsets(hny_builder *b, const hny_range_opts *opts, const hny_query_bitsets *filters,
+                                    uint64_t n_queries, const void *qvectors, size_t qstride, const void *qheaders,
+                                    const uint32_t *query_items, hny_range_result **out);
+int hny_builder_exact_range_count_bitsets_f32(hny_builder *b, const hny_range_opts *opts,
+                                              const hny_query_bitsets *filters, uint64_t n_queries,
+                                              const float *queries, size_t qstride, uint64_t *out_counts);
+int hny_builder_exact_range_bitsets_f32(hny_builder *b, const hny_range_opts *opts, const hny_query_bitsets *filters,
+                                        uint64_t n_queries, const float *queries, size_t qstride,
+                                        hny_range_result **out);
 
 /* ---- resident updates: Writer::add_item / del_item followed by Writer::build (src/writer.rs:462-495, 521-603)
  * on an index whose builder is still alive.  A finished builder holds the codec rows, the norms and the finalised
