@@ -53,6 +53,7 @@ EXPORTED = [
     "hny_builder_finish_delta_encoded", "hny_encoded_delta_free",
     "hny_builder_load_encoded", "hny_builder_load_encoded_f32", "hny_builder_create_incremental_encoded",
     "hny_build_incremental_encoded", "hny_encoded_links_measure", "hny_lmdb_read_links",
+    "hny_builder_rescore", "hny_builder_rescore_f32", "hny_builder_nns_rescored", "hny_builder_nns_rescored_f32",
 ]
 ERR_IO = -9
 NNS_NONE = 0xFFFFFFFF  # by_item: the reference returns None
@@ -141,6 +142,16 @@ class QueryBitsets(C.Structure):
         s.bits = _p(bits).value if bits.size else None
         s.filter_of = _p(fo).value
         return s, (bits, n_bits, fo)
+
+
+class RescoreOpts(C.Structure):
+    """hny_rescore_opts; struct_size is the guard (the struct is not part of hny_abi_sizes)"""
+    _fields_ = [("struct_size", C.c_uint32), ("k", C.c_uint32), ("n_rescore", C.c_uint32), ("ef_search", C.c_uint32),
+                ("cancel", CANCEL_FN), ("cancel_ctx", C.c_void_p), ("did_cancel", C.POINTER(C.c_int32))]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_size = C.sizeof(RescoreOpts)
 
 
 class RangeOpts(C.Structure):
@@ -458,6 +469,15 @@ def load_library():
                             getattr(L, plain + "_f32").argtypes[2:])
     L.hny_range_result_free.restype = None
     L.hny_range_result_free.argtypes = [C.POINTER(RangeResult)]
+    ro = C.POINTER(RescoreOpts)
+    L.hny_builder_rescore.restype = C.c_int
+    L.hny_builder_rescore.argtypes = [vp, ro, C.c_uint64, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]
+    L.hny_builder_rescore_f32.restype = C.c_int
+    L.hny_builder_rescore_f32.argtypes = [vp, ro, C.c_uint64, vp, C.c_size_t, vp, vp, vp, vp, vp]
+    L.hny_builder_nns_rescored.restype = C.c_int
+    L.hny_builder_nns_rescored.argtypes = [vp, vp, ro, C.c_uint64, vp, C.c_size_t, vp, vp, vp, vp, vp]
+    L.hny_builder_nns_rescored_f32.restype = C.c_int
+    L.hny_builder_nns_rescored_f32.argtypes = [vp, vp, ro, C.c_uint64, vp, C.c_size_t, vp, vp, vp]
     L.hny_builder_exact_rows_read.restype = C.c_uint64
     L.hny_builder_exact_rows_read.argtypes = [vp]
     L.hny_builder_create_update.restype = C.c_int
@@ -1804,6 +1824,52 @@ class Builder:
         qb = QueryBitsets.pack(bits, n_bits, filter_of)
         return self._search("hny_builder_exact_knn_bitsets", opts,
                             _query_source(query_items, qf32, qcodes, qheaders), qf32 is not None, qb)
+
+    def _rescore_opts(self, k, n_rescore=0, ef_search=0, cancel=None):
+        """hny_rescore_opts of one call; returns (struct, what it points into, the int32 did_cancel points at)"""
+        o = RescoreOpts()
+        o.k, o.n_rescore, o.ef_search = int(k), int(n_rescore), int(ef_search)
+        flag = C.c_int32(0)
+        keep = [flag]
+        if cancel is not None:
+            fn = CANCEL_FN(lambda _ctx: 1 if cancel() else 0)
+            o.cancel, o.did_cancel = fn, C.pointer(flag)
+            keep.append(fn)
+        return o, keep, flag
+
+    def rescore(self, cand_offsets, cand_ids, qcodes=None, qheaders=None, k=10, query_items=None, cancel=None, qf32=None):
+        """hny_builder_rescore: the k nearest of each query's own candidates, item ids cand_ids[cand_offsets[i] :
+        cand_offsets[i + 1]], ranked on this builder's rows: exact_knn(candidates=that list) for query i alone.
+        Returns (ids, dists, counts) like nns; counts == NNS_NONE by item for an unknown item or an empty list."""
+        o, _keep, flag = self._rescore_opts(k, cancel=cancel)
+        (nq, qc, qs, qh, qi), _arrays = _query_source(query_items, None if qf32 is None else _f32_rows(qf32), qcodes, qheaders)
+        off = np.ascontiguousarray(cand_offsets, np.uint64)
+        if len(off) != nq + 1:
+            raise ValueError(f"cand_offsets has {len(off)} entries for {nq} queries")
+        ids = u32_ids(cand_ids)
+        out = _result_arrays(nq, int(k))
+        cand = (_p(off), _p(ids) if len(ids) else None)
+        if qf32 is not None:
+            _check(load_library().hny_builder_rescore_f32(self._h, C.byref(o), nq, qc, qs, *cand, *map(_p, out)))
+        else:
+            _check(load_library().hny_builder_rescore(self._h, C.byref(o), nq, qc, qs, qh, qi, *cand, *map(_p, out)))
+        self.did_cancel = bool(flag.value)
+        return out
+
+    def nns_rescored(self, fine, qcodes=None, qheaders=None, k=10, n_rescore=100, ef_search=100, query_items=None,
+                     cancel=None, qf32=None):
+        """hny_builder_nns_rescored: nns(k=n_rescore, ef_search) on this (coarse) builder, its hits ranked again on the
+        rows of `fine` (a Builder on the same device, of the same dim), k of them returned.  By item the query row of
+        the second stage is fine's stored row; f32 queries are encoded once per builder."""
+        o, _keep, flag = self._rescore_opts(k, n_rescore, ef_search, cancel)
+        (nq, qc, qs, qh, qi), _arrays = _query_source(query_items, None if qf32 is None else _f32_rows(qf32), qcodes, qheaders)
+        out = _result_arrays(nq, int(k))
+        if qf32 is not None:
+            _check(load_library().hny_builder_nns_rescored_f32(self._h, fine._h, C.byref(o), nq, qc, qs, *map(_p, out)))
+        else:
+            _check(load_library().hny_builder_nns_rescored(self._h, fine._h, C.byref(o), nq, qc, qs, qh, qi, *map(_p, out)))
+        self.did_cancel = bool(flag.value)
+        return out
 
     def exact_rows_read(self):
         """(tile, row) loads of the dense scan in the last exact_knn_filtered / exact_range_filtered call (or their

@@ -215,12 +215,28 @@ class Writer:
         # resident, between prepare_changing_distance and the next build: (old metric, the recoded codes, headers) of
         # the held builder's items — that build goes through hny_builder_create_changed_distance
         self._rb_change = None
+        # resident, after a change from an f32 distance to a binary-quantized one: the f32 source builder, kept next to
+        # its successor until the next build so that searches on the new index can be rescored on the f32 rows
+        self._rb_fine = None
 
     def close(self):
         """releases the resident builder (a Writer without one holds nothing)"""
+        self._drop_fine()
         if self._rb is not None:
             self._rb.close()
             self._rb = None
+
+    def _drop_fine(self):
+        if self._rb_fine is not None:
+            self._rb_fine.close()
+            self._rb_fine = None
+
+    @property
+    def rescore_source(self):
+        """the f32 builder a resident change to a binary-quantized distance left next to the new index, or None:
+        what QueryBuilder.rescore_with takes to rank the new index's hits on the original vectors, nothing reloaded.
+        It holds the items as they were at the change and is released by the next build or close()"""
+        return self._rb_fine
 
     def __enter__(self):
         return self
@@ -490,6 +506,7 @@ class Writer:
             if g is not None:
                 self._rb_ids, self._rb_gen = ids, db.build_generation.get(index, 0) + 1
                 return g
+        self._drop_fine()  # its rows are those of before this build
         if (self._rb is not None and opts_key == self._rb_kw and not relink_all_items and meta is not None
                 and self._rb_gen == db.build_generation.get(index, 0) and set(self._rb_ids.tolist()) == indexed):
             ups = db.item_set(index, np.array(to_insert, np.uint32), self.dimensions)
@@ -563,7 +580,11 @@ class Writer:
         except BaseException:
             succ.close()
             raise
-        self._rb.close()
+        self._drop_fine()
+        if old_metric <= capi.MANHATTAN and new_metric >= capi.BQ_COSINE:  # f32 rows next to a binary-quantized graph: kept for rescore_with
+            self._rb_fine = self._rb
+        else:
+            self._rb.close()
         self._rb, self._rb_kw, self._rb_change = succ, opts_key, None
         return g
 
@@ -636,6 +657,7 @@ class QueryBuilder:
         self._bitsets = None
         self._radius = None
         self._within_filtered = False
+        self._rescore = None
 
     def ef_search(self, ef):
         self._ef = int(ef)
@@ -722,6 +744,21 @@ class QueryBuilder:
         self._within_filtered = bool(filtered)
         return self
 
+    def rescore_with(self, fine_reader, n_rescore):
+        """two-stage search (hny_builder_nns_rescored): the graph search returns its n_rescore best hits, which are
+        ranked again on the rows of `fine_reader` — a Reader, or a Builder such as Writer.rescore_source, of the same
+        dimensions on the same device — and cut to count.  Honoured by by_vectors / by_items and the single-query
+        forms; refused together with .exact(), .within() and any .candidates*()"""
+        self._rescore = (getattr(fine_reader, "_b", fine_reader), int(n_rescore))
+        return self
+
+    def _rescored(self, **source):
+        if (self._exact or self._radius is not None or self._candidates is not None or self._per_query is not None
+                or self._bitsets is not None):
+            raise ValueError("rescore_with() does not go with exact(), within() or candidates")
+        fine, n_rescore = self._rescore
+        return self.reader._b.nns_rescored(fine, k=self.count, n_rescore=n_rescore, ef_search=self._ef, **source)
+
     def _cut(self, hits):
         """(ids, dists, counts) of a top-k search as the CSR of within(): per row the hits with distance <= radius"""
         ids, dists, counts = hits
@@ -762,6 +799,8 @@ class QueryBuilder:
         q = np.ascontiguousarray(vectors, np.float32)
         if q.ndim != 2 or q.shape[1] != r.dimensions:
             raise InvalidVecDimension(f"expected {r.dimensions}, received {q.shape[-1]}")
+        if self._rescore is not None:
+            return self._rescored(qf32=q, cancel=cancel)
         if self._radius is not None:
             if self._exact:
                 return self._within_exact(len(q), qf32=capi._f32_rows(q), cancel=cancel)
@@ -788,6 +827,8 @@ class QueryBuilder:
     def by_items(self, items, cancel=None):
         """batched by_item; counts == capi.NNS_NONE where the reference returns None"""
         self._check_within()
+        if self._rescore is not None:
+            return self._rescored(query_items=capi.u32_ids(items), cancel=cancel)
         if self._radius is not None:
             if self._exact:
                 items = capi.u32_ids(items)

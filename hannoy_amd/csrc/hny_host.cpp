@@ -238,6 +238,15 @@ struct DevBuf {
   }
   ~DevBuf() { release(); }
 };
+// host memory the device copies from and to directly
+template <class T>
+struct PinnedBuf {
+  T *p = nullptr;
+  hipError_t alloc(size_t count) { return hipHostMalloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T), hipHostMallocDefault); }
+  ~PinnedBuf() {
+    if (p) (void)hipHostFree(p);
+  }
+};
 
 // ---- f32 ingest: host rows -> pinned staging -> device staging -> k_ingest, double buffered.  While chunk i is
 // encoded on the consumer's stream, chunk i+1 is copied into pinned memory by the host (pageable input is the
@@ -4674,6 +4683,298 @@ int hny_builder_nns_f32(hny_builder *b, const hny_query_opts *qo, uint64_t nq, c
 }
 
 // ---------------------------------------------------------------------------------------------
+// Two-stage search: hny_builder_rescore ranks every query's own short list of item ids on this
+// builder's rows (k_rescore: one workgroup per query resolves, scores and sorts the list in LDS), and
+// hny_builder_nns_rescored feeds it the hits of nns_impl on a second, coarser builder.  No id is touched on the host
+// and no bitset over slots is made: the lists go up as they are, with a start and a count per query.
+// ---------------------------------------------------------------------------------------------
+// The lists of a rescore call: the caller's CSR, or stage 1's result rows (`row` ids apart, `counts` of them each,
+// HNY_NNS_NONE = stage 1 had no answer)
+struct RescoreCands {
+  const uint64_t *offsets = nullptr;
+  const uint32_t *ids = nullptr;
+  uint32_t row = 0;
+  const uint32_t *counts = nullptr;
+  bool stage1_cancelled = false; // row form: an empty row may be a query stage 1 never started (0 hits, not NONE)
+  uint64_t beg(uint64_t i) const { return offsets ? offsets[i] : i * row; } // (i = nq: where the last list ends)
+  bool none(uint64_t i) const { return !offsets && counts[i] == HNY_NNS_NONE; }
+  uint32_t cnt(uint64_t i) const { return offsets ? (uint32_t)(offsets[i + 1] - offsets[i]) : none(i) ? 0u : counts[i]; }
+};
+
+// the checks of both calls that read the opts alone, in the header's order
+static int check_rescore_opts(const hny_rescore_opts *o, bool fused) {
+  if (!o) return fail(HNY_ERR_INVALID_ARG, "no options");
+  if (o->struct_size != sizeof(hny_rescore_opts))
+    return fail(HNY_ERR_INVALID_ARG, "hny_rescore_opts.struct_size %u: this library has %zu", o->struct_size,
+                sizeof(hny_rescore_opts));
+  if (o->k == 0) return fail(HNY_ERR_INVALID_ARG, "k must be at least 1");
+  if (fused && o->n_rescore < o->k) return fail(HNY_ERR_INVALID_ARG, "n_rescore %u below k %u", o->n_rescore, o->k);
+  if (fused && o->n_rescore > HNY_RESCORE_MAX)
+    return fail(HNY_ERR_UNSUPPORTED, "n_rescore %u: at most %u hits are rescored per query", o->n_rescore, HNY_RESCORE_MAX);
+  return HNY_OK;
+}
+static int check_rescore_offsets(uint64_t nq, const uint64_t *off, const uint32_t *ids) {
+  if (!off) return fail(HNY_ERR_INVALID_ARG, "candidate offsets missing");
+  if (off[0] != 0) return fail(HNY_ERR_INVALID_ARG, "candidate offsets must start at 0");
+  for (uint64_t i = 0; i < nq; i++)
+    if (off[i + 1] < off[i]) return fail(HNY_ERR_INVALID_ARG, "candidate offsets decrease at query %llu", (unsigned long long)i);
+  if (off[nq] && !ids) return fail(HNY_ERR_INVALID_ARG, "candidate ids missing");
+  return HNY_OK;
+}
+// what stage 2 asks of its builder and queries before any device work
+static int check_rescore_queries(const QuerySet &qs) {
+  if (!qs.b || !qs.out_ids || !qs.out_dists || !qs.out_counts) return fail(HNY_ERR_INVALID_ARG, "bad argument");
+  if (int rc = check_query_source(qs, "no queries")) return rc;
+  if (int rc = check_query_rows(qs)) return rc;
+  if (int rc = check_build_finished(qs.b)) return rc;
+  return check_query_stride(qs);
+}
+static hny_query_opts rescore_query_opts(const hny_rescore_opts *o, uint32_t k, int32_t *did_cancel) {
+  hny_query_opts q{};
+  q.k = k;
+  q.ef_search = o->ef_search;
+  q.linear_below_ratio = 1.0f;
+  q.cancel = o->cancel;
+  q.cancel_ctx = o->cancel_ctx;
+  q.did_cancel = did_cancel;
+  return q;
+}
+// words per bitset over slots: every slot and a spare word, in whole runs of four
+static u32 slot_mask_stride(uint32_t n) { return (u32)((((size_t)n + 31) / 32 + 4) & ~(size_t)3); }
+// The live slots as a bitset on the device, and the slot -> id table where slots are not ids (*item_ids; null = the
+// identity): made by whichever call needs them first, the bitset filters (FilterRounds::build_from_id_bits) or k_rescore
+static int ensure_live_bits(hny_builder *b, const QuerySet &q, const u32 **item_ids) {
+  if (int rc = ensure_item_ids(b, item_ids)) return rc;
+  if (b->d_live_bits.p) return HNY_OK;
+  const size_t words = slot_mask_stride(b->n);
+  std::vector<u32> live(words, 0u);
+  for (uint32_t s = 0; s < b->n; s++)
+    if (q.live(s)) live[s >> 5] |= 1u << (s & 31);
+  HIP_TRY(b->d_live_bits.alloc(words));
+  HIP_TRY(hipMemcpy(b->d_live_bits.p, live.data(), words * 4, hipMemcpyHostToDevice));
+  return HNY_OK;
+}
+
+// Stage 2 on checked arguments: chunks of at most HNY_RESCORE_CHUNK queries, each chunk's ids in one copy
+static int rescore_run(hny_builder *b, const QuerySet &qs, const RescoreCands &C, SearchCancel &sc) {
+  const uint64_t nq = qs.nq;
+  const uint32_t k = qs.k, NONE = HNY_NNS_NONE;
+  uint32_t longest = 0;
+  uint64_t span = 0; // ids of the largest chunk
+  for (uint64_t q0 = 0; q0 < nq; q0 += HNY_RESCORE_CHUNK) {
+    const uint64_t q1 = std::min<uint64_t>(nq, q0 + HNY_RESCORE_CHUNK);
+    span = std::max(span, C.beg(q1) - C.beg(q0));
+    for (uint64_t i = q0; i < q1; i++) longest = std::max(longest, C.cnt(i));
+  }
+  if (longest > HNY_RESCORE_MAX)
+    return fail(HNY_ERR_UNSUPPORTED, "a query with %u candidates: at most %u are rescored", longest, HNY_RESCORE_MAX);
+  HIP_TRY(hipSetDevice(b->device));
+  auto unanswered = [&](uint64_t qi) -> uint32_t { // a query that did not run: None by item where it can never have an answer
+    return C.none(qi) || (qs.by_item && qs.live_slot(qs.query_items[qi]) < 0) ? NONE : 0u;
+  };
+  if (b->n == 0 || longest == 0) {
+    for (uint64_t i = 0; i < nq; i++)
+      qs.out_counts[i] = C.stage1_cancelled ? unanswered(i) : qs.by_item ? NONE : 0u;
+    return HNY_OK;
+  }
+  const u32 *item_ids = nullptr;
+  if (int rc = ensure_live_bits(b, qs, &item_ids)) return rc;
+  const uint32_t chunk = (uint32_t)std::min<uint64_t>(HNY_RESCORE_CHUNK, nq), kk = std::min(k, longest);
+  QueryStage st{b, qs};
+  if (int rc = st.alloc(chunk)) return rc;
+  DevBuf<u64> dbeg;
+  DevBuf<u32> dcnt, dids, dout_ids, dout_bits, dout_cnt;
+  HIP_TRY(dbeg.alloc(chunk));
+  HIP_TRY(dcnt.alloc(chunk));
+  HIP_TRY(dids.alloc((size_t)std::max<uint64_t>(span, 1)));
+  HIP_TRY(dout_ids.alloc((size_t)chunk * kk));
+  HIP_TRY(dout_bits.alloc((size_t)chunk * kk));
+  HIP_TRY(dout_cnt.alloc(chunk));
+  std::vector<u64> hbeg(chunk);
+  std::vector<u32> hcnt(chunk), hout_ids((size_t)chunk * kk), hout_bits((size_t)chunk * kk), hout_cnt(chunk);
+  std::vector<unsigned char> runs(chunk);
+  RescoreArgs a{};
+  a.q_stride = b->g.row_stride;
+  a.cand_beg = dbeg.p;
+  a.cand_cnt = dcnt.p;
+  a.cand_ids = dids.p;
+  a.item_ids = item_ids;
+  a.live = b->d_live_bits.p;
+  a.k = k;
+  a.kk = kk;
+  a.rcap = std::max<uint32_t>(64, pow2ceil(longest));
+  a.out_ids = dout_ids.p;
+  a.out_dist_bits = dout_bits.p;
+  a.out_counts = dout_cnt.p;
+  a.cancel = sc.d;
+  for (uint64_t q0 = 0; q0 < nq; q0 += chunk) {
+    const uint32_t cnt = (uint32_t)std::min<uint64_t>(chunk, nq - q0);
+    if (sc.probe()) { // nothing of this chunk is started
+      for (uint32_t i = 0; i < cnt; i++) qs.out_counts[q0 + i] = unanswered(q0 + i);
+      continue;
+    }
+    const uint32_t n_mem = st.members_of(q0, cnt); // (by item: HNY_NNS_NONE to the unknown and deleted items)
+    std::fill(runs.begin(), runs.begin() + cnt, (unsigned char)0);
+    for (uint32_t j = 0; j < n_mem; j++) runs[st.members[j]] = 1;
+    const uint64_t base = C.beg(q0);
+    for (uint32_t i = 0; i < cnt; i++) {
+      if (C.none(q0 + i)) runs[i] = 0, qs.out_counts[q0 + i] = NONE;
+      if (!runs[i]) st.slots[i] = HNY_SENT;
+      hbeg[i] = C.beg(q0 + i) - base;
+      hcnt[i] = runs[i] ? C.cnt(q0 + i) : 0u;
+    }
+    if (int rc = st.stage(q0, cnt)) return rc;
+    const uint64_t ids_here = C.beg(q0 + cnt) - base;
+    HIP_TRY(hipMemcpyAsync(dbeg.p, hbeg.data(), (size_t)cnt * 8, hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(dcnt.p, hcnt.data(), (size_t)cnt * 4, hipMemcpyHostToDevice, b->stream));
+    if (ids_here)
+      HIP_TRY(hipMemcpyAsync(dids.p, C.ids + base, (size_t)ids_here * 4, hipMemcpyHostToDevice, b->stream));
+    a.q_slots = qs.by_item ? st.dqslots.p : nullptr;
+    a.q_rows = st.dq.p;
+    a.q_norms = st.norms();
+    a.nq = cnt;
+    HIP_TRY(hnyk_rescore(b->g, a, b->shape, b->stream));
+    HIP_TRY(hipMemcpyAsync(hout_cnt.data(), dout_cnt.p, (size_t)cnt * 4, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemcpyAsync(hout_ids.data(), dout_ids.p, (size_t)cnt * kk * 4, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemcpyAsync(hout_bits.data(), dout_bits.p, (size_t)cnt * kk * 4, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(sc.wait(b));
+    for (uint32_t i = 0; i < cnt; i++) {
+      const uint64_t qi = q0 + i;
+      if (!runs[i]) continue; // its HNY_NNS_NONE stands
+      uint32_t c = hout_cnt[i]; // hits; 0 where the kernel never started it; NONE by item without a live candidate
+      if (c == NONE && C.stage1_cancelled && hcnt[i] == 0u) c = 0u; // an empty row of a cancelled stage 1: never searched
+      if (c != NONE) {
+        memcpy(&qs.out_ids[qi * k], &hout_ids[(size_t)i * kk], (size_t)c * 4);
+        memcpy(&qs.out_dists[qi * k], &hout_bits[(size_t)i * kk], (size_t)c * 4);
+      }
+      qs.out_counts[qi] = c;
+    }
+  }
+  return HNY_OK;
+}
+
+static int rescore_impl(hny_builder *fine, const hny_rescore_opts *o, const QuerySet &qs, const uint64_t *cand_offsets,
+                        const uint32_t *cand_ids) {
+  if (int rc = check_rescore_opts(o, false)) return rc;
+  if (int rc = check_rescore_offsets(qs.nq, cand_offsets, cand_ids)) return rc;
+  if (int rc = check_rescore_queries(qs)) return rc;
+  RescoreCands C;
+  C.offsets = cand_offsets;
+  C.ids = cand_ids;
+  for (uint64_t i = 0; i < qs.nq; i++) // (before the cancel closure is armed: a refusal leaves did_cancel alone)
+    if (cand_offsets[i + 1] - cand_offsets[i] > HNY_RESCORE_MAX)
+      return fail(HNY_ERR_UNSUPPORTED, "query %llu has %llu candidates: at most %u are rescored", (unsigned long long)i,
+                  (unsigned long long)(cand_offsets[i + 1] - cand_offsets[i]), HNY_RESCORE_MAX);
+  const hny_query_opts qo = rescore_query_opts(o, o->k, o->did_cancel);
+  HIP_TRY(hipSetDevice(fine->device));
+  SearchCancel sc;
+  HIP_TRY(sc.begin(&qo));
+  if (int rc = rescore_run(fine, qs, C, sc)) return rc;
+  return search_end(fine, &qo, sc);
+}
+
+int hny_builder_rescore(hny_builder *fine, const hny_rescore_opts *o, uint64_t nq, const void *qvectors, size_t qstride,
+                        const void *qheaders, const uint32_t *query_items, const uint64_t *cand_offsets,
+                        const uint32_t *cand_ids, uint32_t *out_ids, float *out_dists, uint32_t *out_counts) {
+  QuerySet qs = QuerySet::of(fine, nullptr, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists, out_counts);
+  qs.k = o ? o->k : 0;
+  return rescore_impl(fine, o, qs, cand_offsets, cand_ids);
+}
+
+int hny_builder_rescore_f32(hny_builder *fine, const hny_rescore_opts *o, uint64_t nq, const float *queries,
+                            size_t qstride, const uint64_t *cand_offsets, const uint32_t *cand_ids, uint32_t *out_ids,
+                            float *out_dists, uint32_t *out_counts) {
+  QuerySet qs = QuerySet::of_f32(fine, nullptr, nq, queries, qstride, out_ids, out_dists, out_counts);
+  qs.k = o ? o->k : 0;
+  return rescore_impl(fine, o, qs, cand_offsets, cand_ids);
+}
+
+// the queries [q0, q0 + cnt) of a call as a call of their own, with the rows their hits go to
+static QuerySet query_slice(const QuerySet &q, uint64_t q0, uint64_t cnt, uint32_t *ids, float *dists, uint32_t *counts) {
+  QuerySet s = q;
+  s.nq = cnt;
+  if (q.qvectors) s.qvectors = (const unsigned char *)q.qvectors + q0 * q.qstride;
+  if (q.qheaders) s.qheaders = (const unsigned char *)q.qheaders + q0 * hdr_bytes(q.b->o.metric);
+  if (q.query_items) s.query_items = q.query_items + q0;
+  s.out_ids = ids, s.out_dists = dists, s.out_counts = counts;
+  return s;
+}
+// one set of codec rows serves both builders: the same ingest codec, header constant and bytes
+static bool same_codec(const hny_builder *x, const hny_builder *y) {
+  IngestArgs cx{}, cy{};
+  ingest_codec(cx, x->o.metric, x->o.dim);
+  ingest_codec(cy, y->o.metric, y->o.dim);
+  return cx.codec == cy.codec && cx.hdr_const == cy.hdr_const && cx.vb == cy.vb && cx.hb == cy.hb;
+}
+
+// Both stages.  Stage 1's hits travel through the library's own result rows, n_rescore ids per query (DESIGN.md
+// §3f-3), and go up again as they lie: no id is looked at in between
+static int nns_rescored_impl(hny_builder *coarse, hny_builder *fine, const hny_rescore_opts *o, QuerySet q1, QuerySet q2) {
+  if (int rc = check_rescore_opts(o, true)) return rc;
+  if (!coarse || !fine || !q2.out_ids || !q2.out_dists || !q2.out_counts) return fail(HNY_ERR_INVALID_ARG, "bad argument");
+  if (coarse->device != fine->device)
+    return fail(HNY_ERR_INVALID_ARG, "the builders are on devices %d and %d", coarse->device, fine->device);
+  if (coarse->o.dim != fine->o.dim)
+    return fail(HNY_ERR_INVALID_ARG, "the builders have %u and %u dimensions", coarse->o.dim, fine->o.dim);
+  if (int rc = check_query_source(q2, "no queries")) return rc;
+  if (!q2.by_item && !q2.q_f32 && !same_codec(coarse, fine))
+    return fail(HNY_ERR_INVALID_ARG, "the builders' codecs differ: give f32 queries or query items");
+  q1.k = o->n_rescore;
+  q2.k = o->k;
+  if (int rc = check_rescore_queries(q2)) return rc;
+  if (int rc = check_build_finished(coarse)) return rc;
+  if (int rc = check_query_stride(q1)) return rc;
+  const uint32_t R = o->n_rescore;
+  HIP_TRY(hipSetDevice(fine->device));
+  // the hand-over rows of one chunk, pinned: stage 1 writes its hits here (its distances too: nns_impl has no form
+  // without them), stage 2 uploads the ids from here
+  const uint32_t chunk = (uint32_t)std::min<uint64_t>(HNY_RESCORE_CHUNK, std::max<uint64_t>(q1.nq, 1));
+  PinnedBuf<uint32_t> ids1, counts1;
+  PinnedBuf<float> dists1;
+  HIP_TRY(ids1.alloc((size_t)chunk * R));
+  HIP_TRY(dists1.alloc((size_t)chunk * R));
+  HIP_TRY(counts1.alloc(chunk));
+  if (o->did_cancel) *o->did_cancel = 0;
+  bool cancelled = false;
+  for (uint64_t q0 = 0; q0 < q1.nq; q0 += chunk) {
+    const uint64_t cnt = std::min<uint64_t>(chunk, q1.nq - q0);
+    int32_t cancelled1 = 0, cancelled2 = 0;
+    const hny_query_opts qo1 = rescore_query_opts(o, R, &cancelled1);
+    if (int rc = nns_impl(coarse, &qo1, query_slice(q1, q0, cnt, ids1.p, dists1.p, counts1.p))) return rc;
+    RescoreCands C;
+    C.ids = ids1.p;
+    C.row = R;
+    C.counts = counts1.p;
+    C.stage1_cancelled = cancelled1 != 0;
+    const hny_query_opts qo2 = rescore_query_opts(o, o->k, &cancelled2);
+    SearchCancel sc;
+    HIP_TRY(sc.begin(&qo2));
+    const QuerySet s2 = query_slice(q2, q0, cnt, q2.out_ids + q0 * q2.k, q2.out_dists + q0 * q2.k, q2.out_counts + q0);
+    if (int rc = rescore_run(fine, s2, C, sc)) return rc;
+    if (int rc = search_end(fine, &qo2, sc)) return rc;
+    cancelled = cancelled || cancelled1 || cancelled2;
+  }
+  if (o->did_cancel) *o->did_cancel = cancelled;
+  return HNY_OK;
+}
+
+int hny_builder_nns_rescored(hny_builder *coarse, hny_builder *fine, const hny_rescore_opts *o, uint64_t nq,
+                             const void *qvectors, size_t qstride, const void *qheaders, const uint32_t *query_items,
+                             uint32_t *out_ids, float *out_dists, uint32_t *out_counts) {
+  return nns_rescored_impl(coarse, fine, o,
+                           QuerySet::of(coarse, nullptr, nq, qvectors, qstride, qheaders, query_items, nullptr, nullptr, nullptr),
+                           QuerySet::of(fine, nullptr, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists, out_counts));
+}
+
+int hny_builder_nns_rescored_f32(hny_builder *coarse, hny_builder *fine, const hny_rescore_opts *o, uint64_t nq,
+                                 const float *queries, size_t qstride, uint32_t *out_ids, float *out_dists,
+                                 uint32_t *out_counts) {
+  return nns_rescored_impl(coarse, fine, o,
+                           QuerySet::of_f32(coarse, nullptr, nq, queries, qstride, nullptr, nullptr, nullptr),
+                           QuerySet::of_f32(fine, nullptr, nq, queries, qstride, out_ids, out_dists, out_counts));
+}
+
+// ---------------------------------------------------------------------------------------------
 // One candidates filter per query.  The rows of the queries of one filter are those of nns_impl on
 // these queries alone with that filter; here the filters become bitsets on the device (hnyk_filter_masks), each
 // decides should_linear_scan from its own count, and the queries run as three classes through the launches the
@@ -4711,7 +5012,7 @@ struct FilterRounds {
   DevBuf<u32> dlin, dcs;
   DevBuf<u64> dcs_off;
 
-  static u32 mask_stride(uint32_t n) { return (u32)((((size_t)n + 31) / 32 + 4) & ~(size_t)3); }
+  static u32 mask_stride(uint32_t n) { return slot_mask_stride(n); }
   FilterRounds(hny_builder *b, const QuerySet &q, const FilterSource *fl)
       : b(b), q(q), fl(fl), stride(mask_stride(b->n)),
         per_round((size_t)std::max<uint64_t>(1, filter_mask_budget() / ((uint64_t)stride * 4))) {
@@ -4755,18 +5056,8 @@ struct FilterRounds {
   // masks from the builder's ids and live bits, which the first call puts on the device.  No id is touched here
   int build_from_id_bits(size_t r0, size_t nf) {
     const hny_query_bitsets *ib = fl->id_bits;
-    const bool identity = b->ids[b->n - 1] == b->n - 1; // QuerySet::live_slot's test: slot == id
-    if (!b->d_live_bits.p) {
-      std::vector<u32> live(stride, 0u);
-      for (uint32_t s = 0; s < b->n; s++)
-        if (q.live(s)) live[s >> 5] |= 1u << (s & 31);
-      if (!identity) {
-        HIP_TRY(b->d_item_ids.alloc(b->n));
-        HIP_TRY(hipMemcpy(b->d_item_ids.p, b->ids.data(), (size_t)b->n * 4, hipMemcpyHostToDevice));
-      }
-      HIP_TRY(b->d_live_bits.alloc(stride));
-      HIP_TRY(hipMemcpy(b->d_live_bits.p, live.data(), (size_t)stride * 4, hipMemcpyHostToDevice));
-    }
+    const u32 *item_ids = nullptr; // null where slot == id (QuerySet::live_slot's test)
+    if (int rc = ensure_live_bits(b, q, &item_ids)) return rc;
     const size_t row_words = (size_t)((ib->n_bits + 31) / 32);
     const size_t group = (size_t)std::max<uint64_t>(1, filter_mask_budget() / std::max<uint64_t>(row_words * 4, 1));
     HIP_TRY(dmasks.alloc(nf * stride));
@@ -4775,7 +5066,7 @@ struct FilterRounds {
     HIP_TRY(hipMemsetAsync(dcount.p, 0, nf * 4, b->stream));
     for (size_t j0 = 0; j0 < nf; j0 += group) {
       const size_t j1 = std::min(nf, j0 + group);
-      FilterIdBits a{dmasks.p + j0 * stride, stride, b->n, identity ? nullptr : b->d_item_ids.p, b->d_live_bits.p,
+      FilterIdBits a{dmasks.p + j0 * stride, stride, b->n, item_ids, b->d_live_bits.p,
                      dstage.p, (u32)row_words, ib->n_bits, (u32)(j1 - j0), HNY_SENT};
       for (size_t j = j0; j < j1; j++) {
         const u32 f = used[r0 + j];

@@ -442,6 +442,26 @@ HNY_LDS_FN NnsLinearLds nns_linear_lds(LdsCarve &c, u32 rcap) {
   L.nb_d = c.take<float>(64);
   return L;
 }
+// k_rescore (one 256-thread workgroup per query): the query's candidates as slots, their keys, the scratch of a
+// distance pass for each of the four waves, and the words the waves exchange (ctl[0..4): a wave's count in a
+// compaction round, ctl[4]: the cancel word as thread 0 read it)
+#define HNY_RESCORE_WAVES 4
+struct RescoreLds {
+  u64 *keys;   // [rcap] dist bits << 32 | slot
+  u32 *slots;  // [rcap]
+  u32 *nb_ids; // [HNY_RESCORE_WAVES][64]
+  float *nb_d; // [HNY_RESCORE_WAVES][64]
+  u32 *ctl;    // [8]
+};
+HNY_LDS_FN RescoreLds rescore_lds(LdsCarve &c, u32 rcap) {
+  RescoreLds L;
+  L.keys = c.take<u64>(rcap);
+  L.slots = c.take<u32>(rcap);
+  L.nb_ids = c.take<u32>(HNY_RESCORE_WAVES * 64);
+  L.nb_d = c.take<float>(HNY_RESCORE_WAVES * 64);
+  L.ctl = c.take<u32>(8);
+  return L;
+}
 // k_exact_topk
 struct ExactTopkLds {
   u64 *res; // [rcap]
@@ -589,6 +609,29 @@ hipError_t hnyk_prune(const GraphDev &g, const PruneArgs &a, LaunchShape s, cons
 // a.heap_r set: `res` as a heap in HBM too (result sets beyond the LDS), else the sorted LDS array
 hipError_t hnyk_nns(const GraphDev &g, const NnsArgs &a, LaunchShape s, int grid, hipStream_t st);
 hipError_t hnyk_nns_linear(const GraphDev &g, const NnsArgs &a, LaunchShape s, int grid, hipStream_t st);
+// Two-stage search, stage 2 (hny_builder_rescore): every query's own short candidate list, given as
+// item ids, resolved to live slots, scored and ranked by one workgroup (k_rescore)
+#define HNY_RESCORE_MAX 4095u  // candidates per query: the raw list sits in LDS (rcap <= 4 096)
+#define HNY_RESCORE_CHUNK 1024u // queries per launch
+#define HNY_RESCORE_GRID 768u   // workgroups at most: three of 50 KB per CU; the queries beyond are a grid stride
+struct RescoreArgs {
+  const u32 *q_slots;          // by item: the query's slot, HNY_SENT = it has none (0 hits, the host keeps its NONE)
+  const unsigned char *q_rows; // by vector: staged query rows / header norms
+  const float *q_norms;
+  u32 q_stride;
+  u32 nq;
+  const u64 *cand_beg;         // [nq] where query i's candidates start in cand_ids
+  const u32 *cand_cnt;         // [nq] how many there are, each <= rcap
+  const u32 *cand_ids;         // item ids: any order, duplicates, unknown and deleted ids allowed
+  const u32 *item_ids;         // [n] slot -> item id, ascending; null = the identity
+  const u32 *live;             // bitset over slots: the slot holds a live item
+  u32 k, kk, rcap;             // wanted hits, entries per output row (min(k, longest list)), LDS capacity (a power of two)
+  u32 *out_ids;                // [nq][kk]
+  u32 *out_dist_bits;          // [nq][kk]
+  u32 *out_counts;             // [nq]: hits, HNY_SENT = by item and no live candidate; 0 for a query never started
+  const u32 *cancel;           // pinned host word, non-zero = start no further query
+};
+hipError_t hnyk_rescore(const GraphDev &g, const RescoreArgs &a, LaunchShape s, hipStream_t st);
 // per-query filters: n_filters bitsets over slots, `stride` words apart, from slot lists in CSR form
 // (off[n_filters + 1]); `masks` and `count` must be zero before hnyk_filter_masks, which sets the bits and counts them
 hipError_t hnyk_filter_masks(u32 *masks, u32 stride, const u64 *off, const u32 *slots, u32 n_filters, u64 n_slots,

@@ -37,15 +37,18 @@
 // keeps the order and that pending LDS returns are waited for.  __syncthreads() did that too, but it
 // also drains vmcnt(0) — every row / neighbour-list load in flight — at each of the ~20 syncs of an
 // expansion.
-#ifdef HNY_WSYNC_BARRIER
-#define WSYNC() __syncthreads()
-#else
-#define WSYNC()                                               \
+// WSYNC_WAVE: the wave-local form itself, also for the waves of a larger workgroup whose loops run a different
+// number of times (k_rescore's score phase), where a workgroup barrier would not be met by every wave.
+#define WSYNC_WAVE()                                          \
   do {                                                        \
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");    \
     __builtin_amdgcn_wave_barrier();                          \
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");    \
   } while (0)
+#ifdef HNY_WSYNC_BARRIER
+#define WSYNC() __syncthreads()
+#else
+#define WSYNC() WSYNC_WAVE()
 #endif
 
 #ifndef HNY_RB_MERGE
@@ -2834,6 +2837,157 @@ __global__ __launch_bounds__(64, 4) void k_nns_linear(GraphDev g, NnsArgs a) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Two-stage search, stage 2 (hny_builder_rescore).  k_nns_linear above ranks ONE candidate set, or
+// a few shared ones, that the host has already turned into ascending live slots, one wave per query and a serial
+// sorted_insert per accepted key.  Here every query brings its own short list of item ids (the hits of a coarse
+// index), so the whole of it is done by a workgroup of four waves per query, in three phases that live in LDS:
+// resolve (ids -> distinct live slots, ascending), score (the waves share the batches of 64 slots; dist_rows, hence
+// the bits of every other path, strict mode included), select (one bitonic sort of the keys).  Nothing is
+// proportional to the number of items: rows read = distinct live candidates.
+// ---------------------------------------------------------------------------------------------
+// v[0 .. P) ascending, P a power of two, by the 256 threads of a workgroup: the bitonic network, one barrier per
+// step (P = 4 096: 78 steps of 8 compare-exchanges per thread).  Opens and closes with a barrier
+template <typename T>
+__device__ __forceinline__ void wg_bitonic_sort(T *v, u32 P) {
+  for (u32 size = 2; size <= P; size <<= 1)
+    for (u32 stride = size >> 1; stride > 0; stride >>= 1) {
+      __syncthreads();
+      for (u32 i = threadIdx.x; i < P / 2; i += 256u) {
+        const u32 lo = 2u * i - (i & (stride - 1u)), hi = lo + stride; // the pair whose indices differ in bit `stride`
+        const bool up = (lo & size) == 0u;
+        const T x = v[lo], y = v[hi];
+        if ((x > y) == up) {
+          v[lo] = y;
+          v[hi] = x;
+        }
+      }
+    }
+  __syncthreads();
+}
+
+// (no-packed-fp32-ops: the distance chains inlined here are emitted as single f32 operations, never paired into
+// v_pk_*_f32 — IEEE operation for operation the same bits, and this kernel waits on its row gather, not on the VALU)
+#ifdef __HIP_DEVICE_COMPILE__
+#define HNY_NO_PACKED_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define HNY_NO_PACKED_F32 // (the host pass knows no such feature)
+#endif
+template <int LPR, int NCH>
+__global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_rescore(GraphDev g, RescoreArgs a) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  LdsCarve lds(smem);
+  const RescoreLds lay = rescore_lds(lds, a.rcap);
+  u64 *keys = lay.keys;
+  u32 *slots = lay.slots, *ctl = lay.ctl;
+  const u32 tid = threadIdx.x, wave = uni(tid >> 6);
+  const int ln = HNY_LANE, t = ln % LPR;
+  u32 *nb_ids = lay.nb_ids + wave * 64u;
+  float *nb_d = lay.nb_d + wave * 64u;
+  u64 evals = 0;
+  for (u32 m = blockIdx.x; m < a.nq; m += gridDim.x) {
+    __syncthreads(); // the query before is out of the LDS
+    if (tid == 0) ctl[4] = a.cancel ? __hip_atomic_load(a.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : 0u;
+    __syncthreads();
+    const u32 qslot = a.q_slots ? uni(a.q_slots[m]) : 0u;
+    if (uni(ctl[4]) || qslot == HNY_SENT) { // cancelled before it started, or by item without a row: 0 hits
+      if (tid == 0) a.out_counts[m] = 0u;
+      continue;
+    }
+    u32 cnt = uni(a.cand_cnt[m]);
+    if (cnt > a.rcap) cnt = a.rcap; // (the host refuses longer lists)
+    const u32 *cand = a.cand_ids + uni64(a.cand_beg[m]);
+    u32 P = 1;
+    while (P < cnt) P <<= 1;
+    // ---- resolve: item id -> slot of a live item, HNY_SENT for every other id and for the padding up to P
+    for (u32 i = tid; i < P; i += 256u) {
+      u32 s = HNY_SENT;
+      if (i < cnt) {
+        const u32 id = cand[i];
+        if (!a.item_ids) {
+          if (id < g.n) s = id;
+        } else {
+          u32 lo = 0, hi = g.n;
+          while (lo < hi) {
+            const u32 mid = lo + ((hi - lo) >> 1);
+            if (a.item_ids[mid] < id) lo = mid + 1u;
+            else hi = mid;
+          }
+          if (lo < g.n && a.item_ids[lo] == id) s = lo;
+        }
+        if (s != HNY_SENT && !((a.live[s >> 5] >> (s & 31u)) & 1u)) s = HNY_SENT;
+      }
+      slots[i] = s;
+    }
+    wg_bitonic_sort(slots, P);
+    // sentinels and equal neighbours out, in rounds of 256: ballot, the waves' counts through ctl, prefix popcount.
+    // A round writes below the places it read, and a value it stores at the last place it read is the one that was
+    // there (only when nothing before it was dropped), so the next round's look at its left neighbour still holds
+    u32 nlive = 0;
+    for (u32 r0 = 0; r0 < P; r0 += 256u) {
+      const u32 i = r0 + tid;
+      const u32 v = i < P ? slots[i] : HNY_SENT;
+      const u32 pv = (i > 0u && i < P) ? slots[i - 1u] : HNY_SENT;
+      const bool keep = v != HNY_SENT && v != pv;
+      const u64 bal = ballot(keep);
+      if (ln == 0) ctl[wave] = (u32)__popcll(bal);
+      __syncthreads();
+      u32 before = 0, total = 0;
+#pragma unroll
+      for (u32 w = 0; w < HNY_RESCORE_WAVES; w++) {
+        const u32 c = ctl[w];
+        total += c;
+        if (w < wave) before += c;
+      }
+      if (keep) slots[nlive + before + (u32)__popcll(bal & ((1ull << ln) - 1ull))] = v;
+      nlive += total;
+      __syncthreads();
+    }
+    nlive = uni(nlive);
+    // ---- score: wave w takes the batches w, w + 4, ... of 64 slots; the query row sits in its registers
+    if (wave * 64u < nlive) {
+      float qn = 0.f;
+      const unsigned char *qrow;
+      if (a.q_slots) {
+        qrow = g.rows + (size_t)qslot * g.row_stride;
+        if (g.norms) qn = g.norms[qslot];
+      } else {
+        qrow = a.q_rows + (size_t)m * a.q_stride;
+        if (a.q_norms) qn = a.q_norms[m];
+      }
+      float4 q[NCH];
+      load_row<LPR, NCH>(qrow, t, g.n16, q);
+      for (u32 base = wave * 64u; base < nlive; base += HNY_RESCORE_WAVES * 64u) {
+        const int nc = (int)(nlive - base < 64u ? nlive - base : 64u);
+        WSYNC_WAVE();
+        if (ln < nc) nb_ids[ln] = slots[base + (u32)ln];
+        WSYNC_WAVE();
+        dist_rows<LPR, NCH>(g, q, qn, nb_ids, nc, nb_d, qrow);
+        WSYNC_WAVE();
+        if (ln < nc) keys[base + (u32)ln] = ((u64)fbits(nb_d[ln]) << 32) | nb_ids[ln];
+      }
+    }
+    // ---- select: (distance bits, slot) ascending is (distance bits, id) ascending, slots being in id order
+    u32 P2 = 1;
+    while (P2 < nlive) P2 <<= 1;
+    for (u32 i = nlive + tid; i < P2; i += 256u) keys[i] = ~0ull;
+    wg_bitonic_sort(keys, P2);
+    u32 c = nlive < a.k ? nlive : a.k;
+    if (c > a.kk) c = a.kk;
+    for (u32 e = tid; e < c; e += 256u) {
+      const u64 key = keys[e];
+      const u32 slot = (u32)(key & 0xFFFFFFFFull);
+      a.out_ids[(size_t)m * a.kk + e] = a.item_ids ? a.item_ids[slot] : slot;
+      a.out_dist_bits[(size_t)m * a.kk + e] = (u32)(key >> 32);
+    }
+    if (tid == 0) {
+      a.out_counts[m] = nlive ? c : (a.q_slots ? HNY_SENT : 0u);
+      evals += (u64)nlive;
+    }
+  }
+  if (tid == 0 && evals) atomicAdd(&g.stats[ST_EVALS_WALK], evals);
+}
+
 // Exact k-NN, dense scan (hny_builder_exact_knn).  k_nns_linear above fetches every candidate row
 // once per query; here a workgroup of four waves stages a tile of a.qt query rows in LDS and every wave reads its
 // share of a chunk of consecutive slots from HBM once for the whole tile.  Per (query, row) pair the work is
@@ -4698,6 +4852,14 @@ struct NnsLinearLauncher {
   }
 };
 template <int L, int C>
+struct RescoreLauncher {
+  static hipError_t run(const GraphDev &g, const RescoreArgs &a, hipStream_t st) {
+    const size_t lds = HNY_LDS_BYTES(rescore_lds, a.rcap);
+    const u32 grid = a.nq < HNY_RESCORE_GRID ? a.nq : HNY_RESCORE_GRID;
+    return launch_with_lds(k_rescore<L, C>, dim3(grid), dim3(HNY_RESCORE_WAVES * 64), lds, st, g, a);
+  }
+};
+template <int L, int C>
 struct ExactScoresLauncher {
   static hipError_t run(const GraphDev &g, const ExactArgs &a, hipStream_t st) {
     const size_t lds = HNY_LDS_BYTES(exact_scores_lds, a.qt, g.row_stride);
@@ -4791,6 +4953,11 @@ hipError_t hnyk_nns(const GraphDev &g, const NnsArgs &a, LaunchShape s, int grid
 }
 hipError_t hnyk_nns_linear(const GraphDev &g, const NnsArgs &a, LaunchShape s, int grid, hipStream_t st) {
   return dispatch_shape<NnsLinearLauncher>(s, g, a, grid, st);
+}
+hipError_t hnyk_rescore(const GraphDev &g, const RescoreArgs &a, LaunchShape s, hipStream_t st) {
+  if (!a.nq) return hipSuccess;
+  if (a.rcap < 1u || a.rcap > HNY_RESCORE_MAX + 1u || (a.rcap & (a.rcap - 1u))) return hipErrorInvalidValue;
+  return dispatch_shape<RescoreLauncher>(s, g, a, st);
 }
 hipError_t hnyk_exact_scores(const GraphDev &g, const ExactArgs &a, LaunchShape s, hipStream_t st) {
   if (!a.nq || !a.slab_n) return hipSuccess;

@@ -500,6 +500,58 @@ int hny_builder_exact_knn_bitsets_f32(hny_builder *b, const hny_query_opts *opts
                                       uint64_t n_queries, const float *queries, size_t qstride,
                                       uint32_t *out_ids, float *out_dists, uint32_t *out_counts);
 
+/* ---- two-stage search: the hits of a coarse index rescored on a fine one.  The use of the two
+ * builders that hny_builder_create_changed_distance leaves resident: the walk runs over the binary-quantized codes,
+ * its n_rescore best hits are ranked again on the f32 rows of the source builder, k of them are returned.
+ *
+ * hny_builder_rescore is stage 2 alone.  The candidates of query i are the item ids cand_ids[cand_offsets[i] ..
+ * cand_offsets[i + 1]): any order, duplicates, unknown and deleted ids allowed (they drop out).  Row i is, byte for
+ * byte on ids, distance bits and counts, what hny_builder_exact_knn(fine, k, has_candidates = 1, candidates = that
+ * list) returns for query i alone: the min(k, distinct live candidates) nearest, by (distance bits, id).  An empty
+ * list, or one without a live id, gives 0 hits, HNY_NNS_NONE by item; by item an unknown or deleted query item gives
+ * HNY_NNS_NONE, and the item itself stays in when its list holds it.  Strict mode is served.  Only the first
+ * out_counts[i] entries of row i (of k entries) are written.  One workgroup per query resolves, scores and ranks the
+ * list in LDS: the work is proportional to the candidates given, nothing to the number of items.
+ *
+ * hny_builder_nns_rescored is both stages: hny_builder_nns on `coarse` with k = n_rescore, ef_search and no
+ * candidates, by vector or by item, then hny_builder_rescore on `fine` with the ids stage 1 found for each query; by
+ * item the query row of stage 2 is fine's stored row of the same item.  A query stage 1 answers with HNY_NNS_NONE
+ * stays HNY_NNS_NONE.  The builders must be on one device and have the same dim, both finished or loaded; they need
+ * not hold the same items or related metrics.  By vector the codec rows serve both stages, so the two metrics must
+ * share a codec (HNY_ERR_INVALID_ARG otherwise: use the _f32 form, which encodes the row once per builder, or by item).
+ *
+ * Decided before any device work, outputs untouched, in this order: opts == NULL, a wrong struct_size, k == 0,
+ * n_rescore < k (fused): HNY_ERR_INVALID_ARG; n_rescore > 4 095 (fused): HNY_ERR_UNSUPPORTED; cand_offsets == NULL,
+ * cand_offsets[0] != 0, decreasing offsets, cand_ids == NULL with candidates to read: HNY_ERR_INVALID_ARG; a NULL
+ * builder or output array, no queries given, builders on different devices or of different dim: HNY_ERR_INVALID_ARG;
+ * a builder whose build has not finished: HNY_ERR_INVALID_ARG; qstride below the row's bytes: HNY_ERR_INVALID_DIM;
+ * a list of more than 4 095 ids, counted before duplicates drop out: HNY_ERR_UNSUPPORTED.
+ *
+ * Cancellation as for hny_builder_nns: a query that was not started reports 0 hits, *did_cancel = 1.
+ * hny_rescore_opts carries its own struct_size and is not part of hny_abi_sizes. ---- */
+typedef struct {
+  uint32_t struct_size;      /* sizeof(hny_rescore_opts) as the caller compiled it; anything else: HNY_ERR_INVALID_ARG */
+  uint32_t k;                /* hits returned per query, >= 1 */
+  uint32_t n_rescore;        /* R: coarse hits rescored per query, k <= R <= 4 095 (fused calls only) */
+  uint32_t ef_search;        /* stage 1, as in hny_query_opts; fused calls only */
+  int (*cancel)(void *);
+  void *cancel_ctx;
+  int32_t *did_cancel;
+} hny_rescore_opts;
+int hny_builder_rescore(hny_builder *fine, const hny_rescore_opts *opts, uint64_t n_queries, const void *qvectors,
+                        size_t qstride, const void *qheaders, const uint32_t *query_items,
+                        const uint64_t *cand_offsets, const uint32_t *cand_ids, uint32_t *out_ids, float *out_dists,
+                        uint32_t *out_counts);
+int hny_builder_rescore_f32(hny_builder *fine, const hny_rescore_opts *opts, uint64_t n_queries, const float *queries,
+                            size_t qstride, const uint64_t *cand_offsets, const uint32_t *cand_ids, uint32_t *out_ids,
+                            float *out_dists, uint32_t *out_counts);
+int hny_builder_nns_rescored(hny_builder *coarse, hny_builder *fine, const hny_rescore_opts *opts, uint64_t n_queries,
+                             const void *qvectors, size_t qstride, const void *qheaders, const uint32_t *query_items,
+                             uint32_t *out_ids, float *out_dists, uint32_t *out_counts);
+int hny_builder_nns_rescored_f32(hny_builder *coarse, hny_builder *fine, const hny_rescore_opts *opts,
+                                 uint64_t n_queries, const float *queries, size_t qstride, uint32_t *out_ids,
+                                 float *out_dists, uint32_t *out_counts);
+
 /* ---- exact range search: every item within a radius of each query, and how many there are.  The question a score
  * threshold, a near-duplicate check before an upsert or "how many items lie within r" asks; it has no k, and no k of
  * the calls above answers it.
