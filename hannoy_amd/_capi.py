@@ -54,6 +54,8 @@ EXPORTED = [
     "hny_builder_load_encoded", "hny_builder_load_encoded_f32", "hny_builder_create_incremental_encoded",
     "hny_build_incremental_encoded", "hny_encoded_links_measure", "hny_lmdb_read_links",
     "hny_builder_rescore", "hny_builder_rescore_f32", "hny_builder_nns_rescored", "hny_builder_nns_rescored_f32",
+    "hny_builder_exact_knn_screened", "hny_builder_exact_knn_screened_f32", "hny_builder_exact_screen_stats",
+    "hny_builder_exact_screen_times", "hny_builder_exact_screen_bounds", "hny_builder_n_slots",
 ]
 ERR_IO = -9
 NNS_NONE = 0xFFFFFFFF  # by_item: the reference returns None
@@ -434,6 +436,18 @@ def load_library():
     L.hny_builder_exact_knn.argtypes = [vp, C.POINTER(QueryOpts), C.c_uint64, vp, C.c_size_t, vp, vp, vp, vp, vp]
     L.hny_builder_exact_knn_f32.restype = C.c_int
     L.hny_builder_exact_knn_f32.argtypes = [vp, C.POINTER(QueryOpts), C.c_uint64, vp, C.c_size_t, vp, vp, vp]
+    L.hny_builder_exact_knn_screened.restype = C.c_int
+    L.hny_builder_exact_knn_screened.argtypes = L.hny_builder_exact_knn.argtypes
+    L.hny_builder_exact_knn_screened_f32.restype = C.c_int
+    L.hny_builder_exact_knn_screened_f32.argtypes = L.hny_builder_exact_knn_f32.argtypes
+    L.hny_builder_exact_screen_stats.restype = C.c_int
+    L.hny_builder_exact_screen_stats.argtypes = [vp, vp, vp, vp]
+    L.hny_builder_exact_screen_times.restype = C.c_int
+    L.hny_builder_exact_screen_times.argtypes = [vp, vp]
+    L.hny_builder_exact_screen_bounds.restype = C.c_int
+    L.hny_builder_exact_screen_bounds.argtypes = [vp, C.c_uint64, vp, C.c_size_t, vp, C.c_uint64, vp, vp]
+    L.hny_builder_n_slots.restype = C.c_uint64
+    L.hny_builder_n_slots.argtypes = [vp]
     L.hny_builder_nns_filtered.restype = C.c_int
     L.hny_builder_nns_filtered.argtypes = [vp, C.POINTER(QueryOpts), C.POINTER(QueryFilters), C.c_uint64, vp, C.c_size_t,
                                            vp, vp, vp, vp, vp]
@@ -1678,13 +1692,40 @@ class Builder:
         """exact_knn(by_vector) with f32 queries, encoded on the device"""
         return self.exact_knn(qf32=_f32_rows(queries), **kw)
 
-    def exact_knn(self, qcodes=None, qheaders=None, k=10, candidates=None, query_items=None, cancel=None, qf32=None):
+    def exact_knn(self, qcodes=None, qheaders=None, k=10, candidates=None, query_items=None, cancel=None, qf32=None,
+                  screened=False):
         """hny_builder_exact_knn: the k nearest of the live items (or of `candidates` among them) by a flat scan —
         brute_force_search's result, the ground truth of the index's own distances.  Returns (ids, dists, counts)
-        like nns; counts == NNS_NONE where by_item names an unknown item."""
+        like nns; counts == NNS_NONE where by_item names an unknown item.
+        screened: hny_builder_exact_knn_screened, the same result through the matrix cores (exact_screen_stats)."""
         opts = _query_opts(k, candidates=candidates, cancel=cancel)
-        return self._search("hny_builder_exact_knn", opts, _query_source(query_items, qf32, qcodes, qheaders),
-                            qf32 is not None)
+        name = "hny_builder_exact_knn_screened" if screened else "hny_builder_exact_knn"
+        return self._search(name, opts, _query_source(query_items, qf32, qcodes, qheaders), qf32 is not None)
+
+    def exact_screen_stats(self):
+        """hny_builder_exact_screen_stats of the last exact_knn(screened=True): (n_screened, n_routed, n_candidates)"""
+        out = [C.c_uint64(0) for _ in range(3)]
+        _check(load_library().hny_builder_exact_screen_stats(self._h, *map(C.byref, out)))
+        return tuple(int(v.value) for v in out)
+
+    def exact_screen_times(self):
+        """hny_builder_exact_screen_times: device ms of the last screened call on a profiling builder, as
+        (d_hi scan, k_exact_topk, d_lo scan, collect, settle)"""
+        out = np.zeros(5, np.float64)
+        _check(load_library().hny_builder_exact_screen_times(self._h, _p(out)))
+        return tuple(float(v) for v in out)
+
+    def exact_screen_bounds(self, qcodes, qheaders):
+        """hny_builder_exact_screen_bounds: (lo, hi), f32 [n_queries, n_slots()], the screen's interval of every pair"""
+        (nq, qc, qs, qh, _), _keep = _query_source(qcodes=qcodes, qheaders=qheaders)
+        n = self.n_slots()
+        lo, hi = np.zeros((nq, n), np.float32), np.zeros((nq, n), np.float32)
+        _check(load_library().hny_builder_exact_screen_bounds(self._h, nq, qc, qs, qh, n, _p(lo), _p(hi)))
+        return lo, hi
+
+    def n_slots(self):
+        """hny_builder_n_slots: the builder's items and, after deletions or an update, the slots that stay behind"""
+        return int(load_library().hny_builder_n_slots(self._h))
 
     def _range(self, radius, count_only, qcodes, qheaders, candidates, query_items, cancel, qf32, max_total,
                filters=None):

@@ -653,6 +653,7 @@ class QueryBuilder:
         self._ef, self._candidates = 100, None          # reader.rs:23, 614
         self._linear_below, self._ratio = 1000, 1.0     # reader.rs:28, 31
         self._exact = False
+        self._screened = False
         self._per_query = None
         self._bitsets = None
         self._radius = None
@@ -726,10 +727,13 @@ class QueryBuilder:
         self._ratio = float(ratio)
         return self
 
-    def exact(self):
+    def exact(self, screened=False):
         """the flat scan instead of the graph (hny_builder_exact_knn): brute_force_search over the live items, or
-        over `.candidates()` among them; ef_search and linear_below* are not read"""
+        over `.candidates()` among them; ef_search and linear_below* are not read.
+        screened: the same result through the matrix cores (hny_builder_exact_knn_screened); not read by the forms
+        with a filter per query"""
         self._exact = True
+        self._screened = bool(screened)
         return self
 
     def within(self, radius, filtered=False):
@@ -821,7 +825,8 @@ class QueryBuilder:
                 return r._b.exact_knn_filtered_f32(q, filters, filter_of, k=self.count, cancel=cancel)
             return r._b.nns_filtered_f32(q, filters, filter_of, cancel=cancel, **self._kw_filtered())
         if self._exact:
-            return r._b.exact_knn_f32(q, k=self.count, candidates=self._candidates, cancel=cancel)
+            return r._b.exact_knn_f32(q, k=self.count, candidates=self._candidates, cancel=cancel,
+                                      screened=self._screened)
         return r._b.nns_f32(q, cancel=cancel, **self._kw())  # encoded on the device
 
     def by_items(self, items, cancel=None):
@@ -857,7 +862,7 @@ class QueryBuilder:
                                                **self._kw_filtered())
         if self._exact:
             return self.reader._b.exact_knn(query_items=capi.u32_ids(items), k=self.count,
-                                            candidates=self._candidates, cancel=cancel)
+                                            candidates=self._candidates, cancel=cancel, screened=self._screened)
         return self.reader._b.nns(query_items=capi.u32_ids(items), cancel=cancel, **self._kw())
 
     def by_vector(self, vector):

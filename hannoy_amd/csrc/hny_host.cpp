@@ -470,6 +470,11 @@ struct hny_builder {
   // at creation (hny_builder_reset empties the graph and keeps both; an update makes a successor, a builder of its
   // own), so the two live until hny_builder_destroy and nothing ever has to refresh them
   DevBuf<u32> d_item_ids, d_live_bits;
+  // hny_builder_exact_knn_screened: the f32 sum of squares of every stored row, made by the first
+  // screened call (the rows of a builder never change), and what hny_builder_exact_screen_stats reports
+  DevBuf<float> d_row_n2;
+  uint64_t screen_screened = 0, screen_routed = 0, screen_candidates = 0;
+  double screen_ms[5] = {0, 0, 0, 0, 0}; // profiling: d_hi scan, k_exact_topk, d_lo scan, collect, settle
   // successor builders whose source was profiling: device time (HIP events) and bytes read + written of k_move_rows
   double t_move_rows_s = 0;
   uint64_t move_rows_bytes = 0;
@@ -4179,6 +4184,7 @@ struct TopkOut {
 // (every row read once per tile of qt queries), then the consumer of the slab's scores: k_exact_topk, k_range_count
 // or k_range_emit.  `cancel` is probed before every launch; what slabs() left unfinished reports 0 hits.
 struct DenseScan {
+  using Launch = std::function<hipError_t()>;
   hny_builder *b;
   const QuerySet &q;
   RangeArgs *r; // a range consumer's, null for top-k.  Set here: scores, score_stride, mask, nq, slab_*, radius
@@ -4192,6 +4198,7 @@ struct DenseScan {
   // aim() hands to `a` and `r` with the members, and the tile masks of the members aimed at
   DevBuf<u32> dfof, dtile;
   size_t tile_words = 0;
+  Launch produce; // the slab's scores by another producer than k_exact_scores (k_screen_scores); null = k_exact_scores
 
   DenseScan(hny_builder *b, const QuerySet &q, RangeArgs *r = nullptr) : b(b), q(q), r(r), st{b, q}, q_end(q.nq) {}
   int alloc(uint32_t qblock, const u32 *mask) { // blocks of at most qblock queries; mask: C over slots, on the device
@@ -4239,7 +4246,6 @@ struct DenseScan {
   }
   // Every slab for the queries aimed at: probe, before() if there is one (the filtered top-k's tile masks), the
   // scores, probe, consume().  *stopped: the closure fired, the stream is idle, the consumer's buffers hold a part
-  using Launch = std::function<hipError_t()>;
   int slabs(SearchCancel &sc, bool *stopped, const Launch &consume, const Launch &before = nullptr) {
     *stopped = false;
     for (uint32_t s0 = 0; s0 < b->n; s0 += HNY_EXACT_SLAB) {
@@ -4248,7 +4254,7 @@ struct DenseScan {
       if (r) r->slab_base = a.slab_base, r->slab_n = a.slab_n;
       if ((*stopped = sc.probe())) break;
       if (before) HIP_TRY(before());
-      HIP_TRY(hnyk_exact_scores(b->g, a, b->shape, b->stream));
+      HIP_TRY(produce ? produce() : hnyk_exact_scores(b->g, a, b->shape, b->stream));
       if ((*stopped = sc.probe())) break;
       HIP_TRY(consume());
     }
@@ -5380,46 +5386,69 @@ static int exact_dense_run(hny_builder *b, const QuerySet &qs, const u32 *dmask,
   return HNY_OK;
 }
 
-static int exact_impl(hny_builder *b, const hny_query_opts *qo, const QuerySet &qs) {
+// What exact_impl decides from the arguments, in its order, before any device work; hny_builder_exact_knn_screened
+// takes the same plan, so that both refuse the same calls with the same codes in the same order
+struct ExactPlan {
+  SlotCandidates C;      // C = live items (∩ candidates) as a mask over slots, the one nns_impl builds for its filter
+  uint64_t n_c = 0;      // |C|
+  uint32_t kk = 0;       // hits per query: min(k, |C|)
+  bool answered = false; // C is empty: every query has its answer already
+  bool gather = false;   // strict mode, or a gather of C reads fewer rows than the dense scan
+};
+static int exact_plan(hny_builder *b, const hny_query_opts *qo, const QuerySet &qs, ExactPlan &P) {
   if (int rc = check_search_outputs(qs)) return rc;
   const uint32_t n = b->n, k = qs.k;
   if (int rc = check_query_source(qs, "no queries")) return rc;
   if (int rc = check_candidates(qo)) return rc; // here the candidates come before the f32 rows, in nns_impl after
   if (int rc = check_query_rows(qs)) return rc;
   if (int rc = check_build_finished(b)) return rc;
-  // C = live items (∩ candidates) as a mask over slots, the one nns_impl builds for its filter
-  SlotCandidates C;
-  const uint64_t n_c = qs.slot_mask(qo, C.mask);
+  P.n_c = qs.slot_mask(qo, P.C.mask);
   if (qo->did_cancel) *qo->did_cancel = 0;
-  if (n_c == 0) return qs.none_found();
-  const uint32_t kk = (uint32_t)std::min<uint64_t>(k, n_c); // hits per query
-  if ((uint64_t)kk + 1 > HNY_RES_LDS_MAX)
+  if (P.n_c == 0) {
+    P.answered = true;
+    return qs.none_found();
+  }
+  P.kk = (uint32_t)std::min<uint64_t>(k, P.n_c);
+  if ((uint64_t)P.kk + 1 > HNY_RES_LDS_MAX)
     return fail(HNY_ERR_UNSUPPORTED, "exact scan for %u hits among %llu items: at most %u hits", k,
-                (unsigned long long)n_c, HNY_RES_LDS_MAX - 1);
+                (unsigned long long)P.n_c, HNY_RES_LDS_MAX - 1);
   if (int rc = check_query_stride(qs)) return rc;
   HIP_TRY(hipSetDevice(b->device));
   const uint32_t qt = hnyk_exact_qt(b->g.row_stride);
   const bool strict = b->g.x86_order && b->g.mclass != MC_BIN;
-  if (strict || n_c * qt < n) {
-    // a gather of C reads |C| rows per query, the dense scan n / qt: the one-wave scan over cand_slots = C, the
-    // slots of the mask as they are
-    C.list_slots(n, n_c);
-    C.linear = true;
-    const hny_query_opts o2 = handed_opts(kk, 0, qo, qo->did_cancel);
-    if (kk == k) return nns_slots_impl(b, &o2, qs, &C);
-    SubBatch all{qs, kk}; // rows of kk entries: fewer candidates than k
-    for (uint64_t i = 0; i < qs.nq; i++) all.add(i);
-    if (int rc = nns_slots_impl(b, &o2, all.gather(), &C)) return rc;
-    all.scatter();
-    return HNY_OK;
-  }
+  P.gather = strict || P.n_c * qt < n;
+  return HNY_OK;
+}
+// a gather of C reads |C| rows per query, the dense scan n / qt: the one-wave scan over cand_slots = C, the slots of
+// the mask as they are
+static int exact_gather(hny_builder *b, const hny_query_opts *qo, const QuerySet &qs, ExactPlan &P) {
+  SlotCandidates &C = P.C;
+  const uint32_t kk = P.kk;
+  C.list_slots(b->n, P.n_c);
+  C.linear = true;
+  const hny_query_opts o2 = handed_opts(kk, 0, qo, qo->did_cancel);
+  if (kk == qs.k) return nns_slots_impl(b, &o2, qs, &C);
+  SubBatch all{qs, kk}; // rows of kk entries: fewer candidates than k
+  for (uint64_t i = 0; i < qs.nq; i++) all.add(i);
+  if (int rc = nns_slots_impl(b, &o2, all.gather(), &C)) return rc;
+  all.scatter();
+  return HNY_OK;
+}
+static int exact_dense(hny_builder *b, const hny_query_opts *qo, const QuerySet &qs, ExactPlan &P) {
   DevBuf<u32> dmask;
-  HIP_TRY(dmask.alloc(C.mask.size()));
-  HIP_TRY(hipMemcpyAsync(dmask.p, C.mask.data(), C.mask.size() * 4, hipMemcpyHostToDevice, b->stream));
+  HIP_TRY(dmask.alloc(P.C.mask.size()));
+  HIP_TRY(hipMemcpyAsync(dmask.p, P.C.mask.data(), P.C.mask.size() * 4, hipMemcpyHostToDevice, b->stream));
   SearchCancel sc;
-  HIP_TRY(sc.init(qo)); // (did_cancel was cleared above, ahead of the early returns)
-  if (int rc = exact_dense_run(b, qs, dmask.p, kk, nullptr, sc)) return rc;
+  HIP_TRY(sc.init(qo)); // (did_cancel was cleared by the plan, ahead of the early returns)
+  if (int rc = exact_dense_run(b, qs, dmask.p, P.kk, nullptr, sc)) return rc;
   return search_end(b, qo, sc);
+}
+
+static int exact_impl(hny_builder *b, const hny_query_opts *qo, const QuerySet &qs) {
+  ExactPlan P;
+  if (int rc = exact_plan(b, qo, qs, P)) return rc;
+  if (P.answered) return HNY_OK;
+  return P.gather ? exact_gather(b, qo, qs, P) : exact_dense(b, qo, qs, P);
 }
 
 int hny_builder_exact_knn(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const void *qvectors,
@@ -5432,6 +5461,295 @@ int hny_builder_exact_knn_f32(hny_builder *b, const hny_query_opts *qo, uint64_t
                               size_t qstride, uint32_t *out_ids, float *out_dists, uint32_t *out_counts) {
   if (!queries) return fail(HNY_ERR_INVALID_ARG, "no queries");
   return exact_impl(b, qo, QuerySet::of_f32(b, qo, nq, queries, qstride, out_ids, out_dists, out_counts));
+}
+
+// ---------------------------------------------------------------------------------------------
+// Screened exact k-NN: exact_impl's result, byte for byte, for Cosine and Euclidean in wave order
+// from two matrix-core scans and an exact settling of a few candidates per query.  Pass 1: k_screen_scores writes an
+// upper bound d_hi of every pair's distance, k_exact_topk keeps the k smallest per query: the k-th, T, is at least
+// the k-th exact distance.  Pass 2: lower bounds d_lo, k_screen_collect lists the slots of C with d_lo <= T.  Every
+// item of the true top k is in the list (d_lo <= d <= d_k <= T, ties included), and k_rescore ranks the list on the
+// f32 rows by (distance bits, slot) as k_exact_topk ranks all of C.  Everything else runs exact_impl and is counted
+// as routed: the other metrics, strict mode, filters sparse enough for exact_impl's gather, overflowing lists.
+// ---------------------------------------------------------------------------------------------
+// the constants of the bounds, in double and rounded up; K = the padded dimensions
+static float f32_up(double x) {
+  const float f = (float)x;
+  return (double)f < x ? std::nextafterf(f, INFINITY) : f;
+}
+static void screen_consts(uint32_t n16, ScreenArgs &s) {
+  const double K = 4.0 * n16, u23 = std::ldexp(1.0, -23), u24 = std::ldexp(1.0, -24), tiny = std::ldexp(1.0, -126);
+  s.c_dot = f32_up(1.02 * (2.5 * K + 8) * u23);
+  s.c_l2 = f32_up(1.02 * (2.5 * K + 16) * u23);
+  s.c_sum = f32_up(1.02 * (K + 16) * u24);
+  s.c_n2 = f32_up(1.0 + 1.02 * (K + 16) * u24);
+  s.a_abs = f32_up((3 * K + 8) * tiny);
+  s.a_n2 = f32_up(K * tiny);
+  s.a_flush = f32_up(std::sqrt(K) * tiny);
+}
+static bool screen_serves(const hny_builder *b) {
+  return (b->g.metric == HNY_COSINE || b->g.metric == HNY_EUCLIDEAN) && !b->g.x86_order;
+}
+static int ensure_row_n2(hny_builder *b) {
+  if (b->d_row_n2.p) return HNY_OK;
+  HIP_TRY(b->d_row_n2.alloc(b->n));
+  HIP_TRY(hnyk_screen_n2(b->g.rows, b->g.row_stride, b->g.n16, nullptr, b->n, b->d_row_n2.p, b->stream));
+  return HNY_OK;
+}
+// the sums of squares of the queries DenseScan aims at
+static hipError_t screen_query_n2(hny_builder *b, const ExactArgs &a, float *out) {
+  if (a.q_slots) return hnyk_screen_n2(b->g.rows, b->g.row_stride, b->g.n16, a.q_slots, a.nq, out, b->stream);
+  return hnyk_screen_n2(a.q_rows, a.q_stride, b->g.n16, nullptr, a.nq, out, b->stream);
+}
+
+// device time per kind of launch, for a profiling builder (hny_builder_set_profiling): event pairs around the launches
+struct ScreenClock {
+  hny_builder *b;
+  struct Span {
+    hipEvent_t e0, e1;
+    int kind;
+  };
+  std::vector<Span> spans;
+  ~ScreenClock() { drop(); }
+  void drop() {
+    for (auto &s : spans) (void)hipEventDestroy(s.e0), (void)hipEventDestroy(s.e1);
+    spans.clear();
+  }
+  hipError_t run(int kind, const DenseScan::Launch &f) {
+    if (!b->profiling) return f();
+    Span s{nullptr, nullptr, kind};
+    hipError_t e = hipEventCreate(&s.e0);
+    if (e == hipSuccess) e = hipEventCreate(&s.e1);
+    if (e == hipSuccess) e = hipEventRecord(s.e0, b->stream);
+    if (e == hipSuccess) e = f();
+    if (e == hipSuccess) e = hipEventRecord(s.e1, b->stream);
+    spans.push_back(s);
+    return e;
+  }
+  void add_up() { // the stream is idle
+    for (auto &s : spans) {
+      float ms = 0.f;
+      if (hipEventElapsedTime(&ms, s.e0, s.e1) == hipSuccess) b->screen_ms[s.kind] += ms;
+    }
+    drop();
+  }
+};
+
+// steps 1 - 5 for the queries of `qs`; the queries whose list overflowed are added to `over`
+static int screened_run(hny_builder *b, const QuerySet &qs, const u32 *dmask, uint32_t kk, const u32 *item_ids,
+                        SearchCancel &sc, SubBatch &over) {
+  uint32_t rcap = 64;
+  while (rcap < kk + 1) rcap *= 2;
+  const uint32_t qblock = search_chunk(b, qs.nq, rcap, kk, HNY_EXACT_QBLOCK), LIST = HNY_SCREEN_CAP + 1u;
+  DenseScan scan{b, qs};
+  DevBuf<u64> dlists, dbeg;
+  DevBuf<u32> dln, dcand, dcnt, dout_ids, dout_bits, dout_cnt;
+  DevBuf<float> dqn2;
+  if (int rc = scan.alloc(qblock, dmask)) return rc;
+  HIP_TRY(dlists.alloc((size_t)qblock * rcap));
+  HIP_TRY(dln.alloc(qblock));
+  HIP_TRY(dcand.alloc((size_t)qblock * LIST));
+  // (an overflowed query's list is cut at HNY_SCREEN_CAP entries; k_rescore, whose row for it is not used, reads one more)
+  HIP_TRY(hipMemsetAsync(dcand.p, 0, (size_t)qblock * LIST * 4, b->stream));
+  HIP_TRY(dcnt.alloc(qblock));
+  HIP_TRY(dbeg.alloc(qblock));
+  HIP_TRY(dqn2.alloc(qblock));
+  HIP_TRY(dout_ids.alloc((size_t)qblock * kk));
+  HIP_TRY(dout_bits.alloc((size_t)qblock * kk));
+  HIP_TRY(dout_cnt.alloc(qblock));
+  std::vector<u64> hbeg(qblock);
+  for (uint32_t i = 0; i < qblock; i++) hbeg[i] = (u64)i * LIST;
+  HIP_TRY(hipMemcpyAsync(dbeg.p, hbeg.data(), (size_t)qblock * 8, hipMemcpyHostToDevice, b->stream));
+  std::vector<u32> hcnt(qblock), hout_ids((size_t)qblock * kk), hout_bits((size_t)qblock * kk), hout_cnt(qblock);
+  ExactArgs &a = scan.a;
+  a.lists = dlists.p;
+  a.list_n = dln.p;
+  a.k = kk;
+  a.rcap = rcap;
+  ScreenArgs s{};
+  screen_consts(b->g.n16, s);
+  s.row_n2 = b->d_row_n2.p;
+  s.q_n2 = dqn2.p;
+  ScreenClock clock{b};
+  scan.produce = [&] {
+    return clock.run(s.upper ? 0 : 2, [&] { return hnyk_screen_scores(b->g, a, s, b->stream); });
+  };
+  const DenseScan::Launch topk = [&] { return clock.run(1, [&] { return hnyk_exact_topk(b->g, a, b->stream); }); };
+  const DenseScan::Launch collect = [&] {
+    return clock.run(3, [&] { return hnyk_screen_collect(a, item_ids, dcand.p, dcnt.p, b->stream); });
+  };
+  for (uint64_t q0 = 0; q0 < qs.nq; q0 += qblock) {
+    const uint32_t n_mem = scan.block(q0, qblock);
+    if (n_mem == 0 || sc.probe()) continue; // cancelled: nothing of this block is started, 0 hits each
+    if (int rc = scan.stage()) return rc;
+    scan.aim(0, n_mem);
+    HIP_TRY(screen_query_n2(b, a, dqn2.p));
+    HIP_TRY(hipMemsetAsync(dln.p, 0, (size_t)n_mem * 4, b->stream));
+    HIP_TRY(hipMemsetAsync(dcnt.p, 0, (size_t)n_mem * 4, b->stream));
+    bool stopped;
+    s.upper = 1;
+    if (int rc = scan.slabs(sc, &stopped, topk)) return rc;
+    if (stopped) continue; // the block did not finish: 0 hits each
+    s.upper = 0;
+    if (int rc = scan.slabs(sc, &stopped, collect)) return rc;
+    if (stopped) continue;
+    // settle: k_rescore on the lists as they lie, HNY_SCREEN_CAP + 1 ids apart; a longer list is cut and its
+    // query's row not used
+    RescoreArgs r{};
+    r.q_slots = a.q_slots, r.q_rows = a.q_rows, r.q_norms = a.q_norms, r.q_stride = a.q_stride;
+    r.nq = n_mem;
+    r.cand_beg = dbeg.p, r.cand_cnt = dcnt.p, r.cand_ids = dcand.p;
+    r.item_ids = item_ids;
+    r.live = dmask;
+    r.k = r.kk = kk;
+    r.rcap = LIST;
+    r.out_ids = dout_ids.p, r.out_dist_bits = dout_bits.p, r.out_counts = dout_cnt.p;
+    r.cancel = sc.d;
+    HIP_TRY(clock.run(4, [&] { return hnyk_rescore(b->g, r, b->shape, b->stream); }));
+    HIP_TRY(hipMemcpyAsync(hcnt.data(), dcnt.p, (size_t)n_mem * 4, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemcpyAsync(hout_cnt.data(), dout_cnt.p, (size_t)n_mem * 4, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemcpyAsync(hout_ids.data(), dout_ids.p, (size_t)n_mem * kk * 4, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemcpyAsync(hout_bits.data(), dout_bits.p, (size_t)n_mem * kk * 4, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(sc.wait(b));
+    clock.add_up();
+    if (sc.cancelled) continue; // k_rescore may have left queries out: the block did not finish
+    for (uint32_t j = 0; j < n_mem; j++) {
+      const uint64_t qi = scan.query_of(j);
+      if (hcnt[j] > HNY_SCREEN_CAP) {
+        over.add(qi);
+        continue;
+      }
+      const uint32_t c = hout_cnt[j] == HNY_SENT ? 0u : hout_cnt[j];
+      memcpy(&qs.out_ids[qi * qs.k], &hout_ids[(size_t)j * kk], (size_t)c * 4);
+      memcpy(&qs.out_dists[qi * qs.k], &hout_bits[(size_t)j * kk], (size_t)c * 4);
+      qs.out_counts[qi] = c;
+      b->screen_screened++;
+      b->screen_candidates += hcnt[j];
+    }
+  }
+  return HNY_OK;
+}
+
+static int exact_screened_impl(hny_builder *b, const hny_query_opts *qo, const QuerySet &qs) {
+  if (b) {
+    b->screen_screened = b->screen_routed = b->screen_candidates = 0;
+    for (double &ms : b->screen_ms) ms = 0;
+  }
+  const auto routed = [&] { // exact_impl answers the whole call, its refusals included
+    const int rc = exact_impl(b, qo, qs);
+    if (rc == HNY_OK && b) b->screen_routed = qs.nq;
+    return rc;
+  };
+  if (!b || !screen_serves(b)) return routed();
+  ExactPlan P;
+  if (int rc = exact_plan(b, qo, qs, P)) return rc;
+  if (P.answered) return HNY_OK;
+  if (P.gather) { // nothing dense to screen
+    const int rc = exact_gather(b, qo, qs, P);
+    if (rc == HNY_OK) b->screen_routed = qs.nq;
+    return rc;
+  }
+  SlotCandidates &C = P.C;
+  const uint32_t kk = P.kk;
+  const u32 *item_ids = nullptr;
+  if (int rc = ensure_item_ids(b, &item_ids)) return rc;
+  if (int rc = ensure_row_n2(b)) return rc;
+  DevBuf<u32> dmask;
+  HIP_TRY(dmask.alloc(C.mask.size()));
+  HIP_TRY(hipMemcpyAsync(dmask.p, C.mask.data(), C.mask.size() * 4, hipMemcpyHostToDevice, b->stream));
+  SearchCancel sc;
+  HIP_TRY(sc.init(qo));
+  SubBatch over{qs};
+  if (int rc = screened_run(b, qs, dmask.p, kk, item_ids, sc, over)) return rc;
+  if (int rc = search_end(b, qo, sc)) return rc;
+  if (over.idx.empty() || sc.cancelled) return HNY_OK; // (cancelled: the overflowed queries keep their 0 hits)
+  int32_t cancelled = 0;
+  hny_query_opts o2 = *qo;
+  o2.did_cancel = &cancelled;
+  if (int rc = exact_impl(b, &o2, over.gather())) return rc;
+  over.scatter();
+  b->screen_routed = over.idx.size();
+  if (cancelled && qo->did_cancel) *qo->did_cancel = 1;
+  return HNY_OK;
+}
+
+int hny_builder_exact_knn_screened(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const void *qvectors,
+                                   size_t qstride, const void *qheaders, const uint32_t *query_items, uint32_t *out_ids,
+                                   float *out_dists, uint32_t *out_counts) {
+  return exact_screened_impl(b, qo, QuerySet::of(b, qo, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists,
+                                                 out_counts));
+}
+
+int hny_builder_exact_knn_screened_f32(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const float *queries,
+                                       size_t qstride, uint32_t *out_ids, float *out_dists, uint32_t *out_counts) {
+  if (!queries) return fail(HNY_ERR_INVALID_ARG, "no queries");
+  return exact_screened_impl(b, qo, QuerySet::of_f32(b, qo, nq, queries, qstride, out_ids, out_dists, out_counts));
+}
+
+int hny_builder_exact_screen_stats(const hny_builder *b, uint64_t *n_screened, uint64_t *n_routed, uint64_t *n_candidates) {
+  if (!b) return fail(HNY_ERR_INVALID_ARG, "bad argument");
+  if (n_screened) *n_screened = b->screen_screened;
+  if (n_routed) *n_routed = b->screen_routed;
+  if (n_candidates) *n_candidates = b->screen_candidates;
+  return HNY_OK;
+}
+
+int hny_builder_exact_screen_times(const hny_builder *b, double *out_ms) {
+  if (!b || !out_ms) return fail(HNY_ERR_INVALID_ARG, "bad argument");
+  for (int i = 0; i < 5; i++) out_ms[i] = b->screen_ms[i];
+  return HNY_OK;
+}
+
+uint64_t hny_builder_n_slots(const hny_builder *b) { return b ? b->n : 0; }
+
+int hny_builder_exact_screen_bounds(hny_builder *b, uint64_t nq, const void *qvectors, size_t qstride,
+                                    const void *qheaders, uint64_t n_slots, float *out_lo, float *out_hi) {
+  if (!b || !qvectors || !qheaders || !out_lo || !out_hi) return fail(HNY_ERR_INVALID_ARG, "bad argument");
+  if (n_slots != b->n)
+    return fail(HNY_ERR_INVALID_ARG, "n_slots %llu: the builder has %u slots (hny_builder_n_slots)",
+                (unsigned long long)n_slots, b->n);
+  if (!screen_serves(b))
+    return fail(HNY_ERR_UNSUPPORTED, "the screen serves Cosine and Euclidean builders in wave order");
+  if (nq * (uint64_t)b->n > (uint64_t)1 << 24)
+    return fail(HNY_ERR_UNSUPPORTED, "%llu queries x %u slots: at most 2^24 intervals", (unsigned long long)nq, b->n);
+  std::vector<uint32_t> counts(std::max<uint64_t>(nq, 1));
+  uint32_t none_id = 0;
+  float none_d = 0;
+  QuerySet qs = QuerySet::of(b, nullptr, nq, qvectors, qstride, qheaders, nullptr, &none_id, &none_d, counts.data());
+  if (int rc = check_build_finished(b)) return rc;
+  if (int rc = check_query_stride(qs)) return rc;
+  if (!nq || !b->n) return HNY_OK;
+  HIP_TRY(hipSetDevice(b->device));
+  if (int rc = ensure_row_n2(b)) return rc;
+  const uint32_t qblock = (uint32_t)std::min<uint64_t>(nq, HNY_EXACT_QBLOCK);
+  DenseScan scan{b, qs};
+  DevBuf<float> dqn2;
+  if (int rc = scan.alloc(qblock, nullptr)) return rc;
+  HIP_TRY(dqn2.alloc(qblock));
+  ScreenArgs s{};
+  screen_consts(b->g.n16, s);
+  s.row_n2 = b->d_row_n2.p;
+  s.q_n2 = dqn2.p;
+  scan.produce = [&] { return hnyk_screen_scores(b->g, scan.a, s, b->stream); };
+  SearchCancel sc;
+  for (uint64_t q0 = 0; q0 < nq; q0 += qblock) {
+    const uint32_t n_mem = scan.block(q0, qblock);
+    if (int rc = scan.stage()) return rc;
+    scan.aim(0, n_mem);
+    HIP_TRY(screen_query_n2(b, scan.a, dqn2.p));
+    for (int upper = 0; upper < 2; upper++) {
+      float *out = (upper ? out_hi : out_lo) + q0 * b->n;
+      s.upper = upper;
+      const DenseScan::Launch fetch = [&] { // the slab's columns of every query's row, as the kernel wrote them
+        return hipMemcpy2DAsync(out + scan.a.slab_base, (size_t)b->n * 4, scan.a.scores, (size_t)scan.a.score_stride * 4,
+                                (size_t)scan.a.slab_n * 4, n_mem, hipMemcpyDeviceToHost, b->stream);
+      };
+      bool stopped;
+      if (int rc = scan.slabs(sc, &stopped, fetch)) return rc;
+      HIP_TRY(hipStreamSynchronize(b->stream));
+    }
+  }
+  return HNY_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -692,6 +692,34 @@ hipError_t hnyk_exact_scores(const GraphDev &g, const ExactArgs &a, LaunchShape 
 hipError_t hnyk_exact_topk(const GraphDev &g, const ExactArgs &a, hipStream_t st);
 // a.tile_mask for the slab a.slab_base / a.slab_n from the members' masks (a.filter_of must be set)
 hipError_t hnyk_exact_tile_masks(const ExactArgs &a, hipStream_t st);
+// Screened exact k-NN (hny_builder_exact_knn_screened; hny_screen.hip).  k_screen_scores is a second
+// producer of the slab's score buffer: per (query, slot) pair an f32 MFMA dot product and from it one end of an
+// interval that holds the distance k_exact_scores would write; k_screen_collect is the consumer of the lower ends
+#define HNY_SCREEN_QT 64u        // queries per tile: two 32 x 32 accumulator blocks per wave
+#define HNY_SCREEN_KP 32u        // 16-byte units of every query row per K panel in LDS (128 floats)
+#define HNY_SCREEN_CAP 4095u     // candidates per query (HNY_RESCORE_MAX); lists are HNY_SCREEN_CAP + 1 entries apart
+#define HNY_SCREEN_TOP 0x7FC00000u // the largest distance key there is: the NaN every NaN distance leaves as
+struct ScreenArgs {
+  const float *row_n2; // [n] f32 sum of squares of every stored row (hnyk_screen_n2)
+  const float *q_n2;   // [nq] the same of the block's queries
+  int upper;           // 1: write d_hi, 0: write d_lo
+  // the constants of the bounds, rounded up on the host; K = 4 * n16, the padded dimensions
+  float c_dot;   // |dot~ - acc| <= c_dot * |q| |r| + ...            (Cosine)
+  float c_l2;    // |S~ - S| <= c_l2 * (|q|^2 + |r|^2) + ...          (Euclidean)
+  float c_sum;   // the exact chain of squares: acc = S (1 +- c_sum) +- a_abs
+  float c_n2;    // |x|^2 <= n2 * c_n2 + a_n2 (c_n2 = 1 + the relative error of the f32 sum of squares)
+  float a_abs;   // (3 K + 8) 2^-126: operations whose result may have been flushed
+  float a_n2;    // K 2^-126
+  float a_flush; // sqrt(K) 2^-126: operands the matrix core may have flushed, per unit of |q| + |r|
+};
+hipError_t hnyk_screen_scores(const GraphDev &g, const ExactArgs &a, const ScreenArgs &s, hipStream_t st);
+// out[i] = sum of squares of row idx[i] (null: row i) of n rows `stride` bytes apart, n16 units each
+hipError_t hnyk_screen_n2(const unsigned char *rows, u32 stride, u32 n16, const u32 *idx, u32 n, float *out,
+                          hipStream_t st);
+// One wave per query: the slots of the slab under a.mask whose score (d_lo) is at most the query's threshold, the
+// a.k-th key of its a.lists row, appended to cand[q][cnt[q] ..) in slot order as item ids (item_ids null: slots).
+// cnt keeps counting past HNY_SCREEN_CAP: such a query has overflowed
+hipError_t hnyk_screen_collect(const ExactArgs &a, const u32 *item_ids, u32 *cand, u32 *cnt, hipStream_t st);
 // exact range search (hny_builder_exact_range; hny_range.hip): the consumers of a slab of
 // k_exact_scores' scores that are not a top-k list.  One wave per query of the block
 struct RangeArgs {

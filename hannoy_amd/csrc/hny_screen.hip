@@ -1,0 +1,257 @@
+// hny_screen.hip — gfx950 kernels of the screened exact k-NN (hny_builder_exact_knn_screened).
+//
+// k_screen_scores is a producer of DenseScan's score buffer next to k_exact_scores: for a tile of HNY_SCREEN_QT
+// queries and a chunk of HNY_EXACT_CHUNK consecutive slots it computes dot~ = q . r on the matrix cores
+// (v_mfma_f32_32x32x2_f32) and writes, per pair, ONE end of an interval that holds the distance k_exact_scores would
+// write for the pair: the upper end in pass 1 (a.upper), the lower end in pass 2.  k_exact_topk (unchanged) turns the
+// upper ends into a threshold per query, k_screen_collect lists the slots whose lower end is at or below it, and
+// k_rescore (unchanged) settles each list on the f32 rows with dist_rows: the answer carries the index's own bits.
+//
+// Work split.  256 threads, four waves; wave w of a pass owns 32 consecutive rows, all four share the tile's queries.
+// Lane l of a wave stands for row (l & 31) as the B operand and for queries (l & 31) and 32 + (l & 31) as the A
+// operands; its half h = l >> 5 is the k index of the 32x32x2 instruction.  A lane fetches ONE 16-byte unit of its row
+// per step, unit 2 s + h, straight from HBM into registers, and the same unit of its two queries from LDS; the four
+// components feed four MFMAs per accumulator block.  Step s thus covers the eight dimensions 8 s .. 8 s + 7 in the
+// order (0, 4), (1, 5), (2, 6), (3, 7): a permutation of k that both operands share.  Rows take no LDS round trip.
+// The queries' K dimension goes through LDS in panels of HNY_SCREEN_KP units (33 KB with the padding that spreads
+// the queries over the banks), so the tile is 64 queries whatever the row length; a row that fits one panel is
+// staged once per workgroup.  Accumulators: 2 blocks x 16 registers.
+// Zero fill, never a read: units at and beyond n16, rows at and beyond the chunk's end, queries beyond the tile's.
+// The bytes between the last dimension and the end of its unit are zero in the stored rows (load_row reads them too).
+#include "hny_internal.h"
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+__device__ __forceinline__ u32 fbits(float f) { return __float_as_uint(f); }
+__device__ __forceinline__ u64 ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+
+// finalize_f32 of hny_kernels.hip for Cosine past its test of pnqn = qn * rn > 1.1920929e-07f, restated operation for
+// operation (cosine.rs:40-56); `acc` is finite here
+__device__ __forceinline__ float finalize_cosine(float acc, float pnqn) {
+  float c = acc / pnqn;
+  if (c < -1.0f) c = -1.0f;
+  if (c > 1.0f) c = 1.0f;
+  return (1.0f - c) / 2.0f;
+}
+
+// at least two f32 below / above x (x finite): the rounding of the operation that made x and of the one that takes
+// it, outwards
+__device__ __forceinline__ float nudge(float x) { return __builtin_fmaxf(__builtin_fabsf(x) * 0x1p-22f, 0x1p-126f); }
+__device__ __forceinline__ float below(float x) { return x - nudge(x); }
+__device__ __forceinline__ float above(float x) { return x + nudge(x); }
+
+#define HNY_SCREEN_SLOP 1.00000095367431640625f // 1 + 2^-20: the roundings of a bound's own evaluation
+#define HNY_SCREEN_PSTRIDE (HNY_SCREEN_KP + 1u) // float4 per query of a panel: one unit of padding
+#define HNY_SCREEN_BIG 0x1p126f                 // a bound at or beyond it (or a NaN) makes the pair uncertain
+
+// an upper bound on |x| from the f32 sum of squares of x
+__device__ __forceinline__ float norm_up(float n2up) { return __builtin_sqrtf(n2up) * 1.0000002384185791015625f; }
+
+// (no-packed-fp32-ops, as k_rescore: every f32 operation of the kernels below is emitted on its own, never paired into
+// v_pk_*_f32 — the same bits, and none of them waits on the VALU)
+#ifdef __HIP_DEVICE_COMPILE__
+#define HNY_NO_PACKED_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define HNY_NO_PACKED_F32 // (the host pass knows no such feature)
+#endif
+template <bool L2>
+__global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_screen_scores(GraphDev g, ExactArgs a, ScreenArgs s) {
+  __shared__ float4 qpan[HNY_SCREEN_QT * HNY_SCREEN_PSTRIDE];
+  __shared__ float s_qn[HNY_SCREEN_QT], s_q2[HNY_SCREEN_QT], s_q2up[HNY_SCREEN_QT], s_qnorm[HNY_SCREEN_QT];
+  const u32 tid = threadIdx.x;
+  const u32 q0 = blockIdx.x * HNY_SCREEN_QT;
+  const u32 nqt = a.nq - q0 < HNY_SCREEN_QT ? a.nq - q0 : HNY_SCREEN_QT;
+  const u32 slab_end = a.slab_base + a.slab_n;
+  const u32 c0 = a.slab_base + blockIdx.y * HNY_EXACT_CHUNK;
+  const u32 c1 = slab_end - c0 < HNY_EXACT_CHUNK ? slab_end : c0 + HNY_EXACT_CHUNK;
+  const u32 n16 = g.n16;
+  if (tid < HNY_SCREEN_QT) {
+    float qn = 0.f, q2 = 0.f;
+    if (tid < nqt) {
+      q2 = s.q_n2[q0 + tid];
+      if (a.q_slots) {
+        if (g.norms) qn = g.norms[a.q_slots[q0 + tid]];
+      } else if (a.q_norms) {
+        qn = a.q_norms[q0 + tid];
+      }
+    }
+    const float q2up = q2 * s.c_n2 + s.a_n2;
+    s_qn[tid] = qn;
+    s_q2[tid] = q2;
+    s_q2up[tid] = q2up;
+    s_qnorm[tid] = norm_up(q2up);
+  }
+  const u32 ln = tid & 63u, wave = tid >> 6, j = ln & 31u, h = ln >> 5;
+  const bool one_panel = n16 <= HNY_SCREEN_KP;
+  for (u32 p0 = c0; p0 < c1; p0 += 128u) { // the same trips for every wave: the panels are staged between barriers
+    const u32 row = p0 + wave * 32u + j;
+    const bool valid = row < c1;
+    const unsigned char *rp = g.rows + (size_t)(valid ? row : c0) * g.row_stride;
+    f32x16 acc0, acc1;
+#pragma unroll
+    for (int i = 0; i < 16; i++) acc0[i] = 0.f, acc1[i] = 0.f;
+    for (u32 u0 = 0; u0 < n16; u0 += HNY_SCREEN_KP) {
+      if (!one_panel || p0 == c0) {
+        __syncthreads(); // the panel before is read
+        for (u32 i = tid; i < HNY_SCREEN_QT * HNY_SCREEN_KP; i += 256u) {
+          const u32 qi = i / HNY_SCREEN_KP, f = i % HNY_SCREEN_KP, u = u0 + f;
+          float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (qi < nqt && u < n16) {
+            const unsigned char *src = a.q_slots ? g.rows + (size_t)a.q_slots[q0 + qi] * g.row_stride
+                                                 : a.q_rows + (size_t)(q0 + qi) * a.q_stride;
+            v = *reinterpret_cast<const float4 *>(src + (size_t)u * 16);
+          }
+          qpan[qi * HNY_SCREEN_PSTRIDE + f] = v;
+        }
+        __syncthreads();
+      }
+      const u32 units = n16 - u0 < HNY_SCREEN_KP ? n16 - u0 : HNY_SCREEN_KP;
+      const u32 steps = (units + 1u) / 2u;
+      for (u32 st = 0; st < steps; st++) {
+        const u32 f = 2u * st + h, u = u0 + f; // f < HNY_SCREEN_KP: staged, zero from n16 on
+        float4 rv = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (valid && u < n16) rv = *reinterpret_cast<const float4 *>(rp + (size_t)u * 16);
+        const float4 qa = qpan[j * HNY_SCREEN_PSTRIDE + f], qb = qpan[(32u + j) * HNY_SCREEN_PSTRIDE + f];
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(qa.x, rv.x, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(qb.x, rv.x, acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(qa.y, rv.y, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(qb.y, rv.y, acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(qa.z, rv.z, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(qb.z, rv.z, acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(qa.w, rv.w, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(qb.w, rv.w, acc1, 0, 0, 0);
+      }
+    }
+    // ---- the lane's row against its 2 x 16 queries: accumulator register i of a block is query
+    // 8 (i / 4) + 4 h + (i % 4) of the block, column = the lane's row
+    if (valid) {
+      const float rn = g.norms ? g.norms[row] : 0.f;
+      const float r2 = s.row_n2[row];
+      const float r2up = r2 * s.c_n2 + s.a_n2;
+      const float nr = norm_up(r2up);
+      const float top = __uint_as_float(HNY_SCREEN_TOP);
+#pragma unroll
+      for (int blk = 0; blk < 2; blk++) {
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+          const u32 qi = (u32)(blk * 32 + 8 * (i / 4) + (i % 4)) + 4u * h;
+          if (qi >= nqt) continue;
+          const float dot = blk ? acc1[i] : acc0[i];
+          const float nq = s_qnorm[qi];
+          const float flush = s.a_flush * (nq + nr) * HNY_SCREEN_SLOP;
+          float d;
+          if constexpr (!L2) {
+            const float eps = s.c_dot * (nq * nr) * HNY_SCREEN_SLOP + s.a_abs + flush;
+            if (!(eps < HNY_SCREEN_BIG) || !(__builtin_fabsf(dot) < HNY_SCREEN_BIG)) {
+              d = s.upper ? top : 0.f;
+            } else {
+              // the finaliser's steps are monotone: acc in [dot - eps, dot + eps] gives d in [f(dot + eps), f(dot - eps)].
+              // The nudge covers the sum's and the quotient's rounding, the last step outwards that of 1 - c
+              const float pnqn = s_qn[qi] * rn;
+              if (!(pnqn > 1.1920929e-07f)) {
+                d = 0.f; // the exact kernel's own branch: both ends are its value
+              } else if (s.upper) {
+                d = above(finalize_cosine(below(dot - eps), pnqn));
+              } else {
+                d = below(finalize_cosine(above(dot + eps), pnqn));
+                d = d > 0.f ? d : 0.f;
+              }
+            }
+          } else {
+            const float e = s.c_l2 * (s_q2up[qi] + r2up) * HNY_SCREEN_SLOP + 4.f * s.a_abs + 2.f * flush;
+            if (!(e < HNY_SCREEN_BIG) || !(__builtin_fabsf(dot) < HNY_SCREEN_BIG)) {
+              d = s.upper ? top : 0.f;
+            } else {
+              const float sq = (s_q2[qi] + r2) - 2.f * dot;
+              if (s.upper) {
+                d = above(above(sq + e) * (1.f + s.c_sum) + s.a_abs);
+                if (!(d < __builtin_inff())) d = top;
+              } else {
+                float lo = below(sq - e);
+                lo = lo > 0.f ? lo : 0.f;
+                d = below(lo * (1.f - s.c_sum) - s.a_abs);
+                d = d > 0.f ? d : 0.f;
+              }
+            }
+          }
+          a.scores[(size_t)(q0 + qi) * a.score_stride + (row - a.slab_base)] = d;
+        }
+      }
+    }
+  }
+}
+
+// Eight lanes per row: lane t takes the units t, t + 8, ..., one fma chain, then three butterfly steps.  At most
+// 4 * n16 / 8 + 7 roundings of half an ulp on a sum of non-negative terms
+__global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_screen_n2(const unsigned char *rows, u32 stride, u32 n16, const u32 *idx, u32 n,
+                                                   float *out) {
+  const u64 gid = (u64)blockIdx.x * 256u + threadIdx.x;
+  const u64 row = gid >> 3;
+  const u32 t = (u32)(gid & 7u);
+  float acc = 0.f;
+  if (row < n) {
+    const unsigned char *p = rows + (size_t)(idx ? idx[row] : (u32)row) * stride;
+    for (u32 u = t; u < n16; u += 8u) {
+      const float4 v = *reinterpret_cast<const float4 *>(p + (size_t)u * 16);
+      acc = __builtin_fmaf(v.x, v.x, acc);
+      acc = __builtin_fmaf(v.y, v.y, acc);
+      acc = __builtin_fmaf(v.z, v.z, acc);
+      acc = __builtin_fmaf(v.w, v.w, acc);
+    }
+  }
+  acc += __shfl_xor(acc, 4, 64);
+  acc += __shfl_xor(acc, 2, 64);
+  acc += __shfl_xor(acc, 1, 64);
+  if (row < n && t == 0) out[row] = acc;
+}
+
+// One wave per query.  No atomics: the wave owns its list, slabs follow each other on the stream, and within a slab
+// the places come from the ballot's prefix count, so a list is in slot order and the same from run to run
+__global__ __launch_bounds__(64) HNY_NO_PACKED_F32 void k_screen_collect(ExactArgs a, const u32 *item_ids, u32 *cand, u32 *cnt) {
+  const u32 qi = blockIdx.x, ln = threadIdx.x;
+  const float *sc = a.scores + (size_t)qi * a.score_stride;
+  const u32 thr = a.list_n[qi] >= a.k ? (u32)(a.lists[(size_t)qi * a.rcap + (a.k - 1u)] >> 32) : HNY_SCREEN_TOP;
+  u32 *list = cand + (size_t)qi * (HNY_SCREEN_CAP + 1u);
+  u32 c = cnt[qi];
+  for (u32 base = 0; base < a.slab_n; base += 64u) {
+    const u32 sl = base + ln;
+    bool in = false;
+    u32 slot = 0;
+    if (sl < a.slab_n) {
+      slot = a.slab_base + sl;
+      in = ((a.mask[slot >> 5] >> (slot & 31u)) & 1u) != 0u && fbits(sc[sl]) <= thr;
+    }
+    const u64 bal = ballot(in);
+    const u32 pos = c + (u32)__popcll(bal & ((1ull << ln) - 1ull));
+    if (in && pos < HNY_SCREEN_CAP) list[pos] = item_ids ? item_ids[slot] : slot;
+    c += (u32)__popcll(bal);
+  }
+  if (ln == 0) cnt[qi] = c;
+}
+
+} // namespace
+
+hipError_t hnyk_screen_scores(const GraphDev &g, const ExactArgs &a, const ScreenArgs &s, hipStream_t st) {
+  if (!a.nq || !a.slab_n) return hipSuccess;
+  if (g.metric != 0 && g.metric != 1) return hipErrorInvalidValue; // Cosine and Euclidean only: no silent other path
+  const dim3 grid((a.nq + HNY_SCREEN_QT - 1) / HNY_SCREEN_QT, (a.slab_n + HNY_EXACT_CHUNK - 1) / HNY_EXACT_CHUNK);
+  if (g.metric == 1) hipLaunchKernelGGL(k_screen_scores<true>, grid, dim3(256), 0, st, g, a, s);
+  else hipLaunchKernelGGL(k_screen_scores<false>, grid, dim3(256), 0, st, g, a, s);
+  return hipGetLastError();
+}
+
+hipError_t hnyk_screen_n2(const unsigned char *rows, u32 stride, u32 n16, const u32 *idx, u32 n, float *out,
+                          hipStream_t st) {
+  if (!n) return hipSuccess;
+  const u64 blocks = ((u64)n * 8u + 255u) / 256u;
+  hipLaunchKernelGGL(k_screen_n2, dim3((unsigned)blocks), dim3(256), 0, st, rows, stride, n16, idx, n, out);
+  return hipGetLastError();
+}
+
+hipError_t hnyk_screen_collect(const ExactArgs &a, const u32 *item_ids, u32 *cand, u32 *cnt, hipStream_t st) {
+  if (!a.nq || !a.slab_n) return hipSuccess;
+  hipLaunchKernelGGL(k_screen_collect, dim3(a.nq), dim3(64), 0, st, a, item_ids, cand, cnt);
+  return hipGetLastError();
+}

@@ -386,6 +386,49 @@ int hny_builder_exact_knn_f32(hny_builder *b, const hny_query_opts *opts, uint64
                               const float *queries, size_t qstride, uint32_t *out_ids,
                               float *out_dists, uint32_t *out_counts);
 
+/* ---- exact k-NN through the matrix cores.  Opt-in: nothing else calls it.
+ *
+ * Definition: hny_builder_exact_knn_screened returns, byte for byte (ids, distance bits, counts, did_cancel), what
+ * hny_builder_exact_knn returns on the same builder, queries and options, and refuses what it refuses, with the same
+ * codes, decided in the same order before any device work.
+ *
+ * Method, for Cosine and Euclidean builders in wave order: an f32 MFMA scan writes, per (query, slot) pair, an
+ * interval [d_lo, d_hi] that holds the distance of hny_builder_exact_knn; the k-th smallest d_hi of a query is a
+ * threshold no smaller than its k-th exact distance; the slots with d_lo at or below it, at most 4 095 per query, are
+ * ranked on the f32 rows by the kernel of hny_builder_rescore.  Every other case runs hny_builder_exact_knn itself for
+ * the queries concerned ("routed"): Manhattan and the four bit metrics, strict-mode builders, candidates so few
+ * that hny_builder_exact_knn gathers them, and a query with more than 4 095 slots under its threshold.
+ *
+ * The first screened call on a builder makes one f32 per slot (the row's sum of squares), kept until
+ * hny_builder_destroy. */
+int hny_builder_exact_knn_screened(hny_builder *b, const hny_query_opts *opts, uint64_t n_queries,
+                                   const void *qvectors, size_t qstride, const void *qheaders,
+                                   const uint32_t *query_items, uint32_t *out_ids, float *out_dists,
+                                   uint32_t *out_counts);
+/* by_vector with f32 queries, encoded on the device like hny_builder_exact_knn_f32's */
+int hny_builder_exact_knn_screened_f32(hny_builder *b, const hny_query_opts *opts, uint64_t n_queries,
+                                       const float *queries, size_t qstride, uint32_t *out_ids,
+                                       float *out_dists, uint32_t *out_counts);
+/* The last screened call on b: queries answered through the screen, queries routed to hny_builder_exact_knn, and the
+ * total of the screened queries' candidate list lengths.  Any output may be NULL.  b == NULL: HNY_ERR_INVALID_ARG */
+int hny_builder_exact_screen_stats(const hny_builder *b, uint64_t *n_screened, uint64_t *n_routed,
+                                   uint64_t *n_candidates);
+/* Device milliseconds of the last screened call on a profiling builder (hny_builder_set_profiling), out_ms[5]: the
+ * d_hi scan, k_exact_topk, the d_lo scan, the collection of the lists, the settling.  Zeros without profiling */
+int hny_builder_exact_screen_times(const hny_builder *b, double *out_ms);
+/* The slots of a builder: its items and, in an incremental or updated builder, the deleted ones and every other id
+ * its previous graph names.  The rows of hny_builder_exact_screen_bounds have this many entries.  b == NULL: 0 */
+uint64_t hny_builder_n_slots(const hny_builder *b);
+/* The two interval matrices [n_queries][n_slots] as the scan writes them, for by_vector queries in the builder's
+ * codec: out_lo[i * n_slots + s] <= the distance of query i and slot s <= out_hi[i * n_slots + s], compared as
+ * distance bits (a pair whose bound arithmetic overflowed or met a NaN has lo = 0 and hi = the NaN 0x7FC00000, the
+ * largest distance key).  Every slot has an interval, deleted ones included; n_slots is what the caller sized the
+ * outputs for and must be hny_builder_n_slots(b).  What hny_selftest_lane_ops is to the lane primitives.
+ * NULL arguments or another n_slots: HNY_ERR_INVALID_ARG; a builder the screen does not serve (see above), or
+ * n_queries x n_slots above 2^24: HNY_ERR_UNSUPPORTED; qstride below the codec's bytes: HNY_ERR_INVALID_DIM. */
+int hny_builder_exact_screen_bounds(hny_builder *b, uint64_t n_queries, const void *qvectors, size_t qstride,
+                                    const void *qheaders, uint64_t n_slots, float *out_lo, float *out_hi);
+
 /* ---- batched search with one `.candidates()` filter per query: the reference's filter belongs to one query
  * (src/reader.rs:200-203), so a batch that serves several requests carries several.
  *
