@@ -56,6 +56,7 @@ EXPORTED = [
     "hny_builder_rescore", "hny_builder_rescore_f32", "hny_builder_nns_rescored", "hny_builder_nns_rescored_f32",
     "hny_builder_exact_knn_screened", "hny_builder_exact_knn_screened_f32", "hny_builder_exact_screen_stats",
     "hny_builder_exact_screen_times", "hny_builder_exact_screen_bounds", "hny_builder_n_slots",
+    "hny_builder_check_graph",
 ]
 ERR_IO = -9
 NNS_NONE = 0xFFFFFFFF  # by_item: the reference returns None
@@ -165,6 +166,32 @@ class RangeOpts(C.Structure):
     def __init__(self, *a, **kw):
         super().__init__(*a, **kw)
         self.struct_size = C.sizeof(RangeOpts)
+
+
+CHECK_LISTS, CHECK_REACH, CHECK_LAYERS = 1, 2, 15
+
+
+class CheckOpts(C.Structure):
+    """hny_check_opts; struct_size is the guard (the struct is not part of hny_abi_sizes)"""
+    _fields_ = [("struct_size", C.c_uint32), ("what", C.c_uint32), ("max_rounds", C.c_uint64),
+                ("out_unreachable", C.c_void_p), ("cap_unreachable", C.c_uint64), ("out_degree_hist0", C.c_void_p),
+                ("cancel", CANCEL_FN), ("cancel_ctx", C.c_void_p)]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_size = C.sizeof(CheckOpts)
+
+
+class GraphReport(C.Structure):
+    """hny_graph_report: struct_size is set by the library"""
+    _per_layer = C.c_uint64 * CHECK_LAYERS
+    _fields_ = [("struct_size", C.c_uint32), ("max_level", C.c_uint32), ("n_entry_points", C.c_uint32),
+                ("n_dead_entry_points", C.c_uint32), ("n_slots", C.c_uint64), ("n_live", C.c_uint64),
+                ("n_nodes", _per_layer), ("n_links", _per_layer), ("n_empty_lists", _per_layer),
+                ("n_reached", _per_layer), ("max_degree", C.c_uint32 * CHECK_LAYERS),
+                ("n_dead_links", C.c_uint64), ("n_self_links", C.c_uint64), ("n_level_links", C.c_uint64),
+                ("n_no_inlinks0", C.c_uint64), ("n_unreachable", C.c_uint64), ("n_unreachable_written", C.c_uint64),
+                ("bfs_rounds", C.c_uint64), ("complete", C.c_int32), ("did_cancel", C.c_int32)]
 
 
 class RangeResult(C.Structure):
@@ -520,6 +547,8 @@ def load_library():
     L.hny_builder_finish_delta_encoded.argtypes = [vp, C.POINTER(C.POINTER(EncodedDeltaStruct))]
     L.hny_encoded_delta_free.restype = None
     L.hny_encoded_delta_free.argtypes = [C.POINTER(EncodedDeltaStruct)]
+    L.hny_builder_check_graph.restype = C.c_int
+    L.hny_builder_check_graph.argtypes = [vp, C.POINTER(CheckOpts), C.POINTER(GraphReport)]
     L.hny_abi_sizes.restype = C.c_uint32
     L.hny_abi_sizes.argtypes = [C.POINTER(C.c_uint32), C.c_uint32]
     _check_abi(L)
@@ -1498,6 +1527,31 @@ class Builder:
         gp = C.POINTER(GraphStruct)()
         _check(load_library().hny_builder_finish(self._h, C.byref(gp)))
         return Graph(gp, self.opts, self.items)
+
+    def check_graph(self, lists=True, reach=True, max_rounds=0, max_unreachable=0, degree_hist=False, cancel=None):
+        """hny_builder_check_graph: the report's fields as a dict (per-layer fields as lists of CHECK_LAYERS entries),
+        plus "unreachable" (item ids, ascending, at most max_unreachable) and, with degree_hist, "degree_hist0".
+        Both passes go out as what = 0, the header's word for both; neither is a ValueError, not a silent both."""
+        if not (lists or reach):
+            raise ValueError("check_graph: neither the list pass nor the reachability pass was asked for")
+        o, r = CheckOpts(), GraphReport()
+        o.what = 0 if lists and reach else CHECK_LISTS if lists else CHECK_REACH
+        o.max_rounds = max_rounds
+        unr = np.zeros(max_unreachable, np.uint32)
+        if max_unreachable:
+            o.out_unreachable, o.cap_unreachable = unr.ctypes.data, max_unreachable
+        hist = np.zeros(self.opts.M0 + 1, np.uint64) if degree_hist else None
+        if degree_hist:
+            o.out_degree_hist0 = hist.ctypes.data
+        if cancel is not None:
+            o.cancel = CANCEL_FN(lambda _ctx: int(bool(cancel())))
+        _check(load_library().hny_builder_check_graph(self._h, C.byref(o), C.byref(r)))
+        out = {name: (list(v) if hasattr(v, "__len__") else v)
+               for name, v in ((f[0], getattr(r, f[0])) for f in GraphReport._fields_)}
+        out["unreachable"] = unr[:r.n_unreachable_written]
+        if degree_hist:
+            out["degree_hist0"] = hist
+        return out
 
     def finish_encoded(self):
         """hny_builder_finish_encoded: the Links records with their values serialised on the device"""

@@ -226,6 +226,11 @@ class Writer:
             self._rb.close()
             self._rb = None
 
+    def check(self, **kw):
+        """the resident builder's graph checked on the device (Builder.check_graph), e.g. after a chain of updates;
+        None for a Writer that holds no builder"""
+        return None if self._rb is None else self._rb.check_graph(**kw)
+
     def _drop_fine(self):
         if self._rb_fine is not None:
             self._rb_fine.close()
@@ -981,6 +986,11 @@ class Reader:
         assert set(g.nbrs.tolist()) <= items, "links to items that are not in the database"
         assert items == set(g.rec_item.tolist()), "each item should have one or more Links records"
         assert set(np.asarray(self.meta["entry_points"]).tolist()) <= items
+
+    def check(self, **kw):
+        """the loaded graph checked on the device (Builder.check_graph: links, degrees, reachability); no list comes
+        back to the host, which makes it the check for a reader opened with encoded_links=True"""
+        return self._b.check_graph(**kw)
 
     def by_vec(self, query, n=10, ef_search=200):
         q = np.asarray(query, np.float32)

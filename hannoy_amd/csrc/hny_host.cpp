@@ -6419,6 +6419,185 @@ void hny_range_result_free(hny_range_result *r) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// graph check (include/hannoy_amd.h)
+// ---------------------------------------------------------------------------------------------
+// The lists the searches walk on a builder at rest: a loaded graph's stored lists, else the builder's own finalised
+// ones (an incremental builder's fill_gaps rewrote every surviving record there, which is what finish() exports)
+static CheckGraphArgs check_graph_args(const hny_builder *b) {
+  const GraphDev g = search_graph(b);
+  CheckGraphArgs a{};
+  a.l0_ids = b->load_only ? g.d0_ids : g.l0_ids;
+  a.up_ids = b->load_only ? g.du_ids : g.up_ids;
+  a.upper_idx = g.upper_idx;
+  a.level = g.level;
+  a.has_vec = b->incremental ? g.has_vec : nullptr;
+  a.n = b->n, a.M = g.M, a.M0 = g.M0, a.up_layers = b->up_layers, a.n_upper = b->n_upper;
+  a.words = (u32)(((uint64_t)b->n + 63) / 64 * 2);
+  a.eps = b->d_eps.p;
+  a.n_eps = (u32)b->entry_points.size();
+  a.top_layer = b->n_upper ? std::min<uint32_t>(b->up_layers, HNY_MAX_LEVEL) : 0;
+  return a;
+}
+
+// The reachability pass: from max_level down, the closure of every layer in groups of HNY_CHECK_ROUNDS rounds.  The
+// host reads a group's frontier lengths in one pinned copy; it never needs one to launch a round.
+static int check_reach(hny_builder *b, const hny_check_opts *o, CheckGraphArgs &a, u32 *front[2], u32 *h_len,
+                       hny_graph_report &r, bool &began0) {
+  hipStream_t st = b->stream;
+  u32 *const len = a.wrd + CKW_LEN;
+  auto stopped = [&]() { // before a group is enqueued
+    if (o->cancel && o->cancel(o->cancel_ctx)) r.did_cancel = 1;
+    return r.did_cancel || (o->max_rounds && r.bfs_rounds >= o->max_rounds);
+  };
+  for (u32 layer = b->max_level + 1; layer-- > 0;) {
+    a.layer = layer;
+    if (stopped()) return HNY_OK;
+    // the frontier of the layer's first round: R of the layer above and the layer's own seeds
+    HIP_TRY(hnyk_bfs_lens(a, 0, st));
+    HIP_TRY(hnyk_bfs_seed(a, st));
+    a.front_out = front[0], a.len_out = len;
+    HIP_TRY(hnyk_bfs_frontier(a, st));
+    began0 = layer == 0;
+    for (bool first = true;; first = false) {
+      if (!first) {
+        if (stopped()) return HNY_OK;
+        HIP_TRY(hnyk_bfs_lens(a, 1, st));
+      }
+      const uint64_t left = o->max_rounds ? o->max_rounds - r.bfs_rounds : HNY_CHECK_ROUNDS;
+      const u32 rounds = (u32)std::min<uint64_t>(left, HNY_CHECK_ROUNDS);
+      for (u32 i = 0; i < rounds; i++) {
+        a.front_in = front[i & 1], a.front_out = front[(i + 1) & 1];
+        a.len_in = len + i, a.len_out = len + i + 1;
+        HIP_TRY(hnyk_bfs_expand(a, st));
+      }
+      HIP_TRY(hipMemcpyAsync(h_len, len, (HNY_CHECK_ROUNDS + 1) * 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      // every frontier is what its round claimed (the first: all of R so far), so the lengths add up to |R_layer|
+      if (first) r.n_reached[layer] = h_len[0];
+      for (u32 i = 0; i < rounds; i++) {
+        r.bfs_rounds += h_len[i] != 0;
+        r.n_reached[layer] += h_len[i + 1];
+      }
+      if (h_len[rounds] == 0) break; // the layer is closed
+      if (rounds < HNY_CHECK_ROUNDS) return HNY_OK; // max_rounds ran out on a frontier that is not empty
+      // (HNY_CHECK_ROUNDS is even: the next group's first frontier lies in front[0] again)
+    }
+  }
+  r.complete = 1;
+  return HNY_OK;
+}
+
+int hny_builder_check_graph(hny_builder *b, const hny_check_opts *o, hny_graph_report *out) {
+  if (!b || !o || !out) return fail(HNY_ERR_INVALID_ARG, "null argument");
+  if (o->struct_size != sizeof(hny_check_opts))
+    return fail(HNY_ERR_INVALID_ARG, "hny_check_opts.struct_size %u: this library has %zu", o->struct_size,
+                sizeof(hny_check_opts));
+  if (!o->out_unreachable && o->cap_unreachable) return fail(HNY_ERR_INVALID_ARG, "cap_unreachable without out_unreachable");
+  if (o->what & ~(uint32_t)(HNY_CHECK_LISTS | HNY_CHECK_REACH)) return fail(HNY_ERR_INVALID_ARG, "what %u: unknown bits", o->what);
+  if (int rc = check_build_finished(b)) return rc;
+  if (b->in_batch || b->apply_open) return fail(HNY_ERR_INVALID_ARG, "the builder has a batch pending");
+  if (b->incremental && !b->load_only && !b->gaps_done)
+    return fail(HNY_ERR_INVALID_ARG, "hny_builder_fill_gaps has not run on the incremental builder");
+  const bool lists = !o->what || (o->what & HNY_CHECK_LISTS), reach = !o->what || (o->what & HNY_CHECK_REACH);
+  hny_graph_report r{};
+  r.struct_size = (uint32_t)sizeof(hny_graph_report);
+  r.max_level = b->max_level;
+  r.n_entry_points = (uint32_t)b->entry_points.size();
+  r.n_slots = b->n;
+  r.complete = 1;
+  if (!b->n) {
+    *out = r;
+    return HNY_OK;
+  }
+  HIP_TRY(hipSetDevice(b->device));
+  hipStream_t st = b->stream;
+  if (int rc = ensure_finalized(b, st)) return rc;
+  const u32 *item_ids = nullptr;
+  if (int rc = ensure_item_ids(b, &item_ids)) return rc;
+  // the workspace of this call: three bitsets over slots, the two frontiers, the counters, the unreachable ids
+  CheckGraphArgs a = check_graph_args(b);
+  DevBuf<u32> d_bits, d_wrd, d_hist, d_unr;
+  DevBuf<u64> d_ctr;
+  PinnedBuf<u64> h_ctr;
+  PinnedBuf<u32> h_wrd;
+  HIP_TRY(d_bits.alloc((size_t)3 * a.words));
+  HIP_TRY(d_wrd.alloc(CKW_COUNT));
+  HIP_TRY(d_ctr.alloc(CK_COUNT));
+  HIP_TRY(h_ctr.alloc(CK_COUNT));
+  HIP_TRY(h_wrd.alloc(CKW_BLOCK));
+  HIP_TRY(hipMemsetAsync(d_bits.p, 0, (size_t)3 * a.words * 4, st));
+  HIP_TRY(hipMemsetAsync(d_wrd.p, 0, CKW_COUNT * 4, st));
+  HIP_TRY(hipMemsetAsync(d_ctr.p, 0, CK_COUNT * 8, st));
+  a.live = d_bits.p, a.inlink = d_bits.p + a.words, a.visited = d_bits.p + 2 * (size_t)a.words;
+  a.ctr = d_ctr.p, a.wrd = d_wrd.p;
+  // (a pass's count of x & ~y, read once the stream has been synchronised)
+  auto fetch_counters = [&]() -> int {
+    HIP_TRY(hipMemcpyAsync(h_ctr.p, d_ctr.p, CK_COUNT * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_wrd.p, d_wrd.p, CKW_BLOCK * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return HNY_OK;
+  };
+  HIP_TRY(hnyk_check_live(a, st));
+  if (lists) {
+    if (o->out_degree_hist0) {
+      HIP_TRY(d_hist.alloc((size_t)a.M0 + 1));
+      HIP_TRY(hipMemsetAsync(d_hist.p, 0, ((size_t)a.M0 + 1) * 4, st));
+      a.hist = d_hist.p;
+    }
+    HIP_TRY(hnyk_check_lists(a, st));
+    HIP_TRY(hnyk_check_bits_count(a, a.live, a.inlink, st));
+  }
+  if (int rc = fetch_counters()) return rc;
+  r.n_live = h_ctr.p[CK_LIVE];
+  if (!r.n_live) { // no live item: an all-zero report
+    r = hny_graph_report{};
+    r.struct_size = (uint32_t)sizeof(hny_graph_report);
+    r.complete = 1;
+    *out = r;
+    return HNY_OK;
+  }
+  if (lists) {
+    for (u32 l = 0; l < HNY_CHECK_LAYERS; l++) {
+      r.n_nodes[l] = h_ctr.p[CK_NODES + l], r.n_links[l] = h_ctr.p[CK_LINKS + l];
+      r.n_empty_lists[l] = h_ctr.p[CK_EMPTY + l], r.max_degree[l] = h_wrd.p[CKW_MAXDEG + l];
+    }
+    r.n_dead_links = h_ctr.p[CK_DEAD], r.n_self_links = h_ctr.p[CK_SELF], r.n_level_links = h_ctr.p[CK_LEVEL];
+    r.n_dead_entry_points = (uint32_t)h_ctr.p[CK_DEAD_EPS];
+    r.n_no_inlinks0 = h_ctr.p[CK_BITS];
+    if (o->out_degree_hist0) {
+      std::vector<u32> hist((size_t)a.M0 + 1);
+      HIP_TRY(hipMemcpy(hist.data(), d_hist.p, hist.size() * 4, hipMemcpyDeviceToHost));
+      for (size_t c = 0; c < hist.size(); c++) o->out_degree_hist0[c] = hist[c];
+    }
+  }
+  if (reach) {
+    r.complete = 0;
+    DevBuf<u32> d_front;
+    HIP_TRY(d_front.alloc((size_t)2 * a.n));
+    u32 *front[2] = {d_front.p, d_front.p + a.n};
+    bool began0 = false;
+    if (int rc = check_reach(b, o, a, front, h_wrd.p + CKW_LEN, r, began0)) return rc;
+    // the live slots outside R_0 (as far as the rounds got; stopped above layer 0, R_0 is still empty): their count,
+    // and the first cap_unreachable item ids
+    if (!began0) HIP_TRY(hipMemsetAsync(a.visited, 0, (size_t)a.words * 4, st));
+    HIP_TRY(hipMemsetAsync(d_ctr.p + CK_BITS, 0, 8, st));
+    HIP_TRY(hnyk_check_bits_count(a, a.live, a.visited, st));
+    const uint64_t cap = std::min<uint64_t>(o->cap_unreachable, a.n);
+    if (cap) {
+      HIP_TRY(d_unr.alloc(cap));
+      HIP_TRY(hnyk_check_bits_list(a, a.live, a.visited, item_ids, d_unr.p, cap, st));
+    }
+    if (int rc = fetch_counters()) return rc;
+    r.n_unreachable = h_ctr.p[CK_BITS];
+    r.n_unreachable_written = std::min<uint64_t>(r.n_unreachable, cap);
+    if (r.n_unreachable_written)
+      HIP_TRY(hipMemcpy(o->out_unreachable, d_unr.p, r.n_unreachable_written * 4, hipMemcpyDeviceToHost));
+  }
+  *out = r;
+  return HNY_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // on-disk records
 // ---------------------------------------------------------------------------------------------
 static void put_key(uint16_t index, uint8_t mode, uint32_t item, uint8_t layer, uint8_t k[8]) {

@@ -597,6 +597,11 @@ HNY_LDS_FN DecodeLinksLds decode_links_lds(LdsCarve &c, u32 stage_bytes, u32 rec
   L.bad = c.take<u32>(2);
   return L;
 }
+// k_check_lists (hny_check.hip): the workgroup's layer-0 degree histogram
+struct CheckListsLds {
+  u32 *hist; // [bins] live nodes per layer-0 list length, bins = M0 + 1 (0: no histogram asked for)
+};
+HNY_LDS_FN CheckListsLds check_lists_lds(LdsCarve &c, u32 bins) { return CheckListsLds{c.take<u32>(bins)}; }
 // bytes of a layout: HNY_LDS_BYTES(prune_lds, rcap, capmax) runs the function on a null cursor
 #define HNY_LDS_BYTES(layout, ...) ([&] { LdsCarve c_; (void)layout(c_, __VA_ARGS__); return c_.bytes(); }())
 
@@ -926,3 +931,57 @@ struct DeltaTableArgs {
 };
 hipError_t hnyk_delta_table_count(const DeltaTableArgs &a, hipStream_t st);
 hipError_t hnyk_delta_table_write(const DeltaTableArgs &a, hipStream_t st);
+
+// ---- graph check (hny_check.hip): list statistics and reachability of a resident graph ----
+#define HNY_CHECK_GRID 1024u    // workgroups of 256 threads of every kernel of the check; the rest is a grid stride
+#define HNY_CHECK_ROUNDS 8u     // expansions enqueued between two reads of the frontier lengths
+enum { // u64 counters of the check: three per layer, then the ones over all layers
+  CK_NODES = 0, CK_LINKS = 15, CK_EMPTY = 30, CK_DEAD = 45, CK_SELF, CK_LEVEL, CK_DEAD_EPS, CK_LIVE, CK_BITS, CK_COUNT
+};
+enum { // u32 words of the check: the longest list per layer, then the frontier lengths of a group of rounds
+  CKW_MAXDEG = 0, CKW_LEN = 16, CKW_BLOCK = 32, CKW_COUNT = CKW_BLOCK + HNY_CHECK_GRID
+};
+struct CheckGraphArgs {
+  // the lists hny_builder_nns walks on this builder (ascending or stored order, HNY_SENT beyond the count), the way
+  // EncodeLinksArgs names them: layer 0 at l0_ids + slot * M0, layer l >= 1 at up_ids + (upper_idx[slot] * up_layers +
+  // l - 1) * M
+  const u32 *l0_ids, *up_ids;
+  const int *upper_idx;
+  const unsigned char *level;     // [n]
+  const unsigned char *has_vec;   // [n] or null: every slot holds a row
+  u32 n, M, M0, up_layers, n_upper;
+  u32 words;                      // of every bitset: two per 64 slots
+  u32 *live;                      // bit s = slot s is live (k_check_live writes every word)
+  const u32 *eps;                 // entry points as slots
+  u32 n_eps;
+  u64 *ctr;                       // [CK_COUNT]
+  u32 *wrd;                       // [CKW_COUNT]
+  // k_check_lists
+  u32 top_layer;                  // layers 0 .. top_layer have nodes
+  u32 *inlink;                    // bit s = a live node's layer-0 list names the live slot s
+  u32 *hist;                      // [M0 + 1] or null
+  // k_bfs_*
+  u32 layer;
+  u32 *visited;
+  const u32 *front_in;            // [n] the frontier being expanded, *len_in entries
+  u32 *front_out;                 // [n] the slots this round claimed, *len_out entries
+  const u32 *len_in;
+  u32 *len_out;
+  u32 lg0, lgu;                   // set by the launchers: log2 of the lanes per list on layer 0 / above (3 .. 6)
+};
+hipError_t hnyk_check_live(const CheckGraphArgs &a, hipStream_t st);
+hipError_t hnyk_check_lists(const CheckGraphArgs &a, hipStream_t st);
+// ctr[CK_BITS] += popcount(x & ~y) (y null: popcount(x)); wrd[CKW_BLOCK + b]: the share of block b's range of words
+hipError_t hnyk_check_bits_count(const CheckGraphArgs &a, const u32 *x, const u32 *y, hipStream_t st);
+// after hnyk_check_bits_count of the same x, y: the set slots ascending as item ids (item_ids null: the slots), the
+// first `cap` of them
+hipError_t hnyk_check_bits_list(const CheckGraphArgs &a, const u32 *x, const u32 *y, const u32 *item_ids, u32 *out,
+                                u64 cap, hipStream_t st);
+// the live entry points of level >= a.layer join `visited`
+hipError_t hnyk_bfs_seed(const CheckGraphArgs &a, hipStream_t st);
+// every slot of `visited` -> front_out, *len_out (zero before) counts them
+hipError_t hnyk_bfs_frontier(const CheckGraphArgs &a, hipStream_t st);
+// one round: the unvisited nodes of a.layer the frontier's lists name are claimed and form front_out
+hipError_t hnyk_bfs_expand(const CheckGraphArgs &a, hipStream_t st);
+// the frontier lengths wrd[CKW_LEN ..] for the next group of rounds: carry = 0: all zero; 1: [0] = [HNY_CHECK_ROUNDS]
+hipError_t hnyk_bfs_lens(const CheckGraphArgs &a, int carry, hipStream_t st);

@@ -982,6 +982,68 @@ int hny_lmdb_scan(const hny_lmdb_env *e, const uint8_t *lo, size_t lo_len, const
 int hny_lmdb_read_links(const hny_lmdb_env *e, uint16_t index, hny_encoded_links **out);
 void hny_lmdb_close(hny_lmdb_env *e);
 
+/* ---- graph check: is the graph a builder holds sound — what Reader::assert_validity (reader.rs:905-948) and the
+ * reference's all_items_are_reachable test (src/tests/reader.rs:82-98) ask, answered on the device, where the lists
+ * are, for a builder that has lived through a chain of hny_builder_update calls or was opened by
+ * hny_builder_load_encoded and whose neighbour ids the host never saw.  DESIGN.md §3j.
+ *
+ * Builders served: the ones hny_builder_nns serves — a finished build, a loaded graph, an incremental builder or a
+ * successor after hny_builder_fill_gaps.  Lists checked: the ones the searches walk on that builder once it is at rest
+ * — a loaded builder's stored lists, any other builder's own finalised lists (what hny_builder_finish exports).
+ * Live slot: a slot with a vector (every slot of a fresh builder; of any other, the slots of its items).  Node of
+ * layer L: a live slot whose level is at least L.  n_slots == hny_builder_n_slots(b).
+ *
+ * List pass (HNY_CHECK_LISTS).  Per layer L: n_nodes[L] the nodes of L, n_links[L] the entries of their lists on L,
+ * n_empty_lists[L] the nodes of L whose list on L has no entry, max_degree[L] the longest list on L.  Over all layers:
+ * n_dead_links entries that name a slot that is not live; n_self_links entries that name the list's own node;
+ * n_level_links entries on a layer L >= 1 that name a live slot of level below L; n_no_inlinks0 live slots that no
+ * live node's layer-0 list names (a self link names its node); n_dead_entry_points entry points that are not live
+ * slots; out_degree_hist0[c] the live nodes whose layer-0 list has c entries.  Reader::assert_validity holds exactly
+ * when n_dead_links == 0, n_dead_entry_points == 0 and n_nodes[0] == n_live.
+ *
+ * Reachability pass (HNY_CHECK_REACH).  A link of layer L is followed only if its target is a node of L; every live
+ * entry point is a seed on every layer up to its own level.  R_L is the closure of the seeds of L and R_{L+1}
+ * (R_{max_level+1} is empty) under the followed links of L, computed from max_level down to 0, one frontier expansion
+ * ("round") at a time.  n_reached[L] = |R_L|, n_unreachable = n_live - n_reached[0]; out_unreachable receives the
+ * item ids (not slots) of the live slots outside R_0, ascending, the first cap_unreachable of them
+ * (n_unreachable_written).  bfs_rounds: the expansions that had a non-empty frontier, over all layers; the first
+ * frontier of a layer is all of R_{L+1} and the layer's seeds.  max_rounds and cancel are looked at before a layer is
+ * started and between groups of eight rounds (max_rounds exactly: no round beyond it is run).  When max_rounds has run
+ * out before the last layer was closed, or cancel returned non-zero, complete = 0 (did_cancel = 1 for cancel) and
+ * n_reached, n_unreachable and out_unreachable describe what was reached so far — a layer that was not started has
+ * n_reached 0; the call still returns HNY_OK.  The list pass is one bounded kernel and always runs whole.
+ * Fields of a pass that was not asked for are zero, and complete is 1.  No live item: an all-zero report, complete 1.
+ *
+ * Decided before any device work, *out untouched, in this order: b, opts or out NULL, or a wrong opts->struct_size;
+ * out_unreachable == NULL with cap_unreachable > 0; bits in `what` other than the two defined; a builder whose build
+ * has not finished (batches pending, or an incremental builder before hny_builder_fill_gaps): HNY_ERR_INVALID_ARG
+ * each.  The workspace (three bitsets over slots, two frontiers of n_slots ids) lives for the call only. */
+#define HNY_CHECK_LISTS 1u
+#define HNY_CHECK_REACH 2u
+typedef struct {
+  uint32_t struct_size;        /* own size; not part of hny_abi_sizes */
+  uint32_t what;               /* HNY_CHECK_LISTS = 1, HNY_CHECK_REACH = 2; 0 = both */
+  uint64_t max_rounds;         /* BFS rounds over all layers together; 0 = no cap other than n_live per layer */
+  uint32_t *out_unreachable;   /* optional: item ids of live items not reached on layer 0, ascending */
+  uint64_t cap_unreachable;    /* entries the caller sized it for; the first cap of them are written */
+  uint64_t *out_degree_hist0;  /* optional, M0 + 1 entries: live nodes per layer-0 list length */
+  int (*cancel)(void *); void *cancel_ctx;
+} hny_check_opts;
+
+#define HNY_CHECK_LAYERS 15
+typedef struct {
+  uint32_t struct_size, max_level, n_entry_points, n_dead_entry_points;
+  uint64_t n_slots, n_live;
+  uint64_t n_nodes[HNY_CHECK_LAYERS], n_links[HNY_CHECK_LAYERS], n_empty_lists[HNY_CHECK_LAYERS],
+           n_reached[HNY_CHECK_LAYERS];
+  uint32_t max_degree[HNY_CHECK_LAYERS];
+  uint64_t n_dead_links, n_self_links, n_level_links, n_no_inlinks0;
+  uint64_t n_unreachable, n_unreachable_written, bfs_rounds;
+  int32_t complete, did_cancel;
+} hny_graph_report;
+
+int hny_builder_check_graph(hny_builder *b, const hny_check_opts *opts, hny_graph_report *out);
+
 const char *hny_last_error(void);
 const char *hny_version(void);
 
