@@ -57,6 +57,9 @@ EXPORTED = [
     "hny_builder_exact_knn_screened", "hny_builder_exact_knn_screened_f32", "hny_builder_exact_screen_stats",
     "hny_builder_exact_screen_times", "hny_builder_exact_screen_bounds", "hny_builder_n_slots",
     "hny_builder_check_graph",
+    "hny_builder_exact_range_screened", "hny_builder_exact_range_screened_f32",
+    "hny_builder_exact_range_count_screened", "hny_builder_exact_range_count_screened_f32",
+    "hny_builder_exact_range_screen_stats", "hny_builder_exact_range_screen_times",
 ]
 ERR_IO = -9
 NNS_NONE = 0xFFFFFFFF  # by_item: the reference returns None
@@ -500,6 +503,15 @@ def load_library():
     L.hny_builder_exact_range_count.argtypes = [vp, C.POINTER(RangeOpts), C.c_uint64, vp, C.c_size_t, vp, vp, vp]
     L.hny_builder_exact_range_count_f32.restype = C.c_int
     L.hny_builder_exact_range_count_f32.argtypes = [vp, C.POINTER(RangeOpts), C.c_uint64, vp, C.c_size_t, vp]
+    for count in ("", "_count"):
+        for f32 in ("", "_f32"):
+            fn = getattr(L, f"hny_builder_exact_range{count}_screened{f32}")
+            fn.restype = C.c_int
+            fn.argtypes = getattr(L, f"hny_builder_exact_range{count}{f32}").argtypes
+    L.hny_builder_exact_range_screen_stats.restype = C.c_int
+    L.hny_builder_exact_range_screen_stats.argtypes = [vp, vp, vp, vp, vp]
+    L.hny_builder_exact_range_screen_times.restype = C.c_int
+    L.hny_builder_exact_range_screen_times.argtypes = [vp, vp]
     for kind, struct in (("filtered", QueryFilters), ("bitsets", QueryBitsets)):
         for count in ("", "_count"):
             plain = "hny_builder_exact_range" + count
@@ -1782,7 +1794,7 @@ class Builder:
         return int(load_library().hny_builder_n_slots(self._h))
 
     def _range(self, radius, count_only, qcodes, qheaders, candidates, query_items, cancel, qf32, max_total,
-               filters=None):
+               filters=None, screened=False):
         """One call of hny_builder_exact_range in the form the arguments name; `filters`: ("filtered" | "bitsets",
         QueryFilters.pack's / QueryBitsets.pack's result) for the calls with a filter per query"""
         (nq, qc, qs, qh, qi), _arrays = _query_source(query_items, qf32, qcodes, qheaders)
@@ -1792,7 +1804,8 @@ class Builder:
         self._cancel_flag = flag
         L = load_library()
         name = ("hny_builder_exact_range" + ("_count" if count_only else "") +
-                ("" if filters is None else "_" + filters[0]) + ("_f32" if qf32 is not None else ""))
+                ("" if filters is None else "_" + filters[0]) + ("_screened" if screened else "") +
+                ("_f32" if qf32 is not None else ""))
         head = (self._h, C.byref(ro)) + (() if filters is None else (C.byref(filters[1][0]),))
         src = (nq, qc, qs) if qf32 is not None else (nq, qc, qs, qh, qi)
         if count_only:
@@ -1815,22 +1828,39 @@ class Builder:
         return offsets, ids, dists, is_none
 
     def exact_range(self, radius, qcodes=None, qheaders=None, candidates=None, query_items=None, cancel=None,
-                    qf32=None, max_total=0):
+                    qf32=None, max_total=0, screened=False):
         """hny_builder_exact_range: every live item (or every one of `candidates` among them) whose distance to query
         i is <= radius[i] (a scalar holds for every query), ordered by (distance bits, item id).  Returns (offsets
         [nq + 1], ids, dists, is_none): the hits of query i are ids / dists[offsets[i]:offsets[i + 1]]; is_none is 1
-        where by_item names an unknown item.  max_total != 0: more hits than that in all are refused."""
-        return self._range(radius, False, qcodes, qheaders, candidates, query_items, cancel, qf32, max_total)
+        where by_item names an unknown item.  max_total != 0: more hits than that in all are refused.
+        screened: hny_builder_exact_range_screened, the same result through the matrix cores
+        (exact_range_screen_stats)."""
+        return self._range(radius, False, qcodes, qheaders, candidates, query_items, cancel, qf32, max_total,
+                           screened=screened)
 
     def exact_range_f32(self, queries, radius, **kw):
         """exact_range(by_vector) with f32 queries, encoded on the device"""
         return self.exact_range(radius, qf32=_f32_rows(queries), **kw)
 
     def exact_range_count(self, radius, qcodes=None, qheaders=None, candidates=None, query_items=None, cancel=None,
-                          qf32=None):
+                          qf32=None, screened=False):
         """hny_builder_exact_range_count: the sizes of exact_range's rows alone (uint64), RANGE_NONE where by_item
-        names an unknown item; one scan, nothing is emitted or sorted"""
-        return self._range(radius, True, qcodes, qheaders, candidates, query_items, cancel, qf32, 0)
+        names an unknown item; one scan, nothing is emitted or sorted.  screened: as in exact_range"""
+        return self._range(radius, True, qcodes, qheaders, candidates, query_items, cancel, qf32, 0, screened=screened)
+
+    def exact_range_screen_stats(self):
+        """hny_builder_exact_range_screen_stats of the last exact_range / exact_range_count(screened=True):
+        (n_screened, n_routed, n_certain, n_settled)"""
+        out = [C.c_uint64(0) for _ in range(4)]
+        _check(load_library().hny_builder_exact_range_screen_stats(self._h, *map(C.byref, out)))
+        return tuple(int(v.value) for v in out)
+
+    def exact_range_screen_times(self):
+        """hny_builder_exact_range_screen_times: device ms of the last screened range call on a profiling builder, as
+        (scans, settling)"""
+        out = np.zeros(2, np.float64)
+        _check(load_library().hny_builder_exact_range_screen_times(self._h, _p(out)))
+        return tuple(float(v) for v in out)
 
     def exact_range_count_f32(self, queries, radius, **kw):
         """exact_range_count(by_vector) with f32 queries, encoded on the device"""

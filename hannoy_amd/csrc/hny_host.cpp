@@ -475,6 +475,9 @@ struct hny_builder {
   DevBuf<float> d_row_n2;
   uint64_t screen_screened = 0, screen_routed = 0, screen_candidates = 0;
   double screen_ms[5] = {0, 0, 0, 0, 0}; // profiling: d_hi scan, k_exact_topk, d_lo scan, collect, settle
+  // hny_builder_exact_range_screened: what hny_builder_exact_range_screen_stats reports
+  uint64_t rscreen_screened = 0, rscreen_routed = 0, rscreen_certain = 0, rscreen_settled = 0;
+  double rscreen_ms[2] = {0, 0}; // profiling: k_screen_range, k_range_settle
   // successor builders whose source was profiling: device time (HIP events) and bytes read + written of k_move_rows
   double t_move_rows_s = 0;
   uint64_t move_rows_bytes = 0;
@@ -4201,10 +4204,12 @@ struct DenseScan {
   Launch produce; // the slab's scores by another producer than k_exact_scores (k_screen_scores); null = k_exact_scores
 
   DenseScan(hny_builder *b, const QuerySet &q, RangeArgs *r = nullptr) : b(b), q(q), r(r), st{b, q}, q_end(q.nq) {}
-  int alloc(uint32_t qblock, const u32 *mask) { // blocks of at most qblock queries; mask: C over slots, on the device
+  // blocks of at most qblock queries; mask: C over slots, on the device; scores: false where the producer and the
+  // consumer pass something else than scores between them (the screened range search's bitmaps)
+  int alloc(uint32_t qblock, const u32 *mask, bool scores = true) {
     const uint32_t sstride = (std::min<uint32_t>(b->n, HNY_EXACT_SLAB) + 63u) & ~63u;
     if (int rc = st.alloc(qblock)) return rc;
-    HIP_TRY(dscores.alloc((size_t)qblock * sstride));
+    if (scores) HIP_TRY(dscores.alloc((size_t)qblock * sstride));
     a.q_stride = b->g.row_stride;
     a.qt = hnyk_exact_qt(b->g.row_stride);
     a.scores = dscores.p;
@@ -5505,6 +5510,7 @@ static hipError_t screen_query_n2(hny_builder *b, const ExactArgs &a, float *out
 // device time per kind of launch, for a profiling builder (hny_builder_set_profiling): event pairs around the launches
 struct ScreenClock {
   hny_builder *b;
+  double *ms = nullptr; // the sums by kind; null: b->screen_ms
   struct Span {
     hipEvent_t e0, e1;
     int kind;
@@ -5528,8 +5534,8 @@ struct ScreenClock {
   }
   void add_up() { // the stream is idle
     for (auto &s : spans) {
-      float ms = 0.f;
-      if (hipEventElapsedTime(&ms, s.e0, s.e1) == hipSuccess) b->screen_ms[s.kind] += ms;
+      float t = 0.f;
+      if (hipEventElapsedTime(&t, s.e0, s.e1) == hipSuccess) (ms ? ms : b->screen_ms)[s.kind] += t;
     }
     drop();
   }
@@ -5924,8 +5930,26 @@ struct RangeResult {
   }
 };
 
+// The screened form of the two passes (hny_builder_exact_range_screened).  DenseScan's producer is
+// k_screen_range, which leaves two bits per pair of the slab where k_exact_scores leaves a score, and the consumer
+// of both passes is k_range_settle: pass 1 counts the certain pairs and settles the ambiguous ones, pass 2 settles
+// every candidate of a run and emits the kept ones as k_range_emit would.  Memory: 2 x 8 KB of bitmap per query of a
+// block (16 MB at HNY_EXACT_QBLOCK), whatever the number of slots; the pairs to settle never leave the LDS
+struct RangeScreen {
+  ScreenArgs s{};
+  ScreenRangeArgs bits{};
+  RangeSettleArgs t{};
+  DevBuf<u32> dcand, dcertain;
+  DevBuf<float> dqn2;
+  DevBuf<u64> dtally; // per query aimed at: certain pairs, settled pairs
+  std::vector<u64> htally;
+  ScreenClock clock;
+  explicit RangeScreen(hny_builder *b) : clock{b, b->rscreen_ms} {}
+};
+
 // What the passes of range_impl share and what pass 2 adds.  Of `r`, count, keys, seg and cursor are set here
 struct RangeScan {
+  std::unique_ptr<RangeScreen> scr; // null: k_exact_scores, k_range_count and k_range_emit
   const float *radius; // the caller's, one per query
   RangeArgs r{};
   DenseScan scan;
@@ -5998,6 +6022,10 @@ static int range_stage_block(RangeScan &R) {
 static int range_aim(RangeScan &R, uint32_t m0, uint32_t m1) {
   DenseScan &scan = R.scan;
   scan.aim(m0, m1, R.dradius.p);
+  if (R.scr) { // the screen's sums of squares of these members, their tallies at zero
+    HIP_TRY(screen_query_n2(scan.b, scan.a, R.scr->dqn2.p));
+    HIP_TRY(hipMemsetAsync(R.scr->dtally.p, 0, (size_t)(m1 - m0) * 16, scan.b->stream));
+  }
   if (R.fof.empty()) return HNY_OK;
   R.tiles = R.skip && exact_tiles_sparse(R.hfof.data() + m0, m1 - m0, scan.a.qt, scan.b->n, [&](uint32_t j) {
               return R.fcount[scan.query_of(m0 + j)];
@@ -6010,6 +6038,60 @@ static int range_slabs(RangeScan &R, bool *stopped, const DenseScan::Launch &con
   const DenseScan::Launch tile_masks = [&R] { return hnyk_exact_tile_masks(R.scan.a, R.scan.b->stream); };
   return R.scan.slabs(R.sc, stopped, consume, R.tiles ? tile_masks : nullptr);
 }
+// ---- the screened form's steps (R.scr set) ----
+// the bitmaps, the row sums of squares and k_screen_range as the scan's producer
+static int range_screen_begin(RangeScan &R) {
+  hny_builder *b = R.scan.b;
+  RangeScreen &S = *R.scr;
+  if (int rc = ensure_row_n2(b)) return rc;
+  HIP_TRY(S.dcand.alloc((size_t)R.qblock * HNY_SCREEN_BITS_STRIDE));
+  HIP_TRY(S.dcertain.alloc((size_t)R.qblock * HNY_SCREEN_BITS_STRIDE));
+  HIP_TRY(S.dqn2.alloc(R.qblock));
+  HIP_TRY(S.dtally.alloc((size_t)R.qblock * 2));
+  S.htally.resize((size_t)R.qblock * 2);
+  screen_consts(b->g.n16, S.s);
+  S.s.row_n2 = b->d_row_n2.p;
+  S.s.q_n2 = S.dqn2.p;
+  S.t.cand = S.bits.cand = S.dcand.p;
+  S.t.certain = S.bits.certain = S.dcertain.p;
+  S.t.tally = S.dtally.p;
+  R.scan.produce = [&R, &S, b] {
+    S.bits.radius = R.r.radius;
+    return S.clock.run(0, [&] { return hnyk_screen_range(b->g, R.scan.a, S.s, S.bits, b->stream); });
+  };
+  return HNY_OK;
+}
+// the consumer of a slab's bitmaps for the members aimed at: pass 1 (emit = 0) or a run of pass 2
+static hipError_t range_settle(RangeScan &R, int emit) {
+  hny_builder *b = R.scan.b;
+  RangeScreen &S = *R.scr;
+  const ExactArgs &a = R.scan.a;
+  RangeSettleArgs &t = S.t;
+  t.q_slots = a.q_slots, t.q_rows = a.q_rows, t.q_norms = a.q_norms, t.q_stride = a.q_stride, t.nq = a.nq;
+  t.slab_base = a.slab_base, t.slab_n = a.slab_n;
+  t.mask = a.mask, t.radius = R.r.radius;
+  t.count = R.r.count, t.keys = R.r.keys, t.seg = R.r.seg, t.cursor = R.r.cursor;
+  t.emit = emit;
+  return S.clock.run(1, [&] { return hnyk_range_settle(b->g, t, b->shape, b->stream); });
+}
+// the tallies of the members aimed at: fetched before the pass's wait, added up after it.  `counted`: pass 1, which
+// answers the queries and is the one that counts certain pairs
+static hipError_t range_screen_fetch(RangeScan &R) {
+  if (!R.scr) return hipSuccess;
+  return hipMemcpyAsync(R.scr->htally.data(), R.scr->dtally.p, (size_t)R.scan.a.nq * 16, hipMemcpyDeviceToHost,
+                        R.scan.b->stream);
+}
+static void range_screen_add(RangeScan &R, bool counted) {
+  if (!R.scr) return;
+  hny_builder *b = R.scan.b;
+  for (uint32_t j = 0; j < R.scan.a.nq; j++) {
+    if (counted) b->rscreen_certain += R.scr->htally[2 * j];
+    b->rscreen_settled += R.scr->htally[2 * j + 1];
+  }
+  if (counted) b->rscreen_screened += R.scan.a.nq;
+  R.scr->clock.add_up();
+}
+
 // the device's side of what both passes share
 static int range_scan_begin(RangeScan &R, const std::vector<u32> &mask, const hny_query_opts *qo) {
   hny_builder *b = R.scan.b;
@@ -6017,7 +6099,9 @@ static int range_scan_begin(RangeScan &R, const std::vector<u32> &mask, const hn
   HIP_TRY(R.sc.init(qo));
   HIP_TRY(R.dmask.alloc(mask.size()));
   HIP_TRY(hipMemcpyAsync(R.dmask.p, mask.data(), mask.size() * 4, hipMemcpyHostToDevice, b->stream));
-  if (int rc = R.scan.alloc(R.qblock, R.dmask.p)) return rc;
+  if (R.scr)
+    if (int rc = range_screen_begin(R)) return rc;
+  if (int rc = R.scan.alloc(R.qblock, R.dmask.p, !R.scr)) return rc; // (the screened form has no score buffer)
   HIP_TRY(R.dradius.alloc(R.qblock));
   HIP_TRY(R.dcount.alloc(R.qblock));
   R.r.count = R.dcount.p;
@@ -6037,11 +6121,14 @@ static int range_count_blocks(RangeScan &R, uint64_t lo, uint64_t hi) {
     if (int rc = range_aim(R, 0, n_mem)) return rc;
     HIP_TRY(hipMemsetAsync(R.dcount.p, 0, (size_t)n_mem * 8, b->stream));
     bool stopped;
-    if (int rc = range_slabs(R, &stopped, [&R, b] { return hnyk_range_count(R.r, b->stream); })) return rc;
+    const DenseScan::Launch count = [&R, b] { return R.scr ? range_settle(R, 0) : hnyk_range_count(R.r, b->stream); };
+    if (int rc = range_slabs(R, &stopped, count)) return rc;
     if ((R.dropped |= stopped)) continue; // the block did not finish: 0 hits each
     HIP_TRY(hipMemcpyAsync(R.hcount.data(), R.dcount.p, (size_t)n_mem * 8, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(range_screen_fetch(R));
     HIP_TRY(R.sc.wait(b));
     for (uint32_t j = 0; j < n_mem; j++) R.counts[R.scan.query_of(j)] = R.hcount[j];
+    range_screen_add(R, true);
   }
   return HNY_OK;
 }
@@ -6094,7 +6181,7 @@ static int range_emit_run(RangeScan &R, RangeResult &res, uint32_t m0, uint32_t 
   HIP_TRY(hipMemsetAsync(R.dcursor.p, 0, (size_t)nsub * 4, b->stream));
   if (int rc = range_aim(R, m0, m1)) return rc;
   R.r.keys = keys;
-  const int rc = range_slabs(R, stopped, [&R, b] { return hnyk_range_emit(R.r, b->stream); });
+  const int rc = range_slabs(R, stopped, [&R, b] { return R.scr ? range_settle(R, 1) : hnyk_range_emit(R.r, b->stream); });
   if (rc || *stopped) return rc;
   if ((*stopped = R.sc.probe())) {
     HIP_TRY(hipStreamSynchronize(b->stream));
@@ -6108,7 +6195,9 @@ static int range_emit_run(RangeScan &R, RangeResult &res, uint32_t m0, uint32_t 
   HIP_TRY(hipMemcpyAsync(res.ids + off, dids, (size_t)nh * 4, hipMemcpyDeviceToHost, b->stream));
   HIP_TRY(hipMemcpyAsync(res.dists + off, dbits, (size_t)nh * 4, hipMemcpyDeviceToHost, b->stream));
   HIP_TRY(hipMemcpyAsync(R.hcursor.data(), R.dcursor.p, (size_t)nsub * 4, hipMemcpyDeviceToHost, b->stream));
+  HIP_TRY(range_screen_fetch(R));
   HIP_TRY(R.sc.wait(b));
+  range_screen_add(R, false);
   for (uint32_t j = 0; j < nsub; j++) // the two passes voted alike
     if (R.hcursor[j] != R.hseg[j + 1] - R.hseg[j])
       return fail(HNY_ERR_DEVICE, "exact range search: query %llu emitted %u hits, counted %u",
@@ -6172,7 +6261,7 @@ static int range_emit_pass(RangeScan &R, RangeResult &res) {
 
 static int range_impl(hny_builder *b, const hny_range_opts *ro, uint64_t nq, const void *qvectors, size_t qstride,
                       const void *qheaders, const uint32_t *query_items, bool q_f32, uint64_t *out_counts,
-                      hny_range_result **out) {
+                      hny_range_result **out, bool screened = false) {
   uint32_t *const no = nullptr; // (the hits go to a RangeResult)
   QuerySet qs = q_f32 ? QuerySet::of_f32(b, nullptr, nq, (const float *)qvectors, qstride, no, nullptr, no)
                       : QuerySet::of(b, nullptr, nq, qvectors, qstride, qheaders, query_items, no, nullptr, no);
@@ -6180,6 +6269,10 @@ static int range_impl(hny_builder *b, const hny_range_opts *ro, uint64_t nq, con
   const hny_query_opts qo = range_query_opts(ro);
   RangeScan R{b, qs, ro->radius};
   if (!R.none32) return fail(HNY_ERR_OOM, "out of memory");
+  if (screened && screen_serves(b)) {
+    R.scr.reset(new (std::nothrow) RangeScreen(b));
+    if (!R.scr) return fail(HNY_ERR_OOM, "out of memory");
+  }
   qs.out_counts = R.none32.get();
   SlotCandidates C;
   const uint64_t n_c = qs.slot_mask(&qo, C.mask);
@@ -6225,6 +6318,62 @@ int hny_builder_exact_range_f32(hny_builder *b, const hny_range_opts *ro, uint64
                                 size_t qstride, hny_range_result **out) {
   if (!out || !queries) return fail(HNY_ERR_INVALID_ARG, !queries ? "no queries" : "bad argument");
   return range_impl(b, ro, nq, queries, qstride, nullptr, nullptr, true, nullptr, out);
+}
+
+// Screened exact range search: range_impl with RangeScreen where the screen serves the builder
+// (Cosine and Euclidean in wave order); every other builder takes range_impl as it is and its queries count as routed
+static int range_screened_impl(hny_builder *b, const hny_range_opts *ro, uint64_t nq, const void *qvectors, size_t qstride,
+                               const void *qheaders, const uint32_t *query_items, bool q_f32, uint64_t *out_counts,
+                               hny_range_result **out) {
+  if (b) {
+    b->rscreen_screened = b->rscreen_routed = b->rscreen_certain = b->rscreen_settled = 0;
+    b->rscreen_ms[0] = b->rscreen_ms[1] = 0;
+  }
+  const int rc = range_impl(b, ro, nq, qvectors, qstride, qheaders, query_items, q_f32, out_counts, out, true);
+  if (rc == HNY_OK && b && !screen_serves(b)) b->rscreen_routed = nq;
+  return rc;
+}
+
+int hny_builder_exact_range_count_screened(hny_builder *b, const hny_range_opts *ro, uint64_t nq, const void *qvectors,
+                                           size_t qstride, const void *qheaders, const uint32_t *query_items,
+                                           uint64_t *out_counts) {
+  if (!out_counts) return fail(HNY_ERR_INVALID_ARG, "bad argument");
+  return range_screened_impl(b, ro, nq, qvectors, qstride, qheaders, query_items, false, out_counts, nullptr);
+}
+
+int hny_builder_exact_range_screened(hny_builder *b, const hny_range_opts *ro, uint64_t nq, const void *qvectors,
+                                     size_t qstride, const void *qheaders, const uint32_t *query_items,
+                                     hny_range_result **out) {
+  if (!out) return fail(HNY_ERR_INVALID_ARG, "bad argument");
+  return range_screened_impl(b, ro, nq, qvectors, qstride, qheaders, query_items, false, nullptr, out);
+}
+
+int hny_builder_exact_range_count_screened_f32(hny_builder *b, const hny_range_opts *ro, uint64_t nq,
+                                               const float *queries, size_t qstride, uint64_t *out_counts) {
+  if (!out_counts || !queries) return fail(HNY_ERR_INVALID_ARG, !queries ? "no queries" : "bad argument");
+  return range_screened_impl(b, ro, nq, queries, qstride, nullptr, nullptr, true, out_counts, nullptr);
+}
+
+int hny_builder_exact_range_screened_f32(hny_builder *b, const hny_range_opts *ro, uint64_t nq, const float *queries,
+                                         size_t qstride, hny_range_result **out) {
+  if (!out || !queries) return fail(HNY_ERR_INVALID_ARG, !queries ? "no queries" : "bad argument");
+  return range_screened_impl(b, ro, nq, queries, qstride, nullptr, nullptr, true, nullptr, out);
+}
+
+int hny_builder_exact_range_screen_stats(const hny_builder *b, uint64_t *n_screened, uint64_t *n_routed,
+                                         uint64_t *n_certain, uint64_t *n_settled) {
+  if (!b) return fail(HNY_ERR_INVALID_ARG, "bad argument");
+  if (n_screened) *n_screened = b->rscreen_screened;
+  if (n_routed) *n_routed = b->rscreen_routed;
+  if (n_certain) *n_certain = b->rscreen_certain;
+  if (n_settled) *n_settled = b->rscreen_settled;
+  return HNY_OK;
+}
+
+int hny_builder_exact_range_screen_times(const hny_builder *b, double *out_ms) {
+  if (!b || !out_ms) return fail(HNY_ERR_INVALID_ARG, "bad argument");
+  out_ms[0] = b->rscreen_ms[0], out_ms[1] = b->rscreen_ms[1];
+  return HNY_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -462,6 +462,22 @@ HNY_LDS_FN RescoreLds rescore_lds(LdsCarve &c, u32 rcap) {
   L.ctl = c.take<u32>(8);
   return L;
 }
+// k_range_settle (one 256-thread workgroup per query): the slots of one trip over the query's hit bitmap, their
+// exact distances, and the words the waves exchange (ctl[0..4): a wave's set bits of the trip, ctl[4..8): its kept
+// pairs of a compaction round or its share of the final sums)
+#define HNY_SETTLE_WORDS 128u // bitmap words per trip: 4 096 slots at most
+struct RangeSettleLds {
+  u32 *slots; // [HNY_SETTLE_WORDS * 32]
+  float *d;   // [HNY_SETTLE_WORDS * 32]
+  u32 *ctl;   // [16]
+};
+HNY_LDS_FN RangeSettleLds range_settle_lds(LdsCarve &c) {
+  RangeSettleLds L;
+  L.slots = c.take<u32>(HNY_SETTLE_WORDS * 32u);
+  L.d = c.take<float>(HNY_SETTLE_WORDS * 32u);
+  L.ctl = c.take<u32>(16);
+  return L;
+}
 // k_exact_topk
 struct ExactTopkLds {
   u64 *res; // [rcap]
@@ -746,6 +762,40 @@ struct RangeArgs {
 };
 hipError_t hnyk_range_count(const RangeArgs &a, hipStream_t st);
 hipError_t hnyk_range_emit(const RangeArgs &a, hipStream_t st);
+// Screened exact range search (hny_builder_exact_range_screened).  k_screen_range (hny_screen.hip)
+// is k_screen_scores' scan with another epilogue: both ends of a pair's interval are compared with the query's radius
+// and the pair leaves two bits, in bitmaps over the slab's slots [query][HNY_SCREEN_BITS_STRIDE] (bit s & 31 of word
+// s >> 5 is slot slab_base + s).  cand: d_lo <= r, the pair may be a hit; certain: d_hi <= r, it is one.  Every word
+// below ceil(slab_n / 32) of every query of the block is written by exactly one wave; the mask is not applied here
+#define HNY_SCREEN_BITS_STRIDE (HNY_EXACT_SLAB / 32u)
+struct ScreenRangeArgs {
+  const float *radius; // [nq] of the queries aimed at
+  u32 *cand, *certain; // [nq][HNY_SCREEN_BITS_STRIDE]
+};
+hipError_t hnyk_screen_range(const GraphDev &g, const ExactArgs &a, const ScreenArgs &s, const ScreenRangeArgs &b,
+                             hipStream_t st);
+// k_range_settle (hny_kernels.hip, next to dist_rows): the consumer of a slab's bitmaps, one workgroup per query.
+// Under the mask it counts the certain pairs, lists the pairs to settle in slot order (emit == 0: cand & ~certain,
+// emit != 0: cand), computes their exact distances on the f32 rows and keeps those with d <= r.
+// emit == 0: count[q] += certain + kept.  emit != 0: the kept pairs as keys at keys[seg[q] + cursor[q] ..), as
+// k_range_emit leaves them.  tally[q] += {certain pairs, settled pairs}
+struct RangeSettleArgs {
+  const u32 *q_slots;          // the queries as in ExactArgs
+  const unsigned char *q_rows;
+  const float *q_norms;
+  u32 q_stride, nq;
+  u32 slab_base, slab_n;
+  const u32 *cand, *certain;   // k_screen_range's bitmaps of the slab
+  const u32 *mask;             // live items (∩ candidates) as a bitset over slots
+  const float *radius;         // [nq]
+  u64 *count;                  // [nq]
+  u64 *tally;                  // [nq][2]
+  int emit;
+  u64 *keys;
+  const u32 *seg;              // [nq + 1]
+  u32 *cursor;                 // [nq]
+};
+hipError_t hnyk_range_settle(const GraphDev &g, const RangeSettleArgs &a, LaunchShape s, hipStream_t st);
 // the n keys of n_seg segments seg[i] .. seg[i + 1], each segment ascending; `keys` and `other` are both scratch,
 // *sorted is the one that holds the result.  temp == nullptr: temp_bytes is set and nothing runs
 hipError_t hnyk_range_sort(void *temp, size_t &temp_bytes, u64 *keys, u64 *other, u32 n, u32 n_seg, const u32 *seg,

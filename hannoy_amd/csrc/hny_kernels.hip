@@ -2988,6 +2988,126 @@ __global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_rescore(GraphDev g, R
   if (tid == 0 && evals) atomicAdd(&g.stats[ST_EVALS_WALK], evals);
 }
 
+// Screened exact range search (hny_builder_exact_range_screened): the consumer of the two bitmaps
+// k_screen_range leaves per slab.  One workgroup of four waves owns a query for the whole slab, slabs follow each
+// other on the stream, so its counters and its cursor are plain loads and stores: no atomic, the same from run to run.
+// The query's words are taken in trips of HNY_SETTLE_WORDS, one word per thread of the waves 0 and 1:
+//   count   the certain pairs under the mask, by popcount (EMIT: not needed, every candidate is settled)
+//   expand  the pairs to settle (EMIT: cand, else cand & ~certain, under the mask) as slots in LDS, in slot order, at
+//           the prefix sums of the threads' popcounts: a list never leaves the LDS, a long one takes more trips
+//   settle  dist_rows on batches of 64 listed slots, the waves side by side: k_exact_scores' bits of the pair
+//   keep    d <= r as f32.  EMIT: the kept pairs become keys at the query's cursor, compacted in rounds of 256 as in
+//           k_rescore (slot order); else they are counted
+template <int LPR, int NCH, bool EMIT>
+__global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_range_settle(GraphDev g, RangeSettleArgs a) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  LdsCarve lds(smem);
+  const RangeSettleLds lay = range_settle_lds(lds);
+  u32 *slots = lay.slots, *ctl = lay.ctl;
+  float *sd = lay.d;
+  const u32 tid = threadIdx.x, wave = uni(tid >> 6), qi = blockIdx.x;
+  const int ln = HNY_LANE, t = ln % LPR;
+  const float r = a.radius[qi];
+  float qn = 0.f;
+  const unsigned char *qrow;
+  if (a.q_slots) {
+    const u32 qslot = uni(a.q_slots[qi]);
+    qrow = g.rows + (size_t)qslot * g.row_stride;
+    if (g.norms) qn = g.norms[qslot];
+  } else {
+    qrow = a.q_rows + (size_t)qi * a.q_stride;
+    if (a.q_norms) qn = a.q_norms[qi];
+  }
+  float4 q[NCH];
+  load_row<LPR, NCH>(qrow, t, g.n16, q);
+  const u32 *cw = a.cand + (size_t)qi * HNY_SCREEN_BITS_STRIDE, *hw = a.certain + (size_t)qi * HNY_SCREEN_BITS_STRIDE;
+  const u32 *mw = a.mask + (a.slab_base >> 5);
+  const u32 words = (a.slab_n + 31u) / 32u;
+  const u64 below = (1ull << ln) - 1ull;
+  u32 n_certain = 0, n_kept = 0, n_listed = 0; // the thread's share, summed at the end (a slab has 65 536 slots)
+  u32 at = 0, at0 = 0, end = 0;
+  if constexpr (EMIT) at = at0 = a.seg[qi] + a.cursor[qi], end = a.seg[qi + 1];
+  for (u32 w0 = 0; w0 < words; w0 += HNY_SETTLE_WORDS) {
+    const u32 w = w0 + tid;
+    u32 bits = 0;
+    if (tid < HNY_SETTLE_WORDS && w < words) {
+      const u32 m = mw[w];
+      bits = cw[w] & m;
+      if constexpr (!EMIT) {
+        const u32 c = hw[w] & m;
+        n_certain += (u32)__popc(c);
+        bits &= ~c;
+      }
+    }
+    // expand: the thread's place is the set bits of the threads before it
+    const u32 pc = (u32)__popc(bits);
+    u32 incl = pc;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const u32 y = __shfl_up(incl, d, 64);
+      if (ln >= d) incl += y;
+    }
+    if (ln == 63) ctl[wave] = incl;
+    __syncthreads();
+    const u32 cnt = uni(ctl[0] + ctl[1]);
+    u32 off = incl - pc + (wave == 1u ? ctl[0] : 0u);
+    for (u32 rest = bits; rest; rest &= rest - 1u) slots[off++] = a.slab_base + w * 32u + (u32)(__ffs(rest) - 1);
+    __syncthreads();
+    if (cnt == 0u) continue;
+    if (tid == 0) n_listed += cnt;
+    // settle: wave w takes the batches w, w + 4, ... of 64 listed slots
+    for (u32 base = wave * 64u; base < cnt; base += 256u) {
+      const int nc = (int)(cnt - base < 64u ? cnt - base : 64u);
+      dist_rows<LPR, NCH>(g, q, qn, slots + base, nc, sd + base, qrow);
+    }
+    __syncthreads();
+    if constexpr (!EMIT) {
+      for (u32 i = tid; i < cnt; i += 256u) n_kept += sd[i] <= r ? 1u : 0u;
+    } else {
+      for (u32 r0 = 0; r0 < cnt; r0 += 256u) {
+        const u32 i = r0 + tid;
+        const float d = i < cnt ? sd[i] : 0.f;
+        const bool keep = i < cnt && d <= r;
+        const u64 bal = ballot(keep);
+        if (ln == 0) ctl[4u + wave] = (u32)__popcll(bal);
+        __syncthreads();
+        u32 before = 0, total = 0;
+#pragma unroll
+        for (u32 v = 0; v < 4u; v++) {
+          const u32 c = ctl[4u + v];
+          total += c;
+          if (v < wave) before += c;
+        }
+        const u32 pos = at + before + (u32)__popcll(bal & below);
+        // (never beyond the segment unless the count pass disagrees: then the surplus is dropped, and the host sees
+        // the cursor beyond the count)
+        if (keep && pos < end) a.keys[pos] = ((u64)fbits(d) << 32) | (u64)slots[i];
+        at += total;
+        __syncthreads();
+      }
+    }
+  }
+  // the workgroup's sums: per wave by butterfly, then through ctl
+  __syncthreads();
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    n_certain += __shfl_xor(n_certain, d, 64);
+    n_kept += __shfl_xor(n_kept, d, 64);
+  }
+  if (ln == 0) ctl[8u + wave] = n_certain, ctl[12u + wave] = n_kept;
+  __syncthreads();
+  if (tid == 0) {
+    const u32 certain = ctl[8] + ctl[9] + ctl[10] + ctl[11], kept = ctl[12] + ctl[13] + ctl[14] + ctl[15];
+    if constexpr (EMIT) {
+      if (at != at0) a.cursor[qi] += at - at0;
+    } else if (certain + kept) {
+      a.count[qi] += (u64)certain + kept;
+    }
+    if (certain) a.tally[2u * qi] += certain;
+    if (n_listed) a.tally[2u * qi + 1u] += n_listed;
+  }
+}
+
 // Exact k-NN, dense scan (hny_builder_exact_knn).  k_nns_linear above fetches every candidate row
 // once per query; here a workgroup of four waves stages a tile of a.qt query rows in LDS and every wave reads its
 // share of a chunk of consecutive slots from HBM once for the whole tile.  Per (query, row) pair the work is
@@ -4860,6 +4980,15 @@ struct RescoreLauncher {
   }
 };
 template <int L, int C>
+struct RangeSettleLauncher {
+  static hipError_t run(const GraphDev &g, const RangeSettleArgs &a, hipStream_t st) {
+    LdsCarve c;
+    (void)range_settle_lds(c);
+    if (a.emit) return launch_with_lds(k_range_settle<L, C, true>, dim3(a.nq), dim3(256), c.bytes(), st, g, a);
+    return launch_with_lds(k_range_settle<L, C, false>, dim3(a.nq), dim3(256), c.bytes(), st, g, a);
+  }
+};
+template <int L, int C>
 struct ExactScoresLauncher {
   static hipError_t run(const GraphDev &g, const ExactArgs &a, hipStream_t st) {
     const size_t lds = HNY_LDS_BYTES(exact_scores_lds, a.qt, g.row_stride);
@@ -4958,6 +5087,11 @@ hipError_t hnyk_rescore(const GraphDev &g, const RescoreArgs &a, LaunchShape s, 
   if (!a.nq) return hipSuccess;
   if (a.rcap < 1u || a.rcap > HNY_RESCORE_MAX + 1u || (a.rcap & (a.rcap - 1u))) return hipErrorInvalidValue;
   return dispatch_shape<RescoreLauncher>(s, g, a, st);
+}
+hipError_t hnyk_range_settle(const GraphDev &g, const RangeSettleArgs &a, LaunchShape s, hipStream_t st) {
+  if (!a.nq || !a.slab_n) return hipSuccess;
+  if (a.slab_n > HNY_EXACT_SLAB || (a.slab_base & 31u)) return hipErrorInvalidValue; // the bitmaps' stride and words
+  return dispatch_shape<RangeSettleLauncher>(s, g, a, st);
 }
 hipError_t hnyk_exact_scores(const GraphDev &g, const ExactArgs &a, LaunchShape s, hipStream_t st) {
   if (!a.nq || !a.slab_n) return hipSuccess;

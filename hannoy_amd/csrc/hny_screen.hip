@@ -56,17 +56,61 @@ __device__ __forceinline__ float norm_up(float n2up) { return __builtin_sqrtf(n2
 #else
 #define HNY_NO_PACKED_F32 // (the host pass knows no such feature)
 #endif
+// ---- the interval of one pair, shared by k_screen_scores and k_screen_range.  m: Cosine pnqn = qn * rn as the exact
+// kernel forms it, Euclidean the f32 sum q2 + r2 of the two sums of squares
+// The error bound e of the pair's dot product; false: the pair is uncertain (an overflowed bound or dot product, a
+// NaN), its interval is [0, HNY_SCREEN_TOP]
 template <bool L2>
-__global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_screen_scores(GraphDev g, ExactArgs a, ScreenArgs s) {
-  __shared__ float4 qpan[HNY_SCREEN_QT * HNY_SCREEN_PSTRIDE];
-  __shared__ float s_qn[HNY_SCREEN_QT], s_q2[HNY_SCREEN_QT], s_q2up[HNY_SCREEN_QT], s_qnorm[HNY_SCREEN_QT];
-  const u32 tid = threadIdx.x;
-  const u32 q0 = blockIdx.x * HNY_SCREEN_QT;
-  const u32 nqt = a.nq - q0 < HNY_SCREEN_QT ? a.nq - q0 : HNY_SCREEN_QT;
-  const u32 slab_end = a.slab_base + a.slab_n;
-  const u32 c0 = a.slab_base + blockIdx.y * HNY_EXACT_CHUNK;
-  const u32 c1 = slab_end - c0 < HNY_EXACT_CHUNK ? slab_end : c0 + HNY_EXACT_CHUNK;
-  const u32 n16 = g.n16;
+__device__ __forceinline__ bool screen_err(const ScreenArgs &s, float dot, float nq, float nr, float q2up, float r2up,
+                                           float &e) {
+  const float flush = s.a_flush * (nq + nr) * HNY_SCREEN_SLOP;
+  if constexpr (!L2) e = s.c_dot * (nq * nr) * HNY_SCREEN_SLOP + s.a_abs + flush;
+  else e = s.c_l2 * (q2up + r2up) * HNY_SCREEN_SLOP + 4.f * s.a_abs + 2.f * flush;
+  return e < HNY_SCREEN_BIG && __builtin_fabsf(dot) < HNY_SCREEN_BIG;
+}
+// Cosine: the finaliser's steps are monotone: acc in [dot - e, dot + e] gives d in [f(dot + e), f(dot - e)].  The
+// nudge covers the sum's and the quotient's rounding, the last step outwards that of 1 - c.  pnqn at or below the
+// exact kernel's test is its own branch: both ends are its value, 0
+template <bool L2>
+__device__ __forceinline__ float screen_hi(const ScreenArgs &s, float dot, float e, float m) {
+  if constexpr (!L2) {
+    if (!(m > 1.1920929e-07f)) return 0.f;
+    return above(finalize_cosine(below(dot - e), m));
+  } else {
+    const float sq = m - 2.f * dot;
+    const float d = above(above(sq + e) * (1.f + s.c_sum) + s.a_abs);
+    return d < __builtin_inff() ? d : __uint_as_float(HNY_SCREEN_TOP);
+  }
+}
+template <bool L2>
+__device__ __forceinline__ float screen_lo(const ScreenArgs &s, float dot, float e, float m) {
+  float d;
+  if constexpr (!L2) {
+    if (!(m > 1.1920929e-07f)) return 0.f;
+    d = below(finalize_cosine(above(dot + e), m));
+  } else {
+    const float sq = m - 2.f * dot;
+    float lo = below(sq - e);
+    lo = lo > 0.f ? lo : 0.f;
+    d = below(lo * (1.f - s.c_sum) - s.a_abs);
+  }
+  return d > 0.f ? d : 0.f;
+}
+
+// What the two scans keep in LDS: the tile's K panel and, per query, the stored norm, the sum of squares, its upper
+// bound and the bound on |q|
+struct ScreenLds {
+  float4 *qpan;
+  float *qn, *q2, *q2up, *qnorm;
+};
+#define HNY_SCREEN_LDS(L)                                                                       \
+  __shared__ float4 L##_qpan[HNY_SCREEN_QT * HNY_SCREEN_PSTRIDE];                               \
+  __shared__ float L##_qn[HNY_SCREEN_QT], L##_q2[HNY_SCREEN_QT], L##_q2up[HNY_SCREEN_QT], L##_qnorm[HNY_SCREEN_QT]; \
+  const ScreenLds L{L##_qpan, L##_qn, L##_q2, L##_q2up, L##_qnorm}
+
+// threads 0 .. HNY_SCREEN_QT: the tile's norms (zero beyond its queries); the first barrier of screen_dots publishes them
+__device__ __forceinline__ void screen_stage_norms(const GraphDev &g, const ExactArgs &a, const ScreenArgs &s,
+                                                   const ScreenLds &L, u32 q0, u32 nqt, u32 tid) {
   if (tid < HNY_SCREEN_QT) {
     float qn = 0.f, q2 = 0.f;
     if (tid < nqt) {
@@ -78,60 +122,79 @@ __global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_screen_scores(GraphDe
       }
     }
     const float q2up = q2 * s.c_n2 + s.a_n2;
-    s_qn[tid] = qn;
-    s_q2[tid] = q2;
-    s_q2up[tid] = q2up;
-    s_qnorm[tid] = norm_up(q2up);
+    L.qn[tid] = qn;
+    L.q2[tid] = q2;
+    L.q2up[tid] = q2up;
+    L.qnorm[tid] = norm_up(q2up);
   }
-  const u32 ln = tid & 63u, wave = tid >> 6, j = ln & 31u, h = ln >> 5;
+}
+
+// One pass of a wave: the dot products of the lane's row (rp; !valid: zeros) with the tile's 2 x 32 queries.
+// Accumulator register i of a block is query 8 (i / 4) + 4 h + (i % 4) of the block, column = the lane's row.
+// `first`: the workgroup's first pass, which stages a row that fits one panel for all of them
+__device__ __forceinline__ void screen_dots(const GraphDev &g, const ExactArgs &a, const ScreenLds &L, u32 q0, u32 nqt,
+                                            bool first, const unsigned char *rp, bool valid, f32x16 &acc0,
+                                            f32x16 &acc1) {
+  const u32 tid = threadIdx.x, ln = tid & 63u, j = ln & 31u, h = ln >> 5, n16 = g.n16;
   const bool one_panel = n16 <= HNY_SCREEN_KP;
+  float4 *qpan = L.qpan;
+#pragma unroll
+  for (int i = 0; i < 16; i++) acc0[i] = 0.f, acc1[i] = 0.f;
+  for (u32 u0 = 0; u0 < n16; u0 += HNY_SCREEN_KP) {
+    if (!one_panel || first) {
+      __syncthreads(); // the panel before is read
+      for (u32 i = tid; i < HNY_SCREEN_QT * HNY_SCREEN_KP; i += 256u) {
+        const u32 qi = i / HNY_SCREEN_KP, f = i % HNY_SCREEN_KP, u = u0 + f;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (qi < nqt && u < n16) {
+          const unsigned char *src = a.q_slots ? g.rows + (size_t)a.q_slots[q0 + qi] * g.row_stride
+                                               : a.q_rows + (size_t)(q0 + qi) * a.q_stride;
+          v = *reinterpret_cast<const float4 *>(src + (size_t)u * 16);
+        }
+        qpan[qi * HNY_SCREEN_PSTRIDE + f] = v;
+      }
+      __syncthreads();
+    }
+    const u32 units = n16 - u0 < HNY_SCREEN_KP ? n16 - u0 : HNY_SCREEN_KP;
+    const u32 steps = (units + 1u) / 2u;
+    for (u32 st = 0; st < steps; st++) {
+      const u32 f = 2u * st + h, u = u0 + f; // f < HNY_SCREEN_KP: staged, zero from n16 on
+      float4 rv = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (valid && u < n16) rv = *reinterpret_cast<const float4 *>(rp + (size_t)u * 16);
+      const float4 qa = qpan[j * HNY_SCREEN_PSTRIDE + f], qb = qpan[(32u + j) * HNY_SCREEN_PSTRIDE + f];
+      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(qa.x, rv.x, acc0, 0, 0, 0);
+      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(qb.x, rv.x, acc1, 0, 0, 0);
+      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(qa.y, rv.y, acc0, 0, 0, 0);
+      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(qb.y, rv.y, acc1, 0, 0, 0);
+      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(qa.z, rv.z, acc0, 0, 0, 0);
+      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(qb.z, rv.z, acc1, 0, 0, 0);
+      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(qa.w, rv.w, acc0, 0, 0, 0);
+      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(qb.w, rv.w, acc1, 0, 0, 0);
+    }
+  }
+}
+
+template <bool L2>
+__global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_screen_scores(GraphDev g, ExactArgs a, ScreenArgs s) {
+  HNY_SCREEN_LDS(L);
+  const u32 tid = threadIdx.x;
+  const u32 q0 = blockIdx.x * HNY_SCREEN_QT;
+  const u32 nqt = a.nq - q0 < HNY_SCREEN_QT ? a.nq - q0 : HNY_SCREEN_QT;
+  const u32 slab_end = a.slab_base + a.slab_n;
+  const u32 c0 = a.slab_base + blockIdx.y * HNY_EXACT_CHUNK;
+  const u32 c1 = slab_end - c0 < HNY_EXACT_CHUNK ? slab_end : c0 + HNY_EXACT_CHUNK;
+  screen_stage_norms(g, a, s, L, q0, nqt, tid);
+  const u32 ln = tid & 63u, wave = tid >> 6, j = ln & 31u, h = ln >> 5;
   for (u32 p0 = c0; p0 < c1; p0 += 128u) { // the same trips for every wave: the panels are staged between barriers
     const u32 row = p0 + wave * 32u + j;
     const bool valid = row < c1;
-    const unsigned char *rp = g.rows + (size_t)(valid ? row : c0) * g.row_stride;
     f32x16 acc0, acc1;
-#pragma unroll
-    for (int i = 0; i < 16; i++) acc0[i] = 0.f, acc1[i] = 0.f;
-    for (u32 u0 = 0; u0 < n16; u0 += HNY_SCREEN_KP) {
-      if (!one_panel || p0 == c0) {
-        __syncthreads(); // the panel before is read
-        for (u32 i = tid; i < HNY_SCREEN_QT * HNY_SCREEN_KP; i += 256u) {
-          const u32 qi = i / HNY_SCREEN_KP, f = i % HNY_SCREEN_KP, u = u0 + f;
-          float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (qi < nqt && u < n16) {
-            const unsigned char *src = a.q_slots ? g.rows + (size_t)a.q_slots[q0 + qi] * g.row_stride
-                                                 : a.q_rows + (size_t)(q0 + qi) * a.q_stride;
-            v = *reinterpret_cast<const float4 *>(src + (size_t)u * 16);
-          }
-          qpan[qi * HNY_SCREEN_PSTRIDE + f] = v;
-        }
-        __syncthreads();
-      }
-      const u32 units = n16 - u0 < HNY_SCREEN_KP ? n16 - u0 : HNY_SCREEN_KP;
-      const u32 steps = (units + 1u) / 2u;
-      for (u32 st = 0; st < steps; st++) {
-        const u32 f = 2u * st + h, u = u0 + f; // f < HNY_SCREEN_KP: staged, zero from n16 on
-        float4 rv = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (valid && u < n16) rv = *reinterpret_cast<const float4 *>(rp + (size_t)u * 16);
-        const float4 qa = qpan[j * HNY_SCREEN_PSTRIDE + f], qb = qpan[(32u + j) * HNY_SCREEN_PSTRIDE + f];
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(qa.x, rv.x, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(qb.x, rv.x, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(qa.y, rv.y, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(qb.y, rv.y, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(qa.z, rv.z, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(qb.z, rv.z, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(qa.w, rv.w, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(qb.w, rv.w, acc1, 0, 0, 0);
-      }
-    }
-    // ---- the lane's row against its 2 x 16 queries: accumulator register i of a block is query
-    // 8 (i / 4) + 4 h + (i % 4) of the block, column = the lane's row
+    screen_dots(g, a, L, q0, nqt, p0 == c0, g.rows + (size_t)(valid ? row : c0) * g.row_stride, valid, acc0, acc1);
     if (valid) {
       const float rn = g.norms ? g.norms[row] : 0.f;
       const float r2 = s.row_n2[row];
       const float r2up = r2 * s.c_n2 + s.a_n2;
       const float nr = norm_up(r2up);
-      const float top = __uint_as_float(HNY_SCREEN_TOP);
 #pragma unroll
       for (int blk = 0; blk < 2; blk++) {
 #pragma unroll
@@ -139,44 +202,79 @@ __global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_screen_scores(GraphDe
           const u32 qi = (u32)(blk * 32 + 8 * (i / 4) + (i % 4)) + 4u * h;
           if (qi >= nqt) continue;
           const float dot = blk ? acc1[i] : acc0[i];
-          const float nq = s_qnorm[qi];
-          const float flush = s.a_flush * (nq + nr) * HNY_SCREEN_SLOP;
-          float d;
-          if constexpr (!L2) {
-            const float eps = s.c_dot * (nq * nr) * HNY_SCREEN_SLOP + s.a_abs + flush;
-            if (!(eps < HNY_SCREEN_BIG) || !(__builtin_fabsf(dot) < HNY_SCREEN_BIG)) {
-              d = s.upper ? top : 0.f;
-            } else {
-              // the finaliser's steps are monotone: acc in [dot - eps, dot + eps] gives d in [f(dot + eps), f(dot - eps)].
-              // The nudge covers the sum's and the quotient's rounding, the last step outwards that of 1 - c
-              const float pnqn = s_qn[qi] * rn;
-              if (!(pnqn > 1.1920929e-07f)) {
-                d = 0.f; // the exact kernel's own branch: both ends are its value
-              } else if (s.upper) {
-                d = above(finalize_cosine(below(dot - eps), pnqn));
-              } else {
-                d = below(finalize_cosine(above(dot + eps), pnqn));
-                d = d > 0.f ? d : 0.f;
-              }
-            }
+          float e, d;
+          if (!screen_err<L2>(s, dot, L.qnorm[qi], nr, L.q2up[qi], r2up, e)) {
+            d = s.upper ? __uint_as_float(HNY_SCREEN_TOP) : 0.f;
           } else {
-            const float e = s.c_l2 * (s_q2up[qi] + r2up) * HNY_SCREEN_SLOP + 4.f * s.a_abs + 2.f * flush;
-            if (!(e < HNY_SCREEN_BIG) || !(__builtin_fabsf(dot) < HNY_SCREEN_BIG)) {
-              d = s.upper ? top : 0.f;
-            } else {
-              const float sq = (s_q2[qi] + r2) - 2.f * dot;
-              if (s.upper) {
-                d = above(above(sq + e) * (1.f + s.c_sum) + s.a_abs);
-                if (!(d < __builtin_inff())) d = top;
-              } else {
-                float lo = below(sq - e);
-                lo = lo > 0.f ? lo : 0.f;
-                d = below(lo * (1.f - s.c_sum) - s.a_abs);
-                d = d > 0.f ? d : 0.f;
-              }
-            }
+            const float m = L2 ? L.q2[qi] + r2 : L.qn[qi] * rn;
+            d = s.upper ? screen_hi<L2>(s, dot, e, m) : screen_lo<L2>(s, dot, e, m);
           }
           a.scores[(size_t)(q0 + qi) * a.score_stride + (row - a.slab_base)] = d;
+        }
+      }
+    }
+  }
+}
+
+// The fused scan of the screened range search: k_screen_scores' split and inner loop; the epilogue
+// forms both ends of every pair's interval from the one accumulator value, compares them with the query's radius and
+// votes.  Accumulator register i holds one query in lanes 0 .. 31 and another in lanes 32 .. 63, the lane's row being
+// the bit: one ballot is two finished words of 32 consecutive slots, which the lanes 0 and 32 store.  Exact distances
+// of these metrics are >= +0 or the NaN, so with an uncertain pair as [0, NaN]:
+//   certain  d_hi <= r   (never for the NaN end: d <= d_hi <= r, a hit whatever the row holds)
+//   cand     d_lo <= r   (false for a NaN radius and where r < d_lo <= d: no hit; -0.0 compares as 0)
+// Rows at and beyond the chunk's end vote 0; the call's slot mask is left to the consumer (k_range_settle)
+template <bool L2>
+__global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_screen_range(GraphDev g, ExactArgs a, ScreenArgs s,
+                                                                         ScreenRangeArgs b) {
+  HNY_SCREEN_LDS(L);
+  __shared__ float s_r[HNY_SCREEN_QT];
+  const u32 tid = threadIdx.x;
+  const u32 q0 = blockIdx.x * HNY_SCREEN_QT;
+  const u32 nqt = a.nq - q0 < HNY_SCREEN_QT ? a.nq - q0 : HNY_SCREEN_QT;
+  const u32 slab_end = a.slab_base + a.slab_n;
+  const u32 c0 = a.slab_base + blockIdx.y * HNY_EXACT_CHUNK;
+  const u32 c1 = slab_end - c0 < HNY_EXACT_CHUNK ? slab_end : c0 + HNY_EXACT_CHUNK;
+  screen_stage_norms(g, a, s, L, q0, nqt, tid);
+  if (tid < HNY_SCREEN_QT) s_r[tid] = tid < nqt ? b.radius[q0 + tid] : 0.f;
+  const u32 ln = tid & 63u, wave = tid >> 6, j = ln & 31u, h = ln >> 5;
+  for (u32 p0 = c0; p0 < c1; p0 += 128u) {
+    const u32 row = p0 + wave * 32u + j;
+    const bool valid = row < c1;
+    f32x16 acc0, acc1;
+    screen_dots(g, a, L, q0, nqt, p0 == c0, g.rows + (size_t)(valid ? row : c0) * g.row_stride, valid, acc0, acc1);
+    float rn = 0.f, r2 = 0.f;
+    if (valid) {
+      rn = g.norms ? g.norms[row] : 0.f;
+      r2 = s.row_n2[row];
+    }
+    const float r2up = r2 * s.c_n2 + s.a_n2;
+    const float nr = norm_up(r2up);
+    const u32 word = (p0 - a.slab_base) / 32u + wave; // < HNY_SCREEN_BITS_STRIDE: the chunk lies within the slab
+#pragma unroll
+    for (int blk = 0; blk < 2; blk++) {
+#pragma unroll
+      for (int i = 0; i < 16; i++) {
+        const u32 qi = (u32)(blk * 32 + 8 * (i / 4) + (i % 4)) + 4u * h;
+        const bool on = valid && qi < nqt;
+        const float dot = blk ? acc1[i] : acc0[i];
+        bool cand = false, certain = false;
+        if (on) {
+          const float r = s_r[qi];
+          float e;
+          if (!screen_err<L2>(s, dot, L.qnorm[qi], nr, L.q2up[qi], r2up, e)) {
+            cand = 0.f <= r;
+          } else {
+            const float m = L2 ? L.q2[qi] + r2 : L.qn[qi] * rn;
+            cand = screen_lo<L2>(s, dot, e, m) <= r;
+            certain = screen_hi<L2>(s, dot, e, m) <= r;
+          }
+        }
+        const u64 vc = ballot(cand), vh = ballot(certain);
+        if (j == 0u && qi < nqt) {
+          const size_t at = (size_t)(q0 + qi) * HNY_SCREEN_BITS_STRIDE + word;
+          b.cand[at] = (u32)(vc >> (32u * h));
+          b.certain[at] = (u32)(vh >> (32u * h));
         }
       }
     }
@@ -253,5 +351,16 @@ hipError_t hnyk_screen_n2(const unsigned char *rows, u32 stride, u32 n16, const 
 hipError_t hnyk_screen_collect(const ExactArgs &a, const u32 *item_ids, u32 *cand, u32 *cnt, hipStream_t st) {
   if (!a.nq || !a.slab_n) return hipSuccess;
   hipLaunchKernelGGL(k_screen_collect, dim3(a.nq), dim3(64), 0, st, a, item_ids, cand, cnt);
+  return hipGetLastError();
+}
+
+hipError_t hnyk_screen_range(const GraphDev &g, const ExactArgs &a, const ScreenArgs &s, const ScreenRangeArgs &b,
+                             hipStream_t st) {
+  if (!a.nq || !a.slab_n) return hipSuccess;
+  if (g.metric != 0 && g.metric != 1) return hipErrorInvalidValue; // Cosine and Euclidean only: no silent other path
+  if (a.slab_n > HNY_EXACT_SLAB || a.slab_base % HNY_EXACT_CHUNK) return hipErrorInvalidValue; // the bitmaps' stride
+  const dim3 grid((a.nq + HNY_SCREEN_QT - 1) / HNY_SCREEN_QT, (a.slab_n + HNY_EXACT_CHUNK - 1) / HNY_EXACT_CHUNK);
+  if (g.metric == 1) hipLaunchKernelGGL(k_screen_range<true>, grid, dim3(256), 0, st, g, a, s, b);
+  else hipLaunchKernelGGL(k_screen_range<false>, grid, dim3(256), 0, st, g, a, s, b);
   return hipGetLastError();
 }

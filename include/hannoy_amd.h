@@ -661,6 +661,47 @@ int hny_builder_exact_range_f32(hny_builder *b, const hny_range_opts *opts, uint
                                 const float *queries, size_t qstride, hny_range_result **out);
 void hny_range_result_free(hny_range_result *r); /* NULL is fine */
 
+/* ---- exact range search through the matrix cores.  Opt-in: nothing else calls it.
+ *
+ * Definition: each call returns, byte for byte (offsets, ids, distance bits, order, is_none, out_counts, did_cancel,
+ * HNY_RANGE_NONE), what its namesake without `_screened` returns on the same builder, queries and options, and
+ * refuses what it refuses, with the same codes and messages, decided in the same order and at the same point
+ * (max_total before anything is returned, every other refusal before any device work; *out and out_counts stay
+ * untouched).  A strict-mode f32 builder is refused as hny_builder_exact_range refuses it.
+ *
+ * Method, for Cosine and Euclidean builders in wave order: one f32 MFMA scan forms, per (query, slot) pair, the
+ * interval [d_lo, d_hi] of hny_builder_exact_screen_bounds and compares both ends with the query's radius; it leaves
+ * two bits per pair and no score: "candidate" (d_lo <= r, the pair may be a hit) and "certain" (d_hi <= r, it is
+ * one).  The count is the certain pairs plus those of the other candidates whose exact distance, computed on the f32
+ * rows, is within the radius; the hits call then settles every candidate of its queries that way, which gives the
+ * distance bits of hny_builder_exact_range, and sorts them as it does.  Sound for every radius, -0.0, negative,
+ * +inf and NaN included: the exact distances of the two metrics are >= +0 or the NaN.
+ * Routed to the namesake, whole calls only: Manhattan and the four bit metrics (strict mode among them).
+ * Memory: 16 KB of bitmaps per query of a block of at most 1 024, whatever the number of items; no score buffer.
+ * The forms with one filter per query (_filtered, _bitsets) have no screened variant.
+ *
+ * The first screened call on a builder makes one f32 per slot (the row's sum of squares), as
+ * hny_builder_exact_knn_screened does. */
+int hny_builder_exact_range_count_screened(hny_builder *b, const hny_range_opts *opts, uint64_t n_queries,
+                                           const void *qvectors, size_t qstride, const void *qheaders,
+                                           const uint32_t *query_items, uint64_t *out_counts);
+int hny_builder_exact_range_screened(hny_builder *b, const hny_range_opts *opts, uint64_t n_queries,
+                                     const void *qvectors, size_t qstride, const void *qheaders,
+                                     const uint32_t *query_items, hny_range_result **out);
+/* by_vector with f32 queries, encoded on the device like hny_builder_exact_range_f32's */
+int hny_builder_exact_range_count_screened_f32(hny_builder *b, const hny_range_opts *opts, uint64_t n_queries,
+                                               const float *queries, size_t qstride, uint64_t *out_counts);
+int hny_builder_exact_range_screened_f32(hny_builder *b, const hny_range_opts *opts, uint64_t n_queries,
+                                         const float *queries, size_t qstride, hny_range_result **out);
+/* The last screened range call on b: queries answered through the screen, queries routed to the namesake, pairs the
+ * scan alone decided to be hits, and pairs whose exact distance was computed on the f32 rows (the ambiguous pairs of
+ * the count; in the hits call also every candidate).  Any output may be NULL.  b == NULL: HNY_ERR_INVALID_ARG */
+int hny_builder_exact_range_screen_stats(const hny_builder *b, uint64_t *n_screened, uint64_t *n_routed,
+                                         uint64_t *n_certain, uint64_t *n_settled);
+/* Device milliseconds of the last screened range call on a profiling builder (hny_builder_set_profiling), out_ms[2]:
+ * the scans, the settling.  Zeros without profiling.  NULL arguments: HNY_ERR_INVALID_ARG */
+int hny_builder_exact_range_screen_times(const hny_builder *b, double *out_ms);
+
 /* ---- exact range search with one `.candidates()` filter per query: what a serving process asks that checks for
  * near duplicates inside each tenant's own items, or applies a score threshold under a per-request ACL or facet.  One
  * call in the place of one hny_builder_exact_range call per distinct filter, each of which reads every row twice.
