@@ -60,6 +60,8 @@ EXPORTED = [
     "hny_builder_exact_range_screened", "hny_builder_exact_range_screened_f32",
     "hny_builder_exact_range_count_screened", "hny_builder_exact_range_count_screened_f32",
     "hny_builder_exact_range_screen_stats", "hny_builder_exact_range_screen_times",
+    "hny_builder_exact_knn_voted", "hny_builder_exact_knn_voted_f32", "hny_builder_exact_vote_stats",
+    "hny_builder_exact_vote_times",
 ]
 ERR_IO = -9
 NNS_NONE = 0xFFFFFFFF  # by_item: the reference returns None
@@ -474,6 +476,14 @@ def load_library():
     L.hny_builder_exact_screen_stats.argtypes = [vp, vp, vp, vp]
     L.hny_builder_exact_screen_times.restype = C.c_int
     L.hny_builder_exact_screen_times.argtypes = [vp, vp]
+    L.hny_builder_exact_knn_voted.restype = C.c_int
+    L.hny_builder_exact_knn_voted.argtypes = L.hny_builder_exact_knn.argtypes
+    L.hny_builder_exact_knn_voted_f32.restype = C.c_int
+    L.hny_builder_exact_knn_voted_f32.argtypes = L.hny_builder_exact_knn_f32.argtypes
+    L.hny_builder_exact_vote_stats.restype = C.c_int
+    L.hny_builder_exact_vote_stats.argtypes = [vp, vp, vp, vp, vp]
+    L.hny_builder_exact_vote_times.restype = C.c_int
+    L.hny_builder_exact_vote_times.argtypes = [vp, vp]
     L.hny_builder_exact_screen_bounds.restype = C.c_int
     L.hny_builder_exact_screen_bounds.argtypes = [vp, C.c_uint64, vp, C.c_size_t, vp, C.c_uint64, vp, vp]
     L.hny_builder_n_slots.restype = C.c_uint64
@@ -763,6 +773,15 @@ def _f32_rows(a):
     if a.shape[1] > 1 and a.strides[1] != 4 or a.shape[0] > 1 and a.strides[0] < a.shape[1] * 4:
         a = np.ascontiguousarray(a)
     return a
+
+
+def exact_method(screened):
+    """the `screened` argument of the exact top-k searches as False, True or "votes"; anything else: ValueError"""
+    if isinstance(screened, (bool, np.bool_)):
+        return bool(screened)
+    if isinstance(screened, str) and screened == "votes":
+        return "votes"
+    raise ValueError(f'screened={screened!r}: False, True or "votes"')
 
 
 def _query_opts(k, ef_search=0, linear_below=0, linear_below_ratio=0.0, candidates=None, cancel=None):
@@ -1763,10 +1782,26 @@ class Builder:
         """hny_builder_exact_knn: the k nearest of the live items (or of `candidates` among them) by a flat scan —
         brute_force_search's result, the ground truth of the index's own distances.  Returns (ids, dists, counts)
         like nns; counts == NNS_NONE where by_item names an unknown item.
-        screened: hny_builder_exact_knn_screened, the same result through the matrix cores (exact_screen_stats)."""
+        screened: hny_builder_exact_knn_screened, the same result through the matrix cores (exact_screen_stats);
+        "votes": hny_builder_exact_knn_voted, one scan under a falling threshold (exact_vote_stats)."""
+        name = {False: "hny_builder_exact_knn", True: "hny_builder_exact_knn_screened",
+                "votes": "hny_builder_exact_knn_voted"}[exact_method(screened)]
         opts = _query_opts(k, candidates=candidates, cancel=cancel)
-        name = "hny_builder_exact_knn_screened" if screened else "hny_builder_exact_knn"
         return self._search(name, opts, _query_source(query_items, qf32, qcodes, qheaders), qf32 is not None)
+
+    def exact_vote_stats(self):
+        """hny_builder_exact_vote_stats of the last exact_knn(screened="votes"): (n_voted, n_routed, n_pilot,
+        n_settled)"""
+        out = [C.c_uint64(0) for _ in range(4)]
+        _check(load_library().hny_builder_exact_vote_stats(self._h, *map(C.byref, out)))
+        return tuple(int(v.value) for v in out)
+
+    def exact_vote_times(self):
+        """hny_builder_exact_vote_times: device ms of the last voted call on a profiling builder, as (pilot, scans,
+        settles)"""
+        out = np.zeros(3, np.float64)
+        _check(load_library().hny_builder_exact_vote_times(self._h, _p(out)))
+        return tuple(float(v) for v in out)
 
     def exact_screen_stats(self):
         """hny_builder_exact_screen_stats of the last exact_knn(screened=True): (n_screened, n_routed, n_candidates)"""

@@ -736,9 +736,11 @@ class QueryBuilder:
         """the flat scan instead of the graph (hny_builder_exact_knn): brute_force_search over the live items, or
         over `.candidates()` among them; ef_search and linear_below* are not read.
         screened: the same result through the matrix cores (hny_builder_exact_knn_screened, with .within()
-        hny_builder_exact_range_screened); not read by the forms with a filter per query"""
+        hny_builder_exact_range_screened); "votes": the top-k search by one scan under a falling threshold
+        (hny_builder_exact_knn_voted; .within() then runs the plain range search); not read by the forms with a
+        filter per query"""
         self._exact = True
-        self._screened = bool(screened)
+        self._screened = capi.exact_method(screened)
         return self
 
     def within(self, radius, filtered=False):
@@ -791,7 +793,7 @@ class QueryBuilder:
         if self._per_query is not None or self._bitsets is not None:
             raise ValueError("within().exact() takes one .candidates() for the whole call, not a filter per query "
                              "(within(radius, filtered=True) does)")
-        return b.exact_range(self._radius, candidates=self._candidates, screened=self._screened, **source)[:3]
+        return b.exact_range(self._radius, candidates=self._candidates, screened=self._screened is True, **source)[:3]
 
     def _check_within(self):
         if self._radius is not None and self._within_filtered and not self._exact:

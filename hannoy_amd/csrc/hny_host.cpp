@@ -478,6 +478,9 @@ struct hny_builder {
   // hny_builder_exact_range_screened: what hny_builder_exact_range_screen_stats reports
   uint64_t rscreen_screened = 0, rscreen_routed = 0, rscreen_certain = 0, rscreen_settled = 0;
   double rscreen_ms[2] = {0, 0}; // profiling: k_screen_range, k_range_settle
+  // hny_builder_exact_knn_voted: what hny_builder_exact_vote_stats reports
+  uint64_t vote_voted = 0, vote_routed = 0, vote_pilot = 0, vote_settled = 0;
+  double vote_ms[3] = {0, 0, 0}; // profiling: the pilot, k_screen_range, k_knn_settle on the slabs
   // successor builders whose source was profiling: device time (HIP events) and bytes read + written of k_move_rows
   double t_move_rows_s = 0;
   uint64_t move_rows_bytes = 0;
@@ -5703,6 +5706,152 @@ int hny_builder_exact_screen_stats(const hny_builder *b, uint64_t *n_screened, u
 int hny_builder_exact_screen_times(const hny_builder *b, double *out_ms) {
   if (!b || !out_ms) return fail(HNY_ERR_INVALID_ARG, "bad argument");
   for (int i = 0; i < 5; i++) out_ms[i] = b->screen_ms[i];
+  return HNY_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Exact k-NN by votes: exact_impl's result, byte for byte, from ONE matrix-core scan.  Every query
+// has a threshold on the device, +inf or an upper bound of its k-th exact distance.  A pilot settles a sample of
+// slots spread over the whole index and sets it; then, slab by slab, k_screen_range votes with the thresholds as its
+// radii and k_knn_settle settles the candidates on the f32 rows, keeps the running top-k and lowers the threshold to
+// its k-th distance for the next slab.  No scores, no candidate lists in HBM, no host round trip between the slabs,
+// and no cap on candidates: nothing overflows.  Routing as exact_screened_impl.
+// ---------------------------------------------------------------------------------------------
+// the pilot's sample size: the k-th of P spread slots has about rank k n / P among all, and a slab's candidates are
+// what lies under it.  8 and 4 096 are not tuned (scripts/exact_voted_throughput.py sweeps them through these hooks)
+static uint32_t vote_pilot_size(uint32_t n, uint32_t kk, uint64_t n_c) {
+  const char *ef = getenv("HNY_VOTE_PILOT_FACTOR"), *em = getenv("HNY_VOTE_PILOT_MIN"); // measuring hooks, read per call
+  const uint64_t factor = ef ? strtoull(ef, nullptr, 10) : 8, least = em ? strtoull(em, nullptr, 10) : 4096;
+  uint64_t P = std::max<uint64_t>(least, (factor * kk * n + n_c - 1) / n_c);
+  P = (P + 63) & ~(uint64_t)63;
+  return (uint32_t)std::min<uint64_t>(n, P); // at most every slot once: the sample's slots are distinct
+}
+
+static int voted_run(hny_builder *b, const QuerySet &qs, const u32 *dmask, uint32_t kk, uint64_t n_c, SearchCancel &sc) {
+  uint32_t rcap = 64;
+  while (rcap < kk + 1) rcap *= 2;
+  const uint32_t qblock = search_chunk(b, qs.nq, rcap, kk, HNY_EXACT_QBLOCK);
+  DenseScan scan{b, qs};
+  TopkOut top{b, qs, kk};
+  DevBuf<u64> dlists, dtally;
+  DevBuf<u32> dln, dcand, dcertain;
+  DevBuf<float> dqn2, dthr;
+  if (int rc = scan.alloc(qblock, dmask, /*scores=*/false)) return rc;
+  HIP_TRY(dlists.alloc((size_t)qblock * rcap));
+  if (int rc = top.alloc(qblock)) return rc;
+  HIP_TRY(dln.alloc(qblock));
+  HIP_TRY(dcand.alloc((size_t)qblock * HNY_SCREEN_BITS_STRIDE));
+  HIP_TRY(dcertain.alloc((size_t)qblock * HNY_SCREEN_BITS_STRIDE)); // written by the scan, read by nobody
+  HIP_TRY(dqn2.alloc(qblock));
+  HIP_TRY(dthr.alloc(qblock));
+  HIP_TRY(dtally.alloc((size_t)qblock * 2));
+  std::vector<u64> htally((size_t)qblock * 2);
+  ExactArgs &a = scan.a;
+  ScreenArgs s{};
+  screen_consts(b->g.n16, s);
+  s.row_n2 = b->d_row_n2.p;
+  s.q_n2 = dqn2.p;
+  ScreenRangeArgs bits{dthr.p, dcand.p, dcertain.p};
+  KnnSettleArgs t{};
+  t.cand = dcand.p, t.mask = dmask;
+  t.lists = dlists.p, t.list_n = dln.p, t.k = kk, t.rcap = rcap;
+  t.thr = dthr.p, t.tally = dtally.p;
+  ScreenClock clock{b, b->vote_ms};
+  scan.produce = [&] { return clock.run(1, [&] { return hnyk_screen_range(b->g, a, s, bits, b->stream); }); };
+  const auto settle = [&](int kind, uint32_t pilot_n) {
+    t.q_slots = a.q_slots, t.q_rows = a.q_rows, t.q_norms = a.q_norms, t.q_stride = a.q_stride, t.nq = a.nq;
+    t.slab_base = a.slab_base, t.slab_n = a.slab_n;
+    t.pilot_n = pilot_n;
+    return clock.run(kind, [&] { return hnyk_knn_settle(b->g, t, b->shape, b->stream); });
+  };
+  const DenseScan::Launch slab_settle = [&] { return settle(2, 0); };
+  const uint32_t pilot_n = vote_pilot_size(b->n, kk, n_c);
+  for (uint64_t q0 = 0; q0 < qs.nq; q0 += qblock) {
+    const uint32_t n_mem = scan.block(q0, qblock);
+    if (n_mem == 0 || sc.probe()) continue; // cancelled: nothing of this block is started, 0 hits each
+    if (int rc = scan.stage()) return rc;
+    scan.aim(0, n_mem);
+    HIP_TRY(screen_query_n2(b, a, dqn2.p));
+    HIP_TRY(hnyk_fill_u32(reinterpret_cast<u32 *>(dthr.p), 0x7F800000u, n_mem, b->stream)); // +inf
+    HIP_TRY(hipMemsetAsync(dln.p, 0, (size_t)n_mem * 4, b->stream));
+    HIP_TRY(hipMemsetAsync(dtally.p, 0, (size_t)n_mem * 16, b->stream));
+    bool stopped = sc.probe();
+    if (!stopped) {
+      HIP_TRY(settle(0, pilot_n));
+      if (int rc = scan.slabs(sc, &stopped, slab_settle)) return rc;
+    }
+    if (stopped) { // the block did not finish: 0 hits each
+      HIP_TRY(hipStreamSynchronize(b->stream));
+      clock.add_up();
+      continue;
+    }
+    HIP_TRY(hipMemcpyAsync(htally.data(), dtally.p, (size_t)n_mem * 16, hipMemcpyDeviceToHost, b->stream));
+    if (int rc = top.fetch(dlists.p, dln.p, rcap, n_mem, sc)) return rc;
+    clock.add_up();
+    for (uint32_t j = 0; j < n_mem; j++) {
+      top.emit(j, scan.query_of(j));
+      b->vote_pilot += htally[2 * j];
+      b->vote_settled += htally[2 * j + 1];
+    }
+    b->vote_voted += n_mem;
+  }
+  return HNY_OK;
+}
+
+static int exact_voted_impl(hny_builder *b, const hny_query_opts *qo, const QuerySet &qs) {
+  if (b) {
+    b->vote_voted = b->vote_routed = b->vote_pilot = b->vote_settled = 0;
+    for (double &ms : b->vote_ms) ms = 0;
+  }
+  if (!b || !screen_serves(b)) { // exact_impl answers the whole call, its refusals included
+    const int rc = exact_impl(b, qo, qs);
+    if (rc == HNY_OK && b) b->vote_routed = qs.nq;
+    return rc;
+  }
+  ExactPlan P;
+  if (int rc = exact_plan(b, qo, qs, P)) return rc;
+  if (P.answered) return HNY_OK;
+  if (P.gather) { // nothing dense to vote on
+    const int rc = exact_gather(b, qo, qs, P);
+    if (rc == HNY_OK) b->vote_routed = qs.nq;
+    return rc;
+  }
+  if (int rc = ensure_row_n2(b)) return rc;
+  DevBuf<u32> dmask;
+  HIP_TRY(dmask.alloc(P.C.mask.size()));
+  HIP_TRY(hipMemcpyAsync(dmask.p, P.C.mask.data(), P.C.mask.size() * 4, hipMemcpyHostToDevice, b->stream));
+  SearchCancel sc;
+  HIP_TRY(sc.init(qo));
+  if (int rc = voted_run(b, qs, dmask.p, P.kk, P.n_c, sc)) return rc;
+  return search_end(b, qo, sc);
+}
+
+int hny_builder_exact_knn_voted(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const void *qvectors,
+                                size_t qstride, const void *qheaders, const uint32_t *query_items, uint32_t *out_ids,
+                                float *out_dists, uint32_t *out_counts) {
+  return exact_voted_impl(b, qo, QuerySet::of(b, qo, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists,
+                                              out_counts));
+}
+
+int hny_builder_exact_knn_voted_f32(hny_builder *b, const hny_query_opts *qo, uint64_t nq, const float *queries,
+                                    size_t qstride, uint32_t *out_ids, float *out_dists, uint32_t *out_counts) {
+  if (!queries) return fail(HNY_ERR_INVALID_ARG, "no queries");
+  return exact_voted_impl(b, qo, QuerySet::of_f32(b, qo, nq, queries, qstride, out_ids, out_dists, out_counts));
+}
+
+int hny_builder_exact_vote_stats(const hny_builder *b, uint64_t *n_voted, uint64_t *n_routed, uint64_t *n_pilot,
+                                 uint64_t *n_settled) {
+  if (!b) return fail(HNY_ERR_INVALID_ARG, "bad argument");
+  if (n_voted) *n_voted = b->vote_voted;
+  if (n_routed) *n_routed = b->vote_routed;
+  if (n_pilot) *n_pilot = b->vote_pilot;
+  if (n_settled) *n_settled = b->vote_settled;
+  return HNY_OK;
+}
+
+int hny_builder_exact_vote_times(const hny_builder *b, double *out_ms) {
+  if (!b || !out_ms) return fail(HNY_ERR_INVALID_ARG, "bad argument");
+  for (int i = 0; i < 3; i++) out_ms[i] = b->vote_ms[i];
   return HNY_OK;
 }
 

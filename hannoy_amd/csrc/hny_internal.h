@@ -478,6 +478,26 @@ HNY_LDS_FN RangeSettleLds range_settle_lds(LdsCarve &c) {
   L.ctl = c.take<u32>(16);
   return L;
 }
+// k_knn_settle (one 256-thread workgroup per query): k_range_settle's trip arrays, the words the waves exchange
+// (ctl[0..2): set bits of the trip, ctl[4..8): kept pairs of a compaction round) and the query's keys: the sorted head
+// of at most k entries with the pending keys behind it.  `cap` is a power of two that holds a full head and one
+// compaction round, so a merge always has a network of its size
+#define HNY_KNN_SETTLE_ROUND 256u
+HNY_LDS_FN u32 knn_settle_cap(u32 rcap) { return rcap > HNY_KNN_SETTLE_ROUND ? 2u * rcap : 2u * HNY_KNN_SETTLE_ROUND; }
+struct KnnSettleLds {
+  u64 *keys;  // [knn_settle_cap(rcap)] dist bits << 32 | slot
+  u32 *slots; // [HNY_SETTLE_WORDS * 32]
+  float *d;   // [HNY_SETTLE_WORDS * 32]
+  u32 *ctl;   // [8]
+};
+HNY_LDS_FN KnnSettleLds knn_settle_lds(LdsCarve &c, u32 rcap) {
+  KnnSettleLds L;
+  L.keys = c.take<u64>(knn_settle_cap(rcap));
+  L.slots = c.take<u32>(HNY_SETTLE_WORDS * 32u);
+  L.d = c.take<float>(HNY_SETTLE_WORDS * 32u);
+  L.ctl = c.take<u32>(8);
+  return L;
+}
 // k_exact_topk
 struct ExactTopkLds {
   u64 *res; // [rcap]
@@ -796,6 +816,28 @@ struct RangeSettleArgs {
   u32 *cursor;                 // [nq]
 };
 hipError_t hnyk_range_settle(const GraphDev &g, const RangeSettleArgs &a, LaunchShape s, hipStream_t st);
+// Exact k-NN by votes (hny_builder_exact_knn_voted).  k_knn_settle (hny_kernels.hip, next to
+// k_range_settle) keeps every query's running top-k: one workgroup per query lists its candidates in slot order,
+// computes their exact distances on the f32 rows and merges the keys under the list's k-th into lists[q] (ExactArgs'
+// format).  Once the list is full and its k-th distance is finite, thr[q] falls to it: the radius of the next slab's
+// k_screen_range.  Slab mode (pilot_n == 0): the candidates are the bits of cand & mask of the slab.  Pilot mode: the
+// slots floor(t * n / pilot_n), t < pilot_n, under the mask; only thr[q] is stored.  tally[q] += pairs settled
+struct KnnSettleArgs {
+  const u32 *q_slots;          // the queries as in ExactArgs
+  const unsigned char *q_rows;
+  const float *q_norms;
+  u32 q_stride, nq;
+  u32 slab_base, slab_n;
+  const u32 *cand;             // k_screen_range's candidate bitmap of the slab (slab mode)
+  const u32 *mask;             // live items (∩ candidates) as a bitset over slots
+  u32 pilot_n;                 // pilot mode: the size of the sample, <= g.n (distinct slots); 0: slab mode
+  u64 *lists;                  // [nq][rcap] dist bits << 32 | slot, ascending
+  u32 *list_n;                 // [nq]
+  u32 k, rcap;                 // k < rcap, rcap a power of two
+  float *thr;                  // [nq] +inf or an upper bound of the k-th exact distance
+  u64 *tally;                  // [nq][2]: pairs the pilot settled, pairs settled from the slabs' bitmaps
+};
+hipError_t hnyk_knn_settle(const GraphDev &g, const KnnSettleArgs &a, LaunchShape s, hipStream_t st);
 // the n keys of n_seg segments seg[i] .. seg[i + 1], each segment ascending; `keys` and `other` are both scratch,
 // *sorted is the one that holds the result.  temp == nullptr: temp_bytes is set and nothing runs
 hipError_t hnyk_range_sort(void *temp, size_t &temp_bytes, u64 *keys, u64 *other, u32 n, u32 n_seg, const u32 *seg,

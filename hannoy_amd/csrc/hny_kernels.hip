@@ -3108,6 +3108,145 @@ __global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_range_settle(GraphDev
   }
 }
 
+// Exact k-NN by votes (hny_builder_exact_knn_voted): the consumer of k_screen_range's candidate
+// bitmap when the radius is the query's own falling threshold.  k_range_settle's split: one workgroup of four waves
+// owns the query for the launch, launches follow each other on the stream, so its list, its threshold and its tally
+// are plain loads and stores: no atomic, the same from run to run.  Per trip of HNY_SETTLE_WORDS words:
+//   expand  the candidates as slots in LDS, in slot order, at the prefix sums of the threads' popcounts.  Slab mode:
+//           the set bits of cand & mask.  PILOT: bit j of word w is sample member t = 32 w + j, the slot
+//           floor(t * n / pilot_n), set where that slot is under the mask (pilot_n <= n: the slots are distinct)
+//   settle  dist_rows on batches of 64 listed slots, the waves side by side: k_exact_scores' bits of the pair
+//   keep    key = bits << 32 | slot, kept iff key <= cut, the k-th key of the sorted head (~0 until it is full).  Kept
+//           keys are compacted by ballot in rounds of 256 into the pending area behind the head
+//   merge   when head + pending cannot take another round, and at the end of the launch: one bitonic sort of both,
+//           padded with ~0 to a power of two, cut to k entries; the cut is refreshed, later rounds keep less
+// A launch that kept nothing stores nothing.  Otherwise slab mode stores the head as lists[q] / list_n[q]
+// (k_exact_topk's format), and both modes lower thr[q] to the k-th distance of a full head if that is finite: with
+// fewer than k entries, or a k-th distance of +inf or the NaN, every pair under the mask stays a candidate.
+// the slot that bit j of word w of a trip stands for
+template <bool PILOT>
+__device__ __forceinline__ u32 knn_slot(const GraphDev &g, const KnnSettleArgs &a, u32 w, u32 j) {
+  if constexpr (PILOT) return (u32)(((u64)(w * 32u + j) * g.n) / a.pilot_n);
+  else return a.slab_base + w * 32u + j;
+}
+// head + pending (at most the keys' capacity) sorted, cut to k entries; the cut is the k-th key of a full head
+__device__ __forceinline__ void knn_merge(u64 *keys, u32 k, u32 &head_n, u32 &pend_n, u64 &cut) {
+  const u32 n = head_n + pend_n;
+  u32 P = 1;
+  while (P < n) P <<= 1;
+  for (u32 i = n + threadIdx.x; i < P; i += 256u) keys[i] = ~0ull;
+  wg_bitonic_sort(keys, P);
+  head_n = n < k ? n : k;
+  pend_n = 0;
+  if (head_n == k) cut = keys[k - 1u];
+}
+template <int LPR, int NCH, bool PILOT>
+__global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_knn_settle(GraphDev g, KnnSettleArgs a) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  LdsCarve lds(smem);
+  const KnnSettleLds lay = knn_settle_lds(lds, a.rcap);
+  u64 *keys = lay.keys;
+  u32 *slots = lay.slots, *ctl = lay.ctl;
+  float *sd = lay.d;
+  const u32 tid = threadIdx.x, wave = uni(tid >> 6), qi = blockIdx.x;
+  const int ln = HNY_LANE, t = ln % LPR;
+  float qn = 0.f;
+  const unsigned char *qrow;
+  if (a.q_slots) {
+    const u32 qslot = uni(a.q_slots[qi]);
+    qrow = g.rows + (size_t)qslot * g.row_stride;
+    if (g.norms) qn = g.norms[qslot];
+  } else {
+    qrow = a.q_rows + (size_t)qi * a.q_stride;
+    if (a.q_norms) qn = a.q_norms[qi];
+  }
+  float4 q[NCH];
+  load_row<LPR, NCH>(qrow, t, g.n16, q);
+  const u32 *cw = a.cand + (size_t)qi * HNY_SCREEN_BITS_STRIDE;
+  const u32 *mw = a.mask + (a.slab_base >> 5);
+  const u32 words = ((PILOT ? a.pilot_n : a.slab_n) + 31u) / 32u;
+  const u32 cap = knn_settle_cap(a.rcap);
+  const u64 below = (1ull << ln) - 1ull;
+  u64 *list = a.lists + (size_t)qi * a.rcap;
+  u32 head_n = 0, pend_n = 0, n_listed = 0; // (uniform; n_listed: thread 0's)
+  if constexpr (!PILOT) {
+    head_n = uni(a.list_n[qi]);
+    if (head_n > a.k) head_n = a.k;
+    for (u32 i = tid; i < head_n; i += 256u) keys[i] = list[i];
+    __syncthreads();
+  }
+  u64 cut = head_n == a.k ? keys[a.k - 1u] : ~0ull;
+  bool changed = false;
+  for (u32 w0 = 0; w0 < words; w0 += HNY_SETTLE_WORDS) {
+    const u32 w = w0 + tid;
+    u32 bits = 0;
+    if (tid < HNY_SETTLE_WORDS && w < words) {
+      if constexpr (PILOT) {
+        for (u32 j = 0; j < 32u && w * 32u + j < a.pilot_n; j++) {
+          const u32 s = knn_slot<PILOT>(g, a, w, j);
+          bits |= ((a.mask[s >> 5] >> (s & 31u)) & 1u) << j;
+        }
+      } else {
+        bits = cw[w] & mw[w];
+      }
+    }
+    // expand: the thread's place is the set bits of the threads before it
+    const u32 pc = (u32)__popc(bits);
+    u32 incl = pc;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const u32 y = __shfl_up(incl, d, 64);
+      if (ln >= d) incl += y;
+    }
+    if (ln == 63) ctl[wave] = incl;
+    __syncthreads();
+    const u32 cnt = uni(ctl[0] + ctl[1]);
+    u32 off = incl - pc + (wave == 1u ? ctl[0] : 0u);
+    for (u32 rest = bits; rest; rest &= rest - 1u) slots[off++] = knn_slot<PILOT>(g, a, w, (u32)(__ffs(rest) - 1));
+    __syncthreads();
+    if (cnt == 0u) continue;
+    if (tid == 0) n_listed += cnt;
+    // settle: wave w takes the batches w, w + 4, ... of 64 listed slots
+    for (u32 base = wave * 64u; base < cnt; base += 256u) {
+      const int nc = (int)(cnt - base < 64u ? cnt - base : 64u);
+      dist_rows<LPR, NCH>(g, q, qn, slots + base, nc, sd + base, qrow);
+    }
+    __syncthreads();
+    for (u32 r0 = 0; r0 < cnt; r0 += HNY_KNN_SETTLE_ROUND) {
+      if (head_n + pend_n + HNY_KNN_SETTLE_ROUND > cap) knn_merge(keys, a.k, head_n, pend_n, cut), changed = true;
+      const u32 i = r0 + tid;
+      const u64 key = i < cnt ? (((u64)fbits(sd[i]) << 32) | (u64)slots[i]) : ~0ull;
+      const bool keep = i < cnt && key <= cut;
+      const u64 bal = ballot(keep);
+      if (ln == 0) ctl[4u + wave] = (u32)__popcll(bal);
+      __syncthreads();
+      u32 before = 0, total = 0;
+#pragma unroll
+      for (u32 v = 0; v < 4u; v++) {
+        const u32 c = ctl[4u + v];
+        total += c;
+        if (v < wave) before += c;
+      }
+      if (keep) keys[head_n + pend_n + before + (u32)__popcll(bal & below)] = key;
+      pend_n += uni(total);
+      __syncthreads();
+    }
+  }
+  if (pend_n) knn_merge(keys, a.k, head_n, pend_n, cut), changed = true;
+  if (changed) {
+    if constexpr (!PILOT) {
+      for (u32 i = tid; i < head_n; i += 256u) list[i] = keys[i];
+      if (tid == 0) a.list_n[qi] = head_n;
+    }
+    if (tid == 0 && head_n == a.k) {
+      const u32 kth = (u32)(keys[a.k - 1u] >> 32);
+      const float dk = __builtin_bit_cast(float, kth);
+      if (kth < 0x7F800000u && dk < a.thr[qi]) a.thr[qi] = dk;
+    }
+  }
+  if (tid == 0 && n_listed) a.tally[2u * qi + (PILOT ? 0u : 1u)] += n_listed;
+}
+
 // Exact k-NN, dense scan (hny_builder_exact_knn).  k_nns_linear above fetches every candidate row
 // once per query; here a workgroup of four waves stages a tile of a.qt query rows in LDS and every wave reads its
 // share of a chunk of consecutive slots from HBM once for the whole tile.  Per (query, row) pair the work is
@@ -4989,6 +5128,14 @@ struct RangeSettleLauncher {
   }
 };
 template <int L, int C>
+struct KnnSettleLauncher {
+  static hipError_t run(const GraphDev &g, const KnnSettleArgs &a, hipStream_t st) {
+    const size_t lds = HNY_LDS_BYTES(knn_settle_lds, a.rcap);
+    if (a.pilot_n) return launch_with_lds(k_knn_settle<L, C, true>, dim3(a.nq), dim3(256), lds, st, g, a);
+    return launch_with_lds(k_knn_settle<L, C, false>, dim3(a.nq), dim3(256), lds, st, g, a);
+  }
+};
+template <int L, int C>
 struct ExactScoresLauncher {
   static hipError_t run(const GraphDev &g, const ExactArgs &a, hipStream_t st) {
     const size_t lds = HNY_LDS_BYTES(exact_scores_lds, a.qt, g.row_stride);
@@ -5092,6 +5239,14 @@ hipError_t hnyk_range_settle(const GraphDev &g, const RangeSettleArgs &a, Launch
   if (!a.nq || !a.slab_n) return hipSuccess;
   if (a.slab_n > HNY_EXACT_SLAB || (a.slab_base & 31u)) return hipErrorInvalidValue; // the bitmaps' stride and words
   return dispatch_shape<RangeSettleLauncher>(s, g, a, st);
+}
+hipError_t hnyk_knn_settle(const GraphDev &g, const KnnSettleArgs &a, LaunchShape s, hipStream_t st) {
+  if (!a.nq || (!a.pilot_n && !a.slab_n)) return hipSuccess;
+  if (a.k < 1u || a.k >= a.rcap || a.rcap > HNY_RESCORE_MAX + 1u || (a.rcap & (a.rcap - 1u))) return hipErrorInvalidValue;
+  if (a.pilot_n > g.n) return hipErrorInvalidValue; // a sample of distinct slots
+  if (!a.pilot_n && (a.slab_n > HNY_EXACT_SLAB || (a.slab_base & 31u) || a.slab_n > g.n - a.slab_base))
+    return hipErrorInvalidValue; // the bitmap's stride and words, the mask's end
+  return dispatch_shape<KnnSettleLauncher>(s, g, a, st);
 }
 hipError_t hnyk_exact_scores(const GraphDev &g, const ExactArgs &a, LaunchShape s, hipStream_t st) {
   if (!a.nq || !a.slab_n) return hipSuccess;

@@ -429,6 +429,40 @@ uint64_t hny_builder_n_slots(const hny_builder *b);
 int hny_builder_exact_screen_bounds(hny_builder *b, uint64_t n_queries, const void *qvectors, size_t qstride,
                                     const void *qheaders, uint64_t n_slots, float *out_lo, float *out_hi);
 
+/* ---- exact k-NN by votes: one matrix-core scan under a falling threshold.  Opt-in: nothing else
+ * calls it.
+ *
+ * Definition: hny_builder_exact_knn_voted returns, byte for byte (ids, distance bits, counts, did_cancel,
+ * HNY_NNS_NONE), what hny_builder_exact_knn returns on the same builder, queries and options, and refuses what it
+ * refuses, with the same codes, decided in the same order before any device work.
+ *
+ * Method, for Cosine and Euclidean builders in wave order: every query has a threshold on the device, +inf or an upper
+ * bound of its k-th exact distance.  A pilot computes the exact distances to a sample of slots spread over the whole
+ * index and sets it; then, per slab of 65 536 slots, the scan of hny_builder_exact_range_screened votes with the
+ * thresholds as its radii (a pair whose interval begins at or below the threshold is a candidate), and one workgroup
+ * per query computes the candidates' exact distances on the f32 rows, merges them into the query's running top k and
+ * lowers the threshold to its k-th distance for the next slab.  No score is stored, no list has a cap, nothing
+ * overflows.  Routed to hny_builder_exact_knn, whole calls only: Manhattan and the four bit metrics, strict-mode
+ * builders, and candidates so few that hny_builder_exact_knn gathers them.
+ *
+ * Cancellation as hny_builder_exact_knn: probed between launches, a block that did not finish reports 0 hits.
+ * Results are the same from run to run.  The row sums of squares are shared with hny_builder_exact_knn_screened. */
+int hny_builder_exact_knn_voted(hny_builder *b, const hny_query_opts *opts, uint64_t n_queries,
+                                const void *qvectors, size_t qstride, const void *qheaders,
+                                const uint32_t *query_items, uint32_t *out_ids, float *out_dists,
+                                uint32_t *out_counts);
+/* by_vector with f32 queries, encoded on the device like hny_builder_exact_knn_f32's */
+int hny_builder_exact_knn_voted_f32(hny_builder *b, const hny_query_opts *opts, uint64_t n_queries,
+                                    const float *queries, size_t qstride, uint32_t *out_ids,
+                                    float *out_dists, uint32_t *out_counts);
+/* The last voted call on b: queries answered by votes, queries routed to hny_builder_exact_knn, the pairs the pilot
+ * computed and the pairs settled from the slabs' bitmaps.  Any output may be NULL.  b == NULL: HNY_ERR_INVALID_ARG */
+int hny_builder_exact_vote_stats(const hny_builder *b, uint64_t *n_voted, uint64_t *n_routed, uint64_t *n_pilot,
+                                 uint64_t *n_settled);
+/* Device milliseconds of the last voted call on a profiling builder (hny_builder_set_profiling), out_ms[3]: the
+ * pilot, the scans, the settles.  Zeros without profiling */
+int hny_builder_exact_vote_times(const hny_builder *b, double *out_ms);
+
 /* ---- batched search with one `.candidates()` filter per query: the reference's filter belongs to one query
  * (src/reader.rs:200-203), so a batch that serves several requests carries several.
  *
