@@ -61,7 +61,7 @@ EXPORTED = [
     "hny_builder_exact_range_count_screened", "hny_builder_exact_range_count_screened_f32",
     "hny_builder_exact_range_screen_stats", "hny_builder_exact_range_screen_times",
     "hny_builder_exact_knn_voted", "hny_builder_exact_knn_voted_f32", "hny_builder_exact_vote_stats",
-    "hny_builder_exact_vote_times",
+    "hny_builder_exact_vote_times", "hny_builder_set_bit_screen",
 ]
 ERR_IO = -9
 NNS_NONE = 0xFFFFFFFF  # by_item: the reference returns None
@@ -367,6 +367,8 @@ def load_library():
         getattr(L, name).argtypes = [vp]
     L.hny_builder_set_profiling.restype = C.c_int
     L.hny_builder_set_profiling.argtypes = [vp, C.c_int]
+    L.hny_builder_set_bit_screen.restype = C.c_int
+    L.hny_builder_set_bit_screen.argtypes = [vp, C.c_int]
     L.hny_builder_next_batch.restype = C.c_int
     L.hny_builder_next_batch.argtypes = [vp, C.POINTER(Batch)]
     L.hny_builder_search.restype = C.c_int
@@ -1498,6 +1500,12 @@ class Builder:
 
     def set_profiling(self, on=True):
         _check(load_library().hny_builder_set_profiling(self._h, int(on)))
+
+    def set_bit_screen(self, on=True):
+        """hny_builder_set_bit_screen: exact_range / exact_range_count(screened=True) and exact_knn(screened="votes")
+        of a Hamming or binary-quantized builder in wave order scan on the matrix cores (k_screen_range_bits) and
+        no longer count as routed.  Off by default; no effect on other builders"""
+        _check(load_library().hny_builder_set_bit_screen(self._h, int(on)))
 
     def next_batch(self):
         b = Batch()

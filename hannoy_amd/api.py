@@ -994,6 +994,12 @@ class Reader:
         back to the host, which makes it the check for a reader opened with encoded_links=True"""
         return self._b.check_graph(**kw)
 
+    def set_bit_screen(self, on=True):
+        """Builder.set_bit_screen of the reader's builder: on a Hamming or binary-quantized index,
+        .within(r).exact(screened=True) and .exact(screened="votes") then scan on the integer matrix instruction
+        instead of running the plain calls; the same results"""
+        self._b.set_bit_screen(on)
+
     def by_vec(self, query, n=10, ef_search=200):
         q = np.asarray(query, np.float32)
         if q.ndim != 1 or len(q) != self._dimensions:

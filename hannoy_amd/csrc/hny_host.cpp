@@ -463,6 +463,7 @@ struct hny_builder {
   std::vector<Ev> evs;
   size_t ev_used = 0;
   bool profiling = false;
+  bool bit_screen = false; // hny_builder_set_bit_screen: the bit metrics take the matrix-core scan
   uint64_t n_walk_dispatch = 0; // k_walk launches since the last reset
   uint64_t exact_rows_read = 0; // hny_builder_exact_rows_read: the last hny_builder_exact_knn_filtered call's
   // filters as bitsets over item ids (FilterRounds::build_from_id_bits), made by the first such call:
@@ -2521,6 +2522,12 @@ int hny_builder_apply_merge(hny_builder *b, const void *exch_all_dev, uint32_t r
 int hny_builder_set_profiling(hny_builder *b, int on) {
   if (!b) return fail(HNY_ERR_INVALID_ARG, "null builder");
   b->profiling = on != 0;
+  return HNY_OK;
+}
+
+int hny_builder_set_bit_screen(hny_builder *b, int on) {
+  if (!b) return fail(HNY_ERR_INVALID_ARG, "null builder");
+  b->bit_screen = on != 0;
   return HNY_OK;
 }
 
@@ -5498,6 +5505,12 @@ static void screen_consts(uint32_t n16, ScreenArgs &s) {
 static bool screen_serves(const hny_builder *b) {
   return (b->g.metric == HNY_COSINE || b->g.metric == HNY_EUCLIDEAN) && !b->g.x86_order;
 }
+// the bit metrics' scan (k_screen_range_bits): opted into per builder; it produces bitmaps only, so
+// it serves the range and voted calls and not the score-buffer method or hny_builder_exact_screen_bounds
+static bool bit_screen_serves(const hny_builder *b) {
+  return b->bit_screen && b->g.metric >= HNY_HAMMING && b->g.mclass == MC_BIN && !b->g.x86_order;
+}
+static bool bitmaps_serve(const hny_builder *b) { return screen_serves(b) || bit_screen_serves(b); }
 static int ensure_row_n2(hny_builder *b) {
   if (b->d_row_n2.p) return HNY_OK;
   HIP_TRY(b->d_row_n2.alloc(b->n));
@@ -5509,6 +5522,39 @@ static hipError_t screen_query_n2(hny_builder *b, const ExactArgs &a, float *out
   if (a.q_slots) return hnyk_screen_n2(b->g.rows, b->g.row_stride, b->g.n16, a.q_slots, a.nq, out, b->stream);
   return hnyk_screen_n2(a.q_rows, a.q_stride, b->g.n16, nullptr, a.nq, out, b->stream);
 }
+// The producer of a slab's bitmaps for the range and voted calls and what it needs per builder and per query.  An
+// f32 builder: k_screen_range with the sums of squares of rows and queries and the constants of the bounds.  A bit
+// builder (bit_screen_serves): k_screen_range_bits with the popcounts of the queries and nothing per row
+struct BitmapScan {
+  hny_builder *b;
+  bool bin;
+  ScreenArgs s{};
+  DevBuf<float> dqn2;
+  DevBuf<u32> dqpop;
+  explicit BitmapScan(hny_builder *b) : b(b), bin(bit_screen_serves(b)) {}
+  int begin(uint32_t qblock) {
+    if (bin) {
+      HIP_TRY(dqpop.alloc(qblock));
+      return HNY_OK;
+    }
+    if (int rc = ensure_row_n2(b)) return rc;
+    HIP_TRY(dqn2.alloc(qblock));
+    screen_consts(b->g.n16, s);
+    s.row_n2 = b->d_row_n2.p;
+    s.q_n2 = dqn2.p;
+    return HNY_OK;
+  }
+  // per block or run: the sums of the queries DenseScan aims at
+  hipError_t query_sums(const ExactArgs &a) {
+    if (!bin) return screen_query_n2(b, a, dqn2.p);
+    if (a.q_slots) return hnyk_screen_pop(b->g.rows, b->g.row_stride, b->g.n16, a.q_slots, a.nq, dqpop.p, b->stream);
+    return hnyk_screen_pop(a.q_rows, a.q_stride, b->g.n16, nullptr, a.nq, dqpop.p, b->stream);
+  }
+  hipError_t produce(const ExactArgs &a, const ScreenRangeArgs &bits) {
+    if (bin) return hnyk_screen_range_bits(b->g, a, dqpop.p, bits, b->stream);
+    return hnyk_screen_range(b->g, a, s, bits, b->stream);
+  }
+};
 
 // device time per kind of launch, for a profiling builder (hny_builder_set_profiling): event pairs around the launches
 struct ScreenClock {
@@ -5735,29 +5781,26 @@ static int voted_run(hny_builder *b, const QuerySet &qs, const u32 *dmask, uint3
   TopkOut top{b, qs, kk};
   DevBuf<u64> dlists, dtally;
   DevBuf<u32> dln, dcand, dcertain;
-  DevBuf<float> dqn2, dthr;
+  DevBuf<float> dthr;
+  BitmapScan prod{b};
   if (int rc = scan.alloc(qblock, dmask, /*scores=*/false)) return rc;
+  if (int rc = prod.begin(qblock)) return rc;
   HIP_TRY(dlists.alloc((size_t)qblock * rcap));
   if (int rc = top.alloc(qblock)) return rc;
   HIP_TRY(dln.alloc(qblock));
   HIP_TRY(dcand.alloc((size_t)qblock * HNY_SCREEN_BITS_STRIDE));
   HIP_TRY(dcertain.alloc((size_t)qblock * HNY_SCREEN_BITS_STRIDE)); // written by the scan, read by nobody
-  HIP_TRY(dqn2.alloc(qblock));
   HIP_TRY(dthr.alloc(qblock));
   HIP_TRY(dtally.alloc((size_t)qblock * 2));
   std::vector<u64> htally((size_t)qblock * 2);
   ExactArgs &a = scan.a;
-  ScreenArgs s{};
-  screen_consts(b->g.n16, s);
-  s.row_n2 = b->d_row_n2.p;
-  s.q_n2 = dqn2.p;
   ScreenRangeArgs bits{dthr.p, dcand.p, dcertain.p};
   KnnSettleArgs t{};
   t.cand = dcand.p, t.mask = dmask;
   t.lists = dlists.p, t.list_n = dln.p, t.k = kk, t.rcap = rcap;
   t.thr = dthr.p, t.tally = dtally.p;
   ScreenClock clock{b, b->vote_ms};
-  scan.produce = [&] { return clock.run(1, [&] { return hnyk_screen_range(b->g, a, s, bits, b->stream); }); };
+  scan.produce = [&] { return clock.run(1, [&] { return prod.produce(a, bits); }); };
   const auto settle = [&](int kind, uint32_t pilot_n) {
     t.q_slots = a.q_slots, t.q_rows = a.q_rows, t.q_norms = a.q_norms, t.q_stride = a.q_stride, t.nq = a.nq;
     t.slab_base = a.slab_base, t.slab_n = a.slab_n;
@@ -5771,7 +5814,7 @@ static int voted_run(hny_builder *b, const QuerySet &qs, const u32 *dmask, uint3
     if (n_mem == 0 || sc.probe()) continue; // cancelled: nothing of this block is started, 0 hits each
     if (int rc = scan.stage()) return rc;
     scan.aim(0, n_mem);
-    HIP_TRY(screen_query_n2(b, a, dqn2.p));
+    HIP_TRY(prod.query_sums(a));
     HIP_TRY(hnyk_fill_u32(reinterpret_cast<u32 *>(dthr.p), 0x7F800000u, n_mem, b->stream)); // +inf
     HIP_TRY(hipMemsetAsync(dln.p, 0, (size_t)n_mem * 4, b->stream));
     HIP_TRY(hipMemsetAsync(dtally.p, 0, (size_t)n_mem * 16, b->stream));
@@ -5803,7 +5846,7 @@ static int exact_voted_impl(hny_builder *b, const hny_query_opts *qo, const Quer
     b->vote_voted = b->vote_routed = b->vote_pilot = b->vote_settled = 0;
     for (double &ms : b->vote_ms) ms = 0;
   }
-  if (!b || !screen_serves(b)) { // exact_impl answers the whole call, its refusals included
+  if (!b || !bitmaps_serve(b)) { // exact_impl answers the whole call, its refusals included
     const int rc = exact_impl(b, qo, qs);
     if (rc == HNY_OK && b) b->vote_routed = qs.nq;
     return rc;
@@ -5816,7 +5859,6 @@ static int exact_voted_impl(hny_builder *b, const hny_query_opts *qo, const Quer
     if (rc == HNY_OK) b->vote_routed = qs.nq;
     return rc;
   }
-  if (int rc = ensure_row_n2(b)) return rc;
   DevBuf<u32> dmask;
   HIP_TRY(dmask.alloc(P.C.mask.size()));
   HIP_TRY(hipMemcpyAsync(dmask.p, P.C.mask.data(), P.C.mask.size() * 4, hipMemcpyHostToDevice, b->stream));
@@ -6085,15 +6127,14 @@ struct RangeResult {
 // every candidate of a run and emits the kept ones as k_range_emit would.  Memory: 2 x 8 KB of bitmap per query of a
 // block (16 MB at HNY_EXACT_QBLOCK), whatever the number of slots; the pairs to settle never leave the LDS
 struct RangeScreen {
-  ScreenArgs s{};
+  BitmapScan prod;
   ScreenRangeArgs bits{};
   RangeSettleArgs t{};
   DevBuf<u32> dcand, dcertain;
-  DevBuf<float> dqn2;
   DevBuf<u64> dtally; // per query aimed at: certain pairs, settled pairs
   std::vector<u64> htally;
   ScreenClock clock;
-  explicit RangeScreen(hny_builder *b) : clock{b, b->rscreen_ms} {}
+  explicit RangeScreen(hny_builder *b) : prod{b}, clock{b, b->rscreen_ms} {}
 };
 
 // What the passes of range_impl share and what pass 2 adds.  Of `r`, count, keys, seg and cursor are set here
@@ -6172,7 +6213,7 @@ static int range_aim(RangeScan &R, uint32_t m0, uint32_t m1) {
   DenseScan &scan = R.scan;
   scan.aim(m0, m1, R.dradius.p);
   if (R.scr) { // the screen's sums of squares of these members, their tallies at zero
-    HIP_TRY(screen_query_n2(scan.b, scan.a, R.scr->dqn2.p));
+    HIP_TRY(R.scr->prod.query_sums(scan.a));
     HIP_TRY(hipMemsetAsync(R.scr->dtally.p, 0, (size_t)(m1 - m0) * 16, scan.b->stream));
   }
   if (R.fof.empty()) return HNY_OK;
@@ -6188,25 +6229,20 @@ static int range_slabs(RangeScan &R, bool *stopped, const DenseScan::Launch &con
   return R.scan.slabs(R.sc, stopped, consume, R.tiles ? tile_masks : nullptr);
 }
 // ---- the screened form's steps (R.scr set) ----
-// the bitmaps, the row sums of squares and k_screen_range as the scan's producer
+// the bitmaps and BitmapScan as the scan's producer
 static int range_screen_begin(RangeScan &R) {
-  hny_builder *b = R.scan.b;
   RangeScreen &S = *R.scr;
-  if (int rc = ensure_row_n2(b)) return rc;
+  if (int rc = S.prod.begin(R.qblock)) return rc;
   HIP_TRY(S.dcand.alloc((size_t)R.qblock * HNY_SCREEN_BITS_STRIDE));
   HIP_TRY(S.dcertain.alloc((size_t)R.qblock * HNY_SCREEN_BITS_STRIDE));
-  HIP_TRY(S.dqn2.alloc(R.qblock));
   HIP_TRY(S.dtally.alloc((size_t)R.qblock * 2));
   S.htally.resize((size_t)R.qblock * 2);
-  screen_consts(b->g.n16, S.s);
-  S.s.row_n2 = b->d_row_n2.p;
-  S.s.q_n2 = S.dqn2.p;
   S.t.cand = S.bits.cand = S.dcand.p;
   S.t.certain = S.bits.certain = S.dcertain.p;
   S.t.tally = S.dtally.p;
-  R.scan.produce = [&R, &S, b] {
+  R.scan.produce = [&R, &S] {
     S.bits.radius = R.r.radius;
-    return S.clock.run(0, [&] { return hnyk_screen_range(b->g, R.scan.a, S.s, S.bits, b->stream); });
+    return S.clock.run(0, [&] { return S.prod.produce(R.scan.a, S.bits); });
   };
   return HNY_OK;
 }
@@ -6418,7 +6454,7 @@ static int range_impl(hny_builder *b, const hny_range_opts *ro, uint64_t nq, con
   const hny_query_opts qo = range_query_opts(ro);
   RangeScan R{b, qs, ro->radius};
   if (!R.none32) return fail(HNY_ERR_OOM, "out of memory");
-  if (screened && screen_serves(b)) {
+  if (screened && bitmaps_serve(b)) {
     R.scr.reset(new (std::nothrow) RangeScreen(b));
     if (!R.scr) return fail(HNY_ERR_OOM, "out of memory");
   }
@@ -6469,8 +6505,9 @@ int hny_builder_exact_range_f32(hny_builder *b, const hny_range_opts *ro, uint64
   return range_impl(b, ro, nq, queries, qstride, nullptr, nullptr, true, nullptr, out);
 }
 
-// Screened exact range search: range_impl with RangeScreen where the screen serves the builder
-// (Cosine and Euclidean in wave order); every other builder takes range_impl as it is and its queries count as routed
+// Screened exact range search: range_impl with RangeScreen where a producer of bitmaps serves the
+// builder (Cosine and Euclidean in wave order; the bit metrics after hny_builder_set_bit_screen, §3d-8); every other
+// builder takes range_impl as it is and its queries count as routed
 static int range_screened_impl(hny_builder *b, const hny_range_opts *ro, uint64_t nq, const void *qvectors, size_t qstride,
                                const void *qheaders, const uint32_t *query_items, bool q_f32, uint64_t *out_counts,
                                hny_range_result **out) {
@@ -6479,7 +6516,7 @@ static int range_screened_impl(hny_builder *b, const hny_range_opts *ro, uint64_
     b->rscreen_ms[0] = b->rscreen_ms[1] = 0;
   }
   const int rc = range_impl(b, ro, nq, qvectors, qstride, qheaders, query_items, q_f32, out_counts, out, true);
-  if (rc == HNY_OK && b && !screen_serves(b)) b->rscreen_routed = nq;
+  if (rc == HNY_OK && b && !bitmaps_serve(b)) b->rscreen_routed = nq;
   return rc;
 }
 

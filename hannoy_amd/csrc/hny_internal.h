@@ -794,6 +794,14 @@ struct ScreenRangeArgs {
 };
 hipError_t hnyk_screen_range(const GraphDev &g, const ExactArgs &a, const ScreenArgs &s, const ScreenRangeArgs &b,
                              hipStream_t st);
+// The bit metrics' producer of the same bitmaps (hny_builder_set_bit_screen): k_screen_range_bits
+// gets popcount(q ^ r) - popcount(q) from v_mfma_i32_32x32x32_i8, adds q_pop[query] and compares the index's own
+// distance with the radius: certain = d <= r, cand = certain or a NaN d.  Metrics 3 .. 6 only
+hipError_t hnyk_screen_range_bits(const GraphDev &g, const ExactArgs &a, const u32 *q_pop, const ScreenRangeArgs &b,
+                                  hipStream_t st);
+// out[i] = popcount of the n16 units of row idx[i] (null: row i) of n rows `stride` bytes apart
+hipError_t hnyk_screen_pop(const unsigned char *rows, u32 stride, u32 n16, const u32 *idx, u32 n, u32 *out,
+                           hipStream_t st);
 // k_range_settle (hny_kernels.hip, next to dist_rows): the consumer of a slab's bitmaps, one workgroup per query.
 // Under the mask it counts the certain pairs, lists the pairs to settle in slot order (emit == 0: cand & ~certain,
 // emit != 0: cand), computes their exact distances on the f32 rows and keeps those with d <= r.

@@ -281,6 +281,189 @@ __global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_screen_range(GraphDev
   }
 }
 
+// ---- the bit metrics' producer of the same bitmaps: k_screen_range's split on the integer matrix
+// instruction v_mfma_i32_32x32x32_i8.  With the row's bits r_k as the bytes 0 / 1 and the query's bits as the signed
+// bytes 1 - 2 q_k (+1 / -1):   sum_k r_k (1 - 2 q_k) = popcount(q ^ r) - popcount(q),   so pop = acc + q_pop[query],
+// exact, and the epilogue evaluates the index's own distance: no interval, nothing uncertain.
+// Operand order.  bit_bytes(w, i) holds bits i, 8 + i, 16 + i, 24 + i of word w as bytes.  Word w of a 16-byte unit
+// makes the eight dwords bit_bytes(w, 0 .. 7); dwords 0 .. 3 are one operand, 4 .. 7 the next: eight operands per
+// unit, operand m = 2 w + (i >> 2).  Lane (j, h) of step s holds unit 2 s + h of its row and of its two queries, so
+// both operands of an MFMA cover the same 2 x 128 bits in the same order, whatever k index the hardware gives a byte.
+// Rows: HBM -> registers, expanded with two VALU operations per dword.  Queries: expanded once per workgroup and
+// panel into LDS as 128 B per (query, unit) in operand order, one ds_read_b128 per MFMA.
+#define HNY_BITS_KP 4u                             // 16-byte units (512 bits) of every query per panel
+#define HNY_BITS_PSTRIDE (HNY_BITS_KP * 8u + 1u)   // uint4 per query of a panel: 16 B of padding (4 banks per query)
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x16 __attribute__((ext_vector_type(16)));
+
+__device__ __forceinline__ u32 bit_bytes(u32 w, int i) { return (w >> i) & 0x01010101u; }
+// the bytes 0 / 1 as +1 / -1 (0x01 / 0xFF): no borrow between bytes
+__device__ __forceinline__ u32 sign_bytes(u32 x) { return (x * 0xFFu) | 0x01010101u; }
+template <bool SIGNED>
+__device__ __forceinline__ i32x4 bit_operand(u32 w, int half) {
+  i32x4 v;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const u32 x = bit_bytes(w, 4 * half + i);
+    v[i] = (int)(SIGNED ? sign_bytes(x) : x);
+  }
+  return v;
+}
+
+// finalize_bin of hny_kernels.hip, restated operation for operation
+template <int METRIC>
+__device__ __forceinline__ float finalize_bits(const GraphDev &g, u32 pop, float qn, float rn) {
+  if constexpr (METRIC == 3) {
+    return g.bin_inv != 0.f ? (float)pop * g.bin_inv : (float)pop / (float)g.bin_bits;
+  } else if constexpr (METRIC == 4) {
+    const float pq = (float)((int)g.bin_bits - 2 * (int)pop);
+    const float pnqn = qn * rn;
+    if (pnqn != 0.0f) {
+      const float c = pq / pnqn;
+      return (1.0f - c) / 2.0f;
+    }
+    return 0.0f;
+  } else if constexpr (METRIC == 5) {
+    return (float)(pop * 4u);
+  } else {
+    return (float)(pop * 2u);
+  }
+}
+
+// One pass of a wave: acc = popcount(q ^ r) - popcount(q) of the lane's row (rp; !valid: zeros) with the tile's
+// 2 x 32 queries; screen_dots' loop structure and accumulator layout
+__device__ __forceinline__ void screen_bits_dots(const GraphDev &g, const ExactArgs &a, uint4 *qpan, u32 q0, u32 nqt,
+                                                 bool first, const unsigned char *rp, bool valid, i32x16 &acc0,
+                                                 i32x16 &acc1) {
+  const u32 tid = threadIdx.x, ln = tid & 63u, j = ln & 31u, h = ln >> 5, n16 = g.n16;
+  const bool one_panel = n16 <= HNY_BITS_KP;
+#pragma unroll
+  for (int i = 0; i < 16; i++) acc0[i] = 0, acc1[i] = 0;
+  for (u32 u0 = 0; u0 < n16; u0 += HNY_BITS_KP) {
+    if (!one_panel || first) {
+      __syncthreads(); // the panel before is read
+      {                // 256 threads = 64 queries x 4 units: one unit each
+        const u32 qi = tid / HNY_BITS_KP, f = tid % HNY_BITS_KP, u = u0 + f;
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        const bool have = qi < nqt && u < n16;
+        if (have) {
+          const unsigned char *src = a.q_slots ? g.rows + (size_t)a.q_slots[q0 + qi] * g.row_stride
+                                               : a.q_rows + (size_t)(q0 + qi) * a.q_stride;
+          v = *reinterpret_cast<const uint4 *>(src + (size_t)u * 16);
+        }
+        const u32 w[4] = {v.x, v.y, v.z, v.w};
+        uint4 *dst = qpan + qi * HNY_BITS_PSTRIDE + f * 8u;
+#pragma unroll
+        for (int m = 0; m < 8; m++) {
+          const i32x4 o = bit_operand<true>(w[m >> 1], m & 1);
+          // (a query or unit that is not there is all zero bytes, not +1: it adds nothing)
+          dst[m] = have ? make_uint4((u32)o[0], (u32)o[1], (u32)o[2], (u32)o[3]) : make_uint4(0u, 0u, 0u, 0u);
+        }
+      }
+      __syncthreads();
+    }
+    const u32 units = n16 - u0 < HNY_BITS_KP ? n16 - u0 : HNY_BITS_KP;
+    const u32 steps = (units + 1u) / 2u;
+    for (u32 st = 0; st < steps; st++) {
+      const u32 f = 2u * st + h, u = u0 + f; // f < HNY_BITS_KP: staged, zero from n16 on
+      uint4 rv = make_uint4(0u, 0u, 0u, 0u);
+      if (valid && u < n16) rv = *reinterpret_cast<const uint4 *>(rp + (size_t)u * 16);
+      const u32 w[4] = {rv.x, rv.y, rv.z, rv.w};
+      const i32x4 *qa = reinterpret_cast<const i32x4 *>(qpan + j * HNY_BITS_PSTRIDE + f * 8u);
+      const i32x4 *qb = reinterpret_cast<const i32x4 *>(qpan + (32u + j) * HNY_BITS_PSTRIDE + f * 8u);
+#pragma unroll
+      for (int m = 0; m < 8; m++) {
+        const i32x4 rb = bit_operand<false>(w[m >> 1], m & 1);
+        acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(qa[m], rb, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(qb[m], rb, acc1, 0, 0, 0);
+      }
+    }
+  }
+}
+
+// The epilogue holds the index's own distance bits:  certain  d <= r;  cand  certain, or d is the NaN (only from a
+// NaN / inf header norm of a by-vector query: never certain, the consumer decides it as the plain call does).  A NaN
+// radius gives no certain pair.  Rows at and beyond the chunk's end vote 0; the slot mask is left to the consumer
+template <int METRIC>
+__global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_screen_range_bits(GraphDev g, ExactArgs a, const u32 *q_pop,
+                                                                              ScreenRangeArgs b) {
+  __shared__ uint4 s_qpan[HNY_SCREEN_QT * HNY_BITS_PSTRIDE];
+  __shared__ float s_r[HNY_SCREEN_QT], s_qn[HNY_SCREEN_QT];
+  __shared__ u32 s_pop[HNY_SCREEN_QT];
+  const u32 tid = threadIdx.x;
+  const u32 q0 = blockIdx.x * HNY_SCREEN_QT;
+  const u32 nqt = a.nq - q0 < HNY_SCREEN_QT ? a.nq - q0 : HNY_SCREEN_QT;
+  const u32 slab_end = a.slab_base + a.slab_n;
+  const u32 c0 = a.slab_base + blockIdx.y * HNY_EXACT_CHUNK;
+  const u32 c1 = slab_end - c0 < HNY_EXACT_CHUNK ? slab_end : c0 + HNY_EXACT_CHUNK;
+  if (tid < HNY_SCREEN_QT) { // published by the first barrier of screen_bits_dots
+    float r = 0.f, qn = 0.f;
+    u32 pop = 0;
+    if (tid < nqt) {
+      r = b.radius[q0 + tid];
+      pop = q_pop[q0 + tid];
+      if (METRIC == 4) {
+        if (a.q_slots) {
+          if (g.norms) qn = g.norms[a.q_slots[q0 + tid]];
+        } else if (a.q_norms) {
+          qn = a.q_norms[q0 + tid];
+        }
+      }
+    }
+    s_r[tid] = r, s_qn[tid] = qn, s_pop[tid] = pop;
+  }
+  const u32 ln = tid & 63u, wave = tid >> 6, j = ln & 31u, h = ln >> 5;
+  for (u32 p0 = c0; p0 < c1; p0 += 128u) { // the same trips for every wave: the panels are staged between barriers
+    const u32 row = p0 + wave * 32u + j;
+    const bool valid = row < c1;
+    i32x16 acc0, acc1;
+    screen_bits_dots(g, a, s_qpan, q0, nqt, p0 == c0, g.rows + (size_t)(valid ? row : c0) * g.row_stride, valid, acc0,
+                     acc1);
+    const float rn = METRIC == 4 && valid && g.norms ? g.norms[row] : 0.f;
+    const u32 word = (p0 - a.slab_base) / 32u + wave; // < HNY_SCREEN_BITS_STRIDE: the chunk lies within the slab
+#pragma unroll
+    for (int blk = 0; blk < 2; blk++) {
+#pragma unroll
+      for (int i = 0; i < 16; i++) {
+        const u32 qi = (u32)(blk * 32 + 8 * (i / 4) + (i % 4)) + 4u * h;
+        bool cand = false, certain = false;
+        if (valid && qi < nqt) {
+          const u32 pop = (u32)((blk ? acc1[i] : acc0[i]) + (int)s_pop[qi]);
+          const float d = finalize_bits<METRIC>(g, pop, s_qn[qi], rn);
+          certain = d <= s_r[qi];
+          cand = certain || d != d;
+        }
+        const u64 vc = ballot(cand), vh = ballot(certain);
+        if (j == 0u && qi < nqt) {
+          const size_t at = (size_t)(q0 + qi) * HNY_SCREEN_BITS_STRIDE + word;
+          b.cand[at] = (u32)(vc >> (32u * h));
+          b.certain[at] = (u32)(vh >> (32u * h));
+        }
+      }
+    }
+  }
+}
+
+// popcount of the units 0 .. n16 - 1 of a row, the bits partial_bin counts; eight lanes per row as k_screen_n2
+__global__ __launch_bounds__(256) void k_screen_pop(const unsigned char *rows, u32 stride, u32 n16, const u32 *idx, u32 n,
+                                                    u32 *out) {
+  const u64 gid = (u64)blockIdx.x * 256u + threadIdx.x;
+  const u64 row = gid >> 3;
+  const u32 t = (u32)(gid & 7u);
+  u32 acc = 0;
+  if (row < n) {
+    const unsigned char *p = rows + (size_t)(idx ? idx[row] : (u32)row) * stride;
+    for (u32 u = t; u < n16; u += 8u) {
+      const uint4 v = *reinterpret_cast<const uint4 *>(p + (size_t)u * 16);
+      acc += __popc(v.x) + __popc(v.y) + __popc(v.z) + __popc(v.w);
+    }
+  }
+  acc += __shfl_xor(acc, 4, 64);
+  acc += __shfl_xor(acc, 2, 64);
+  acc += __shfl_xor(acc, 1, 64);
+  if (row < n && t == 0) out[row] = acc;
+}
+
 // Eight lanes per row: lane t takes the units t, t + 8, ..., one fma chain, then three butterfly steps.  At most
 // 4 * n16 / 8 + 7 roundings of half an ulp on a sum of non-negative terms
 __global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_screen_n2(const unsigned char *rows, u32 stride, u32 n16, const u32 *idx, u32 n,
@@ -362,5 +545,28 @@ hipError_t hnyk_screen_range(const GraphDev &g, const ExactArgs &a, const Screen
   const dim3 grid((a.nq + HNY_SCREEN_QT - 1) / HNY_SCREEN_QT, (a.slab_n + HNY_EXACT_CHUNK - 1) / HNY_EXACT_CHUNK);
   if (g.metric == 1) hipLaunchKernelGGL(k_screen_range<true>, grid, dim3(256), 0, st, g, a, s, b);
   else hipLaunchKernelGGL(k_screen_range<false>, grid, dim3(256), 0, st, g, a, s, b);
+  return hipGetLastError();
+}
+
+hipError_t hnyk_screen_pop(const unsigned char *rows, u32 stride, u32 n16, const u32 *idx, u32 n, u32 *out,
+                           hipStream_t st) {
+  if (!n) return hipSuccess;
+  const u64 blocks = ((u64)n * 8u + 255u) / 256u;
+  hipLaunchKernelGGL(k_screen_pop, dim3((unsigned)blocks), dim3(256), 0, st, rows, stride, n16, idx, n, out);
+  return hipGetLastError();
+}
+
+hipError_t hnyk_screen_range_bits(const GraphDev &g, const ExactArgs &a, const u32 *q_pop, const ScreenRangeArgs &b,
+                                  hipStream_t st) {
+  if (!a.nq || !a.slab_n) return hipSuccess;
+  if (g.metric < 3 || g.metric > 6) return hipErrorInvalidValue; // the four bit metrics only: no silent other path
+  if (a.slab_n > HNY_EXACT_SLAB || a.slab_base % HNY_EXACT_CHUNK) return hipErrorInvalidValue; // the bitmaps' stride
+  const dim3 grid((a.nq + HNY_SCREEN_QT - 1) / HNY_SCREEN_QT, (a.slab_n + HNY_EXACT_CHUNK - 1) / HNY_EXACT_CHUNK);
+  switch (g.metric) {
+    case 3: hipLaunchKernelGGL(k_screen_range_bits<3>, grid, dim3(256), 0, st, g, a, q_pop, b); break;
+    case 4: hipLaunchKernelGGL(k_screen_range_bits<4>, grid, dim3(256), 0, st, g, a, q_pop, b); break;
+    case 5: hipLaunchKernelGGL(k_screen_range_bits<5>, grid, dim3(256), 0, st, g, a, q_pop, b); break;
+    default: hipLaunchKernelGGL(k_screen_range_bits<6>, grid, dim3(256), 0, st, g, a, q_pop, b); break;
+  }
   return hipGetLastError();
 }

@@ -442,8 +442,8 @@ int hny_builder_exact_screen_bounds(hny_builder *b, uint64_t n_queries, const vo
  * thresholds as its radii (a pair whose interval begins at or below the threshold is a candidate), and one workgroup
  * per query computes the candidates' exact distances on the f32 rows, merges them into the query's running top k and
  * lowers the threshold to its k-th distance for the next slab.  No score is stored, no list has a cap, nothing
- * overflows.  Routed to hny_builder_exact_knn, whole calls only: Manhattan and the four bit metrics, strict-mode
- * builders, and candidates so few that hny_builder_exact_knn gathers them.
+ * overflows.  Routed to hny_builder_exact_knn, whole calls only: Manhattan and the four bit metrics (those until
+ * hny_builder_set_bit_screen), strict-mode builders, and candidates so few that hny_builder_exact_knn gathers them.
  *
  * Cancellation as hny_builder_exact_knn: probed between launches, a block that did not finish reports 0 hits.
  * Results are the same from run to run.  The row sums of squares are shared with hny_builder_exact_knn_screened. */
@@ -462,6 +462,18 @@ int hny_builder_exact_vote_stats(const hny_builder *b, uint64_t *n_voted, uint64
 /* Device milliseconds of the last voted call on a profiling builder (hny_builder_set_profiling), out_ms[3]: the
  * pilot, the scans, the settles.  Zeros without profiling */
 int hny_builder_exact_vote_times(const hny_builder *b, double *out_ms);
+/* The bit metrics on the matrix cores, opted into per builder (off by default).  on != 0: for a Hamming or
+ * binary-quantized builder in wave order, hny_builder_exact_range_screened, hny_builder_exact_range_count_screened,
+ * hny_builder_exact_knn_voted and their _f32 forms no longer route to their plain namesakes.  Every distance of these
+ * metrics is a function of popcount(q ^ r), and with the row's bits as bytes 0 / 1 and the query's as +1 / -1 the
+ * integer matrix instruction gives popcount(q ^ r) - popcount(q) exactly; the scan adds popcount(q), evaluates the
+ * index's own distance and compares it with the radius or threshold.  Every pair it decides is a "certain" pair of
+ * hny_builder_exact_range_screen_stats (the count call settles nothing); only a NaN distance, which takes a NaN or
+ * infinite header norm of a by-vector query, is left to the consumer.  Results and refusals stay those of the plain
+ * calls, byte for byte.  No effect on other builders, on strict-mode builders, on hny_builder_exact_knn_screened
+ * (which keeps routing the bit metrics) or on hny_builder_exact_screen_bounds (which keeps refusing them).
+ * b == NULL: HNY_ERR_INVALID_ARG */
+int hny_builder_set_bit_screen(hny_builder *b, int on);
 
 /* ---- batched search with one `.candidates()` filter per query: the reference's filter belongs to one query
  * (src/reader.rs:200-203), so a batch that serves several requests carries several.
