@@ -61,9 +61,10 @@ EXPORTED = [
     "hny_builder_exact_range_count_screened", "hny_builder_exact_range_count_screened_f32",
     "hny_builder_exact_range_screen_stats", "hny_builder_exact_range_screen_times",
     "hny_builder_exact_knn_voted", "hny_builder_exact_knn_voted_f32", "hny_builder_exact_vote_stats",
-    "hny_builder_exact_vote_times", "hny_builder_set_bit_screen",
+    "hny_builder_exact_vote_times", "hny_builder_set_bit_screen", "hny_builder_set_screen_precision",
 ]
 ERR_IO = -9
+SCREEN_PRECISIONS = {"f32": 0, "bf16x3": 1}  # HNY_SCREEN_F32, HNY_SCREEN_BF16X3
 NNS_NONE = 0xFFFFFFFF  # by_item: the reference returns None
 NNS_FILTER_NONE = 0xFFFFFFFF  # hny_query_filters.filter_of: no .candidates() for this query
 RANGE_NONE = 0xFFFFFFFFFFFFFFFF  # exact_range_count by_item: the reference returns None
@@ -369,6 +370,8 @@ def load_library():
     L.hny_builder_set_profiling.argtypes = [vp, C.c_int]
     L.hny_builder_set_bit_screen.restype = C.c_int
     L.hny_builder_set_bit_screen.argtypes = [vp, C.c_int]
+    L.hny_builder_set_screen_precision.restype = C.c_int
+    L.hny_builder_set_screen_precision.argtypes = [vp, C.c_int]
     L.hny_builder_next_batch.restype = C.c_int
     L.hny_builder_next_batch.argtypes = [vp, C.POINTER(Batch)]
     L.hny_builder_search.restype = C.c_int
@@ -1506,6 +1509,15 @@ class Builder:
         of a Hamming or binary-quantized builder in wave order scan on the matrix cores (k_screen_range_bits) and
         no longer count as routed.  Off by default; no effect on other builders"""
         _check(load_library().hny_builder_set_bit_screen(self._h, int(on)))
+
+    def set_screen_precision(self, mode):
+        """hny_builder_set_screen_precision, mode "f32" (the default) or "bf16x3": exact_range / exact_range_count
+        (screened=True) and exact_knn(screened="votes") of a Cosine or Euclidean builder in wave order scan on the bf16
+        matrix instruction over two bf16 halves of every f32 (k_screen_range_split).  The same results; no effect on
+        other builders or on exact_knn(screened=True)"""
+        if mode not in SCREEN_PRECISIONS:
+            raise ValueError(f"screen precision {mode!r}: expected one of {sorted(SCREEN_PRECISIONS)}")
+        _check(load_library().hny_builder_set_screen_precision(self._h, SCREEN_PRECISIONS[mode]))
 
     def next_batch(self):
         b = Batch()

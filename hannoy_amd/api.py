@@ -1000,6 +1000,12 @@ class Reader:
         instead of running the plain calls; the same results"""
         self._b.set_bit_screen(on)
 
+    def set_screen_precision(self, mode):
+        """Builder.set_screen_precision of the reader's builder: "bf16x3" runs the matrix-core scan of
+        .within(r).exact(screened=True) and .exact(screened="votes") of a Cosine or Euclidean index on split bf16
+        halves, "f32" (the default) on the f32 instruction; the same results"""
+        self._b.set_screen_precision(mode)
+
     def by_vec(self, query, n=10, ef_search=200):
         q = np.asarray(query, np.float32)
         if q.ndim != 1 or len(q) != self._dimensions:

@@ -463,6 +463,7 @@ struct hny_builder {
   std::vector<Ev> evs;
   size_t ev_used = 0;
   bool profiling = false;
+  int screen_precision = 0; // hny_builder_set_screen_precision: HNY_SCREEN_F32 or HNY_SCREEN_BF16X3
   bool bit_screen = false; // hny_builder_set_bit_screen: the bit metrics take the matrix-core scan
   uint64_t n_walk_dispatch = 0; // k_walk launches since the last reset
   uint64_t exact_rows_read = 0; // hny_builder_exact_rows_read: the last hny_builder_exact_knn_filtered call's
@@ -2528,6 +2529,13 @@ int hny_builder_set_profiling(hny_builder *b, int on) {
 int hny_builder_set_bit_screen(hny_builder *b, int on) {
   if (!b) return fail(HNY_ERR_INVALID_ARG, "null builder");
   b->bit_screen = on != 0;
+  return HNY_OK;
+}
+
+int hny_builder_set_screen_precision(hny_builder *b, int mode) {
+  if (mode != HNY_SCREEN_F32 && mode != HNY_SCREEN_BF16X3) return fail(HNY_ERR_INVALID_ARG, "unknown screen precision");
+  if (!b) return fail(HNY_ERR_INVALID_ARG, "null builder");
+  b->screen_precision = mode;
   return HNY_OK;
 }
 
@@ -5502,6 +5510,26 @@ static void screen_consts(uint32_t n16, ScreenArgs &s) {
   s.a_n2 = f32_up(K * tiny);
   s.a_flush = f32_up(std::sqrt(K) * tiny);
 }
+// The constants of k_screen_range_split's bound, by the same conventions.  With u = 2^-8 the unit
+// roundoff charged to a conversion to bf16 (round to nearest gives 2^-9; the bound does not depend on it):
+//   |hi| <= (1 + u) |x|,  |lo| <= u (1 + u) |x|,  |x - hi - lo| <= u^2 |x| = 2^-16 |x|.
+// The three kinds of product the scan sums are exact and at most T |q_i r_i| together, T = (1 + u)^2 (1 + 2 u); their
+// 3 K additions are charged one ulp each, dist_rows' chain half an ulp for K + 8 operations.  What the scan leaves
+// out per dimension, lo_q lo_r and the two remainders, is at most u^2 ((1 + u)^2 + 2 + u^2) |q_i r_i|; Cauchy-Schwarz
+// takes sum |q_i r_i| to |q| |r| (Cosine) and 2 sum |q_i r_i| to |q|^2 + |r|^2 (Euclidean), as for the f32 scan.
+// Absolute terms: 3 K products and 3 K sums of the matrix core and the chain's K + 8 results may have been flushed;
+// per element the halves may be off by 4 * 2^-126 more than u^2 |x| (a flushed hi, a flushed or subnormal x - hi, a
+// flushed or subnormal lo, lo as the core reads it), which costs 4 sqrt(K) 2^-126 per unit of |q| + |r|, rounded to 5.
+// c_sum, c_n2, a_n2 belong to k_screen_n2 and to the exact chain on the f32 values: unchanged
+static void screen_consts_split(uint32_t n16, ScreenArgs &s) {
+  screen_consts(n16, s);
+  const double K = 4.0 * n16, u23 = std::ldexp(1.0, -23), tiny = std::ldexp(1.0, -126), u = std::ldexp(1.0, -8);
+  const double T = (1 + u) * (1 + u) * (1 + 2 * u), left_out = u * u * ((1 + u) * (1 + u) + 2 + u * u);
+  s.c_dot = f32_up(1.02 * ((3 * K * T + 0.5 * K + 8) * u23 + left_out));
+  s.c_l2 = f32_up(1.02 * ((3 * K * T + 0.5 * K + 16) * u23 + left_out));
+  s.a_abs = f32_up((7 * K + 8) * tiny);
+  s.a_flush = f32_up(5 * std::sqrt(K) * tiny);
+}
 static bool screen_serves(const hny_builder *b) {
   return (b->g.metric == HNY_COSINE || b->g.metric == HNY_EUCLIDEAN) && !b->g.x86_order;
 }
@@ -5524,14 +5552,17 @@ static hipError_t screen_query_n2(hny_builder *b, const ExactArgs &a, float *out
 }
 // The producer of a slab's bitmaps for the range and voted calls and what it needs per builder and per query.  An
 // f32 builder: k_screen_range with the sums of squares of rows and queries and the constants of the bounds.  A bit
-// builder (bit_screen_serves): k_screen_range_bits with the popcounts of the queries and nothing per row
+// builder (bit_screen_serves): k_screen_range_bits with the popcounts of the queries and nothing per row.  An f32
+// builder under HNY_SCREEN_BF16X3 (hny_builder_set_screen_precision): k_screen_range_split, the same sums of squares
+// and that scan's own constants
 struct BitmapScan {
   hny_builder *b;
-  bool bin;
+  bool bin, split;
   ScreenArgs s{};
   DevBuf<float> dqn2;
   DevBuf<u32> dqpop;
-  explicit BitmapScan(hny_builder *b) : b(b), bin(bit_screen_serves(b)) {}
+  explicit BitmapScan(hny_builder *b)
+      : b(b), bin(bit_screen_serves(b)), split(b->screen_precision == HNY_SCREEN_BF16X3 && screen_serves(b)) {}
   int begin(uint32_t qblock) {
     if (bin) {
       HIP_TRY(dqpop.alloc(qblock));
@@ -5539,7 +5570,8 @@ struct BitmapScan {
     }
     if (int rc = ensure_row_n2(b)) return rc;
     HIP_TRY(dqn2.alloc(qblock));
-    screen_consts(b->g.n16, s);
+    if (split) screen_consts_split(b->g.n16, s);
+    else screen_consts(b->g.n16, s);
     s.row_n2 = b->d_row_n2.p;
     s.q_n2 = dqn2.p;
     return HNY_OK;
@@ -5552,6 +5584,7 @@ struct BitmapScan {
   }
   hipError_t produce(const ExactArgs &a, const ScreenRangeArgs &bits) {
     if (bin) return hnyk_screen_range_bits(b->g, a, dqpop.p, bits, b->stream);
+    if (split) return hnyk_screen_range_split(b->g, a, s, bits, b->stream);
     return hnyk_screen_range(b->g, a, s, bits, b->stream);
   }
 };

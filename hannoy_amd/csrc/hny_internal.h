@@ -794,6 +794,11 @@ struct ScreenRangeArgs {
 };
 hipError_t hnyk_screen_range(const GraphDev &g, const ExactArgs &a, const ScreenArgs &s, const ScreenRangeArgs &b,
                              hipStream_t st);
+// The split-bf16 producer of the same bitmaps (hny_builder_set_screen_precision):
+// k_screen_range_split is k_screen_range with its dot products from v_mfma_f32_32x32x16_bf16 on two bf16 halves of
+// every f32 (hi hi + hi lo + lo hi); `s` carries the constants of that scan's bound (screen_consts_split)
+hipError_t hnyk_screen_range_split(const GraphDev &g, const ExactArgs &a, const ScreenArgs &s,
+                                   const ScreenRangeArgs &b, hipStream_t st);
 // The bit metrics' producer of the same bitmaps (hny_builder_set_bit_screen): k_screen_range_bits
 // gets popcount(q ^ r) - popcount(q) from v_mfma_i32_32x32x32_i8, adds q_pop[query] and compares the index's own
 // distance with the radius: certain = d <= r, cand = certain or a NaN d.  Metrics 3 .. 6 only

@@ -216,6 +216,80 @@ __global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_screen_scores(GraphDe
   }
 }
 
+// ---- the split-bf16 producer of the same dot products: v_mfma_f32_32x32x16_bf16 on two bf16
+// halves of every f32.  hi = bf16(x), lo = bf16(x - hi) (the subtraction is exact in f32), and
+//   dot~ = sum  hi_q hi_r + hi_q lo_r + lo_q hi_r,
+// three MFMAs per 16 dimensions into ONE accumulator per block.  A product of two bf16 is exact in f32, so only the
+// additions round; lo_q lo_r and the two remainders x - hi - lo are part of the bound (screen_consts_split).
+// Lane (j, h) of step s stands for the dimensions 16 s + 8 h .. + 7 of its row and of its two queries: two 16-byte
+// units from HBM, split in registers into two bf16x8 operands.  Both operands of an MFMA hold the same eight
+// dimensions in the same order, so the k index the hardware gives an element does not matter.
+// Queries: split once per workgroup and K panel into LDS in operand order, per (query, group of 8 dimensions) 16 B of
+// hi, then 16 B of lo: a panel of 128 dimensions is the 512 B per query of screen_dots with the same padding, and an
+// A operand is one ds_read_b128.
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x8 __attribute__((ext_vector_type(8)));
+
+// the conversion is LLVM's fptrunc, round to nearest even (v_cvt_pk_bf16_f32 on gfx950); an infinite hi (|x| near
+// FLT_MAX) or a NaN leaves a dot product that is not finite: an uncertain pair
+__device__ __forceinline__ void split_bf16(const float4 &a, const float4 &b, bf16x8 &hi, bf16x8 &lo) {
+  const f32x8 x = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+  hi = __builtin_convertvector(x, bf16x8);
+  lo = __builtin_convertvector(x - __builtin_convertvector(hi, f32x8), bf16x8);
+}
+
+// screen_dots on the split halves: the same loop structure, panels, barriers and accumulator layout
+__device__ __forceinline__ void screen_dots_split(const GraphDev &g, const ExactArgs &a, const ScreenLds &L, u32 q0,
+                                                  u32 nqt, bool first, const unsigned char *rp, bool valid,
+                                                  f32x16 &acc0, f32x16 &acc1) {
+  const u32 tid = threadIdx.x, ln = tid & 63u, j = ln & 31u, h = ln >> 5, n16 = g.n16;
+  const bool one_panel = n16 <= HNY_SCREEN_KP;
+  bf16x8 *qpan = reinterpret_cast<bf16x8 *>(L.qpan);
+  const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int i = 0; i < 16; i++) acc0[i] = 0.f, acc1[i] = 0.f;
+  for (u32 u0 = 0; u0 < n16; u0 += HNY_SCREEN_KP) {
+    if (!one_panel || first) {
+      __syncthreads(); // the panel before is read
+      for (u32 i = tid; i < HNY_SCREEN_QT * (HNY_SCREEN_KP / 2u); i += 256u) {
+        const u32 qi = i / (HNY_SCREEN_KP / 2u), f = i % (HNY_SCREEN_KP / 2u), u = u0 + 2u * f;
+        float4 va = zero, vb = zero;
+        if (qi < nqt && u < n16) {
+          const unsigned char *src = a.q_slots ? g.rows + (size_t)a.q_slots[q0 + qi] * g.row_stride
+                                               : a.q_rows + (size_t)(q0 + qi) * a.q_stride;
+          va = *reinterpret_cast<const float4 *>(src + (size_t)u * 16);
+          if (u + 1u < n16) vb = *reinterpret_cast<const float4 *>(src + (size_t)(u + 1u) * 16);
+        }
+        bf16x8 hi, lo;
+        split_bf16(va, vb, hi, lo);
+        qpan[qi * HNY_SCREEN_PSTRIDE + 2u * f] = hi;
+        qpan[qi * HNY_SCREEN_PSTRIDE + 2u * f + 1u] = lo;
+      }
+      __syncthreads();
+    }
+    const u32 units = n16 - u0 < HNY_SCREEN_KP ? n16 - u0 : HNY_SCREEN_KP;
+    const u32 steps = (units + 3u) / 4u;
+    for (u32 st = 0; st < steps; st++) {
+      const u32 f = 2u * st + h, u = u0 + 2u * f; // f < HNY_SCREEN_KP / 2: staged, zero from n16 on
+      float4 ra = zero, rb = zero;
+      if (valid && u < n16) {
+        ra = *reinterpret_cast<const float4 *>(rp + (size_t)u * 16);
+        if (u + 1u < n16) rb = *reinterpret_cast<const float4 *>(rp + (size_t)(u + 1u) * 16);
+      }
+      bf16x8 rh, rl;
+      split_bf16(ra, rb, rh, rl);
+      const bf16x8 *qa = qpan + j * HNY_SCREEN_PSTRIDE + 2u * f, *qb = qpan + (32u + j) * HNY_SCREEN_PSTRIDE + 2u * f;
+      const bf16x8 ah = qa[0], al = qa[1], bh = qb[0], bl = qb[1];
+      acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, rh, acc0, 0, 0, 0); // the small terms first
+      acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bl, rh, acc1, 0, 0, 0);
+      acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, rl, acc0, 0, 0, 0);
+      acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh, rl, acc1, 0, 0, 0);
+      acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, rh, acc0, 0, 0, 0);
+      acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh, rh, acc1, 0, 0, 0);
+    }
+  }
+}
+
 // The fused scan of the screened range search: k_screen_scores' split and inner loop; the epilogue
 // forms both ends of every pair's interval from the one accumulator value, compares them with the query's radius and
 // votes.  Accumulator register i holds one query in lanes 0 .. 31 and another in lanes 32 .. 63, the lane's row being
@@ -223,12 +297,13 @@ __global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_screen_scores(GraphDe
 // of these metrics are >= +0 or the NaN, so with an uncertain pair as [0, NaN]:
 //   certain  d_hi <= r   (never for the NaN end: d <= d_hi <= r, a hit whatever the row holds)
 //   cand     d_lo <= r   (false for a NaN radius and where r < d_lo <= d: no hit; -0.0 compares as 0)
-// Rows at and beyond the chunk's end vote 0; the call's slot mask is left to the consumer (k_range_settle)
-template <bool L2>
-__global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_screen_range(GraphDev g, ExactArgs a, ScreenArgs s,
-                                                                         ScreenRangeArgs b) {
-  HNY_SCREEN_LDS(L);
-  __shared__ float s_r[HNY_SCREEN_QT];
+// Rows at and beyond the chunk's end vote 0; the call's slot mask is left to the consumer (k_range_settle).
+// k_screen_range and k_screen_range_split are this one body: SPLIT chooses the producer of the accumulators, and `s`
+// carries that producer's constants.  (The arguments come by value, as the kernels hold them: by reference the
+// compiler schedules k_screen_range's epilogue differently.)
+template <bool L2, bool SPLIT>
+__device__ __forceinline__ void screen_range_body(const GraphDev g, const ExactArgs a, const ScreenArgs s,
+                                                  const ScreenRangeArgs b, const ScreenLds L, float *s_r) {
   const u32 tid = threadIdx.x;
   const u32 q0 = blockIdx.x * HNY_SCREEN_QT;
   const u32 nqt = a.nq - q0 < HNY_SCREEN_QT ? a.nq - q0 : HNY_SCREEN_QT;
@@ -242,7 +317,9 @@ __global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_screen_range(GraphDev
     const u32 row = p0 + wave * 32u + j;
     const bool valid = row < c1;
     f32x16 acc0, acc1;
-    screen_dots(g, a, L, q0, nqt, p0 == c0, g.rows + (size_t)(valid ? row : c0) * g.row_stride, valid, acc0, acc1);
+    const unsigned char *rp = g.rows + (size_t)(valid ? row : c0) * g.row_stride;
+    if constexpr (SPLIT) screen_dots_split(g, a, L, q0, nqt, p0 == c0, rp, valid, acc0, acc1);
+    else screen_dots(g, a, L, q0, nqt, p0 == c0, rp, valid, acc0, acc1);
     float rn = 0.f, r2 = 0.f;
     if (valid) {
       rn = g.norms ? g.norms[row] : 0.f;
@@ -279,6 +356,20 @@ __global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_screen_range(GraphDev
       }
     }
   }
+}
+template <bool L2>
+__global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_screen_range(GraphDev g, ExactArgs a, ScreenArgs s,
+                                                                         ScreenRangeArgs b) {
+  HNY_SCREEN_LDS(L);
+  __shared__ float s_r[HNY_SCREEN_QT];
+  screen_range_body<L2, false>(g, a, s, b, L, s_r);
+}
+template <bool L2>
+__global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_screen_range_split(GraphDev g, ExactArgs a, ScreenArgs s,
+                                                                               ScreenRangeArgs b) {
+  HNY_SCREEN_LDS(L);
+  __shared__ float s_r[HNY_SCREEN_QT];
+  screen_range_body<L2, true>(g, a, s, b, L, s_r);
 }
 
 // ---- the bit metrics' producer of the same bitmaps: k_screen_range's split on the integer matrix
@@ -545,6 +636,17 @@ hipError_t hnyk_screen_range(const GraphDev &g, const ExactArgs &a, const Screen
   const dim3 grid((a.nq + HNY_SCREEN_QT - 1) / HNY_SCREEN_QT, (a.slab_n + HNY_EXACT_CHUNK - 1) / HNY_EXACT_CHUNK);
   if (g.metric == 1) hipLaunchKernelGGL(k_screen_range<true>, grid, dim3(256), 0, st, g, a, s, b);
   else hipLaunchKernelGGL(k_screen_range<false>, grid, dim3(256), 0, st, g, a, s, b);
+  return hipGetLastError();
+}
+
+hipError_t hnyk_screen_range_split(const GraphDev &g, const ExactArgs &a, const ScreenArgs &s,
+                                   const ScreenRangeArgs &b, hipStream_t st) {
+  if (!a.nq || !a.slab_n) return hipSuccess;
+  if (g.metric != 0 && g.metric != 1) return hipErrorInvalidValue; // Cosine and Euclidean only: no silent other path
+  if (a.slab_n > HNY_EXACT_SLAB || a.slab_base % HNY_EXACT_CHUNK) return hipErrorInvalidValue; // the bitmaps' stride
+  const dim3 grid((a.nq + HNY_SCREEN_QT - 1) / HNY_SCREEN_QT, (a.slab_n + HNY_EXACT_CHUNK - 1) / HNY_EXACT_CHUNK);
+  if (g.metric == 1) hipLaunchKernelGGL(k_screen_range_split<true>, grid, dim3(256), 0, st, g, a, s, b);
+  else hipLaunchKernelGGL(k_screen_range_split<false>, grid, dim3(256), 0, st, g, a, s, b);
   return hipGetLastError();
 }
 

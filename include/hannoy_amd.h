@@ -474,6 +474,17 @@ int hny_builder_exact_vote_times(const hny_builder *b, double *out_ms);
  * (which keeps routing the bit metrics) or on hny_builder_exact_screen_bounds (which keeps refusing them).
  * b == NULL: HNY_ERR_INVALID_ARG */
 int hny_builder_set_bit_screen(hny_builder *b, int on);
+/* The precision of the matrix-core scan behind hny_builder_exact_range_screened, hny_builder_exact_range_count_screened,
+ * hny_builder_exact_knn_voted and their _f32 forms on a Cosine or Euclidean builder in wave order, per builder.
+ * HNY_SCREEN_F32 (the default): dot products on the f32 matrix instruction.  HNY_SCREEN_BF16X3: every f32 is split
+ * into two bf16 halves, hi = bf16(x) and lo = bf16(x - hi), and the scan sums hi hi + hi lo + lo hi on the bf16 matrix
+ * instruction; what that leaves out widens each pair's interval by about 3 * 2^-16 of |q| |r|, a few more pairs are
+ * settled on the f32 rows, and results and refusals stay those of the plain calls, byte for byte.  Accepted on any
+ * builder; no effect on other metrics, strict-mode builders, hny_builder_exact_knn_screened or
+ * hny_builder_exact_screen_bounds, which keep the f32 scan.  b == NULL or another mode: HNY_ERR_INVALID_ARG */
+#define HNY_SCREEN_F32 0
+#define HNY_SCREEN_BF16X3 1
+int hny_builder_set_screen_precision(hny_builder *b, int mode);
 
 /* ---- batched search with one `.candidates()` filter per query: the reference's filter belongs to one query
  * (src/reader.rs:200-203), so a batch that serves several requests carries several.
