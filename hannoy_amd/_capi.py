@@ -62,6 +62,7 @@ EXPORTED = [
     "hny_builder_exact_range_screen_stats", "hny_builder_exact_range_screen_times",
     "hny_builder_exact_knn_voted", "hny_builder_exact_knn_voted_f32", "hny_builder_exact_vote_stats",
     "hny_builder_exact_vote_times", "hny_builder_set_bit_screen", "hny_builder_set_screen_precision",
+    "hny_builder_set_l1_screen",
 ]
 ERR_IO = -9
 SCREEN_PRECISIONS = {"f32": 0, "bf16x3": 1}  # HNY_SCREEN_F32, HNY_SCREEN_BF16X3
@@ -370,6 +371,8 @@ def load_library():
     L.hny_builder_set_profiling.argtypes = [vp, C.c_int]
     L.hny_builder_set_bit_screen.restype = C.c_int
     L.hny_builder_set_bit_screen.argtypes = [vp, C.c_int]
+    L.hny_builder_set_l1_screen.restype = C.c_int
+    L.hny_builder_set_l1_screen.argtypes = [vp, C.c_int]
     L.hny_builder_set_screen_precision.restype = C.c_int
     L.hny_builder_set_screen_precision.argtypes = [vp, C.c_int]
     L.hny_builder_next_batch.restype = C.c_int
@@ -1509,6 +1512,12 @@ class Builder:
         of a Hamming or binary-quantized builder in wave order scan on the matrix cores (k_screen_range_bits) and
         no longer count as routed.  Off by default; no effect on other builders"""
         _check(load_library().hny_builder_set_bit_screen(self._h, int(on)))
+
+    def set_l1_screen(self, on=True):
+        """hny_builder_set_l1_screen: exact_range / exact_range_count(screened=True) and exact_knn(screened="votes")
+        of a Manhattan builder in wave order scan with the tiled VALU kernel (k_screen_range_l1) and no longer count
+        as routed.  Off by default; no effect on other builders"""
+        _check(load_library().hny_builder_set_l1_screen(self._h, int(on)))
 
     def set_screen_precision(self, mode):
         """hny_builder_set_screen_precision, mode "f32" (the default) or "bf16x3": exact_range / exact_range_count

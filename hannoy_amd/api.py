@@ -1000,6 +1000,12 @@ class Reader:
         instead of running the plain calls; the same results"""
         self._b.set_bit_screen(on)
 
+    def set_l1_screen(self, on=True):
+        """Builder.set_l1_screen of the reader's builder: on a Manhattan index, .within(r).exact(screened=True) and
+        .exact(screened="votes") then scan with the tiled VALU kernel instead of running the plain calls; the same
+        results"""
+        self._b.set_l1_screen(on)
+
     def set_screen_precision(self, mode):
         """Builder.set_screen_precision of the reader's builder: "bf16x3" runs the matrix-core scan of
         .within(r).exact(screened=True) and .exact(screened="votes") of a Cosine or Euclidean index on split bf16

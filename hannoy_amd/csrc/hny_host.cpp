@@ -465,6 +465,7 @@ struct hny_builder {
   bool profiling = false;
   int screen_precision = 0; // hny_builder_set_screen_precision: HNY_SCREEN_F32 or HNY_SCREEN_BF16X3
   bool bit_screen = false; // hny_builder_set_bit_screen: the bit metrics take the matrix-core scan
+  bool l1_screen = false;  // hny_builder_set_l1_screen: Manhattan takes the bitmap scan
   uint64_t n_walk_dispatch = 0; // k_walk launches since the last reset
   uint64_t exact_rows_read = 0; // hny_builder_exact_rows_read: the last hny_builder_exact_knn_filtered call's
   // filters as bitsets over item ids (FilterRounds::build_from_id_bits), made by the first such call:
@@ -2529,6 +2530,12 @@ int hny_builder_set_profiling(hny_builder *b, int on) {
 int hny_builder_set_bit_screen(hny_builder *b, int on) {
   if (!b) return fail(HNY_ERR_INVALID_ARG, "null builder");
   b->bit_screen = on != 0;
+  return HNY_OK;
+}
+
+int hny_builder_set_l1_screen(hny_builder *b, int on) {
+  if (!b) return fail(HNY_ERR_INVALID_ARG, "null builder");
+  b->l1_screen = on != 0;
   return HNY_OK;
 }
 
@@ -5530,6 +5537,20 @@ static void screen_consts_split(uint32_t n16, ScreenArgs &s) {
   s.a_abs = f32_up((7 * K + 8) * tiny);
   s.a_flush = f32_up(5 * std::sqrt(K) * tiny);
 }
+// The constants of k_screen_range_l1's bound.  The exact kernel's sum D and the scan's S~ are f32
+// sums of the same K terms |fl(q_i - r_i)| >= 0 in two orders.  A summation tree over K leaves rounds at most K - 1
+// times on the way of any leaf (an addition of +0 is exact), and all terms have one sign, so with S the real sum both
+// lie in S [(1 - u)^(K-1), (1 + u)^(K-1)], u = 2^-24: D / S~ is within rho^+-1, rho = ((1 + u) / (1 - u))^(K-1), and
+// 1 / rho >= 1 - (rho - 1).  Under a flush of subnormal results every addition of either sum may drop less than
+// 2^-126: at most K 2^-126 per sum, 2 K rho together.  finalize_f32 adds nothing for MC_L1 (a NaN stays a NaN, which
+// the scan calls uncertain).  The bound's own product and sum are covered by below / above in the kernel
+static void screen_consts_l1(uint32_t n16, ScreenL1Args &s) {
+  const double K = 4.0 * n16, u = std::ldexp(1.0, -24), tiny = std::ldexp(1.0, -126);
+  const double c = 1.02 * std::expm1((K - 1) * (std::log1p(u) - std::log1p(-u)));
+  s.m_hi = f32_up(1.0 + c);
+  s.m_lo = -f32_up(-(1.0 - c));
+  s.a_abs = f32_up(1.02 * (2 * K + 8) * tiny);
+}
 static bool screen_serves(const hny_builder *b) {
   return (b->g.metric == HNY_COSINE || b->g.metric == HNY_EUCLIDEAN) && !b->g.x86_order;
 }
@@ -5538,7 +5559,13 @@ static bool screen_serves(const hny_builder *b) {
 static bool bit_screen_serves(const hny_builder *b) {
   return b->bit_screen && b->g.metric >= HNY_HAMMING && b->g.mclass == MC_BIN && !b->g.x86_order;
 }
-static bool bitmaps_serve(const hny_builder *b) { return screen_serves(b) || bit_screen_serves(b); }
+// Manhattan's scan (k_screen_range_l1): opted into per builder, bitmaps only as the bit scan
+static bool l1_screen_serves(const hny_builder *b) {
+  return b->l1_screen && b->g.metric == HNY_MANHATTAN && !b->g.x86_order;
+}
+static bool bitmaps_serve(const hny_builder *b) {
+  return screen_serves(b) || bit_screen_serves(b) || l1_screen_serves(b);
+}
 static int ensure_row_n2(hny_builder *b) {
   if (b->d_row_n2.p) return HNY_OK;
   HIP_TRY(b->d_row_n2.alloc(b->n));
@@ -5554,16 +5581,23 @@ static hipError_t screen_query_n2(hny_builder *b, const ExactArgs &a, float *out
 // f32 builder: k_screen_range with the sums of squares of rows and queries and the constants of the bounds.  A bit
 // builder (bit_screen_serves): k_screen_range_bits with the popcounts of the queries and nothing per row.  An f32
 // builder under HNY_SCREEN_BF16X3 (hny_builder_set_screen_precision): k_screen_range_split, the same sums of squares
-// and that scan's own constants
+// and that scan's own constants.  A Manhattan builder (l1_screen_serves): k_screen_range_l1 with its three constants
+// and nothing per row or per query
 struct BitmapScan {
   hny_builder *b;
-  bool bin, split;
+  bool bin, split, l1;
   ScreenArgs s{};
+  ScreenL1Args s1{};
   DevBuf<float> dqn2;
   DevBuf<u32> dqpop;
   explicit BitmapScan(hny_builder *b)
-      : b(b), bin(bit_screen_serves(b)), split(b->screen_precision == HNY_SCREEN_BF16X3 && screen_serves(b)) {}
+      : b(b), bin(bit_screen_serves(b)), split(b->screen_precision == HNY_SCREEN_BF16X3 && screen_serves(b)),
+        l1(l1_screen_serves(b)) {}
   int begin(uint32_t qblock) {
+    if (l1) {
+      screen_consts_l1(b->g.n16, s1);
+      return HNY_OK;
+    }
     if (bin) {
       HIP_TRY(dqpop.alloc(qblock));
       return HNY_OK;
@@ -5578,11 +5612,13 @@ struct BitmapScan {
   }
   // per block or run: the sums of the queries DenseScan aims at
   hipError_t query_sums(const ExactArgs &a) {
+    if (l1) return hipSuccess;
     if (!bin) return screen_query_n2(b, a, dqn2.p);
     if (a.q_slots) return hnyk_screen_pop(b->g.rows, b->g.row_stride, b->g.n16, a.q_slots, a.nq, dqpop.p, b->stream);
     return hnyk_screen_pop(a.q_rows, a.q_stride, b->g.n16, nullptr, a.nq, dqpop.p, b->stream);
   }
   hipError_t produce(const ExactArgs &a, const ScreenRangeArgs &bits) {
+    if (l1) return hnyk_screen_range_l1(b->g, a, s1, bits, b->stream);
     if (bin) return hnyk_screen_range_bits(b->g, a, dqpop.p, bits, b->stream);
     if (split) return hnyk_screen_range_split(b->g, a, s, bits, b->stream);
     return hnyk_screen_range(b->g, a, s, bits, b->stream);
@@ -6539,7 +6575,8 @@ int hny_builder_exact_range_f32(hny_builder *b, const hny_range_opts *ro, uint64
 }
 
 // Screened exact range search: range_impl with RangeScreen where a producer of bitmaps serves the
-// builder (Cosine and Euclidean in wave order; the bit metrics after hny_builder_set_bit_screen, §3d-8); every other
+// builder (Cosine and Euclidean in wave order; the bit metrics after hny_builder_set_bit_screen, §3d-8; Manhattan
+// after hny_builder_set_l1_screen, §3d-10); every other
 // builder takes range_impl as it is and its queries count as routed
 static int range_screened_impl(hny_builder *b, const hny_range_opts *ro, uint64_t nq, const void *qvectors, size_t qstride,
                                const void *qheaders, const uint32_t *query_items, bool q_f32, uint64_t *out_counts,

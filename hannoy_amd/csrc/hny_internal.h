@@ -807,6 +807,17 @@ hipError_t hnyk_screen_range_bits(const GraphDev &g, const ExactArgs &a, const u
 // out[i] = popcount of the n16 units of row idx[i] (null: row i) of n rows `stride` bytes apart
 hipError_t hnyk_screen_pop(const unsigned char *rows, u32 stride, u32 n16, const u32 *idx, u32 n, u32 *out,
                            hipStream_t st);
+// Manhattan's producer of the same bitmaps (hny_builder_set_l1_screen): k_screen_range_l1 is a
+// tiled VALU scan, S~ = sum |q_i - r_i| with the exact kernel's terms in another order.  The exact distance D lies in
+// [S~ m_lo - a_abs, S~ m_hi + a_abs] (screen_consts_l1); a NaN or overflowed S~ is uncertain.  Nothing per row or per
+// query but the rows themselves.  Metric 2 only
+struct ScreenL1Args {
+  float m_lo;  // 1 - c_l1, rounded down
+  float m_hi;  // 1 + c_l1, rounded up; c_l1 = 1.02 (((1 + u) / (1 - u))^(K - 1) - 1), u = 2^-24, K = 4 * n16
+  float a_abs; // 1.02 (2 K + 8) 2^-126: partial sums of either kernel a flush may have dropped
+};
+hipError_t hnyk_screen_range_l1(const GraphDev &g, const ExactArgs &a, const ScreenL1Args &s, const ScreenRangeArgs &b,
+                                hipStream_t st);
 // k_range_settle (hny_kernels.hip, next to dist_rows): the consumer of a slab's bitmaps, one workgroup per query.
 // Under the mask it counts the certain pairs, lists the pairs to settle in slot order (emit == 0: cand & ~certain,
 // emit != 0: cand), computes their exact distances on the f32 rows and keeps those with d <= r.

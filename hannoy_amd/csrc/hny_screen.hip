@@ -535,6 +535,139 @@ __global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_screen_range_bits(Gra
   }
 }
 
+// ---- Manhattan's producer of the same bitmaps (hny_builder_set_l1_screen): an L1 sum has no matrix
+// form, so this scan is a tiled VALU kernel.  S~ = sum |fl(q_i - r_i)| has the very terms of partial_f32 (the plain
+// IEEE subtraction, no contraction), summed in another order; every term is >= 0, so the exact kernel's sum D lies in
+// S~ [1 - c, 1 + c] whatever the values are (screen_consts_l1), and finalize_f32 adds nothing to a sum that is no NaN.
+// Work split.  256 threads, four waves; a chunk of HNY_EXACT_CHUNK slots gives each wave 128 consecutive slots.  Lane l
+// owns the rows l and 64 + l of its wave's span (lane = slot): the ballot of one (query, r) is 64 consecutive slots,
+// two finished words at (c0 - slab_base) / 32 + 4 wave + 2 r, which lane 0 stores.
+// Rows: HBM -> registers in 16-byte units, one row per lane, the next unit's loads issued ahead of the arithmetic.
+// Queries are wave-uniform: a step is one group of HNY_L1_QG queries and one K panel of HNY_SCREEN_KP units, staged
+// in LDS between two barriers (a step is tens of thousands of VALU operations long).  The inner loop reads a
+// (query, unit) with one uniform-address ds_read_b128 — a broadcast — and uses it for both rows: 16 VALU operations
+// per LDS read.  Accumulators: HNY_L1_QG x 2.  A wave reads its rows once per group, and a chunk's rows (512 x the row
+// bytes per workgroup, tens of workgroups per L2) do not stay in the L2 between groups: the group is the whole tile,
+// so every workgroup reads its rows once (a group of 8 was measured: the scan then moves the rows eight times and
+// runs at the plain call's speed).  Groups of eight queries beyond the tile's last are skipped, wave-uniformly.
+// Zero fill, never a read: units at and beyond n16 (the loops end there), rows at and beyond the chunk's end, queries
+// beyond the tile's.
+#define HNY_L1_QG 64u // queries per group: 128 accumulators per lane
+static_assert(HNY_SCREEN_QT % HNY_L1_QG == 0u && HNY_L1_QG % 8u == 0u, "whole groups, whole eights");
+
+__device__ __forceinline__ void l1_unit(float (&acc)[HNY_L1_QG][2], const float4 *qp, u32 nqg, const float4 &r0,
+                                        const float4 &r1) {
+#pragma unroll
+  for (u32 i0 = 0; i0 < HNY_L1_QG; i0 += 8u) {
+    if (i0 < nqg) {
+#pragma unroll
+      for (u32 i = i0; i < i0 + 8u; i++) {
+        const float4 q = qp[i * HNY_SCREEN_KP];
+        acc[i][0] = acc[i][0] + __builtin_fabsf(q.x - r0.x);
+        acc[i][1] = acc[i][1] + __builtin_fabsf(q.x - r1.x);
+        acc[i][0] = acc[i][0] + __builtin_fabsf(q.y - r0.y);
+        acc[i][1] = acc[i][1] + __builtin_fabsf(q.y - r1.y);
+        acc[i][0] = acc[i][0] + __builtin_fabsf(q.z - r0.z);
+        acc[i][1] = acc[i][1] + __builtin_fabsf(q.z - r1.z);
+        acc[i][0] = acc[i][0] + __builtin_fabsf(q.w - r0.w);
+        acc[i][1] = acc[i][1] + __builtin_fabsf(q.w - r1.w);
+      }
+    }
+  }
+}
+
+// Epilogue, per accumulator S~: a NaN or a sum at or beyond HNY_SCREEN_BIG makes the pair uncertain, cand = 0 <= r and
+// never certain, as the f32 producers treat an overflowed bound.  Otherwise D >= S~ m_lo - a_abs and D <= S~ m_hi +
+// a_abs; below / above cover the product's and the sum's rounding.  S~ == r is a candidate and never certain
+// (the subtraction is not packed into v_pk_add_f32: that form has no |x| modifier, so the pair costs two v_and more
+// than it saves; the body is a function of its own because a kernel that carries the target attribute inlines
+// nothing that does not)
+__device__ __forceinline__ void screen_range_l1_body(const GraphDev g, const ExactArgs a, const ScreenL1Args s,
+                                                     const ScreenRangeArgs b, float4 *s_q, float *s_r) {
+  const u32 tid = threadIdx.x, ln = tid & 63u, wave = tid >> 6, n16 = g.n16;
+  const u32 q0 = blockIdx.x * HNY_SCREEN_QT;
+  const u32 nqt = a.nq - q0 < HNY_SCREEN_QT ? a.nq - q0 : HNY_SCREEN_QT;
+  const u32 slab_end = a.slab_base + a.slab_n;
+  const u32 c0 = a.slab_base + blockIdx.y * HNY_EXACT_CHUNK;
+  const u32 c1 = slab_end - c0 < HNY_EXACT_CHUNK ? slab_end : c0 + HNY_EXACT_CHUNK;
+  if (tid < HNY_SCREEN_QT) s_r[tid] = tid < nqt ? b.radius[q0 + tid] : 0.f; // published by the first step's barrier
+  const u32 row0 = c0 + wave * 128u + ln, row1 = row0 + 64u;
+  // a row at or beyond the chunk's end is not read: its lane reads row c0 again and votes 0; a wave wholly beyond
+  // the end reads nothing
+  const bool valid0 = row0 < c1, valid1 = row1 < c1, wave_on = c0 + wave * 128u < c1;
+  const unsigned char *rp0 = g.rows + (size_t)(valid0 ? row0 : c0) * g.row_stride;
+  const unsigned char *rp1 = g.rows + (size_t)(valid1 ? row1 : c0) * g.row_stride;
+  const u32 word = (c0 - a.slab_base) / 32u + 4u * wave; // + 3 < HNY_SCREEN_BITS_STRIDE: the chunk lies within the slab
+  const u32 npanels = (n16 + HNY_SCREEN_KP - 1u) / HNY_SCREEN_KP;
+  const u32 steps = ((nqt + HNY_L1_QG - 1u) / HNY_L1_QG) * npanels; // the same trips for every wave
+  float acc[HNY_L1_QG][2];
+  for (u32 step = 0; step < steps; step++) {
+    const u32 g0 = (step / npanels) * HNY_L1_QG, pan = step % npanels, u0 = pan * HNY_SCREEN_KP;
+    const u32 nqg = nqt - g0 < HNY_L1_QG ? nqt - g0 : HNY_L1_QG;
+    if (step) __syncthreads(); // the panel before is read
+    for (u32 i = tid; i < HNY_L1_QG * HNY_SCREEN_KP; i += 256u) { // [query of the group][unit of the panel]
+      const u32 qi = g0 + i / HNY_SCREEN_KP, u = u0 + i % HNY_SCREEN_KP;
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (qi < nqt && u < n16) {
+        const unsigned char *src = a.q_slots ? g.rows + (size_t)a.q_slots[q0 + qi] * g.row_stride
+                                             : a.q_rows + (size_t)(q0 + qi) * a.q_stride;
+        v = *reinterpret_cast<const float4 *>(src + (size_t)u * 16);
+      }
+      s_q[i] = v;
+    }
+    __syncthreads();
+    if (pan == 0u) {
+#pragma unroll
+      for (u32 i = 0; i < HNY_L1_QG; i++) acc[i][0] = 0.f, acc[i][1] = 0.f;
+    }
+    if (wave_on) {
+      const u32 units = n16 - u0 < HNY_SCREEN_KP ? n16 - u0 : HNY_SCREEN_KP;
+      float4 r0 = *reinterpret_cast<const float4 *>(rp0 + (size_t)u0 * 16);
+      float4 r1 = *reinterpret_cast<const float4 *>(rp1 + (size_t)u0 * 16);
+      for (u32 f = 0; f + 1u < units; f++) {
+        const float4 n0 = *reinterpret_cast<const float4 *>(rp0 + (size_t)(u0 + f + 1u) * 16);
+        const float4 n1 = *reinterpret_cast<const float4 *>(rp1 + (size_t)(u0 + f + 1u) * 16);
+        l1_unit(acc, s_q + f, nqg, r0, r1);
+        r0 = n0, r1 = n1;
+      }
+      l1_unit(acc, s_q + (units - 1u), nqg, r0, r1);
+    }
+    if (pan + 1u == npanels) {
+#pragma unroll
+      for (u32 i = 0; i < HNY_L1_QG; i++) {
+        const u32 qi = g0 + i;
+        const float r = s_r[qi];
+#pragma unroll
+        for (u32 rr = 0; rr < 2u; rr++) {
+          const float sum = acc[i][rr];
+          bool cand = false, certain = false;
+          if ((rr ? valid1 : valid0) && qi < nqt) {
+            if (!(sum < HNY_SCREEN_BIG)) {
+              cand = 0.f <= r;
+            } else {
+              const float lo = below(sum * s.m_lo) - s.a_abs;
+              cand = (lo > 0.f ? lo : 0.f) <= r;
+              certain = above(sum * s.m_hi + s.a_abs) <= r;
+            }
+          }
+          const u64 vc = ballot(cand), vh = ballot(certain);
+          if (ln == 0u && qi < nqt) {
+            const size_t at = (size_t)(q0 + qi) * HNY_SCREEN_BITS_STRIDE + word + 2u * rr;
+            b.cand[at] = (u32)vc, b.cand[at + 1u] = (u32)(vc >> 32);
+            b.certain[at] = (u32)vh, b.certain[at + 1u] = (u32)(vh >> 32);
+          }
+        }
+      }
+    }
+  }
+}
+__global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_screen_range_l1(GraphDev g, ExactArgs a, ScreenL1Args s,
+                                                                            ScreenRangeArgs b) {
+  __shared__ float4 s_q[HNY_L1_QG * HNY_SCREEN_KP];
+  __shared__ float s_r[HNY_SCREEN_QT];
+  screen_range_l1_body(g, a, s, b, s_q, s_r);
+}
+
 // popcount of the units 0 .. n16 - 1 of a row, the bits partial_bin counts; eight lanes per row as k_screen_n2
 __global__ __launch_bounds__(256) void k_screen_pop(const unsigned char *rows, u32 stride, u32 n16, const u32 *idx, u32 n,
                                                     u32 *out) {
@@ -670,5 +803,15 @@ hipError_t hnyk_screen_range_bits(const GraphDev &g, const ExactArgs &a, const u
     case 5: hipLaunchKernelGGL(k_screen_range_bits<5>, grid, dim3(256), 0, st, g, a, q_pop, b); break;
     default: hipLaunchKernelGGL(k_screen_range_bits<6>, grid, dim3(256), 0, st, g, a, q_pop, b); break;
   }
+  return hipGetLastError();
+}
+
+hipError_t hnyk_screen_range_l1(const GraphDev &g, const ExactArgs &a, const ScreenL1Args &s, const ScreenRangeArgs &b,
+                                hipStream_t st) {
+  if (!a.nq || !a.slab_n) return hipSuccess;
+  if (g.metric != 2 || g.mclass != MC_L1 || !g.n16) return hipErrorInvalidValue; // Manhattan only: no silent other path
+  if (a.slab_n > HNY_EXACT_SLAB || a.slab_base % HNY_EXACT_CHUNK) return hipErrorInvalidValue; // the bitmaps' stride
+  const dim3 grid((a.nq + HNY_SCREEN_QT - 1) / HNY_SCREEN_QT, (a.slab_n + HNY_EXACT_CHUNK - 1) / HNY_EXACT_CHUNK);
+  hipLaunchKernelGGL(k_screen_range_l1, grid, dim3(256), 0, st, g, a, s, b);
   return hipGetLastError();
 }

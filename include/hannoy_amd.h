@@ -396,7 +396,8 @@ int hny_builder_exact_knn_f32(hny_builder *b, const hny_query_opts *opts, uint64
  * interval [d_lo, d_hi] that holds the distance of hny_builder_exact_knn; the k-th smallest d_hi of a query is a
  * threshold no smaller than its k-th exact distance; the slots with d_lo at or below it, at most 4 095 per query, are
  * ranked on the f32 rows by the kernel of hny_builder_rescore.  Every other case runs hny_builder_exact_knn itself for
- * the queries concerned ("routed"): Manhattan and the four bit metrics, strict-mode builders, candidates so few
+ * the queries concerned ("routed"): Manhattan and the four bit metrics (here hny_builder_set_l1_screen and
+ * hny_builder_set_bit_screen change nothing), strict-mode builders, candidates so few
  * that hny_builder_exact_knn gathers them, and a query with more than 4 095 slots under its threshold.
  *
  * The first screened call on a builder makes one f32 per slot (the row's sum of squares), kept until
@@ -442,8 +443,8 @@ int hny_builder_exact_screen_bounds(hny_builder *b, uint64_t n_queries, const vo
  * thresholds as its radii (a pair whose interval begins at or below the threshold is a candidate), and one workgroup
  * per query computes the candidates' exact distances on the f32 rows, merges them into the query's running top k and
  * lowers the threshold to its k-th distance for the next slab.  No score is stored, no list has a cap, nothing
- * overflows.  Routed to hny_builder_exact_knn, whole calls only: Manhattan and the four bit metrics (those until
- * hny_builder_set_bit_screen), strict-mode builders, and candidates so few that hny_builder_exact_knn gathers them.
+ * overflows.  Routed to hny_builder_exact_knn, whole calls only: Manhattan (until hny_builder_set_l1_screen) and the four bit metrics
+ * (until hny_builder_set_bit_screen), strict-mode builders, and candidates so few that hny_builder_exact_knn gathers them.
  *
  * Cancellation as hny_builder_exact_knn: probed between launches, a block that did not finish reports 0 hits.
  * Results are the same from run to run.  The row sums of squares are shared with hny_builder_exact_knn_screened. */
@@ -474,6 +475,16 @@ int hny_builder_exact_vote_times(const hny_builder *b, double *out_ms);
  * (which keeps routing the bit metrics) or on hny_builder_exact_screen_bounds (which keeps refusing them).
  * b == NULL: HNY_ERR_INVALID_ARG */
 int hny_builder_set_bit_screen(hny_builder *b, int on);
+/* Manhattan on the bitmap scan, opted into per builder (off by default).  on != 0: for a Manhattan builder in wave
+ * order, hny_builder_exact_range_screened, hny_builder_exact_range_count_screened, hny_builder_exact_knn_voted and
+ * their _f32 forms no longer route to their plain namesakes.  An L1 sum has no matrix form: the scan is a tiled
+ * vector-ALU kernel that sums the exact kernel's own terms |q_i - r_i| in another order.  All terms are >= 0, so the
+ * two sums agree to about 2 K 2^-24 relative whatever the values are; pairs whose interval holds the radius or
+ * threshold are settled on the f32 rows, the others are decided by the scan ("certain" and "settled" of the stats calls
+ * count them as for Cosine and Euclidean).  Results and refusals stay those of the plain calls, byte for byte.  No
+ * effect on other builders, on strict-mode builders, on hny_builder_exact_knn_screened (which keeps routing Manhattan)
+ * or on hny_builder_exact_screen_bounds (which keeps refusing it).  b == NULL: HNY_ERR_INVALID_ARG */
+int hny_builder_set_l1_screen(hny_builder *b, int on);
 /* The precision of the matrix-core scan behind hny_builder_exact_range_screened, hny_builder_exact_range_count_screened,
  * hny_builder_exact_knn_voted and their _f32 forms on a Cosine or Euclidean builder in wave order, per builder.
  * HNY_SCREEN_F32 (the default): dot products on the f32 matrix instruction.  HNY_SCREEN_BF16X3: every f32 is split
@@ -733,7 +744,8 @@ void hny_range_result_free(hny_range_result *r); /* NULL is fine */
  * rows, is within the radius; the hits call then settles every candidate of its queries that way, which gives the
  * distance bits of hny_builder_exact_range, and sorts them as it does.  Sound for every radius, -0.0, negative,
  * +inf and NaN included: the exact distances of the two metrics are >= +0 or the NaN.
- * Routed to the namesake, whole calls only: Manhattan and the four bit metrics (strict mode among them).
+ * Routed to the namesake, whole calls only: Manhattan (until hny_builder_set_l1_screen), the four bit metrics (until
+ * hny_builder_set_bit_screen) and strict-mode builders.
  * Memory: 16 KB of bitmaps per query of a block of at most 1 024, whatever the number of items; no score buffer.
  * The forms with one filter per query (_filtered, _bitsets) have no screened variant.
  *
