@@ -63,6 +63,8 @@ EXPORTED = [
     "hny_builder_exact_knn_voted", "hny_builder_exact_knn_voted_f32", "hny_builder_exact_vote_stats",
     "hny_builder_exact_vote_times", "hny_builder_set_bit_screen", "hny_builder_set_screen_precision",
     "hny_builder_set_l1_screen",
+    "hny_builder_exact_knn_filtered_voted", "hny_builder_exact_knn_filtered_voted_f32",
+    "hny_builder_exact_knn_bitsets_voted", "hny_builder_exact_knn_bitsets_voted_f32",
 ]
 ERR_IO = -9
 SCREEN_PRECISIONS = {"f32": 0, "bf16x3": 1}  # HNY_SCREEN_F32, HNY_SCREEN_BF16X3
@@ -506,7 +508,11 @@ def load_library():
     L.hny_builder_exact_knn_filtered.argtypes = L.hny_builder_nns_filtered.argtypes
     L.hny_builder_exact_knn_filtered_f32.restype = C.c_int
     L.hny_builder_exact_knn_filtered_f32.argtypes = L.hny_builder_nns_filtered_f32.argtypes
-    for name in ("hny_builder_nns_bitsets", "hny_builder_exact_knn_bitsets"):
+    L.hny_builder_exact_knn_filtered_voted.restype = C.c_int
+    L.hny_builder_exact_knn_filtered_voted.argtypes = L.hny_builder_nns_filtered.argtypes
+    L.hny_builder_exact_knn_filtered_voted_f32.restype = C.c_int
+    L.hny_builder_exact_knn_filtered_voted_f32.argtypes = L.hny_builder_nns_filtered_f32.argtypes
+    for name in ("hny_builder_nns_bitsets", "hny_builder_exact_knn_bitsets", "hny_builder_exact_knn_bitsets_voted"):
         fn, f32 = getattr(L, name), getattr(L, name + "_f32")
         fn.restype = f32.restype = C.c_int
         fn.argtypes = [vp, C.POINTER(QueryOpts), C.POINTER(QueryBitsets)] + L.hny_builder_nns_filtered.argtypes[3:]
@@ -790,6 +796,14 @@ def exact_method(screened):
     if isinstance(screened, str) and screened == "votes":
         return "votes"
     raise ValueError(f'screened={screened!r}: False, True or "votes"')
+
+
+def _filtered_method(name, screened):
+    """the entry point of an exact top-k search with a filter per query: `name`, or its _voted form"""
+    method = exact_method(screened)
+    if method is True:
+        raise ValueError('screened=True: the score-buffer method has no form with a filter per query; "votes" has')
+    return name + "_voted" if method == "votes" else name
 
 
 def _query_opts(k, ef_search=0, linear_below=0, linear_below_ratio=0.0, candidates=None, cancel=None):
@@ -1978,13 +1992,17 @@ class Builder:
         return self.exact_knn_filtered(filters, filter_of, qf32=_f32_rows(queries), **kw)
 
     def exact_knn_filtered(self, filters, filter_of, qcodes=None, qheaders=None, k=10, query_items=None, cancel=None,
-                           qf32=None):
+                           qf32=None, screened=False):
         """hny_builder_exact_knn_filtered: exact_knn with one .candidates() filter per query, `filters` and
         `filter_of` as in nns_filtered.  The rows of the queries of one filter equal exact_knn(candidates=that
-        filter) on those queries alone: counts[i] = min(k, live candidates of query i's filter)."""
+        filter) on those queries alone: counts[i] = min(k, live candidates of query i's filter).
+        screened="votes": the same result from hny_builder_exact_knn_filtered_voted, the voted scan with a mask, a k
+        and a pilot per query (exact_vote_stats, exact_rows_read); True is refused, the score-buffer method has no
+        form with filters."""
+        fn = _filtered_method("hny_builder_exact_knn_filtered", screened)
         opts = _query_opts(k, cancel=cancel)
         qf = QueryFilters.pack(filters, filter_of)
-        return self._search("hny_builder_exact_knn_filtered", opts,
+        return self._search(fn, opts,
                             _query_source(query_items, qf32, qcodes, qheaders), qf32 is not None, qf)
 
     def nns_bitsets_f32(self, queries, bits, n_bits, filter_of, **kw):
@@ -2006,12 +2024,14 @@ class Builder:
         return self.exact_knn_bitsets(bits, n_bits, filter_of, qf32=_f32_rows(queries), **kw)
 
     def exact_knn_bitsets(self, bits, n_bits, filter_of, qcodes=None, qheaders=None, k=10, query_items=None,
-                          cancel=None, qf32=None):
+                          cancel=None, qf32=None, screened=False):
         """hny_builder_exact_knn_bitsets: exact_knn_filtered with the filters as bitsets over item ids, `bits`,
-        `n_bits` and `filter_of` as in nns_bitsets.  Equal to exact_knn_filtered on the set bits of each filter."""
+        `n_bits` and `filter_of` as in nns_bitsets.  Equal to exact_knn_filtered on the set bits of each filter.
+        screened as in exact_knn_filtered (hny_builder_exact_knn_bitsets_voted)."""
+        fn = _filtered_method("hny_builder_exact_knn_bitsets", screened)
         opts = _query_opts(k, cancel=cancel)
         qb = QueryBitsets.pack(bits, n_bits, filter_of)
-        return self._search("hny_builder_exact_knn_bitsets", opts,
+        return self._search(fn, opts,
                             _query_source(query_items, qf32, qcodes, qheaders), qf32 is not None, qb)
 
     def _rescore_opts(self, k, n_rescore=0, ef_search=0, cancel=None):

@@ -737,8 +737,9 @@ class QueryBuilder:
         over `.candidates()` among them; ef_search and linear_below* are not read.
         screened: the same result through the matrix cores (hny_builder_exact_knn_screened, with .within()
         hny_builder_exact_range_screened); "votes": the top-k search by one scan under a falling threshold
-        (hny_builder_exact_knn_voted; .within() then runs the plain range search); not read by the forms with a
-        filter per query"""
+        (hny_builder_exact_knn_voted; .within() then runs the plain range search).  With candidates_per_query() /
+        candidates_bitsets() "votes" runs hny_builder_exact_knn_filtered_voted / _bitsets_voted; True is not read by
+        the forms with a filter per query"""
         self._exact = True
         self._screened = capi.exact_method(screened)
         return self
@@ -799,6 +800,11 @@ class QueryBuilder:
         if self._radius is not None and self._within_filtered and not self._exact:
             raise ValueError("within(radius, filtered=True) needs .exact(): the graph search has no range form")
 
+    def _filtered_votes(self):
+        """`screened` of the top-k calls with a filter per query: "votes" is honoured (hny_builder_exact_knn_filtered_voted
+        / _bitsets_voted); True has no form with filters and stays the plain call"""
+        return "votes" if self._screened == "votes" else False
+
     def _kw(self):
         return dict(k=self.count, ef_search=self._ef, candidates=self._candidates,
                     linear_below=self._linear_below, linear_below_ratio=self._ratio)
@@ -824,12 +830,14 @@ class QueryBuilder:
         if self._bitsets is not None:
             bits, n_bits, filter_of = self._id_bits(len(q))
             if self._exact:
-                return r._b.exact_knn_bitsets_f32(q, bits, n_bits, filter_of, k=self.count, cancel=cancel)
+                return r._b.exact_knn_bitsets_f32(q, bits, n_bits, filter_of, k=self.count, cancel=cancel,
+                                                  screened=self._filtered_votes())
             return r._b.nns_bitsets_f32(q, bits, n_bits, filter_of, cancel=cancel, **self._kw_filtered())
         if self._per_query is not None:
             filters, filter_of = self._filters(len(q))
             if self._exact:
-                return r._b.exact_knn_filtered_f32(q, filters, filter_of, k=self.count, cancel=cancel)
+                return r._b.exact_knn_filtered_f32(q, filters, filter_of, k=self.count, cancel=cancel,
+                                                   screened=self._filtered_votes())
             return r._b.nns_filtered_f32(q, filters, filter_of, cancel=cancel, **self._kw_filtered())
         if self._exact:
             return r._b.exact_knn_f32(q, k=self.count, candidates=self._candidates, cancel=cancel,
@@ -856,7 +864,7 @@ class QueryBuilder:
             bits, n_bits, filter_of = self._id_bits(len(items))
             if self._exact:
                 return self.reader._b.exact_knn_bitsets(bits, n_bits, filter_of, query_items=items, k=self.count,
-                                                        cancel=cancel)
+                                                        cancel=cancel, screened=self._filtered_votes())
             return self.reader._b.nns_bitsets(bits, n_bits, filter_of, query_items=items, cancel=cancel,
                                               **self._kw_filtered())
         if self._per_query is not None:
@@ -864,7 +872,7 @@ class QueryBuilder:
             filters, filter_of = self._filters(len(items))
             if self._exact:
                 return self.reader._b.exact_knn_filtered(filters, filter_of, query_items=items, k=self.count,
-                                                         cancel=cancel)
+                                                         cancel=cancel, screened=self._filtered_votes())
             return self.reader._b.nns_filtered(filters, filter_of, query_items=items, cancel=cancel,
                                                **self._kw_filtered())
         if self._exact:

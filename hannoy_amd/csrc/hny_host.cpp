@@ -5842,16 +5842,26 @@ static uint32_t vote_pilot_size(uint32_t n, uint32_t kk, uint64_t n_c) {
   return (uint32_t)std::min<uint64_t>(n, P); // at most every slot once: the sample's slots are distinct
 }
 
-static int voted_run(hny_builder *b, const QuerySet &qs, const u32 *dmask, uint32_t kk, uint64_t n_c, SearchCancel &sc) {
+// With F (exact_filtered_impl's dense sub-batch) every member has its own mask, its own k <= kk and
+// its own pilot sample, sized from its filter's count; n_c is not read.  The queries come in filter order, so the
+// tiles of HNY_SCREEN_QT members are as homogeneous as that makes them, and per slab k_exact_tile_masks leaves the OR
+// of each tile's masks for the MASKED scan.  exact_dense_run's rule holds at this tile width: where the tiles together
+// want more than half of tiles x n rows, no tile masks are made and the unmasked scan runs (it counts no rows, so the
+// host adds tiles x n to hny_builder_exact_rows_read); F->skip == false (HNY_EXACT_SKIP=0) is the masked scan on
+// all-ones tile masks, which reads and counts every row.
+static int voted_run(hny_builder *b, const QuerySet &qs, const u32 *dmask, uint32_t kk, uint64_t n_c, SearchCancel &sc,
+                     const ExactFilters *F = nullptr) {
   uint32_t rcap = 64;
   while (rcap < kk + 1) rcap *= 2;
   const uint32_t qblock = search_chunk(b, qs.nq, rcap, kk, HNY_EXACT_QBLOCK);
   DenseScan scan{b, qs};
   TopkOut top{b, qs, kk};
   DevBuf<u64> dlists, dtally;
-  DevBuf<u32> dln, dcand, dcertain;
+  DevBuf<u32> dln, dcand, dcertain, dfof, dkof, dpil, dtile;
   DevBuf<float> dthr;
   BitmapScan prod{b};
+  std::vector<u32> hfof(F ? qblock : 0), hkof(F ? qblock : 0), hpil(F ? qblock : 0);
+  const size_t tile_words = (size_t)((qblock + HNY_SCREEN_QT - 1) / HNY_SCREEN_QT) * HNY_SCREEN_BITS_STRIDE;
   if (int rc = scan.alloc(qblock, dmask, /*scores=*/false)) return rc;
   if (int rc = prod.begin(qblock)) return rc;
   HIP_TRY(dlists.alloc((size_t)qblock * rcap));
@@ -5868,8 +5878,23 @@ static int voted_run(hny_builder *b, const QuerySet &qs, const u32 *dmask, uint3
   t.cand = dcand.p, t.mask = dmask;
   t.lists = dlists.p, t.list_n = dln.p, t.k = kk, t.rcap = rcap;
   t.thr = dthr.p, t.tally = dtally.p;
+  if (F) {
+    HIP_TRY(dfof.alloc(qblock));
+    HIP_TRY(dkof.alloc(qblock));
+    HIP_TRY(dpil.alloc(qblock));
+    HIP_TRY(dtile.alloc(tile_words));
+    a.filter_of = t.filter_of = dfof.p; // (`a`: what k_exact_tile_masks reads)
+    a.masks = t.masks = F->masks;
+    a.mask_stride = t.mask_stride = F->mask_stride;
+    t.k_of = dkof.p, t.pilot_of = dpil.p;
+  }
   ScreenClock clock{b, b->vote_ms};
   scan.produce = [&] { return clock.run(1, [&] { return prod.produce(a, bits); }); };
+  const DenseScan::Launch tile_masks = [&] { // the OR of the masks of every tile of HNY_SCREEN_QT members, this slab
+    ExactArgs m = a; // (a.tile_mask is dtile)
+    m.qt = HNY_SCREEN_QT;
+    return clock.run(1, [&] { return hnyk_exact_tile_masks(m, b->stream); });
+  };
   const auto settle = [&](int kind, uint32_t pilot_n) {
     t.q_slots = a.q_slots, t.q_rows = a.q_rows, t.q_norms = a.q_norms, t.q_stride = a.q_stride, t.nq = a.nq;
     t.slab_base = a.slab_base, t.slab_n = a.slab_n;
@@ -5877,12 +5902,31 @@ static int voted_run(hny_builder *b, const QuerySet &qs, const u32 *dmask, uint3
     return clock.run(kind, [&] { return hnyk_knn_settle(b->g, t, b->shape, b->stream); });
   };
   const DenseScan::Launch slab_settle = [&] { return settle(2, 0); };
-  const uint32_t pilot_n = vote_pilot_size(b->n, kk, n_c);
+  uint32_t pilot_n = F ? 0 : vote_pilot_size(b->n, kk, n_c);
   for (uint64_t q0 = 0; q0 < qs.nq; q0 += qblock) {
     const uint32_t n_mem = scan.block(q0, qblock);
     if (n_mem == 0 || sc.probe()) continue; // cancelled: nothing of this block is started, 0 hits each
     if (int rc = scan.stage()) return rc;
     scan.aim(0, n_mem);
+    bool masked = false, made = false; // the MASKED scan; on tile masks made per slab from the members' masks
+    if (F) {
+      pilot_n = 0;
+      for (uint32_t j = 0; j < n_mem; j++) {
+        const uint64_t qi = scan.query_of(j);
+        hfof[j] = F->filter_of[qi];
+        hkof[j] = F->k_of[qi];
+        hpil[j] = vote_pilot_size(b->n, hkof[j], F->count_of[qi]);
+        pilot_n = std::max(pilot_n, hpil[j]); // (<= n each: hnyk_knn_settle refuses a larger one)
+      }
+      HIP_TRY(hipMemcpyAsync(dfof.p, hfof.data(), (size_t)n_mem * 4, hipMemcpyHostToDevice, b->stream));
+      HIP_TRY(hipMemcpyAsync(dkof.p, hkof.data(), (size_t)n_mem * 4, hipMemcpyHostToDevice, b->stream));
+      HIP_TRY(hipMemcpyAsync(dpil.p, hpil.data(), (size_t)n_mem * 4, hipMemcpyHostToDevice, b->stream));
+      made = F->skip && exact_tiles_sparse(hfof.data(), n_mem, HNY_SCREEN_QT, b->n,
+                                           [&](uint32_t j) { return F->count_of[scan.query_of(j)]; });
+      masked = made || !F->skip;
+      if (masked && !made) HIP_TRY(hnyk_fill_u32(dtile.p, 0xFFFFFFFFu, tile_words, b->stream));
+      a.tile_mask = masked ? dtile.p : nullptr; // != null: the MASKED scan
+    }
     HIP_TRY(prod.query_sums(a));
     HIP_TRY(hnyk_fill_u32(reinterpret_cast<u32 *>(dthr.p), 0x7F800000u, n_mem, b->stream)); // +inf
     HIP_TRY(hipMemsetAsync(dln.p, 0, (size_t)n_mem * 4, b->stream));
@@ -5890,7 +5934,7 @@ static int voted_run(hny_builder *b, const QuerySet &qs, const u32 *dmask, uint3
     bool stopped = sc.probe();
     if (!stopped) {
       HIP_TRY(settle(0, pilot_n));
-      if (int rc = scan.slabs(sc, &stopped, slab_settle)) return rc;
+      if (int rc = scan.slabs(sc, &stopped, slab_settle, made ? tile_masks : nullptr)) return rc;
     }
     if (stopped) { // the block did not finish: 0 hits each
       HIP_TRY(hipStreamSynchronize(b->stream));
@@ -5906,6 +5950,7 @@ static int voted_run(hny_builder *b, const QuerySet &qs, const u32 *dmask, uint3
       b->vote_settled += htally[2 * j + 1];
     }
     b->vote_voted += n_mem;
+    if (F && !masked) b->exact_rows_read += (uint64_t)((n_mem + HNY_SCREEN_QT - 1) / HNY_SCREEN_QT) * b->n;
   }
   return HNY_OK;
 }
@@ -6030,9 +6075,22 @@ static bool exact_skip_env() {
   return !(e && e[0] == '0' && !e[1]);
 }
 
-static int exact_filtered_impl(hny_builder *b, const hny_query_opts *qo, const QuerySet &qs, const FilterSource &src) {
+// voted (hny_builder_exact_knn_filtered_voted / _bitsets_voted): the same checks, rounds and classes;
+// the dense sub-batch runs voted_run where it runs exact_dense_run otherwise.  The gathered queries count as routed,
+// and so does the whole call on a builder whose rows no bitmap scan serves: that one runs the plain method
+static int exact_filtered_impl(hny_builder *b, const hny_query_opts *qo, const QuerySet &qs, const FilterSource &src,
+                               bool voted = false) {
   const FilterSource *fl = &src;
   const uint64_t nq = qs.nq;
+  if (voted && b) {
+    b->vote_voted = b->vote_routed = b->vote_pilot = b->vote_settled = 0;
+    for (double &ms : b->vote_ms) ms = 0;
+    if (!bitmaps_serve(b)) {
+      const int rc = exact_filtered_impl(b, qo, qs, src);
+      if (rc == HNY_OK) b->vote_routed = nq;
+      return rc;
+    }
+  }
   if (int rc = check_search_outputs(qs)) return rc;
   if (int rc = check_filters(qo, fl, nq)) return rc; // the candidates' side before the f32 rows, as in exact_impl
   const uint32_t n = b->n, k = qs.k;
@@ -6088,7 +6146,11 @@ static int exact_filtered_impl(hny_builder *b, const hny_query_opts *qo, const Q
     dense.k = most;
     const QuerySet sub = dense.gather();
     const ExactFilters F{dense.filter_of.data(), k_of.data(), count_of.data(), fr.dmasks.p, fr.stride, skip};
-    if (int rc = exact_dense_run(b, sub, dlive.p, most, &F, sc)) return rc;
+    if (voted) {
+      if (int rc = voted_run(b, sub, dlive.p, most, 0, sc, &F)) return rc;
+    } else if (int rc = exact_dense_run(b, sub, dlive.p, most, &F, sc)) {
+      return rc;
+    }
     dense.scatter();
     return HNY_OK;
   };
@@ -6107,6 +6169,7 @@ static int exact_filtered_impl(hny_builder *b, const hny_query_opts *qo, const Q
       L.filter_of = scan.filter_of.data();
       if (int rc = nns_run(b, qo, sub, L, true, false, most_hits, linear_rcap(most_hits), sc)) return rc;
       scan.scatter();
+      if (voted) b->vote_routed += scan.idx.size();
     }
     if (!dense.idx.empty())
       if (int rc = run_dense(dense)) return rc;
@@ -6117,7 +6180,9 @@ static int exact_filtered_impl(hny_builder *b, const hny_query_opts *qo, const Q
     if (int rc = run_dense(rest)) return rc;
   }
   HIP_TRY(hipStreamSynchronize(b->stream));
-  HIP_TRY(hipMemcpy(&b->exact_rows_read, b->g.stats + ST_EXACT_ROWS, sizeof(u64), hipMemcpyDeviceToHost));
+  u64 rows_read = 0; // the device's count, next to what voted_run added for its unmasked scans
+  HIP_TRY(hipMemcpy(&rows_read, b->g.stats + ST_EXACT_ROWS, sizeof(u64), hipMemcpyDeviceToHost));
+  b->exact_rows_read += rows_read;
   return search_end(b, qo, sc);
 }
 
@@ -6150,6 +6215,41 @@ int hny_builder_exact_knn_bitsets_f32(hny_builder *b, const hny_query_opts *qo, 
                                       float *out_dists, uint32_t *out_counts) {
   if (!queries) return fail(HNY_ERR_INVALID_ARG, "no queries");
   return exact_filtered_impl(b, qo, QuerySet::of_f32(b, qo, nq, queries, qstride, out_ids, out_dists, out_counts), filters);
+}
+
+// the same four calls by votes
+int hny_builder_exact_knn_filtered_voted(hny_builder *b, const hny_query_opts *qo, const hny_query_filters *filters,
+                                         uint64_t nq, const void *qvectors, size_t qstride, const void *qheaders,
+                                         const uint32_t *query_items, uint32_t *out_ids, float *out_dists,
+                                         uint32_t *out_counts) {
+  return exact_filtered_impl(
+      b, qo, QuerySet::of(b, qo, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists, out_counts), filters,
+      true);
+}
+
+int hny_builder_exact_knn_filtered_voted_f32(hny_builder *b, const hny_query_opts *qo, const hny_query_filters *filters,
+                                             uint64_t nq, const float *queries, size_t qstride, uint32_t *out_ids,
+                                             float *out_dists, uint32_t *out_counts) {
+  if (!queries) return fail(HNY_ERR_INVALID_ARG, "no queries");
+  return exact_filtered_impl(b, qo, QuerySet::of_f32(b, qo, nq, queries, qstride, out_ids, out_dists, out_counts), filters,
+                             true);
+}
+
+int hny_builder_exact_knn_bitsets_voted(hny_builder *b, const hny_query_opts *qo, const hny_query_bitsets *filters,
+                                        uint64_t nq, const void *qvectors, size_t qstride, const void *qheaders,
+                                        const uint32_t *query_items, uint32_t *out_ids, float *out_dists,
+                                        uint32_t *out_counts) {
+  return exact_filtered_impl(
+      b, qo, QuerySet::of(b, qo, nq, qvectors, qstride, qheaders, query_items, out_ids, out_dists, out_counts), filters,
+      true);
+}
+
+int hny_builder_exact_knn_bitsets_voted_f32(hny_builder *b, const hny_query_opts *qo, const hny_query_bitsets *filters,
+                                            uint64_t nq, const float *queries, size_t qstride, uint32_t *out_ids,
+                                            float *out_dists, uint32_t *out_counts) {
+  if (!queries) return fail(HNY_ERR_INVALID_ARG, "no queries");
+  return exact_filtered_impl(b, qo, QuerySet::of_f32(b, qo, nq, queries, qstride, out_ids, out_dists, out_counts), filters,
+                             true);
 }
 
 uint64_t hny_builder_exact_rows_read(const hny_builder *b) { return b ? b->exact_rows_read : 0; }

@@ -792,6 +792,10 @@ struct ScreenRangeArgs {
   const float *radius; // [nq] of the queries aimed at
   u32 *cand, *certain; // [nq][HNY_SCREEN_BITS_STRIDE]
 };
+// ExactArgs::tile_mask != null with one of the four scans below: its MASKED instance (hny_builder_exact_knn_filtered_voted,
+// DESIGN.md §3d-11), which reads no row outside tile_mask[tile of HNY_SCREEN_QT queries][HNY_SCREEN_BITS_STRIDE], the
+// OR of the masks of the tile's members over the slab (hnyk_exact_tile_masks with qt = HNY_SCREEN_QT, or all ones),
+// writes the bitmap words of skipped rows as 0 and adds the rows it loads to g.stats[ST_EXACT_ROWS]
 hipError_t hnyk_screen_range(const GraphDev &g, const ExactArgs &a, const ScreenArgs &s, const ScreenRangeArgs &b,
                              hipStream_t st);
 // The split-bf16 producer of the same bitmaps (hny_builder_set_screen_precision):
@@ -860,6 +864,13 @@ struct KnnSettleArgs {
   u32 k, rcap;                 // k < rcap, rcap a power of two
   float *thr;                  // [nq] +inf or an upper bound of the k-th exact distance
   u64 *tally;                  // [nq][2]: pairs the pilot settled, pairs settled from the slabs' bitmaps
+  // a mask, a k and a pilot per member (hny_builder_exact_knn_filtered_voted); all null in the call
+  // without filters.  filter_of != null: the PER instances of the kernel
+  const u32 *filter_of;        // [nq] the member's mask among `masks`, HNY_SENT = `mask` (the live items)
+  const u32 *masks;            // the filters' bitsets over slots (live slots only), mask_stride words apart
+  u32 mask_stride;
+  const u32 *k_of;             // [nq] the member's own k, 1 <= k_of[q] <= k (rcap is sized for the largest)
+  const u32 *pilot_of;         // [nq] pilot mode: the member's own sample size, <= pilot_n (the block's largest)
 };
 hipError_t hnyk_knn_settle(const GraphDev &g, const KnnSettleArgs &a, LaunchShape s, hipStream_t st);
 // the n keys of n_seg segments seg[i] .. seg[i + 1], each segment ascending; `keys` and `other` are both scratch,

@@ -3123,10 +3123,15 @@ __global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_range_settle(GraphDev
 // A launch that kept nothing stores nothing.  Otherwise slab mode stores the head as lists[q] / list_n[q]
 // (k_exact_topk's format), and both modes lower thr[q] to the k-th distance of a full head if that is finite: with
 // fewer than k entries, or a k-th distance of +inf or the NaN, every pair under the mask stays a candidate.
-// the slot that bit j of word w of a trip stands for
+// PER (hny_builder_exact_knn_filtered_voted): the member has a mask, a k and a pilot sample of its
+// own.  The workgroup resolves them once, workgroup-uniformly (k_exact_topk's readfirstlane): the mask
+// masks + filter_of[q] * mask_stride, or the call's live mask for a member without a filter; kk = k_of[q] <= a.k, at
+// which the head is full, the cut is taken and the threshold falls; pilot_of[q] <= a.pilot_n, the sample
+// floor(t * n / pilot_of[q]).  rcap, the key area and the merge rule are the block's: a.k only sizes them.
+// the slot that bit j of word w of a trip stands for; pilot_n: the member's sample size
 template <bool PILOT>
-__device__ __forceinline__ u32 knn_slot(const GraphDev &g, const KnnSettleArgs &a, u32 w, u32 j) {
-  if constexpr (PILOT) return (u32)(((u64)(w * 32u + j) * g.n) / a.pilot_n);
+__device__ __forceinline__ u32 knn_slot(const GraphDev &g, const KnnSettleArgs &a, u32 pilot_n, u32 w, u32 j) {
+  if constexpr (PILOT) return (u32)(((u64)(w * 32u + j) * g.n) / pilot_n);
   else return a.slab_base + w * 32u + j;
 }
 // head + pending (at most the keys' capacity) sorted, cut to k entries; the cut is the k-th key of a full head
@@ -3140,7 +3145,7 @@ __device__ __forceinline__ void knn_merge(u64 *keys, u32 k, u32 &head_n, u32 &pe
   pend_n = 0;
   if (head_n == k) cut = keys[k - 1u];
 }
-template <int LPR, int NCH, bool PILOT>
+template <int LPR, int NCH, bool PILOT, bool PER = false>
 __global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_knn_settle(GraphDev g, KnnSettleArgs a) {
   extern __shared__ __align__(16) unsigned char smem[];
   LdsCarve lds(smem);
@@ -3163,28 +3168,41 @@ __global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_knn_settle(GraphDev g
   float4 q[NCH];
   load_row<LPR, NCH>(qrow, t, g.n16, q);
   const u32 *cw = a.cand + (size_t)qi * HNY_SCREEN_BITS_STRIDE;
-  const u32 *mw = a.mask + (a.slab_base >> 5);
-  const u32 words = ((PILOT ? a.pilot_n : a.slab_n) + 31u) / 32u;
+  const u32 *mask = a.mask;
+  u32 kk = a.k, pilot_n = a.pilot_n;
+  if constexpr (PER) {
+    const u32 f = uni(a.filter_of[qi]);
+    if (f != HNY_SENT) mask = a.masks + (size_t)f * a.mask_stride;
+    kk = uni(a.k_of[qi]);
+    if (kk > a.k) kk = a.k; // (never: the host sizes rcap for the largest)
+    if (kk == 0u) return;   // (never: a member of an empty filter is answered on the host)
+    if constexpr (PILOT) {
+      pilot_n = uni(a.pilot_of[qi]);
+      if (pilot_n > a.pilot_n) pilot_n = a.pilot_n; // (never: a.pilot_n is the block's largest, <= n)
+    }
+  }
+  const u32 *mw = mask + (a.slab_base >> 5);
+  const u32 words = ((PILOT ? pilot_n : a.slab_n) + 31u) / 32u;
   const u32 cap = knn_settle_cap(a.rcap);
   const u64 below = (1ull << ln) - 1ull;
   u64 *list = a.lists + (size_t)qi * a.rcap;
   u32 head_n = 0, pend_n = 0, n_listed = 0; // (uniform; n_listed: thread 0's)
   if constexpr (!PILOT) {
     head_n = uni(a.list_n[qi]);
-    if (head_n > a.k) head_n = a.k;
+    if (head_n > kk) head_n = kk;
     for (u32 i = tid; i < head_n; i += 256u) keys[i] = list[i];
     __syncthreads();
   }
-  u64 cut = head_n == a.k ? keys[a.k - 1u] : ~0ull;
+  u64 cut = head_n == kk ? keys[kk - 1u] : ~0ull;
   bool changed = false;
   for (u32 w0 = 0; w0 < words; w0 += HNY_SETTLE_WORDS) {
     const u32 w = w0 + tid;
     u32 bits = 0;
     if (tid < HNY_SETTLE_WORDS && w < words) {
       if constexpr (PILOT) {
-        for (u32 j = 0; j < 32u && w * 32u + j < a.pilot_n; j++) {
-          const u32 s = knn_slot<PILOT>(g, a, w, j);
-          bits |= ((a.mask[s >> 5] >> (s & 31u)) & 1u) << j;
+        for (u32 j = 0; j < 32u && w * 32u + j < pilot_n; j++) {
+          const u32 s = knn_slot<PILOT>(g, a, pilot_n, w, j);
+          bits |= ((mask[s >> 5] >> (s & 31u)) & 1u) << j;
         }
       } else {
         bits = cw[w] & mw[w];
@@ -3202,7 +3220,7 @@ __global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_knn_settle(GraphDev g
     __syncthreads();
     const u32 cnt = uni(ctl[0] + ctl[1]);
     u32 off = incl - pc + (wave == 1u ? ctl[0] : 0u);
-    for (u32 rest = bits; rest; rest &= rest - 1u) slots[off++] = knn_slot<PILOT>(g, a, w, (u32)(__ffs(rest) - 1));
+    for (u32 rest = bits; rest; rest &= rest - 1u) slots[off++] = knn_slot<PILOT>(g, a, pilot_n, w, (u32)(__ffs(rest) - 1));
     __syncthreads();
     if (cnt == 0u) continue;
     if (tid == 0) n_listed += cnt;
@@ -3213,7 +3231,7 @@ __global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_knn_settle(GraphDev g
     }
     __syncthreads();
     for (u32 r0 = 0; r0 < cnt; r0 += HNY_KNN_SETTLE_ROUND) {
-      if (head_n + pend_n + HNY_KNN_SETTLE_ROUND > cap) knn_merge(keys, a.k, head_n, pend_n, cut), changed = true;
+      if (head_n + pend_n + HNY_KNN_SETTLE_ROUND > cap) knn_merge(keys, kk, head_n, pend_n, cut), changed = true;
       const u32 i = r0 + tid;
       const u64 key = i < cnt ? (((u64)fbits(sd[i]) << 32) | (u64)slots[i]) : ~0ull;
       const bool keep = i < cnt && key <= cut;
@@ -3232,14 +3250,14 @@ __global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_knn_settle(GraphDev g
       __syncthreads();
     }
   }
-  if (pend_n) knn_merge(keys, a.k, head_n, pend_n, cut), changed = true;
+  if (pend_n) knn_merge(keys, kk, head_n, pend_n, cut), changed = true;
   if (changed) {
     if constexpr (!PILOT) {
       for (u32 i = tid; i < head_n; i += 256u) list[i] = keys[i];
       if (tid == 0) a.list_n[qi] = head_n;
     }
-    if (tid == 0 && head_n == a.k) {
-      const u32 kth = (u32)(keys[a.k - 1u] >> 32);
+    if (tid == 0 && head_n == kk) {
+      const u32 kth = (u32)(keys[kk - 1u] >> 32);
       const float dk = __builtin_bit_cast(float, kth);
       if (kth < 0x7F800000u && dk < a.thr[qi]) a.thr[qi] = dk;
     }
@@ -5131,6 +5149,10 @@ template <int L, int C>
 struct KnnSettleLauncher {
   static hipError_t run(const GraphDev &g, const KnnSettleArgs &a, hipStream_t st) {
     const size_t lds = HNY_LDS_BYTES(knn_settle_lds, a.rcap);
+    if (a.filter_of) { // a mask, a k and a pilot per member
+      if (a.pilot_n) return launch_with_lds(k_knn_settle<L, C, true, true>, dim3(a.nq), dim3(256), lds, st, g, a);
+      return launch_with_lds(k_knn_settle<L, C, false, true>, dim3(a.nq), dim3(256), lds, st, g, a);
+    }
     if (a.pilot_n) return launch_with_lds(k_knn_settle<L, C, true>, dim3(a.nq), dim3(256), lds, st, g, a);
     return launch_with_lds(k_knn_settle<L, C, false>, dim3(a.nq), dim3(256), lds, st, g, a);
   }
@@ -5243,7 +5265,8 @@ hipError_t hnyk_range_settle(const GraphDev &g, const RangeSettleArgs &a, Launch
 hipError_t hnyk_knn_settle(const GraphDev &g, const KnnSettleArgs &a, LaunchShape s, hipStream_t st) {
   if (!a.nq || (!a.pilot_n && !a.slab_n)) return hipSuccess;
   if (a.k < 1u || a.k >= a.rcap || a.rcap > HNY_RESCORE_MAX + 1u || (a.rcap & (a.rcap - 1u))) return hipErrorInvalidValue;
-  if (a.pilot_n > g.n) return hipErrorInvalidValue; // a sample of distinct slots
+  if (a.pilot_n > g.n) return hipErrorInvalidValue; // a sample of distinct slots (per member: pilot_of[q] <= pilot_n)
+  if (a.filter_of && (!a.k_of || !a.masks || (a.pilot_n && !a.pilot_of))) return hipErrorInvalidValue;
   if (!a.pilot_n && (a.slab_n > HNY_EXACT_SLAB || (a.slab_base & 31u) || a.slab_n > g.n - a.slab_base))
     return hipErrorInvalidValue; // the bitmap's stride and words, the mask's end
   return dispatch_shape<KnnSettleLauncher>(s, g, a, st);

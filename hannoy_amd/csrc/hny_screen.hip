@@ -132,9 +132,12 @@ __device__ __forceinline__ void screen_stage_norms(const GraphDev &g, const Exac
 // One pass of a wave: the dot products of the lane's row (rp; !valid: zeros) with the tile's 2 x 32 queries.
 // Accumulator register i of a block is query 8 (i / 4) + 4 h + (i % 4) of the block, column = the lane's row.
 // `first`: the workgroup's first pass, which stages a row that fits one panel for all of them
+// MASKED: a wave with !want (its 32 rows are in no mask of the tile; wave-uniform) takes its share
+// of the staging and reaches every barrier, but loads no row and issues no matrix instruction; its accumulators are 0
+template <bool MASKED = false>
 __device__ __forceinline__ void screen_dots(const GraphDev &g, const ExactArgs &a, const ScreenLds &L, u32 q0, u32 nqt,
                                             bool first, const unsigned char *rp, bool valid, f32x16 &acc0,
-                                            f32x16 &acc1) {
+                                            f32x16 &acc1, bool want = true) {
   const u32 tid = threadIdx.x, ln = tid & 63u, j = ln & 31u, h = ln >> 5, n16 = g.n16;
   const bool one_panel = n16 <= HNY_SCREEN_KP;
   float4 *qpan = L.qpan;
@@ -156,7 +159,7 @@ __device__ __forceinline__ void screen_dots(const GraphDev &g, const ExactArgs &
       __syncthreads();
     }
     const u32 units = n16 - u0 < HNY_SCREEN_KP ? n16 - u0 : HNY_SCREEN_KP;
-    const u32 steps = (units + 1u) / 2u;
+    const u32 steps = MASKED && !want ? 0u : (units + 1u) / 2u;
     for (u32 st = 0; st < steps; st++) {
       const u32 f = 2u * st + h, u = u0 + f; // f < HNY_SCREEN_KP: staged, zero from n16 on
       float4 rv = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -239,9 +242,10 @@ __device__ __forceinline__ void split_bf16(const float4 &a, const float4 &b, bf1
 }
 
 // screen_dots on the split halves: the same loop structure, panels, barriers and accumulator layout
+template <bool MASKED = false>
 __device__ __forceinline__ void screen_dots_split(const GraphDev &g, const ExactArgs &a, const ScreenLds &L, u32 q0,
                                                   u32 nqt, bool first, const unsigned char *rp, bool valid,
-                                                  f32x16 &acc0, f32x16 &acc1) {
+                                                  f32x16 &acc0, f32x16 &acc1, bool want = true) {
   const u32 tid = threadIdx.x, ln = tid & 63u, j = ln & 31u, h = ln >> 5, n16 = g.n16;
   const bool one_panel = n16 <= HNY_SCREEN_KP;
   bf16x8 *qpan = reinterpret_cast<bf16x8 *>(L.qpan);
@@ -268,7 +272,7 @@ __device__ __forceinline__ void screen_dots_split(const GraphDev &g, const Exact
       __syncthreads();
     }
     const u32 units = n16 - u0 < HNY_SCREEN_KP ? n16 - u0 : HNY_SCREEN_KP;
-    const u32 steps = (units + 3u) / 4u;
+    const u32 steps = MASKED && !want ? 0u : (units + 3u) / 4u;
     for (u32 st = 0; st < steps; st++) {
       const u32 f = 2u * st + h, u = u0 + 2u * f; // f < HNY_SCREEN_KP / 2: staged, zero from n16 on
       float4 ra = zero, rb = zero;
@@ -301,7 +305,47 @@ __device__ __forceinline__ void screen_dots_split(const GraphDev &g, const Exact
 // k_screen_range and k_screen_range_split are this one body: SPLIT chooses the producer of the accumulators, and `s`
 // carries that producer's constants.  (The arguments come by value, as the kernels hold them: by reference the
 // compiler schedules k_screen_range's epilogue differently.)
-template <bool L2, bool SPLIT>
+// ---- the masked form of the four scans (hny_builder_exact_knn_filtered_voted).  a.tile_mask holds,
+// per tile of HNY_SCREEN_QT queries, the OR of its members' slot masks over the slab (k_exact_tile_masks at this tile
+// width), one word per 32 slots: the word of a wave's 32 rows of a pass.  Three skips, each as uniform as its scope:
+//   chunk  no word of the chunk's 16 is set: the workgroup writes the chunk's words of its queries as 0 and ends
+//          before it stages anything
+//   pass   none of the pass's four words is set: every wave writes its word as 0, nobody enters the dot products, so
+//          no barrier is met by a part of the workgroup (the test reads the same four words in every thread)
+//   wave   its own word is 0: it goes through the dot products' staging and barriers with `want` false, then writes
+//          its word as 0
+// Every bitmap word of the chunk keeps exactly one writer, the wave that owns it in the unmasked scan (the chunk skip
+// hands wave w the words w, w + 4, ...).  The member's own mask is not applied: that stays with the consumer.
+// the chunk's words of the tile's mask; null: the chunk is skipped and its bitmap words are written
+__device__ __forceinline__ const u32 *screen_chunk_mask(const ExactArgs &a, const ScreenRangeArgs &b, u32 q0, u32 nqt,
+                                                        u32 c0, u32 c1) {
+  const u32 cw = (c0 - a.slab_base) / 32u; // + 15 < HNY_SCREEN_BITS_STRIDE: the chunk lies within the slab
+  const u32 *tm = a.tile_mask + (size_t)blockIdx.x * HNY_SCREEN_BITS_STRIDE + cw;
+  u32 any = 0;
+#pragma unroll
+  for (u32 w = 0; w < HNY_EXACT_CHUNK / 32u; w++) any |= tm[w];
+  if (any) return tm;
+  const u32 nw = ((c1 - c0 + 127u) / 128u) * 4u; // the words the passes of the unmasked scan write
+  for (u32 i = threadIdx.x; i < nqt * nw; i += 256u) {
+    const size_t at = (size_t)(q0 + i / nw) * HNY_SCREEN_BITS_STRIDE + cw + i % nw;
+    b.cand[at] = 0u, b.certain[at] = 0u;
+  }
+  return nullptr;
+}
+// a wave's word `word` of the tile's queries as 0: lane l writes query l's
+__device__ __forceinline__ void screen_zero_word(const ScreenRangeArgs &b, u32 q0, u32 nqt, u32 word) {
+  const u32 ln = threadIdx.x & 63u;
+  if (ln < nqt) {
+    const size_t at = (size_t)(q0 + ln) * HNY_SCREEN_BITS_STRIDE + word;
+    b.cand[at] = 0u, b.certain[at] = 0u;
+  }
+}
+// the rows a wave loaded, to hny_builder_exact_rows_read: one atomic per wave, as k_exact_scores<.., TILE>
+__device__ __forceinline__ void screen_rows_read(const GraphDev &g, u32 rows_read) {
+  if ((threadIdx.x & 63u) == 0u && rows_read) atomicAdd(&g.stats[ST_EXACT_ROWS], (u64)rows_read);
+}
+
+template <bool L2, bool SPLIT, bool MASKED = false>
 __device__ __forceinline__ void screen_range_body(const GraphDev g, const ExactArgs a, const ScreenArgs s,
                                                   const ScreenRangeArgs b, const ScreenLds L, float *s_r) {
   const u32 tid = threadIdx.x;
@@ -310,16 +354,44 @@ __device__ __forceinline__ void screen_range_body(const GraphDev g, const ExactA
   const u32 slab_end = a.slab_base + a.slab_n;
   const u32 c0 = a.slab_base + blockIdx.y * HNY_EXACT_CHUNK;
   const u32 c1 = slab_end - c0 < HNY_EXACT_CHUNK ? slab_end : c0 + HNY_EXACT_CHUNK;
+  const u32 *tm = nullptr;
+  if constexpr (MASKED) {
+    tm = screen_chunk_mask(a, b, q0, nqt, c0, c1);
+    if (!tm) return;
+  }
   screen_stage_norms(g, a, s, L, q0, nqt, tid);
   if (tid < HNY_SCREEN_QT) s_r[tid] = tid < nqt ? b.radius[q0 + tid] : 0.f;
   const u32 ln = tid & 63u, wave = tid >> 6, j = ln & 31u, h = ln >> 5;
+  bool first = true;  // MASKED: no pass has gone through the dot products yet
+  u32 rows_read = 0;  // MASKED: the rows of this wave's wanted passes
   for (u32 p0 = c0; p0 < c1; p0 += 128u) {
     const u32 row = p0 + wave * 32u + j;
-    const bool valid = row < c1;
+    const u32 word = (p0 - a.slab_base) / 32u + wave; // < HNY_SCREEN_BITS_STRIDE: the chunk lies within the slab
+    bool valid = row < c1;
+    bool want = true;
+    if constexpr (MASKED) {
+      const u32 *pw = tm + (p0 - c0) / 32u; // the pass's four words, within the chunk's 16
+      if (!(pw[0] | pw[1] | pw[2] | pw[3])) { // the same in every thread of the workgroup
+        screen_zero_word(b, q0, nqt, word);
+        continue;
+      }
+      want = __builtin_amdgcn_readfirstlane((int)pw[wave]) != 0;
+      valid = valid && want;
+      if (want && p0 + wave * 32u < c1) rows_read += c1 - (p0 + wave * 32u) < 32u ? c1 - (p0 + wave * 32u) : 32u;
+    } else {
+      first = p0 == c0;
+    }
     f32x16 acc0, acc1;
     const unsigned char *rp = g.rows + (size_t)(valid ? row : c0) * g.row_stride;
-    if constexpr (SPLIT) screen_dots_split(g, a, L, q0, nqt, p0 == c0, rp, valid, acc0, acc1);
-    else screen_dots(g, a, L, q0, nqt, p0 == c0, rp, valid, acc0, acc1);
+    if constexpr (SPLIT) screen_dots_split<MASKED>(g, a, L, q0, nqt, first, rp, valid, acc0, acc1, want);
+    else screen_dots<MASKED>(g, a, L, q0, nqt, first, rp, valid, acc0, acc1, want);
+    if constexpr (MASKED) {
+      first = false;
+      if (!want) { // past the barriers of this pass
+        screen_zero_word(b, q0, nqt, word);
+        continue;
+      }
+    }
     float rn = 0.f, r2 = 0.f;
     if (valid) {
       rn = g.norms ? g.norms[row] : 0.f;
@@ -327,7 +399,6 @@ __device__ __forceinline__ void screen_range_body(const GraphDev g, const ExactA
     }
     const float r2up = r2 * s.c_n2 + s.a_n2;
     const float nr = norm_up(r2up);
-    const u32 word = (p0 - a.slab_base) / 32u + wave; // < HNY_SCREEN_BITS_STRIDE: the chunk lies within the slab
 #pragma unroll
     for (int blk = 0; blk < 2; blk++) {
 #pragma unroll
@@ -356,20 +427,21 @@ __device__ __forceinline__ void screen_range_body(const GraphDev g, const ExactA
       }
     }
   }
+  if constexpr (MASKED) screen_rows_read(g, rows_read);
 }
-template <bool L2>
+template <bool L2, bool MASKED = false>
 __global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_screen_range(GraphDev g, ExactArgs a, ScreenArgs s,
                                                                          ScreenRangeArgs b) {
   HNY_SCREEN_LDS(L);
   __shared__ float s_r[HNY_SCREEN_QT];
-  screen_range_body<L2, false>(g, a, s, b, L, s_r);
+  screen_range_body<L2, false, MASKED>(g, a, s, b, L, s_r);
 }
-template <bool L2>
+template <bool L2, bool MASKED = false>
 __global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_screen_range_split(GraphDev g, ExactArgs a, ScreenArgs s,
                                                                                ScreenRangeArgs b) {
   HNY_SCREEN_LDS(L);
   __shared__ float s_r[HNY_SCREEN_QT];
-  screen_range_body<L2, true>(g, a, s, b, L, s_r);
+  screen_range_body<L2, true, MASKED>(g, a, s, b, L, s_r);
 }
 
 // ---- the bit metrics' producer of the same bitmaps: k_screen_range's split on the integer matrix
@@ -423,9 +495,10 @@ __device__ __forceinline__ float finalize_bits(const GraphDev &g, u32 pop, float
 
 // One pass of a wave: acc = popcount(q ^ r) - popcount(q) of the lane's row (rp; !valid: zeros) with the tile's
 // 2 x 32 queries; screen_dots' loop structure and accumulator layout
+template <bool MASKED = false>
 __device__ __forceinline__ void screen_bits_dots(const GraphDev &g, const ExactArgs &a, uint4 *qpan, u32 q0, u32 nqt,
                                                  bool first, const unsigned char *rp, bool valid, i32x16 &acc0,
-                                                 i32x16 &acc1) {
+                                                 i32x16 &acc1, bool want = true) {
   const u32 tid = threadIdx.x, ln = tid & 63u, j = ln & 31u, h = ln >> 5, n16 = g.n16;
   const bool one_panel = n16 <= HNY_BITS_KP;
 #pragma unroll
@@ -454,7 +527,7 @@ __device__ __forceinline__ void screen_bits_dots(const GraphDev &g, const ExactA
       __syncthreads();
     }
     const u32 units = n16 - u0 < HNY_BITS_KP ? n16 - u0 : HNY_BITS_KP;
-    const u32 steps = (units + 1u) / 2u;
+    const u32 steps = MASKED && !want ? 0u : (units + 1u) / 2u;
     for (u32 st = 0; st < steps; st++) {
       const u32 f = 2u * st + h, u = u0 + f; // f < HNY_BITS_KP: staged, zero from n16 on
       uint4 rv = make_uint4(0u, 0u, 0u, 0u);
@@ -475,7 +548,8 @@ __device__ __forceinline__ void screen_bits_dots(const GraphDev &g, const ExactA
 // The epilogue holds the index's own distance bits:  certain  d <= r;  cand  certain, or d is the NaN (only from a
 // NaN / inf header norm of a by-vector query: never certain, the consumer decides it as the plain call does).  A NaN
 // radius gives no certain pair.  Rows at and beyond the chunk's end vote 0; the slot mask is left to the consumer
-template <int METRIC>
+// MASKED: the skips of screen_range_body, word for word
+template <int METRIC, bool MASKED = false>
 __global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_screen_range_bits(GraphDev g, ExactArgs a, const u32 *q_pop,
                                                                               ScreenRangeArgs b) {
   __shared__ uint4 s_qpan[HNY_SCREEN_QT * HNY_BITS_PSTRIDE];
@@ -487,6 +561,11 @@ __global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_screen_range_bits(Gra
   const u32 slab_end = a.slab_base + a.slab_n;
   const u32 c0 = a.slab_base + blockIdx.y * HNY_EXACT_CHUNK;
   const u32 c1 = slab_end - c0 < HNY_EXACT_CHUNK ? slab_end : c0 + HNY_EXACT_CHUNK;
+  const u32 *tm = nullptr;
+  if constexpr (MASKED) {
+    tm = screen_chunk_mask(a, b, q0, nqt, c0, c1);
+    if (!tm) return;
+  }
   if (tid < HNY_SCREEN_QT) { // published by the first barrier of screen_bits_dots
     float r = 0.f, qn = 0.f;
     u32 pop = 0;
@@ -504,14 +583,36 @@ __global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_screen_range_bits(Gra
     s_r[tid] = r, s_qn[tid] = qn, s_pop[tid] = pop;
   }
   const u32 ln = tid & 63u, wave = tid >> 6, j = ln & 31u, h = ln >> 5;
+  bool first = true; // MASKED: no pass has gone through the dot products yet
+  u32 rows_read = 0; // MASKED: the rows of this wave's wanted passes
   for (u32 p0 = c0; p0 < c1; p0 += 128u) { // the same trips for every wave: the panels are staged between barriers
     const u32 row = p0 + wave * 32u + j;
-    const bool valid = row < c1;
-    i32x16 acc0, acc1;
-    screen_bits_dots(g, a, s_qpan, q0, nqt, p0 == c0, g.rows + (size_t)(valid ? row : c0) * g.row_stride, valid, acc0,
-                     acc1);
-    const float rn = METRIC == 4 && valid && g.norms ? g.norms[row] : 0.f;
     const u32 word = (p0 - a.slab_base) / 32u + wave; // < HNY_SCREEN_BITS_STRIDE: the chunk lies within the slab
+    bool valid = row < c1;
+    bool want = true;
+    if constexpr (MASKED) {
+      const u32 *pw = tm + (p0 - c0) / 32u; // the pass's four words, within the chunk's 16
+      if (!(pw[0] | pw[1] | pw[2] | pw[3])) { // the same in every thread of the workgroup
+        screen_zero_word(b, q0, nqt, word);
+        continue;
+      }
+      want = __builtin_amdgcn_readfirstlane((int)pw[wave]) != 0;
+      valid = valid && want;
+      if (want && p0 + wave * 32u < c1) rows_read += c1 - (p0 + wave * 32u) < 32u ? c1 - (p0 + wave * 32u) : 32u;
+    } else {
+      first = p0 == c0;
+    }
+    i32x16 acc0, acc1;
+    screen_bits_dots<MASKED>(g, a, s_qpan, q0, nqt, first, g.rows + (size_t)(valid ? row : c0) * g.row_stride, valid,
+                             acc0, acc1, want);
+    if constexpr (MASKED) {
+      first = false;
+      if (!want) { // past the barriers of this pass
+        screen_zero_word(b, q0, nqt, word);
+        continue;
+      }
+    }
+    const float rn = METRIC == 4 && valid && g.norms ? g.norms[row] : 0.f;
 #pragma unroll
     for (int blk = 0; blk < 2; blk++) {
 #pragma unroll
@@ -533,6 +634,7 @@ __global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_screen_range_bits(Gra
       }
     }
   }
+  if constexpr (MASKED) screen_rows_read(g, rows_read);
 }
 
 // ---- Manhattan's producer of the same bitmaps (hny_builder_set_l1_screen): an L1 sum has no matrix
@@ -576,12 +678,24 @@ __device__ __forceinline__ void l1_unit(float (&acc)[HNY_L1_QG][2], const float4
   }
 }
 
+// MASKED: unit u of a lane's row; a lane without a wanted row loads nothing
+__device__ __forceinline__ float4 l1_load(const unsigned char *rp, u32 u, bool valid) {
+  if (!valid) return make_float4(0.f, 0.f, 0.f, 0.f);
+  return *reinterpret_cast<const float4 *>(rp + (size_t)u * 16);
+}
+
 // Epilogue, per accumulator S~: a NaN or a sum at or beyond HNY_SCREEN_BIG makes the pair uncertain, cand = 0 <= r and
 // never certain, as the f32 producers treat an overflowed bound.  Otherwise D >= S~ m_lo - a_abs and D <= S~ m_hi +
 // a_abs; below / above cover the product's and the sum's rounding.  S~ == r is a candidate and never certain
 // (the subtraction is not packed into v_pk_add_f32: that form has no |x| modifier, so the pair costs two v_and more
 // than it saves; the body is a function of its own because a kernel that carries the target attribute inlines
 // nothing that does not)
+// MASKED.  A lane owns two rows, a wave the four words word .. word + 3 of the tile's mask, and a
+// lane's loads are its own: a lane whose row's word is 0 (lanes 0 .. 31 and 32 .. 63 of either row set: 32 rows) loads
+// nothing, computes on zeros and votes 0.  A wave none of whose four words is set does no arithmetic at all and writes
+// four zero words per query; it still stages its share of every panel and meets every barrier, the trips being those
+// of the chunk.  A chunk without a wanted row ends the workgroup as in the matrix scans
+template <bool MASKED = false>
 __device__ __forceinline__ void screen_range_l1_body(const GraphDev g, const ExactArgs a, const ScreenL1Args s,
                                                      const ScreenRangeArgs b, float4 *s_q, float *s_r) {
   const u32 tid = threadIdx.x, ln = tid & 63u, wave = tid >> 6, n16 = g.n16;
@@ -590,11 +704,21 @@ __device__ __forceinline__ void screen_range_l1_body(const GraphDev g, const Exa
   const u32 slab_end = a.slab_base + a.slab_n;
   const u32 c0 = a.slab_base + blockIdx.y * HNY_EXACT_CHUNK;
   const u32 c1 = slab_end - c0 < HNY_EXACT_CHUNK ? slab_end : c0 + HNY_EXACT_CHUNK;
+  const u32 *tm = nullptr;
+  if constexpr (MASKED) {
+    tm = screen_chunk_mask(a, b, q0, nqt, c0, c1);
+    if (!tm) return;
+  }
   if (tid < HNY_SCREEN_QT) s_r[tid] = tid < nqt ? b.radius[q0 + tid] : 0.f; // published by the first step's barrier
   const u32 row0 = c0 + wave * 128u + ln, row1 = row0 + 64u;
   // a row at or beyond the chunk's end is not read: its lane reads row c0 again and votes 0; a wave wholly beyond
   // the end reads nothing
-  const bool valid0 = row0 < c1, valid1 = row1 < c1, wave_on = c0 + wave * 128u < c1;
+  // MASKED: an unwanted row is one beyond the end, and neither is read (l1_load)
+  bool want0 = true, want1 = true;
+  if constexpr (MASKED) want0 = tm[4u * wave + (ln >> 5)] != 0u, want1 = tm[4u * wave + 2u + (ln >> 5)] != 0u;
+  const bool valid0 = row0 < c1 && want0, valid1 = row1 < c1 && want1;
+  const bool wave_on = MASKED ? (ballot(valid0) | ballot(valid1)) != 0ull : c0 + wave * 128u < c1;
+  if constexpr (MASKED) screen_rows_read(g, (u32)(__popcll(ballot(valid0)) + __popcll(ballot(valid1))));
   const unsigned char *rp0 = g.rows + (size_t)(valid0 ? row0 : c0) * g.row_stride;
   const unsigned char *rp1 = g.rows + (size_t)(valid1 ? row1 : c0) * g.row_stride;
   const u32 word = (c0 - a.slab_base) / 32u + 4u * wave; // + 3 < HNY_SCREEN_BITS_STRIDE: the chunk lies within the slab
@@ -622,15 +746,27 @@ __device__ __forceinline__ void screen_range_l1_body(const GraphDev g, const Exa
     }
     if (wave_on) {
       const u32 units = n16 - u0 < HNY_SCREEN_KP ? n16 - u0 : HNY_SCREEN_KP;
-      float4 r0 = *reinterpret_cast<const float4 *>(rp0 + (size_t)u0 * 16);
-      float4 r1 = *reinterpret_cast<const float4 *>(rp1 + (size_t)u0 * 16);
-      for (u32 f = 0; f + 1u < units; f++) {
-        const float4 n0 = *reinterpret_cast<const float4 *>(rp0 + (size_t)(u0 + f + 1u) * 16);
-        const float4 n1 = *reinterpret_cast<const float4 *>(rp1 + (size_t)(u0 + f + 1u) * 16);
-        l1_unit(acc, s_q + f, nqg, r0, r1);
-        r0 = n0, r1 = n1;
+      if constexpr (MASKED) {
+        float4 r0 = l1_load(rp0, u0, valid0);
+        float4 r1 = l1_load(rp1, u0, valid1);
+        for (u32 f = 0; f + 1u < units; f++) {
+          const float4 n0 = l1_load(rp0, u0 + f + 1u, valid0);
+          const float4 n1 = l1_load(rp1, u0 + f + 1u, valid1);
+          l1_unit(acc, s_q + f, nqg, r0, r1);
+          r0 = n0, r1 = n1;
+        }
+        l1_unit(acc, s_q + (units - 1u), nqg, r0, r1);
+      } else {
+        float4 r0 = *reinterpret_cast<const float4 *>(rp0 + (size_t)u0 * 16);
+        float4 r1 = *reinterpret_cast<const float4 *>(rp1 + (size_t)u0 * 16);
+        for (u32 f = 0; f + 1u < units; f++) {
+          const float4 n0 = *reinterpret_cast<const float4 *>(rp0 + (size_t)(u0 + f + 1u) * 16);
+          const float4 n1 = *reinterpret_cast<const float4 *>(rp1 + (size_t)(u0 + f + 1u) * 16);
+          l1_unit(acc, s_q + f, nqg, r0, r1);
+          r0 = n0, r1 = n1;
+        }
+        l1_unit(acc, s_q + (units - 1u), nqg, r0, r1);
       }
-      l1_unit(acc, s_q + (units - 1u), nqg, r0, r1);
     }
     if (pan + 1u == npanels) {
 #pragma unroll
@@ -665,7 +801,13 @@ __global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_screen_range_l1(Graph
                                                                             ScreenRangeArgs b) {
   __shared__ float4 s_q[HNY_L1_QG * HNY_SCREEN_KP];
   __shared__ float s_r[HNY_SCREEN_QT];
-  screen_range_l1_body(g, a, s, b, s_q, s_r);
+  screen_range_l1_body<false>(g, a, s, b, s_q, s_r);
+}
+__global__ __launch_bounds__(256) HNY_NO_PACKED_F32 void k_screen_range_l1_masked(GraphDev g, ExactArgs a,
+                                                                                   ScreenL1Args s, ScreenRangeArgs b) {
+  __shared__ float4 s_q[HNY_L1_QG * HNY_SCREEN_KP];
+  __shared__ float s_r[HNY_SCREEN_QT];
+  screen_range_l1_body<true>(g, a, s, b, s_q, s_r);
 }
 
 // popcount of the units 0 .. n16 - 1 of a row, the bits partial_bin counts; eight lanes per row as k_screen_n2
@@ -767,7 +909,10 @@ hipError_t hnyk_screen_range(const GraphDev &g, const ExactArgs &a, const Screen
   if (g.metric != 0 && g.metric != 1) return hipErrorInvalidValue; // Cosine and Euclidean only: no silent other path
   if (a.slab_n > HNY_EXACT_SLAB || a.slab_base % HNY_EXACT_CHUNK) return hipErrorInvalidValue; // the bitmaps' stride
   const dim3 grid((a.nq + HNY_SCREEN_QT - 1) / HNY_SCREEN_QT, (a.slab_n + HNY_EXACT_CHUNK - 1) / HNY_EXACT_CHUNK);
-  if (g.metric == 1) hipLaunchKernelGGL(k_screen_range<true>, grid, dim3(256), 0, st, g, a, s, b);
+  if (a.tile_mask) { // the masked form
+    if (g.metric == 1) hipLaunchKernelGGL((k_screen_range<true, true>), grid, dim3(256), 0, st, g, a, s, b);
+    else hipLaunchKernelGGL((k_screen_range<false, true>), grid, dim3(256), 0, st, g, a, s, b);
+  } else if (g.metric == 1) hipLaunchKernelGGL(k_screen_range<true>, grid, dim3(256), 0, st, g, a, s, b);
   else hipLaunchKernelGGL(k_screen_range<false>, grid, dim3(256), 0, st, g, a, s, b);
   return hipGetLastError();
 }
@@ -778,7 +923,10 @@ hipError_t hnyk_screen_range_split(const GraphDev &g, const ExactArgs &a, const 
   if (g.metric != 0 && g.metric != 1) return hipErrorInvalidValue; // Cosine and Euclidean only: no silent other path
   if (a.slab_n > HNY_EXACT_SLAB || a.slab_base % HNY_EXACT_CHUNK) return hipErrorInvalidValue; // the bitmaps' stride
   const dim3 grid((a.nq + HNY_SCREEN_QT - 1) / HNY_SCREEN_QT, (a.slab_n + HNY_EXACT_CHUNK - 1) / HNY_EXACT_CHUNK);
-  if (g.metric == 1) hipLaunchKernelGGL(k_screen_range_split<true>, grid, dim3(256), 0, st, g, a, s, b);
+  if (a.tile_mask) {
+    if (g.metric == 1) hipLaunchKernelGGL((k_screen_range_split<true, true>), grid, dim3(256), 0, st, g, a, s, b);
+    else hipLaunchKernelGGL((k_screen_range_split<false, true>), grid, dim3(256), 0, st, g, a, s, b);
+  } else if (g.metric == 1) hipLaunchKernelGGL(k_screen_range_split<true>, grid, dim3(256), 0, st, g, a, s, b);
   else hipLaunchKernelGGL(k_screen_range_split<false>, grid, dim3(256), 0, st, g, a, s, b);
   return hipGetLastError();
 }
@@ -797,6 +945,15 @@ hipError_t hnyk_screen_range_bits(const GraphDev &g, const ExactArgs &a, const u
   if (g.metric < 3 || g.metric > 6) return hipErrorInvalidValue; // the four bit metrics only: no silent other path
   if (a.slab_n > HNY_EXACT_SLAB || a.slab_base % HNY_EXACT_CHUNK) return hipErrorInvalidValue; // the bitmaps' stride
   const dim3 grid((a.nq + HNY_SCREEN_QT - 1) / HNY_SCREEN_QT, (a.slab_n + HNY_EXACT_CHUNK - 1) / HNY_EXACT_CHUNK);
+  if (a.tile_mask) {
+    switch (g.metric) {
+      case 3: hipLaunchKernelGGL((k_screen_range_bits<3, true>), grid, dim3(256), 0, st, g, a, q_pop, b); break;
+      case 4: hipLaunchKernelGGL((k_screen_range_bits<4, true>), grid, dim3(256), 0, st, g, a, q_pop, b); break;
+      case 5: hipLaunchKernelGGL((k_screen_range_bits<5, true>), grid, dim3(256), 0, st, g, a, q_pop, b); break;
+      default: hipLaunchKernelGGL((k_screen_range_bits<6, true>), grid, dim3(256), 0, st, g, a, q_pop, b); break;
+    }
+    return hipGetLastError();
+  }
   switch (g.metric) {
     case 3: hipLaunchKernelGGL(k_screen_range_bits<3>, grid, dim3(256), 0, st, g, a, q_pop, b); break;
     case 4: hipLaunchKernelGGL(k_screen_range_bits<4>, grid, dim3(256), 0, st, g, a, q_pop, b); break;
@@ -812,6 +969,7 @@ hipError_t hnyk_screen_range_l1(const GraphDev &g, const ExactArgs &a, const Scr
   if (g.metric != 2 || g.mclass != MC_L1 || !g.n16) return hipErrorInvalidValue; // Manhattan only: no silent other path
   if (a.slab_n > HNY_EXACT_SLAB || a.slab_base % HNY_EXACT_CHUNK) return hipErrorInvalidValue; // the bitmaps' stride
   const dim3 grid((a.nq + HNY_SCREEN_QT - 1) / HNY_SCREEN_QT, (a.slab_n + HNY_EXACT_CHUNK - 1) / HNY_EXACT_CHUNK);
-  hipLaunchKernelGGL(k_screen_range_l1, grid, dim3(256), 0, st, g, a, s, b);
+  if (a.tile_mask) hipLaunchKernelGGL(k_screen_range_l1_masked, grid, dim3(256), 0, st, g, a, s, b);
+  else hipLaunchKernelGGL(k_screen_range_l1, grid, dim3(256), 0, st, g, a, s, b);
   return hipGetLastError();
 }

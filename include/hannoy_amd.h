@@ -611,6 +611,34 @@ int hny_builder_exact_knn_bitsets_f32(hny_builder *b, const hny_query_opts *opts
                                       uint64_t n_queries, const float *queries, size_t qstride,
                                       uint32_t *out_ids, float *out_dists, uint32_t *out_counts);
 
+/* ---- exact k-NN with a filter per query by votes.  Opt-in: nothing else calls them.
+ *
+ * Definition: each call returns, byte for byte (ids, distance bits, counts, row lengths min(k, |C_f|), HNY_NNS_NONE,
+ * did_cancel), what its namesake without _voted returns on the same builder, queries, filters and options, and refuses
+ * what it refuses, with the same codes and messages, at the same point.
+ *
+ * Method: the namesake's plan (the filters as bitsets over slots, sparse filters gathered, the others and the queries
+ * without a filter in one dense sub-batch in filter order), with hny_builder_exact_knn_voted's scan for the dense
+ * sub-batch.  Every member carries its own mask, its own k = min(k, |C_f|) and its own pilot sample; the scan reads,
+ * per tile of 64 queries, only the rows that some member of the tile wants.  Routed to the namesake, whole calls: the
+ * builders that hny_builder_exact_knn_voted routes (strict mode; Manhattan and the bit metrics until their switch).
+ * hny_builder_exact_vote_stats counts the routed and the gathered queries as n_routed, hny_builder_exact_vote_times
+ * and hny_builder_exact_rows_read report this call as they report the calls they are named after. */
+int hny_builder_exact_knn_filtered_voted(hny_builder *b, const hny_query_opts *opts, const hny_query_filters *filters,
+                                         uint64_t n_queries, const void *qvectors, size_t qstride, const void *qheaders,
+                                         const uint32_t *query_items, uint32_t *out_ids, float *out_dists,
+                                         uint32_t *out_counts);
+int hny_builder_exact_knn_filtered_voted_f32(hny_builder *b, const hny_query_opts *opts,
+                                             const hny_query_filters *filters, uint64_t n_queries, const float *queries,
+                                             size_t qstride, uint32_t *out_ids, float *out_dists, uint32_t *out_counts);
+int hny_builder_exact_knn_bitsets_voted(hny_builder *b, const hny_query_opts *opts, const hny_query_bitsets *filters,
+                                        uint64_t n_queries, const void *qvectors, size_t qstride, const void *qheaders,
+                                        const uint32_t *query_items, uint32_t *out_ids, float *out_dists,
+                                        uint32_t *out_counts);
+int hny_builder_exact_knn_bitsets_voted_f32(hny_builder *b, const hny_query_opts *opts,
+                                            const hny_query_bitsets *filters, uint64_t n_queries, const float *queries,
+                                            size_t qstride, uint32_t *out_ids, float *out_dists, uint32_t *out_counts);
+
 /* ---- two-stage search: the hits of a coarse index rescored on a fine one.  The use of the two
  * builders that hny_builder_create_changed_distance leaves resident: the walk runs over the binary-quantized codes,
  * its n_rescore best hits are ranked again on the f32 rows of the source builder, k of them are returned.
